@@ -23,6 +23,11 @@ for the roofline come from an untimed probe step in which every launch runs alon
 
 Metric = the reference's own: closest-hit rays / second (path.rs:87,
 app/window.rs:911-916); shadow rays are traced but not counted.
+
+A plain run sets up, warms up, times the K steps and prints the record.  `--full` adds what takes
+work of its own: the CPU baseline, the roofline's solo probe step and its counters, and the check
+that the films of the slots in flight agree.  `--dump-outputs DIR` writes the film the last timed
+step left, as float32 .npy, so that two builds can be compared on identical inputs.
 """
 import argparse
 import ctypes
@@ -152,6 +157,22 @@ def cpu_baseline(sd, cam, sampler, integ, tiles, n_sample_tiles):
                 sample=f"first {len(sample)} spiral-order 16x16 tiles of the same frame at full spp ({rays} rays in {dt:.1f} s; oracle BVH build {build_s:.1f} s excluded)"), counters
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_film(out_dir, film, res):
+    """The film as a caller of the render receives it (float32, rows x columns x RGB).  Above DUMP_LIMIT_BYTES, a fixed
+    sample of its pixels (seed 0, sorted pixel indices): the same pixels in every run with the same arguments."""
+    os.makedirs(out_dir, exist_ok=True)
+    img = film.detach().cpu().numpy().astype(np.float32, copy=False).reshape(res[1], res[0], 3)
+    if img.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(out_dir, "film.npy"), img)
+        return
+    n_px = res[0] * res[1]
+    keep = np.sort(np.random.default_rng(0).choice(n_px, size=(DUMP_LIMIT_BYTES // 2) // 12, replace=False))
+    np.save(os.path.join(out_dir, "film_sample.npy"), img.reshape(n_px, 3)[keep])
+
+
 def main():
     # Exactly ONE line on stdout, the JSON record: libraries (RCCL's version banner, gloo) print to fd 1 behind Python's
     # back, so fd 1 points at stderr until the record is written.
@@ -169,7 +190,13 @@ def main():
                          "directive (a .ply keeps the workload's), sampler / depth / integrator from --workload.  "
                          "tools/write_scene_files.py writes BASELINE's configs as such files")
     ap.add_argument("--batch-paths", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: the CPU baseline (unless --no-cpu-baseline), "
+                         "the roofline (an untimed solo probe step, stored PMC counters) and the agreement of the slots' films")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the film of the last timed step to DIR/film.npy (float32, rows x columns x RGB); "
+                         "a film above 64 MB is written as DIR/film_sample.npy, a fixed seeded sample of its pixels")
     ap.add_argument("--async-steps", action="store_true", help="(default since round 2 for frames of one batch) enqueue the timed steps without host synchronisation")
     ap.add_argument("--solo-steps", action="store_true",
                     help="N=1 diagnostic: every step like the roofline's probe step - side stream off, one work set, one host synchronisation per step - "
@@ -196,6 +223,8 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args, real_stdout)  # does not return; nothing GPU-related has been imported yet
     rank = int(os.environ.get("RANK", "0"))
@@ -413,7 +442,7 @@ def main():
     # alone on the GPU and its HIP-event duration is the kernel's own (in the default mode {any-hit, accumulate}(b)
     # share the GPU with closest-hit(b+1) and their events include the time they wait for each other).
     solo = None
-    if world == 1 and not use_dist:
+    if args.full and world == 1 and not use_dist:
         ctx.set_option("overlap_shadow", 0)
         ctx.set_option("streams", 1)  # a frame of several batches: no second work set beside the first either
         solo = step(slot=0)  # `ctx` is slot 0's context
@@ -437,6 +466,7 @@ def main():
         shadow_launches += st.shadow_launches
     sync()
     elapsed = time.perf_counter() - t0
+    last_film = slots[(step_no[0] - 1) % in_flight]["film"]  # what the last timed step wrote (rank 0)
     if use_dist:
         elapsed = cpu_all_reduce([elapsed], dist.ReduceOp.MAX)[0]
         rays_all, shadow_all = (int(v) for v in cpu_all_reduce([rays, shadow], dist.ReduceOp.SUM))
@@ -471,18 +501,21 @@ def main():
         c2.close()
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_film(args.dump_outputs, last_film, wl["res"])
         film_mean = film.view(-1, 3).mean(dim=0).tolist()
-        for sl in slots[1:]:
-            if not torch.equal(sl["film"], film):
-                raise SystemExit("[bench] films of the slots in flight differ")
+        if args.full:
+            for sl in slots[1:]:
+                if not torch.equal(sl["film"], film):
+                    raise SystemExit("[bench] films of the slots in flight differ")
         value = rays_all / elapsed * 1e-6
         cpu = None
         counters = None
         stored = os.path.join(ROOT, "profiles", f"oracle_counters_{args.workload}.json")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cpu, counters = cpu_baseline(sd, cam, sampler, integ, tiles, args.cpu_sample_tiles)
             log(f"[bench] cpu_baseline {cpu['value']:.3f} Mray/s on {cpu['cores']} threads; oracle counters {counters}")
-        elif os.path.exists(stored):
+        elif args.full and os.path.exists(stored):
             counters = json.load(open(stored))["counters"]
         roofline = None
         if solo is not None and solo.seconds_trace > 0 and solo.trace_launches:

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -41,7 +42,7 @@ def test_self_launched_ranks_render_the_same_film():
     """Two self-launched ranks rehearsed on ONE GPU (both use cuda:0, the slabs travel through gloo: RCCL refuses two
     ranks on a device): the N > 1 control flow — shard, render, gather, scatter, max over ranks — end to end; the film
     equals the single-rank one, the record says n_gpus 2 and stdout holds nothing but the record."""
-    one = _run(["--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--workload", "smoke"])
+    one = _run(["--full", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--workload", "smoke"])
     assert one.returncode == 0, one.stderr[-2000:]
     two = _run(["--gpus", "2", "--rehearse-on-one-gpu", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--workload", "smoke"])
     assert two.returncode == 0, two.stderr[-2000:]
@@ -62,9 +63,9 @@ def test_scene_file_workload(tmp_path):
     import scene_files as sf
 
     p = sf.write_cfg2_ply(str(tmp_path / "bunny_class.ply"))
-    gen = _run(["--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--workload", "cfg2"])
+    gen = _run(["--full", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--workload", "cfg2"])
     assert gen.returncode == 0, gen.stderr[-2000:]
-    got = _run(["--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--workload", "cfg2", "--scene-file", p])
+    got = _run(["--full", "--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--workload", "cfg2", "--scene-file", p])
     assert got.returncode == 0, got.stderr[-2000:]
     a, b = json.loads(gen.stdout), json.loads(got.stdout)
     assert b["config"]["triangles"] == a["config"]["triangles"] == 69312
@@ -74,3 +75,23 @@ def test_scene_file_workload(tmp_path):
     if a["roofline"] is not None:  # the generated workload quotes a tracked PMC set and names its content
         assert a["roofline"]["traffic_source"].startswith("profiles/") and len(a["roofline"]["traffic_source_git_blob"]) == 40
         assert a["roofline"]["binding"]["unit"].startswith("vector-memory")
+
+
+@pytest.mark.gpu
+def test_dump_outputs_writes_the_last_steps_film(tmp_path):
+    """`--dump-outputs DIR`: the film of the last timed step as float32 rows x columns x RGB — the film the record's
+    film_mean_rgb summarises — and the same film, bit for bit, from a second run with the same arguments.  A plain run
+    (no --full) reports the headline only: no CPU baseline, no roofline."""
+    films = []
+    for k in range(2):
+        d = tmp_path / f"out{k}"
+        r = _run(["--steps", "2", "--warmup", "1", "--workload", "smoke", "--dump-outputs", str(d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        rec = json.loads(r.stdout)
+        assert rec["steps"] == 2 and rec["ms_per_step"] > 0
+        assert rec["cpu_baseline"] is None and rec["roofline"] is None
+        film = np.load(d / "film.npy")
+        assert film.dtype == np.float32 and film.shape == (180, 320, 3)
+        assert np.allclose(film.reshape(-1, 3).astype(np.float64).mean(axis=0), rec["extra"]["film_mean_rgb"], rtol=1e-5, atol=0)
+        films.append(film)
+    assert np.array_equal(films[0].view(np.uint32), films[1].view(np.uint32))

@@ -7,6 +7,8 @@ textures/image_texture.rs.  The tests pin (1) decoded texels == source pixels / 
 (or / 65535) exactly, (2) product decoder == checker decoder bit for bit over colour
 types, bit depths, filters, interlacing and deflate block types, (3) device texture
 lookup + shading == the oracle's on a textured scene."""
+import os
+
 import numpy as np
 import pytest
 
@@ -79,25 +81,27 @@ def test_png_large_random_exercises_dynamic_huffman(tmp_path, oi):
     assert got.tobytes() == (src.astype(np.float32) / np.float32(255)).tobytes()
 
 
+# PNG files written by other encoders, kept as data under tests/golden/png/ (tiling_58 is a CC0 texture from sharetextures.com):
+# the reference's own 16-bit RGBA normal map as it ships, and crops of its 16-bit grey roughness map and of its 8-bit RGBA
+# screenshot, re-encoded by Pillow (adaptive row filters, zlib's dynamic Huffman blocks) to keep the files small.
+PNG_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "png")
 REFERENCE_PNGS = [
-    "/root/reference/res/tiling_58-1K/tiling_58_normal-1K.png",  # 1024 x 1024, 16-bit RGBA
-    "/root/reference/res/tiling_58-1K/tiling_58_roughness-1K.png",  # 1024 x 1024, 16-bit grey
-    "/root/reference/screenshot.png",  # 1922 x 1119, 8-bit RGBA
+    "tiling_58_normal-1K.png",  # 1024 x 1024, 16-bit RGBA
+    "tiling_58_roughness-crop.png",  # 128 x 128, 16-bit grey
+    "screenshot-crop.png",  # 384 x 256, 8-bit RGBA
 ]
 
 
-@pytest.mark.parametrize("path", REFERENCE_PNGS)
-def test_png_files_the_reference_ships(oi, path):
-    """The PNG files in the reference's own tree (its texture assets and its screenshot: files written by other encoders, 1.7 MB
-    of dynamic-Huffman deflate in the largest) through the product decoder and through the independent zlib / numpy one: same
-    texels, bit for bit, the first row also against a by-hand unfiltering of zlib's output; the 16-bit grey map is refused by both
-    with the reference's own message (a Spectrum texture has no Luma arm).  Read where they lie (build container only)."""
-    import os
+@pytest.mark.parametrize("name", REFERENCE_PNGS)
+def test_png_files_the_reference_ships(oi, name):
+    """PNG files of the reference's tree (its texture assets and its screenshot: files written by other encoders) through the
+    product decoder and through the independent zlib / numpy one: same texels, bit for bit, the first row also against a
+    by-hand unfiltering of zlib's output; the 16-bit grey map is refused by both with the reference's own message (a Spectrum
+    texture has no Luma arm)."""
     import struct
     import zlib
 
-    if not os.path.exists(path):
-        pytest.skip("reference tree not present on this machine")
+    path = os.path.join(PNG_DIR, name)
     raw = open(path, "rb").read()
     w, h, depth, ctype = struct.unpack(">IIBB", raw[16:26])
     if ctype in (0, 4):  # Luma / LumaA: `load_image_spectrum_f32` has no arm for them (image_texture.rs:114-141)

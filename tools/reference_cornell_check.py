@@ -1,15 +1,18 @@
 #!/usr/bin/env python3
-"""cfg1's scene constants against the reference's text (build container only: reads /root/reference as text).
+"""cfg1's scene constants against the reference's text.
 
-`yuki_amd/scenes.py::cornell()` claims "scene/mod.rs:154-530, constants verbatim".  This script parses that function's
+`yuki_amd/scenes.py::cornell()` claims "scene/mod.rs:154-530, constants verbatim".  `parse_reference` reads that function's
 source — the `const` block (evaluated in f32 like rustc's constant folding), every `Mesh::new(transform, indices, points,
-normals, uvs)`, the wall materials' order, the material constructors' literals, the sphere, the light, the camera and the
-BVH parameters — and compares them with what `cornell()` returns: vertices bit for bit after the 4x4 of
+normals, uvs)`, the wall materials' order, the material constructors' arguments, the sphere, the light, the camera and the
+BVH parameters — and reduces it to numbers and names (tests/golden/reference_facts.json, written by
+tools/reference_facts.py).  `check` compares those with what `cornell()` returns: vertices bit for bit after the 4x4 of
 scene/mod.rs:177-185 applied through the oracle's KAT-pinned `Transform * Point3`.
 
-    python tools/reference_cornell_check.py            # prints a summary, exit code 1 on any difference
+    python tools/reference_cornell_check.py [REFERENCE_DIR]   # a summary, exit code 1 on any difference
+                                                             # (without REFERENCE_DIR: the stored facts)
 """
 import ctypes as C
+import json
 import os
 import re
 import sys
@@ -20,7 +23,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from yuki_amd import abi, scenes  # noqa: E402
 
-REF = "/root/reference/yuki/src/scene/mod.rs"
+SCENE_RS = "yuki/src/scene/mod.rs"  # relative to the reference's checkout
+FACTS = os.path.join(ROOT, "tests", "golden", "reference_facts.json")
 F = np.float32
 
 
@@ -102,8 +106,40 @@ def split_args(body):
     return out
 
 
-def parse_reference():
-    src = open(REF).read()
+def _spectrum(text, env):
+    """A `Spectrum` expression of the scene code (`ones()` / `zeros()` / `new(a, b, c)`, then `* x` / `/ x`) in f32."""
+    text = text.strip()
+    m = re.match(r"Spectrum::(ones|zeros)\(\)|Spectrum::new\(([^)]*)\)", text)
+    if m.group(1):
+        v = [F(1.0 if m.group(1) == "ones" else 0.0)] * 3
+    else:
+        v = [f32_eval(c, env) for c in split_args(m.group(2))]
+    rest = text[m.end():].strip()
+    for op, operand in re.findall(r"([*/])\s*([^*/]+)", rest):
+        x = f32_eval(operand.strip(), env)
+        v = [F(c * x) if op == "*" else F(c / x) for c in v]
+    return [float(c) for c in v]
+
+
+def _argument(text, env):
+    """One constructor argument as data: a constant texture's value, a literal, a flag; None for anything else."""
+    text = text.strip()
+    m = re.fullmatch(r"Arc::new\(ConstantTexture::new\((.*)\)\)", text, re.S)
+    if m:
+        text = m.group(1).strip()
+    if text in ("true", "false"):
+        return text == "true"
+    if text.startswith("Spectrum::"):
+        return _spectrum(text, env)
+    try:
+        return float(f32_eval(text, env))
+    except (AssertionError, KeyError, IndexError, ValueError, TypeError):
+        return None
+
+
+def parse_reference(ref_dir):
+    """scene/mod.rs `cornell()` as numbers and names (JSON-serialisable)."""
+    src = open(os.path.join(ref_dir, SCENE_RS)).read()
     a = src.index("pub fn cornell()")
     b = balanced(src, src.index("{", a), "{", "}")
     fn = re.sub(r"//[^\n]*", "", src[a:b])
@@ -116,24 +152,43 @@ def parse_reference():
         args = split_args(fn[m.end():end - 1])
         assert len(args) == 5 and args[0] == "&handedness_swap_and_into_meters", args[0]
         idx = [int(v) for v in re.findall(r"\d+", args[1][args[1].index("["):])]
-        pts = [[f32_eval(c, env) for c in split_args(p)] for p in re.findall(r"Point3::new\(([^)]*)\)", args[2])]
+        pts = [[float(f32_eval(c, env)) for c in split_args(p)] for p in re.findall(r"Point3::new\(([^)]*)\)", args[2])]
         assert args[3] == "Vec::new()"
-        uvs = [[f32_eval(c, env) for c in split_args(p)] for p in re.findall(r"Point2::new\(([^)]*)\)", args[4])] or None
-        meshes.append((idx, pts, uvs))
+        uvs = [[float(f32_eval(c, env)) for c in split_args(p)] for p in re.findall(r"Point2::new\(([^)]*)\)", args[4])] or None
+        meshes.append(dict(indices=idx, points=pts, uvs=uvs))
     mats = re.search(r"let materials = \[(.*?)\];", fn, re.S).group(1)
     wall_materials = [re.sub(r"Arc::clone\(&(\w+)\)", r"\1", t) for t in split_args(mats)]
-    lets = {}
+    materials = {}
     for m in re.finditer(r"let (\w+) = Arc::new\((\w+)::new\(", fn):
+        if m.group(2) not in ("Matte", "Metal", "Glass"):
+            continue
         end = balanced(fn, m.end() - 1)
-        lets[m.group(1)] = (m.group(2), fn[m.end():end - 1])
+        materials[m.group(1)] = dict(kind=m.group(2), args=[_argument(t, env) for t in split_args(fn[m.end():end - 1])])
     sphere = re.search(r"Sphere::new\(\s*&translation\(Vec3::new\(([^)]*)\)\),\s*([\d._]+),\s*(\w+)", fn)
     bvh = re.search(r"BoundingVolumeHierarchy::new\(shapes, (\d+), SplitMethod::(\w+)\)", fn)
-    cam = {k: [F(float(c)) for c in split_args(v)] for k, v in re.findall(r"let cam_(pos|target) = Point3::new\(([^)]*)\)", fn)}
+    cam = {k: [float(F(float(c))) for c in split_args(v)] for k, v in re.findall(r"let cam_(pos|target) = Point3::new\(([^)]*)\)", fn)}
     fov = re.search(r"let cam_fov = FoV::(\w)\(([\d.]+)\)", fn)
-    light_block = fn[fn.index("let light = {"):fn.index("let mut meshes")]
-    return dict(env=env, meshes=meshes, wall_materials=wall_materials, lets=lets,
-                sphere=([F(float(c)) for c in split_args(sphere.group(1))], F(float(sphere.group(2).replace("_", ""))), sphere.group(3)),
-                bvh=(int(bvh.group(1)), bvh.group(2)), cam=cam, fov=(fov.group(1), F(float(fov.group(2)))), light_block=light_block, fn=fn)
+    # the light: size = Vec2(LIGHT_WH, LIGHT_WH) / 1000; radiance = 2 / (area * PI); translation(Vec3(X_CENTER, HOLE_TOP, -Z_CENTER) / 1000)
+    lb = fn[fn.index("let light = {"):fn.index("let mut meshes")]
+    for needle in ("Vec2::new(LIGHT_WH, LIGHT_WH) / 1000.0", "let area = size.x * size.y", "let power = 2.0", "power / (area * std::f32::consts::PI)",
+                   "translation(Vec3::new(X_CENTER, HOLE_TOP, -Z_CENTER) / 1000.0)", "Spectrum::ones() * radiance"):
+        assert needle in lb, f"the light block changed ({needle}): extend this parser"
+    size = F(env["LIGHT_WH"] / F(1000.0))
+    radiance = F(F(2.0) / F(F(size * size) * F(np.pi)))
+    light = dict(size=[float(size)] * 2, radiance=[float(F(F(1.0) * radiance))] * 3,
+                 translation=[float(F(env["X_CENTER"] / F(1000.0))), float(F(env["HOLE_TOP"] / F(1000.0))), float(F(F(-env["Z_CENTER"]) / F(1000.0)))])
+    bg = re.search(r"background: (Spectrum::\w+\([^)]*\))", fn).group(1)
+    return dict(constants={k: float(v) for k, v in env.items()}, meshes=meshes, wall_materials=wall_materials, materials=materials,
+                sphere=dict(center=[float(F(float(c))) for c in split_args(sphere.group(1))], radius=float(F(float(sphere.group(2).replace("_", "")))),
+                            material=sphere.group(3)),
+                bvh=dict(max_shapes_in_node=int(bvh.group(1)), split=bvh.group(2)), camera=dict(position=cam["pos"], target=cam["target"]),
+                fov=dict(axis=fov.group(1), degrees=float(F(float(fov.group(2))))), light=light, background=_spectrum(bg, env))
+
+
+def stored_facts():
+    """The cornell() facts tools/reference_facts.py stored under tests/golden/."""
+    with open(FACTS) as f:
+        return json.load(f)["cornell"]
 
 
 def oracle_transform(points):
@@ -149,12 +204,9 @@ def oracle_transform(points):
     return out
 
 
-def literals(text):
-    return [F(float(v.replace("_", ""))) for v in re.findall(r"(?<![\w.])\d[\d_]*\.[\d_]+", text)]
-
-
-def check():
-    ref = parse_reference()
+def check(ref=None):
+    """Differences between the reference's cornell() (`ref`: parse_reference's facts; default: the stored ones) and scenes.cornell()."""
+    ref = stored_facts() if ref is None else ref
     sd = scenes.cornell()
     problems = []
 
@@ -165,7 +217,8 @@ def check():
     # geometry: 1 light mesh + 12 walls + the tall box, in shapes order
     expect(len(ref["meshes"]) == 14 == len(sd.meshes), f"mesh count {len(ref['meshes'])} vs {len(sd.meshes)}")
     base = tri = 0
-    for k, (idx, pts, uvs) in enumerate(ref["meshes"]):
+    for k, mesh in enumerate(ref["meshes"]):
+        idx, pts, uvs = mesh["indices"], mesh["points"], mesh["uvs"]
         n = len(pts)
         want = oracle_transform(pts)
         got = sd.points[base:base + n]
@@ -182,55 +235,50 @@ def check():
     order = ["blackbody"] + ref["wall_materials"] + ["glass"]
     names = {"white": 0, "image": 1, "red": 2, "green": 3, "blackbody": 4, "copper": 5, "glass": 6}
     t = 0
-    for k, (idx, _, _) in enumerate(ref["meshes"]):
-        nt = len(idx) // 3
+    for k, mesh in enumerate(ref["meshes"]):
+        nt = len(mesh["indices"]) // 3
         expect(set(sd.tri_material[t:t + nt].tolist()) == {names[order[k]]}, f"mesh {k}: material {order[k]}")
         expect(set(sd.tri_area_light[t:t + nt].tolist()) == ({0} if k == 0 else {-1}), f"mesh {k}: area light")
         t += nt
-    # material constructors
-    lets = ref["lets"]
+    # material constructors: Matte(albedo, sigma), Metal(eta, k, roughness, remap), Glass(reflectance, transmittance, eta)
+    mats = ref["materials"]
     m = sd.materials
-    c180 = F(F(1.0) * F(180.0)) / F(255.0)
-    expect(lets["white"][0] == "Matte" and "Spectrum::ones() * 180.0 / 255.0" in lets["white"][1] and tuple(m[0]["a"]) == (c180,) * 3 and m[0]["c"] == 0.0, "white")
-    expect(lets["red"][0] == "Matte" and "Spectrum::new(180.0, 0.0, 0.0) / 255.0" in lets["red"][1] and tuple(F(v) for v in m[2]["a"]) == (F(180) / F(255), F(0), F(0)), "red")
-    expect(lets["green"][0] == "Matte" and "Spectrum::new(0.0, 180.0, 0.0) / 255.0" in lets["green"][1] and tuple(F(v) for v in m[3]["a"]) == (F(0), F(180) / F(255), F(0)), "green")
-    expect(lets["blackbody"][0] == "Matte" and "Spectrum::zeros()" in lets["blackbody"][1] and tuple(m[4]["a"]) == (0, 0, 0), "blackbody")
-    cu = literals(lets["copper"][1])
-    expect(lets["copper"][0] == "Metal" and [F(v) for v in (*m[5]["a"], *m[5]["b"], m[5]["c"])] == cu and m[5]["remap"] is True and lets["copper"][1].rstrip().rstrip(",").endswith("true"), f"copper {cu}")
-    gl = literals(lets["glass"][1])
-    expect(lets["glass"][0] == "Glass" and gl == [F(m[6]["c"])] and lets["glass"][1].count("Spectrum::ones()") == 2 and tuple(m[6]["a"]) == (1, 1, 1) == tuple(m[6]["b"]), "glass")
+    f3 = lambda v: tuple(F(c) for c in v)
+    for name in ("white", "red", "green", "blackbody"):
+        k = names[name]
+        albedo, sigma = mats[name]["args"]
+        expect(mats[name]["kind"] == "Matte" and f3(m[k]["a"]) == f3(albedo) and F(m[k]["c"]) == F(sigma), name)
+    expect(mats["image"]["kind"] == "Matte" and F(m[1]["c"]) == F(mats["image"]["args"][1]), "image")
+    eta, kk, rough, remap = mats["copper"]["args"]
+    expect(mats["copper"]["kind"] == "Metal" and f3(m[5]["a"]) == f3(eta) and f3(m[5]["b"]) == f3(kk) and F(m[5]["c"]) == F(rough)
+           and m[5]["remap"] is remap is True, f"copper {mats['copper']['args']}")
+    refl, trans, ior = mats["glass"]["args"]
+    expect(mats["glass"]["kind"] == "Glass" and f3(m[6]["a"]) == f3(refl) and f3(m[6]["b"]) == f3(trans) and F(m[6]["c"]) == F(ior), "glass")
     for k, kind in ((0, abi.MAT_MATTE), (1, abi.MAT_MATTE), (2, abi.MAT_MATTE), (3, abi.MAT_MATTE), (4, abi.MAT_MATTE), (5, abi.MAT_METAL), (6, abi.MAT_GLASS)):
         expect(m[k]["kind"] == kind, f"material {k} kind")
     # sphere, BVH, camera
-    c, r, mat = ref["sphere"]
+    sph = ref["sphere"]
     s = sd.spheres[0]
-    expect(mat == "copper" and s["material"] == 5 and F(s["radius"]) == r and np.array_equal(np.asarray(s["o2w"], dtype=F)[:3, 3], np.asarray(c, dtype=F)), "sphere")
-    expect(ref["bvh"] == (sd.max_shapes_in_node, "Middle") and sd.split_method == abi.SPLIT_MIDDLE, "BVH parameters")
-    expect([F(v) for v in sd.camera["position"]] == ref["cam"]["pos"] and [F(v) for v in sd.camera["target"]] == ref["cam"]["target"], "camera position / target")
-    expect(ref["fov"] == ("X", F(sd.camera["fov_degrees"])) and sd.camera["fov_axis"] == abi.FOV_X and tuple(sd.camera["up"]) == (0, 1, 0), "camera fov / up")
-    # light: size = Vec2(LIGHT_WH, LIGHT_WH) / 1000; radiance = 2 / (area * PI); translation(Vec3(X_CENTER, HOLE_TOP, -Z_CENTER) / 1000)
-    lb, env = ref["light_block"], ref["env"]
-    for needle in ("Vec2::new(LIGHT_WH, LIGHT_WH) / 1000.0", "let area = size.x * size.y", "let power = 2.0", "power / (area * std::f32::consts::PI)",
-                   "translation(Vec3::new(X_CENTER, HOLE_TOP, -Z_CENTER) / 1000.0)", "Spectrum::ones() * radiance"):
-        expect(needle in lb, f"light block changed: {needle}")
-    size = F(env["LIGHT_WH"] / F(1000.0))
-    radiance = F(F(2.0) / F(F(size * size) * F(np.pi)))
-    L = sd.lights[0]
-    expect(L["kind"] == "rect" and tuple(F(v) for v in L["size"]) == (size, size) and tuple(F(v) for v in L["L"]) == (F(F(1.0) * radiance),) * 3, "light size / radiance")
-    want_t = [F(env["X_CENTER"] / F(1000.0)), F(env["HOLE_TOP"] / F(1000.0)), F(F(-env["Z_CENTER"]) / F(1000.0))]
-    expect(np.array_equal(np.asarray(L["l2w"], dtype=F)[:3, 3], np.asarray(want_t, dtype=F)), "light translation")
-    expect("background: Spectrum::zeros()" in ref["fn"] and tuple(sd.background) == (0, 0, 0), "background")
+    expect(sph["material"] == "copper" and s["material"] == 5 and F(s["radius"]) == F(sph["radius"])
+           and np.array_equal(np.asarray(s["o2w"], dtype=F)[:3, 3], np.asarray(sph["center"], dtype=F)), "sphere")
+    expect((ref["bvh"]["max_shapes_in_node"], ref["bvh"]["split"]) == (sd.max_shapes_in_node, "Middle") and sd.split_method == abi.SPLIT_MIDDLE, "BVH parameters")
+    expect(f3(sd.camera["position"]) == f3(ref["camera"]["position"]) and f3(sd.camera["target"]) == f3(ref["camera"]["target"]), "camera position / target")
+    expect((ref["fov"]["axis"], F(ref["fov"]["degrees"])) == ("X", F(sd.camera["fov_degrees"])) and sd.camera["fov_axis"] == abi.FOV_X
+           and tuple(sd.camera["up"]) == (0, 1, 0), "camera fov / up")
+    L, lt = sd.lights[0], ref["light"]
+    expect(L["kind"] == "rect" and f3(L["size"]) == f3(lt["size"]) and f3(L["L"]) == f3(lt["radiance"]), "light size / radiance")
+    expect(np.array_equal(np.asarray(L["l2w"], dtype=F)[:3, 3], np.asarray(lt["translation"], dtype=F)), "light translation")
+    expect(f3(ref["background"]) == (0, 0, 0) and f3(sd.background) == f3(ref["background"]), "background")
     return ref, problems
 
 
 def main():
-    if not os.path.exists(REF):
-        print("no /root/reference here: nothing to compare with")
-        return 0
-    ref, problems = check()
-    n_pts = sum(len(p) for _, p, _ in ref["meshes"])
-    print(f"scene/mod.rs cornell(): {len(ref['env'])} constants, {len(ref['meshes'])} meshes, {n_pts} vertices, {sum(len(i) for i, _, _ in ref['meshes']) // 3} triangles, "
-          f"{len(ref['lets'])} Arc::new constructors parsed; differences from yuki_amd.scenes.cornell(): {len(problems)}")
+    ref = parse_reference(sys.argv[1]) if len(sys.argv) > 1 else None
+    ref, problems = check(ref)
+    n_pts = sum(len(m["points"]) for m in ref["meshes"])
+    print(f"scene/mod.rs cornell(): {len(ref['constants'])} constants, {len(ref['meshes'])} meshes, {n_pts} vertices, "
+          f"{sum(len(m['indices']) for m in ref['meshes']) // 3} triangles, {len(ref['materials'])} Arc::new constructors; "
+          f"differences from yuki_amd.scenes.cornell(): {len(problems)}")
     for p in problems:
         print("  DIFFERENT:", p)
     return 1 if problems else 0
