@@ -295,7 +295,7 @@ yk_status yk_render_tiles_device(yk_context* ctx, const yk_scene* scene, const y
  * FilmTile.sample (tile_samples[t], u16 like film.rs:52, which must be below the sampler's
  * samples per pixel as in render_manager.rs:135-143 — YK_ERR_INVALID_ARGUMENT otherwise); the
  * raw radiance is stored (divided by 1).  Fold the result into the film with yk_film_accumulate_tiles[_device]; the displayed
- * image is film / samples (tonemap.rs:240-241). */
+ * image is film / samples (tonemap.rs:240-241), which yk_tone_map computes. */
 yk_status yk_render_tiles_accumulating(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler,
                                        const yk_integrator_desc* integrator, const yk_tile* tiles, const uint16_t* tile_samples, size_t n_tiles,
                                        float* out_rgb, yk_render_stats* stats, yk_cancel_fn cancel, void* user);
@@ -355,6 +355,49 @@ yk_status yk_film_accumulate_tile_list_passes_device(yk_context* ctx, const yk_t
  * pixels: row-major RGB, row 0 = top. */
 yk_status yk_write_exr(const char* path, uint32_t width, uint32_t height, const float* rgb);
 yk_status yk_write_pfm(const char* path, uint32_t width, uint32_t height, const float* rgb);
+
+/* ---- tone map (app/renderpasses/tonemap.rs; what `yuki --out` writes, app/headless.rs:62-84) ----------
+ * The film the reference writes to its EXR is, unless the settings say Raw, the tone-mapped one (ToneMapType,
+ * default Filmic { exposure: 1.0 }, tonemap.rs:40-51).  The shader arithmetic is fixed to one evaluation order
+ * (binary32, every operation separate and left to right, no FMA, correctly rounded divisions); the rules are
+ * stated next to the tonemap.rs lines they come from in yuki_amd/csrc/yk_tonemap.h.  In short:
+ *   Filmic (FILMIC_FS_CODE :318-385): divide by (float)samples[flat] when > 0, where flat = (y / tile_dim) *
+ *     (res_x / tile_dim, FLOOR) + x / tile_dim indexes a table laid out over the CEIL grid (FilmTile.index) — the
+ *     reference's own mismatch when res_x % tile_dim != 0, reproduced; then * exposure, ACESInputMat, RRTAndODTFit,
+ *     ACESOutputMat, saturate(x) = x > 0 ? (x < 1 ? x : 1) : 0 (NaN -> 0).
+ *   Heatmap (HEATMAP_FS_CODE :387-422): maps texel[channel] for Green / Blue and LUMINANCE for Red and Luminance
+ *     (the shader's `channel > 0 && channel < 3`), while yk_film_min_max reads red for Red (find_min_max :447-472) —
+ *     reproduced.  Bounds not given: find_min_max over the film first (headless.rs:135-145).
+ *   Raw: the film unchanged (:163). */
+typedef enum yk_tone_map_kind { YK_TONE_MAP_RAW = 0, YK_TONE_MAP_FILMIC = 1, YK_TONE_MAP_HEATMAP = 2 } yk_tone_map_kind;
+typedef enum yk_heatmap_channel { YK_HEATMAP_RED = 0, YK_HEATMAP_GREEN = 1, YK_HEATMAP_BLUE = 2, YK_HEATMAP_LUMINANCE = 3 } yk_heatmap_channel;
+typedef struct yk_tone_map_desc {
+    uint32_t kind;       /* yk_tone_map_kind */
+    float exposure;      /* Filmic */
+    uint32_t channel;    /* Heatmap: yk_heatmap_channel */
+    uint32_t has_bounds; /* Heatmap: 0 = find_min_max over the film */
+    float bounds[2];     /* Heatmap (min, max) when has_bounds */
+} yk_tone_map_desc;
+/* Host buffers, row-major RGB (h, w, 3).  ctx NULL = the host instance on the CPU (like yk_scene_create), else on
+ * ctx's device (synchronous).  tile_dim: Film::tile_dim() (film.rs:143-150) — the width of the first tile of the
+ * film's spiral queue, 16 without tiles (tonemap.rs:238).  samples: Film.samples, ceil(res_x/tile_dim) *
+ * ceil(res_y/tile_dim) u32 in FilmTile.index order (film.rs:299-331), or NULL for a film that does not accumulate
+ * (no division).  used_bounds: the Heatmap bounds applied, may be NULL.  out_rgb may equal film_rgb.
+ * YK_ERR_INVALID_ARGUMENT: unknown kind or channel, tile_dim 0, a zero resolution, NULL film or out. */
+yk_status yk_tone_map(yk_context* ctx, const yk_tone_map_desc* desc, const float* film_rgb, uint16_t res_x, uint16_t res_y,
+                      uint16_t tile_dim, const uint32_t* samples, float* out_rgb, float* used_bounds);
+/* The same on device buffers (e.g. yk_multi_film_device_ptr, a film updated with yk_film_update_tile_list_device),
+ * enqueued on `stream` (NULL = the context's) without waiting for the device: a Heatmap without bounds finds them on
+ * the device and the map reads them there.  `samples` is a HOST table, copied before the call returns (through the
+ * context's pinned staging: a call that brings a table waits for the previous call's upload of one, if that has not
+ * run yet).  d_out_rgb may equal d_film_rgb.  The tone map's work buffers belong to the context: calls on one context
+ * are ordered only when they share a stream.  Allocates on first use only. */
+yk_status yk_tone_map_device(yk_context* ctx, const yk_tone_map_desc* desc, const void* d_film_rgb, uint16_t res_x, uint16_t res_y,
+                             uint16_t tile_dim, const uint32_t* samples, void* d_out_rgb, void* stream);
+/* find_min_max (tonemap.rs:447-472) over a host film: the fold from (FLT_MAX, -FLT_MAX) that skips NaN pixels; red,
+ * green, blue or luminance ((0.2126*r + 0.7152*g) + 0.0722*b).  ctx NULL = CPU.  The sign of a zero bound is not
+ * specified. */
+yk_status yk_film_min_max(yk_context* ctx, const float* film_rgb, uint16_t res_x, uint16_t res_y, uint32_t channel, float out_min_max[2]);
 
 /* Exactly the trait method: one tile, returns the ray count through *out_rays. */
 yk_status yk_render_tile(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler,

@@ -36,6 +36,13 @@ pub const YK_INTEGRATOR_PATH: u32 = 1;
 pub const YK_INTEGRATOR_BVH_INTERSECTIONS: u32 = 2;
 pub const YK_INTEGRATOR_GEOMETRY_NORMALS: u32 = 3;
 pub const YK_INTEGRATOR_SHADING_NORMALS: u32 = 4;
+pub const YK_TONE_MAP_RAW: u32 = 0;
+pub const YK_TONE_MAP_FILMIC: u32 = 1;
+pub const YK_TONE_MAP_HEATMAP: u32 = 2;
+pub const YK_HEATMAP_RED: u32 = 0;
+pub const YK_HEATMAP_GREEN: u32 = 1;
+pub const YK_HEATMAP_BLUE: u32 = 2;
+pub const YK_HEATMAP_LUMINANCE: u32 = 3;
 
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -155,6 +162,17 @@ pub struct yk_integrator_desc {
     pub indirect_clamp: f32,
 }
 
+/// ToneMapType (app/renderpasses/tonemap.rs:40-44) with its params
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct yk_tone_map_desc {
+    pub kind: u32,
+    pub exposure: f32,
+    pub channel: u32,
+    pub has_bounds: u32,
+    pub bounds: [f32; 2],
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct yk_tile {
@@ -269,6 +287,9 @@ extern "C" {
     pub fn yk_film_accumulate_tile_list_passes_device(ctx: *mut yk_context, list: *const yk_tile_list, d_passes_rgb: *const c_void, n_passes: u32, res_x: u16, res_y: u16, d_film_rgb: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_write_exr(path: *const c_char, width: u32, height: u32, rgb: *const f32) -> yk_status;
     pub fn yk_write_pfm(path: *const c_char, width: u32, height: u32, rgb: *const f32) -> yk_status;
+    pub fn yk_tone_map(ctx: *mut yk_context, desc: *const yk_tone_map_desc, film_rgb: *const f32, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, out_rgb: *mut f32, used_bounds: *mut f32) -> yk_status;
+    pub fn yk_tone_map_device(ctx: *mut yk_context, desc: *const yk_tone_map_desc, d_film_rgb: *const c_void, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, d_out_rgb: *mut c_void, stream: *mut c_void) -> yk_status;
+    pub fn yk_film_min_max(ctx: *mut yk_context, film_rgb: *const f32, res_x: u16, res_y: u16, channel: u32, out_min_max: *mut f32) -> yk_status;
     pub fn yk_render_tile(ctx: *mut yk_context, scene: *const yk_scene, camera: *const yk_camera, sampler: *const yk_sampler_desc, integrator: *const yk_integrator_desc, tile: *const yk_tile, tile_pixels: *mut f32, out_rays: *mut u64) -> yk_status;
     pub fn yk_film_update_tiles_device(ctx: *mut yk_context, tiles: *const yk_tile, n_tiles: usize, d_tile_rgb: *const c_void, res_x: u16, res_y: u16, d_film_rgb: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_li(ctx: *mut yk_context, scene: *const yk_scene, sampler: *const yk_sampler_desc, integrator: *const yk_integrator_desc, n: usize, ray_o: *const f32, ray_d: *const f32, pixel_xy: *const u16, sample_index: *const u32, dimension: u32, out_li: *mut f32, out_ray_counts: *mut u32) -> yk_status;

@@ -126,6 +126,9 @@ SYMBOLS = {
     "yk_film_accumulate_tile_list_passes_device": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint16, C.c_uint16, vp, vp]),
     "yk_write_exr": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, vp]),
     "yk_write_pfm": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, vp]),
+    "yk_tone_map": (C.c_int, [vp, C.POINTER(abi.ToneMapDesc), vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp]),
+    "yk_tone_map_device": (C.c_int, [vp, C.POINTER(abi.ToneMapDesc), vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp]),
+    "yk_film_min_max": (C.c_int, [vp, vp, C.c_uint16, C.c_uint16, C.c_uint32, vp]),
     # several GPUs
     "yk_multi_create": (C.c_int, [C.POINTER(C.c_int), C.c_uint32, C.POINTER(vp)]),
     "yk_multi_create_ex": (C.c_int, [C.POINTER(C.c_int), C.c_uint32, C.c_uint32, C.POINTER(vp)]),

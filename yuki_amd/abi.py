@@ -108,6 +108,12 @@ class IntegratorDesc(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("max_depth", C.c_uint32), ("has_clamp", C.c_uint32), ("indirect_clamp", C.c_float)]
 
 
+class ToneMapDesc(C.Structure):
+    """yk_tone_map_desc: ToneMapType (app/renderpasses/tonemap.rs:40-44) with its params."""
+
+    _fields_ = [("kind", C.c_uint32), ("exposure", C.c_float), ("channel", C.c_uint32), ("has_bounds", C.c_uint32), ("bounds", C.c_float * 2)]
+
+
 class Tile(C.Structure):
     _fields_ = [("x0", C.c_uint16), ("y0", C.c_uint16), ("x1", C.c_uint16), ("y1", C.c_uint16)]
 
@@ -146,6 +152,8 @@ LIGHT_POINT, LIGHT_SPOT, LIGHT_DISTANT, LIGHT_RECT = 0, 1, 2, 3
 SAMPLER_UNIFORM, SAMPLER_STRATIFIED = 0, 1
 INTEGRATOR_WHITTED, INTEGRATOR_PATH, INTEGRATOR_BVH_INTERSECTIONS, INTEGRATOR_GEOMETRY_NORMALS, INTEGRATOR_SHADING_NORMALS = 0, 1, 2, 3, 4
 FOV_X, FOV_Y = 0, 1
+TONE_MAP_RAW, TONE_MAP_FILMIC, TONE_MAP_HEATMAP = 0, 1, 2
+HEATMAP_RED, HEATMAP_GREEN, HEATMAP_BLUE, HEATMAP_LUMINANCE = 0, 1, 2, 3
 
 
 def ptr(a, ty):

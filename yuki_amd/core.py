@@ -103,6 +103,123 @@ def write_pfm(path, film):
     check(lib().yk_write_pfm(str(path).encode(), film.shape[1], film.shape[0], _p(film)))
 
 
+# --------------------------------------------------------------------------- tone map
+@dataclass
+class FilmicParams:
+    """app/renderpasses/tonemap.rs:12-22."""
+
+    exposure: float = 1.0
+
+
+class HeatmapChannel:
+    """tonemap.rs:53-59."""
+
+    Red, Green, Blue, Luminance = abi.HEATMAP_RED, abi.HEATMAP_GREEN, abi.HEATMAP_BLUE, abi.HEATMAP_LUMINANCE
+
+
+@dataclass
+class HeatmapParams:
+    """tonemap.rs:24-38: bounds None = find_min_max over the film first (app/headless.rs:135-145)."""
+
+    bounds: tuple = None
+    channel: int = HeatmapChannel.Red
+
+
+class ToneMapType:
+    """tonemap.rs:40-51; the semantics are stated in yuki_amd/csrc/yk_tonemap.h."""
+
+    Raw = abi.ToneMapDesc(abi.TONE_MAP_RAW, 1.0, 0, 0, (C.c_float * 2)(0.0, 0.0))
+
+    @staticmethod
+    def Filmic(params: FilmicParams = None):
+        params = params or FilmicParams()
+        return abi.ToneMapDesc(abi.TONE_MAP_FILMIC, params.exposure, 0, 0, (C.c_float * 2)(0.0, 0.0))
+
+    @staticmethod
+    def Heatmap(params: HeatmapParams = None):
+        params = params or HeatmapParams()
+        b = (0.0, 0.0) if params.bounds is None else params.bounds
+        return abi.ToneMapDesc(abi.TONE_MAP_HEATMAP, 1.0, int(params.channel), 0 if params.bounds is None else 1, (C.c_float * 2)(*[float(v) for v in b]))
+
+    @staticmethod
+    def default():
+        return ToneMapType.Filmic(FilmicParams())
+
+
+def film_tile_dim(settings: FilmSettings):
+    """Film::tile_dim() (film.rs:143-150) as the tone map reads it (tonemap.rs:238): the width of the first tile of the
+    spiral queue (film.rs:173-181), 16 without tiles.  It differs from settings.tile_dim only for a film narrower than a tile."""
+    t = film_tiles(settings)
+    return 16 if len(t) == 0 else int(t[0]["x1"]) - int(t[0]["x0"])
+
+
+def _table_len(res, tile_dim):
+    return (-(-int(res[0]) // tile_dim)) * (-(-int(res[1]) // tile_dim))
+
+
+def film_samples(settings: FilmSettings, tiles, counts):
+    """Film.samples (film.rs:74, 260-272) from per-tile counts.  accumulate_tiles counts by POSITION in `tiles` (spiral
+    order); the table is in FilmTile.index order (generate_tiles, film.rs:299-331): (y0 / td) * ceil(W / td) + x0 / td."""
+    tiles = np.ascontiguousarray(tiles, dtype=abi.TILE_DTYPE)
+    counts = np.asarray(counts, dtype=np.uint32)
+    if len(counts) != len(tiles):
+        raise ValueError("one count per tile")
+    td = int(settings.tile_dim)
+    cols = -(-int(settings.res[0]) // td)
+    table = np.zeros(_table_len(settings.res, td), dtype=np.uint32)
+    idx = (tiles["y0"].astype(np.int64) // td) * cols + tiles["x0"].astype(np.int64) // td
+    np.add.at(table, idx, counts)
+    return table
+
+
+def _tone_map_args(res, tone_map, tile_dim, samples):
+    if not isinstance(tone_map, abi.ToneMapDesc):
+        raise TypeError("tone_map is a ToneMapType")
+    if samples is not None:
+        samples = np.ascontiguousarray(samples, dtype=np.uint32)
+        if int(tile_dim) > 0 and samples.size != _table_len(res, int(tile_dim)):
+            raise ValueError(f"samples has {samples.size} entries, the film's tile grid {_table_len(res, int(tile_dim))}")
+    return samples
+
+
+def tone_map(film, tone_map, tile_dim, samples=None, ctx=None, used_bounds=None):
+    """ToneMapFilm::draw (tonemap.rs:143-213) plus the bounds search of headless.rs:135-145: (h, w, 3) float32 in and out.
+    ctx None = the host instance; `used_bounds` (a float32[2] array) receives the Heatmap bounds applied."""
+    return _apply_tone_map(film, tone_map, tile_dim, samples, ctx, used_bounds)
+
+
+def _apply_tone_map(film, desc, tile_dim, samples, ctx, used_bounds):
+    film = np.ascontiguousarray(film, dtype=np.float32)
+    h, w = film.shape[0], film.shape[1]
+    samples = _tone_map_args((w, h), desc, tile_dim, samples)
+    out = np.empty_like(film)
+    c = ctx.h if ctx else None
+    check(lib().yk_tone_map(c, C.byref(desc), _p(film), w, h, int(tile_dim), _p(samples), _p(out), _p(used_bounds)), c)
+    return out
+
+
+def find_min_max(film, channel, ctx=None):
+    """tonemap.rs:447-472: (min, max) of a channel (or luminance) over the film, NaN pixels skipped."""
+    film = np.ascontiguousarray(film, dtype=np.float32)
+    out = np.zeros(2, dtype=np.float32)
+    c = ctx.h if ctx else None
+    check(lib().yk_film_min_max(c, _p(film), film.shape[1], film.shape[0], int(channel), _p(out)), c)
+    return float(out[0]), float(out[1])
+
+
+def write_output(path, film, tone_map=None, settings=None, samples=None, ctx=None):
+    """The Finished branch of app/headless.rs:62-84: Raw writes the film as it is, anything else writes the tone-mapped
+    film (a Heatmap without bounds finds them first).  tone_map None = ToneMapType.default(); settings None = a film of the
+    array's size with the default tile_dim."""
+    film = np.ascontiguousarray(film, dtype=np.float32)
+    tone_map = ToneMapType.default() if tone_map is None else tone_map
+    settings = settings or FilmSettings(res=(film.shape[1], film.shape[0]))
+    if tone_map.kind == abi.TONE_MAP_RAW:
+        write_exr(path, film)
+        return
+    write_exr(path, _apply_tone_map(film, tone_map, film_tile_dim(settings), samples, ctx, None))
+
+
 class TileList:
     """A tile list prepared once on the device (yk_tile_list): the GPU worker's tile queue."""
 
@@ -234,6 +351,12 @@ class Context:
     def interrupt(self):
         """yk_context_interrupt: stop what the context has enqueued (any thread)."""
         check(lib().yk_context_interrupt(self.h))
+
+    def tone_map_device(self, d_film_ptr, res, tile_dim, tone_map, samples, d_out_ptr, stream=None):
+        """yk_tone_map_device: device film -> device out, enqueued on `stream` (default: the context's) without waiting;
+        `samples` is a host table (or None), copied before the call returns."""
+        samples = _tone_map_args(res, tone_map, tile_dim, samples)
+        check(lib().yk_tone_map_device(self.h, C.byref(tone_map), C.c_void_p(d_film_ptr), res[0], res[1], int(tile_dim), _p(samples), C.c_void_p(d_out_ptr), C.c_void_p(stream) if stream else None), self.h)
 
     @property
     def stream_handle(self):

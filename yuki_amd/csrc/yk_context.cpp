@@ -115,6 +115,11 @@ void yk_context_destroy(yk_context* ctx) {
     DevBuf* all[] = {&ctx->sample_buf, &ctx->pixel_xy, &ctx->pixel_aux, &ctx->tiles, &ctx->tile_off, &ctx->counters, &ctx->stats4, &ctx->hit4};
     for (DevBuf* b : all) b->release();
     for (DevBuf& b : ctx->scratch) b.release();
+    ctx->tonemap.partials.release();
+    ctx->tonemap.bounds.release();
+    ctx->tonemap.samples.release();
+    if (ctx->tonemap.staging) (void)hipHostFree(ctx->tonemap.staging);
+    if (ctx->tonemap.staged) (void)hipEventDestroy(ctx->tonemap.staged);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
     if (ctx->cancel_stream) {
         (void)hipStreamSynchronize(ctx->cancel_stream);
@@ -275,6 +280,7 @@ size_t yk_sizeof(int what) {
         case 10: return sizeof(yk_mesh_desc);
         case 11: return sizeof(yk_render_stats);
         case 12: return sizeof(yk_scene_info);
+        case 13: return sizeof(yk_tone_map_desc);
         default: return 0;
     }
 }

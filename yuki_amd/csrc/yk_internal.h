@@ -76,6 +76,13 @@ struct yk_context {
     hipStream_t cancel_stream = nullptr;  // carries that copy past the kernels in flight (made after the context's first interruption)
     bool want_cancel_stream = false;
     std::atomic<bool> cancel_raised{false};
+    // the tone map's buffers (yk_tonemap.hip), grown on first use
+    struct ToneMapState {
+        DevBuf partials, bounds, samples;  // per-block (min, max) pairs, the bounds slot, the sample table on the device
+        uint32_t* staging = nullptr;       // pinned host copy the sample table is uploaded from
+        size_t staging_words = 0;
+        hipEvent_t staged = nullptr;       // the latest upload out of `staging`
+    } tonemap;
     // every entry point that touches the context's buffers or streams holds this: calls on one
     // context from several host threads (the reference's tile workers) are serialised
     std::recursive_mutex mu;
