@@ -242,7 +242,11 @@ yk_status yk_context_interrupt(yk_context* ctx);
  * lanes by material kind), "top_nodes" (tree-top nodes the traversal kernels keep
  * in LDS, 0..1023; the kernels hold at most what they were built for) and "wide_bvh" (0: binary nodes only | 1: traverse the 4-wide collapse of the
  * BVH | 2, default: keep both, jobs of up to 6 M paths use the 4-wide one) — the last two apply
- * to scenes created afterwards. */
+ * to scenes created afterwards.  Test hook: "trace_stage_kernel" (0, default: yk_trace_closest /
+ * yk_trace_any run the generic kernels as documented | 1: the generic kernels in the render loop's
+ * flavour | 2: the wave-packet kernels; modes 1 and 2 report shape ids and verdicts only, and
+ * refuse out_t, out_bary, counters, a closest-hit t_max and, in mode 2, a tree deeper than 64
+ * with YK_ERR_INVALID_ARGUMENT). */
 yk_status yk_context_set_option(yk_context* ctx, const char* key, int64_t value);
 
 /* ---- host-side restatements (no GPU needed) -------------------------------- */

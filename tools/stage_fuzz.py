@@ -3,7 +3,9 @@ for degenerate rays — directions with exact zero components (0 * inf = NaN lan
 test), origins on box faces and on vertices, rays along triangle edges and through vertices,
 small and large directions, finite t_max at exact hit distances — on the random scenes of
 parity_fuzz.py.  Hit shape, t bits and (binary layout) the three counters must equal the oracle's.
-    stage_fuzz.py [first_seed] [count]"""
+kernel = 1 / 2 runs the stages through the render-loop flavour of the generic kernels / the wave-packet
+kernels (context option trace_stage_kernel): shape ids and any-hit verdicts only, no closest-hit t_max.
+    stage_fuzz.py [first_seed] [count] [kernel]"""
 import sys
 sys.path.insert(0, ".")
 sys.path.insert(0, "tools")
@@ -46,32 +48,61 @@ def rays_for(sd, r, n=1500):
     return o, d
 
 
-def check_seed(oracle, seed):
-    ctx = pf.variant_context(seed)
+def closest_ids(sc, o, d):
+    """yk_trace_closest with shape ids only (no t, barycentrics or counters): the call every trace_stage_kernel accepts."""
+    import ctypes as C
+
+    o = np.ascontiguousarray(o, dtype=F)
+    d = np.ascontiguousarray(d, dtype=F)
+    out = np.zeros(o.shape[0], dtype=np.int32)
+    vp = C.c_void_p
+    yk.check(yk.lib().yk_trace_closest(sc.ctx.h, sc.h, o.shape[0], vp(o.ctypes.data), vp(d.ctypes.data), None, vp(out.ctypes.data), None, None, None, None, None), sc.ctx.h)
+    return out
+
+
+_kernel_ctx = {}
+
+
+def kernel_context(seed, kernel):
+    """The seed's option variant (parity_fuzz.VARIANTS) with trace_stage_kernel = kernel."""
+    if kernel == 0:
+        return pf.variant_context(seed)
+    k = (seed % len(pf.VARIANTS), kernel)
+    if k not in _kernel_ctx:
+        _kernel_ctx[k] = yk.Context(0, trace_stage_kernel=kernel, **pf.VARIANTS[k[0]])
+    return _kernel_ctx[k]
+
+
+def check_seed(oracle, seed, kernel=0):
+    ctx = kernel_context(seed, kernel)
     sd = pf.random_scene(seed)
     r = np.random.default_rng(seed ^ 0xABCDEF)
     o, d = rays_for(sd, r)
     sc = yk.Scene(ctx, sd)
     osc = oracle.OracleScene(sd)
     bad = []
-    binary = pf.VARIANTS[seed % len(pf.VARIANTS)].get("wide_bvh", 2) == 0
-    g = sc.intersect(o, d, counters=True)
     w = osc.intersect(o, d)
     hit = w["shape"] >= 0
-    if not np.array_equal(g["shape"], w["shape"]):
-        bad.append(("shape", int((g["shape"] != w["shape"]).sum())))
-    if not np.array_equal(g["t"][hit].view(np.uint32), w["t"][hit].view(np.uint32)):
-        bad.append(("t", int((g["t"][hit].view(np.uint32) != w["t"][hit].view(np.uint32)).sum())))
-    for k in ("node_tests", "node_hits", "shape_tests"):  # the counting kernel always walks the binary nodes
-        if not np.array_equal(g[k], w[k]):
-            bad.append((k, int((g[k] != w[k]).sum())))
+    if kernel == 0:
+        g = sc.intersect(o, d, counters=True)
+        if not np.array_equal(g["t"][hit].view(np.uint32), w["t"][hit].view(np.uint32)):
+            bad.append(("t", int((g["t"][hit].view(np.uint32) != w["t"][hit].view(np.uint32)).sum())))
+        for k in ("node_tests", "node_hits", "shape_tests"):  # the counting kernel always walks the binary nodes
+            if not np.array_equal(g[k], w[k]):
+                bad.append((k, int((g[k] != w[k]).sum())))
+        shape = g["shape"]
+    else:
+        shape = closest_ids(sc, o, d)
+    if not np.array_equal(shape, w["shape"]):
+        bad.append(("shape", int((shape != w["shape"]).sum())))
     # finite t_max: exactly the hit distance, one ulp below / above it, and random
     tm = np.where(hit, w["t"], F(1.0)).astype(F)
     for name, tmax in (("t_max = t", tm), ("t_max = t-", np.nextafter(tm, F(0))), ("t_max = t+", np.nextafter(tm, F(np.inf))), ("random t_max", r.uniform(0, 4, len(o)).astype(F))):
-        g2 = sc.intersect(o, d, t_max=tmax)
-        w2 = osc.intersect(o, d, tmax)
-        if not np.array_equal(g2["shape"], w2["shape"]):
-            bad.append((name + " shape", int((g2["shape"] != w2["shape"]).sum())))
+        if kernel == 0:  # the other kernels take no closest-hit t_max
+            g2 = sc.intersect(o, d, t_max=tmax)
+            w2 = osc.intersect(o, d, tmax)
+            if not np.array_equal(g2["shape"], w2["shape"]):
+                bad.append((name + " shape", int((g2["shape"] != w2["shape"]).sum())))
         al = r.integers(-1, max(1, len(sd.lights)), len(o)).astype(np.int32)
         ga = sc.any_intersect(o, d, tmax, al)
         wa = osc.any_intersect(o, d, tmax, al)
@@ -86,9 +117,10 @@ if __name__ == "__main__":
 
     first = int(sys.argv[1]) if len(sys.argv) > 1 else 0
     count = int(sys.argv[2]) if len(sys.argv) > 2 else 200
+    kernel = int(sys.argv[3]) if len(sys.argv) > 3 else 0
     failures = 0
     for seed in range(first, first + count):
-        bad = check_seed(oracle, seed)
+        bad = check_seed(oracle, seed, kernel)
         if bad:
             failures += 1
             print(f"seed {seed} (variant {pf.VARIANTS[seed % len(pf.VARIANTS)]}): MISMATCH {bad}", flush=True)

@@ -167,6 +167,9 @@ yk_status yk_context_set_option(yk_context* ctx, const char* key, int64_t value)
     } else if (k == "wide_bvh") {
         if (value < 0 || value > 2) return YK_ERR_INVALID_ARGUMENT;
         ctx->wide_bvh = value;
+    } else if (k == "trace_stage_kernel") {
+        if (value < 0 || value > 2) return YK_ERR_INVALID_ARGUMENT;
+        ctx->trace_stage_kernel = value;
     } else if (k == "time_kernels") {
         ctx->time_kernels = value;
     } else {

@@ -51,6 +51,7 @@ struct yk_context {
     int64_t overlap_shadow = 1;  // run {trace_any, accumulate}(b) on a side stream beside trace_closest(b+1)
     int64_t wide_bvh = 2;   // scenes created afterwards: 0 binary nodes only, 1 traverse the 4-wide collapse, 2 keep both and pick per job
     int64_t top_nodes = YK_TOP_MAX; // interior nodes (capped by what the kernels were built for) of the first tree levels the traversal kernels keep in LDS
+    int64_t trace_stage_kernel = 0;  // which kernels yk_trace_closest / yk_trace_any launch (yk_stages.cpp): 0 generic, API flavour | 1 generic, render-loop flavour | 2 wave packets
     int64_t sample_buf_cap = (int64_t)64 << 30;
     int64_t time_kernels = 1;
     int64_t streams = 2;  // batches in flight (1 or 2): the second stream's launches fill the first one's tails
@@ -97,6 +98,7 @@ struct yk_scene {
     uint32_t n_triangles = 0, n_spheres = 0, n_lights = 0, n_delta_lights = 0;
     bool wide_auto = false;  // both node layouts on the device: the 4-wide one is used for jobs below YK_WIDE_MAX_PATHS
     yk_scene_info info;
+    std::vector<uint8_t> shape_kind;  // source shape -> device BSDF kind of its material (the kind bits of a render-loop hit word)
     // device
     DevBuf nodes, nodes4, top_nodes, top_nodes_any, tris, prim_shade, prim_attr, indices, points, normals, uvs, tri_mesh, tri_material, tri_area_light, mesh_flags, materials, lights, spheres, texels, tex_info;
     DevScene dev;

@@ -99,6 +99,7 @@ struct SceneImage {
     std::vector<uint4> prim_shade, tex_info;
     std::vector<uint32_t> mesh_flags, tri_mesh;
     std::vector<int32_t> tri_al;
+    std::vector<uint8_t> shape_kind;  // source shape -> BSDF kind (yk_scene::shape_kind)
     std::vector<Material> mats;
     std::vector<DevSphere> spheres;
     std::vector<DevLight> lights;
@@ -341,6 +342,9 @@ yk_status yk_build_scene_image(yk_context* ctx, const yk_scene_desc* d, std::sha
         prim_shade.assign(np, make_uint4(0u, 0u, 0u, 0u));
         std::vector<uint32_t> mat_kind(std::max<uint32_t>(d->n_materials, 1), 0u);  // device BSDF kind (MK_*) per material
         for (uint32_t m = 0; m < d->n_materials; ++m) mat_kind[m] = make_material(d->materials[m]).kind & 7u;
+        s->shape_kind.resize(np);
+        for (uint32_t i = 0; i < d->n_triangles; ++i) s->shape_kind[i] = (uint8_t)mat_kind[d->tri_material[i]];
+        for (uint32_t k = 0; k < d->n_spheres; ++k) s->shape_kind[(size_t)d->n_triangles + k] = (uint8_t)mat_kind[d->spheres[k].material];
         std::vector<uint8_t> last(np, 0);
         for (const yk_bvh_node& n : nodes)
             if (n.is_leaf) last[(size_t)n.a + n.count - 1] = 1;
@@ -460,6 +464,7 @@ yk_status yk_upload_scene_image(yk_context* ctx, const std::shared_ptr<SceneImag
     s->n_lights = img->n_lights;
     s->n_delta_lights = img->n_delta_lights;
     s->info = img->info;
+    s->shape_kind = img->shape_kind;
     if (ctx) {
         if (!img->has_device_records) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "scene image was built without device records");
         const yk_scene_desc* d = img->d;

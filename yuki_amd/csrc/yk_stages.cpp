@@ -13,6 +13,36 @@
 
 #include "yk_internal.h"
 
+// "trace_stage_kernel" (yk_context_set_option): the kernels the two traversal stages launch.
+//   0  k_trace_closest_pt / k_trace_any_pt, API flavour (source shape, t, barycentrics; vis = 0 / 1)
+//   1  the same kernels as the render loop launches them: the closest-hit kernel reports the leaf-order hit word
+//      (slot | BSDF kind bits), the any-hit kernel scatters its verdicts through a slot_of map (vis[slot] = 2)
+//   2  the wave-packet kernels of yk_packet.hip, on the render's grid; the caller's ray order decides the packets
+// A mode never falls back to another kernel: an argument it cannot honour is refused.
+static yk_status check_stage_kernel(yk_context* ctx, const yk_scene* scene, bool closest, const float* t_max, bool wants_extras) {
+    const int64_t mode = ctx->trace_stage_kernel;
+    if (mode == 0) return YK_OK;
+    if (wants_extras) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "trace_stage_kernel " + std::to_string(mode) + " reports shape ids only (no t, barycentrics or counters)");
+    if (closest && t_max)
+        return fail(ctx, YK_ERR_INVALID_ARGUMENT, mode == 1 ? "trace_stage_kernel 1: the render-loop closest-hit kernel takes no t_max"
+                                                            : "trace_stage_kernel 2: the packet closest-hit kernel starts at t_max = inf");
+    if (mode == 2 && scene->bvh->depth > 64) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "trace_stage_kernel 2: the packet kernels need a tree depth <= 64");
+    return YK_OK;
+}
+
+// the grid run_bounces gives the packet kernels (yk_render.cpp)
+static unsigned packet_grid(const yk_context* ctx) { return (unsigned)ctx->n_cu * packet_blocks_per_cu(); }
+
+// slot_of of the stage's any-hit modes 1 and 2: reversed, so that a verdict written to its ray's own index shows
+static yk_status upload_reversed_slots(yk_context* ctx, size_t n, hipStream_t st) {
+    std::vector<uint32_t> slots(n);
+    for (size_t k = 0; k < n; ++k) slots[k] = (uint32_t)(n - 1 - k);
+    HIP_TRY(ctx, ctx->scratch[3].ensure(n * 4));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[3].p, slots.data(), n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));  // `slots` goes out of scope
+    return YK_OK;
+}
+
 extern "C" {
 
 // ------------------------------------------------------------------ per-stage entry points
@@ -24,12 +54,14 @@ yk_status yk_trace_closest(yk_context* ctx, const yk_scene* scene, size_t n, con
     if (!scene || !ray_o || !ray_d || !out_shape || n == 0) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null argument");
     if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "scene was not created on this context's device");
     if (n > 0xFFFFFF00ull) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "too many rays");
+    const bool want_stats = out_node_tests || out_node_hits || out_shape_tests;
+    yk_status wb = check_stage_kernel(ctx, scene, true, t_max, out_t || out_bary || want_stats);
+    if (wb != YK_OK) return wb;
+    const int64_t mode = ctx->trace_stage_kernel;
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
-    yk_status wb = ensure_work_buffers(ctx, ctx->ws[0], n, scene->n_lights, scene->n_delta_lights);
-    if (wb != YK_OK) return wb;
+    if ((wb = ensure_work_buffers(ctx, ctx->ws[0], n, scene->n_lights, scene->n_delta_lights)) != YK_OK) return wb;
     if ((wb = ensure_spill(ctx, ctx->ws[0])) != YK_OK) return wb;
-    const bool want_stats = out_node_tests || out_node_hits || out_shape_tests;
     HIP_TRY(ctx, ctx->scratch[4].ensure(n * 12));
     HIP_TRY(ctx, ctx->scratch[5].ensure(n * 12));
     HIP_TRY(ctx, ctx->scratch[6].ensure(n * 4));
@@ -45,9 +77,15 @@ yk_status yk_trace_closest(yk_context* ctx, const yk_scene* scene, size_t n, con
     unsigned nn = (unsigned)n;
     HIP_TRY(ctx, hipMemcpyAsync(ctrl, &nn, 4, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
-    launch_trace_closest(st, trace_grid(ctx), dev_scene_for(scene, n), pb.rayO, pb.rayD, t_max ? ctx->scratch[6].as<float>() : nullptr, ctrl, ctrl + YK_CTRL_HEADS,
-                         ctx->ws[0].hit.as<int>(), ctx->hit4.as<float4>(), want_stats ? ctx->stats4.as<uint4>() : nullptr, ctx->ws[0].spill.as<uint2>(),
-                         trace_grid(ctx) * trace_block_size(), ctrl, nullptr);
+    if (mode == 0)
+        launch_trace_closest(st, trace_grid(ctx), dev_scene_for(scene, n), pb.rayO, pb.rayD, t_max ? ctx->scratch[6].as<float>() : nullptr, ctrl, ctrl + YK_CTRL_HEADS,
+                             ctx->ws[0].hit.as<int>(), ctx->hit4.as<float4>(), want_stats ? ctx->stats4.as<uint4>() : nullptr, ctx->ws[0].spill.as<uint2>(),
+                             trace_grid(ctx) * trace_block_size(), ctrl, nullptr);
+    else if (mode == 1)  // no t_max, no hit_out: the render loop's flavour (launch_trace_closest picks it from these two)
+        launch_trace_closest(st, trace_grid(ctx), dev_scene_for(scene, n), pb.rayO, pb.rayD, nullptr, ctrl, ctrl + YK_CTRL_HEADS, ctx->ws[0].hit.as<int>(), nullptr,
+                             nullptr, ctx->ws[0].spill.as<uint2>(), trace_grid(ctx) * trace_block_size(), ctrl, nullptr);
+    else
+        launch_trace_closest_packet(st, packet_grid(ctx), dev_scene_for(scene, n), pb.rayO, pb.rayD, ctrl, ctrl + YK_CTRL_HEADS, ctx->ws[0].hit.as<int>(), nullptr);
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipMemcpyAsync(out_shape, ctx->ws[0].hit.p, n * 4, hipMemcpyDeviceToHost, st));
     std::vector<float> h4;
@@ -63,6 +101,21 @@ yk_status yk_trace_closest(yk_context* ctx, const yk_scene* scene, size_t n, con
     unsigned host_ctrl[4];
     HIP_TRY(ctx, hipMemcpyAsync(host_ctrl, ctrl, 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (mode != 0) {  // hit word -> source shape (the scene's leaf-order table); its kind bits must be the shape's material's
+        const std::vector<uint32_t>& order = scene->bvh->shape_order;
+        for (size_t i = 0; i < n; ++i) {
+            const int32_t h = out_shape[i];
+            if (h == -1) continue;
+            const uint32_t prim = (uint32_t)h & YK_HIT_PRIM_MASK, kind = ((uint32_t)h >> YK_HIT_KIND_SHIFT) & 7u;
+            if (h < 0 || prim >= order.size())
+                return fail(ctx, YK_ERR_DEVICE, "trace_stage_kernel " + std::to_string(mode) + ": ray " + std::to_string(i) + " got hit word " + std::to_string(h));
+            const uint32_t src = order[prim];
+            if (kind != scene->shape_kind[src])
+                return fail(ctx, YK_ERR_DEVICE, "trace_stage_kernel " + std::to_string(mode) + ": ray " + std::to_string(i) + " hit shape " + std::to_string(src) +
+                                                     " with kind bits " + std::to_string(kind) + ", its material's kind is " + std::to_string(scene->shape_kind[src]));
+            out_shape[i] = (int32_t)src;
+        }
+    }
     for (size_t i = 0; i < n; ++i) {
         if (out_t) out_t[i] = out_shape[i] >= 0 ? h4[4 * i] : __builtin_inff();
         if (out_bary) {
@@ -79,17 +132,21 @@ yk_status yk_trace_closest(yk_context* ctx, const yk_scene* scene, size_t n, con
 } YK_CATCH(ctx)
 
 yk_status yk_trace_any(yk_context* ctx, const yk_scene* scene, size_t n, const float* ray_o, const float* ray_d, const float* t_max,
-                       const int32_t* area_light, uint8_t* out_hit) {
+                       const int32_t* area_light, uint8_t* out_hit) try {
     if (!ctx) return YK_ERR_INVALID_ARGUMENT;
     YK_LOCK(ctx);
     if (!scene || !ray_o || !ray_d || !t_max || !out_hit || n == 0) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null argument");
     if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "scene was not created on this context's device");
     if (n > 0xFFFFFF00ull) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "too many rays");
+    yk_status wb = check_stage_kernel(ctx, scene, false, t_max, false);
+    if (wb != YK_OK) return wb;
+    const int64_t mode = ctx->trace_stage_kernel;
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
-    yk_status wb = ensure_work_buffers(ctx, ctx->ws[0], n, scene->n_lights, scene->n_delta_lights);
-    if (wb != YK_OK) return wb;
+    if ((wb = ensure_work_buffers(ctx, ctx->ws[0], n, scene->n_lights, scene->n_delta_lights)) != YK_OK) return wb;
     if ((wb = ensure_spill(ctx, ctx->ws[0])) != YK_OK) return wb;
+    if (mode != 0 && (wb = upload_reversed_slots(ctx, n, st)) != YK_OK) return wb;
+    const unsigned* slot_of = mode != 0 ? ctx->scratch[3].as<unsigned>() : nullptr;
     HIP_TRY(ctx, ctx->scratch[4].ensure(n * 12));
     HIP_TRY(ctx, ctx->scratch[5].ensure(n * 12));
     HIP_TRY(ctx, ctx->scratch[6].ensure(n * 4));
@@ -104,17 +161,29 @@ yk_status yk_trace_any(yk_context* ctx, const yk_scene* scene, size_t n, const f
     HIP_TRY(ctx, hipMemsetAsync(ctrl, 0, YK_CTRL_WORDS * 4, st));
     unsigned nn = (unsigned)n;
     HIP_TRY(ctx, hipMemcpyAsync(ctrl, &nn, 4, hipMemcpyHostToDevice, st));
+    if (slot_of) HIP_TRY(ctx, hipMemsetAsync(ctx->ws[0].vis.p, 0, n, st));  // as k_shade leaves it: the kernels only mark occluded slots
     HIP_TRY(ctx, hipStreamSynchronize(st));
-    launch_trace_any(st, trace_grid(ctx), dev_scene_for(scene, n), ctx->ws[0].shO.as<float4>(), ctx->ws[0].shD.as<float4>(), nullptr, ctrl, ctrl + YK_CTRL_HEADS,
-                     ctx->ws[0].vis.as<unsigned char>(), ctx->ws[0].spill.as<uint2>(), trace_grid(ctx) * trace_block_size(), ctrl, nullptr);
+    if (mode == 2)
+        launch_trace_any_packet(st, packet_grid(ctx), dev_scene_for(scene, n), ctx->ws[0].shO.as<float4>(), ctx->ws[0].shD.as<float4>(), slot_of, ctrl,
+                                ctrl + YK_CTRL_HEADS, ctx->ws[0].vis.as<unsigned char>(), nullptr);
+    else
+        launch_trace_any(st, trace_grid(ctx), dev_scene_for(scene, n), ctx->ws[0].shO.as<float4>(), ctx->ws[0].shD.as<float4>(), slot_of, ctrl, ctrl + YK_CTRL_HEADS,
+                         ctx->ws[0].vis.as<unsigned char>(), ctx->ws[0].spill.as<uint2>(), trace_grid(ctx) * trace_block_size(), ctrl, nullptr);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipMemcpyAsync(out_hit, ctx->ws[0].vis.p, n, hipMemcpyDeviceToHost, st));
+    std::vector<uint8_t> vis(slot_of ? n : 0);
+    HIP_TRY(ctx, hipMemcpyAsync(slot_of ? vis.data() : out_hit, ctx->ws[0].vis.p, n, hipMemcpyDeviceToHost, st));
     unsigned host_ctrl[4];
     HIP_TRY(ctx, hipMemcpyAsync(host_ctrl, ctrl, 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     if (host_ctrl[YK_CTRL_ERR] & 1u) return fail(ctx, YK_ERR_STACK_OVERFLOW, "BVH traversal stack exceeded 64 entries (bvh.rs:174)");
+    for (size_t k = 0; k < vis.size(); ++k) {  // ray k's verdict is in slot n - 1 - k: 2 occluded, 0 untouched
+        const uint8_t v = vis[n - 1 - k];
+        if (v != 0 && v != 2)
+            return fail(ctx, YK_ERR_DEVICE, "trace_stage_kernel " + std::to_string(mode) + ": slot " + std::to_string(n - 1 - k) + " holds " + std::to_string(v));
+        out_hit[k] = v == 2 ? 1 : 0;
+    }
     return YK_OK;
-}
+} YK_CATCH(ctx)
 
 yk_status yk_sampler_sequence(yk_context* ctx, const yk_sampler_desc* sampler, uint16_t px, uint16_t py, uint32_t sample_index, const uint8_t* dims,
                               size_t n_draws, float* out) {
