@@ -156,7 +156,8 @@ typedef enum yk_integrator_kind {
     YK_INTEGRATOR_PATH = 1,
     YK_INTEGRATOR_BVH_INTERSECTIONS = 2,
     YK_INTEGRATOR_GEOMETRY_NORMALS = 3,
-    YK_INTEGRATOR_SHADING_NORMALS = 4
+    YK_INTEGRATOR_SHADING_NORMALS = 4,
+    YK_INTEGRATOR_SHADING_UVS = 5 /* shading_uvs.rs: (uv.x, uv.y, 0) on a hit, black on a miss */
 } yk_integrator_kind;
 typedef struct yk_integrator_desc {
     uint32_t kind;
@@ -416,6 +417,30 @@ yk_status yk_film_update_tiles_device(yk_context* ctx, const yk_tile* tiles, siz
 yk_status yk_li(yk_context* ctx, const yk_scene* scene, const yk_sampler_desc* sampler, const yk_integrator_desc* integrator,
                 size_t n, const float* ray_o, const float* ray_d, const uint16_t* pixel_xy, const uint32_t* sample_index,
                 uint32_t dimension, float* out_li, uint32_t* out_ray_counts);
+
+/* Integrator::li_debug (integrators/mod.rs:103-115): the rays of a sample, each with its type (mod.rs:83-90) */
+typedef enum yk_ray_type { YK_RAY_DIRECT = 0, YK_RAY_REFLECTION = 1, YK_RAY_REFRACTION = 2, YK_RAY_NORMAL = 3, YK_RAY_SHADOW = 4 } yk_ray_type;
+typedef struct yk_integrator_ray {
+    float o[3];
+    float d[3];
+    float t_max;
+    uint32_t ray_type; /* yk_ray_type (IntegratorRay::ray_type; `type` is a Rust keyword) */
+} yk_integrator_ray;   /* 32 bytes */
+#define YK_LI_DEBUG_MAX_RECORDS (1u << 24) /* largest n * ray_cap yk_li_debug accepts */
+/* Integrator::li_debug for n caller-supplied rays; the sampler is started as in yk_li.  Path only (other kinds:
+ * YK_ERR_UNSUPPORTED, as the reference's Whitted and debug integrators keep the trait default).  Returns li, the
+ * closest-hit ray count of every sample (ray_scene_intersections; may be NULL) and its records in Path::li_internal's
+ * push order (path.rs:71-149): every traced segment (Direct, then Reflection or Refraction by the sampled lobe; t_max =
+ * the hit t, else the camera ray's own t_max or the exit through the BVH root box), a Normal record (si.p, si.n) after
+ * each hit, and a Shadow record (VisibilityTester::ray) for every light whose li is non-black and that has a visibility
+ * tester.  Normal records and segments that miss the root box have t_max = min_debug_ray_length (path.rs:58-62).
+ * out_rays: n * ray_cap records, sample-major (unused slots zero; may be NULL when ray_cap == 0); out_n_rays[i] is the
+ * number of records sample i produced and may exceed ray_cap (then only ray_cap were written).
+ * ray_cap = max_depth * (2 + n_lights) always suffices; n * ray_cap must not exceed YK_LI_DEBUG_MAX_RECORDS. */
+yk_status yk_li_debug(yk_context* ctx, const yk_scene* scene, const yk_sampler_desc* sampler, const yk_integrator_desc* integrator,
+                      size_t n, const float* ray_o, const float* ray_d, const uint16_t* pixel_xy, const uint32_t* sample_index,
+                      uint32_t dimension, uint32_t ray_cap, float* out_li, uint32_t* out_ray_counts,
+                      yk_integrator_ray* out_rays, uint32_t* out_n_rays);
 
 /* ---- per-stage entry points (parity tests, profiling) ------------------------- */
 /* BoundingVolumeHierarchy::intersect (bvh.rs:160-232) for n host rays.

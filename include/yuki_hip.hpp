@@ -104,6 +104,7 @@ struct IntegratorType {
     static yk_integrator_desc BVHIntersections() { return yk_integrator_desc{YK_INTEGRATOR_BVH_INTERSECTIONS, 1, 0, 0.0f}; }
     static yk_integrator_desc GeometryNormals() { return yk_integrator_desc{YK_INTEGRATOR_GEOMETRY_NORMALS, 1, 0, 0.0f}; }
     static yk_integrator_desc ShadingNormals() { return yk_integrator_desc{YK_INTEGRATOR_SHADING_NORMALS, 1, 0, 0.0f}; }
+    static yk_integrator_desc ShadingUVs() { return yk_integrator_desc{YK_INTEGRATOR_SHADING_UVS, 1, 0, 0.0f}; }
 };
 
 class Context {
@@ -124,11 +125,12 @@ class Context {
 // scene/mod.rs:41-49.  ctx == nullptr: host-only (BVH build / export, no GPU).
 class Scene {
    public:
-    Scene(Context* ctx, const yk_scene_desc& desc) : ctx_(ctx) { check(yk_scene_create(ctx ? ctx->handle() : nullptr, &desc, &h_), ctx ? ctx->handle() : nullptr); }
+    Scene(Context* ctx, const yk_scene_desc& desc) : ctx_(ctx), n_lights_(desc.n_lights) { check(yk_scene_create(ctx ? ctx->handle() : nullptr, &desc, &h_), ctx ? ctx->handle() : nullptr); }
     ~Scene() { yk_scene_destroy(h_); }
     Scene(const Scene&) = delete;
     Scene& operator=(const Scene&) = delete;
     yk_scene* handle() const { return h_; }
+    uint32_t n_lights() const { return n_lights_; }
     yk_scene_info info() const {
         yk_scene_info i;
         check(yk_scene_get_info(h_, &i));
@@ -144,6 +146,7 @@ class Scene {
 
    private:
     Context* ctx_;
+    uint32_t n_lights_ = 0;
     yk_scene* h_ = nullptr;
 };
 
@@ -209,6 +212,29 @@ class Integrator {
                                                   out_rgb, &st, nullptr, nullptr),
               ctx_.handle());
         return st;
+    }
+
+    // Integrator::li_debug (integrators/mod.rs:103-115), Path only: per sample the radiance, the closest-hit ray count and its
+    // rays in the reference's push order; the sampler is started at (pixel_xy[i], sample_index[i]) after `dimension` draws
+    struct LiDebug {
+        std::vector<float> li;  // n x RGB
+        std::vector<uint32_t> ray_counts;
+        std::vector<std::vector<yk_integrator_ray>> rays;
+    };
+    LiDebug li_debug(const Scene& scene, const yk_sampler_desc& sampler, size_t n, const float* ray_o, const float* ray_d, const uint16_t* pixel_xy,
+                     const uint32_t* sample_index, uint32_t dimension = 2) const {
+        const uint32_t cap = desc_.max_depth * (2u + scene.n_lights());  // always suffices
+        LiDebug r;
+        r.li.resize(3 * n);
+        r.ray_counts.resize(n);
+        std::vector<yk_integrator_ray> recs((size_t)n * cap);
+        std::vector<uint32_t> n_rays(n);
+        check(yk_li_debug(ctx_.handle(), scene.handle(), &sampler, &desc_, n, ray_o, ray_d, pixel_xy, sample_index, dimension, cap, r.li.data(),
+                          r.ray_counts.data(), recs.data(), n_rays.data()),
+              ctx_.handle());
+        r.rays.resize(n);
+        for (size_t i = 0; i < n; ++i) r.rays[i].assign(recs.begin() + i * cap, recs.begin() + i * cap + n_rays[i]);
+        return r;
     }
 
    private:

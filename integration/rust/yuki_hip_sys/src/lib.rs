@@ -36,6 +36,13 @@ pub const YK_INTEGRATOR_PATH: u32 = 1;
 pub const YK_INTEGRATOR_BVH_INTERSECTIONS: u32 = 2;
 pub const YK_INTEGRATOR_GEOMETRY_NORMALS: u32 = 3;
 pub const YK_INTEGRATOR_SHADING_NORMALS: u32 = 4;
+pub const YK_INTEGRATOR_SHADING_UVS: u32 = 5;
+pub const YK_RAY_DIRECT: u32 = 0;
+pub const YK_RAY_REFLECTION: u32 = 1;
+pub const YK_RAY_REFRACTION: u32 = 2;
+pub const YK_RAY_NORMAL: u32 = 3;
+pub const YK_RAY_SHADOW: u32 = 4;
+pub const YK_LI_DEBUG_MAX_RECORDS: u32 = 1 << 24;
 pub const YK_TONE_MAP_RAW: u32 = 0;
 pub const YK_TONE_MAP_FILMIC: u32 = 1;
 pub const YK_TONE_MAP_HEATMAP: u32 = 2;
@@ -173,6 +180,16 @@ pub struct yk_tone_map_desc {
     pub bounds: [f32; 2],
 }
 
+/// IntegratorRay (integrators/mod.rs:76-80): the ray and its yk_ray_type
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct yk_integrator_ray {
+    pub o: [f32; 3],
+    pub d: [f32; 3],
+    pub t_max: f32,
+    pub ray_type: u32,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct yk_tile {
@@ -293,6 +310,7 @@ extern "C" {
     pub fn yk_render_tile(ctx: *mut yk_context, scene: *const yk_scene, camera: *const yk_camera, sampler: *const yk_sampler_desc, integrator: *const yk_integrator_desc, tile: *const yk_tile, tile_pixels: *mut f32, out_rays: *mut u64) -> yk_status;
     pub fn yk_film_update_tiles_device(ctx: *mut yk_context, tiles: *const yk_tile, n_tiles: usize, d_tile_rgb: *const c_void, res_x: u16, res_y: u16, d_film_rgb: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_li(ctx: *mut yk_context, scene: *const yk_scene, sampler: *const yk_sampler_desc, integrator: *const yk_integrator_desc, n: usize, ray_o: *const f32, ray_d: *const f32, pixel_xy: *const u16, sample_index: *const u32, dimension: u32, out_li: *mut f32, out_ray_counts: *mut u32) -> yk_status;
+    pub fn yk_li_debug(ctx: *mut yk_context, scene: *const yk_scene, sampler: *const yk_sampler_desc, integrator: *const yk_integrator_desc, n: usize, ray_o: *const f32, ray_d: *const f32, pixel_xy: *const u16, sample_index: *const u32, dimension: u32, ray_cap: u32, out_li: *mut f32, out_ray_counts: *mut u32, out_rays: *mut yk_integrator_ray, out_n_rays: *mut u32) -> yk_status;
     pub fn yk_image_texture_load(path: *const c_char, out: *mut yk_texture_desc) -> yk_status;
     pub fn yk_image_texture_free(tex: *mut yk_texture_desc);
     pub fn yk_load_ply(path: *const c_char, split_method: u32, max_shapes_in_node: u32, out: *mut *mut yk_loaded_scene) -> yk_status;

@@ -8,7 +8,7 @@
 //!   renderer/render_manager.rs build the `HipDevice` when a scene is loaded (see gpu_worker.rs)
 #![cfg(feature = "hip")]
 
-use super::{path, whitted, Integrator, RadianceResult};
+use super::{path, whitted, Integrator, IntegratorRay, RadianceResult};
 use crate::{
     camera::Camera,
     describe::{LightDesc, MaterialDesc, SamplerDesc, ShapeDesc, TextureDesc},
@@ -345,7 +345,27 @@ impl HipPath {
 
 impl Integrator for HipPath {
     fn li(&self, _s: &ScopedScratch, _ray: Ray<f32>, _scene: &Scene, _depth: u32, _sampler: &mut Box<dyn Sampler>) -> RadianceResult {
-        unimplemented!("per-ray li goes through yk_li; the UI's debug ray keeps using the CPU Path")
+        unimplemented!("per-ray li goes through yk_li; the UI's debug ray goes through li_debug")
+    }
+
+    /// The UI's "fire debug ray" (app/window.rs:812-900).  The trait hands over a sampler that was never started for a
+    /// pixel sample (window.rs:880-885), and that state cannot be carried to the device (yk_li_debug starts the sampler
+    /// itself, as yk_li does), so the ray is traced by the CPU `path::Path` with the same parameters.  Whitted keeps the
+    /// trait default, as the reference's `Whitted` does.
+    fn li_debug(
+        &self,
+        scratch: &ScopedScratch,
+        ray: Ray<f32>,
+        scene: &Scene,
+        depth: u32,
+        sampler: &mut Box<dyn Sampler>,
+        rays: &mut Vec<IntegratorRay>,
+    ) -> RadianceResult {
+        if self.desc.kind != sys::YK_INTEGRATOR_PATH {
+            return RadianceResult::default();
+        }
+        let params = path::Params { max_depth: self.desc.max_depth, indirect_clamp: (self.desc.has_clamp != 0).then_some(self.desc.indirect_clamp) };
+        path::Path::new(params).li_debug(scratch, ray, scene, depth, sampler, rays)
     }
 
     /// One tile through the device, the way the unchanged render manager calls it: from `num_cpus - 1` worker threads at once.

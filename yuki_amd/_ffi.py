@@ -95,6 +95,7 @@ SYMBOLS = {
     "yk_render_tile": (C.c_int, [vp, vp, C.POINTER(abi.CameraMatrices), C.POINTER(abi.SamplerDesc), C.POINTER(abi.IntegratorDesc), C.POINTER(abi.Tile), vp, C.POINTER(C.c_uint64)]),
     "yk_film_update_tiles_device": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_uint16, C.c_uint16, vp, vp]),
     "yk_li": (C.c_int, [vp, vp, C.POINTER(abi.SamplerDesc), C.POINTER(abi.IntegratorDesc), C.c_size_t, vp, vp, vp, vp, C.c_uint32, vp, vp]),
+    "yk_li_debug": (C.c_int, [vp, vp, C.POINTER(abi.SamplerDesc), C.POINTER(abi.IntegratorDesc), C.c_size_t, vp, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]),
     "yk_trace_closest": (C.c_int, [vp, vp, C.c_size_t] + [vp] * 9),
     "yk_trace_any": (C.c_int, [vp, vp, C.c_size_t] + [vp] * 5),
     "yk_sampler_sequence": (C.c_int, [vp, C.POINTER(abi.SamplerDesc), C.c_uint16, C.c_uint16, C.c_uint32, vp, C.c_size_t, vp]),

@@ -114,6 +114,12 @@ class ToneMapDesc(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("exposure", C.c_float), ("channel", C.c_uint32), ("has_bounds", C.c_uint32), ("bounds", C.c_float * 2)]
 
 
+class IntegratorRay(C.Structure):
+    """yk_integrator_ray: IntegratorRay (integrators/mod.rs:76-80), the ray and its yk_ray_type."""
+
+    _fields_ = [("o", C.c_float * 3), ("d", C.c_float * 3), ("t_max", C.c_float), ("ray_type", C.c_uint32)]
+
+
 class Tile(C.Structure):
     _fields_ = [("x0", C.c_uint16), ("y0", C.c_uint16), ("x1", C.c_uint16), ("y1", C.c_uint16)]
 
@@ -144,13 +150,15 @@ BVH_NODE_DTYPE = np.dtype(
     [("bmin", "<f4", 3), ("bmax", "<f4", 3), ("a", "<u4"), ("count", "<u2"), ("axis", "u1"), ("is_leaf", "u1")]
 )
 TILE_DTYPE = np.dtype([("x0", "<u2"), ("y0", "<u2"), ("x1", "<u2"), ("y1", "<u2")])
+INTEGRATOR_RAY_DTYPE = np.dtype([("o", "<f4", 3), ("d", "<f4", 3), ("t_max", "<f4"), ("ray_type", "<u4")])
 
 # enums (include/yuki_hip.h)
 SPLIT_SAH, SPLIT_MIDDLE, SPLIT_EQUAL_COUNTS = 0, 1, 2
 MAT_MATTE, MAT_GLASS, MAT_METAL, MAT_GLOSSY = 0, 1, 2, 3
 LIGHT_POINT, LIGHT_SPOT, LIGHT_DISTANT, LIGHT_RECT = 0, 1, 2, 3
 SAMPLER_UNIFORM, SAMPLER_STRATIFIED = 0, 1
-INTEGRATOR_WHITTED, INTEGRATOR_PATH, INTEGRATOR_BVH_INTERSECTIONS, INTEGRATOR_GEOMETRY_NORMALS, INTEGRATOR_SHADING_NORMALS = 0, 1, 2, 3, 4
+INTEGRATOR_WHITTED, INTEGRATOR_PATH, INTEGRATOR_BVH_INTERSECTIONS, INTEGRATOR_GEOMETRY_NORMALS, INTEGRATOR_SHADING_NORMALS, INTEGRATOR_SHADING_UVS = 0, 1, 2, 3, 4, 5
+RAY_DIRECT, RAY_REFLECTION, RAY_REFRACTION, RAY_NORMAL, RAY_SHADOW = 0, 1, 2, 3, 4
 FOV_X, FOV_Y = 0, 1
 TONE_MAP_RAW, TONE_MAP_FILMIC, TONE_MAP_HEATMAP = 0, 1, 2
 HEATMAP_RED, HEATMAP_GREEN, HEATMAP_BLUE, HEATMAP_LUMINANCE = 0, 1, 2, 3

@@ -384,6 +384,7 @@ class Scene:
         self.ctx = ctx
         self.data = scene_data
         d, self._keep = scene_data.desc(LightFactory)
+        self.n_lights = int(d.n_lights)
         h = C.c_void_p()
         check(lib().yk_scene_create(ctx.h if ctx else None, C.byref(d), C.byref(h)), ctx.h if ctx else None)
         self.h = h
@@ -648,6 +649,12 @@ class Combiner:
 
 
 # --------------------------------------------------------------------------- integrators
+class RayType:
+    """integrators/mod.rs:83-90: the type of an IntegratorRay (yk_ray_type)."""
+
+    Direct, Reflection, Refraction, Normal, Shadow = abi.RAY_DIRECT, abi.RAY_REFLECTION, abi.RAY_REFRACTION, abi.RAY_NORMAL, abi.RAY_SHADOW
+
+
 class Integrator:
     """trait Integrator (integrators/mod.rs:92-186) over the HIP wavefront."""
 
@@ -758,6 +765,32 @@ class Integrator:
         check(lib().yk_li(self.ctx.h, scene.h, C.byref(sampler), C.byref(self.desc), o.shape[0], _p(o), _p(d), _p(pix), _p(si), dimension, _p(out), None), self.ctx.h)
         return out
 
+    def li_debug(self, scene, sampler, ray_o, ray_d, pixel_xy, sample_index, dimension=2):
+        """Integrator::li_debug (integrators/mod.rs:103-115), Path only: returns (li (n,3), ray_counts (n,), rays), where
+        rays[i] holds sample i's records (abi.INTEGRATOR_RAY_DTYPE, `ray_type` a RayType) in the reference's push order.
+        The capacity is max_depth * (2 + lights), which always suffices."""
+        cap = self.desc.max_depth * (2 + scene.n_lights)
+        li, counts, recs, n_rays = self.li_debug_records(scene, sampler, ray_o, ray_d, pixel_xy, sample_index, dimension, cap)
+        return li, counts, [recs[i, : n_rays[i]] for i in range(len(n_rays))]
+
+    def li_debug_records(self, scene, sampler, ray_o, ray_d, pixel_xy, sample_index, dimension, ray_cap):
+        """yk_li_debug as it is: (li, ray_counts, records (n, ray_cap), n_rays), where n_rays[i] may exceed ray_cap
+        (then only the first ray_cap records of sample i were stored)."""
+        o = np.ascontiguousarray(ray_o, dtype=np.float32)
+        d = np.ascontiguousarray(ray_d, dtype=np.float32)
+        pix = np.ascontiguousarray(pixel_xy, dtype=np.uint16)
+        si = np.ascontiguousarray(sample_index, dtype=np.uint32)
+        n = o.shape[0]
+        out = np.zeros((n, 3), dtype=np.float32)
+        counts = np.zeros(n, dtype=np.uint32)
+        n_rays = np.zeros(n, dtype=np.uint32)
+        recs = np.zeros((n, ray_cap), dtype=abi.INTEGRATOR_RAY_DTYPE)
+        check(
+            lib().yk_li_debug(self.ctx.h, scene.h, C.byref(sampler), C.byref(self.desc), n, _p(o), _p(d), _p(pix), _p(si), dimension, ray_cap, _p(out), _p(counts), _p(recs) if ray_cap else None, _p(n_rays)),
+            self.ctx.h,
+        )
+        return out, counts, recs, n_rays
+
 
 class IntegratorType:
     """integrators/mod.rs:33-53."""
@@ -774,6 +807,7 @@ class IntegratorType:
     BVHIntersections = abi.IntegratorDesc(abi.INTEGRATOR_BVH_INTERSECTIONS, 1, 0, 0.0)
     GeometryNormals = abi.IntegratorDesc(abi.INTEGRATOR_GEOMETRY_NORMALS, 1, 0, 0.0)
     ShadingNormals = abi.IntegratorDesc(abi.INTEGRATOR_SHADING_NORMALS, 1, 0, 0.0)
+    ShadingUVs = abi.IntegratorDesc(abi.INTEGRATOR_SHADING_UVS, 1, 0, 0.0)
 
     @staticmethod
     def instantiate(ctx, desc):

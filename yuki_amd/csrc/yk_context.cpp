@@ -284,6 +284,7 @@ size_t yk_sizeof(int what) {
         case 11: return sizeof(yk_render_stats);
         case 12: return sizeof(yk_scene_info);
         case 13: return sizeof(yk_tone_map_desc);
+        case 14: return sizeof(yk_integrator_ray);
         default: return 0;
     }
 }

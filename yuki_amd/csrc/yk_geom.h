@@ -302,7 +302,8 @@ YK_HD Surface hit_surface(const DevScene& sc, uint32_t shape, V3 o, V3 d) {
 // report): the 48-byte traversal record holds the vertices, the area light and the source
 // shape, DevScene::prim_shade the vertex indices, material and mesh flags — one dependent
 // fetch less than going through indices -> points and tri_mesh -> mesh_flags.
-YK_HD Surface hit_surface_prim(const DevScene& sc, uint32_t prim, V3 o, V3 d) {
+// `want_uv`: also compute a sphere's uv (sphere.rs:95-103); the shading path needs it only for image textures.
+YK_HD Surface hit_surface_prim(const DevScene& sc, uint32_t prim, V3 o, V3 d, bool want_uv) {
     const float4 v0 = sc.tris[3 * prim], v1 = sc.tris[3 * prim + 1], v2 = sc.tris[3 * prim + 2];
     const uint4 ps = sc.prim_shade[prim];
     const uint32_t src = __float_as_uint(v1.w);
@@ -311,7 +312,7 @@ YK_HD Surface hit_surface_prim(const DevScene& sc, uint32_t prim, V3 o, V3 d) {
         V3 ro, rd;
         float t = 0.0f;
         sphere_hit_t(sp, o, d, __builtin_inff(), t, ro, rd);
-        return make_surface_sphere(sp, ro, rd, t, d, sc.texels != nullptr);
+        return make_surface_sphere(sp, ro, rd, t, d, want_uv);
     }
     // per-vertex normals and uvs of the primitive, copied into leaf order at scene creation: their address depends on the
     // hit alone, so they are in flight together with the vertices instead of waiting for the vertex indices (k_shade
@@ -338,6 +339,7 @@ YK_HD Surface hit_surface_prim(const DevScene& sc, uint32_t prim, V3 o, V3 d) {
     s.wo = -d;
     return s;
 }
+YK_HD Surface hit_surface_prim(const DevScene& sc, uint32_t prim, V3 o, V3 d) { return hit_surface_prim(sc, prim, o, d, sc.texels != nullptr); }
 
 // ImageTexture::evaluate, textures/image_texture.rs:81-111: repeat, flip v, point sample.
 // `as usize` saturates (NaN and negatives -> 0); the index cannot leave the image.

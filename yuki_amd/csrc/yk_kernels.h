@@ -33,6 +33,10 @@ void launch_trace_closest(hipStream_t s, unsigned grid, const DevScene& sc, cons
 void launch_whitted(hipStream_t s, unsigned grid, const DevScene& sc, const RenderParams& prm, const uint32_t* pixel_xy, const uint32_t* sample_index_tab,
                     PathBuffers cur, uint32_t n, float4* sample_buf, uint2* spill, unsigned spill_stride, unsigned* ctrl, unsigned long long* counters);
 unsigned whitted_max_depth();
+// Path::li_debug (yk_li_debug): one lane per sample, the radiance, closest-hit ray count and ray records of every sample
+void launch_path_debug(hipStream_t s, unsigned grid, const DevScene& sc, const RenderParams& prm, const uint32_t* pixel_xy, const uint32_t* sample_index_tab,
+                       PathBuffers cur, uint32_t n, float4* sample_buf, uint32_t* out_counts, float4* out_rays, unsigned ray_cap, uint32_t* out_n_rays,
+                       float min_len, uint2* spill, unsigned spill_stride, unsigned* ctrl);
 void launch_trace_any(hipStream_t s, unsigned grid, const DevScene& sc, const float4* shO, const float4* shD, const unsigned* slot_of,
                       const unsigned* count_ptr, unsigned* head, unsigned char* vis, uint2* spill, unsigned spill_stride, unsigned* ctrl,
                       unsigned long long* shadow_counter, const unsigned* cancel_host = nullptr);

@@ -577,8 +577,8 @@ __global__ void k_film_scatter(const uint32_t* pixel_xy, uint32_t n_pixels, cons
 }
 
 // ------------------------------------------------------------------ debug integrators
-// BVHIntersections / GeometryNormals / ShadingNormals::li (bvh_heatmap.rs:25-40,
-// geometry_normals.rs:24-33, shading_normals.rs)
+// BVHIntersections / GeometryNormals / ShadingNormals / ShadingUVs::li (bvh_heatmap.rs:25-40,
+// geometry_normals.rs:24-33, shading_normals.rs, shading_uvs.rs: (uv.x, uv.y, 0) on a hit, black on a miss)
 __global__ void k_debug_shade(DevScene sc, uint32_t integrator, PathBuffers cur, const int* hit_tri, const uint4* stats, uint32_t n,
                               float4* sample_buf) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -589,6 +589,10 @@ __global__ void k_debug_shade(DevScene sc, uint32_t integrator, PathBuffers cur,
     if (integrator == YK_INTEGRATOR_BVH_INTERSECTIONS) {
         uint4 s = stats[i];
         c = RGB{(float)s.x, (float)s.y, tri >= 0 ? (float)s.y : 0.0f};
+    } else if (tri >= 0 && integrator == YK_INTEGRATOR_SHADING_UVS) {
+        V3 o = f4_xyz(cur.rayO[i]), d = f4_xyz(cur.rayD[i]);
+        Surface sf = hit_surface_prim(sc, (uint32_t)tri & YK_HIT_PRIM_MASK, o, d, true);  // a sphere's uv also without image textures
+        c = RGB{sf.u, sf.v, 0.0f};
     } else if (tri >= 0) {
         V3 o = f4_xyz(cur.rayO[i]), d = f4_xyz(cur.rayD[i]);
         Surface sf = hit_surface_prim(sc, (uint32_t)tri & YK_HIT_PRIM_MASK, o, d);  // the normals integrators trace with the render-loop kernel: leaf-order slots

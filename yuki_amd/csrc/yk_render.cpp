@@ -101,7 +101,7 @@ yk_status make_params(yk_context* ctx, const yk_sampler_desc* smp, const yk_inte
     prm.integrator = integ->kind;
     if (integ->kind == YK_INTEGRATOR_WHITTED && integ->max_depth > whitted_max_depth())
         return fail(ctx, YK_ERR_UNSUPPORTED, "Whitted: max_depth above 16 is not supported on the device");
-    if (integ->kind > YK_INTEGRATOR_SHADING_NORMALS) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "bad integrator kind");
+    if (integ->kind > YK_INTEGRATOR_SHADING_UVS) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "bad integrator kind");
     return YK_OK;
 }
 
@@ -904,6 +904,83 @@ yk_status yk_li(yk_context* ctx, const yk_scene* scene, const yk_sampler_desc* s
         out_li[3 * i + 2] = tmp[4 * i + 2];
     }
     if (out_ray_counts) std::memset(out_ray_counts, 0, n * 4);  // per-ray counts are not tracked by the wavefront
+    return YK_OK;
+} YK_CATCH(ctx)
+
+yk_status yk_li_debug(yk_context* ctx, const yk_scene* scene, const yk_sampler_desc* sampler, const yk_integrator_desc* integrator, size_t n,
+                      const float* ray_o, const float* ray_d, const uint16_t* pixel_xy, const uint32_t* sample_index, uint32_t dimension, uint32_t ray_cap,
+                      float* out_li, uint32_t* out_ray_counts, yk_integrator_ray* out_rays, uint32_t* out_n_rays) try {
+    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
+    YK_LOCK(ctx);
+    if (!scene || !ray_o || !ray_d || !pixel_xy || !sample_index || !out_li || !out_n_rays || (ray_cap && !out_rays) || n == 0)
+        return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null argument");
+    if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "scene was not created on this context's device");
+    if (n > ((size_t)1 << 28)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "too many rays");
+    if ((uint64_t)n * ray_cap > YK_LI_DEBUG_MAX_RECORDS) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "n * ray_cap exceeds YK_LI_DEBUG_MAX_RECORDS");
+    RenderParams prm;
+    yk_status ps = make_params(ctx, sampler, integrator, prm);
+    if (ps != YK_OK) return ps;
+    if (prm.integrator != YK_INTEGRATOR_PATH) return fail(ctx, YK_ERR_UNSUPPORTED, "yk_li_debug implements the Path integrator (the others keep the trait's default)");
+    prm.spe = 1;  // one table entry (pixel, sample index) per ray
+    for (size_t i = 0; i < n; ++i)
+        if (sample_index[i] >= prm.sampler.spp) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "sample_index >= samples per pixel");
+    (void)hipSetDevice(ctx->device);
+    yk_status cs = clear_cancel(ctx);
+    if (cs != YK_OK) return cs;
+    hipStream_t st = ctx->stream;
+    yk_status wb = ensure_work_buffers(ctx, ctx->ws[0], n, scene->n_lights, scene->n_delta_lights);
+    if (wb != YK_OK) return wb;
+    if ((wb = ensure_spill(ctx, ctx->ws[0])) != YK_OK) return wb;
+    const size_t rec_bytes = (size_t)n * ray_cap * sizeof(yk_integrator_ray);
+    HIP_TRY(ctx, ctx->scratch[0].ensure(std::max<size_t>(rec_bytes, 32)));
+    HIP_TRY(ctx, ctx->scratch[1].ensure(n * 4));
+    HIP_TRY(ctx, ctx->scratch[2].ensure(n * 4));
+    HIP_TRY(ctx, ctx->scratch[4].ensure(n * 12));
+    HIP_TRY(ctx, ctx->scratch[5].ensure(n * 12));
+    HIP_TRY(ctx, ctx->scratch[6].ensure(n * 4));
+    HIP_TRY(ctx, ctx->scratch[7].ensure(n * 4));
+    HIP_TRY(ctx, ctx->pixel_xy.ensure(n * 4));
+    HIP_TRY(ctx, ctx->sample_buf.ensure(n * 16));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[4].p, ray_o, n * 12, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[5].p, ray_d, n * 12, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[6].p, pixel_xy, n * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[7].p, sample_index, n * 4, hipMemcpyHostToDevice, st));
+    unsigned* ctrl = ctx->ws[0].ctrl.as<unsigned>();
+    HIP_TRY(ctx, hipMemsetAsync(ctx->counters.p, 0, YK_COUNTER_BYTES, st));  // the error block with it: stack-overflow flag, interruption word
+    HIP_TRY(ctx, hipMemsetAsync(ctrl, 0, YK_CTRL_WORDS * 4, st));
+    if (rec_bytes) HIP_TRY(ctx, hipMemsetAsync(ctx->scratch[0].p, 0, rec_bytes, st));  // the slots a sample leaves unused read as zero
+    prm.cancel = cancel_ref(ctx);
+    launch_raygen_user(st, prm, ctx->scratch[4].as<float>(), ctx->scratch[5].as<float>(), ctx->scratch[6].as<uint16_t>(), ctx->scratch[7].as<uint32_t>(),
+                       dimension, (uint32_t)n, path_buffers(ctx->ws[0], 0), ctx->sample_buf.as<float4>(), ctx->pixel_xy.as<uint32_t>(), ctrl + YK_CTRL_BOUNCE(0));
+    // path.rs:58-62: min_debug_ray_length, the root box's extent on Bounds3::maximum_extent (bounds.rs:147-156) / 10
+    const float* lo = scene->dev.root_bmin;
+    const float* hi = scene->dev.root_bmax;
+    const float dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
+    const int axis = (dx > dy && dx > dz) ? 0 : (dy > dz ? 1 : 2);
+    const float min_len = (hi[axis] - lo[axis]) / 10.0f;
+    launch_path_debug(st, trace_grid(ctx), scene->dev, prm, ctx->pixel_xy.as<uint32_t>(), ctx->scratch[7].as<uint32_t>(), path_buffers(ctx->ws[0], 0), (uint32_t)n,
+                      ctx->sample_buf.as<float4>(), ctx->scratch[1].as<uint32_t>(), ctx->scratch[0].as<float4>(), ray_cap, ctx->scratch[2].as<uint32_t>(), min_len,
+                      ctx->ws[0].spill.as<uint2>(), trace_grid(ctx) * trace_block_size(), error_block(ctx));
+    HIP_TRY(ctx, hipGetLastError());
+    std::vector<float> tmp(n * 4);
+    std::vector<uint32_t> counts(n), n_rays(n);
+    unsigned host_err[4];
+    HIP_TRY(ctx, hipMemcpyAsync(tmp.data(), ctx->sample_buf.p, n * 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(counts.data(), ctx->scratch[1].p, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(n_rays.data(), ctx->scratch[2].p, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(host_err, error_block(ctx), sizeof(host_err), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (ctx->cancel_raised.load(std::memory_order_acquire) || host_err[YK_CTRL_CANCELLED])
+        return fail(ctx, YK_ERR_CANCELLED, "interrupted (yk_context_interrupt)");
+    if (host_err[YK_CTRL_ERR] & 1u) return fail(ctx, YK_ERR_STACK_OVERFLOW, "BVH traversal stack exceeded 64 entries (bvh.rs:174)");
+    if (rec_bytes) HIP_TRY(ctx, hipMemcpy(out_rays, ctx->scratch[0].p, rec_bytes, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) {
+        out_li[3 * i] = tmp[4 * i];
+        out_li[3 * i + 1] = tmp[4 * i + 1];
+        out_li[3 * i + 2] = tmp[4 * i + 2];
+    }
+    if (out_ray_counts) std::memcpy(out_ray_counts, counts.data(), n * 4);
+    std::memcpy(out_n_rays, n_rays.data(), n * 4);
     return YK_OK;
 } YK_CATCH(ctx)
 

@@ -5,6 +5,7 @@
 // order is the reference's: two sampler dimensions per light whether or not it contributes, then the BSDF sample, then
 // Russian roulette; every expression keeps its operation order.  (A per-lane kernel that took the last few paths of a
 // batch to their end with the same four steps was measured and dropped: profiles/r02_tail_kernel_sweep.txt)
+// `k_path_debug` (yk_trace.hip) runs the same steps one lane per sample for yk_li_debug.
 #pragma once
 #include "yk_device.h"
 #include "yk_geom.h"
@@ -20,9 +21,8 @@ struct PathVertex {
     V3 wo;
 };
 
-// `prim`: leaf-order slot of the primitive that was hit (what the render-loop traversal kernels report)
-__device__ __forceinline__ void vertex_setup(const DevScene& sc, uint32_t prim, V3 o, V3 d, PathVertex& v) {
-    v.sf = hit_surface_prim(sc, prim, o, d);
+// the rest of the vertex once v.sf holds the surface: material (with its texture), shading frame, wo
+__device__ __forceinline__ void vertex_setup_material(const DevScene& sc, V3 d, PathVertex& v) {
     v.mat = sc.materials[v.sf.material];
     if (v.mat.tex) {  // matte.rs:29-30: reflectance = kd.evaluate(si); no lobe when black
         RGB kd = texture_eval(sc, v.mat.tex - 1u, v.sf.u, v.sf.v);
@@ -34,18 +34,34 @@ __device__ __forceinline__ void vertex_setup(const DevScene& sc, uint32_t prim, 
     v.fr = make_frame(v.sf.n, v.sf.ns, v.sf.dpdus);
     v.wo = -d;
 }
+// `prim`: leaf-order slot of the primitive that was hit (what the render-loop traversal kernels report)
+__device__ __forceinline__ void vertex_setup(const DevScene& sc, uint32_t prim, V3 o, V3 d, PathVertex& v) {
+    v.sf = hit_surface_prim(sc, prim, o, d);
+    vertex_setup_material(sc, d, v);
+}
 
 // next-event estimation towards light l (path.rs:102-119): draws its two sampler dimensions, and when the light
-// contributes returns the contribution f * li * clamp(ns . l) / pdf and the shadow ray of its VisibilityTester
+// contributes returns the contribution f * li * clamp(ns . l) / pdf and the shadow ray of its VisibilityTester.
+// RAY_ALWAYS (k_path_debug): the shadow ray is also returned when the light has a visibility tester but f is black
+// (`has_ray`; path.rs:103-113 records that ray although it traces nothing).
 struct NeeSample {
     bool want;
+    bool has_ray;  // RAY_ALWAYS only: f was black; so / sd hold the tester's ray, nothing is to be traced
     RGB contrib;
     V3 so, sd;
     int al;  // the sampled area light (its own surface does not occlude, bvh.rs:269-280) or -1
 };
+// VisibilityTester::ray = p0.spawn_ray_to(p1), interaction.rs:44-59 (t_max 0.9999)
+__device__ __forceinline__ void vertex_shadow_ray(const PathVertex& v, const LightSample& ls, V3& so, V3& sd) {
+    V3 offset = v.sf.n * 0.001f;
+    so = dot(ls.p1 - v.sf.p, v.sf.n) > 0.0f ? v.sf.p + offset : v.sf.p - offset;
+    sd = ls.p1 - so;
+}
+template <bool RAY_ALWAYS = false>
 __device__ __forceinline__ NeeSample vertex_light(const DevScene& sc, const RenderParams& prm, SamplerState& st, unsigned l, const PathVertex& v) {
     NeeSample r;
     r.want = false;
+    r.has_ray = false;
     r.contrib = RGB{0, 0, 0};
     r.so = V3{0, 0, 0};
     r.sd = V3{0, 0, 1};
@@ -57,12 +73,12 @@ __device__ __forceinline__ NeeSample vertex_light(const DevScene& sc, const Rend
         RGB f = bsdf_f(v.mat, v.fr, v.sf.wo, ls.l);  // path.rs:105 uses si.wo
         if (ls.has_vis && !is_black(f)) {
             r.contrib = f * ls.li * rclamp(dot_nv(v.sf.ns, ls.l), 0.0f, 1.0f) / ls.pdf;
-            // VisibilityTester::ray = p0.spawn_ray_to(p1), interaction.rs:44-59
-            V3 offset = v.sf.n * 0.001f;
-            r.so = dot(ls.p1 - v.sf.p, v.sf.n) > 0.0f ? v.sf.p + offset : v.sf.p - offset;
-            r.sd = ls.p1 - r.so;
+            vertex_shadow_ray(v, ls, r.so, r.sd);
             r.al = ls.area_light;
             r.want = true;
+        } else if (RAY_ALWAYS && ls.has_vis) {
+            vertex_shadow_ray(v, ls, r.so, r.sd);
+            r.has_ray = true;
         }
     }
     return r;
@@ -88,6 +104,7 @@ struct VertexEnd {
     unsigned kind;
     bool alive, sampled;
     V3 no, wi;
+    unsigned lobe;  // BxdfType of the BSDF sample when `sampled` (k_path_debug tags the next segment with it)
 };
 __device__ __forceinline__ VertexEnd vertex_finish(const DevScene& sc, const RenderParams& prm, SamplerState& st, const PathVertex& v, RGB& beta, unsigned& bounces,
                                                     bool& specular_bounce) {
@@ -98,6 +115,7 @@ __device__ __forceinline__ VertexEnd vertex_finish(const DevScene& sc, const Ren
     e.sampled = false;
     e.no = V3{0, 0, 0};
     e.wi = V3{0, 0, 1};
+    e.lobe = 0;
     if (bounces == 0 || specular_bounce) {  // path.rs:121-123
         RGB le = RGB{0, 0, 0};
         if (v.sf.area_light >= 0) {
@@ -117,6 +135,7 @@ __device__ __forceinline__ VertexEnd vertex_finish(const DevScene& sc, const Ren
         beta = beta * (bs.f * fabsf(dot_nv(bs.wi, v.sf.ns)) / bs.pdf);
         e.no = spawn_origin(v.sf.p, v.sf.n, bs.wi);
         e.wi = bs.wi;
+        e.lobe = bs.type;
         e.alive = true;
         e.sampled = true;
         // Russian roulette, path.rs:162-169

@@ -6,6 +6,7 @@
 //   k_trace_closest<STATS> / k_trace_any  plain one-ray-per-lane loops; the STATS
 //       flavour reproduces IntersectionResult's counters (bvh.rs:167-179) for the
 //       BVHIntersections integrator and the parity tests
+//   k_whitted / k_path_debug  one lane per sample: Whitted's recursion, Path::li_debug
 //
 // Both families implement BoundingVolumeHierarchy::intersect (bvh.rs:160-232) and
 // ::any_intersect (bvh.rs:235-302) with the reference's visiting order.
@@ -14,6 +15,7 @@
 #include "yk_device.h"
 #include "yk_geom.h"
 #include "yk_kernels.h"
+#include "yk_shade.h"
 #ifdef YK_EXPERIMENT_XCD
 #include "../../tools/micro/xcd_claim_experiment.h"
 #endif
@@ -997,6 +999,96 @@ __global__ __launch_bounds__(BLOCK) void k_whitted(DevScene sc, RenderParams prm
     }
 }
 
+// ------------------------------------------------------------------ Path::li_debug
+// Path::li_internal with ray collection (path.rs:48-204) for yk_li_debug, one lane per sample: the bounce loop of the
+// wavefront — traverse_closest, the shading steps of yk_shade.h, traverse_any for each shadow ray, vertex_accumulate —
+// run to the end of the path in one lane, so the radiance is the wavefront's bit for bit.  Each sample writes its
+// yk_integrator_ray records (two float4: o.xyz d.x | d.yz t_max type) in the reference's push order, the first
+// `ray_cap` of them at out_rays[i * ray_cap ...], and in out_n_rays the number it produced.
+__device__ __forceinline__ void debug_ray_store(float4* out, uint32_t i, unsigned ray_cap, unsigned k, V3 o, V3 d, float t_max, unsigned type) {
+    if (k >= ray_cap) return;
+    float4* r = out + 2 * ((size_t)i * ray_cap + k);
+    r[0] = make_float4(o.x, o.y, o.z, d.x);
+    r[1] = make_float4(d.y, d.z, t_max, __uint_as_float(type));
+}
+// Bounds3::intersections (bounds.rs:176-206) of the root box for a ray with t_max = inf: the exit distance, or
+// `miss_len` when the box is missed.  Operation by operation with Rust's f32::min / max (rmin / rmax).
+__device__ __forceinline__ float root_exit(const DevScene& sc, V3 o, V3 d, float miss_len) {
+    const float ix = 1.0f / d.x, iy = 1.0f / d.y, iz = 1.0f / d.z;
+    const float t0x = (sc.root_bmin[0] - o.x) * ix, t0y = (sc.root_bmin[1] - o.y) * iy, t0z = (sc.root_bmin[2] - o.z) * iz;
+    const float t1x = (sc.root_bmax[0] - o.x) * ix, t1y = (sc.root_bmax[1] - o.y) * iy, t1z = (sc.root_bmax[2] - o.z) * iz;
+    const float tmin = rmax(rmax(rmin(t0x, t1x), rmax(rmin(t0y, t1y), rmin(t0z, t1z))), 0.0f);
+    const float tmax = rmin(rmin(rmax(t0x, t1x), rmin(rmax(t0y, t1y), rmax(t0z, t1z))), __builtin_inff());
+    return tmin <= tmax ? tmax : miss_len;
+}
+
+template <int BLOCK, int LDS_DEPTH>
+__global__ __launch_bounds__(BLOCK) void k_path_debug(DevScene sc, RenderParams prm, const uint32_t* pixel_xy, const uint32_t* sample_index_tab, PathBuffers cur,
+                                                      uint32_t n, float4* sample_buf, uint32_t* out_counts, float4* out_rays, unsigned ray_cap,
+                                                      uint32_t* out_n_rays, float min_len, uint2* spill, unsigned spill_stride, unsigned* ctrl) {
+    __shared__ unsigned long long lds_stack[LDS_DEPTH * BLOCK];
+    TravStack<BLOCK, LDS_DEPTH> stk;
+    stk.lds = (lds_u64*)lds_stack;
+    stk.spill = (glb_u64*)spill;
+    stk.spill_stride = spill_stride;
+    stk.gtid = blockIdx.x * BLOCK + threadIdx.x;
+    unsigned* err = ctrl + YK_CTRL_ERR;
+    if (cancel_raised(prm.cancel)) n = 0;  // interrupted before this launch started (yk_device.h, CancelRef)
+    for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
+        const float4 a = cur.rayO[i], b = cur.rayD[i], c = cur.thru[i];
+        const uint4 r = cur.rngs[i];
+        V3 o = f4_xyz(a), d = f4_xyz(b);
+        const unsigned sid = __float_as_uint(b.w);
+        SamplerState st;
+        st.rng.state = (u64)r.x | ((u64)r.y << 32);
+        st.rng.inc = (u64)r.z | ((u64)r.w << 32);
+        st.dimension = __float_as_uint(c.w);
+        uint32_t pix, ks;
+        split_sample_id(sid, prm.spe, pix, ks);
+        const uint32_t xy = pixel_xy[pix];
+        st.px = xy & 0xffffu;
+        st.py = xy >> 16;
+        st.sample_index = (sample_index_tab ? sample_index_tab[pix] : prm.sample_base) + ks;
+        RGB L = RGB{0.0f, 0.0f, 0.0f}, beta = RGB{c.x, c.y, c.z};
+        unsigned bounces = 0, n_closest = 0, k = 0, type = YK_RAY_DIRECT;
+        bool specular_bounce = false, alive = prm.max_depth > 0;
+        while (alive) {
+            // the segment: Direct keeps the camera ray's t_max, later ones the root box's exit; a hit replaces it with t
+            n_closest += 1;
+            int shape;
+            TriHit th = TriHit{0.0f, 0.0f, 0.0f, 0.0f};
+            unsigned nt = 0, nh = 0, ns = 0;
+            traverse_closest<BLOCK, LDS_DEPTH, false>(sc, o, d, __builtin_inff(), stk, shape, th, nt, nh, ns, err);
+            if (shape < 0) {
+                debug_ray_store(out_rays, i, ray_cap, k++, o, d, type == YK_RAY_DIRECT ? __builtin_inff() : root_exit(sc, o, d, min_len), type);
+                L = vertex_accumulate(prm, L, RGB{1.0f, 1.0f, 1.0f}, RGB{0.0f, 0.0f, 0.0f}, vertex_miss_term(sc, beta), YK_PEND_MISS);
+                break;
+            }
+            debug_ray_store(out_rays, i, ray_cap, k++, o, d, th.t, type);
+            PathVertex v;
+            v.sf = hit_surface(sc, (uint32_t)shape, o, d);  // the source shape, as k_whitted (vertex_setup takes a leaf-order slot)
+            vertex_setup_material(sc, d, v);
+            debug_ray_store(out_rays, i, ray_cap, k++, v.sf.p, v.sf.n, min_len, YK_RAY_NORMAL);
+            RGB radiance = RGB{0.0f, 0.0f, 0.0f};
+            for (unsigned l = 0; l < sc.n_lights; ++l) {
+                const NeeSample ne = vertex_light<true>(sc, prm, st, l, v);
+                if (ne.want || ne.has_ray) debug_ray_store(out_rays, i, ray_cap, k++, ne.so, ne.sd, 0.9999f, YK_RAY_SHADOW);
+                if (ne.want && !traverse_any<BLOCK, LDS_DEPTH>(sc, ne.so, ne.sd, 0.9999f, ne.al, stk, err)) radiance = radiance + ne.contrib;
+            }
+            const RGB beta_in = beta;  // vertex_accumulate takes the throughput the vertex was entered with
+            const VertexEnd e = vertex_finish(sc, prm, st, v, beta, bounces, specular_bounce);
+            L = vertex_accumulate(prm, L, beta_in, radiance, e.term, e.kind);
+            alive = e.alive;
+            o = e.no;
+            d = e.wi;
+            type = (e.lobe & BX_REFLECTION) ? YK_RAY_REFLECTION : YK_RAY_REFRACTION;
+        }
+        sample_buf[sid] = make_float4(L.r, L.g, L.b, 0.0f);
+        out_counts[i] = n_closest;
+        out_n_rays[i] = k;
+    }
+}
+
 // ------------------------------------------------------------------ launchers
 #ifndef TRACE_PF_MIN
 #define TRACE_PF_MIN 16
@@ -1051,6 +1143,12 @@ void launch_whitted(hipStream_t s, unsigned grid, const DevScene& sc, const Rend
                        spill_stride, ctrl, counters);
 }
 unsigned whitted_max_depth() { return YK_WHITTED_MAX_DEPTH; }
+void launch_path_debug(hipStream_t s, unsigned grid, const DevScene& sc, const RenderParams& prm, const uint32_t* pixel_xy, const uint32_t* sample_index_tab,
+                       PathBuffers cur, uint32_t n, float4* sample_buf, uint32_t* out_counts, float4* out_rays, unsigned ray_cap, uint32_t* out_n_rays,
+                       float min_len, uint2* spill, unsigned spill_stride, unsigned* ctrl) {
+    hipLaunchKernelGGL((k_path_debug<TRACE_BLOCK, TRACE_LDS>), dim3(grid), dim3(TRACE_BLOCK), 0, s, sc, prm, pixel_xy, sample_index_tab, cur, n, sample_buf,
+                       out_counts, out_rays, ray_cap, out_n_rays, min_len, spill, spill_stride, ctrl);
+}
 void launch_trace_any(hipStream_t s, unsigned grid, const DevScene& sc, const float4* shO, const float4* shD, const unsigned* slot_of,
                       const unsigned* count_ptr, unsigned* head, unsigned char* vis, uint2* spill, unsigned spill_stride, unsigned* ctrl,
                       unsigned long long* shadow_counter, const unsigned* cancel_host) {
