@@ -9,5 +9,3 @@ run() { n=$1; lib=$2; shift 2
 run base sort YK_SORT_BOUNCES=0
 run k4_b9_m0_sh sort YK_SORT_BOUNCES=4 YK_SORT_BITS=9 YK_SORT_MODE=0 YK_SORT_SHADOW=1
 run k4_b9_m2_sh sort YK_SORT_BOUNCES=4 YK_SORT_BITS=9 YK_SORT_MODE=2 YK_SORT_SHADOW=1
-run xcd_k4_b9_m2_sh sortxcd YK_SORT_BOUNCES=4 YK_SORT_BITS=9 YK_SORT_MODE=2 YK_SORT_SHADOW=1
-run xcd_k0 sortxcd YK_SORT_BOUNCES=0

@@ -77,14 +77,6 @@ struct Sorter {
         (void)hipEventCreate(&e0);
         (void)hipEventCreate(&e1);
     }
-    DevBuf xcd_heads;
-    // YK_EXPERIMENT_XCD: eight zeroed queue heads for the next traversal launch on `st` (slot 0 closest-hit, 1 any-hit)
-    unsigned* heads(hipStream_t st, int slot) {
-        (void)xcd_heads.ensure(2 * 64);
-        unsigned* h = xcd_heads.as<unsigned>() + 16 * slot;
-        (void)hipMemsetAsync(h, 0, 64, st);
-        return h;
-    }
     unsigned end_bit() const { return mode == 3 ? 3u : (mode == 2 ? 3u * bits : 3u * bits + 3u); }
     // sorts (keys, vals) of n rays; returns the sorted index array
     const unsigned* sort(hipStream_t st, const float4* rayO, const float4* rayD, unsigned n, const yk::DevScene& sc) {

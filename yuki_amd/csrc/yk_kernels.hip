@@ -366,16 +366,8 @@ __global__ __launch_bounds__(BLOCK, SHADE_MIN_WAVES) void k_shade(DevScene sc, R
             beta = RGB{c.x, c.y, c.z};
             bounces = flags & 0xffu;
             specular_bounce = (flags >> 8) & 1u;
-            st.rng.state = (u64)r.x | ((u64)r.y << 32);
-            st.rng.inc = (u64)r.z | ((u64)r.w << 32);
-            st.dimension = __float_as_uint(c.w);
             // film renders: sample_id = pixel*spp + sample ; yk_li: one table entry per ray
-            uint32_t pix, ks;  // entry of the pixel table and sample within it (yk_device.h: RenderParams::spe)
-            split_sample_id(sid, prm.spe, pix, ks);
-            uint32_t xy = pixel_xy[pix];
-            st.px = xy & 0xffffu;
-            st.py = xy >> 16;
-            st.sample_index = (sample_index_tab ? sample_index_tab[pix] : prm.sample_base) + ks;
+            st = path_sampler(prm, pixel_xy, sample_index_tab, r, __float_as_uint(c.w), sid);
             int tri = hit_tri[i];
             hit = tri >= 0;
             if (hit) vertex_setup(sc, (uint32_t)tri & YK_HIT_PRIM_MASK, o, d, v);  // the leaf-order slot reported by the render-loop trace kernels

@@ -26,46 +26,13 @@
 #include "yk_device.h"
 #include "yk_geom.h"
 #include "yk_kernels.h"
+#include "yk_traverse.h"
 #include "yk_wave.h"
 
 namespace yk {
 
 #define YK_PKT_STACK 64  // one entry per tree level at most; packets are used only when depth <= 64
 #define YK_PKT_BLOCK 256
-
-struct PktNode {
-    V3 lo0, hi0, lo1, hi1;
-    unsigned ref0, ref1, axis;
-};
-// Scene data never changes during a launch: reading it through the constant address space
-// tells the compiler so, and a wave-uniform address then becomes a scalar load (s_load_*,
-// served by the scalar cache) instead of 64 identical vector requests.
-typedef float f4v __attribute__((ext_vector_type(4)));
-typedef unsigned u2v __attribute__((ext_vector_type(2)));
-typedef const __attribute__((address_space(4))) f4v cf4;
-typedef const __attribute__((address_space(4))) u2v cu2;
-__device__ __forceinline__ cf4* as_const(const float4* p) { return (cf4*)(unsigned long long)p; }
-__device__ __forceinline__ float4 ldc(cf4* p, int i) {
-    const f4v v = p[i];
-    return make_float4(v.x, v.y, v.z, v.w);
-}
-
-// `idx` is wave-uniform
-__device__ __forceinline__ PktNode pkt_load_node(const DevNode* nodes, unsigned idx) {
-    cf4* q = as_const(reinterpret_cast<const float4*>(nodes + idx));
-    const float4 a = ldc(q, 0), b = ldc(q, 1), c = ldc(q, 2);
-    const u2v dv = ((cu2*)q)[6];
-    const uint2 d = make_uint2(dv.x, dv.y);
-    PktNode n;
-    n.lo0 = V3{a.x, a.y, a.z};
-    n.hi0 = V3{a.w, b.x, b.y};
-    n.lo1 = V3{b.z, b.w, c.x};
-    n.hi1 = V3{c.y, c.z, c.w};
-    n.ref0 = d.x;
-    n.ref1 = d.y & ~YK_AXIS_MASK;
-    n.axis = (d.y >> YK_AXIS_SHIFT) & 3u;
-    return n;
-}
 
 __device__ __forceinline__ unsigned uni(unsigned v) { return (unsigned)__builtin_amdgcn_readfirstlane((int)v); }
 __device__ __forceinline__ unsigned long long uni64(unsigned long long v) { return (unsigned long long)uni((unsigned)v) | ((unsigned long long)uni((unsigned)(v >> 32)) << 32); }
@@ -97,48 +64,39 @@ __device__ __forceinline__ unsigned pkt_claim_size(unsigned n) {
     packets = packets < 1u ? 1u : (packets > (unsigned)YK_PKT_CHUNK ? (unsigned)YK_PKT_CHUNK : packets);
     return packets * YK_WAVE;
 }
-
-struct PktRay {
-    V3 o, inv, d;
-    RayTri rt;
-    float t_max;
-};
+// Claims rays for the wave until the queue of n is drained and runs packet(base) on each packet of YK_WAVE of them
+// (base is wave-uniform; lanes past the queue's end come along with nothing to trace).  One atomic per YK_PKT_CHUNK
+// packets: a per-packet atomic on the single head word would cap the launch at ~100 M atomics/s (2 M packets = 20 ms).
+template <class Packet> __device__ __forceinline__ void claim_packets(unsigned n, unsigned* head, const CancelRef& cancel, Packet packet) {
+    const unsigned per_claim = pkt_claim_size(n);
+    for (;;) {
+        unsigned claim = 0;
+        if (lane_id() == 0) {
+            claim = atomicAdd(head, per_claim);
+            if (blockIdx.x == 0 && threadIdx.x == 0 && cancel_relay(cancel, head)) claim = 0xffffffffu;  // interrupted (yk_device.h): the head is poisoned, nobody claims again
+        }
+        claim = uni(claim);
+        if (claim >= n) break;
+        const unsigned claim_end = claim + per_claim < n ? claim + per_claim : n;
+        for (unsigned base = claim; base < claim_end; base += YK_WAVE) packet(base);
+    }
+}
 
 // one group of lanes with equal direction signs `sg`; updates best / r.t_max of its lanes
 template <bool SPHERES>
-__device__ __forceinline__ void pkt_closest_group(const DevScene& sc, PktStack& stk, PktRay& r, int& best, unsigned long long group, unsigned sg) {
+__device__ __forceinline__ void pkt_closest_group(const DevScene& sc, PktStack& stk, TraceRay& r, int& best, unsigned long long group, unsigned sg) {
     unsigned cur = sc.root_ref;
     unsigned long long cmask = group;
     int sp = 0;
     for (;;) {
         bool need_pop = false;
         if (cur & YK_LEAF_BIT) {
-            unsigned prim = cur & ~YK_LEAF_BIT;
-            const bool mine = in_mask(cmask);
-            for (;;) {
-                cf4* tq = as_const(sc.tris + 3 * prim);
-                const float4 v0 = ldc(tq, 0), v1 = ldc(tq, 1), v2 = ldc(tq, 2);
-                const unsigned pflags = __float_as_uint(v2.w);
-                if (mine) {
-                    TriHit h = TriHit{0.0f, 0.0f, 0.0f, 0.0f};
-                    bool got;
-                    if (SPHERES && (pflags & YK_PRIM_SPHERE)) {
-                        V3 ro, rd;
-                        got = sphere_hit_t(sc.spheres[__float_as_uint(v1.w) - sc.n_triangles], r.o, r.d, r.t_max, h.t, ro, rd);
-                    } else {
-                        got = tri_intersect(r.o, r.rt, r.t_max, f4_xyz(v0), f4_xyz(v1), f4_xyz(v2), h);
-                    }
-                    if (got) {
-                        best = YK_HIT_WORD(prim, pflags);  // leaf-order slot | BSDF kind, like the render-loop flavour of k_trace_closest_pt
-                        r.t_max = h.t;
-                    }
-                }
-                if (pflags & YK_PRIM_LAST) break;
-                ++prim;
-            }
+            leaf_closest<SPHERES, true, false>(sc, cur & ~YK_LEAF_BIT, in_mask(cmask), r, nullptr, [&](unsigned prim, float4, unsigned pflags, const TriHit&) {
+                best = YK_HIT_WORD(prim, pflags);  // leaf-order slot | BSDF kind, like the render-loop flavour of k_trace_closest_pt
+            });
             need_pop = true;
         } else {
-            const PktNode nb = pkt_load_node(sc.nodes, cur);
+            const NodeBoxes nb = load_node_uniform(sc.nodes, cur);
             const bool mine = in_mask(cmask);
             float t0, t1;
             // exact bound for a child entered now; a deferred (far) child is re-tested exactly when popped, so the
@@ -173,7 +131,7 @@ __device__ __forceinline__ void pkt_closest_group(const DevScene& sc, PktStack& 
                 unsigned parent, which;
                 unsigned long long mask;
                 stk.at(sp, parent, which, mask);
-                const PktNode nb = pkt_load_node(sc.nodes, parent);
+                const NodeBoxes nb = load_node_uniform(sc.nodes, parent);
                 float t;
                 const bool h = in_mask(mask) && (which ? slab(nb.lo1, nb.hi1, r.o, r.inv, r.t_max, t) : slab(nb.lo0, nb.hi0, r.o, r.inv, r.t_max, t));
                 const unsigned long long m = __ballot(h);
@@ -195,51 +153,25 @@ __global__ __launch_bounds__(YK_PKT_BLOCK, 8) void k_trace_closest_packet(DevSce
     __shared__ uint4 lds_stack[(YK_PKT_BLOCK / YK_WAVE) * YK_PKT_STACK];
     PktStack stk;
     stk.base = lds_stack + (threadIdx.x / YK_WAVE) * YK_PKT_STACK;
-    const unsigned n = cancel_raised(cancel) ? 0u : *count_ptr;
-    if (ray_counter && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(ray_counter, (unsigned long long)n);
-    const V3 root_lo = V3{sc.root_bmin[0], sc.root_bmin[1], sc.root_bmin[2]}, root_hi = V3{sc.root_bmax[0], sc.root_bmax[1], sc.root_bmax[2]};
-    // one atomic per YK_PKT_CHUNK packets: a per-packet atomic on the single head word would
-    // cap the launch at ~100 M atomics/s (2 M packets = 20 ms)
-    const unsigned per_claim = pkt_claim_size(n);
-    for (;;) {
-        unsigned claim = 0;
-        if (lane_id() == 0) {
-            claim = atomicAdd(head, per_claim);
-            if (blockIdx.x == 0 && threadIdx.x == 0 && cancel_relay(cancel, head)) claim = 0xffffffffu;  // interrupted (yk_device.h): the head is poisoned, nobody claims again
-        }
-        claim = uni(claim);
-        if (claim >= n) break;
-        const unsigned claim_end = claim + per_claim < n ? claim + per_claim : n;
-    for (unsigned base = claim; base < claim_end; base += YK_WAVE) {
+    const unsigned n = queue_length(count_ptr, cancel, ray_counter);
+    claim_packets(n, head, cancel, [&](unsigned base) {
         const unsigned idx = base + lane_id();
         const bool valid = idx < n;
-        PktRay r;
-        unsigned negmask = 0;
-        bool alive = false;
+        // rayO == null: the lean camera bounce, all rays start at the camera's origin (yk_device.h, YK_CTRL_CAM_O)
+        const float4 ro = !valid ? make_float4(0, 0, 0, 0) : (rayO ? rayO[idx] : *lean_origin), rd = valid ? rayD[idx] : make_float4(0, 0, 1, 0);
+        TraceRay r = ray_setup(f4_xyz(ro), f4_xyz(rd), __builtin_inff());
+        const bool alive = valid && root_hit(sc, r);
         int best = -1;
-        {
-            // rayO == null: the lean camera bounce, all rays start at the camera's origin (yk_device.h, YK_CTRL_CAM_O)
-            const float4 ro = !valid ? make_float4(0, 0, 0, 0) : (rayO ? rayO[idx] : *lean_origin), rd = valid ? rayD[idx] : make_float4(0, 0, 1, 0);
-            r.o = f4_xyz(ro);
-            r.d = f4_xyz(rd);
-            r.inv = V3{1.0f / r.d.x, 1.0f / r.d.y, 1.0f / r.d.z};
-            negmask = (r.inv.x < 0.0f ? 1u : 0u) | (r.inv.y < 0.0f ? 2u : 0u) | (r.inv.z < 0.0f ? 4u : 0u);
-            r.rt = ray_tri_setup(r.d);
-            r.t_max = __builtin_inff();
-            float tmin;
-            alive = valid && slab(root_lo, root_hi, r.o, r.inv, r.t_max, tmin);
-        }
         unsigned long long remaining = __ballot(alive);
         while (remaining) {
             const int first = __ffsll((long long)remaining) - 1;
-            const unsigned sg = (unsigned)__builtin_amdgcn_readlane((int)negmask, first);
-            const unsigned long long group = __ballot(alive && negmask == sg);
+            const unsigned sg = (unsigned)__builtin_amdgcn_readlane((int)r.negmask, first);
+            const unsigned long long group = __ballot(alive && r.negmask == sg);
             remaining &= ~group;
             pkt_closest_group<SPHERES>(sc, stk, r, best, group, sg);
         }
         if (valid) hit_tri[idx] = best;
-    }
-    }
+    });
 }
 
 // Shadow rays (dense queue); vis[slot] = 2 when occluded (slot_of given) — as k_trace_any_pt.
@@ -250,43 +182,20 @@ __global__ __launch_bounds__(YK_PKT_BLOCK, 8) void k_trace_any_packet(DevScene s
     __shared__ uint4 lds_stack[(YK_PKT_BLOCK / YK_WAVE) * YK_PKT_STACK];
     PktStack stk;
     stk.base = lds_stack + (threadIdx.x / YK_WAVE) * YK_PKT_STACK;
-    const unsigned n = cancel_raised(cancel) ? 0u : *count_ptr;
-    if (shadow_counter && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(shadow_counter, (unsigned long long)n);
-    const V3 root_lo = V3{sc.root_bmin[0], sc.root_bmin[1], sc.root_bmin[2]}, root_hi = V3{sc.root_bmax[0], sc.root_bmax[1], sc.root_bmax[2]};
-    const unsigned per_claim = pkt_claim_size(n);
-    for (;;) {
-        unsigned claim = 0;
-        if (lane_id() == 0) {
-            claim = atomicAdd(head, per_claim);
-            if (blockIdx.x == 0 && threadIdx.x == 0 && cancel_relay(cancel, head)) claim = 0xffffffffu;  // interrupted (yk_device.h): the head is poisoned, nobody claims again
-        }
-        claim = uni(claim);
-        if (claim >= n) break;
-        const unsigned claim_end = claim + per_claim < n ? claim + per_claim : n;
-    for (unsigned base = claim; base < claim_end; base += YK_WAVE) {
+    const unsigned n = queue_length(count_ptr, cancel, shadow_counter);
+    claim_packets(n, head, cancel, [&](unsigned base) {
         const unsigned k = base + lane_id();
         const bool valid = k < n;
-        PktRay r;
-        int area_light = -1;
-        unsigned slot = 0, negmask = 0;
-        bool alive = false, occluded = false;
-        {
-            const float4 ro = valid ? shO[k] : make_float4(0, 0, 0, 0), rd = valid ? shD[k] : make_float4(0, 0, 1, 0);
-            r.o = f4_xyz(ro);
-            r.d = f4_xyz(rd);
-            r.inv = V3{1.0f / r.d.x, 1.0f / r.d.y, 1.0f / r.d.z};
-            negmask = (r.inv.x < 0.0f ? 1u : 0u) | (r.inv.y < 0.0f ? 2u : 0u) | (r.inv.z < 0.0f ? 4u : 0u);
-            r.rt = ray_tri_setup(r.d);
-            r.t_max = ro.w;
-            area_light = (int)__float_as_uint(rd.w);
-            slot = valid ? (slot_of ? slot_of[k] : k) : 0u;
-            float tmin;
-            alive = valid && slab(root_lo, root_hi, r.o, r.inv, r.t_max, tmin);
-        }
+        const float4 ro = valid ? shO[k] : make_float4(0, 0, 0, 0), rd = valid ? shD[k] : make_float4(0, 0, 1, 0);
+        const TraceRay r = ray_setup(f4_xyz(ro), f4_xyz(rd), ro.w);
+        const int area_light = (int)__float_as_uint(rd.w);
+        const unsigned slot = valid ? (slot_of ? slot_of[k] : k) : 0u;
+        const bool alive = valid && root_hit(sc, r);
+        bool occluded = false;
         unsigned long long cmask = __ballot(alive);
         if (cmask) {
             // visiting order only affects how soon occluders are found: follow the first lane's signs
-            const unsigned sg = (unsigned)__builtin_amdgcn_readlane((int)negmask, __ffsll((long long)cmask) - 1);
+            const unsigned sg = (unsigned)__builtin_amdgcn_readlane((int)r.negmask, __ffsll((long long)cmask) - 1);
             unsigned cur = sc.root_ref;
             int sp = 0;
             for (;;) {
@@ -295,29 +204,15 @@ __global__ __launch_bounds__(YK_PKT_BLOCK, 8) void k_trace_any_packet(DevScene s
                     unsigned prim = cur & ~YK_LEAF_BIT;
                     for (;;) {
                         cf4* tq = as_const(sc.tris + 3 * prim);
-                const float4 v0 = ldc(tq, 0), v1 = ldc(tq, 1), v2 = ldc(tq, 2);
-                        const unsigned pflags = __float_as_uint(v2.w);
-                        if (in_mask(cmask) && !occluded) {
-                            TriHit h;
-                            bool got;
-                            if (SPHERES && (pflags & YK_PRIM_SPHERE)) {
-                                V3 ro, rd;
-                                got = sphere_hit_t(sc.spheres[__float_as_uint(v1.w) - sc.n_triangles], r.o, r.d, r.t_max, h.t, ro, rd);
-                            } else {
-                                got = tri_intersect(r.o, r.rt, r.t_max, f4_xyz(v0), f4_xyz(v1), f4_xyz(v2), h);
-                            }
-                            if (got) {
-                                // bvh.rs:269-280: the sampled area light's own surface does not occlude
-                                const int prim_light = (int)__float_as_uint(v0.w);
-                                if (!(area_light >= 0 && prim_light >= 0 && prim_light == area_light)) occluded = true;
-                            }
-                        }
-                        if (pflags & YK_PRIM_LAST) break;
+                        const float4 v0 = ldc(tq, 0), v1 = ldc(tq, 1), v2 = ldc(tq, 2);
+                        TriHit h;
+                        if (in_mask(cmask) && !occluded && prim_hit<SPHERES>(sc, r, v0, v1, v2, h) && occludes(v0, area_light)) occluded = true;
+                        if (__float_as_uint(v2.w) & YK_PRIM_LAST) break;
                         ++prim;
                     }
                     need_pop = true;
                 } else {
-                    const PktNode nb = pkt_load_node(sc.nodes, cur);
+                    const NodeBoxes nb = load_node_uniform(sc.nodes, cur);
                     const bool mine = in_mask(cmask) && !occluded;
                     float t0, t1;
                     const bool h0 = mine && slab(nb.lo0, nb.hi0, r.o, r.inv, r.t_max, t0);
@@ -369,8 +264,7 @@ __global__ __launch_bounds__(YK_PKT_BLOCK, 8) void k_trace_any_packet(DevScene s
             else if (!slot_of)
                 vis[slot] = 0;
         }
-    }
-    }
+    });
 }
 
 unsigned packet_blocks_per_cu() { return 8u; }

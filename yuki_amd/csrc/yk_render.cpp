@@ -164,11 +164,7 @@ void run_bounces(yk_context* ctx, WorkSet& ws, hipStream_t st, const yk_scene* s
         if (packet)
             launch_trace_closest_packet(st, pg, ds, lean_origin ? nullptr : pc.rayO, pc.rayD, bc, bc + YK_CTRL_HEAD, ws.hit.as<int>(), counters, lean_origin, prm.cancel);
         else {
-            unsigned* head = bc + YK_CTRL_HEAD;
-#ifdef YK_EXPERIMENT_XCD
-            head = yk_exp::sorter().heads(st, 0);
-#endif
-            launch_trace_closest(st, tg, ds, pc.rayO, pc.rayD, nullptr, bc, head, ws.hit.as<int>(), nullptr, nullptr,
+            launch_trace_closest(st, tg, ds, pc.rayO, pc.rayD, nullptr, bc, bc + YK_CTRL_HEAD, ws.hit.as<int>(), nullptr, nullptr,
                                  ws.spill.as<uint2>(), spill_stride, errblk, counters, prm.cancel.host);
         }
         kt.end(e, 0, st);
@@ -191,12 +187,8 @@ void run_bounces(yk_context* ctx, WorkSet& ws, hipStream_t st, const yk_scene* s
             launch_trace_any_packet(sb, pg_any, ds, ws.shO.as<float4>(), ws.shD.as<float4>(), ws.shq.as<unsigned>(), bc + YK_CTRL_SHQ,
                                     bc + YK_CTRL_HEAD + 1, ws.vis.as<unsigned char>(), counters + 1, prm.cancel);
         } else {
-            unsigned* any_head = bc + YK_CTRL_HEAD + 1;
-#ifdef YK_EXPERIMENT_XCD
-            any_head = yk_exp::sorter().heads(sb, 1);
-#endif
             launch_trace_any(sb, tg_any, ds, ws.shO.as<float4>(), ws.shD.as<float4>(), ws.shq.as<unsigned>(), bc + YK_CTRL_SHQ,
-                             any_head, ws.vis.as<unsigned char>(), any_spill, spill_stride, errblk, counters + 1, prm.cancel.host);
+                             bc + YK_CTRL_HEAD + 1, ws.vis.as<unsigned char>(), any_spill, spill_stride, errblk, counters + 1, prm.cancel.host);
             if (split && n_shadow_launches) ++*n_shadow_launches;
             if (split)  // rays converging on a point / spot / distant light: wave packets
                 launch_trace_any_packet(sb, pg_any, ds, ws.shO2.as<float4>(), ws.shD2.as<float4>(), ws.shq2.as<unsigned>(), bc + YK_CTRL_SHQ2,

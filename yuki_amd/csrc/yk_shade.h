@@ -21,6 +21,23 @@ struct PathVertex {
     V3 wo;
 };
 
+// The sampler state a path carries in PathBuffers: the PCG32 stream (rngs[i]), the next dimension (bits of thru[i].w)
+// and the sample id (bits of rayD[i].w), whose pixel-table entry gives the pixel and the sample index.
+__device__ __forceinline__ SamplerState path_sampler(const RenderParams& prm, const uint32_t* pixel_xy, const uint32_t* sample_index_tab, uint4 rng,
+                                                     uint32_t dimension, uint32_t sid) {
+    SamplerState st;
+    st.rng.state = (u64)rng.x | ((u64)rng.y << 32);
+    st.rng.inc = (u64)rng.z | ((u64)rng.w << 32);
+    st.dimension = dimension;
+    uint32_t pix, ks;  // entry of the pixel table and sample within it (yk_device.h: RenderParams::spe)
+    split_sample_id(sid, prm.spe, pix, ks);
+    const uint32_t xy = pixel_xy[pix];
+    st.px = xy & 0xffffu;
+    st.py = xy >> 16;
+    st.sample_index = (sample_index_tab ? sample_index_tab[pix] : prm.sample_base) + ks;
+    return st;
+}
+
 // the rest of the vertex once v.sf holds the surface: material (with its texture), shading frame, wo
 __device__ __forceinline__ void vertex_setup_material(const DevScene& sc, V3 d, PathVertex& v) {
     v.mat = sc.materials[v.sf.material];

@@ -3,22 +3,21 @@
 //   k_trace_closest_pt / k_trace_any_pt   production kernels: persistent waves,
 //       per-lane ray replacement with software prefetch, wave-uniform choice
 //       between an interior-node step and a leaf step (LDS-staged stacks)
-//   k_trace_closest<STATS> / k_trace_any  plain one-ray-per-lane loops; the STATS
-//       flavour reproduces IntersectionResult's counters (bvh.rs:167-179) for the
-//       BVHIntersections integrator and the parity tests
+//   k_trace_closest<STATS>  plain one-ray-per-lane loop; the STATS flavour reproduces
+//       IntersectionResult's counters (bvh.rs:167-179) for the BVHIntersections
+//       integrator and the parity tests
 //   k_whitted / k_path_debug  one lane per sample: Whitted's recursion, Path::li_debug
 //
-// Both families implement BoundingVolumeHierarchy::intersect (bvh.rs:160-232) and
-// ::any_intersect (bvh.rs:235-302) with the reference's visiting order.
+// All of them implement BoundingVolumeHierarchy::intersect (bvh.rs:160-232) and
+// ::any_intersect (bvh.rs:235-302) with the reference's visiting order, through the
+// node steps below and the rules of yk_traverse.h.
 #include <hip/hip_runtime.h>
 
 #include "yk_device.h"
 #include "yk_geom.h"
 #include "yk_kernels.h"
 #include "yk_shade.h"
-#ifdef YK_EXPERIMENT_XCD
-#include "../../tools/micro/xcd_claim_experiment.h"
-#endif
+#include "yk_traverse.h"
 #include "yk_wave.h"
 
 // build-time tuning knobs of the persistent traversal kernels
@@ -58,90 +57,145 @@ namespace yk {
 #define YK_REF_STACK_CAP 64  // the reference's to_visit_stack (bvh.rs:172-174): binary traversal
 #define YK_STACK_CAP 96      // storage: 64 binary entries can become 96 in the 4-wide traversal
 
-// LDS words are addressed through an address_space(3) pointer so the compiler
-// emits ds_read_b64 / ds_write_b64 (a generic pointer in a struct degrades to
-// flat_load/flat_store, which also ties the access to vmcnt).
-typedef __attribute__((address_space(3))) unsigned long long lds_u64;
-typedef __attribute__((address_space(1))) unsigned long long glb_u64;
-
-template <int BLOCK, int LDS_DEPTH> struct TravStack {
-    lds_u64* lds;    // [LDS_DEPTH][BLOCK], entry = ref | tmin_bits << 32
-    glb_u64* spill;  // [YK_STACK_CAP - LDS_DEPTH][spill_stride]
+// Entry E: unsigned long long = ref | entry distance bits << 32 (closest hit); unsigned = the bare ref (any hit,
+// which never re-tests a deferred box: half the LDS).  The spill buffer is sized for 8-byte entries; 4-byte ones use
+// it as words with the same stride.  LDS words are addressed through an address_space(3) pointer so the compiler
+// emits ds_read / ds_write (a generic pointer in a struct degrades to flat_load/flat_store, which also ties the
+// access to vmcnt).
+template <int BLOCK, int LDS_DEPTH, class E> struct TravStack {
+    typedef __attribute__((address_space(3))) E lds_e;
+    typedef __attribute__((address_space(1))) E glb_e;
+    lds_e* lds;    // [LDS_DEPTH][BLOCK]
+    glb_e* spill;  // [YK_STACK_CAP - LDS_DEPTH][spill_stride]
     unsigned spill_stride, gtid;
     __device__ __forceinline__ void push(int sp, unsigned ref, float tmin) {
-        unsigned long long e = (unsigned long long)ref | ((unsigned long long)__float_as_uint(tmin) << 32);
+        const E e = sizeof(E) == 8 ? (E)((unsigned long long)ref | ((unsigned long long)__float_as_uint(tmin) << 32)) : (E)ref;
         if (sp < LDS_DEPTH)
             lds[sp * BLOCK + threadIdx.x] = e;
         else
             spill[(size_t)(sp - LDS_DEPTH) * spill_stride + gtid] = e;
     }
-    __device__ __forceinline__ uint2 at(int sp) const {
-        unsigned long long e;
-        if (sp < LDS_DEPTH)
-            e = lds[sp * BLOCK + threadIdx.x];
-        else
-            e = spill[(size_t)(sp - LDS_DEPTH) * spill_stride + gtid];
-        return make_uint2((unsigned)e, (unsigned)(e >> 32));
-    }
-};
-
-// any-hit traversal never re-tests a deferred box, so its stack holds bare refs: half the LDS
-typedef __attribute__((address_space(3))) unsigned lds_u32;
-typedef __attribute__((address_space(1))) unsigned glb_u32;
-template <int BLOCK, int LDS_DEPTH> struct TravStack32 {
-    lds_u32* lds;    // [LDS_DEPTH][BLOCK]
-    glb_u32* spill;  // [YK_STACK_CAP - LDS_DEPTH][spill_stride] (the 8-byte-entry spill buffer, used as words)
-    unsigned spill_stride, gtid;
-    __device__ __forceinline__ void push(int sp, unsigned ref) {
-        if (sp < LDS_DEPTH)
-            lds[sp * BLOCK + threadIdx.x] = ref;
-        else
-            spill[(size_t)(sp - LDS_DEPTH) * spill_stride + gtid] = ref;
-    }
-    __device__ __forceinline__ unsigned at(int sp) const {
+    __device__ __forceinline__ E at(int sp) const {
         return sp < LDS_DEPTH ? lds[sp * BLOCK + threadIdx.x] : spill[(size_t)(sp - LDS_DEPTH) * spill_stride + gtid];
     }
 };
-
-struct NodeBoxes {
-    V3 lo0, hi0, lo1, hi1;
-    unsigned ref0, ref1, axis;
+// `lds`: the kernel's __shared__ E[LDS_DEPTH * BLOCK]
+template <int BLOCK, int LDS_DEPTH, class E>
+__device__ __forceinline__ TravStack<BLOCK, LDS_DEPTH, E> make_stack(E* lds, uint2* spill, unsigned spill_stride) {
+    typedef TravStack<BLOCK, LDS_DEPTH, E> S;
+    S s;
+    s.lds = (typename S::lds_e*)lds;
+    s.spill = (typename S::glb_e*)spill;
+    s.spill_stride = spill_stride;
+    s.gtid = blockIdx.x * BLOCK + threadIdx.x;
+    return s;
+}
+// A push onto a full stack flags the overflow (the host reports YK_ERR_STACK_OVERFLOW), empties the stack and returns false.
+template <int CAP, class Stack>
+__device__ __forceinline__ bool push_capped(Stack& stk, int& sp, unsigned ref, float tmin, unsigned* err) {
+    if (sp >= CAP) {
+        atomicOr(err, 1u);
+        sp = 0;
+        return false;
+    }
+    stk.push(sp, ref, tmin);
+    ++sp;
+    return true;
+}
+// IntersectionResult's counters (bvh.rs:167-179); the traversal functions take a null pointer when nothing is counted
+struct TraceStats {
+    unsigned node_tests, node_hits, shape_tests;
 };
-__device__ __forceinline__ NodeBoxes load_node(const DevNode* nodes, unsigned idx) {
-    const float4* q = reinterpret_cast<const float4*>(nodes + idx);
-    float4 a = q[0], b = q[1], c = q[2];
-    uint2 d = reinterpret_cast<const uint2*>(q)[6];  // only 56 of the node's 64 bytes are fetched
-    NodeBoxes n;
-    n.lo0 = V3{a.x, a.y, a.z};
-    n.hi0 = V3{a.w, b.x, b.y};
-    n.lo1 = V3{b.z, b.w, c.x};
-    n.hi1 = V3{c.y, c.z, c.w};
-    n.ref0 = d.x;
-    n.ref1 = d.y & ~YK_AXIS_MASK;
-    n.axis = (d.y >> YK_AXIS_SHIFT) & 3u;
-    return n;
+// Closest hit: pops until an entry whose entry distance still satisfies tmin <= t_max (the reference's test at pop time).
+template <bool STATS, class Stack>
+__device__ __forceinline__ bool pop_closest(Stack& stk, int& sp, float t_max, unsigned& cur, TraceStats* stats) {
+    while (sp > 0) {
+        --sp;
+        const unsigned long long e = stk.at(sp);
+        if (STATS) stats->node_tests += 1;
+        if (__uint_as_float((unsigned)(e >> 32)) <= t_max) {
+            if (STATS) stats->node_hits += 1;
+            cur = (unsigned)e;
+            return true;
+        }
+    }
+    return false;
+}
+template <class Stack> __device__ __forceinline__ bool pop_any(Stack& stk, int& sp, unsigned& cur) {
+    if (sp == 0) return false;
+    --sp;
+    cur = (unsigned)stk.at(sp);
+    return true;
 }
 
 // the first tree levels live in LDS (YK_TOP_BIT refs): a block copies them once
-typedef __attribute__((address_space(3))) float4 lds_f4;
-__device__ __forceinline__ NodeBoxes load_node_lds(const float4* top, unsigned idx) {
-    const float4* q = top + 4 * idx;
-    float4 a = q[0], b = q[1], c = q[2];
-    uint2 d = reinterpret_cast<const uint2*>(q)[6];  // only 56 of the node's 64 bytes are fetched
-    NodeBoxes n;
-    n.lo0 = V3{a.x, a.y, a.z};
-    n.hi0 = V3{a.w, b.x, b.y};
-    n.lo1 = V3{b.z, b.w, c.x};
-    n.hi1 = V3{c.y, c.z, c.w};
-    n.ref0 = d.x;
-    n.ref1 = d.y & ~YK_AXIS_MASK;
-    n.axis = (d.y >> YK_AXIS_SHIFT) & 3u;
-    return n;
-}
 template <int BLOCK> __device__ __forceinline__ void fill_top(float4* lds_top, const DevNode* top_nodes, unsigned n_top) {
     const float4* src = reinterpret_cast<const float4*>(top_nodes);
     for (unsigned i = threadIdx.x; i < n_top * 4u; i += BLOCK) lds_top[i] = src[i];
     __syncthreads();
+}
+__device__ __forceinline__ NodeBoxes load_node(const float4* lds_top, const DevNode* nodes, unsigned ref) {
+    return (ref & YK_TOP_BIT) ? load_node_lds((lf4*)lds_top, ref & ~YK_TOP_BIT) : load_node(nodes, ref);
+}
+
+// ---- 2-wide node steps
+// What a step leaves: STEP_ENTER, `cur` is the child entered now; STEP_POP, the ray goes on with a pop; STEP_OVERFLOW,
+// a push overflowed (flagged, the stack emptied; `cur` is the near child when it was entered).  The persistent kernels
+// go on with the near child, the one-lane loops end the ray.
+enum StepEnd { STEP_POP, STEP_ENTER, STEP_OVERFLOW };
+// Closest hit with the reference's visiting order (near child first by the sign of the direction along the split
+// axis, far child deferred).  The box of a deferred child is evaluated when its parent is visited — against a
+// slightly relaxed bound, because a tie hit can raise t_max by a few ulps (deferred_t_max, yk_geom.h) — and completed
+// at pop time by the exact `tmin <= t_max`, which is the reference's test at pop time (DESIGN.md §traversal
+// equivalence).  A child entered right away gets the exact bound.  STATS counts the near child's test and pushes the
+// far child even when its box is missed, so that its test is counted when it is popped, as the reference does.
+template <bool STATS, class Stack>
+__device__ __forceinline__ StepEnd node2_closest(const NodeBoxes& nb, const TraceRay& r, Stack& stk, int& sp, unsigned& cur, unsigned* err, TraceStats* stats) {
+    float t0, t1;
+    const float t_def = deferred_t_max(r.t_max);
+    const bool h0 = slab(nb.lo0, nb.hi0, r.o, r.inv, t_def, t0);
+    const bool h1 = slab(nb.lo1, nb.hi1, r.o, r.inv, t_def, t1);
+    const bool swap = (r.negmask >> nb.axis) & 1u;
+    const unsigned near_ref = swap ? nb.ref1 : nb.ref0, far_ref = swap ? nb.ref0 : nb.ref1;
+    const bool near_hit = (swap ? h1 : h0) && (swap ? t1 : t0) <= r.t_max, far_hit = swap ? h0 : h1;
+    const float far_t = swap ? t0 : t1;
+    bool pushed = true;
+    if (STATS) {
+        stats->node_tests += 1;
+        if (near_hit) stats->node_hits += 1;
+        pushed = push_capped<YK_REF_STACK_CAP>(stk, sp, far_ref, far_hit ? far_t : __builtin_nanf(""), err);
+    }
+    if (near_hit) {
+        if (!STATS && far_hit) pushed = push_capped<YK_REF_STACK_CAP>(stk, sp, far_ref, far_t, err);
+        cur = near_ref;
+        return pushed ? STEP_ENTER : STEP_OVERFLOW;
+    }
+    if (!pushed) return STEP_OVERFLOW;
+    if (!STATS && far_hit && far_t <= r.t_max) {
+        cur = far_ref;
+        return STEP_ENTER;
+    }
+    return STEP_POP;
+}
+// Any hit: the verdict does not depend on the visiting order; near-first finds occluders sooner.
+template <class Stack>
+__device__ __forceinline__ StepEnd node2_any(const NodeBoxes& nb, const TraceRay& r, Stack& stk, int& sp, unsigned& cur, unsigned* err) {
+    float t0, t1;
+    const bool h0 = slab(nb.lo0, nb.hi0, r.o, r.inv, r.t_max, t0);
+    const bool h1 = slab(nb.lo1, nb.hi1, r.o, r.inv, r.t_max, t1);
+    const bool swap = (r.negmask >> nb.axis) & 1u;
+    const unsigned near_ref = swap ? nb.ref1 : nb.ref0, far_ref = swap ? nb.ref0 : nb.ref1;
+    const bool near_hit = swap ? h1 : h0, far_hit = swap ? h0 : h1;
+    if (near_hit) {
+        const bool pushed = !far_hit || push_capped<YK_REF_STACK_CAP>(stk, sp, far_ref, 0.0f, err);
+        cur = near_ref;
+        return pushed ? STEP_ENTER : STEP_OVERFLOW;
+    }
+    if (far_hit) {
+        cur = far_ref;
+        return STEP_ENTER;
+    }
+    return STEP_POP;
 }
 
 // ---- 4-wide node step ------------------------------------------------------------
@@ -160,7 +214,7 @@ struct Step4 {
     unsigned ref[4];
     float t[4];
 };
-__device__ __forceinline__ Step4 node4_step(const DevNode4* nodes, unsigned idx, const V3& o, const V3& inv, float t_max, unsigned negmask) {
+__device__ __forceinline__ Step4 node4_boxes(const DevNode4* nodes, unsigned idx, const V3& o, const V3& inv, float t_max, unsigned negmask) {
     const float4* q = reinterpret_cast<const float4*>(nodes + idx);
     const float4 a0 = q[0], a1 = q[1], a2 = q[2], b0 = q[3], b1 = q[4], b2 = q[5];
     const uint4 refs = reinterpret_cast<const uint4*>(q)[6];
@@ -191,100 +245,77 @@ __device__ __forceinline__ Step4 node4_step(const DevNode4* nodes, unsigned idx,
 #undef YK_CSWAP
     return s;
 }
-
-// Closest hit with the reference's visiting order (near child first by the sign
-// of the direction along the split axis, far child deferred, leaves in shape
-// order, a later hit with t == t_max replaces the earlier one).  The box of a
-// deferred child is evaluated when its parent is visited — against a slightly
-// relaxed bound, because a tie hit can raise t_max by a few ulps (deferred_t_max,
-// yk_geom.h) — and completed at pop time by the exact `tmin <= t_max`, which is the
-// reference's test at pop time (DESIGN.md §traversal equivalence).
-template <int BLOCK, int LDS_DEPTH, bool STATS>
-__device__ __forceinline__ void traverse_closest(const DevScene& sc, V3 o, V3 d, float t_max_in, TravStack<BLOCK, LDS_DEPTH>& stk, int& out_tri,
-                                                 TriHit& out_hit, unsigned& node_tests, unsigned& node_hits, unsigned& shape_tests,
-                                                 unsigned* err) {
-    V3 inv = V3{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
-    bool neg[3] = {inv.x < 0.0f, inv.y < 0.0f, inv.z < 0.0f};
-    RayTri rt = ray_tri_setup(d);
-    float t_max = t_max_in;
-    out_tri = -1;
-    int sp = 0;
-    float tmin;
-    if (STATS) node_tests += 1;
-    if (!slab(V3{sc.root_bmin[0], sc.root_bmin[1], sc.root_bmin[2]}, V3{sc.root_bmax[0], sc.root_bmax[1], sc.root_bmax[2]}, o, inv, t_max, tmin)) return;
-    if (STATS) node_hits += 1;
-    unsigned cur = sc.root_ref;
-    for (;;) {
-        if (!(cur & YK_LEAF_BIT)) {
-            NodeBoxes nb = load_node(sc.nodes, cur);
-            float t0, t1;
-            const float t_def = deferred_t_max(t_max);
-            bool h0 = slab(nb.lo0, nb.hi0, o, inv, t_def, t0);
-            bool h1 = slab(nb.lo1, nb.hi1, o, inv, t_def, t1);
-            bool swap = neg[nb.axis];
-            unsigned near_ref = swap ? nb.ref1 : nb.ref0, far_ref = swap ? nb.ref0 : nb.ref1;
-            // the near child is entered now: exact bound; the far child is deferred: relaxed now, exact at pop
-            bool near_hit = (swap ? h1 : h0) && (swap ? t1 : t0) <= t_max, far_hit = swap ? h0 : h1;
-            float far_t = swap ? t0 : t1;
-            if (STATS) {
-                node_tests += 1;  // the near child is tested right away; the far one is counted when popped
-                if (near_hit) node_hits += 1;
-            }
-            if (STATS || far_hit) {
-                // with STATS the far child is pushed even when its box is missed so
-                // that the test is counted at pop time like the reference does
-                if (sp >= YK_REF_STACK_CAP) {
-                    atomicOr(err, 1u);
-                    return;
-                }
-                stk.push(sp, far_ref, far_hit ? far_t : __builtin_nanf(""));
-                ++sp;
-            }
-            if (near_hit) {
-                cur = near_ref;
-                continue;
-            }
-        } else {
-            unsigned prim = cur & ~YK_LEAF_BIT;
-            for (;;) {
-                float4 v0 = sc.tris[3 * prim], v1 = sc.tris[3 * prim + 1], v2 = sc.tris[3 * prim + 2];
-                const unsigned pflags = __float_as_uint(v2.w);
-                TriHit h = TriHit{0.0f, 0.0f, 0.0f, 0.0f};
-                if (STATS) shape_tests += 1;
-                bool got;
-                if (pflags & YK_PRIM_SPHERE) {
-                    V3 ro, rd;
-                    got = sphere_hit_t(sc.spheres[__float_as_uint(v1.w) - sc.n_triangles], o, d, t_max, h.t, ro, rd);
-                } else {
-                    got = tri_intersect(o, rt, t_max, f4_xyz(v0), f4_xyz(v1), f4_xyz(v2), h);
-                }
-                if (got) {
-                    out_hit = h;
-                    out_tri = (int)__float_as_uint(v1.w);
-                    t_max = h.t;
-                }
-                if (pflags & YK_PRIM_LAST) break;
-                ++prim;
-            }
+// The first hit slot is entered now and the later ones are pushed, last first.  Closest hit: boxes are screened with the
+// relaxed bound, and the first slot (in visiting order) that passes the exact bound is the one entered; slots before it
+// fail now as they would in the reference (t_max cannot change before they are tested), the later ones are deferred:
+// exact when popped (yk_geom.h).
+template <bool CLOSEST, class Stack>
+__device__ __forceinline__ bool node4_step(const DevNode4* nodes, const TraceRay& r, Stack& stk, int& sp, unsigned& cur, unsigned* err) {
+    Step4 st = node4_boxes(nodes, cur, r.o, r.inv, CLOSEST ? deferred_t_max(r.t_max) : r.t_max, r.negmask);
+    if (CLOSEST) {
+        bool entered = false;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const bool exact = st.ref[k] != YK_REF_NONE && st.t[k] <= r.t_max;
+            if (!entered && !exact) st.ref[k] = YK_REF_NONE;
+            entered = entered || exact;
         }
-        // pop
-        bool found = false;
-        while (sp > 0) {
-            --sp;
-            uint2 e = stk.at(sp);
-            float et = __uint_as_float(e.y);
-            if (STATS) node_tests += 1;
-            if (et <= t_max) {
-                if (STATS) node_hits += 1;
-                cur = e.x;
-                found = true;
-                break;
-            }
-        }
-        if (!found) return;
     }
+    unsigned next = YK_REF_NONE;
+    float next_t = 0.0f;
+#pragma unroll
+    for (int k = 3; k >= 0; --k) {
+        if (st.ref[k] != YK_REF_NONE) {
+            if (next != YK_REF_NONE) push_capped<YK_STACK_CAP>(stk, sp, next, next_t, err);
+            next = st.ref[k];
+            next_t = st.t[k];
+        }
+    }
+    if (next == YK_REF_NONE) return false;
+    cur = next;  // no leaf was visited since the test: its result is final
+    return true;
 }
 
+// ---- one-lane loops (k_trace_closest<STATS>, k_whitted, k_path_debug): out_tri = the source shape hit, or -1
+template <bool STATS, class Stack>
+__device__ __forceinline__ void traverse_closest(const DevScene& sc, TraceRay r, Stack& stk, int& out_tri, TriHit& out_hit, TraceStats* stats, unsigned* err) {
+    out_tri = -1;
+    if (STATS) stats->node_tests += 1;
+    if (!root_hit(sc, r)) return;
+    if (STATS) stats->node_hits += 1;
+    unsigned cur = sc.root_ref;
+    int sp = 0;
+    for (;;) {
+        if (!(cur & YK_LEAF_BIT)) {
+            const StepEnd e = node2_closest<STATS>(load_node(sc.nodes, cur), r, stk, sp, cur, err, stats);
+            if (e == STEP_ENTER) continue;
+            if (e == STEP_OVERFLOW) return;
+        } else {
+            leaf_closest<true, false, STATS>(sc, cur & ~YK_LEAF_BIT, true, r, STATS ? &stats->shape_tests : nullptr, [&](unsigned, float4 v1, unsigned, const TriHit& h) {
+                out_hit = h;
+                out_tri = (int)__float_as_uint(v1.w);
+            });
+        }
+        if (!pop_closest<STATS>(stk, sp, r.t_max, cur, stats)) return;
+    }
+}
+// true = occluded
+template <class Stack>
+__device__ __forceinline__ bool traverse_any(const DevScene& sc, const TraceRay& r, int area_light, Stack& stk, unsigned* err) {
+    if (!root_hit(sc, r)) return false;
+    unsigned cur = sc.root_ref;
+    int sp = 0;
+    for (;;) {
+        if (!(cur & YK_LEAF_BIT)) {
+            const StepEnd e = node2_any(load_node(sc.nodes, cur), r, stk, sp, cur, err);
+            if (e == STEP_ENTER) continue;
+            if (e == STEP_OVERFLOW) return false;
+        } else if (leaf_any<true>(sc, cur & ~YK_LEAF_BIT, r, area_light)) {
+            return true;
+        }
+        if (!pop_any(stk, sp, cur)) return false;
+    }
+}
 
 // ------------------------------------------------------------------ persistent-thread traversal
 // A wave owns 64 ray slots.  Work arrives in CHUNK-sized index ranges claimed with
@@ -300,48 +331,14 @@ __device__ __forceinline__ void traverse_closest(const DevScene& sc, V3 o, V3 d,
 // lanes (lane utilisation of the plain loop: 26 %, profiles/r01_a_pmc_summary.json).
 // Per-ray arithmetic and visiting order are exactly those of traverse_closest /
 // traverse_any above.
-struct LaneRay {
-    V3 o, inv, d;
-    RayTri rt;
-    float t_max;
-    unsigned negmask;
-};
-
-__device__ __forceinline__ void lane_ray_setup(LaneRay& r, V3 o, V3 d, float t_max) {
-    r.o = o;
-    r.d = d;
-    r.inv = V3{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
-    r.negmask = (r.inv.x < 0.0f ? 1u : 0u) | (r.inv.y < 0.0f ? 2u : 0u) | (r.inv.z < 0.0f ? 4u : 0u);
-    r.rt = ray_tri_setup(d);
-    r.t_max = t_max;
-}
-
-// pops until an entry whose stored entry distance still satisfies tmin <= t_max
-template <int BLOCK, int LDS_DEPTH> __device__ __forceinline__ bool pop_closest(TravStack<BLOCK, LDS_DEPTH>& stk, int& sp, float t_max, unsigned& cur) {
-    while (sp > 0) {
-        --sp;
-        uint2 e = stk.at(sp);
-        if (__uint_as_float(e.y) <= t_max) {
-            cur = e.x;
-            return true;
-        }
-    }
-    return false;
-}
 
 // Wave-local work distribution: claims CHUNK indices at a time from *head.
 struct ChunkCursor {
     unsigned cur, end;  // wave-uniform
     bool exhausted, took_share;
-#ifdef YK_EXPERIMENT_XCD
-    unsigned xcd_step;  // ranges this wave has found drained
-#endif
     __device__ __forceinline__ void init() {
         cur = end = 0;
         exhausted = took_share = false;
-#ifdef YK_EXPERIMENT_XCD
-        xcd_step = 0;
-#endif
     }
     // hands `want` lanes consecutive indices; returns the index of this lane or
     // 0xffffffff.  All lanes of the wave call it (converged).
@@ -371,9 +368,6 @@ struct ChunkCursor {
             } else {
                 chunk = (unsigned)CHUNK;
                 base = 0;
-#ifdef YK_EXPERIMENT_XCD  // timing builds only (tools/micro/xcd_claim_experiment.h): XCD-affine claims
-                YK_XCD_CLAIM
-#endif
                 if (lane_id() == 0) {
                     base = atomicAdd(head, chunk);
                     if (blockIdx.x == 0 && threadIdx.x == 0 && cancel_relay(cancel, head)) base = 0xffffffffu;
@@ -386,9 +380,6 @@ struct ChunkCursor {
             }
             cur = base;
             end = base + chunk < n ? base + chunk : n;
-#ifdef YK_EXPERIMENT_XCD
-        claimed:;
-#endif
         }
         unsigned rank = (unsigned)__popcll(mask & ((1ull << lane_id()) - 1ull));
         unsigned idx = cur + rank;
@@ -398,40 +389,16 @@ struct ChunkCursor {
     }
 };
 
-template <int BLOCK, int LDS_DEPTH, int PF_MIN, int START_MIN, int LEAF_MIN, int CHUNK, bool SPHERES, bool API, bool WIDE>
-__global__ __launch_bounds__(BLOCK, TRACE_MIN_WAVES) void k_trace_closest_pt(DevScene sc, const float4* __restrict__ rayO, const float4* __restrict__ rayD,
-                                                            const float* __restrict__ t_max_opt, const unsigned* count_ptr, unsigned* head,
-                                                            int* __restrict__ hit_tri, float4* __restrict__ hit_out, uint2* spill,
-                                                            unsigned spill_stride, unsigned* ctrl, unsigned long long* ray_counter, const unsigned* cancel_host) {
-    __shared__ unsigned long long lds_stack[LDS_DEPTH * BLOCK];
-    __shared__ float4 lds_top[WIDE ? 1 : TRACE_TOP * 4];
-    if (!WIDE) fill_top<BLOCK>(lds_top, sc.top_nodes, sc.n_top);
-    TravStack<BLOCK, LDS_DEPTH> stk;
-    stk.lds = (lds_u64*)lds_stack;
-    stk.spill = (glb_u64*)spill;
-    stk.spill_stride = spill_stride;
-    stk.gtid = blockIdx.x * BLOCK + threadIdx.x;
-    const CancelRef cancel = CancelRef{cancel_host, cancel_host ? ctrl + YK_CTRL_CANCELLED : nullptr};  // render loop: ctrl is the context's error block
-    const unsigned n = cancel_raised(cancel) ? 0u : *count_ptr;
-    if (ray_counter && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(ray_counter, (unsigned long long)n);
-    const unsigned root = WIDE ? 0u : (sc.n_top ? YK_TOP_BIT : sc.root_ref);
-    const V3 root_lo = V3{sc.root_bmin[0], sc.root_bmin[1], sc.root_bmin[2]}, root_hi = V3{sc.root_bmax[0], sc.root_bmax[1], sc.root_bmax[2]};
-
+// The loop both persistent kernels run; they supply the per-ray parts: prefetch(idx) loads queue entry idx into the
+// lane's prefetch registers, start() begins the prefetched ray (false: it missed the root box and is done), and
+// node_step() / leaf_step() advance a ray standing on an interior node / a leaf (false: the ray is done).  `cur` is the
+// lane's current ref.
+template <int PF_MIN, int START_MIN, int LEAF_MIN, int CHUNK, class Prefetch, class Start, class NodeStep, class LeafStep>
+__device__ __forceinline__ void persistent_rays(unsigned n, unsigned* head, const CancelRef& cancel, const unsigned& cur, Prefetch prefetch, Start start,
+                                                NodeStep node_step, LeafStep leaf_step) {
     ChunkCursor work;
     work.init();
     bool active = false, pf_valid = false;
-    float4 pf_o = make_float4(0, 0, 0, 0), pf_d = make_float4(0, 0, 1, 0);
-    float pf_t = 0.0f;
-    unsigned pf_idx = 0;
-    LaneRay r;
-    r.o = r.inv = r.d = V3{0, 0, 0};
-    r.rt = RayTri{0, 1, 2, 0, 0, 0};
-    r.t_max = 0.0f;
-    r.negmask = 0;
-    unsigned ray_i = 0, cur = 0;
-    int sp = 0, best = -1;
-    TriHit best_hit = TriHit{0, 0, 0, 0};
-
     for (;;) {
         // ---- start prefetched rays once START_MIN lanes are idle (the setup code —
         // six IEEE divisions and the root test — runs divergently, so it is batched)
@@ -439,30 +406,15 @@ __global__ __launch_bounds__(BLOCK, TRACE_MIN_WAVES) void k_trace_closest_pt(Dev
         const bool go = (unsigned)__popcll(__ballot(startable)) >= (unsigned)START_MIN || !__any(active);
         if (go && startable) {
             pf_valid = false;
-            lane_ray_setup(r, f4_xyz(pf_o), f4_xyz(pf_d), API ? pf_t : __builtin_inff());
-            ray_i = pf_idx;
-            float tmin;
-            if (slab(root_lo, root_hi, r.o, r.inv, r.t_max, tmin)) {
-                active = true;
-                cur = root;
-                sp = 0;
-                best = -1;
-            } else {
-                hit_tri[ray_i] = -1;
-            }
+            active = start();
         }
         // ---- top up the prefetch registers (loads are consumed in a later iteration)
-        {
-            unsigned n_need = (unsigned)__popcll(__ballot(!pf_valid));
-            if (!work.exhausted && (n_need >= (unsigned)PF_MIN || !__any(active))) {
-                unsigned idx = work.take<CHUNK>(!pf_valid, n, head, cancel);
-                if (idx != 0xffffffffu) {
-                    pf_o = rayO[idx];
-                    pf_d = rayD[idx];
-                    pf_t = (API && t_max_opt) ? t_max_opt[idx] : __builtin_inff();
-                    pf_idx = idx;
-                    pf_valid = true;
-                }
+        const unsigned n_need = (unsigned)__popcll(__ballot(!pf_valid));
+        if (!work.exhausted && (n_need >= (unsigned)PF_MIN || !__any(active))) {
+            const unsigned idx = work.take<CHUNK>(!pf_valid, n, head, cancel);
+            if (idx != 0xffffffffu) {
+                prefetch(idx);
+                pf_valid = true;
             }
         }
         if (!__any(active)) {
@@ -474,106 +426,77 @@ __global__ __launch_bounds__(BLOCK, TRACE_MIN_WAVES) void k_trace_closest_pt(Dev
         const bool on_node = active && !(cur & YK_LEAF_BIT);
         const unsigned n_leaf = (unsigned)__popcll(__ballot(on_leaf));
         if (__any(on_node) && n_leaf < (unsigned)LEAF_MIN) {
-            if (WIDE) {
-                if (on_node) {
-                    Step4 st = node4_step(sc.nodes4, cur, r.o, r.inv, deferred_t_max(r.t_max), r.negmask);
-                    // The first slot (in visiting order) that passes the exact bound is entered right away; slots
-                    // before it fail now as they would in the reference (t_max cannot change before they are
-                    // tested); the later ones are deferred: relaxed here, exact when popped (yk_geom.h).
-                    bool entered = false;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const bool exact = st.ref[k] != YK_REF_NONE && st.t[k] <= r.t_max;
-                        if (!entered && !exact) st.ref[k] = YK_REF_NONE;
-                        entered = entered || exact;
-                    }
-                    // push the later-visited hits (last first)
-                    unsigned next = YK_REF_NONE;
-                    float next_t = 0.0f;
-#pragma unroll
-                    for (int k = 3; k >= 0; --k) {
-                        if (st.ref[k] != YK_REF_NONE) {
-                            if (next != YK_REF_NONE) {
-                                if (sp >= YK_STACK_CAP) {
-                                    atomicOr(ctrl + YK_CTRL_ERR, 1u);
-                                    sp = 0;
-                                } else {
-                                    stk.push(sp, next, next_t);
-                                    ++sp;
-                                }
-                            }
-                            next = st.ref[k];
-                            next_t = st.t[k];
-                        }
-                    }
-                    if (next != YK_REF_NONE) {
-                        cur = next;  // no leaf was visited since the test: its result is final
-                    } else if (!pop_closest(stk, sp, r.t_max, cur)) {
-                        hit_tri[ray_i] = best;
-                        if (API && hit_out) hit_out[ray_i] = make_float4(best_hit.t, best_hit.b0, best_hit.b1, best_hit.b2);
-                        active = false;
-                    }
-                }
-            } else if (on_node) {
-                NodeBoxes nb = (cur & YK_TOP_BIT) ? load_node_lds(lds_top, cur & ~YK_TOP_BIT) : load_node(sc.nodes, cur);
-                YK_EXPERIMENT_NODE(sc.nodes + cur, nb);
-                float t0, t1;
-                const float t_def = deferred_t_max(r.t_max);  // yk_geom.h: a deferred box is screened with a relaxed bound
-                bool h0 = slab(nb.lo0, nb.hi0, r.o, r.inv, t_def, t0);
-                bool h1 = slab(nb.lo1, nb.hi1, r.o, r.inv, t_def, t1);
-                bool swap = (r.negmask >> nb.axis) & 1u;
-                unsigned near_ref = swap ? nb.ref1 : nb.ref0, far_ref = swap ? nb.ref0 : nb.ref1;
-                bool near_hit = (swap ? h1 : h0) && (swap ? t1 : t0) <= r.t_max, far_hit = swap ? h0 : h1;
-                float far_t = swap ? t0 : t1;
-                if (near_hit) {
-                    if (far_hit) {
-                        if (sp >= YK_REF_STACK_CAP) {
-                            atomicOr(ctrl + YK_CTRL_ERR, 1u);
-                            sp = 0;  // abandon this ray; the host reports YK_ERR_STACK_OVERFLOW
-                        } else {
-                            stk.push(sp, far_ref, far_t);
-                            ++sp;
-                        }
-                    }
-                    cur = near_ref;
-                } else if (far_hit && far_t <= r.t_max) {
-                    cur = far_ref;  // entered now (no leaf in between): the exact bound decides
-                } else if (!pop_closest(stk, sp, r.t_max, cur)) {
-                    hit_tri[ray_i] = best;
-                    if (API && hit_out) hit_out[ray_i] = make_float4(best_hit.t, best_hit.b0, best_hit.b1, best_hit.b2);
-                    active = false;
-                }
-            }
+            if (on_node) active = node_step();
         } else if (on_leaf) {
-            unsigned prim = cur & ~YK_LEAF_BIT;
-            for (;;) {
-                float4 v0 = sc.tris[3 * prim], v1 = sc.tris[3 * prim + 1], v2 = sc.tris[3 * prim + 2];
-                const unsigned pflags = __float_as_uint(v2.w);
-                TriHit h = TriHit{0.0f, 0.0f, 0.0f, 0.0f};
-                bool got;
-                if (SPHERES && (pflags & YK_PRIM_SPHERE)) {
-                    V3 ro, rd;
-                    got = sphere_hit_t(sc.spheres[__float_as_uint(v1.w) - sc.n_triangles], r.o, r.d, r.t_max, h.t, ro, rd);
-                } else {
-                    got = tri_intersect(r.o, r.rt, r.t_max, f4_xyz(v0), f4_xyz(v1), f4_xyz(v2), h);
-                }
-                if (got) {
-                    if (API) best_hit = h;
-                    // API callers get the source shape; the render loop gets the leaf-order slot, from
-                    // which k_shade reaches everything it needs in one hop (hit_surface_prim)
-                    best = API ? (int)__float_as_uint(v1.w) : YK_HIT_WORD(prim, pflags);
-                    r.t_max = h.t;
-                }
-                if (pflags & YK_PRIM_LAST) break;
-                ++prim;
-            }
-            if (!pop_closest(stk, sp, r.t_max, cur)) {
-                hit_tri[ray_i] = best;
-                if (API && hit_out) hit_out[ray_i] = make_float4(best_hit.t, best_hit.b0, best_hit.b1, best_hit.b2);
-                active = false;
-            }
+            active = leaf_step();
         }
     }
+}
+
+template <int BLOCK, int LDS_DEPTH, int PF_MIN, int START_MIN, int LEAF_MIN, int CHUNK, bool SPHERES, bool API, bool WIDE>
+__global__ __launch_bounds__(BLOCK, TRACE_MIN_WAVES) void k_trace_closest_pt(DevScene sc, const float4* __restrict__ rayO, const float4* __restrict__ rayD,
+                                                            const float* __restrict__ t_max_opt, const unsigned* count_ptr, unsigned* head,
+                                                            int* __restrict__ hit_tri, float4* __restrict__ hit_out, uint2* spill,
+                                                            unsigned spill_stride, unsigned* ctrl, unsigned long long* ray_counter, const unsigned* cancel_host) {
+    __shared__ unsigned long long lds_stack[LDS_DEPTH * BLOCK];
+    __shared__ float4 lds_top[WIDE ? 1 : TRACE_TOP * 4];
+    if (!WIDE) fill_top<BLOCK>(lds_top, sc.top_nodes, sc.n_top);
+    auto stk = make_stack<BLOCK, LDS_DEPTH>(lds_stack, spill, spill_stride);
+    const CancelRef cancel = CancelRef{cancel_host, cancel_host ? ctrl + YK_CTRL_CANCELLED : nullptr};  // render loop: ctrl is the context's error block
+    const unsigned n = queue_length(count_ptr, cancel, ray_counter);
+    const unsigned root = WIDE ? 0u : (sc.n_top ? YK_TOP_BIT : sc.root_ref);
+    unsigned* err = ctrl + YK_CTRL_ERR;
+
+    float4 pf_o = make_float4(0, 0, 0, 0), pf_d = make_float4(0, 0, 1, 0);
+    float pf_t = 0.0f;
+    unsigned pf_idx = 0, ray_i = 0, cur = 0;
+    TraceRay r = idle_ray();
+    int sp = 0, best = -1;
+    TriHit best_hit = TriHit{0, 0, 0, 0};
+    const auto retire = [&]() {
+        hit_tri[ray_i] = best;
+        if (API && hit_out) hit_out[ray_i] = make_float4(best_hit.t, best_hit.b0, best_hit.b1, best_hit.b2);
+        return false;
+    };
+    persistent_rays<PF_MIN, START_MIN, LEAF_MIN, CHUNK>(
+        n, head, cancel, cur,
+        [&](unsigned idx) {
+            pf_o = rayO[idx];
+            pf_d = rayD[idx];
+            pf_t = (API && t_max_opt) ? t_max_opt[idx] : __builtin_inff();
+            pf_idx = idx;
+        },
+        [&]() {
+            r = ray_setup(f4_xyz(pf_o), f4_xyz(pf_d), API ? pf_t : __builtin_inff());
+            ray_i = pf_idx;
+            if (!root_hit(sc, r)) {
+                hit_tri[ray_i] = -1;
+                return false;
+            }
+            cur = root;
+            sp = 0;
+            best = -1;
+            return true;
+        },
+        [&]() {
+            if (WIDE) {
+                if (node4_step<true>(sc.nodes4, r, stk, sp, cur, err)) return true;
+            } else {
+                const NodeBoxes nb = load_node(lds_top, sc.nodes, cur);
+                YK_EXPERIMENT_NODE(sc.nodes + cur, nb);
+                if (node2_closest<false>(nb, r, stk, sp, cur, err, nullptr) != STEP_POP) return true;  // after an overflow: the near child, an empty stack
+            }
+            return pop_closest<false>(stk, sp, r.t_max, cur, nullptr) || retire();
+        },
+        [&]() {
+            leaf_closest<SPHERES, false, false>(sc, cur & ~YK_LEAF_BIT, true, r, nullptr, [&](unsigned prim, float4 v1, unsigned pflags, const TriHit& h) {
+                if (API) best_hit = h;
+                // API callers get the source shape; the render loop gets the leaf-order slot, from which k_shade reaches
+                // everything it needs in one hop (hit_surface_prim)
+                best = API ? (int)__float_as_uint(v1.w) : YK_HIT_WORD(prim, pflags);
+            });
+            return pop_closest<false>(stk, sp, r.t_max, cur, nullptr) || retire();
+        });
 }
 
 // Shadow rays: shO/shD are dense (compacted by `shade`); slot_of[k] is where the
@@ -586,164 +509,49 @@ __global__ __launch_bounds__(BLOCK, TRACE_MIN_WAVES) void k_trace_any_pt(DevScen
     __shared__ unsigned lds_stack[LDS_DEPTH * BLOCK];
     __shared__ float4 lds_top[WIDE ? 1 : TRACE_ANY_TOP * 4];
     if (!WIDE) fill_top<BLOCK>(lds_top, sc.top_nodes_any, sc.n_top_any);
-    TravStack32<BLOCK, LDS_DEPTH> stk;
-    stk.lds = (lds_u32*)lds_stack;
-    stk.spill = (glb_u32*)spill;
-    stk.spill_stride = spill_stride;
-    stk.gtid = blockIdx.x * BLOCK + threadIdx.x;
+    auto stk = make_stack<BLOCK, LDS_DEPTH>(lds_stack, spill, spill_stride);
     const CancelRef cancel = CancelRef{cancel_host, cancel_host ? ctrl + YK_CTRL_CANCELLED : nullptr};
-    const unsigned n = cancel_raised(cancel) ? 0u : *count_ptr;
-    if (shadow_counter && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(shadow_counter, (unsigned long long)n);
+    const unsigned n = queue_length(count_ptr, cancel, shadow_counter);
     const unsigned root = WIDE ? 0u : (sc.n_top_any ? YK_TOP_BIT : sc.root_ref);
-    const V3 root_lo = V3{sc.root_bmin[0], sc.root_bmin[1], sc.root_bmin[2]}, root_hi = V3{sc.root_bmax[0], sc.root_bmax[1], sc.root_bmax[2]};
+    unsigned* err = ctrl + YK_CTRL_ERR;
 
-    ChunkCursor work;
-    work.init();
-    bool active = false, pf_valid = false;
     float4 pf_o = make_float4(0, 0, 0, 0), pf_d = make_float4(0, 0, 1, 0);
-    unsigned pf_slot = 0;
-    LaneRay r;
-    r.o = r.inv = r.d = V3{0, 0, 0};
-    r.rt = RayTri{0, 1, 2, 0, 0, 0};
-    r.t_max = 0.0f;
-    r.negmask = 0;
-    unsigned slot = 0, cur = 0;
+    unsigned pf_slot = 0, slot = 0, cur = 0;
+    TraceRay r = idle_ray();
     int sp = 0, area_light = -1;
-
-    for (;;) {
-        const bool startable = !active && pf_valid;
-        const bool go = (unsigned)__popcll(__ballot(startable)) >= (unsigned)START_MIN || !__any(active);
-        if (go && startable) {
-            pf_valid = false;
-            lane_ray_setup(r, f4_xyz(pf_o), f4_xyz(pf_d), pf_o.w);
+    const auto unoccluded = [&]() {
+        if (!slot_of) vis[slot] = 0;
+        return false;
+    };
+    persistent_rays<PF_MIN, START_MIN, LEAF_MIN, CHUNK>(
+        n, head, cancel, cur,
+        [&](unsigned k) {
+            pf_o = shO[k];
+            pf_d = shD[k];
+            pf_slot = slot_of ? slot_of[k] : k;
+        },
+        [&]() {
+            r = ray_setup(f4_xyz(pf_o), f4_xyz(pf_d), pf_o.w);
             area_light = (int)__float_as_uint(pf_d.w);
             slot = pf_slot;
-            float tmin;
-            if (slab(root_lo, root_hi, r.o, r.inv, r.t_max, tmin)) {
-                active = true;
-                cur = root;
-                sp = 0;
-            } else if (!slot_of) {
-                vis[slot] = 0;
-            }
-        }
-        {
-            unsigned n_need = (unsigned)__popcll(__ballot(!pf_valid));
-            if (!work.exhausted && (n_need >= (unsigned)PF_MIN || !__any(active))) {
-                unsigned k = work.take<CHUNK>(!pf_valid, n, head, cancel);
-                if (k != 0xffffffffu) {
-                    pf_o = shO[k];
-                    pf_d = shD[k];
-                    pf_slot = slot_of ? slot_of[k] : k;
-                    pf_valid = true;
-                }
-            }
-        }
-        if (!__any(active)) {
-            if (work.exhausted && !__any(pf_valid)) break;
-            continue;
-        }
-        const bool on_leaf = active && (cur & YK_LEAF_BIT);
-        const bool on_node = active && !(cur & YK_LEAF_BIT);
-        const unsigned n_leaf = (unsigned)__popcll(__ballot(on_leaf));
-        if (__any(on_node) && n_leaf < (unsigned)LEAF_MIN) {
-            if (WIDE) {
-                if (on_node) {
-                    // any-hit: the verdict does not depend on the visiting order; near-first finds occluders sooner
-                    Step4 st = node4_step(sc.nodes4, cur, r.o, r.inv, r.t_max, r.negmask);
-                    unsigned next = YK_REF_NONE;
-#pragma unroll
-                    for (int k = 3; k >= 0; --k) {
-                        if (st.ref[k] != YK_REF_NONE) {
-                            if (next != YK_REF_NONE) {
-                                if (sp >= YK_STACK_CAP) {
-                                    atomicOr(ctrl + YK_CTRL_ERR, 1u);
-                                    sp = 0;
-                                } else {
-                                    stk.push(sp, next);
-                                    ++sp;
-                                }
-                            }
-                            next = st.ref[k];
-                        }
-                    }
-                    if (next != YK_REF_NONE) {
-                        cur = next;
-                    } else if (sp > 0) {
-                        --sp;
-                        cur = stk.at(sp);
-                    } else {
-                        if (!slot_of) vis[slot] = 0;
-                        active = false;  // unoccluded
-                    }
-                }
-            } else if (on_node) {
-                NodeBoxes nb = (cur & YK_TOP_BIT) ? load_node_lds(lds_top, cur & ~YK_TOP_BIT) : load_node(sc.nodes, cur);
-                float t0, t1;
-                bool h0 = slab(nb.lo0, nb.hi0, r.o, r.inv, r.t_max, t0);
-                bool h1 = slab(nb.lo1, nb.hi1, r.o, r.inv, r.t_max, t1);
-                bool swap = (r.negmask >> nb.axis) & 1u;
-                unsigned near_ref = swap ? nb.ref1 : nb.ref0, far_ref = swap ? nb.ref0 : nb.ref1;
-                bool near_hit = swap ? h1 : h0, far_hit = swap ? h0 : h1;
-                if (near_hit) {
-                    if (far_hit) {
-                        if (sp >= YK_REF_STACK_CAP) {
-                            atomicOr(ctrl + YK_CTRL_ERR, 1u);
-                            sp = 0;
-                        } else {
-                            stk.push(sp, far_ref);
-                            ++sp;
-                        }
-                    }
-                    cur = near_ref;
-                } else if (far_hit) {
-                    cur = far_ref;
-                } else if (sp > 0) {
-                    --sp;
-                    cur = stk.at(sp);
-                } else {
-                    if (!slot_of) vis[slot] = 0;
-                    active = false;  // unoccluded
-                }
-            }
-        } else if (on_leaf) {
-            unsigned prim = cur & ~YK_LEAF_BIT;
-            bool occluded = false;
-            for (;;) {
-                float4 v0 = sc.tris[3 * prim], v1 = sc.tris[3 * prim + 1], v2 = sc.tris[3 * prim + 2];
-                const unsigned pflags = __float_as_uint(v2.w);
-                TriHit h;
-                bool got;
-                if (SPHERES && (pflags & YK_PRIM_SPHERE)) {
-                    V3 ro, rd;
-                    got = sphere_hit_t(sc.spheres[__float_as_uint(v1.w) - sc.n_triangles], r.o, r.d, r.t_max, h.t, ro, rd);
-                } else {
-                    got = tri_intersect(r.o, r.rt, r.t_max, f4_xyz(v0), f4_xyz(v1), f4_xyz(v2), h);
-                }
-                if (got) {
-                    // bvh.rs:269-280: a hit on the sampled area light's own surface does not occlude
-                    // (spheres carry no area light: v0.w = -1)
-                    int prim_light = (int)__float_as_uint(v0.w);
-                    if (!(area_light >= 0 && prim_light >= 0 && prim_light == area_light)) {
-                        occluded = true;
-                        break;
-                    }
-                }
-                if (pflags & YK_PRIM_LAST) break;
-                ++prim;
-            }
-            if (occluded) {
+            if (!root_hit(sc, r)) return unoccluded();
+            cur = root;
+            sp = 0;
+            return true;
+        },
+        [&]() {
+            const bool entered = WIDE ? node4_step<false>(sc.nodes4, r, stk, sp, cur, err)
+                                      : node2_any(load_node(lds_top, sc.nodes, cur), r, stk, sp, cur, err) != STEP_POP;  // after an overflow: the near child, an empty stack
+            if (entered) return true;
+            return pop_any(stk, sp, cur) || unoccluded();
+        },
+        [&]() {
+            if (leaf_any<SPHERES>(sc, cur & ~YK_LEAF_BIT, r, area_light)) {
                 vis[slot] = slot_of ? 2 : 1;
-                active = false;
-            } else if (sp > 0) {
-                --sp;
-                cur = stk.at(sp);
-            } else {
-                if (!slot_of) vis[slot] = 0;
-                active = false;
+                return false;
             }
-        }
-    }
+            return pop_any(stk, sp, cur) || unoccluded();
+        });
 }
 
 // Persistent waves: each wave pulls 64 consecutive rays from a global head until
@@ -754,13 +562,8 @@ __global__ __launch_bounds__(BLOCK) void k_trace_closest(DevScene sc, const floa
                                                          uint4* stats_out, uint2* spill, unsigned spill_stride, unsigned* ctrl,
                                                          unsigned long long* ray_counter) {
     __shared__ unsigned long long lds_stack[LDS_DEPTH * BLOCK];
-    TravStack<BLOCK, LDS_DEPTH> stk;
-    stk.lds = (lds_u64*)lds_stack;
-    stk.spill = (glb_u64*)spill;
-    stk.spill_stride = spill_stride;
-    stk.gtid = blockIdx.x * BLOCK + threadIdx.x;
-    const unsigned n = *count_ptr;
-    if (ray_counter && blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(ray_counter, (unsigned long long)n);
+    auto stk = make_stack<BLOCK, LDS_DEPTH>(lds_stack, spill, spill_stride);
+    const unsigned n = queue_length(count_ptr, CancelRef{nullptr, nullptr}, ray_counter);
     for (;;) {
         unsigned base = 0;
         if (lane_id() == 0) base = atomicAdd(head, YK_WAVE);
@@ -772,80 +575,17 @@ __global__ __launch_bounds__(BLOCK) void k_trace_closest(DevScene sc, const floa
             float tm = t_max_opt ? t_max_opt[i] : __builtin_inff();
             int tri;
             TriHit h = TriHit{0.0f, 0.0f, 0.0f, 0.0f};
-            unsigned nt = 0, nh = 0, st = 0;
-            traverse_closest<BLOCK, LDS_DEPTH, STATS>(sc, f4_xyz(ro), f4_xyz(rd), tm, stk, tri, h, nt, nh, st, ctrl + YK_CTRL_ERR);
+            TraceStats s = TraceStats{0, 0, 0};
+            traverse_closest<STATS>(sc, ray_setup(f4_xyz(ro), f4_xyz(rd), tm), stk, tri, h, &s, ctrl + YK_CTRL_ERR);
             hit_tri[i] = tri;
             if (hit_out) hit_out[i] = make_float4(h.t, h.b0, h.b1, h.b2);
-            if (STATS) stats_out[i] = make_uint4(nt, nh, st, 0u);
+            if (STATS) stats_out[i] = make_uint4(s.node_tests, s.node_hits, s.shape_tests, 0u);
         }
     }
 }
 
 
 // ------------------------------------------------------------------ Whitted
-// BoundingVolumeHierarchy::any_intersect (bvh.rs:235-302) for one lane: true = occluded.  A hit
-// on the sampled area light's own surface does not occlude (bvh.rs:269-280).
-template <int BLOCK, int LDS_DEPTH>
-__device__ __forceinline__ bool traverse_any(const DevScene& sc, V3 o, V3 d, float t_max, int area_light, TravStack<BLOCK, LDS_DEPTH>& stk, unsigned* err) {
-    V3 inv = V3{1.0f / d.x, 1.0f / d.y, 1.0f / d.z};
-    bool neg[3] = {inv.x < 0.0f, inv.y < 0.0f, inv.z < 0.0f};
-    RayTri rt = ray_tri_setup(d);
-    float tmin;
-    if (!slab(V3{sc.root_bmin[0], sc.root_bmin[1], sc.root_bmin[2]}, V3{sc.root_bmax[0], sc.root_bmax[1], sc.root_bmax[2]}, o, inv, t_max, tmin)) return false;
-    int sp = 0;
-    unsigned cur = sc.root_ref;
-    for (;;) {
-        if (!(cur & YK_LEAF_BIT)) {
-            NodeBoxes nb = load_node(sc.nodes, cur);
-            float t0, t1;
-            bool h0 = slab(nb.lo0, nb.hi0, o, inv, t_max, t0);
-            bool h1 = slab(nb.lo1, nb.hi1, o, inv, t_max, t1);
-            bool swap = neg[nb.axis];
-            unsigned near_ref = swap ? nb.ref1 : nb.ref0, far_ref = swap ? nb.ref0 : nb.ref1;
-            bool near_hit = swap ? h1 : h0, far_hit = swap ? h0 : h1;
-            if (near_hit) {
-                if (far_hit) {
-                    if (sp >= YK_REF_STACK_CAP) {
-                        atomicOr(err, 1u);
-                        return false;
-                    }
-                    stk.push(sp, far_ref, 0.0f);
-                    ++sp;
-                }
-                cur = near_ref;
-                continue;
-            }
-            if (far_hit) {
-                cur = far_ref;
-                continue;
-            }
-        } else {
-            unsigned prim = cur & ~YK_LEAF_BIT;
-            for (;;) {
-                float4 v0 = sc.tris[3 * prim], v1 = sc.tris[3 * prim + 1], v2 = sc.tris[3 * prim + 2];
-                const unsigned pflags = __float_as_uint(v2.w);
-                TriHit h = TriHit{0.0f, 0.0f, 0.0f, 0.0f};
-                bool got;
-                if (pflags & YK_PRIM_SPHERE) {
-                    V3 ro, rd;
-                    got = sphere_hit_t(sc.spheres[__float_as_uint(v1.w) - sc.n_triangles], o, d, t_max, h.t, ro, rd);
-                } else {
-                    got = tri_intersect(o, rt, t_max, f4_xyz(v0), f4_xyz(v1), f4_xyz(v2), h);
-                }
-                if (got) {
-                    int prim_light = (int)__float_as_uint(v0.w);
-                    if (!(area_light >= 0 && prim_light >= 0 && prim_light == area_light)) return true;
-                }
-                if (pflags & YK_PRIM_LAST) break;
-                ++prim;
-            }
-        }
-        if (sp == 0) return false;
-        --sp;
-        cur = stk.at(sp).x;
-    }
-}
-
 // Whitted::li_internal (whitted.rs:74-181), one lane per camera sample.  The recursion —
 // direct lighting, then the specular reflection subtree, then the specular transmission
 // subtree, each child weighted as (f * li) * |wi . ns| with no pdf (whitted.rs:66) — is run
@@ -869,29 +609,15 @@ __global__ __launch_bounds__(BLOCK) void k_whitted(DevScene sc, RenderParams prm
                                                    uint32_t n, float4* sample_buf, uint2* spill, unsigned spill_stride, unsigned* ctrl,
                                                    unsigned long long* counters) {
     __shared__ unsigned long long lds_stack[LDS_DEPTH * BLOCK];
-    TravStack<BLOCK, LDS_DEPTH> stk;
-    stk.lds = (lds_u64*)lds_stack;
-    stk.spill = (glb_u64*)spill;
-    stk.spill_stride = spill_stride;
-    stk.gtid = blockIdx.x * BLOCK + threadIdx.x;
+    auto stk = make_stack<BLOCK, LDS_DEPTH>(lds_stack, spill, spill_stride);
     unsigned* err = ctrl + YK_CTRL_ERR;
     unsigned long long n_rays = 0, n_shadow = 0;
     if (cancel_raised(prm.cancel)) n = 0;  // interrupted before this launch started (yk_device.h, CancelRef)
     for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
         const float4 a = cur.rayO[i], b = cur.rayD[i], c = cur.thru[i];
-        const uint4 r = cur.rngs[i];
         V3 o = f4_xyz(a), d = f4_xyz(b);
         const unsigned sid = __float_as_uint(b.w);
-        SamplerState st;
-        st.rng.state = (u64)r.x | ((u64)r.y << 32);
-        st.rng.inc = (u64)r.z | ((u64)r.w << 32);
-        st.dimension = __float_as_uint(c.w);
-        uint32_t pix, ks;
-        split_sample_id(sid, prm.spe, pix, ks);
-        const uint32_t xy = pixel_xy[pix];
-        st.px = xy & 0xffffu;
-        st.py = xy >> 16;
-        st.sample_index = (sample_index_tab ? sample_index_tab[pix] : prm.sample_base) + ks;
+        SamplerState st = path_sampler(prm, pixel_xy, sample_index_tab, cur.rngs[i], __float_as_uint(c.w), sid);
         WhittedFrame frames[YK_WHITTED_MAX_DEPTH];
         int sp = 0;  // frames on the stack = depth of the call being evaluated
         bool is_specular = false;
@@ -901,8 +627,7 @@ __global__ __launch_bounds__(BLOCK) void k_whitted(DevScene sc, RenderParams prm
             n_rays += 1;
             int shape;
             TriHit th = TriHit{0.0f, 0.0f, 0.0f, 0.0f};
-            unsigned nt = 0, nh = 0, ns = 0;
-            traverse_closest<BLOCK, LDS_DEPTH, false>(sc, o, d, __builtin_inff(), stk, shape, th, nt, nh, ns, err);
+            traverse_closest<false>(sc, ray_setup(o, d, __builtin_inff()), stk, shape, th, nullptr, err);
             bool called = false;
             if (shape < 0) {
                 ret = RGB{sc.background[0], sc.background[1], sc.background[2]};  // whitted.rs:171
@@ -928,7 +653,7 @@ __global__ __launch_bounds__(BLOCK) void k_whitted(DevScene sc, RenderParams prm
                     V3 offset = sf.n * 0.001f;  // VisibilityTester::ray = p0.spawn_ray_to(p1), interaction.rs:44-59
                     V3 so = dot(ls.p1 - sf.p, sf.n) > 0.0f ? sf.p + offset : sf.p - offset;
                     n_shadow += 1;
-                    if (!traverse_any<BLOCK, LDS_DEPTH>(sc, so, ls.p1 - so, 0.9999f, ls.area_light, stk, err))
+                    if (!traverse_any(sc, ray_setup(so, ls.p1 - so, 0.9999f), ls.area_light, stk, err))
                         sum = sum + f * ls.li * rclamp(dot_nv(sf.ns, ls.l), 0.0f, 1.0f) / ls.pdf;
                 }
                 if (sp == 0 || is_specular) {  // whitted.rs:135-137, rectangular_light.rs:75-81
@@ -1027,28 +752,14 @@ __global__ __launch_bounds__(BLOCK) void k_path_debug(DevScene sc, RenderParams 
                                                       uint32_t n, float4* sample_buf, uint32_t* out_counts, float4* out_rays, unsigned ray_cap,
                                                       uint32_t* out_n_rays, float min_len, uint2* spill, unsigned spill_stride, unsigned* ctrl) {
     __shared__ unsigned long long lds_stack[LDS_DEPTH * BLOCK];
-    TravStack<BLOCK, LDS_DEPTH> stk;
-    stk.lds = (lds_u64*)lds_stack;
-    stk.spill = (glb_u64*)spill;
-    stk.spill_stride = spill_stride;
-    stk.gtid = blockIdx.x * BLOCK + threadIdx.x;
+    auto stk = make_stack<BLOCK, LDS_DEPTH>(lds_stack, spill, spill_stride);
     unsigned* err = ctrl + YK_CTRL_ERR;
     if (cancel_raised(prm.cancel)) n = 0;  // interrupted before this launch started (yk_device.h, CancelRef)
     for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
         const float4 a = cur.rayO[i], b = cur.rayD[i], c = cur.thru[i];
-        const uint4 r = cur.rngs[i];
         V3 o = f4_xyz(a), d = f4_xyz(b);
         const unsigned sid = __float_as_uint(b.w);
-        SamplerState st;
-        st.rng.state = (u64)r.x | ((u64)r.y << 32);
-        st.rng.inc = (u64)r.z | ((u64)r.w << 32);
-        st.dimension = __float_as_uint(c.w);
-        uint32_t pix, ks;
-        split_sample_id(sid, prm.spe, pix, ks);
-        const uint32_t xy = pixel_xy[pix];
-        st.px = xy & 0xffffu;
-        st.py = xy >> 16;
-        st.sample_index = (sample_index_tab ? sample_index_tab[pix] : prm.sample_base) + ks;
+        SamplerState st = path_sampler(prm, pixel_xy, sample_index_tab, cur.rngs[i], __float_as_uint(c.w), sid);
         RGB L = RGB{0.0f, 0.0f, 0.0f}, beta = RGB{c.x, c.y, c.z};
         unsigned bounces = 0, n_closest = 0, k = 0, type = YK_RAY_DIRECT;
         bool specular_bounce = false, alive = prm.max_depth > 0;
@@ -1057,8 +768,7 @@ __global__ __launch_bounds__(BLOCK) void k_path_debug(DevScene sc, RenderParams 
             n_closest += 1;
             int shape;
             TriHit th = TriHit{0.0f, 0.0f, 0.0f, 0.0f};
-            unsigned nt = 0, nh = 0, ns = 0;
-            traverse_closest<BLOCK, LDS_DEPTH, false>(sc, o, d, __builtin_inff(), stk, shape, th, nt, nh, ns, err);
+            traverse_closest<false>(sc, ray_setup(o, d, __builtin_inff()), stk, shape, th, nullptr, err);
             if (shape < 0) {
                 debug_ray_store(out_rays, i, ray_cap, k++, o, d, type == YK_RAY_DIRECT ? __builtin_inff() : root_exit(sc, o, d, min_len), type);
                 L = vertex_accumulate(prm, L, RGB{1.0f, 1.0f, 1.0f}, RGB{0.0f, 0.0f, 0.0f}, vertex_miss_term(sc, beta), YK_PEND_MISS);
@@ -1073,7 +783,7 @@ __global__ __launch_bounds__(BLOCK) void k_path_debug(DevScene sc, RenderParams 
             for (unsigned l = 0; l < sc.n_lights; ++l) {
                 const NeeSample ne = vertex_light<true>(sc, prm, st, l, v);
                 if (ne.want || ne.has_ray) debug_ray_store(out_rays, i, ray_cap, k++, ne.so, ne.sd, 0.9999f, YK_RAY_SHADOW);
-                if (ne.want && !traverse_any<BLOCK, LDS_DEPTH>(sc, ne.so, ne.sd, 0.9999f, ne.al, stk, err)) radiance = radiance + ne.contrib;
+                if (ne.want && !traverse_any(sc, ray_setup(ne.so, ne.sd, 0.9999f), ne.al, stk, err)) radiance = radiance + ne.contrib;
             }
             const RGB beta_in = beta;  // vertex_accumulate takes the throughput the vertex was entered with
             const VertexEnd e = vertex_finish(sc, prm, st, v, beta, bounces, specular_bounce);
