@@ -623,6 +623,11 @@ yk_status yk_combiner_last_error(const yk_combiner* combiner, char* buf, size_t 
  *                 Rotate, Attribute/Transform blocks, Include, (Make)NamedMaterial/Material
  *                 {matte,glass,glossy,metal}, LightSource {infinite,distant,point}, Shape
  *                 {sphere,trianglemesh,plymesh}, Texture "spectrum" "imagemap" for matte Kd.
+ *   yk_load_mitsuba  scene::mitsuba::load  scene/mitsuba/mod.rs:28-218 — Mitsuba 2.1.0 XML as far as
+ *                 the reference reads it: sensor (fov, fov_axis, transform), default resx / resy,
+ *                 bsdf {diffuse,twosided,dielectric}, emitter {constant,point,spot}, shape "ply" with
+ *                 a transform; everything is mirrored by scale(-1, 1, 1) on the way in.
+ *   yk_load_scene    try_load_scene  app/util.rs:15-63 — one of the three by file extension.
  * split_method / max_shapes_in_node are SceneLoadSettings (scene/mod.rs:25-39) and are
  * copied into the description.  Errors: where the reference returns LoadError or panics
  * the call returns non-zero and yk_loader_last_error() (thread-local) holds the reason. */
@@ -639,6 +644,13 @@ void yk_image_texture_free(yk_texture_desc* tex);
 typedef struct yk_loaded_scene yk_loaded_scene;
 yk_status yk_load_ply(const char* path, uint32_t split_method, uint32_t max_shapes_in_node, yk_loaded_scene** out);
 yk_status yk_load_pbrt(const char* path, uint32_t split_method, uint32_t max_shapes_in_node, yk_loaded_scene** out);
+/* scene::mitsuba::load (scene/mitsuba/mod.rs:28-218) */
+yk_status yk_load_mitsuba(const char* path, uint32_t split_method, uint32_t max_shapes_in_node, yk_loaded_scene** out);
+/* app/util.rs:15-63 try_load_scene: by extension — "ply", "xml", "pbrt" (exact, case-sensitive like the
+ * reference's match); anything else YK_ERR_INVALID_ARGUMENT with the reference's message ("Unknown extension
+ * 'x'", "Expected a file with an extension", "Scene does not exist '...'").  The empty path (the Cornell box
+ * in the reference) is YK_ERR_INVALID_ARGUMENT here: that scene is built by the caller (scenes.cornell()). */
+yk_status yk_load_scene(const char* path, uint32_t split_method, uint32_t max_shapes_in_node, yk_loaded_scene** out);
 /* Pointers written into *desc stay valid until yk_loaded_scene_destroy.  camera->res_x/res_y
  * carry FilmSettings.res; *tile_dim its tile_dim (16).  camera / tile_dim may be NULL. */
 yk_status yk_loaded_scene_get(const yk_loaded_scene* loaded, yk_scene_desc* desc, yk_camera_params* camera, uint16_t* tile_dim);

@@ -150,13 +150,14 @@ class Scene {
     yk_scene* h_ = nullptr;
 };
 
-// scene::pbrt::load / Scene::ply (scene/pbrt/mod.rs:94, scene/mod.rs:99): the parsed scene as a
+// scene::pbrt::load / Scene::ply / scene::mitsuba::load (scene/pbrt/mod.rs:94, scene/mod.rs:99, scene/mitsuba/mod.rs:28): the parsed scene as a
 // ready yk_scene_desc plus the CameraParameters and FilmSettings the reference's loaders return
 class LoadedScene {
    public:
-    enum class Format { Ply, Pbrt };
+    enum class Format { Ply, Pbrt, Mitsuba, ByExtension };  // ByExtension: try_load_scene, app/util.rs:15-63
     LoadedScene(const std::string& path, Format format, uint32_t split_method = YK_SPLIT_SAH, uint32_t max_shapes_in_node = 1) {
-        yk_status st = format == Format::Ply ? yk_load_ply(path.c_str(), split_method, max_shapes_in_node, &h_) : yk_load_pbrt(path.c_str(), split_method, max_shapes_in_node, &h_);
+        auto load = format == Format::Ply ? yk_load_ply : (format == Format::Pbrt ? yk_load_pbrt : (format == Format::Mitsuba ? yk_load_mitsuba : yk_load_scene));
+        yk_status st = load(path.c_str(), split_method, max_shapes_in_node, &h_);
         if (st != YK_OK) throw Error(st, yk_loader_last_error());
         uint16_t tile_dim = 16;
         yk_camera_params cp;

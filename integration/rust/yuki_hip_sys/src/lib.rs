@@ -315,6 +315,8 @@ extern "C" {
     pub fn yk_image_texture_free(tex: *mut yk_texture_desc);
     pub fn yk_load_ply(path: *const c_char, split_method: u32, max_shapes_in_node: u32, out: *mut *mut yk_loaded_scene) -> yk_status;
     pub fn yk_load_pbrt(path: *const c_char, split_method: u32, max_shapes_in_node: u32, out: *mut *mut yk_loaded_scene) -> yk_status;
+    pub fn yk_load_mitsuba(path: *const c_char, split_method: u32, max_shapes_in_node: u32, out: *mut *mut yk_loaded_scene) -> yk_status;
+    pub fn yk_load_scene(path: *const c_char, split_method: u32, max_shapes_in_node: u32, out: *mut *mut yk_loaded_scene) -> yk_status;
     pub fn yk_loaded_scene_get(loaded: *const yk_loaded_scene, desc: *mut yk_scene_desc, camera: *mut yk_camera_params, tile_dim: *mut u16) -> yk_status;
     pub fn yk_loaded_scene_destroy(loaded: *mut yk_loaded_scene);
     pub fn yk_loader_last_error() -> *const c_char;

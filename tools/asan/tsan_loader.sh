@@ -7,7 +7,7 @@ ROOT=$(cd "$(dirname "$0")/../.." && pwd)
 OUT=${TMPDIR:-/tmp}/yk_tsan_loader
 rm -rf $OUT; mkdir -p $OUT
 cd $ROOT/yuki_amd/csrc
-hipcc -x hip --cuda-host-only -O1 -g -fsanitize=thread -std=c++17 -fPIC -ffp-contract=off -shared -o $OUT/libyk_host_tsan.so yk_loaders.cpp yk_image.cpp yk_image_formats.cpp yk_host.cpp 2>/dev/null
+hipcc -x hip --cuda-host-only -O1 -g -fsanitize=thread -std=c++17 -fPIC -ffp-contract=off -shared -o $OUT/libyk_host_tsan.so yk_loaders.cpp yk_mitsuba.cpp yk_image.cpp yk_image_formats.cpp yk_host.cpp 2>/dev/null
 /opt/rocm/lib/llvm/bin/clang++ -O1 -g -fsanitize=thread -std=c++17 $ROOT/tools/asan/harness.cpp -o $OUT/harness -L$OUT -lyk_host_tsan -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,$OUT
 cd $ROOT && python - "$OUT/files" "${1:-city-small}" <<'P'
 import sys

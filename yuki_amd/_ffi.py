@@ -108,6 +108,8 @@ SYMBOLS = {
     "yk_sizeof": (C.c_size_t, [C.c_int]),
     "yk_load_ply": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(vp)]),
     "yk_load_pbrt": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(vp)]),
+    "yk_load_mitsuba": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(vp)]),
+    "yk_load_scene": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.POINTER(vp)]),
     "yk_loaded_scene_get": (C.c_int, [vp, C.POINTER(abi.SceneDesc), C.POINTER(abi.CameraParams), C.POINTER(C.c_uint16)]),
     "yk_loaded_scene_destroy": (None, [vp]),
     "yk_loader_last_error": (C.c_char_p, []),

@@ -32,37 +32,20 @@
 #include "yk_host.h"
 #include "yk_libm.h"
 #include "yk_math.h"
+#include "yk_loaders_internal.h"  // yk_loaded_scene, PlyMesh, PlyJob: shared with yk_mitsuba.cpp
 
 using namespace yk;
-
-struct yk_loaded_scene {
-    std::vector<float> points, normals, uvs;
-    std::vector<uint32_t> indices, tri_mesh;
-    std::vector<uint32_t> shape_order, shape_order_flat;  // file order of shapes: triangle id | 0x80000000+sphere id
-    std::vector<int32_t> tri_material, tri_area_light;
-    std::vector<yk_mesh_desc> meshes;
-    std::vector<yk_sphere_desc> spheres;
-    std::vector<yk_material_desc> materials;
-    std::vector<yk_light_desc> lights;
-    std::vector<std::vector<float>> texture_data;
-    std::vector<yk_texture_desc> textures;
-    float background[3] = {0, 0, 0};
-    yk_camera_params camera;
-    uint16_t tile_dim = 16;
-    uint32_t split_method = YK_SPLIT_SAH, max_shapes_in_node = 1;
-    bool any_normals = false, any_uvs = false;
-};
 
 yk_status yk_image_decode_file(const std::string& path, uint32_t& w, uint32_t& h, std::vector<float>& rgb, std::string& err);  // yk_image.cpp
 
 static thread_local std::string g_loader_error;
-static yk_status lfail(yk_status st, const std::string& msg) {
+yk_status lfail(yk_status st, const std::string& msg) {
     g_loader_error = msg;
     return st;
 }
 
 // ------------------------------------------------------------------ helpers
-static yk_material_desc make_mat(uint32_t kind, const float a[3], const float b[3], float c, bool remap) {
+yk_material_desc make_mat(uint32_t kind, const float a[3], const float b[3], float c, bool remap) {
     yk_material_desc m;
     std::memset(&m, 0, sizeof(m));
     m.kind = kind;
@@ -215,11 +198,7 @@ struct PlyReader {
 
 // The payload of one PLY file as ply::load reads it (scene/ply.rs:19-130), before any transform.  Pure: touches nothing but its
 // arguments (errors come back through the thread-local loader error of the CALLING thread), so several files are read at once.
-struct PlyMesh {
-    std::vector<float> pts, nrm, uv;
-    std::vector<uint32_t> indices;
-};
-static yk_status read_ply_mesh(const std::string& path, PlyMesh& out) {
+yk_status read_ply_mesh(const std::string& path, PlyMesh& out) {
     std::vector<unsigned char> buf;
     if (!read_file(path, buf)) return lfail(YK_ERR_INVALID_ARGUMENT, "Could not open '" + path + "'");
     // ---- header
@@ -355,7 +334,7 @@ static yk_status read_ply_mesh(const std::string& path, PlyMesh& out) {
 }
 
 // Mesh::new for a PLY payload.  No transform given (Scene::ply): scale / translate into the unit cube (ply.rs:99-108).
-static void add_ply_mesh(yk_loaded_scene& s, const PlyMesh& m, const Xf* transform, int material) {
+void add_ply_mesh(yk_loaded_scene& s, const PlyMesh& m, const Xf* transform, int material) {
     const std::vector<float>& pts = m.pts;
     const size_t nv = pts.size() / 3;
     Xf t;
@@ -634,6 +613,9 @@ yk_status get_material(const std::string& type, const ParamSet& p, const std::ma
 
 }  // namespace
 
+Xf loader_rotation(float theta, V3 axis) { return xf_rotation(theta, axis); }
+bool rust_float_grammar(const std::string& s) { return rust_f64_grammar(s); }
+
 // `n as i32` from f64: saturating, NaN -> 0
 static int sat_i32(double v) {
     if (v != v) return 0;
@@ -643,17 +625,13 @@ static int sat_i32(double v) {
 }
 
 // scene/pbrt/mod.rs: ParseShape — shapes in file order; `plymesh` files are read after the parse, in parallel (:786-800)
-struct ParseShape {
+struct ParseShape : PlyJob {
     int kind = 0;  // 0 sphere, 1 trianglemesh, 2 plymesh
     yk_sphere_desc sphere;
     Xf transform;
     int material = 0;
     std::vector<uint32_t> idx;
     std::vector<float> P, N, UV;
-    std::string ply_path;
-    PlyMesh ply;
-    yk_status status = YK_OK;
-    std::string error;
 };
 
 struct PbrtState {
@@ -1023,7 +1001,43 @@ static yk_status load_pbrt_file(const std::string& path, yk_loaded_scene& s, Pbr
     }
 }
 
-static void default_camera(yk_loaded_scene& s) {
+void read_ply_jobs(const std::vector<PlyJob*>& ply, bool find_stray_vertices) {
+    unsigned n_threads = (unsigned)std::min<size_t>(ply.size(), std::min(16u, std::max(1u, std::thread::hardware_concurrency())));
+    if (const char* e = std::getenv("YK_LOADER_THREADS")) n_threads = (unsigned)std::min<size_t>(ply.size(), (size_t)std::max(1, std::atoi(e)));  // measurements
+    std::atomic<size_t> next_ply{0};
+    auto work = [&]() {
+        for (;;) {
+            const size_t k = next_ply.fetch_add(1);
+            if (k >= ply.size()) return;
+            PlyJob& ph = *ply[k];
+            try {
+                ph.status = read_ply_mesh(ph.ply_path, ph.ply);
+                if (ph.status != YK_OK) ph.error = g_loader_error;  // this thread's own copy
+                if (ph.status == YK_OK && find_stray_vertices) {
+                    std::vector<unsigned char> seen(ph.ply.pts.size() / 3, 0);
+                    for (uint32_t q : ph.ply.indices) seen[q] = 1;
+                    ph.all_referenced = std::find(seen.begin(), seen.end(), 0) == seen.end();
+                }
+            } catch (const std::exception& e) {  // e.g. bad_alloc on an absurd element count
+                ph.status = YK_ERR_INVALID_ARGUMENT;
+                ph.error = std::string("PLY: ") + e.what();
+            }
+        }
+    };
+    if (n_threads <= 1) {
+        work();
+    } else {
+        std::vector<std::thread> pool;
+        try {
+            for (unsigned t = 0; t < n_threads; ++t) pool.emplace_back(work);
+        } catch (const std::exception&) {  // no more threads: the ones that started (and this one) finish the list
+        }
+        work();
+        for (std::thread& t : pool) t.join();
+    }
+}
+
+void default_camera(yk_loaded_scene& s) {
     std::memset(&s.camera, 0, sizeof(s.camera));
     s.camera.up[1] = 1.0f;
     s.camera.fov_axis = 0;
@@ -1089,37 +1103,10 @@ yk_status yk_load_pbrt(const char* path, uint32_t split_method, uint32_t max_sha
     if (st == YK_OK) {
         // "load plys" (pbrt/mod.rs:786-800: parse_shapes.par_iter_mut().try_for_each(ply::load)): the files are read by a few
         // threads, each into its own ParseShape; the meshes then join the scene in file order ("collect meshes", :807-822)
-        std::vector<size_t> ply;
-        for (size_t i = 0; i < S.shapes.size(); ++i)
-            if (S.shapes[i].kind == 2) ply.push_back(i);
-        unsigned n_threads = (unsigned)std::min<size_t>(ply.size(), std::min(16u, std::max(1u, std::thread::hardware_concurrency())));
-        if (const char* e = std::getenv("YK_LOADER_THREADS")) n_threads = (unsigned)std::min<size_t>(ply.size(), (size_t)std::max(1, std::atoi(e)));  // measurements
-        std::atomic<size_t> next_ply{0};
-        auto work = [&]() {
-            for (;;) {
-                const size_t k = next_ply.fetch_add(1);
-                if (k >= ply.size()) return;
-                ParseShape& ph = S.shapes[ply[k]];
-                try {
-                    ph.status = read_ply_mesh(ph.ply_path, ph.ply);
-                    if (ph.status != YK_OK) ph.error = g_loader_error;  // this thread's own copy
-                } catch (const std::exception& e) {  // e.g. bad_alloc on an absurd element count
-                    ph.status = YK_ERR_INVALID_ARGUMENT;
-                    ph.error = std::string("PLY: ") + e.what();
-                }
-            }
-        };
-        if (n_threads <= 1) {
-            work();
-        } else {
-            std::vector<std::thread> pool;
-            try {
-                for (unsigned t = 0; t < n_threads; ++t) pool.emplace_back(work);
-            } catch (const std::exception&) {  // no more threads: the ones that started (and this one) finish the list
-            }
-            work();
-            for (std::thread& t : pool) t.join();
-        }
+        std::vector<PlyJob*> ply;
+        for (ParseShape& ph : S.shapes)
+            if (ph.kind == 2) ply.push_back(&ph);
+        read_ply_jobs(ply);
         for (ParseShape& ph : S.shapes) {
             if (ph.kind == 2 && ph.status != YK_OK) {  // the first failing file in file order
                 st = lfail(ph.status, ph.error);

@@ -3,11 +3,13 @@
     SceneLoadSettings                       yuki/src/scene/mod.rs:25-39
     Scene::ply(settings)                    yuki/src/scene/mod.rs:99-152  (+ scene/ply.rs)
     scene::pbrt::load(settings)             yuki/src/scene/pbrt/mod.rs:94-857
+    scene::mitsuba::load(settings)          yuki/src/scene/mitsuba/mod.rs:28-218
+    try_load_scene(settings)                yuki/src/app/util.rs:15-63
 
-Both return what the reference returns — the scene, the `CameraParameters` and the
+All return what the reference returns — the scene, the `CameraParameters` and the
 `FilmSettings` — with the scene as a `SceneData` ready for `core.Scene(ctx, data)`.
 The parsing itself runs in libyuki_hip.so (`yk_load_ply` / `yk_load_pbrt`,
-yuki_amd/csrc/yk_loaders.cpp); this file copies the result out of the library.
+yuki_amd/csrc/yk_loaders.cpp; `yk_load_mitsuba` / `yk_load_scene`, yk_mitsuba.cpp); this file copies the result out of the library.
 """
 import ctypes as C
 import os
@@ -129,3 +131,13 @@ def load_ply(settings):
 def load_pbrt(settings):
     """scene::pbrt::load: (SceneData, CameraParameters, FilmSettings)."""
     return _load("yk_load_pbrt", settings)
+
+
+def load_mitsuba(settings):
+    """scene::mitsuba::load (Mitsuba 2.1.0 XML + PLY shapes): (SceneData, CameraParameters, FilmSettings)."""
+    return _load("yk_load_mitsuba", settings)
+
+
+def load_scene(settings):
+    """try_load_scene: `.ply`, `.xml` or `.pbrt` by extension: (SceneData, CameraParameters, FilmSettings)."""
+    return _load("yk_load_scene", settings)
