@@ -187,6 +187,34 @@ typedef struct yk_scene_info {
     uint32_t max_leaf_shapes, tree_depth;
 } yk_scene_info;
 
+/* How a scene's tree was built (yk_scene_get_build_info). */
+enum {
+    YK_BVH_BUILDER_HOST = 0,        /* the host recursion (the reference's, node for node) */
+    YK_BVH_BUILDER_DEVICE = 1,      /* the level-synchronous builder on the device: the same tree */
+    YK_BVH_BUILDER_HOST_LEVELS = 2  /* the host instance of the level algorithm (environment YK_BVH_BUILDER=levels) */
+};
+enum {                                /* why a build that was asked for the level builder ran the host recursion */
+    YK_BVH_REASON_NONE = 0,
+    YK_BVH_REASON_SPLIT_METHOD = 1,   /* YK_SPLIT_EQUAL_COUNTS: its select_nth over the whole array is sequential */
+    YK_BVH_REASON_NON_FINITE = 2,     /* a shape bound or centroid is not finite */
+    YK_BVH_REASON_SELECT_NTH = 3,     /* a range longer than max(bvh_small_range, 2) needed the equal-counts fallback */
+    YK_BVH_REASON_TOO_MANY_NODES = 4, /* more than 2^28 nodes or shapes */
+    YK_BVH_REASON_OUT_OF_MEMORY = 5,  /* the builder could not get its device memory */
+    YK_BVH_REASON_DEVICE_ERROR = 6    /* a HIP call of the builder failed */
+};
+typedef struct yk_bvh_build_info {
+    uint32_t builder;      /* YK_BVH_BUILDER_* : who produced the tree */
+    uint32_t reason;       /* YK_BVH_REASON_* : non-zero when the level builder was asked for and not used */
+    uint32_t levels;       /* levels the level phase ran */
+    uint32_t small_range;  /* the small-range limit S in effect */
+    uint64_t small_ranges; /* ranges finished by the small-range path */
+    double seconds_upload;    /* shape bounds to the device, primitive array */
+    double seconds_levels;    /* level phase */
+    double seconds_small;     /* small-range phase */
+    double seconds_layout;    /* depth-first numbering, interior boxes */
+    double seconds_copy_back; /* nodes and shape order to the host */
+} yk_bvh_build_info;
+
 typedef struct yk_render_stats {
     uint64_t rays;          /* closest-hit rays == the reference's ray_count (path.rs:87) */
     uint64_t shadow_rays;   /* any-hit rays, not part of the metric */
@@ -241,9 +269,13 @@ yk_status yk_context_interrupt(yk_context* ctx);
  * "packet_bounces" / "packet_shadow_bounces" (leading bounces traced by the wave-packet
  * kernels), "overlap_shadow" (0|1), "shade_reorder" (0|1: paths of a shade block dealt to
  * lanes by material kind), "top_nodes" (tree-top nodes the traversal kernels keep
- * in LDS, 0..1023; the kernels hold at most what they were built for) and "wide_bvh" (0: binary nodes only | 1: traverse the 4-wide collapse of the
- * BVH | 2, default: keep both, jobs of up to 6 M paths use the 4-wide one) — the last two apply
- * to scenes created afterwards.  Test hook: "trace_stage_kernel" (0, default: yk_trace_closest /
+ * in LDS, 0..1023; the kernels hold at most what they were built for), "wide_bvh" (0: binary nodes only | 1: traverse the 4-wide collapse of the
+ * BVH | 2, default: keep both, jobs of up to 6 M paths use the 4-wide one), "bvh_builder" (0, default: the
+ * tree is built by the host recursion | 1: by the level-synchronous builder on the device where the input
+ * qualifies — YK_SPLIT_SAH or YK_SPLIT_MIDDLE, finite bounds, no long range that needs select_nth — and by
+ * the host recursion otherwise; the tree is the same either way, yk_scene_get_build_info says which ran)
+ * and "bvh_small_range" (0 .. 2^20, default 32: ranges of at most this many shapes are finished by one
+ * lane each) — the last four apply to scenes created afterwards.  Test hook: "trace_stage_kernel" (0, default: yk_trace_closest /
  * yk_trace_any run the generic kernels as documented | 1: the generic kernels in the render loop's
  * flavour | 2: the wave-packet kernels; modes 1 and 2 report shape ids and verdicts only, and
  * refuse out_t, out_bary, counters, a closest-hit t_max and, in mode 2, a tree deeper than 64
@@ -281,6 +313,15 @@ yk_status yk_scene_get_info(const yk_scene* scene, yk_scene_info* out);
 /* nodes: n_nodes entries in the reference's depth-first layout; shape_order:
  * n_shapes source indices in leaf order (bvh.rs:96).  Either may be NULL. */
 yk_status yk_scene_export_bvh(const yk_scene* scene, yk_bvh_node* nodes, uint32_t* shape_order);
+/* Which builder produced the scene's tree, why the device builder was not used when "bvh_builder" asked
+ * for it, and the seconds of its phases (zero for the host recursion; yk_scene_info.build_seconds is the
+ * whole build whichever builder ran).  A fallback is silent for the result and visible here only.
+ * Scenes of a yk_multi (yk_multi_scene_create) are always built by the host recursion. */
+yk_status yk_scene_get_build_info(const yk_scene* scene, yk_bvh_build_info* out);
+/* Test hook: the partition step of the level builder on its own.  pass[i] says whether the element at
+ * position i passes the predicate; `order` (n words, in and out) is rearranged exactly as the two-ended
+ * swap partition of the host recursion (itertools::partition) would.  Returns the number passing. */
+size_t yk_bvh_partition_plan(const uint8_t* pass, size_t n, uint32_t* order);
 
 /* ---- the hot path -------------------------------------------------------------- */
 /* Integrator::render for a batch of tiles (integrators/mod.rs:120-185, non-accumulating

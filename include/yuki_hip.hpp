@@ -136,6 +136,11 @@ class Scene {
         check(yk_scene_get_info(h_, &i));
         return i;
     }
+    yk_bvh_build_info build_info() const {  // who built the tree, and why not the device when "bvh_builder" asked for it
+        yk_bvh_build_info i;
+        check(yk_scene_get_build_info(h_, &i));
+        return i;
+    }
     std::pair<std::vector<yk_bvh_node>, std::vector<uint32_t>> export_bvh() const {
         yk_scene_info i = info();
         std::vector<yk_bvh_node> nodes(i.n_nodes);

@@ -225,6 +225,25 @@ pub struct yk_scene_info {
     pub tree_depth: u32,
 }
 
+pub const YK_BVH_BUILDER_HOST: u32 = 0;
+pub const YK_BVH_BUILDER_DEVICE: u32 = 1;
+pub const YK_BVH_BUILDER_HOST_LEVELS: u32 = 2;
+
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct yk_bvh_build_info {
+    pub builder: u32,
+    pub reason: u32,
+    pub levels: u32,
+    pub small_range: u32,
+    pub small_ranges: u64,
+    pub seconds_upload: f64,
+    pub seconds_levels: f64,
+    pub seconds_small: f64,
+    pub seconds_layout: f64,
+    pub seconds_copy_back: f64,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct yk_combiner_info {
@@ -282,6 +301,7 @@ extern "C" {
     pub fn yk_scene_destroy(scene: *mut yk_scene);
     pub fn yk_scene_get_info(scene: *const yk_scene, out: *mut yk_scene_info) -> yk_status;
     pub fn yk_scene_export_bvh(scene: *const yk_scene, nodes: *mut yk_bvh_node, shape_order: *mut u32) -> yk_status;
+    pub fn yk_scene_get_build_info(scene: *const yk_scene, out: *mut yk_bvh_build_info) -> yk_status;
     pub fn yk_render_tiles(ctx: *mut yk_context, scene: *const yk_scene, camera: *const yk_camera, sampler: *const yk_sampler_desc, integrator: *const yk_integrator_desc, tiles: *const yk_tile, n_tiles: usize, out_rgb: *mut f32, stats: *mut yk_render_stats, cancel: yk_cancel_fn, user: *mut c_void) -> yk_status;
     pub fn yk_render_tiles_device(ctx: *mut yk_context, scene: *const yk_scene, camera: *const yk_camera, sampler: *const yk_sampler_desc, integrator: *const yk_integrator_desc, tiles: *const yk_tile, n_tiles: usize, d_out_rgb: *mut c_void, stream: *mut c_void, stats: *mut yk_render_stats, cancel: yk_cancel_fn, user: *mut c_void) -> yk_status;
     pub fn yk_render_tiles_accumulating(ctx: *mut yk_context, scene: *const yk_scene, camera: *const yk_camera, sampler: *const yk_sampler_desc, integrator: *const yk_integrator_desc, tiles: *const yk_tile, tile_samples: *const u16, n_tiles: usize, out_rgb: *mut f32, stats: *mut yk_render_stats, cancel: yk_cancel_fn, user: *mut c_void) -> yk_status;

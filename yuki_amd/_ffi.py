@@ -48,6 +48,25 @@ class SceneInfo(C.Structure):
     ]
 
 
+class BvhBuildInfo(C.Structure):
+    _fields_ = [
+        ("builder", C.c_uint32),
+        ("reason", C.c_uint32),
+        ("levels", C.c_uint32),
+        ("small_range", C.c_uint32),
+        ("small_ranges", C.c_uint64),
+        ("seconds_upload", C.c_double),
+        ("seconds_levels", C.c_double),
+        ("seconds_small", C.c_double),
+        ("seconds_layout", C.c_double),
+        ("seconds_copy_back", C.c_double),
+    ]
+
+
+BVH_BUILDER_NAMES = {0: "host recursion", 1: "device", 2: "host levels"}
+BVH_REASON_NAMES = {0: "", 1: "split method", 2: "non-finite bound", 3: "select_nth on a long range", 4: "too many nodes", 5: "out of device memory", 6: "device error"}
+
+
 class RenderStats(C.Structure):
     _fields_ = [
         ("rays", C.c_uint64),
@@ -90,6 +109,8 @@ SYMBOLS = {
     "yk_scene_destroy": (None, [vp]),
     "yk_scene_get_info": (C.c_int, [vp, C.POINTER(SceneInfo)]),
     "yk_scene_export_bvh": (C.c_int, [vp, vp, vp]),
+    "yk_scene_get_build_info": (C.c_int, [vp, C.POINTER(BvhBuildInfo)]),
+    "yk_bvh_partition_plan": (C.c_size_t, [vp, C.c_size_t, vp]),
     "yk_render_tiles": (C.c_int, [vp, vp, C.POINTER(abi.CameraMatrices), C.POINTER(abi.SamplerDesc), C.POINTER(abi.IntegratorDesc), vp, C.c_size_t, vp, C.POINTER(RenderStats), vp, vp]),
     "yk_render_tiles_device": (C.c_int, [vp, vp, C.POINTER(abi.CameraMatrices), C.POINTER(abi.SamplerDesc), C.POINTER(abi.IntegratorDesc), vp, C.c_size_t, vp, vp, C.POINTER(RenderStats), vp, vp]),
     "yk_render_tile": (C.c_int, [vp, vp, C.POINTER(abi.CameraMatrices), C.POINTER(abi.SamplerDesc), C.POINTER(abi.IntegratorDesc), C.POINTER(abi.Tile), vp, C.POINTER(C.c_uint64)]),

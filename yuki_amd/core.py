@@ -21,7 +21,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _ffi, abi
-from ._ffi import RenderStats, SceneInfo, YukiError, check, lib
+from ._ffi import BvhBuildInfo, RenderStats, SceneInfo, YukiError, check, lib
 
 
 def _p(a):
@@ -404,6 +404,12 @@ class Scene:
     def info(self):
         i = SceneInfo()
         check(lib().yk_scene_get_info(self.h, C.byref(i)))
+        return i
+
+    def build_info(self):
+        """yk_scene_get_build_info: who built the tree (_ffi.BVH_BUILDER_NAMES), why not the device (_ffi.BVH_REASON_NAMES), phase seconds."""
+        i = BvhBuildInfo()
+        check(lib().yk_scene_get_build_info(self.h, C.byref(i)))
         return i
 
     def export_bvh(self):

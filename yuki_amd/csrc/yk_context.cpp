@@ -167,6 +167,12 @@ yk_status yk_context_set_option(yk_context* ctx, const char* key, int64_t value)
     } else if (k == "wide_bvh") {
         if (value < 0 || value > 2) return YK_ERR_INVALID_ARGUMENT;
         ctx->wide_bvh = value;
+    } else if (k == "bvh_builder") {
+        if (value < 0 || value > 1) return YK_ERR_INVALID_ARGUMENT;
+        ctx->bvh_builder = value;
+    } else if (k == "bvh_small_range") {
+        if (value < 0 || value > (1 << 20)) return YK_ERR_INVALID_ARGUMENT;
+        ctx->bvh_small_range = value;
     } else if (k == "trace_stage_kernel") {
         if (value < 0 || value > 2) return YK_ERR_INVALID_ARGUMENT;
         ctx->trace_stage_kernel = value;
@@ -285,6 +291,7 @@ size_t yk_sizeof(int what) {
         case 12: return sizeof(yk_scene_info);
         case 13: return sizeof(yk_tone_map_desc);
         case 14: return sizeof(yk_integrator_ray);
+        case 15: return sizeof(yk_bvh_build_info);
         default: return 0;
     }
 }

@@ -38,6 +38,8 @@ struct DevBuf {
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+#define YK_BVH_SMALL_RANGE 32  // default of "bvh_small_range" (profiles/bvh_build_device.json: the sweep that chose it)
+
 struct yk_context {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -51,6 +53,8 @@ struct yk_context {
     int64_t overlap_shadow = 1;  // run {trace_any, accumulate}(b) on a side stream beside trace_closest(b+1)
     int64_t wide_bvh = 2;   // scenes created afterwards: 0 binary nodes only, 1 traverse the 4-wide collapse, 2 keep both and pick per job
     int64_t top_nodes = YK_TOP_MAX; // interior nodes (capped by what the kernels were built for) of the first tree levels the traversal kernels keep in LDS
+    int64_t bvh_builder = 0;       // scenes created afterwards: 0 the host recursion builds the tree, 1 the device builder where the input qualifies (yk_bvh_build.hip)
+    int64_t bvh_small_range = YK_BVH_SMALL_RANGE;  // ranges of at most this many shapes are finished by one lane each
     int64_t trace_stage_kernel = 0;  // which kernels yk_trace_closest / yk_trace_any launch (yk_stages.cpp): 0 generic, API flavour | 1 generic, render-loop flavour | 2 wave packets
     int64_t sample_buf_cap = (int64_t)64 << 30;
     int64_t time_kernels = 1;
@@ -98,6 +102,7 @@ struct yk_scene {
     uint32_t n_triangles = 0, n_spheres = 0, n_lights = 0, n_delta_lights = 0;
     bool wide_auto = false;  // both node layouts on the device: the 4-wide one is used for jobs below YK_WIDE_MAX_PATHS
     yk_scene_info info;
+    yk_bvh_build_info build_info;
     std::vector<uint8_t> shape_kind;  // source shape -> device BSDF kind of its material (the kind bits of a render-loop hit word)
     // device
     DevBuf nodes, nodes4, top_nodes, top_nodes_any, tris, prim_shade, prim_attr, indices, points, normals, uvs, tri_mesh, tri_material, tri_area_light, mesh_flags, materials, lights, spheres, texels, tex_info;
@@ -150,12 +155,18 @@ static inline yk_status fail(yk_context* ctx, yk_status st, const std::string& m
 // (BoundingVolumeHierarchy::new, bvh.rs:39-115) and the device records laid out from it.  Built once;
 // uploaded to one device (yk_scene_create) or to every device of a yk_multi (yk_multi_scene_create).
 struct SceneImage;
-yk_status yk_build_scene_image(yk_context* opt_ctx, const yk_scene_desc* d, std::shared_ptr<SceneImage>& out);
+yk_status yk_build_scene_image(yk_context* opt_ctx, const yk_scene_desc* d, std::shared_ptr<SceneImage>& out, bool device_builder_allowed = true);  // false: yk_multi_scene_create
 yk_status yk_upload_scene_image(yk_context* ctx, const std::shared_ptr<SceneImage>& img, yk_scene** out);
 
 static inline double now_seconds() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
+
+// ------------------------------------------------------------------ yk_bvh_build.hip
+// The level-synchronous builder (yk_bvh_build.h) on the device and its host instance.  Both return true with the
+// host recursion's tree in `out`, or false with bi.reason set and `out` untouched: the caller then runs build_bvh.
+bool build_bvh_device(yk_context* ctx, const std::vector<ShapeBounds>& bounds, uint32_t max_shapes_in_node, uint32_t split_method, uint32_t small_range, HostBvh& out, yk_bvh_build_info& bi);
+bool build_bvh_levels(const std::vector<ShapeBounds>& bounds, uint32_t max_shapes_in_node, uint32_t split_method, uint32_t small_range, HostBvh& out, yk_bvh_build_info& bi);
 
 // ------------------------------------------------------------------ yk_scene.cpp
 Material make_material(const yk_material_desc& m);  // per-hit constants folded (GGX alpha, Oren-Nayar A / B)

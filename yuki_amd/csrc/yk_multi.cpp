@@ -370,7 +370,7 @@ yk_status yk_multi_scene_create(yk_multi* m, const yk_scene_desc* desc, yk_multi
     *out = nullptr;
     // the host work — validation, BoundingVolumeHierarchy::new, device records — happens once
     std::shared_ptr<SceneImage> img;
-    yk_status st = yk_build_scene_image(m->ctx[0], desc, img);
+    yk_status st = yk_build_scene_image(m->ctx[0], desc, img, false);  // one host tree serves every device: the host recursion builds it
     if (st != YK_OK) return mfail(m, st, m->ctx[0]->last_error);
     std::unique_ptr<yk_multi_scene> s(new yk_multi_scene());
     s->owner = m;

@@ -91,6 +91,7 @@ struct SceneImage {
                                        // from the description, so an image is only valid inside the call that built it
     uint32_t n_triangles = 0, n_spheres = 0, n_lights = 0, n_delta_lights = 0;
     yk_scene_info info;  // host part: node counts, bounds, build time
+    yk_bvh_build_info build_info;
     bool has_device_records = false, wide = false, wide_auto = false;
     uint32_t root_ref = 0;
     std::vector<DevNode> dn, top, top_any;
@@ -107,7 +108,7 @@ struct SceneImage {
 
 // Host half of yk_scene_create: validation, BoundingVolumeHierarchy::new (bvh.rs:39-115) and — when `ctx` is given (its
 // "top_nodes" / "wide_bvh" options apply) — the device records laid out from the tree.
-yk_status yk_build_scene_image(yk_context* ctx, const yk_scene_desc* d, std::shared_ptr<SceneImage>& out) try {
+yk_status yk_build_scene_image(yk_context* ctx, const yk_scene_desc* d, std::shared_ptr<SceneImage>& out, bool device_builder_allowed) try {
     if (!d) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null scene description");
     out.reset();
     if ((uint64_t)d->n_triangles + d->n_spheres == 0) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "empty scene");
@@ -199,7 +200,23 @@ yk_status yk_build_scene_image(yk_context* ctx, const yk_scene_desc* d, std::sha
         sb.swap(ordered);
     }
     double t0 = now_seconds();
-    build_bvh(sb, d->max_shapes_in_node, d->split_method, *bvh);
+    // Who builds the tree: the host recursion unless the context's "bvh_builder" asks for the device or the environment
+    // (YK_BVH_BUILDER=levels, YK_BVH_SMALL_RANGE=n; next to YK_BVH_THREADS) for the host instance of the level algorithm.
+    // A level builder that refuses leaves its reason in the build info and the recursion builds the same tree.
+    yk_bvh_build_info& bi = s->build_info;
+    std::memset(&bi, 0, sizeof(bi));
+    bool built = false;
+    const char* env_builder = std::getenv("YK_BVH_BUILDER");
+    if (ctx && ctx->bvh_builder == 1 && device_builder_allowed) {
+        built = build_bvh_device(ctx, sb, d->max_shapes_in_node, d->split_method, (uint32_t)ctx->bvh_small_range, *bvh, bi);
+    } else if (env_builder && std::strcmp(env_builder, "levels") == 0) {
+        const char* e = std::getenv("YK_BVH_SMALL_RANGE");
+        built = build_bvh_levels(sb, d->max_shapes_in_node, d->split_method, e ? (uint32_t)std::max(0, std::atoi(e)) : (uint32_t)YK_BVH_SMALL_RANGE, *bvh, bi);
+    }
+    if (!built) {
+        bi.builder = YK_BVH_BUILDER_HOST;
+        build_bvh(sb, d->max_shapes_in_node, d->split_method, *bvh);
+    }
     s->info.build_seconds = now_seconds() - t0;
     if (d->shape_order)  // leaf order -> position in Scene.shapes -> source shape
         for (uint32_t& o : bvh->shape_order) o = d->shape_order[o];
@@ -464,6 +481,7 @@ yk_status yk_upload_scene_image(yk_context* ctx, const std::shared_ptr<SceneImag
     s->n_lights = img->n_lights;
     s->n_delta_lights = img->n_delta_lights;
     s->info = img->info;
+    s->build_info = img->build_info;
     s->shape_kind = img->shape_kind;
     if (ctx) {
         if (!img->has_device_records) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "scene image was built without device records");
@@ -564,6 +582,12 @@ void yk_scene_destroy(yk_scene* s) {
 yk_status yk_scene_get_info(const yk_scene* s, yk_scene_info* out) {
     if (!s || !out) return YK_ERR_INVALID_ARGUMENT;
     *out = s->info;
+    return YK_OK;
+}
+
+yk_status yk_scene_get_build_info(const yk_scene* s, yk_bvh_build_info* out) {
+    if (!s || !out) return YK_ERR_INVALID_ARGUMENT;
+    *out = s->build_info;
     return YK_OK;
 }
 
