@@ -275,7 +275,8 @@ yk_status yk_context_interrupt(yk_context* ctx);
  * qualifies — YK_SPLIT_SAH or YK_SPLIT_MIDDLE, finite bounds, no long range that needs select_nth — and by
  * the host recursion otherwise; the tree is the same either way, yk_scene_get_build_info says which ran)
  * and "bvh_small_range" (0 .. 2^20, default 32: ranges of at most this many shapes are finished by one
- * lane each) — the last four apply to scenes created afterwards.  Test hook: "trace_stage_kernel" (0, default: yk_trace_closest /
+ * lane each) — the last four apply to scenes created afterwards; "overlay_coop_min" (1 .. 65536, default 32: box
+ * edges of at least this many pixels are drawn by a whole wave in yk_overlay_draw[_device], shorter ones by one lane).  Test hook: "trace_stage_kernel" (0, default: yk_trace_closest /
  * yk_trace_any run the generic kernels as documented | 1: the generic kernels in the render loop's
  * flavour | 2: the wave-packet kernels; modes 1 and 2 report shape ids and verdicts only, and
  * refuse out_t, out_bary, counters, a closest-hit t_max and, in mode 2, a tree deeper than 64
@@ -482,6 +483,41 @@ yk_status yk_li_debug(yk_context* ctx, const yk_scene* scene, const yk_sampler_d
                       size_t n, const float* ray_o, const float* ray_d, const uint16_t* pixel_xy, const uint32_t* sample_index,
                       uint32_t dimension, uint32_t ray_cap, float* out_li, uint32_t* out_ray_counts,
                       yk_integrator_ray* out_rays, uint32_t* out_n_rays);
+
+/* ---- the overlays of draw_visualizations (app/window.rs:1033-1063) ------------
+ * RayVisualization (app/renderpasses/ray_visualization.rs) and BvhVisualization (bvh_visualization.rs) draw GL lines into
+ * the tone-mapped film, rays first, then boxes.  GL fixes no bit-level result for a line; the rule fixed here is stated
+ * in yuki_amd/csrc/yk_overlay.h (binary32, no FMA: clip coordinates, clipping to the view volume, one pixel per major-axis
+ * pixel centre, the last primitive in list order wins a pixel), and the host and the device instance agree bit for bit. */
+/* BoundingVolumeHierarchy::node_bounds (bvh.rs:121-157): the root box first when target_level <= 0, then the breadth-first
+ * walk from (node 0, level 1) that pushes both children's boxes of every interior node at target_level (at every level when
+ * target_level < 0): -1 gives n_nodes boxes, 0 the root alone.  Six floats a box (p_min, p_max).  Returns the number of
+ * boxes and writes min(cap, n) of them; out_bounds may be NULL.  A host function: works on a scene made without a device. */
+size_t yk_scene_node_bounds(const yk_scene* scene, int32_t target_level, float* out_bounds, size_t cap);
+/* The `world_to_clip` both passes build (ray_visualization.rs:80-150, bvh_visualization.rs:101-171), row-major:
+ * flip_y * (camera_to_clip * look_at), with zf the largest distance from the camera to a corner of scene_bounds (p_min,
+ * p_max of scene.bvh.bounds(), the root box) and zn = zf * 1e-5.  params->res_x / res_y: FilmSettings.res.  A host function.
+ * YK_ERR_INVALID_ARGUMENT: a non-finite bound, zf == 0, a degenerate look_at, a non-finite matrix entry. */
+yk_status yk_overlay_world_to_clip(const yk_camera_params* params, const float scene_bounds[6], float out[16]);
+typedef struct yk_overlay_line {
+    float p0[3], p1[3], rgb[3];
+} yk_overlay_line; /* 36 bytes: a world-space segment and its colour */
+/* RayVisualization::set_rays (:28-56): p0 = o, p1 = o + d * t_max per component, the colour by type (Direct white,
+ * Reflection red, Refraction green, Normal blue, Shadow yellow).  The reference indexes its vertices with u16, so
+ * more than 32,768 rays (or an unknown type) is YK_ERR_INVALID_ARGUMENT.  A host function. */
+yk_status yk_overlay_ray_lines(const yk_integrator_ray* rays, size_t n, yk_overlay_line* out);
+/* Draws the lines, then the boxes (six floats each, as yk_scene_node_bounds writes them: expanded into the reference's 8
+ * corners and 12 edges, red for an even array index, green for an odd one) into a row-major RGB film (h, w, 3) on the
+ * host.  ctx NULL = the host instance on the CPU, else on ctx's device (synchronous).  Pixels no primitive covers keep
+ * their bits.  YK_ERR_INVALID_ARGUMENT: NULL matrix or film, a zero resolution, a NULL list with a non-zero count,
+ * n_lines + 12 * n_boxes above 2^32 - 2. */
+yk_status yk_overlay_draw(yk_context* ctx, const float world_to_clip[16], const yk_overlay_line* lines, size_t n_lines, const float* boxes,
+                          size_t n_boxes, float* film_rgb, uint16_t res_x, uint16_t res_y);
+/* The same on device buffers, in place in d_film_rgb (4-byte alignment suffices), enqueued on `stream` (NULL = the
+ * context's) without waiting for the device.  The id buffer the passes share belongs to the context and is allocated on
+ * first use (and when a larger film comes): calls on one context are ordered only when they share a stream. */
+yk_status yk_overlay_draw_device(yk_context* ctx, const float world_to_clip[16], const void* d_lines, size_t n_lines, const void* d_boxes,
+                                 size_t n_boxes, void* d_film_rgb, uint16_t res_x, uint16_t res_y, void* stream);
 
 /* ---- per-stage entry points (parity tests, profiling) ------------------------- */
 /* BoundingVolumeHierarchy::intersect (bvh.rs:160-232) for n host rays.

@@ -148,12 +148,40 @@ class Scene {
         check(yk_scene_export_bvh(h_, nodes.data(), order.data()));
         return {std::move(nodes), std::move(order)};
     }
+    // BoundingVolumeHierarchy::node_bounds (bvh.rs:121-157): six floats a box (p_min, p_max); -1 = every node, 0 = the root
+    std::vector<float> node_bounds(int32_t target_level) const {
+        std::vector<float> out(6 * yk_scene_node_bounds(h_, target_level, nullptr, 0));
+        yk_scene_node_bounds(h_, target_level, out.data(), out.size() / 6);
+        return out;
+    }
 
    private:
     Context* ctx_;
     uint32_t n_lights_ = 0;
     yk_scene* h_ = nullptr;
 };
+
+// draw_visualizations (app/window.rs:1033-1063): RayVisualization and BvhVisualization drawn into a tone-mapped film.
+using OverlayLine = yk_overlay_line;
+// RayVisualization::set_rays (ray_visualization.rs:28-56)
+inline std::vector<OverlayLine> overlay_ray_lines(const std::vector<yk_integrator_ray>& rays) {
+    std::vector<OverlayLine> out(rays.size());
+    check(yk_overlay_ray_lines(rays.data(), rays.size(), out.data()));
+    return out;
+}
+// The rays of a debug sample (may be empty), then, when draw_level is set, the boxes of BVH level target_level (-1 = every level),
+// under the world_to_clip of the scene's root box.  ctx == nullptr: the host instance.  film: row-major RGB, res.x * res.y * 3.
+inline void draw_visualizations(Context* ctx, const Scene& scene, const yk_camera_params& camera_params, const std::vector<yk_integrator_ray>& rays,
+                                bool draw_level, int32_t target_level, float* film) {
+    const std::vector<float> root = scene.node_bounds(0);
+    float m[16];
+    check(yk_overlay_world_to_clip(&camera_params, root.data(), m));
+    const std::vector<OverlayLine> lines = overlay_ray_lines(rays);
+    const std::vector<float> boxes = draw_level ? scene.node_bounds(target_level) : std::vector<float>();
+    yk_context* c = ctx ? ctx->handle() : nullptr;
+    check(yk_overlay_draw(c, m, lines.empty() ? nullptr : lines.data(), lines.size(), boxes.empty() ? nullptr : boxes.data(), boxes.size() / 6, film,
+                          camera_params.res_x, camera_params.res_y), c);
+}
 
 // scene::pbrt::load / Scene::ply / scene::mitsuba::load (scene/pbrt/mod.rs:94, scene/mod.rs:99, scene/mitsuba/mod.rs:28): the parsed scene as a
 // ready yk_scene_desc plus the CameraParameters and FilmSettings the reference's loaders return

@@ -190,6 +190,15 @@ pub struct yk_integrator_ray {
     pub ray_type: u32,
 }
 
+/// A world-space segment and its colour (RayVisualization's two vertices of a line)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct yk_overlay_line {
+    pub p0: [f32; 3],
+    pub p1: [f32; 3],
+    pub rgb: [f32; 3],
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct yk_tile {
@@ -327,6 +336,11 @@ extern "C" {
     pub fn yk_tone_map(ctx: *mut yk_context, desc: *const yk_tone_map_desc, film_rgb: *const f32, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, out_rgb: *mut f32, used_bounds: *mut f32) -> yk_status;
     pub fn yk_tone_map_device(ctx: *mut yk_context, desc: *const yk_tone_map_desc, d_film_rgb: *const c_void, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, d_out_rgb: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_film_min_max(ctx: *mut yk_context, film_rgb: *const f32, res_x: u16, res_y: u16, channel: u32, out_min_max: *mut f32) -> yk_status;
+    pub fn yk_scene_node_bounds(scene: *const yk_scene, target_level: i32, out_bounds: *mut f32, cap: usize) -> usize;
+    pub fn yk_overlay_world_to_clip(params: *const yk_camera_params, scene_bounds: *const f32, out: *mut f32) -> yk_status;
+    pub fn yk_overlay_ray_lines(rays: *const yk_integrator_ray, n: usize, out: *mut yk_overlay_line) -> yk_status;
+    pub fn yk_overlay_draw(ctx: *mut yk_context, world_to_clip: *const f32, lines: *const yk_overlay_line, n_lines: usize, boxes: *const f32, n_boxes: usize, film_rgb: *mut f32, res_x: u16, res_y: u16) -> yk_status;
+    pub fn yk_overlay_draw_device(ctx: *mut yk_context, world_to_clip: *const f32, d_lines: *const c_void, n_lines: usize, d_boxes: *const c_void, n_boxes: usize, d_film_rgb: *mut c_void, res_x: u16, res_y: u16, stream: *mut c_void) -> yk_status;
     pub fn yk_render_tile(ctx: *mut yk_context, scene: *const yk_scene, camera: *const yk_camera, sampler: *const yk_sampler_desc, integrator: *const yk_integrator_desc, tile: *const yk_tile, tile_pixels: *mut f32, out_rays: *mut u64) -> yk_status;
     pub fn yk_film_update_tiles_device(ctx: *mut yk_context, tiles: *const yk_tile, n_tiles: usize, d_tile_rgb: *const c_void, res_x: u16, res_y: u16, d_film_rgb: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_li(ctx: *mut yk_context, scene: *const yk_scene, sampler: *const yk_sampler_desc, integrator: *const yk_integrator_desc, n: usize, ray_o: *const f32, ray_d: *const f32, pixel_xy: *const u16, sample_index: *const u32, dimension: u32, out_li: *mut f32, out_ray_counts: *mut u32) -> yk_status;

@@ -153,6 +153,11 @@ SYMBOLS = {
     "yk_tone_map": (C.c_int, [vp, C.POINTER(abi.ToneMapDesc), vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp]),
     "yk_tone_map_device": (C.c_int, [vp, C.POINTER(abi.ToneMapDesc), vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp]),
     "yk_film_min_max": (C.c_int, [vp, vp, C.c_uint16, C.c_uint16, C.c_uint32, vp]),
+    "yk_scene_node_bounds": (C.c_size_t, [vp, C.c_int32, vp, C.c_size_t]),
+    "yk_overlay_world_to_clip": (C.c_int, [C.POINTER(abi.CameraParams), vp, vp]),
+    "yk_overlay_ray_lines": (C.c_int, [vp, C.c_size_t, vp]),
+    "yk_overlay_draw": (C.c_int, [vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_uint16, C.c_uint16]),
+    "yk_overlay_draw_device": (C.c_int, [vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_uint16, C.c_uint16, vp]),
     # several GPUs
     "yk_multi_create": (C.c_int, [C.POINTER(C.c_int), C.c_uint32, C.POINTER(vp)]),
     "yk_multi_create_ex": (C.c_int, [C.POINTER(C.c_int), C.c_uint32, C.c_uint32, C.POINTER(vp)]),

@@ -220,6 +220,66 @@ def write_output(path, film, tone_map=None, settings=None, samples=None, ctx=Non
     write_exr(path, _apply_tone_map(film, tone_map, film_tile_dim(settings), samples, ctx, None))
 
 
+# --------------------------------------------------------------------------- overlays
+def _camera_params(params, res):
+    if isinstance(params, dict):
+        params = CameraParameters(**params)
+    p = abi.CameraParams()
+    p.position = abi.f3(params.position)
+    p.target = abi.f3(params.target)
+    p.up = abi.f3(params.up)
+    p.fov_axis = params.fov_axis
+    p.fov_degrees = params.fov_degrees
+    p.res_x, p.res_y = res
+    return p
+
+
+def overlay_world_to_clip(camera_params, film_settings, scene_bounds):
+    """The `world_to_clip` of RayVisualization::draw / BvhVisualization::draw (ray_visualization.rs:80-150): (4, 4) float32,
+    row-major.  scene_bounds: (p_min, p_max) of scene.bvh.bounds(), e.g. Scene.node_bounds(0)[0]."""
+    p = _camera_params(camera_params, film_settings.res)
+    bounds = np.ascontiguousarray(scene_bounds, dtype=np.float32).reshape(6)
+    out = np.zeros((4, 4), dtype=np.float32)
+    check(lib().yk_overlay_world_to_clip(C.byref(p), _p(bounds), _p(out)))
+    return out
+
+
+def overlay_ray_lines(rays):
+    """RayVisualization::set_rays (ray_visualization.rs:28-56): li_debug records (abi.INTEGRATOR_RAY_DTYPE) -> lines
+    (abi.OVERLAY_LINE_DTYPE) coloured by ray type."""
+    rays = np.ascontiguousarray(rays, dtype=abi.INTEGRATOR_RAY_DTYPE).reshape(-1)
+    out = np.zeros(len(rays), dtype=abi.OVERLAY_LINE_DTYPE)
+    check(lib().yk_overlay_ray_lines(_p(rays), len(rays), _p(out)))
+    return out
+
+
+def _overlay_args(world_to_clip, lines, boxes):
+    m = np.ascontiguousarray(world_to_clip, dtype=np.float32).reshape(16)
+    lines = None if lines is None else np.ascontiguousarray(lines, dtype=abi.OVERLAY_LINE_DTYPE).reshape(-1)
+    boxes = None if boxes is None else np.ascontiguousarray(boxes, dtype=np.float32).reshape(-1, 6)
+    return m, lines, boxes
+
+
+def draw_overlay(film, world_to_clip, lines=None, boxes=None, ctx=None):
+    """yk_overlay_draw: the lines, then the boxes ((n, 2, 3) or (n, 6): p_min, p_max), drawn into a copy of the
+    (h, w, 3) float32 film by the rule of csrc/yk_overlay.h.  ctx None = the host instance."""
+    out = np.array(film, dtype=np.float32, order="C", copy=True)
+    m, lines, boxes = _overlay_args(world_to_clip, lines, boxes)
+    c = ctx.h if ctx else None
+    check(lib().yk_overlay_draw(c, _p(m), _p(lines), 0 if lines is None else len(lines), _p(boxes), 0 if boxes is None else len(boxes), _p(out), out.shape[1], out.shape[0]), c)
+    return out
+
+
+def draw_visualizations(film, scene, camera_params, film_settings, rays=None, bvh_level=None, ctx=None):
+    """draw_visualizations (app/window.rs:1033-1063) on a tone-mapped (h, w, 3) film: the rays of a debug sample
+    (li_debug records, or None), then the boxes of BVH level `bvh_level` (-1 = every level, None = none), both under the
+    world_to_clip of the scene's root box.  Returns the new film; ctx None = the host instance."""
+    m = overlay_world_to_clip(camera_params, film_settings, scene.node_bounds(0)[0])
+    lines = None if rays is None else overlay_ray_lines(rays)
+    boxes = None if bvh_level is None else scene.node_bounds(bvh_level)
+    return draw_overlay(film, m, lines, boxes, ctx)
+
+
 class TileList:
     """A tile list prepared once on the device (yk_tile_list): the GPU worker's tile queue."""
 
@@ -358,6 +418,15 @@ class Context:
         samples = _tone_map_args(res, tone_map, tile_dim, samples)
         check(lib().yk_tone_map_device(self.h, C.byref(tone_map), C.c_void_p(d_film_ptr), res[0], res[1], int(tile_dim), _p(samples), C.c_void_p(d_out_ptr), C.c_void_p(stream) if stream else None), self.h)
 
+    def draw_overlay_device(self, d_film_ptr, res, world_to_clip, d_lines_ptr=None, n_lines=0, d_boxes_ptr=None, n_boxes=0, stream=None):
+        """yk_overlay_draw_device: n_lines yk_overlay_line records and n_boxes boxes of six floats, both on the device,
+        drawn in place into the device film; enqueued on `stream` (default: the context's) without waiting."""
+        m = np.ascontiguousarray(world_to_clip, dtype=np.float32).reshape(16)
+        check(
+            lib().yk_overlay_draw_device(self.h, _p(m), C.c_void_p(d_lines_ptr) if d_lines_ptr else None, int(n_lines), C.c_void_p(d_boxes_ptr) if d_boxes_ptr else None, int(n_boxes), C.c_void_p(d_film_ptr), res[0], res[1], C.c_void_p(stream) if stream else None),
+            self.h,
+        )
+
     @property
     def stream_handle(self):
         """The context's hipStream_t as an integer (yk_context_stream): wrap it, e.g. with
@@ -418,6 +487,14 @@ class Scene:
         order = np.zeros(i.n_shapes, dtype=np.uint32)
         check(lib().yk_scene_export_bvh(self.h, _p(nodes), _p(order)))
         return nodes, order
+
+    def node_bounds(self, level):
+        """BoundingVolumeHierarchy::node_bounds (bvh.rs:121-157): (n, 2, 3) float32 (p_min, p_max); level -1 = every
+        node's box, 0 = the root's."""
+        n = lib().yk_scene_node_bounds(self.h, int(level), None, 0)
+        out = np.zeros((n, 2, 3), dtype=np.float32)
+        lib().yk_scene_node_bounds(self.h, int(level), _p(out), n)
+        return out
 
     # per-stage entry points ---------------------------------------------------
     def intersect(self, o, d, t_max=None, counters=False):

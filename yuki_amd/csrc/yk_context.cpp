@@ -118,6 +118,7 @@ void yk_context_destroy(yk_context* ctx) {
     ctx->tonemap.partials.release();
     ctx->tonemap.bounds.release();
     ctx->tonemap.samples.release();
+    ctx->overlay.ids.release();
     if (ctx->tonemap.staging) (void)hipHostFree(ctx->tonemap.staging);
     if (ctx->tonemap.staged) (void)hipEventDestroy(ctx->tonemap.staged);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
@@ -176,6 +177,9 @@ yk_status yk_context_set_option(yk_context* ctx, const char* key, int64_t value)
     } else if (k == "trace_stage_kernel") {
         if (value < 0 || value > 2) return YK_ERR_INVALID_ARGUMENT;
         ctx->trace_stage_kernel = value;
+    } else if (k == "overlay_coop_min") {
+        if (value < 1 || value > 65536) return YK_ERR_INVALID_ARGUMENT;
+        ctx->overlay.coop_min = value;
     } else if (k == "time_kernels") {
         ctx->time_kernels = value;
     } else {
@@ -292,6 +296,7 @@ size_t yk_sizeof(int what) {
         case 13: return sizeof(yk_tone_map_desc);
         case 14: return sizeof(yk_integrator_ray);
         case 15: return sizeof(yk_bvh_build_info);
+        case 16: return sizeof(yk_overlay_line);
         default: return 0;
     }
 }

@@ -88,6 +88,11 @@ struct yk_context {
         size_t staging_words = 0;
         hipEvent_t staged = nullptr;       // the latest upload out of `staging`
     } tonemap;
+    // the overlay pass's buffers (yk_overlay.hip), grown on first use
+    struct OverlayState {
+        DevBuf ids;        // one u32 a pixel: the winning ordinal + 1
+        int64_t coop_min = 32;  // "overlay_coop_min": segments of at least this many pixels are drawn by a whole wave
+    } overlay;
     // every entry point that touches the context's buffers or streams holds this: calls on one
     // context from several host threads (the reference's tile workers) are serialised
     std::recursive_mutex mu;
