@@ -275,7 +275,11 @@ yk_status yk_context_interrupt(yk_context* ctx);
  * qualifies — YK_SPLIT_SAH or YK_SPLIT_MIDDLE, finite bounds, no long range that needs select_nth — and by
  * the host recursion otherwise; the tree is the same either way, yk_scene_get_build_info says which ran)
  * and "bvh_small_range" (0 .. 2^20, default 32: ranges of at most this many shapes are finished by one
- * lane each) — the last four apply to scenes created afterwards; "overlay_coop_min" (1 .. 65536, default 32: box
+ * lane each), "scene_layout" (0, default: the traversal records are laid out from the tree on the host and uploaded |
+ * 1: on the device, from the builder's tree in place or from an uploaded host-built one — the same bytes either way,
+ * yk_scene_get_layout_info says which ran; a device-built, device-laid scene copies its 32-byte nodes back only when
+ * yk_scene_export_bvh, yk_scene_node_bounds or a "trace_stage_kernel" stage call asks for them) — the last five apply
+ * to scenes created afterwards; "overlay_coop_min" (1 .. 65536, default 32: box
  * edges of at least this many pixels are drawn by a whole wave in yk_overlay_draw[_device], shorter ones by one lane).  Test hook: "trace_stage_kernel" (0, default: yk_trace_closest /
  * yk_trace_any run the generic kernels as documented | 1: the generic kernels in the render loop's
  * flavour | 2: the wave-packet kernels; modes 1 and 2 report shape ids and verdicts only, and
@@ -319,6 +323,38 @@ yk_status yk_scene_export_bvh(const yk_scene* scene, yk_bvh_node* nodes, uint32_
  * whole build whichever builder ran).  A fallback is silent for the result and visible here only.
  * Scenes of a yk_multi (yk_multi_scene_create) are always built by the host recursion. */
 yk_status yk_scene_get_build_info(const yk_scene* scene, yk_bvh_build_info* out);
+/* Where a scene's traversal records (the 64-byte nodes, the two LDS tree tops, the 4-wide collapse, the leaf-order
+ * tris / prim_shade / prim_attr) were laid out — "scene_layout" of yk_context_set_option — and what the traversal
+ * kernels are handed with them.  A device layout that fails falls back to the host layout: the scene is valid and
+ * `reason` says why.  Scenes of a yk_multi are always laid out on the host. */
+enum { YK_LAYOUT_HOST = 0, YK_LAYOUT_DEVICE = 1 };
+enum {
+    YK_LAYOUT_REASON_NONE = 0,
+    YK_LAYOUT_REASON_OUT_OF_MEMORY = 1, /* the layout could not get its device memory */
+    YK_LAYOUT_REASON_DEVICE_ERROR = 2,  /* a HIP call of the layout failed */
+    YK_LAYOUT_REASON_MULTI = 3          /* a scene of a yk_multi */
+};
+typedef struct yk_scene_layout_info {
+    uint32_t layout;       /* YK_LAYOUT_* : who laid the records out */
+    uint32_t reason;       /* YK_LAYOUT_REASON_* : non-zero when the device layout was asked for and not used */
+    double seconds_upload; /* device layout: the tree (when the host built it) and the small tables to the device */
+    double seconds_layout; /* device layout: the layout kernels */
+    uint32_t tree_fetched; /* 1 once the host copy of the 32-byte nodes and the shape order exists (always 1 for a host-built tree;
+                            * a device-built, device-laid scene copies them back on the first call that reads them) */
+    uint32_t root_ref, n_top, n_top_any, wide, wide_auto; /* DevScene's root reference and tree-top sizes; whether the 4-wide
+                                                           * nodes exist and whether they serve small jobs only ("wide_bvh" = 2) */
+} yk_scene_layout_info;
+yk_status yk_scene_get_layout_info(const yk_scene* scene, yk_scene_layout_info* out);
+/* Test hook: one of the scene's device record buffers copied back, however it was laid out.  *n_bytes receives the
+ * buffer's size; with out == NULL that is all, otherwise cap_bytes must be at least that (YK_ERR_INVALID_ARGUMENT). */
+enum { YK_RECORDS_NODES = 0, YK_RECORDS_NODES4 = 1, YK_RECORDS_TOP = 2, YK_RECORDS_TOP_ANY = 3, YK_RECORDS_TRIS = 4, YK_RECORDS_PRIM_SHADE = 5, YK_RECORDS_PRIM_ATTR = 6 };
+yk_status yk_scene_read_records(const yk_scene* scene, uint32_t which, void* out, size_t cap_bytes, size_t* n_bytes);
+/* Test hooks: the host instance of the two order rules of the device layout (yuki_amd/csrc/yk_scene_layout.h) over an
+ * exported tree of n nodes.  yk_layout_top_order: the reference node indices of the tree top of at most `cap` nodes,
+ * breadth first; returns their number (out_order: cap entries).  yk_layout_wide_slots: the DevNode4 index of every
+ * reference node the 4-wide collapse keeps, 0xffffffff for the others; returns the number of DevNode4 (0: leaf root). */
+size_t yk_layout_top_order(const yk_bvh_node* nodes, size_t n, uint32_t cap, uint32_t* out_order);
+size_t yk_layout_wide_slots(const yk_bvh_node* nodes, size_t n, uint32_t* out_slot_per_node);
 /* Test hook: the partition step of the level builder on its own.  pass[i] says whether the element at
  * position i passes the predicate; `order` (n words, in and out) is rearranged exactly as the two-ended
  * swap partition of the host recursion (itertools::partition) would.  Returns the number passing. */

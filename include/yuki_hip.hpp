@@ -141,6 +141,18 @@ class Scene {
         check(yk_scene_get_build_info(h_, &i));
         return i;
     }
+    yk_scene_layout_info layout_info() const {  // who laid the traversal records out ("scene_layout"), and whether the host tree is fetched
+        yk_scene_layout_info i;
+        check(yk_scene_get_layout_info(h_, &i));
+        return i;
+    }
+    std::vector<uint8_t> device_records(uint32_t which) const {  // test hook: one record buffer (YK_RECORDS_*) copied back
+        size_t n = 0;
+        check(yk_scene_read_records(h_, which, nullptr, 0, &n));
+        std::vector<uint8_t> out(n);
+        check(yk_scene_read_records(h_, which, out.data(), out.size(), &n));
+        return out;
+    }
     std::pair<std::vector<yk_bvh_node>, std::vector<uint32_t>> export_bvh() const {
         yk_scene_info i = info();
         std::vector<yk_bvh_node> nodes(i.n_nodes);

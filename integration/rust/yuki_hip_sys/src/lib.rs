@@ -253,6 +253,24 @@ pub struct yk_bvh_build_info {
     pub seconds_copy_back: f64,
 }
 
+pub const YK_LAYOUT_HOST: u32 = 0;
+pub const YK_LAYOUT_DEVICE: u32 = 1;
+
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct yk_scene_layout_info {
+    pub layout: u32,
+    pub reason: u32,
+    pub seconds_upload: f64,
+    pub seconds_layout: f64,
+    pub tree_fetched: u32,
+    pub root_ref: u32,
+    pub n_top: u32,
+    pub n_top_any: u32,
+    pub wide: u32,
+    pub wide_auto: u32,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct yk_combiner_info {
@@ -311,6 +329,7 @@ extern "C" {
     pub fn yk_scene_get_info(scene: *const yk_scene, out: *mut yk_scene_info) -> yk_status;
     pub fn yk_scene_export_bvh(scene: *const yk_scene, nodes: *mut yk_bvh_node, shape_order: *mut u32) -> yk_status;
     pub fn yk_scene_get_build_info(scene: *const yk_scene, out: *mut yk_bvh_build_info) -> yk_status;
+    pub fn yk_scene_get_layout_info(scene: *const yk_scene, out: *mut yk_scene_layout_info) -> yk_status;
     pub fn yk_render_tiles(ctx: *mut yk_context, scene: *const yk_scene, camera: *const yk_camera, sampler: *const yk_sampler_desc, integrator: *const yk_integrator_desc, tiles: *const yk_tile, n_tiles: usize, out_rgb: *mut f32, stats: *mut yk_render_stats, cancel: yk_cancel_fn, user: *mut c_void) -> yk_status;
     pub fn yk_render_tiles_device(ctx: *mut yk_context, scene: *const yk_scene, camera: *const yk_camera, sampler: *const yk_sampler_desc, integrator: *const yk_integrator_desc, tiles: *const yk_tile, n_tiles: usize, d_out_rgb: *mut c_void, stream: *mut c_void, stats: *mut yk_render_stats, cancel: yk_cancel_fn, user: *mut c_void) -> yk_status;
     pub fn yk_render_tiles_accumulating(ctx: *mut yk_context, scene: *const yk_scene, camera: *const yk_camera, sampler: *const yk_sampler_desc, integrator: *const yk_integrator_desc, tiles: *const yk_tile, tile_samples: *const u16, n_tiles: usize, out_rgb: *mut f32, stats: *mut yk_render_stats, cancel: yk_cancel_fn, user: *mut c_void) -> yk_status;

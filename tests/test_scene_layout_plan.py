@@ -1,0 +1,116 @@
+"""The two order rules of the device scene layout ("scene_layout" = 1, yuki_amd/csrc/yk_scene_layout.h), host instance,
+proven without a GPU: the breadth-first tree top under the host loop's admission rule and the slot numbering of the
+4-wide collapse, both in closed form, against a restatement of the sequential loops of yk_scene.cpp
+(layout_records_host: build_top and the DevNode4 stack walk)."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from yuki_amd import abi, scenes
+
+from test_bvh_levels import SCENES, _one_and_seven
+
+NONE = 0xFFFFFFFF
+CAPS = (0, 1, 2, 3, 7, 1023)
+METHODS = (abi.SPLIT_SAH, abi.SPLIT_MIDDLE, abi.SPLIT_EQUAL_COUNTS)
+
+
+def _top_order_loop(is_leaf, a, cap):
+    """build_top: a child is admitted only while the set is below cap, checked when it is seen."""
+    if is_leaf[0] or cap == 0:
+        return []
+    order = [0]
+    q = 0
+    while q < len(order) and len(order) < cap:
+        P = order[q]
+        for c in (P + 1, a[P]):
+            if not is_leaf[c] and len(order) < cap:
+                order.append(c)
+        q += 1
+    return order
+
+
+def _wide_slots_loop(is_leaf, a):
+    """The DevNode4 stack walk: slot per reference node, and the number of DevNode4."""
+    slot = [NONE] * len(is_leaf)
+    if is_leaf[0]:
+        return slot, 0
+    n4 = 1
+    slot[0] = 0
+    stack = [(0, 0)]
+    while stack:
+        P, _ = stack.pop()
+        A, B = P + 1, a[P]
+        child = [A, NONE] if is_leaf[A] else [A + 1, a[A]]
+        child += [B, NONE] if is_leaf[B] else [B + 1, a[B]]
+        ref = [NONE] * 4
+        for k in range(4):
+            if child[k] == NONE or is_leaf[child[k]]:
+                continue
+            ref[k] = n4
+            slot[child[k]] = n4
+            n4 += 1
+        for k in (3, 2, 1, 0):
+            if ref[k] != NONE:
+                stack.append((child[k], ref[k]))
+    return slot, n4
+
+
+def _check(yk, sd):
+    L = yk.lib()
+    nodes, _ = yk.Scene(None, sd).export_bvh()
+    n = len(nodes)
+    is_leaf, a = (nodes["is_leaf"] != 0).tolist(), nodes["a"].tolist()
+    for cap in CAPS:
+        want = _top_order_loop(is_leaf, a, cap)
+        got = np.full(max(cap, 1), NONE, dtype=np.uint32)
+        k = L.yk_layout_top_order(nodes.ctypes.data_as(C.c_void_p), n, cap, got.ctypes.data_as(C.c_void_p))
+        assert k == len(want), (cap, k, len(want))
+        assert got[:k].tolist() == want, cap
+        assert (got[k:] == NONE).all()  # nothing is written past the set
+    want_slot, want_n4 = _wide_slots_loop(is_leaf, a)
+    got = np.zeros(n, dtype=np.uint32)
+    n4 = L.yk_layout_wide_slots(nodes.ctypes.data_as(C.c_void_p), n, got.ctypes.data_as(C.c_void_p))
+    assert n4 == want_n4
+    assert got.tolist() == want_slot
+    return nodes
+
+
+@pytest.mark.parametrize("name", list(SCENES))
+@pytest.mark.parametrize("method", METHODS)
+@pytest.mark.parametrize("max_shapes", [1, 4])
+def test_order_rules_on_the_scenes(yk, name, method, max_shapes):
+    sd = SCENES[name]()
+    sd.split_method, sd.max_shapes_in_node = method, max_shapes
+    _check(yk, sd)
+
+
+def _first_triangles(k, xs):
+    """k triangles of one shape, moved to the given x offsets."""
+    base = scenes.by_name("city-tiny")
+    tri = base.points[:3].astype(np.float32)
+    pts = np.concatenate([tri + np.array([x, 0.0, 0.0], dtype=np.float32) for x in xs]).astype(np.float32)
+    idx = np.arange(3 * k, dtype=np.uint32).reshape(k, 3)
+    return scenes.SceneData(points=pts, indices=idx, tri_mesh=np.zeros(k, np.uint32), tri_material=np.zeros(k, np.int32), tri_area_light=np.full(k, -1, np.int32),
+                            meshes=[(False, False, False)], materials=base.materials[:1], lights=base.lights, camera=base.camera)
+
+
+@pytest.mark.parametrize("method", METHODS)
+def test_order_rules_on_degenerate_trees(yk, method):
+    one, _ = _one_and_seven()
+    one.split_method = method
+    nodes = _check(yk, one)
+    assert len(nodes) == 1 and nodes["is_leaf"][0]  # a leaf root: no top, no collapse
+    two = _first_triangles(2, (0.0, 10.0))
+    two.split_method = method
+    nodes = _check(yk, two)
+    assert len(nodes) == 3  # an interior root over two leaves: the collapse is its root alone
+
+
+def test_order_rules_with_a_leaf_beside_an_interior_child(yk):
+    sd = _first_triangles(3, (0.0, 100.0, 101.0))  # Middle: one triangle left of the middle, two right of it
+    sd.split_method, sd.max_shapes_in_node = abi.SPLIT_MIDDLE, 1
+    nodes = _check(yk, sd)
+    assert len(nodes) == 5 and not nodes["is_leaf"][0]
+    assert nodes["is_leaf"][1] and not nodes["is_leaf"][int(nodes["a"][0])]  # the root's children: a leaf, then an interior node

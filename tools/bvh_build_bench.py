@@ -10,6 +10,13 @@ small-range limit S (and, with --use-sweep-best, runs the alternating builds wit
 
     python tools/bvh_build_bench.py --out profiles/bvh_build_device.json
     python tools/bvh_build_bench.py --scenes cfg5 --builds 1 --no-host      # one device build, e.g. under a kernel trace
+
+`--layout` measures the device scene layout ("scene_layout" = 1) instead: after a warm-up of each, (bvh_builder 1,
+scene_layout 0) — the yardstick — and (bvh_builder 1, scene_layout 1) alternate, `--builds` yk_scene_create calls each;
+recorded per call: its wall time and the phase split (build, builder phases, layout upload / kernels).  The warm-up
+compares the seven device record buffers of the two (bytes).
+
+    python tools/bvh_build_bench.py --layout --out profiles/scene_layout_device.json
 """
 import argparse
 import hashlib
@@ -37,9 +44,59 @@ def build(ctx, sd):
     return s, rec
 
 
+def records_digest(s):
+    return [hashlib.sha256(s.device_records(name).tobytes()).hexdigest() for name in abi.RECORD_NAMES]
+
+
+def layout_bench(a):
+    """(builder 1, layout 0) against (builder 1, layout 1), alternating, one process."""
+    ctxs = {0: yk.Context(0, bvh_builder=1), 1: yk.Context(0, bvh_builder=1, scene_layout=1)}
+    result = dict(tool="tools/bvh_build_bench.py --layout", split_method="SAH", max_shapes_in_node=1, scenes={})
+    for name in a.scenes.split(","):
+        sd = scenes.by_name(name)
+        sd.split_method, sd.max_shapes_in_node = abi.SPLIT_SAH, 1
+        out = dict(n_shapes=int(sd.n_triangles), layout0=[], layout1=[])
+
+        def create(layout):
+            s, rec = build(ctxs[layout], sd)
+            li = s.layout_info()
+            assert rec["builder"] == 1 and rec["reason"] == 0 and (li.layout, li.reason) == (layout, 0), (rec, li.layout, li.reason)
+            rec.update(layout=int(li.layout), layout_seconds_upload=li.seconds_upload, layout_seconds_layout=li.seconds_layout, device_bytes=int(s.info().device_bytes))
+            return s, rec
+
+        want = None
+        for layout in (0, 1):  # warm-up, and the comparison
+            s, _ = create(layout)
+            got = records_digest(s)
+            assert want is None or got == want, "device-laid records differ from the host-laid ones"
+            want = got
+            s.close()
+        for k in range(a.builds):
+            for layout in (0, 1):
+                s, rec = create(layout)
+                s.close()
+                out[f"layout{layout}"].append(rec)
+                print(f"{name} layout {layout} #{k}: scene_create {rec['scene_create_seconds']:.4f} s, build {rec['build_seconds']:.4f} s (copy_back {rec['seconds_copy_back']:.4f}), upload {rec['upload_seconds']:.4f} s"
+                      f" (layout: upload {rec['layout_seconds_upload']:.4f}, kernels {rec['layout_seconds_layout']:.4f})", flush=True)
+        out["layout0_fastest_create_seconds"] = min(r["scene_create_seconds"] for r in out["layout0"])
+        out["layout1_slowest_create_seconds"] = max(r["scene_create_seconds"] for r in out["layout1"])
+        out["layout1_slowest_below_layout0_fastest"] = out["layout1_slowest_create_seconds"] < out["layout0_fastest_create_seconds"]
+        result["scenes"][name] = out
+    return result
+
+
 def digest(s):
     n, o = s.export_bvh()
     return hashlib.sha256(n.tobytes()).hexdigest() + hashlib.sha256(o.tobytes()).hexdigest()
+
+
+def write(result, path):
+    print(json.dumps(result))
+    if path:
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        with open(path, "w") as f:
+            json.dump(result, f, indent=1)
+            f.write("\n")
 
 
 def main():
@@ -50,8 +107,12 @@ def main():
     ap.add_argument("--small-range", type=int, default=-1, help="small-range limit of the alternating runs (default: the library's)")
     ap.add_argument("--use-sweep-best", action="store_true", help="run the alternating builds with the sweep's fastest limit instead")
     ap.add_argument("--no-host", action="store_true", help="device builds only (no baseline, no comparison)")
+    ap.add_argument("--layout", action="store_true", help='measure "scene_layout" = 1 against 0, both on a device-built tree')
     ap.add_argument("--out", default="")
     a = ap.parse_args()
+    if a.layout:
+        write(layout_bench(a), a.out)
+        return
     host_ctx, dev_ctx = yk.Context(0), yk.Context(0)
     dev_ctx.set_option("bvh_builder", 1)
     result = dict(tool="tools/bvh_build_bench.py", split_method="SAH", max_shapes_in_node=1, scenes={})
@@ -100,13 +161,7 @@ def main():
             out["device_slowest_build_seconds"] = max(r["build_seconds"] for r in out["device"])
             out["device_slowest_below_host_fastest"] = out["device_slowest_build_seconds"] < out["host_fastest_build_seconds"]
         result["scenes"][name] = out
-    line = json.dumps(result)
-    print(line)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(result, f, indent=1)
-            f.write("\n")
+    write(result, a.out)
 
 
 if __name__ == "__main__":

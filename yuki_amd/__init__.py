@@ -6,6 +6,7 @@ Integrator / Sampler / Film / Camera / Scene interface plus the synthetic scene
 generators; importing the stage API fails loudly if the library is missing.
 """
 from . import abi, scenes  # noqa: F401
+from .abi import LAYOUT_DEVICE, LAYOUT_HOST, RECORD_NAMES, SceneLayoutInfo  # noqa: F401  ("scene_layout": Scene.layout_info / device_records)
 
 
 def __getattr__(name):

@@ -111,6 +111,10 @@ SYMBOLS = {
     "yk_scene_export_bvh": (C.c_int, [vp, vp, vp]),
     "yk_scene_get_build_info": (C.c_int, [vp, C.POINTER(BvhBuildInfo)]),
     "yk_bvh_partition_plan": (C.c_size_t, [vp, C.c_size_t, vp]),
+    "yk_scene_get_layout_info": (C.c_int, [vp, C.POINTER(abi.SceneLayoutInfo)]),
+    "yk_scene_read_records": (C.c_int, [vp, C.c_uint32, vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "yk_layout_top_order": (C.c_size_t, [vp, C.c_size_t, C.c_uint32, vp]),
+    "yk_layout_wide_slots": (C.c_size_t, [vp, C.c_size_t, vp]),
     "yk_render_tiles": (C.c_int, [vp, vp, C.POINTER(abi.CameraMatrices), C.POINTER(abi.SamplerDesc), C.POINTER(abi.IntegratorDesc), vp, C.c_size_t, vp, C.POINTER(RenderStats), vp, vp]),
     "yk_render_tiles_device": (C.c_int, [vp, vp, C.POINTER(abi.CameraMatrices), C.POINTER(abi.SamplerDesc), C.POINTER(abi.IntegratorDesc), vp, C.c_size_t, vp, vp, C.POINTER(RenderStats), vp, vp]),
     "yk_render_tile": (C.c_int, [vp, vp, C.POINTER(abi.CameraMatrices), C.POINTER(abi.SamplerDesc), C.POINTER(abi.IntegratorDesc), C.POINTER(abi.Tile), vp, C.POINTER(C.c_uint64)]),

@@ -135,6 +135,23 @@ class BvhNode(C.Structure):
     ]
 
 
+class SceneLayoutInfo(C.Structure):
+    """yk_scene_layout_info: who laid a scene's traversal records out ("scene_layout"), and what the kernels get with them."""
+
+    _fields_ = [
+        ("layout", C.c_uint32),
+        ("reason", C.c_uint32),
+        ("seconds_upload", C.c_double),
+        ("seconds_layout", C.c_double),
+        ("tree_fetched", C.c_uint32),
+        ("root_ref", C.c_uint32),
+        ("n_top", C.c_uint32),
+        ("n_top_any", C.c_uint32),
+        ("wide", C.c_uint32),
+        ("wide_auto", C.c_uint32),
+    ]
+
+
 class TraceStats(C.Structure):
     _fields_ = [
         ("closest_rays", C.c_uint64),
@@ -163,6 +180,10 @@ RAY_DIRECT, RAY_REFLECTION, RAY_REFRACTION, RAY_NORMAL, RAY_SHADOW = 0, 1, 2, 3,
 FOV_X, FOV_Y = 0, 1
 TONE_MAP_RAW, TONE_MAP_FILMIC, TONE_MAP_HEATMAP = 0, 1, 2
 HEATMAP_RED, HEATMAP_GREEN, HEATMAP_BLUE, HEATMAP_LUMINANCE = 0, 1, 2, 3
+LAYOUT_HOST, LAYOUT_DEVICE = 0, 1
+LAYOUT_REASON_NONE, LAYOUT_REASON_OUT_OF_MEMORY, LAYOUT_REASON_DEVICE_ERROR, LAYOUT_REASON_MULTI = 0, 1, 2, 3
+RECORDS_NODES, RECORDS_NODES4, RECORDS_TOP, RECORDS_TOP_ANY, RECORDS_TRIS, RECORDS_PRIM_SHADE, RECORDS_PRIM_ATTR = range(7)
+RECORD_NAMES = ("nodes", "nodes4", "top", "top_any", "tris", "prim_shade", "prim_attr")
 
 
 def ptr(a, ty):

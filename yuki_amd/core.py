@@ -481,6 +481,23 @@ class Scene:
         check(lib().yk_scene_get_build_info(self.h, C.byref(i)))
         return i
 
+    def layout_info(self):
+        """yk_scene_get_layout_info: who laid the traversal records out (abi.LAYOUT_*), why not the device (abi.LAYOUT_REASON_*),
+        whether the host copy of the tree exists yet, and the root ref / tree-top sizes / wide flags the kernels are handed."""
+        i = abi.SceneLayoutInfo()
+        check(lib().yk_scene_get_layout_info(self.h, C.byref(i)))
+        return i
+
+    def device_records(self, which):
+        """yk_scene_read_records: one of the scene's device record buffers (abi.RECORDS_* or a name of abi.RECORD_NAMES) as uint8."""
+        if isinstance(which, str):
+            which = abi.RECORD_NAMES.index(which)
+        n = C.c_size_t(0)
+        check(lib().yk_scene_read_records(self.h, int(which), None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=np.uint8)
+        check(lib().yk_scene_read_records(self.h, int(which), _p(out), out.nbytes, C.byref(n)))
+        return out
+
     def export_bvh(self):
         i = self.info()
         nodes = np.zeros(i.n_nodes, dtype=abi.BVH_NODE_DTYPE)

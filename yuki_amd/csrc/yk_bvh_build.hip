@@ -222,6 +222,12 @@ struct DevBufs {  // freed on every way out
         out = reinterpret_cast<T*>(p);
         return true;
     }
+    template <class T> void give(T* p, size_t count, DevBuf& to) {  // hands one buffer on to a new owner
+        all.erase(std::find(all.begin(), all.end(), (void*)p));
+        to.release();
+        to.p = p;
+        to.bytes = std::max<size_t>(count * sizeof(T), 16);
+    }
 };
 
 bool refuse(yk_bvh_build_info& bi, uint32_t reason) {
@@ -238,7 +244,7 @@ void words_to_nodes(const uint32_t* w, size_t n, std::vector<yk_bvh_node>& out) 
 }  // namespace
 
 // ------------------------------------------------------------------ the device builder
-bool build_bvh_device(yk_context* ctx, const std::vector<ShapeBounds>& sb, uint32_t max_shapes, uint32_t method, uint32_t small_range, HostBvh& out, yk_bvh_build_info& bi) {
+bool build_bvh_device(yk_context* ctx, const std::vector<ShapeBounds>& sb, uint32_t max_shapes, uint32_t method, uint32_t small_range, HostBvh& out, yk_bvh_build_info& bi, DeviceTree* keep) {
     bi.small_range = small_range;
     if (method != YK_SPLIT_SAH && method != YK_SPLIT_MIDDLE) return refuse(bi, YK_BVH_REASON_SPLIT_METHOD);
     if (sb.empty() || sb.size() > ((size_t)1 << 28)) return refuse(bi, YK_BVH_REASON_TOO_MANY_NODES);
@@ -339,14 +345,25 @@ bool build_bvh_device(yk_context* ctx, const std::vector<ShapeBounds>& sb, uint3
     DEV_TRY(hipStreamSynchronize(st));
     bi.seconds_layout = now_seconds() - t0;
 
-    // ---- copy back
+    // ---- copy back: the arrays, or node 0 alone when the tree stays in HBM for the device layout
     t0 = now_seconds();
-    std::vector<yk_bvh_node> nodes(n_nodes);
-    std::vector<uint32_t> order(N);
-    DEV_TRY(hipMemcpyAsync(nodes.data(), d_nodes, (size_t)n_nodes * 32, hipMemcpyDeviceToHost, st));
-    DEV_TRY(hipMemcpyAsync(order.data(), d_shape, (size_t)N * 4, hipMemcpyDeviceToHost, st));
+    std::vector<yk_bvh_node> nodes(keep ? 0 : n_nodes);
+    std::vector<uint32_t> order(keep ? 0 : N);
+    if (keep) {
+        DEV_TRY(hipMemcpyAsync(keep->root_words, d_nodes, 32, hipMemcpyDeviceToHost, st));
+    } else {
+        DEV_TRY(hipMemcpyAsync(nodes.data(), d_nodes, (size_t)n_nodes * 32, hipMemcpyDeviceToHost, st));
+        DEV_TRY(hipMemcpyAsync(order.data(), d_shape, (size_t)N * 4, hipMemcpyDeviceToHost, st));
+    }
     DEV_TRY(hipStreamSynchronize(st));
 #undef DEV_TRY
+    if (keep) {
+        mem.give(d_nodes, 8 * (size_t)n_slots, keep->nodes);
+        mem.give(d_depth, n_slots, keep->depth);
+        mem.give(d_shape, N, keep->order);
+        keep->n_nodes = n_nodes;
+        keep->n_shapes = N;
+    }
     out.nodes.swap(nodes);
     out.shape_order.swap(order);
     out.max_leaf_shapes = ctr.max_leaf;

@@ -174,6 +174,9 @@ yk_status yk_context_set_option(yk_context* ctx, const char* key, int64_t value)
     } else if (k == "bvh_small_range") {
         if (value < 0 || value > (1 << 20)) return YK_ERR_INVALID_ARGUMENT;
         ctx->bvh_small_range = value;
+    } else if (k == "scene_layout") {
+        if (value < 0 || value > 1) return YK_ERR_INVALID_ARGUMENT;
+        ctx->scene_layout = value;
     } else if (k == "trace_stage_kernel") {
         if (value < 0 || value > 2) return YK_ERR_INVALID_ARGUMENT;
         ctx->trace_stage_kernel = value;
@@ -297,6 +300,7 @@ size_t yk_sizeof(int what) {
         case 14: return sizeof(yk_integrator_ray);
         case 15: return sizeof(yk_bvh_build_info);
         case 16: return sizeof(yk_overlay_line);
+        case 17: return sizeof(yk_scene_layout_info);
         default: return 0;
     }
 }

@@ -55,6 +55,7 @@ struct yk_context {
     int64_t top_nodes = YK_TOP_MAX; // interior nodes (capped by what the kernels were built for) of the first tree levels the traversal kernels keep in LDS
     int64_t bvh_builder = 0;       // scenes created afterwards: 0 the host recursion builds the tree, 1 the device builder where the input qualifies (yk_bvh_build.hip)
     int64_t bvh_small_range = YK_BVH_SMALL_RANGE;  // ranges of at most this many shapes are finished by one lane each
+    int64_t scene_layout = 0;      // scenes created afterwards: 0 the device records are laid out on the host and uploaded, 1 on the device (yk_scene_layout.hip)
     int64_t trace_stage_kernel = 0;  // which kernels yk_trace_closest / yk_trace_any launch (yk_stages.cpp): 0 generic, API flavour | 1 generic, render-loop flavour | 2 wave packets
     int64_t sample_buf_cap = (int64_t)64 << 30;
     int64_t time_kernels = 1;
@@ -101,9 +102,31 @@ struct yk_context {
 typedef yk_context::WorkSet WorkSet;
 static const uint32_t YK_WIDE_MAX_PATHS = 6u << 20;  // jobs up to this many paths traverse the 4-wide nodes (wide_bvh = 2)
 
+// A tree in HBM: the builder's 32-byte nodes (8 words each, yk_bvh_build.h), every node's depth and the leaf order —
+// left there by build_bvh_device for the device layout, or uploaded for it from a host-built tree.
+struct DeviceTree {
+    DevBuf nodes, depth, order;
+    uint32_t n_nodes = 0, n_shapes = 0;
+    uint32_t root_words[8] = {};  // node 0
+    void release() {
+        nodes.release();
+        depth.release();
+        order.release();
+    }
+};
+
 struct yk_scene {
     int device = -1;  // a scene belongs to the device, not to the context that made it: any context there renders it, and it may outlive them
-    std::shared_ptr<const HostBvh> bvh;  // one host tree may serve the copies of a scene on several devices (yk_multi_scene)
+    // One host tree may serve the copies of a scene on several devices (yk_multi_scene).  Its scalars (depth, max_leaf_shapes)
+    // are always there; a device-built, device-laid scene leaves `nodes` and `shape_order` in HBM (tree_nodes, tree_order)
+    // until something reads them: every reader of the two arrays goes through scene_host_tree().
+    std::shared_ptr<const HostBvh> bvh;
+    std::shared_ptr<HostBvh> bvh_lazy;  // the same object, writable: set while the arrays are still to be fetched
+    DevBuf tree_nodes, tree_order;
+    mutable std::once_flag tree_once;
+    mutable std::atomic<uint32_t> tree_fetched{1};
+    yk_scene_layout_info layout = {};
+    size_t record_bytes[7] = {};  // exact sizes of the seven record buffers (YK_RECORDS_*; a DevBuf is never smaller than 16 bytes)
     uint32_t n_triangles = 0, n_spheres = 0, n_lights = 0, n_delta_lights = 0;
     bool wide_auto = false;  // both node layouts on the device: the 4-wide one is used for jobs below YK_WIDE_MAX_PATHS
     yk_scene_info info;
@@ -163,6 +186,10 @@ struct SceneImage;
 yk_status yk_build_scene_image(yk_context* opt_ctx, const yk_scene_desc* d, std::shared_ptr<SceneImage>& out, bool device_builder_allowed = true);  // false: yk_multi_scene_create
 yk_status yk_upload_scene_image(yk_context* ctx, const std::shared_ptr<SceneImage>& img, yk_scene** out);
 
+// The scene's host tree with its node and shape-order arrays, copied back from HBM on the first call when the scene kept
+// them there (thread-safe).  NULL when that copy fails.
+const HostBvh* scene_host_tree(const yk_scene* scene);
+
 static inline double now_seconds() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
@@ -170,8 +197,17 @@ static inline double now_seconds() {
 // ------------------------------------------------------------------ yk_bvh_build.hip
 // The level-synchronous builder (yk_bvh_build.h) on the device and its host instance.  Both return true with the
 // host recursion's tree in `out`, or false with bi.reason set and `out` untouched: the caller then runs build_bvh.
-bool build_bvh_device(yk_context* ctx, const std::vector<ShapeBounds>& bounds, uint32_t max_shapes_in_node, uint32_t split_method, uint32_t small_range, HostBvh& out, yk_bvh_build_info& bi);
+// With `keep`, build_bvh_device leaves nodes, depths and order in HBM (DeviceTree) instead of copying them back: `out` then
+// receives the scalars only and its two arrays stay empty.
+bool build_bvh_device(yk_context* ctx, const std::vector<ShapeBounds>& bounds, uint32_t max_shapes_in_node, uint32_t split_method, uint32_t small_range, HostBvh& out, yk_bvh_build_info& bi,
+                      DeviceTree* keep = nullptr);
 bool build_bvh_levels(const std::vector<ShapeBounds>& bounds, uint32_t max_shapes_in_node, uint32_t split_method, uint32_t small_range, HostBvh& out, yk_bvh_build_info& bi);
+
+// ------------------------------------------------------------------ yk_scene_layout.hip
+// The device records of `s` (nodes, nodes4, top_nodes, top_nodes_any, tris, prim_shade, prim_attr; s->layout, s->record_bytes)
+// from the tree in HBM and the scene's own uploaded arrays.  d_user_order (may be NULL): the caller's shape order, applied to
+// tree.order in place first (*order_applied says whether that happened).  Returns YK_LAYOUT_REASON_NONE, or the reason with the scene's records undefined.
+uint32_t layout_scene_device(yk_context* ctx, yk_scene* s, const DeviceTree& tree, const uint32_t* d_user_order, const uint8_t* d_mat_kind, bool has_attr, uint32_t tree_depth, bool* order_applied);
 
 // ------------------------------------------------------------------ yk_scene.cpp
 Material make_material(const yk_material_desc& m);  // per-hit constants folded (GGX alpha, Oren-Nayar A / B)

@@ -223,8 +223,9 @@ extern "C" {
 
 // BoundingVolumeHierarchy::node_bounds (bvh.rs:121-157), statement by statement.
 size_t yk_scene_node_bounds(const yk_scene* scene, int32_t target_level, float* out_bounds, size_t cap) try {
-    if (!scene || !scene->bvh || scene->bvh->nodes.empty()) return 0;
-    const std::vector<yk_bvh_node>& nodes = scene->bvh->nodes;
+    const HostBvh* tree = scene_host_tree(scene);
+    if (!tree || tree->nodes.empty()) return 0;
+    const std::vector<yk_bvh_node>& nodes = tree->nodes;
     size_t n = 0;
     auto push = [&](const yk_bvh_node& node) {
         if (out_bounds && n < cap) {

@@ -87,6 +87,13 @@ DevLight make_light(const yk_light_desc& l) {
 // Everything yk_scene_create derives from a scene description on the host (yk_internal.h).
 struct SceneImage {
     std::shared_ptr<const HostBvh> bvh;
+    std::shared_ptr<HostBvh> bvh_mut;  // the same tree, writable: its arrays are filled late when the builder left them in HBM
+    // "scene_layout" = 1 (single-device scenes): the records below dn .. prim_attr stay empty and yk_upload_scene_image lays them
+    // out on the device — from dtree, where the device builder left the tree (tree_on_device), or from an upload of the host tree
+    bool device_layout = false, tree_on_device = false, order_applied = false;  // order_applied: the caller's shape order went into dtree.order
+    uint32_t layout_reason = 0;  // YK_LAYOUT_REASON_*: why a device layout that was asked for is not attempted
+    DeviceTree dtree;
+    ~SceneImage() { dtree.release(); }
     const yk_scene_desc* d = nullptr;  // BORROWED: the caller's arrays (indices, points, normals, uvs, tri_material) are uploaded straight
                                        // from the description, so an image is only valid inside the call that built it
     uint32_t n_triangles = 0, n_spheres = 0, n_lights = 0, n_delta_lights = 0;
@@ -98,13 +105,15 @@ struct SceneImage {
     std::vector<DevNode4> dn4;
     std::vector<float4> tris, texels, prim_attr;
     std::vector<uint4> prim_shade, tex_info;
-    std::vector<uint32_t> mesh_flags, tri_mesh;
+    std::vector<uint32_t> mesh_flags, tri_mesh, mat_kind;  // mat_kind: device BSDF kind (MK_*) per material
     std::vector<int32_t> tri_al;
     std::vector<uint8_t> shape_kind;  // source shape -> BSDF kind (yk_scene::shape_kind)
     std::vector<Material> mats;
     std::vector<DevSphere> spheres;
     std::vector<DevLight> lights;
 };
+
+static void layout_records_host(const yk_context* ctx, SceneImage* s);
 
 // Host half of yk_scene_create: validation, BoundingVolumeHierarchy::new (bvh.rs:39-115) and — when `ctx` is given (its
 // "top_nodes" / "wide_bvh" options apply) — the device records laid out from the tree.
@@ -150,7 +159,10 @@ yk_status yk_build_scene_image(yk_context* ctx, const yk_scene_desc* d, std::sha
     SceneImage* s = img.get();
     std::shared_ptr<HostBvh> bvh = std::make_shared<HostBvh>();
     s->bvh = bvh;
+    s->bvh_mut = bvh;
     s->d = d;
+    s->device_layout = ctx && ctx->scene_layout == 1 && device_builder_allowed;
+    s->layout_reason = ctx && ctx->scene_layout == 1 && !device_builder_allowed ? (uint32_t)YK_LAYOUT_REASON_MULTI : 0u;
     s->n_triangles = d->n_triangles;
     s->n_spheres = d->n_spheres;
     s->n_lights = d->n_lights;
@@ -208,7 +220,8 @@ yk_status yk_build_scene_image(yk_context* ctx, const yk_scene_desc* d, std::sha
     bool built = false;
     const char* env_builder = std::getenv("YK_BVH_BUILDER");
     if (ctx && ctx->bvh_builder == 1 && device_builder_allowed) {
-        built = build_bvh_device(ctx, sb, d->max_shapes_in_node, d->split_method, (uint32_t)ctx->bvh_small_range, *bvh, bi);
+        built = build_bvh_device(ctx, sb, d->max_shapes_in_node, d->split_method, (uint32_t)ctx->bvh_small_range, *bvh, bi, s->device_layout ? &s->dtree : nullptr);
+        s->tree_on_device = built && s->device_layout;
     } else if (env_builder && std::strcmp(env_builder, "levels") == 0) {
         const char* e = std::getenv("YK_BVH_SMALL_RANGE");
         built = build_bvh_levels(sb, d->max_shapes_in_node, d->split_method, e ? (uint32_t)std::max(0, std::atoi(e)) : (uint32_t)YK_BVH_SMALL_RANGE, *bvh, bi);
@@ -218,204 +231,47 @@ yk_status yk_build_scene_image(yk_context* ctx, const yk_scene_desc* d, std::sha
         build_bvh(sb, d->max_shapes_in_node, d->split_method, *bvh);
     }
     s->info.build_seconds = now_seconds() - t0;
-    if (d->shape_order)  // leaf order -> position in Scene.shapes -> source shape
+    if (d->shape_order && !s->tree_on_device)  // leaf order -> position in Scene.shapes -> source shape (a tree in HBM: the layout applies it there)
         for (uint32_t& o : bvh->shape_order) o = d->shape_order[o];
-    if (bvh->split_failed || bvh->nodes.empty()) {
+    if (bvh->split_failed || (s->tree_on_device ? s->dtree.n_nodes == 0 : bvh->nodes.empty())) {
         return fail(ctx, YK_ERR_BVH_BUILD, "BVH split failed (reference: assert_ne!(mid, start))");
     }
-    s->info.n_nodes = bvh->nodes.size();
-    s->info.n_shapes = bvh->shape_order.size();
     s->info.max_leaf_shapes = bvh->max_leaf_shapes;
     s->info.tree_depth = bvh->depth;
-    for (int k = 0; k < 3; ++k) {
-        s->info.bounds_min[k] = bvh->nodes[0].bmin[k];
-        s->info.bounds_max[k] = bvh->nodes[0].bmax[k];
+    if (s->tree_on_device) {  // the builder's counters and node 0; a binary tree of n nodes has (n - 1) / 2 interior ones
+        yk_bvh_node root;
+        std::memcpy(&root, s->dtree.root_words, sizeof(root));
+        s->info.n_nodes = s->dtree.n_nodes;
+        s->info.n_shapes = s->dtree.n_shapes;
+        s->info.n_interior = (s->dtree.n_nodes - 1u) / 2u;
+        for (int k = 0; k < 3; ++k) {
+            s->info.bounds_min[k] = root.bmin[k];
+            s->info.bounds_max[k] = root.bmax[k];
+        }
+    } else {
+        s->info.n_nodes = bvh->nodes.size();
+        s->info.n_shapes = bvh->shape_order.size();
+        for (int k = 0; k < 3; ++k) {
+            s->info.bounds_min[k] = bvh->nodes[0].bmin[k];
+            s->info.bounds_max[k] = bvh->nodes[0].bmax[k];
+        }
+        uint64_t n_interior = 0;
+        for (const yk_bvh_node& n : bvh->nodes) n_interior += n.is_leaf ? 0 : 1;
+        s->info.n_interior = n_interior;
     }
-    uint64_t n_interior = 0;
-    for (const yk_bvh_node& n : bvh->nodes) n_interior += n.is_leaf ? 0 : 1;
-    s->info.n_interior = n_interior;
 
     if (ctx) {  // device records (a host-only scene — ctx == NULL — stops at the tree)
-        const std::vector<yk_bvh_node>& nodes = bvh->nodes;
-        // interior index of each reference node = number of interior nodes before it
-        std::vector<uint32_t> interior_index(nodes.size());
-        uint32_t cnt = 0;
-        for (size_t i = 0; i < nodes.size(); ++i) {
-            interior_index[i] = cnt;
-            if (!nodes[i].is_leaf) ++cnt;
-        }
-        if (nodes.size() > YK_REF_INDEX_MAX || bvh->shape_order.size() > YK_REF_INDEX_MAX) {
+        if (s->info.n_nodes > YK_REF_INDEX_MAX || s->info.n_shapes > YK_REF_INDEX_MAX) {
             return fail(ctx, YK_ERR_UNSUPPORTED, "more than 2^28 BVH nodes or shapes");
         }
-        auto ref_of = [&](uint32_t idx) -> uint32_t { return nodes[idx].is_leaf ? (YK_LEAF_BIT | nodes[idx].a) : interior_index[idx]; };
-        std::vector<DevNode>& dn = s->dn;
-        dn.assign(std::max<size_t>(n_interior, 1), DevNode());
-        for (size_t i = 0; i < nodes.size(); ++i) {
-            if (nodes[i].is_leaf) continue;
-            const yk_bvh_node& c0 = nodes[i + 1];
-            const yk_bvh_node& c1 = nodes[nodes[i].a];
-            DevNode& o = dn[interior_index[i]];
-            o.q0 = make_float4(c0.bmin[0], c0.bmin[1], c0.bmin[2], c0.bmax[0]);
-            o.q1 = make_float4(c0.bmax[1], c0.bmax[2], c1.bmin[0], c1.bmin[1]);
-            o.q2 = make_float4(c1.bmin[2], c1.bmax[0], c1.bmax[1], c1.bmax[2]);
-            o.q3 = make_uint4(ref_of((uint32_t)i + 1), ref_of(nodes[i].a) | ((uint32_t)nodes[i].axis << YK_AXIS_SHIFT), 0u, 0u);
-        }
-        // top of the tree, breadth first, for the LDS-resident copies (YK_TOP_BIT refs).  Two sets: the closest-hit kernels
-        // keep 8-byte stack entries (ref, entry distance) in LDS and have room for trace_top_nodes() nodes beside them; the
-        // any-hit kernel's entries are a bare ref (4 bytes), which leaves room for trace_top_nodes_any() — more than twice as many.
-        auto build_top = [&](size_t cap, std::vector<DevNode>& top) {
-            top.clear();
-            if (nodes[0].is_leaf || cap == 0) return;
-            std::vector<uint32_t> order;  // reference node indices, breadth first
-            std::vector<uint32_t> top_id(nodes.size(), 0xffffffffu);
-            order.push_back(0);
-            top_id[0] = 0;
-            for (size_t q = 0; q < order.size() && order.size() < cap; ++q) {
-                const uint32_t P = order[q];
-                for (uint32_t c : {P + 1, nodes[P].a}) {
-                    if (!nodes[c].is_leaf && order.size() < cap) {
-                        top_id[c] = (uint32_t)order.size();
-                        order.push_back(c);
-                    }
-                }
-            }
-            for (uint32_t P : order) {
-                DevNode t = dn[interior_index[P]];
-                const uint32_t c0 = P + 1, c1 = nodes[P].a;
-                if (top_id[c0] != 0xffffffffu) t.q3.x = YK_TOP_BIT | top_id[c0];
-                if (top_id[c1] != 0xffffffffu) t.q3.y = YK_TOP_BIT | top_id[c1] | ((uint32_t)nodes[P].axis << YK_AXIS_SHIFT);
-                top.push_back(t);
-            }
-        };
-        build_top((size_t)std::min<int64_t>(ctx->top_nodes, trace_top_nodes()), s->top);
-        build_top((size_t)std::min<int64_t>(ctx->top_nodes, trace_top_nodes_any()), s->top_any);
-        // 4-wide collapse (DevNode4): one node per reference interior node reached at even depth
-        // below the root.  Built only while the traversal stack of the collapsed tree is
-        // guaranteed to fit (the reference asserts on its own stack depth, bvh.rs:172-174).
-        std::vector<DevNode4>& dn4 = s->dn4;
-        const bool wide = s->wide = ctx->wide_bvh != 0 && !nodes[0].is_leaf && bvh->depth <= 64;
-        if (wide) {
-            dn4.reserve(n_interior / 2 + 1);
-            struct Todo {
-                uint32_t binary;  // reference node index of P
-                uint32_t slot;    // DevNode4 index to fill
-            };
-            std::vector<Todo> stack;
-            dn4.emplace_back();
-            stack.push_back(Todo{0u, 0u});
-            while (!stack.empty()) {
-                const Todo td = stack.back();
-                stack.pop_back();
-                const uint32_t P = td.binary, A = P + 1, B = nodes[P].a;
-                uint32_t child[4] = {YK_REF_NONE, YK_REF_NONE, YK_REF_NONE, YK_REF_NONE};  // reference node index per slot
-                if (nodes[A].is_leaf) {
-                    child[0] = A;
-                } else {
-                    child[0] = A + 1;
-                    child[1] = nodes[A].a;
-                }
-                if (nodes[B].is_leaf) {
-                    child[2] = B;
-                } else {
-                    child[2] = B + 1;
-                    child[3] = nodes[B].a;
-                }
-                float box[4][6] = {};
-                uint32_t ref[4];
-                for (int k = 0; k < 4; ++k) {
-                    ref[k] = YK_REF_NONE;
-                    if (child[k] == YK_REF_NONE) continue;
-                    const yk_bvh_node& c = nodes[child[k]];
-                    for (int a = 0; a < 3; ++a) {
-                        box[k][a] = c.bmin[a];
-                        box[k][3 + a] = c.bmax[a];
-                    }
-                    if (c.is_leaf) {
-                        ref[k] = YK_LEAF_BIT | c.a;
-                    } else {
-                        ref[k] = (uint32_t)dn4.size();
-                        dn4.emplace_back();
-                    }
-                }
-                // children are expanded so that the first visited subtree (for a positive ray) follows in memory
-                for (int k = 3; k >= 0; --k)
-                    if (ref[k] != YK_REF_NONE && !(ref[k] & YK_LEAF_BIT)) stack.push_back(Todo{child[k], ref[k]});
-                DevNode4& o = dn4[td.slot];
-                o.q0 = make_float4(box[0][0], box[0][1], box[0][2], box[0][3]);
-                o.q1 = make_float4(box[0][4], box[0][5], box[1][0], box[1][1]);
-                o.q2 = make_float4(box[1][2], box[1][3], box[1][4], box[1][5]);
-                o.q3 = make_float4(box[2][0], box[2][1], box[2][2], box[2][3]);
-                o.q4 = make_float4(box[2][4], box[2][5], box[3][0], box[3][1]);
-                o.q5 = make_float4(box[3][2], box[3][3], box[3][4], box[3][5]);
-                o.q6 = make_uint4(ref[0], ref[1], ref[2], ref[3]);
-                const uint32_t axA = nodes[A].is_leaf ? 0u : nodes[A].axis, axB = nodes[B].is_leaf ? 0u : nodes[B].axis;
-                o.q7 = make_uint4((uint32_t)nodes[P].axis | (axA << 2) | (axB << 4), 0u, 0u, 0u);
-            }
-        }
-        const size_t np = bvh->shape_order.size();
-        std::vector<float4>& tris = s->tris;
-        tris.assign(3 * np, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-        std::vector<uint4>& prim_shade = s->prim_shade;
-        prim_shade.assign(np, make_uint4(0u, 0u, 0u, 0u));
-        std::vector<uint32_t> mat_kind(std::max<uint32_t>(d->n_materials, 1), 0u);  // device BSDF kind (MK_*) per material
+        const size_t np = s->info.n_shapes;
+        std::vector<uint32_t>& mat_kind = s->mat_kind;
+        mat_kind.assign(std::max<uint32_t>(d->n_materials, 1), 0u);
         for (uint32_t m = 0; m < d->n_materials; ++m) mat_kind[m] = make_material(d->materials[m]).kind & 7u;
         s->shape_kind.resize(np);
         for (uint32_t i = 0; i < d->n_triangles; ++i) s->shape_kind[i] = (uint8_t)mat_kind[d->tri_material[i]];
         for (uint32_t k = 0; k < d->n_spheres; ++k) s->shape_kind[(size_t)d->n_triangles + k] = (uint8_t)mat_kind[d->spheres[k].material];
-        std::vector<uint8_t> last(np, 0);
-        for (const yk_bvh_node& n : nodes)
-            if (n.is_leaf) last[(size_t)n.a + n.count - 1] = 1;
-        for (size_t p = 0; p < np; ++p) {
-            uint32_t src = bvh->shape_order[p];
-            if (src >= d->n_triangles) {  // sphere: only the source index and the flags are read
-                uint32_t none = 0xffffffffu, fl = (last[p] ? YK_PRIM_LAST : 0u) | YK_PRIM_SPHERE | (mat_kind[d->spheres[src - d->n_triangles].material] << YK_PRIM_KIND_SHIFT);
-                float w0, w1, w2;
-                std::memcpy(&w0, &none, 4);
-                std::memcpy(&w1, &src, 4);
-                std::memcpy(&w2, &fl, 4);
-                tris[3 * p + 0] = make_float4(0.0f, 0.0f, 0.0f, w0);
-                tris[3 * p + 1] = make_float4(0.0f, 0.0f, 0.0f, w1);
-                tris[3 * p + 2] = make_float4(0.0f, 0.0f, 0.0f, w2);
-                prim_shade[p] = make_uint4(0u, 0u, 0u, ((uint32_t)d->spheres[src - d->n_triangles].material << 6) | (mat_kind[d->spheres[src - d->n_triangles].material] << 3));
-                continue;
-            }
-            const float* p0 = d->points + 3 * (size_t)d->indices[3 * src];
-            const float* p1 = d->points + 3 * (size_t)d->indices[3 * src + 1];
-            const float* p2 = d->points + 3 * (size_t)d->indices[3 * src + 2];
-            int al = d->tri_area_light ? d->tri_area_light[src] : -1;
-            uint32_t alb = (uint32_t)al, lastb = (last[p] ? YK_PRIM_LAST : 0u) | (mat_kind[d->tri_material[src]] << YK_PRIM_KIND_SHIFT);
-            float w0, w1, w2;
-            std::memcpy(&w0, &alb, 4);
-            std::memcpy(&w1, &src, 4);
-            std::memcpy(&w2, &lastb, 4);
-            tris[3 * p + 0] = make_float4(p0[0], p0[1], p0[2], w0);
-            tris[3 * p + 1] = make_float4(p1[0], p1[1], p1[2], w1);
-            tris[3 * p + 2] = make_float4(p2[0], p2[1], p2[2], w2);
-            const yk_mesh_desc& md = d->meshes[d->tri_mesh ? d->tri_mesh[src] : 0];
-            const uint32_t mfl = (md.has_normals ? YK_MESH_NORMALS : 0u) | (md.has_uvs ? YK_MESH_UVS : 0u) | (md.swaps_handedness ? YK_MESH_SWAPS : 0u);
-            prim_shade[p] = make_uint4(d->indices[3 * src], d->indices[3 * src + 1], d->indices[3 * src + 2],
-                                       ((uint32_t)d->tri_material[src] << 6) | (mat_kind[d->tri_material[src]] << 3) | mfl);
-        }
-        if (d->normals || d->uvs) {  // leaf-order copy of the per-vertex normals / uvs (yk_device.h: DevScene::prim_attr)
-            s->prim_attr.assign(4 * np, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-            for (size_t p = 0; p < np; ++p) {
-                const uint32_t src = bvh->shape_order[p];
-                if (src >= d->n_triangles) continue;
-                const yk_mesh_desc& md = d->meshes[d->tri_mesh ? d->tri_mesh[src] : 0];
-                float nrm[3][3] = {}, uv[3][2] = {};
-                for (int k = 0; k < 3; ++k) {
-                    const size_t vi = d->indices[3 * (size_t)src + k];
-                    if (md.has_normals)
-                        for (int c = 0; c < 3; ++c) nrm[k][c] = d->normals[3 * vi + c];
-                    if (md.has_uvs)
-                        for (int c = 0; c < 2; ++c) uv[k][c] = d->uvs[2 * vi + c];
-                }
-                s->prim_attr[4 * p + 0] = make_float4(nrm[0][0], nrm[0][1], nrm[0][2], uv[0][0]);
-                s->prim_attr[4 * p + 1] = make_float4(nrm[1][0], nrm[1][1], nrm[1][2], uv[0][1]);
-                s->prim_attr[4 * p + 2] = make_float4(nrm[2][0], nrm[2][1], nrm[2][2], uv[1][0]);
-                s->prim_attr[4 * p + 3] = make_float4(uv[1][1], uv[2][0], uv[2][1], 0.0f);
-            }
-        }
+        if (!s->device_layout) layout_records_host(ctx, s);
         std::vector<uint32_t>& mesh_flags = s->mesh_flags;
         mesh_flags.assign(std::max<uint32_t>(d->n_meshes, 1), 0);
         for (uint32_t m = 0; m < d->n_meshes; ++m)
@@ -454,13 +310,273 @@ yk_status yk_build_scene_image(yk_context* ctx, const yk_scene_desc* d, std::sha
             if (s->texels.size() + n > 0xffffffffull) return fail(ctx, YK_ERR_UNSUPPORTED, "more than 2^32 texels");
             for (size_t k = 0; k < n; ++k) s->texels.push_back(make_float4(td.rgb[3 * k], td.rgb[3 * k + 1], td.rgb[3 * k + 2], 0.0f));
         }
-        s->root_ref = ref_of(0);
-        s->wide_auto = wide && ctx->wide_bvh == 2;
         s->has_device_records = true;
     }
     out = img;
     return YK_OK;
 } YK_CATCH(ctx)
+
+// The device records from the host tree (s->bvh with its arrays): the sequential loops the device layout
+// (yk_scene_layout.hip) is held against.
+static void layout_records_host(const yk_context* ctx, SceneImage* s) {
+    const yk_scene_desc* d = s->d;
+    const HostBvh* bvh = s->bvh.get();
+    const std::vector<yk_bvh_node>& nodes = bvh->nodes;
+    const std::vector<uint32_t>& mat_kind = s->mat_kind;
+    const uint64_t n_interior = s->info.n_interior;
+    // interior index of each reference node = number of interior nodes before it
+    std::vector<uint32_t> interior_index(nodes.size());
+    uint32_t cnt = 0;
+    for (size_t i = 0; i < nodes.size(); ++i) {
+        interior_index[i] = cnt;
+        if (!nodes[i].is_leaf) ++cnt;
+    }
+    auto ref_of = [&](uint32_t idx) -> uint32_t { return nodes[idx].is_leaf ? (YK_LEAF_BIT | nodes[idx].a) : interior_index[idx]; };
+    std::vector<DevNode>& dn = s->dn;
+    dn.assign(std::max<size_t>(n_interior, 1), DevNode());
+    for (size_t i = 0; i < nodes.size(); ++i) {
+        if (nodes[i].is_leaf) continue;
+        const yk_bvh_node& c0 = nodes[i + 1];
+        const yk_bvh_node& c1 = nodes[nodes[i].a];
+        DevNode& o = dn[interior_index[i]];
+        o.q0 = make_float4(c0.bmin[0], c0.bmin[1], c0.bmin[2], c0.bmax[0]);
+        o.q1 = make_float4(c0.bmax[1], c0.bmax[2], c1.bmin[0], c1.bmin[1]);
+        o.q2 = make_float4(c1.bmin[2], c1.bmax[0], c1.bmax[1], c1.bmax[2]);
+        o.q3 = make_uint4(ref_of((uint32_t)i + 1), ref_of(nodes[i].a) | ((uint32_t)nodes[i].axis << YK_AXIS_SHIFT), 0u, 0u);
+    }
+    // top of the tree, breadth first, for the LDS-resident copies (YK_TOP_BIT refs).  Two sets: the closest-hit kernels
+    // keep 8-byte stack entries (ref, entry distance) in LDS and have room for trace_top_nodes() nodes beside them; the
+    // any-hit kernel's entries are a bare ref (4 bytes), which leaves room for trace_top_nodes_any() — more than twice as many.
+    auto build_top = [&](size_t cap, std::vector<DevNode>& top) {
+        top.clear();
+        if (nodes[0].is_leaf || cap == 0) return;
+        std::vector<uint32_t> order;  // reference node indices, breadth first
+        std::vector<uint32_t> top_id(nodes.size(), 0xffffffffu);
+        order.push_back(0);
+        top_id[0] = 0;
+        for (size_t q = 0; q < order.size() && order.size() < cap; ++q) {
+            const uint32_t P = order[q];
+            for (uint32_t c : {P + 1, nodes[P].a}) {
+                if (!nodes[c].is_leaf && order.size() < cap) {
+                    top_id[c] = (uint32_t)order.size();
+                    order.push_back(c);
+                }
+            }
+        }
+        for (uint32_t P : order) {
+            DevNode t = dn[interior_index[P]];
+            const uint32_t c0 = P + 1, c1 = nodes[P].a;
+            if (top_id[c0] != 0xffffffffu) t.q3.x = YK_TOP_BIT | top_id[c0];
+            if (top_id[c1] != 0xffffffffu) t.q3.y = YK_TOP_BIT | top_id[c1] | ((uint32_t)nodes[P].axis << YK_AXIS_SHIFT);
+            top.push_back(t);
+        }
+    };
+    build_top((size_t)std::min<int64_t>(ctx->top_nodes, trace_top_nodes()), s->top);
+    build_top((size_t)std::min<int64_t>(ctx->top_nodes, trace_top_nodes_any()), s->top_any);
+    // 4-wide collapse (DevNode4): one node per reference interior node reached at even depth
+    // below the root.  Built only while the traversal stack of the collapsed tree is
+    // guaranteed to fit (the reference asserts on its own stack depth, bvh.rs:172-174).
+    std::vector<DevNode4>& dn4 = s->dn4;
+    const bool wide = s->wide = ctx->wide_bvh != 0 && !nodes[0].is_leaf && bvh->depth <= 64;
+    if (wide) {
+        dn4.reserve(n_interior / 2 + 1);
+        struct Todo {
+            uint32_t binary;  // reference node index of P
+            uint32_t slot;    // DevNode4 index to fill
+        };
+        std::vector<Todo> stack;
+        dn4.emplace_back();
+        stack.push_back(Todo{0u, 0u});
+        while (!stack.empty()) {
+            const Todo td = stack.back();
+            stack.pop_back();
+            const uint32_t P = td.binary, A = P + 1, B = nodes[P].a;
+            uint32_t child[4] = {YK_REF_NONE, YK_REF_NONE, YK_REF_NONE, YK_REF_NONE};  // reference node index per slot
+            if (nodes[A].is_leaf) {
+                child[0] = A;
+            } else {
+                child[0] = A + 1;
+                child[1] = nodes[A].a;
+            }
+            if (nodes[B].is_leaf) {
+                child[2] = B;
+            } else {
+                child[2] = B + 1;
+                child[3] = nodes[B].a;
+            }
+            float box[4][6] = {};
+            uint32_t ref[4];
+            for (int k = 0; k < 4; ++k) {
+                ref[k] = YK_REF_NONE;
+                if (child[k] == YK_REF_NONE) continue;
+                const yk_bvh_node& c = nodes[child[k]];
+                for (int a = 0; a < 3; ++a) {
+                    box[k][a] = c.bmin[a];
+                    box[k][3 + a] = c.bmax[a];
+                }
+                if (c.is_leaf) {
+                    ref[k] = YK_LEAF_BIT | c.a;
+                } else {
+                    ref[k] = (uint32_t)dn4.size();
+                    dn4.emplace_back();
+                }
+            }
+            // children are expanded so that the first visited subtree (for a positive ray) follows in memory
+            for (int k = 3; k >= 0; --k)
+                if (ref[k] != YK_REF_NONE && !(ref[k] & YK_LEAF_BIT)) stack.push_back(Todo{child[k], ref[k]});
+            DevNode4& o = dn4[td.slot];
+            o.q0 = make_float4(box[0][0], box[0][1], box[0][2], box[0][3]);
+            o.q1 = make_float4(box[0][4], box[0][5], box[1][0], box[1][1]);
+            o.q2 = make_float4(box[1][2], box[1][3], box[1][4], box[1][5]);
+            o.q3 = make_float4(box[2][0], box[2][1], box[2][2], box[2][3]);
+            o.q4 = make_float4(box[2][4], box[2][5], box[3][0], box[3][1]);
+            o.q5 = make_float4(box[3][2], box[3][3], box[3][4], box[3][5]);
+            o.q6 = make_uint4(ref[0], ref[1], ref[2], ref[3]);
+            const uint32_t axA = nodes[A].is_leaf ? 0u : nodes[A].axis, axB = nodes[B].is_leaf ? 0u : nodes[B].axis;
+            o.q7 = make_uint4((uint32_t)nodes[P].axis | (axA << 2) | (axB << 4), 0u, 0u, 0u);
+        }
+    }
+    const size_t np = bvh->shape_order.size();
+    std::vector<float4>& tris = s->tris;
+    tris.assign(3 * np, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+    std::vector<uint4>& prim_shade = s->prim_shade;
+    prim_shade.assign(np, make_uint4(0u, 0u, 0u, 0u));
+    std::vector<uint8_t> last(np, 0);
+    for (const yk_bvh_node& n : nodes)
+        if (n.is_leaf) last[(size_t)n.a + n.count - 1] = 1;
+    for (size_t p = 0; p < np; ++p) {
+        uint32_t src = bvh->shape_order[p];
+        if (src >= d->n_triangles) {  // sphere: only the source index and the flags are read
+            uint32_t none = 0xffffffffu, fl = (last[p] ? YK_PRIM_LAST : 0u) | YK_PRIM_SPHERE | (mat_kind[d->spheres[src - d->n_triangles].material] << YK_PRIM_KIND_SHIFT);
+            float w0, w1, w2;
+            std::memcpy(&w0, &none, 4);
+            std::memcpy(&w1, &src, 4);
+            std::memcpy(&w2, &fl, 4);
+            tris[3 * p + 0] = make_float4(0.0f, 0.0f, 0.0f, w0);
+            tris[3 * p + 1] = make_float4(0.0f, 0.0f, 0.0f, w1);
+            tris[3 * p + 2] = make_float4(0.0f, 0.0f, 0.0f, w2);
+            prim_shade[p] = make_uint4(0u, 0u, 0u, ((uint32_t)d->spheres[src - d->n_triangles].material << 6) | (mat_kind[d->spheres[src - d->n_triangles].material] << 3));
+            continue;
+        }
+        const float* p0 = d->points + 3 * (size_t)d->indices[3 * src];
+        const float* p1 = d->points + 3 * (size_t)d->indices[3 * src + 1];
+        const float* p2 = d->points + 3 * (size_t)d->indices[3 * src + 2];
+        int al = d->tri_area_light ? d->tri_area_light[src] : -1;
+        uint32_t alb = (uint32_t)al, lastb = (last[p] ? YK_PRIM_LAST : 0u) | (mat_kind[d->tri_material[src]] << YK_PRIM_KIND_SHIFT);
+        float w0, w1, w2;
+        std::memcpy(&w0, &alb, 4);
+        std::memcpy(&w1, &src, 4);
+        std::memcpy(&w2, &lastb, 4);
+        tris[3 * p + 0] = make_float4(p0[0], p0[1], p0[2], w0);
+        tris[3 * p + 1] = make_float4(p1[0], p1[1], p1[2], w1);
+        tris[3 * p + 2] = make_float4(p2[0], p2[1], p2[2], w2);
+        const yk_mesh_desc& md = d->meshes[d->tri_mesh ? d->tri_mesh[src] : 0];
+        const uint32_t mfl = (md.has_normals ? YK_MESH_NORMALS : 0u) | (md.has_uvs ? YK_MESH_UVS : 0u) | (md.swaps_handedness ? YK_MESH_SWAPS : 0u);
+        prim_shade[p] = make_uint4(d->indices[3 * src], d->indices[3 * src + 1], d->indices[3 * src + 2],
+                                   ((uint32_t)d->tri_material[src] << 6) | (mat_kind[d->tri_material[src]] << 3) | mfl);
+    }
+    if (d->normals || d->uvs) {  // leaf-order copy of the per-vertex normals / uvs (yk_device.h: DevScene::prim_attr)
+        s->prim_attr.assign(4 * np, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
+        for (size_t p = 0; p < np; ++p) {
+            const uint32_t src = bvh->shape_order[p];
+            if (src >= d->n_triangles) continue;
+            const yk_mesh_desc& md = d->meshes[d->tri_mesh ? d->tri_mesh[src] : 0];
+            float nrm[3][3] = {}, uv[3][2] = {};
+            for (int k = 0; k < 3; ++k) {
+                const size_t vi = d->indices[3 * (size_t)src + k];
+                if (md.has_normals)
+                    for (int c = 0; c < 3; ++c) nrm[k][c] = d->normals[3 * vi + c];
+                if (md.has_uvs)
+                    for (int c = 0; c < 2; ++c) uv[k][c] = d->uvs[2 * vi + c];
+            }
+            s->prim_attr[4 * p + 0] = make_float4(nrm[0][0], nrm[0][1], nrm[0][2], uv[0][0]);
+            s->prim_attr[4 * p + 1] = make_float4(nrm[1][0], nrm[1][1], nrm[1][2], uv[0][1]);
+            s->prim_attr[4 * p + 2] = make_float4(nrm[2][0], nrm[2][1], nrm[2][2], uv[1][0]);
+            s->prim_attr[4 * p + 3] = make_float4(uv[1][1], uv[2][0], uv[2][1], 0.0f);
+        }
+    }
+    s->root_ref = ref_of(0);
+    s->wide_auto = wide && ctx->wide_bvh == 2;
+}
+
+// 32-byte nodes and shape order from HBM into the host tree (no-op for buffers that are not there)
+static yk_status fetch_tree(int device, const DevBuf& d_nodes, const DevBuf& d_order, uint32_t n_nodes, uint32_t n_shapes, HostBvh& out) {
+    if (!d_nodes.p || !d_order.p || !out.nodes.empty()) return YK_OK;
+    (void)hipSetDevice(device);
+    std::vector<yk_bvh_node> nodes(n_nodes);
+    std::vector<uint32_t> order(n_shapes);
+    if (hipMemcpy(nodes.data(), d_nodes.p, (size_t)n_nodes * sizeof(yk_bvh_node), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(order.data(), d_order.p, (size_t)n_shapes * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess) {
+        (void)hipGetLastError();
+        return YK_ERR_DEVICE;
+    }
+    out.nodes.swap(nodes);
+    out.shape_order.swap(order);
+    return YK_OK;
+}
+
+const HostBvh* scene_host_tree(const yk_scene* s) {
+    if (!s || !s->bvh) return nullptr;
+    if (s->bvh_lazy)
+        std::call_once(s->tree_once, [s] {
+            if (fetch_tree(s->device, s->tree_nodes, s->tree_order, (uint32_t)s->info.n_nodes, (uint32_t)s->info.n_shapes, *s->bvh_lazy) == YK_OK) s->tree_fetched.store(1u);
+        });
+    return s->tree_fetched.load() ? s->bvh.get() : nullptr;
+}
+
+// "scene_layout" = 1: the tree to HBM unless the builder left it there, the two small tables, the layout kernels
+// (yk_scene_layout.hip).  The scene's own arrays (indices .. spheres) are uploaded already.  Returns YK_LAYOUT_REASON_*.
+static uint32_t layout_on_device(yk_context* ctx, SceneImage* img, yk_scene* s) {
+    const yk_scene_desc* d = img->d;
+    DeviceTree& tree = img->dtree;
+    double t0 = now_seconds();
+    DevBuf d_mat_kind, d_user;
+    struct Free {
+        DevBuf &a, &b;
+        ~Free() {
+            a.release();
+            b.release();
+        }
+    } free_tables{d_mat_kind, d_user};
+    auto put = [&](DevBuf& buf, const void* src, size_t bytes) -> uint32_t {
+        hipError_t e = buf.ensure(std::max<size_t>(bytes, 16));
+        if (e == hipSuccess && bytes) e = hipMemcpy(buf.p, src, bytes, hipMemcpyHostToDevice);
+        if (e == hipSuccess) return YK_LAYOUT_REASON_NONE;
+        (void)hipGetLastError();
+        return e == hipErrorOutOfMemory ? YK_LAYOUT_REASON_OUT_OF_MEMORY : YK_LAYOUT_REASON_DEVICE_ERROR;
+    };
+    uint32_t r;
+    std::vector<uint8_t> kinds(img->mat_kind.begin(), img->mat_kind.end());
+    if ((r = put(d_mat_kind, kinds.data(), kinds.size())) != 0) return r;
+    if (img->tree_on_device) {
+        if (d->shape_order && (r = put(d_user, d->shape_order, (size_t)tree.n_shapes * 4)) != 0) return r;
+    } else {  // a host-built tree: its nodes, their depths (children follow their parent in the array) and the final order
+        const HostBvh& bvh = *img->bvh;
+        std::vector<uint32_t> depth(bvh.nodes.size(), 0u);
+        depth[0] = 1u;
+        for (size_t i = 0; i < bvh.nodes.size(); ++i)
+            if (!bvh.nodes[i].is_leaf) depth[i + 1] = depth[bvh.nodes[i].a] = depth[i] + 1u;
+        tree.n_nodes = (uint32_t)bvh.nodes.size();
+        tree.n_shapes = (uint32_t)bvh.shape_order.size();
+        std::memcpy(tree.root_words, bvh.nodes.data(), 32);
+        if ((r = put(tree.nodes, bvh.nodes.data(), bvh.nodes.size() * sizeof(yk_bvh_node))) != 0 || (r = put(tree.depth, depth.data(), depth.size() * 4)) != 0 ||
+            (r = put(tree.order, bvh.shape_order.data(), bvh.shape_order.size() * 4)) != 0)
+            return r;
+    }
+    s->layout.seconds_upload = now_seconds() - t0;
+    t0 = now_seconds();
+    r = layout_scene_device(ctx, s, tree, img->tree_on_device && d->shape_order ? d_user.as<uint32_t>() : nullptr, d_mat_kind.as<uint8_t>(), d->normals || d->uvs, img->bvh->depth, &img->order_applied);
+    s->layout.seconds_layout = now_seconds() - t0;
+    if (r != YK_LAYOUT_REASON_NONE) return r;
+    if (img->tree_on_device) {  // the host copy of the arrays is made when something asks for it (scene_host_tree)
+        std::swap(s->tree_nodes, tree.nodes);
+        std::swap(s->tree_order, tree.order);
+        s->bvh_lazy = img->bvh_mut;
+        s->tree_fetched.store(0u);
+    }
+    tree.release();
+    return YK_LAYOUT_REASON_NONE;
+}
 
 // Device half: one copy of the image in the HBM of ctx's device.
 yk_status yk_upload_scene_image(yk_context* ctx, const std::shared_ptr<SceneImage>& img, yk_scene** out) try {
@@ -491,13 +607,6 @@ yk_status yk_upload_scene_image(yk_context* ctx, const std::shared_ptr<SceneImag
         yk_status st;
 #define UP(buf, ptr, n) \
     if ((st = upload(ctx, s->buf, ptr, n)) != YK_OK) return st;
-        UP(nodes, img->dn.data(), img->dn.size());
-        UP(nodes4, img->dn4.data(), img->dn4.size());
-        UP(top_nodes, img->top.data(), img->top.size());
-        UP(top_nodes_any, img->top_any.data(), img->top_any.size());
-        UP(tris, img->tris.data(), img->tris.size());
-        UP(prim_shade, img->prim_shade.data(), img->prim_shade.size());
-        UP(prim_attr, img->prim_attr.data(), img->prim_attr.size());
         UP(indices, d->indices, 3 * (size_t)d->n_triangles);
         UP(points, d->points, 3 * (size_t)d->n_vertices);
         UP(normals, d->normals, d->normals ? 3 * (size_t)d->n_vertices : 0);
@@ -511,25 +620,61 @@ yk_status yk_upload_scene_image(yk_context* ctx, const std::shared_ptr<SceneImag
         UP(spheres, img->spheres.data(), img->spheres.size());
         UP(texels, img->texels.data(), img->texels.size());
         UP(tex_info, img->tex_info.data(), img->tex_info.size());
+        yk_scene_layout_info& li = s->layout;
+        li.reason = img->layout_reason;
+        if (img->device_layout) {  // the records from the tree in HBM; whatever fails there leaves its reason and the host lays them out
+            li.reason = layout_on_device(ctx, img.get(), s);
+            if (li.reason == YK_LAYOUT_REASON_NONE) {
+                li.layout = YK_LAYOUT_DEVICE;
+            } else {
+                yk_status fs = fetch_tree(ctx->device, img->dtree.nodes, img->dtree.order, img->dtree.n_nodes, img->dtree.n_shapes, *img->bvh_mut);
+                if (fs != YK_OK) return fail(ctx, fs, "the device layout failed and the tree could not be copied back for the host layout");
+                if (img->tree_on_device && d->shape_order && !img->order_applied)
+                    for (uint32_t& o : img->bvh_mut->shape_order) o = d->shape_order[o];
+                img->tree_on_device = false;
+                img->dtree.release();
+                layout_records_host(ctx, img.get());
+            }
+        }
+        if (li.layout == YK_LAYOUT_HOST) {
+            UP(nodes, img->dn.data(), img->dn.size());
+            UP(nodes4, img->dn4.data(), img->dn4.size());
+            UP(top_nodes, img->top.data(), img->top.size());
+            UP(top_nodes_any, img->top_any.data(), img->top_any.size());
+            UP(tris, img->tris.data(), img->tris.size());
+            UP(prim_shade, img->prim_shade.data(), img->prim_shade.size());
+            UP(prim_attr, img->prim_attr.data(), img->prim_attr.size());
+            li.root_ref = img->root_ref;
+            li.n_top = (uint32_t)img->top.size();
+            li.n_top_any = (uint32_t)img->top_any.size();
+            li.wide = img->wide ? 1u : 0u;
+            li.wide_auto = img->wide_auto ? 1u : 0u;
+            s->record_bytes[YK_RECORDS_NODES] = img->dn.size() * sizeof(DevNode);
+            s->record_bytes[YK_RECORDS_NODES4] = img->dn4.size() * sizeof(DevNode4);
+            s->record_bytes[YK_RECORDS_TOP] = img->top.size() * sizeof(DevNode);
+            s->record_bytes[YK_RECORDS_TOP_ANY] = img->top_any.size() * sizeof(DevNode);
+            s->record_bytes[YK_RECORDS_TRIS] = img->tris.size() * sizeof(float4);
+            s->record_bytes[YK_RECORDS_PRIM_SHADE] = img->prim_shade.size() * sizeof(uint4);
+            s->record_bytes[YK_RECORDS_PRIM_ATTR] = img->prim_attr.size() * sizeof(float4);
+        }
 #undef UP
-        const std::vector<yk_bvh_node>& nodes = img->bvh->nodes;
         DevScene& ds = s->dev;
         ds.nodes = s->nodes.as<DevNode>();
-        ds.nodes4 = img->wide ? s->nodes4.as<DevNode4>() : nullptr;
-        s->wide_auto = img->wide_auto;
+        ds.nodes4 = li.wide ? s->nodes4.as<DevNode4>() : nullptr;
+        s->wide_auto = li.wide_auto != 0;
         ds.top_nodes = s->top_nodes.as<DevNode>();
-        ds.n_top = (uint32_t)img->top.size();
+        ds.n_top = li.n_top;
         ds.top_nodes_any = s->top_nodes_any.as<DevNode>();
-        ds.n_top_any = (uint32_t)img->top_any.size();
+        ds.n_top_any = li.n_top_any;
         ds.tris = s->tris.as<float4>();
         ds.prim_shade = s->prim_shade.as<uint4>();
-        ds.prim_attr = img->prim_attr.empty() ? nullptr : s->prim_attr.as<float4>();
+        ds.prim_attr = s->record_bytes[YK_RECORDS_PRIM_ATTR] ? s->prim_attr.as<float4>() : nullptr;
         ds.spheres = d->n_spheres ? s->spheres.as<DevSphere>() : nullptr;
         ds.n_triangles = d->n_triangles;
-        ds.root_ref = img->root_ref;
-        for (int k = 0; k < 3; ++k) {
-            ds.root_bmin[k] = nodes[0].bmin[k];
-            ds.root_bmax[k] = nodes[0].bmax[k];
+        ds.root_ref = li.root_ref;
+        for (int k = 0; k < 3; ++k) {  // node 0's box
+            ds.root_bmin[k] = s->info.bounds_min[k];
+            ds.root_bmax[k] = s->info.bounds_max[k];
             ds.background[k] = d->background[k];
         }
         ds.indices = s->indices.as<uint32_t>();
@@ -548,7 +693,7 @@ yk_status yk_upload_scene_image(yk_context* ctx, const std::shared_ptr<SceneImag
         s->on_device = true;
         s->info.upload_seconds = now_seconds() - u0;
         DevBuf* all[] = {&s->nodes, &s->nodes4, &s->top_nodes, &s->top_nodes_any, &s->tris, &s->prim_shade, &s->prim_attr, &s->indices, &s->points, &s->normals, &s->uvs, &s->tri_mesh, &s->tri_material, &s->tri_area_light,
-                         &s->mesh_flags, &s->materials, &s->lights, &s->spheres, &s->texels, &s->tex_info};
+                         &s->mesh_flags, &s->materials, &s->lights, &s->spheres, &s->texels, &s->tex_info, &s->tree_nodes, &s->tree_order};
         for (DevBuf* b : all) s->info.device_bytes += b->bytes;
     }
     guard.s = nullptr;
@@ -574,7 +719,7 @@ void yk_scene_destroy(yk_scene* s) {
     if (!s) return;
     if (s->device >= 0) (void)hipSetDevice(s->device);
     DevBuf* all[] = {&s->nodes, &s->nodes4, &s->top_nodes, &s->top_nodes_any, &s->tris, &s->prim_shade, &s->prim_attr, &s->indices, &s->points, &s->normals, &s->uvs, &s->tri_mesh, &s->tri_material, &s->tri_area_light,
-                     &s->mesh_flags, &s->materials, &s->lights, &s->spheres, &s->texels, &s->tex_info};
+                     &s->mesh_flags, &s->materials, &s->lights, &s->spheres, &s->texels, &s->tex_info, &s->tree_nodes, &s->tree_order};
     for (DevBuf* b : all) b->release();
     delete s;
 }
@@ -593,8 +738,32 @@ yk_status yk_scene_get_build_info(const yk_scene* s, yk_bvh_build_info* out) {
 
 yk_status yk_scene_export_bvh(const yk_scene* s, yk_bvh_node* nodes, uint32_t* shape_order) {
     if (!s) return YK_ERR_INVALID_ARGUMENT;
-    if (nodes) std::memcpy(nodes, s->bvh->nodes.data(), s->bvh->nodes.size() * sizeof(yk_bvh_node));
-    if (shape_order) std::memcpy(shape_order, s->bvh->shape_order.data(), s->bvh->shape_order.size() * sizeof(uint32_t));
+    const HostBvh* bvh = scene_host_tree(s);
+    if (!bvh) return YK_ERR_DEVICE;
+    if (nodes) std::memcpy(nodes, bvh->nodes.data(), bvh->nodes.size() * sizeof(yk_bvh_node));
+    if (shape_order) std::memcpy(shape_order, bvh->shape_order.data(), bvh->shape_order.size() * sizeof(uint32_t));
+    return YK_OK;
+}
+
+yk_status yk_scene_get_layout_info(const yk_scene* s, yk_scene_layout_info* out) {
+    if (!s || !out) return YK_ERR_INVALID_ARGUMENT;
+    *out = s->layout;
+    out->tree_fetched = s->tree_fetched.load();
+    return YK_OK;
+}
+
+yk_status yk_scene_read_records(const yk_scene* s, uint32_t which, void* out, size_t cap_bytes, size_t* n_bytes) {
+    if (!s || !s->on_device || which > YK_RECORDS_PRIM_ATTR || !n_bytes) return YK_ERR_INVALID_ARGUMENT;
+    const DevBuf* bufs[] = {&s->nodes, &s->nodes4, &s->top_nodes, &s->top_nodes_any, &s->tris, &s->prim_shade, &s->prim_attr};
+    const size_t bytes = s->record_bytes[which];
+    *n_bytes = bytes;
+    if (!out) return YK_OK;
+    if (cap_bytes < bytes || bufs[which]->bytes < bytes) return YK_ERR_INVALID_ARGUMENT;
+    (void)hipSetDevice(s->device);
+    if (bytes && hipMemcpy(out, bufs[which]->p, bytes, hipMemcpyDeviceToHost) != hipSuccess) {
+        (void)hipGetLastError();
+        return YK_ERR_DEVICE;
+    }
     return YK_OK;
 }
 

@@ -1,0 +1,338 @@
+// yk_scene_layout.hip — "scene_layout" = 1: a scene's traversal records (DevNode, the two LDS tree tops, the
+// DevNode4 collapse, tris / prim_shade / prim_attr in leaf order) laid out on the device from the tree in HBM
+// (yk_scene_layout.h), and the host instance of the two order rules (yk_layout_top_order, yk_layout_wide_slots).
+// The bytes are those of layout_records_host (yk_scene.cpp); a failure here leaves its reason and the caller
+// lays the records out on the host.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "yk_internal.h"
+#include "yk_scene_layout.h"
+
+using namespace yk::lay;
+
+namespace {
+
+const int kScanThreads = 1024;  // nodes per block of a scan
+const int kThreads = 256;
+
+struct HostExec {
+    uint32_t tid = 0, nt = 1;
+    void sync() {}
+    uint32_t scan(uint32_t v, uint32_t& total) {
+        total = v;
+        return 0u;
+    }
+};
+struct WaveExec {  // one wave of 64 lanes
+    uint32_t tid, nt;
+    __device__ void sync() { __syncthreads(); }
+    __device__ uint32_t scan(uint32_t v, uint32_t& total) {
+        uint32_t inc = v;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const uint32_t o = __shfl_up(inc, off);
+            if (tid >= (uint32_t)off) inc += o;
+        }
+        total = __shfl(inc, 63);
+        return inc - v;
+    }
+};
+
+// ------------------------------------------------------------------ scans over the node array
+// The shape of the builder's compaction (k_scan_block / k_scan_sums, yk_bvh_build.hip): ranks inside blocks of
+// 1024, one block scans the block sums, a third pass makes the ranks absolute.
+__device__ uint32_t block_excl_scan(uint32_t v, uint32_t& total, uint32_t* wt) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    uint32_t inc = v;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const uint32_t o = __shfl_up(inc, off);
+        if (lane >= (uint32_t)off) inc += o;
+    }
+    if (lane == 63u) wt[wave] = inc;
+    __syncthreads();
+    uint32_t before = inc - v, all = 0u;
+    for (uint32_t w = 0; w < nw; ++w) {
+        const uint32_t t = wt[w];
+        if (w < wave) before += t;
+        all += t;
+    }
+    __syncthreads();
+    total = all;
+    return before;
+}
+// WIDE false: !is_leaf (-> interior index); true: w(i) (-> E, yk_scene_layout.h)
+template <bool WIDE> __global__ void __launch_bounds__(kScanThreads) k_scan_block(const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ depth, uint32_t n, uint32_t* index, uint32_t* bsum) {
+    __shared__ uint32_t wt[16];
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t v = 0u;
+    if (i < n) v = WIDE ? wide_count(nodes, depth, i) : (nd_leaf(nodes, i) ? 0u : 1u);
+    uint32_t total;
+    const uint32_t r = block_excl_scan(v, total, wt);
+    if (i < n) index[i] = r;
+    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
+}
+__global__ void __launch_bounds__(kScanThreads) k_scan_sums(uint32_t* bsum, uint32_t nb, uint32_t* total_out) {
+    __shared__ uint32_t wt[16];
+    uint32_t run = 0u;
+    for (uint32_t base = 0; base < nb; base += blockDim.x) {
+        const uint32_t i = base + threadIdx.x;
+        uint32_t total;
+        const uint32_t r = block_excl_scan(i < nb ? bsum[i] : 0u, total, wt);
+        if (i < nb) bsum[i] = run + r;
+        run += total;
+    }
+    if (threadIdx.x == 0) *total_out = run;
+}
+__global__ void k_scan_add(uint32_t* index, const uint32_t* __restrict__ bsum, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) index[i] += bsum[i / kScanThreads];
+}
+
+// ------------------------------------------------------------------ records
+// leaf order -> position in the caller's shape order -> source shape (in place: every lane owns its word)
+__global__ void k_apply_order(uint32_t* order, const uint32_t* __restrict__ user, uint32_t np) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < np) order[p] = user[order[p]];
+}
+// one lane per node: an interior node writes its DevNode, a leaf marks the last slot of its run
+__global__ void k_nodes(const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ iidx, uint32_t n, uint4* out, uint8_t* last) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (nd_leaf(nodes, i)) {
+        last[(size_t)nd_a(nodes, i) + nd_count(nodes, i) - 1u] = 1;
+        return;
+    }
+    uint4 q[4];
+    dev_node_words(nodes, i, ref_of(nodes, iidx, i + 1u), ref_of(nodes, iidx, nd_a(nodes, i)), q);
+    uint4* o = out + 4 * (size_t)iidx[i];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = q[k];
+}
+// block b (one wave) walks the queue of tree top b and writes its nodes; words[2 + b] = its size
+__global__ void __launch_bounds__(64) k_tops(const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ iidx, uint32_t cap_closest, uint32_t cap_any, uint4* out_closest, uint4* out_any, uint32_t* words) {
+    __shared__ uint32_t order[YK_TOP_MAX], id0[YK_TOP_MAX], id1[YK_TOP_MAX];
+    const uint32_t cap = blockIdx.x == 0 ? cap_closest : cap_any;
+    uint4* out = blockIdx.x == 0 ? out_closest : out_any;
+    WaveExec ex{threadIdx.x, blockDim.x};
+    const uint32_t size = top_order(ex, nodes, cap, order, id0, id1);
+    for (uint32_t q = threadIdx.x; q < size; q += blockDim.x) {
+        const uint32_t P = order[q];
+        const uint32_t r0 = id0[q] != kNone ? (YK_TOP_BIT | id0[q]) : ref_of(nodes, iidx, P + 1u);
+        const uint32_t r1 = id1[q] != kNone ? (YK_TOP_BIT | id1[q]) : ref_of(nodes, iidx, nd_a(nodes, P));
+        uint4 w[4];
+        dev_node_words(nodes, P, r0, r1, w);
+        uint4* o = out + 4 * (size_t)q;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) o[k] = w[k];
+    }
+    if (threadIdx.x == 0) words[2 + blockIdx.x] = size;
+}
+// one lane per collapsed node: the slots of its interior children
+__global__ void k_wide_slots(const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ depth, const uint32_t* __restrict__ excl, uint32_t n, uint32_t* slot) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || !wide_collapsed(nodes, depth, i)) return;
+    if (i == 0u) slot[0] = 0u;
+    uint32_t child[4], ref[4];
+    wide_children(nodes, i, child);
+    wide_refs(nodes, excl[i], child, ref, slot);
+}
+// one lane per collapsed node: its 128-byte record
+__global__ void k_wide_nodes(const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ depth, const uint32_t* __restrict__ excl, const uint32_t* __restrict__ slot, uint32_t n, uint32_t n4, uint4* out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n || !wide_collapsed(nodes, depth, i)) return;
+    const uint32_t me = slot[i];
+    if (me >= n4) return;
+    uint32_t child[4], ref[4];
+    wide_children(nodes, i, child);
+    wide_refs(nodes, excl[i], child, ref, nullptr);
+    uint4 q[8];
+    dev_node4_words(nodes, i, child, ref, q);
+    uint4* o = out + 8 * (size_t)me;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) o[k] = q[k];
+}
+// one lane per slot of the leaf order
+__global__ void k_prims(PrimArrays s, const uint32_t* __restrict__ order, const uint8_t* __restrict__ last, uint32_t np, uint32_t n_shapes_total, uint4* tris, uint4* prim_shade, uint4* prim_attr) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= np) return;
+    const uint32_t src = order[p];
+    if (src >= n_shapes_total) return;  // cannot happen (the order is a permutation of the shapes); guards the gathers
+    uint4 tri[3], shade, attr[4];
+    prim_words(s, src, last[p] != 0, tri, shade, attr, prim_attr != nullptr);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) tris[3 * (size_t)p + k] = tri[k];
+    prim_shade[p] = shade;
+    if (prim_attr) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) prim_attr[4 * (size_t)p + k] = attr[k];
+    }
+}
+
+struct Temp {  // freed on every way out
+    std::vector<void*> all;
+    ~Temp() {
+        for (void* p : all) (void)hipFree(p);
+    }
+    template <class T> bool get(T*& out, size_t count) {
+        void* p = nullptr;
+        if (hipMalloc(&p, std::max<size_t>(count * sizeof(T), 16)) != hipSuccess) {
+            (void)hipGetLastError();
+            return false;
+        }
+        all.push_back(p);
+        out = reinterpret_cast<T*>(p);
+        return true;
+    }
+};
+
+unsigned blocks(size_t n, int threads) { return (unsigned)((n + threads - 1) / threads); }
+
+}  // namespace
+
+// ------------------------------------------------------------------ the device layout
+uint32_t layout_scene_device(yk_context* ctx, yk_scene* s, const DeviceTree& tree, const uint32_t* d_user_order, const uint8_t* d_mat_kind, bool has_attr, uint32_t tree_depth, bool* order_applied) {
+    const uint32_t n = tree.n_nodes, np = tree.n_shapes;
+    if (n == 0 || np == 0 || n > YK_REF_INDEX_MAX || np > YK_REF_INDEX_MAX) return YK_LAYOUT_REASON_DEVICE_ERROR;
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    const uint32_t* nodes = tree.nodes.as<uint32_t>();
+    const uint32_t* depth = tree.depth.as<uint32_t>();
+    uint32_t* order = tree.order.as<uint32_t>();
+    const bool root_leaf = (tree.root_words[7] >> 24) != 0u;
+    const uint32_t n_interior = (n - 1u) / 2u;  // a full binary tree
+    const uint32_t cap_closest = (uint32_t)std::min<int64_t>(std::min<int64_t>(ctx->top_nodes, trace_top_nodes()), YK_TOP_MAX);
+    const uint32_t cap_any = (uint32_t)std::min<int64_t>(std::min<int64_t>(ctx->top_nodes, trace_top_nodes_any()), YK_TOP_MAX);
+    const bool wide = ctx->wide_bvh != 0 && !root_leaf && tree_depth <= 64;
+    const uint32_t nb = (n + kScanThreads - 1) / kScanThreads;
+
+    Temp tmp;
+    uint32_t *d_index = nullptr, *d_bsum = nullptr, *d_slot = nullptr, *d_words = nullptr;
+    uint8_t* d_last = nullptr;
+    if (!tmp.get(d_index, n) || !tmp.get(d_bsum, nb) || !tmp.get(d_last, np) || !tmp.get(d_words, 16) || (wide && !tmp.get(d_slot, n))) return YK_LAYOUT_REASON_OUT_OF_MEMORY;
+#define LAY_TRY(expr)                                                                                   \
+    do {                                                                                                \
+        const hipError_t e_ = (expr);                                                                   \
+        if (e_ != hipSuccess) {                                                                         \
+            (void)hipGetLastError();                                                                    \
+            (void)hipStreamSynchronize(st);                                                             \
+            return e_ == hipErrorOutOfMemory ? YK_LAYOUT_REASON_OUT_OF_MEMORY : YK_LAYOUT_REASON_DEVICE_ERROR; \
+        }                                                                                               \
+    } while (0)
+    LAY_TRY(s->nodes.ensure(std::max<size_t>(n_interior, 1) * sizeof(DevNode)));
+    LAY_TRY(s->top_nodes.ensure(std::max<size_t>((size_t)std::min(cap_closest, n_interior) * sizeof(DevNode), 16)));
+    LAY_TRY(s->top_nodes_any.ensure(std::max<size_t>((size_t)std::min(cap_any, n_interior) * sizeof(DevNode), 16)));
+    LAY_TRY(s->tris.ensure(3 * (size_t)np * sizeof(float4)));
+    LAY_TRY(s->prim_shade.ensure((size_t)np * sizeof(uint4)));
+    LAY_TRY(s->prim_attr.ensure(has_attr ? 4 * (size_t)np * sizeof(float4) : 16));
+
+    LAY_TRY(hipMemsetAsync(d_words, 0, 16 * sizeof(uint32_t), st));
+    LAY_TRY(hipMemsetAsync(d_last, 0, np, st));
+    if (d_user_order) {
+        k_apply_order<<<blocks(np, kThreads), kThreads, 0, st>>>(order, d_user_order, np);
+        LAY_TRY(hipGetLastError());
+        *order_applied = true;
+    }
+    // interior index, DevNode, last-in-leaf marks
+    k_scan_block<false><<<nb, kScanThreads, 0, st>>>(nodes, depth, n, d_index, d_bsum);
+    k_scan_sums<<<1, kScanThreads, 0, st>>>(d_bsum, nb, d_words + 0);
+    k_scan_add<<<blocks(n, kThreads), kThreads, 0, st>>>(d_index, d_bsum, n);
+    if (n_interior == 0) LAY_TRY(hipMemsetAsync(s->nodes.p, 0, sizeof(DevNode), st));  // a single leaf: one default node
+    k_nodes<<<blocks(n, kThreads), kThreads, 0, st>>>(nodes, d_index, n, s->nodes.as<uint4>(), d_last);
+    // tree tops (they read the interior index, which the wide scan below overwrites)
+    k_tops<<<2, 64, 0, st>>>(nodes, d_index, std::min(cap_closest, n_interior), std::min(cap_any, n_interior), s->top_nodes.as<uint4>(), s->top_nodes_any.as<uint4>(), d_words);
+    LAY_TRY(hipGetLastError());
+    // primitive records
+    PrimArrays pa;
+    pa.indices = s->indices.as<uint32_t>();
+    pa.points = s->points.as<float>();
+    pa.normals = s->normals.as<float>();
+    pa.uvs = s->uvs.as<float>();
+    pa.tri_mesh = s->tri_mesh.as<uint32_t>();
+    pa.tri_material = s->tri_material.as<int32_t>();
+    pa.tri_area_light = s->tri_area_light.as<int32_t>();
+    pa.mesh_flags = s->mesh_flags.as<uint32_t>();
+    pa.spheres = s->spheres.as<DevSphere>();
+    pa.mat_kind = d_mat_kind;
+    pa.n_triangles = s->n_triangles;
+    k_prims<<<blocks(np, kThreads), kThreads, 0, st>>>(pa, order, d_last, np, s->n_triangles + s->n_spheres, s->tris.as<uint4>(), s->prim_shade.as<uint4>(), has_attr ? s->prim_attr.as<uint4>() : nullptr);
+    LAY_TRY(hipGetLastError());
+    // 4-wide collapse: E over the array, the slots, the records
+    uint32_t words[16];
+    if (wide) {
+        k_scan_block<true><<<nb, kScanThreads, 0, st>>>(nodes, depth, n, d_index, d_bsum);
+        k_scan_sums<<<1, kScanThreads, 0, st>>>(d_bsum, nb, d_words + 1);
+        k_scan_add<<<blocks(n, kThreads), kThreads, 0, st>>>(d_index, d_bsum, n);
+        k_wide_slots<<<blocks(n, kThreads), kThreads, 0, st>>>(nodes, depth, d_index, n, d_slot);
+        LAY_TRY(hipGetLastError());
+    }
+    LAY_TRY(hipMemcpyAsync(words, d_words, sizeof(words), hipMemcpyDeviceToHost, st));
+    LAY_TRY(hipStreamSynchronize(st));
+    if (words[0] != n_interior) return YK_LAYOUT_REASON_DEVICE_ERROR;
+    uint32_t n4 = 0;
+    if (wide) {
+        n4 = 1u + words[1];
+        if (n4 > n_interior) return YK_LAYOUT_REASON_DEVICE_ERROR;
+        LAY_TRY(s->nodes4.ensure((size_t)n4 * sizeof(DevNode4)));
+        k_wide_nodes<<<blocks(n, kThreads), kThreads, 0, st>>>(nodes, depth, d_index, d_slot, n, n4, s->nodes4.as<uint4>());
+        LAY_TRY(hipGetLastError());
+        LAY_TRY(hipStreamSynchronize(st));
+    } else {
+        LAY_TRY(s->nodes4.ensure(16));
+    }
+#undef LAY_TRY
+    yk_scene_layout_info& li = s->layout;
+    li.root_ref = root_leaf ? (YK_LEAF_BIT | tree.root_words[6]) : 0u;
+    li.n_top = words[2];
+    li.n_top_any = words[3];
+    li.wide = wide ? 1u : 0u;
+    li.wide_auto = wide && ctx->wide_bvh == 2 ? 1u : 0u;
+    s->record_bytes[YK_RECORDS_NODES] = std::max<size_t>(n_interior, 1) * sizeof(DevNode);
+    s->record_bytes[YK_RECORDS_NODES4] = (size_t)n4 * sizeof(DevNode4);
+    s->record_bytes[YK_RECORDS_TOP] = (size_t)words[2] * sizeof(DevNode);
+    s->record_bytes[YK_RECORDS_TOP_ANY] = (size_t)words[3] * sizeof(DevNode);
+    s->record_bytes[YK_RECORDS_TRIS] = 3 * (size_t)np * sizeof(float4);
+    s->record_bytes[YK_RECORDS_PRIM_SHADE] = (size_t)np * sizeof(uint4);
+    s->record_bytes[YK_RECORDS_PRIM_ATTR] = has_attr ? 4 * (size_t)np * sizeof(float4) : 0;
+    return YK_LAYOUT_REASON_NONE;
+}
+
+// ------------------------------------------------------------------ the host instance of the two order rules
+extern "C" size_t yk_layout_top_order(const yk_bvh_node* nodes, size_t n, uint32_t cap, uint32_t* out_order) try {
+    if (!nodes || n == 0 || n > YK_REF_INDEX_MAX || (cap && !out_order)) return 0;
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(nodes);
+    HostExec ex;
+    return top_order(ex, w, cap, out_order, (uint32_t*)nullptr, (uint32_t*)nullptr);
+} catch (const std::exception&) {
+    return 0;
+}
+
+extern "C" size_t yk_layout_wide_slots(const yk_bvh_node* nodes, size_t n, uint32_t* out_slot_per_node) try {
+    if (!nodes || n == 0 || n > YK_REF_INDEX_MAX || !out_slot_per_node) return 0;
+    const uint32_t* w = reinterpret_cast<const uint32_t*>(nodes);
+    for (size_t i = 0; i < n; ++i) out_slot_per_node[i] = kNone;
+    if (nd_leaf(w, 0u)) return 0;
+    std::vector<uint32_t> depth(n, 0u), excl(n);
+    depth[0] = 1u;
+    for (uint32_t i = 0; i < (uint32_t)n; ++i)
+        if (!nd_leaf(w, i)) depth[i + 1u] = depth[nd_a(w, i)] = depth[i] + 1u;
+    uint32_t run = 0u;
+    for (uint32_t i = 0; i < (uint32_t)n; ++i) {  // the scan
+        excl[i] = run;
+        run += wide_count(w, depth.data(), i);
+    }
+    out_slot_per_node[0] = 0u;
+    for (uint32_t i = 0; i < (uint32_t)n; ++i) {  // the lanes of k_wide_slots
+        if (!wide_collapsed(w, depth.data(), i)) continue;
+        uint32_t child[4], ref[4];
+        wide_children(w, i, child);
+        wide_refs(w, excl[i], child, ref, out_slot_per_node);
+    }
+    return 1u + (size_t)run;
+} catch (const std::exception&) {
+    return 0;
+}

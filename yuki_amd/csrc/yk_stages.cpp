@@ -102,7 +102,9 @@ yk_status yk_trace_closest(yk_context* ctx, const yk_scene* scene, size_t n, con
     HIP_TRY(ctx, hipMemcpyAsync(host_ctrl, ctrl, 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     if (mode != 0) {  // hit word -> source shape (the scene's leaf-order table); its kind bits must be the shape's material's
-        const std::vector<uint32_t>& order = scene->bvh->shape_order;
+        const HostBvh* tree = scene_host_tree(scene);
+        if (!tree) return fail(ctx, YK_ERR_DEVICE, "the scene's shape order could not be copied back from the device");
+        const std::vector<uint32_t>& order = tree->shape_order;
         for (size_t i = 0; i < n; ++i) {
             const int32_t h = out_shape[i];
             if (h == -1) continue;
