@@ -555,6 +555,56 @@ yk_status yk_overlay_draw(yk_context* ctx, const float world_to_clip[16], const 
 yk_status yk_overlay_draw_device(yk_context* ctx, const float world_to_clip[16], const void* d_lines, size_t n_lines, const void* d_boxes,
                                  size_t n_boxes, void* d_film_rgb, uint16_t res_x, uint16_t res_y, void* stream);
 
+/* ---- present: ScaleOutput::draw (app/renderpasses/scale_output.rs), the last pass of a frame (app/window.rs:246-270) ----
+ * The tone-mapped film stretched into the window with bilinear filtering, the aspect ratio kept inside a letterbox,
+ * sRGB-encoded, as an 8-bit frame.  GL fixes no bit-level result for a textured quad; the rule fixed here is stated next
+ * to the scale_output.rs lines it comes from in yuki_amd/csrc/yk_present.h, and the host and the device instance agree
+ * bit for bit.  In short (binary32, every operation separate, no FMA):
+ *   Rectangle (:64-84, the reference's u32 arithmetic): frame_aspect < texture_aspect: scaled_height = (W*h)/w, full
+ *     width, centred vertically with the larger margin ABOVE when the difference is odd; otherwise scaled_width =
+ *     (H*w)/h, full height, centred with the larger margin on the right.  Film row 0 is the top row.  Coverage is
+ *     exactly that integer rectangle; it may be empty.
+ *   Texture coordinate, exact: n = (2*(i - x0) + 1)*w - width, d = 2*width, first tap floor(n / d), neighbour's weight
+ *     (float)(n mod d) / (float)d; rows alike.  Identity and integer magnification have exact taps.
+ *   Filter (:58-62): Linear both ways, 2 x 2 taps, no mip levels; BorderClamp with GL's border (0, 0, 0), so a magnified
+ *     film has a dark half-texel fringe (reproduced).  mix(x, y, a) = a == 0 ? x : x*(1 - a) + y*a, horizontal mixes
+ *     first; a tap of weight zero is not read.  A NaN an operation produces is 0x7fc00000; a copied value keeps its bits.
+ *   Encode: NONE = the shader's output with gamma_before_output == 0; SHADER = its linearToSRGB (:154-158), x <=
+ *     0.0031308 ? 12.92*x : 1.055*pow(x, 1/2.2) - 0.055; SRGB = what an sRGB back buffer stores (the reference's default,
+ *     window.rs:94-127): 0 for x <= 0 or NaN, 12.92*x below 0.0031308, 1.055*pow(x, 0.41666) - 0.055 below 1, else 1.
+ *     pow(x, y) = exp(y * log(x)) with the library's own logf / expf.
+ *   Frame: RGBA8 = (uint8_t)(saturate(x)*255 + 0.5) per channel (NaN -> 0), alpha 255, the clear colour (0, 0, 0, 255)
+ *     outside the rectangle (window.rs:247), rows top-down, bytes R, G, B, A.  RGB32F = the three floats before
+ *     quantisation, 0 outside. */
+typedef enum yk_present_encode { YK_PRESENT_ENCODE_NONE = 0, YK_PRESENT_ENCODE_SHADER = 1, YK_PRESENT_ENCODE_SRGB = 2 } yk_present_encode;
+typedef enum yk_present_format { YK_PRESENT_RGBA8 = 0, YK_PRESENT_RGB32F = 1 } yk_present_format;
+typedef struct yk_present_desc {
+    uint16_t window_x, window_y; /* the window (frame.get_dimensions()) */
+    uint32_t encode;             /* yk_present_encode */
+    uint32_t format;             /* yk_present_format */
+} yk_present_desc;               /* 12 bytes */
+typedef struct yk_present_rect {
+    int32_t x0, y0;         /* top-down window coordinates of the first column and row */
+    uint32_t width, height; /* either may be 0 */
+} yk_present_rect;
+/* The target rectangle of a res_x x res_y film in a window_x x window_y window, unclipped.  A host function.
+ * YK_ERR_INVALID_ARGUMENT: a zero dimension, NULL out. */
+yk_status yk_present_target_rect(uint16_t res_x, uint16_t res_y, uint16_t window_x, uint16_t window_y, yk_present_rect* out);
+/* Host buffers: film_rgb row-major RGB (res_y, res_x, 3); out (window_y, window_x) pixels of 4 bytes (RGBA8) or of three
+ * floats (RGB32F).  ctx NULL = the host instance on the CPU, else on ctx's device (synchronous).
+ * YK_ERR_INVALID_ARGUMENT: a NULL pointer, a zero film or window dimension, an unknown encode or format, an output that
+ * overlaps the film. */
+yk_status yk_present(yk_context* ctx, const yk_present_desc* desc, const float* film_rgb, uint16_t res_x, uint16_t res_y, void* out);
+/* The same on device buffers, enqueued on `stream` (NULL = the context's): one kernel writes every window pixel, the
+ * letterbox included; no host synchronisation, no allocation, no work buffer.  d_film_rgb and d_out need 4-byte
+ * alignment (anything else: YK_ERR_INVALID_ARGUMENT, nothing is launched). */
+yk_status yk_present_device(yk_context* ctx, const yk_present_desc* desc, const void* d_film_rgb, uint16_t res_x, uint16_t res_y,
+                            void* d_out, void* stream);
+/* An 8-bit PNG: channels 3 (RGB) or 4 (RGBA), non-interlaced, filter type 0 on every row, the data in stored deflate
+ * blocks.  pixels: row-major, row 0 = top, `channels` bytes a pixel — what yk_present writes as RGBA8.  Host only.
+ * YK_ERR_INVALID_ARGUMENT: NULL path or pixels, a zero dimension, channels other than 3 or 4, a file that cannot be written. */
+yk_status yk_write_png(const char* path, uint32_t width, uint32_t height, uint32_t channels, const uint8_t* pixels);
+
 /* ---- per-stage entry points (parity tests, profiling) ------------------------- */
 /* BoundingVolumeHierarchy::intersect (bvh.rs:160-232) for n host rays.
  * out_shape: source shape index or -1; counters as IntersectionResult. */

@@ -230,6 +230,31 @@ class LoadedScene {
 // app/util.rs:90-111
 inline void write_exr(const std::string& path, uint32_t width, uint32_t height, const float* rgb) { check(yk_write_exr(path.c_str(), width, height, rgb)); }
 
+// ScaleOutput::draw (app/renderpasses/scale_output.rs), the last pass of a frame: the rule is stated in yuki_hip.h.
+inline yk_present_rect present_target_rect(uint16_t res_x, uint16_t res_y, uint16_t window_x, uint16_t window_y) {
+    yk_present_rect r;
+    check(yk_present_target_rect(res_x, res_y, window_x, window_y, &r));
+    return r;
+}
+// The tone-mapped film (row-major RGB, res_x * res_y * 3) as the window's RGBA8 frame, rows top-down: window_x * window_y * 4
+// bytes.  ctx == nullptr: the host instance.  encode: the reference's default is the sRGB back buffer.
+inline std::vector<uint8_t> present_rgba8(Context* ctx, const float* film, uint16_t res_x, uint16_t res_y, uint16_t window_x, uint16_t window_y,
+                                          uint32_t encode = YK_PRESENT_ENCODE_SRGB) {
+    const yk_present_desc d = {window_x, window_y, encode, YK_PRESENT_RGBA8};
+    std::vector<uint8_t> out((size_t)window_x * window_y * 4);
+    yk_context* c = ctx ? ctx->handle() : nullptr;
+    check(yk_present(c, &d, film, res_x, res_y, out.data()), c);
+    return out;
+}
+// The same on device buffers, enqueued on `stream` (nullptr: the context's): one kernel, no allocation, no synchronisation.
+inline void present_device(Context& ctx, const yk_present_desc& desc, const void* d_film, uint16_t res_x, uint16_t res_y, void* d_out, void* stream = nullptr) {
+    check(yk_present_device(ctx.handle(), &desc, d_film, res_x, res_y, d_out, stream), ctx.handle());
+}
+// 8-bit PNG, channels 3 or 4, row 0 at the top
+inline void write_png(const std::string& path, uint32_t width, uint32_t height, uint32_t channels, const uint8_t* pixels) {
+    check(yk_write_png(path.c_str(), width, height, channels, pixels));
+}
+
 // trait Integrator, integrators/mod.rs:92-186
 class Integrator {
    public:

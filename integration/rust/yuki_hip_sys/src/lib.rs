@@ -50,6 +50,11 @@ pub const YK_HEATMAP_RED: u32 = 0;
 pub const YK_HEATMAP_GREEN: u32 = 1;
 pub const YK_HEATMAP_BLUE: u32 = 2;
 pub const YK_HEATMAP_LUMINANCE: u32 = 3;
+pub const YK_PRESENT_ENCODE_NONE: u32 = 0;
+pub const YK_PRESENT_ENCODE_SHADER: u32 = 1;
+pub const YK_PRESENT_ENCODE_SRGB: u32 = 2;
+pub const YK_PRESENT_RGBA8: u32 = 0;
+pub const YK_PRESENT_RGB32F: u32 = 1;
 
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -178,6 +183,26 @@ pub struct yk_tone_map_desc {
     pub channel: u32,
     pub has_bounds: u32,
     pub bounds: [f32; 2],
+}
+
+/// ScaleOutput::draw (app/renderpasses/scale_output.rs): the window, the encode and the frame format
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct yk_present_desc {
+    pub window_x: u16,
+    pub window_y: u16,
+    pub encode: u32,
+    pub format: u32,
+}
+
+/// The target rectangle of ScaleOutput::draw in top-down window coordinates
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct yk_present_rect {
+    pub x0: i32,
+    pub y0: i32,
+    pub width: u32,
+    pub height: u32,
 }
 
 /// IntegratorRay (integrators/mod.rs:76-80): the ray and its yk_ray_type
@@ -360,6 +385,10 @@ extern "C" {
     pub fn yk_overlay_ray_lines(rays: *const yk_integrator_ray, n: usize, out: *mut yk_overlay_line) -> yk_status;
     pub fn yk_overlay_draw(ctx: *mut yk_context, world_to_clip: *const f32, lines: *const yk_overlay_line, n_lines: usize, boxes: *const f32, n_boxes: usize, film_rgb: *mut f32, res_x: u16, res_y: u16) -> yk_status;
     pub fn yk_overlay_draw_device(ctx: *mut yk_context, world_to_clip: *const f32, d_lines: *const c_void, n_lines: usize, d_boxes: *const c_void, n_boxes: usize, d_film_rgb: *mut c_void, res_x: u16, res_y: u16, stream: *mut c_void) -> yk_status;
+    pub fn yk_present_target_rect(res_x: u16, res_y: u16, window_x: u16, window_y: u16, out: *mut yk_present_rect) -> yk_status;
+    pub fn yk_present(ctx: *mut yk_context, desc: *const yk_present_desc, film_rgb: *const f32, res_x: u16, res_y: u16, out: *mut c_void) -> yk_status;
+    pub fn yk_present_device(ctx: *mut yk_context, desc: *const yk_present_desc, d_film_rgb: *const c_void, res_x: u16, res_y: u16, d_out: *mut c_void, stream: *mut c_void) -> yk_status;
+    pub fn yk_write_png(path: *const c_char, width: u32, height: u32, channels: u32, pixels: *const u8) -> yk_status;
     pub fn yk_render_tile(ctx: *mut yk_context, scene: *const yk_scene, camera: *const yk_camera, sampler: *const yk_sampler_desc, integrator: *const yk_integrator_desc, tile: *const yk_tile, tile_pixels: *mut f32, out_rays: *mut u64) -> yk_status;
     pub fn yk_film_update_tiles_device(ctx: *mut yk_context, tiles: *const yk_tile, n_tiles: usize, d_tile_rgb: *const c_void, res_x: u16, res_y: u16, d_film_rgb: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_li(ctx: *mut yk_context, scene: *const yk_scene, sampler: *const yk_sampler_desc, integrator: *const yk_integrator_desc, n: usize, ray_o: *const f32, ray_d: *const f32, pixel_xy: *const u16, sample_index: *const u32, dimension: u32, out_li: *mut f32, out_ray_counts: *mut u32) -> yk_status;

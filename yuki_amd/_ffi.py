@@ -162,6 +162,10 @@ SYMBOLS = {
     "yk_overlay_ray_lines": (C.c_int, [vp, C.c_size_t, vp]),
     "yk_overlay_draw": (C.c_int, [vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_uint16, C.c_uint16]),
     "yk_overlay_draw_device": (C.c_int, [vp, vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_uint16, C.c_uint16, vp]),
+    "yk_present_target_rect": (C.c_int, [C.c_uint16, C.c_uint16, C.c_uint16, C.c_uint16, C.POINTER(abi.PresentRect)]),
+    "yk_present": (C.c_int, [vp, C.POINTER(abi.PresentDesc), vp, C.c_uint16, C.c_uint16, vp]),
+    "yk_present_device": (C.c_int, [vp, C.POINTER(abi.PresentDesc), vp, C.c_uint16, C.c_uint16, vp, vp]),
+    "yk_write_png": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
     # several GPUs
     "yk_multi_create": (C.c_int, [C.POINTER(C.c_int), C.c_uint32, C.POINTER(vp)]),
     "yk_multi_create_ex": (C.c_int, [C.POINTER(C.c_int), C.c_uint32, C.c_uint32, C.POINTER(vp)]),

@@ -114,6 +114,18 @@ class ToneMapDesc(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("exposure", C.c_float), ("channel", C.c_uint32), ("has_bounds", C.c_uint32), ("bounds", C.c_float * 2)]
 
 
+class PresentDesc(C.Structure):
+    """yk_present_desc: the window, the encode (yk_present_encode) and the frame format (yk_present_format)."""
+
+    _fields_ = [("window_x", C.c_uint16), ("window_y", C.c_uint16), ("encode", C.c_uint32), ("format", C.c_uint32)]
+
+
+class PresentRect(C.Structure):
+    """yk_present_rect: the target rectangle of ScaleOutput::draw in top-down window coordinates."""
+
+    _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("width", C.c_uint32), ("height", C.c_uint32)]
+
+
 class IntegratorRay(C.Structure):
     """yk_integrator_ray: IntegratorRay (integrators/mod.rs:76-80), the ray and its yk_ray_type."""
 
@@ -180,6 +192,8 @@ RAY_DIRECT, RAY_REFLECTION, RAY_REFRACTION, RAY_NORMAL, RAY_SHADOW = 0, 1, 2, 3,
 FOV_X, FOV_Y = 0, 1
 TONE_MAP_RAW, TONE_MAP_FILMIC, TONE_MAP_HEATMAP = 0, 1, 2
 HEATMAP_RED, HEATMAP_GREEN, HEATMAP_BLUE, HEATMAP_LUMINANCE = 0, 1, 2, 3
+PRESENT_ENCODE_NONE, PRESENT_ENCODE_SHADER, PRESENT_ENCODE_SRGB = 0, 1, 2
+PRESENT_RGBA8, PRESENT_RGB32F = 0, 1
 LAYOUT_HOST, LAYOUT_DEVICE = 0, 1
 LAYOUT_REASON_NONE, LAYOUT_REASON_OUT_OF_MEMORY, LAYOUT_REASON_DEVICE_ERROR, LAYOUT_REASON_MULTI = 0, 1, 2, 3
 RECORDS_NODES, RECORDS_NODES4, RECORDS_TOP, RECORDS_TOP_ANY, RECORDS_TRIS, RECORDS_PRIM_SHADE, RECORDS_PRIM_ATTR = range(7)

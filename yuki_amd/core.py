@@ -280,6 +280,61 @@ def draw_visualizations(film, scene, camera_params, film_settings, rays=None, bv
     return draw_overlay(film, m, lines, boxes, ctx)
 
 
+# --------------------------------------------------------------------------- present
+_PRESENT_FORMATS = {"rgba8": abi.PRESENT_RGBA8, "rgb32f": abi.PRESENT_RGB32F}
+
+
+def _present_desc(window, encode, fmt):
+    if isinstance(fmt, str):
+        if fmt not in _PRESENT_FORMATS:
+            raise ValueError(f"fmt is 'rgba8' or 'rgb32f', not {fmt!r}")
+        fmt = _PRESENT_FORMATS[fmt]
+    return abi.PresentDesc(int(window[0]), int(window[1]), int(encode), int(fmt))
+
+
+def present_target_rect(res, window):
+    """The target rectangle of ScaleOutput::draw (scale_output.rs:64-84) for a film of `res` = (w, h) in a window (W, H):
+    (x0, y0, width, height) in top-down window coordinates, unclipped."""
+    r = abi.PresentRect()
+    check(lib().yk_present_target_rect(int(res[0]), int(res[1]), int(window[0]), int(window[1]), C.byref(r)))
+    return int(r.x0), int(r.y0), int(r.width), int(r.height)
+
+
+def present(film, window, encode=2, fmt="rgba8", ctx=None):
+    """ScaleOutput::draw (app/renderpasses/scale_output.rs) by the rule of csrc/yk_present.h: the (h, w, 3) float32
+    tone-mapped film stretched into a window (W, H) with bilinear filtering inside a letterbox.  encode 0 none, 1 the
+    shader's linearToSRGB, 2 an sRGB back buffer (the reference's default).  Returns (H, W, 4) uint8 for fmt "rgba8",
+    (H, W, 3) float32 (the values before quantisation) for "rgb32f".  ctx None = the host instance."""
+    film = np.ascontiguousarray(film, dtype=np.float32)
+    if film.ndim != 3 or film.shape[2] != 3:
+        raise ValueError("film is (h, w, 3)")
+    d = _present_desc(window, encode, fmt)
+    out = np.empty((d.window_y, d.window_x, 4), dtype=np.uint8) if d.format == abi.PRESENT_RGBA8 else np.empty((d.window_y, d.window_x, 3), dtype=np.float32)
+    c = ctx.h if ctx else None
+    check(lib().yk_present(c, C.byref(d), _p(film), film.shape[1], film.shape[0], _p(out)), c)
+    return out
+
+
+def write_png(path, pixels):
+    """yk_write_png: (h, w, 3) or (h, w, 4) uint8 -> an 8-bit PNG, row 0 at the top."""
+    pixels = np.ascontiguousarray(pixels, dtype=np.uint8)
+    if pixels.ndim != 3:
+        raise ValueError("pixels is (h, w, 3) or (h, w, 4)")
+    check(lib().yk_write_png(str(path).encode(), pixels.shape[1], pixels.shape[0], pixels.shape[2], _p(pixels)))
+
+
+def write_preview(path, film, tone_map=None, settings=None, samples=None, window=None, ctx=None):
+    """What the window shows, as a PNG: the tone map (as write_output: None = ToneMapType.default(), Raw = none), then
+    present into `window` (default: the film's size) as an sRGB back buffer stores it (encode 2), then write_png."""
+    film = np.ascontiguousarray(film, dtype=np.float32)
+    tone_map = ToneMapType.default() if tone_map is None else tone_map
+    settings = settings or FilmSettings(res=(film.shape[1], film.shape[0]))
+    if tone_map.kind != abi.TONE_MAP_RAW:
+        film = _apply_tone_map(film, tone_map, film_tile_dim(settings), samples, ctx, None)
+    window = (film.shape[1], film.shape[0]) if window is None else window
+    write_png(path, present(film, window, abi.PRESENT_ENCODE_SRGB, "rgba8", ctx))
+
+
 class TileList:
     """A tile list prepared once on the device (yk_tile_list): the GPU worker's tile queue."""
 
@@ -426,6 +481,13 @@ class Context:
             lib().yk_overlay_draw_device(self.h, _p(m), C.c_void_p(d_lines_ptr) if d_lines_ptr else None, int(n_lines), C.c_void_p(d_boxes_ptr) if d_boxes_ptr else None, int(n_boxes), C.c_void_p(d_film_ptr), res[0], res[1], C.c_void_p(stream) if stream else None),
             self.h,
         )
+
+    def present_device(self, d_film_ptr, res, window, encode, fmt, d_out_ptr, stream=None):
+        """yk_present_device: the device film of `res` = (w, h) -> the device frame of `window` = (W, H) ("rgba8": 4 bytes
+        a pixel, "rgb32f": three floats), enqueued on `stream` (default: the context's) without waiting; one kernel, no
+        allocation.  Both pointers need 4-byte alignment."""
+        d = _present_desc(window, encode, fmt)
+        check(lib().yk_present_device(self.h, C.byref(d), C.c_void_p(d_film_ptr), int(res[0]), int(res[1]), C.c_void_p(d_out_ptr), C.c_void_p(stream) if stream else None), self.h)
 
     @property
     def stream_handle(self):

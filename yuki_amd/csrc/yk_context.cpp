@@ -301,6 +301,8 @@ size_t yk_sizeof(int what) {
         case 15: return sizeof(yk_bvh_build_info);
         case 16: return sizeof(yk_overlay_line);
         case 17: return sizeof(yk_scene_layout_info);
+        case 18: return sizeof(yk_present_desc);
+        case 19: return sizeof(yk_present_rect);
         default: return 0;
     }
 }

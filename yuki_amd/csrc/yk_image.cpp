@@ -9,7 +9,9 @@
 //   * no gamma / sRGB conversion, alpha dropped, Adam7 interlace supported, CRC and
 //     Adler-32 verified (a corrupt file is a decode error in the reference too).
 // The decoder is chosen from the file extension, like image::io::Reader::open; the other
-// containers (BMP, TGA, PPM, QOI, farbfeld, EXR) live in yk_image_formats.cpp.
+// containers (BMP, TGA, PPM, QOI, farbfeld, EXR) live in yk_image_formats.cpp.  The film and
+// frame writers (EXR, PFM, PNG) are at the end.
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -451,6 +453,65 @@ yk_status yk_write_pfm(const char* path, uint32_t width, uint32_t height, const 
     for (uint32_t y = height; y-- > 0 && ok;) ok = std::fwrite(rgb + 3 * (size_t)y * width, 4, 3 * (size_t)width, f) == 3 * (size_t)width;
     ok = (std::fclose(f) == 0) && ok;
     return ok ? YK_OK : YK_ERR_INVALID_ARGUMENT;
+}
+
+// PNG (ISO/IEC 15948): IHDR, one IDAT, IEND.  8 bits a sample, colour type 2 (RGB) or 6 (RGBA), no interlace, filter
+// type 0 in front of every row; the zlib stream holds stored deflate blocks (at most 65535 bytes each) and ends in the
+// Adler-32 of the filtered rows.  The frame of yk_present goes in as it is.
+yk_status yk_write_png(const char* path, uint32_t width, uint32_t height, uint32_t channels, const uint8_t* pixels) try {
+    if (!path || !pixels || width == 0 || height == 0 || (channels != 3 && channels != 4)) return YK_ERR_INVALID_ARGUMENT;
+    const uint64_t stride = (uint64_t)width * channels, raw_bytes = (stride + 1) * height;
+    if (raw_bytes > (1ull << 30)) return ifail(YK_ERR_INVALID_ARGUMENT, "PNG: image too large for one IDAT chunk");
+    std::vector<uint8_t> raw;
+    raw.reserve((size_t)raw_bytes);
+    for (uint32_t y = 0; y < height; ++y) {
+        raw.push_back(0);  // filter type 0 (None)
+        raw.insert(raw.end(), pixels + (size_t)y * stride, pixels + (size_t)(y + 1) * stride);
+    }
+    std::vector<uint8_t> file;
+    auto put32 = [&](uint32_t v) {
+        for (int s = 24; s >= 0; s -= 8) file.push_back((uint8_t)(v >> s));
+    };
+    // a chunk: length, type + data, CRC-32 of type + data
+    auto chunk = [&](const char* type, const std::vector<uint8_t>& data) {
+        put32((uint32_t)data.size());
+        const size_t at = file.size();
+        file.insert(file.end(), type, type + 4);
+        file.insert(file.end(), data.begin(), data.end());
+        put32(crc32(file.data() + at, 4 + data.size()));
+    };
+    static const uint8_t SIG[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
+    file.insert(file.end(), SIG, SIG + 8);
+    std::vector<uint8_t> ihdr;
+    for (uint32_t v : {width, height})
+        for (int s = 24; s >= 0; s -= 8) ihdr.push_back((uint8_t)(v >> s));
+    const uint8_t tail[5] = {8, (uint8_t)(channels == 3 ? 2 : 6), 0, 0, 0};  // bit depth, colour type, compression, filter method, interlace
+    ihdr.insert(ihdr.end(), tail, tail + 5);
+    chunk("IHDR", ihdr);
+    std::vector<uint8_t> z;
+    z.reserve(raw.size() + 5 * (raw.size() / 65535 + 1) + 6);
+    z.push_back(0x78);  // CM = 8 (deflate), CINFO = 7 (32 KiB window)
+    z.push_back(0x01);  // FLEVEL 0, no dictionary; 0x7801 is a multiple of 31
+    for (size_t at = 0; at < raw.size(); at += 65535) {
+        const size_t n = std::min<size_t>(65535, raw.size() - at);
+        z.push_back(at + n == raw.size() ? 1 : 0);  // BFINAL, BTYPE = 00 (stored)
+        z.push_back((uint8_t)n);
+        z.push_back((uint8_t)(n >> 8));
+        z.push_back((uint8_t)~n);
+        z.push_back((uint8_t)(~n >> 8));
+        z.insert(z.end(), raw.begin() + at, raw.begin() + at + n);
+    }
+    const uint32_t ad = adler32(raw);
+    for (int s = 24; s >= 0; s -= 8) z.push_back((uint8_t)(ad >> s));
+    chunk("IDAT", z);
+    chunk("IEND", {});
+    std::FILE* f = std::fopen(path, "wb");
+    if (!f) return ifail(YK_ERR_INVALID_ARGUMENT, std::string("Error writing PNG to '") + path + "'");
+    bool ok = std::fwrite(file.data(), 1, file.size(), f) == file.size();
+    ok = (std::fclose(f) == 0) && ok;
+    return ok ? YK_OK : ifail(YK_ERR_INVALID_ARGUMENT, std::string("Error writing PNG to '") + path + "'");
+} catch (const std::exception&) {
+    return ifail(YK_ERR_OUT_OF_MEMORY, "PNG: host allocation failed");
 }
 
 void yk_image_texture_free(yk_texture_desc* tex) {

@@ -393,7 +393,8 @@ YK_HD float gl_tanf(float x) {
     return gl_kernel_tanf(y0, y1, 1 - ((n & 1) << 1));
 }
 
-// expf (e_expf.c, the `__expf_fma` build; host side only — the pbrt loader's CIE fits): 2^(k/32) from a table, a cubic in binary64
+// expf (e_expf.c, the `__expf_fma` build; the pbrt loader's CIE fits on the host, pow of the present pass's sRGB encode on both sides,
+// yk_present.h): 2^(k/32) from a table, a cubic in binary64
 YK_HD unsigned long long gl_exp2f_entry(unsigned i) {
     const unsigned long long tab[32] = {
     0x3ff0000000000000, 0x3fefd9b0d3158574, 0x3fefb5586cf9890f, 0x3fef9301d0125b51, 0x3fef72b83c7d517b, 0x3fef54873168b9aa, 0x3fef387a6e756238, 0x3fef1e9df51fdee1,
