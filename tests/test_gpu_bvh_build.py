@@ -8,6 +8,7 @@ import pytest
 from yuki_amd import abi, scenes
 
 from test_bvh_levels import SCENES, TABLE, _one_and_seven, _signed_zero_scene, _tree
+from test_scene_layout_plan import _seam_scene
 
 pytestmark = pytest.mark.gpu
 SEED = 0x73B9642E74AC471C
@@ -61,6 +62,17 @@ def test_every_small_range_limit_on_the_device(yk, method, small_range):
             _, bi = _assert_device_built_equals_host(yk, c, sd)
             assert bi.small_range == small_range
     c.close()
+
+
+@pytest.mark.parametrize("k", [512, 513])
+@pytest.mark.parametrize("method", [abi.SPLIT_SAH, abi.SPLIT_MIDDLE])
+@pytest.mark.parametrize("max_shapes", [1, 4])
+def test_compaction_at_the_scan_block_seam(yk, dev_ctx, k, method, max_shapes):
+    """1024 and 1026 slots: one full block of the compaction's scan, then one full block and a tail of two."""
+    sd = _seam_scene(k)
+    sd.split_method, sd.max_shapes_in_node = method, max_shapes
+    got, _ = _assert_device_built_equals_host(yk, dev_ctx, sd)
+    assert got[2][0] == {(512, 1): 1023, (513, 1): 1025, (512, 4): 255, (513, 4): 257}[(k, max_shapes)]
 
 
 def test_cornell_with_its_sphere(yk, dev_ctx):

@@ -11,7 +11,7 @@ import pytest
 from yuki_amd import abi, scenes
 
 from test_bvh_levels import _one_and_seven, _signed_zero_scene, _tree
-from test_scene_layout_plan import _first_triangles
+from test_scene_layout_plan import _first_triangles, _seam_scene
 
 pytestmark = pytest.mark.gpu
 SEED = 0x73B9642E74AC471C
@@ -113,6 +113,21 @@ def test_split_methods_and_leaf_sizes(yk, contexts, method, builder, max_shapes)
         sd = make()
         sd.split_method, sd.max_shapes_in_node = method, max_shapes
         _assert_device_layout_equals_host(yk, contexts, sd, builder)
+
+
+@pytest.mark.parametrize("k", [512, 513])
+@pytest.mark.parametrize("method", [abi.SPLIT_SAH, abi.SPLIT_MIDDLE])
+@pytest.mark.parametrize("max_shapes", [1, 4])
+def test_scans_at_the_block_seam(yk, contexts, k, method, max_shapes):
+    """1023 and 1025 nodes (255 and 257 at four shapes per leaf): the layout's two scans on either side of one block of 1024."""
+    sd = _seam_scene(k)
+    sd.split_method, sd.max_shapes_in_node = method, max_shapes
+    for builder in (0, 1):
+        for wide in (0, 2):
+            want, head, who = _assert_device_layout_equals_host(yk, contexts, sd, builder, wide_bvh=wide)
+            assert who[2:] == (builder, 0)
+            assert len(want["nodes"]) // 64 == {(512, 1): 511, (513, 1): 512, (512, 4): 127, (513, 4): 128}[(k, max_shapes)]
+            assert head[3] == (1 if wide else 0) and (len(want["nodes4"]) > 0) == bool(wide)
 
 
 def test_equal_counts_with_the_device_builder_asked_for(yk, contexts):

@@ -96,6 +96,23 @@ def _first_triangles(k, xs):
                             meshes=[(False, False, False)], materials=base.materials[:1], lights=base.lights, camera=base.camera)
 
 
+def _seam_scene(k):
+    """k triangles in a row: 2k - 1 nodes at one shape per leaf, 2k builder slots — k = 512 and 513 put the 1024-wide
+    blocks of the device scan (yuki_amd/csrc/yk_scan.h) on either side of their seam."""
+    return _first_triangles(k, 1.5 * np.arange(k))
+
+
+@pytest.mark.parametrize("k", [512, 513])
+@pytest.mark.parametrize("method", METHODS)
+@pytest.mark.parametrize("max_shapes", [1, 4])
+def test_order_rules_at_the_scan_block_seam(yk, k, method, max_shapes):
+    sd = _seam_scene(k)
+    sd.split_method, sd.max_shapes_in_node = method, max_shapes
+    nodes = _check(yk, sd)
+    if method != abi.SPLIT_EQUAL_COUNTS:  # 1023 / 1025 nodes, and 255 / 257
+        assert len(nodes) == {(512, 1): 1023, (513, 1): 1025, (512, 4): 255, (513, 4): 257}[(k, max_shapes)]
+
+
 @pytest.mark.parametrize("method", METHODS)
 def test_order_rules_on_degenerate_trees(yk, method):
     one, _ = _one_and_seven()

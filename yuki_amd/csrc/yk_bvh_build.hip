@@ -10,13 +10,14 @@
 
 #include "yk_bvh_build.h"
 #include "yk_internal.h"
+#include "yk_scan.h"
 
 using namespace yk::lv;
+using namespace yk::scan;
 
 namespace {
 
-const int kLevelThreads = 512;   // one block per open range
-const int kScanThreads = 1024;   // slots per block of the compaction's scan
+const int kLevelThreads = 512;  // one block per open range
 
 // ------------------------------------------------------------------ the two executors of level_range
 struct HostExec {
@@ -144,58 +145,20 @@ __global__ void __launch_bounds__(64) k_small(Prims p, Params prm, const Range* 
     if (st.split_failed) ctr->split_failed = 1u;
 }
 
-// exclusive scan of v over the block; wt: 16 words of LDS
-__device__ uint32_t block_excl_scan(uint32_t v, uint32_t& total, uint32_t* wt) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(inc, off);
-        if (lane >= (uint32_t)off) inc += o;
-    }
-    if (lane == 63u) wt[wave] = inc;
-    __syncthreads();
-    uint32_t before = inc - v, all = 0u;
-    for (uint32_t w = 0; w < nw; ++w) {
-        const uint32_t t = wt[w];
-        if (w < wave) before += t;
-        all += t;
-    }
-    __syncthreads();
-    total = all;
-    return before;
-}
-// used slots -> their rank inside the block (index) and the block's count (bsum)
-__global__ void __launch_bounds__(kScanThreads) k_scan_block(const uint32_t* __restrict__ slot_depth, uint32_t n_slots, uint32_t* index, uint32_t* bsum) {
-    __shared__ uint32_t wt[16];
-    const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t total;
-    const uint32_t r = block_excl_scan(s < n_slots && slot_depth[s] != 0u ? 1u : 0u, total, wt);
-    if (s < n_slots) index[s] = r;
-    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
-}
-// one block: bsum -> its exclusive scan; total[0] = number of nodes
-__global__ void __launch_bounds__(kScanThreads) k_scan_sums(uint32_t* bsum, uint32_t nb, uint32_t* total_out) {
-    __shared__ uint32_t wt[16];
-    uint32_t run = 0u;
-    for (uint32_t base = 0; base < nb; base += blockDim.x) {
-        const uint32_t i = base + threadIdx.x;
-        uint32_t total;
-        const uint32_t r = block_excl_scan(i < nb ? bsum[i] : 0u, total, wt);
-        if (i < nb) bsum[i] = run + r;
-        run += total;
-    }
-    if (threadIdx.x == 0) *total_out = run;
-}
+// the compaction's scan (yk_scan.h) counts the used slots
+struct SlotUsed {
+    const uint32_t* __restrict__ slot_depth;
+    __device__ uint32_t operator()(uint32_t s) const { return slot_depth[s] != 0u ? 1u : 0u; }
+};
 // slots -> the depth-first node array: second-child slots become node indices
 __global__ void k_compact(const uint32_t* __restrict__ slots, const uint32_t* __restrict__ slot_depth, uint32_t n_slots, const uint32_t* __restrict__ index, const uint32_t* __restrict__ bsum, uint32_t* nodes,
                           uint32_t* depth) {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n_slots || slot_depth[s] == 0u) return;
-    const uint32_t i = index[s] + bsum[s / kScanThreads];
+    const uint32_t i = scan_rank(index, bsum, s);
     const uint4* src = reinterpret_cast<const uint4*>(slots + 8 * (size_t)s);
     uint4 a = src[0], b = src[1];
-    if ((b.w >> 24) == 0u) b.z = index[b.z] + bsum[b.z / kScanThreads];
+    if ((b.w >> 24) == 0u) b.z = scan_rank(index, bsum, b.z);
     uint4* dst = reinterpret_cast<uint4*>(nodes + 8 * (size_t)i);
     dst[0] = a;
     dst[1] = b;
@@ -206,29 +169,6 @@ __global__ void k_interior_bounds(uint32_t* nodes, const uint32_t* __restrict__ 
     if (i >= n_nodes || depth[i] != d || (nodes[8 * (size_t)i + 7] >> 24) != 0u) return;
     interior_bounds(nodes, i);
 }
-
-struct DevBufs {  // freed on every way out
-    std::vector<void*> all;
-    ~DevBufs() {
-        for (void* p : all) (void)hipFree(p);
-    }
-    template <class T> bool get(T*& out, size_t count) {
-        void* p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(count * sizeof(T), 16)) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        all.push_back(p);
-        out = reinterpret_cast<T*>(p);
-        return true;
-    }
-    template <class T> void give(T* p, size_t count, DevBuf& to) {  // hands one buffer on to a new owner
-        all.erase(std::find(all.begin(), all.end(), (void*)p));
-        to.release();
-        to.p = p;
-        to.bytes = std::max<size_t>(count * sizeof(T), 16);
-    }
-};
 
 bool refuse(yk_bvh_build_info& bi, uint32_t reason) {
     bi.reason = reason;
@@ -251,13 +191,12 @@ bool build_bvh_device(yk_context* ctx, const std::vector<ShapeBounds>& sb, uint3
     const uint32_t N = (uint32_t)sb.size(), n_slots = 2u * N;
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
-    DevBufs mem;
+    DevScratch mem;
     float *d_sb = nullptr, *d_soa = nullptr;
     uint32_t *d_shape = nullptr, *d_list = nullptr, *d_slots = nullptr, *d_slot_depth = nullptr, *d_index = nullptr, *d_bsum = nullptr, *d_nodes = nullptr, *d_depth = nullptr, *d_words = nullptr;
     Range *d_q[2] = {nullptr, nullptr}, *d_small = nullptr;
-    const uint32_t n_scan_blocks = (n_slots + kScanThreads - 1) / kScanThreads;
     if (!mem.get(d_sb, 6 * (size_t)N) || !mem.get(d_soa, 9 * (size_t)N) || !mem.get(d_shape, N) || !mem.get(d_list, N) || !mem.get(d_slots, 8 * (size_t)n_slots) || !mem.get(d_slot_depth, n_slots) ||
-        !mem.get(d_index, n_slots) || !mem.get(d_bsum, n_scan_blocks) || !mem.get(d_nodes, 8 * (size_t)n_slots) || !mem.get(d_depth, n_slots) || !mem.get(d_words, 16) || !mem.get(d_q[0], N) || !mem.get(d_q[1], N) ||
+        !mem.get(d_index, n_slots) || !mem.get(d_bsum, scan_blocks(n_slots)) || !mem.get(d_nodes, 8 * (size_t)n_slots) || !mem.get(d_depth, n_slots) || !mem.get(d_words, 16) || !mem.get(d_q[0], N) || !mem.get(d_q[1], N) ||
         !mem.get(d_small, N))
         return refuse(bi, YK_BVH_REASON_OUT_OF_MEMORY);
     Counters* d_ctr = reinterpret_cast<Counters*>(d_words);  // 8 words; word 8: non-finite flag; word 9: node count
@@ -332,8 +271,7 @@ bool build_bvh_device(yk_context* ctx, const std::vector<ShapeBounds>& sb, uint3
 
     // ---- depth-first layout: compaction of the used slots, then the interior boxes bottom-up
     t0 = now_seconds();
-    k_scan_block<<<n_scan_blocks, kScanThreads, 0, st>>>(d_slot_depth, n_slots, d_index, d_bsum);
-    k_scan_sums<<<1, kScanThreads, 0, st>>>(d_bsum, n_scan_blocks, d_words + 9);
+    enqueue_scan(st, SlotUsed{d_slot_depth}, n_slots, d_index, d_bsum, d_words + 9, false);  // k_compact folds the block sums in itself
     k_compact<<<(n_slots + 255) / 256, 256, 0, st>>>(d_slots, d_slot_depth, n_slots, d_index, d_bsum, d_nodes, d_depth);
     DEV_TRY(hipGetLastError());
     DEV_TRY(hipMemcpyAsync(words, d_words, sizeof(words), hipMemcpyDeviceToHost, st));

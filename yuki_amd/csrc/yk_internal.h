@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <memory>
@@ -36,6 +37,30 @@ struct DevBuf {
         bytes = 0;
     }
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
+};
+
+// A function's device temporaries: freed on every way out, unless handed on.
+struct DevScratch {
+    std::vector<void*> all;
+    ~DevScratch() {
+        for (void* p : all) (void)hipFree(p);
+    }
+    template <class T> bool get(T*& out, size_t count) {
+        void* p = nullptr;
+        if (hipMalloc(&p, std::max<size_t>(count * sizeof(T), 16)) != hipSuccess) {
+            (void)hipGetLastError();
+            return false;
+        }
+        all.push_back(p);
+        out = reinterpret_cast<T*>(p);
+        return true;
+    }
+    template <class T> void give(T* p, size_t count, DevBuf& to) {  // hands one buffer on to a new owner
+        all.erase(std::find(all.begin(), all.end(), (void*)p));
+        to.release();
+        to.p = p;
+        to.bytes = std::max<size_t>(count * sizeof(T), 16);
+    }
 };
 
 #define YK_BVH_SMALL_RANGE 32  // default of "bvh_small_range" (profiles/bvh_build_device.json: the sweep that chose it)
@@ -210,6 +235,9 @@ bool build_bvh_levels(const std::vector<ShapeBounds>& bounds, uint32_t max_shape
 uint32_t layout_scene_device(yk_context* ctx, yk_scene* s, const DeviceTree& tree, const uint32_t* d_user_order, const uint8_t* d_mat_kind, bool has_attr, uint32_t tree_depth, bool* order_applied);
 
 // ------------------------------------------------------------------ yk_scene.cpp
+// The exact sizes of a scene's seven record buffers (s->record_bytes) and the head of s->layout from what was laid out,
+// for whoever laid it out.  n_wide: DevNode4 records; 0 says there is no 4-wide layout.
+void set_record_layout(yk_scene* s, size_t n_interior, size_t n_wide, size_t n_top, size_t n_top_any, size_t n_shapes, bool has_attr, uint32_t root_ref, bool wide_auto);
 Material make_material(const yk_material_desc& m);  // per-hit constants folded (GGX alpha, Oren-Nayar A / B)
 DevLight make_light(const yk_light_desc& l);
 

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -12,6 +13,7 @@
 #include <vector>
 
 #include "yk_internal.h"
+#include "yk_scene_layout.h"
 
 template <class T> static yk_status upload(yk_context* ctx, DevBuf& buf, const T* src, size_t count) {
     size_t bytes = std::max<size_t>(count * sizeof(T), 16);
@@ -84,6 +86,29 @@ DevLight make_light(const yk_light_desc& l) {
     return d;
 }
 
+// Every device buffer a scene owns.  The first seven are its record buffers, in the order of YK_RECORDS_*.
+static std::array<DevBuf*, 22> scene_buffers(yk_scene* s) {
+    return {&s->nodes,    &s->nodes4,       &s->top_nodes,      &s->top_nodes_any, &s->tris,      &s->prim_shade, &s->prim_attr, &s->indices, &s->points,  &s->normals,    &s->uvs,
+            &s->tri_mesh, &s->tri_material, &s->tri_area_light, &s->mesh_flags,    &s->materials, &s->lights,     &s->spheres,   &s->texels,  &s->tex_info, &s->tree_nodes, &s->tree_order};
+}
+static const DevBuf& record_buffer(const yk_scene* s, uint32_t which) { return *scene_buffers(const_cast<yk_scene*>(s))[which]; }
+
+void set_record_layout(yk_scene* s, size_t n_interior, size_t n_wide, size_t n_top, size_t n_top_any, size_t n_shapes, bool has_attr, uint32_t root_ref, bool wide_auto) {
+    yk_scene_layout_info& li = s->layout;
+    li.root_ref = root_ref;
+    li.n_top = (uint32_t)n_top;
+    li.n_top_any = (uint32_t)n_top_any;
+    li.wide = n_wide ? 1u : 0u;
+    li.wide_auto = wide_auto ? 1u : 0u;
+    s->record_bytes[YK_RECORDS_NODES] = std::max<size_t>(n_interior, 1) * sizeof(DevNode);
+    s->record_bytes[YK_RECORDS_NODES4] = n_wide * sizeof(DevNode4);
+    s->record_bytes[YK_RECORDS_TOP] = n_top * sizeof(DevNode);
+    s->record_bytes[YK_RECORDS_TOP_ANY] = n_top_any * sizeof(DevNode);
+    s->record_bytes[YK_RECORDS_TRIS] = 3 * n_shapes * sizeof(float4);
+    s->record_bytes[YK_RECORDS_PRIM_SHADE] = n_shapes * sizeof(uint4);
+    s->record_bytes[YK_RECORDS_PRIM_ATTR] = has_attr ? 4 * n_shapes * sizeof(float4) : 0;
+}
+
 // Everything yk_scene_create derives from a scene description on the host (yk_internal.h).
 struct SceneImage {
     std::shared_ptr<const HostBvh> bvh;
@@ -99,7 +124,7 @@ struct SceneImage {
     uint32_t n_triangles = 0, n_spheres = 0, n_lights = 0, n_delta_lights = 0;
     yk_scene_info info;  // host part: node counts, bounds, build time
     yk_bvh_build_info build_info;
-    bool has_device_records = false, wide = false, wide_auto = false;
+    bool has_device_records = false, wide_auto = false;  // wide_auto, root_ref: of the host layout
     uint32_t root_ref = 0;
     std::vector<DevNode> dn, top, top_any;
     std::vector<DevNode4> dn4;
@@ -115,11 +140,8 @@ struct SceneImage {
 
 static void layout_records_host(const yk_context* ctx, SceneImage* s);
 
-// Host half of yk_scene_create: validation, BoundingVolumeHierarchy::new (bvh.rs:39-115) and — when `ctx` is given (its
-// "top_nodes" / "wide_bvh" options apply) — the device records laid out from the tree.
-yk_status yk_build_scene_image(yk_context* ctx, const yk_scene_desc* d, std::shared_ptr<SceneImage>& out, bool device_builder_allowed) try {
-    if (!d) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null scene description");
-    out.reset();
+// ---- the steps of yk_build_scene_image, in its order
+static yk_status check_description(yk_context* ctx, const yk_scene_desc* d) {
     if ((uint64_t)d->n_triangles + d->n_spheres == 0) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "empty scene");
     if (d->n_triangles && (!d->points || !d->indices)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "missing geometry arrays");
     if (d->max_shapes_in_node == 0 || d->max_shapes_in_node > 65535u || d->split_method > 2) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "bad BVH settings");
@@ -154,24 +176,13 @@ yk_status yk_build_scene_image(yk_context* ctx, const yk_scene_desc* d, std::sha
         if (d->meshes[m].has_normals && !d->normals) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "mesh has_normals without a normals array");
         if (d->meshes[m].has_uvs && !d->uvs) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "mesh has_uvs without a uvs array");
     }
+    return YK_OK;
+}
 
-    std::shared_ptr<SceneImage> img = std::make_shared<SceneImage>();
-    SceneImage* s = img.get();
-    std::shared_ptr<HostBvh> bvh = std::make_shared<HostBvh>();
-    s->bvh = bvh;
-    s->bvh_mut = bvh;
-    s->d = d;
-    s->device_layout = ctx && ctx->scene_layout == 1 && device_builder_allowed;
-    s->layout_reason = ctx && ctx->scene_layout == 1 && !device_builder_allowed ? (uint32_t)YK_LAYOUT_REASON_MULTI : 0u;
-    s->n_triangles = d->n_triangles;
-    s->n_spheres = d->n_spheres;
-    s->n_lights = d->n_lights;
-    for (uint32_t l = 0; l < d->n_lights; ++l) s->n_delta_lights += d->lights[l].kind != YK_LIGHT_RECT ? 1u : 0u;
-    std::memset(&s->info, 0, sizeof(s->info));
-
-    // world bounds of every shape: Triangle::world_bound (triangle.rs:229-235),
-    // Sphere::world_bound (sphere.rs:121-123)
-    std::vector<ShapeBounds> sb((size_t)d->n_triangles + d->n_spheres);
+// world bounds of every shape — Triangle::world_bound (triangle.rs:229-235), Sphere::world_bound (sphere.rs:121-123) —
+// in the caller's shape order when there is one
+static yk_status shape_bounds(yk_context* ctx, const yk_scene_desc* d, std::vector<ShapeBounds>& sb) {
+    sb.assign((size_t)d->n_triangles + d->n_spheres, ShapeBounds());
     for (uint32_t i = 0; i < d->n_triangles; ++i) {
         const float* p0 = d->points + 3 * (size_t)d->indices[3 * i];
         const float* p1 = d->points + 3 * (size_t)d->indices[3 * i + 1];
@@ -203,14 +214,17 @@ yk_status yk_build_scene_image(yk_context* ctx, const yk_scene_desc* d, std::sha
         std::vector<ShapeBounds> ordered(sb.size());
         for (size_t i = 0; i < sb.size(); ++i) {
             const uint32_t src = d->shape_order[i];
-            if (src >= sb.size() || seen[src]) {
-                return fail(ctx, YK_ERR_INVALID_ARGUMENT, "shape_order is not a permutation of the shapes");
-            }
+            if (src >= sb.size() || seen[src]) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "shape_order is not a permutation of the shapes");
             seen[src] = 1;
             ordered[i] = sb[src];
         }
         sb.swap(ordered);
     }
+    return YK_OK;
+}
+
+// the tree into s->bvh_mut (or, "scene_layout" = 1 and the device builder, into s->dtree), who built it and how long it took
+static yk_status build_tree(yk_context* ctx, const yk_scene_desc* d, const std::vector<ShapeBounds>& sb, bool device_builder_allowed, SceneImage* s) {
     double t0 = now_seconds();
     // Who builds the tree: the host recursion unless the context's "bvh_builder" asks for the device or the environment
     // (YK_BVH_BUILDER=levels, YK_BVH_SMALL_RANGE=n; next to YK_BVH_THREADS) for the host instance of the level algorithm.
@@ -220,96 +234,107 @@ yk_status yk_build_scene_image(yk_context* ctx, const yk_scene_desc* d, std::sha
     bool built = false;
     const char* env_builder = std::getenv("YK_BVH_BUILDER");
     if (ctx && ctx->bvh_builder == 1 && device_builder_allowed) {
-        built = build_bvh_device(ctx, sb, d->max_shapes_in_node, d->split_method, (uint32_t)ctx->bvh_small_range, *bvh, bi, s->device_layout ? &s->dtree : nullptr);
+        built = build_bvh_device(ctx, sb, d->max_shapes_in_node, d->split_method, (uint32_t)ctx->bvh_small_range, *s->bvh_mut, bi, s->device_layout ? &s->dtree : nullptr);
         s->tree_on_device = built && s->device_layout;
     } else if (env_builder && std::strcmp(env_builder, "levels") == 0) {
         const char* e = std::getenv("YK_BVH_SMALL_RANGE");
-        built = build_bvh_levels(sb, d->max_shapes_in_node, d->split_method, e ? (uint32_t)std::max(0, std::atoi(e)) : (uint32_t)YK_BVH_SMALL_RANGE, *bvh, bi);
+        built = build_bvh_levels(sb, d->max_shapes_in_node, d->split_method, e ? (uint32_t)std::max(0, std::atoi(e)) : (uint32_t)YK_BVH_SMALL_RANGE, *s->bvh_mut, bi);
     }
     if (!built) {
         bi.builder = YK_BVH_BUILDER_HOST;
-        build_bvh(sb, d->max_shapes_in_node, d->split_method, *bvh);
+        build_bvh(sb, d->max_shapes_in_node, d->split_method, *s->bvh_mut);
     }
     s->info.build_seconds = now_seconds() - t0;
     if (d->shape_order && !s->tree_on_device)  // leaf order -> position in Scene.shapes -> source shape (a tree in HBM: the layout applies it there)
-        for (uint32_t& o : bvh->shape_order) o = d->shape_order[o];
-    if (bvh->split_failed || (s->tree_on_device ? s->dtree.n_nodes == 0 : bvh->nodes.empty())) {
-        return fail(ctx, YK_ERR_BVH_BUILD, "BVH split failed (reference: assert_ne!(mid, start))");
-    }
+        for (uint32_t& o : s->bvh_mut->shape_order) o = d->shape_order[o];
+    if (s->bvh_mut->split_failed || (s->tree_on_device ? s->dtree.n_nodes == 0 : s->bvh_mut->nodes.empty())) return fail(ctx, YK_ERR_BVH_BUILD, "BVH split failed (reference: assert_ne!(mid, start))");
+    return YK_OK;
+}
+
+static void fill_scene_info(SceneImage* s) {
+    const HostBvh* bvh = s->bvh.get();
     s->info.max_leaf_shapes = bvh->max_leaf_shapes;
     s->info.tree_depth = bvh->depth;
-    if (s->tree_on_device) {  // the builder's counters and node 0; a binary tree of n nodes has (n - 1) / 2 interior ones
-        yk_bvh_node root;
-        std::memcpy(&root, s->dtree.root_words, sizeof(root));
-        s->info.n_nodes = s->dtree.n_nodes;
-        s->info.n_shapes = s->dtree.n_shapes;
-        s->info.n_interior = (s->dtree.n_nodes - 1u) / 2u;
-        for (int k = 0; k < 3; ++k) {
-            s->info.bounds_min[k] = root.bmin[k];
-            s->info.bounds_max[k] = root.bmax[k];
-        }
-    } else {
-        s->info.n_nodes = bvh->nodes.size();
-        s->info.n_shapes = bvh->shape_order.size();
-        for (int k = 0; k < 3; ++k) {
-            s->info.bounds_min[k] = bvh->nodes[0].bmin[k];
-            s->info.bounds_max[k] = bvh->nodes[0].bmax[k];
-        }
-        uint64_t n_interior = 0;
-        for (const yk_bvh_node& n : bvh->nodes) n_interior += n.is_leaf ? 0 : 1;
-        s->info.n_interior = n_interior;
+    yk_bvh_node root;  // a tree in HBM: the builder's counters and node 0; a binary tree of n nodes has (n - 1) / 2 interior ones
+    std::memcpy(&root, s->tree_on_device ? (const void*)s->dtree.root_words : (const void*)bvh->nodes.data(), sizeof(root));
+    s->info.n_nodes = s->tree_on_device ? s->dtree.n_nodes : bvh->nodes.size();
+    s->info.n_shapes = s->tree_on_device ? s->dtree.n_shapes : bvh->shape_order.size();
+    s->info.n_interior = s->tree_on_device ? (s->dtree.n_nodes - 1u) / 2u : (uint64_t)std::count_if(bvh->nodes.begin(), bvh->nodes.end(), [](const yk_bvh_node& n) { return !n.is_leaf; });
+    for (int k = 0; k < 3; ++k) {
+        s->info.bounds_min[k] = root.bmin[k];
+        s->info.bounds_max[k] = root.bmax[k];
     }
+}
 
+// the small tables of the device scene; the host layout reads mat_kind and mesh_flags
+static yk_status host_tables(yk_context* ctx, const yk_scene_desc* d, SceneImage* s) {
+    s->mats.resize(std::max<uint32_t>(d->n_materials, 1));
+    s->mat_kind.assign(s->mats.size(), 0u);
+    for (uint32_t m = 0; m < d->n_materials; ++m) {
+        s->mats[m] = make_material(d->materials[m]);
+        s->mat_kind[m] = s->mats[m].kind & 7u;
+    }
+    s->shape_kind.resize(s->info.n_shapes);
+    for (uint32_t i = 0; i < d->n_triangles; ++i) s->shape_kind[i] = (uint8_t)s->mat_kind[d->tri_material[i]];
+    for (uint32_t k = 0; k < d->n_spheres; ++k) s->shape_kind[(size_t)d->n_triangles + k] = (uint8_t)s->mat_kind[d->spheres[k].material];
+    s->mesh_flags.assign(std::max<uint32_t>(d->n_meshes, 1), 0);
+    for (uint32_t m = 0; m < d->n_meshes; ++m)
+        s->mesh_flags[m] = (d->meshes[m].has_normals ? YK_MESH_NORMALS : 0u) | (d->meshes[m].has_uvs ? YK_MESH_UVS : 0u) | (d->meshes[m].swaps_handedness ? YK_MESH_SWAPS : 0u);
+    s->spheres.resize(std::max<uint32_t>(d->n_spheres, 1));
+    for (uint32_t k = 0; k < d->n_spheres; ++k) {
+        DevSphere& o = s->spheres[k];
+        std::memcpy(o.o2w, d->spheres[k].object_to_world, 64);
+        std::memcpy(o.w2o, d->spheres[k].world_to_object, 64);
+        o.radius = d->spheres[k].radius;
+        o.material = d->spheres[k].material;
+        const float* m = o.o2w;  // Transform::swaps_handedness, transform.rs:85-91
+        float det = m[0] * (m[5] * m[10] - m[6] * m[9]) - m[1] * (m[4] * m[10] - m[6] * m[8]) + m[2] * (m[4] * m[9] - m[5] * m[8]);
+        o.swaps_handedness = det < 0.0f ? 1u : 0u;
+        o.pad = 0;
+    }
+    s->lights.resize(std::max<uint32_t>(d->n_lights, 1));
+    for (uint32_t l = 0; l < d->n_lights; ++l) s->lights[l] = make_light(d->lights[l]);
+    s->tri_mesh.assign(d->n_triangles, 0);
+    if (d->tri_mesh) std::memcpy(s->tri_mesh.data(), d->tri_mesh, sizeof(uint32_t) * d->n_triangles);
+    s->tri_al.assign(d->n_triangles, -1);
+    if (d->tri_area_light) std::memcpy(s->tri_al.data(), d->tri_area_light, sizeof(int32_t) * d->n_triangles);
+    for (uint32_t t = 0; t < d->n_textures; ++t) {
+        const yk_texture_desc& td = d->textures[t];
+        s->tex_info.push_back(make_uint4((unsigned)s->texels.size(), td.width, td.height, 0u));
+        const size_t n = (size_t)td.width * td.height;
+        if (s->texels.size() + n > 0xffffffffull) return fail(ctx, YK_ERR_UNSUPPORTED, "more than 2^32 texels");
+        for (size_t k = 0; k < n; ++k) s->texels.push_back(make_float4(td.rgb[3 * k], td.rgb[3 * k + 1], td.rgb[3 * k + 2], 0.0f));
+    }
+    return YK_OK;
+}
+
+// Host half of yk_scene_create: validation, BoundingVolumeHierarchy::new (bvh.rs:39-115) and — when `ctx` is given (its
+// "top_nodes" / "wide_bvh" options apply) — the device records laid out from the tree.
+yk_status yk_build_scene_image(yk_context* ctx, const yk_scene_desc* d, std::shared_ptr<SceneImage>& out, bool device_builder_allowed) try {
+    if (!d) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null scene description");
+    out.reset();
+    yk_status st = check_description(ctx, d);
+    if (st != YK_OK) return st;
+
+    std::shared_ptr<SceneImage> img = std::make_shared<SceneImage>();
+    SceneImage* s = img.get();
+    s->bvh = s->bvh_mut = std::make_shared<HostBvh>();
+    s->d = d;
+    s->device_layout = ctx && ctx->scene_layout == 1 && device_builder_allowed;
+    s->layout_reason = ctx && ctx->scene_layout == 1 && !device_builder_allowed ? (uint32_t)YK_LAYOUT_REASON_MULTI : 0u;
+    s->n_triangles = d->n_triangles;
+    s->n_spheres = d->n_spheres;
+    s->n_lights = d->n_lights;
+    for (uint32_t l = 0; l < d->n_lights; ++l) s->n_delta_lights += d->lights[l].kind != YK_LIGHT_RECT ? 1u : 0u;
+    std::memset(&s->info, 0, sizeof(s->info));
+
+    std::vector<ShapeBounds> sb;
+    if ((st = shape_bounds(ctx, d, sb)) != YK_OK || (st = build_tree(ctx, d, sb, device_builder_allowed, s)) != YK_OK) return st;
+    fill_scene_info(s);
     if (ctx) {  // device records (a host-only scene — ctx == NULL — stops at the tree)
-        if (s->info.n_nodes > YK_REF_INDEX_MAX || s->info.n_shapes > YK_REF_INDEX_MAX) {
-            return fail(ctx, YK_ERR_UNSUPPORTED, "more than 2^28 BVH nodes or shapes");
-        }
-        const size_t np = s->info.n_shapes;
-        std::vector<uint32_t>& mat_kind = s->mat_kind;
-        mat_kind.assign(std::max<uint32_t>(d->n_materials, 1), 0u);
-        for (uint32_t m = 0; m < d->n_materials; ++m) mat_kind[m] = make_material(d->materials[m]).kind & 7u;
-        s->shape_kind.resize(np);
-        for (uint32_t i = 0; i < d->n_triangles; ++i) s->shape_kind[i] = (uint8_t)mat_kind[d->tri_material[i]];
-        for (uint32_t k = 0; k < d->n_spheres; ++k) s->shape_kind[(size_t)d->n_triangles + k] = (uint8_t)mat_kind[d->spheres[k].material];
+        if (s->info.n_nodes > YK_REF_INDEX_MAX || s->info.n_shapes > YK_REF_INDEX_MAX) return fail(ctx, YK_ERR_UNSUPPORTED, "more than 2^28 BVH nodes or shapes");
+        if ((st = host_tables(ctx, d, s)) != YK_OK) return st;
         if (!s->device_layout) layout_records_host(ctx, s);
-        std::vector<uint32_t>& mesh_flags = s->mesh_flags;
-        mesh_flags.assign(std::max<uint32_t>(d->n_meshes, 1), 0);
-        for (uint32_t m = 0; m < d->n_meshes; ++m)
-            mesh_flags[m] = (d->meshes[m].has_normals ? YK_MESH_NORMALS : 0u) | (d->meshes[m].has_uvs ? YK_MESH_UVS : 0u) |
-                            (d->meshes[m].swaps_handedness ? YK_MESH_SWAPS : 0u);
-        std::vector<Material>& mats = s->mats;
-        mats.resize(std::max<uint32_t>(d->n_materials, 1));
-        for (uint32_t m = 0; m < d->n_materials; ++m) mats[m] = make_material(d->materials[m]);
-        std::vector<DevSphere>& spheres = s->spheres;
-        spheres.resize(std::max<uint32_t>(d->n_spheres, 1));
-        for (uint32_t k = 0; k < d->n_spheres; ++k) {
-            DevSphere& o = spheres[k];
-            std::memcpy(o.o2w, d->spheres[k].object_to_world, 64);
-            std::memcpy(o.w2o, d->spheres[k].world_to_object, 64);
-            o.radius = d->spheres[k].radius;
-            o.material = d->spheres[k].material;
-            const float* m = o.o2w;  // Transform::swaps_handedness, transform.rs:85-91
-            float det = m[0] * (m[5] * m[10] - m[6] * m[9]) - m[1] * (m[4] * m[10] - m[6] * m[8]) + m[2] * (m[4] * m[9] - m[5] * m[8]);
-            o.swaps_handedness = det < 0.0f ? 1u : 0u;
-            o.pad = 0;
-        }
-        std::vector<DevLight>& lights = s->lights;
-        lights.resize(std::max<uint32_t>(d->n_lights, 1));
-        for (uint32_t l = 0; l < d->n_lights; ++l) lights[l] = make_light(d->lights[l]);
-        std::vector<uint32_t>& tri_mesh = s->tri_mesh;
-        tri_mesh.assign(d->n_triangles, 0);
-        if (d->tri_mesh) std::memcpy(tri_mesh.data(), d->tri_mesh, sizeof(uint32_t) * d->n_triangles);
-        std::vector<int32_t>& tri_al = s->tri_al;
-        tri_al.assign(d->n_triangles, -1);
-        if (d->tri_area_light) std::memcpy(tri_al.data(), d->tri_area_light, sizeof(int32_t) * d->n_triangles);
-
-        for (uint32_t t = 0; t < d->n_textures; ++t) {
-            const yk_texture_desc& td = d->textures[t];
-            s->tex_info.push_back(make_uint4((unsigned)s->texels.size(), td.width, td.height, 0u));
-            const size_t n = (size_t)td.width * td.height;
-            if (s->texels.size() + n > 0xffffffffull) return fail(ctx, YK_ERR_UNSUPPORTED, "more than 2^32 texels");
-            for (size_t k = 0; k < n; ++k) s->texels.push_back(make_float4(td.rgb[3 * k], td.rgb[3 * k + 1], td.rgb[3 * k + 2], 0.0f));
-        }
         s->has_device_records = true;
     }
     out = img;
@@ -317,12 +342,10 @@ yk_status yk_build_scene_image(yk_context* ctx, const yk_scene_desc* d, std::sha
 } YK_CATCH(ctx)
 
 // The device records from the host tree (s->bvh with its arrays): the sequential loops the device layout
-// (yk_scene_layout.hip) is held against.
-static void layout_records_host(const yk_context* ctx, SceneImage* s) {
-    const yk_scene_desc* d = s->d;
-    const HostBvh* bvh = s->bvh.get();
-    const std::vector<yk_bvh_node>& nodes = bvh->nodes;
-    const std::vector<uint32_t>& mat_kind = s->mat_kind;
+// (yk_scene_layout.hip) is held against, in three sections.
+// DevNode per interior node, the root ref and the two tree tops
+static void layout_nodes_host(const yk_context* ctx, SceneImage* s) {
+    const std::vector<yk_bvh_node>& nodes = s->bvh->nodes;
     const uint64_t n_interior = s->info.n_interior;
     // interior index of each reference node = number of interior nodes before it
     std::vector<uint32_t> interior_index(nodes.size());
@@ -373,11 +396,19 @@ static void layout_records_host(const yk_context* ctx, SceneImage* s) {
     };
     build_top((size_t)std::min<int64_t>(ctx->top_nodes, trace_top_nodes()), s->top);
     build_top((size_t)std::min<int64_t>(ctx->top_nodes, trace_top_nodes_any()), s->top_any);
+    s->root_ref = ref_of(0);
+}
+
+static void layout_wide_host(const yk_context* ctx, SceneImage* s) {
+    const HostBvh* bvh = s->bvh.get();
+    const std::vector<yk_bvh_node>& nodes = bvh->nodes;
+    const uint64_t n_interior = s->info.n_interior;
     // 4-wide collapse (DevNode4): one node per reference interior node reached at even depth
     // below the root.  Built only while the traversal stack of the collapsed tree is
     // guaranteed to fit (the reference asserts on its own stack depth, bvh.rs:172-174).
     std::vector<DevNode4>& dn4 = s->dn4;
-    const bool wide = s->wide = ctx->wide_bvh != 0 && !nodes[0].is_leaf && bvh->depth <= 64;
+    const bool wide = ctx->wide_bvh != 0 && !nodes[0].is_leaf && bvh->depth <= 64;
+    s->wide_auto = wide && ctx->wide_bvh == 2;
     if (wide) {
         dn4.reserve(n_interior / 2 + 1);
         struct Todo {
@@ -436,13 +467,20 @@ static void layout_records_host(const yk_context* ctx, SceneImage* s) {
             o.q7 = make_uint4((uint32_t)nodes[P].axis | (axA << 2) | (axB << 4), 0u, 0u, 0u);
         }
     }
+}
+
+// tris / prim_shade / prim_attr in leaf order
+static void layout_prims_host(SceneImage* s) {
+    const yk_scene_desc* d = s->d;
+    const HostBvh* bvh = s->bvh.get();
+    const std::vector<uint32_t>& mat_kind = s->mat_kind;
     const size_t np = bvh->shape_order.size();
     std::vector<float4>& tris = s->tris;
     tris.assign(3 * np, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
     std::vector<uint4>& prim_shade = s->prim_shade;
     prim_shade.assign(np, make_uint4(0u, 0u, 0u, 0u));
     std::vector<uint8_t> last(np, 0);
-    for (const yk_bvh_node& n : nodes)
+    for (const yk_bvh_node& n : bvh->nodes)
         if (n.is_leaf) last[(size_t)n.a + n.count - 1] = 1;
     for (size_t p = 0; p < np; ++p) {
         uint32_t src = bvh->shape_order[p];
@@ -470,8 +508,7 @@ static void layout_records_host(const yk_context* ctx, SceneImage* s) {
         tris[3 * p + 0] = make_float4(p0[0], p0[1], p0[2], w0);
         tris[3 * p + 1] = make_float4(p1[0], p1[1], p1[2], w1);
         tris[3 * p + 2] = make_float4(p2[0], p2[1], p2[2], w2);
-        const yk_mesh_desc& md = d->meshes[d->tri_mesh ? d->tri_mesh[src] : 0];
-        const uint32_t mfl = (md.has_normals ? YK_MESH_NORMALS : 0u) | (md.has_uvs ? YK_MESH_UVS : 0u) | (md.swaps_handedness ? YK_MESH_SWAPS : 0u);
+        const uint32_t mfl = s->mesh_flags[s->tri_mesh[src]];
         prim_shade[p] = make_uint4(d->indices[3 * src], d->indices[3 * src + 1], d->indices[3 * src + 2],
                                    ((uint32_t)d->tri_material[src] << 6) | (mat_kind[d->tri_material[src]] << 3) | mfl);
     }
@@ -480,13 +517,13 @@ static void layout_records_host(const yk_context* ctx, SceneImage* s) {
         for (size_t p = 0; p < np; ++p) {
             const uint32_t src = bvh->shape_order[p];
             if (src >= d->n_triangles) continue;
-            const yk_mesh_desc& md = d->meshes[d->tri_mesh ? d->tri_mesh[src] : 0];
+            const uint32_t mfl = s->mesh_flags[s->tri_mesh[src]];
             float nrm[3][3] = {}, uv[3][2] = {};
             for (int k = 0; k < 3; ++k) {
                 const size_t vi = d->indices[3 * (size_t)src + k];
-                if (md.has_normals)
+                if (mfl & YK_MESH_NORMALS)
                     for (int c = 0; c < 3; ++c) nrm[k][c] = d->normals[3 * vi + c];
-                if (md.has_uvs)
+                if (mfl & YK_MESH_UVS)
                     for (int c = 0; c < 2; ++c) uv[k][c] = d->uvs[2 * vi + c];
             }
             s->prim_attr[4 * p + 0] = make_float4(nrm[0][0], nrm[0][1], nrm[0][2], uv[0][0]);
@@ -495,8 +532,12 @@ static void layout_records_host(const yk_context* ctx, SceneImage* s) {
             s->prim_attr[4 * p + 3] = make_float4(uv[1][1], uv[2][0], uv[2][1], 0.0f);
         }
     }
-    s->root_ref = ref_of(0);
-    s->wide_auto = wide && ctx->wide_bvh == 2;
+}
+
+static void layout_records_host(const yk_context* ctx, SceneImage* s) {
+    layout_nodes_host(ctx, s);
+    layout_wide_host(ctx, s);
+    layout_prims_host(s);
 }
 
 // 32-byte nodes and shape order from HBM into the host tree (no-op for buffers that are not there)
@@ -552,10 +593,7 @@ static uint32_t layout_on_device(yk_context* ctx, SceneImage* img, yk_scene* s) 
         if (d->shape_order && (r = put(d_user, d->shape_order, (size_t)tree.n_shapes * 4)) != 0) return r;
     } else {  // a host-built tree: its nodes, their depths (children follow their parent in the array) and the final order
         const HostBvh& bvh = *img->bvh;
-        std::vector<uint32_t> depth(bvh.nodes.size(), 0u);
-        depth[0] = 1u;
-        for (size_t i = 0; i < bvh.nodes.size(); ++i)
-            if (!bvh.nodes[i].is_leaf) depth[i + 1] = depth[bvh.nodes[i].a] = depth[i] + 1u;
+        const std::vector<uint32_t> depth = lay::node_depths(reinterpret_cast<const uint32_t*>(bvh.nodes.data()), bvh.nodes.size());
         tree.n_nodes = (uint32_t)bvh.nodes.size();
         tree.n_shapes = (uint32_t)bvh.shape_order.size();
         std::memcpy(tree.root_words, bvh.nodes.data(), 32);
@@ -644,18 +682,7 @@ yk_status yk_upload_scene_image(yk_context* ctx, const std::shared_ptr<SceneImag
             UP(tris, img->tris.data(), img->tris.size());
             UP(prim_shade, img->prim_shade.data(), img->prim_shade.size());
             UP(prim_attr, img->prim_attr.data(), img->prim_attr.size());
-            li.root_ref = img->root_ref;
-            li.n_top = (uint32_t)img->top.size();
-            li.n_top_any = (uint32_t)img->top_any.size();
-            li.wide = img->wide ? 1u : 0u;
-            li.wide_auto = img->wide_auto ? 1u : 0u;
-            s->record_bytes[YK_RECORDS_NODES] = img->dn.size() * sizeof(DevNode);
-            s->record_bytes[YK_RECORDS_NODES4] = img->dn4.size() * sizeof(DevNode4);
-            s->record_bytes[YK_RECORDS_TOP] = img->top.size() * sizeof(DevNode);
-            s->record_bytes[YK_RECORDS_TOP_ANY] = img->top_any.size() * sizeof(DevNode);
-            s->record_bytes[YK_RECORDS_TRIS] = img->tris.size() * sizeof(float4);
-            s->record_bytes[YK_RECORDS_PRIM_SHADE] = img->prim_shade.size() * sizeof(uint4);
-            s->record_bytes[YK_RECORDS_PRIM_ATTR] = img->prim_attr.size() * sizeof(float4);
+            set_record_layout(s, s->info.n_interior, img->dn4.size(), img->top.size(), img->top_any.size(), s->info.n_shapes, d->normals || d->uvs, img->root_ref, img->wide_auto);
         }
 #undef UP
         DevScene& ds = s->dev;
@@ -692,9 +719,7 @@ yk_status yk_upload_scene_image(yk_context* ctx, const std::shared_ptr<SceneImag
         ds.tex_info = d->n_textures ? s->tex_info.as<uint4>() : nullptr;
         s->on_device = true;
         s->info.upload_seconds = now_seconds() - u0;
-        DevBuf* all[] = {&s->nodes, &s->nodes4, &s->top_nodes, &s->top_nodes_any, &s->tris, &s->prim_shade, &s->prim_attr, &s->indices, &s->points, &s->normals, &s->uvs, &s->tri_mesh, &s->tri_material, &s->tri_area_light,
-                         &s->mesh_flags, &s->materials, &s->lights, &s->spheres, &s->texels, &s->tex_info, &s->tree_nodes, &s->tree_order};
-        for (DevBuf* b : all) s->info.device_bytes += b->bytes;
+        for (DevBuf* b : scene_buffers(s)) s->info.device_bytes += b->bytes;
     }
     guard.s = nullptr;
     *out = s;
@@ -714,13 +739,10 @@ yk_status yk_scene_create(yk_context* ctx, const yk_scene_desc* d, yk_scene** ou
     return yk_upload_scene_image(ctx, img, out);
 }
 
-
 void yk_scene_destroy(yk_scene* s) {
     if (!s) return;
     if (s->device >= 0) (void)hipSetDevice(s->device);
-    DevBuf* all[] = {&s->nodes, &s->nodes4, &s->top_nodes, &s->top_nodes_any, &s->tris, &s->prim_shade, &s->prim_attr, &s->indices, &s->points, &s->normals, &s->uvs, &s->tri_mesh, &s->tri_material, &s->tri_area_light,
-                     &s->mesh_flags, &s->materials, &s->lights, &s->spheres, &s->texels, &s->tex_info, &s->tree_nodes, &s->tree_order};
-    for (DevBuf* b : all) b->release();
+    for (DevBuf* b : scene_buffers(s)) b->release();
     delete s;
 }
 
@@ -754,13 +776,13 @@ yk_status yk_scene_get_layout_info(const yk_scene* s, yk_scene_layout_info* out)
 
 yk_status yk_scene_read_records(const yk_scene* s, uint32_t which, void* out, size_t cap_bytes, size_t* n_bytes) {
     if (!s || !s->on_device || which > YK_RECORDS_PRIM_ATTR || !n_bytes) return YK_ERR_INVALID_ARGUMENT;
-    const DevBuf* bufs[] = {&s->nodes, &s->nodes4, &s->top_nodes, &s->top_nodes_any, &s->tris, &s->prim_shade, &s->prim_attr};
+    const DevBuf& buf = record_buffer(s, which);
     const size_t bytes = s->record_bytes[which];
     *n_bytes = bytes;
     if (!out) return YK_OK;
-    if (cap_bytes < bytes || bufs[which]->bytes < bytes) return YK_ERR_INVALID_ARGUMENT;
+    if (cap_bytes < bytes || buf.bytes < bytes) return YK_ERR_INVALID_ARGUMENT;
     (void)hipSetDevice(s->device);
-    if (bytes && hipMemcpy(out, bufs[which]->p, bytes, hipMemcpyDeviceToHost) != hipSuccess) {
+    if (bytes && hipMemcpy(out, buf.p, bytes, hipMemcpyDeviceToHost) != hipSuccess) {
         (void)hipGetLastError();
         return YK_ERR_DEVICE;
     }

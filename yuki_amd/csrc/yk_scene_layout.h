@@ -24,6 +24,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "yk_bvh_build.h"
 #include "yk_device.h"
 
@@ -36,6 +38,15 @@ YK_HD bool nd_leaf(const uint32_t* nodes, uint32_t i) { return (nodes[8 * (size_
 YK_HD uint32_t nd_a(const uint32_t* nodes, uint32_t i) { return nodes[8 * (size_t)i + 6]; }
 YK_HD uint32_t nd_count(const uint32_t* nodes, uint32_t i) { return nodes[8 * (size_t)i + 7] & 0xffffu; }
 YK_HD uint32_t nd_axis(const uint32_t* nodes, uint32_t i) { return (nodes[8 * (size_t)i + 7] >> 16) & 0xffu; }
+
+// host: every node's depth (the root's is 1) from the pre-order array, where both children follow their parent
+inline std::vector<uint32_t> node_depths(const uint32_t* nodes, size_t n) {
+    std::vector<uint32_t> depth(n, 0u);
+    depth[0] = 1u;
+    for (uint32_t i = 0; i < (uint32_t)n; ++i)
+        if (!nd_leaf(nodes, i)) depth[i + 1u] = depth[nd_a(nodes, i)] = depth[i] + 1u;
+    return depth;
+}
 
 // leaf: the leaf bit and its first slot of the leaf order; interior: its interior index
 YK_HD uint32_t ref_of(const uint32_t* nodes, const uint32_t* interior_index, uint32_t i) { return nd_leaf(nodes, i) ? (YK_LEAF_BIT | nd_a(nodes, i)) : interior_index[i]; }

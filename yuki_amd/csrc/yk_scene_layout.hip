@@ -10,13 +10,14 @@
 #include <vector>
 
 #include "yk_internal.h"
+#include "yk_scan.h"
 #include "yk_scene_layout.h"
 
 using namespace yk::lay;
+using namespace yk::scan;
 
 namespace {
 
-const int kScanThreads = 1024;  // nodes per block of a scan
 const int kThreads = 256;
 
 struct HostExec {
@@ -31,67 +32,21 @@ struct WaveExec {  // one wave of 64 lanes
     uint32_t tid, nt;
     __device__ void sync() { __syncthreads(); }
     __device__ uint32_t scan(uint32_t v, uint32_t& total) {
-        uint32_t inc = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = __shfl_up(inc, off);
-            if (tid >= (uint32_t)off) inc += o;
-        }
+        const uint32_t inc = wave_incl_scan(v, tid);
         total = __shfl(inc, 63);
         return inc - v;
     }
 };
 
-// ------------------------------------------------------------------ scans over the node array
-// The shape of the builder's compaction (k_scan_block / k_scan_sums, yk_bvh_build.hip): ranks inside blocks of
-// 1024, one block scans the block sums, a third pass makes the ranks absolute.
-__device__ uint32_t block_excl_scan(uint32_t v, uint32_t& total, uint32_t* wt) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t o = __shfl_up(inc, off);
-        if (lane >= (uint32_t)off) inc += o;
-    }
-    if (lane == 63u) wt[wave] = inc;
-    __syncthreads();
-    uint32_t before = inc - v, all = 0u;
-    for (uint32_t w = 0; w < nw; ++w) {
-        const uint32_t t = wt[w];
-        if (w < wave) before += t;
-        all += t;
-    }
-    __syncthreads();
-    total = all;
-    return before;
-}
-// WIDE false: !is_leaf (-> interior index); true: w(i) (-> E, yk_scene_layout.h)
-template <bool WIDE> __global__ void __launch_bounds__(kScanThreads) k_scan_block(const uint32_t* __restrict__ nodes, const uint32_t* __restrict__ depth, uint32_t n, uint32_t* index, uint32_t* bsum) {
-    __shared__ uint32_t wt[16];
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    uint32_t v = 0u;
-    if (i < n) v = WIDE ? wide_count(nodes, depth, i) : (nd_leaf(nodes, i) ? 0u : 1u);
-    uint32_t total;
-    const uint32_t r = block_excl_scan(v, total, wt);
-    if (i < n) index[i] = r;
-    if (threadIdx.x == 0) bsum[blockIdx.x] = total;
-}
-__global__ void __launch_bounds__(kScanThreads) k_scan_sums(uint32_t* bsum, uint32_t nb, uint32_t* total_out) {
-    __shared__ uint32_t wt[16];
-    uint32_t run = 0u;
-    for (uint32_t base = 0; base < nb; base += blockDim.x) {
-        const uint32_t i = base + threadIdx.x;
-        uint32_t total;
-        const uint32_t r = block_excl_scan(i < nb ? bsum[i] : 0u, total, wt);
-        if (i < nb) bsum[i] = run + r;
-        run += total;
-    }
-    if (threadIdx.x == 0) *total_out = run;
-}
-__global__ void k_scan_add(uint32_t* index, const uint32_t* __restrict__ bsum, uint32_t n) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) index[i] += bsum[i / kScanThreads];
-}
+// ------------------------------------------------------------------ what the two scans over the node array (yk_scan.h) add up
+struct IsInterior {  // -> interior index
+    const uint32_t* __restrict__ nodes;
+    __device__ uint32_t operator()(uint32_t i) const { return nd_leaf(nodes, i) ? 0u : 1u; }
+};
+struct WideCount {  // w(i) -> E (yk_scene_layout.h)
+    const uint32_t *__restrict__ nodes, *__restrict__ depth;
+    __device__ uint32_t operator()(uint32_t i) const { return wide_count(nodes, depth, i); }
+};
 
 // ------------------------------------------------------------------ records
 // leaf order -> position in the caller's shape order -> source shape (in place: every lane owns its word)
@@ -173,23 +128,6 @@ __global__ void k_prims(PrimArrays s, const uint32_t* __restrict__ order, const 
     }
 }
 
-struct Temp {  // freed on every way out
-    std::vector<void*> all;
-    ~Temp() {
-        for (void* p : all) (void)hipFree(p);
-    }
-    template <class T> bool get(T*& out, size_t count) {
-        void* p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(count * sizeof(T), 16)) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        all.push_back(p);
-        out = reinterpret_cast<T*>(p);
-        return true;
-    }
-};
-
 unsigned blocks(size_t n, int threads) { return (unsigned)((n + threads - 1) / threads); }
 
 }  // namespace
@@ -208,12 +146,11 @@ uint32_t layout_scene_device(yk_context* ctx, yk_scene* s, const DeviceTree& tre
     const uint32_t cap_closest = (uint32_t)std::min<int64_t>(std::min<int64_t>(ctx->top_nodes, trace_top_nodes()), YK_TOP_MAX);
     const uint32_t cap_any = (uint32_t)std::min<int64_t>(std::min<int64_t>(ctx->top_nodes, trace_top_nodes_any()), YK_TOP_MAX);
     const bool wide = ctx->wide_bvh != 0 && !root_leaf && tree_depth <= 64;
-    const uint32_t nb = (n + kScanThreads - 1) / kScanThreads;
 
-    Temp tmp;
+    DevScratch tmp;
     uint32_t *d_index = nullptr, *d_bsum = nullptr, *d_slot = nullptr, *d_words = nullptr;
     uint8_t* d_last = nullptr;
-    if (!tmp.get(d_index, n) || !tmp.get(d_bsum, nb) || !tmp.get(d_last, np) || !tmp.get(d_words, 16) || (wide && !tmp.get(d_slot, n))) return YK_LAYOUT_REASON_OUT_OF_MEMORY;
+    if (!tmp.get(d_index, n) || !tmp.get(d_bsum, scan_blocks(n)) || !tmp.get(d_last, np) || !tmp.get(d_words, 16) || (wide && !tmp.get(d_slot, n))) return YK_LAYOUT_REASON_OUT_OF_MEMORY;
 #define LAY_TRY(expr)                                                                                   \
     do {                                                                                                \
         const hipError_t e_ = (expr);                                                                   \
@@ -237,10 +174,8 @@ uint32_t layout_scene_device(yk_context* ctx, yk_scene* s, const DeviceTree& tre
         LAY_TRY(hipGetLastError());
         *order_applied = true;
     }
-    // interior index, DevNode, last-in-leaf marks
-    k_scan_block<false><<<nb, kScanThreads, 0, st>>>(nodes, depth, n, d_index, d_bsum);
-    k_scan_sums<<<1, kScanThreads, 0, st>>>(d_bsum, nb, d_words + 0);
-    k_scan_add<<<blocks(n, kThreads), kThreads, 0, st>>>(d_index, d_bsum, n);
+    // interior index (absolute: ref_of reads it as the host does), DevNode, last-in-leaf marks
+    enqueue_scan(st, IsInterior{nodes}, n, d_index, d_bsum, d_words + 0, true);
     if (n_interior == 0) LAY_TRY(hipMemsetAsync(s->nodes.p, 0, sizeof(DevNode), st));  // a single leaf: one default node
     k_nodes<<<blocks(n, kThreads), kThreads, 0, st>>>(nodes, d_index, n, s->nodes.as<uint4>(), d_last);
     // tree tops (they read the interior index, which the wide scan below overwrites)
@@ -264,9 +199,7 @@ uint32_t layout_scene_device(yk_context* ctx, yk_scene* s, const DeviceTree& tre
     // 4-wide collapse: E over the array, the slots, the records
     uint32_t words[16];
     if (wide) {
-        k_scan_block<true><<<nb, kScanThreads, 0, st>>>(nodes, depth, n, d_index, d_bsum);
-        k_scan_sums<<<1, kScanThreads, 0, st>>>(d_bsum, nb, d_words + 1);
-        k_scan_add<<<blocks(n, kThreads), kThreads, 0, st>>>(d_index, d_bsum, n);
+        enqueue_scan(st, WideCount{nodes, depth}, n, d_index, d_bsum, d_words + 1, true);
         k_wide_slots<<<blocks(n, kThreads), kThreads, 0, st>>>(nodes, depth, d_index, n, d_slot);
         LAY_TRY(hipGetLastError());
     }
@@ -285,19 +218,7 @@ uint32_t layout_scene_device(yk_context* ctx, yk_scene* s, const DeviceTree& tre
         LAY_TRY(s->nodes4.ensure(16));
     }
 #undef LAY_TRY
-    yk_scene_layout_info& li = s->layout;
-    li.root_ref = root_leaf ? (YK_LEAF_BIT | tree.root_words[6]) : 0u;
-    li.n_top = words[2];
-    li.n_top_any = words[3];
-    li.wide = wide ? 1u : 0u;
-    li.wide_auto = wide && ctx->wide_bvh == 2 ? 1u : 0u;
-    s->record_bytes[YK_RECORDS_NODES] = std::max<size_t>(n_interior, 1) * sizeof(DevNode);
-    s->record_bytes[YK_RECORDS_NODES4] = (size_t)n4 * sizeof(DevNode4);
-    s->record_bytes[YK_RECORDS_TOP] = (size_t)words[2] * sizeof(DevNode);
-    s->record_bytes[YK_RECORDS_TOP_ANY] = (size_t)words[3] * sizeof(DevNode);
-    s->record_bytes[YK_RECORDS_TRIS] = 3 * (size_t)np * sizeof(float4);
-    s->record_bytes[YK_RECORDS_PRIM_SHADE] = (size_t)np * sizeof(uint4);
-    s->record_bytes[YK_RECORDS_PRIM_ATTR] = has_attr ? 4 * (size_t)np * sizeof(float4) : 0;
+    set_record_layout(s, n_interior, n4, words[2], words[3], np, has_attr, root_leaf ? (YK_LEAF_BIT | tree.root_words[6]) : 0u, wide && ctx->wide_bvh == 2);
     return YK_LAYOUT_REASON_NONE;
 }
 
@@ -316,10 +237,8 @@ extern "C" size_t yk_layout_wide_slots(const yk_bvh_node* nodes, size_t n, uint3
     const uint32_t* w = reinterpret_cast<const uint32_t*>(nodes);
     for (size_t i = 0; i < n; ++i) out_slot_per_node[i] = kNone;
     if (nd_leaf(w, 0u)) return 0;
-    std::vector<uint32_t> depth(n, 0u), excl(n);
-    depth[0] = 1u;
-    for (uint32_t i = 0; i < (uint32_t)n; ++i)
-        if (!nd_leaf(w, i)) depth[i + 1u] = depth[nd_a(w, i)] = depth[i] + 1u;
+    const std::vector<uint32_t> depth = node_depths(w, n);
+    std::vector<uint32_t> excl(n);
     uint32_t run = 0u;
     for (uint32_t i = 0; i < (uint32_t)n; ++i) {  // the scan
         excl[i] = run;
