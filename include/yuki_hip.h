@@ -313,6 +313,24 @@ yk_status yk_film_update_tiles(const yk_tile* tiles, size_t n_tiles, const float
  * overlaps the bulk of the next.  Destroy it only after every render that uses
  * it has completed (the library does not reference-count scenes). */
 yk_status yk_scene_create(yk_context* ctx, const yk_scene_desc* desc, yk_scene** out);
+/* The same scene from geometry that is in device memory already: a tensor of the caller's, the output of its own kernel,
+ * the next frame of an animation.  `desc` is read as by yk_scene_create, except that its large arrays — points, normals,
+ * uvs, indices, tri_mesh, tri_material, tri_area_light, shape_order — are DEVICE pointers on ctx's device (the same ones
+ * may be NULL); meshes, spheres, materials, lights and textures with their texels stay host pointers.  `stream` is the
+ * hipStream_t on which the caller produced the arrays (NULL: nothing to wait for): the context's stream waits for an event
+ * recorded there and all work runs on the context's stream.  The call is synchronous; on return the caller may free or
+ * overwrite its arrays — the scene owns device-to-device copies — and the scene is an ordinary one for every entry point.
+ * Nothing of O(n) runs on the host and no geometry crosses the host link: the per-triangle checks, the permutation test
+ * of shape_order and the shape bounds are kernels (their first error, in the order and with the message of
+ * yk_scene_create, is read back before any kernel follows an index), and the device builder and the device layout run
+ * whatever "bvh_builder" and "scene_layout" say ("bvh_small_range", "top_nodes" and "wide_bvh" apply).  Where the builder
+ * or the layout refuses (yk_scene_get_build_info / yk_scene_get_layout_info say who ran and why), the geometry is copied
+ * to the host once and yk_scene_create's path builds the same scene.  A triangle coordinate that is NaN or infinite counts
+ * as YK_BVH_REASON_NON_FINITE here, also where the fold of the bound would drop the NaN.  The host copies of the tree and of the per-shape
+ * material kinds are fetched on the first call that reads them.  YK_ERR_INVALID_ARGUMENT: ctx NULL; a large array that
+ * is not device memory of this context's device (checked with hipPointerGetAttributes before anything is launched) or
+ * whose allocation ends before its count does; whatever yk_scene_create refuses. */
+yk_status yk_scene_create_device(yk_context* ctx, const yk_scene_desc* desc, void* stream, yk_scene** out);
 void yk_scene_destroy(yk_scene* scene);
 yk_status yk_scene_get_info(const yk_scene* scene, yk_scene_info* out);
 /* nodes: n_nodes entries in the reference's depth-first layout; shape_order:

@@ -126,6 +126,9 @@ class Context {
 class Scene {
    public:
     Scene(Context* ctx, const yk_scene_desc& desc) : ctx_(ctx), n_lights_(desc.n_lights) { check(yk_scene_create(ctx ? ctx->handle() : nullptr, &desc, &h_), ctx ? ctx->handle() : nullptr); }
+    // yk_scene_create_device: desc's large arrays are device pointers on ctx's device, produced on `stream` (a hipStream_t, or nullptr)
+    struct FromDevice {};
+    Scene(FromDevice, Context& ctx, const yk_scene_desc& desc, void* stream = nullptr) : ctx_(&ctx), n_lights_(desc.n_lights) { check(yk_scene_create_device(ctx.handle(), &desc, stream, &h_), ctx.handle()); }
     ~Scene() { yk_scene_destroy(h_); }
     Scene(const Scene&) = delete;
     Scene& operator=(const Scene&) = delete;

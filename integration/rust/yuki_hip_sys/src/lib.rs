@@ -350,6 +350,8 @@ extern "C" {
     pub fn yk_make_point_light(light_to_world: *const f32, intensity: *const f32, out: *mut yk_light_desc) -> yk_status;
     pub fn yk_film_update_tiles(tiles: *const yk_tile, n_tiles: usize, tile_rgb: *const f32, res_x: u16, res_y: u16, film_rgb: *mut f32) -> yk_status;
     pub fn yk_scene_create(ctx: *mut yk_context, desc: *const yk_scene_desc, out: *mut *mut yk_scene) -> yk_status;
+    /// `desc`'s large arrays are device pointers on `ctx`'s device; `stream` is the hipStream_t that produced them (or null).
+    pub fn yk_scene_create_device(ctx: *mut yk_context, desc: *const yk_scene_desc, stream: *mut c_void, out: *mut *mut yk_scene) -> yk_status;
     pub fn yk_scene_destroy(scene: *mut yk_scene);
     pub fn yk_scene_get_info(scene: *const yk_scene, out: *mut yk_scene_info) -> yk_status;
     pub fn yk_scene_export_bvh(scene: *const yk_scene, nodes: *mut yk_bvh_node, shape_order: *mut u32) -> yk_status;

@@ -106,6 +106,7 @@ SYMBOLS = {
     "yk_make_point_light": (C.c_int, [abi.f32p, abi.f32p, C.POINTER(abi.LightDesc)]),
     "yk_film_update_tiles": (C.c_int, [vp, C.c_size_t, vp, C.c_uint16, C.c_uint16, vp]),
     "yk_scene_create": (C.c_int, [vp, C.POINTER(abi.SceneDesc), C.POINTER(vp)]),
+    "yk_scene_create_device": (C.c_int, [vp, C.POINTER(abi.SceneDesc), vp, C.POINTER(vp)]),
     "yk_scene_destroy": (None, [vp]),
     "yk_scene_get_info": (C.c_int, [vp, C.POINTER(SceneInfo)]),
     "yk_scene_export_bvh": (C.c_int, [vp, vp, vp]),

@@ -521,6 +521,71 @@ class Scene:
         self.h = h
         self._keep = None  # the library copied everything it needs
 
+    # name -> (pointer type of the yk_scene_desc field, accepted element types, elements per vertex "v" | triangle "t" | shape "s")
+    DEVICE_ARRAYS = {
+        "points": (abi.f32p, ("float32",), "v", 3),
+        "normals": (abi.f32p, ("float32",), "v", 3),
+        "uvs": (abi.f32p, ("float32",), "v", 2),
+        "indices": (abi.u32p, ("uint32", "int32"), "t", 3),
+        "tri_mesh": (abi.u32p, ("uint32", "int32"), "t", 1),
+        "tri_material": (abi.i32p, ("int32",), "t", 1),
+        "tri_area_light": (abi.i32p, ("int32",), "t", 1),
+        "shape_order": (abi.u32p, ("uint32", "int32"), "s", 1),
+    }
+
+    @classmethod
+    def from_device(cls, ctx, scene_data, arrays, stream=None):
+        """yk_scene_create_device: the scene of `scene_data` from geometry that is in device memory already.
+
+        `arrays` maps the names of Scene.DEVICE_ARRAYS to torch tensors on the context's device or to raw device addresses
+        (int); a name left out (or None) is a NULL array, as in yk_scene_desc.  A tensor's element type, contiguity,
+        element count and device are checked here (ValueError) before anything reaches the library; an address is taken
+        as it is.  `scene_data` supplies the small tables (meshes, spheres, materials, lights, textures), the BVH settings
+        and the counts: its own large arrays are read for their shapes only.  `stream`: the hipStream_t (an int, or a
+        torch stream) on which the arrays were produced; None waits for the current torch stream of a tensor's device
+        instead.  The call is synchronous and the scene keeps copies: the tensors may be freed or overwritten after it."""
+        unknown = set(arrays) - set(cls.DEVICE_ARRAYS)
+        if unknown:
+            raise ValueError(f"unknown device arrays {sorted(unknown)}; the names are {sorted(cls.DEVICE_ARRAYS)}")
+        counts = {"v": int(scene_data.points.shape[0]), "t": int(scene_data.indices.shape[0])}
+        counts["s"] = counts["t"] + len(scene_data.spheres)
+        address, tensors = {}, []
+        for name, (_, dtypes, per, k) in cls.DEVICE_ARRAYS.items():
+            a = arrays.get(name)
+            if a is None or isinstance(a, (int, np.integer)):
+                address[name] = int(a) if a else None
+                continue
+            if not hasattr(a, "data_ptr"):
+                raise ValueError(f"{name}: expected a torch tensor or a device address, got {type(a).__name__}")
+            if str(a.dtype).replace("torch.", "") not in dtypes:
+                raise ValueError(f"{name}: element type {a.dtype}, expected {' or '.join(dtypes)}")
+            if not a.is_contiguous():
+                raise ValueError(f"{name}: the tensor is not contiguous")
+            if a.numel() != k * counts[per]:
+                raise ValueError(f"{name}: {a.numel()} elements, expected {k * counts[per]}")
+            tensors.append((name, a))
+        for name, a in tensors:  # ... and only then where they are
+            if not a.is_cuda or a.device.index != ctx.device:
+                raise ValueError(f"{name}: the tensor is on {a.device}, not on the context's device {ctx.device}")
+            address[name] = a.data_ptr() or None
+        if stream is None and tensors:
+            import torch
+
+            torch.cuda.current_stream(tensors[0][1].device).synchronize()
+        elif stream is not None and not isinstance(stream, int):
+            stream = stream.cuda_stream
+        self = cls.__new__(cls)
+        self.ctx, self.data = ctx, scene_data
+        d, keep = scene_data.desc(LightFactory)
+        for name, (ptype, _, _, _) in cls.DEVICE_ARRAYS.items():
+            setattr(d, name, C.cast(C.c_void_p(address[name]), ptype))
+        self.n_lights = int(d.n_lights)
+        h = C.c_void_p()
+        check(lib().yk_scene_create_device(ctx.h, C.byref(d), C.c_void_p(stream) if stream else None, C.byref(h)), ctx.h)
+        self.h = h
+        del keep, tensors
+        return self
+
     def close(self):
         if getattr(self, "h", None):
             lib().yk_scene_destroy(self.h)

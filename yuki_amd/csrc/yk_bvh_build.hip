@@ -185,17 +185,24 @@ void words_to_nodes(const uint32_t* w, size_t n, std::vector<yk_bvh_node>& out) 
 
 // ------------------------------------------------------------------ the device builder
 bool build_bvh_device(yk_context* ctx, const std::vector<ShapeBounds>& sb, uint32_t max_shapes, uint32_t method, uint32_t small_range, HostBvh& out, yk_bvh_build_info& bi, DeviceTree* keep) {
+    return build_bvh_device(ctx, sb.data(), nullptr, sb.size(), max_shapes, method, small_range, out, bi, keep);
+}
+
+// The builder proper.  The bounds (six floats a shape) come from the host (h_sb) or are in HBM already (d_bounds, written
+// on the context's stream or ordered before it): then nothing is uploaded.
+bool build_bvh_device(yk_context* ctx, const ShapeBounds* h_sb, const float* d_bounds, size_t n_bounds, uint32_t max_shapes, uint32_t method, uint32_t small_range, HostBvh& out, yk_bvh_build_info& bi,
+                      DeviceTree* keep) {
     bi.small_range = small_range;
     if (method != YK_SPLIT_SAH && method != YK_SPLIT_MIDDLE) return refuse(bi, YK_BVH_REASON_SPLIT_METHOD);
-    if (sb.empty() || sb.size() > ((size_t)1 << 28)) return refuse(bi, YK_BVH_REASON_TOO_MANY_NODES);
-    const uint32_t N = (uint32_t)sb.size(), n_slots = 2u * N;
+    if (n_bounds == 0 || n_bounds > ((size_t)1 << 28)) return refuse(bi, YK_BVH_REASON_TOO_MANY_NODES);
+    const uint32_t N = (uint32_t)n_bounds, n_slots = 2u * N;
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
     DevScratch mem;
     float *d_sb = nullptr, *d_soa = nullptr;
     uint32_t *d_shape = nullptr, *d_list = nullptr, *d_slots = nullptr, *d_slot_depth = nullptr, *d_index = nullptr, *d_bsum = nullptr, *d_nodes = nullptr, *d_depth = nullptr, *d_words = nullptr;
     Range *d_q[2] = {nullptr, nullptr}, *d_small = nullptr;
-    if (!mem.get(d_sb, 6 * (size_t)N) || !mem.get(d_soa, 9 * (size_t)N) || !mem.get(d_shape, N) || !mem.get(d_list, N) || !mem.get(d_slots, 8 * (size_t)n_slots) || !mem.get(d_slot_depth, n_slots) ||
+    if ((!d_bounds && !mem.get(d_sb, 6 * (size_t)N)) || !mem.get(d_soa, 9 * (size_t)N) || !mem.get(d_shape, N) || !mem.get(d_list, N) || !mem.get(d_slots, 8 * (size_t)n_slots) || !mem.get(d_slot_depth, n_slots) ||
         !mem.get(d_index, n_slots) || !mem.get(d_bsum, scan_blocks(n_slots)) || !mem.get(d_nodes, 8 * (size_t)n_slots) || !mem.get(d_depth, n_slots) || !mem.get(d_words, 16) || !mem.get(d_q[0], N) || !mem.get(d_q[1], N) ||
         !mem.get(d_small, N))
         return refuse(bi, YK_BVH_REASON_OUT_OF_MEMORY);
@@ -216,10 +223,12 @@ bool build_bvh_device(yk_context* ctx, const std::vector<ShapeBounds>& sb, uint3
     }
     double t0 = now_seconds();
     uint32_t words[16];
-    DEV_TRY(hipMemcpyAsync(d_sb, sb.data(), 6 * (size_t)N * sizeof(float), hipMemcpyHostToDevice, st));
+    if (!d_bounds) {
+        DEV_TRY(hipMemcpyAsync(d_sb, h_sb, 6 * (size_t)N * sizeof(float), hipMemcpyHostToDevice, st));
+    }
     DEV_TRY(hipMemsetAsync(d_words, 0, 16 * sizeof(uint32_t), st));
     DEV_TRY(hipMemsetAsync(d_slot_depth, 0, (size_t)n_slots * sizeof(uint32_t), st));
-    k_prepare<<<(N + 255) / 256, 256, 0, st>>>(d_sb, N, p, d_words + 8);
+    k_prepare<<<(N + 255) / 256, 256, 0, st>>>(d_bounds ? d_bounds : d_sb, N, p, d_words + 8);
     DEV_TRY(hipGetLastError());
     DEV_TRY(hipMemcpyAsync(words, d_words, sizeof(words), hipMemcpyDeviceToHost, st));
     DEV_TRY(hipStreamSynchronize(st));

@@ -15,6 +15,7 @@
 #include "yk_device.h"
 #include "yk_host.h"
 #include "yk_kernels.h"
+#include "yk_scene_input.h"
 
 using namespace yk;
 
@@ -156,7 +157,15 @@ struct yk_scene {
     bool wide_auto = false;  // both node layouts on the device: the 4-wide one is used for jobs below YK_WIDE_MAX_PATHS
     yk_scene_info info;
     yk_bvh_build_info build_info;
-    std::vector<uint8_t> shape_kind;  // source shape -> device BSDF kind of its material (the kind bits of a render-loop hit word)
+    // source shape -> device BSDF kind of its material (the kind bits of a render-loop hit word).  A scene made from device arrays
+    // (yk_scene_create_device) has no host copy of tri_material: it keeps the kind of every material and of every sphere
+    // (lazy_mat_kind, lazy_sphere_kind) and fills the table from its device copy on the first call that reads it: every reader
+    // goes through scene_shape_kind().
+    mutable std::vector<uint8_t> shape_kind;
+    std::vector<uint8_t> lazy_mat_kind, lazy_sphere_kind;
+    bool shape_kind_lazy = false;
+    mutable std::once_flag kind_once;
+    mutable std::atomic<uint32_t> kind_fetched{1};
     // device
     DevBuf nodes, nodes4, top_nodes, top_nodes_any, tris, prim_shade, prim_attr, indices, points, normals, uvs, tri_mesh, tri_material, tri_area_light, mesh_flags, materials, lights, spheres, texels, tex_info;
     DevScene dev;
@@ -215,6 +224,10 @@ yk_status yk_upload_scene_image(yk_context* ctx, const std::shared_ptr<SceneImag
 // them there (thread-safe).  NULL when that copy fails.
 const HostBvh* scene_host_tree(const yk_scene* scene);
 
+// The scene's shape -> BSDF kind table, filled from the device copy of tri_material on the first call when the scene was
+// made from device arrays (thread-safe).  NULL when that copy fails.
+const std::vector<uint8_t>* scene_shape_kind(const yk_scene* scene);
+
 static inline double now_seconds() {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
@@ -226,6 +239,9 @@ static inline double now_seconds() {
 // receives the scalars only and its two arrays stay empty.
 bool build_bvh_device(yk_context* ctx, const std::vector<ShapeBounds>& bounds, uint32_t max_shapes_in_node, uint32_t split_method, uint32_t small_range, HostBvh& out, yk_bvh_build_info& bi,
                       DeviceTree* keep = nullptr);
+// The same with the bounds (six floats a shape: min.xyz, max.xyz) given as a host array or, d_bounds != NULL, in HBM already.
+bool build_bvh_device(yk_context* ctx, const ShapeBounds* h_bounds, const float* d_bounds, size_t n_bounds, uint32_t max_shapes_in_node, uint32_t split_method, uint32_t small_range, HostBvh& out,
+                      yk_bvh_build_info& bi, DeviceTree* keep);
 bool build_bvh_levels(const std::vector<ShapeBounds>& bounds, uint32_t max_shapes_in_node, uint32_t split_method, uint32_t small_range, HostBvh& out, yk_bvh_build_info& bi);
 
 // ------------------------------------------------------------------ yk_scene_layout.hip
@@ -233,6 +249,18 @@ bool build_bvh_levels(const std::vector<ShapeBounds>& bounds, uint32_t max_shape
 // from the tree in HBM and the scene's own uploaded arrays.  d_user_order (may be NULL): the caller's shape order, applied to
 // tree.order in place first (*order_applied says whether that happened).  Returns YK_LAYOUT_REASON_NONE, or the reason with the scene's records undefined.
 uint32_t layout_scene_device(yk_context* ctx, yk_scene* s, const DeviceTree& tree, const uint32_t* d_user_order, const uint8_t* d_mat_kind, bool has_attr, uint32_t tree_depth, bool* order_applied);
+
+// ------------------------------------------------------------------ yk_scene_input.hip
+// The input stage of yk_scene_create_device (yk_scene_input.h); both enqueue on `st` and return the launch status.
+// Checks: d_words receives the first failing per-triangle check, the first triangle that breaks the area-light rule and,
+// with d_order, whether it is a permutation of n_shapes shapes (d_seen: one bit a shape).  They read the index arrays and
+// d_light_kind (yk_light_kind per light) only.
+hipError_t enqueue_geometry_checks(hipStream_t st, const inp::Geometry& g, const uint8_t* d_light_kind, const uint32_t* d_order, uint32_t n_shapes, uint32_t* d_seen, inp::CheckWords* d_words);
+// d_sb[6 p ..]: the world bound of the shape at position p of the shape order (d_order, may be NULL); d_sphere_bounds: six
+// floats a sphere.  Only for arrays the checks have passed.  Sets d_words->non_finite (cleared by enqueue_geometry_checks)
+// when a triangle has a coordinate that is not finite.
+hipError_t enqueue_shape_bounds(hipStream_t st, const float* d_points, const uint32_t* d_indices, const uint32_t* d_order, const float* d_sphere_bounds, uint32_t n_triangles, uint32_t n_shapes, float* d_sb,
+                                inp::CheckWords* d_words);
 
 // ------------------------------------------------------------------ yk_scene.cpp
 // The exact sizes of a scene's seven record buffers (s->record_bytes) and the head of s->layout from what was laid out,

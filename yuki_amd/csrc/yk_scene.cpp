@@ -141,11 +141,13 @@ struct SceneImage {
 static void layout_records_host(const yk_context* ctx, SceneImage* s);
 
 // ---- the steps of yk_build_scene_image, in its order
-static yk_status check_description(yk_context* ctx, const yk_scene_desc* d) {
+// arrays_on_host false (yk_scene_create_device): the large arrays are device pointers; the two loops over the triangles are
+// left to k_check_geometry, which runs after everything here has passed
+static yk_status check_description(yk_context* ctx, const yk_scene_desc* d, bool arrays_on_host = true) {
     if ((uint64_t)d->n_triangles + d->n_spheres == 0) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "empty scene");
     if (d->n_triangles && (!d->points || !d->indices)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "missing geometry arrays");
     if (d->max_shapes_in_node == 0 || d->max_shapes_in_node > 65535u || d->split_method > 2) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "bad BVH settings");
-    for (uint32_t i = 0; i < d->n_triangles; ++i) {
+    for (uint32_t i = 0; arrays_on_host && i < d->n_triangles; ++i) {
         for (int k = 0; k < 3; ++k)
             if (d->indices[3 * i + k] >= d->n_vertices) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "vertex index out of range");
         if (d->tri_mesh && d->tri_mesh[i] >= d->n_meshes) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "mesh index out of range");
@@ -155,7 +157,7 @@ static yk_status check_description(yk_context* ctx, const yk_scene_desc* d) {
     }
     if ((d->n_spheres && !d->spheres) || (d->n_materials && !d->materials) || (d->n_lights && !d->lights) || (d->n_meshes && !d->meshes))
         return fail(ctx, YK_ERR_INVALID_ARGUMENT, "a count is non-zero but its array is NULL");
-    if (d->tri_area_light)  // Triangle.area_light is Option<Arc<RectangularLight>> (triangle.rs:22): -1 or a rectangular light
+    if (d->tri_area_light && arrays_on_host)  // Triangle.area_light is Option<Arc<RectangularLight>> (triangle.rs:22): -1 or a rectangular light
         for (uint32_t i = 0; i < d->n_triangles; ++i) {
             const int32_t al = d->tri_area_light[i];
             if (al < -1 || (al >= 0 && d->lights[al].kind != YK_LIGHT_RECT)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "tri_area_light must be -1 or index a rectangular light");
@@ -179,8 +181,25 @@ static yk_status check_description(yk_context* ctx, const yk_scene_desc* d) {
     return YK_OK;
 }
 
-// world bounds of every shape — Triangle::world_bound (triangle.rs:229-235), Sphere::world_bound (sphere.rs:121-123) —
-// in the caller's shape order when there is one
+// Sphere::world_bound (sphere.rs:121-123)
+static ShapeBounds sphere_bound(const yk_sphere_desc& sp) {
+    const float r = sp.radius;
+    const float lo[3] = {-r, -r, -r}, hi[3] = {r, r, r};
+    const float big = 3.40282347e+38f;
+    ShapeBounds b = {{big, big, big}, {-big, -big, -big}};
+    const int corner[8][3] = {{0, 0, 0}, {1, 0, 0}, {0, 1, 0}, {0, 0, 1}, {1, 1, 0}, {1, 0, 1}, {0, 1, 1}, {1, 1, 1}};  // transform.rs:194-206
+    for (int c = 0; c < 8; ++c) {
+        V3 q = xf_point(sp.object_to_world, V3{corner[c][0] ? hi[0] : lo[0], corner[c][1] ? hi[1] : lo[1], corner[c][2] ? hi[2] : lo[2]});
+        const float qq[3] = {q.x, q.y, q.z};
+        for (int k = 0; k < 3; ++k) {
+            b.bmin[k] = rmin(b.bmin[k], qq[k]);
+            b.bmax[k] = rmax(b.bmax[k], qq[k]);
+        }
+    }
+    return b;
+}
+// world bounds of every shape — Triangle::world_bound (triangle.rs:229-235), Sphere::world_bound — in the caller's shape
+// order when there is one
 static yk_status shape_bounds(yk_context* ctx, const yk_scene_desc* d, std::vector<ShapeBounds>& sb) {
     sb.assign((size_t)d->n_triangles + d->n_spheres, ShapeBounds());
     for (uint32_t i = 0; i < d->n_triangles; ++i) {
@@ -192,23 +211,7 @@ static yk_status shape_bounds(yk_context* ctx, const yk_scene_desc* d, std::vect
             sb[i].bmax[k] = rmax(rmax(p0[k], p1[k]), p2[k]);
         }
     }
-    for (uint32_t i = 0; i < d->n_spheres; ++i) {
-        const yk_sphere_desc& sp = d->spheres[i];
-        const float r = sp.radius;
-        const float lo[3] = {-r, -r, -r}, hi[3] = {r, r, r};
-        const float big = 3.40282347e+38f;
-        ShapeBounds b = {{big, big, big}, {-big, -big, -big}};
-        const int corner[8][3] = {{0, 0, 0}, {1, 0, 0}, {0, 1, 0}, {0, 0, 1}, {1, 1, 0}, {1, 0, 1}, {0, 1, 1}, {1, 1, 1}};  // transform.rs:194-206
-        for (int c = 0; c < 8; ++c) {
-            V3 q = xf_point(sp.object_to_world, V3{corner[c][0] ? hi[0] : lo[0], corner[c][1] ? hi[1] : lo[1], corner[c][2] ? hi[2] : lo[2]});
-            const float qq[3] = {q.x, q.y, q.z};
-            for (int k = 0; k < 3; ++k) {
-                b.bmin[k] = rmin(b.bmin[k], qq[k]);
-                b.bmax[k] = rmax(b.bmax[k], qq[k]);
-            }
-        }
-        sb[(size_t)d->n_triangles + i] = b;
-    }
+    for (uint32_t i = 0; i < d->n_spheres; ++i) sb[(size_t)d->n_triangles + i] = sphere_bound(d->spheres[i]);
     if (d->shape_order) {  // the caller's Scene.shapes order (a permutation of all shapes)
         std::vector<uint8_t> seen(sb.size(), 0);
         std::vector<ShapeBounds> ordered(sb.size());
@@ -266,17 +269,14 @@ static void fill_scene_info(SceneImage* s) {
     }
 }
 
-// the small tables of the device scene; the host layout reads mat_kind and mesh_flags
-static yk_status host_tables(yk_context* ctx, const yk_scene_desc* d, SceneImage* s) {
+// the small tables of the device scene, from the description's host tables alone; the host layout reads mat_kind and mesh_flags
+static yk_status small_tables(yk_context* ctx, const yk_scene_desc* d, SceneImage* s) {
     s->mats.resize(std::max<uint32_t>(d->n_materials, 1));
     s->mat_kind.assign(s->mats.size(), 0u);
     for (uint32_t m = 0; m < d->n_materials; ++m) {
         s->mats[m] = make_material(d->materials[m]);
         s->mat_kind[m] = s->mats[m].kind & 7u;
     }
-    s->shape_kind.resize(s->info.n_shapes);
-    for (uint32_t i = 0; i < d->n_triangles; ++i) s->shape_kind[i] = (uint8_t)s->mat_kind[d->tri_material[i]];
-    for (uint32_t k = 0; k < d->n_spheres; ++k) s->shape_kind[(size_t)d->n_triangles + k] = (uint8_t)s->mat_kind[d->spheres[k].material];
     s->mesh_flags.assign(std::max<uint32_t>(d->n_meshes, 1), 0);
     for (uint32_t m = 0; m < d->n_meshes; ++m)
         s->mesh_flags[m] = (d->meshes[m].has_normals ? YK_MESH_NORMALS : 0u) | (d->meshes[m].has_uvs ? YK_MESH_UVS : 0u) | (d->meshes[m].swaps_handedness ? YK_MESH_SWAPS : 0u);
@@ -294,10 +294,6 @@ static yk_status host_tables(yk_context* ctx, const yk_scene_desc* d, SceneImage
     }
     s->lights.resize(std::max<uint32_t>(d->n_lights, 1));
     for (uint32_t l = 0; l < d->n_lights; ++l) s->lights[l] = make_light(d->lights[l]);
-    s->tri_mesh.assign(d->n_triangles, 0);
-    if (d->tri_mesh) std::memcpy(s->tri_mesh.data(), d->tri_mesh, sizeof(uint32_t) * d->n_triangles);
-    s->tri_al.assign(d->n_triangles, -1);
-    if (d->tri_area_light) std::memcpy(s->tri_al.data(), d->tri_area_light, sizeof(int32_t) * d->n_triangles);
     for (uint32_t t = 0; t < d->n_textures; ++t) {
         const yk_texture_desc& td = d->textures[t];
         s->tex_info.push_back(make_uint4((unsigned)s->texels.size(), td.width, td.height, 0u));
@@ -305,6 +301,19 @@ static yk_status host_tables(yk_context* ctx, const yk_scene_desc* d, SceneImage
         if (s->texels.size() + n > 0xffffffffull) return fail(ctx, YK_ERR_UNSUPPORTED, "more than 2^32 texels");
         for (size_t k = 0; k < n; ++k) s->texels.push_back(make_float4(td.rgb[3 * k], td.rgb[3 * k + 1], td.rgb[3 * k + 2], 0.0f));
     }
+    return YK_OK;
+}
+// ... and what is derived from the per-triangle arrays on the host
+static yk_status host_tables(yk_context* ctx, const yk_scene_desc* d, SceneImage* s) {
+    yk_status st = small_tables(ctx, d, s);
+    if (st != YK_OK) return st;
+    s->shape_kind.resize(s->info.n_shapes);
+    for (uint32_t i = 0; i < d->n_triangles; ++i) s->shape_kind[i] = (uint8_t)s->mat_kind[d->tri_material[i]];
+    for (uint32_t k = 0; k < d->n_spheres; ++k) s->shape_kind[(size_t)d->n_triangles + k] = (uint8_t)s->mat_kind[d->spheres[k].material];
+    s->tri_mesh.assign(d->n_triangles, 0);
+    if (d->tri_mesh) std::memcpy(s->tri_mesh.data(), d->tri_mesh, sizeof(uint32_t) * d->n_triangles);
+    s->tri_al.assign(d->n_triangles, -1);
+    if (d->tri_area_light) std::memcpy(s->tri_al.data(), d->tri_area_light, sizeof(int32_t) * d->n_triangles);
     return YK_OK;
 }
 
@@ -616,6 +625,45 @@ static uint32_t layout_on_device(yk_context* ctx, SceneImage* img, yk_scene* s) 
     return YK_LAYOUT_REASON_NONE;
 }
 
+// The DevScene the kernels are handed, from the scene's buffers, its layout info and the description's scalars.
+static void bind_device_scene(yk_scene* s, const yk_scene_desc* d) {
+    const yk_scene_layout_info& li = s->layout;
+    DevScene& ds = s->dev;
+    ds.nodes = s->nodes.as<DevNode>();
+    ds.nodes4 = li.wide ? s->nodes4.as<DevNode4>() : nullptr;
+    s->wide_auto = li.wide_auto != 0;
+    ds.top_nodes = s->top_nodes.as<DevNode>();
+    ds.n_top = li.n_top;
+    ds.top_nodes_any = s->top_nodes_any.as<DevNode>();
+    ds.n_top_any = li.n_top_any;
+    ds.tris = s->tris.as<float4>();
+    ds.prim_shade = s->prim_shade.as<uint4>();
+    ds.prim_attr = s->record_bytes[YK_RECORDS_PRIM_ATTR] ? s->prim_attr.as<float4>() : nullptr;
+    ds.spheres = d->n_spheres ? s->spheres.as<DevSphere>() : nullptr;
+    ds.n_triangles = d->n_triangles;
+    ds.root_ref = li.root_ref;
+    for (int k = 0; k < 3; ++k) {  // node 0's box
+        ds.root_bmin[k] = s->info.bounds_min[k];
+        ds.root_bmax[k] = s->info.bounds_max[k];
+        ds.background[k] = d->background[k];
+    }
+    ds.indices = s->indices.as<uint32_t>();
+    ds.points = s->points.as<float>();
+    ds.normals = s->normals.as<float>();
+    ds.uvs = s->uvs.as<float>();
+    ds.tri_mesh = s->tri_mesh.as<uint32_t>();
+    ds.tri_material = s->tri_material.as<int32_t>();
+    ds.tri_area_light = s->tri_area_light.as<int32_t>();
+    ds.mesh_flags = s->mesh_flags.as<uint32_t>();
+    ds.materials = s->materials.as<Material>();
+    ds.lights = s->lights.as<DevLight>();
+    ds.n_lights = d->n_lights;
+    ds.texels = d->n_textures ? s->texels.as<float4>() : nullptr;
+    ds.tex_info = d->n_textures ? s->tex_info.as<uint4>() : nullptr;
+    s->on_device = true;
+    for (DevBuf* b : scene_buffers(s)) s->info.device_bytes += b->bytes;
+}
+
 // Device half: one copy of the image in the HBM of ctx's device.
 yk_status yk_upload_scene_image(yk_context* ctx, const std::shared_ptr<SceneImage>& img, yk_scene** out) try {
     if (!out) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null out");
@@ -685,46 +733,248 @@ yk_status yk_upload_scene_image(yk_context* ctx, const std::shared_ptr<SceneImag
             set_record_layout(s, s->info.n_interior, img->dn4.size(), img->top.size(), img->top_any.size(), s->info.n_shapes, d->normals || d->uvs, img->root_ref, img->wide_auto);
         }
 #undef UP
-        DevScene& ds = s->dev;
-        ds.nodes = s->nodes.as<DevNode>();
-        ds.nodes4 = li.wide ? s->nodes4.as<DevNode4>() : nullptr;
-        s->wide_auto = li.wide_auto != 0;
-        ds.top_nodes = s->top_nodes.as<DevNode>();
-        ds.n_top = li.n_top;
-        ds.top_nodes_any = s->top_nodes_any.as<DevNode>();
-        ds.n_top_any = li.n_top_any;
-        ds.tris = s->tris.as<float4>();
-        ds.prim_shade = s->prim_shade.as<uint4>();
-        ds.prim_attr = s->record_bytes[YK_RECORDS_PRIM_ATTR] ? s->prim_attr.as<float4>() : nullptr;
-        ds.spheres = d->n_spheres ? s->spheres.as<DevSphere>() : nullptr;
-        ds.n_triangles = d->n_triangles;
-        ds.root_ref = li.root_ref;
-        for (int k = 0; k < 3; ++k) {  // node 0's box
-            ds.root_bmin[k] = s->info.bounds_min[k];
-            ds.root_bmax[k] = s->info.bounds_max[k];
-            ds.background[k] = d->background[k];
-        }
-        ds.indices = s->indices.as<uint32_t>();
-        ds.points = s->points.as<float>();
-        ds.normals = s->normals.as<float>();
-        ds.uvs = s->uvs.as<float>();
-        ds.tri_mesh = s->tri_mesh.as<uint32_t>();
-        ds.tri_material = s->tri_material.as<int32_t>();
-        ds.tri_area_light = s->tri_area_light.as<int32_t>();
-        ds.mesh_flags = s->mesh_flags.as<uint32_t>();
-        ds.materials = s->materials.as<Material>();
-        ds.lights = s->lights.as<DevLight>();
-        ds.n_lights = d->n_lights;
-        ds.texels = d->n_textures ? s->texels.as<float4>() : nullptr;
-        ds.tex_info = d->n_textures ? s->tex_info.as<uint4>() : nullptr;
-        s->on_device = true;
+        bind_device_scene(s, d);
         s->info.upload_seconds = now_seconds() - u0;
-        for (DevBuf* b : scene_buffers(s)) s->info.device_bytes += b->bytes;
     }
     guard.s = nullptr;
     *out = s;
     return YK_OK;
 } YK_CATCH(ctx)
+
+const std::vector<uint8_t>* scene_shape_kind(const yk_scene* s) {
+    if (!s) return nullptr;
+    if (s->shape_kind_lazy)
+        std::call_once(s->kind_once, [s] {
+            std::vector<int32_t> mat(s->n_triangles);
+            (void)hipSetDevice(s->device);
+            if (s->n_triangles && hipMemcpy(mat.data(), s->tri_material.p, (size_t)s->n_triangles * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess) {
+                (void)hipGetLastError();
+                return;
+            }
+            std::vector<uint8_t> kinds((size_t)s->n_triangles + s->n_spheres);
+            for (uint32_t i = 0; i < s->n_triangles; ++i) kinds[i] = s->lazy_mat_kind[(uint32_t)mat[i]];
+            for (uint32_t k = 0; k < s->n_spheres; ++k) kinds[(size_t)s->n_triangles + k] = s->lazy_sphere_kind[k];
+            s->shape_kind.swap(kinds);
+            s->kind_fetched.store(1u);
+        });
+    return s->kind_fetched.load() ? &s->shape_kind : nullptr;
+}
+
+// ------------------------------------------------------------------ yk_scene_create_device
+// The same scene from large arrays that are in HBM already ("Input from device memory"): the per-triangle
+// checks, the permutation test and the shape bounds run as kernels (yk_scene_input.hip), the builder starts from bounds
+// it finds in HBM and the layout reads the scene's own device-to-device copies.
+
+// every non-NULL large array is device memory of ctx's device, and its allocation reaches as far as its count says
+static yk_status check_device_arrays(yk_context* ctx, const yk_scene_desc* d) {
+    const size_t nv = d->n_vertices, nt = d->n_triangles, ns = nt + d->n_spheres;
+    const struct {
+        const char* name;
+        const void* p;
+        size_t bytes;
+    } arrays[] = {{"points", d->points, 12 * nv},          {"normals", d->normals, 12 * nv},          {"uvs", d->uvs, 8 * nv},
+                  {"indices", d->indices, 12 * nt},        {"tri_mesh", d->tri_mesh, 4 * nt},         {"tri_material", d->tri_material, 4 * nt},
+                  {"tri_area_light", d->tri_area_light, 4 * nt}, {"shape_order", d->shape_order, 4 * ns}};
+    for (const auto& a : arrays) {
+        if (!a.p) continue;
+        hipPointerAttribute_t at;
+        std::memset(&at, 0, sizeof(at));
+        const hipError_t e = hipPointerGetAttributes(&at, a.p);
+        if (e != hipSuccess) (void)hipGetLastError();
+        if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, std::string(a.name) + " is not device memory of this context's device");
+        hipDeviceptr_t base = nullptr;
+        size_t size = 0;
+        if (hipMemGetAddressRange(&base, &size, const_cast<void*>(a.p)) != hipSuccess) {
+            (void)hipGetLastError();
+        } else if (reinterpret_cast<const char*>(a.p) + a.bytes > reinterpret_cast<const char*>(base) + size) {
+            return fail(ctx, YK_ERR_INVALID_ARGUMENT, std::string(a.name) + " is shorter than its count says");
+        }
+    }
+    return YK_OK;
+}
+
+// The device route.  *fall_back: the builder or the layout refused and the caller builds the scene by the host path — *refused
+// then holds the builder's info with its reason (reason 0: it was the layout); any other failure is final.
+static yk_status create_scene_on_device(yk_context* ctx, const yk_scene_desc* d, hipStream_t st, yk_scene** out, bool* fall_back, yk_bvh_build_info* refused) {
+    *fall_back = false;
+    std::memset(refused, 0, sizeof(*refused));
+    const uint32_t nt = d->n_triangles, N = nt + d->n_spheres;
+    yk_scene* s = new yk_scene();
+    struct SceneGuard {
+        yk_scene* s;
+        ~SceneGuard() {
+            if (s) yk_scene_destroy(s);
+        }
+    } guard{s};
+    s->device = ctx->device;
+    s->n_triangles = nt;
+    s->n_spheres = d->n_spheres;
+    s->n_lights = d->n_lights;
+    for (uint32_t l = 0; l < d->n_lights; ++l) s->n_delta_lights += d->lights[l].kind != YK_LIGHT_RECT ? 1u : 0u;
+    std::memset(&s->info, 0, sizeof(s->info));
+    std::memset(&s->build_info, 0, sizeof(s->build_info));
+    const double u0 = now_seconds();
+
+    // the scene's own copies; a missing tri_mesh reads as zeros, a missing tri_area_light as -1
+    auto own = [&](DevBuf& buf, const void* src, size_t bytes, int fill) -> hipError_t {
+        hipError_t e = buf.ensure(std::max<size_t>(bytes, 16));
+        if (e != hipSuccess || bytes == 0) return e;
+        return src ? hipMemcpyAsync(buf.p, src, bytes, hipMemcpyDeviceToDevice, st) : hipMemsetAsync(buf.p, fill, bytes, st);
+    };
+    HIP_TRY(ctx, own(s->indices, d->indices, 12 * (size_t)nt, 0));
+    HIP_TRY(ctx, own(s->points, d->points, 12 * (size_t)d->n_vertices, 0));
+    HIP_TRY(ctx, own(s->normals, d->normals, d->normals ? 12 * (size_t)d->n_vertices : 0, 0));
+    HIP_TRY(ctx, own(s->uvs, d->uvs, d->uvs ? 8 * (size_t)d->n_vertices : 0, 0));
+    HIP_TRY(ctx, own(s->tri_mesh, d->tri_mesh, 4 * (size_t)nt, 0));
+    HIP_TRY(ctx, own(s->tri_material, d->tri_material, 4 * (size_t)nt, 0));
+    HIP_TRY(ctx, own(s->tri_area_light, d->tri_area_light, 4 * (size_t)nt, 0xff));
+
+    SceneImage img;  // the small tables, and the tree while it waits for the layout
+    std::memset(&img.info, 0, sizeof(img.info));
+    yk_status rc = small_tables(ctx, d, &img);
+    if (rc != YK_OK) return rc;
+    std::vector<uint8_t> light_kind(std::max<uint32_t>(d->n_lights, 1), 0), mat_kind(img.mat_kind.begin(), img.mat_kind.end());
+    for (uint32_t l = 0; l < d->n_lights; ++l) light_kind[l] = (uint8_t)d->lights[l].kind;
+    std::vector<ShapeBounds> sphere_b(std::max<uint32_t>(d->n_spheres, 1));
+    for (uint32_t k = 0; k < d->n_spheres; ++k) sphere_b[k] = sphere_bound(d->spheres[k]);
+
+    DevScratch tmp;
+    inp::CheckWords* d_words = nullptr;
+    uint8_t *d_light_kind = nullptr, *d_mat_kind = nullptr;
+    uint32_t *d_seen = nullptr, *d_user = nullptr;
+    float *d_sphere_b = nullptr, *d_sb = nullptr;
+    if (!tmp.get(d_words, 1) || !tmp.get(d_light_kind, light_kind.size()) || !tmp.get(d_mat_kind, mat_kind.size()) || !tmp.get(d_sphere_b, 6 * sphere_b.size()) || !tmp.get(d_sb, 6 * (size_t)N) ||
+        (d->shape_order && (!tmp.get(d_seen, ((size_t)N + 31) / 32) || !tmp.get(d_user, N))))
+        return fail(ctx, YK_ERR_OUT_OF_MEMORY, "no device memory for the scene's input stage");
+    HIP_TRY(ctx, hipMemcpyAsync(d_light_kind, light_kind.data(), light_kind.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_mat_kind, mat_kind.data(), mat_kind.size(), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_sphere_b, sphere_b.data(), sphere_b.size() * sizeof(ShapeBounds), hipMemcpyHostToDevice, st));
+    if (d->shape_order) HIP_TRY(ctx, hipMemcpyAsync(d_user, d->shape_order, 4 * (size_t)N, hipMemcpyDeviceToDevice, st));
+
+    // the checks, on the scene's copies; their words are read before any kernel follows an index
+    inp::Geometry g;
+    g.indices = s->indices.as<uint32_t>();
+    g.tri_mesh = d->tri_mesh ? s->tri_mesh.as<uint32_t>() : nullptr;
+    g.tri_material = s->tri_material.as<int32_t>();
+    g.tri_area_light = d->tri_area_light ? s->tri_area_light.as<int32_t>() : nullptr;
+    g.n_triangles = nt;
+    g.n_vertices = d->n_vertices;
+    g.n_meshes = d->n_meshes;
+    g.n_materials = d->n_materials;
+    g.n_lights = d->n_lights;
+    inp::CheckWords words;
+    HIP_TRY(ctx, enqueue_geometry_checks(st, g, d_light_kind, d_user, N, d_seen, d_words));
+    HIP_TRY(ctx, hipMemcpyAsync(&words, d_words, sizeof(words), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (words.first != inp::kNoFailure) {
+        static const char* const what[4] = {"vertex index out of range", "mesh index out of range", "material index out of range", "light index out of range"};
+        return fail(ctx, YK_ERR_INVALID_ARGUMENT, what[words.first & 3u]);
+    }
+    if (words.light != inp::kNoFailure) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "tri_area_light must be -1 or index a rectangular light");
+    if (words.order_bad) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "shape_order is not a permutation of the shapes");
+
+    // bounds and tree
+    const double t0 = now_seconds();
+    HIP_TRY(ctx, enqueue_shape_bounds(st, s->points.as<float>(), s->indices.as<uint32_t>(), d_user, d_sphere_b, nt, N, d_sb, d_words));
+    HIP_TRY(ctx, hipMemcpyAsync(&words.non_finite, &d_words->non_finite, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (words.non_finite) {  // a NaN that rmin / rmax dropped from its bound included (yk_scene_input.h)
+        refused->small_range = (uint32_t)ctx->bvh_small_range;
+        refused->reason = YK_BVH_REASON_NON_FINITE;
+        *fall_back = true;
+        return YK_OK;
+    }
+    img.bvh = img.bvh_mut = std::make_shared<HostBvh>();
+    img.tree_on_device = true;
+    if (!build_bvh_device(ctx, nullptr, d_sb, N, d->max_shapes_in_node, d->split_method, (uint32_t)ctx->bvh_small_range, *img.bvh_mut, s->build_info, &img.dtree)) {
+        *refused = s->build_info;
+        *fall_back = true;
+        return YK_OK;
+    }
+    img.info.build_seconds = now_seconds() - t0;
+    if (img.bvh->split_failed || img.dtree.n_nodes == 0) return fail(ctx, YK_ERR_BVH_BUILD, "BVH split failed (reference: assert_ne!(mid, start))");
+    fill_scene_info(&img);
+    if (img.info.n_nodes > YK_REF_INDEX_MAX || img.info.n_shapes > YK_REF_INDEX_MAX) return fail(ctx, YK_ERR_UNSUPPORTED, "more than 2^28 BVH nodes or shapes");
+    s->info = img.info;
+
+    // small tables, records
+    if ((rc = upload(ctx, s->mesh_flags, img.mesh_flags.data(), img.mesh_flags.size())) != YK_OK || (rc = upload(ctx, s->materials, img.mats.data(), img.mats.size())) != YK_OK ||
+        (rc = upload(ctx, s->lights, img.lights.data(), img.lights.size())) != YK_OK || (rc = upload(ctx, s->spheres, img.spheres.data(), img.spheres.size())) != YK_OK ||
+        (rc = upload(ctx, s->texels, img.texels.data(), img.texels.size())) != YK_OK || (rc = upload(ctx, s->tex_info, img.tex_info.data(), img.tex_info.size())) != YK_OK)
+        return rc;
+    const double l0 = now_seconds();
+    bool order_applied = false;
+    if (layout_scene_device(ctx, s, img.dtree, d_user, d_mat_kind, d->normals || d->uvs, img.bvh->depth, &order_applied) != YK_LAYOUT_REASON_NONE) {
+        *fall_back = true;
+        return YK_OK;
+    }
+    s->layout.layout = YK_LAYOUT_DEVICE;
+    s->layout.seconds_layout = now_seconds() - l0;
+    std::swap(s->tree_nodes, img.dtree.nodes);  // the host copy of the tree is made when something asks for it (scene_host_tree)
+    std::swap(s->tree_order, img.dtree.order);
+    s->bvh = img.bvh;
+    s->bvh_lazy = img.bvh_mut;
+    s->tree_fetched.store(0u);
+    s->lazy_mat_kind.swap(mat_kind);  // ... and so is the shape -> kind table (scene_shape_kind)
+    s->lazy_sphere_kind.resize(d->n_spheres);
+    for (uint32_t k = 0; k < d->n_spheres; ++k) s->lazy_sphere_kind[k] = s->lazy_mat_kind[(uint32_t)d->spheres[k].material];
+    s->shape_kind_lazy = true;
+    s->kind_fetched.store(0u);
+    bind_device_scene(s, d);
+    s->info.upload_seconds = now_seconds() - u0;
+    guard.s = nullptr;
+    *out = s;
+    return YK_OK;
+}
+
+// The builder or the layout refused: the geometry goes to the host once and the host path builds the scene with the
+// device layout asked for.  Where the builder refused, the host recursion builds the tree and the build info keeps the
+// refusal (`refused`, with its reason); where the layout failed, the builder is asked again and the layout falls back
+// as it does for host input.
+static yk_status create_scene_from_host_copy(yk_context* ctx, const yk_scene_desc* d, hipStream_t st, const yk_bvh_build_info& refused, yk_scene** out) {
+    const size_t nv = d->n_vertices, nt = d->n_triangles, ns = nt + d->n_spheres;
+    std::vector<float> points(3 * nv), normals(d->normals ? 3 * nv : 0), uvs(d->uvs ? 2 * nv : 0);
+    std::vector<uint32_t> indices(3 * nt), tri_mesh(d->tri_mesh ? nt : 0), order(d->shape_order ? ns : 0);
+    std::vector<int32_t> tri_material(nt), tri_al(d->tri_area_light ? nt : 0);
+    yk_scene_desc h = *d;
+    auto fetch = [&](auto& v, const void* src) -> hipError_t { return v.empty() ? hipSuccess : hipMemcpyAsync(v.data(), src, v.size() * sizeof(v[0]), hipMemcpyDeviceToHost, st); };
+    HIP_TRY(ctx, fetch(points, d->points));
+    HIP_TRY(ctx, fetch(normals, d->normals));
+    HIP_TRY(ctx, fetch(uvs, d->uvs));
+    HIP_TRY(ctx, fetch(indices, d->indices));
+    HIP_TRY(ctx, fetch(tri_mesh, d->tri_mesh));
+    HIP_TRY(ctx, fetch(tri_material, d->tri_material));
+    HIP_TRY(ctx, fetch(tri_al, d->tri_area_light));
+    HIP_TRY(ctx, fetch(order, d->shape_order));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    h.points = points.data();
+    h.normals = d->normals ? normals.data() : nullptr;
+    h.uvs = d->uvs ? uvs.data() : nullptr;
+    h.indices = indices.data();
+    h.tri_mesh = d->tri_mesh ? tri_mesh.data() : nullptr;
+    h.tri_material = tri_material.data();
+    h.tri_area_light = d->tri_area_light ? tri_al.data() : nullptr;
+    h.shape_order = d->shape_order ? order.data() : nullptr;
+    struct Options {  // this entry point always asks for the device builder and layout
+        yk_context* ctx;
+        int64_t builder, layout;
+        ~Options() {
+            ctx->bvh_builder = builder;
+            ctx->scene_layout = layout;
+        }
+    } restore{ctx, ctx->bvh_builder, ctx->scene_layout};
+    ctx->bvh_builder = refused.reason ? 0 : 1;
+    ctx->scene_layout = 1;
+    std::shared_ptr<SceneImage> img;
+    yk_status rc = yk_build_scene_image(ctx, &h, img);
+    if (rc != YK_OK || (rc = yk_upload_scene_image(ctx, img, out)) != YK_OK) return rc;
+    if (refused.reason) {  // who built the tree is the host path's answer, why is the refusal's
+        const uint32_t builder = (*out)->build_info.builder;
+        (*out)->build_info = refused;
+        (*out)->build_info.builder = builder;
+    }
+    return YK_OK;
+}
 
 extern "C" {
 
@@ -738,6 +988,31 @@ yk_status yk_scene_create(yk_context* ctx, const yk_scene_desc* d, yk_scene** ou
     if (st != YK_OK) return st;
     return yk_upload_scene_image(ctx, img, out);
 }
+
+yk_status yk_scene_create_device(yk_context* ctx, const yk_scene_desc* d, void* stream, yk_scene** out) try {
+    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
+    YK_LOCK(ctx);
+    if (!d || !out) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null scene description");
+    *out = nullptr;
+    yk_status rc = check_description(ctx, d, false);  // everything that reads host tables only
+    if (rc != YK_OK) return rc;
+    if ((uint64_t)d->n_triangles + d->n_spheres > YK_REF_INDEX_MAX) return fail(ctx, YK_ERR_UNSUPPORTED, "more than 2^28 BVH nodes or shapes");
+    (void)hipSetDevice(ctx->device);
+    if ((rc = check_device_arrays(ctx, d)) != YK_OK) return rc;
+    hipStream_t st = ctx->stream;
+    if (stream) {  // the caller's arrays are complete where its stream stands now
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_in, (hipStream_t)stream));
+        HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_in, 0));
+    }
+    bool fall_back = false;
+    yk_bvh_build_info refused;
+    rc = create_scene_on_device(ctx, d, st, out, &fall_back, &refused);
+    if (rc != YK_OK || !fall_back) {
+        if (rc != YK_OK) (void)hipStreamSynchronize(st);  // the caller may free its arrays on return
+        return rc;
+    }
+    return create_scene_from_host_copy(ctx, d, st, refused, out);
+} YK_CATCH(ctx)
 
 void yk_scene_destroy(yk_scene* s) {
     if (!s) return;

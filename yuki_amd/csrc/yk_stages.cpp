@@ -105,6 +105,8 @@ yk_status yk_trace_closest(yk_context* ctx, const yk_scene* scene, size_t n, con
         const HostBvh* tree = scene_host_tree(scene);
         if (!tree) return fail(ctx, YK_ERR_DEVICE, "the scene's shape order could not be copied back from the device");
         const std::vector<uint32_t>& order = tree->shape_order;
+        const std::vector<uint8_t>* kinds = scene_shape_kind(scene);
+        if (!kinds) return fail(ctx, YK_ERR_DEVICE, "the scene's triangle materials could not be copied back from the device");
         for (size_t i = 0; i < n; ++i) {
             const int32_t h = out_shape[i];
             if (h == -1) continue;
@@ -112,9 +114,9 @@ yk_status yk_trace_closest(yk_context* ctx, const yk_scene* scene, size_t n, con
             if (h < 0 || prim >= order.size())
                 return fail(ctx, YK_ERR_DEVICE, "trace_stage_kernel " + std::to_string(mode) + ": ray " + std::to_string(i) + " got hit word " + std::to_string(h));
             const uint32_t src = order[prim];
-            if (kind != scene->shape_kind[src])
+            if (kind != (*kinds)[src])
                 return fail(ctx, YK_ERR_DEVICE, "trace_stage_kernel " + std::to_string(mode) + ": ray " + std::to_string(i) + " hit shape " + std::to_string(src) +
-                                                     " with kind bits " + std::to_string(kind) + ", its material's kind is " + std::to_string(scene->shape_kind[src]));
+                                                     " with kind bits " + std::to_string(kind) + ", its material's kind is " + std::to_string((*kinds)[src]));
             out_shape[i] = (int32_t)src;
         }
     }
