@@ -280,7 +280,9 @@ yk_status yk_context_interrupt(yk_context* ctx);
  * yk_scene_get_layout_info says which ran; a device-built, device-laid scene copies its 32-byte nodes back only when
  * yk_scene_export_bvh, yk_scene_node_bounds or a "trace_stage_kernel" stage call asks for them) — the last five apply
  * to scenes created afterwards; "overlay_coop_min" (1 .. 65536, default 32: box
- * edges of at least this many pixels are drawn by a whole wave in yk_overlay_draw[_device], shorter ones by one lane).  Test hook: "trace_stage_kernel" (0, default: yk_trace_closest /
+ * edges of at least this many pixels are drawn by a whole wave in yk_overlay_draw[_device], shorter ones by one lane);
+ * "denoise_lds_max_step" (0 | 1 | 2, default 2: the a-trous iterations of yk_denoise[_device] with a step up to this
+ * stage their taps in LDS, the others read global memory).  Test hook: "trace_stage_kernel" (0, default: yk_trace_closest /
  * yk_trace_any run the generic kernels as documented | 1: the generic kernels in the render loop's
  * flavour | 2: the wave-packet kernels; modes 1 and 2 report shape ids and verdicts only, and
  * refuse out_t, out_bary, counters, a closest-hit t_max and, in mode 2, a tree deeper than 64
@@ -622,6 +624,56 @@ yk_status yk_present_device(yk_context* ctx, const yk_present_desc* desc, const 
  * blocks.  pixels: row-major, row 0 = top, `channels` bytes a pixel — what yk_present writes as RGBA8.  Host only.
  * YK_ERR_INVALID_ARGUMENT: NULL path or pixels, a zero dimension, channels other than 3 or 4, a file that cannot be written. */
 yk_status yk_write_png(const char* path, uint32_t width, uint32_t height, uint32_t channels, const uint8_t* pixels);
+
+/* ---- denoise: first-hit guides and an edge-avoiding a-trous filter, between the film and the tone map ----
+ * The reference shows its raw Monte-Carlo film; this pass is the library's own.  The filter is the edge-avoiding a-trous
+ * wavelet transform (Dammertz et al., HPG 2010) with a colour stop, a normal stop and a plane-distance stop.  Its rule is
+ * stated next to each expression in yuki_amd/csrc/yk_denoise.h, and the host and the device instance agree bit for bit.
+ * In short (binary32, every operation separate, no FMA, exp = the library's expf, a NaN an operation produces is
+ * 0x7fc00000):
+ *   Input: the film's RGB; with a sample table every channel is divided by (float)samples[flat] where that count is > 0,
+ *     flat by the tone map's index rule (floor / ceil mismatch included).
+ *   Iteration i = 0 .. iterations-1, step s = 1 << i, colour scale sigma_color / (float)(1 << i); every iteration reads
+ *     the previous iteration's colours of all pixels.  iterations = 0 returns the normalised film, copied as bits.
+ *   Taps: dy = -2..2 outside, dx = -2..2 inside, Q = P + s*(dx, dy), skipped outside the film; h = k[|dx|]*k[|dy|] with
+ *     k = (3/8, 1/4, 1/16).  The centre tap has weight h alone.  Any other tap: w = h*exp(-e), e = (a_c + a_n) + a_p,
+ *     a_c = ((dr*dr + dg*dg) + db*db) / (sigma_c,i * sigma_c,i); both hits: a_n = |ns_P - ns_Q|^2 / sigma_normal^2 and
+ *     a_p = d*d / sigma_plane^2 with d = dot(ns_P, p_Q - p_P); both misses: a_n = a_p = 0; a hit and a miss: w = 0.
+ *     A tap whose weight is 0 or NaN is skipped, so an infinite or NaN pixel stays where it is and does not spread.
+ *   Output: sum(w * c_Q) / sum(w) per channel. */
+typedef struct yk_guide {
+    float ns[3]; /* si.shading.n as the ShadingNormals integrator reads it (not halved, not offset); 0 on a miss */
+    float hit;   /* 1.0f on a hit, 0.0f on a miss */
+    float p[3];  /* si.p; 0 on a miss */
+    float t;     /* Hit.t; 0 on a miss */
+} yk_guide;      /* 32 bytes: a filter tap is two 16-byte loads */
+typedef struct yk_denoise_desc {
+    uint32_t iterations; /* 0 .. 8 */
+    float sigma_color, sigma_normal, sigma_plane; /* each > 0; +inf switches its stop off */
+} yk_denoise_desc;
+/* The guides of a res_x x res_y film, row-major: one ray per pixel through the pixel centre, Camera::ray((x + 0.5, y + 0.5)),
+ * traced by the render loop's closest-hit kernels; spheres are served like triangles.  Synchronous, `out` is a host array
+ * of res_x * res_y records.  YK_ERR_INVALID_ARGUMENT: a NULL pointer, a zero resolution, a scene of another device. */
+yk_status yk_render_guides(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, uint16_t res_x, uint16_t res_y, yk_guide* out);
+/* The same into device memory (16-byte aligned), ordered on `stream` (NULL = the context's) without waiting on the host.
+ * Guides depend on the camera and the scene only: render them again when either changes, not with every pass. */
+yk_status yk_render_guides_device(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, uint16_t res_x, uint16_t res_y,
+                                  void* d_guides, void* stream);
+/* Host buffers: film_rgb and out_rgb row-major RGB (res_y, res_x, 3), guides res_x * res_y records; `samples` = Film.samples
+ * in FilmTile.index order (ceil(res_x / tile_dim) * ceil(res_y / tile_dim) entries) or NULL for a film that does not
+ * accumulate.  ctx NULL = the host instance on the CPU, else on ctx's device (synchronous).  out_rgb may equal film_rgb.
+ * YK_ERR_INVALID_ARGUMENT: iterations > 8, a sigma that is <= 0 or NaN, a NULL pointer, a zero resolution, tile_dim 0,
+ * guides that overlap the output, an output that overlaps the film without being equal to it. */
+yk_status yk_denoise(yk_context* ctx, const yk_denoise_desc* desc, const float* film_rgb, const yk_guide* guides, uint16_t res_x,
+                     uint16_t res_y, uint16_t tile_dim, const uint32_t* samples, float* out_rgb);
+/* The same on device buffers, enqueued on `stream` (NULL = the context's) without waiting for the device: one launch per
+ * iteration.  `samples` is a HOST table (copied before the call returns, through the same pinned staging as the tone
+ * map's).  The two ping-pong buffers between iterations (16 bytes a pixel each) belong to the context: allocated on first
+ * use and again when a larger film comes.  d_film_rgb and d_out_rgb need 4-byte alignment, d_guides 16-byte alignment
+ * (anything else: YK_ERR_INVALID_ARGUMENT, nothing is launched).  d_out_rgb may equal d_film_rgb.
+ * Context option "denoise_lds_max_step" (0, 1 or 2, default 2): iterations with a step up to it stage their taps in LDS. */
+yk_status yk_denoise_device(yk_context* ctx, const yk_denoise_desc* desc, const void* d_film_rgb, const void* d_guides, uint16_t res_x,
+                            uint16_t res_y, uint16_t tile_dim, const uint32_t* samples, void* d_out_rgb, void* stream);
 
 /* ---- per-stage entry points (parity tests, profiling) ------------------------- */
 /* BoundingVolumeHierarchy::intersect (bvh.rs:160-232) for n host rays.

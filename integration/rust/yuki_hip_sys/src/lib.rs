@@ -195,6 +195,26 @@ pub struct yk_present_desc {
     pub format: u32,
 }
 
+/// First-hit geometry of the ray through a pixel centre: what the denoiser's stops read (yuki_amd/csrc/yk_denoise.h)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct yk_guide {
+    pub ns: [f32; 3],
+    pub hit: f32,
+    pub p: [f32; 3],
+    pub t: f32,
+}
+
+/// The à-trous iterations (0 ..= 8) and the colour, normal and plane-distance stops; +inf switches a stop off
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct yk_denoise_desc {
+    pub iterations: u32,
+    pub sigma_color: f32,
+    pub sigma_normal: f32,
+    pub sigma_plane: f32,
+}
+
 /// The target rectangle of ScaleOutput::draw in top-down window coordinates
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -390,6 +410,10 @@ extern "C" {
     pub fn yk_present_target_rect(res_x: u16, res_y: u16, window_x: u16, window_y: u16, out: *mut yk_present_rect) -> yk_status;
     pub fn yk_present(ctx: *mut yk_context, desc: *const yk_present_desc, film_rgb: *const f32, res_x: u16, res_y: u16, out: *mut c_void) -> yk_status;
     pub fn yk_present_device(ctx: *mut yk_context, desc: *const yk_present_desc, d_film_rgb: *const c_void, res_x: u16, res_y: u16, d_out: *mut c_void, stream: *mut c_void) -> yk_status;
+    pub fn yk_render_guides(ctx: *mut yk_context, scene: *const yk_scene, camera: *const yk_camera, res_x: u16, res_y: u16, out: *mut yk_guide) -> yk_status;
+    pub fn yk_render_guides_device(ctx: *mut yk_context, scene: *const yk_scene, camera: *const yk_camera, res_x: u16, res_y: u16, d_guides: *mut c_void, stream: *mut c_void) -> yk_status;
+    pub fn yk_denoise(ctx: *mut yk_context, desc: *const yk_denoise_desc, film_rgb: *const f32, guides: *const yk_guide, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, out_rgb: *mut f32) -> yk_status;
+    pub fn yk_denoise_device(ctx: *mut yk_context, desc: *const yk_denoise_desc, d_film_rgb: *const c_void, d_guides: *const c_void, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, d_out_rgb: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_write_png(path: *const c_char, width: u32, height: u32, channels: u32, pixels: *const u8) -> yk_status;
     pub fn yk_render_tile(ctx: *mut yk_context, scene: *const yk_scene, camera: *const yk_camera, sampler: *const yk_sampler_desc, integrator: *const yk_integrator_desc, tile: *const yk_tile, tile_pixels: *mut f32, out_rays: *mut u64) -> yk_status;
     pub fn yk_film_update_tiles_device(ctx: *mut yk_context, tiles: *const yk_tile, n_tiles: usize, d_tile_rgb: *const c_void, res_x: u16, res_y: u16, d_film_rgb: *mut c_void, stream: *mut c_void) -> yk_status;

@@ -166,6 +166,10 @@ SYMBOLS = {
     "yk_present_target_rect": (C.c_int, [C.c_uint16, C.c_uint16, C.c_uint16, C.c_uint16, C.POINTER(abi.PresentRect)]),
     "yk_present": (C.c_int, [vp, C.POINTER(abi.PresentDesc), vp, C.c_uint16, C.c_uint16, vp]),
     "yk_present_device": (C.c_int, [vp, C.POINTER(abi.PresentDesc), vp, C.c_uint16, C.c_uint16, vp, vp]),
+    "yk_render_guides": (C.c_int, [vp, vp, C.POINTER(abi.CameraMatrices), C.c_uint16, C.c_uint16, vp]),
+    "yk_render_guides_device": (C.c_int, [vp, vp, C.POINTER(abi.CameraMatrices), C.c_uint16, C.c_uint16, vp, vp]),
+    "yk_denoise": (C.c_int, [vp, C.POINTER(abi.DenoiseDesc), vp, vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp]),
+    "yk_denoise_device": (C.c_int, [vp, C.POINTER(abi.DenoiseDesc), vp, vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp]),
     "yk_write_png": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
     # several GPUs
     "yk_multi_create": (C.c_int, [C.POINTER(C.c_int), C.c_uint32, C.POINTER(vp)]),

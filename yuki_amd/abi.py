@@ -126,6 +126,12 @@ class PresentRect(C.Structure):
     _fields_ = [("x0", C.c_int32), ("y0", C.c_int32), ("width", C.c_uint32), ("height", C.c_uint32)]
 
 
+class DenoiseDesc(C.Structure):
+    """yk_denoise_desc: the à-trous iterations and the three stops (csrc/yk_denoise.h)."""
+
+    _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float)]
+
+
 class IntegratorRay(C.Structure):
     """yk_integrator_ray: IntegratorRay (integrators/mod.rs:76-80), the ray and its yk_ray_type."""
 
@@ -181,6 +187,7 @@ BVH_NODE_DTYPE = np.dtype(
 TILE_DTYPE = np.dtype([("x0", "<u2"), ("y0", "<u2"), ("x1", "<u2"), ("y1", "<u2")])
 INTEGRATOR_RAY_DTYPE = np.dtype([("o", "<f4", 3), ("d", "<f4", 3), ("t_max", "<f4"), ("ray_type", "<u4")])
 OVERLAY_LINE_DTYPE = np.dtype([("p0", "<f4", 3), ("p1", "<f4", 3), ("rgb", "<f4", 3)])  # yk_overlay_line, 36 bytes
+GUIDE_DTYPE = np.dtype([("ns", "<f4", 3), ("hit", "<f4"), ("p", "<f4", 3), ("t", "<f4")])  # yk_guide, 32 bytes
 
 # enums (include/yuki_hip.h)
 SPLIT_SAH, SPLIT_MIDDLE, SPLIT_EQUAL_COUNTS = 0, 1, 2

@@ -207,13 +207,85 @@ def find_min_max(film, channel, ctx=None):
     return float(out[0]), float(out[1])
 
 
-def write_output(path, film, tone_map=None, settings=None, samples=None, ctx=None):
+# --------------------------------------------------------------------------- denoise
+@dataclass
+class DenoiseParams:
+    """yk_denoise_desc: the à-trous iterations (0 .. 8) and the colour, normal and plane-distance stops of
+    csrc/yk_denoise.h; float("inf") switches a stop off.  sigma_plane is in scene units: None stands for "no plane stop"
+    (+inf); DenoiseParams.for_scene scales it to the scene."""
+
+    iterations: int = 5
+    sigma_color: float = 4.0
+    sigma_normal: float = 0.3
+    sigma_plane: float = None
+
+    @staticmethod
+    def for_scene(scene, **kw):
+        """sigma_plane = 0.01 x the diagonal of the scene's bounds (Scene.info())."""
+        i = scene.info()
+        diag = float(np.linalg.norm(np.array(i.bounds_max[:], dtype=np.float64) - np.array(i.bounds_min[:], dtype=np.float64)))
+        return DenoiseParams(sigma_plane=0.01 * diag, **kw)
+
+    def as_struct(self):
+        return abi.DenoiseDesc(int(self.iterations), float(self.sigma_color), float(self.sigma_normal), float("inf") if self.sigma_plane is None else float(self.sigma_plane))
+
+
+def _denoise_args(res, params, guides, tile_dim, samples):
+    if not isinstance(params, DenoiseParams):
+        raise TypeError("params is a DenoiseParams")
+    if samples is not None:
+        samples = np.ascontiguousarray(samples, dtype=np.uint32)
+        if int(tile_dim) > 0 and samples.size != _table_len(res, int(tile_dim)):
+            raise ValueError(f"samples has {samples.size} entries, the film's tile grid {_table_len(res, int(tile_dim))}")
+    if guides is not None:
+        guides = np.ascontiguousarray(guides, dtype=abi.GUIDE_DTYPE)
+        if guides.size != int(res[0]) * int(res[1]):
+            raise ValueError("one guide record per film pixel")
+    return params.as_struct(), guides, samples
+
+
+def render_guides(ctx, scene, camera, film_settings):
+    """yk_render_guides: the first-hit geometry of the ray through every pixel centre as an (h, w) array of
+    abi.GUIDE_DTYPE records (ns, hit, p, t); a miss is an all-zero record."""
+    w, h = film_settings.res
+    out = np.zeros((h, w), dtype=abi.GUIDE_DTYPE)
+    check(lib().yk_render_guides(ctx.h, scene.h, C.byref(camera.matrices), w, h, _p(out)), ctx.h)
+    return out
+
+
+def denoise(film, guides, params, tile_dim=16, samples=None, ctx=None):
+    """yk_denoise: the edge-avoiding à-trous filter of csrc/yk_denoise.h over an (h, w, 3) float32 film under (h, w)
+    guides; `samples` = Film.samples (film_samples) for an accumulating film, whose sums are normalised first.  Returns the
+    new film; ctx None = the host instance."""
+    film = np.ascontiguousarray(film, dtype=np.float32)
+    if film.ndim != 3 or film.shape[2] != 3:
+        raise ValueError("film is (h, w, 3)")
+    h, w = film.shape[0], film.shape[1]
+    d, guides, samples = _denoise_args((w, h), params, guides, tile_dim, samples)
+    out = np.empty_like(film)
+    c = ctx.h if ctx else None
+    check(lib().yk_denoise(c, C.byref(d), _p(film), _p(guides), w, h, int(tile_dim), _p(samples), _p(out)), c)
+    return out
+
+
+def _denoise_for_output(film, denoise_params, guides, tile_dim, samples, ctx):
+    """The denoise step of write_output / write_preview: (film, samples) for the tone map that follows — the denoised film
+    is normalised already, so it goes on without the sample table."""
+    if denoise_params is None:
+        return film, samples
+    if guides is None:
+        raise ValueError("denoise needs guides (render_guides)")
+    return denoise(film, guides, denoise_params, tile_dim, samples, ctx), None
+
+
+def write_output(path, film, tone_map=None, settings=None, samples=None, ctx=None, denoise=None, guides=None):
     """The Finished branch of app/headless.rs:62-84: Raw writes the film as it is, anything else writes the tone-mapped
     film (a Heatmap without bounds finds them first).  tone_map None = ToneMapType.default(); settings None = a film of the
-    array's size with the default tile_dim."""
+    array's size with the default tile_dim.  denoise (a DenoiseParams) with guides: the film is denoised first."""
     film = np.ascontiguousarray(film, dtype=np.float32)
     tone_map = ToneMapType.default() if tone_map is None else tone_map
     settings = settings or FilmSettings(res=(film.shape[1], film.shape[0]))
+    film, samples = _denoise_for_output(film, denoise, guides, film_tile_dim(settings), samples, ctx)
     if tone_map.kind == abi.TONE_MAP_RAW:
         write_exr(path, film)
         return
@@ -323,12 +395,14 @@ def write_png(path, pixels):
     check(lib().yk_write_png(str(path).encode(), pixels.shape[1], pixels.shape[0], pixels.shape[2], _p(pixels)))
 
 
-def write_preview(path, film, tone_map=None, settings=None, samples=None, window=None, ctx=None):
-    """What the window shows, as a PNG: the tone map (as write_output: None = ToneMapType.default(), Raw = none), then
-    present into `window` (default: the film's size) as an sRGB back buffer stores it (encode 2), then write_png."""
+def write_preview(path, film, tone_map=None, settings=None, samples=None, window=None, ctx=None, denoise=None, guides=None):
+    """What the window shows, as a PNG: the denoiser when `denoise` (a DenoiseParams) and `guides` are given, the tone map
+    (as write_output: None = ToneMapType.default(), Raw = none), then present into `window` (default: the film's size) as
+    an sRGB back buffer stores it (encode 2), then write_png."""
     film = np.ascontiguousarray(film, dtype=np.float32)
     tone_map = ToneMapType.default() if tone_map is None else tone_map
     settings = settings or FilmSettings(res=(film.shape[1], film.shape[0]))
+    film, samples = _denoise_for_output(film, denoise, guides, film_tile_dim(settings), samples, ctx)
     if tone_map.kind != abi.TONE_MAP_RAW:
         film = _apply_tone_map(film, tone_map, film_tile_dim(settings), samples, ctx, None)
     window = (film.shape[1], film.shape[0]) if window is None else window
@@ -488,6 +562,17 @@ class Context:
         allocation.  Both pointers need 4-byte alignment."""
         d = _present_desc(window, encode, fmt)
         check(lib().yk_present_device(self.h, C.byref(d), C.c_void_p(d_film_ptr), int(res[0]), int(res[1]), C.c_void_p(d_out_ptr), C.c_void_p(stream) if stream else None), self.h)
+
+    def render_guides_device(self, scene, camera, res, d_guides_ptr, stream=None):
+        """yk_render_guides_device: res[0] * res[1] yk_guide records (32 bytes each, 16-byte aligned) into device memory,
+        ordered on `stream` (default: the context's) without waiting on the host."""
+        check(lib().yk_render_guides_device(self.h, scene.h, C.byref(camera.matrices), int(res[0]), int(res[1]), C.c_void_p(d_guides_ptr), C.c_void_p(stream) if stream else None), self.h)
+
+    def denoise_device(self, d_film_ptr, d_guides_ptr, res, params, tile_dim, samples, d_out_ptr, stream=None):
+        """yk_denoise_device: device film + device guides -> device out (may be the film), enqueued on `stream` (default:
+        the context's) without waiting; `samples` is a host table (or None), copied before the call returns."""
+        d, _, samples = _denoise_args(res, params, None, tile_dim, samples)
+        check(lib().yk_denoise_device(self.h, C.byref(d), C.c_void_p(d_film_ptr), C.c_void_p(d_guides_ptr), int(res[0]), int(res[1]), int(tile_dim), _p(samples), C.c_void_p(d_out_ptr), C.c_void_p(stream) if stream else None), self.h)
 
     @property
     def stream_handle(self):

@@ -119,6 +119,9 @@ void yk_context_destroy(yk_context* ctx) {
     ctx->tonemap.bounds.release();
     ctx->tonemap.samples.release();
     ctx->overlay.ids.release();
+    ctx->denoise.ping[0].release();
+    ctx->denoise.ping[1].release();
+    ctx->denoise.samples.release();
     if (ctx->tonemap.staging) (void)hipHostFree(ctx->tonemap.staging);
     if (ctx->tonemap.staged) (void)hipEventDestroy(ctx->tonemap.staged);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
@@ -183,6 +186,9 @@ yk_status yk_context_set_option(yk_context* ctx, const char* key, int64_t value)
     } else if (k == "overlay_coop_min") {
         if (value < 1 || value > 65536) return YK_ERR_INVALID_ARGUMENT;
         ctx->overlay.coop_min = value;
+    } else if (k == "denoise_lds_max_step") {
+        if (value < 0 || value > 2) return YK_ERR_INVALID_ARGUMENT;
+        ctx->denoise.lds_max_step = value;
     } else if (k == "time_kernels") {
         ctx->time_kernels = value;
     } else {

@@ -1,0 +1,296 @@
+// yk_denoise.hip — the edge-avoiding à-trous filter on gfx950, behind yk_denoise and yk_denoise_device; the per-pixel
+// arithmetic is yk_denoise.h's, whose host instance these entry points run without a context.
+//
+// One launch per iteration, one lane per pixel, a block is a DN_TX x DN_TY tile of the film (a wave covers two rows of 32
+// pixels).  Iteration 0 reads the RGB film (dword loads: 4-byte alignment) and normalises it by the sample table, the last
+// iteration writes RGB, the ones in between move 16-byte colour records between the context's two ping-pong buffers; a
+// guide record is two 16-byte loads.  A tap is 48 bytes, 25 of them a pixel, nearly all re-read from cache.  Two variants
+// of the tap fetch (k_atrous<.., S>):
+//   S == 0: every tap from global memory;
+//   S == 1, 2: the block first stages the colours (normalised once per staged pixel) and guides of its tile plus a halo
+//     of 2*S pixels in LDS, and the taps are ds_read_b128s — for the steps whose halo is small against the tile.
+// "denoise_lds_max_step" picks the variant per step (the measurement that chose the default).
+// Everything the pass needs on the device (ping-pong buffers, staged sample table) is grown in the context on first use;
+// after that the stream-ordered entry point does not allocate.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <vector>
+
+#include "yk_denoise.h"
+#include "yk_internal.h"
+
+namespace {
+
+constexpr unsigned DN_TX = 32, DN_TY = 8;  // 256 lanes: 4 waves of 64
+
+struct DnIo {
+    const float* film;        // iteration 0: the RGB film ...
+    const uint32_t* samples;  // ... and its sample table (may be NULL)
+    const float4* in;         // later iterations: the previous iteration's colour records
+    const float4* guides;     // two float4 a pixel: (ns, hit), (p, t)
+    float4* out;              // colour records, or ...
+    float* out_rgb;           // ... the last iteration's RGB
+};
+
+template <bool IN_RGB>
+__device__ __forceinline__ void dn_load_color(const DnParams& a, const DnIo& io, uint32_t x, uint32_t y, float* c) {
+    const size_t i = (size_t)y * a.res_x + x;
+    if (IN_RGB) {
+        c[0] = io.film[3 * i];
+        c[1] = io.film[3 * i + 1];
+        c[2] = io.film[3 * i + 2];
+        dn_normalise(dn_count(a, io.samples, x, y), c);
+    } else {
+        const float4 v = io.in[i];
+        c[0] = v.x;
+        c[1] = v.y;
+        c[2] = v.z;
+    }
+}
+
+__device__ __forceinline__ void dn_set_guide(DnTap& t, float4 ga, float4 gb) {
+    t.ns[0] = ga.x;
+    t.ns[1] = ga.y;
+    t.ns[2] = ga.z;
+    t.hit = ga.w;
+    t.p[0] = gb.x;
+    t.p[1] = gb.y;
+    t.p[2] = gb.z;
+}
+
+// The film, the records and the output of one launch never overlap (enqueue sees to it), the guides are only read.
+template <bool IN_RGB, bool OUT_RGB, int S>
+__global__ __launch_bounds__(DN_TX* DN_TY) void k_atrous(DnIo io, DnParams a, float den_c, int step) {
+    const uint32_t x0 = blockIdx.x * DN_TX, y0 = blockIdx.y * DN_TY;
+    const uint32_t x = x0 + threadIdx.x, y = y0 + threadIdx.y;
+    const bool inside = x < a.res_x && y < a.res_y;
+    float rgb[3] = {0.0f, 0.0f, 0.0f};
+    if (S == 0) {
+        if (!inside) return;
+        dn_pixel(a, den_c, step, x, y,
+                 [&](uint32_t qx, uint32_t qy, DnTap& t) {
+                     dn_load_color<IN_RGB>(a, io, qx, qy, t.c);
+                     const size_t i = (size_t)qy * a.res_x + qx;
+                     dn_set_guide(t, io.guides[2 * i], io.guides[2 * i + 1]);
+                 },
+                 rgb);
+    } else {
+        constexpr int H = 2 * S, W = (int)DN_TX + 2 * H, ROWS = (int)DN_TY + 2 * H;
+        __shared__ float4 lds_c[W * ROWS], lds_a[W * ROWS], lds_b[W * ROWS];
+        const int bx = (int)x0 - H, by = (int)y0 - H;
+        for (int k = (int)(threadIdx.y * DN_TX + threadIdx.x); k < W * ROWS; k += (int)(DN_TX * DN_TY)) {
+            const int gx = bx + k % W, gy = by + k / W;
+            if (gx < 0 || gy < 0 || gx >= (int)a.res_x || gy >= (int)a.res_y) continue;  // never read: taps outside the film are skipped
+            float c[3];
+            dn_load_color<IN_RGB>(a, io, (uint32_t)gx, (uint32_t)gy, c);
+            const size_t i = (size_t)gy * a.res_x + (size_t)gx;
+            lds_c[k] = make_float4(c[0], c[1], c[2], 0.0f);
+            lds_a[k] = io.guides[2 * i];
+            lds_b[k] = io.guides[2 * i + 1];
+        }
+        __syncthreads();
+        if (!inside) return;
+        dn_pixel(a, den_c, S, x, y,
+                 [&](uint32_t qx, uint32_t qy, DnTap& t) {
+                     const int k = ((int)qy - by) * W + ((int)qx - bx);
+                     const float4 v = lds_c[k];
+                     t.c[0] = v.x;
+                     t.c[1] = v.y;
+                     t.c[2] = v.z;
+                     dn_set_guide(t, lds_a[k], lds_b[k]);
+                 },
+                 rgb);
+    }
+    const size_t i = (size_t)y * a.res_x + x;
+    if (OUT_RGB) {
+        io.out_rgb[3 * i] = rgb[0];
+        io.out_rgb[3 * i + 1] = rgb[1];
+        io.out_rgb[3 * i + 2] = rgb[2];
+    } else {
+        io.out[i] = make_float4(rgb[0], rgb[1], rgb[2], 0.0f);
+    }
+}
+
+// The normalised film as colour records (a one-iteration denoise in place) or as RGB (iterations == 0; out_rgb may be the
+// film: a lane reads its pixel before it writes it and touches no other).
+__global__ __launch_bounds__(256) void k_dn_normalise(DnIo io, DnParams a) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.res_x * a.res_y) return;
+    const uint32_t y = i / a.res_x, x = i - y * a.res_x;
+    float c[3];
+    dn_load_color<true>(a, io, x, y, c);
+    if (io.out_rgb) {
+        io.out_rgb[3 * (size_t)i] = c[0];
+        io.out_rgb[3 * (size_t)i + 1] = c[1];
+        io.out_rgb[3 * (size_t)i + 2] = c[2];
+    } else {
+        io.out[i] = make_float4(c[0], c[1], c[2], 0.0f);
+    }
+}
+
+template <bool IN_RGB, bool OUT_RGB>
+void launch_atrous(hipStream_t st, int variant, const DnIo& io, const DnParams& a, float den_c, int step) {
+    const dim3 grid((a.res_x + DN_TX - 1) / DN_TX, (a.res_y + DN_TY - 1) / DN_TY), block(DN_TX, DN_TY);
+    if (variant == 1) hipLaunchKernelGGL((k_atrous<IN_RGB, OUT_RGB, 1>), grid, block, 0, st, io, a, den_c, step);
+    else if (variant == 2) hipLaunchKernelGGL((k_atrous<IN_RGB, OUT_RGB, 2>), grid, block, 0, st, io, a, den_c, step);
+    else hipLaunchKernelGGL((k_atrous<IN_RGB, OUT_RGB, 0>), grid, block, 0, st, io, a, den_c, step);
+}
+
+bool overlaps(const void* p, size_t np, const void* q, size_t nq) {
+    const uintptr_t p0 = (uintptr_t)p, q0 = (uintptr_t)q;
+    return p0 < q0 + nq && q0 < p0 + np;
+}
+
+yk_status check_call(const yk_denoise_desc* d, const void* film, const void* guides, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const void* out) {
+    if (!d || !film || !guides || !out || res_x == 0 || res_y == 0 || tile_dim == 0) return YK_ERR_INVALID_ARGUMENT;
+    if (d->iterations > DN_MAX_ITERATIONS) return YK_ERR_INVALID_ARGUMENT;
+    if (!(d->sigma_color > 0.0f) || !(d->sigma_normal > 0.0f) || !(d->sigma_plane > 0.0f)) return YK_ERR_INVALID_ARGUMENT;  // <= 0 or NaN
+    const size_t n_px = (size_t)res_x * res_y;
+    if (overlaps(guides, n_px * sizeof(yk_guide), out, n_px * 12)) return YK_ERR_INVALID_ARGUMENT;
+    if (out != film && overlaps(film, n_px * 12, out, n_px * 12)) return YK_ERR_INVALID_ARGUMENT;
+    return YK_OK;
+}
+
+DnParams make_params(const yk_denoise_desc* d, uint16_t res_x, uint16_t res_y, uint16_t tile_dim) {
+    DnParams a;
+    a.res_x = res_x;
+    a.res_y = res_y;
+    a.tile_dim = tile_dim;
+    a.x_tile_count = res_x / tile_dim;
+    a.sigma_color = d->sigma_color;
+    a.den_n = d->sigma_normal * d->sigma_normal;
+    a.den_p = d->sigma_plane * d->sigma_plane;
+    return a;
+}
+
+size_t table_words(uint16_t res_x, uint16_t res_y, uint16_t tile_dim) {
+    return (size_t)((res_x + tile_dim - 1) / tile_dim) * (size_t)((res_y + tile_dim - 1) / tile_dim);
+}
+
+// The device passes on `st`.
+yk_status enqueue(yk_context* ctx, hipStream_t st, const yk_denoise_desc* d, const float* film, const void* guides, uint16_t res_x, uint16_t res_y, uint16_t tile_dim,
+                  const uint32_t* samples, float* out) {
+    const uint32_t n_px = (uint32_t)res_x * res_y;
+    auto& dn = ctx->denoise;
+    const DnParams a = make_params(d, res_x, res_y, tile_dim);
+    DnIo io{};
+    io.film = film;
+    io.guides = reinterpret_cast<const float4*>(guides);
+    if (samples) {
+        yk_status ss = stage_sample_table(ctx, st, samples, table_words(res_x, res_y, tile_dim), dn.samples);
+        if (ss != YK_OK) return ss;
+        io.samples = dn.samples.as<const uint32_t>();
+    }
+    if (d->iterations == 0) {
+        if (samples) {
+            io.out_rgb = out;
+            hipLaunchKernelGGL(k_dn_normalise, dim3((n_px - 1) / 256 + 1), dim3(256), 0, st, io, a);
+        } else if (film != out) {
+            HIP_TRY(ctx, hipMemcpyAsync(out, film, (size_t)n_px * 12, hipMemcpyDeviceToDevice, st));
+        }
+        HIP_TRY(ctx, hipGetLastError());
+        return YK_OK;
+    }
+    uint32_t n_it = d->iterations;
+    const bool in_place_single = n_it == 1 && film == out;  // the one launch would read the film while it writes it
+    if (n_it > 1 || in_place_single) {
+        HIP_TRY(ctx, dn.ping[0].ensure((size_t)n_px * 16));
+        if (n_it > 2) HIP_TRY(ctx, dn.ping[1].ensure((size_t)n_px * 16));
+    }
+    bool in_rgb = true;
+    int src = -1;  // which ping-pong buffer holds the previous iteration's colours
+    if (in_place_single) {
+        io.out = dn.ping[0].as<float4>();
+        hipLaunchKernelGGL(k_dn_normalise, dim3((n_px - 1) / 256 + 1), dim3(256), 0, st, io, a);
+        in_rgb = false;
+        src = 0;
+    }
+    for (uint32_t i = 0; i < n_it; ++i) {
+        const int step = 1 << i;
+        const int variant = step <= (int)dn.lds_max_step ? step : 0;
+        const float den_c = dn_color_denominator(a.sigma_color, i);
+        const bool last = i + 1 == n_it;
+        const int dst = src == 0 ? 1 : 0;
+        io.in = src >= 0 ? dn.ping[src].as<const float4>() : nullptr;
+        io.out = last ? nullptr : dn.ping[dst].as<float4>();
+        io.out_rgb = last ? out : nullptr;
+        if (in_rgb && last) launch_atrous<true, true>(st, variant, io, a, den_c, step);
+        else if (in_rgb) launch_atrous<true, false>(st, variant, io, a, den_c, step);
+        else if (last) launch_atrous<false, true>(st, variant, io, a, den_c, step);
+        else launch_atrous<false, false>(st, variant, io, a, den_c, step);
+        in_rgb = false;
+        src = dst;
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return YK_OK;
+}
+
+void denoise_host(const yk_denoise_desc* d, const float* film, const yk_guide* guides, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const uint32_t* samples,
+                  float* out) {
+    const DnParams a = make_params(d, res_x, res_y, tile_dim);
+    const size_t n_px = (size_t)res_x * res_y;
+    std::vector<float> cur(3 * n_px), nxt(d->iterations ? 3 * n_px : 0);
+    for (uint32_t y = 0; y < res_y; ++y)
+        for (uint32_t x = 0; x < res_x; ++x) {
+            const size_t i = (size_t)y * res_x + x;
+            std::memcpy(&cur[3 * i], film + 3 * i, 12);
+            dn_normalise(dn_count(a, samples, x, y), &cur[3 * i]);
+        }
+    for (uint32_t it = 0; it < d->iterations; ++it) {
+        const float den_c = dn_color_denominator(a.sigma_color, it);
+        const auto fetch = [&](uint32_t qx, uint32_t qy, DnTap& t) {
+            const size_t i = (size_t)qy * res_x + qx;
+            std::memcpy(t.c, &cur[3 * i], 12);
+            std::memcpy(t.ns, guides[i].ns, 12);
+            t.hit = guides[i].hit;
+            std::memcpy(t.p, guides[i].p, 12);
+        };
+        for (uint32_t y = 0; y < res_y; ++y)
+            for (uint32_t x = 0; x < res_x; ++x) dn_pixel(a, den_c, 1 << it, x, y, fetch, &nxt[3 * ((size_t)y * res_x + x)]);
+        cur.swap(nxt);
+    }
+    std::memcpy(out, cur.data(), 12 * n_px);
+}
+
+}  // namespace
+
+extern "C" {
+
+yk_status yk_denoise(yk_context* ctx, const yk_denoise_desc* desc, const float* film_rgb, const yk_guide* guides, uint16_t res_x, uint16_t res_y, uint16_t tile_dim,
+                     const uint32_t* samples, float* out_rgb) try {
+    if (check_call(desc, film_rgb, guides, res_x, res_y, tile_dim, out_rgb) != YK_OK) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_denoise: bad argument");
+    if (!ctx) {  // the host instance
+        denoise_host(desc, film_rgb, guides, res_x, res_y, tile_dim, samples, out_rgb);
+        return YK_OK;
+    }
+    YK_LOCK(ctx);
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    const size_t n_px = (size_t)res_x * res_y;
+    HIP_TRY(ctx, ctx->scratch[4].ensure(n_px * 12));
+    HIP_TRY(ctx, ctx->scratch[5].ensure(n_px * 12));
+    HIP_TRY(ctx, ctx->scratch[6].ensure(n_px * sizeof(yk_guide)));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[4].p, film_rgb, n_px * 12, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[6].p, guides, n_px * sizeof(yk_guide), hipMemcpyHostToDevice, st));
+    yk_status s = enqueue(ctx, st, desc, ctx->scratch[4].as<const float>(), ctx->scratch[6].p, res_x, res_y, tile_dim, samples, ctx->scratch[5].as<float>());
+    if (s != YK_OK) return s;
+    HIP_TRY(ctx, hipMemcpyAsync(out_rgb, ctx->scratch[5].p, n_px * 12, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return YK_OK;
+} YK_CATCH(ctx)
+
+yk_status yk_denoise_device(yk_context* ctx, const yk_denoise_desc* desc, const void* d_film_rgb, const void* d_guides, uint16_t res_x, uint16_t res_y, uint16_t tile_dim,
+                            const uint32_t* samples, void* d_out_rgb, void* stream) {
+    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
+    YK_LOCK(ctx);
+    if (check_call(desc, d_film_rgb, d_guides, res_x, res_y, tile_dim, d_out_rgb) != YK_OK) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_denoise_device: bad argument");
+    // dword loads and stores of the film and the output, 16-byte loads of the guides
+    if (((uintptr_t)d_film_rgb & 3u) || ((uintptr_t)d_out_rgb & 3u) || ((uintptr_t)d_guides & 15u))
+        return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_denoise_device: film and output must be 4-byte aligned, guides 16-byte aligned");
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    return enqueue(ctx, st, desc, reinterpret_cast<const float*>(d_film_rgb), d_guides, res_x, res_y, tile_dim, samples, reinterpret_cast<float*>(d_out_rgb));
+}
+
+}  // extern "C"

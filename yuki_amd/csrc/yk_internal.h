@@ -115,6 +115,12 @@ struct yk_context {
         size_t staging_words = 0;
         hipEvent_t staged = nullptr;       // the latest upload out of `staging`
     } tonemap;
+    // the denoiser's buffers (yk_denoise.hip), grown on first use and again when a larger film comes
+    struct DenoiseState {
+        DevBuf ping[2];   // the colours between two iterations, 16 bytes a pixel each
+        DevBuf samples;   // the sample table on the device (staged through the tone map's pinned copy)
+        int64_t lds_max_step = 2;  // "denoise_lds_max_step": iterations with a step up to this (0, 1 or 2) stage their taps in LDS (the measurement that chose 2)
+    } denoise;
     // the overlay pass's buffers (yk_overlay.hip), grown on first use
     struct OverlayState {
         DevBuf ids;        // one u32 a pixel: the winning ordinal + 1
@@ -261,6 +267,12 @@ hipError_t enqueue_geometry_checks(hipStream_t st, const inp::Geometry& g, const
 // when a triangle has a coordinate that is not finite.
 hipError_t enqueue_shape_bounds(hipStream_t st, const float* d_points, const uint32_t* d_indices, const uint32_t* d_order, const float* d_sphere_bounds, uint32_t n_triangles, uint32_t n_shapes, float* d_sb,
                                 inp::CheckWords* d_words);
+
+// ------------------------------------------------------------------ yk_tonemap.hip
+// A host sample table (Film.samples, `words` entries) -> `dst` on the device, enqueued on `st`.  It goes through the
+// context's pinned staging (tonemap.staging), so the upload is truly asynchronous; the staging is rewritten only once the
+// previous upload out of it has run.
+yk_status stage_sample_table(yk_context* ctx, hipStream_t st, const uint32_t* samples, size_t words, DevBuf& dst);
 
 // ------------------------------------------------------------------ yk_scene.cpp
 // The exact sizes of a scene's seven record buffers (s->record_bytes) and the head of s->layout from what was laid out,

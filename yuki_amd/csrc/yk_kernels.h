@@ -51,6 +51,8 @@ void launch_film_scatter(hipStream_t s, const uint32_t* pixel_xy, uint32_t n_pix
                          uint32_t n_passes = 1, size_t pass_stride = 0);
 void launch_debug_shade(hipStream_t s, const DevScene& sc, uint32_t integrator, PathBuffers cur, const int* hit_tri, const uint4* stats, uint32_t n,
                         float4* sample_buf);
+// the guide pass (yk_render_guides): one yk_guide record (two float4) per traced camera ray, at its pixel of a res_x-wide film
+void launch_guides(hipStream_t s, const DevScene& sc, PathBuffers cur, const int* hit_tri, uint32_t n, const uint32_t* pixel_xy, uint32_t res_x, float4* guides);
 void launch_device_math(hipStream_t s, int fn, size_t n, const float* a, const float* b, float* out);
 void launch_sampler_sequence(hipStream_t s, const SamplerCfg& cfg, uint32_t px, uint32_t py, uint32_t sample_index, const uint8_t* dims, size_t n_draws,
                              float* out);

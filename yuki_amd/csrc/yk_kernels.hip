@@ -594,6 +594,27 @@ __global__ void k_debug_shade(DevScene sc, uint32_t integrator, PathBuffers cur,
     sample_buf[sid] = make_float4(c.r, c.g, c.b, 0.0f);
 }
 
+// The guide pass (yk_render_guides): the first-hit geometry of one camera ray per pixel as a yk_guide record — (ns, hit),
+// (p, t) — at the pixel's place of a row-major res_x-wide film; a miss is an all-zero record.  One sample per pixel: the
+// ray's sample id is its pixel's index in pixel_xy.
+__global__ void k_guides(DevScene sc, PathBuffers cur, const int* hit_tri, uint32_t n, const uint32_t* pixel_xy, uint32_t res_x, float4* guides) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 rd = cur.rayD[i];
+    const uint32_t xy = pixel_xy[__float_as_uint(rd.w)];
+    const size_t px = (size_t)(xy >> 16) * res_x + (xy & 0xffffu);
+    const int tri = hit_tri[i];
+    float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a;
+    if (tri >= 0) {
+        float t = 0.0f;
+        const Surface sf = hit_surface_prim(sc, (uint32_t)tri & YK_HIT_PRIM_MASK, f4_xyz(cur.rayO[i]), f4_xyz(rd), sc.texels != nullptr, &t);
+        a = make_float4(sf.ns.x, sf.ns.y, sf.ns.z, 1.0f);
+        b = make_float4(sf.p.x, sf.p.y, sf.p.z, t);
+    }
+    guides[2 * px] = a;
+    guides[2 * px + 1] = b;
+}
+
 // ------------------------------------------------------------------ unit-test kernels
 __global__ void k_device_math(int fn, size_t n, const float* a, const float* b, float* out) {
     size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
@@ -803,6 +824,9 @@ void launch_film_scatter(hipStream_t s, const uint32_t* pixel_xy, uint32_t n_pix
 void launch_debug_shade(hipStream_t s, const DevScene& sc, uint32_t integrator, PathBuffers cur, const int* hit_tri, const uint4* stats, uint32_t n,
                         float4* sample_buf) {
     hipLaunchKernelGGL(k_debug_shade, dim3(blocks_for(n, 256)), dim3(256), 0, s, sc, integrator, cur, hit_tri, stats, n, sample_buf);
+}
+void launch_guides(hipStream_t s, const DevScene& sc, PathBuffers cur, const int* hit_tri, uint32_t n, const uint32_t* pixel_xy, uint32_t res_x, float4* guides) {
+    hipLaunchKernelGGL(k_guides, dim3(blocks_for(n, 256)), dim3(256), 0, s, sc, cur, hit_tri, n, pixel_xy, res_x, guides);
 }
 void launch_device_math(hipStream_t s, int fn, size_t n, const float* a, const float* b, float* out) {
     hipLaunchKernelGGL(k_device_math, dim3(blocks_for(n, 256)), dim3(256), 0, s, fn, n, a, b, out);

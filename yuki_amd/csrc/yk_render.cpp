@@ -277,10 +277,13 @@ static bool wait_polling(yk_context* ctx, hipEvent_t done, hipStream_t st, yk_ca
 // Integrator::render for a list of tiles.  tile_samples == nullptr: the plain film (all
 // samples of a pixel, mean stored).  Otherwise the accumulating film (integrators/mod.rs:
 // 146-161): one sample per pixel with global index tile_samples[t], raw value stored.
+// guides_res_x != 0: the guide pass (yk_render_guides) — a debug integrator's trace, one sample a pixel; d_out_rgb is then
+// a row-major film of yk_guide records, guides_res_x wide, written by k_guides instead of the shade and resolve kernels.
 static yk_status render_tiles_impl(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler,
                                    const yk_integrator_desc* integrator, const yk_tile* tiles, const uint16_t* tile_samples, size_t n_tiles,
                                    void* d_out_rgb, void* stream, yk_render_stats* stats, yk_cancel_fn cancel, void* user,
-                                   const yk_tile_list* prepared = nullptr, uint32_t n_passes = 1, int64_t uniform_first_sample = -1) try {
+                                   const yk_tile_list* prepared = nullptr, uint32_t n_passes = 1, int64_t uniform_first_sample = -1,
+                                   uint32_t guides_res_x = 0) try {
     if (!ctx) return YK_ERR_INVALID_ARGUMENT;
     YK_LOCK(ctx);
     if (prepared) {
@@ -516,7 +519,8 @@ static yk_status render_tiles_impl(yk_context* ctx, const yk_scene* scene, const
                                      want_stats ? ctx->stats4.as<uint4>() : nullptr, ws.spill.as<uint2>(), trace_grid(ctx) * trace_block_size(), errblk,
                                      counters);
                 kt.end(e, 0, bs);
-                launch_debug_shade(bs, scene->dev, prm.integrator, pc, ws.hit.as<int>(), ctx->stats4.as<uint4>(), n, sample_buf);
+                if (guides_res_x) launch_guides(bs, scene->dev, pc, ws.hit.as<int>(), n, pixel_xy, guides_res_x, reinterpret_cast<float4*>(d_out_rgb));
+                else launch_debug_shade(bs, scene->dev, prm.integrator, pc, ws.hit.as<int>(), ctx->stats4.as<uint4>(), n, sample_buf);
                 ++n_trace;
             }
             if (cancel) {
@@ -529,7 +533,9 @@ static yk_status render_tiles_impl(yk_context* ctx, const yk_scene* scene, const
             HIP_TRY(ctx, hipEventRecord(ctx->ws[1].done, ctx->ws[1].stream));
             HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ws[1].done, 0));
         }
-        if (accumulating)  // raw values, pass-major over the whole tile list
+        if (guides_res_x)  // k_guides wrote every record at its pixel: nothing to resolve
+            ;
+        else if (accumulating)  // raw values, pass-major over the whole tile list
             launch_resolve_passes(st, sample_buf, npx, spp, out + 3 * (size_t)px0, 3 * (size_t)total_px);
         else
             launch_resolve(st, sample_buf, npx, spp, out + 3 * (size_t)px0);
@@ -777,6 +783,40 @@ static yk_status render_tiles_host(yk_context* ctx, const yk_scene* scene, const
 }
 
 extern "C" {
+
+// The guides: the ShadingNormals integrator's trace of the whole film as one tile under a 1 x 1 Stratified sampler without
+// jitter, whose camera sample is the pixel centre whatever its seed, so the ray is Camera::ray((x + 0.5, y + 0.5)).
+static yk_status render_guides(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, uint16_t res_x, uint16_t res_y, void* d_guides, void* stream) {
+    yk_sampler_desc smp = {};
+    smp.kind = YK_SAMPLER_STRATIFIED;
+    smp.nx = smp.ny = 1;
+    yk_integrator_desc integ = {};
+    integ.kind = YK_INTEGRATOR_SHADING_NORMALS;
+    const yk_tile film = {0, 0, res_x, res_y};
+    return render_tiles_impl(ctx, scene, camera, &smp, &integ, &film, nullptr, 1, d_guides, stream, nullptr, nullptr, nullptr, nullptr, 1, -1, res_x);
+}
+
+yk_status yk_render_guides_device(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, uint16_t res_x, uint16_t res_y, void* d_guides, void* stream) {
+    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
+    YK_LOCK(ctx);
+    if (!scene || !camera || !d_guides || res_x == 0 || res_y == 0) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_guides_device: bad argument");
+    if ((uintptr_t)d_guides & 15u) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_guides_device: guides must be 16-byte aligned");
+    return render_guides(ctx, scene, camera, res_x, res_y, d_guides, stream);
+}
+
+yk_status yk_render_guides(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, uint16_t res_x, uint16_t res_y, yk_guide* out) {
+    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
+    YK_LOCK(ctx);
+    if (!scene || !camera || !out || res_x == 0 || res_y == 0) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_guides: bad argument");
+    const size_t bytes = (size_t)res_x * res_y * sizeof(yk_guide);
+    (void)hipSetDevice(ctx->device);
+    HIP_TRY(ctx, ctx->scratch[0].ensure(bytes));
+    yk_status st = render_guides(ctx, scene, camera, res_x, res_y, ctx->scratch[0].p, nullptr);
+    if (st != YK_OK) return st;
+    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->scratch[0].p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return YK_OK;
+}
 
 yk_status yk_render_tile(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler,
                          const yk_integrator_desc* integrator, const yk_tile* tile, float* tile_pixels, uint64_t* out_rays) {

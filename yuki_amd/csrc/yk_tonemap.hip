@@ -148,6 +148,30 @@ size_t table_words(uint16_t res_x, uint16_t res_y, uint16_t tile_dim) {
     return (size_t)((res_x + tile_dim - 1) / tile_dim) * (size_t)((res_y + tile_dim - 1) / tile_dim);
 }
 
+}  // namespace
+
+// The caller's table is copied into pinned staging, so that the upload is truly asynchronous; the staging is rewritten only
+// once the previous call's upload out of it has run (normally long done).
+yk_status stage_sample_table(yk_context* ctx, hipStream_t st, const uint32_t* samples, size_t words, DevBuf& dst) {
+    auto& tm = ctx->tonemap;
+    HIP_TRY(ctx, dst.ensure(words * 4));
+    if (words > tm.staging_words) {
+        if (tm.staging) HIP_TRY(ctx, hipHostFree(tm.staging));
+        tm.staging = nullptr;
+        tm.staging_words = 0;
+        HIP_TRY(ctx, hipHostMalloc((void**)&tm.staging, words * 4, hipHostMallocDefault));
+        tm.staging_words = words;
+    }
+    if (!tm.staged) HIP_TRY(ctx, hipEventCreateWithFlags(&tm.staged, hipEventDisableTiming));
+    else HIP_TRY(ctx, hipEventSynchronize(tm.staged));
+    std::memcpy(tm.staging, samples, words * 4);
+    HIP_TRY(ctx, hipMemcpyAsync(dst.p, tm.staging, words * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipEventRecord(tm.staged, st));
+    return YK_OK;
+}
+
+namespace {
+
 // The device passes on `st`; a Heatmap without bounds leaves the bounds it found in the context's slot (tm.bounds).
 yk_status enqueue(yk_context* ctx, hipStream_t st, const yk_tone_map_desc* d, const float* film, uint16_t res_x, uint16_t res_y, uint16_t tile_dim,
                   const uint32_t* samples, float* out) {
@@ -168,22 +192,8 @@ yk_status enqueue(yk_context* ctx, hipStream_t st, const yk_tone_map_desc* d, co
         return YK_OK;
     }
     if (d->kind == YK_TONE_MAP_FILMIC && samples) {
-        // The caller's table is copied into pinned staging, so that the upload is truly asynchronous; the staging is
-        // rewritten only once the previous call's upload out of it has run (normally long done).
-        const size_t words = table_words(res_x, res_y, tile_dim);
-        HIP_TRY(ctx, tm.samples.ensure(words * 4));
-        if (words > tm.staging_words) {
-            if (tm.staging) HIP_TRY(ctx, hipHostFree(tm.staging));
-            tm.staging = nullptr;
-            tm.staging_words = 0;
-            HIP_TRY(ctx, hipHostMalloc((void**)&tm.staging, words * 4, hipHostMallocDefault));
-            tm.staging_words = words;
-        }
-        if (!tm.staged) HIP_TRY(ctx, hipEventCreateWithFlags(&tm.staged, hipEventDisableTiming));
-        else HIP_TRY(ctx, hipEventSynchronize(tm.staged));
-        std::memcpy(tm.staging, samples, words * 4);
-        HIP_TRY(ctx, hipMemcpyAsync(tm.samples.p, tm.staging, words * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipEventRecord(tm.staged, st));
+        yk_status ss = stage_sample_table(ctx, st, samples, table_words(res_x, res_y, tile_dim), tm.samples);
+        if (ss != YK_OK) return ss;
         a.samples = tm.samples.as<uint32_t>();
     }
     if (d->kind == YK_TONE_MAP_HEATMAP && !d->has_bounds) {
