@@ -675,6 +675,65 @@ yk_status yk_denoise(yk_context* ctx, const yk_denoise_desc* desc, const float* 
 yk_status yk_denoise_device(yk_context* ctx, const yk_denoise_desc* desc, const void* d_film_rgb, const void* d_guides, uint16_t res_x,
                             uint16_t res_y, uint16_t tile_dim, const uint32_t* samples, void* d_out_rgb, void* stream);
 
+/* ---- temporal: the film across camera moves — reprojected history, between the film and the denoiser ----
+ * The reference clears its film when the camera moves; these two passes are the library's own.  "Reproject" carries the
+ * history of the previous view (a mean and a sample count per pixel) to the current view through the first-hit guides of
+ * both; "blend" folds the current view's film into it.  The rule is stated next to each expression in
+ * yuki_amd/csrc/yk_temporal.h; the host and the device instance agree bit for bit (binary32, every operation separate, no
+ * FMA, a NaN an operation produces is 0x7fc00000, a value that is only copied keeps its bits).
+ * Intended use: while a camera stands, every displayed frame is blend(R, film, samples) with R reprojected ONCE when the
+ * camera moved (R NULL before the first move); the last blend's history output is the next move's previous history, and
+ * the guides of that view are its previous guides.  Downstream passes take the blended RGB with samples = NULL.
+ * Reprojected radiance is exact for diffuse surfaces only: on glass and metal it lags the view, for as long as
+ * max_history lets it (a new sample always weighs at least m / (max_history + m)).
+ * Reproject, current pixel P with guide G[P]:
+ *   1. G[P] a miss: the all-zero record.
+ *   2. p_cam = camera_to_world_inv' . p_P, r = raster_to_camera_inv' . p_cam (the point transform of Camera::ray; ' = the
+ *      previous camera).  The homogeneous w of the second transform <= 0 or NaN: zero record.
+ *   3. fx = r.x - 0.5, fy = r.y - 0.5; NaN, < -1 or >= (float)res on either axis: zero record.  x0 = floor(fx), ax = fx - x0.
+ *   4. Taps (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1), b = (1 - ax | ax) * (1 - ay | ay).  A tap is skipped when it lies
+ *      outside the film, b == 0, its previous guide is a miss, its n is <= 0 or NaN, a channel of it is NaN or infinite,
+ *      d = dot(ns_P, p_Q - p_P) has |d| > plane_tolerance or is NaN, or dot(ns_P, ns_Q) < normal_cos_min or is NaN.
+ *   5. sw = sum b over the taps taken; 0: zero record; else rgb = sum(b * c_Q) / sw, n = sum(b * n_Q) / sw.
+ * Blend, per pixel: m = (float)samples[flat] (the tone map's index rule) or 1 without a table; c = the film's RGB, divided
+ *   by m with a table where m > 0; n = min(h.n, max_history).  The history is absent when the pointer is NULL, n is <= 0
+ *   or NaN, or a channel of h is not finite; the current view when m == 0.  Both absent: zeros.  Only the history absent:
+ *   (c, m).  Only the current view absent: (h.rgb, n).  Neither: t = n + m, rgb = (n*h + m*c) / t, the record is (rgb, t). */
+typedef struct yk_history {
+    float rgb[3]; /* the mean radiance */
+    float n;      /* the effective number of samples behind it; 0 = no history */
+} yk_history;     /* 16 bytes; 16-byte aligned on the device */
+typedef struct yk_temporal_desc {
+    float plane_tolerance; /* scene units, > 0; +inf switches the plane test off */
+    float normal_cos_min;  /* [-1, 1] */
+    float max_history;     /* >= 1 */
+} yk_temporal_desc;
+/* Host buffers: res_x * res_y records each, row-major.  ctx NULL = the host instance on the CPU, else on ctx's device
+ * (synchronous).  YK_ERR_INVALID_ARGUMENT: a NULL pointer, a zero resolution, a parameter out of range or NaN, an output
+ * that overlaps any input. */
+yk_status yk_history_reproject(yk_context* ctx, const yk_temporal_desc* desc, const yk_history* prev_history, const yk_guide* prev_guides,
+                               const yk_camera* prev_camera, const yk_guide* guides, uint16_t res_x, uint16_t res_y, yk_history* out_history);
+/* The same on device buffers (all 16-byte aligned; anything else: YK_ERR_INVALID_ARGUMENT, nothing is launched), enqueued
+ * on `stream` (NULL = the context's) without waiting for the device: one launch, no allocation.  The camera is read before
+ * the call returns. */
+yk_status yk_history_reproject_device(yk_context* ctx, const yk_temporal_desc* desc, const void* d_prev_history, const void* d_prev_guides,
+                                      const yk_camera* prev_camera, const void* d_guides, uint16_t res_x, uint16_t res_y, void* d_out_history,
+                                      void* stream);
+/* film_rgb row-major RGB (res_y, res_x, 3); `samples` and tile_dim as yk_denoise takes them; history may be NULL; either
+ * output may be NULL, not both.  out_history may equal history and out_rgb may equal film_rgb.
+ * YK_ERR_INVALID_ARGUMENT: a NULL desc or film, a zero resolution, tile_dim 0, a parameter out of range or NaN, both outputs
+ * NULL, an output that overlaps an input without being equal to its own counterpart, outputs that overlap each other. */
+yk_status yk_history_blend(yk_context* ctx, const yk_temporal_desc* desc, const float* film_rgb, uint16_t res_x, uint16_t res_y,
+                           uint16_t tile_dim, const uint32_t* samples, const yk_history* history, yk_history* out_history, float* out_rgb);
+/* The same on device buffers, enqueued on `stream` (NULL = the context's) without waiting for the device: one launch.
+ * `samples` is a HOST table (copied before the call returns, through the pinned staging of the tone map and the denoiser);
+ * its device copy belongs to the context, allocated on first use and again when a larger table comes.  d_film_rgb and
+ * d_out_rgb need 4-byte alignment, the histories 16-byte alignment (anything else: YK_ERR_INVALID_ARGUMENT, nothing is
+ * launched). */
+yk_status yk_history_blend_device(yk_context* ctx, const yk_temporal_desc* desc, const void* d_film_rgb, uint16_t res_x, uint16_t res_y,
+                                  uint16_t tile_dim, const uint32_t* samples, const void* d_history, void* d_out_history, void* d_out_rgb,
+                                  void* stream);
+
 /* ---- per-stage entry points (parity tests, profiling) ------------------------- */
 /* BoundingVolumeHierarchy::intersect (bvh.rs:160-232) for n host rays.
  * out_shape: source shape index or -1; counters as IntersectionResult. */

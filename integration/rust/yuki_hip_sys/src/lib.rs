@@ -215,6 +215,24 @@ pub struct yk_denoise_desc {
     pub sigma_plane: f32,
 }
 
+/// A pixel's history across camera moves: the mean radiance and the effective number of samples behind it (0 = none);
+/// 16-byte aligned on the device (yuki_amd/csrc/yk_temporal.h)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct yk_history {
+    pub rgb: [f32; 3],
+    pub n: f32,
+}
+
+/// The plane test (scene units, > 0, +inf = off) and the normal test ([-1, 1]) of reproject, and blend's history clamp (>= 1)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct yk_temporal_desc {
+    pub plane_tolerance: f32,
+    pub normal_cos_min: f32,
+    pub max_history: f32,
+}
+
 /// The target rectangle of ScaleOutput::draw in top-down window coordinates
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -414,6 +432,10 @@ extern "C" {
     pub fn yk_render_guides_device(ctx: *mut yk_context, scene: *const yk_scene, camera: *const yk_camera, res_x: u16, res_y: u16, d_guides: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_denoise(ctx: *mut yk_context, desc: *const yk_denoise_desc, film_rgb: *const f32, guides: *const yk_guide, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, out_rgb: *mut f32) -> yk_status;
     pub fn yk_denoise_device(ctx: *mut yk_context, desc: *const yk_denoise_desc, d_film_rgb: *const c_void, d_guides: *const c_void, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, d_out_rgb: *mut c_void, stream: *mut c_void) -> yk_status;
+    pub fn yk_history_reproject(ctx: *mut yk_context, desc: *const yk_temporal_desc, prev_history: *const yk_history, prev_guides: *const yk_guide, prev_camera: *const yk_camera, guides: *const yk_guide, res_x: u16, res_y: u16, out_history: *mut yk_history) -> yk_status;
+    pub fn yk_history_reproject_device(ctx: *mut yk_context, desc: *const yk_temporal_desc, d_prev_history: *const c_void, d_prev_guides: *const c_void, prev_camera: *const yk_camera, d_guides: *const c_void, res_x: u16, res_y: u16, d_out_history: *mut c_void, stream: *mut c_void) -> yk_status;
+    pub fn yk_history_blend(ctx: *mut yk_context, desc: *const yk_temporal_desc, film_rgb: *const f32, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, history: *const yk_history, out_history: *mut yk_history, out_rgb: *mut f32) -> yk_status;
+    pub fn yk_history_blend_device(ctx: *mut yk_context, desc: *const yk_temporal_desc, d_film_rgb: *const c_void, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, d_history: *const c_void, d_out_history: *mut c_void, d_out_rgb: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_write_png(path: *const c_char, width: u32, height: u32, channels: u32, pixels: *const u8) -> yk_status;
     pub fn yk_render_tile(ctx: *mut yk_context, scene: *const yk_scene, camera: *const yk_camera, sampler: *const yk_sampler_desc, integrator: *const yk_integrator_desc, tile: *const yk_tile, tile_pixels: *mut f32, out_rays: *mut u64) -> yk_status;
     pub fn yk_film_update_tiles_device(ctx: *mut yk_context, tiles: *const yk_tile, n_tiles: usize, d_tile_rgb: *const c_void, res_x: u16, res_y: u16, d_film_rgb: *mut c_void, stream: *mut c_void) -> yk_status;

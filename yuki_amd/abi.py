@@ -132,6 +132,12 @@ class DenoiseDesc(C.Structure):
     _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float)]
 
 
+class TemporalDesc(C.Structure):
+    """yk_temporal_desc: the plane and normal tests of reproject and blend's history clamp (csrc/yk_temporal.h)."""
+
+    _fields_ = [("plane_tolerance", C.c_float), ("normal_cos_min", C.c_float), ("max_history", C.c_float)]
+
+
 class IntegratorRay(C.Structure):
     """yk_integrator_ray: IntegratorRay (integrators/mod.rs:76-80), the ray and its yk_ray_type."""
 
@@ -188,6 +194,7 @@ TILE_DTYPE = np.dtype([("x0", "<u2"), ("y0", "<u2"), ("x1", "<u2"), ("y1", "<u2"
 INTEGRATOR_RAY_DTYPE = np.dtype([("o", "<f4", 3), ("d", "<f4", 3), ("t_max", "<f4"), ("ray_type", "<u4")])
 OVERLAY_LINE_DTYPE = np.dtype([("p0", "<f4", 3), ("p1", "<f4", 3), ("rgb", "<f4", 3)])  # yk_overlay_line, 36 bytes
 GUIDE_DTYPE = np.dtype([("ns", "<f4", 3), ("hit", "<f4"), ("p", "<f4", 3), ("t", "<f4")])  # yk_guide, 32 bytes
+HISTORY_DTYPE = np.dtype([("rgb", "<f4", 3), ("n", "<f4")])  # yk_history, 16 bytes
 
 # enums (include/yuki_hip.h)
 SPLIT_SAH, SPLIT_MIDDLE, SPLIT_EQUAL_COUNTS = 0, 1, 2

@@ -268,6 +268,84 @@ def denoise(film, guides, params, tile_dim=16, samples=None, ctx=None):
     return out
 
 
+# --------------------------------------------------------------------------- temporal
+@dataclass
+class TemporalParams:
+    """yk_temporal_desc: the plane and normal tests of reproject_history and the history clamp of blend_history
+    (csrc/yk_temporal.h).  plane_tolerance is in scene units: None stands for "no plane test" (+inf);
+    TemporalParams.for_scene scales it to the scene."""
+
+    plane_tolerance: float = None
+    normal_cos_min: float = 0.9
+    max_history: float = 64.0
+
+    @staticmethod
+    def for_scene(scene, **kw):
+        """plane_tolerance = 0.01 x the diagonal of the scene's bounds (Scene.info()), as DenoiseParams.for_scene."""
+        i = scene.info()
+        diag = float(np.linalg.norm(np.array(i.bounds_max[:], dtype=np.float64) - np.array(i.bounds_min[:], dtype=np.float64)))
+        return TemporalParams(plane_tolerance=0.01 * diag, **kw)
+
+    def as_struct(self):
+        return abi.TemporalDesc(float("inf") if self.plane_tolerance is None else float(self.plane_tolerance), float(self.normal_cos_min), float(self.max_history))
+
+
+def _temporal_desc(params):
+    if not isinstance(params, TemporalParams):
+        raise TypeError("params is a TemporalParams")
+    return params.as_struct()
+
+
+def _records(a, dtype, res, what):
+    a = np.ascontiguousarray(a, dtype=dtype)
+    if a.size != int(res[0]) * int(res[1]):
+        raise ValueError(f"one {what} record per film pixel")
+    return a
+
+
+def reproject_history(history, prev_guides, prev_camera, guides, params, ctx=None):
+    """yk_history_reproject: the (h, w) abi.HISTORY_DTYPE history of the previous view, its guides and its Camera, and the
+    current view's guides -> the history as the current view sees it.  ctx None = the host instance."""
+    guides = np.ascontiguousarray(guides, dtype=abi.GUIDE_DTYPE)
+    if guides.ndim != 2:
+        raise ValueError("guides is (h, w)")
+    h, w = guides.shape
+    history = _records(history, abi.HISTORY_DTYPE, (w, h), "history")
+    prev_guides = _records(prev_guides, abi.GUIDE_DTYPE, (w, h), "guide")
+    d = _temporal_desc(params)
+    out = np.zeros((h, w), dtype=abi.HISTORY_DTYPE)
+    c = ctx.h if ctx else None
+    check(lib().yk_history_reproject(c, C.byref(d), _p(history), _p(prev_guides), C.byref(prev_camera.matrices), _p(guides), w, h, _p(out)), c)
+    return out
+
+
+def _blend_samples(res, tile_dim, samples):
+    if samples is not None:
+        samples = np.ascontiguousarray(samples, dtype=np.uint32)
+        if int(tile_dim) > 0 and samples.size != _table_len(res, int(tile_dim)):
+            raise ValueError(f"samples has {samples.size} entries, the film's tile grid {_table_len(res, int(tile_dim))}")
+    return samples
+
+
+def blend_history(film, params, tile_dim=16, samples=None, history=None, ctx=None):
+    """yk_history_blend: the current view's (h, w, 3) float32 film (with `samples` = Film.samples for an accumulating one)
+    folded into a reprojected history (or None) -> (rgb, history): the film of the means, which downstream passes take with
+    samples=None, and the new (h, w) abi.HISTORY_DTYPE history.  ctx None = the host instance."""
+    film = np.ascontiguousarray(film, dtype=np.float32)
+    if film.ndim != 3 or film.shape[2] != 3:
+        raise ValueError("film is (h, w, 3)")
+    h, w = film.shape[0], film.shape[1]
+    d = _temporal_desc(params)
+    samples = _blend_samples((w, h), tile_dim, samples)
+    if history is not None:
+        history = _records(history, abi.HISTORY_DTYPE, (w, h), "history")
+    rgb = np.empty_like(film)
+    out = np.zeros((h, w), dtype=abi.HISTORY_DTYPE)
+    c = ctx.h if ctx else None
+    check(lib().yk_history_blend(c, C.byref(d), _p(film), w, h, int(tile_dim), _p(samples), _p(history), _p(out), _p(rgb)), c)
+    return rgb, out
+
+
 def _denoise_for_output(film, denoise_params, guides, tile_dim, samples, ctx):
     """The denoise step of write_output / write_preview: (film, samples) for the tone map that follows — the denoised film
     is normalised already, so it goes on without the sample table."""
@@ -573,6 +651,23 @@ class Context:
         the context's) without waiting; `samples` is a host table (or None), copied before the call returns."""
         d, _, samples = _denoise_args(res, params, None, tile_dim, samples)
         check(lib().yk_denoise_device(self.h, C.byref(d), C.c_void_p(d_film_ptr), C.c_void_p(d_guides_ptr), int(res[0]), int(res[1]), int(tile_dim), _p(samples), C.c_void_p(d_out_ptr), C.c_void_p(stream) if stream else None), self.h)
+
+    def reproject_history_device(self, d_prev_history_ptr, d_prev_guides_ptr, prev_camera, d_guides_ptr, res, params, d_out_history_ptr, stream=None):
+        """yk_history_reproject_device: the previous view's device history and guides, its Camera and the current view's
+        device guides -> the device history of the current view (all 16-byte aligned), enqueued on `stream` (default: the
+        context's) without waiting."""
+        d = _temporal_desc(params)
+        vp = C.c_void_p
+        check(lib().yk_history_reproject_device(self.h, C.byref(d), vp(d_prev_history_ptr), vp(d_prev_guides_ptr), C.byref(prev_camera.matrices), vp(d_guides_ptr), int(res[0]), int(res[1]), vp(d_out_history_ptr), vp(stream) if stream else None), self.h)
+
+    def blend_history_device(self, d_film_ptr, res, params, tile_dim, samples, d_history_ptr, d_out_history_ptr, d_out_rgb_ptr, stream=None):
+        """yk_history_blend_device: device film + device history (or None) -> device history and / or device RGB (None = not
+        wanted; they may be the inputs), enqueued on `stream` (default: the context's) without waiting; `samples` is a host
+        table (or None), copied before the call returns."""
+        d = _temporal_desc(params)
+        samples = _blend_samples(res, tile_dim, samples)
+        vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
+        check(lib().yk_history_blend_device(self.h, C.byref(d), vp(d_film_ptr), int(res[0]), int(res[1]), int(tile_dim), _p(samples), vp(d_history_ptr), vp(d_out_history_ptr), vp(d_out_rgb_ptr), vp(stream)), self.h)
 
     @property
     def stream_handle(self):

@@ -121,6 +121,10 @@ struct yk_context {
         DevBuf samples;   // the sample table on the device (staged through the tone map's pinned copy)
         int64_t lds_max_step = 2;  // "denoise_lds_max_step": iterations with a step up to this (0, 1 or 2) stage their taps in LDS (the measurement that chose 2)
     } denoise;
+    // the temporal passes' buffer (yk_temporal.hip), grown on first use
+    struct TemporalState {
+        DevBuf samples;   // blend's sample table on the device (staged through the tone map's pinned copy)
+    } temporal;
     // the overlay pass's buffers (yk_overlay.hip), grown on first use
     struct OverlayState {
         DevBuf ids;        // one u32 a pixel: the winning ordinal + 1

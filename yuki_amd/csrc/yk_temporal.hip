@@ -1,0 +1,321 @@
+// yk_temporal.hip — reproject and blend on gfx950, behind yk_history_reproject[_device] and yk_history_blend[_device]; the
+// per-pixel arithmetic is yk_temporal.h's, whose host instance these entry points run without a context.
+//
+// k_reproject: one lane per pixel, a block is a TP_TX x TP_TY tile of the film (the à-trous launch shape: a wave covers two
+//   rows of 32 pixels, so under small motion neighbouring lanes project to neighbouring taps).  A lane reads its guide (two
+//   16-byte loads), up to four taps of the previous view (two 16-byte guide loads and one 16-byte history load each, all
+//   issued before the first is consumed; a tap outside the film is never read, its request goes to the nearest pixel inside) and writes one 16-byte record.  The previous
+//   camera's two inverse matrices travel as kernel arguments: scalar registers.  No LDS: the footprint of a tile is not
+//   known before the projection.
+// k_blend: streaming, one lane per pixel: three dword loads of the film (4-byte alignment), one 16-byte load and one 16-byte
+//   store of the records, three dword stores of the RGB output.  "No table", "no history", "no history output" and "no RGB
+//   output" are template variants: no lane tests a pointer.  A lane reads its own pixel only, and before it writes it, so
+//   out_history may be the history and out_rgb the film.
+// The sample table is staged through the pinned copy the tone map and the denoiser share; the stream-ordered entry points
+// allocate nothing once the context has seen a table of that size.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+
+#include "yk_internal.h"
+#include "yk_temporal.h"
+
+namespace {
+
+constexpr unsigned TP_TX = 32, TP_TY = 8;  // 256 lanes: 4 waves of 64
+
+struct TpIo {
+    const float4* prev_history;  // one float4 a pixel: (rgb, n)
+    const float4* prev_guides;   // two float4 a pixel: (ns, hit), (p, t)
+    const float4* guides;
+    float4* out;
+};
+
+__global__ __launch_bounds__(TP_TX* TP_TY) void k_reproject(TpIo io, TpParams a, M44 c2w_inv, M44 r2c_inv) {
+    const uint32_t x = blockIdx.x * TP_TX + threadIdx.x, y = blockIdx.y * TP_TY + threadIdx.y;
+    if (x >= a.dn.res_x || y >= a.dn.res_y) return;
+    const size_t i = (size_t)y * a.dn.res_x + x;
+    const float4 ga = io.guides[2 * i], gb = io.guides[2 * i + 1];
+    float rec[4];
+    tp_reproject_pixel(a, c2w_inv.m, r2c_inv.m, V3{ga.x, ga.y, ga.z}, ga.w, V3{gb.x, gb.y, gb.z},
+                       [&](uint32_t qx, uint32_t qy, TpTap& t) {
+                           const size_t q = (size_t)qy * a.dn.res_x + qx;
+                           const float4 hv = io.prev_history[q], qa = io.prev_guides[2 * q], qb = io.prev_guides[2 * q + 1];
+                           t.c[0] = hv.x;
+                           t.c[1] = hv.y;
+                           t.c[2] = hv.z;
+                           t.n = hv.w;
+                           t.ns[0] = qa.x;
+                           t.ns[1] = qa.y;
+                           t.ns[2] = qa.z;
+                           t.hit = qa.w;
+                           t.p[0] = qb.x;
+                           t.p[1] = qb.y;
+                           t.p[2] = qb.z;
+                       },
+                       rec);
+    io.out[i] = make_float4(rec[0], rec[1], rec[2], rec[3]);
+}
+
+struct TpBlendIo {
+    const float* film;
+    const uint32_t* samples;
+    const float4* history;
+    float4* out_history;
+    float* out_rgb;
+};
+
+template <bool TABLE, bool HIST, bool OUT_HIST, bool OUT_RGB>
+__global__ __launch_bounds__(256) void k_blend(TpBlendIo io, TpParams a) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.dn.res_x * a.dn.res_y) return;
+    const float c[3] = {io.film[3 * (size_t)i], io.film[3 * (size_t)i + 1], io.film[3 * (size_t)i + 2]};
+    float m = 1.0f;
+    if (TABLE) {
+        const uint32_t y = i / a.dn.res_x, x = i - y * a.dn.res_x;
+        m = dn_count(a.dn, io.samples, x, y);
+    }
+    float h[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (HIST) {
+        const float4 v = io.history[i];
+        h[0] = v.x;
+        h[1] = v.y;
+        h[2] = v.z;
+        h[3] = v.w;
+    }
+    float rec[4];
+    tp_blend_pixel(a, TABLE, m, c, HIST ? h : nullptr, rec);
+    if (OUT_HIST) io.out_history[i] = make_float4(rec[0], rec[1], rec[2], rec[3]);
+    if (OUT_RGB) {
+        io.out_rgb[3 * (size_t)i] = rec[0];
+        io.out_rgb[3 * (size_t)i + 1] = rec[1];
+        io.out_rgb[3 * (size_t)i + 2] = rec[2];
+    }
+}
+
+template <bool TABLE, bool HIST, bool OUT_HIST>
+void launch_blend3(hipStream_t st, uint32_t n_px, const TpBlendIo& io, const TpParams& a) {
+    const dim3 grid((n_px - 1) / 256 + 1), block(256);
+    if (!OUT_HIST || io.out_rgb) hipLaunchKernelGGL((k_blend<TABLE, HIST, OUT_HIST, true>), grid, block, 0, st, io, a);  // one output at least (check_blend)
+    else hipLaunchKernelGGL((k_blend<TABLE, HIST, true, false>), grid, block, 0, st, io, a);
+}
+template <bool TABLE, bool HIST>
+void launch_blend2(hipStream_t st, uint32_t n_px, const TpBlendIo& io, const TpParams& a) {
+    if (io.out_history) launch_blend3<TABLE, HIST, true>(st, n_px, io, a);
+    else launch_blend3<TABLE, HIST, false>(st, n_px, io, a);
+}
+void launch_blend(hipStream_t st, uint32_t n_px, const TpBlendIo& io, const TpParams& a) {
+    if (io.samples && io.history) launch_blend2<true, true>(st, n_px, io, a);
+    else if (io.samples) launch_blend2<true, false>(st, n_px, io, a);
+    else if (io.history) launch_blend2<false, true>(st, n_px, io, a);
+    else launch_blend2<false, false>(st, n_px, io, a);
+}
+
+bool overlaps(const void* p, size_t np, const void* q, size_t nq) {
+    const uintptr_t p0 = (uintptr_t)p, q0 = (uintptr_t)q;
+    return p0 < q0 + nq && q0 < p0 + np;
+}
+
+bool desc_ok(const yk_temporal_desc* d) {
+    if (!d) return false;
+    if (!(d->plane_tolerance > 0.0f)) return false;                               // <= 0 or NaN
+    if (!(d->normal_cos_min >= -1.0f) || !(d->normal_cos_min <= 1.0f)) return false;  // outside [-1, 1] or NaN
+    if (!(d->max_history >= 1.0f)) return false;                                  // < 1 or NaN
+    return true;
+}
+
+TpParams make_params(const yk_temporal_desc* d, uint16_t res_x, uint16_t res_y, uint16_t tile_dim) {
+    TpParams a{};
+    a.dn.res_x = res_x;
+    a.dn.res_y = res_y;
+    a.dn.tile_dim = tile_dim;
+    a.dn.x_tile_count = res_x / tile_dim;
+    a.plane_tolerance = d->plane_tolerance;
+    a.normal_cos_min = d->normal_cos_min;
+    a.max_history = d->max_history;
+    return a;
+}
+
+size_t table_words(uint16_t res_x, uint16_t res_y, uint16_t tile_dim) {
+    return (size_t)((res_x + tile_dim - 1) / tile_dim) * (size_t)((res_y + tile_dim - 1) / tile_dim);
+}
+
+yk_status check_reproject(const yk_temporal_desc* d, const void* prev_history, const void* prev_guides, const yk_camera* prev_camera, const void* guides, uint16_t res_x, uint16_t res_y,
+                          const void* out) {
+    if (!desc_ok(d) || !prev_history || !prev_guides || !prev_camera || !guides || !out || res_x == 0 || res_y == 0) return YK_ERR_INVALID_ARGUMENT;
+    const size_t n_px = (size_t)res_x * res_y;
+    if (overlaps(out, n_px * 16, prev_history, n_px * 16) || overlaps(out, n_px * 16, prev_guides, n_px * sizeof(yk_guide)) || overlaps(out, n_px * 16, guides, n_px * sizeof(yk_guide)))
+        return YK_ERR_INVALID_ARGUMENT;
+    return YK_OK;
+}
+
+yk_status check_blend(const yk_temporal_desc* d, const void* film, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const void* history, const void* out_history, const void* out_rgb) {
+    if (!desc_ok(d) || !film || res_x == 0 || res_y == 0 || tile_dim == 0) return YK_ERR_INVALID_ARGUMENT;
+    if (!out_history && !out_rgb) return YK_ERR_INVALID_ARGUMENT;
+    const size_t n_px = (size_t)res_x * res_y;
+    if (out_history) {
+        if (overlaps(out_history, n_px * 16, film, n_px * 12)) return YK_ERR_INVALID_ARGUMENT;
+        if (history && out_history != history && overlaps(out_history, n_px * 16, history, n_px * 16)) return YK_ERR_INVALID_ARGUMENT;
+        if (out_rgb && overlaps(out_history, n_px * 16, out_rgb, n_px * 12)) return YK_ERR_INVALID_ARGUMENT;
+    }
+    if (out_rgb) {
+        if (out_rgb != film && overlaps(out_rgb, n_px * 12, film, n_px * 12)) return YK_ERR_INVALID_ARGUMENT;
+        if (history && overlaps(out_rgb, n_px * 12, history, n_px * 16)) return YK_ERR_INVALID_ARGUMENT;
+    }
+    return YK_OK;
+}
+
+yk_status enqueue_reproject(yk_context* ctx, hipStream_t st, const yk_temporal_desc* d, const void* prev_history, const void* prev_guides, const yk_camera* cam, const void* guides,
+                            uint16_t res_x, uint16_t res_y, void* out) {
+    const TpParams a = make_params(d, res_x, res_y, 1);
+    TpIo io{reinterpret_cast<const float4*>(prev_history), reinterpret_cast<const float4*>(prev_guides), reinterpret_cast<const float4*>(guides), reinterpret_cast<float4*>(out)};
+    M44 c2w_inv, r2c_inv;
+    std::memcpy(c2w_inv.m, cam->camera_to_world_inv, 64);
+    std::memcpy(r2c_inv.m, cam->raster_to_camera_inv, 64);
+    const dim3 grid((res_x + TP_TX - 1) / TP_TX, (res_y + TP_TY - 1) / TP_TY), block(TP_TX, TP_TY);
+    hipLaunchKernelGGL(k_reproject, grid, block, 0, st, io, a, c2w_inv, r2c_inv);
+    HIP_TRY(ctx, hipGetLastError());
+    return YK_OK;
+}
+
+yk_status enqueue_blend(yk_context* ctx, hipStream_t st, const yk_temporal_desc* d, const float* film, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const uint32_t* samples,
+                        const void* history, void* out_history, float* out_rgb) {
+    const TpParams a = make_params(d, res_x, res_y, tile_dim);
+    TpBlendIo io{};
+    io.film = film;
+    io.history = reinterpret_cast<const float4*>(history);
+    io.out_history = reinterpret_cast<float4*>(out_history);
+    io.out_rgb = out_rgb;
+    if (samples) {
+        yk_status ss = stage_sample_table(ctx, st, samples, table_words(res_x, res_y, tile_dim), ctx->temporal.samples);
+        if (ss != YK_OK) return ss;
+        io.samples = ctx->temporal.samples.as<const uint32_t>();
+    }
+    launch_blend(st, (uint32_t)res_x * res_y, io, a);
+    HIP_TRY(ctx, hipGetLastError());
+    return YK_OK;
+}
+
+void fetch_host(const float* hist, const yk_guide* g, size_t q, TpTap& t) {
+    std::memcpy(t.c, hist + 4 * q, 12);
+    t.n = hist[4 * q + 3];
+    std::memcpy(t.ns, g[q].ns, 12);
+    t.hit = g[q].hit;
+    std::memcpy(t.p, g[q].p, 12);
+}
+
+void reproject_host(const yk_temporal_desc* d, const yk_history* prev_history, const yk_guide* prev_guides, const yk_camera* cam, const yk_guide* guides, uint16_t res_x, uint16_t res_y,
+                    yk_history* out) {
+    const TpParams a = make_params(d, res_x, res_y, 1);
+    const float* hist = reinterpret_cast<const float*>(prev_history);
+    const auto fetch = [&](uint32_t qx, uint32_t qy, TpTap& t) { fetch_host(hist, prev_guides, (size_t)qy * res_x + qx, t); };
+    for (uint32_t y = 0; y < res_y; ++y)
+        for (uint32_t x = 0; x < res_x; ++x) {
+            const size_t i = (size_t)y * res_x + x;
+            const yk_guide& g = guides[i];
+            float rec[4];
+            tp_reproject_pixel(a, cam->camera_to_world_inv, cam->raster_to_camera_inv, V3{g.ns[0], g.ns[1], g.ns[2]}, g.hit, V3{g.p[0], g.p[1], g.p[2]}, fetch, rec);
+            std::memcpy(&out[i], rec, 16);
+        }
+}
+
+void blend_host(const yk_temporal_desc* d, const float* film, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const uint32_t* samples, const yk_history* history, yk_history* out_history,
+                float* out_rgb) {
+    const TpParams a = make_params(d, res_x, res_y, tile_dim);
+    for (uint32_t y = 0; y < res_y; ++y)
+        for (uint32_t x = 0; x < res_x; ++x) {
+            const size_t i = (size_t)y * res_x + x;
+            float c[3], h[4], rec[4];
+            std::memcpy(c, film + 3 * i, 12);
+            if (history) std::memcpy(h, &history[i], 16);
+            tp_blend_pixel(a, samples != nullptr, samples ? dn_count(a.dn, samples, x, y) : 1.0f, c, history ? h : nullptr, rec);
+            if (out_history) std::memcpy(&out_history[i], rec, 16);
+            if (out_rgb) std::memcpy(out_rgb + 3 * i, rec, 12);
+        }
+}
+
+}  // namespace
+
+extern "C" {
+
+yk_status yk_history_reproject(yk_context* ctx, const yk_temporal_desc* desc, const yk_history* prev_history, const yk_guide* prev_guides, const yk_camera* prev_camera,
+                               const yk_guide* guides, uint16_t res_x, uint16_t res_y, yk_history* out_history) {
+    if (check_reproject(desc, prev_history, prev_guides, prev_camera, guides, res_x, res_y, out_history) != YK_OK)
+        return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_history_reproject: bad argument");
+    if (!ctx) {  // the host instance
+        reproject_host(desc, prev_history, prev_guides, prev_camera, guides, res_x, res_y, out_history);
+        return YK_OK;
+    }
+    YK_LOCK(ctx);
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    const size_t n_px = (size_t)res_x * res_y;
+    HIP_TRY(ctx, ctx->scratch[4].ensure(n_px * 16));
+    HIP_TRY(ctx, ctx->scratch[5].ensure(n_px * sizeof(yk_guide)));
+    HIP_TRY(ctx, ctx->scratch[6].ensure(n_px * sizeof(yk_guide)));
+    HIP_TRY(ctx, ctx->scratch[7].ensure(n_px * 16));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[4].p, prev_history, n_px * 16, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[5].p, prev_guides, n_px * sizeof(yk_guide), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[6].p, guides, n_px * sizeof(yk_guide), hipMemcpyHostToDevice, st));
+    yk_status s = enqueue_reproject(ctx, st, desc, ctx->scratch[4].p, ctx->scratch[5].p, prev_camera, ctx->scratch[6].p, res_x, res_y, ctx->scratch[7].p);
+    if (s != YK_OK) return s;
+    HIP_TRY(ctx, hipMemcpyAsync(out_history, ctx->scratch[7].p, n_px * 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return YK_OK;
+}
+
+yk_status yk_history_reproject_device(yk_context* ctx, const yk_temporal_desc* desc, const void* d_prev_history, const void* d_prev_guides, const yk_camera* prev_camera,
+                                      const void* d_guides, uint16_t res_x, uint16_t res_y, void* d_out_history, void* stream) {
+    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
+    YK_LOCK(ctx);
+    if (check_reproject(desc, d_prev_history, d_prev_guides, prev_camera, d_guides, res_x, res_y, d_out_history) != YK_OK)
+        return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_history_reproject_device: bad argument");
+    // 16-byte loads and stores of the records and the guides
+    if (((uintptr_t)d_prev_history & 15u) || ((uintptr_t)d_prev_guides & 15u) || ((uintptr_t)d_guides & 15u) || ((uintptr_t)d_out_history & 15u))
+        return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_history_reproject_device: histories and guides must be 16-byte aligned");
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    return enqueue_reproject(ctx, st, desc, d_prev_history, d_prev_guides, prev_camera, d_guides, res_x, res_y, d_out_history);
+}
+
+yk_status yk_history_blend(yk_context* ctx, const yk_temporal_desc* desc, const float* film_rgb, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const uint32_t* samples,
+                           const yk_history* history, yk_history* out_history, float* out_rgb) {
+    if (check_blend(desc, film_rgb, res_x, res_y, tile_dim, history, out_history, out_rgb) != YK_OK) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_history_blend: bad argument");
+    if (!ctx) {  // the host instance
+        blend_host(desc, film_rgb, res_x, res_y, tile_dim, samples, history, out_history, out_rgb);
+        return YK_OK;
+    }
+    YK_LOCK(ctx);
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    const size_t n_px = (size_t)res_x * res_y;
+    HIP_TRY(ctx, ctx->scratch[4].ensure(n_px * 12));
+    HIP_TRY(ctx, ctx->scratch[5].ensure(n_px * 16));
+    HIP_TRY(ctx, ctx->scratch[6].ensure(n_px * 16));
+    HIP_TRY(ctx, ctx->scratch[7].ensure(n_px * 12));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[4].p, film_rgb, n_px * 12, hipMemcpyHostToDevice, st));
+    if (history) HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[5].p, history, n_px * 16, hipMemcpyHostToDevice, st));
+    yk_status s = enqueue_blend(ctx, st, desc, ctx->scratch[4].as<const float>(), res_x, res_y, tile_dim, samples, history ? ctx->scratch[5].p : nullptr,
+                                out_history ? ctx->scratch[6].p : nullptr, out_rgb ? ctx->scratch[7].as<float>() : nullptr);
+    if (s != YK_OK) return s;
+    if (out_history) HIP_TRY(ctx, hipMemcpyAsync(out_history, ctx->scratch[6].p, n_px * 16, hipMemcpyDeviceToHost, st));
+    if (out_rgb) HIP_TRY(ctx, hipMemcpyAsync(out_rgb, ctx->scratch[7].p, n_px * 12, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return YK_OK;
+}
+
+yk_status yk_history_blend_device(yk_context* ctx, const yk_temporal_desc* desc, const void* d_film_rgb, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const uint32_t* samples,
+                                  const void* d_history, void* d_out_history, void* d_out_rgb, void* stream) {
+    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
+    YK_LOCK(ctx);
+    if (check_blend(desc, d_film_rgb, res_x, res_y, tile_dim, d_history, d_out_history, d_out_rgb) != YK_OK)
+        return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_history_blend_device: bad argument");
+    // dword loads and stores of the film and the RGB output, 16-byte loads and stores of the records
+    if (((uintptr_t)d_film_rgb & 3u) || ((uintptr_t)d_out_rgb & 3u) || ((uintptr_t)d_history & 15u) || ((uintptr_t)d_out_history & 15u))
+        return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_history_blend_device: film and RGB output must be 4-byte aligned, histories 16-byte aligned");
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    return enqueue_blend(ctx, st, desc, reinterpret_cast<const float*>(d_film_rgb), res_x, res_y, tile_dim, samples, d_history, d_out_history, reinterpret_cast<float*>(d_out_rgb));
+}
+
+}  // extern "C"
