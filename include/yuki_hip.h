@@ -252,6 +252,7 @@ uint32_t yk_abi_version(void);
 const char* yk_status_string(yk_status s);
 yk_status yk_context_create(int device, yk_context** out);
 void yk_context_destroy(yk_context* ctx);
+/* ctx NULL: the message of the calling thread's last failed call that took no context (a host-only scene); reading clears it. */
 yk_status yk_last_error(const yk_context* ctx, char* buf, size_t cap);
 /* The hipStream_t every entry point of this context runs on when it is given no stream of the
  * caller's (a render also uses a side stream that joins it again before the call's last launch).
@@ -282,7 +283,8 @@ yk_status yk_context_interrupt(yk_context* ctx);
  * to scenes created afterwards; "overlay_coop_min" (1 .. 65536, default 32: box
  * edges of at least this many pixels are drawn by a whole wave in yk_overlay_draw[_device], shorter ones by one lane);
  * "denoise_lds_max_step" (0 | 1 | 2, default 2: the a-trous iterations of yk_denoise[_device] with a step up to this
- * stage their taps in LDS, the others read global memory).  Test hook: "trace_stage_kernel" (0, default: yk_trace_closest /
+ * stage their taps in LDS, the others read global memory); "update_top_block" (0 | 1, default 1: the device route of
+ * yk_scene_update finishes the tree's top levels of at most 256 nodes each with one block instead of a launch per level).  Test hook: "trace_stage_kernel" (0, default: yk_trace_closest /
  * yk_trace_any run the generic kernels as documented | 1: the generic kernels in the render loop's
  * flavour | 2: the wave-packet kernels; modes 1 and 2 report shape ids and verdicts only, and
  * refuse out_t, out_bary, counters, a closest-hit t_max and, in mode 2, a tree deeper than 64
@@ -333,6 +335,53 @@ yk_status yk_scene_create(yk_context* ctx, const yk_scene_desc* desc, yk_scene**
  * is not device memory of this context's device (checked with hipPointerGetAttributes before anything is launched) or
  * whose allocation ends before its count does; whatever yk_scene_create refuses. */
 yk_status yk_scene_create_device(yk_context* ctx, const yk_scene_desc* desc, void* stream, yk_scene** out);
+/* Update in place: the scene's vertices move, its tree is refitted and its records are rewritten ("Update in
+ * place").  `points` holds 3 floats for each of the scene's n_vertices (the count of its description); `normals` is the
+ * same size, or NULL to keep the normals the scene has — non-NULL for a scene created without normals is
+ * YK_ERR_INVALID_ARGUMENT.  Indices, uvs, materials, lights and spheres do not change, and neither does the tree's
+ * topology: every node keeps its children, split axis, leaf flag, first slot and count, and the leaf order stays.  A leaf's
+ * box is folded from its shapes in leaf order (a triangle's bound from the new points, a sphere's as at creation), an
+ * interior node's from its two children in child order, and all seven record buffers, yk_scene_info.bounds_min/max and the
+ * layout info's scalars follow.  A scene updated with its own points is byte for byte what it was.  A rectangular light's
+ * record is not moved: vertices of triangles that carry an area light are the caller's business.  The tree's depth stays
+ * too: rays that overflow the 64-entry traversal stack of a tree deeper than that (YK_ERR_STACK_OVERFLOW) still do.
+ *   yk_scene_update        host arrays.  It follows the scene's layout (yk_scene_get_layout_info): a device-laid scene
+ *                          uploads the arrays and takes the device route, a host-laid one refits on the host
+ *                          (yk_bvh_refit), lays the records out there and uploads them.  ctx may be NULL for a host-only
+ *                          scene: its tree is refitted.
+ *   yk_scene_update_device DEVICE pointers on ctx's device, produced on `stream` (a hipStream_t, NULL: nothing to wait for),
+ *                          checked as yk_scene_create_device checks its arrays, with the same messages.  It always takes
+ *                          the device route: leaf boxes, one launch per tree level bottom-up and the layout's own kernels.
+ *                          Where an allocation or a HIP call fails there, the arrays are copied to the host once and the
+ *                          host route runs; yk_scene_get_update_info says so.  Both routes write the same bytes.
+ * All or nothing: the arguments are tested before anything of the scene is written, and a refused update leaves every
+ * buffer of the scene untouched.  Every coordinate of `points` must be finite ("points: coordinate not finite",
+ * YK_ERR_INVALID_ARGUMENT) — deliberately stricter than creation, which hands such geometry to the host builder.
+ * Ordering: the call holds the context's lock, waits for `stream` as yk_scene_create_device does and for everything this
+ * context has enqueued — renders of this scene enqueued on it before the call finish on the old geometry — and returns when
+ * the records are complete.  Renders of the scene from ANOTHER context or a combiner are the caller's to order: none may be
+ * in flight during the call.  After a device-route update the host copy of the tree is stale: yk_scene_export_bvh,
+ * yk_scene_node_bounds and the "trace_stage_kernel" stage calls fetch the refitted one on their next call.  Scenes of a
+ * yk_multi cannot be updated (no entry point takes one). */
+yk_status yk_scene_update(yk_context* ctx, yk_scene* scene, const float* points, const float* normals);
+yk_status yk_scene_update_device(yk_context* ctx, yk_scene* scene, const float* d_points, const float* d_normals, void* stream);
+enum { YK_UPDATE_ROUTE_HOST = 0, YK_UPDATE_ROUTE_DEVICE = 1 };
+typedef struct yk_scene_update_info {
+    uint32_t n_updates;    /* updates that were carried out (refused ones do not count) */
+    uint32_t route;        /* YK_UPDATE_ROUTE_* of the last update */
+    uint32_t reason;       /* YK_LAYOUT_REASON_* : non-zero when the last update asked for the device route and ran on the host */
+    uint32_t n_levels;     /* device route: launches of the level pass (the depth of the deepest interior node) */
+    uint64_t plan_bytes;   /* device memory the update state keeps (tree, depths, level lists, small tables); built on the
+                            * first device-route update and added to yk_scene_info.device_bytes */
+    double seconds_check, seconds_boxes, seconds_records, seconds_total; /* last update: the finite test (with the copy of
+                            * the arrays into the scene), leaf and interior boxes, the seven record buffers, the whole call */
+} yk_scene_update_info;
+yk_status yk_scene_get_update_info(const yk_scene* scene, yk_scene_update_info* out);
+/* The refit rule on the host, over an exported tree (yk_scene_export_bvh): the boxes of `nodes` are recomputed in place
+ * from shape_bounds — six floats (min.xyz, max.xyz) per SOURCE shape, n_shapes of them — leaves folded from the default
+ * bounds in leaf order through shape_order, interior nodes from their children in descending array index.  Nothing else
+ * of a node is written.  YK_ERR_INVALID_ARGUMENT: a NULL array, or a link, slot or shape index out of range. */
+yk_status yk_bvh_refit(yk_bvh_node* nodes, size_t n_nodes, const uint32_t* shape_order, size_t n_shapes, const float* shape_bounds);
 void yk_scene_destroy(yk_scene* scene);
 yk_status yk_scene_get_info(const yk_scene* scene, yk_scene_info* out);
 /* nodes: n_nodes entries in the reference's depth-first layout; shape_order:

@@ -149,6 +149,14 @@ class Scene {
         check(yk_scene_get_layout_info(h_, &i));
         return i;
     }
+    // yk_scene_update / yk_scene_update_device: the vertices move, the tree is refitted in place; normals may be nullptr (kept)
+    void update(const float* points, const float* normals = nullptr) { check(yk_scene_update(ctx_ ? ctx_->handle() : nullptr, h_, points, normals), ctx_ ? ctx_->handle() : nullptr); }
+    void update_device(const float* d_points, const float* d_normals = nullptr, void* stream = nullptr) { check(yk_scene_update_device(ctx_->handle(), h_, d_points, d_normals, stream), ctx_->handle()); }
+    yk_scene_update_info update_info() const {  // the last update's route, reason and phase seconds; the plan's levels and bytes
+        yk_scene_update_info i;
+        check(yk_scene_get_update_info(h_, &i));
+        return i;
+    }
     std::vector<uint8_t> device_records(uint32_t which) const {  // test hook: one record buffer (YK_RECORDS_*) copied back
         size_t n = 0;
         check(yk_scene_read_records(h_, which, nullptr, 0, &n));

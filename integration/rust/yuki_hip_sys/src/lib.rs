@@ -334,6 +334,23 @@ pub struct yk_scene_layout_info {
     pub wide_auto: u32,
 }
 
+pub const YK_UPDATE_ROUTE_HOST: u32 = 0;
+pub const YK_UPDATE_ROUTE_DEVICE: u32 = 1;
+
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct yk_scene_update_info {
+    pub n_updates: u32,
+    pub route: u32,
+    pub reason: u32,
+    pub n_levels: u32,
+    pub plan_bytes: u64,
+    pub seconds_check: f64,
+    pub seconds_boxes: f64,
+    pub seconds_records: f64,
+    pub seconds_total: f64,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct yk_combiner_info {
@@ -392,6 +409,10 @@ extern "C" {
     pub fn yk_scene_create_device(ctx: *mut yk_context, desc: *const yk_scene_desc, stream: *mut c_void, out: *mut *mut yk_scene) -> yk_status;
     pub fn yk_scene_destroy(scene: *mut yk_scene);
     pub fn yk_scene_get_info(scene: *const yk_scene, out: *mut yk_scene_info) -> yk_status;
+    pub fn yk_scene_update(ctx: *mut yk_context, scene: *mut yk_scene, points: *const f32, normals: *const f32) -> yk_status;
+    pub fn yk_scene_update_device(ctx: *mut yk_context, scene: *mut yk_scene, d_points: *const f32, d_normals: *const f32, stream: *mut c_void) -> yk_status;
+    pub fn yk_scene_get_update_info(scene: *const yk_scene, out: *mut yk_scene_update_info) -> yk_status;
+    pub fn yk_bvh_refit(nodes: *mut yk_bvh_node, n_nodes: usize, shape_order: *const u32, n_shapes: usize, shape_bounds: *const f32) -> yk_status;
     pub fn yk_scene_export_bvh(scene: *const yk_scene, nodes: *mut yk_bvh_node, shape_order: *mut u32) -> yk_status;
     pub fn yk_scene_get_build_info(scene: *const yk_scene, out: *mut yk_bvh_build_info) -> yk_status;
     pub fn yk_scene_get_layout_info(scene: *const yk_scene, out: *mut yk_scene_layout_info) -> yk_status;

@@ -1,0 +1,49 @@
+//! `yuki/src/app/gpu_worker.rs` — show a moved mesh without building its scene again.  The reference has no animation:
+//! a changed mesh means a new `Scene` and a new BVH.  With `yk_scene_update[_device]` the worker keeps the `yk_scene` it
+//! made for the first frame and hands every later frame's vertex positions to it: the tree keeps its topology, its
+//! boxes are refitted bottom-up and the traversal records are rewritten, all on the device when the positions are
+//! there already (a skinning or simulation kernel's output).  What the caller must keep in mind:
+//!   * indices, uvs, materials, lights and spheres stay; only positions (and, optionally, normals) move;
+//!   * vertices of triangles that carry an area light must not move (the light's own record does not follow);
+//!   * every coordinate must be finite, or the call is refused and the scene stays as it was;
+//!   * the call waits for what this context has enqueued; renders from other contexts must not be in flight;
+//!   * a refit never improves the tree: after a large deformation traversal is slower than through a rebuilt tree
+//!     (profiles/scene_update_device.json has both), so a worker may rebuild every so often.
+//! The rule: yuki_amd/csrc/yk_scene_update.h.  SOURCE ONLY.
+#![cfg(feature = "hip")]
+
+use std::ffi::c_void;
+use yuki_hip_sys as sys;
+
+/// Host positions (3 floats a vertex, the scene's own vertex count) and optional normals of the same size.
+pub fn update_scene(ctx: *mut sys::yk_context, scene: *mut sys::yk_scene, points: &[f32], normals: Option<&[f32]>) -> Result<sys::yk_scene_update_info, String> {
+    if let Some(n) = normals {
+        assert!(n.len() == points.len());
+    }
+    let status = unsafe { sys::yk_scene_update(ctx, scene, points.as_ptr(), normals.map_or(std::ptr::null(), |n| n.as_ptr())) };
+    finish(ctx, scene, status)
+}
+
+/// Device positions produced on `stream` (a hipStream_t, or null): nothing crosses the host link.
+pub fn update_scene_device(
+    ctx: *mut sys::yk_context,
+    scene: *mut sys::yk_scene,
+    d_points: *const f32,
+    d_normals: *const f32,
+    stream: *mut c_void,
+) -> Result<sys::yk_scene_update_info, String> {
+    let status = unsafe { sys::yk_scene_update_device(ctx, scene, d_points, d_normals, stream) };
+    finish(ctx, scene, status)
+}
+
+fn finish(ctx: *mut sys::yk_context, scene: *mut sys::yk_scene, status: sys::yk_status) -> Result<sys::yk_scene_update_info, String> {
+    if status != sys::YK_OK {
+        return Err(sys::last_error(ctx));
+    }
+    let mut info = sys::yk_scene_update_info::default();
+    unsafe { sys::yk_scene_get_update_info(scene, &mut info) };
+    if info.route == sys::YK_UPDATE_ROUTE_HOST && info.reason != 0 {
+        log::warn!("scene update fell back to the host route (reason {})", info.reason);
+    }
+    Ok(info)
+}

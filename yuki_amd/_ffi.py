@@ -107,6 +107,10 @@ SYMBOLS = {
     "yk_film_update_tiles": (C.c_int, [vp, C.c_size_t, vp, C.c_uint16, C.c_uint16, vp]),
     "yk_scene_create": (C.c_int, [vp, C.POINTER(abi.SceneDesc), C.POINTER(vp)]),
     "yk_scene_create_device": (C.c_int, [vp, C.POINTER(abi.SceneDesc), vp, C.POINTER(vp)]),
+    "yk_scene_update": (C.c_int, [vp, vp, vp, vp]),
+    "yk_scene_update_device": (C.c_int, [vp, vp, vp, vp, vp]),
+    "yk_scene_get_update_info": (C.c_int, [vp, C.POINTER(abi.SceneUpdateInfo)]),
+    "yk_bvh_refit": (C.c_int, [vp, C.c_size_t, vp, C.c_size_t, vp]),
     "yk_scene_destroy": (None, [vp]),
     "yk_scene_get_info": (C.c_int, [vp, C.POINTER(SceneInfo)]),
     "yk_scene_export_bvh": (C.c_int, [vp, vp, vp]),
@@ -235,11 +239,9 @@ def lib():
 
 def check(status, ctx=None):
     if status != YK_OK:
-        msg = ""
-        if ctx:
-            buf = C.create_string_buffer(512)
-            lib().yk_last_error(ctx, buf, 512)
-            msg = buf.value.decode(errors="replace")
+        buf = C.create_string_buffer(512)  # ctx None: the message this thread's call without a context left
+        lib().yk_last_error(ctx, buf, 512)
+        msg = buf.value.decode(errors="replace")
         if not msg:
             msg = lib().yk_status_string(status).decode()
         raise YukiError(status, msg)

@@ -176,6 +176,22 @@ class SceneLayoutInfo(C.Structure):
     ]
 
 
+class SceneUpdateInfo(C.Structure):
+    """yk_scene_update_info: how a scene's last update in place ran (yk_scene_update / yk_scene_update_device)."""
+
+    _fields_ = [
+        ("n_updates", C.c_uint32),
+        ("route", C.c_uint32),
+        ("reason", C.c_uint32),
+        ("n_levels", C.c_uint32),
+        ("plan_bytes", C.c_uint64),
+        ("seconds_check", C.c_double),
+        ("seconds_boxes", C.c_double),
+        ("seconds_records", C.c_double),
+        ("seconds_total", C.c_double),
+    ]
+
+
 class TraceStats(C.Structure):
     _fields_ = [
         ("closest_rays", C.c_uint64),
@@ -209,6 +225,7 @@ HEATMAP_RED, HEATMAP_GREEN, HEATMAP_BLUE, HEATMAP_LUMINANCE = 0, 1, 2, 3
 PRESENT_ENCODE_NONE, PRESENT_ENCODE_SHADER, PRESENT_ENCODE_SRGB = 0, 1, 2
 PRESENT_RGBA8, PRESENT_RGB32F = 0, 1
 LAYOUT_HOST, LAYOUT_DEVICE = 0, 1
+UPDATE_ROUTE_HOST, UPDATE_ROUTE_DEVICE = 0, 1
 LAYOUT_REASON_NONE, LAYOUT_REASON_OUT_OF_MEMORY, LAYOUT_REASON_DEVICE_ERROR, LAYOUT_REASON_MULTI = 0, 1, 2, 3
 RECORDS_NODES, RECORDS_NODES4, RECORDS_TOP, RECORDS_TOP_ANY, RECORDS_TRIS, RECORDS_PRIM_SHADE, RECORDS_PRIM_ATTR = range(7)
 RECORD_NAMES = ("nodes", "nodes4", "top", "top_any", "tris", "prim_shade", "prim_attr")

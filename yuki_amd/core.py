@@ -795,6 +795,74 @@ class Scene:
         check(lib().yk_scene_get_layout_info(self.h, C.byref(i)))
         return i
 
+    def update(self, points, normals=None, stream=None):
+        """yk_scene_update / yk_scene_update_device: the scene's vertices move, its tree is refitted in place (topology and
+        leaf order kept) and its records are rewritten.  `points` is (n_vertices, 3) float32 for the scene's own vertex
+        count, `normals` the same or None to keep the scene's normals.  numpy arrays go to yk_scene_update (which follows
+        the scene's layout); torch tensors on the context's device, or raw device addresses (int), go to
+        yk_scene_update_device, which always takes the device route — `stream` as in from_device.  A tensor's element
+        type, contiguity, element count and device are checked here (ValueError) before the library is reached; an
+        address is taken as it is.  Every coordinate must be finite.  With numpy input `self.data` becomes a copy that
+        carries the new arrays; with tensors or addresses it is left alone and keeps describing the geometry the scene
+        was created from."""
+        nv = int(self.data.points.shape[0])
+        given = {"points": points, "normals": normals}
+        if all(a is None or isinstance(a, np.ndarray) or isinstance(a, (list, tuple)) for a in given.values()):
+            host = {}
+            for name, a in given.items():
+                if a is None:
+                    host[name] = None
+                    continue
+                a = np.ascontiguousarray(a, dtype=np.float32)
+                if a.size != 3 * nv:
+                    raise ValueError(f"{name}: {a.size} elements, expected {3 * nv}")
+                host[name] = a.reshape(nv, 3)
+            ctx_h = self.ctx.h if self.ctx else None
+            check(lib().yk_scene_update(ctx_h, self.h, _p(host["points"]), _p(host["normals"])), ctx_h)
+            import copy
+
+            self.data = copy.copy(self.data)
+            if host["points"] is not None:
+                self.data.points = host["points"]
+            if host["normals"] is not None:
+                self.data.normals = host["normals"]
+            return
+        if self.ctx is None:
+            raise ValueError("a host-only scene is updated with numpy arrays")
+        address, tensors = {}, []
+        for name, a in given.items():
+            if a is None or isinstance(a, (int, np.integer)):
+                address[name] = int(a) if a else None
+                continue
+            if not hasattr(a, "data_ptr"):
+                raise ValueError(f"{name}: expected a torch tensor or a device address, got {type(a).__name__}")
+            if str(a.dtype).replace("torch.", "") != "float32":
+                raise ValueError(f"{name}: element type {a.dtype}, expected float32")
+            if not a.is_contiguous():
+                raise ValueError(f"{name}: the tensor is not contiguous")
+            if a.numel() != 3 * nv:
+                raise ValueError(f"{name}: {a.numel()} elements, expected {3 * nv}")
+            tensors.append((name, a))
+        for name, a in tensors:  # ... and only then where they are
+            if not a.is_cuda or a.device.index != self.ctx.device:
+                raise ValueError(f"{name}: the tensor is on {a.device}, not on the context's device {self.ctx.device}")
+            address[name] = a.data_ptr() or None
+        if stream is None and tensors:
+            import torch
+
+            torch.cuda.current_stream(tensors[0][1].device).synchronize()
+        elif stream is not None and not isinstance(stream, int):
+            stream = stream.cuda_stream
+        vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
+        check(lib().yk_scene_update_device(self.ctx.h, self.h, vp(address["points"]), vp(address["normals"]), vp(stream)), self.ctx.h)
+
+    def update_info(self):
+        """yk_scene_get_update_info: how many updates ran, the last one's route (abi.UPDATE_ROUTE_*) and reason
+        (abi.LAYOUT_REASON_*), the level launches and device bytes of the plan, and the last update's phase seconds."""
+        i = abi.SceneUpdateInfo()
+        check(lib().yk_scene_get_update_info(self.h, C.byref(i)))
+        return i
+
     def device_records(self, which):
         """yk_scene_read_records: one of the scene's device record buffers (abi.RECORDS_* or a name of abi.RECORD_NAMES) as uint8."""
         if isinstance(which, str):
@@ -845,6 +913,17 @@ class Scene:
         out = np.zeros(o.shape[0], dtype=np.uint8)
         check(lib().yk_trace_any(self.ctx.h, self.h, o.shape[0], _p(o), _p(d), _p(tm), _p(al), _p(out)), self.ctx.h)
         return out
+
+
+def refit_bvh(nodes, order, shape_bounds):
+    """yk_bvh_refit: the refit rule on the host over an exported tree.  nodes: abi.BVH_NODE_DTYPE, order: the leaf order
+    (both as Scene.export_bvh returns them), shape_bounds: (n_shapes, 6) or (n_shapes, 2, 3) float32, min.xyz and max.xyz per
+    SOURCE shape.  -> a refitted copy of `nodes`; links, axes, counts and flags are untouched."""
+    out = np.array(nodes, dtype=abi.BVH_NODE_DTYPE).copy()
+    order = np.ascontiguousarray(order, dtype=np.uint32)
+    sb = np.ascontiguousarray(shape_bounds, dtype=np.float32).reshape(-1, 6)
+    check(lib().yk_bvh_refit(_p(out), len(out), _p(order), len(sb), _p(sb)))
+    return out
 
 
 # --------------------------------------------------------------------------- several GPUs

@@ -136,7 +136,12 @@ void yk_context_destroy(yk_context* ctx) {
 }
 
 yk_status yk_last_error(const yk_context* ctx, char* buf, size_t cap) {
-    if (!ctx || !buf || cap == 0) return YK_ERR_INVALID_ARGUMENT;
+    if (!buf || cap == 0) return YK_ERR_INVALID_ARGUMENT;
+    if (!ctx) {  // the calling thread's last failure of a call without a context; reading it clears it
+        std::snprintf(buf, cap, "%s", host_last_error().c_str());
+        host_last_error().clear();
+        return YK_OK;
+    }
     std::snprintf(buf, cap, "%s", ctx->last_error.c_str());
     return YK_OK;
 }
@@ -190,6 +195,8 @@ yk_status yk_context_set_option(yk_context* ctx, const char* key, int64_t value)
     } else if (k == "denoise_lds_max_step") {
         if (value < 0 || value > 2) return YK_ERR_INVALID_ARGUMENT;
         ctx->denoise.lds_max_step = value;
+    } else if (k == "update_top_block") {
+        ctx->update_top_block = value != 0;
     } else if (k == "time_kernels") {
         ctx->time_kernels = value;
     } else {

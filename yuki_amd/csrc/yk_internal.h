@@ -83,6 +83,7 @@ struct yk_context {
     int64_t bvh_small_range = YK_BVH_SMALL_RANGE;  // ranges of at most this many shapes are finished by one lane each
     int64_t scene_layout = 0;      // scenes created afterwards: 0 the device records are laid out on the host and uploaded, 1 on the device (yk_scene_layout.hip)
     int64_t trace_stage_kernel = 0;  // which kernels yk_trace_closest / yk_trace_any launch (yk_stages.cpp): 0 generic, API flavour | 1 generic, render-loop flavour | 2 wave packets
+    int64_t update_top_block = 1;    // yk_scene_update, device route: 1 the tree's top levels of at most a block's lanes are finished by one block | 0 one launch per level throughout (the measurement)
     int64_t sample_buf_cap = (int64_t)64 << 30;
     int64_t time_kernels = 1;
     int64_t streams = 2;  // batches in flight (1 or 2): the second stream's launches fill the first one's tails
@@ -159,7 +160,8 @@ struct yk_scene {
     std::shared_ptr<const HostBvh> bvh;
     std::shared_ptr<HostBvh> bvh_lazy;  // the same object, writable: set while the arrays are still to be fetched
     DevBuf tree_nodes, tree_order;
-    mutable std::once_flag tree_once;
+    // tree_fetched says whether the host arrays are current; a device-route update (yk_scene_update.hip) clears it again
+    mutable std::mutex tree_mu;
     mutable std::atomic<uint32_t> tree_fetched{1};
     yk_scene_layout_info layout = {};
     size_t record_bytes[7] = {};  // exact sizes of the seven record buffers (YK_RECORDS_*; a DevBuf is never smaller than 16 bytes)
@@ -180,6 +182,23 @@ struct yk_scene {
     DevBuf nodes, nodes4, top_nodes, top_nodes_any, tris, prim_shade, prim_attr, indices, points, normals, uvs, tri_mesh, tri_material, tri_area_light, mesh_flags, materials, lights, spheres, texels, tex_info;
     DevScene dev;
     bool on_device = false;
+    // What yk_scene_update needs after creation (yk_scene_update.h).  A host-only scene (no context) keeps its indices on the
+    // host; every other scene reads them from its device copy.
+    struct UpdateState {
+        uint32_t n_vertices = 0;
+        bool has_normals = false, has_uvs = false;
+        int64_t top_nodes = 0, wide_bvh = 0;  // the context's options the records were laid out with
+        std::vector<float> sphere_bounds;     // six floats a sphere: Sphere::world_bound as at creation
+        std::vector<uint8_t> mat_kind;        // device BSDF kind (MK_*) per material
+        std::vector<uint32_t> host_indices;   // host-only scenes
+        // the plan of the device route, built by the first update that takes it: the tree's nodes and order stay in
+        // tree_nodes / tree_order; depth = every node's depth; list = the interior nodes grouped by depth (level_off[d] ..
+        // level_off[d + 1] holds depth d + 1), then the leaves (from level_off[n_levels])
+        bool planned = false;
+        DevBuf depth, list, sphere_b, mat_kind_d, words;
+        std::vector<uint32_t> level_off;
+        yk_scene_update_info info = {};
+    } upd;
 };
 
 // The device scene a job of `n` rays traverses: with both node layouts present the 4-wide one
@@ -201,8 +220,17 @@ struct yk_tile_list {
     DevBuf pixel_xy, pixel_sample;
 };
 
+// The message of a call that has no context to leave it in (a host-only scene): per thread, read and cleared by
+// yk_last_error(NULL, ...).
+inline std::string& host_last_error() {
+    static thread_local std::string msg;
+    return msg;
+}
 static inline yk_status fail(yk_context* ctx, yk_status st, const std::string& msg) {
-    if (ctx) ctx->last_error = msg;
+    if (ctx)
+        ctx->last_error = msg;
+    else
+        host_last_error() = msg;
     return st;
 }
 
@@ -258,7 +286,15 @@ bool build_bvh_levels(const std::vector<ShapeBounds>& bounds, uint32_t max_shape
 // The device records of `s` (nodes, nodes4, top_nodes, top_nodes_any, tris, prim_shade, prim_attr; s->layout, s->record_bytes)
 // from the tree in HBM and the scene's own uploaded arrays.  d_user_order (may be NULL): the caller's shape order, applied to
 // tree.order in place first (*order_applied says whether that happened).  Returns YK_LAYOUT_REASON_NONE, or the reason with the scene's records undefined.
+// The options "top_nodes" and "wide_bvh" are read from s->upd (the values the scene was created with), so that an update lays out what creation did.
 uint32_t layout_scene_device(yk_context* ctx, yk_scene* s, const DeviceTree& tree, const uint32_t* d_user_order, const uint8_t* d_mat_kind, bool has_attr, uint32_t tree_depth, bool* order_applied);
+
+// ------------------------------------------------------------------ yk_scene_update.hip
+// The device route of yk_scene_update[_device] (yk_scene_update.h): the finite test over d_points, then — nothing of the scene
+// is written before it has passed — the copies into the scene's arrays, leaf boxes, interior boxes level by level and the
+// layout.  Returns YK_LAYOUT_REASON_NONE, or the reason with the scene to be rewritten by the host route; *not_finite: the
+// test refused the points and the scene is untouched.  The caller holds the context's lock and has drained its streams.
+uint32_t update_scene_device(yk_context* ctx, yk_scene* s, const float* d_points, const float* d_normals, bool* not_finite);
 
 // ------------------------------------------------------------------ yk_scene_input.hip
 // The input stage of yk_scene_create_device (yk_scene_input.h); both enqueue on `st` and return the launch status.

@@ -14,6 +14,7 @@
 
 #include "yk_internal.h"
 #include "yk_scene_layout.h"
+#include "yk_scene_update.h"
 
 template <class T> static yk_status upload(yk_context* ctx, DevBuf& buf, const T* src, size_t count) {
     size_t bytes = std::max<size_t>(count * sizeof(T), 16);
@@ -567,10 +568,10 @@ static yk_status fetch_tree(int device, const DevBuf& d_nodes, const DevBuf& d_o
 
 const HostBvh* scene_host_tree(const yk_scene* s) {
     if (!s || !s->bvh) return nullptr;
-    if (s->bvh_lazy)
-        std::call_once(s->tree_once, [s] {
-            if (fetch_tree(s->device, s->tree_nodes, s->tree_order, (uint32_t)s->info.n_nodes, (uint32_t)s->info.n_shapes, *s->bvh_lazy) == YK_OK) s->tree_fetched.store(1u);
-        });
+    std::lock_guard<std::mutex> lock(s->tree_mu);  // a device-route update makes the copy stale again (yk_scene_update)
+    if (s->bvh_lazy && !s->tree_fetched.load() &&
+        fetch_tree(s->device, s->tree_nodes, s->tree_order, (uint32_t)s->info.n_nodes, (uint32_t)s->info.n_shapes, *s->bvh_lazy) == YK_OK)
+        s->tree_fetched.store(1u);
     return s->tree_fetched.load() ? s->bvh.get() : nullptr;
 }
 
@@ -618,6 +619,7 @@ static uint32_t layout_on_device(yk_context* ctx, SceneImage* img, yk_scene* s) 
     if (img->tree_on_device) {  // the host copy of the arrays is made when something asks for it (scene_host_tree)
         std::swap(s->tree_nodes, tree.nodes);
         std::swap(s->tree_order, tree.order);
+        std::swap(s->upd.depth, tree.depth);  // kept for the scene's updates
         s->bvh_lazy = img->bvh_mut;
         s->tree_fetched.store(0u);
     }
@@ -664,6 +666,26 @@ static void bind_device_scene(yk_scene* s, const yk_scene_desc* d) {
     for (DevBuf* b : scene_buffers(s)) s->info.device_bytes += b->bytes;
 }
 
+// What an update needs of the description after creation (yk_scene::UpdateState).
+static void init_update_state(const yk_context* ctx, yk_scene* s, const yk_scene_desc* d, const std::vector<uint32_t>& mat_kind) {
+    yk_scene::UpdateState& u = s->upd;
+    u.n_vertices = d->n_vertices;
+    u.has_normals = d->normals != nullptr;
+    u.has_uvs = d->uvs != nullptr;
+    u.top_nodes = ctx ? ctx->top_nodes : 0;
+    u.wide_bvh = ctx ? ctx->wide_bvh : 0;
+    u.mat_kind.assign(mat_kind.begin(), mat_kind.end());
+    u.sphere_bounds.resize(6 * (size_t)d->n_spheres);
+    for (uint32_t k = 0; k < d->n_spheres; ++k) {
+        const ShapeBounds b = sphere_bound(d->spheres[k]);
+        for (int a = 0; a < 3; ++a) {
+            u.sphere_bounds[6 * (size_t)k + a] = b.bmin[a];
+            u.sphere_bounds[6 * (size_t)k + 3 + a] = b.bmax[a];
+        }
+    }
+    if (!ctx && d->n_triangles) u.host_indices.assign(d->indices, d->indices + 3 * (size_t)d->n_triangles);
+}
+
 // Device half: one copy of the image in the HBM of ctx's device.
 yk_status yk_upload_scene_image(yk_context* ctx, const std::shared_ptr<SceneImage>& img, yk_scene** out) try {
     if (!out) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null out");
@@ -685,6 +707,7 @@ yk_status yk_upload_scene_image(yk_context* ctx, const std::shared_ptr<SceneImag
     s->info = img->info;
     s->build_info = img->build_info;
     s->shape_kind = img->shape_kind;
+    init_update_state(ctx, s, img->d, img->mat_kind);
     if (ctx) {
         if (!img->has_device_records) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "scene image was built without device records");
         const yk_scene_desc* d = img->d;
@@ -834,6 +857,7 @@ static yk_status create_scene_on_device(yk_context* ctx, const yk_scene_desc* d,
     yk_status rc = small_tables(ctx, d, &img);
     if (rc != YK_OK) return rc;
     std::vector<uint8_t> light_kind(std::max<uint32_t>(d->n_lights, 1), 0), mat_kind(img.mat_kind.begin(), img.mat_kind.end());
+    init_update_state(ctx, s, d, img.mat_kind);
     for (uint32_t l = 0; l < d->n_lights; ++l) light_kind[l] = (uint8_t)d->lights[l].kind;
     std::vector<ShapeBounds> sphere_b(std::max<uint32_t>(d->n_spheres, 1));
     for (uint32_t k = 0; k < d->n_spheres; ++k) sphere_b[k] = sphere_bound(d->spheres[k]);
@@ -912,6 +936,7 @@ static yk_status create_scene_on_device(yk_context* ctx, const yk_scene_desc* d,
     s->layout.seconds_layout = now_seconds() - l0;
     std::swap(s->tree_nodes, img.dtree.nodes);  // the host copy of the tree is made when something asks for it (scene_host_tree)
     std::swap(s->tree_order, img.dtree.order);
+    std::swap(s->upd.depth, img.dtree.depth);  // kept for the scene's updates
     s->bvh = img.bvh;
     s->bvh_lazy = img.bvh_mut;
     s->tree_fetched.store(0u);
@@ -976,6 +1001,200 @@ static yk_status create_scene_from_host_copy(yk_context* ctx, const yk_scene_des
     return YK_OK;
 }
 
+
+// ------------------------------------------------------------------ yk_scene_update
+// Update in place: the rule is yk_scene_update.h's, the device route yk_scene_update.hip's; here are the
+// host route and the entry points.
+
+static bool all_finite(const float* p, size_t n) {
+    for (size_t i = 0; i < n; ++i) {
+        uint32_t u;
+        std::memcpy(&u, p + i, 4);
+        if (upd::not_finite_bits(u)) return false;
+    }
+    return true;
+}
+
+// what the kernels are handed, after either route rewrote the records
+static void rebind_records(yk_scene* s) {
+    const yk_scene_layout_info& li = s->layout;
+    DevScene& ds = s->dev;
+    ds.nodes = s->nodes.as<DevNode>();
+    ds.nodes4 = li.wide ? s->nodes4.as<DevNode4>() : nullptr;
+    s->wide_auto = li.wide_auto != 0;
+    ds.top_nodes = s->top_nodes.as<DevNode>();
+    ds.n_top = li.n_top;
+    ds.top_nodes_any = s->top_nodes_any.as<DevNode>();
+    ds.n_top_any = li.n_top_any;
+    ds.tris = s->tris.as<float4>();
+    ds.prim_shade = s->prim_shade.as<uint4>();
+    ds.prim_attr = s->record_bytes[YK_RECORDS_PRIM_ATTR] ? s->prim_attr.as<float4>() : nullptr;
+    ds.root_ref = li.root_ref;
+    for (int k = 0; k < 3; ++k) {
+        ds.root_bmin[k] = s->info.bounds_min[k];
+        ds.root_bmax[k] = s->info.bounds_max[k];
+    }
+}
+
+// The host route: yk_bvh_refit on a copy of the host tree, layout_records_host, an upload of the arrays and the records.
+// `points` (and `normals`, may be NULL) are host arrays that have passed the finite test.  ctx NULL: a host-only scene.
+static yk_status update_scene_host(yk_context* ctx, yk_scene* s, const float* points, const float* normals) {
+    yk_scene::UpdateState& u = s->upd;
+    const size_t nt = s->n_triangles, ns = s->n_spheres, nv = u.n_vertices;
+    const HostBvh* old = scene_host_tree(s);
+    if (!old) return fail(ctx, YK_ERR_DEVICE, "the scene's tree could not be copied back from the device");
+    double t0 = now_seconds();
+    if (ctx) (void)hipSetDevice(ctx->device);
+    auto fetch = [&](auto& v, const DevBuf& src) -> hipError_t { return v.empty() ? hipSuccess : hipMemcpy(v.data(), src.p, v.size() * sizeof(v[0]), hipMemcpyDeviceToHost); };
+    std::vector<uint32_t> fetched_indices(ctx ? 3 * nt : 0);
+    if (ctx) HIP_TRY(ctx, fetch(fetched_indices, s->indices));
+    const uint32_t* indices = ctx ? fetched_indices.data() : u.host_indices.data();
+    std::vector<float> sb(6 * (nt + ns));  // per source shape
+    for (size_t i = 0; i < nt; ++i) {
+        float b[6];
+        (void)inp::tri_bound(points, indices, (uint32_t)i, b);
+        std::memcpy(&sb[6 * i], b, sizeof(b));
+    }
+    std::copy(u.sphere_bounds.begin(), u.sphere_bounds.end(), sb.begin() + 6 * nt);
+    std::shared_ptr<HostBvh> tree = std::make_shared<HostBvh>(*old);  // never through a tree that may be shared
+    yk_status rc = yk_bvh_refit(tree->nodes.data(), tree->nodes.size(), tree->shape_order.data(), nt + ns, sb.data());
+    if (rc != YK_OK) return fail(ctx, rc, "the scene's tree does not fit its shapes");
+    u.info.seconds_boxes = now_seconds() - t0;
+    t0 = now_seconds();
+    if (ctx) {
+        // the description's arrays as the host layout reads them: the new points and normals, everything else from the scene
+        std::vector<float> old_normals(u.has_normals && !normals ? 3 * nv : 0), uvs(u.has_uvs ? 2 * nv : 0);
+        std::vector<uint32_t> tri_mesh(nt), mesh_flags(s->mesh_flags.bytes / 4);
+        std::vector<int32_t> tri_material(nt), tri_al(nt);
+        std::vector<DevSphere> dev_spheres(ns);
+        HIP_TRY(ctx, fetch(old_normals, s->normals));
+        HIP_TRY(ctx, fetch(uvs, s->uvs));
+        HIP_TRY(ctx, fetch(tri_mesh, s->tri_mesh));
+        HIP_TRY(ctx, fetch(mesh_flags, s->mesh_flags));
+        HIP_TRY(ctx, fetch(tri_material, s->tri_material));
+        HIP_TRY(ctx, fetch(tri_al, s->tri_area_light));
+        HIP_TRY(ctx, fetch(dev_spheres, s->spheres));
+        std::vector<yk_sphere_desc> spheres(ns);
+        for (size_t k = 0; k < ns; ++k) {
+            std::memset(&spheres[k], 0, sizeof(spheres[k]));
+            spheres[k].material = dev_spheres[k].material;
+        }
+        yk_scene_desc d;
+        std::memset(&d, 0, sizeof(d));
+        d.n_triangles = (uint32_t)nt;
+        d.n_spheres = (uint32_t)ns;
+        d.n_vertices = (uint32_t)nv;
+        d.points = points;
+        d.normals = normals ? normals : (u.has_normals ? old_normals.data() : nullptr);
+        d.uvs = u.has_uvs ? uvs.data() : nullptr;
+        d.indices = indices;
+        d.tri_material = tri_material.data();
+        d.tri_area_light = tri_al.data();
+        d.spheres = spheres.data();
+        SceneImage img;
+        std::memset(&img.info, 0, sizeof(img.info));
+        img.bvh = tree;
+        img.d = &d;
+        img.info.n_interior = s->info.n_interior;
+        img.mat_kind.assign(u.mat_kind.begin(), u.mat_kind.end());
+        img.mesh_flags.swap(mesh_flags);
+        img.tri_mesh.swap(tri_mesh);
+        {
+            struct Options {  // the records as creation laid them out, whatever the context's options say today
+                yk_context* ctx;
+                int64_t top_nodes, wide_bvh;
+                ~Options() {
+                    ctx->top_nodes = top_nodes;
+                    ctx->wide_bvh = wide_bvh;
+                }
+            } restore{ctx, ctx->top_nodes, ctx->wide_bvh};
+            ctx->top_nodes = u.top_nodes;
+            ctx->wide_bvh = u.wide_bvh;
+            layout_records_host(ctx, &img);
+        }
+        if ((rc = upload(ctx, s->points, points, 3 * nv)) != YK_OK || (normals && (rc = upload(ctx, s->normals, normals, 3 * nv)) != YK_OK) ||
+            (rc = upload(ctx, s->nodes, img.dn.data(), img.dn.size())) != YK_OK || (rc = upload(ctx, s->nodes4, img.dn4.data(), img.dn4.size())) != YK_OK ||
+            (rc = upload(ctx, s->top_nodes, img.top.data(), img.top.size())) != YK_OK || (rc = upload(ctx, s->top_nodes_any, img.top_any.data(), img.top_any.size())) != YK_OK ||
+            (rc = upload(ctx, s->tris, img.tris.data(), img.tris.size())) != YK_OK || (rc = upload(ctx, s->prim_shade, img.prim_shade.data(), img.prim_shade.size())) != YK_OK ||
+            (rc = upload(ctx, s->prim_attr, img.prim_attr.data(), img.prim_attr.size())) != YK_OK)
+            return rc;
+        if (s->tree_nodes.p)  // the tree a later device-route update starts from
+            HIP_TRY(ctx, hipMemcpy(s->tree_nodes.p, tree->nodes.data(), tree->nodes.size() * sizeof(yk_bvh_node), hipMemcpyHostToDevice));
+        set_record_layout(s, s->info.n_interior, img.dn4.size(), img.top.size(), img.top_any.size(), s->info.n_shapes, u.has_normals || u.has_uvs, img.root_ref, img.wide_auto);
+    }
+    for (int k = 0; k < 3; ++k) {
+        s->info.bounds_min[k] = tree->nodes[0].bmin[k];
+        s->info.bounds_max[k] = tree->nodes[0].bmax[k];
+    }
+    {
+        std::lock_guard<std::mutex> lock(s->tree_mu);
+        s->bvh = tree;
+        s->bvh_lazy.reset();
+        s->tree_fetched.store(1u);
+    }
+    if (ctx) rebind_records(s);
+    u.info.seconds_records = now_seconds() - t0;
+    return YK_OK;
+}
+
+// everything the context has enqueued: renders of the scene that were enqueued before the update finish on the old geometry
+static yk_status drain_context(yk_context* ctx) {
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (WorkSet& w : ctx->ws) {
+        if (w.stream && w.stream != ctx->stream) HIP_TRY(ctx, hipStreamSynchronize(w.stream));
+        if (w.side) HIP_TRY(ctx, hipStreamSynchronize(w.side));
+    }
+    return YK_OK;
+}
+
+// The device route on device arrays; where it fails, the arrays go to the host once (h_points / h_normals when the caller
+// has them there already) and the host route rewrites the scene.
+static yk_status update_scene(yk_context* ctx, yk_scene* s, const float* d_points, const float* d_normals, const float* h_points, const float* h_normals) {
+    yk_scene::UpdateState& u = s->upd;
+    bool not_finite = false;
+    const uint32_t reason = update_scene_device(ctx, s, d_points, d_normals, &not_finite);
+    if (not_finite) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "points: coordinate not finite");
+    if (reason == YK_LAYOUT_REASON_NONE) {  // the host copy of the tree is stale: the next reader fetches the refitted one
+        std::lock_guard<std::mutex> lock(s->tree_mu);
+        std::shared_ptr<HostBvh> fresh = std::make_shared<HostBvh>();
+        fresh->max_leaf_shapes = s->bvh->max_leaf_shapes;
+        fresh->depth = s->bvh->depth;
+        fresh->split_failed = s->bvh->split_failed;
+        s->bvh = s->bvh_lazy = fresh;
+        s->tree_fetched.store(0u);
+        rebind_records(s);
+        u.info.route = YK_UPDATE_ROUTE_DEVICE;
+        u.info.reason = YK_LAYOUT_REASON_NONE;
+        return YK_OK;
+    }
+    (void)hipGetLastError();
+    const size_t n = 3 * (size_t)u.n_vertices;
+    std::vector<float> points(h_points ? 0 : n), normals(d_normals && !h_normals ? n : 0);
+    if (!h_points) HIP_TRY(ctx, hipMemcpy(points.data(), d_points, n * 4, hipMemcpyDeviceToHost));
+    if (d_normals && !h_normals) HIP_TRY(ctx, hipMemcpy(normals.data(), d_normals, n * 4, hipMemcpyDeviceToHost));
+    if (!h_points) h_points = points.data();
+    if (d_normals && !h_normals) h_normals = normals.data();
+    if (!all_finite(h_points, n)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "points: coordinate not finite");
+    const yk_status rc = update_scene_host(ctx, s, h_points, h_normals);
+    u.info.route = YK_UPDATE_ROUTE_HOST;
+    u.info.reason = reason;
+    return rc;
+}
+
+// the arguments both entry points refuse alike
+static yk_status check_update(yk_context* ctx, const yk_scene* s, const float* points, const float* normals) {
+    if (!s) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null scene");
+    if (!points) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null points");
+    if (normals && !s->upd.has_normals) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "normals given for a scene created without normals");
+    if (ctx ? (!s->on_device || s->device != ctx->device) : s->on_device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "scene was not created on this context's device");
+    return YK_OK;
+}
+
+static void finish_update(yk_scene* s, double t_begin) {
+    s->upd.info.n_updates += 1;
+    s->upd.info.seconds_total = now_seconds() - t_begin;
+}
+
 extern "C" {
 
 yk_status yk_scene_create(yk_context* ctx, const yk_scene_desc* d, yk_scene** out) {
@@ -1014,10 +1233,75 @@ yk_status yk_scene_create_device(yk_context* ctx, const yk_scene_desc* d, void* 
     return create_scene_from_host_copy(ctx, d, st, refused, out);
 } YK_CATCH(ctx)
 
+yk_status yk_scene_update(yk_context* ctx, yk_scene* s, const float* points, const float* normals) try {
+    std::unique_lock<std::recursive_mutex> yk_lock_;
+    if (ctx) yk_lock_ = std::unique_lock<std::recursive_mutex>(ctx->mu);
+    const double t_begin = now_seconds();
+    yk_status rc = check_update(ctx, s, points, normals);
+    if (rc != YK_OK) return rc;
+    yk_scene::UpdateState& u = s->upd;
+    const size_t n = 3 * (size_t)u.n_vertices;
+    if (!all_finite(points, n)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "points: coordinate not finite");
+    u.info.seconds_check = now_seconds() - t_begin;
+    if (ctx) {
+        (void)hipSetDevice(ctx->device);
+        if ((rc = drain_context(ctx)) != YK_OK) return rc;
+    }
+    if (ctx && s->layout.layout == YK_LAYOUT_DEVICE) {  // the arrays go up and the device route runs
+        DevScratch tmp;
+        float *d_points = nullptr, *d_normals = nullptr;
+        if (tmp.get(d_points, n) && (!normals || tmp.get(d_normals, n)) && hipMemcpy(d_points, points, n * 4, hipMemcpyHostToDevice) == hipSuccess &&
+            (!normals || hipMemcpy(d_normals, normals, n * 4, hipMemcpyHostToDevice) == hipSuccess)) {
+            rc = update_scene(ctx, s, d_points, d_normals, points, normals);
+        } else {
+            (void)hipGetLastError();
+            rc = update_scene_host(ctx, s, points, normals);
+            u.info.route = YK_UPDATE_ROUTE_HOST;
+            u.info.reason = YK_LAYOUT_REASON_OUT_OF_MEMORY;
+        }
+    } else {
+        rc = update_scene_host(ctx, s, points, normals);
+        u.info.route = YK_UPDATE_ROUTE_HOST;
+        u.info.reason = YK_LAYOUT_REASON_NONE;
+    }
+    if (rc == YK_OK) finish_update(s, t_begin);
+    return rc;
+} YK_CATCH(ctx)
+
+yk_status yk_scene_update_device(yk_context* ctx, yk_scene* s, const float* d_points, const float* d_normals, void* stream) try {
+    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
+    YK_LOCK(ctx);
+    const double t_begin = now_seconds();
+    yk_status rc = check_update(ctx, s, d_points, d_normals);
+    if (rc != YK_OK) return rc;
+    (void)hipSetDevice(ctx->device);
+    yk_scene_desc d;  // the pointer checks of yk_scene_create_device, with its messages
+    std::memset(&d, 0, sizeof(d));
+    d.n_vertices = s->upd.n_vertices;
+    d.points = d_points;
+    d.normals = d_normals;
+    if ((rc = check_device_arrays(ctx, &d)) != YK_OK) return rc;
+    if (stream) {  // the caller's arrays are complete where its stream stands now
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_in, (hipStream_t)stream));
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_in, 0));
+    }
+    if ((rc = drain_context(ctx)) != YK_OK) return rc;
+    rc = update_scene(ctx, s, d_points, d_normals, nullptr, nullptr);
+    if (rc == YK_OK) finish_update(s, t_begin);
+    return rc;
+} YK_CATCH(ctx)
+
+yk_status yk_scene_get_update_info(const yk_scene* s, yk_scene_update_info* out) {
+    if (!s || !out) return YK_ERR_INVALID_ARGUMENT;
+    *out = s->upd.info;
+    return YK_OK;
+}
+
 void yk_scene_destroy(yk_scene* s) {
     if (!s) return;
     if (s->device >= 0) (void)hipSetDevice(s->device);
     for (DevBuf* b : scene_buffers(s)) b->release();
+    for (DevBuf* b : {&s->upd.depth, &s->upd.list, &s->upd.sphere_b, &s->upd.mat_kind_d, &s->upd.words}) b->release();
     delete s;
 }
 

@@ -143,9 +143,9 @@ uint32_t layout_scene_device(yk_context* ctx, yk_scene* s, const DeviceTree& tre
     uint32_t* order = tree.order.as<uint32_t>();
     const bool root_leaf = (tree.root_words[7] >> 24) != 0u;
     const uint32_t n_interior = (n - 1u) / 2u;  // a full binary tree
-    const uint32_t cap_closest = (uint32_t)std::min<int64_t>(std::min<int64_t>(ctx->top_nodes, trace_top_nodes()), YK_TOP_MAX);
-    const uint32_t cap_any = (uint32_t)std::min<int64_t>(std::min<int64_t>(ctx->top_nodes, trace_top_nodes_any()), YK_TOP_MAX);
-    const bool wide = ctx->wide_bvh != 0 && !root_leaf && tree_depth <= 64;
+    const uint32_t cap_closest = (uint32_t)std::min<int64_t>(std::min<int64_t>(s->upd.top_nodes, trace_top_nodes()), YK_TOP_MAX);
+    const uint32_t cap_any = (uint32_t)std::min<int64_t>(std::min<int64_t>(s->upd.top_nodes, trace_top_nodes_any()), YK_TOP_MAX);
+    const bool wide = s->upd.wide_bvh != 0 && !root_leaf && tree_depth <= 64;
 
     DevScratch tmp;
     uint32_t *d_index = nullptr, *d_bsum = nullptr, *d_slot = nullptr, *d_words = nullptr;
@@ -218,7 +218,7 @@ uint32_t layout_scene_device(yk_context* ctx, yk_scene* s, const DeviceTree& tre
         LAY_TRY(s->nodes4.ensure(16));
     }
 #undef LAY_TRY
-    set_record_layout(s, n_interior, n4, words[2], words[3], np, has_attr, root_leaf ? (YK_LEAF_BIT | tree.root_words[6]) : 0u, wide && ctx->wide_bvh == 2);
+    set_record_layout(s, n_interior, n4, words[2], words[3], np, has_attr, root_leaf ? (YK_LEAF_BIT | tree.root_words[6]) : 0u, wide && s->upd.wide_bvh == 2);
     return YK_LAYOUT_REASON_NONE;
 }
 
