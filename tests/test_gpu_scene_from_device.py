@@ -254,6 +254,27 @@ def test_equal_counts_falls_back_to_the_host_builder(yk, contexts):
     assert got["who"] == (0, 1, abi.LAYOUT_DEVICE, 0)  # host recursion, YK_BVH_REASON_SPLIT_METHOD; the layout still on the device
 
 
+def test_the_fallback_leaves_the_contexts_options_alone(yk):
+    """The fallback asks the host path for the device layout (and, where the builder did not refuse, the device builder) as
+    an argument: the context's "bvh_builder" and "scene_layout" stay 0 for the scene created next."""
+    ctx = yk.Context(0)
+    try:
+        sd = scenes.by_name("city-tiny")
+        sd.split_method, sd.max_shapes_in_node = abi.SPLIT_EQUAL_COUNTS, 2
+        s = yk.Scene.from_device(ctx, sd, _tensors(sd))
+        bi, li = s.build_info(), s.layout_info()
+        assert (bi.builder, bi.reason, li.layout, li.reason) == (0, 1, abi.LAYOUT_DEVICE, 0)  # it fell back: the host recursion, the device layout
+        s.close()
+        sah = scenes.by_name("city-tiny")
+        sah.split_method = abi.SPLIT_SAH
+        t = yk.Scene(ctx, sah)
+        assert t.layout_info().layout == abi.LAYOUT_HOST
+        assert _ffi.BVH_BUILDER_NAMES[t.build_info().builder] == "host recursion"
+        t.close()
+    finally:
+        ctx.close()
+
+
 @pytest.mark.parametrize("value", [np.nan, np.inf])
 def test_a_non_finite_coordinate_falls_back(yk, contexts, value):
     """One coordinate of one vertex of city-tiny made NaN, and +inf: reason NON_FINITE, and the host-input scene's records,

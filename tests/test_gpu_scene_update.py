@@ -293,3 +293,36 @@ def test_points_produced_on_a_side_stream(yk, contexts):
     _assert_same_scene(_snapshot(s), want)
     assert float(busy[0, 0]) == 1.0
     s.close()
+
+
+# ---- 9. the options an update lays out with are creation's
+@pytest.mark.parametrize("source", ["host-input", "device-input"])
+def test_an_update_lays_out_what_creation_did_whatever_the_context_says_today(yk, source):
+    """A scene created with top_nodes = 3 and wide_bvh = 2 keeps its three-node tree tops and both node layouts through an
+    update made after the context's two options were set to 0, by the host route (host input, host layout) and by the device
+    route (device input); a scene created afterwards on the same context has neither, so the update did not touch the
+    live options either."""
+    sd = SCENES["city-tiny"]()
+    ctx = yk.Context(0, top_nodes=3, wide_bvh=2)
+    try:
+        arrays = _tensors(sd)
+        s = yk.Scene(ctx, sd) if source == "host-input" else yk.Scene.from_device(ctx, sd, arrays)
+        before = _snapshot(s)
+        assert before["head"][1:] == (3, 3, 1, 1)  # n_top, n_top_any, wide, wide_auto
+        assert before["who"][2] == (abi.LAYOUT_HOST if source == "host-input" else abi.LAYOUT_DEVICE)
+        ctx.set_option("top_nodes", 0)
+        ctx.set_option("wide_bvh", 0)
+        if source == "host-input":
+            s.update(np.ascontiguousarray(sd.points, dtype=np.float32))
+        else:
+            s.update(arrays["points"])
+        i = s.update_info()
+        assert (i.n_updates, i.route, i.reason) == (1, abi.UPDATE_ROUTE_HOST if source == "host-input" else abi.UPDATE_ROUTE_DEVICE, 0)
+        _assert_same_scene(_snapshot(s), before)
+        s.close()
+        fresh = yk.Scene(ctx, sd)
+        li = fresh.layout_info()
+        assert (li.n_top, li.n_top_any, li.wide, li.wide_auto) == (0, 0, 0, 0)
+        fresh.close()
+    finally:
+        ctx.close()

@@ -89,3 +89,23 @@ def test_host_tensors_and_unknown_names_are_refused(yk, checked_only):
     with pytest.raises(ValueError, match="unknown device arrays"):
         yk.Scene.from_device(checked_only, sd, dict(_tensors(sd), vertices=0))
     assert set(yk.Scene.DEVICE_ARRAYS) == {f for f, _ in abi.SceneDesc._fields_ if f in ("points", "normals", "uvs", "indices", "tri_mesh", "tri_material", "tri_area_light", "shape_order")}
+
+
+@needs_torch
+def test_scene_update_refuses_tensors_with_the_messages_of_from_device(yk, checked_only):
+    """Scene.update and Scene.from_device check their tensors with one helper: wrong element type, wrong strides, a short
+    tensor and a host tensor raise the same text from both, before the library is reached."""
+    sd = scenes.by_name("city-tiny")
+    nv = len(sd.points)
+    scene = yk.Scene.__new__(yk.Scene)
+    scene.ctx, scene.data, scene.h = checked_only, sd, None
+    good = _tensors(sd)["points"]
+    bad = {"element type": good.to(torch.float64), "contiguous": torch.zeros((3, nv), dtype=torch.float32).t(), "elements": good[:-1].contiguous(), "not on the context's device": good}
+    for what, points in bad.items():
+        with pytest.raises(ValueError, match=what) as from_update:
+            scene.update(points)
+        with pytest.raises(ValueError, match=what) as from_create:
+            yk.Scene.from_device(checked_only, sd, dict(_tensors(sd), points=points))
+        assert str(from_update.value) == str(from_create.value) and str(from_update.value).startswith("points: ")
+    with pytest.raises(ValueError, match="normals: .*float64"):  # every array's shape and type before any array's place
+        scene.update(good, good.to(torch.float64))

@@ -1,6 +1,6 @@
 """The two order rules of the device scene layout ("scene_layout" = 1, yuki_amd/csrc/yk_scene_layout.h), host instance,
 proven without a GPU: the breadth-first tree top under the host loop's admission rule and the slot numbering of the
-4-wide collapse, both in closed form, against a restatement of the sequential loops of yk_scene.cpp
+4-wide collapse, both in closed form, against a restatement of the sequential loops of yk_scene_records.cpp
 (layout_records_host: build_top and the DevNode4 stack walk)."""
 import ctypes as C
 

@@ -687,6 +687,40 @@ class Context:
             pass
 
 
+def _device_addresses(given, table, ctx, stream):
+    """The device arrays of Scene.from_device and Scene.update: `given` maps names to torch tensors, raw device addresses
+    (int) or None, `table` maps every name to (accepted element types, expected element count).  Checks every tensor's
+    element type, contiguity and element count first and only then where the tensors are (ValueError); an address is
+    taken as it is.  Returns ({name: address or None}, the stream to pass on: an int or None).  With `stream` None the
+    current torch stream of the first tensor's device is waited for."""
+    address, tensors = {}, []
+    for name, (dtypes, expected) in table.items():
+        a = given.get(name)
+        if a is None or isinstance(a, (int, np.integer)):
+            address[name] = int(a) if a else None
+            continue
+        if not hasattr(a, "data_ptr"):
+            raise ValueError(f"{name}: expected a torch tensor or a device address, got {type(a).__name__}")
+        if str(a.dtype).replace("torch.", "") not in dtypes:
+            raise ValueError(f"{name}: element type {a.dtype}, expected {' or '.join(dtypes)}")
+        if not a.is_contiguous():
+            raise ValueError(f"{name}: the tensor is not contiguous")
+        if a.numel() != expected:
+            raise ValueError(f"{name}: {a.numel()} elements, expected {expected}")
+        tensors.append((name, a))
+    for name, a in tensors:  # ... and only then where they are
+        if not a.is_cuda or a.device.index != ctx.device:
+            raise ValueError(f"{name}: the tensor is on {a.device}, not on the context's device {ctx.device}")
+        address[name] = a.data_ptr() or None
+    if stream is None and tensors:
+        import torch
+
+        torch.cuda.current_stream(tensors[0][1].device).synchronize()
+    elif stream is not None and not isinstance(stream, int):
+        stream = stream.cuda_stream
+    return address, stream
+
+
 class Scene:
     """scene/mod.rs:41-49: shapes + BVH + lights + background.  `ctx=None` builds
     the BVH on the host only (no GPU needed)."""
@@ -729,31 +763,7 @@ class Scene:
             raise ValueError(f"unknown device arrays {sorted(unknown)}; the names are {sorted(cls.DEVICE_ARRAYS)}")
         counts = {"v": int(scene_data.points.shape[0]), "t": int(scene_data.indices.shape[0])}
         counts["s"] = counts["t"] + len(scene_data.spheres)
-        address, tensors = {}, []
-        for name, (_, dtypes, per, k) in cls.DEVICE_ARRAYS.items():
-            a = arrays.get(name)
-            if a is None or isinstance(a, (int, np.integer)):
-                address[name] = int(a) if a else None
-                continue
-            if not hasattr(a, "data_ptr"):
-                raise ValueError(f"{name}: expected a torch tensor or a device address, got {type(a).__name__}")
-            if str(a.dtype).replace("torch.", "") not in dtypes:
-                raise ValueError(f"{name}: element type {a.dtype}, expected {' or '.join(dtypes)}")
-            if not a.is_contiguous():
-                raise ValueError(f"{name}: the tensor is not contiguous")
-            if a.numel() != k * counts[per]:
-                raise ValueError(f"{name}: {a.numel()} elements, expected {k * counts[per]}")
-            tensors.append((name, a))
-        for name, a in tensors:  # ... and only then where they are
-            if not a.is_cuda or a.device.index != ctx.device:
-                raise ValueError(f"{name}: the tensor is on {a.device}, not on the context's device {ctx.device}")
-            address[name] = a.data_ptr() or None
-        if stream is None and tensors:
-            import torch
-
-            torch.cuda.current_stream(tensors[0][1].device).synchronize()
-        elif stream is not None and not isinstance(stream, int):
-            stream = stream.cuda_stream
+        address, stream = _device_addresses(arrays, {name: (dtypes, k * counts[per]) for name, (_, dtypes, per, k) in cls.DEVICE_ARRAYS.items()}, ctx, stream)
         self = cls.__new__(cls)
         self.ctx, self.data = ctx, scene_data
         d, keep = scene_data.desc(LightFactory)
@@ -763,7 +773,7 @@ class Scene:
         h = C.c_void_p()
         check(lib().yk_scene_create_device(ctx.h, C.byref(d), C.c_void_p(stream) if stream else None, C.byref(h)), ctx.h)
         self.h = h
-        del keep, tensors
+        del keep
         return self
 
     def close(self):
@@ -829,30 +839,7 @@ class Scene:
             return
         if self.ctx is None:
             raise ValueError("a host-only scene is updated with numpy arrays")
-        address, tensors = {}, []
-        for name, a in given.items():
-            if a is None or isinstance(a, (int, np.integer)):
-                address[name] = int(a) if a else None
-                continue
-            if not hasattr(a, "data_ptr"):
-                raise ValueError(f"{name}: expected a torch tensor or a device address, got {type(a).__name__}")
-            if str(a.dtype).replace("torch.", "") != "float32":
-                raise ValueError(f"{name}: element type {a.dtype}, expected float32")
-            if not a.is_contiguous():
-                raise ValueError(f"{name}: the tensor is not contiguous")
-            if a.numel() != 3 * nv:
-                raise ValueError(f"{name}: {a.numel()} elements, expected {3 * nv}")
-            tensors.append((name, a))
-        for name, a in tensors:  # ... and only then where they are
-            if not a.is_cuda or a.device.index != self.ctx.device:
-                raise ValueError(f"{name}: the tensor is on {a.device}, not on the context's device {self.ctx.device}")
-            address[name] = a.data_ptr() or None
-        if stream is None and tensors:
-            import torch
-
-            torch.cuda.current_stream(tensors[0][1].device).synchronize()
-        elif stream is not None and not isinstance(stream, int):
-            stream = stream.cuda_stream
+        address, stream = _device_addresses(given, {name: (("float32",), 3 * nv) for name in given}, self.ctx, stream)
         vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
         check(lib().yk_scene_update_device(self.ctx.h, self.h, vp(address["points"]), vp(address["normals"]), vp(stream)), self.ctx.h)
 

@@ -16,6 +16,7 @@
 #include "yk_host.h"
 #include "yk_kernels.h"
 #include "yk_scene_input.h"
+#include "yk_scene_records.h"
 
 using namespace yk;
 
@@ -39,16 +40,29 @@ struct DevBuf {
     }
     template <class T> T* as() const { return reinterpret_cast<T*>(p); }
 };
+// `bytes` of a host array into `buf`, grown to hold them (never smaller than 16 bytes)
+static inline hipError_t put_host_array(DevBuf& buf, const void* src, size_t bytes) {
+    hipError_t e = buf.ensure(std::max<size_t>(bytes, 16));
+    if (e == hipSuccess && bytes) e = hipMemcpy(buf.p, src, bytes, hipMemcpyHostToDevice);
+    return e;
+}
+
+// ... and what a failed device call says to the code that falls back instead of failing (YK_LAYOUT_REASON_*); clears the error
+static inline uint32_t layout_reason_of(hipError_t e) {
+    (void)hipGetLastError();
+    return e == hipErrorOutOfMemory ? YK_LAYOUT_REASON_OUT_OF_MEMORY : YK_LAYOUT_REASON_DEVICE_ERROR;
+}
 
 // A function's device temporaries: freed on every way out, unless handed on.
 struct DevScratch {
     std::vector<void*> all;
+    hipError_t err = hipSuccess;  // of the allocation that failed
     ~DevScratch() {
         for (void* p : all) (void)hipFree(p);
     }
     template <class T> bool get(T*& out, size_t count) {
         void* p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(count * sizeof(T), 16)) != hipSuccess) {
+        if ((err = hipMalloc(&p, std::max<size_t>(count * sizeof(T), 16))) != hipSuccess) {
             (void)hipGetLastError();
             return false;
         }
@@ -187,7 +201,7 @@ struct yk_scene {
     struct UpdateState {
         uint32_t n_vertices = 0;
         bool has_normals = false, has_uvs = false;
-        int64_t top_nodes = 0, wide_bvh = 0;  // the context's options the records were laid out with
+        LayoutOptions opt;  // the context's "top_nodes" / "wide_bvh" at creation: every layout of the scene, then and at an update, reads these
         std::vector<float> sphere_bounds;     // six floats a sphere: Sphere::world_bound as at creation
         std::vector<uint8_t> mat_kind;        // device BSDF kind (MK_*) per material
         std::vector<uint32_t> host_indices;   // host-only scenes
@@ -251,11 +265,17 @@ static inline yk_status fail(yk_context* ctx, yk_status st, const std::string& m
     catch (const std::exception& e) { return fail(ctx, YK_ERR_INVALID_ARGUMENT, std::string("exception: ") + e.what()); }
 
 
-// Everything yk_scene_create derives from a scene description on the host — the reference's BVH
-// (BoundingVolumeHierarchy::new, bvh.rs:39-115) and the device records laid out from it.  Built once;
-// uploaded to one device (yk_scene_create) or to every device of a yk_multi (yk_multi_scene_create).
+// The inputs of the scene pipeline as yk_scene_create derives them from a description on the host — the
+// reference's BVH (BoundingVolumeHierarchy::new, bvh.rs:39-115), the small tables, the context's LayoutOptions — and, where
+// the host lays out, the records.  Built once; uploaded to one device or to every device of a yk_multi.
 struct SceneImage;
-yk_status yk_build_scene_image(yk_context* opt_ctx, const yk_scene_desc* d, std::shared_ptr<SceneImage>& out, bool device_builder_allowed = true);  // false: yk_multi_scene_create
+// What yk_build_scene_image builds: who builds the tree, who lays out the records, and the YK_LAYOUT_REASON_* to report
+// where the device layout was asked for but is not attempted.
+struct SceneBuild {
+    bool device_builder, device_layout;
+    uint32_t layout_reason;
+};
+yk_status yk_build_scene_image(yk_context* opt_ctx, const yk_scene_desc* d, std::shared_ptr<SceneImage>& out, const SceneBuild& what);
 yk_status yk_upload_scene_image(yk_context* ctx, const std::shared_ptr<SceneImage>& img, yk_scene** out);
 
 // The scene's host tree with its node and shape-order arrays, copied back from HBM on the first call when the scene kept
@@ -286,7 +306,7 @@ bool build_bvh_levels(const std::vector<ShapeBounds>& bounds, uint32_t max_shape
 // The device records of `s` (nodes, nodes4, top_nodes, top_nodes_any, tris, prim_shade, prim_attr; s->layout, s->record_bytes)
 // from the tree in HBM and the scene's own uploaded arrays.  d_user_order (may be NULL): the caller's shape order, applied to
 // tree.order in place first (*order_applied says whether that happened).  Returns YK_LAYOUT_REASON_NONE, or the reason with the scene's records undefined.
-// The options "top_nodes" and "wide_bvh" are read from s->upd (the values the scene was created with), so that an update lays out what creation did.
+// "top_nodes" and "wide_bvh" are s->upd.opt, the values captured at creation, as for the host layout.
 uint32_t layout_scene_device(yk_context* ctx, yk_scene* s, const DeviceTree& tree, const uint32_t* d_user_order, const uint8_t* d_mat_kind, bool has_attr, uint32_t tree_depth, bool* order_applied);
 
 // ------------------------------------------------------------------ yk_scene_update.hip
@@ -318,6 +338,12 @@ yk_status stage_sample_table(yk_context* ctx, hipStream_t st, const uint32_t* sa
 // The exact sizes of a scene's seven record buffers (s->record_bytes) and the head of s->layout from what was laid out,
 // for whoever laid it out.  n_wide: DevNode4 records; 0 says there is no 4-wide layout.
 void set_record_layout(yk_scene* s, size_t n_interior, size_t n_wide, size_t n_top, size_t n_top_any, size_t n_shapes, bool has_attr, uint32_t root_ref, bool wide_auto);
+// A host tree into HBM for device work (the device layout, the plan of the device-route update): nodes, every node's
+// depth (lay::node_depths) and the order, with the counts and node 0.
+hipError_t upload_host_tree(const HostBvh& bvh, DeviceTree& tree);
+// The tree's three buffers become the scene's (tree_nodes, tree_order, upd.depth); what the scene held comes back in
+// `tree`.  `lazy` (may be NULL): the host tree whose arrays are still to be fetched from them (scene_host_tree).
+void adopt_device_tree(yk_scene* s, DeviceTree& tree, const std::shared_ptr<HostBvh>& lazy);
 Material make_material(const yk_material_desc& m);  // per-hit constants folded (GGX alpha, Oren-Nayar A / B)
 DevLight make_light(const yk_light_desc& l);
 

@@ -370,7 +370,8 @@ yk_status yk_multi_scene_create(yk_multi* m, const yk_scene_desc* desc, yk_multi
     *out = nullptr;
     // the host work — validation, BoundingVolumeHierarchy::new, device records — happens once
     std::shared_ptr<SceneImage> img;
-    yk_status st = yk_build_scene_image(m->ctx[0], desc, img, false);  // one host tree serves every device: the host recursion builds it
+    const SceneBuild host{false, false, m->ctx[0]->scene_layout == 1 ? (uint32_t)YK_LAYOUT_REASON_MULTI : 0u};  // one host tree, one set of host records for every device
+    yk_status st = yk_build_scene_image(m->ctx[0], desc, img, host);
     if (st != YK_OK) return mfail(m, st, m->ctx[0]->last_error);
     std::unique_ptr<yk_multi_scene> s(new yk_multi_scene());
     s->owner = m;

@@ -1,5 +1,9 @@
-// yk_scene.cpp — scene description -> the reference's BVH (host) -> device records -> one copy per device.
-// (yk_scene_create, bvh.rs:39-115 via yk_host.cpp; the record layouts are in yk_device.h and DESIGN.md §3.)
+// yk_scene.cpp — a scene's creation and update, one pipeline (the record layouts are in yk_device.h):
+//   inputs   a tree (the reference's BVH, bvh.rs:39-115 via yk_host.cpp, or the device builder's), the geometry, the small
+//            tables and the LayoutOptions captured at creation — from a description, from arrays in HBM, or from the scene
+//   layout   layout_records_host (yk_scene_records.cpp) + upload_records, or layout_scene_device (yk_scene_layout.hip)
+//   bind     bind_records, at creation (inside bind_device_scene) and after an update
+// Which builder and which layout is an argument (SceneBuild); nothing here writes a context option.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,11 +20,24 @@
 #include "yk_scene_layout.h"
 #include "yk_scene_update.h"
 
+// host array -> device buffer.  Not put_host_array inside HIP_TRY: the context's message names the call that failed
+// ("buf.ensure(bytes): ..." or "hipMemcpy(...): ..."), and those texts stay.
 template <class T> static yk_status upload(yk_context* ctx, DevBuf& buf, const T* src, size_t count) {
     size_t bytes = std::max<size_t>(count * sizeof(T), 16);
     HIP_TRY(ctx, buf.ensure(bytes));
     if (count) HIP_TRY(ctx, hipMemcpy(buf.p, src, count * sizeof(T), hipMemcpyHostToDevice));
     return YK_OK;
+}
+
+// a scene under construction: destroyed (yk_scene_destroy) on every early return and on an exception, released into *out at the end
+typedef std::unique_ptr<yk_scene, void (*)(yk_scene*)> ScenePtr;
+
+// the counts a scene keeps of its description
+static void set_scene_counts(yk_scene* s, const yk_scene_desc* d) {
+    s->n_triangles = d->n_triangles;
+    s->n_spheres = d->n_spheres;
+    s->n_lights = d->n_lights;
+    for (uint32_t l = 0; l < d->n_lights; ++l) s->n_delta_lights += d->lights[l].kind != YK_LIGHT_RECT ? 1u : 0u;
 }
 
 Material make_material(const yk_material_desc& m) {
@@ -110,36 +127,34 @@ void set_record_layout(yk_scene* s, size_t n_interior, size_t n_wide, size_t n_t
     s->record_bytes[YK_RECORDS_PRIM_ATTR] = has_attr ? 4 * n_shapes * sizeof(float4) : 0;
 }
 
-// Everything yk_scene_create derives from a scene description on the host (yk_internal.h).
+// The inputs of the pipeline as creation derives them from a scene description on the host (yk_internal.h): the tree, the
+// small tables, the options the records are laid out with and — host layout — the records themselves.
 struct SceneImage {
     std::shared_ptr<const HostBvh> bvh;
     std::shared_ptr<HostBvh> bvh_mut;  // the same tree, writable: its arrays are filled late when the builder left them in HBM
-    // "scene_layout" = 1 (single-device scenes): the records below dn .. prim_attr stay empty and yk_upload_scene_image lays them
-    // out on the device — from dtree, where the device builder left the tree (tree_on_device), or from an upload of the host tree
+    // a device layout (single-device scenes): `rec` stays empty and yk_upload_scene_image lays the records out on the
+    // device — from dtree, where the device builder left the tree (tree_on_device), or from an upload of the host tree
     bool device_layout = false, tree_on_device = false, order_applied = false;  // order_applied: the caller's shape order went into dtree.order
     uint32_t layout_reason = 0;  // YK_LAYOUT_REASON_*: why a device layout that was asked for is not attempted
     DeviceTree dtree;
     ~SceneImage() { dtree.release(); }
     const yk_scene_desc* d = nullptr;  // BORROWED: the caller's arrays (indices, points, normals, uvs, tri_material) are uploaded straight
                                        // from the description, so an image is only valid inside the call that built it
-    uint32_t n_triangles = 0, n_spheres = 0, n_lights = 0, n_delta_lights = 0;
     yk_scene_info info;  // host part: node counts, bounds, build time
     yk_bvh_build_info build_info;
-    bool has_device_records = false, wide_auto = false;  // wide_auto, root_ref: of the host layout
-    uint32_t root_ref = 0;
-    std::vector<DevNode> dn, top, top_any;
-    std::vector<DevNode4> dn4;
-    std::vector<float4> tris, texels, prim_attr;
-    std::vector<uint4> prim_shade, tex_info;
-    std::vector<uint32_t> mesh_flags, tri_mesh, mat_kind;  // mat_kind: device BSDF kind (MK_*) per material
+    LayoutOptions opt;  // the context's, captured when the image is built
+    bool has_device_records = false;
+    SceneRecords rec;  // of the host layout
+    std::vector<float4> texels;
+    std::vector<uint4> tex_info;
+    std::vector<uint32_t> mesh_flags, tri_mesh;
+    std::vector<uint8_t> mat_kind;  // device BSDF kind (MK_*) per material
     std::vector<int32_t> tri_al;
     std::vector<uint8_t> shape_kind;  // source shape -> BSDF kind (yk_scene::shape_kind)
     std::vector<Material> mats;
     std::vector<DevSphere> spheres;
     std::vector<DevLight> lights;
 };
-
-static void layout_records_host(const yk_context* ctx, SceneImage* s);
 
 // ---- the steps of yk_build_scene_image, in its order
 // arrays_on_host false (yk_scene_create_device): the large arrays are device pointers; the two loops over the triangles are
@@ -228,16 +243,16 @@ static yk_status shape_bounds(yk_context* ctx, const yk_scene_desc* d, std::vect
 }
 
 // the tree into s->bvh_mut (or, "scene_layout" = 1 and the device builder, into s->dtree), who built it and how long it took
-static yk_status build_tree(yk_context* ctx, const yk_scene_desc* d, const std::vector<ShapeBounds>& sb, bool device_builder_allowed, SceneImage* s) {
+static yk_status build_tree(yk_context* ctx, const yk_scene_desc* d, const std::vector<ShapeBounds>& sb, bool device_builder, SceneImage* s) {
     double t0 = now_seconds();
-    // Who builds the tree: the host recursion unless the context's "bvh_builder" asks for the device or the environment
+    // Who builds the tree: the host recursion unless the caller asks for the device builder or the environment
     // (YK_BVH_BUILDER=levels, YK_BVH_SMALL_RANGE=n; next to YK_BVH_THREADS) for the host instance of the level algorithm.
     // A level builder that refuses leaves its reason in the build info and the recursion builds the same tree.
     yk_bvh_build_info& bi = s->build_info;
     std::memset(&bi, 0, sizeof(bi));
     bool built = false;
     const char* env_builder = std::getenv("YK_BVH_BUILDER");
-    if (ctx && ctx->bvh_builder == 1 && device_builder_allowed) {
+    if (ctx && device_builder) {
         built = build_bvh_device(ctx, sb, d->max_shapes_in_node, d->split_method, (uint32_t)ctx->bvh_small_range, *s->bvh_mut, bi, s->device_layout ? &s->dtree : nullptr);
         s->tree_on_device = built && s->device_layout;
     } else if (env_builder && std::strcmp(env_builder, "levels") == 0) {
@@ -276,7 +291,7 @@ static yk_status small_tables(yk_context* ctx, const yk_scene_desc* d, SceneImag
     s->mat_kind.assign(s->mats.size(), 0u);
     for (uint32_t m = 0; m < d->n_materials; ++m) {
         s->mats[m] = make_material(d->materials[m]);
-        s->mat_kind[m] = s->mats[m].kind & 7u;
+        s->mat_kind[m] = (uint8_t)(s->mats[m].kind & 7u);
     }
     s->mesh_flags.assign(std::max<uint32_t>(d->n_meshes, 1), 0);
     for (uint32_t m = 0; m < d->n_meshes; ++m)
@@ -309,8 +324,8 @@ static yk_status host_tables(yk_context* ctx, const yk_scene_desc* d, SceneImage
     yk_status st = small_tables(ctx, d, s);
     if (st != YK_OK) return st;
     s->shape_kind.resize(s->info.n_shapes);
-    for (uint32_t i = 0; i < d->n_triangles; ++i) s->shape_kind[i] = (uint8_t)s->mat_kind[d->tri_material[i]];
-    for (uint32_t k = 0; k < d->n_spheres; ++k) s->shape_kind[(size_t)d->n_triangles + k] = (uint8_t)s->mat_kind[d->spheres[k].material];
+    for (uint32_t i = 0; i < d->n_triangles; ++i) s->shape_kind[i] = s->mat_kind[d->tri_material[i]];
+    for (uint32_t k = 0; k < d->n_spheres; ++k) s->shape_kind[(size_t)d->n_triangles + k] = s->mat_kind[d->spheres[k].material];
     s->tri_mesh.assign(d->n_triangles, 0);
     if (d->tri_mesh) std::memcpy(s->tri_mesh.data(), d->tri_mesh, sizeof(uint32_t) * d->n_triangles);
     s->tri_al.assign(d->n_triangles, -1);
@@ -318,9 +333,32 @@ static yk_status host_tables(yk_context* ctx, const yk_scene_desc* d, SceneImage
     return YK_OK;
 }
 
+// The host layout of an image: its input from the description and the image's own tables.
+static void layout_image_host(SceneImage* s) {
+    const yk_scene_desc* d = s->d;
+    std::vector<int32_t> sphere_material(d->n_spheres);
+    for (uint32_t k = 0; k < d->n_spheres; ++k) sphere_material[k] = d->spheres[k].material;
+    HostLayoutInput in;
+    in.bvh = s->bvh.get();
+    in.n_interior = s->info.n_interior;
+    in.indices = d->indices;
+    in.points = d->points;
+    in.normals = d->normals;
+    in.uvs = d->uvs;
+    in.tri_material = d->tri_material;
+    in.tri_area_light = s->tri_al.data();
+    in.tri_mesh = s->tri_mesh.data();
+    in.mesh_flags = s->mesh_flags.data();
+    in.n_triangles = d->n_triangles;
+    in.sphere_material = sphere_material.data();
+    in.mat_kind = s->mat_kind.data();
+    in.opt = s->opt;
+    s->rec = layout_records_host(in);
+}
+
 // Host half of yk_scene_create: validation, BoundingVolumeHierarchy::new (bvh.rs:39-115) and — when `ctx` is given (its
-// "top_nodes" / "wide_bvh" options apply) — the device records laid out from the tree.
-yk_status yk_build_scene_image(yk_context* ctx, const yk_scene_desc* d, std::shared_ptr<SceneImage>& out, bool device_builder_allowed) try {
+// "top_nodes" / "wide_bvh" options are captured here) — the small tables and, unless the device lays out, the records.
+yk_status yk_build_scene_image(yk_context* ctx, const yk_scene_desc* d, std::shared_ptr<SceneImage>& out, const SceneBuild& what) try {
     if (!d) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null scene description");
     out.reset();
     yk_status st = check_description(ctx, d);
@@ -330,225 +368,23 @@ yk_status yk_build_scene_image(yk_context* ctx, const yk_scene_desc* d, std::sha
     SceneImage* s = img.get();
     s->bvh = s->bvh_mut = std::make_shared<HostBvh>();
     s->d = d;
-    s->device_layout = ctx && ctx->scene_layout == 1 && device_builder_allowed;
-    s->layout_reason = ctx && ctx->scene_layout == 1 && !device_builder_allowed ? (uint32_t)YK_LAYOUT_REASON_MULTI : 0u;
-    s->n_triangles = d->n_triangles;
-    s->n_spheres = d->n_spheres;
-    s->n_lights = d->n_lights;
-    for (uint32_t l = 0; l < d->n_lights; ++l) s->n_delta_lights += d->lights[l].kind != YK_LIGHT_RECT ? 1u : 0u;
+    s->device_layout = ctx && what.device_layout;
+    s->layout_reason = ctx ? what.layout_reason : 0u;
+    if (ctx) s->opt = LayoutOptions{ctx->top_nodes, ctx->wide_bvh};
     std::memset(&s->info, 0, sizeof(s->info));
 
     std::vector<ShapeBounds> sb;
-    if ((st = shape_bounds(ctx, d, sb)) != YK_OK || (st = build_tree(ctx, d, sb, device_builder_allowed, s)) != YK_OK) return st;
+    if ((st = shape_bounds(ctx, d, sb)) != YK_OK || (st = build_tree(ctx, d, sb, what.device_builder, s)) != YK_OK) return st;
     fill_scene_info(s);
     if (ctx) {  // device records (a host-only scene — ctx == NULL — stops at the tree)
         if (s->info.n_nodes > YK_REF_INDEX_MAX || s->info.n_shapes > YK_REF_INDEX_MAX) return fail(ctx, YK_ERR_UNSUPPORTED, "more than 2^28 BVH nodes or shapes");
         if ((st = host_tables(ctx, d, s)) != YK_OK) return st;
-        if (!s->device_layout) layout_records_host(ctx, s);
+        if (!s->device_layout) layout_image_host(s);
         s->has_device_records = true;
     }
     out = img;
     return YK_OK;
 } YK_CATCH(ctx)
-
-// The device records from the host tree (s->bvh with its arrays): the sequential loops the device layout
-// (yk_scene_layout.hip) is held against, in three sections.
-// DevNode per interior node, the root ref and the two tree tops
-static void layout_nodes_host(const yk_context* ctx, SceneImage* s) {
-    const std::vector<yk_bvh_node>& nodes = s->bvh->nodes;
-    const uint64_t n_interior = s->info.n_interior;
-    // interior index of each reference node = number of interior nodes before it
-    std::vector<uint32_t> interior_index(nodes.size());
-    uint32_t cnt = 0;
-    for (size_t i = 0; i < nodes.size(); ++i) {
-        interior_index[i] = cnt;
-        if (!nodes[i].is_leaf) ++cnt;
-    }
-    auto ref_of = [&](uint32_t idx) -> uint32_t { return nodes[idx].is_leaf ? (YK_LEAF_BIT | nodes[idx].a) : interior_index[idx]; };
-    std::vector<DevNode>& dn = s->dn;
-    dn.assign(std::max<size_t>(n_interior, 1), DevNode());
-    for (size_t i = 0; i < nodes.size(); ++i) {
-        if (nodes[i].is_leaf) continue;
-        const yk_bvh_node& c0 = nodes[i + 1];
-        const yk_bvh_node& c1 = nodes[nodes[i].a];
-        DevNode& o = dn[interior_index[i]];
-        o.q0 = make_float4(c0.bmin[0], c0.bmin[1], c0.bmin[2], c0.bmax[0]);
-        o.q1 = make_float4(c0.bmax[1], c0.bmax[2], c1.bmin[0], c1.bmin[1]);
-        o.q2 = make_float4(c1.bmin[2], c1.bmax[0], c1.bmax[1], c1.bmax[2]);
-        o.q3 = make_uint4(ref_of((uint32_t)i + 1), ref_of(nodes[i].a) | ((uint32_t)nodes[i].axis << YK_AXIS_SHIFT), 0u, 0u);
-    }
-    // top of the tree, breadth first, for the LDS-resident copies (YK_TOP_BIT refs).  Two sets: the closest-hit kernels
-    // keep 8-byte stack entries (ref, entry distance) in LDS and have room for trace_top_nodes() nodes beside them; the
-    // any-hit kernel's entries are a bare ref (4 bytes), which leaves room for trace_top_nodes_any() — more than twice as many.
-    auto build_top = [&](size_t cap, std::vector<DevNode>& top) {
-        top.clear();
-        if (nodes[0].is_leaf || cap == 0) return;
-        std::vector<uint32_t> order;  // reference node indices, breadth first
-        std::vector<uint32_t> top_id(nodes.size(), 0xffffffffu);
-        order.push_back(0);
-        top_id[0] = 0;
-        for (size_t q = 0; q < order.size() && order.size() < cap; ++q) {
-            const uint32_t P = order[q];
-            for (uint32_t c : {P + 1, nodes[P].a}) {
-                if (!nodes[c].is_leaf && order.size() < cap) {
-                    top_id[c] = (uint32_t)order.size();
-                    order.push_back(c);
-                }
-            }
-        }
-        for (uint32_t P : order) {
-            DevNode t = dn[interior_index[P]];
-            const uint32_t c0 = P + 1, c1 = nodes[P].a;
-            if (top_id[c0] != 0xffffffffu) t.q3.x = YK_TOP_BIT | top_id[c0];
-            if (top_id[c1] != 0xffffffffu) t.q3.y = YK_TOP_BIT | top_id[c1] | ((uint32_t)nodes[P].axis << YK_AXIS_SHIFT);
-            top.push_back(t);
-        }
-    };
-    build_top((size_t)std::min<int64_t>(ctx->top_nodes, trace_top_nodes()), s->top);
-    build_top((size_t)std::min<int64_t>(ctx->top_nodes, trace_top_nodes_any()), s->top_any);
-    s->root_ref = ref_of(0);
-}
-
-static void layout_wide_host(const yk_context* ctx, SceneImage* s) {
-    const HostBvh* bvh = s->bvh.get();
-    const std::vector<yk_bvh_node>& nodes = bvh->nodes;
-    const uint64_t n_interior = s->info.n_interior;
-    // 4-wide collapse (DevNode4): one node per reference interior node reached at even depth
-    // below the root.  Built only while the traversal stack of the collapsed tree is
-    // guaranteed to fit (the reference asserts on its own stack depth, bvh.rs:172-174).
-    std::vector<DevNode4>& dn4 = s->dn4;
-    const bool wide = ctx->wide_bvh != 0 && !nodes[0].is_leaf && bvh->depth <= 64;
-    s->wide_auto = wide && ctx->wide_bvh == 2;
-    if (wide) {
-        dn4.reserve(n_interior / 2 + 1);
-        struct Todo {
-            uint32_t binary;  // reference node index of P
-            uint32_t slot;    // DevNode4 index to fill
-        };
-        std::vector<Todo> stack;
-        dn4.emplace_back();
-        stack.push_back(Todo{0u, 0u});
-        while (!stack.empty()) {
-            const Todo td = stack.back();
-            stack.pop_back();
-            const uint32_t P = td.binary, A = P + 1, B = nodes[P].a;
-            uint32_t child[4] = {YK_REF_NONE, YK_REF_NONE, YK_REF_NONE, YK_REF_NONE};  // reference node index per slot
-            if (nodes[A].is_leaf) {
-                child[0] = A;
-            } else {
-                child[0] = A + 1;
-                child[1] = nodes[A].a;
-            }
-            if (nodes[B].is_leaf) {
-                child[2] = B;
-            } else {
-                child[2] = B + 1;
-                child[3] = nodes[B].a;
-            }
-            float box[4][6] = {};
-            uint32_t ref[4];
-            for (int k = 0; k < 4; ++k) {
-                ref[k] = YK_REF_NONE;
-                if (child[k] == YK_REF_NONE) continue;
-                const yk_bvh_node& c = nodes[child[k]];
-                for (int a = 0; a < 3; ++a) {
-                    box[k][a] = c.bmin[a];
-                    box[k][3 + a] = c.bmax[a];
-                }
-                if (c.is_leaf) {
-                    ref[k] = YK_LEAF_BIT | c.a;
-                } else {
-                    ref[k] = (uint32_t)dn4.size();
-                    dn4.emplace_back();
-                }
-            }
-            // children are expanded so that the first visited subtree (for a positive ray) follows in memory
-            for (int k = 3; k >= 0; --k)
-                if (ref[k] != YK_REF_NONE && !(ref[k] & YK_LEAF_BIT)) stack.push_back(Todo{child[k], ref[k]});
-            DevNode4& o = dn4[td.slot];
-            o.q0 = make_float4(box[0][0], box[0][1], box[0][2], box[0][3]);
-            o.q1 = make_float4(box[0][4], box[0][5], box[1][0], box[1][1]);
-            o.q2 = make_float4(box[1][2], box[1][3], box[1][4], box[1][5]);
-            o.q3 = make_float4(box[2][0], box[2][1], box[2][2], box[2][3]);
-            o.q4 = make_float4(box[2][4], box[2][5], box[3][0], box[3][1]);
-            o.q5 = make_float4(box[3][2], box[3][3], box[3][4], box[3][5]);
-            o.q6 = make_uint4(ref[0], ref[1], ref[2], ref[3]);
-            const uint32_t axA = nodes[A].is_leaf ? 0u : nodes[A].axis, axB = nodes[B].is_leaf ? 0u : nodes[B].axis;
-            o.q7 = make_uint4((uint32_t)nodes[P].axis | (axA << 2) | (axB << 4), 0u, 0u, 0u);
-        }
-    }
-}
-
-// tris / prim_shade / prim_attr in leaf order
-static void layout_prims_host(SceneImage* s) {
-    const yk_scene_desc* d = s->d;
-    const HostBvh* bvh = s->bvh.get();
-    const std::vector<uint32_t>& mat_kind = s->mat_kind;
-    const size_t np = bvh->shape_order.size();
-    std::vector<float4>& tris = s->tris;
-    tris.assign(3 * np, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-    std::vector<uint4>& prim_shade = s->prim_shade;
-    prim_shade.assign(np, make_uint4(0u, 0u, 0u, 0u));
-    std::vector<uint8_t> last(np, 0);
-    for (const yk_bvh_node& n : bvh->nodes)
-        if (n.is_leaf) last[(size_t)n.a + n.count - 1] = 1;
-    for (size_t p = 0; p < np; ++p) {
-        uint32_t src = bvh->shape_order[p];
-        if (src >= d->n_triangles) {  // sphere: only the source index and the flags are read
-            uint32_t none = 0xffffffffu, fl = (last[p] ? YK_PRIM_LAST : 0u) | YK_PRIM_SPHERE | (mat_kind[d->spheres[src - d->n_triangles].material] << YK_PRIM_KIND_SHIFT);
-            float w0, w1, w2;
-            std::memcpy(&w0, &none, 4);
-            std::memcpy(&w1, &src, 4);
-            std::memcpy(&w2, &fl, 4);
-            tris[3 * p + 0] = make_float4(0.0f, 0.0f, 0.0f, w0);
-            tris[3 * p + 1] = make_float4(0.0f, 0.0f, 0.0f, w1);
-            tris[3 * p + 2] = make_float4(0.0f, 0.0f, 0.0f, w2);
-            prim_shade[p] = make_uint4(0u, 0u, 0u, ((uint32_t)d->spheres[src - d->n_triangles].material << 6) | (mat_kind[d->spheres[src - d->n_triangles].material] << 3));
-            continue;
-        }
-        const float* p0 = d->points + 3 * (size_t)d->indices[3 * src];
-        const float* p1 = d->points + 3 * (size_t)d->indices[3 * src + 1];
-        const float* p2 = d->points + 3 * (size_t)d->indices[3 * src + 2];
-        int al = d->tri_area_light ? d->tri_area_light[src] : -1;
-        uint32_t alb = (uint32_t)al, lastb = (last[p] ? YK_PRIM_LAST : 0u) | (mat_kind[d->tri_material[src]] << YK_PRIM_KIND_SHIFT);
-        float w0, w1, w2;
-        std::memcpy(&w0, &alb, 4);
-        std::memcpy(&w1, &src, 4);
-        std::memcpy(&w2, &lastb, 4);
-        tris[3 * p + 0] = make_float4(p0[0], p0[1], p0[2], w0);
-        tris[3 * p + 1] = make_float4(p1[0], p1[1], p1[2], w1);
-        tris[3 * p + 2] = make_float4(p2[0], p2[1], p2[2], w2);
-        const uint32_t mfl = s->mesh_flags[s->tri_mesh[src]];
-        prim_shade[p] = make_uint4(d->indices[3 * src], d->indices[3 * src + 1], d->indices[3 * src + 2],
-                                   ((uint32_t)d->tri_material[src] << 6) | (mat_kind[d->tri_material[src]] << 3) | mfl);
-    }
-    if (d->normals || d->uvs) {  // leaf-order copy of the per-vertex normals / uvs (yk_device.h: DevScene::prim_attr)
-        s->prim_attr.assign(4 * np, make_float4(0.0f, 0.0f, 0.0f, 0.0f));
-        for (size_t p = 0; p < np; ++p) {
-            const uint32_t src = bvh->shape_order[p];
-            if (src >= d->n_triangles) continue;
-            const uint32_t mfl = s->mesh_flags[s->tri_mesh[src]];
-            float nrm[3][3] = {}, uv[3][2] = {};
-            for (int k = 0; k < 3; ++k) {
-                const size_t vi = d->indices[3 * (size_t)src + k];
-                if (mfl & YK_MESH_NORMALS)
-                    for (int c = 0; c < 3; ++c) nrm[k][c] = d->normals[3 * vi + c];
-                if (mfl & YK_MESH_UVS)
-                    for (int c = 0; c < 2; ++c) uv[k][c] = d->uvs[2 * vi + c];
-            }
-            s->prim_attr[4 * p + 0] = make_float4(nrm[0][0], nrm[0][1], nrm[0][2], uv[0][0]);
-            s->prim_attr[4 * p + 1] = make_float4(nrm[1][0], nrm[1][1], nrm[1][2], uv[0][1]);
-            s->prim_attr[4 * p + 2] = make_float4(nrm[2][0], nrm[2][1], nrm[2][2], uv[1][0]);
-            s->prim_attr[4 * p + 3] = make_float4(uv[1][1], uv[2][0], uv[2][1], 0.0f);
-        }
-    }
-}
-
-static void layout_records_host(const yk_context* ctx, SceneImage* s) {
-    layout_nodes_host(ctx, s);
-    layout_wide_host(ctx, s);
-    layout_prims_host(s);
-}
 
 // 32-byte nodes and shape order from HBM into the host tree (no-op for buffers that are not there)
 static yk_status fetch_tree(int device, const DevBuf& d_nodes, const DevBuf& d_order, uint32_t n_nodes, uint32_t n_shapes, HostBvh& out) {
@@ -575,60 +411,68 @@ const HostBvh* scene_host_tree(const yk_scene* s) {
     return s->tree_fetched.load() ? s->bvh.get() : nullptr;
 }
 
-// "scene_layout" = 1: the tree to HBM unless the builder left it there, the two small tables, the layout kernels
+hipError_t upload_host_tree(const HostBvh& bvh, DeviceTree& tree) {
+    const std::vector<uint32_t> depth = lay::node_depths(reinterpret_cast<const uint32_t*>(bvh.nodes.data()), bvh.nodes.size());  // children follow their parent in the array
+    tree.n_nodes = (uint32_t)bvh.nodes.size();
+    tree.n_shapes = (uint32_t)bvh.shape_order.size();
+    std::memcpy(tree.root_words, bvh.nodes.data(), 32);
+    hipError_t e = put_host_array(tree.nodes, bvh.nodes.data(), bvh.nodes.size() * sizeof(yk_bvh_node));
+    if (e == hipSuccess) e = put_host_array(tree.depth, depth.data(), depth.size() * 4);
+    if (e == hipSuccess) e = put_host_array(tree.order, bvh.shape_order.data(), bvh.shape_order.size() * 4);
+    return e;
+}
+
+void adopt_device_tree(yk_scene* s, DeviceTree& tree, const std::shared_ptr<HostBvh>& lazy) {
+    std::swap(s->tree_nodes, tree.nodes);
+    std::swap(s->tree_order, tree.order);
+    std::swap(s->upd.depth, tree.depth);  // kept for the scene's updates
+    if (lazy) {  // the host copy of the arrays is made when something asks for it (scene_host_tree)
+        s->bvh_lazy = lazy;
+        s->tree_fetched.store(0u);
+    }
+}
+
+// The device layout of an image: the tree to HBM unless the builder left it there, the two small tables, the layout kernels
 // (yk_scene_layout.hip).  The scene's own arrays (indices .. spheres) are uploaded already.  Returns YK_LAYOUT_REASON_*.
 static uint32_t layout_on_device(yk_context* ctx, SceneImage* img, yk_scene* s) {
     const yk_scene_desc* d = img->d;
     DeviceTree& tree = img->dtree;
     double t0 = now_seconds();
-    DevBuf d_mat_kind, d_user;
-    struct Free {
-        DevBuf &a, &b;
-        ~Free() {
-            a.release();
-            b.release();
-        }
-    } free_tables{d_mat_kind, d_user};
-    auto put = [&](DevBuf& buf, const void* src, size_t bytes) -> uint32_t {
-        hipError_t e = buf.ensure(std::max<size_t>(bytes, 16));
-        if (e == hipSuccess && bytes) e = hipMemcpy(buf.p, src, bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess) return YK_LAYOUT_REASON_NONE;
-        (void)hipGetLastError();
-        return e == hipErrorOutOfMemory ? YK_LAYOUT_REASON_OUT_OF_MEMORY : YK_LAYOUT_REASON_DEVICE_ERROR;
-    };
-    uint32_t r;
-    std::vector<uint8_t> kinds(img->mat_kind.begin(), img->mat_kind.end());
-    if ((r = put(d_mat_kind, kinds.data(), kinds.size())) != 0) return r;
-    if (img->tree_on_device) {
-        if (d->shape_order && (r = put(d_user, d->shape_order, (size_t)tree.n_shapes * 4)) != 0) return r;
-    } else {  // a host-built tree: its nodes, their depths (children follow their parent in the array) and the final order
-        const HostBvh& bvh = *img->bvh;
-        const std::vector<uint32_t> depth = lay::node_depths(reinterpret_cast<const uint32_t*>(bvh.nodes.data()), bvh.nodes.size());
-        tree.n_nodes = (uint32_t)bvh.nodes.size();
-        tree.n_shapes = (uint32_t)bvh.shape_order.size();
-        std::memcpy(tree.root_words, bvh.nodes.data(), 32);
-        if ((r = put(tree.nodes, bvh.nodes.data(), bvh.nodes.size() * sizeof(yk_bvh_node))) != 0 || (r = put(tree.depth, depth.data(), depth.size() * 4)) != 0 ||
-            (r = put(tree.order, bvh.shape_order.data(), bvh.shape_order.size() * 4)) != 0)
-            return r;
-    }
+    const bool user_order = img->tree_on_device && d->shape_order;  // a host-built tree's order has it applied already
+    DevScratch tmp;
+    uint8_t* d_mat_kind = nullptr;
+    uint32_t* d_user = nullptr;
+    if (!tmp.get(d_mat_kind, img->mat_kind.size()) || (user_order && !tmp.get(d_user, tree.n_shapes))) return layout_reason_of(tmp.err);
+    hipError_t e = hipMemcpy(d_mat_kind, img->mat_kind.data(), img->mat_kind.size(), hipMemcpyHostToDevice);
+    if (e == hipSuccess && user_order) e = hipMemcpy(d_user, d->shape_order, (size_t)tree.n_shapes * 4, hipMemcpyHostToDevice);
+    if (e == hipSuccess && !img->tree_on_device) e = upload_host_tree(*img->bvh, tree);
+    if (e != hipSuccess) return layout_reason_of(e);
     s->layout.seconds_upload = now_seconds() - t0;
     t0 = now_seconds();
-    r = layout_scene_device(ctx, s, tree, img->tree_on_device && d->shape_order ? d_user.as<uint32_t>() : nullptr, d_mat_kind.as<uint8_t>(), d->normals || d->uvs, img->bvh->depth, &img->order_applied);
+    const uint32_t r = layout_scene_device(ctx, s, tree, d_user, d_mat_kind, d->normals || d->uvs, img->bvh->depth, &img->order_applied);
     s->layout.seconds_layout = now_seconds() - t0;
     if (r != YK_LAYOUT_REASON_NONE) return r;
-    if (img->tree_on_device) {  // the host copy of the arrays is made when something asks for it (scene_host_tree)
-        std::swap(s->tree_nodes, tree.nodes);
-        std::swap(s->tree_order, tree.order);
-        std::swap(s->upd.depth, tree.depth);  // kept for the scene's updates
-        s->bvh_lazy = img->bvh_mut;
-        s->tree_fetched.store(0u);
-    }
+    if (img->tree_on_device) adopt_device_tree(s, tree, img->bvh_mut);
     tree.release();
     return YK_LAYOUT_REASON_NONE;
 }
 
-// The DevScene the kernels are handed, from the scene's buffers, its layout info and the description's scalars.
-static void bind_device_scene(yk_scene* s, const yk_scene_desc* d) {
+// The seven record vectors of a host layout into the scene's record buffers, and the sizes and layout head that go with them.
+static yk_status upload_records(yk_context* ctx, yk_scene* s, const SceneRecords& r) {
+    yk_status st;
+    if ((st = upload(ctx, s->nodes, r.nodes.data(), r.nodes.size())) != YK_OK || (st = upload(ctx, s->nodes4, r.nodes4.data(), r.nodes4.size())) != YK_OK ||
+        (st = upload(ctx, s->top_nodes, r.top.data(), r.top.size())) != YK_OK || (st = upload(ctx, s->top_nodes_any, r.top_any.data(), r.top_any.size())) != YK_OK ||
+        (st = upload(ctx, s->tris, r.tris.data(), r.tris.size())) != YK_OK || (st = upload(ctx, s->prim_shade, r.prim_shade.data(), r.prim_shade.size())) != YK_OK ||
+        (st = upload(ctx, s->prim_attr, r.prim_attr.data(), r.prim_attr.size())) != YK_OK)
+        return st;
+    // prim_attr is 4 * n_shapes records where the scene has normals or uvs and empty otherwise; a scene has at least one shape
+    set_record_layout(s, s->info.n_interior, r.nodes4.size(), r.top.size(), r.top_any.size(), s->info.n_shapes, !r.prim_attr.empty(), r.root_ref, r.wide_auto);
+    return YK_OK;
+}
+
+// What the kernels are handed of the records and the root box, from the scene's record buffers, its layout info and its
+// bounds: at creation and again after either route of an update rewrote them.  The root box reaches DevScene here only.
+static void bind_records(yk_scene* s) {
     const yk_scene_layout_info& li = s->layout;
     DevScene& ds = s->dev;
     ds.nodes = s->nodes.as<DevNode>();
@@ -641,14 +485,20 @@ static void bind_device_scene(yk_scene* s, const yk_scene_desc* d) {
     ds.tris = s->tris.as<float4>();
     ds.prim_shade = s->prim_shade.as<uint4>();
     ds.prim_attr = s->record_bytes[YK_RECORDS_PRIM_ATTR] ? s->prim_attr.as<float4>() : nullptr;
-    ds.spheres = d->n_spheres ? s->spheres.as<DevSphere>() : nullptr;
-    ds.n_triangles = d->n_triangles;
     ds.root_ref = li.root_ref;
     for (int k = 0; k < 3; ++k) {  // node 0's box
         ds.root_bmin[k] = s->info.bounds_min[k];
         ds.root_bmax[k] = s->info.bounds_max[k];
-        ds.background[k] = d->background[k];
     }
+}
+
+// The DevScene the kernels are handed: the records, then the scene's own arrays and the description's scalars.
+static void bind_device_scene(yk_scene* s, const yk_scene_desc* d) {
+    bind_records(s);
+    DevScene& ds = s->dev;
+    ds.spheres = d->n_spheres ? s->spheres.as<DevSphere>() : nullptr;
+    ds.n_triangles = d->n_triangles;
+    for (int k = 0; k < 3; ++k) ds.background[k] = d->background[k];
     ds.indices = s->indices.as<uint32_t>();
     ds.points = s->points.as<float>();
     ds.normals = s->normals.as<float>();
@@ -667,23 +517,19 @@ static void bind_device_scene(yk_scene* s, const yk_scene_desc* d) {
 }
 
 // What an update needs of the description after creation (yk_scene::UpdateState).
-static void init_update_state(const yk_context* ctx, yk_scene* s, const yk_scene_desc* d, const std::vector<uint32_t>& mat_kind) {
+static void init_update_state(yk_scene* s, const yk_scene_desc* d, const LayoutOptions& opt, const std::vector<uint8_t>& mat_kind, bool host_only) {
     yk_scene::UpdateState& u = s->upd;
     u.n_vertices = d->n_vertices;
     u.has_normals = d->normals != nullptr;
     u.has_uvs = d->uvs != nullptr;
-    u.top_nodes = ctx ? ctx->top_nodes : 0;
-    u.wide_bvh = ctx ? ctx->wide_bvh : 0;
-    u.mat_kind.assign(mat_kind.begin(), mat_kind.end());
-    u.sphere_bounds.resize(6 * (size_t)d->n_spheres);
+    u.opt = opt;
+    u.mat_kind = mat_kind;
+    u.sphere_bounds.resize(6 * (size_t)d->n_spheres);  // bmin, bmax per sphere: a ShapeBounds is those six floats
     for (uint32_t k = 0; k < d->n_spheres; ++k) {
         const ShapeBounds b = sphere_bound(d->spheres[k]);
-        for (int a = 0; a < 3; ++a) {
-            u.sphere_bounds[6 * (size_t)k + a] = b.bmin[a];
-            u.sphere_bounds[6 * (size_t)k + 3 + a] = b.bmax[a];
-        }
+        std::memcpy(&u.sphere_bounds[6 * (size_t)k], &b, sizeof(b));
     }
-    if (!ctx && d->n_triangles) u.host_indices.assign(d->indices, d->indices + 3 * (size_t)d->n_triangles);
+    if (host_only && d->n_triangles) u.host_indices.assign(d->indices, d->indices + 3 * (size_t)d->n_triangles);
 }
 
 // Device half: one copy of the image in the HBM of ctx's device.
@@ -691,23 +537,15 @@ yk_status yk_upload_scene_image(yk_context* ctx, const std::shared_ptr<SceneImag
     if (!out) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null out");
     *out = nullptr;
     if (!img || !img->bvh) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null scene image");
-    yk_scene* s = new yk_scene();
-    struct SceneGuard {  // frees the half-built scene on every early return and on an exception
-        yk_scene* s;
-        ~SceneGuard() {
-            if (s) yk_scene_destroy(s);
-        }
-    } guard{s};
+    ScenePtr guard(new yk_scene(), yk_scene_destroy);
+    yk_scene* s = guard.get();
     s->device = ctx ? ctx->device : -1;
     s->bvh = img->bvh;
-    s->n_triangles = img->n_triangles;
-    s->n_spheres = img->n_spheres;
-    s->n_lights = img->n_lights;
-    s->n_delta_lights = img->n_delta_lights;
+    set_scene_counts(s, img->d);
     s->info = img->info;
     s->build_info = img->build_info;
     s->shape_kind = img->shape_kind;
-    init_update_state(ctx, s, img->d, img->mat_kind);
+    init_update_state(s, img->d, img->opt, img->mat_kind, ctx == nullptr);
     if (ctx) {
         if (!img->has_device_records) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "scene image was built without device records");
         const yk_scene_desc* d = img->d;
@@ -742,25 +580,15 @@ yk_status yk_upload_scene_image(yk_context* ctx, const std::shared_ptr<SceneImag
                     for (uint32_t& o : img->bvh_mut->shape_order) o = d->shape_order[o];
                 img->tree_on_device = false;
                 img->dtree.release();
-                layout_records_host(ctx, img.get());
+                layout_image_host(img.get());
             }
         }
-        if (li.layout == YK_LAYOUT_HOST) {
-            UP(nodes, img->dn.data(), img->dn.size());
-            UP(nodes4, img->dn4.data(), img->dn4.size());
-            UP(top_nodes, img->top.data(), img->top.size());
-            UP(top_nodes_any, img->top_any.data(), img->top_any.size());
-            UP(tris, img->tris.data(), img->tris.size());
-            UP(prim_shade, img->prim_shade.data(), img->prim_shade.size());
-            UP(prim_attr, img->prim_attr.data(), img->prim_attr.size());
-            set_record_layout(s, s->info.n_interior, img->dn4.size(), img->top.size(), img->top_any.size(), s->info.n_shapes, d->normals || d->uvs, img->root_ref, img->wide_auto);
-        }
 #undef UP
+        if (li.layout == YK_LAYOUT_HOST && (st = upload_records(ctx, s, img->rec)) != YK_OK) return st;
         bind_device_scene(s, d);
         s->info.upload_seconds = now_seconds() - u0;
     }
-    guard.s = nullptr;
-    *out = s;
+    *out = guard.release();
     return YK_OK;
 } YK_CATCH(ctx)
 
@@ -789,16 +617,13 @@ const std::vector<uint8_t>* scene_shape_kind(const yk_scene* s) {
 // it finds in HBM and the layout reads the scene's own device-to-device copies.
 
 // every non-NULL large array is device memory of ctx's device, and its allocation reaches as far as its count says
-static yk_status check_device_arrays(yk_context* ctx, const yk_scene_desc* d) {
-    const size_t nv = d->n_vertices, nt = d->n_triangles, ns = nt + d->n_spheres;
-    const struct {
-        const char* name;
-        const void* p;
-        size_t bytes;
-    } arrays[] = {{"points", d->points, 12 * nv},          {"normals", d->normals, 12 * nv},          {"uvs", d->uvs, 8 * nv},
-                  {"indices", d->indices, 12 * nt},        {"tri_mesh", d->tri_mesh, 4 * nt},         {"tri_material", d->tri_material, 4 * nt},
-                  {"tri_area_light", d->tri_area_light, 4 * nt}, {"shape_order", d->shape_order, 4 * ns}};
-    for (const auto& a : arrays) {
+struct DeviceArray {
+    const char* name;
+    const void* p;
+    size_t bytes;
+};
+static yk_status check_device_arrays(yk_context* ctx, std::initializer_list<DeviceArray> arrays) {
+    for (const DeviceArray& a : arrays) {
         if (!a.p) continue;
         hipPointerAttribute_t at;
         std::memset(&at, 0, sizeof(at));
@@ -822,18 +647,10 @@ static yk_status create_scene_on_device(yk_context* ctx, const yk_scene_desc* d,
     *fall_back = false;
     std::memset(refused, 0, sizeof(*refused));
     const uint32_t nt = d->n_triangles, N = nt + d->n_spheres;
-    yk_scene* s = new yk_scene();
-    struct SceneGuard {
-        yk_scene* s;
-        ~SceneGuard() {
-            if (s) yk_scene_destroy(s);
-        }
-    } guard{s};
+    ScenePtr guard(new yk_scene(), yk_scene_destroy);
+    yk_scene* s = guard.get();
     s->device = ctx->device;
-    s->n_triangles = nt;
-    s->n_spheres = d->n_spheres;
-    s->n_lights = d->n_lights;
-    for (uint32_t l = 0; l < d->n_lights; ++l) s->n_delta_lights += d->lights[l].kind != YK_LIGHT_RECT ? 1u : 0u;
+    set_scene_counts(s, d);
     std::memset(&s->info, 0, sizeof(s->info));
     std::memset(&s->build_info, 0, sizeof(s->build_info));
     const double u0 = now_seconds();
@@ -856,8 +673,9 @@ static yk_status create_scene_on_device(yk_context* ctx, const yk_scene_desc* d,
     std::memset(&img.info, 0, sizeof(img.info));
     yk_status rc = small_tables(ctx, d, &img);
     if (rc != YK_OK) return rc;
-    std::vector<uint8_t> light_kind(std::max<uint32_t>(d->n_lights, 1), 0), mat_kind(img.mat_kind.begin(), img.mat_kind.end());
-    init_update_state(ctx, s, d, img.mat_kind);
+    std::vector<uint8_t> light_kind(std::max<uint32_t>(d->n_lights, 1), 0);
+    std::vector<uint8_t>& mat_kind = img.mat_kind;
+    init_update_state(s, d, LayoutOptions{ctx->top_nodes, ctx->wide_bvh}, mat_kind, false);
     for (uint32_t l = 0; l < d->n_lights; ++l) light_kind[l] = (uint8_t)d->lights[l].kind;
     std::vector<ShapeBounds> sphere_b(std::max<uint32_t>(d->n_spheres, 1));
     for (uint32_t k = 0; k < d->n_spheres; ++k) sphere_b[k] = sphere_bound(d->spheres[k]);
@@ -934,21 +752,16 @@ static yk_status create_scene_on_device(yk_context* ctx, const yk_scene_desc* d,
     }
     s->layout.layout = YK_LAYOUT_DEVICE;
     s->layout.seconds_layout = now_seconds() - l0;
-    std::swap(s->tree_nodes, img.dtree.nodes);  // the host copy of the tree is made when something asks for it (scene_host_tree)
-    std::swap(s->tree_order, img.dtree.order);
-    std::swap(s->upd.depth, img.dtree.depth);  // kept for the scene's updates
     s->bvh = img.bvh;
-    s->bvh_lazy = img.bvh_mut;
-    s->tree_fetched.store(0u);
-    s->lazy_mat_kind.swap(mat_kind);  // ... and so is the shape -> kind table (scene_shape_kind)
+    adopt_device_tree(s, img.dtree, img.bvh_mut);
+    s->lazy_mat_kind.swap(mat_kind);  // the shape -> kind table is made when something asks for it, too (scene_shape_kind)
     s->lazy_sphere_kind.resize(d->n_spheres);
     for (uint32_t k = 0; k < d->n_spheres; ++k) s->lazy_sphere_kind[k] = s->lazy_mat_kind[(uint32_t)d->spheres[k].material];
     s->shape_kind_lazy = true;
     s->kind_fetched.store(0u);
     bind_device_scene(s, d);
     s->info.upload_seconds = now_seconds() - u0;
-    guard.s = nullptr;
-    *out = s;
+    *out = guard.release();
     return YK_OK;
 }
 
@@ -961,37 +774,23 @@ static yk_status create_scene_from_host_copy(yk_context* ctx, const yk_scene_des
     std::vector<float> points(3 * nv), normals(d->normals ? 3 * nv : 0), uvs(d->uvs ? 2 * nv : 0);
     std::vector<uint32_t> indices(3 * nt), tri_mesh(d->tri_mesh ? nt : 0), order(d->shape_order ? ns : 0);
     std::vector<int32_t> tri_material(nt), tri_al(d->tri_area_light ? nt : 0);
-    yk_scene_desc h = *d;
-    auto fetch = [&](auto& v, const void* src) -> hipError_t { return v.empty() ? hipSuccess : hipMemcpyAsync(v.data(), src, v.size() * sizeof(v[0]), hipMemcpyDeviceToHost, st); };
-    HIP_TRY(ctx, fetch(points, d->points));
-    HIP_TRY(ctx, fetch(normals, d->normals));
-    HIP_TRY(ctx, fetch(uvs, d->uvs));
-    HIP_TRY(ctx, fetch(indices, d->indices));
-    HIP_TRY(ctx, fetch(tri_mesh, d->tri_mesh));
-    HIP_TRY(ctx, fetch(tri_material, d->tri_material));
-    HIP_TRY(ctx, fetch(tri_al, d->tri_area_light));
-    HIP_TRY(ctx, fetch(order, d->shape_order));
+    yk_scene_desc h = *d;  // the caller's description, its large arrays repointed at the host copies
+    auto fetch = [&](auto& v, auto& field) -> hipError_t {
+        const void* src = field;
+        field = v.empty() ? nullptr : v.data();
+        return v.empty() ? hipSuccess : hipMemcpyAsync(v.data(), src, v.size() * sizeof(v[0]), hipMemcpyDeviceToHost, st);
+    };
+    HIP_TRY(ctx, fetch(points, h.points));
+    HIP_TRY(ctx, fetch(normals, h.normals));
+    HIP_TRY(ctx, fetch(uvs, h.uvs));
+    HIP_TRY(ctx, fetch(indices, h.indices));
+    HIP_TRY(ctx, fetch(tri_mesh, h.tri_mesh));
+    HIP_TRY(ctx, fetch(tri_material, h.tri_material));
+    HIP_TRY(ctx, fetch(tri_al, h.tri_area_light));
+    HIP_TRY(ctx, fetch(order, h.shape_order));
     HIP_TRY(ctx, hipStreamSynchronize(st));
-    h.points = points.data();
-    h.normals = d->normals ? normals.data() : nullptr;
-    h.uvs = d->uvs ? uvs.data() : nullptr;
-    h.indices = indices.data();
-    h.tri_mesh = d->tri_mesh ? tri_mesh.data() : nullptr;
-    h.tri_material = tri_material.data();
-    h.tri_area_light = d->tri_area_light ? tri_al.data() : nullptr;
-    h.shape_order = d->shape_order ? order.data() : nullptr;
-    struct Options {  // this entry point always asks for the device builder and layout
-        yk_context* ctx;
-        int64_t builder, layout;
-        ~Options() {
-            ctx->bvh_builder = builder;
-            ctx->scene_layout = layout;
-        }
-    } restore{ctx, ctx->bvh_builder, ctx->scene_layout};
-    ctx->bvh_builder = refused.reason ? 0 : 1;
-    ctx->scene_layout = 1;
-    std::shared_ptr<SceneImage> img;
-    yk_status rc = yk_build_scene_image(ctx, &h, img);
+    std::shared_ptr<SceneImage> img;  // this entry point always asks for the device layout, and for the device builder unless it has refused
+    yk_status rc = yk_build_scene_image(ctx, &h, img, SceneBuild{refused.reason == 0, true, 0u});
     if (rc != YK_OK || (rc = yk_upload_scene_image(ctx, img, out)) != YK_OK) return rc;
     if (refused.reason) {  // who built the tree is the host path's answer, why is the refusal's
         const uint32_t builder = (*out)->build_info.builder;
@@ -1000,7 +799,6 @@ static yk_status create_scene_from_host_copy(yk_context* ctx, const yk_scene_des
     }
     return YK_OK;
 }
-
 
 // ------------------------------------------------------------------ yk_scene_update
 // Update in place: the rule is yk_scene_update.h's, the device route yk_scene_update.hip's; here are the
@@ -1015,31 +813,13 @@ static bool all_finite(const float* p, size_t n) {
     return true;
 }
 
-// what the kernels are handed, after either route rewrote the records
-static void rebind_records(yk_scene* s) {
-    const yk_scene_layout_info& li = s->layout;
-    DevScene& ds = s->dev;
-    ds.nodes = s->nodes.as<DevNode>();
-    ds.nodes4 = li.wide ? s->nodes4.as<DevNode4>() : nullptr;
-    s->wide_auto = li.wide_auto != 0;
-    ds.top_nodes = s->top_nodes.as<DevNode>();
-    ds.n_top = li.n_top;
-    ds.top_nodes_any = s->top_nodes_any.as<DevNode>();
-    ds.n_top_any = li.n_top_any;
-    ds.tris = s->tris.as<float4>();
-    ds.prim_shade = s->prim_shade.as<uint4>();
-    ds.prim_attr = s->record_bytes[YK_RECORDS_PRIM_ATTR] ? s->prim_attr.as<float4>() : nullptr;
-    ds.root_ref = li.root_ref;
-    for (int k = 0; k < 3; ++k) {
-        ds.root_bmin[k] = s->info.bounds_min[k];
-        ds.root_bmax[k] = s->info.bounds_max[k];
-    }
-}
-
-// The host route: yk_bvh_refit on a copy of the host tree, layout_records_host, an upload of the arrays and the records.
+// The host route: yk_bvh_refit on a copy of the host tree, layout_records_host, an upload of the arrays, upload_records.
 // `points` (and `normals`, may be NULL) are host arrays that have passed the finite test.  ctx NULL: a host-only scene.
-static yk_status update_scene_host(yk_context* ctx, yk_scene* s, const float* points, const float* normals) {
+// `reason`: why the device route was not taken or did not finish (YK_LAYOUT_REASON_*), for the update info.
+static yk_status update_scene_host(yk_context* ctx, yk_scene* s, const float* points, const float* normals, uint32_t reason) {
     yk_scene::UpdateState& u = s->upd;
+    u.info.route = YK_UPDATE_ROUTE_HOST;
+    u.info.reason = reason;
     const size_t nt = s->n_triangles, ns = s->n_spheres, nv = u.n_vertices;
     const HostBvh* old = scene_host_tree(s);
     if (!old) return fail(ctx, YK_ERR_DEVICE, "the scene's tree could not be copied back from the device");
@@ -1062,10 +842,10 @@ static yk_status update_scene_host(yk_context* ctx, yk_scene* s, const float* po
     u.info.seconds_boxes = now_seconds() - t0;
     t0 = now_seconds();
     if (ctx) {
-        // the description's arrays as the host layout reads them: the new points and normals, everything else from the scene
+        // the host layout's input: the new points and normals, everything else fetched from the scene
         std::vector<float> old_normals(u.has_normals && !normals ? 3 * nv : 0), uvs(u.has_uvs ? 2 * nv : 0);
         std::vector<uint32_t> tri_mesh(nt), mesh_flags(s->mesh_flags.bytes / 4);
-        std::vector<int32_t> tri_material(nt), tri_al(nt);
+        std::vector<int32_t> tri_material(nt), tri_al(nt), sphere_material(ns);
         std::vector<DevSphere> dev_spheres(ns);
         HIP_TRY(ctx, fetch(old_normals, s->normals));
         HIP_TRY(ctx, fetch(uvs, s->uvs));
@@ -1074,53 +854,27 @@ static yk_status update_scene_host(yk_context* ctx, yk_scene* s, const float* po
         HIP_TRY(ctx, fetch(tri_material, s->tri_material));
         HIP_TRY(ctx, fetch(tri_al, s->tri_area_light));
         HIP_TRY(ctx, fetch(dev_spheres, s->spheres));
-        std::vector<yk_sphere_desc> spheres(ns);
-        for (size_t k = 0; k < ns; ++k) {
-            std::memset(&spheres[k], 0, sizeof(spheres[k]));
-            spheres[k].material = dev_spheres[k].material;
-        }
-        yk_scene_desc d;
-        std::memset(&d, 0, sizeof(d));
-        d.n_triangles = (uint32_t)nt;
-        d.n_spheres = (uint32_t)ns;
-        d.n_vertices = (uint32_t)nv;
-        d.points = points;
-        d.normals = normals ? normals : (u.has_normals ? old_normals.data() : nullptr);
-        d.uvs = u.has_uvs ? uvs.data() : nullptr;
-        d.indices = indices;
-        d.tri_material = tri_material.data();
-        d.tri_area_light = tri_al.data();
-        d.spheres = spheres.data();
-        SceneImage img;
-        std::memset(&img.info, 0, sizeof(img.info));
-        img.bvh = tree;
-        img.d = &d;
-        img.info.n_interior = s->info.n_interior;
-        img.mat_kind.assign(u.mat_kind.begin(), u.mat_kind.end());
-        img.mesh_flags.swap(mesh_flags);
-        img.tri_mesh.swap(tri_mesh);
-        {
-            struct Options {  // the records as creation laid them out, whatever the context's options say today
-                yk_context* ctx;
-                int64_t top_nodes, wide_bvh;
-                ~Options() {
-                    ctx->top_nodes = top_nodes;
-                    ctx->wide_bvh = wide_bvh;
-                }
-            } restore{ctx, ctx->top_nodes, ctx->wide_bvh};
-            ctx->top_nodes = u.top_nodes;
-            ctx->wide_bvh = u.wide_bvh;
-            layout_records_host(ctx, &img);
-        }
+        for (size_t k = 0; k < ns; ++k) sphere_material[k] = dev_spheres[k].material;
+        HostLayoutInput in;
+        in.bvh = tree.get();
+        in.n_interior = s->info.n_interior;
+        in.indices = indices;
+        in.points = points;
+        in.normals = normals ? normals : (u.has_normals ? old_normals.data() : nullptr);
+        in.uvs = u.has_uvs ? uvs.data() : nullptr;
+        in.tri_material = tri_material.data();
+        in.tri_area_light = tri_al.data();
+        in.tri_mesh = tri_mesh.data();
+        in.mesh_flags = mesh_flags.data();
+        in.n_triangles = (uint32_t)nt;
+        in.sphere_material = sphere_material.data();
+        in.mat_kind = u.mat_kind.data();
+        in.opt = u.opt;  // the records as creation laid them out, whatever the context's options say today
         if ((rc = upload(ctx, s->points, points, 3 * nv)) != YK_OK || (normals && (rc = upload(ctx, s->normals, normals, 3 * nv)) != YK_OK) ||
-            (rc = upload(ctx, s->nodes, img.dn.data(), img.dn.size())) != YK_OK || (rc = upload(ctx, s->nodes4, img.dn4.data(), img.dn4.size())) != YK_OK ||
-            (rc = upload(ctx, s->top_nodes, img.top.data(), img.top.size())) != YK_OK || (rc = upload(ctx, s->top_nodes_any, img.top_any.data(), img.top_any.size())) != YK_OK ||
-            (rc = upload(ctx, s->tris, img.tris.data(), img.tris.size())) != YK_OK || (rc = upload(ctx, s->prim_shade, img.prim_shade.data(), img.prim_shade.size())) != YK_OK ||
-            (rc = upload(ctx, s->prim_attr, img.prim_attr.data(), img.prim_attr.size())) != YK_OK)
+            (rc = upload_records(ctx, s, layout_records_host(in))) != YK_OK)
             return rc;
         if (s->tree_nodes.p)  // the tree a later device-route update starts from
             HIP_TRY(ctx, hipMemcpy(s->tree_nodes.p, tree->nodes.data(), tree->nodes.size() * sizeof(yk_bvh_node), hipMemcpyHostToDevice));
-        set_record_layout(s, s->info.n_interior, img.dn4.size(), img.top.size(), img.top_any.size(), s->info.n_shapes, u.has_normals || u.has_uvs, img.root_ref, img.wide_auto);
     }
     for (int k = 0; k < 3; ++k) {
         s->info.bounds_min[k] = tree->nodes[0].bmin[k];
@@ -1132,7 +886,7 @@ static yk_status update_scene_host(yk_context* ctx, yk_scene* s, const float* po
         s->bvh_lazy.reset();
         s->tree_fetched.store(1u);
     }
-    if (ctx) rebind_records(s);
+    if (ctx) bind_records(s);
     u.info.seconds_records = now_seconds() - t0;
     return YK_OK;
 }
@@ -1162,7 +916,7 @@ static yk_status update_scene(yk_context* ctx, yk_scene* s, const float* d_point
         fresh->split_failed = s->bvh->split_failed;
         s->bvh = s->bvh_lazy = fresh;
         s->tree_fetched.store(0u);
-        rebind_records(s);
+        bind_records(s);
         u.info.route = YK_UPDATE_ROUTE_DEVICE;
         u.info.reason = YK_LAYOUT_REASON_NONE;
         return YK_OK;
@@ -1175,10 +929,7 @@ static yk_status update_scene(yk_context* ctx, yk_scene* s, const float* d_point
     if (!h_points) h_points = points.data();
     if (d_normals && !h_normals) h_normals = normals.data();
     if (!all_finite(h_points, n)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "points: coordinate not finite");
-    const yk_status rc = update_scene_host(ctx, s, h_points, h_normals);
-    u.info.route = YK_UPDATE_ROUTE_HOST;
-    u.info.reason = reason;
-    return rc;
+    return update_scene_host(ctx, s, h_points, h_normals, reason);
 }
 
 // the arguments both entry points refuse alike
@@ -1203,7 +954,8 @@ yk_status yk_scene_create(yk_context* ctx, const yk_scene_desc* d, yk_scene** ou
     if (!d || !out) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null scene description");
     *out = nullptr;
     std::shared_ptr<SceneImage> img;
-    yk_status st = yk_build_scene_image(ctx, d, img);
+    const SceneBuild what{ctx && ctx->bvh_builder == 1, ctx && ctx->scene_layout == 1, 0u};  // what the context's options ask for
+    yk_status st = yk_build_scene_image(ctx, d, img, what);
     if (st != YK_OK) return st;
     return yk_upload_scene_image(ctx, img, out);
 }
@@ -1217,7 +969,11 @@ yk_status yk_scene_create_device(yk_context* ctx, const yk_scene_desc* d, void* 
     if (rc != YK_OK) return rc;
     if ((uint64_t)d->n_triangles + d->n_spheres > YK_REF_INDEX_MAX) return fail(ctx, YK_ERR_UNSUPPORTED, "more than 2^28 BVH nodes or shapes");
     (void)hipSetDevice(ctx->device);
-    if ((rc = check_device_arrays(ctx, d)) != YK_OK) return rc;
+    const size_t nv = d->n_vertices, nt = d->n_triangles, ns = nt + d->n_spheres;
+    rc = check_device_arrays(ctx, {{"points", d->points, 12 * nv}, {"normals", d->normals, 12 * nv}, {"uvs", d->uvs, 8 * nv},
+                                   {"indices", d->indices, 12 * nt}, {"tri_mesh", d->tri_mesh, 4 * nt}, {"tri_material", d->tri_material, 4 * nt},
+                                   {"tri_area_light", d->tri_area_light, 4 * nt}, {"shape_order", d->shape_order, 4 * ns}});
+    if (rc != YK_OK) return rc;
     hipStream_t st = ctx->stream;
     if (stream) {  // the caller's arrays are complete where its stream stands now
         HIP_TRY(ctx, hipEventRecord(ctx->ev_in, (hipStream_t)stream));
@@ -1255,14 +1011,10 @@ yk_status yk_scene_update(yk_context* ctx, yk_scene* s, const float* points, con
             rc = update_scene(ctx, s, d_points, d_normals, points, normals);
         } else {
             (void)hipGetLastError();
-            rc = update_scene_host(ctx, s, points, normals);
-            u.info.route = YK_UPDATE_ROUTE_HOST;
-            u.info.reason = YK_LAYOUT_REASON_OUT_OF_MEMORY;
+            rc = update_scene_host(ctx, s, points, normals, YK_LAYOUT_REASON_OUT_OF_MEMORY);
         }
     } else {
-        rc = update_scene_host(ctx, s, points, normals);
-        u.info.route = YK_UPDATE_ROUTE_HOST;
-        u.info.reason = YK_LAYOUT_REASON_NONE;
+        rc = update_scene_host(ctx, s, points, normals, YK_LAYOUT_REASON_NONE);
     }
     if (rc == YK_OK) finish_update(s, t_begin);
     return rc;
@@ -1275,12 +1027,8 @@ yk_status yk_scene_update_device(yk_context* ctx, yk_scene* s, const float* d_po
     yk_status rc = check_update(ctx, s, d_points, d_normals);
     if (rc != YK_OK) return rc;
     (void)hipSetDevice(ctx->device);
-    yk_scene_desc d;  // the pointer checks of yk_scene_create_device, with its messages
-    std::memset(&d, 0, sizeof(d));
-    d.n_vertices = s->upd.n_vertices;
-    d.points = d_points;
-    d.normals = d_normals;
-    if ((rc = check_device_arrays(ctx, &d)) != YK_OK) return rc;
+    const size_t bytes = 12 * (size_t)s->upd.n_vertices;  // the pointer checks of yk_scene_create_device, with its messages
+    if ((rc = check_device_arrays(ctx, {{"points", d_points, bytes}, {"normals", d_normals, bytes}})) != YK_OK) return rc;
     if (stream) {  // the caller's arrays are complete where its stream stands now
         HIP_TRY(ctx, hipEventRecord(ctx->ev_in, (hipStream_t)stream));
         HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_in, 0));

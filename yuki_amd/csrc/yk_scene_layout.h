@@ -1,6 +1,6 @@
 // yk_scene_layout.h — the traversal records of a scene as functions of its tree, written once for the gfx950
 // kernels of yk_scene_layout.hip ("scene_layout" = 1) and for the host instance of the two order rules (ibid.,
-// yk_layout_top_order / yk_layout_wide_slots).  The bytes are the ones the sequential loops of yk_scene.cpp
+// yk_layout_top_order / yk_layout_wide_slots).  The bytes are the ones the sequential loops of yk_scene_records.cpp
 // (layout_records_host) produce; those loops stay the yardstick, the expressions below restate them.
 //
 // The tree is the reference's depth-first array of 32-byte nodes, read as 8 words a node (yk_bvh_build.h):

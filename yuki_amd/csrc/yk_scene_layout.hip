@@ -1,7 +1,7 @@
 // yk_scene_layout.hip — "scene_layout" = 1: a scene's traversal records (DevNode, the two LDS tree tops, the
 // DevNode4 collapse, tris / prim_shade / prim_attr in leaf order) laid out on the device from the tree in HBM
 // (yk_scene_layout.h), and the host instance of the two order rules (yk_layout_top_order, yk_layout_wide_slots).
-// The bytes are those of layout_records_host (yk_scene.cpp); a failure here leaves its reason and the caller
+// The bytes are those of layout_records_host (yk_scene_records.cpp); a failure here leaves its reason and the caller
 // lays the records out on the host.
 #include <hip/hip_runtime.h>
 
@@ -143,9 +143,9 @@ uint32_t layout_scene_device(yk_context* ctx, yk_scene* s, const DeviceTree& tre
     uint32_t* order = tree.order.as<uint32_t>();
     const bool root_leaf = (tree.root_words[7] >> 24) != 0u;
     const uint32_t n_interior = (n - 1u) / 2u;  // a full binary tree
-    const uint32_t cap_closest = (uint32_t)std::min<int64_t>(std::min<int64_t>(s->upd.top_nodes, trace_top_nodes()), YK_TOP_MAX);
-    const uint32_t cap_any = (uint32_t)std::min<int64_t>(std::min<int64_t>(s->upd.top_nodes, trace_top_nodes_any()), YK_TOP_MAX);
-    const bool wide = s->upd.wide_bvh != 0 && !root_leaf && tree_depth <= 64;
+    const uint32_t cap_closest = (uint32_t)std::min<int64_t>(std::min<int64_t>(s->upd.opt.top_nodes, trace_top_nodes()), YK_TOP_MAX);
+    const uint32_t cap_any = (uint32_t)std::min<int64_t>(std::min<int64_t>(s->upd.opt.top_nodes, trace_top_nodes_any()), YK_TOP_MAX);
+    const bool wide = s->upd.opt.wide_bvh != 0 && !root_leaf && tree_depth <= 64;
 
     DevScratch tmp;
     uint32_t *d_index = nullptr, *d_bsum = nullptr, *d_slot = nullptr, *d_words = nullptr;
@@ -155,9 +155,8 @@ uint32_t layout_scene_device(yk_context* ctx, yk_scene* s, const DeviceTree& tre
     do {                                                                                                \
         const hipError_t e_ = (expr);                                                                   \
         if (e_ != hipSuccess) {                                                                         \
-            (void)hipGetLastError();                                                                    \
             (void)hipStreamSynchronize(st);                                                             \
-            return e_ == hipErrorOutOfMemory ? YK_LAYOUT_REASON_OUT_OF_MEMORY : YK_LAYOUT_REASON_DEVICE_ERROR; \
+            return layout_reason_of(e_);                                                                \
         }                                                                                               \
     } while (0)
     LAY_TRY(s->nodes.ensure(std::max<size_t>(n_interior, 1) * sizeof(DevNode)));
@@ -218,7 +217,7 @@ uint32_t layout_scene_device(yk_context* ctx, yk_scene* s, const DeviceTree& tre
         LAY_TRY(s->nodes4.ensure(16));
     }
 #undef LAY_TRY
-    set_record_layout(s, n_interior, n4, words[2], words[3], np, has_attr, root_leaf ? (YK_LEAF_BIT | tree.root_words[6]) : 0u, wide && s->upd.wide_bvh == 2);
+    set_record_layout(s, n_interior, n4, words[2], words[3], np, has_attr, root_leaf ? (YK_LEAF_BIT | tree.root_words[6]) : 0u, wide && s->upd.opt.wide_bvh == 2);
     return YK_LAYOUT_REASON_NONE;
 }
 

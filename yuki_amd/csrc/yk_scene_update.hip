@@ -105,15 +105,12 @@ __global__ void __launch_bounds__(kThreads) k_top_levels(uint32_t* nodes, const 
 
 unsigned blocks(size_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
-uint32_t reason_of(hipError_t e) { return e == hipErrorOutOfMemory ? YK_LAYOUT_REASON_OUT_OF_MEMORY : YK_LAYOUT_REASON_DEVICE_ERROR; }
-
 #define UPD_TRY(expr)                       \
     do {                                    \
         const hipError_t e_ = (expr);       \
         if (e_ != hipSuccess) {             \
-            (void)hipGetLastError();        \
             (void)hipStreamSynchronize(st); \
-            return reason_of(e_);           \
+            return layout_reason_of(e_);    \
         }                                   \
     } while (0)
 
@@ -124,25 +121,25 @@ uint32_t build_plan(yk_context* ctx, yk_scene* s) {
     const uint32_t n = (uint32_t)s->info.n_nodes, np = (uint32_t)s->info.n_shapes;
     if (n == 0 || np == 0 || n > YK_REF_INDEX_MAX || np > YK_REF_INDEX_MAX) return YK_LAYOUT_REASON_DEVICE_ERROR;
     size_t added = 0;
-    auto put = [&](DevBuf& buf, const void* src, size_t bytes) -> hipError_t {
-        const size_t had = buf.bytes;
-        hipError_t e = buf.ensure(std::max<size_t>(bytes, 16));
-        if (e == hipSuccess && bytes) e = hipMemcpy(buf.p, src, bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess) added += buf.bytes - had;
-        return e;
-    };
     if (!s->tree_nodes.p || !s->tree_order.p || !u.depth.p) {  // a host-built tree: nodes, depths and order go up, as for the device layout
         const HostBvh* bvh = scene_host_tree(s);
         if (!bvh || bvh->nodes.size() != n || bvh->shape_order.size() != np) return YK_LAYOUT_REASON_DEVICE_ERROR;
-        const std::vector<uint32_t> depth = node_depths(reinterpret_cast<const uint32_t*>(bvh->nodes.data()), n);
-        UPD_TRY(put(s->tree_nodes, bvh->nodes.data(), (size_t)n * sizeof(yk_bvh_node)));
-        UPD_TRY(put(s->tree_order, bvh->shape_order.data(), (size_t)np * 4));
-        UPD_TRY(put(u.depth, depth.data(), (size_t)n * 4));
+        const size_t had = s->tree_nodes.bytes + s->tree_order.bytes + u.depth.bytes;  // nothing, unless a scene kept some of the three
+        DeviceTree up;
+        const hipError_t e = upload_host_tree(*bvh, up);
+        if (e == hipSuccess) adopt_device_tree(s, up, nullptr);  // the host copy stays current
+        up.release();  // what the scene held before (resident beside the upload until here), or the failed upload
+        UPD_TRY(e);
+        added += s->tree_nodes.bytes + s->tree_order.bytes + u.depth.bytes - had;  // growth only: a tree's buffers have one size
     } else {
         added += u.depth.bytes;  // the builder's own, kept since creation
     }
-    UPD_TRY(put(u.sphere_b, u.sphere_bounds.data(), u.sphere_bounds.size() * 4));
-    UPD_TRY(put(u.mat_kind_d, u.mat_kind.data(), u.mat_kind.size()));
+    {
+        const size_t had = u.sphere_b.bytes + u.mat_kind_d.bytes;
+        UPD_TRY(put_host_array(u.sphere_b, u.sphere_bounds.data(), u.sphere_bounds.size() * 4));
+        UPD_TRY(put_host_array(u.mat_kind_d, u.mat_kind.data(), u.mat_kind.size()));
+        added += u.sphere_b.bytes + u.mat_kind_d.bytes - had;
+    }
     // groups: interior nodes by depth below the root (fewer than the tree's depth), then the leaves
     const uint32_t leaf_group = s->bvh->depth + 1u;
     std::vector<uint32_t> words(leaf_group + 2u, 0u);
@@ -257,8 +254,8 @@ uint32_t update_scene_device(yk_context* ctx, yk_scene* s, const float* d_points
     yk_bvh_node root;
     std::memcpy(&root, tree.root_words, sizeof(root));
     for (int k = 0; k < 3; ++k) {
-        s->info.bounds_min[k] = s->dev.root_bmin[k] = root.bmin[k];
-        s->info.bounds_max[k] = s->dev.root_bmax[k] = root.bmax[k];
+        s->info.bounds_min[k] = root.bmin[k];  // bind_records hands them to the kernels
+        s->info.bounds_max[k] = root.bmax[k];
     }
     return YK_LAYOUT_REASON_NONE;
 }
