@@ -783,6 +783,70 @@ yk_status yk_history_blend_device(yk_context* ctx, const yk_temporal_desc* desc,
                                   uint16_t tile_dim, const uint32_t* samples, const void* d_history, void* d_out_history, void* d_out_rgb,
                                   void* stream);
 
+/* ---- motion: the film across moves of the geometry — surface ids, previous positions, reprojection through them ----
+ * After yk_scene_update a pixel's first hit lies on a surface point that stood somewhere else in the previous frame, so
+ * yk_history_reproject (which projects the CURRENT position into the previous camera) carries the wrong history or none.
+ * Three passes, the library's own; the rule is stated next to each expression in yuki_amd/csrc/yk_motion.h and
+ * yk_temporal.h, and the host and the device instance agree bit for bit (binary32, every operation separate, no FMA, a NaN
+ * an operation produces is 0x7fc00000, a value that is only copied keeps its bits).
+ * Intended use: the caller keeps the vertex array it gave to the previous yk_scene_update (or to creation): the scene
+ * copies what it is given.  Then: update(new) -> yk_render_guides_ids -> yk_surface_motion(prev_points = the OLD array)
+ * -> yk_history_reproject_moved -> blend, denoise, tone map as after a camera move.
+ * Ids: one trace per view, the guide pass itself; the id is the identity of the first hit: the source shape as
+ *   yk_trace_closest reports it and the hit's barycentrics (TriHit b0, b1, b2), the operands of si.p.
+ * Motion, per pixel, the cases in this order:
+ *   1. ids.shape == YK_SURFACE_NONE or guides.hit == 0: the all-zero record.
+ *   2. shape >= n_triangles + n_spheres: the all-zero record; the index is never followed.
+ *   3. shape >= n_triangles (a sphere; updates do not move spheres): (guides.p as bits, 1).
+ *   4. A triangle with vertex indices i0, i1, i2: p_prev = P'[i0]*b0 + P'[i1]*b1 + P'[i2]*b2 per component, products first,
+ *      summed left to right (the expression of si.p), P' = prev_points; known = 1.
+ * Reproject-moved: yk_history_reproject's rule with p_P := motion.p_prev; known == 0 gives the zero record as a miss does;
+ *   ns_P and the hit flag come from the CURRENT guide.  So the point projected into the previous camera is the previous
+ *   position, and the plane test d = dot(ns_P, p_Q - p'_P) runs in the previous frame's world, where the previous guides
+ *   live — with the CURRENT normal: exact for a translation, approximate under a rotation (the error is the tap distance
+ *   times the sine of the turn), and a surface that turns by more than acos(normal_cos_min) between two frames loses its
+ *   history.  Carried radiance is the radiance the surface HAD: shadows and reflections of things that moved lag for as
+ *   long as max_history lets them.
+ * Not handled: moving spheres or lights, yk_multi scenes. */
+#define YK_SURFACE_NONE 0xffffffffu
+typedef struct yk_surface_id {
+    uint32_t shape; /* source shape index as yk_trace_closest reports it (a sphere is n_triangles + k); YK_SURFACE_NONE on a miss */
+    float b[3];     /* the hit's barycentrics b0, b1, b2 (TriHit); 0 for a sphere and on a miss */
+} yk_surface_id;    /* 16 bytes; 16-byte aligned on the device */
+typedef struct yk_motion {
+    float p_prev[3]; /* where the pixel's surface point stood under prev_points (world space) */
+    float known;     /* 1.0f, or 0.0f: no previous position (then p_prev is 0) */
+} yk_motion;         /* 16 bytes; 16-byte aligned on the device */
+/* yk_render_guides with the ids beside the guides: the same single trace; the guides are byte for byte yk_render_guides'.
+ * Either output may be NULL, not both.  YK_ERR_INVALID_ARGUMENT: as yk_render_guides, both outputs NULL. */
+yk_status yk_render_guides_ids(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, uint16_t res_x, uint16_t res_y,
+                               yk_guide* out_guides, yk_surface_id* out_ids);
+/* The same into device memory (both 16-byte aligned, not overlapping; anything else: YK_ERR_INVALID_ARGUMENT, nothing is
+ * launched), ordered on `stream` as yk_render_guides_device. */
+yk_status yk_render_guides_ids_device(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, uint16_t res_x, uint16_t res_y,
+                                      void* d_guides, void* d_ids, void* stream);
+/* Host buffers: res_x * res_y records each, row-major; prev_points holds 3 floats for each of the scene's n_vertices (the
+ * call cannot see its length: the caller answers for it).  ctx NULL = the host instance on the CPU, else on ctx's device
+ * (synchronous).  The host instance reads the scene's vertex indices on the host: a host-only scene keeps them; for a
+ * scene in device memory (yk_scene_create, yk_scene_create_device) they are copied back from its device with every call.
+ * YK_ERR_INVALID_ARGUMENT: a NULL pointer, a zero resolution, an output that overlaps an input, with a context a scene of
+ * another device. */
+yk_status yk_surface_motion(yk_context* ctx, const yk_scene* scene, const yk_surface_id* ids, const yk_guide* guides,
+                            const float* prev_points, uint16_t res_x, uint16_t res_y, yk_motion* out);
+/* The same on device buffers (ids, guides and output 16-byte aligned, prev_points 4-byte aligned, the output overlapping no
+ * input; anything else: YK_ERR_INVALID_ARGUMENT, nothing is launched), enqueued on `stream` (NULL = the context's) without
+ * waiting for the device: one launch, no allocation.  An id whose shape is out of range is answered as in the rule. */
+yk_status yk_surface_motion_device(yk_context* ctx, const yk_scene* scene, const void* d_ids, const void* d_guides,
+                                   const float* d_prev_points, uint16_t res_x, uint16_t res_y, void* d_out, void* stream);
+/* yk_history_reproject through the motion records; arguments and errors as yk_history_reproject, plus `motion`. */
+yk_status yk_history_reproject_moved(yk_context* ctx, const yk_temporal_desc* desc, const yk_history* prev_history,
+                                     const yk_guide* prev_guides, const yk_camera* prev_camera, const yk_guide* guides,
+                                     const yk_motion* motion, uint16_t res_x, uint16_t res_y, yk_history* out_history);
+/* The same on device buffers, as yk_history_reproject_device (d_motion 16-byte aligned too). */
+yk_status yk_history_reproject_moved_device(yk_context* ctx, const yk_temporal_desc* desc, const void* d_prev_history,
+                                            const void* d_prev_guides, const yk_camera* prev_camera, const void* d_guides,
+                                            const void* d_motion, uint16_t res_x, uint16_t res_y, void* d_out_history, void* stream);
+
 /* ---- per-stage entry points (parity tests, profiling) ------------------------- */
 /* BoundingVolumeHierarchy::intersect (bvh.rs:160-232) for n host rays.
  * out_shape: source shape index or -1; counters as IntersectionResult. */

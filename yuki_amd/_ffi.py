@@ -178,6 +178,12 @@ SYMBOLS = {
     "yk_history_reproject_device": (C.c_int, [vp, C.POINTER(abi.TemporalDesc), vp, vp, C.POINTER(abi.CameraMatrices), vp, C.c_uint16, C.c_uint16, vp, vp]),
     "yk_history_blend": (C.c_int, [vp, C.POINTER(abi.TemporalDesc), vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp, vp]),
     "yk_history_blend_device": (C.c_int, [vp, C.POINTER(abi.TemporalDesc), vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp, vp, vp]),
+    "yk_render_guides_ids": (C.c_int, [vp, vp, C.POINTER(abi.CameraMatrices), C.c_uint16, C.c_uint16, vp, vp]),
+    "yk_render_guides_ids_device": (C.c_int, [vp, vp, C.POINTER(abi.CameraMatrices), C.c_uint16, C.c_uint16, vp, vp, vp]),
+    "yk_surface_motion": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint16, C.c_uint16, vp]),
+    "yk_surface_motion_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint16, C.c_uint16, vp, vp]),
+    "yk_history_reproject_moved": (C.c_int, [vp, C.POINTER(abi.TemporalDesc), vp, vp, C.POINTER(abi.CameraMatrices), vp, vp, C.c_uint16, C.c_uint16, vp]),
+    "yk_history_reproject_moved_device": (C.c_int, [vp, C.POINTER(abi.TemporalDesc), vp, vp, C.POINTER(abi.CameraMatrices), vp, vp, C.c_uint16, C.c_uint16, vp, vp]),
     "yk_write_png": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
     # several GPUs
     "yk_multi_create": (C.c_int, [C.POINTER(C.c_int), C.c_uint32, C.POINTER(vp)]),

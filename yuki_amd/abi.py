@@ -211,6 +211,9 @@ INTEGRATOR_RAY_DTYPE = np.dtype([("o", "<f4", 3), ("d", "<f4", 3), ("t_max", "<f
 OVERLAY_LINE_DTYPE = np.dtype([("p0", "<f4", 3), ("p1", "<f4", 3), ("rgb", "<f4", 3)])  # yk_overlay_line, 36 bytes
 GUIDE_DTYPE = np.dtype([("ns", "<f4", 3), ("hit", "<f4"), ("p", "<f4", 3), ("t", "<f4")])  # yk_guide, 32 bytes
 HISTORY_DTYPE = np.dtype([("rgb", "<f4", 3), ("n", "<f4")])  # yk_history, 16 bytes
+SURFACE_NONE = 0xFFFFFFFF  # YK_SURFACE_NONE
+SURFACE_ID_DTYPE = np.dtype([("shape", "<u4"), ("b", "<f4", 3)])  # yk_surface_id, 16 bytes
+MOTION_DTYPE = np.dtype([("p_prev", "<f4", 3), ("known", "<f4")])  # yk_motion, 16 bytes
 
 # enums (include/yuki_hip.h)
 SPLIT_SAH, SPLIT_MIDDLE, SPLIT_EQUAL_COUNTS = 0, 1, 2

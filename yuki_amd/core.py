@@ -319,6 +319,67 @@ def reproject_history(history, prev_guides, prev_camera, guides, params, ctx=Non
     return out
 
 
+# --------------------------------------------------------------------------- motion (csrc/yk_motion.h)
+# After Scene.update the film survives like this — the caller keeps the array it gave to the previous update (or to
+# creation), the scene copies what it is given:
+#   scene.update(new); guides, ids = render_guides_ids(...); motion = surface_motion(scene, ids, guides, old);
+#   carried = reproject_history_moved(history, prev_guides, prev_camera, guides, motion, params); then blend_history,
+#   denoise and the tone map as after a camera move.
+def render_guides_ids(ctx, scene, camera, film_settings):
+    """yk_render_guides_ids: render_guides with the identity of every first hit beside it, from the same single trace ->
+    (guides, ids): (h, w) abi.GUIDE_DTYPE, byte for byte render_guides', and (h, w) abi.SURFACE_ID_DTYPE records (shape, b);
+    a miss has shape abi.SURFACE_NONE."""
+    w, h = film_settings.res
+    guides = np.zeros((h, w), dtype=abi.GUIDE_DTYPE)
+    ids = np.zeros((h, w), dtype=abi.SURFACE_ID_DTYPE)
+    check(lib().yk_render_guides_ids(ctx.h, scene.h, C.byref(camera.matrices), w, h, _p(guides), _p(ids)), ctx.h)
+    return guides, ids
+
+
+def _prev_points(scene, prev_points):
+    nv = int(scene.data.points.shape[0])
+    a = np.asarray(prev_points)
+    if a.dtype != np.float32:
+        raise ValueError(f"prev_points is float32, not {a.dtype}")
+    if a.shape not in ((nv, 3), (3 * nv,)):
+        raise ValueError(f"prev_points has shape {a.shape}, the scene {nv} vertices: ({nv}, 3)")
+    return np.ascontiguousarray(a)
+
+
+def surface_motion(scene, ids, guides, prev_points, ctx=None):
+    """yk_surface_motion: where every pixel's surface point stood when the scene's vertices were `prev_points`
+    ((n_vertices, 3) float32, the array given to the previous update or to creation) -> (h, w) abi.MOTION_DTYPE records
+    (p_prev, known).  `ids` and `guides` are render_guides_ids' of the current geometry.  ctx None = the host instance."""
+    guides = np.ascontiguousarray(guides, dtype=abi.GUIDE_DTYPE)
+    if guides.ndim != 2:
+        raise ValueError("guides is (h, w)")
+    h, w = guides.shape
+    ids = _records(ids, abi.SURFACE_ID_DTYPE, (w, h), "surface id")
+    prev_points = _prev_points(scene, prev_points)
+    out = np.zeros((h, w), dtype=abi.MOTION_DTYPE)
+    c = ctx.h if ctx else None
+    check(lib().yk_surface_motion(c, scene.h, _p(ids), _p(guides), _p(prev_points), w, h, _p(out)), c)
+    return out
+
+
+def reproject_history_moved(history, prev_guides, prev_camera, guides, motion, params, ctx=None):
+    """yk_history_reproject_moved: reproject_history after the geometry moved: every pixel is carried from where its
+    surface point stood (`motion`, surface_motion's records) instead of from where it stands.  ctx None = the host
+    instance."""
+    guides = np.ascontiguousarray(guides, dtype=abi.GUIDE_DTYPE)
+    if guides.ndim != 2:
+        raise ValueError("guides is (h, w)")
+    h, w = guides.shape
+    history = _records(history, abi.HISTORY_DTYPE, (w, h), "history")
+    prev_guides = _records(prev_guides, abi.GUIDE_DTYPE, (w, h), "guide")
+    motion = _records(motion, abi.MOTION_DTYPE, (w, h), "motion")
+    d = _temporal_desc(params)
+    out = np.zeros((h, w), dtype=abi.HISTORY_DTYPE)
+    c = ctx.h if ctx else None
+    check(lib().yk_history_reproject_moved(c, C.byref(d), _p(history), _p(prev_guides), C.byref(prev_camera.matrices), _p(guides), _p(motion), w, h, _p(out)), c)
+    return out
+
+
 def _blend_samples(res, tile_dim, samples):
     if samples is not None:
         samples = np.ascontiguousarray(samples, dtype=np.uint32)
@@ -659,6 +720,26 @@ class Context:
         d = _temporal_desc(params)
         vp = C.c_void_p
         check(lib().yk_history_reproject_device(self.h, C.byref(d), vp(d_prev_history_ptr), vp(d_prev_guides_ptr), C.byref(prev_camera.matrices), vp(d_guides_ptr), int(res[0]), int(res[1]), vp(d_out_history_ptr), vp(stream) if stream else None), self.h)
+
+    def render_guides_ids_device(self, scene, camera, res, d_guides_ptr, d_ids_ptr, stream=None):
+        """yk_render_guides_ids_device: render_guides_device with res[0] * res[1] yk_surface_id records (16 bytes each,
+        16-byte aligned) beside the guides, from the same trace; either pointer may be None, not both."""
+        vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
+        check(lib().yk_render_guides_ids_device(self.h, scene.h, C.byref(camera.matrices), int(res[0]), int(res[1]), vp(d_guides_ptr), vp(d_ids_ptr), vp(stream)), self.h)
+
+    def surface_motion_device(self, scene, d_ids_ptr, d_guides_ptr, d_prev_points_ptr, res, d_out_ptr, stream=None):
+        """yk_surface_motion_device: device ids and guides of the current geometry and the PREVIOUS vertex array on the device
+        (3 floats for each of the scene's vertices: the caller answers for its length) -> res[0] * res[1] device yk_motion
+        records, enqueued on `stream` (default: the context's) without waiting; one launch, no allocation."""
+        vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
+        check(lib().yk_surface_motion_device(self.h, scene.h, vp(d_ids_ptr), vp(d_guides_ptr), vp(d_prev_points_ptr), int(res[0]), int(res[1]), vp(d_out_ptr), vp(stream)), self.h)
+
+    def reproject_history_moved_device(self, d_prev_history_ptr, d_prev_guides_ptr, prev_camera, d_guides_ptr, d_motion_ptr, res, params, d_out_history_ptr, stream=None):
+        """yk_history_reproject_moved_device: reproject_history_device through the device motion records of
+        surface_motion_device (all 16-byte aligned), enqueued on `stream` (default: the context's) without waiting."""
+        d = _temporal_desc(params)
+        vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
+        check(lib().yk_history_reproject_moved_device(self.h, C.byref(d), vp(d_prev_history_ptr), vp(d_prev_guides_ptr), C.byref(prev_camera.matrices), vp(d_guides_ptr), vp(d_motion_ptr), int(res[0]), int(res[1]), vp(d_out_history_ptr), vp(stream)), self.h)
 
     def blend_history_device(self, d_film_ptr, res, params, tile_dim, samples, d_history_ptr, d_out_history_ptr, d_out_rgb_ptr, stream=None):
         """yk_history_blend_device: device film + device history (or None) -> device history and / or device RGB (None = not

@@ -304,7 +304,9 @@ YK_HD Surface hit_surface(const DevScene& sc, uint32_t shape, V3 o, V3 d) {
 // fetch less than going through indices -> points and tri_mesh -> mesh_flags.
 // `want_uv`: also compute a sphere's uv (sphere.rs:95-103); the shading path needs it only for image textures.
 // `t_out` (may be NULL): receives the hit distance, Hit.t (the guide pass, k_guides).
-YK_HD Surface hit_surface_prim(const DevScene& sc, uint32_t prim, V3 o, V3 d, bool want_uv, float* t_out) {
+// `id_out` (may be NULL): receives the surface id of the hit (k_guides_ids): the source shape and the TriHit's b0, b1, b2 as
+// bits — the operands Surface::p is combined from; a sphere has no barycentrics and reports zeros.
+YK_HD Surface hit_surface_prim(const DevScene& sc, uint32_t prim, V3 o, V3 d, bool want_uv, float* t_out, uint4* id_out) {
     const float4 v0 = sc.tris[3 * prim], v1 = sc.tris[3 * prim + 1], v2 = sc.tris[3 * prim + 2];
     const uint4 ps = sc.prim_shade[prim];
     const uint32_t src = __float_as_uint(v1.w);
@@ -314,6 +316,7 @@ YK_HD Surface hit_surface_prim(const DevScene& sc, uint32_t prim, V3 o, V3 d, bo
         float t = 0.0f;
         sphere_hit_t(sp, o, d, __builtin_inff(), t, ro, rd);
         if (t_out) *t_out = t;
+        if (id_out) *id_out = make_uint4(src, 0u, 0u, 0u);
         return make_surface_sphere(sp, ro, rd, t, d, want_uv);
     }
     // per-vertex normals and uvs of the primitive, copied into leaf order at scene creation: their address depends on the
@@ -336,14 +339,16 @@ YK_HD Surface hit_surface_prim(const DevScene& sc, uint32_t prim, V3 o, V3 d, bo
     const V3 p0 = V3{v0.x, v0.y, v0.z}, p1 = V3{v1.x, v1.y, v1.z}, p2 = V3{v2.x, v2.y, v2.z};
     tri_intersect(o, rt, __builtin_inff(), p0, p1, p2, th);
     if (t_out) *t_out = th.t;
+    if (id_out) *id_out = make_uint4(src, __float_as_uint(th.b0), __float_as_uint(th.b1), __float_as_uint(th.b2));
     Surface s = sc.prim_attr ? make_surface_vals(p0, p1, p2, at, ps.w & 7u, th) : make_surface_core(sc, p0, p1, p2, ps.x, ps.y, ps.z, ps.w & 7u, th);
     s.material = (int)(ps.w >> 6);
     s.area_light = (int)__float_as_uint(v0.w);
     s.wo = -d;
     return s;
 }
-YK_HD Surface hit_surface_prim(const DevScene& sc, uint32_t prim, V3 o, V3 d, bool want_uv) { return hit_surface_prim(sc, prim, o, d, want_uv, nullptr); }
-YK_HD Surface hit_surface_prim(const DevScene& sc, uint32_t prim, V3 o, V3 d) { return hit_surface_prim(sc, prim, o, d, sc.texels != nullptr, nullptr); }
+YK_HD Surface hit_surface_prim(const DevScene& sc, uint32_t prim, V3 o, V3 d, bool want_uv, float* t_out) { return hit_surface_prim(sc, prim, o, d, want_uv, t_out, nullptr); }
+YK_HD Surface hit_surface_prim(const DevScene& sc, uint32_t prim, V3 o, V3 d, bool want_uv) { return hit_surface_prim(sc, prim, o, d, want_uv, nullptr, nullptr); }
+YK_HD Surface hit_surface_prim(const DevScene& sc, uint32_t prim, V3 o, V3 d) { return hit_surface_prim(sc, prim, o, d, sc.texels != nullptr, nullptr, nullptr); }
 
 // ImageTexture::evaluate, textures/image_texture.rs:81-111: repeat, flip v, point sample.
 // `as usize` saturates (NaN and negatives -> 0); the index cannot leave the image.

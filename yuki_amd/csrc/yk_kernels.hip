@@ -615,6 +615,31 @@ __global__ void k_guides(DevScene sc, PathBuffers cur, const int* hit_tri, uint3
     guides[2 * px + 1] = b;
 }
 
+// The same trace with the surface id beside the guide (yk_render_guides_ids): ids[px] = (source shape, bits of b0, b1, b2),
+// (YK_SURFACE_NONE, 0, 0, 0) on a miss.  Either output may be null (a kernel argument: no lane disagrees); the guide
+// record is k_guides' own, expression for expression.
+__global__ void k_guides_ids(DevScene sc, PathBuffers cur, const int* hit_tri, uint32_t n, const uint32_t* pixel_xy, uint32_t res_x, float4* guides, uint4* ids) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 rd = cur.rayD[i];
+    const uint32_t xy = pixel_xy[__float_as_uint(rd.w)];
+    const size_t px = (size_t)(xy >> 16) * res_x + (xy & 0xffffu);
+    const int tri = hit_tri[i];
+    float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f), b = a;
+    uint4 id = make_uint4(YK_SURFACE_NONE, 0u, 0u, 0u);
+    if (tri >= 0) {
+        float t = 0.0f;
+        const Surface sf = hit_surface_prim(sc, (uint32_t)tri & YK_HIT_PRIM_MASK, f4_xyz(cur.rayO[i]), f4_xyz(rd), sc.texels != nullptr, &t, &id);
+        a = make_float4(sf.ns.x, sf.ns.y, sf.ns.z, 1.0f);
+        b = make_float4(sf.p.x, sf.p.y, sf.p.z, t);
+    }
+    if (guides) {
+        guides[2 * px] = a;
+        guides[2 * px + 1] = b;
+    }
+    if (ids) ids[px] = id;
+}
+
 // ------------------------------------------------------------------ unit-test kernels
 __global__ void k_device_math(int fn, size_t n, const float* a, const float* b, float* out) {
     size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
@@ -827,6 +852,9 @@ void launch_debug_shade(hipStream_t s, const DevScene& sc, uint32_t integrator, 
 }
 void launch_guides(hipStream_t s, const DevScene& sc, PathBuffers cur, const int* hit_tri, uint32_t n, const uint32_t* pixel_xy, uint32_t res_x, float4* guides) {
     hipLaunchKernelGGL(k_guides, dim3(blocks_for(n, 256)), dim3(256), 0, s, sc, cur, hit_tri, n, pixel_xy, res_x, guides);
+}
+void launch_guides_ids(hipStream_t s, const DevScene& sc, PathBuffers cur, const int* hit_tri, uint32_t n, const uint32_t* pixel_xy, uint32_t res_x, float4* guides, uint4* ids) {
+    hipLaunchKernelGGL(k_guides_ids, dim3(blocks_for(n, 256)), dim3(256), 0, s, sc, cur, hit_tri, n, pixel_xy, res_x, guides, ids);
 }
 void launch_device_math(hipStream_t s, int fn, size_t n, const float* a, const float* b, float* out) {
     hipLaunchKernelGGL(k_device_math, dim3(blocks_for(n, 256)), dim3(256), 0, s, fn, n, a, b, out);

@@ -1,0 +1,144 @@
+// yk_motion.hip — previous positions on gfx950, behind yk_surface_motion[_device]; the per-pixel arithmetic is yk_motion.h's,
+// whose host instance these entry points run without a context.
+//
+// k_motion: one lane per pixel, a block is a MO_TX x MO_TY tile of the film (k_reproject's launch shape: neighbouring lanes
+//   hit neighbouring triangles, so their index and vertex requests share cache lines).  A lane reads its id (one 16-byte
+//   load) and its guide (two 16-byte loads), then follows a two-hop gather: three dword index loads requested together,
+//   then nine dword vertex loads requested together (a vertex is 12 bytes at a 4-byte aligned address: no wider load is
+//   always legal), and writes one 16-byte record.  No load stands under a per-lane branch: a lane that is not a triangle
+//   asks for triangle 0 and drops the answer.  No LDS: which vertices a tile touches is not known before the ids are read.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <vector>
+
+#include "yk_internal.h"
+#include "yk_motion.h"
+
+namespace {
+
+constexpr unsigned MO_TX = 32, MO_TY = 8;  // 256 lanes: 4 waves of 64
+
+struct MoIo {
+    const uint4* ids;         // one uint4 a pixel: (shape, bits of b0, b1, b2)
+    const float4* guides;     // two float4 a pixel: (ns, hit), (p, t)
+    const uint32_t* indices;  // the scene's own: 3 a triangle
+    const float* prev_points; // 3 a vertex
+    float4* out;
+};
+
+__global__ __launch_bounds__(MO_TX* MO_TY) void k_motion(MoIo io, MoParams a) {
+    const uint32_t x = blockIdx.x * MO_TX + threadIdx.x, y = blockIdx.y * MO_TY + threadIdx.y;
+    if (x >= a.res_x || y >= a.res_y) return;
+    const size_t i = (size_t)y * a.res_x + x;
+    const uint4 id = io.ids[i];
+    const float4 ga = io.guides[2 * i], gb = io.guides[2 * i + 1];
+    const float p[3] = {gb.x, gb.y, gb.z};
+    float rec[4];
+    mo_pixel(a, id.x, __uint_as_float(id.y), __uint_as_float(id.z), __uint_as_float(id.w), ga.w, p,
+             [&](size_t k) { return io.indices[k]; },
+             [&](uint32_t v) { return V3{io.prev_points[3 * (size_t)v], io.prev_points[3 * (size_t)v + 1], io.prev_points[3 * (size_t)v + 2]}; }, rec);
+    io.out[i] = make_float4(rec[0], rec[1], rec[2], rec[3]);
+}
+
+bool overlaps(const void* p, size_t np, const void* q, size_t nq) {
+    const uintptr_t p0 = (uintptr_t)p, q0 = (uintptr_t)q;
+    return p0 < q0 + nq && q0 < p0 + np;
+}
+
+yk_status check_call(const yk_scene* scene, const void* ids, const void* guides, const float* prev_points, uint16_t res_x, uint16_t res_y, const void* out) {
+    if (!scene || !ids || !guides || !prev_points || !out || res_x == 0 || res_y == 0) return YK_ERR_INVALID_ARGUMENT;
+    const size_t n_px = (size_t)res_x * res_y;
+    if (overlaps(out, n_px * sizeof(yk_motion), ids, n_px * sizeof(yk_surface_id)) || overlaps(out, n_px * sizeof(yk_motion), guides, n_px * sizeof(yk_guide)) ||
+        overlaps(out, n_px * sizeof(yk_motion), prev_points, (size_t)scene->upd.n_vertices * 12))
+        return YK_ERR_INVALID_ARGUMENT;
+    return YK_OK;
+}
+
+MoParams make_params(const yk_scene* scene, uint16_t res_x, uint16_t res_y) {
+    MoParams a{};
+    a.res_x = res_x;
+    a.res_y = res_y;
+    a.n_triangles = scene->n_triangles;
+    a.n_shapes = scene->n_triangles + scene->n_spheres;
+    return a;
+}
+
+yk_status enqueue(yk_context* ctx, hipStream_t st, const yk_scene* scene, const void* ids, const void* guides, const float* prev_points, uint16_t res_x, uint16_t res_y, void* out) {
+    const MoParams a = make_params(scene, res_x, res_y);
+    MoIo io{reinterpret_cast<const uint4*>(ids), reinterpret_cast<const float4*>(guides), scene->dev.indices, prev_points, reinterpret_cast<float4*>(out)};
+    const dim3 grid((res_x + MO_TX - 1) / MO_TX, (res_y + MO_TY - 1) / MO_TY), block(MO_TX, MO_TY);
+    hipLaunchKernelGGL(k_motion, grid, block, 0, st, io, a);
+    HIP_TRY(ctx, hipGetLastError());
+    return YK_OK;
+}
+
+void motion_host(const yk_scene* scene, const uint32_t* indices, const yk_surface_id* ids, const yk_guide* guides, const float* prev_points, uint16_t res_x, uint16_t res_y, yk_motion* out) {
+    const MoParams a = make_params(scene, res_x, res_y);
+    const auto index = [&](size_t k) { return indices[k]; };
+    const auto point = [&](uint32_t v) { return V3{prev_points[3 * (size_t)v], prev_points[3 * (size_t)v + 1], prev_points[3 * (size_t)v + 2]}; };
+    const size_t n_px = (size_t)res_x * res_y;
+    for (size_t i = 0; i < n_px; ++i) {
+        float rec[4];
+        mo_pixel(a, ids[i].shape, ids[i].b[0], ids[i].b[1], ids[i].b[2], guides[i].hit, guides[i].p, index, point, rec);
+        std::memcpy(&out[i], rec, 16);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+yk_status yk_surface_motion(yk_context* ctx, const yk_scene* scene, const yk_surface_id* ids, const yk_guide* guides, const float* prev_points, uint16_t res_x, uint16_t res_y,
+                            yk_motion* out) try {
+    if (check_call(scene, ids, guides, prev_points, res_x, res_y, out) != YK_OK) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_surface_motion: bad argument");
+    const size_t n_px = (size_t)res_x * res_y;
+    if (!ctx) {  // the host instance
+        const size_t n_idx = 3 * (size_t)scene->n_triangles;
+        std::vector<uint32_t> fetched;
+        const uint32_t* indices = scene->upd.host_indices.data();
+        if (n_idx && scene->upd.host_indices.size() != n_idx) {  // a scene in device memory: its indices live there
+            if (!scene->on_device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_surface_motion: the scene has no vertex indices");
+            fetched.resize(n_idx);
+            (void)hipSetDevice(scene->device);
+            HIP_TRY(ctx, hipMemcpy(fetched.data(), scene->indices.p, n_idx * 4, hipMemcpyDeviceToHost));
+            indices = fetched.data();
+        }
+        motion_host(scene, indices, ids, guides, prev_points, res_x, res_y, out);
+        return YK_OK;
+    }
+    YK_LOCK(ctx);
+    if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_surface_motion: scene was not created on this context's device");
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    const size_t point_bytes = std::max<size_t>((size_t)scene->upd.n_vertices * 12, 16);
+    HIP_TRY(ctx, ctx->scratch[4].ensure(n_px * sizeof(yk_surface_id)));
+    HIP_TRY(ctx, ctx->scratch[5].ensure(n_px * sizeof(yk_guide)));
+    HIP_TRY(ctx, ctx->scratch[6].ensure(point_bytes));
+    HIP_TRY(ctx, ctx->scratch[7].ensure(n_px * sizeof(yk_motion)));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[4].p, ids, n_px * sizeof(yk_surface_id), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[5].p, guides, n_px * sizeof(yk_guide), hipMemcpyHostToDevice, st));
+    if (scene->upd.n_vertices) HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[6].p, prev_points, (size_t)scene->upd.n_vertices * 12, hipMemcpyHostToDevice, st));
+    yk_status s = enqueue(ctx, st, scene, ctx->scratch[4].p, ctx->scratch[5].p, ctx->scratch[6].as<const float>(), res_x, res_y, ctx->scratch[7].p);
+    if (s != YK_OK) return s;
+    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->scratch[7].p, n_px * sizeof(yk_motion), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return YK_OK;
+}
+YK_CATCH(ctx)
+
+yk_status yk_surface_motion_device(yk_context* ctx, const yk_scene* scene, const void* d_ids, const void* d_guides, const float* d_prev_points, uint16_t res_x, uint16_t res_y, void* d_out,
+                                   void* stream) {
+    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
+    YK_LOCK(ctx);
+    if (check_call(scene, d_ids, d_guides, d_prev_points, res_x, res_y, d_out) != YK_OK) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_surface_motion_device: bad argument");
+    if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_surface_motion_device: scene was not created on this context's device");
+    // 16-byte loads and stores of the records and the guides, dword loads of the vertices
+    if (((uintptr_t)d_ids & 15u) || ((uintptr_t)d_guides & 15u) || ((uintptr_t)d_out & 15u) || ((uintptr_t)d_prev_points & 3u))
+        return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_surface_motion_device: ids, guides and output must be 16-byte aligned, prev_points 4-byte aligned");
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    return enqueue(ctx, st, scene, d_ids, d_guides, d_prev_points, res_x, res_y, d_out);
+}
+
+}  // extern "C"

@@ -279,11 +279,12 @@ static bool wait_polling(yk_context* ctx, hipEvent_t done, hipStream_t st, yk_ca
 // 146-161): one sample per pixel with global index tile_samples[t], raw value stored.
 // guides_res_x != 0: the guide pass (yk_render_guides) — a debug integrator's trace, one sample a pixel; d_out_rgb is then
 // a row-major film of yk_guide records, guides_res_x wide, written by k_guides instead of the shade and resolve kernels.
+// With d_ids (yk_render_guides_ids) k_guides_ids writes the yk_surface_id records there too, and d_out_rgb may be NULL.
 static yk_status render_tiles_impl(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler,
                                    const yk_integrator_desc* integrator, const yk_tile* tiles, const uint16_t* tile_samples, size_t n_tiles,
                                    void* d_out_rgb, void* stream, yk_render_stats* stats, yk_cancel_fn cancel, void* user,
                                    const yk_tile_list* prepared = nullptr, uint32_t n_passes = 1, int64_t uniform_first_sample = -1,
-                                   uint32_t guides_res_x = 0) try {
+                                   uint32_t guides_res_x = 0, void* d_ids = nullptr) try {
     if (!ctx) return YK_ERR_INVALID_ARGUMENT;
     YK_LOCK(ctx);
     if (prepared) {
@@ -292,7 +293,7 @@ static yk_status render_tiles_impl(yk_context* ctx, const yk_scene* scene, const
         tile_samples = prepared->samples.empty() ? nullptr : prepared->samples.data();
         n_tiles = prepared->tiles.size();
     }
-    if (!scene || !camera || !tiles || n_tiles == 0 || !d_out_rgb) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null argument");
+    if (!scene || !camera || !tiles || n_tiles == 0 || (!d_out_rgb && !(guides_res_x && d_ids))) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null argument");
     if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "scene was not created on this context's device");
     RenderParams prm;
     yk_status ps = make_params(ctx, sampler, integrator, prm);
@@ -519,7 +520,8 @@ static yk_status render_tiles_impl(yk_context* ctx, const yk_scene* scene, const
                                      want_stats ? ctx->stats4.as<uint4>() : nullptr, ws.spill.as<uint2>(), trace_grid(ctx) * trace_block_size(), errblk,
                                      counters);
                 kt.end(e, 0, bs);
-                if (guides_res_x) launch_guides(bs, scene->dev, pc, ws.hit.as<int>(), n, pixel_xy, guides_res_x, reinterpret_cast<float4*>(d_out_rgb));
+                if (guides_res_x && d_ids) launch_guides_ids(bs, scene->dev, pc, ws.hit.as<int>(), n, pixel_xy, guides_res_x, reinterpret_cast<float4*>(d_out_rgb), reinterpret_cast<uint4*>(d_ids));
+                else if (guides_res_x) launch_guides(bs, scene->dev, pc, ws.hit.as<int>(), n, pixel_xy, guides_res_x, reinterpret_cast<float4*>(d_out_rgb));
                 else launch_debug_shade(bs, scene->dev, prm.integrator, pc, ws.hit.as<int>(), ctx->stats4.as<uint4>(), n, sample_buf);
                 ++n_trace;
             }
@@ -786,14 +788,14 @@ extern "C" {
 
 // The guides: the ShadingNormals integrator's trace of the whole film as one tile under a 1 x 1 Stratified sampler without
 // jitter, whose camera sample is the pixel centre whatever its seed, so the ray is Camera::ray((x + 0.5, y + 0.5)).
-static yk_status render_guides(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, uint16_t res_x, uint16_t res_y, void* d_guides, void* stream) {
+static yk_status render_guides(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, uint16_t res_x, uint16_t res_y, void* d_guides, void* stream, void* d_ids = nullptr) {
     yk_sampler_desc smp = {};
     smp.kind = YK_SAMPLER_STRATIFIED;
     smp.nx = smp.ny = 1;
     yk_integrator_desc integ = {};
     integ.kind = YK_INTEGRATOR_SHADING_NORMALS;
     const yk_tile film = {0, 0, res_x, res_y};
-    return render_tiles_impl(ctx, scene, camera, &smp, &integ, &film, nullptr, 1, d_guides, stream, nullptr, nullptr, nullptr, nullptr, 1, -1, res_x);
+    return render_tiles_impl(ctx, scene, camera, &smp, &integ, &film, nullptr, 1, d_guides, stream, nullptr, nullptr, nullptr, nullptr, 1, -1, res_x, d_ids);
 }
 
 yk_status yk_render_guides_device(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, uint16_t res_x, uint16_t res_y, void* d_guides, void* stream) {
@@ -814,6 +816,35 @@ yk_status yk_render_guides(yk_context* ctx, const yk_scene* scene, const yk_came
     yk_status st = render_guides(ctx, scene, camera, res_x, res_y, ctx->scratch[0].p, nullptr);
     if (st != YK_OK) return st;
     HIP_TRY(ctx, hipMemcpyAsync(out, ctx->scratch[0].p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return YK_OK;
+}
+
+// The guides with the surface ids beside them (yk_motion.h): the same single trace, k_guides_ids instead of k_guides.
+yk_status yk_render_guides_ids_device(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, uint16_t res_x, uint16_t res_y, void* d_guides, void* d_ids, void* stream) {
+    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
+    YK_LOCK(ctx);
+    if (!scene || !camera || (!d_guides && !d_ids) || res_x == 0 || res_y == 0) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_guides_ids_device: bad argument");
+    if (((uintptr_t)d_guides & 15u) || ((uintptr_t)d_ids & 15u)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_guides_ids_device: guides and ids must be 16-byte aligned");
+    const size_t n_px = (size_t)res_x * res_y;
+    if (d_guides && d_ids && (uintptr_t)d_guides < (uintptr_t)d_ids + n_px * sizeof(yk_surface_id) && (uintptr_t)d_ids < (uintptr_t)d_guides + n_px * sizeof(yk_guide))
+        return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_guides_ids_device: guides and ids overlap");
+    if (!d_ids) return render_guides(ctx, scene, camera, res_x, res_y, d_guides, stream);  // guides alone: yk_render_guides_device
+    return render_guides(ctx, scene, camera, res_x, res_y, d_guides, stream, d_ids);
+}
+
+yk_status yk_render_guides_ids(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, uint16_t res_x, uint16_t res_y, yk_guide* out_guides, yk_surface_id* out_ids) {
+    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
+    YK_LOCK(ctx);
+    if (!scene || !camera || (!out_guides && !out_ids) || res_x == 0 || res_y == 0) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_guides_ids: bad argument");
+    const size_t n_px = (size_t)res_x * res_y;
+    (void)hipSetDevice(ctx->device);
+    if (out_guides) HIP_TRY(ctx, ctx->scratch[0].ensure(n_px * sizeof(yk_guide)));
+    if (out_ids) HIP_TRY(ctx, ctx->scratch[1].ensure(n_px * sizeof(yk_surface_id)));
+    yk_status st = render_guides(ctx, scene, camera, res_x, res_y, out_guides ? ctx->scratch[0].p : nullptr, nullptr, out_ids ? ctx->scratch[1].p : nullptr);
+    if (st != YK_OK) return st;
+    if (out_guides) HIP_TRY(ctx, hipMemcpyAsync(out_guides, ctx->scratch[0].p, n_px * sizeof(yk_guide), hipMemcpyDeviceToHost, ctx->stream));
+    if (out_ids) HIP_TRY(ctx, hipMemcpyAsync(out_ids, ctx->scratch[1].p, n_px * sizeof(yk_surface_id), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return YK_OK;
 }

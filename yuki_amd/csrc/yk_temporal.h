@@ -12,7 +12,8 @@
 //
 // Reprojected radiance is exact for view-independent (diffuse) surfaces only.  On glass and metal the carried mean is the
 // radiance towards the PREVIOUS eye: it lags the view, and max_history bounds how long — a new sample always weighs at
-// least m / (max_history + m).  Geometry that moves is not handled: the guides carry no primitive identity.
+// least m / (max_history + m).  Geometry that moves: tp_reproject_moved_pixel below, through the motion records of
+// yk_motion.h.
 #pragma once
 #include "yk_denoise.h"
 #include "yk_math.h"
@@ -131,6 +132,21 @@ YK_HD void tp_reproject_pixel(const TpParams& a, const float* c2w_inv, const flo
     out[1] = dn_canon(sg / sw);
     out[2] = dn_canon(sb / sw);
     out[3] = dn_canon(sn / sw);
+}
+
+// Reproject after the GEOMETRY moved (yk_history_reproject_moved), one current pixel whose guide is (nsP, hitP, .) and whose
+// motion record is mv = (p_prev, known): tp_reproject_pixel with pP := p_prev; known == 0 gives the zero record, as a miss
+// does.  Nothing else of the rule changes:
+//   - the point projected into the previous camera is the previous position of the pixel's surface point;
+//   - the plane test d = dot(nsP, p_Q - p_prev) runs entirely in the previous frame's world, where the previous guides live;
+//   - nsP is the CURRENT shading normal, in the plane test and in the normal test.  The plane test is therefore exact for
+//     a translation and approximate under a rotation: the error is the tap distance times the sine of the turn.  A surface
+//     that turns by more than acos(normal_cos_min) between two frames loses its history.
+// Carried radiance is the radiance the surface HAD: shadows and reflections of things that moved lag, for as long as
+// max_history lets them.  A NaN in p_prev makes the projection's w a NaN (0 * NaN included): the zero record.
+template <class Fetch>
+YK_HD void tp_reproject_moved_pixel(const TpParams& a, const float* c2w_inv, const float* r2c_inv, V3 nsP, float hitP, const float* mv, const Fetch& fetch, float* out) {
+    tp_reproject_pixel(a, c2w_inv, r2c_inv, nsP, mv[3] == 0.0f ? 0.0f : hitP, V3{mv[0], mv[1], mv[2]}, fetch, out);
 }
 
 // Blend, one pixel.  c: the film's RGB (its bits); m = (float)samples[tm_sample_index] (dn_count, the floor / ceil

@@ -11,6 +11,9 @@
 //   store of the records, three dword stores of the RGB output.  "No table", "no history", "no history output" and "no RGB
 //   output" are template variants: no lane tests a pointer.  A lane reads its own pixel only, and before it writes it, so
 //   out_history may be the history and out_rgb the film.
+// k_reproject<true> (yk_history_reproject_moved): the same lane with the pixel's motion record (one 16-byte load, requested
+//   with the guide loads) in the place of the guide's (p, t) half, which this instance does not read.  The motion pointer
+//   is the kernel's last argument: k_reproject<false> is the kernel as it was.
 // The sample table is staged through the pinned copy the tone map and the denoiser share; the stream-ordered entry points
 // allocate nothing once the context has seen a table of that size.
 #include <hip/hip_runtime.h>
@@ -31,13 +34,14 @@ struct TpIo {
     float4* out;
 };
 
-__global__ __launch_bounds__(TP_TX* TP_TY) void k_reproject(TpIo io, TpParams a, M44 c2w_inv, M44 r2c_inv) {
+template <bool MOVED>
+__global__ __launch_bounds__(TP_TX* TP_TY) void k_reproject(TpIo io, TpParams a, M44 c2w_inv, M44 r2c_inv, const float4* motion) {
     const uint32_t x = blockIdx.x * TP_TX + threadIdx.x, y = blockIdx.y * TP_TY + threadIdx.y;
     if (x >= a.dn.res_x || y >= a.dn.res_y) return;
     const size_t i = (size_t)y * a.dn.res_x + x;
-    const float4 ga = io.guides[2 * i], gb = io.guides[2 * i + 1];
+    const float4 ga = io.guides[2 * i], gb = MOVED ? motion[i] : io.guides[2 * i + 1];  // MOVED: (p_prev, known) for (p, t)
     float rec[4];
-    tp_reproject_pixel(a, c2w_inv.m, r2c_inv.m, V3{ga.x, ga.y, ga.z}, ga.w, V3{gb.x, gb.y, gb.z},
+    tp_reproject_pixel(a, c2w_inv.m, r2c_inv.m, V3{ga.x, ga.y, ga.z}, MOVED && gb.w == 0.0f ? 0.0f : ga.w, V3{gb.x, gb.y, gb.z},
                        [&](uint32_t qx, uint32_t qy, TpTap& t) {
                            const size_t q = (size_t)qy * a.dn.res_x + qx;
                            const float4 hv = io.prev_history[q], qa = io.prev_guides[2 * q], qb = io.prev_guides[2 * q + 1];
@@ -140,12 +144,14 @@ size_t table_words(uint16_t res_x, uint16_t res_y, uint16_t tile_dim) {
     return (size_t)((res_x + tile_dim - 1) / tile_dim) * (size_t)((res_y + tile_dim - 1) / tile_dim);
 }
 
+// has_motion: the call is yk_history_reproject_moved's and `motion` is one more input
 yk_status check_reproject(const yk_temporal_desc* d, const void* prev_history, const void* prev_guides, const yk_camera* prev_camera, const void* guides, uint16_t res_x, uint16_t res_y,
-                          const void* out) {
-    if (!desc_ok(d) || !prev_history || !prev_guides || !prev_camera || !guides || !out || res_x == 0 || res_y == 0) return YK_ERR_INVALID_ARGUMENT;
+                          const void* out, bool has_motion = false, const void* motion = nullptr) {
+    if (!desc_ok(d) || !prev_history || !prev_guides || !prev_camera || !guides || !out || res_x == 0 || res_y == 0 || (has_motion && !motion)) return YK_ERR_INVALID_ARGUMENT;
     const size_t n_px = (size_t)res_x * res_y;
     if (overlaps(out, n_px * 16, prev_history, n_px * 16) || overlaps(out, n_px * 16, prev_guides, n_px * sizeof(yk_guide)) || overlaps(out, n_px * 16, guides, n_px * sizeof(yk_guide)))
         return YK_ERR_INVALID_ARGUMENT;
+    if (has_motion && overlaps(out, n_px * 16, motion, n_px * sizeof(yk_motion))) return YK_ERR_INVALID_ARGUMENT;
     return YK_OK;
 }
 
@@ -166,14 +172,15 @@ yk_status check_blend(const yk_temporal_desc* d, const void* film, uint16_t res_
 }
 
 yk_status enqueue_reproject(yk_context* ctx, hipStream_t st, const yk_temporal_desc* d, const void* prev_history, const void* prev_guides, const yk_camera* cam, const void* guides,
-                            uint16_t res_x, uint16_t res_y, void* out) {
+                            uint16_t res_x, uint16_t res_y, void* out, const void* motion = nullptr) {
     const TpParams a = make_params(d, res_x, res_y, 1);
     TpIo io{reinterpret_cast<const float4*>(prev_history), reinterpret_cast<const float4*>(prev_guides), reinterpret_cast<const float4*>(guides), reinterpret_cast<float4*>(out)};
     M44 c2w_inv, r2c_inv;
     std::memcpy(c2w_inv.m, cam->camera_to_world_inv, 64);
     std::memcpy(r2c_inv.m, cam->raster_to_camera_inv, 64);
     const dim3 grid((res_x + TP_TX - 1) / TP_TX, (res_y + TP_TY - 1) / TP_TY), block(TP_TX, TP_TY);
-    hipLaunchKernelGGL(k_reproject, grid, block, 0, st, io, a, c2w_inv, r2c_inv);
+    if (motion) hipLaunchKernelGGL(k_reproject<true>, grid, block, 0, st, io, a, c2w_inv, r2c_inv, reinterpret_cast<const float4*>(motion));
+    else hipLaunchKernelGGL(k_reproject<false>, grid, block, 0, st, io, a, c2w_inv, r2c_inv, (const float4*)nullptr);
     HIP_TRY(ctx, hipGetLastError());
     return YK_OK;
 }
@@ -205,7 +212,7 @@ void fetch_host(const float* hist, const yk_guide* g, size_t q, TpTap& t) {
 }
 
 void reproject_host(const yk_temporal_desc* d, const yk_history* prev_history, const yk_guide* prev_guides, const yk_camera* cam, const yk_guide* guides, uint16_t res_x, uint16_t res_y,
-                    yk_history* out) {
+                    yk_history* out, const yk_motion* motion = nullptr) {
     const TpParams a = make_params(d, res_x, res_y, 1);
     const float* hist = reinterpret_cast<const float*>(prev_history);
     const auto fetch = [&](uint32_t qx, uint32_t qy, TpTap& t) { fetch_host(hist, prev_guides, (size_t)qy * res_x + qx, t); };
@@ -214,7 +221,11 @@ void reproject_host(const yk_temporal_desc* d, const yk_history* prev_history, c
             const size_t i = (size_t)y * res_x + x;
             const yk_guide& g = guides[i];
             float rec[4];
-            tp_reproject_pixel(a, cam->camera_to_world_inv, cam->raster_to_camera_inv, V3{g.ns[0], g.ns[1], g.ns[2]}, g.hit, V3{g.p[0], g.p[1], g.p[2]}, fetch, rec);
+            if (motion) {
+                const float mv[4] = {motion[i].p_prev[0], motion[i].p_prev[1], motion[i].p_prev[2], motion[i].known};
+                tp_reproject_moved_pixel(a, cam->camera_to_world_inv, cam->raster_to_camera_inv, V3{g.ns[0], g.ns[1], g.ns[2]}, g.hit, mv, fetch, rec);
+            } else
+                tp_reproject_pixel(a, cam->camera_to_world_inv, cam->raster_to_camera_inv, V3{g.ns[0], g.ns[1], g.ns[2]}, g.hit, V3{g.p[0], g.p[1], g.p[2]}, fetch, rec);
             std::memcpy(&out[i], rec, 16);
         }
 }
@@ -276,6 +287,48 @@ yk_status yk_history_reproject_device(yk_context* ctx, const yk_temporal_desc* d
     (void)hipSetDevice(ctx->device);
     hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
     return enqueue_reproject(ctx, st, desc, d_prev_history, d_prev_guides, prev_camera, d_guides, res_x, res_y, d_out_history);
+}
+
+yk_status yk_history_reproject_moved(yk_context* ctx, const yk_temporal_desc* desc, const yk_history* prev_history, const yk_guide* prev_guides, const yk_camera* prev_camera,
+                                     const yk_guide* guides, const yk_motion* motion, uint16_t res_x, uint16_t res_y, yk_history* out_history) {
+    if (check_reproject(desc, prev_history, prev_guides, prev_camera, guides, res_x, res_y, out_history, true, motion) != YK_OK)
+        return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_history_reproject_moved: bad argument");
+    if (!ctx) {  // the host instance
+        reproject_host(desc, prev_history, prev_guides, prev_camera, guides, res_x, res_y, out_history, motion);
+        return YK_OK;
+    }
+    YK_LOCK(ctx);
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    const size_t n_px = (size_t)res_x * res_y;
+    HIP_TRY(ctx, ctx->scratch[3].ensure(n_px * sizeof(yk_motion)));
+    HIP_TRY(ctx, ctx->scratch[4].ensure(n_px * 16));
+    HIP_TRY(ctx, ctx->scratch[5].ensure(n_px * sizeof(yk_guide)));
+    HIP_TRY(ctx, ctx->scratch[6].ensure(n_px * sizeof(yk_guide)));
+    HIP_TRY(ctx, ctx->scratch[7].ensure(n_px * 16));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[3].p, motion, n_px * sizeof(yk_motion), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[4].p, prev_history, n_px * 16, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[5].p, prev_guides, n_px * sizeof(yk_guide), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[6].p, guides, n_px * sizeof(yk_guide), hipMemcpyHostToDevice, st));
+    yk_status s = enqueue_reproject(ctx, st, desc, ctx->scratch[4].p, ctx->scratch[5].p, prev_camera, ctx->scratch[6].p, res_x, res_y, ctx->scratch[7].p, ctx->scratch[3].p);
+    if (s != YK_OK) return s;
+    HIP_TRY(ctx, hipMemcpyAsync(out_history, ctx->scratch[7].p, n_px * 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return YK_OK;
+}
+
+yk_status yk_history_reproject_moved_device(yk_context* ctx, const yk_temporal_desc* desc, const void* d_prev_history, const void* d_prev_guides, const yk_camera* prev_camera,
+                                            const void* d_guides, const void* d_motion, uint16_t res_x, uint16_t res_y, void* d_out_history, void* stream) {
+    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
+    YK_LOCK(ctx);
+    if (check_reproject(desc, d_prev_history, d_prev_guides, prev_camera, d_guides, res_x, res_y, d_out_history, true, d_motion) != YK_OK)
+        return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_history_reproject_moved_device: bad argument");
+    // 16-byte loads and stores of the records, the guides and the motion
+    if (((uintptr_t)d_prev_history & 15u) || ((uintptr_t)d_prev_guides & 15u) || ((uintptr_t)d_guides & 15u) || ((uintptr_t)d_motion & 15u) || ((uintptr_t)d_out_history & 15u))
+        return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_history_reproject_moved_device: histories, guides and motion must be 16-byte aligned");
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    return enqueue_reproject(ctx, st, desc, d_prev_history, d_prev_guides, prev_camera, d_guides, res_x, res_y, d_out_history, d_motion);
 }
 
 yk_status yk_history_blend(yk_context* ctx, const yk_temporal_desc* desc, const float* film_rgb, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const uint32_t* samples,
