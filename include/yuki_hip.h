@@ -847,6 +847,61 @@ yk_status yk_history_reproject_moved_device(yk_context* ctx, const yk_temporal_d
                                             const void* d_prev_guides, const yk_camera* prev_camera, const void* d_guides,
                                             const void* d_motion, uint16_t res_x, uint16_t res_y, void* d_out_history, void* stream);
 
+/* ---- albedo: textures under the denoiser — first-hit albedo from surface ids, and the a-trous filter on radiance / albedo ----
+ * yk_denoise filters radiance, so on a textured surface it either blurs the texture (an open colour stop) or keeps the
+ * noise (a closed one).  Two passes, the library's own; the rule is stated next to each expression in
+ * yuki_amd/csrc/yk_albedo.h, and the host and the device instance agree bit for bit (binary32, every operation separate, no
+ * FMA, divisions correctly rounded, a NaN an operation produces is 0x7fc00000, a value that is only copied keeps its bits).
+ * Intended use: yk_render_guides_ids -> yk_surface_albedo -> yk_denoise_albedo where yk_denoise stood; the ids and the
+ * albedo depend on the camera and the scene only, as the guides do.  After a temporal blend the blended RGB goes in with
+ * samples = NULL as it goes into yk_denoise: the history stays in radiance.
+ * Albedo, per pixel, the cases in this order:
+ *   1. ids.shape == YK_SURFACE_NONE: (1, 1, 1, 0).
+ *   2. shape >= n_triangles + n_spheres: (1, 1, 1, 0); the index is never followed.
+ *   3. The material is tri_material[shape] for a triangle, spheres[shape - n_triangles].material for a sphere.  An index
+ *      outside materials[]: (1, 1, 1, 0), never followed.  Not YK_MAT_MATTE (glass, metal, glossy): (1, 1, 1, 0).
+ *   4. An untextured matte: (Kd as bits, 1).
+ *   5. A textured matte on a triangle: uv = (uv0*b0 + uv1*b1) + uv2*b2 per component, products first, summed left to
+ *      right; uv0..2 the mesh's uvs at the triangle's indices, or (0,0), (1,0), (1,1) where the mesh has none.  The record
+ *      is (the texel ImageTexture::evaluate reads there, as bits, 1).
+ *   6. A textured matte on a sphere: (1, 1, 1, 0).
+ * Demodulated denoise: yk_denoise's rule with
+ *   the divisor d per pixel and channel: a where a is finite and a >= YK_ALBEDO_FLOOR; 1 where a is NaN or infinite;
+ *     YK_ALBEDO_FLOOR otherwise.  `known` is not read: the records of cases 1-3 and 6 are all ones;
+ *   in: after the normalisation by the sample table every channel is divided by d, once per pixel; the iterations run on
+ *     these colours, so sigma_color acts on demodulated radiance;
+ *   out: the last iteration's sum(w * c_Q) / sum(w) is multiplied by the pixel's own d;
+ *   iterations = 0: the normalised film, copied as bits: no division, no product.
+ * Not handled: texels smaller than a pixel (the albedo is that of ONE ray through the pixel centre, not the mean over the
+ *   pixel's samples: there the quotient is noisier than the film and plain yk_denoise is the better choice), glass, metal and
+ *   glossy surfaces, textured spheres, yk_multi scenes. */
+#define YK_ALBEDO_FLOOR 0.015625f /* 2^-6, exact */
+typedef struct yk_albedo {
+    float a[3];  /* the first hit's diffuse albedo; (1, 1, 1) where it is not known */
+    float known; /* 1.0f, or 0.0f: nothing to demodulate by */
+} yk_albedo;     /* 16 bytes; 16-byte aligned on the device */
+/* Host buffers: res_x * res_y records each, row-major.  ctx NULL = the host instance on the CPU, else on ctx's device
+ * (synchronous).  The host instance reads the scene's indices, uvs, materials and texels on the host: a host-only scene keeps
+ * them; for a scene in device memory they are copied back from its device with every call.
+ * YK_ERR_INVALID_ARGUMENT: a NULL pointer, a zero resolution, an output that overlaps the ids, with a context a scene of
+ * another device. */
+yk_status yk_surface_albedo(yk_context* ctx, const yk_scene* scene, const yk_surface_id* ids, uint16_t res_x, uint16_t res_y,
+                            yk_albedo* out);
+/* The same on device buffers (both 16-byte aligned, not overlapping; anything else: YK_ERR_INVALID_ARGUMENT, nothing is
+ * launched), enqueued on `stream` (NULL = the context's) without waiting for the device: one launch, no allocation. */
+yk_status yk_surface_albedo_device(yk_context* ctx, const yk_scene* scene, const void* d_ids, uint16_t res_x, uint16_t res_y,
+                                   void* d_out, void* stream);
+/* yk_denoise with the albedo records; arguments and errors as yk_denoise, plus: a NULL albedo, an albedo that overlaps the
+ * output. */
+yk_status yk_denoise_albedo(yk_context* ctx, const yk_denoise_desc* desc, const float* film_rgb, const yk_guide* guides,
+                            const yk_albedo* albedo, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const uint32_t* samples,
+                            float* out_rgb);
+/* The same on device buffers, as yk_denoise_device (d_albedo 16-byte aligned too): a preparing launch, then one launch per
+ * iteration; both ping-pong buffers of the context are used from two iterations on. */
+yk_status yk_denoise_albedo_device(yk_context* ctx, const yk_denoise_desc* desc, const void* d_film_rgb, const void* d_guides,
+                                   const void* d_albedo, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const uint32_t* samples,
+                                   void* d_out_rgb, void* stream);
+
 /* ---- per-stage entry points (parity tests, profiling) ------------------------- */
 /* BoundingVolumeHierarchy::intersect (bvh.rs:160-232) for n host rays.
  * out_shape: source shape index or -1; counters as IntersectionResult. */

@@ -266,6 +266,34 @@ inline void write_png(const std::string& path, uint32_t width, uint32_t height, 
     check(yk_write_png(path.c_str(), width, height, channels, pixels));
 }
 
+// Textures under the denoiser (the library's own passes; the rule is stated in yuki_hip.h and csrc/yk_albedo.h).
+using Albedo = yk_albedo;
+// The first-hit albedo of every pixel from yk_render_guides_ids' ids (res_x * res_y records, row-major).  ctx == nullptr: the
+// host instance.
+inline std::vector<Albedo> surface_albedo(Context* ctx, const Scene& scene, const yk_surface_id* ids, uint16_t res_x, uint16_t res_y) {
+    std::vector<Albedo> out((size_t)res_x * res_y);
+    yk_context* c = ctx ? ctx->handle() : nullptr;
+    check(yk_surface_albedo(c, scene.handle(), ids, res_x, res_y, out.data()), c);
+    return out;
+}
+// The same on device buffers, enqueued on `stream` (nullptr: the context's): one kernel, no allocation, no synchronisation.
+inline void surface_albedo_device(Context& ctx, const Scene& scene, const void* d_ids, uint16_t res_x, uint16_t res_y, void* d_out, void* stream = nullptr) {
+    check(yk_surface_albedo_device(ctx.handle(), scene.handle(), d_ids, res_x, res_y, d_out, stream), ctx.handle());
+}
+// yk_denoise on radiance / albedo: the film (row-major RGB; `samples` = Film.samples or nullptr) -> the denoised film.
+inline std::vector<float> denoise_albedo(Context* ctx, const yk_denoise_desc& desc, const float* film, const yk_guide* guides, const Albedo* albedo, uint16_t res_x,
+                                         uint16_t res_y, uint16_t tile_dim, const uint32_t* samples = nullptr) {
+    std::vector<float> out((size_t)res_x * res_y * 3);
+    yk_context* c = ctx ? ctx->handle() : nullptr;
+    check(yk_denoise_albedo(c, &desc, film, guides, albedo, res_x, res_y, tile_dim, samples, out.data()), c);
+    return out;
+}
+// The same on device buffers (d_out may be d_film), enqueued on `stream`: a preparing launch and one launch per iteration.
+inline void denoise_albedo_device(Context& ctx, const yk_denoise_desc& desc, const void* d_film, const void* d_guides, const void* d_albedo, uint16_t res_x,
+                                  uint16_t res_y, uint16_t tile_dim, const uint32_t* samples, void* d_out, void* stream = nullptr) {
+    check(yk_denoise_albedo_device(ctx.handle(), &desc, d_film, d_guides, d_albedo, res_x, res_y, tile_dim, samples, d_out, stream), ctx.handle());
+}
+
 // trait Integrator, integrators/mod.rs:92-186
 class Integrator {
    public:

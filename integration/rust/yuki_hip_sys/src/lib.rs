@@ -253,6 +253,18 @@ pub struct yk_motion {
     pub known: f32,
 }
 
+/// The floor under the divisor of `yk_denoise_albedo`, 2^-6
+pub const YK_ALBEDO_FLOOR: f32 = 0.015625;
+
+/// The diffuse albedo of a pixel's first hit; known = 0: nothing to demodulate by (then a is all ones); 16-byte aligned on
+/// the device (yuki_amd/csrc/yk_albedo.h)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct yk_albedo {
+    pub a: [f32; 3],
+    pub known: f32,
+}
+
 /// The target rectangle of ScaleOutput::draw in top-down window coordinates
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -483,6 +495,10 @@ extern "C" {
     pub fn yk_surface_motion_device(ctx: *mut yk_context, scene: *const yk_scene, d_ids: *const c_void, d_guides: *const c_void, d_prev_points: *const f32, res_x: u16, res_y: u16, d_out: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_history_reproject_moved(ctx: *mut yk_context, desc: *const yk_temporal_desc, prev_history: *const yk_history, prev_guides: *const yk_guide, prev_camera: *const yk_camera, guides: *const yk_guide, motion: *const yk_motion, res_x: u16, res_y: u16, out_history: *mut yk_history) -> yk_status;
     pub fn yk_history_reproject_moved_device(ctx: *mut yk_context, desc: *const yk_temporal_desc, d_prev_history: *const c_void, d_prev_guides: *const c_void, prev_camera: *const yk_camera, d_guides: *const c_void, d_motion: *const c_void, res_x: u16, res_y: u16, d_out_history: *mut c_void, stream: *mut c_void) -> yk_status;
+    pub fn yk_surface_albedo(ctx: *mut yk_context, scene: *const yk_scene, ids: *const yk_surface_id, res_x: u16, res_y: u16, out: *mut yk_albedo) -> yk_status;
+    pub fn yk_surface_albedo_device(ctx: *mut yk_context, scene: *const yk_scene, d_ids: *const c_void, res_x: u16, res_y: u16, d_out: *mut c_void, stream: *mut c_void) -> yk_status;
+    pub fn yk_denoise_albedo(ctx: *mut yk_context, desc: *const yk_denoise_desc, film_rgb: *const f32, guides: *const yk_guide, albedo: *const yk_albedo, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, out_rgb: *mut f32) -> yk_status;
+    pub fn yk_denoise_albedo_device(ctx: *mut yk_context, desc: *const yk_denoise_desc, d_film_rgb: *const c_void, d_guides: *const c_void, d_albedo: *const c_void, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, d_out_rgb: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_write_png(path: *const c_char, width: u32, height: u32, channels: u32, pixels: *const u8) -> yk_status;
     pub fn yk_render_tile(ctx: *mut yk_context, scene: *const yk_scene, camera: *const yk_camera, sampler: *const yk_sampler_desc, integrator: *const yk_integrator_desc, tile: *const yk_tile, tile_pixels: *mut f32, out_rays: *mut u64) -> yk_status;
     pub fn yk_film_update_tiles_device(ctx: *mut yk_context, tiles: *const yk_tile, n_tiles: usize, d_tile_rgb: *const c_void, res_x: u16, res_y: u16, d_film_rgb: *mut c_void, stream: *mut c_void) -> yk_status;

@@ -131,3 +131,66 @@ pub unsafe fn denoise_device(
         Err(status)
     }
 }
+
+/// Textures under the denoiser (yuki_amd/csrc/yk_albedo.h).  Where the worker renders its guides it renders the ids beside
+/// them (`yk_render_guides_ids_device`, motion.rs) and turns them into the diffuse albedo of every first hit: `d_albedo`
+/// is a device buffer of `res.x * res.y * 16` bytes, 16-byte aligned, made once per film size.  Like the guides it changes
+/// only with the camera or the scene.
+///
+/// # Safety
+/// `d_ids` and `d_albedo` are device allocations of `res.x * res.y * 16` bytes on `ctx`'s device, 16-byte aligned, not
+/// overlapping; `scene` was created on it.
+pub unsafe fn albedo_device(
+    ctx: *mut sys::yk_context,
+    scene: *const sys::yk_scene,
+    d_ids: *const c_void,
+    res: Vec2<u16>,
+    d_albedo: *mut c_void,
+    stream: *mut c_void,
+) -> Result<(), sys::yk_status> {
+    let status = sys::yk_surface_albedo_device(ctx, scene, d_ids, res.x, res.y, d_albedo, stream);
+    if status == sys::YK_OK {
+        Ok(())
+    } else {
+        Err(status)
+    }
+}
+
+/// `denoise_device` on radiance / albedo: the filter no longer has to choose between blurring a texture and keeping the
+/// noise on it.  Glass, metal, glossy surfaces and textured spheres are filtered as before (their albedo record is all
+/// ones); texels smaller than a pixel are better left to `denoise_device`.  After a temporal blend the blended RGB goes
+/// in with `samples = None`, as it goes into `denoise_device`.
+///
+/// # Safety
+/// As `denoise_device`; `d_albedo` is `albedo_device`'s buffer and does not overlap the output.
+pub unsafe fn denoise_albedo_device(
+    ctx: *mut sys::yk_context,
+    params: &DenoiseParams,
+    d_film: *const c_void,
+    d_guides: *const c_void,
+    d_albedo: *const c_void,
+    res: Vec2<u16>,
+    tile_dim: u16,
+    samples: Option<&[u32]>,
+    d_clean: *mut c_void,
+    stream: *mut c_void,
+) -> Result<(), sys::yk_status> {
+    let status = sys::yk_denoise_albedo_device(
+        ctx,
+        &params.desc(),
+        d_film,
+        d_guides,
+        d_albedo,
+        res.x,
+        res.y,
+        tile_dim,
+        samples.map_or(std::ptr::null(), |s| s.as_ptr()),
+        d_clean,
+        stream,
+    );
+    if status == sys::YK_OK {
+        Ok(())
+    } else {
+        Err(status)
+    }
+}

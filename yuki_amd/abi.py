@@ -214,6 +214,8 @@ HISTORY_DTYPE = np.dtype([("rgb", "<f4", 3), ("n", "<f4")])  # yk_history, 16 by
 SURFACE_NONE = 0xFFFFFFFF  # YK_SURFACE_NONE
 SURFACE_ID_DTYPE = np.dtype([("shape", "<u4"), ("b", "<f4", 3)])  # yk_surface_id, 16 bytes
 MOTION_DTYPE = np.dtype([("p_prev", "<f4", 3), ("known", "<f4")])  # yk_motion, 16 bytes
+ALBEDO_DTYPE = np.dtype([("a", "<f4", 3), ("known", "<f4")])  # yk_albedo, 16 bytes
+ALBEDO_FLOOR = 0.015625  # YK_ALBEDO_FLOOR, 2^-6
 
 # enums (include/yuki_hip.h)
 SPLIT_SAH, SPLIT_MIDDLE, SPLIT_EQUAL_COUNTS = 0, 1, 2

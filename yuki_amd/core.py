@@ -253,10 +253,11 @@ def render_guides(ctx, scene, camera, film_settings):
     return out
 
 
-def denoise(film, guides, params, tile_dim=16, samples=None, ctx=None):
+def denoise(film, guides, params, tile_dim=16, samples=None, ctx=None, albedo=None):
     """yk_denoise: the edge-avoiding à-trous filter of csrc/yk_denoise.h over an (h, w, 3) float32 film under (h, w)
     guides; `samples` = Film.samples (film_samples) for an accumulating film, whose sums are normalised first.  Returns the
-    new film; ctx None = the host instance."""
+    new film; ctx None = the host instance.  albedo (surface_albedo's (h, w) records): yk_denoise_albedo, the same filter
+    on radiance / albedo (csrc/yk_albedo.h)."""
     film = np.ascontiguousarray(film, dtype=np.float32)
     if film.ndim != 3 or film.shape[2] != 3:
         raise ValueError("film is (h, w, 3)")
@@ -264,6 +265,10 @@ def denoise(film, guides, params, tile_dim=16, samples=None, ctx=None):
     d, guides, samples = _denoise_args((w, h), params, guides, tile_dim, samples)
     out = np.empty_like(film)
     c = ctx.h if ctx else None
+    if albedo is not None:
+        albedo = _records(albedo, abi.ALBEDO_DTYPE, (w, h), "albedo")
+        check(lib().yk_denoise_albedo(c, C.byref(d), _p(film), _p(guides), _p(albedo), w, h, int(tile_dim), _p(samples), _p(out)), c)
+        return out
     check(lib().yk_denoise(c, C.byref(d), _p(film), _p(guides), w, h, int(tile_dim), _p(samples), _p(out)), c)
     return out
 
@@ -362,6 +367,20 @@ def surface_motion(scene, ids, guides, prev_points, ctx=None):
     return out
 
 
+def surface_albedo(scene, ids, ctx=None):
+    """yk_surface_albedo: the diffuse albedo of every pixel's first hit from render_guides_ids' (h, w) `ids` -> (h, w)
+    abi.ALBEDO_DTYPE records (a, known): Kd or the texel of a matte surface, (1, 1, 1, 0) for everything denoise(albedo=...)
+    is not to demodulate (csrc/yk_albedo.h).  ctx None = the host instance."""
+    ids = np.ascontiguousarray(ids, dtype=abi.SURFACE_ID_DTYPE)
+    if ids.ndim != 2:
+        raise ValueError("ids is (h, w)")
+    h, w = ids.shape
+    out = np.zeros((h, w), dtype=abi.ALBEDO_DTYPE)
+    c = ctx.h if ctx else None
+    check(lib().yk_surface_albedo(c, scene.h, _p(ids), w, h, _p(out)), c)
+    return out
+
+
 def reproject_history_moved(history, prev_guides, prev_camera, guides, motion, params, ctx=None):
     """yk_history_reproject_moved: reproject_history after the geometry moved: every pixel is carried from where its
     surface point stood (`motion`, surface_motion's records) instead of from where it stands.  ctx None = the host
@@ -407,24 +426,27 @@ def blend_history(film, params, tile_dim=16, samples=None, history=None, ctx=Non
     return rgb, out
 
 
-def _denoise_for_output(film, denoise_params, guides, tile_dim, samples, ctx):
+def _denoise_for_output(film, denoise_params, guides, tile_dim, samples, ctx, albedo=None):
     """The denoise step of write_output / write_preview: (film, samples) for the tone map that follows — the denoised film
     is normalised already, so it goes on without the sample table."""
     if denoise_params is None:
+        if albedo is not None:
+            raise ValueError("albedo needs denoise (a DenoiseParams) and guides")
         return film, samples
     if guides is None:
         raise ValueError("denoise needs guides (render_guides)")
-    return denoise(film, guides, denoise_params, tile_dim, samples, ctx), None
+    return denoise(film, guides, denoise_params, tile_dim, samples, ctx, albedo), None
 
 
-def write_output(path, film, tone_map=None, settings=None, samples=None, ctx=None, denoise=None, guides=None):
+def write_output(path, film, tone_map=None, settings=None, samples=None, ctx=None, denoise=None, guides=None, albedo=None):
     """The Finished branch of app/headless.rs:62-84: Raw writes the film as it is, anything else writes the tone-mapped
     film (a Heatmap without bounds finds them first).  tone_map None = ToneMapType.default(); settings None = a film of the
-    array's size with the default tile_dim.  denoise (a DenoiseParams) with guides: the film is denoised first."""
+    array's size with the default tile_dim.  denoise (a DenoiseParams) with guides: the film is denoised first; with albedo
+    (surface_albedo's records) too: by the demodulated filter."""
     film = np.ascontiguousarray(film, dtype=np.float32)
     tone_map = ToneMapType.default() if tone_map is None else tone_map
     settings = settings or FilmSettings(res=(film.shape[1], film.shape[0]))
-    film, samples = _denoise_for_output(film, denoise, guides, film_tile_dim(settings), samples, ctx)
+    film, samples = _denoise_for_output(film, denoise, guides, film_tile_dim(settings), samples, ctx, albedo)
     if tone_map.kind == abi.TONE_MAP_RAW:
         write_exr(path, film)
         return
@@ -534,14 +556,15 @@ def write_png(path, pixels):
     check(lib().yk_write_png(str(path).encode(), pixels.shape[1], pixels.shape[0], pixels.shape[2], _p(pixels)))
 
 
-def write_preview(path, film, tone_map=None, settings=None, samples=None, window=None, ctx=None, denoise=None, guides=None):
-    """What the window shows, as a PNG: the denoiser when `denoise` (a DenoiseParams) and `guides` are given, the tone map
+def write_preview(path, film, tone_map=None, settings=None, samples=None, window=None, ctx=None, denoise=None, guides=None, albedo=None):
+    """What the window shows, as a PNG: the denoiser when `denoise` (a DenoiseParams) and `guides` are given (demodulated
+    by `albedo`, surface_albedo's records, when that is given too), the tone map
     (as write_output: None = ToneMapType.default(), Raw = none), then present into `window` (default: the film's size) as
     an sRGB back buffer stores it (encode 2), then write_png."""
     film = np.ascontiguousarray(film, dtype=np.float32)
     tone_map = ToneMapType.default() if tone_map is None else tone_map
     settings = settings or FilmSettings(res=(film.shape[1], film.shape[0]))
-    film, samples = _denoise_for_output(film, denoise, guides, film_tile_dim(settings), samples, ctx)
+    film, samples = _denoise_for_output(film, denoise, guides, film_tile_dim(settings), samples, ctx, albedo)
     if tone_map.kind != abi.TONE_MAP_RAW:
         film = _apply_tone_map(film, tone_map, film_tile_dim(settings), samples, ctx, None)
     window = (film.shape[1], film.shape[0]) if window is None else window
@@ -707,10 +730,13 @@ class Context:
         ordered on `stream` (default: the context's) without waiting on the host."""
         check(lib().yk_render_guides_device(self.h, scene.h, C.byref(camera.matrices), int(res[0]), int(res[1]), C.c_void_p(d_guides_ptr), C.c_void_p(stream) if stream else None), self.h)
 
-    def denoise_device(self, d_film_ptr, d_guides_ptr, res, params, tile_dim, samples, d_out_ptr, stream=None):
+    def denoise_device(self, d_film_ptr, d_guides_ptr, res, params, tile_dim, samples, d_out_ptr, stream=None, albedo=None):
         """yk_denoise_device: device film + device guides -> device out (may be the film), enqueued on `stream` (default:
         the context's) without waiting; `samples` is a host table (or None), copied before the call returns."""
         d, _, samples = _denoise_args(res, params, None, tile_dim, samples)
+        if albedo is not None:  # the device pointer of surface_albedo_device's records: yk_denoise_albedo_device
+            check(lib().yk_denoise_albedo_device(self.h, C.byref(d), C.c_void_p(d_film_ptr), C.c_void_p(d_guides_ptr), C.c_void_p(albedo), int(res[0]), int(res[1]), int(tile_dim), _p(samples), C.c_void_p(d_out_ptr), C.c_void_p(stream) if stream else None), self.h)
+            return
         check(lib().yk_denoise_device(self.h, C.byref(d), C.c_void_p(d_film_ptr), C.c_void_p(d_guides_ptr), int(res[0]), int(res[1]), int(tile_dim), _p(samples), C.c_void_p(d_out_ptr), C.c_void_p(stream) if stream else None), self.h)
 
     def reproject_history_device(self, d_prev_history_ptr, d_prev_guides_ptr, prev_camera, d_guides_ptr, res, params, d_out_history_ptr, stream=None):
@@ -733,6 +759,12 @@ class Context:
         records, enqueued on `stream` (default: the context's) without waiting; one launch, no allocation."""
         vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
         check(lib().yk_surface_motion_device(self.h, scene.h, vp(d_ids_ptr), vp(d_guides_ptr), vp(d_prev_points_ptr), int(res[0]), int(res[1]), vp(d_out_ptr), vp(stream)), self.h)
+
+    def surface_albedo_device(self, scene, d_ids_ptr, res, d_out_ptr, stream=None):
+        """yk_surface_albedo_device: device ids -> res[0] * res[1] device yk_albedo records (both 16-byte aligned), enqueued
+        on `stream` (default: the context's) without waiting."""
+        vp = C.c_void_p
+        check(lib().yk_surface_albedo_device(self.h, scene.h, vp(d_ids_ptr), int(res[0]), int(res[1]), vp(d_out_ptr), vp(stream)), self.h)
 
     def reproject_history_moved_device(self, d_prev_history_ptr, d_prev_guides_ptr, prev_camera, d_guides_ptr, d_motion_ptr, res, params, d_out_history_ptr, stream=None):
         """yk_history_reproject_moved_device: reproject_history_device through the device motion records of

@@ -1,0 +1,166 @@
+// yk_albedo.hip — first-hit albedo on gfx950, behind yk_surface_albedo[_device]; the per-pixel rule is yk_albedo.h's, whose
+// host instance these entry points run without a context.  (The demodulated denoise that reads the records is in
+// yk_denoise.hip, next to the filter it wraps.)
+//
+// k_albedo: one lane per pixel, a block is an AL_TX x AL_TY tile of the film (k_motion's launch shape: neighbouring lanes
+//   hit neighbouring triangles and, on a textured surface, neighbouring texels, so their requests share cache lines).  A
+//   lane reads its id (one 16-byte load) and follows a four-hop gather: the shape's material index, mesh and three vertex
+//   indices; the material (five dwords of its 44-byte record), the mesh flags and six uv floats; the texture's info (one
+//   16-byte load); the texel (one 16-byte load); and writes one 16-byte record.  Every index is clamped into its array and
+//   no load stands under a per-lane branch: a lane whose case needs no texture asks for texture 0 and drops the answer.
+//   No LDS: which records a tile touches is not known before the ids are read.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <vector>
+
+#include "yk_albedo.h"
+#include "yk_internal.h"
+
+namespace {
+
+constexpr unsigned AL_TX = 32, AL_TY = 8;  // 256 lanes: 4 waves of 64
+
+__global__ __launch_bounds__(AL_TX* AL_TY) void k_albedo(const uint4* __restrict__ ids, DevScene sc, AlParams a, float4* __restrict__ out) {
+    const uint32_t x = blockIdx.x * AL_TX + threadIdx.x, y = blockIdx.y * AL_TY + threadIdx.y;
+    if (x >= a.res_x || y >= a.res_y) return;
+    const size_t i = (size_t)y * a.res_x + x;
+    const uint4 id = ids[i];
+    float rec[4];
+    al_pixel(a, sc, id.x, __uint_as_float(id.y), __uint_as_float(id.z), __uint_as_float(id.w), rec);
+    out[i] = make_float4(rec[0], rec[1], rec[2], rec[3]);
+}
+
+bool overlaps(const void* p, size_t np, const void* q, size_t nq) {
+    const uintptr_t p0 = (uintptr_t)p, q0 = (uintptr_t)q;
+    return p0 < q0 + nq && q0 < p0 + np;
+}
+
+yk_status check_call(const yk_scene* scene, const void* ids, uint16_t res_x, uint16_t res_y, const void* out) {
+    if (!scene || !ids || !out || res_x == 0 || res_y == 0) return YK_ERR_INVALID_ARGUMENT;
+    const size_t n_px = (size_t)res_x * res_y;
+    if (overlaps(out, n_px * sizeof(yk_albedo), ids, n_px * sizeof(yk_surface_id))) return YK_ERR_INVALID_ARGUMENT;
+    return YK_OK;
+}
+
+AlParams make_params(const yk_scene* scene, uint16_t res_x, uint16_t res_y) {
+    AlParams a{};
+    a.res_x = res_x;
+    a.res_y = res_y;
+    a.n_triangles = scene->n_triangles;
+    a.n_shapes = scene->n_triangles + scene->n_spheres;
+    a.n_vertices = scene->upd.n_vertices;
+    a.n_meshes = scene->n_meshes;
+    a.n_materials = scene->n_materials;
+    a.n_textures = scene->n_textures;
+    a.has_uvs = scene->upd.has_uvs ? 1u : 0u;
+    return a;
+}
+
+yk_status enqueue(yk_context* ctx, hipStream_t st, const yk_scene* scene, const void* ids, uint16_t res_x, uint16_t res_y, void* out) {
+    const AlParams a = make_params(scene, res_x, res_y);
+    const dim3 grid((res_x + AL_TX - 1) / AL_TX, (res_y + AL_TY - 1) / AL_TY), block(AL_TX, AL_TY);
+    hipLaunchKernelGGL(k_albedo, grid, block, 0, st, reinterpret_cast<const uint4*>(ids), scene->dev, a, reinterpret_cast<float4*>(out));
+    HIP_TRY(ctx, hipGetLastError());
+    return YK_OK;
+}
+
+// The arrays al_pixel reads, as host arrays behind a DevScene.
+DevScene host_view(const yk_scene::ShadingTables& h, const uint32_t* indices) {
+    DevScene sc{};
+    sc.indices = indices;
+    sc.uvs = h.uvs.data();
+    sc.tri_mesh = h.tri_mesh.data();
+    sc.tri_material = h.tri_material.data();
+    sc.mesh_flags = h.mesh_flags.data();
+    sc.materials = h.materials.data();
+    sc.spheres = h.spheres.data();
+    sc.texels = h.texels.data();
+    sc.tex_info = h.tex_info.data();
+    return sc;
+}
+
+// A scene in device memory: the same arrays copied back from its device.
+hipError_t fetch_tables(const yk_scene* s, yk_scene::ShadingTables& h) {
+    const size_t nt = s->n_triangles;
+    h.indices.resize(3 * nt);
+    h.tri_mesh.resize(nt);
+    h.tri_material.resize(nt);
+    h.mesh_flags.resize(std::max<uint32_t>(s->n_meshes, 1));
+    h.materials.resize(std::max<uint32_t>(s->n_materials, 1));
+    h.spheres.resize(std::max<uint32_t>(s->n_spheres, 1));
+    h.uvs.resize(s->upd.has_uvs ? 2 * (size_t)s->upd.n_vertices : 0);
+    h.tex_info.resize(s->n_textures);
+    const auto get = [](auto& v, const DevBuf& b) -> hipError_t {
+        const size_t bytes = v.size() * sizeof(v[0]);
+        if (bytes == 0) return hipSuccess;
+        if (!b.p || b.bytes < bytes) return hipErrorInvalidValue;
+        return hipMemcpy(v.data(), b.p, bytes, hipMemcpyDeviceToHost);
+    };
+    hipError_t e;
+    if ((e = get(h.indices, s->indices)) != hipSuccess || (e = get(h.tri_mesh, s->tri_mesh)) != hipSuccess || (e = get(h.tri_material, s->tri_material)) != hipSuccess ||
+        (e = get(h.mesh_flags, s->mesh_flags)) != hipSuccess || (e = get(h.materials, s->materials)) != hipSuccess || (e = get(h.spheres, s->spheres)) != hipSuccess ||
+        (e = get(h.uvs, s->uvs)) != hipSuccess || (e = get(h.tex_info, s->tex_info)) != hipSuccess)
+        return e;
+    size_t n_texels = 0;
+    for (const uint4& t : h.tex_info) n_texels = std::max(n_texels, (size_t)t.x + (size_t)t.y * t.z);
+    h.texels.resize(n_texels);
+    return get(h.texels, s->texels);
+}
+
+void albedo_host(const yk_scene* scene, const DevScene& sc, const yk_surface_id* ids, uint16_t res_x, uint16_t res_y, yk_albedo* out) {
+    const AlParams a = make_params(scene, res_x, res_y);
+    const size_t n_px = (size_t)res_x * res_y;
+    for (size_t i = 0; i < n_px; ++i) {
+        float rec[4];
+        al_pixel(a, sc, ids[i].shape, ids[i].b[0], ids[i].b[1], ids[i].b[2], rec);
+        std::memcpy(&out[i], rec, 16);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+yk_status yk_surface_albedo(yk_context* ctx, const yk_scene* scene, const yk_surface_id* ids, uint16_t res_x, uint16_t res_y, yk_albedo* out) try {
+    if (check_call(scene, ids, res_x, res_y, out) != YK_OK) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_surface_albedo: bad argument");
+    const size_t n_px = (size_t)res_x * res_y;
+    if (!ctx) {  // the host instance
+        if (!scene->on_device) {  // a host-only scene keeps its tables
+            albedo_host(scene, host_view(scene->host_shading, scene->upd.host_indices.data()), ids, res_x, res_y, out);
+            return YK_OK;
+        }
+        yk_scene::ShadingTables fetched;  // a scene in device memory: its tables live there
+        (void)hipSetDevice(scene->device);
+        HIP_TRY(ctx, fetch_tables(scene, fetched));
+        albedo_host(scene, host_view(fetched, fetched.indices.data()), ids, res_x, res_y, out);
+        return YK_OK;
+    }
+    YK_LOCK(ctx);
+    if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_surface_albedo: scene was not created on this context's device");
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    HIP_TRY(ctx, ctx->scratch[4].ensure(n_px * sizeof(yk_surface_id)));
+    HIP_TRY(ctx, ctx->scratch[7].ensure(n_px * sizeof(yk_albedo)));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[4].p, ids, n_px * sizeof(yk_surface_id), hipMemcpyHostToDevice, st));
+    yk_status s = enqueue(ctx, st, scene, ctx->scratch[4].p, res_x, res_y, ctx->scratch[7].p);
+    if (s != YK_OK) return s;
+    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->scratch[7].p, n_px * sizeof(yk_albedo), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return YK_OK;
+}
+YK_CATCH(ctx)
+
+yk_status yk_surface_albedo_device(yk_context* ctx, const yk_scene* scene, const void* d_ids, uint16_t res_x, uint16_t res_y, void* d_out, void* stream) {
+    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
+    YK_LOCK(ctx);
+    if (check_call(scene, d_ids, res_x, res_y, d_out) != YK_OK) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_surface_albedo_device: bad argument");
+    if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_surface_albedo_device: scene was not created on this context's device");
+    if (((uintptr_t)d_ids & 15u) || ((uintptr_t)d_out & 15u))  // 16-byte loads and stores of the records
+        return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_surface_albedo_device: ids and output must be 16-byte aligned");
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    return enqueue(ctx, st, scene, d_ids, res_x, res_y, d_out);
+}
+
+}  // extern "C"

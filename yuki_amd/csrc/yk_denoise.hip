@@ -10,6 +10,9 @@
 //   S == 1, 2: the block first stages the colours (normalised once per staged pixel) and guides of its tile plus a halo
 //     of 2*S pixels in LDS, and the taps are ds_read_b128s — for the steps whose halo is small against the tile.
 // "denoise_lds_max_step" picks the variant per step (the measurement that chose the default).
+// The demodulated denoise (yk_denoise_albedo[_device], yk_albedo.h) lives here as well: k_dn_demodulate
+// writes the normalised film divided by the albedo as colour records, every iteration then reads records, and the last one
+// is k_atrous_albedo, which multiplies the albedo back before it stores RGB.
 // Everything the pass needs on the device (ping-pong buffers, staged sample table) is grown in the context on first use;
 // after that the stream-ordered entry point does not allocate.
 #include <hip/hip_runtime.h>
@@ -17,6 +20,7 @@
 #include <cstring>
 #include <vector>
 
+#include "yk_albedo.h"
 #include "yk_denoise.h"
 #include "yk_internal.h"
 
@@ -112,6 +116,73 @@ __global__ __launch_bounds__(DN_TX* DN_TY) void k_atrous(DnIo io, DnParams a, fl
     }
 }
 
+// The last iteration of the demodulated denoise (yk_albedo.h): k_atrous<false, true, S> — colour records in, RGB out — whose
+// filtered colour is multiplied by the divisor of the pixel's own albedo record before it is stored (al_remodulate: one
+// extra 16-byte load a pixel).  A kernel of its own and not one more parameter of k_atrous: any change to that template,
+// a shared body included, moved instructions in the twelve instantiations yk_denoise runs.
+template <int S>
+__global__ __launch_bounds__(DN_TX* DN_TY) void k_atrous_albedo(DnIo io, DnParams a, float den_c, int step, const float4* __restrict__ albedo) {
+    const uint32_t x0 = blockIdx.x * DN_TX, y0 = blockIdx.y * DN_TY;
+    const uint32_t x = x0 + threadIdx.x, y = y0 + threadIdx.y;
+    const bool inside = x < a.res_x && y < a.res_y;
+    float rgb[3] = {0.0f, 0.0f, 0.0f};
+    if (S == 0) {
+        if (!inside) return;
+        dn_pixel(a, den_c, step, x, y,
+                 [&](uint32_t qx, uint32_t qy, DnTap& t) {
+                     dn_load_color<false>(a, io, qx, qy, t.c);
+                     const size_t i = (size_t)qy * a.res_x + qx;
+                     dn_set_guide(t, io.guides[2 * i], io.guides[2 * i + 1]);
+                 },
+                 rgb);
+    } else {
+        constexpr int H = 2 * S, W = (int)DN_TX + 2 * H, ROWS = (int)DN_TY + 2 * H;
+        __shared__ float4 lds_c[W * ROWS], lds_a[W * ROWS], lds_b[W * ROWS];
+        const int bx = (int)x0 - H, by = (int)y0 - H;
+        for (int k = (int)(threadIdx.y * DN_TX + threadIdx.x); k < W * ROWS; k += (int)(DN_TX * DN_TY)) {
+            const int gx = bx + k % W, gy = by + k / W;
+            if (gx < 0 || gy < 0 || gx >= (int)a.res_x || gy >= (int)a.res_y) continue;  // never read: taps outside the film are skipped
+            const size_t i = (size_t)gy * a.res_x + (size_t)gx;
+            lds_c[k] = io.in[i];
+            lds_a[k] = io.guides[2 * i];
+            lds_b[k] = io.guides[2 * i + 1];
+        }
+        __syncthreads();
+        if (!inside) return;
+        dn_pixel(a, den_c, S, x, y,
+                 [&](uint32_t qx, uint32_t qy, DnTap& t) {
+                     const int k = ((int)qy - by) * W + ((int)qx - bx);
+                     const float4 v = lds_c[k];
+                     t.c[0] = v.x;
+                     t.c[1] = v.y;
+                     t.c[2] = v.z;
+                     dn_set_guide(t, lds_a[k], lds_b[k]);
+                 },
+                 rgb);
+    }
+    const size_t i = (size_t)y * a.res_x + x;
+    const float4 al = albedo[i];
+    const float alb[3] = {al.x, al.y, al.z};
+    al_remodulate(alb, rgb);
+    io.out_rgb[3 * i] = rgb[0];
+    io.out_rgb[3 * i + 1] = rgb[1];
+    io.out_rgb[3 * i + 2] = rgb[2];
+}
+
+// The preparing pass of the demodulated denoise, a sibling of k_dn_normalise: the normalised film divided by the divisor
+// of every pixel's albedo (al_demodulate), as colour records.  Every iteration then reads records.
+__global__ __launch_bounds__(256) void k_dn_demodulate(DnIo io, DnParams a, const float4* __restrict__ albedo) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.res_x * a.res_y) return;
+    const uint32_t y = i / a.res_x, x = i - y * a.res_x;
+    const float4 al = albedo[i];
+    float c[3];
+    dn_load_color<true>(a, io, x, y, c);
+    const float alb[3] = {al.x, al.y, al.z};
+    al_demodulate(alb, c);
+    io.out[i] = make_float4(c[0], c[1], c[2], 0.0f);
+}
+
 // The normalised film as colour records (a one-iteration denoise in place) or as RGB (iterations == 0; out_rgb may be the
 // film: a lane reads its pixel before it writes it and touches no other).
 __global__ __launch_bounds__(256) void k_dn_normalise(DnIo io, DnParams a) {
@@ -168,9 +239,44 @@ size_t table_words(uint16_t res_x, uint16_t res_y, uint16_t tile_dim) {
     return (size_t)((res_x + tile_dim - 1) / tile_dim) * (size_t)((res_y + tile_dim - 1) / tile_dim);
 }
 
-// The device passes on `st`.
+// The demodulated denoise on `st` (iterations >= 1): the preparing pass into ping[0], then every iteration as plain
+// denoise's later ones, the last through k_atrous_albedo.
+yk_status enqueue_albedo(yk_context* ctx, hipStream_t st, const yk_denoise_desc* d, DnIo io, const DnParams& a, const float4* albedo, float* out) {
+    const uint32_t n_px = a.res_x * a.res_y;
+    auto& dn = ctx->denoise;
+    const uint32_t n_it = d->iterations;
+    HIP_TRY(ctx, dn.ping[0].ensure((size_t)n_px * 16));
+    if (n_it > 1) HIP_TRY(ctx, dn.ping[1].ensure((size_t)n_px * 16));
+    io.out = dn.ping[0].as<float4>();
+    hipLaunchKernelGGL(k_dn_demodulate, dim3((n_px - 1) / 256 + 1), dim3(256), 0, st, io, a, albedo);
+    int src = 0;
+    const dim3 grid((a.res_x + DN_TX - 1) / DN_TX, (a.res_y + DN_TY - 1) / DN_TY), block(DN_TX, DN_TY);
+    for (uint32_t i = 0; i < n_it; ++i) {
+        const int step = 1 << i;
+        const int variant = step <= (int)dn.lds_max_step ? step : 0;
+        const float den_c = dn_color_denominator(a.sigma_color, i);
+        const int dst = src == 0 ? 1 : 0;
+        io.in = dn.ping[src].as<const float4>();
+        if (i + 1 < n_it) {
+            io.out = dn.ping[dst].as<float4>();
+            io.out_rgb = nullptr;
+            launch_atrous<false, false>(st, variant, io, a, den_c, step);
+        } else {
+            io.out = nullptr;
+            io.out_rgb = out;
+            if (variant == 1) hipLaunchKernelGGL((k_atrous_albedo<1>), grid, block, 0, st, io, a, den_c, step, albedo);
+            else if (variant == 2) hipLaunchKernelGGL((k_atrous_albedo<2>), grid, block, 0, st, io, a, den_c, step, albedo);
+            else hipLaunchKernelGGL((k_atrous_albedo<0>), grid, block, 0, st, io, a, den_c, step, albedo);
+        }
+        src = dst;
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return YK_OK;
+}
+
+// The device passes on `st`; albedo NULL: the plain denoise.
 yk_status enqueue(yk_context* ctx, hipStream_t st, const yk_denoise_desc* d, const float* film, const void* guides, uint16_t res_x, uint16_t res_y, uint16_t tile_dim,
-                  const uint32_t* samples, float* out) {
+                  const uint32_t* samples, float* out, const void* albedo = nullptr) {
     const uint32_t n_px = (uint32_t)res_x * res_y;
     auto& dn = ctx->denoise;
     const DnParams a = make_params(d, res_x, res_y, tile_dim);
@@ -192,6 +298,7 @@ yk_status enqueue(yk_context* ctx, hipStream_t st, const yk_denoise_desc* d, con
         HIP_TRY(ctx, hipGetLastError());
         return YK_OK;
     }
+    if (albedo) return enqueue_albedo(ctx, st, d, io, a, reinterpret_cast<const float4*>(albedo), out);
     uint32_t n_it = d->iterations;
     const bool in_place_single = n_it == 1 && film == out;  // the one launch would read the film while it writes it
     if (n_it > 1 || in_place_single) {
@@ -226,16 +333,20 @@ yk_status enqueue(yk_context* ctx, hipStream_t st, const yk_denoise_desc* d, con
     return YK_OK;
 }
 
+// albedo NULL: the plain denoise; else the demodulated one (yk_albedo.h), which divides before the first iteration and
+// multiplies after the last — and does neither when there is no iteration.
 void denoise_host(const yk_denoise_desc* d, const float* film, const yk_guide* guides, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const uint32_t* samples,
-                  float* out) {
+                  float* out, const yk_albedo* albedo = nullptr) {
     const DnParams a = make_params(d, res_x, res_y, tile_dim);
     const size_t n_px = (size_t)res_x * res_y;
+    if (d->iterations == 0) albedo = nullptr;
     std::vector<float> cur(3 * n_px), nxt(d->iterations ? 3 * n_px : 0);
     for (uint32_t y = 0; y < res_y; ++y)
         for (uint32_t x = 0; x < res_x; ++x) {
             const size_t i = (size_t)y * res_x + x;
             std::memcpy(&cur[3 * i], film + 3 * i, 12);
             dn_normalise(dn_count(a, samples, x, y), &cur[3 * i]);
+            if (albedo) al_demodulate(albedo[i].a, &cur[3 * i]);
         }
     for (uint32_t it = 0; it < d->iterations; ++it) {
         const float den_c = dn_color_denominator(a.sigma_color, it);
@@ -250,7 +361,17 @@ void denoise_host(const yk_denoise_desc* d, const float* film, const yk_guide* g
             for (uint32_t x = 0; x < res_x; ++x) dn_pixel(a, den_c, 1 << it, x, y, fetch, &nxt[3 * ((size_t)y * res_x + x)]);
         cur.swap(nxt);
     }
+    if (albedo)
+        for (size_t i = 0; i < n_px; ++i) al_remodulate(albedo[i].a, &cur[3 * i]);
     std::memcpy(out, cur.data(), 12 * n_px);
+}
+
+// yk_denoise's refusals plus the albedo's: NULL, or overlapping the output
+yk_status check_call_albedo(const yk_denoise_desc* d, const void* film, const void* guides, const void* albedo, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const void* out) {
+    if (check_call(d, film, guides, res_x, res_y, tile_dim, out) != YK_OK || !albedo) return YK_ERR_INVALID_ARGUMENT;
+    const size_t n_px = (size_t)res_x * res_y;
+    if (overlaps(albedo, n_px * sizeof(yk_albedo), out, n_px * 12)) return YK_ERR_INVALID_ARGUMENT;
+    return YK_OK;
 }
 
 }  // namespace
@@ -291,6 +412,44 @@ yk_status yk_denoise_device(yk_context* ctx, const yk_denoise_desc* desc, const 
     (void)hipSetDevice(ctx->device);
     hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
     return enqueue(ctx, st, desc, reinterpret_cast<const float*>(d_film_rgb), d_guides, res_x, res_y, tile_dim, samples, reinterpret_cast<float*>(d_out_rgb));
+}
+
+yk_status yk_denoise_albedo(yk_context* ctx, const yk_denoise_desc* desc, const float* film_rgb, const yk_guide* guides, const yk_albedo* albedo, uint16_t res_x, uint16_t res_y,
+                            uint16_t tile_dim, const uint32_t* samples, float* out_rgb) try {
+    if (check_call_albedo(desc, film_rgb, guides, albedo, res_x, res_y, tile_dim, out_rgb) != YK_OK) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_denoise_albedo: bad argument");
+    if (!ctx) {  // the host instance
+        denoise_host(desc, film_rgb, guides, res_x, res_y, tile_dim, samples, out_rgb, albedo);
+        return YK_OK;
+    }
+    YK_LOCK(ctx);
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    const size_t n_px = (size_t)res_x * res_y;
+    HIP_TRY(ctx, ctx->scratch[4].ensure(n_px * 12));
+    HIP_TRY(ctx, ctx->scratch[5].ensure(n_px * 12));
+    HIP_TRY(ctx, ctx->scratch[6].ensure(n_px * sizeof(yk_guide)));
+    HIP_TRY(ctx, ctx->scratch[7].ensure(n_px * sizeof(yk_albedo)));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[4].p, film_rgb, n_px * 12, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[6].p, guides, n_px * sizeof(yk_guide), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch[7].p, albedo, n_px * sizeof(yk_albedo), hipMemcpyHostToDevice, st));
+    yk_status s = enqueue(ctx, st, desc, ctx->scratch[4].as<const float>(), ctx->scratch[6].p, res_x, res_y, tile_dim, samples, ctx->scratch[5].as<float>(), ctx->scratch[7].p);
+    if (s != YK_OK) return s;
+    HIP_TRY(ctx, hipMemcpyAsync(out_rgb, ctx->scratch[5].p, n_px * 12, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return YK_OK;
+} YK_CATCH(ctx)
+
+yk_status yk_denoise_albedo_device(yk_context* ctx, const yk_denoise_desc* desc, const void* d_film_rgb, const void* d_guides, const void* d_albedo, uint16_t res_x, uint16_t res_y,
+                                   uint16_t tile_dim, const uint32_t* samples, void* d_out_rgb, void* stream) {
+    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
+    YK_LOCK(ctx);
+    if (check_call_albedo(desc, d_film_rgb, d_guides, d_albedo, res_x, res_y, tile_dim, d_out_rgb) != YK_OK) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_denoise_albedo_device: bad argument");
+    // dword loads and stores of the film and the output, 16-byte loads of the guides and the albedo
+    if (((uintptr_t)d_film_rgb & 3u) || ((uintptr_t)d_out_rgb & 3u) || ((uintptr_t)d_guides & 15u) || ((uintptr_t)d_albedo & 15u))
+        return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_denoise_albedo_device: film and output must be 4-byte aligned, guides and albedo 16-byte aligned");
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    return enqueue(ctx, st, desc, reinterpret_cast<const float*>(d_film_rgb), d_guides, res_x, res_y, tile_dim, samples, reinterpret_cast<float*>(d_out_rgb), d_albedo);
 }
 
 }  // extern "C"

@@ -180,6 +180,7 @@ struct yk_scene {
     yk_scene_layout_info layout = {};
     size_t record_bytes[7] = {};  // exact sizes of the seven record buffers (YK_RECORDS_*; a DevBuf is never smaller than 16 bytes)
     uint32_t n_triangles = 0, n_spheres = 0, n_lights = 0, n_delta_lights = 0;
+    uint32_t n_materials = 0, n_meshes = 0, n_textures = 0;
     bool wide_auto = false;  // both node layouts on the device: the 4-wide one is used for jobs below YK_WIDE_MAX_PATHS
     yk_scene_info info;
     yk_bvh_build_info build_info;
@@ -213,6 +214,17 @@ struct yk_scene {
         std::vector<uint32_t> level_off;
         yk_scene_update_info info = {};
     } upd;
+    // What the host instance of yk_surface_albedo reads (yk_albedo.h).  A host-only scene keeps these; for a scene in device
+    // memory they are copied back from its device with every call.
+    struct ShadingTables {
+        std::vector<uint32_t> indices, tri_mesh, mesh_flags;
+        std::vector<int32_t> tri_material;
+        std::vector<float> uvs;
+        std::vector<Material> materials;
+        std::vector<DevSphere> spheres;
+        std::vector<float4> texels;
+        std::vector<uint4> tex_info;
+    } host_shading;
 };
 
 // The device scene a job of `n` rays traverses: with both node layouts present the 4-wide one

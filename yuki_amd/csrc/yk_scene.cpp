@@ -37,6 +37,9 @@ static void set_scene_counts(yk_scene* s, const yk_scene_desc* d) {
     s->n_triangles = d->n_triangles;
     s->n_spheres = d->n_spheres;
     s->n_lights = d->n_lights;
+    s->n_materials = d->n_materials;
+    s->n_meshes = d->n_meshes;
+    s->n_textures = d->n_textures;
     for (uint32_t l = 0; l < d->n_lights; ++l) s->n_delta_lights += d->lights[l].kind != YK_LIGHT_RECT ? 1u : 0u;
 }
 
@@ -546,6 +549,22 @@ yk_status yk_upload_scene_image(yk_context* ctx, const std::shared_ptr<SceneImag
     s->build_info = img->build_info;
     s->shape_kind = img->shape_kind;
     init_update_state(s, img->d, img->opt, img->mat_kind, ctx == nullptr);
+    if (!ctx) {  // a host-only scene keeps what the host instance of yk_surface_albedo reads (its indices: init_update_state)
+        const yk_scene_desc* d = img->d;
+        SceneImage tables;
+        yk_status st = small_tables(nullptr, d, &tables);
+        if (st != YK_OK) return st;
+        yk_scene::ShadingTables& h = s->host_shading;
+        h.mesh_flags.swap(tables.mesh_flags);
+        h.materials.swap(tables.mats);
+        h.spheres.swap(tables.spheres);
+        h.texels.swap(tables.texels);
+        h.tex_info.swap(tables.tex_info);
+        h.tri_mesh.assign(d->n_triangles, 0);
+        if (d->tri_mesh) std::memcpy(h.tri_mesh.data(), d->tri_mesh, sizeof(uint32_t) * d->n_triangles);
+        if (d->n_triangles) h.tri_material.assign(d->tri_material, d->tri_material + d->n_triangles);
+        if (d->uvs) h.uvs.assign(d->uvs, d->uvs + 2 * (size_t)d->n_vertices);
+    }
     if (ctx) {
         if (!img->has_device_records) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "scene image was built without device records");
         const yk_scene_desc* d = img->d;
