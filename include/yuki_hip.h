@@ -902,6 +902,83 @@ yk_status yk_denoise_albedo_device(yk_context* ctx, const yk_denoise_desc* desc,
                                    const void* d_albedo, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const uint32_t* samples,
                                    void* d_out_rgb, void* stream);
 
+/* ---- variance: carried luminance moments steer the a-trous filter ----
+ * yk_denoise's colour stop sigma_color / 2^i is one global constant: a film that yk_history_blend has carried for 32
+ * samples gets the blur of a film of 4.  Three passes, the library's own (after Schied et al., "Spatiotemporal
+ * Variance-Guided Filtering", HPG 2017); the rule is stated next to each expression in yuki_amd/csrc/yk_variance.h, and the
+ * host and the device instance agree bit for bit (binary32, every operation separate, no FMA, divisions correctly rounded,
+ * exp = the library's expf, a NaN an operation produces is 0x7fc00000, a value that is only copied keeps its bits).
+ * Intended use, per frame: every pass is rendered into a cleared film; yk_history_blend folds it into the colour history and
+ * yk_moments_blend folds the SAME film into the moments; when the camera or the geometry moves the moments buffer goes
+ * through yk_history_reproject[_moved] cast to yk_history (same layout, same taps, same weights, same skip set as the colour
+ * history); then yk_variance(moments, blended RGB, samples = NULL) -> yk_denoise_variance(blended RGB, variance) where
+ * yk_denoise stood.
+ * Luminance l(c) = (0.2126f*r + 0.7152f*g) + 0.0722f*b.
+ * Moments blend, per pixel: c and m as yk_history_blend reads them; l = l(c), ll = l*l; n = min(h.n, max_history).  The
+ *   moments are absent when the pointer is NULL, n is <= 0 or NaN, or a field is not finite; the current view when m == 0
+ *   or ll is not finite (a non-finite pixel never enters the moments).  Both absent: zeros.  Only the moments absent:
+ *   (l, ll, 1, m).  Only the current view absent: (h.m1, h.m2, h.frames * (n / h.n), n).  Neither: t = n + m — the count
+ *   yk_history_blend writes, bit for bit — m1 = (n*h.m1 + m*l) / t, m2 = (n*h.m2 + m*ll) / t,
+ *   frames = h.frames * (n / h.n) + 1.
+ * Variance, per pixel: where the moments are present and frames >= 2 the temporal estimate max(0, m2 - m1*m1) / (frames - 1)
+ *   (with an albedo divided by the square of the luminance of the pixel's own divisors: an approximation, exact for a grey
+ *   albedo); everywhere else spatial_scale times the weighted variance of l over the 7 x 7 window of the normalised (with an
+ *   albedo: demodulated) film, the weights being yk_denoise's normal and plane stops without a kernel and without a colour
+ *   stop; taps outside the film, of the other hit class, of weight 0 or NaN, or whose l*l is not finite are skipped, the
+ *   centre is always taken.  NaN or negative is written as 0; +inf stays and switches the colour stop off for that pixel.
+ * Filter: yk_denoise's rule (taps, kernel, normal and plane stops, skip rule, always-taken centre, iterations = 0, in-place
+ *   output, albedo as yk_denoise_albedo) with a_c = (dl*dl) / (sigma_variance^2 * g + epsilon), dl the luminance difference
+ *   of the two colours, g the 3 x 3 Gaussian (1/4, 1/8, 1/16) of the variance around P at unit spacing over the taps inside
+ *   the film whose variance is finite, renormalised (g = +inf where P's own variance is; sigma_variance = +inf: the stop is
+ *   off); no / 2^i.  The variance travels with the colours: var' = sum(w*w * var_Q) / (sum w)^2 over the taken taps whose
+ *   variance is finite; an infinite variance stays where it is and does not spread.
+ * Limits: variance of luminance only; yk_multi scenes are not served; the temporal estimate inherits the history's lag on
+ *   glass and metal. */
+typedef struct yk_moments {
+    float m1;     /* the mean luminance */
+    float m2;     /* the mean squared luminance of the frame means */
+    float frames; /* the effective number of frames behind them */
+    float n;      /* the effective number of samples, yk_history's n */
+} yk_moments;     /* 16 bytes, the layout of yk_history; 16-byte aligned on the device */
+typedef struct yk_variance_desc {
+    uint32_t iterations;                             /* 0 .. 8 */
+    float sigma_variance, sigma_normal, sigma_plane; /* each > 0; +inf switches its stop off */
+    float epsilon;                                   /* >= 0: added to the colour stop's denominator */
+    float spatial_scale;                             /* >= 0: the factor on the spatial estimate */
+} yk_variance_desc;
+/* film_rgb, `samples` and tile_dim as yk_history_blend takes them; `desc` may be the one given to yk_history_blend (only
+ * max_history is used, all of it is checked); moments may be NULL; out_moments may equal moments.
+ * YK_ERR_INVALID_ARGUMENT: a NULL desc, film or output, a zero resolution, tile_dim 0, a parameter out of range or NaN, an
+ * output that overlaps the film, or the moments without being equal to them. */
+yk_status yk_moments_blend(yk_context* ctx, const yk_temporal_desc* desc, const float* film_rgb, uint16_t res_x, uint16_t res_y,
+                           uint16_t tile_dim, const uint32_t* samples, const yk_moments* moments, yk_moments* out_moments);
+/* The same on device buffers, enqueued on `stream` (NULL = the context's) without waiting for the device: one launch.
+ * d_film_rgb needs 4-byte alignment, the moments 16-byte alignment (anything else: YK_ERR_INVALID_ARGUMENT, nothing is
+ * launched). */
+yk_status yk_moments_blend_device(yk_context* ctx, const yk_temporal_desc* desc, const void* d_film_rgb, uint16_t res_x, uint16_t res_y,
+                                  uint16_t tile_dim, const uint32_t* samples, const void* d_moments, void* d_out_moments, void* stream);
+/* moments and albedo may be NULL; out_variance holds res_x * res_y floats.  ctx NULL = the host instance.
+ * YK_ERR_INVALID_ARGUMENT: a NULL desc, film, guides or output, a zero resolution, tile_dim 0, iterations > 8, a sigma that
+ * is <= 0 or NaN, an epsilon or spatial_scale that is < 0 or NaN, an output that overlaps an input. */
+yk_status yk_variance(yk_context* ctx, const yk_variance_desc* desc, const yk_moments* moments, const float* film_rgb,
+                      const yk_guide* guides, const yk_albedo* albedo, uint16_t res_x, uint16_t res_y, uint16_t tile_dim,
+                      const uint32_t* samples, float* out_variance);
+/* The same on device buffers, one launch on `stream`: film and variance 4-byte aligned, moments, guides and albedo 16-byte
+ * aligned (anything else: YK_ERR_INVALID_ARGUMENT, nothing is launched). */
+yk_status yk_variance_device(yk_context* ctx, const yk_variance_desc* desc, const void* d_moments, const void* d_film_rgb,
+                             const void* d_guides, const void* d_albedo, uint16_t res_x, uint16_t res_y, uint16_t tile_dim,
+                             const uint32_t* samples, void* d_out_variance, void* stream);
+/* yk_denoise with the variance image; albedo may be NULL; out_rgb may equal film_rgb.  Errors as yk_denoise's, plus: a NULL
+ * variance, a variance or an albedo that overlaps the output, an epsilon that is < 0 or NaN. */
+yk_status yk_denoise_variance(yk_context* ctx, const yk_variance_desc* desc, const float* film_rgb, const yk_guide* guides,
+                              const float* variance, const yk_albedo* albedo, uint16_t res_x, uint16_t res_y, uint16_t tile_dim,
+                              const uint32_t* samples, float* out_rgb);
+/* The same on device buffers, as yk_denoise_albedo_device: a preparing launch, then one launch per iteration through the
+ * context's ping-pong buffers; film, variance and output 4-byte aligned, guides and albedo 16-byte aligned. */
+yk_status yk_denoise_variance_device(yk_context* ctx, const yk_variance_desc* desc, const void* d_film_rgb, const void* d_guides,
+                                     const void* d_variance, const void* d_albedo, uint16_t res_x, uint16_t res_y, uint16_t tile_dim,
+                                     const uint32_t* samples, void* d_out_rgb, void* stream);
+
 /* ---- per-stage entry points (parity tests, profiling) ------------------------- */
 /* BoundingVolumeHierarchy::intersect (bvh.rs:160-232) for n host rays.
  * out_shape: source shape index or -1; counters as IntersectionResult. */

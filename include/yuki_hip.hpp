@@ -294,6 +294,47 @@ inline void denoise_albedo_device(Context& ctx, const yk_denoise_desc& desc, con
     check(yk_denoise_albedo_device(ctx.handle(), &desc, d_film, d_guides, d_albedo, res_x, res_y, tile_dim, samples, d_out, stream), ctx.handle());
 }
 
+// Variance-guided denoise (the library's own passes; the rule is stated in yuki_hip.h and csrc/yk_variance.h).
+using Moments = yk_moments;
+// The film yk_history_blend folds into the history, folded into the moments (nullptr: none yet).  ctx == nullptr: the host
+// instance.  A moments buffer is reprojected by yk_history_reproject[_moved] cast to yk_history.
+inline std::vector<Moments> moments_blend(Context* ctx, const yk_temporal_desc& desc, const float* film, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const uint32_t* samples,
+                                          const Moments* moments) {
+    std::vector<Moments> out((size_t)res_x * res_y);
+    yk_context* c = ctx ? ctx->handle() : nullptr;
+    check(yk_moments_blend(c, &desc, film, res_x, res_y, tile_dim, samples, moments, out.data()), c);
+    return out;
+}
+inline void moments_blend_device(Context& ctx, const yk_temporal_desc& desc, const void* d_film, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const uint32_t* samples,
+                                 const void* d_moments, void* d_out_moments, void* stream = nullptr) {
+    check(yk_moments_blend_device(ctx.handle(), &desc, d_film, res_x, res_y, tile_dim, samples, d_moments, d_out_moments, stream), ctx.handle());
+}
+// The variance of the luminance of `film` as denoise_variance will filter it; moments and albedo may be nullptr.
+inline std::vector<float> variance(Context* ctx, const yk_variance_desc& desc, const Moments* moments, const float* film, const yk_guide* guides, const Albedo* albedo, uint16_t res_x,
+                                   uint16_t res_y, uint16_t tile_dim, const uint32_t* samples = nullptr) {
+    std::vector<float> out((size_t)res_x * res_y);
+    yk_context* c = ctx ? ctx->handle() : nullptr;
+    check(yk_variance(c, &desc, moments, film, guides, albedo, res_x, res_y, tile_dim, samples, out.data()), c);
+    return out;
+}
+inline void variance_device(Context& ctx, const yk_variance_desc& desc, const void* d_moments, const void* d_film, const void* d_guides, const void* d_albedo, uint16_t res_x,
+                            uint16_t res_y, uint16_t tile_dim, const uint32_t* samples, void* d_out_variance, void* stream = nullptr) {
+    check(yk_variance_device(ctx.handle(), &desc, d_moments, d_film, d_guides, d_albedo, res_x, res_y, tile_dim, samples, d_out_variance, stream), ctx.handle());
+}
+// yk_denoise with a colour stop that follows the variance image; albedo may be nullptr.
+inline std::vector<float> denoise_variance(Context* ctx, const yk_variance_desc& desc, const float* film, const yk_guide* guides, const float* variance, const Albedo* albedo,
+                                           uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const uint32_t* samples = nullptr) {
+    std::vector<float> out((size_t)res_x * res_y * 3);
+    yk_context* c = ctx ? ctx->handle() : nullptr;
+    check(yk_denoise_variance(c, &desc, film, guides, variance, albedo, res_x, res_y, tile_dim, samples, out.data()), c);
+    return out;
+}
+// The same on device buffers (d_out may be d_film), enqueued on `stream`: a preparing launch and one launch per iteration.
+inline void denoise_variance_device(Context& ctx, const yk_variance_desc& desc, const void* d_film, const void* d_guides, const void* d_variance, const void* d_albedo, uint16_t res_x,
+                                    uint16_t res_y, uint16_t tile_dim, const uint32_t* samples, void* d_out, void* stream = nullptr) {
+    check(yk_denoise_variance_device(ctx.handle(), &desc, d_film, d_guides, d_variance, d_albedo, res_x, res_y, tile_dim, samples, d_out, stream), ctx.handle());
+}
+
 // trait Integrator, integrators/mod.rs:92-186
 class Integrator {
    public:

@@ -233,6 +233,30 @@ pub struct yk_temporal_desc {
     pub max_history: f32,
 }
 
+/// A pixel's luminance moments beside its history: the layout of `yk_history`, so a moments buffer goes through
+/// `yk_history_reproject[_moved][_device]` cast to it (yuki_amd/csrc/yk_variance.h)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct yk_moments {
+    pub m1: f32,
+    pub m2: f32,
+    pub frames: f32,
+    pub n: f32,
+}
+
+/// The variance-guided a-trous filter: iterations 0..=8, the variance-scaled colour stop, the normal and plane stops (each
+/// > 0, +inf = off), epsilon under the colour stop and the factor on the spatial variance estimate (both >= 0)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct yk_variance_desc {
+    pub iterations: u32,
+    pub sigma_variance: f32,
+    pub sigma_normal: f32,
+    pub sigma_plane: f32,
+    pub epsilon: f32,
+    pub spatial_scale: f32,
+}
+
 /// `yk_surface_id::shape` on a miss
 pub const YK_SURFACE_NONE: u32 = 0xffff_ffff;
 
@@ -499,6 +523,12 @@ extern "C" {
     pub fn yk_surface_albedo_device(ctx: *mut yk_context, scene: *const yk_scene, d_ids: *const c_void, res_x: u16, res_y: u16, d_out: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_denoise_albedo(ctx: *mut yk_context, desc: *const yk_denoise_desc, film_rgb: *const f32, guides: *const yk_guide, albedo: *const yk_albedo, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, out_rgb: *mut f32) -> yk_status;
     pub fn yk_denoise_albedo_device(ctx: *mut yk_context, desc: *const yk_denoise_desc, d_film_rgb: *const c_void, d_guides: *const c_void, d_albedo: *const c_void, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, d_out_rgb: *mut c_void, stream: *mut c_void) -> yk_status;
+    pub fn yk_moments_blend(ctx: *mut yk_context, desc: *const yk_temporal_desc, film_rgb: *const f32, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, moments: *const yk_moments, out_moments: *mut yk_moments) -> yk_status;
+    pub fn yk_moments_blend_device(ctx: *mut yk_context, desc: *const yk_temporal_desc, d_film_rgb: *const c_void, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, d_moments: *const c_void, d_out_moments: *mut c_void, stream: *mut c_void) -> yk_status;
+    pub fn yk_variance(ctx: *mut yk_context, desc: *const yk_variance_desc, moments: *const yk_moments, film_rgb: *const f32, guides: *const yk_guide, albedo: *const yk_albedo, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, out_variance: *mut f32) -> yk_status;
+    pub fn yk_variance_device(ctx: *mut yk_context, desc: *const yk_variance_desc, d_moments: *const c_void, d_film_rgb: *const c_void, d_guides: *const c_void, d_albedo: *const c_void, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, d_out_variance: *mut c_void, stream: *mut c_void) -> yk_status;
+    pub fn yk_denoise_variance(ctx: *mut yk_context, desc: *const yk_variance_desc, film_rgb: *const f32, guides: *const yk_guide, variance: *const f32, albedo: *const yk_albedo, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, out_rgb: *mut f32) -> yk_status;
+    pub fn yk_denoise_variance_device(ctx: *mut yk_context, desc: *const yk_variance_desc, d_film_rgb: *const c_void, d_guides: *const c_void, d_variance: *const c_void, d_albedo: *const c_void, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, d_out_rgb: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_write_png(path: *const c_char, width: u32, height: u32, channels: u32, pixels: *const u8) -> yk_status;
     pub fn yk_render_tile(ctx: *mut yk_context, scene: *const yk_scene, camera: *const yk_camera, sampler: *const yk_sampler_desc, integrator: *const yk_integrator_desc, tile: *const yk_tile, tile_pixels: *mut f32, out_rays: *mut u64) -> yk_status;
     pub fn yk_film_update_tiles_device(ctx: *mut yk_context, tiles: *const yk_tile, n_tiles: usize, d_tile_rgb: *const c_void, res_x: u16, res_y: u16, d_film_rgb: *mut c_void, stream: *mut c_void) -> yk_status;

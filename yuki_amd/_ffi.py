@@ -188,6 +188,12 @@ SYMBOLS = {
     "yk_denoise_albedo_device": (C.c_int, [vp, C.POINTER(abi.DenoiseDesc), vp, vp, vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp]),
     "yk_history_reproject_moved": (C.c_int, [vp, C.POINTER(abi.TemporalDesc), vp, vp, C.POINTER(abi.CameraMatrices), vp, vp, C.c_uint16, C.c_uint16, vp]),
     "yk_history_reproject_moved_device": (C.c_int, [vp, C.POINTER(abi.TemporalDesc), vp, vp, C.POINTER(abi.CameraMatrices), vp, vp, C.c_uint16, C.c_uint16, vp, vp]),
+    "yk_moments_blend": (C.c_int, [vp, C.POINTER(abi.TemporalDesc), vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp]),
+    "yk_moments_blend_device": (C.c_int, [vp, C.POINTER(abi.TemporalDesc), vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp, vp]),
+    "yk_variance": (C.c_int, [vp, C.POINTER(abi.VarianceDesc), vp, vp, vp, vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp]),
+    "yk_variance_device": (C.c_int, [vp, C.POINTER(abi.VarianceDesc), vp, vp, vp, vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp]),
+    "yk_denoise_variance": (C.c_int, [vp, C.POINTER(abi.VarianceDesc), vp, vp, vp, vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp]),
+    "yk_denoise_variance_device": (C.c_int, [vp, C.POINTER(abi.VarianceDesc), vp, vp, vp, vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp]),
     "yk_write_png": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
     # several GPUs
     "yk_multi_create": (C.c_int, [C.POINTER(C.c_int), C.c_uint32, C.POINTER(vp)]),

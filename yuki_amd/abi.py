@@ -138,6 +138,13 @@ class TemporalDesc(C.Structure):
     _fields_ = [("plane_tolerance", C.c_float), ("normal_cos_min", C.c_float), ("max_history", C.c_float)]
 
 
+class VarianceDesc(C.Structure):
+    """yk_variance_desc: the à-trous iterations, the variance-scaled colour stop and the two geometric stops
+    (csrc/yk_variance.h)."""
+
+    _fields_ = [("iterations", C.c_uint32), ("sigma_variance", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float), ("epsilon", C.c_float), ("spatial_scale", C.c_float)]
+
+
 class IntegratorRay(C.Structure):
     """yk_integrator_ray: IntegratorRay (integrators/mod.rs:76-80), the ray and its yk_ray_type."""
 
@@ -216,6 +223,7 @@ SURFACE_ID_DTYPE = np.dtype([("shape", "<u4"), ("b", "<f4", 3)])  # yk_surface_i
 MOTION_DTYPE = np.dtype([("p_prev", "<f4", 3), ("known", "<f4")])  # yk_motion, 16 bytes
 ALBEDO_DTYPE = np.dtype([("a", "<f4", 3), ("known", "<f4")])  # yk_albedo, 16 bytes
 ALBEDO_FLOOR = 0.015625  # YK_ALBEDO_FLOOR, 2^-6
+MOMENTS_DTYPE = np.dtype([("m1", "<f4"), ("m2", "<f4"), ("frames", "<f4"), ("n", "<f4")])  # yk_moments, 16 bytes: yk_history's layout
 
 # enums (include/yuki_hip.h)
 SPLIT_SAH, SPLIT_MIDDLE, SPLIT_EQUAL_COUNTS = 0, 1, 2

@@ -253,15 +253,31 @@ def render_guides(ctx, scene, camera, film_settings):
     return out
 
 
-def denoise(film, guides, params, tile_dim=16, samples=None, ctx=None, albedo=None):
+def denoise(film, guides, params, tile_dim=16, samples=None, ctx=None, albedo=None, variance=None):
     """yk_denoise: the edge-avoiding à-trous filter of csrc/yk_denoise.h over an (h, w, 3) float32 film under (h, w)
     guides; `samples` = Film.samples (film_samples) for an accumulating film, whose sums are normalised first.  Returns the
     new film; ctx None = the host instance.  albedo (surface_albedo's (h, w) records): yk_denoise_albedo, the same filter
-    on radiance / albedo (csrc/yk_albedo.h)."""
+    on radiance / albedo (csrc/yk_albedo.h).  variance (variance()'s (h, w) image) with a VarianceParams:
+    yk_denoise_variance, whose colour stop follows the variance (csrc/yk_variance.h); albedo is honoured there too."""
     film = np.ascontiguousarray(film, dtype=np.float32)
     if film.ndim != 3 or film.shape[2] != 3:
         raise ValueError("film is (h, w, 3)")
     h, w = film.shape[0], film.shape[1]
+    if variance is not None or isinstance(params, VarianceParams):
+        if variance is None:
+            raise ValueError("a VarianceParams needs variance (variance())")
+        d = _variance_desc(params)
+        samples = _blend_samples((w, h), tile_dim, samples)
+        guides = _records(guides, abi.GUIDE_DTYPE, (w, h), "guide")
+        variance = np.ascontiguousarray(variance, dtype=np.float32)
+        if variance.size != w * h:
+            raise ValueError("one variance per film pixel")
+        if albedo is not None:
+            albedo = _records(albedo, abi.ALBEDO_DTYPE, (w, h), "albedo")
+        out = np.empty_like(film)
+        c = ctx.h if ctx else None
+        check(lib().yk_denoise_variance(c, C.byref(d), _p(film), _p(guides), _p(variance), _p(albedo), w, h, int(tile_dim), _p(samples), _p(out)), c)
+        return out
     d, guides, samples = _denoise_args((w, h), params, guides, tile_dim, samples)
     out = np.empty_like(film)
     c = ctx.h if ctx else None
@@ -426,27 +442,103 @@ def blend_history(film, params, tile_dim=16, samples=None, history=None, ctx=Non
     return rgb, out
 
 
-def _denoise_for_output(film, denoise_params, guides, tile_dim, samples, ctx, albedo=None):
+# --------------------------------------------------------------------------- variance (csrc/yk_variance.h)
+# Per frame: render the pass into a cleared film; rgb, history = blend_history(film, tp, samples=..., history=carried);
+# moments = blend_moments(film, tp, samples=..., moments=carried_moments) from the SAME film; after a move the moments go
+# through reproject_history[_moved] like the history (same layout: pass moments.view(abi.HISTORY_DTYPE));
+# var = variance(moments, rgb, guides, vp); out = denoise(rgb, guides, vp, variance=var).
+@dataclass
+class VarianceParams:
+    """yk_variance_desc: the à-trous iterations (0 .. 8), the variance-scaled colour stop, the normal and plane-distance
+    stops of DenoiseParams, epsilon under the colour stop and the factor on the spatial estimate (csrc/yk_variance.h);
+    float("inf") switches a stop off.  The defaults of sigma_variance, epsilon and spatial_scale are the best row of
+    profiles/variance_quality.json.  sigma_plane None stands for "no plane stop"; for_scene scales it to the scene."""
+
+    iterations: int = 5
+    sigma_variance: float = 3.0
+    sigma_normal: float = 0.3
+    sigma_plane: float = None
+    epsilon: float = 1e-8
+    spatial_scale: float = 1.0
+
+    @staticmethod
+    def for_scene(scene, **kw):
+        """sigma_plane = 0.01 x the diagonal of the scene's bounds (Scene.info()), as DenoiseParams.for_scene."""
+        i = scene.info()
+        diag = float(np.linalg.norm(np.array(i.bounds_max[:], dtype=np.float64) - np.array(i.bounds_min[:], dtype=np.float64)))
+        return VarianceParams(sigma_plane=0.01 * diag, **kw)
+
+    def as_struct(self):
+        return abi.VarianceDesc(int(self.iterations), float(self.sigma_variance), float(self.sigma_normal), float("inf") if self.sigma_plane is None else float(self.sigma_plane), float(self.epsilon), float(self.spatial_scale))
+
+
+def _variance_desc(params):
+    if not isinstance(params, VarianceParams):
+        raise TypeError("params is a VarianceParams")
+    return params.as_struct()
+
+
+def blend_moments(film, params, tile_dim=16, samples=None, moments=None, ctx=None):
+    """yk_moments_blend: the luminance of the film blend_history folds into the history, folded into the (reprojected)
+    (h, w) abi.MOMENTS_DTYPE moments (or None) -> the new moments.  `params` is blend_history's TemporalParams.  ctx None =
+    the host instance."""
+    film = np.ascontiguousarray(film, dtype=np.float32)
+    if film.ndim != 3 or film.shape[2] != 3:
+        raise ValueError("film is (h, w, 3)")
+    h, w = film.shape[0], film.shape[1]
+    d = _temporal_desc(params)
+    samples = _blend_samples((w, h), tile_dim, samples)
+    if moments is not None:
+        moments = _records(moments, abi.MOMENTS_DTYPE, (w, h), "moments")
+    out = np.zeros((h, w), dtype=abi.MOMENTS_DTYPE)
+    c = ctx.h if ctx else None
+    check(lib().yk_moments_blend(c, C.byref(d), _p(film), w, h, int(tile_dim), _p(samples), _p(moments), _p(out)), c)
+    return out
+
+
+def variance(moments, film, guides, params, tile_dim=16, samples=None, ctx=None, albedo=None):
+    """yk_variance: the (h, w) float32 variance of the luminance of `film` as denoise(..., variance=) will filter it: from
+    the moments (or None) where they hold two frames or more, from the 7 x 7 neighbourhood everywhere else.  With albedo:
+    the variance of the demodulated film.  ctx None = the host instance."""
+    film = np.ascontiguousarray(film, dtype=np.float32)
+    if film.ndim != 3 or film.shape[2] != 3:
+        raise ValueError("film is (h, w, 3)")
+    h, w = film.shape[0], film.shape[1]
+    d = _variance_desc(params)
+    samples = _blend_samples((w, h), tile_dim, samples)
+    guides = _records(guides, abi.GUIDE_DTYPE, (w, h), "guide")
+    if moments is not None:
+        moments = _records(moments, abi.MOMENTS_DTYPE, (w, h), "moments")
+    if albedo is not None:
+        albedo = _records(albedo, abi.ALBEDO_DTYPE, (w, h), "albedo")
+    out = np.zeros((h, w), dtype=np.float32)
+    c = ctx.h if ctx else None
+    check(lib().yk_variance(c, C.byref(d), _p(moments), _p(film), _p(guides), _p(albedo), w, h, int(tile_dim), _p(samples), _p(out)), c)
+    return out
+
+
+def _denoise_for_output(film, denoise_params, guides, tile_dim, samples, ctx, albedo=None, variance=None):
     """The denoise step of write_output / write_preview: (film, samples) for the tone map that follows — the denoised film
     is normalised already, so it goes on without the sample table."""
     if denoise_params is None:
-        if albedo is not None:
-            raise ValueError("albedo needs denoise (a DenoiseParams) and guides")
+        if albedo is not None or variance is not None:
+            raise ValueError("albedo and variance need denoise (a DenoiseParams or VarianceParams) and guides")
         return film, samples
     if guides is None:
         raise ValueError("denoise needs guides (render_guides)")
-    return denoise(film, guides, denoise_params, tile_dim, samples, ctx, albedo), None
+    return denoise(film, guides, denoise_params, tile_dim, samples, ctx, albedo, variance), None
 
 
-def write_output(path, film, tone_map=None, settings=None, samples=None, ctx=None, denoise=None, guides=None, albedo=None):
+def write_output(path, film, tone_map=None, settings=None, samples=None, ctx=None, denoise=None, guides=None, albedo=None, variance=None):
     """The Finished branch of app/headless.rs:62-84: Raw writes the film as it is, anything else writes the tone-mapped
     film (a Heatmap without bounds finds them first).  tone_map None = ToneMapType.default(); settings None = a film of the
     array's size with the default tile_dim.  denoise (a DenoiseParams) with guides: the film is denoised first; with albedo
-    (surface_albedo's records) too: by the demodulated filter."""
+    (surface_albedo's records) too: by the demodulated filter; with a VarianceParams and variance (variance()'s image): by
+    the variance-guided filter."""
     film = np.ascontiguousarray(film, dtype=np.float32)
     tone_map = ToneMapType.default() if tone_map is None else tone_map
     settings = settings or FilmSettings(res=(film.shape[1], film.shape[0]))
-    film, samples = _denoise_for_output(film, denoise, guides, film_tile_dim(settings), samples, ctx, albedo)
+    film, samples = _denoise_for_output(film, denoise, guides, film_tile_dim(settings), samples, ctx, albedo, variance)
     if tone_map.kind == abi.TONE_MAP_RAW:
         write_exr(path, film)
         return
@@ -556,15 +648,16 @@ def write_png(path, pixels):
     check(lib().yk_write_png(str(path).encode(), pixels.shape[1], pixels.shape[0], pixels.shape[2], _p(pixels)))
 
 
-def write_preview(path, film, tone_map=None, settings=None, samples=None, window=None, ctx=None, denoise=None, guides=None, albedo=None):
+def write_preview(path, film, tone_map=None, settings=None, samples=None, window=None, ctx=None, denoise=None, guides=None, albedo=None, variance=None):
     """What the window shows, as a PNG: the denoiser when `denoise` (a DenoiseParams) and `guides` are given (demodulated
-    by `albedo`, surface_albedo's records, when that is given too), the tone map
+    by `albedo`, surface_albedo's records, when that is given too; variance-guided when `denoise` is a VarianceParams and
+    `variance` its image), the tone map
     (as write_output: None = ToneMapType.default(), Raw = none), then present into `window` (default: the film's size) as
     an sRGB back buffer stores it (encode 2), then write_png."""
     film = np.ascontiguousarray(film, dtype=np.float32)
     tone_map = ToneMapType.default() if tone_map is None else tone_map
     settings = settings or FilmSettings(res=(film.shape[1], film.shape[0]))
-    film, samples = _denoise_for_output(film, denoise, guides, film_tile_dim(settings), samples, ctx, albedo)
+    film, samples = _denoise_for_output(film, denoise, guides, film_tile_dim(settings), samples, ctx, albedo, variance)
     if tone_map.kind != abi.TONE_MAP_RAW:
         film = _apply_tone_map(film, tone_map, film_tile_dim(settings), samples, ctx, None)
     window = (film.shape[1], film.shape[0]) if window is None else window
@@ -781,6 +874,30 @@ class Context:
         samples = _blend_samples(res, tile_dim, samples)
         vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
         check(lib().yk_history_blend_device(self.h, C.byref(d), vp(d_film_ptr), int(res[0]), int(res[1]), int(tile_dim), _p(samples), vp(d_history_ptr), vp(d_out_history_ptr), vp(d_out_rgb_ptr), vp(stream)), self.h)
+
+    def blend_moments_device(self, d_film_ptr, res, params, tile_dim, samples, d_moments_ptr, d_out_moments_ptr, stream=None):
+        """yk_moments_blend_device: device film + device moments (or None) -> device moments (may be the input), enqueued on
+        `stream` (default: the context's) without waiting; `params` is blend_history_device's TemporalParams."""
+        d = _temporal_desc(params)
+        samples = _blend_samples(res, tile_dim, samples)
+        vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
+        check(lib().yk_moments_blend_device(self.h, C.byref(d), vp(d_film_ptr), int(res[0]), int(res[1]), int(tile_dim), _p(samples), vp(d_moments_ptr), vp(d_out_moments_ptr), vp(stream)), self.h)
+
+    def variance_device(self, d_moments_ptr, d_film_ptr, d_guides_ptr, res, params, tile_dim, samples, d_out_ptr, stream=None, albedo=None):
+        """yk_variance_device: device moments (or None), film, guides and albedo (or None) -> res[0] * res[1] device floats,
+        enqueued on `stream` (default: the context's) without waiting; one launch."""
+        d = _variance_desc(params)
+        samples = _blend_samples(res, tile_dim, samples)
+        vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
+        check(lib().yk_variance_device(self.h, C.byref(d), vp(d_moments_ptr), vp(d_film_ptr), vp(d_guides_ptr), vp(albedo), int(res[0]), int(res[1]), int(tile_dim), _p(samples), vp(d_out_ptr), vp(stream)), self.h)
+
+    def denoise_variance_device(self, d_film_ptr, d_guides_ptr, d_variance_ptr, res, params, tile_dim, samples, d_out_ptr, stream=None, albedo=None):
+        """yk_denoise_variance_device: denoise_device with the device variance image of variance_device and a
+        VarianceParams; d_out_ptr may be the film."""
+        d = _variance_desc(params)
+        samples = _blend_samples(res, tile_dim, samples)
+        vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
+        check(lib().yk_denoise_variance_device(self.h, C.byref(d), vp(d_film_ptr), vp(d_guides_ptr), vp(d_variance_ptr), vp(albedo), int(res[0]), int(res[1]), int(tile_dim), _p(samples), vp(d_out_ptr), vp(stream)), self.h)
 
     @property
     def stream_handle(self):
