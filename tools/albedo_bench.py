@@ -61,9 +61,12 @@ def main():
     ap.add_argument("--launches", type=int, default=20)
     ap.add_argument("--plain-only", action="store_true", help="time plain yk_denoise_device alone (a build without the albedo passes)")
     ap.add_argument("--other-plain", default="", help="the --plain-only result of another build, quoted beside this one's")
+    ap.add_argument("--lds-max-step", type=int, default=None, help='"denoise_lds_max_step" (0, 1 or 2) instead of the library\'s default')
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     ctx = yk.Context(0)
+    if a.lds_max_step is not None:
+        ctx.set_option("denoise_lds_max_step", a.lds_max_step)
     sd = scenes.by_name(a.scene)
     fs = yk.FilmSettings(res=RES, tile_dim=16)
     cam = yk.Camera(sd.camera, fs)
@@ -79,7 +82,7 @@ def main():
     d_film = torch.from_numpy(film.reshape(-1)).to("cuda:0")
     d_guides, d_ids, d_albedo, d_out = z(8 * n_px), z(4 * n_px), z(4 * n_px), z(3 * n_px)
     torch.cuda.synchronize()
-    result = dict(tool="tools/albedo_bench.py", timing="device events around each call", film=list(RES), scene=a.scene, iterations=ITERATIONS, warmup=a.warmup, launches=a.launches,
+    result = dict(tool="tools/albedo_bench.py", timing="device events around each call", film=list(RES), scene=a.scene, iterations=ITERATIONS, warmup=a.warmup, launches=a.launches, lds_max_step=a.lds_max_step,
                   params=dict(sigma_color=params.sigma_color, sigma_normal=params.sigma_normal, sigma_plane=params.sigma_plane), copy_ceiling_gbps=COPY_CEILING_GBPS)
 
     us = timed(stream, a.launches, a.warmup, lambda: ctx.render_guides_device(sc, cam, RES, d_guides.data_ptr(), stream=cs))

@@ -55,9 +55,12 @@ def main():
     ap.add_argument("--scene", default="cfg3")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--launches", type=int, default=20)
+    ap.add_argument("--lds-max-step", type=int, default=None, help='"denoise_lds_max_step" (0, 1 or 2) instead of the library\'s default')
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     ctx = yk.Context(0)
+    if a.lds_max_step is not None:
+        ctx.set_option("denoise_lds_max_step", a.lds_max_step)
     sd = scenes.by_name(a.scene)
     fs = yk.FilmSettings(res=RES, tile_dim=16)
     cam = yk.Camera(sd.camera, fs)
@@ -82,7 +85,7 @@ def main():
     ctx.blend_moments_device(d_frames[0].data_ptr(), RES, tp, 16, None, None, d_mom.data_ptr(), stream=cs)
     ctx.blend_history_device(d_frames[1].data_ptr(), RES, tp, 16, None, d_hist.data_ptr(), d_hist.data_ptr(), d_rgb.data_ptr(), stream=cs)
     stream.synchronize()
-    result = dict(tool="tools/variance_bench.py", timing="device events around each call", film=list(RES), scene=a.scene, iterations=ITERATIONS, warmup=a.warmup, launches=a.launches,
+    result = dict(tool="tools/variance_bench.py", timing="device events around each call", film=list(RES), scene=a.scene, iterations=ITERATIONS, warmup=a.warmup, launches=a.launches, lds_max_step=a.lds_max_step,
                   params=dict(sigma_variance=vpar.sigma_variance, sigma_normal=vpar.sigma_normal, sigma_plane=vpar.sigma_plane, epsilon=vpar.epsilon, spatial_scale=vpar.spatial_scale,
                               plain_sigma_color=plain_params.sigma_color))  # fmt: skip
 

@@ -44,6 +44,24 @@ struct DnTap {
     float p[3];
 };
 
+// A guide record as two halves of four floats, (ns, hit) and (p, t): two 16-byte loads on the device, a yk_guide's ns and p
+// on the host.  Copies; t is not read (k_variance keeps a luminance in its slot).
+YK_HD void dn_guide(const float* ga, const float* gb, float* ns, float& hit, float* p) {
+    ns[0] = ga[0];
+    ns[1] = ga[1];
+    ns[2] = ga[2];
+    hit = ga[3];
+    p[0] = gb[0];
+    p[1] = gb[1];
+    p[2] = gb[2];
+}
+
+// What every denoise descriptor must satisfy: at most DN_MAX_ITERATIONS iterations, and the sigma of the colour (or
+// variance) stop, of the normal stop and of the plane stop each > 0, which refuses a NaN as well.
+inline bool dn_desc_ok(uint32_t iterations, float sigma_first, float sigma_normal, float sigma_plane) {
+    return iterations <= DN_MAX_ITERATIONS && sigma_first > 0.0f && sigma_normal > 0.0f && sigma_plane > 0.0f;
+}
+
 // Input.  The film's RGB; with a sample table each channel is divided by count = (float)samples[tm_sample_index(x, y)]
 // when count > 0 (the Filmic tone map's normalisation, tm_filmic step 1).  Without a table, or where the count is 0, the
 // bits are copied.
@@ -79,6 +97,26 @@ YK_HD float dn_color_denominator(float sigma_color, uint32_t i) {
 // weight is 0 or NaN, which happens exactly when: one pixel is a hit and the other a miss; e is NaN or +inf (a channel of
 // either colour is NaN or infinite, a difference or its square overflows, a guide is not finite, a denominator is 0 or
 // the quotient inf / inf); or exp(-e) underflows to 0 (e above about 103.97).
+//
+// dn_stops: a_n and a_p of two pixels of one hit class (hit: both are hits), apart — every caller adds them to its
+// exponent in its own order (dn_weight and vr_weight: (a_c + a_n) + a_p; the variance window: a_n + a_p).
+struct DnStops {
+    float a_n, a_p;
+};
+YK_HD DnStops dn_stops(const DnParams& a, bool hit, const float* nsP, const float* pP, const float* nsQ, const float* pQ) {
+    float a_n = 0.0f, a_p = 0.0f;
+    if (hit) {
+        const V3 nP = V3{nsP[0], nsP[1], nsP[2]};
+        const V3 n = nP - V3{nsQ[0], nsQ[1], nsQ[2]};
+        const float nn = dot(n, n);
+        a_n = nn / a.den_n;
+        const V3 v = V3{pQ[0], pQ[1], pQ[2]} - V3{pP[0], pP[1], pP[2]};
+        const float d = dot(nP, v);
+        const float dd = d * d;
+        a_p = dd / a.den_p;
+    }
+    return DnStops{a_n, a_p};
+}
 YK_HD float dn_weight(const DnParams& a, float den_c, float h, const DnTap& P, const DnTap& Q) {
     const bool hp = P.hit != 0.0f, hq = Q.hit != 0.0f;
     if (hp != hq) return 0.0f;
@@ -86,18 +124,8 @@ YK_HD float dn_weight(const DnParams& a, float den_c, float h, const DnTap& P, c
     const float rr = dr * dr, gg = dg * dg, bb = db * db;
     const float cs = (rr + gg) + bb;
     const float a_c = cs / den_c;
-    float a_n = 0.0f, a_p = 0.0f;
-    if (hp) {
-        const V3 nP = V3{P.ns[0], P.ns[1], P.ns[2]};
-        const V3 n = nP - V3{Q.ns[0], Q.ns[1], Q.ns[2]};
-        const float nn = dot(n, n);
-        a_n = nn / a.den_n;
-        const V3 v = V3{Q.p[0], Q.p[1], Q.p[2]} - V3{P.p[0], P.p[1], P.p[2]};
-        const float d = dot(nP, v);
-        const float dd = d * d;
-        a_p = dd / a.den_p;
-    }
-    const float e = (a_c + a_n) + a_p;
+    const DnStops g = dn_stops(a, hp, P.ns, P.p, Q.ns, Q.p);
+    const float e = (a_c + g.a_n) + g.a_p;
     const float x = det_expf(-e);
     return h * x;
 }

@@ -8,8 +8,8 @@
 //   - IEEE-754 binary32, round to nearest, every operation separate (-ffp-contract=off), divisions correctly rounded,
 //     exp is det_expf;
 //   - a NaN that an operation PRODUCES is 0x7fc00000 (dn_canon); a value that is only copied keeps its bits.
-// One text, two instances: the host instance (no context) and the gfx950 kernels of yk_variance.hip call the functions
-// below and agree bit for bit.
+// One text, two instances: the host instance (no context) and the gfx950 kernels (yk_variance.hip: the moments and the
+// variance image; yk_denoise.hip: the filter) call the functions below and agree bit for bit.
 //
 // The moments record yk_moments (m1, m2, frames, n) has the layout of yk_history (rgb[3], n) ON PURPOSE: a moments
 // buffer is reprojected by yk_history_reproject[_device] and yk_history_reproject_moved[_device] as they are, cast to
@@ -33,6 +33,22 @@ struct VrParams {
     float sv2;  // sigma_variance * sigma_variance
     float epsilon, spatial_scale;
 };
+// What yk_variance and yk_denoise_variance ask of their descriptor, and the parameters it makes.
+inline bool vr_desc_ok(const yk_variance_desc* d) {
+    if (!d || !dn_desc_ok(d->iterations, d->sigma_variance, d->sigma_normal, d->sigma_plane)) return false;
+    return d->epsilon >= 0.0f && d->spatial_scale >= 0.0f;  // < 0 or NaN
+}
+inline VrParams vr_make_params(const yk_variance_desc* d, uint32_t res_x, uint32_t res_y, uint32_t tile_dim) {
+    VrParams a{};
+    dn_set_grid(a.dn, res_x, res_y, tile_dim);
+    a.dn.sigma_color = 0.0f;
+    a.dn.den_n = d->sigma_normal * d->sigma_normal;
+    a.dn.den_p = d->sigma_plane * d->sigma_plane;
+    a.sv2 = d->sigma_variance * d->sigma_variance;
+    a.epsilon = d->epsilon;
+    a.spatial_scale = d->spatial_scale;
+    return a;
+}
 
 // Luminance: fixed Rec. 709 weights as exact float literals, products first, summed left to right.
 YK_HD float vr_luminance(const float* c) {
@@ -146,18 +162,8 @@ YK_HD float vr_tap_luminance(const DnParams& a, const float* film, const uint32_
 
 // The geometric part of dn_weight's exponent for taps of one hit class: a_n + a_p for two hits, 0 for two misses.
 YK_HD float vr_geometry(const DnParams& a, bool hit, const float* nsP, const float* pP, const float* nsQ, const float* pQ) {
-    float a_n = 0.0f, a_p = 0.0f;
-    if (hit) {
-        const V3 nP = V3{nsP[0], nsP[1], nsP[2]};
-        const V3 n = nP - V3{nsQ[0], nsQ[1], nsQ[2]};
-        const float nn = dot(n, n);
-        a_n = nn / a.den_n;
-        const V3 v = V3{pQ[0], pQ[1], pQ[2]} - V3{pP[0], pP[1], pP[2]};
-        const float d = dot(nP, v);
-        const float dd = d * d;
-        a_p = dd / a.den_p;
-    }
-    return a_n + a_p;
+    const DnStops g = dn_stops(a, hit, nsP, pP, nsQ, pQ);
+    return g.a_n + g.a_p;
 }
 
 // Spatial estimate, everywhere else (the first frame, disocclusions, no moments): the weighted variance of l over the
@@ -262,18 +268,8 @@ YK_HD float vr_weight(const DnParams& a, float den_c, float h, const DnTap& P, f
     const float dl = lP - lQ;
     const float d2 = dl * dl;
     const float a_c = d2 / den_c;
-    float a_n = 0.0f, a_p = 0.0f;
-    if (hp) {
-        const V3 nP = V3{P.ns[0], P.ns[1], P.ns[2]};
-        const V3 n = nP - V3{Q.ns[0], Q.ns[1], Q.ns[2]};
-        const float nn = dot(n, n);
-        a_n = nn / a.den_n;
-        const V3 v = V3{Q.p[0], Q.p[1], Q.p[2]} - V3{P.p[0], P.p[1], P.p[2]};
-        const float d = dot(nP, v);
-        const float dd = d * d;
-        a_p = dd / a.den_p;
-    }
-    const float e = (a_c + a_n) + a_p;
+    const DnStops g = dn_stops(a, hp, P.ns, P.p, Q.ns, Q.p);
+    const float e = (a_c + g.a_n) + g.a_p;
     const float x = det_expf(-e);
     return h * x;
 }
