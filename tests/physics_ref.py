@@ -1,0 +1,603 @@
+"""Float64 physics for the shading path: BSDF lobes, Fresnel terms, microfacet distribution, light sampling, polygon
+irradiance and directional albedo, written from the published models in plain numpy.
+
+Test infrastructure only.  Nothing here imports the oracle or the product, calls their arithmetic or follows their
+operation order: every function states the formula of its source (named in its docstring) in float64, so a term that
+the oracle and the device both misread disagrees with this file.
+
+Where the reference renderer knowingly differs from the textbook, the difference is an entry of DEVIATIONS and the
+functions follow the reference *only while that entry is switched on* (the default).  `textbook(key)` switches one entry
+off, `mutated(name)` plants one single-term mistake (MUTATIONS); tests/test_physics.py uses the first to prove that every
+entry is live and the second to prove that the comparisons would notice a misread term.
+
+Conventions: arrays are (n, 3) float64, directions point away from the surface (wo towards the viewer, wi towards the
+light), local frames have the shading normal on +z, spectra are RGB triples.
+"""
+import contextlib
+
+import numpy as np
+
+MATTE, GLASS, METAL, GLOSSY = 0, 1, 2, 3
+POINT, SPOT, DISTANT, RECT = 0, 1, 2, 3
+BX_REFLECTION, BX_TRANSMISSION, BX_DIFFUSE, BX_GLOSSY, BX_SPECULAR = 1, 2, 4, 8, 16
+
+# ----------------------------------------------------------------------------- the deviation ledger
+# Each entry: key, the SURVEY §8 quirk it restates (None = found by these tests), where the reference does it
+# (file:line under yuki/src of the reference), the sentence that SURVEY's quirk ledger carries, and what the tests assert
+# instead of the textbook.  The citations were read in the reference's text; tests/test_physics.py::test_ledger_entry_is_live
+# switches every entry off in turn and requires the figure named in `live` (case of tests/physics_cases.py, figure) to fail.
+DEVIATIONS = [
+    dict(
+        key="emission_beta_squared", quirk=2, where="integrators/path.rs:121-129",
+        sentence="Emission seen after a specular bounce is weighted by beta twice (beta^2 * Le), not once.",
+        asserts="li of an emitter seen through an index-matched pane is (T/0.5)^2 * Le per transmitted sample",
+        live=("estimator", "emitter_through_pane"),
+    ),
+    dict(
+        key="nee_consumes_dimensions", quirk=4, where="integrators/path.rs:103-114",
+        sentence="Every light consumes two sampler dimensions at every hit whether or not it contributes; the cosine is clamp(ns.l, 0, 1).",
+        asserts="a light below the floor leaves the furnace mean intact and shifts every later draw by two dimensions",
+        live=("estimator", "dimension_shift"),
+    ),
+    dict(
+        key="lobe_choice_uniform", quirk=9, where="materials/bsdfs/mod.rs:166-198, materials/glass.rs:27-45",
+        sentence="Glass is two specular lobes chosen uniformly by u0 < 0.5 with pdf 1/2 each, not one Fresnel-weighted lobe; the remapped u0 is u0*(k-comp).",
+        asserts="glass samples: reflection iff u0 < 0.5, pdf exactly 0.5 (pbrt's FresnelSpecular would give pdf F or 1-F)",
+        live=("bsdf/glass-1.5/ortho", "s_pdf_abs"),
+    ),
+    dict(
+        key="signed_pdf", quirk=11, where="materials/bsdfs/trowbridge_reitz.rs:76-78",
+        sentence="The half-vector pdf is D(wh)*cos(theta_h) without abs: it is negative whenever wo lies below the shading normal.",
+        asserts="microfacet sample pdf = sign(cos theta_o) * D*|cos theta_h| / (4 wo.wh)",
+        live=("bsdf/metal-0.2/ortho", "s_pdf_rel"),
+    ),
+    dict(
+        key="alpha_clamp", quirk=11, where="materials/bsdfs/trowbridge_reitz.rs:16-20",
+        sentence="Trowbridge-Reitz alpha is clamped to at least 1e-3.",
+        asserts="metal at alpha 1e-4 evaluates as alpha 1e-3",
+        live=("bsdf/metal-0.0001/ortho", "f_rel"),
+    ),
+    dict(
+        key="glossy_alpha_squared", quirk=11, where="materials/glossy.rs:39-49",
+        sentence="Glossy uses alpha = r^2, and under remap alpha = roughness_to_alpha(r)^2 (the square is applied after the remap, not to r).",
+        asserts="glossy f and pdf with alpha = roughness_to_alpha(r)**2 (remap) or r**2",
+        live=("bsdf/glossy-remap-0.4/ortho", "f_rel"),
+    ),
+    dict(
+        key="sigma_radians", quirk=12, where="materials/bsdfs/oren_nayar.rs:17-22, materials/matte.rs:32, scene/pbrt/mod.rs:904-907",
+        sentence="Oren-Nayar takes sigma in radians (pbrt: degrees), Lambert iff sigma == 0 exactly; the pbrt loader converts a file's sigma to radians twice.",
+        asserts="Oren-Nayar A, B from sigma as given, in radians",
+        live=("bsdf/oren-nayar-0.349/ortho", "f_rel"),
+    ),
+    dict(
+        key="fixed_offset", quirk=13, where="interaction.rs:27-59",
+        sentence="Rays leave a surface from p +- 1e-3*n (geometric n, side chosen by the direction), shadow rays run to t_max 0.9999 along the unnormalised p1 - o.",
+        asserts="shadow ray origin p +- 1e-3*ng, direction p1 - origin (pbrt: error-bound offset, here none for an exact p)",
+        live=("light/point", "ray_o_pos"),
+    ),
+    dict(
+        key="no_eta2_transmission", quirk=None, where="materials/bsdfs/specular.rs:83-84",
+        sentence="Specular transmission carries no (eta_i/eta_t)^2 radiance factor.",
+        asserts="glass transmission f = T*(1-F)/|cos theta_i|",
+        live=("bsdf/glass-1.5/ortho", "s_fresnel_abs"),
+    ),
+    dict(
+        key="schlick_signed_cos", quirk=None, where="materials/bsdfs/fresnel.rs:113-115, materials/bsdfs/microfacet.rs:65-67",
+        sentence="Schlick's Fresnel is evaluated at the signed cosine wi.faceforward(wh, +z): below the shading normal (1 - cos)^5 exceeds 1 and F exceeds 1.",
+        asserts="glossy f with (1 - c)^5 at c = sign(wh.z) * wi.wh",
+        live=("bsdf/glossy-0.3/ortho", "f_rel"),
+    ),
+    dict(
+        key="distant_fixed_reach", quirk=None, where="lights/distant_light.rs:31",
+        sentence="A distant light's shadow ray ends 10000 units away, not at twice the world radius.",
+        asserts="distant light p1 = p + 1e4 * w",
+        live=("light/distant", "p1_pos"),
+    ),
+    dict(
+        key="spot_no_tester_when_black", quirk=None, where="lights/spot_light.rs:61-72",
+        sentence="A spot light returns no visibility tester when its Li is black (outside the cone); pbrt always returns one.",
+        asserts="spot light has-visibility flag = (Li is not black)",
+        live=("light/spot", "flag_mismatch"),
+    ),
+]
+# Read in the reference and found to agree with pbrt-v3, hence no entries: the spot light's falloff (lights/spot_light.rs:38-50:
+# smooth (delta^2)^2 between cos_total_width and cos_falloff_start, 0 outside, 1 inside) and the rectangular light's emitting
+# side (lights/rectangular_light.rs:48-55: the side its normal (0,-1,0) faces, as DiffuseAreaLight's n.w > 0).
+
+DISTANT_WORLD_RADIUS = 10.0  # only what `textbook("distant_fixed_reach")` expects instead of the fixed reach
+
+MUTATIONS = [
+    "schlick_exponent_4",  # (1 - cos)^4 for (1 - cos)^5
+    "oren_nayar_030",  # A = 1 - s^2 / (2 (s^2 + 0.30))
+    "g_dropped",  # masking-shadowing G = 1
+    "pdf_without_jacobian",  # half-vector pdf without the 1 / (4 wo.wh)
+    "albedo_without_cos",  # directional albedo integrates f, not f cos
+    "fresnel_rpar_swapped_eta",  # r_parallel with eta_i and eta_t exchanged (exchanging them in both amplitudes only swaps the two)
+    "li_inverse_distance",  # point light Li = I / d
+    "rect_pdf_without_cos",  # area-to-solid-angle pdf d^2 / A
+    "snell_eta_inverted",  # refraction with eta_t / eta_i
+    "sigma_to_degrees",  # Oren-Nayar's sigma converted as if it were wanted in degrees
+]
+_MUTATION = None
+_OFF = set()
+
+
+@contextlib.contextmanager
+def mutated(name):
+    """Plant one single-term mistake in this reference (the power check)."""
+    global _MUTATION
+    assert name in MUTATIONS, name
+    prev, _MUTATION = _MUTATION, name
+    try:
+        yield
+    finally:
+        _MUTATION = prev
+
+
+@contextlib.contextmanager
+def textbook(key):
+    """Switch one ledger entry off: expect what the textbook does there."""
+    assert key in {d["key"] for d in DEVIATIONS}, key
+    _OFF.add(key)
+    try:
+        yield
+    finally:
+        _OFF.discard(key)
+
+
+def _m(name):
+    return _MUTATION == name
+
+
+def _on(key):
+    return key not in _OFF
+
+
+# ----------------------------------------------------------------------------- vectors and frames
+def f64(a):
+    return np.asarray(a, dtype=np.float64)
+
+
+def dot(a, b):
+    return np.sum(f64(a) * f64(b), axis=-1)
+
+
+def normalize(v):
+    v = f64(v)
+    return v / np.linalg.norm(v, axis=-1, keepdims=True)
+
+
+def frame(ns, dpdu):
+    """Shading frame (s, t, n) — pbrt-v3 §9.1 (BSDF constructor): s = normalize(dpdu), t = n x s."""
+    n = f64(ns)
+    s = normalize(dpdu)
+    return s, np.cross(n, s), n
+
+
+def to_local(v, fr):
+    """pbrt-v3 §9.1 BSDF::WorldToLocal."""
+    return np.stack([dot(v, fr[0]), dot(v, fr[1]), dot(v, fr[2])], axis=-1)
+
+
+def to_world(v, fr):
+    """pbrt-v3 §9.1 BSDF::LocalToWorld."""
+    v = f64(v)
+    return fr[0] * v[..., 0:1] + fr[1] * v[..., 1:2] + fr[2] * v[..., 2:3]
+
+
+# ----------------------------------------------------------------------------- diffuse lobes
+def lambert_f(kd):
+    """Lambertian BRDF R/pi — pbrt-v3 §8.3."""
+    return f64(kd) / np.pi
+
+
+def oren_nayar_ab(sigma):
+    """Oren-Nayar A, B from sigma in radians — pbrt-v3 §8.4.1 (Oren and Nayar 1994, the qualitative model)."""
+    sigma = float(sigma)
+    if not _on("sigma_radians"):
+        sigma = np.radians(sigma)  # pbrt's convention: the parameter is in degrees
+    if _m("sigma_to_degrees"):
+        sigma = np.degrees(sigma)
+    s2 = sigma * sigma
+    c = 0.30 if _m("oren_nayar_030") else 0.33
+    return 1.0 - s2 / (2.0 * (s2 + c)), 0.45 * s2 / (s2 + 0.09)
+
+
+def oren_nayar_f(kd, sigma, wo, wi):
+    """f = R/pi (A + B max(0, cos(phi_i - phi_o)) sin(alpha) tan(beta)), alpha = max(theta_i, theta_o), beta = min —
+    pbrt-v3 §8.4.1 eq. 8.10, local directions."""
+    a, b = oren_nayar_ab(sigma)
+    wo, wi = f64(wo), f64(wi)
+    co, ci = np.abs(wo[:, 2]), np.abs(wi[:, 2])
+    so, si = np.sqrt(np.maximum(0.0, 1.0 - co * co)), np.sqrt(np.maximum(0.0, 1.0 - ci * ci))
+    with np.errstate(all="ignore"):
+        cos_dphi = np.where((so > 0) & (si > 0), (wo[:, 0] * wi[:, 0] + wo[:, 1] * wi[:, 1]) / (so * si), 0.0)
+        o_is_alpha = co < ci  # the larger polar angle has the smaller cosine
+        sin_alpha = np.where(o_is_alpha, so, si)
+        tan_beta = np.where(o_is_alpha, si / ci, so / co)
+    return lambert_f(kd)[None, :] * (a + b * np.maximum(0.0, cos_dphi) * sin_alpha * tan_beta)[:, None]
+
+
+def concentric_disk(u):
+    """Shirley and Chiu's concentric map of the unit square onto the unit disk — pbrt-v3 §13.6.2."""
+    o = 2.0 * f64(u) - 1.0
+    x, y = o[:, 0], o[:, 1]
+    with np.errstate(all="ignore"):
+        wide = np.abs(x) > np.abs(y)
+        r = np.where(wide, x, y)
+        theta = np.where(wide, (np.pi / 4.0) * (y / x), np.pi / 2.0 - (np.pi / 4.0) * (x / y))
+    theta = np.where((x == 0) & (y == 0), 0.0, theta)
+    return np.stack([r * np.cos(theta), r * np.sin(theta)], axis=-1)
+
+
+def cosine_hemisphere_sample(wo, u):
+    """Malley's method: the concentric disk sample lifted to the hemisphere on wo's side — pbrt-v3 §13.6.3."""
+    d = concentric_disk(u)
+    z = np.sqrt(np.maximum(0.0, 1.0 - d[:, 0] ** 2 - d[:, 1] ** 2))
+    return np.stack([d[:, 0], d[:, 1], np.where(f64(wo)[:, 2] < 0, -z, z)], axis=-1)
+
+
+def cosine_hemisphere_pdf(wo, wi):
+    """|cos theta_i| / pi on wo's side, 0 on the other — pbrt-v3 §13.6.3 with BxDF::Pdf §14.1."""
+    wo, wi = f64(wo), f64(wi)
+    return np.where(wo[:, 2] * wi[:, 2] > 0, np.abs(wi[:, 2]) / np.pi, 0.0)
+
+
+# ----------------------------------------------------------------------------- Fresnel
+def fresnel_dielectric(cos_i, eta_i, eta_t):
+    """Unpolarised Fresnel reflectance of a dielectric interface; a negative cosine means the ray arrives from the
+    eta_t side — pbrt-v3 §8.2.1 (FrDielectric).  1 under total internal reflection."""
+    c = np.clip(f64(cos_i), -1.0, 1.0)
+    inside = c <= 0
+    ei = np.where(inside, eta_t, eta_i)
+    et = np.where(inside, eta_i, eta_t)
+    c = np.abs(c)
+    sin_t = ei / et * np.sqrt(np.maximum(0.0, 1.0 - c * c))
+    tir = sin_t >= 1.0
+    cos_t = np.sqrt(np.maximum(0.0, 1.0 - sin_t * sin_t))
+    with np.errstate(all="ignore"):
+        if _m("fresnel_rpar_swapped_eta"):
+            r_par = (ei * c - et * cos_t) / (ei * c + et * cos_t)
+        else:
+            r_par = (et * c - ei * cos_t) / (et * c + ei * cos_t)
+        r_perp = (ei * c - et * cos_t) / (ei * c + et * cos_t)
+        f = 0.5 * (r_par * r_par + r_perp * r_perp)
+    return np.where(tir, 1.0, f)
+
+
+def sin_theta_t(cos_i, eta_i, eta_t):
+    """Snell's law: sin theta_t for the interface fresnel_dielectric describes — pbrt-v3 §8.2.1."""
+    c = np.clip(f64(cos_i), -1.0, 1.0)
+    inside = c <= 0
+    ratio = np.where(inside, eta_t / eta_i, eta_i / eta_t)
+    return ratio * np.sqrt(np.maximum(0.0, 1.0 - c * c))
+
+
+def fresnel_conductor(cos_i, eta, k, eta_i=1.0):
+    """Fresnel reflectance of a conductor with complex index eta + i k under a dielectric eta_i, from the complex
+    amplitude coefficients r_s, r_p (Born and Wolf §14.2; pbrt-v3 §8.2.1 FrConductor is their expansion).  (n, 3)."""
+    c = np.minimum(np.abs(f64(cos_i)), 1.0)[:, None]
+    n = (f64(eta)[None, :] + 1j * f64(k)[None, :]) / eta_i
+    s2 = 1.0 - c * c
+    root = np.sqrt(n * n - s2)
+    r_s = (c - root) / (c + root)
+    r_p = (n * n * c - root) / (n * n * c + root)
+    return 0.5 * (np.abs(r_s) ** 2 + np.abs(r_p) ** 2)
+
+
+def fresnel_schlick(cos_i, r0):
+    """Schlick's approximation R0 + (1 - R0)(1 - cos)^5 — Schlick 1994; pbrt-v3 §8.5 eq. 8.24."""
+    c = np.clip(f64(cos_i), -1.0, 1.0)[:, None]
+    e = 4 if _m("schlick_exponent_4") else 5
+    r0 = f64(r0)[None, :]
+    return r0 + (1.0 - r0) * (1.0 - c) ** e
+
+
+# ----------------------------------------------------------------------------- Trowbridge-Reitz microfacets
+def roughness_to_alpha(r):
+    """pbrt-v3 §8.4.2 TrowbridgeReitzDistribution::RoughnessToAlpha: a quartic in ln(max(r, 1e-3))."""
+    x = np.log(max(float(r), 1e-3))
+    return 1.62142 + 0.819955 * x + 0.1734 * x**2 + 0.0171201 * x**3 + 0.000640711 * x**4
+
+
+def tr_alpha(alpha):
+    return max(float(alpha), 1e-3) if _on("alpha_clamp") else float(alpha)
+
+
+def tr_d(wh, alpha):
+    """Isotropic Trowbridge-Reitz (GGX) D(wh) = 1 / (pi a^2 cos^4 (1 + tan^2/a^2)^2) — pbrt-v3 §8.4.2 eq. 8.12."""
+    c2 = f64(wh)[:, 2] ** 2
+    with np.errstate(all="ignore"):
+        t2 = (1.0 - c2) / c2
+        d = 1.0 / (np.pi * alpha * alpha * c2 * c2 * (1.0 + t2 / (alpha * alpha)) ** 2)
+    return np.where(c2 > 0, d, 0.0)
+
+
+def tr_lambda(w, alpha):
+    """Lambda(w) = (-1 + sqrt(1 + a^2 tan^2 theta)) / 2 — pbrt-v3 §8.4.3 eq. 8.13 for Trowbridge-Reitz."""
+    c2 = f64(w)[:, 2] ** 2
+    with np.errstate(all="ignore"):
+        t2 = (1.0 - c2) / c2
+        lam = 0.5 * (-1.0 + np.sqrt(1.0 + alpha * alpha * t2))
+    return np.where(c2 > 0, lam, 0.0)
+
+
+def tr_g(wo, wi, alpha):
+    """Height-correlated masking-shadowing G = 1 / (1 + Lambda(wo) + Lambda(wi)) — pbrt-v3 §8.4.3."""
+    if _m("g_dropped"):
+        return np.ones(len(wo))
+    return 1.0 / (1.0 + tr_lambda(wo, alpha) + tr_lambda(wi, alpha))
+
+
+def half_vector(wo, wi):
+    return normalize(f64(wo) + f64(wi))
+
+
+def torrance_sparrow_f(wo, wi, alpha, fresnel):
+    """f = D(wh) G(wo, wi) F / (4 |cos theta_o| |cos theta_i|) — pbrt-v3 §8.4.4 eq. 8.19.  `fresnel(c, c_signed)` -> (n, 3)
+    is given the cosine between wi and the half vector, and the same cosine measured against the half vector turned to +z."""
+    wo, wi = f64(wo), f64(wi)
+    wh = half_vector(wo, wi)
+    c = dot(wi, wh)
+    c_signed = np.where(wh[:, 2] < 0, -c, c)
+    with np.errstate(all="ignore"):
+        s = tr_d(wh, alpha) * tr_g(wo, wi, alpha) / (4.0 * np.abs(wo[:, 2]) * np.abs(wi[:, 2]))
+    return s[:, None] * fresnel(c, c_signed)
+
+
+def half_vector_pdf(wo, wi, alpha):
+    """Pdf of wi when wh is drawn from D(wh)|cos theta_h|: D |cos theta_h| / (4 wo.wh) — pbrt-v3 §14.1.1 (the
+    half-angle change of variables d wh / d wi = 1 / (4 wo.wh)).  0 across hemispheres."""
+    wo, wi = f64(wo), f64(wi)
+    wh = half_vector(wo, wi)
+    p = tr_d(wh, alpha) * np.abs(wh[:, 2])
+    if _on("signed_pdf"):
+        p = p * np.sign(wo[:, 2])
+    if not _m("pdf_without_jacobian"):
+        with np.errstate(all="ignore"):
+            p = p / (4.0 * dot(wo, wh))
+    return np.where(wo[:, 2] * wi[:, 2] > 0, p, 0.0)
+
+
+def tr_sample_wh(wo, u, alpha):
+    """Half vector for (u0, u1) when the full distribution of normals is sampled: tan^2 theta = a^2 u0 / (1 - u0),
+    phi = 2 pi u1, turned into wo's hemisphere — pbrt-v3 §14.1.1 (TrowbridgeReitzDistribution::Sample_wh, sampleVisibleArea off)."""
+    u = f64(u)
+    t2 = alpha * alpha * u[:, 0] / (1.0 - u[:, 0])
+    ct = 1.0 / np.sqrt(1.0 + t2)
+    st = np.sqrt(np.maximum(0.0, 1.0 - ct * ct))
+    phi = 2.0 * np.pi * u[:, 1]
+    wh = np.stack([st * np.cos(phi), st * np.sin(phi), ct], axis=-1)
+    return np.where((f64(wo)[:, 2] * wh[:, 2] > 0)[:, None], wh, -wh)
+
+
+# ----------------------------------------------------------------------------- specular directions
+def mirror(wo, n):
+    """Reflection of wo about n: -wo + 2 (wo.n) n — pbrt-v3 §8.2.2."""
+    wo, n = f64(wo), f64(n)
+    return -wo + 2.0 * dot(wo, n)[:, None] * n
+
+
+def snell(wo, eta_above, eta_below):
+    """Refracted local direction through the z = 0 interface (index eta_above over +z, eta_below under it) and the total
+    internal reflection mask — pbrt-v3 §8.2.3 (Refract): wt = -eta wo + (eta cos_i - cos_t) n, eta = eta_i / eta_t."""
+    wo = f64(wo)
+    above = wo[:, 2] > 0
+    eta = np.where(above, eta_above / eta_below, eta_below / eta_above)
+    if _m("snell_eta_inverted"):
+        eta = 1.0 / eta
+    n = np.where(above, 1.0, -1.0)
+    ci = np.abs(wo[:, 2])
+    s2t = eta * eta * np.maximum(0.0, 1.0 - ci * ci)
+    tir = s2t >= 1.0
+    ct = np.sqrt(np.maximum(0.0, 1.0 - s2t))
+    wt = -eta[:, None] * wo
+    wt[:, 2] += (eta * ci - ct) * n
+    return wt, tir
+
+
+# ----------------------------------------------------------------------------- materials -> BSDF
+def material_alpha(m):
+    """Microfacet alpha of a metal or glossy material description (kind, c = roughness, remap)."""
+    r = float(np.float32(m["c"]))
+    if m["kind"] == GLOSSY and not _on("glossy_alpha_squared"):
+        # what a reader of "Glossy squares roughness" might expect instead: the square applied to r before the remap,
+        # and no square at all without it (pbrt's alpha = roughness)
+        return tr_alpha(roughness_to_alpha(r * r) if m.get("remap") else r)
+    a = roughness_to_alpha(r) if m.get("remap") else r
+    if m["kind"] == GLOSSY:
+        a = a * a
+    return tr_alpha(a)
+
+
+def _spec(v):
+    return f64(np.asarray(v, dtype=np.float32))
+
+
+def lobe_f_local(m, wo, wi):
+    """The material's non-specular BRDF for local directions, (n, 3); 0 for glass and for a black matte."""
+    n = len(wo)
+    kind = m["kind"]
+    if kind == MATTE:
+        kd = _spec(m["a"])
+        if not kd.any():
+            return np.zeros((n, 3))
+        sigma = float(np.float32(m.get("c", 0.0)))
+        if sigma == 0.0:
+            return np.broadcast_to(lambert_f(kd), (n, 3)).copy()
+        return oren_nayar_f(kd, sigma, wo, wi)
+    if kind == METAL:
+        eta, k = _spec(m["a"]), _spec(m["b"])
+        return torrance_sparrow_f(wo, wi, material_alpha(m), lambda c, cs: fresnel_conductor(c, eta, k))
+    if kind == GLOSSY:
+        r0 = _spec(m["a"])
+        return torrance_sparrow_f(wo, wi, material_alpha(m), lambda c, cs: fresnel_schlick(cs if _on("schlick_signed_cos") else np.abs(c), r0))
+    return np.zeros((n, 3))
+
+
+def bsdf_f(m, ng, ns, dpdu, wo, wi):
+    """BSDF::f — pbrt-v3 §9.1: world directions go to the shading frame; reflection lobes count only when wo and wi lie on
+    the same side of the *geometric* normal (every lobe with a non-zero f here is a reflection lobe).  -> (f (n, 3), same-side mask)."""
+    fr = frame(ns, dpdu)
+    reflect = dot(wi, ng) * dot(wo, ng) > 0
+    with np.errstate(all="ignore"):
+        f = lobe_f_local(m, to_local(wo, fr), to_local(wi, fr))
+    return np.where(reflect[:, None], f, 0.0), reflect
+
+
+def lobe_pdf_local(m, wo, wi):
+    """Sampling density of the material's non-specular lobe for local directions."""
+    if m["kind"] == MATTE:
+        return cosine_hemisphere_pdf(wo, wi)
+    return half_vector_pdf(wo, wi, material_alpha(m))
+
+
+def lobe_type(m):
+    """BxDF type bits of the non-specular lobe — pbrt-v3 §8.1 (BxDFType)."""
+    return (BX_DIFFUSE if m["kind"] == MATTE else BX_GLOSSY) | BX_REFLECTION
+
+
+def glass_sample(m, wo_local, u):
+    """Specular reflection / transmission of a smooth dielectric — pbrt-v3 §8.2.2-8.2.3, as the two lobes
+    SpecularReflection (f = R F / |cos|) and SpecularTransmission (f = T (1 - F) [eta_i^2/eta_t^2] / |cos|).
+    -> dict(reflect mask, wi, f, pdf, type, tir mask, fresnel F of the chosen lobe)."""
+    wo = f64(wo_local)
+    u = f64(u)
+    n = len(wo)
+    eta = float(np.float32(m["c"]))
+    R, T = _spec(m["a"]), _spec(m["b"])
+    fr_wo = fresnel_dielectric(wo[:, 2], 1.0, eta)
+    wt, tir = snell(wo, 1.0, eta)
+    with np.errstate(all="ignore"):
+        fr_wt = fresnel_dielectric(wt[:, 2], 1.0, eta)
+        f_r = R[None, :] * (fr_wo / np.abs(wo[:, 2]))[:, None]
+        f_t = T[None, :] * ((1.0 - fr_wt) / np.abs(wt[:, 2]))[:, None]
+    if not _on("no_eta2_transmission"):
+        e = np.where(wo[:, 2] > 0, 1.0 / eta, eta)  # eta_i / eta_t along the path
+        f_t = f_t * (e * e)[:, None]
+    if _on("lobe_choice_uniform"):
+        refl = u[:, 0] < 0.5
+        pdf = np.full(n, 0.5)
+    else:  # one Fresnel-weighted lobe (pbrt-v3 §8.2.4 FresnelSpecular, sampled in §14.1.3)
+        refl = u[:, 0] < fr_wo
+        pdf = np.where(refl, fr_wo, 1.0 - fr_wo)
+    wi = np.where(refl[:, None], wo * np.array([-1.0, -1.0, 1.0]), wt)
+    f = np.where(refl[:, None], f_r, f_t)
+    typ = np.where(refl, BX_SPECULAR | BX_REFLECTION, BX_SPECULAR | BX_TRANSMISSION)
+    none = ~refl & tir
+    wi[none] = 0
+    f[none] = 0
+    return dict(reflect=refl, wi=wi, f=f, pdf=np.where(none, 0.0, pdf), type=np.where(none, 0, typ), tir=tir, none=none,
+                fresnel=np.where(refl, fr_wo, fr_wt), sin_t=sin_theta_t(wo[:, 2], 1.0, eta))
+
+
+# ----------------------------------------------------------------------------- lights
+def _apply_point(m, p):
+    m = f64(m)
+    return f64(p) @ m[:3, :3].T + m[:3, 3]
+
+
+def shadow_ray(p, ng, p1):
+    """The ray from a surface point towards p1: origin moved off the surface, direction p1 - origin (not normalised),
+    t_max 0.9999 (pbrt-v3 §3.9.5 Interaction::SpawnRayTo with 1 - ShadowEpsilon; the origin offset follows the ledger)."""
+    p, ng, p1 = f64(p), f64(ng), f64(p1)
+    if _on("fixed_offset"):
+        side = np.where(dot(p1 - p, ng) > 0, 1.0, -1.0)
+        o = p + 1e-3 * side[:, None] * ng
+    else:
+        o = p.copy()  # pbrt offsets by the error bound of p, which is zero for a point given exactly
+    return o, p1 - o, 0.9999
+
+
+def spot_falloff(cos_theta, total_deg, falloff_deg):
+    """pbrt-v3 §12.3.1 SpotLight::Falloff: 0 outside the cone, 1 inside the falloff start, (delta^2)^2 between."""
+    ct, cf = np.cos(np.radians(total_deg)), np.cos(np.radians(falloff_deg))
+    d = np.clip((f64(cos_theta) - ct) / (cf - ct), 0.0, 1.0)
+    return np.where(cos_theta < ct, 0.0, d**4)
+
+
+def light_sample(light, index, p, ng, u):
+    """Light::Sample_Li for n surface points — pbrt-v3 §12.3 (point), §12.3.1 (spot), §12.4 (distant), §12.5 + §14.2.2
+    (diffuse area light sampled by area, pdf converted to solid angle: d^2 / (|cos| A)).
+    `light`: dict(kind, l2w 4x4, I or L, and total/falloff degrees | w | size).
+    -> dict(l, li, pdf, has_vis, area_light, p1, ray_o, ray_d, t_max, plus `dist`, `cos_light`, `cos_spot` for conditioning)."""
+    p, ng, u = f64(p), f64(ng), f64(u)
+    n = len(p)
+    kind = light["kind"]
+    out = dict(area_light=np.full(n, -1.0), pdf=np.ones(n), has_vis=np.ones(n))
+    if kind in (POINT, SPOT):
+        pos = _apply_point(light["l2w"], np.zeros(3))
+        to = pos[None, :] - p
+        d = np.linalg.norm(to, axis=1)
+        l = to / d[:, None]
+        inten = f64(np.asarray(light["I"], dtype=np.float32))
+        li = inten[None, :] / (d if _m("li_inverse_distance") else d * d)[:, None]
+        if kind == SPOT:
+            w2l = np.linalg.inv(f64(light["l2w"]))
+            cos_spot = normalize((-l) @ w2l[:3, :3].T)[:, 2]
+            li = li * spot_falloff(cos_spot, light["total"], light["falloff"])[:, None]
+            out["cos_spot"] = cos_spot
+            if _on("spot_no_tester_when_black"):
+                out["has_vis"] = (li.max(axis=1) > 0).astype(np.float64)
+        out.update(l=l, li=li, p1=np.broadcast_to(pos, (n, 3)).copy(), dist=d)
+    elif kind == DISTANT:
+        w = f64(np.asarray(light["w"], dtype=np.float32))
+        reach = 1e4 if _on("distant_fixed_reach") else 2.0 * DISTANT_WORLD_RADIUS
+        out.update(l=np.broadcast_to(w, (n, 3)).copy(), li=np.broadcast_to(f64(np.asarray(light["L"], dtype=np.float32)), (n, 3)).copy(),
+                   p1=p + reach * w[None, :], dist=np.full(n, reach))
+    else:
+        sx, sy = (float(np.float32(s)) for s in light["size"])
+        local = np.stack([(u[:, 0] - 0.5) * sx, np.zeros(n), (u[:, 1] - 0.5) * sy], axis=-1)
+        ps = _apply_point(light["l2w"], local)
+        nl = f64(light["l2w"])[:3, :3] @ np.array([0.0, -1.0, 0.0])  # rigid transform: normals rotate like vectors
+        to = ps - p
+        d = np.linalg.norm(to, axis=1)
+        wi = to / d[:, None]
+        cos_l = -(wi @ nl)
+        radiance = f64(np.asarray(light["L"], dtype=np.float32))
+        with np.errstate(all="ignore"):
+            pdf = d * d / (sx * sy) if _m("rect_pdf_without_cos") else d * d / (np.abs(cos_l) * sx * sy)
+        out.update(l=wi, li=np.where((cos_l > 0)[:, None], radiance[None, :], 0.0), pdf=pdf, p1=ps, dist=d, cos_light=cos_l,
+                   area_light=np.full(n, float(index)))
+    out["ray_o"], out["ray_d"], out["t_max"] = shadow_ray(p, ng, out["p1"])
+    return out
+
+
+def polygon_irradiance(p, n, verts):
+    """Irradiance at p (normal n) from a polygon of unit radiance seen from its emitting side: Lambert's formula
+    E = 1/2 sum_i theta_i (gamma_i . n), theta_i the angle subtended by edge i and gamma_i the unit normal of the plane
+    through p and edge i (Lambert 1760; Arvo 1995, "Applications of irradiance tensors to the simulation of non-Lambertian phenomena", eq. 1).  Vertices in order; the sign is fixed by
+    taking the absolute value, valid while the whole polygon lies above the horizon of n."""
+    p, n = f64(p), f64(n)
+    v = normalize(f64(verts) - p)
+    e = 0.0
+    for i in range(len(v)):
+        a, b = v[i], v[(i + 1) % len(v)]
+        theta = np.arccos(np.clip(a @ b, -1.0, 1.0))
+        gamma = np.cross(a, b)
+        e += theta * (gamma / np.linalg.norm(gamma)) @ n
+    return abs(0.5 * e)
+
+
+# ----------------------------------------------------------------------------- directional albedo
+def directional_albedo(m, cos_o, n_mu=1024, n_phi=512):
+    """rho(wo) = integral of f(wo, wi) |cos theta_i| d wi over wo's hemisphere by the midpoint rule over (mu = cos theta_i, phi),
+    with mu = t^2 so that the cells crowd towards grazing wi less than towards the lobe — pbrt-v3 §8.1.1 (rho_hd).  (3,) RGB.
+    At the default grid the result is within 7e-5 of the 4096 x 2048 grid's for every material and angle the tests use
+    (alpha >= 0.09), under a fiftieth of the standard error it is compared with."""
+    cos_o = float(cos_o)
+    wo = np.array([[np.sqrt(1.0 - cos_o * cos_o), 0.0, cos_o]])
+    t = (np.arange(n_mu) + 0.5) / n_mu
+    mu, dmu = t * t, 2.0 * t / n_mu
+    phi = (np.arange(n_phi) + 0.5) * (2.0 * np.pi / n_phi)
+    total = np.zeros(3)
+    for k in range(0, n_mu, 64):  # in slabs: the full grid at once is 2 M directions x several temporaries
+        m_, dm_ = mu[k : k + 64, None], dmu[k : k + 64, None]
+        s = np.sqrt(1.0 - m_ * m_)
+        wi = np.stack([(s * np.cos(phi)[None, :]).ravel(), (s * np.sin(phi)[None, :]).ravel(), np.broadcast_to(m_, (len(m_), n_phi)).ravel()], axis=-1)
+        f = lobe_f_local(m, np.broadcast_to(wo, wi.shape), wi)
+        w = np.broadcast_to(dm_ * (2.0 * np.pi / n_phi), (len(m_), n_phi)).ravel()
+        if not _m("albedo_without_cos"):
+            w = w * wi[:, 2]
+        total += (f * w[:, None]).sum(axis=0)
+    return total

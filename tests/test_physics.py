@@ -1,0 +1,149 @@
+"""Shading against float64 physics, on the CPU oracle: BSDF lobes, lights and the Path estimator.
+
+Every other shading test asks whether the device equals the oracle; these ask whether the oracle (and, in
+tests/test_gpu_physics.py, the device) equals the published models, restated in float64 by tests/physics_ref.py from the
+textbook and not from our code.  Where the reference renderer knowingly differs, physics_ref.DEVIATIONS says so, and
+test_ledger_entry_is_live proves that each entry is needed; test_mutation_is_caught proves that a single misread term in
+the physics would be noticed.  Tolerances are measured (tools/physics_tolerances.py -> profiles/physics_tolerances.json):
+4 x the oracle's worst error on calibration seeds that these tests do not use.  Cases, inputs and figures: tests/physics_cases.py.
+"""
+import os
+import sys
+
+import pytest
+
+import physics_cases as K
+import physics_ref as P
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+Z_MAX = K.Z_MAX
+
+
+@pytest.fixture(scope="module")
+def be(oracle):
+    return K.OracleBackend(oracle)
+
+
+@pytest.mark.parametrize("case_id", list(K.deterministic_cases()))
+def test_stage_or_estimator_matches_physics(be, case_id):
+    """Bsdf::f / sample_f per material (orthonormal frame, and ns != ng), Light::sample_li per kind, Path::li at depth 1 under a
+    point, spot and distant light and the exact furnaces: every figure within its measured tolerance, the zero / no-sample
+    / flag patterns exactly as float64 predicts, at most 5 % of a batch excluded."""
+    K.check_deterministic(be, case_id)
+
+
+@pytest.mark.parametrize("name", list(K.mc_cases()))
+def test_estimator_mean_matches_physics(be, name):
+    """Monte-Carlo cases (Uniform sampler, fixed seed, N from the tolerance file): the furnace mean against B x the
+    directional albedo by quadrature (or B for the R = T = 1 pane), the same with a light below the floor, and a Lambert
+    floor under the rectangular light against Lambert's polygon formula — within 4 standard errors."""
+    K.check_monte_carlo(be, name)
+
+
+def test_light_below_the_floor_shifts_the_draws(be):
+    """Quirk 4, per sample: the unused light consumes two dimensions."""
+    r = K.run_dimension_shift(be)
+    assert r["shift_mismatch"] == 0 and r["shift_rows_differing"] > 200, r
+
+
+def _figure(be, where):
+    case_id, figure = where
+    if case_id == "estimator":
+        if figure == "emitter_through_pane":
+            r = K.run_emitter_through_pane(be)
+            assert 0.3 < r["lit_share"] < 0.7
+            return r["emission_rel"], 2.0**-20  # beta and beta^2 Le take three f32 roundings
+        r = K.run_dimension_shift(be)
+        return float(r["shift_mismatch"]), 0.0
+    return K.run_case(be, case_id)[figure], (K.tolerance(case_id, figure) if K.is_toleranced(figure) else 0.0)
+
+
+@pytest.mark.parametrize("key", [d["key"] for d in P.DEVIATIONS])
+def test_ledger_entry_is_live(be, key):
+    """With the entry on, its figure passes; with the entry off — the textbook expected — the same figure fails.  So no
+    entry can hide a bug: the day the reference's behaviour and the textbook's coincide for these inputs, this fails."""
+    entry = next(d for d in P.DEVIATIONS if d["key"] == key)
+    value, tol = _figure(be, entry["live"])
+    assert value <= tol, (key, value, tol)
+    with P.textbook(key):
+        off, _ = _figure(be, entry["live"])
+    print(key, entry["live"], "on", value, "off", off, "tolerance", tol)
+    assert off > max(tol, 0.0) and off > 10 * value, (key, off, tol)
+
+
+MUTATION_CASES = {
+    "schlick_exponent_4": ("bsdf/glossy-0.3/ortho", "f_rel"),
+    "oren_nayar_030": ("bsdf/oren-nayar-0.349/ortho", "f_rel"),
+    "g_dropped": ("bsdf/metal-0.2/ortho", "f_rel"),
+    "pdf_without_jacobian": ("bsdf/metal-0.2/ortho", "s_pdf_rel"),
+    "albedo_without_cos": ("mc", "furnace/metal-0.2/45"),
+    "fresnel_rpar_swapped_eta": ("bsdf/glass-1.5/ortho", "s_fresnel_abs"),
+    "li_inverse_distance": ("light/point", "li_rel"),
+    "rect_pdf_without_cos": ("light/rect", "pdf_rel"),
+    "snell_eta_inverted": ("bsdf/glass-1.5/ortho", "s_wi_abs"),
+    "sigma_to_degrees": ("bsdf/oren-nayar-1.0/ortho", "f_rel"),
+}
+
+
+@pytest.mark.parametrize("name", P.MUTATIONS)
+def test_mutation_is_caught(be, name):
+    """The power check: one single-term mistake planted in the REFERENCE must push its comparison past 10 x the tolerance
+    in use (for the Monte-Carlo case: past 10 x the 4 standard errors)."""
+    case_id, figure = MUTATION_CASES[name]
+    with P.mutated(name):
+        if case_id == "mc":
+            spec = K.mc_cases()[figure]
+            fig = K.mc_figures(K.mc_samples(be, spec, K.tolerances()["monte_carlo"][figure]["n"]), K.mc_truth(spec))
+            value, tol = abs(fig["z"]), Z_MAX
+        else:
+            value, tol = K.run_case(be, case_id)[figure], K.tolerance(case_id, figure)
+    print(name, case_id, figure, value, tol)
+    assert value >= 10 * tol, (name, value, tol)
+
+
+def test_every_mutation_has_a_case():
+    assert set(MUTATION_CASES) == set(P.MUTATIONS) and len(P.MUTATIONS) >= 10
+
+
+def test_tolerance_file_is_current(be):
+    """profiles/physics_tolerances.json covers exactly today's cases with tolerance = 4 x worst (at least one f32 ulp), and
+    one row, measured again on its calibration seeds, gives the recorded figures."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import physics_tolerances as T
+
+    doc = K.tolerances()
+    assert doc["margin"] == K.MARGIN == 4.0
+    want_rows = set()
+    for case_id in K.all_cases():
+        want_rows |= {f"{case_id}:{k}" for k in K.run_case(be, case_id) if K.is_toleranced(k)}
+    assert set(doc["rows"]) == want_rows
+    assert set(doc["monte_carlo"]) == set(K.mc_cases())
+    for key, row in doc["rows"].items():
+        assert row["tolerance"] == pytest.approx(K.adopt(row["worst"]), rel=1e-5), key
+        assert row["excluded"] <= K.MAX_EXCLUDED, key
+    for name, rec in doc["monte_carlo"].items():
+        assert rec["n"] & (rec["n"] - 1) == 0 and 256 <= rec["n"] <= 65536
+        assert abs(rec["z"]) <= 3 or rec.get("note"), name
+    case_id = "bsdf/metal-0.2/tilted"
+    for k, row in T.measure_row(be, case_id).items():
+        assert row["worst"] == pytest.approx(doc["rows"][f"{case_id}:{k}"]["worst"], rel=1e-4), k
+    rec = T.measure_mc(be, "rect/1")
+    assert rec["n"] == doc["monte_carlo"]["rect/1"]["n"] and rec["z"] == pytest.approx(doc["monte_carlo"]["rect/1"]["z"], abs=1e-3)
+
+
+def test_ledger_is_written_down():
+    """Every ledger entry cites the reference and its sentence stands in SURVEY's quirk ledger; the float64 reference does
+    not lean on the code it judges."""
+    with open(os.path.join(ROOT, "SURVEY.md")) as fh:
+        survey = fh.read()
+    keys = [d["key"] for d in P.DEVIATIONS]
+    assert len(set(keys)) == len(keys)
+    for d in P.DEVIATIONS:
+        assert ".rs:" in d["where"], d["key"]
+        assert d["sentence"] in survey, d["key"]
+    for q in (2, 4, 9, 11, 12, 13):
+        assert any(d["quirk"] == q for d in P.DEVIATIONS), q
+    with open(os.path.join(ROOT, "tests", "physics_ref.py")) as fh:
+        src = fh.read()
+    imports = [line.split()[1].split(".")[0] for line in src.splitlines() if line.startswith(("import ", "from "))]
+    assert sorted(imports) == ["contextlib", "numpy"]
