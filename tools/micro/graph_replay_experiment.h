@@ -2,11 +2,14 @@
 // tools/graph_tile_bench.py, profiles/r03_graph_tile.txt): what a hipGraph of a small job's ~40 dependent launches returns.
 // YK_GRAPH_REPLAY=N (read per call: the tool sets it after a plain warm-up call): the job's launches are captured into a graph once and the
 // graph is launched N times; the time of one replay goes to stderr.  Needs a job that enqueues without host synchronisation (one tile, or a
-// prepared list) whose buffers exist already.  Expanded inside render_tiles_impl (yk_render.cpp): uses its locals ctx, st, stats, cancel, kt, ev0.
+// prepared list) whose buffers exist already.  Expanded inside render_tiles_impl (yk_render.cpp): uses its locals ctx, rq (the request) and s (the submission).
 #pragma once
 #define YK_GRAPH_BEGIN \
     const int graph_replay = std::getenv("YK_GRAPH_REPLAY") ? std::atoi(std::getenv("YK_GRAPH_REPLAY")) : 0; /* read per call: the tool sets it after a plain warm-up call */ \
-    const bool capturing = graph_replay > 0 && stats != nullptr && !cancel; \
+    const hipStream_t st = s.st; \
+    KernelTimer& kt = s.kt; \
+    hipEvent_t& ev0 = s.frame_ev.a; \
+    const bool capturing = graph_replay > 0 && rq.stats != nullptr && !rq.cancel; \
     if (capturing) { \
         kt.on = false; \
         HIP_TRY(ctx, hipStreamSynchronize(st)); \

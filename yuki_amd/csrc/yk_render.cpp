@@ -7,6 +7,13 @@
 // samples; each batch runs raygen + max_depth x (trace, shade, shadow,
 // accumulate) without any host synchronisation — queue lengths live in device
 // memory and the persistent kernels read them there.
+//
+// Order of the file: the work buffers and run_bounces (one batch's bounce loop; yk_stages.cpp uses them too), the
+// interruption helpers, then one submission — a RenderRequest (what an entry point asks for), the plan made of it before
+// the device is touched (yk_render_plan.h: pixel offsets, accumulation rules, chunks, batch, work sets) and the phases
+// render_tiles_impl runs in order: check_and_plan, the hand-over from a caller's stream, grow_buffers, begin_call, per
+// chunk make_pixel_tables and per batch gate_on_cancel + enqueue_batch, the resolve, finish_call — then what yk_li and
+// yk_li_debug share (LiCall), and last the entry points in one extern "C" block.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,6 +27,7 @@
 #include <vector>
 
 #include "yk_film_call.h"
+#include "yk_render_plan.h"
 #include "yk_staging.h"
 #ifdef YK_EXPERIMENT_SORT  // timing builds only (tools/build_variant.sh sort -DYK_EXPERIMENT_SORT): DESIGN.md §9
 #include "../../tools/micro/ray_sort_experiment.h"
@@ -275,130 +283,80 @@ static bool wait_polling(yk_context* ctx, hipEvent_t done, hipStream_t st, yk_ca
     return fired;
 }
 
-// Integrator::render for a list of tiles.  tile_samples == nullptr: the plain film (all
-// samples of a pixel, mean stored).  Otherwise the accumulating film (integrators/mod.rs:
-// 146-161): one sample per pixel with global index tile_samples[t], raw value stored.
-// guides_res_x != 0: the guide pass (yk_render_guides) — a debug integrator's trace, one sample a pixel; d_out_rgb is then
-// a row-major film of yk_guide records, guides_res_x wide, written by k_guides instead of the shade and resolve kernels.
-// With d_ids (yk_render_guides_ids) k_guides_ids writes the yk_surface_id records there too, and d_out_rgb may be NULL.
-static yk_status render_tiles_impl(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler,
-                                   const yk_integrator_desc* integrator, const yk_tile* tiles, const uint16_t* tile_samples, size_t n_tiles,
-                                   void* d_out_rgb, void* stream, yk_render_stats* stats, yk_cancel_fn cancel, void* user,
-                                   const yk_tile_list* prepared = nullptr, uint32_t n_passes = 1, int64_t uniform_first_sample = -1,
-                                   uint32_t guides_res_x = 0, void* d_ids = nullptr) try {
-    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
-    YK_LOCK(ctx);
-    if (prepared) {
-        if (prepared->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "tile list was not created on this context's device");
-        tiles = prepared->tiles.data();
-        tile_samples = prepared->samples.empty() ? nullptr : prepared->samples.data();
-        n_tiles = prepared->tiles.size();
+// ------------------------------------------------------------------ what the entry points share
+// The four words of the error block, read back, as the call's verdict.
+static yk_status error_block_status(yk_context* ctx, const unsigned* words) {
+    if (words[YK_CTRL_ERR] & 1u) return fail(ctx, YK_ERR_STACK_OVERFLOW, "BVH traversal stack exceeded 64 entries (bvh.rs:174)");
+    return YK_OK;
+}
+
+// tiles -> pixel offsets (yk_render_plan.h); `too_many`: how this caller says that they exceed 32 bits
+static yk_status tile_offsets(yk_context* ctx, const yk_tile* tiles, size_t n_tiles, std::vector<uint32_t>& off, const char* too_many) {
+    switch (yk_plan::tile_ranges(tiles, n_tiles, off)) {
+        case yk_plan::TILES_OK: return YK_OK;
+        case yk_plan::TILES_TOO_MANY_PIXELS: return fail(ctx, YK_ERR_INVALID_ARGUMENT, too_many);
+        default: return fail(ctx, YK_ERR_INVALID_ARGUMENT, "Bounds2 with a dimension <= 0");
     }
-    if (!scene || !camera || !tiles || n_tiles == 0 || (!d_out_rgb && !(guides_res_x && d_ids))) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null argument");
-    if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "scene was not created on this context's device");
+}
+
+// ------------------------------------------------------------------ one render submission
+// Integrator::render for a list of tiles, as every render entry point asks for it: each fills in what it means.
+struct RenderRequest {
+    const yk_scene* scene = nullptr;
+    const yk_camera* camera = nullptr;
+    const yk_sampler_desc* sampler = nullptr;
+    const yk_integrator_desc* integrator = nullptr;
+    const yk_tile* tiles = nullptr;
+    size_t n_tiles = 0;
+    // NULL: the plain film (all samples of a pixel, mean stored).  Otherwise the accumulating film (integrators/mod.rs:
+    // 146-161): passes FilmTile.sample .. + n_passes - 1 of every tile, raw values stored pass-major.
+    const uint16_t* tile_samples = nullptr;
+    const yk_tile_list* list = nullptr;  // instead of the three above: a prepared list, its pixel table on the device already
+    uint32_t n_passes = 1;
+    int64_t uniform_first_sample = -1;  // >= 0: the accumulating film with this first sample index for every tile
+    void* d_out = nullptr;
+    // != 0: the guide pass (yk_render_guides) — a debug integrator's trace, one sample a pixel; d_out is then a row-major
+    // film of yk_guide records, guides_res_x wide, written by k_guides instead of the shade and resolve kernels.  With
+    // d_ids (yk_render_guides_ids) k_guides_ids writes the yk_surface_id records there too, and d_out may be NULL.
+    uint32_t guides_res_x = 0;
+    void* d_ids = nullptr;
+    void* stream = nullptr;
+    yk_render_stats* stats = nullptr;
+    yk_cancel_fn cancel = nullptr;
+    void* user = nullptr;
+};
+// what the tile entry points of the ABI pass through as they got it, in the ABI's order; the tiles are theirs to fill in
+static RenderRequest request_for(const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler, const yk_integrator_desc* integrator,
+                                 void* d_out_rgb, void* stream, yk_render_stats* stats, yk_cancel_fn cancel, void* user) {
+    RenderRequest rq;
+    rq.scene = scene;
+    rq.camera = camera;
+    rq.sampler = sampler;
+    rq.integrator = integrator;
+    rq.d_out = d_out_rgb;
+    rq.stream = stream;
+    rq.stats = stats;
+    rq.cancel = cancel;
+    rq.user = user;
+    return rq;
+}
+
+// The phases of a submission in the order render_tiles_impl runs them, over what they share.
+struct Submission {
+    yk_context* const ctx;
+    const RenderRequest& rq;
+    const yk_scene* const scene;
+    const yk_tile* tiles;  // the request's, or its prepared list's
+    const uint16_t* tile_samples;
+    size_t n_tiles;
+    std::vector<uint32_t> own_off;
+    const uint32_t* off = nullptr;  // n_tiles + 1 pixel offsets: the prepared list's, or own_off
+    const hipStream_t st;           // the render always runs on the context's own streams (render_tiles_impl: the hand-over)
+    yk_plan::RenderPlan plan;
     RenderParams prm;
-    yk_status ps = make_params(ctx, sampler, integrator, prm);
-    if (ps != YK_OK) return ps;
-    if (prm.integrator == YK_INTEGRATOR_PATH && prm.max_depth > YK_CTRL_MAX_DEPTH)
-        return fail(ctx, YK_ERR_INVALID_ARGUMENT, "max_depth too large");
-    (void)hipSetDevice(ctx->device);
-    {
-        yk_status cs = clear_cancel(ctx);
-        if (cs != YK_OK) return cs;
-    }
-    // The render always runs on the context's own streams; a caller's stream hands over to them
-    // and takes over again at the end (two event waits), so the work is ordered on it as if it
-    // had been launched there — and the main / side stream pair keeps its own hardware queues.
-    hipStream_t caller = (hipStream_t)stream;
-    hipStream_t st = ctx->stream;
-    if (caller) {
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_in, caller));
-        HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_in, 0));
-    }
-    struct HandBack {  // on every exit path: whatever was enqueued is ordered before the caller's next work
-        yk_context* c;
-        hipStream_t caller, st;
-        ~HandBack() {
-            if (!caller) return;
-            if (hipEventRecord(c->ev_out, st) == hipSuccess) (void)hipStreamWaitEvent(caller, c->ev_out, 0);
-        }
-    } hand_back{ctx, caller, st};
-
-    // tiles -> pixel ranges (assert!(tile_pixels.len() >= tile.bb.area()), integrators/mod.rs:131)
-    std::vector<uint32_t> off(n_tiles + 1, 0);
-    uint64_t total_px = 0;
-    for (size_t t = 0; t < n_tiles; ++t) {
-        if (tiles[t].x0 >= tiles[t].x1 || tiles[t].y0 >= tiles[t].y1) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "Bounds2 with a dimension <= 0");
-        total_px += (uint64_t)(tiles[t].x1 - tiles[t].x0) * (uint64_t)(tiles[t].y1 - tiles[t].y0);
-        if (total_px > 0xFFFFFFFFull) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "too many pixels in one call");
-        off[t + 1] = (uint32_t)total_px;
-    }
-    // accumulating film: FilmTile.sample per tile (tile_samples), or one sample index shared by all tiles
-    const bool accumulating = tile_samples != nullptr || uniform_first_sample >= 0;
-    if (tile_samples && uniform_first_sample >= 0) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "an accumulating tile list carries its own sample indices");
-    if (n_passes == 0 || n_passes > 0xFFFFu || (!accumulating && n_passes != 1)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "bad number of passes");
-    // samples rendered per pixel by this call: the accumulating film renders passes FilmTile.sample .. + n_passes - 1
-    const uint32_t spp = accumulating ? n_passes : prm.sampler.spp;
-    prm.spe = spp;
-    if (accumulating) {
-        // render_manager.rs:135-143 queues samples 0 .. spp-1 of a tile and nothing else; an index beyond that is
-        // outside the samplers' domain (the stratified permutation walks cycles of [0, spp) and need not terminate)
-        for (size_t t = 0; tile_samples && t < n_tiles; ++t)
-            if ((uint64_t)tile_samples[t] + n_passes > prm.sampler.spp)
-                return fail(ctx, YK_ERR_INVALID_ARGUMENT, "FilmTile.sample (+ passes) beyond the sampler's samples per pixel");
-        if (uniform_first_sample >= 0 && (uint64_t)uniform_first_sample + n_passes > prm.sampler.spp)
-            return fail(ctx, YK_ERR_INVALID_ARGUMENT, "first_sample (+ passes) beyond the sampler's samples per pixel");
-        if (uniform_first_sample >= 0) prm.sample_base = (uint32_t)uniform_first_sample;
-    }
-    const bool sample_table = tile_samples != nullptr;  // a per-pixel table of sample indices (absent: prm.sample_base for every pixel)
-    // chunk so that sample ids fit u32 and the sample buffer stays under the cap
-    uint64_t max_px_chunk = std::min<uint64_t>(0xFFFFFFF0ull / spp, (uint64_t)ctx->sample_buf_cap / (16ull * spp));
-    if (max_px_chunk == 0) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "sample_buf_cap too small for one pixel");
-
     DevCamera cam;
-    std::memcpy(cam.c2w, camera->camera_to_world, 64);
-    std::memcpy(cam.r2c, camera->raster_to_camera, 64);
-
-    const bool is_path = prm.integrator == YK_INTEGRATOR_PATH;
-    // Work is cut into batches of <= batch_paths camera samples.  With streams == 2
-    // batches alternate between two work sets / HIP streams, so the latency-bound
-    // tail launches of one batch (late bounces, few rays) run beside the bulk
-    // launches of the other.  A job that fits one batch stays on one work set: splitting it
-    // gains nothing once the side stream overlaps shadow rays with the next bounce (measured).
-    const uint64_t total_work = total_px * spp;
-    size_t batch = (size_t)std::min<uint64_t>((uint64_t)ctx->batch_paths, total_work);
-    const int n_ws = (ctx->streams >= 2 && is_path && !stream && total_work > batch) ? 2 : 1;
-    {
-        // keep the per-batch work buffers (148 + 53*n_lights bytes per path) within half of the free HBM
-        size_t free_b = 0, total_b = 0;
-        if (batch > ctx->ws[0].cap_paths && hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            const size_t per_path = (148 + 53 * (size_t)std::max(1u, scene->n_lights) + 36) * (size_t)n_ws;
-            const size_t fit = (free_b / 2) / per_path;
-            if (fit >= 65536 && batch > fit) batch = fit;
-        }
-    }
-    if (n_ws == 2 && !ctx->ws[1].stream) {  // the second work set's stream pair, on first use
-        HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->ws[1].stream, hipStreamNonBlocking));
-        HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->ws[1].side, hipStreamNonBlocking));
-    }
-    for (int w = 0; w < n_ws; ++w) {
-        yk_status wb = ensure_work_buffers(ctx, ctx->ws[w], batch, scene->n_lights, scene->n_delta_lights);
-        if (wb != YK_OK) return wb;
-        if ((wb = ensure_spill(ctx, ctx->ws[w])) != YK_OK) return wb;
-    }
-    HIP_TRY(ctx, ctx->tiles.ensure(n_tiles * sizeof(yk_tile)));
-    HIP_TRY(ctx, ctx->tile_off.ensure((n_tiles + 1) * 4));
-    if (!is_path && prm.integrator == YK_INTEGRATOR_BVH_INTERSECTIONS) HIP_TRY(ctx, ctx->stats4.ensure(batch * 16));
-
-    unsigned long long* counters = ctx->counters.as<unsigned long long>();
-    HIP_TRY(ctx, hipMemsetAsync(counters, 0, YK_COUNTER_BYTES, st));  // the error block with it: stack-overflow flag, interruption word
-    unsigned* errblk = error_block(ctx);
-    prm.cancel = cancel_ref(ctx);
+    bool is_path = false;
     KernelTimer kt;
-    kt.ctx = ctx;
-    // per-kernel HIP-event timings: two event records per launch and one elapsed-time query per
-    // kernel — not for jobs so small (a tile, a few tiles) that this bookkeeping is the cost
-    kt.on = stats != nullptr && ctx->time_kernels != 0 && (total_work >= (1u << 20) || ctx->time_kernels > 1);
     struct EventPair {  // destroyed on every exit path
         hipEvent_t a = nullptr, b = nullptr;
         ~EventPair() {
@@ -406,336 +364,331 @@ static yk_status render_tiles_impl(yk_context* ctx, const yk_scene* scene, const
             if (b) (void)hipEventDestroy(b);
         }
     } frame_ev;
-    hipEvent_t& ev0 = frame_ev.a;
-    hipEvent_t& ev1 = frame_ev.b;
-    if (stats) {
-        HIP_TRY(ctx, hipEventCreate(&ev0));
-        HIP_TRY(ctx, hipEventCreate(&ev1));
-        HIP_TRY(ctx, hipEventRecord(ev0, st));
-    }
-#ifdef YK_EXPERIMENT_GRAPH  // timing builds only (tools/micro/graph_replay_experiment.h, DESIGN.md §9)
-    YK_GRAPH_BEGIN
-#endif
     uint32_t n_batches = 0, n_trace = 0, n_shadow = 0;
-    float* out = reinterpret_cast<float*>(d_out_rgb);
+    // the chunk in progress
+    float4* sample_buf = nullptr;
+    uint32_t* pixel_xy = nullptr;
+    uint32_t* pixel_sample = nullptr;
+    int which = 0;
+    bool ws_busy[2] = {false, false};
 
-    size_t t_begin = 0;
-    while (t_begin < n_tiles) {
-        size_t t_end = t_begin;
-        while (t_end < n_tiles && (uint64_t)(off[t_end + 1] - off[t_begin]) <= max_px_chunk) ++t_end;
-        if (t_end == t_begin) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "a single tile exceeds sample_buf_cap");
-        const uint32_t px0 = off[t_begin], npx = off[t_end] - off[t_begin];
-        HIP_TRY(ctx, ctx->sample_buf.ensure((size_t)npx * spp * 16));
-        float4* sample_buf = ctx->sample_buf.as<float4>();
-        uint32_t* pixel_xy = nullptr;
-        uint32_t* pixel_sample = nullptr;
-        const uint16_t* d_tile_sample = nullptr;
-        if (prepared) {  // the pixel table of the whole list is already on the device
-            pixel_xy = prepared->pixel_xy.as<uint32_t>() + px0;
-            if (sample_table) pixel_sample = prepared->pixel_sample.as<uint32_t>() + px0;
-        } else if (t_end - t_begin == 1) {  // one tile (the reference's per-tile call): it travels as a kernel argument
-            HIP_TRY(ctx, ctx->pixel_xy.ensure((size_t)npx * 4));
-            pixel_xy = ctx->pixel_xy.as<uint32_t>();
-            if (sample_table) {
-                HIP_TRY(ctx, ctx->pixel_sample.ensure((size_t)npx * 4));
-                pixel_sample = ctx->pixel_sample.as<uint32_t>();
-            }
-            launch_pixel_table_one(st, tiles[t_begin], npx, pixel_xy, sample_table ? tile_samples[t_begin] : 0u, pixel_sample);
-        } else {
-        std::vector<uint32_t> loc(t_end - t_begin + 1);
-        for (size_t t = t_begin; t <= t_end; ++t) loc[t - t_begin] = off[t] - px0;
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->tiles.p, tiles + t_begin, (t_end - t_begin) * sizeof(yk_tile), hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->tile_off.p, loc.data(), loc.size() * 4, hipMemcpyHostToDevice, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));  // `loc` is a stack-lifetime staging buffer
-        HIP_TRY(ctx, ctx->pixel_xy.ensure((size_t)npx * 4));
+    Submission(yk_context* c, const RenderRequest& r) : ctx(c), rq(r), scene(r.scene), tiles(r.tiles), tile_samples(r.tile_samples), n_tiles(r.n_tiles), st(c->stream) {}
+    unsigned long long* counters() const { return ctx->counters.as<unsigned long long>(); }
+
+    // the arguments, then — nothing of it touches the device — the plan
+    yk_status check_and_plan() {
+        if (rq.list) {
+            if (rq.list->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "tile list was not created on this context's device");
+            tiles = rq.list->tiles.data();
+            tile_samples = rq.list->samples.empty() ? nullptr : rq.list->samples.data();
+            n_tiles = rq.list->tiles.size();
+        }
+        if (!scene || !rq.camera || !tiles || n_tiles == 0 || (!rq.d_out && !(rq.guides_res_x && rq.d_ids))) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null argument");
+        if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "scene was not created on this context's device");
+        yk_status rc = make_params(ctx, rq.sampler, rq.integrator, prm);
+        if (rc != YK_OK) return rc;
+        is_path = prm.integrator == YK_INTEGRATOR_PATH;
+        if (is_path && prm.max_depth > YK_CTRL_MAX_DEPTH) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "max_depth too large");
+        (void)hipSetDevice(ctx->device);
+        if ((rc = clear_cancel(ctx)) != YK_OK) return rc;
+        if (!rq.list && (rc = tile_offsets(ctx, tiles, n_tiles, own_off, "too many pixels in one call")) != YK_OK) return rc;
+        off = rq.list ? rq.list->off.data() : own_off.data();  // a list's were validated when it was made
+        const char* refusal = plan.set_samples(tile_samples, n_tiles, rq.uniform_first_sample, rq.n_passes, prm.sampler.spp);
+        if (!refusal) refusal = plan.set_chunks(off, n_tiles, (uint64_t)ctx->sample_buf_cap);
+        if (refusal) return fail(ctx, YK_ERR_INVALID_ARGUMENT, refusal);
+        plan.set_batch((uint64_t)ctx->batch_paths, ctx->streams, is_path, rq.stream != nullptr);
+        prm.spe = plan.spp;
+        prm.sample_base = plan.sample_base;
+        std::memcpy(cam.c2w, rq.camera->camera_to_world, 64);
+        std::memcpy(cam.r2c, rq.camera->raster_to_camera, 64);
+        return YK_OK;
+    }
+
+    yk_status grow_buffers() {
+        size_t free_b = 0, total_b = 0;
+        if (plan.batch > ctx->ws[0].cap_paths && hipMemGetInfo(&free_b, &total_b) == hipSuccess) plan.clamp_batch_to_hbm(free_b, scene->n_lights);
+        if (plan.n_ws == 2 && !ctx->ws[1].stream) {  // the second work set's stream pair, on first use
+            HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->ws[1].stream, hipStreamNonBlocking));
+            HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->ws[1].side, hipStreamNonBlocking));
+        }
+        for (int w = 0; w < plan.n_ws; ++w) {
+            yk_status wb = ensure_work_buffers(ctx, ctx->ws[w], plan.batch, scene->n_lights, scene->n_delta_lights);
+            if (wb != YK_OK) return wb;
+            if ((wb = ensure_spill(ctx, ctx->ws[w])) != YK_OK) return wb;
+        }
+        HIP_TRY(ctx, ctx->tiles.ensure(n_tiles * sizeof(yk_tile)));
+        HIP_TRY(ctx, ctx->tile_off.ensure((n_tiles + 1) * 4));
+        if (prm.integrator == YK_INTEGRATOR_BVH_INTERSECTIONS) HIP_TRY(ctx, ctx->stats4.ensure(plan.batch * 16));
+        return YK_OK;
+    }
+
+    yk_status begin_call() {
+        HIP_TRY(ctx, hipMemsetAsync(counters(), 0, YK_COUNTER_BYTES, st));  // the error block with it: stack-overflow flag, interruption word
+        prm.cancel = cancel_ref(ctx);
+        kt.ctx = ctx;
+        // per-kernel HIP-event timings: two event records per launch and one elapsed-time query per
+        // kernel — not for jobs so small (a tile, a few tiles) that this bookkeeping is the cost
+        kt.on = rq.stats != nullptr && ctx->time_kernels != 0 && (plan.total_work >= (1u << 20) || ctx->time_kernels > 1);
+        if (rq.stats) {
+            HIP_TRY(ctx, hipEventCreate(&frame_ev.a));
+            HIP_TRY(ctx, hipEventCreate(&frame_ev.b));
+            HIP_TRY(ctx, hipEventRecord(frame_ev.a, st));
+        }
+        return YK_OK;
+    }
+
+    // the chunk's pixel table (and, with a sample table, its per-pixel sample indices) on the device, by one of three routes
+    yk_status make_pixel_tables(const yk_plan::Chunk& c) {
+        const bool sample_table = plan.sample_table;
+        const size_t nt = c.t_end - c.t_begin;
+        pixel_sample = nullptr;
+        if (rq.list) {  // the pixel table of the whole list is already on the device
+            pixel_xy = rq.list->pixel_xy.as<uint32_t>() + c.px0;
+            if (sample_table) pixel_sample = rq.list->pixel_sample.as<uint32_t>() + c.px0;
+            return YK_OK;
+        }
+        HIP_TRY(ctx, ctx->pixel_xy.ensure((size_t)c.npx * 4));
         pixel_xy = ctx->pixel_xy.as<uint32_t>();
         if (sample_table) {
-            HIP_TRY(ctx, ctx->tile_sample.ensure((t_end - t_begin) * 2));
-            HIP_TRY(ctx, ctx->pixel_sample.ensure((size_t)npx * 4));
-            HIP_TRY(ctx, hipMemcpyAsync(ctx->tile_sample.p, tile_samples + t_begin, (t_end - t_begin) * 2, hipMemcpyHostToDevice, st));
-            d_tile_sample = ctx->tile_sample.as<uint16_t>();
+            HIP_TRY(ctx, ctx->pixel_sample.ensure((size_t)c.npx * 4));
             pixel_sample = ctx->pixel_sample.as<uint32_t>();
         }
-        launch_pixel_table(st, ctx->tiles.as<yk_tile>(), ctx->tile_off.as<uint32_t>(), (uint32_t)(t_end - t_begin), npx, pixel_xy, d_tile_sample, pixel_sample);
+        if (nt == 1) {  // one tile (the reference's per-tile call): it travels as a kernel argument
+            launch_pixel_table_one(st, tiles[c.t_begin], c.npx, pixel_xy, sample_table ? tile_samples[c.t_begin] : 0u, pixel_sample);
+            return YK_OK;
         }
+        std::vector<uint32_t> loc(nt + 1);
+        for (size_t t = c.t_begin; t <= c.t_end; ++t) loc[t - c.t_begin] = off[t] - c.px0;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->tiles.p, tiles + c.t_begin, nt * sizeof(yk_tile), hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->tile_off.p, loc.data(), loc.size() * 4, hipMemcpyHostToDevice, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));  // `loc` is a stack-lifetime staging buffer
+        const uint16_t* d_tile_sample = nullptr;
+        if (sample_table) {
+            HIP_TRY(ctx, ctx->tile_sample.ensure(nt * 2));
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->tile_sample.p, tile_samples + c.t_begin, nt * 2, hipMemcpyHostToDevice, st));
+            d_tile_sample = ctx->tile_sample.as<uint16_t>();
+        }
+        launch_pixel_table(st, ctx->tiles.as<yk_tile>(), ctx->tile_off.as<uint32_t>(), (uint32_t)nt, c.npx, pixel_xy, d_tile_sample, pixel_sample);
+        return YK_OK;
+    }
+
+    // An interruptible job of many batches is not enqueued all at once: a work set takes its next batch when its
+    // previous one has finished (the other work set's batch keeps the GPU busy meanwhile), the predicate is polled
+    // during the wait, and an interruption has at most two batches' launches left to drain — each of them an empty
+    // launch of a few microseconds, but a 4K x 256 spp job holds 1300 of them.
+    yk_status gate_on_cancel(WorkSet& ws, uint64_t w0, uint64_t work) {
+        if (!rq.cancel) return YK_OK;
+        bool fired = ws_busy[which] && poll_until(ctx, ws.ev_batch, rq.cancel, rq.user);
+        if (!fired && rq.cancel(rq.user)) {
+            raise_cancel(ctx);
+            fired = true;
+        }
+        if (!fired) return YK_OK;
+        // what is already enqueued drains at once
+        const double t0 = g_debug_cancel ? now_ms() : 0.0;
+        (void)hipStreamSynchronize(st);
+        const double t1 = g_debug_cancel ? now_ms() : 0.0;
+        if (plan.n_ws == 2) (void)hipStreamSynchronize(ctx->ws[1].stream);
+        if (g_debug_cancel) {
+            unsigned words[4] = {0, 0, 0, 0};
+            (void)hipMemcpy(words, error_block(ctx), sizeof words, hipMemcpyDeviceToHost);
+            std::fprintf(stderr, "[yk cancel] drain: stream0 %.3f ms, stream1 %.3f ms, batch %llu of %llu, device word %u\n", t1 - t0, now_ms() - t1,
+                         (unsigned long long)(w0 / plan.batch), (unsigned long long)((work + plan.batch - 1) / plan.batch), words[YK_CTRL_CANCELLED]);
+        }
+        return fail(ctx, YK_ERR_CANCELLED, "cancelled by early_termination_predicate");
+    }
+
+    // raygen for samples [w0, w0 + n) of the chunk, then the integrator family's kernels, on `bs`
+    yk_status enqueue_batch(WorkSet& ws, hipStream_t bs, uint64_t w0, uint32_t n) {
+        unsigned* ctrl = ws.ctrl.as<unsigned>();
+        unsigned* bc0 = ctrl + YK_CTRL_BOUNCE(0);
+        unsigned* errblk = error_block(ctx);
+        const unsigned spill_stride = trace_grid(ctx) * trace_block_size();
+        PathBuffers pc = path_buffers(ws, 0);
+        HIP_TRY(ctx, hipMemsetAsync(ctrl, 0, YK_CTRL_WORDS * 4, bs));
+        // Path, camera rays traced by the packet kernel: the lean camera bounce (yk_device.h, YK_CTRL_CAM_O)
+        const bool lean = is_path && prm.max_depth > 0 && packet_kernel_traces_bounce(ctx, scene, 0);
+        launch_raygen(bs, cam, prm, pixel_xy, pixel_sample, w0, n, pc, sample_buf, bc0, lean ? reinterpret_cast<float4*>(ctrl + YK_CTRL_CAM_O) : nullptr,
+                      ctx->pixel_aux.as<uint4>());
+        ++n_batches;
+        if (is_path) {
+            run_bounces(ctx, ws, bs, scene, prm, pixel_xy, pixel_sample, sample_buf, kt, counters(), true, n, (uint32_t)w0, lean, &n_shadow);
+            n_trace += prm.max_depth;
+            return YK_OK;
+        }
+        ++n_trace;
+        int e = kt.begin(bs);
+        if (prm.integrator == YK_INTEGRATOR_WHITTED) {  // one lane per camera sample runs the whole recursion (whitted.rs:74-181)
+            launch_whitted(bs, trace_grid(ctx), scene->dev, prm, pixel_xy, pixel_sample, pc, n, sample_buf, ws.spill.as<uint2>(), spill_stride, errblk, counters());
+            kt.end(e, 0, bs);
+            return YK_OK;
+        }
+        const bool want_stats = prm.integrator == YK_INTEGRATOR_BVH_INTERSECTIONS;
+        launch_trace_closest(bs, trace_grid(ctx), dev_scene_for(scene, n), pc.rayO, pc.rayD, nullptr, bc0, bc0 + YK_CTRL_HEAD, ws.hit.as<int>(), nullptr,
+                             want_stats ? ctx->stats4.as<uint4>() : nullptr, ws.spill.as<uint2>(), spill_stride, errblk, counters());
+        kt.end(e, 0, bs);
+        if (rq.guides_res_x && rq.d_ids)
+            launch_guides_ids(bs, scene->dev, pc, ws.hit.as<int>(), n, pixel_xy, rq.guides_res_x, reinterpret_cast<float4*>(rq.d_out), reinterpret_cast<uint4*>(rq.d_ids));
+        else if (rq.guides_res_x)
+            launch_guides(bs, scene->dev, pc, ws.hit.as<int>(), n, pixel_xy, rq.guides_res_x, reinterpret_cast<float4*>(rq.d_out));
+        else
+            launch_debug_shade(bs, scene->dev, prm.integrator, pc, ws.hit.as<int>(), ctx->stats4.as<uint4>(), n, sample_buf);
+        return YK_OK;
+    }
+
+    yk_status render_chunk(const yk_plan::Chunk& c) {
+        const uint32_t spp = plan.spp;
+        HIP_TRY(ctx, ctx->sample_buf.ensure((size_t)c.npx * spp * 16));
+        sample_buf = ctx->sample_buf.as<float4>();
+        yk_status rc = make_pixel_tables(c);
+        if (rc != YK_OK) return rc;
         // the pixel's share of every camera sample's sampler start, once per pixel (yk_rng.h, PixelSampler)
-        HIP_TRY(ctx, ctx->pixel_aux.ensure((size_t)npx * 16));
-        launch_pixel_sampler(st, prm.sampler, pixel_xy, npx, ctx->pixel_aux.as<uint4>());
-        // the second stream starts after the pixel table exists
-        if (n_ws == 2) {
+        HIP_TRY(ctx, ctx->pixel_aux.ensure((size_t)c.npx * 16));
+        launch_pixel_sampler(st, prm.sampler, pixel_xy, c.npx, ctx->pixel_aux.as<uint4>());
+        const bool two = plan.n_ws == 2;
+        if (two) {  // the second stream starts after the pixel table exists
             HIP_TRY(ctx, hipEventRecord(ctx->ws[0].done, st));
             HIP_TRY(ctx, hipStreamWaitEvent(ctx->ws[1].stream, ctx->ws[0].done, 0));
         }
-
-        const uint64_t work = (uint64_t)npx * spp;
-        int which = 0;
-        bool ws_busy[2] = {false, false};
-        for (uint64_t w0 = 0; w0 < work; w0 += batch) {
+        const uint64_t work = (uint64_t)c.npx * spp;
+        which = 0;
+        ws_busy[0] = ws_busy[1] = false;
+        for (uint64_t w0 = 0; w0 < work; w0 += plan.batch) {
             WorkSet& ws = ctx->ws[which];
-            // An interruptible job of many batches is not enqueued all at once: a work set takes its next batch when its
-            // previous one has finished (the other work set's batch keeps the GPU busy meanwhile), the predicate is polled
-            // during the wait, and an interruption has at most two batches' launches left to drain — each of them an empty
-            // launch of a few microseconds, but a 4K x 256 spp job holds 1300 of them.
-            bool fired = cancel && ws_busy[which] && poll_until(ctx, ws.ev_batch, cancel, user);
-            if (!fired && cancel && cancel(user)) {
-                raise_cancel(ctx);
-                fired = true;
-            }
-            if (fired) {  // what is already enqueued drains at once
-                const double t0 = g_debug_cancel ? now_ms() : 0.0;
-                (void)hipStreamSynchronize(st);
-                const double t1 = g_debug_cancel ? now_ms() : 0.0;
-                if (n_ws == 2) (void)hipStreamSynchronize(ctx->ws[1].stream);
-                if (g_debug_cancel) {
-                    unsigned words[4] = {0, 0, 0, 0};
-                    (void)hipMemcpy(words, error_block(ctx), sizeof words, hipMemcpyDeviceToHost);
-                    std::fprintf(stderr, "[yk cancel] drain: stream0 %.3f ms, stream1 %.3f ms, batch %llu of %llu, device word %u\n", t1 - t0, now_ms() - t1,
-                                 (unsigned long long)(w0 / batch), (unsigned long long)((work + batch - 1) / batch), words[YK_CTRL_CANCELLED]);
-                }
-                return fail(ctx, YK_ERR_CANCELLED, "cancelled by early_termination_predicate");
-            }
-            hipStream_t bs = n_ws == 2 ? ws.stream : st;
-            unsigned* ctrl = ws.ctrl.as<unsigned>();
-            const uint32_t n = (uint32_t)std::min<uint64_t>(batch, work - w0);
-            HIP_TRY(ctx, hipMemsetAsync(ctrl, 0, YK_CTRL_WORDS * 4, bs));
-            // Path, camera rays traced by the packet kernel: the lean camera bounce (yk_device.h, YK_CTRL_CAM_O)
-            const bool lean = is_path && prm.max_depth > 0 && packet_kernel_traces_bounce(ctx, scene, 0);
-            launch_raygen(bs, cam, prm, pixel_xy, pixel_sample, w0, n, path_buffers(ws, 0), sample_buf, ctrl + YK_CTRL_BOUNCE(0),
-                          lean ? reinterpret_cast<float4*>(ctrl + YK_CTRL_CAM_O) : nullptr, ctx->pixel_aux.as<uint4>());
-            ++n_batches;
-            if (is_path) {
-                run_bounces(ctx, ws, bs, scene, prm, pixel_xy, pixel_sample, sample_buf, kt, counters, true, n, (uint32_t)w0, lean, &n_shadow);
-                n_trace += prm.max_depth;
-            } else if (prm.integrator == YK_INTEGRATOR_WHITTED) {
-                // one lane per camera sample runs the whole recursion (whitted.rs:74-181)
-                int e = kt.begin(bs);
-                launch_whitted(bs, trace_grid(ctx), scene->dev, prm, pixel_xy, pixel_sample, path_buffers(ws, 0), n, sample_buf, ws.spill.as<uint2>(),
-                               trace_grid(ctx) * trace_block_size(), errblk, counters);
-                kt.end(e, 0, bs);
-                ++n_trace;
-            } else {
-                PathBuffers pc = path_buffers(ws, 0);
-                const bool want_stats = prm.integrator == YK_INTEGRATOR_BVH_INTERSECTIONS;
-                int e = kt.begin(bs);
-                launch_trace_closest(bs, trace_grid(ctx), dev_scene_for(scene, n), pc.rayO, pc.rayD, nullptr, ctrl + YK_CTRL_BOUNCE(0), ctrl + YK_CTRL_BOUNCE(0) + YK_CTRL_HEAD, ws.hit.as<int>(), nullptr,
-                                     want_stats ? ctx->stats4.as<uint4>() : nullptr, ws.spill.as<uint2>(), trace_grid(ctx) * trace_block_size(), errblk,
-                                     counters);
-                kt.end(e, 0, bs);
-                if (guides_res_x && d_ids) launch_guides_ids(bs, scene->dev, pc, ws.hit.as<int>(), n, pixel_xy, guides_res_x, reinterpret_cast<float4*>(d_out_rgb), reinterpret_cast<uint4*>(d_ids));
-                else if (guides_res_x) launch_guides(bs, scene->dev, pc, ws.hit.as<int>(), n, pixel_xy, guides_res_x, reinterpret_cast<float4*>(d_out_rgb));
-                else launch_debug_shade(bs, scene->dev, prm.integrator, pc, ws.hit.as<int>(), ctx->stats4.as<uint4>(), n, sample_buf);
-                ++n_trace;
-            }
-            if (cancel) {
+            if ((rc = gate_on_cancel(ws, w0, work)) != YK_OK) return rc;
+            hipStream_t bs = two ? ws.stream : st;
+            if ((rc = enqueue_batch(ws, bs, w0, (uint32_t)std::min<uint64_t>(plan.batch, work - w0))) != YK_OK) return rc;
+            if (rq.cancel) {
                 HIP_TRY(ctx, hipEventRecord(ws.ev_batch, bs));
                 ws_busy[which] = true;
             }
-            if (n_ws == 2) which ^= 1;
+            if (two) which ^= 1;
         }
-        if (n_ws == 2) {  // resolve (on the caller-visible stream) waits for the second stream
+        if (two) {  // resolve (on the caller-visible stream) waits for the second stream
             HIP_TRY(ctx, hipEventRecord(ctx->ws[1].done, ctx->ws[1].stream));
             HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ws[1].done, 0));
         }
-        if (guides_res_x)  // k_guides wrote every record at its pixel: nothing to resolve
+        float* out = reinterpret_cast<float*>(rq.d_out) + 3 * (size_t)c.px0;
+        if (rq.guides_res_x)  // k_guides wrote every record at its pixel: nothing to resolve
             ;
-        else if (accumulating)  // raw values, pass-major over the whole tile list
-            launch_resolve_passes(st, sample_buf, npx, spp, out + 3 * (size_t)px0, 3 * (size_t)total_px);
+        else if (plan.accumulating)  // raw values, pass-major over the whole tile list
+            launch_resolve_passes(st, sample_buf, c.npx, spp, out, 3 * (size_t)plan.total_px);
         else
-            launch_resolve(st, sample_buf, npx, spp, out + 3 * (size_t)px0);
-        t_begin = t_end;
+            launch_resolve(st, sample_buf, c.npx, spp, out);
+        return YK_OK;
     }
+
+    yk_status finish_call() {
+        yk_render_stats* stats = rq.stats;
+        unsigned words[4];
+        if (stats) {
+            HIP_TRY(ctx, hipEventRecord(frame_ev.b, st));
+            // a synchronous call: the predicate is polled while the GPU works
+            if (wait_polling(ctx, frame_ev.b, st, rq.cancel, rq.user)) return fail(ctx, YK_ERR_CANCELLED, "cancelled by early_termination_predicate");
+            if (ctx->cancel_raised.load(std::memory_order_acquire)) return fail(ctx, YK_ERR_CANCELLED, "interrupted (yk_context_interrupt)");
+            HIP_TRY(ctx, hipGetLastError());
+            std::memset(stats, 0, sizeof(*stats));
+            unsigned long long host_counters[YK_COUNTER_BYTES / 8];
+            HIP_TRY(ctx, hipMemcpy(host_counters, counters(), YK_COUNTER_BYTES, hipMemcpyDeviceToHost));
+            std::memcpy(words, host_counters + 16, sizeof(words));
+            float ms = 0.0f;
+            (void)hipEventElapsedTime(&ms, frame_ev.a, frame_ev.b);
+            stats->rays = host_counters[0];
+            stats->shadow_rays = host_counters[1];
+            stats->samples = plan.total_work;
+            stats->seconds_total = ms * 1e-3;
+            stats->seconds_trace = kt.total(0);
+            stats->seconds_shadow = kt.total(1);
+            stats->seconds_shade = kt.total(2);
+            stats->trace_launches = n_trace;
+            stats->shadow_launches = n_shadow;
+            stats->batches = n_batches;
+            return error_block_status(ctx, words);
+        }
+        if (scene->bvh->depth <= 64) return YK_OK;
+        // A tree deeper than the reference's 64-entry stack (bvh.rs:172-174) can overflow it: such a render is
+        // not left asynchronous — the flag is read before the call returns, whoever the caller is.
+        HIP_TRY(ctx, hipMemcpyAsync(words, error_block(ctx), sizeof(words), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        return error_block_status(ctx, words);
+    }
+};
+
+static yk_status render_tiles_impl(yk_context* ctx, const RenderRequest& rq) try {
+    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
+    YK_LOCK(ctx);
+    struct HandBack {  // on every exit path: whatever was enqueued is ordered before the caller's next work
+        yk_context* c;
+        hipStream_t caller;
+        ~HandBack() {
+            if (!caller) return;
+            if (hipEventRecord(c->ev_out, c->stream) == hipSuccess) (void)hipStreamWaitEvent(caller, c->ev_out, 0);
+        }
+    } hand_back{ctx, nullptr};
+    Submission s(ctx, rq);
+    yk_status rc = s.check_and_plan();
+    if (rc != YK_OK) return rc;
+    // The render always runs on the context's own streams; a caller's stream hands over to them
+    // and takes over again at the end (two event waits), so the work is ordered on it as if it
+    // had been launched there — and the main / side stream pair keeps its own hardware queues.
+    if (hipStream_t caller = (hipStream_t)rq.stream) {
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_in, caller));
+        HIP_TRY(ctx, hipStreamWaitEvent(s.st, ctx->ev_in, 0));
+        hand_back.caller = caller;
+    }
+    if ((rc = s.grow_buffers()) != YK_OK) return rc;
+    if ((rc = s.begin_call()) != YK_OK) return rc;
+#ifdef YK_EXPERIMENT_GRAPH  // timing builds only (tools/micro/graph_replay_experiment.h, DESIGN.md §9)
+    YK_GRAPH_BEGIN
+#endif
+    for (const yk_plan::Chunk& c : s.plan.chunks)
+        if ((rc = s.render_chunk(c)) != YK_OK) return rc;
     HIP_TRY(ctx, hipGetLastError());
 #ifdef YK_EXPERIMENT_GRAPH
     YK_GRAPH_END
 #endif
-    if (stats) {
-        HIP_TRY(ctx, hipEventRecord(ev1, st));
-        // a synchronous call: the predicate is polled while the GPU works
-        if (wait_polling(ctx, ev1, st, cancel, user)) return fail(ctx, YK_ERR_CANCELLED, "cancelled by early_termination_predicate");
-        if (ctx->cancel_raised.load(std::memory_order_acquire)) return fail(ctx, YK_ERR_CANCELLED, "interrupted (yk_context_interrupt)");
-        HIP_TRY(ctx, hipGetLastError());
-        std::memset(stats, 0, sizeof(*stats));
-        unsigned long long host_counters[YK_COUNTER_BYTES / 8];
-        HIP_TRY(ctx, hipMemcpy(host_counters, counters, YK_COUNTER_BYTES, hipMemcpyDeviceToHost));
-        unsigned host_err[4];
-        std::memcpy(host_err, host_counters + 16, sizeof(host_err));
-        float ms = 0.0f;
-        (void)hipEventElapsedTime(&ms, ev0, ev1);
-        stats->rays = host_counters[0];
-        stats->shadow_rays = host_counters[1];
-        stats->samples = total_px * spp;
-        stats->seconds_total = ms * 1e-3;
-        stats->seconds_trace = kt.total(0);
-        stats->seconds_shadow = kt.total(1);
-        stats->seconds_shade = kt.total(2);
-        stats->trace_launches = n_trace;
-        stats->shadow_launches = n_shadow;
-        stats->batches = n_batches;
-        if (host_err[YK_CTRL_ERR] & 1u) return fail(ctx, YK_ERR_STACK_OVERFLOW, "BVH traversal stack exceeded 64 entries (bvh.rs:174)");
-    } else if (scene->bvh->depth > 64) {
-        // A tree deeper than the reference's 64-entry stack (bvh.rs:172-174) can overflow it: such a render is
-        // not left asynchronous — the flag is read before the call returns, whoever the caller is.
-        unsigned host_err[4];
-        HIP_TRY(ctx, hipMemcpyAsync(host_err, errblk, sizeof(host_err), hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        if (host_err[YK_CTRL_ERR] & 1u) return fail(ctx, YK_ERR_STACK_OVERFLOW, "BVH traversal stack exceeded 64 entries (bvh.rs:174)");
-    }
-    return YK_OK;
+    return s.finish_call();
 } YK_CATCH(ctx)
 
-static yk_status render_tiles_host(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler,
-                                   const yk_integrator_desc* integrator, const yk_tile* tiles, const uint16_t* tile_samples, size_t n_tiles,
-                                   float* out_rgb, yk_render_stats* stats, yk_cancel_fn cancel, void* user, uint32_t n_passes = 1);
-
-extern "C" {
-
-yk_status yk_render_tiles_device(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler,
-                                 const yk_integrator_desc* integrator, const yk_tile* tiles, size_t n_tiles, void* d_out_rgb, void* stream,
-                                 yk_render_stats* stats, yk_cancel_fn cancel, void* user) {
-    return render_tiles_impl(ctx, scene, camera, sampler, integrator, tiles, nullptr, n_tiles, d_out_rgb, stream, stats, cancel, user);
-}
-
-yk_status yk_render_tiles_accumulating_device(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler,
-                                              const yk_integrator_desc* integrator, const yk_tile* tiles, const uint16_t* tile_samples, size_t n_tiles,
-                                              void* d_out_rgb, void* stream, yk_render_stats* stats, yk_cancel_fn cancel, void* user) {
+// a render into a host array: the output staged around the device call
+static yk_status render_tiles_host(yk_context* ctx, RenderRequest rq, float* out_rgb) {
     if (!ctx) return YK_ERR_INVALID_ARGUMENT;
     YK_LOCK(ctx);
-    if (!tile_samples) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null tile_samples");
-    return render_tiles_impl(ctx, scene, camera, sampler, integrator, tiles, tile_samples, n_tiles, d_out_rgb, stream, stats, cancel, user);
+    if (!rq.tiles || rq.n_tiles == 0 || !out_rgb) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null argument");
+    std::vector<uint32_t> off;
+    yk_status st = tile_offsets(ctx, rq.tiles, rq.n_tiles, off, "too many pixels in one call");
+    if (st != YK_OK) return st;
+    if (rq.n_passes == 0 || rq.n_passes > 0xFFFFu) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "bad number of passes");
+    Staging sg(ctx);
+    rq.d_out = sg.output(out_rgb, (size_t)off.back() * 3 * rq.n_passes);
+    if (!sg.ok()) return sg.status();
+    yk_render_stats local;
+    if (!rq.stats) rq.stats = &local;
+    if ((st = render_tiles_impl(ctx, rq)) != YK_OK) return st;
+    return sg.finish();
 }
 
-yk_status yk_render_tiles_accumulating(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler,
-                                       const yk_integrator_desc* integrator, const yk_tile* tiles, const uint16_t* tile_samples, size_t n_tiles,
-                                       float* out_rgb, yk_render_stats* stats, yk_cancel_fn cancel, void* user) {
-    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
-    YK_LOCK(ctx);
-    if (!tile_samples) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null tile_samples");
-    return render_tiles_host(ctx, scene, camera, sampler, integrator, tiles, tile_samples, n_tiles, out_rgb, stats, cancel, user);
-}
-
-yk_status yk_render_tiles_accumulating_passes(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler,
-                                              const yk_integrator_desc* integrator, const yk_tile* tiles, const uint16_t* tile_samples, size_t n_tiles,
-                                              uint32_t n_passes, float* out_rgb, yk_render_stats* stats, yk_cancel_fn cancel, void* user) {
-    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
-    YK_LOCK(ctx);
-    if (!tile_samples) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null tile_samples");
-    return render_tiles_host(ctx, scene, camera, sampler, integrator, tiles, tile_samples, n_tiles, out_rgb, stats, cancel, user, n_passes);
-}
-
-yk_status yk_tile_list_create(yk_context* ctx, const yk_tile* tiles, const uint16_t* tile_samples, size_t n_tiles, yk_tile_list** out) try {
-    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
-    YK_LOCK(ctx);
-    if (!tiles || !out || n_tiles == 0) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null argument");
-    *out = nullptr;
-    yk_tile_list* l = new yk_tile_list();
-    l->device = ctx->device;
-    l->tiles.assign(tiles, tiles + n_tiles);
-    if (tile_samples) l->samples.assign(tile_samples, tile_samples + n_tiles);
-    l->off.assign(n_tiles + 1, 0);
-    uint64_t total = 0;
-    for (size_t t = 0; t < n_tiles; ++t) {
-        if (tiles[t].x0 >= tiles[t].x1 || tiles[t].y0 >= tiles[t].y1) {
-            delete l;
-            return fail(ctx, YK_ERR_INVALID_ARGUMENT, "Bounds2 with a dimension <= 0");
-        }
-        total += (uint64_t)(tiles[t].x1 - tiles[t].x0) * (uint64_t)(tiles[t].y1 - tiles[t].y0);
-        if (total > 0xFFFFFFFFull) {
-            delete l;
-            return fail(ctx, YK_ERR_INVALID_ARGUMENT, "too many pixels in one list");
-        }
-        l->off[t + 1] = (uint32_t)total;
-    }
-    (void)hipSetDevice(ctx->device);
-    hipStream_t st = ctx->stream;
-    yk_status rc = YK_OK;
-    auto tryhip = [&](hipError_t e, const char* what) {
-        if (e != hipSuccess && rc == YK_OK) rc = fail(ctx, e == hipErrorOutOfMemory ? YK_ERR_OUT_OF_MEMORY : YK_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
-    };
-    tryhip(ctx->tiles.ensure(n_tiles * sizeof(yk_tile)), "tiles");
-    tryhip(ctx->tile_off.ensure((n_tiles + 1) * 4), "tile offsets");
-    tryhip(l->pixel_xy.ensure((size_t)total * 4), "pixel table");
-    if (tile_samples) {
-        tryhip(ctx->tile_sample.ensure(n_tiles * 2), "tile samples");
-        tryhip(l->pixel_sample.ensure((size_t)total * 4), "pixel samples");
-    }
-    if (rc == YK_OK) {
-        tryhip(hipMemcpyAsync(ctx->tiles.p, tiles, n_tiles * sizeof(yk_tile), hipMemcpyHostToDevice, st), "upload tiles");
-        tryhip(hipMemcpyAsync(ctx->tile_off.p, l->off.data(), l->off.size() * 4, hipMemcpyHostToDevice, st), "upload offsets");
-        if (tile_samples) tryhip(hipMemcpyAsync(ctx->tile_sample.p, tile_samples, n_tiles * 2, hipMemcpyHostToDevice, st), "upload samples");
-    }
-    if (rc == YK_OK) {
-        launch_pixel_table(st, ctx->tiles.as<yk_tile>(), ctx->tile_off.as<uint32_t>(), (uint32_t)n_tiles, (uint32_t)total, l->pixel_xy.as<uint32_t>(),
-                           tile_samples ? ctx->tile_sample.as<uint16_t>() : nullptr, tile_samples ? l->pixel_sample.as<uint32_t>() : nullptr);
-        tryhip(hipGetLastError(), "pixel table kernel");
-        tryhip(hipStreamSynchronize(st), "sync");
-    }
-    if (rc != YK_OK) {
-        l->pixel_xy.release();
-        l->pixel_sample.release();
-        delete l;
-        return rc;
-    }
-    *out = l;
-    return YK_OK;
-} YK_CATCH(ctx)
-
-void yk_tile_list_destroy(yk_tile_list* l) {
-    if (!l) return;
-    if (l->device >= 0) (void)hipSetDevice(l->device);
-    l->pixel_xy.release();
-    l->pixel_sample.release();
-    delete l;
-}
-
-yk_status yk_render_tile_list_device(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler,
-                                     const yk_integrator_desc* integrator, const yk_tile_list* list, void* d_out_rgb, void* stream,
-                                     yk_render_stats* stats, yk_cancel_fn cancel, void* user) {
-    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
-    if (!list) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null tile list");
-    return render_tiles_impl(ctx, scene, camera, sampler, integrator, list->tiles.data(), nullptr, list->tiles.size(), d_out_rgb, stream, stats, cancel,
-                             user, list);
-}
-
-yk_status yk_render_tile_list_passes_device(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler,
-                                            const yk_integrator_desc* integrator, const yk_tile_list* list, uint32_t n_passes, void* d_out_rgb, void* stream,
-                                            yk_render_stats* stats, yk_cancel_fn cancel, void* user) {
-    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
-    if (!list) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null tile list");
-    if (list->samples.empty()) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "passes need an accumulating tile list (tile_samples)");
-    return render_tiles_impl(ctx, scene, camera, sampler, integrator, list->tiles.data(), nullptr, list->tiles.size(), d_out_rgb, stream, stats, cancel,
-                             user, list, n_passes);
-}
-
-yk_status yk_render_tile_list_samples_device(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler,
-                                             const yk_integrator_desc* integrator, const yk_tile_list* list, uint32_t first_sample, uint32_t n_passes,
-                                             void* d_out_rgb, void* stream, yk_render_stats* stats, yk_cancel_fn cancel, void* user) {
-    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
-    if (!list) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null tile list");
-    if (!list->samples.empty()) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "the list carries per-tile sample indices: use yk_render_tile_list_passes_device");
-    return render_tiles_impl(ctx, scene, camera, sampler, integrator, list->tiles.data(), nullptr, list->tiles.size(), d_out_rgb, stream, stats, cancel,
-                             user, list, n_passes, (int64_t)first_sample);
-}
-
-// An interruption from any thread (the call that renders holds the context's lock for its whole duration, this one
-// takes none): what the context has enqueued stops at the kernels' next look at the word, the next submission waits
-// for it to drain and clears the word.
-yk_status yk_context_interrupt(yk_context* ctx) {
-    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
-    raise_cancel(ctx, false);  // the host word only: no HIP call from a thread that may not have the device current
-    return YK_OK;
-}
-
-static yk_status film_update_list(yk_context* ctx, const yk_tile_list* list, const void* d_tile_rgb, uint16_t res_x, uint16_t res_y, void* d_film_rgb,
-                                  void* stream, int accumulate, uint32_t n_passes);
-
-yk_status yk_film_accumulate_tile_list_passes_device(yk_context* ctx, const yk_tile_list* list, const void* d_passes_rgb, uint32_t n_passes, uint16_t res_x,
-                                                     uint16_t res_y, void* d_film_rgb, void* stream) {
-    return film_update_list(ctx, list, d_passes_rgb, res_x, res_y, d_film_rgb, stream, 1, n_passes);
-}
-
-yk_status yk_film_update_tile_list_device(yk_context* ctx, const yk_tile_list* list, const void* d_tile_rgb, uint16_t res_x, uint16_t res_y,
-                                          void* d_film_rgb, void* stream, int accumulate) {
-    return film_update_list(ctx, list, d_tile_rgb, res_x, res_y, d_film_rgb, stream, accumulate, 1);
+// The guides: the ShadingNormals integrator's trace of the whole film as one tile under a 1 x 1 Stratified sampler without
+// jitter, whose camera sample is the pixel centre whatever its seed, so the ray is Camera::ray((x + 0.5, y + 0.5)).
+static yk_status render_guides(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, uint16_t res_x, uint16_t res_y, void* d_guides, void* stream, void* d_ids = nullptr) {
+    yk_sampler_desc smp = {};
+    smp.kind = YK_SAMPLER_STRATIFIED;
+    smp.nx = smp.ny = 1;
+    yk_integrator_desc integ = {};
+    integ.kind = YK_INTEGRATOR_SHADING_NORMALS;
+    const yk_tile film = {0, 0, res_x, res_y};
+    RenderRequest rq;
+    rq.scene = scene;
+    rq.camera = camera;
+    rq.sampler = &smp;
+    rq.integrator = &integ;
+    rq.tiles = &film;
+    rq.n_tiles = 1;
+    rq.d_out = d_guides;
+    rq.guides_res_x = res_x;
+    rq.d_ids = d_ids;
+    rq.stream = stream;
+    return render_tiles_impl(ctx, rq);
 }
 
 static yk_status film_update_list(yk_context* ctx, const yk_tile_list* list, const void* d_tile_rgb, uint16_t res_x, uint16_t res_y, void* d_film_rgb,
@@ -755,47 +708,260 @@ static yk_status film_update_list(yk_context* ctx, const yk_tile_list* list, con
     return YK_OK;  // asynchronous: ordered on `stream`
 }
 
-yk_status yk_render_tiles(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler,
-                          const yk_integrator_desc* integrator, const yk_tile* tiles, size_t n_tiles, float* out_rgb, yk_render_stats* stats,
-                          yk_cancel_fn cancel, void* user) {
-    return render_tiles_host(ctx, scene, camera, sampler, integrator, tiles, nullptr, n_tiles, out_rgb, stats, cancel, user);
-}
-
-}  // extern "C"
-
-static yk_status render_tiles_host(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler,
-                                   const yk_integrator_desc* integrator, const yk_tile* tiles, const uint16_t* tile_samples, size_t n_tiles,
-                                   float* out_rgb, yk_render_stats* stats, yk_cancel_fn cancel, void* user, uint32_t n_passes) {
+static yk_status film_tiles_device(yk_context* ctx, const yk_tile* tiles, size_t n_tiles, const void* d_tile_rgb, uint16_t res_x, uint16_t res_y,
+                                   void* d_film_rgb, void* stream, int accumulate) try {
     if (!ctx) return YK_ERR_INVALID_ARGUMENT;
     YK_LOCK(ctx);
-    if (!tiles || n_tiles == 0 || !out_rgb) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null argument");
-    uint64_t total_px = 0;
-    for (size_t t = 0; t < n_tiles; ++t) {
-        if (tiles[t].x0 >= tiles[t].x1 || tiles[t].y0 >= tiles[t].y1) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "Bounds2 with a dimension <= 0");
-        total_px += (uint64_t)(tiles[t].x1 - tiles[t].x0) * (uint64_t)(tiles[t].y1 - tiles[t].y0);
+    if (!tiles || !d_tile_rgb || !d_film_rgb || n_tiles == 0) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null argument");
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
+    std::vector<uint32_t> off;
+    const yk_plan::TileRefusal no = yk_plan::tile_ranges(tiles, n_tiles, off, res_x, res_y);
+    if (no == yk_plan::TILES_TOO_MANY_PIXELS) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "too many pixels");
+    if (no != yk_plan::TILES_OK) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "update_tile: Tile doesn't fit film");
+    const uint32_t total = off.back();
+    HIP_TRY(ctx, ctx->film_tiles.ensure(n_tiles * sizeof(yk_tile)));
+    HIP_TRY(ctx, ctx->film_tile_off.ensure((n_tiles + 1) * 4));
+    HIP_TRY(ctx, ctx->film_pixel_xy.ensure((size_t)total * 4));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->film_tiles.p, tiles, n_tiles * sizeof(yk_tile), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->film_tile_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    launch_pixel_table(st, ctx->film_tiles.as<yk_tile>(), ctx->film_tile_off.as<uint32_t>(), (uint32_t)n_tiles, total, ctx->film_pixel_xy.as<uint32_t>());
+    launch_film_scatter(st, ctx->film_pixel_xy.as<uint32_t>(), total, reinterpret_cast<const float*>(d_tile_rgb), res_x, reinterpret_cast<float*>(d_film_rgb), accumulate);
+    HIP_TRY(ctx, hipGetLastError());
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return YK_OK;
+} YK_CATCH(ctx)
+
+// ------------------------------------------------------------------ yk_li / yk_li_debug: what both do
+// One ray per table entry (pixel, sample index), generated by launch_raygen_user into work set 0.
+struct LiCall {
+    yk_context* const ctx;
+    const yk_scene* const scene;
+    const size_t n;
+    RenderParams prm;
+    const uint32_t* d_sample_index = nullptr;
+    unsigned words[4];  // the error block, read back
+
+    // The checks and the parameters.  `refuse_size`, `refuse_integrator`: the entry point's own refusals (NULL: none), said
+    // where they have always been said.
+    yk_status check(bool arrays_given, const yk_sampler_desc* sampler, const yk_integrator_desc* integrator, const uint32_t* sample_index, const char* refuse_size,
+                    const char* refuse_integrator) {
+        if (!scene || !arrays_given || n == 0) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null argument");
+        if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "scene was not created on this context's device");
+        if (n > ((size_t)1 << 28)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "too many rays");
+        if (refuse_size) return fail(ctx, YK_ERR_INVALID_ARGUMENT, refuse_size);
+        yk_status ps = make_params(ctx, sampler, integrator, prm);
+        if (ps != YK_OK) return ps;
+        if (refuse_integrator) return fail(ctx, YK_ERR_UNSUPPORTED, refuse_integrator);
+        prm.spe = 1;  // one table entry (pixel, sample index) per ray
+        for (size_t i = 0; i < n; ++i)
+            if (sample_index[i] >= prm.sampler.spp) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "sample_index >= samples per pixel");
+        return YK_OK;
     }
-    if (n_passes == 0 || n_passes > 0xFFFFu) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "bad number of passes");
-    Staging sg(ctx);
-    float* d_out = sg.output(out_rgb, total_px * 3 * n_passes);
-    if (!sg.ok()) return sg.status();
-    yk_render_stats local;
-    yk_status st = render_tiles_impl(ctx, scene, camera, sampler, integrator, tiles, tile_samples, n_tiles, d_out, nullptr, stats ? stats : &local, cancel, user, nullptr, n_passes);
-    if (st != YK_OK) return st;
-    return sg.finish();
-}
+    // the buffers of work set 0 and the context's counters: cancel_ref(ctx) points into them, so it is taken after this
+    yk_status grow() {
+        yk_status wb = ensure_work_buffers(ctx, ctx->ws[0], n, scene->n_lights, scene->n_delta_lights);
+        if (wb != YK_OK) return wb;
+        if ((wb = ensure_spill(ctx, ctx->ws[0])) != YK_OK) return wb;
+        HIP_TRY(ctx, ctx->pixel_xy.ensure(n * 4));
+        HIP_TRY(ctx, ctx->sample_buf.ensure(n * 16));
+        return YK_OK;
+    }
+    // the four inputs staged, counters and control block zeroed, the rays generated
+    yk_status raygen(Staging& sg, const float* ray_o, const float* ray_d, const uint16_t* pixel_xy, const uint32_t* sample_index, uint32_t dimension) {
+        const float* d_ray_o = sg.upload(ray_o, n * 3);
+        const float* d_ray_d = sg.upload(ray_d, n * 3);
+        const uint16_t* d_pixel_xy = sg.upload(pixel_xy, n * 2);
+        d_sample_index = sg.upload(sample_index, n);
+        if (!sg.ok()) return sg.status();
+        unsigned* ctrl = ctx->ws[0].ctrl.as<unsigned>();
+        HIP_TRY(ctx, hipMemsetAsync(ctx->counters.p, 0, YK_COUNTER_BYTES, sg.stream));  // the error block with it: stack-overflow flag, interruption word
+        HIP_TRY(ctx, hipMemsetAsync(ctrl, 0, YK_CTRL_WORDS * 4, sg.stream));
+        launch_raygen_user(sg.stream, prm, d_ray_o, d_ray_d, d_pixel_xy, d_sample_index, dimension, (uint32_t)n, path_buffers(ctx->ws[0], 0), ctx->sample_buf.as<float4>(),
+                           ctx->pixel_xy.as<uint32_t>(), ctrl + YK_CTRL_BOUNCE(0));
+        return YK_OK;
+    }
+    // after the synchronisation: the verdict of the error block, then the float4 samples as RGB
+    yk_status verdict_and_rgb(const std::vector<float>& rgba, float* out_li) {
+        yk_status st = error_block_status(ctx, words);
+        for (size_t i = 0; st == YK_OK && i < n; ++i) std::memcpy(out_li + 3 * i, rgba.data() + 4 * i, 12);
+        return st;
+    }
+};
 
 extern "C" {
 
-// The guides: the ShadingNormals integrator's trace of the whole film as one tile under a 1 x 1 Stratified sampler without
-// jitter, whose camera sample is the pixel centre whatever its seed, so the ray is Camera::ray((x + 0.5, y + 0.5)).
-static yk_status render_guides(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, uint16_t res_x, uint16_t res_y, void* d_guides, void* stream, void* d_ids = nullptr) {
-    yk_sampler_desc smp = {};
-    smp.kind = YK_SAMPLER_STRATIFIED;
-    smp.nx = smp.ny = 1;
-    yk_integrator_desc integ = {};
-    integ.kind = YK_INTEGRATOR_SHADING_NORMALS;
-    const yk_tile film = {0, 0, res_x, res_y};
-    return render_tiles_impl(ctx, scene, camera, &smp, &integ, &film, nullptr, 1, d_guides, stream, nullptr, nullptr, nullptr, nullptr, 1, -1, res_x, d_ids);
+yk_status yk_render_tiles_device(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler,
+                                 const yk_integrator_desc* integrator, const yk_tile* tiles, size_t n_tiles, void* d_out_rgb, void* stream,
+                                 yk_render_stats* stats, yk_cancel_fn cancel, void* user) {
+    RenderRequest rq = request_for(scene, camera, sampler, integrator, d_out_rgb, stream, stats, cancel, user);
+    rq.tiles = tiles;
+    rq.n_tiles = n_tiles;
+    return render_tiles_impl(ctx, rq);
+}
+
+yk_status yk_render_tiles_accumulating_device(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler,
+                                              const yk_integrator_desc* integrator, const yk_tile* tiles, const uint16_t* tile_samples, size_t n_tiles,
+                                              void* d_out_rgb, void* stream, yk_render_stats* stats, yk_cancel_fn cancel, void* user) {
+    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
+    YK_LOCK(ctx);
+    if (!tile_samples) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null tile_samples");
+    RenderRequest rq = request_for(scene, camera, sampler, integrator, d_out_rgb, stream, stats, cancel, user);
+    rq.tiles = tiles;
+    rq.tile_samples = tile_samples;
+    rq.n_tiles = n_tiles;
+    return render_tiles_impl(ctx, rq);
+}
+
+yk_status yk_render_tiles_accumulating_passes(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler,
+                                              const yk_integrator_desc* integrator, const yk_tile* tiles, const uint16_t* tile_samples, size_t n_tiles,
+                                              uint32_t n_passes, float* out_rgb, yk_render_stats* stats, yk_cancel_fn cancel, void* user) {
+    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
+    YK_LOCK(ctx);
+    if (!tile_samples) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null tile_samples");
+    RenderRequest rq = request_for(scene, camera, sampler, integrator, nullptr, nullptr, stats, cancel, user);  // the output is staged
+    rq.tiles = tiles;
+    rq.tile_samples = tile_samples;
+    rq.n_tiles = n_tiles;
+    rq.n_passes = n_passes;
+    return render_tiles_host(ctx, rq, out_rgb);
+}
+
+yk_status yk_render_tiles_accumulating(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler,
+                                       const yk_integrator_desc* integrator, const yk_tile* tiles, const uint16_t* tile_samples, size_t n_tiles,
+                                       float* out_rgb, yk_render_stats* stats, yk_cancel_fn cancel, void* user) {
+    return yk_render_tiles_accumulating_passes(ctx, scene, camera, sampler, integrator, tiles, tile_samples, n_tiles, 1, out_rgb, stats, cancel, user);
+}
+
+yk_status yk_render_tiles(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler,
+                          const yk_integrator_desc* integrator, const yk_tile* tiles, size_t n_tiles, float* out_rgb, yk_render_stats* stats,
+                          yk_cancel_fn cancel, void* user) {
+    RenderRequest rq = request_for(scene, camera, sampler, integrator, nullptr, nullptr, stats, cancel, user);  // the output is staged
+    rq.tiles = tiles;
+    rq.n_tiles = n_tiles;
+    return render_tiles_host(ctx, rq, out_rgb);
+}
+
+yk_status yk_render_tile(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler,
+                         const yk_integrator_desc* integrator, const yk_tile* tile, float* tile_pixels, uint64_t* out_rays) {
+    yk_render_stats stats;
+    yk_status st = yk_render_tiles(ctx, scene, camera, sampler, integrator, tile, 1, tile_pixels, &stats, nullptr, nullptr);
+    if (st == YK_OK && out_rays) *out_rays = stats.rays;
+    return st;
+}
+
+yk_status yk_tile_list_create(yk_context* ctx, const yk_tile* tiles, const uint16_t* tile_samples, size_t n_tiles, yk_tile_list** out) try {
+    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
+    YK_LOCK(ctx);
+    if (!tiles || !out || n_tiles == 0) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    std::unique_ptr<yk_tile_list> l(new yk_tile_list());
+    l->device = ctx->device;
+    l->tiles.assign(tiles, tiles + n_tiles);
+    if (tile_samples) l->samples.assign(tile_samples, tile_samples + n_tiles);
+    yk_status rc = tile_offsets(ctx, tiles, n_tiles, l->off, "too many pixels in one list");
+    if (rc != YK_OK) return rc;
+    const uint32_t total = l->off.back();
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    auto tryhip = [&](hipError_t e, const char* what) {
+        if (e != hipSuccess && rc == YK_OK) rc = fail(ctx, e == hipErrorOutOfMemory ? YK_ERR_OUT_OF_MEMORY : YK_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e));
+    };
+    tryhip(ctx->tiles.ensure(n_tiles * sizeof(yk_tile)), "tiles");
+    tryhip(ctx->tile_off.ensure((n_tiles + 1) * 4), "tile offsets");
+    tryhip(l->pixel_xy.ensure((size_t)total * 4), "pixel table");
+    if (tile_samples) {
+        tryhip(ctx->tile_sample.ensure(n_tiles * 2), "tile samples");
+        tryhip(l->pixel_sample.ensure((size_t)total * 4), "pixel samples");
+    }
+    if (rc == YK_OK) {
+        tryhip(hipMemcpyAsync(ctx->tiles.p, tiles, n_tiles * sizeof(yk_tile), hipMemcpyHostToDevice, st), "upload tiles");
+        tryhip(hipMemcpyAsync(ctx->tile_off.p, l->off.data(), l->off.size() * 4, hipMemcpyHostToDevice, st), "upload offsets");
+        if (tile_samples) tryhip(hipMemcpyAsync(ctx->tile_sample.p, tile_samples, n_tiles * 2, hipMemcpyHostToDevice, st), "upload samples");
+    }
+    if (rc == YK_OK) {
+        launch_pixel_table(st, ctx->tiles.as<yk_tile>(), ctx->tile_off.as<uint32_t>(), (uint32_t)n_tiles, total, l->pixel_xy.as<uint32_t>(),
+                           tile_samples ? ctx->tile_sample.as<uint16_t>() : nullptr, tile_samples ? l->pixel_sample.as<uint32_t>() : nullptr);
+        tryhip(hipGetLastError(), "pixel table kernel");
+        tryhip(hipStreamSynchronize(st), "sync");
+    }
+    if (rc != YK_OK) {
+        l->pixel_xy.release();
+        l->pixel_sample.release();
+        return rc;
+    }
+    *out = l.release();
+    return YK_OK;
+} YK_CATCH(ctx)
+
+void yk_tile_list_destroy(yk_tile_list* l) {
+    if (!l) return;
+    if (l->device >= 0) (void)hipSetDevice(l->device);
+    l->pixel_xy.release();
+    l->pixel_sample.release();
+    delete l;
+}
+
+// a prepared list: plain, with the passes of an accumulating list, or with a first sample index for every tile of a plain one
+static yk_status render_tile_list(yk_context* ctx, RenderRequest rq, const yk_tile_list* list, const char* wrong_list) {
+    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
+    if (!list) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null tile list");
+    if (wrong_list) return fail(ctx, YK_ERR_INVALID_ARGUMENT, wrong_list);
+    rq.list = list;
+    return render_tiles_impl(ctx, rq);
+}
+
+yk_status yk_render_tile_list_device(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler,
+                                     const yk_integrator_desc* integrator, const yk_tile_list* list, void* d_out_rgb, void* stream,
+                                     yk_render_stats* stats, yk_cancel_fn cancel, void* user) {
+    return render_tile_list(ctx, request_for(scene, camera, sampler, integrator, d_out_rgb, stream, stats, cancel, user), list, nullptr);
+}
+
+yk_status yk_render_tile_list_passes_device(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler,
+                                            const yk_integrator_desc* integrator, const yk_tile_list* list, uint32_t n_passes, void* d_out_rgb, void* stream,
+                                            yk_render_stats* stats, yk_cancel_fn cancel, void* user) {
+    RenderRequest rq = request_for(scene, camera, sampler, integrator, d_out_rgb, stream, stats, cancel, user);
+    rq.n_passes = n_passes;
+    return render_tile_list(ctx, rq, list, list && list->samples.empty() ? "passes need an accumulating tile list (tile_samples)" : nullptr);
+}
+
+yk_status yk_render_tile_list_samples_device(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler,
+                                             const yk_integrator_desc* integrator, const yk_tile_list* list, uint32_t first_sample, uint32_t n_passes,
+                                             void* d_out_rgb, void* stream, yk_render_stats* stats, yk_cancel_fn cancel, void* user) {
+    RenderRequest rq = request_for(scene, camera, sampler, integrator, d_out_rgb, stream, stats, cancel, user);
+    rq.n_passes = n_passes;
+    rq.uniform_first_sample = (int64_t)first_sample;
+    return render_tile_list(ctx, rq, list, list && !list->samples.empty() ? "the list carries per-tile sample indices: use yk_render_tile_list_passes_device" : nullptr);
+}
+
+// An interruption from any thread (the call that renders holds the context's lock for its whole duration, this one
+// takes none): what the context has enqueued stops at the kernels' next look at the word, the next submission waits
+// for it to drain and clears the word.
+yk_status yk_context_interrupt(yk_context* ctx) {
+    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
+    raise_cancel(ctx, false);  // the host word only: no HIP call from a thread that may not have the device current
+    return YK_OK;
+}
+
+yk_status yk_film_accumulate_tile_list_passes_device(yk_context* ctx, const yk_tile_list* list, const void* d_passes_rgb, uint32_t n_passes, uint16_t res_x,
+                                                     uint16_t res_y, void* d_film_rgb, void* stream) {
+    return film_update_list(ctx, list, d_passes_rgb, res_x, res_y, d_film_rgb, stream, 1, n_passes);
+}
+
+yk_status yk_film_update_tile_list_device(yk_context* ctx, const yk_tile_list* list, const void* d_tile_rgb, uint16_t res_x, uint16_t res_y,
+                                          void* d_film_rgb, void* stream, int accumulate) {
+    return film_update_list(ctx, list, d_tile_rgb, res_x, res_y, d_film_rgb, stream, accumulate, 1);
+}
+
+yk_status yk_film_update_tiles_device(yk_context* ctx, const yk_tile* tiles, size_t n_tiles, const void* d_tile_rgb, uint16_t res_x, uint16_t res_y,
+                                      void* d_film_rgb, void* stream) {
+    return film_tiles_device(ctx, tiles, n_tiles, d_tile_rgb, res_x, res_y, d_film_rgb, stream, 0);
+}
+
+yk_status yk_film_accumulate_tiles_device(yk_context* ctx, const yk_tile* tiles, size_t n_tiles, const void* d_tile_rgb, uint16_t res_x, uint16_t res_y,
+                                          void* d_film_rgb, void* stream) {
+    return film_tiles_device(ctx, tiles, n_tiles, d_tile_rgb, res_x, res_y, d_film_rgb, stream, 1);
 }
 
 yk_status yk_render_guides_device(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, uint16_t res_x, uint16_t res_y, void* d_guides, void* stream) {
@@ -827,8 +993,7 @@ yk_status yk_render_guides_ids_device(yk_context* ctx, const yk_scene* scene, co
     const size_t n_px = (size_t)res_x * res_y;
     if (d_guides && d_ids && overlaps(d_guides, n_px * sizeof(yk_guide), d_ids, n_px * sizeof(yk_surface_id)))
         return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_guides_ids_device: guides and ids overlap");
-    if (!d_ids) return render_guides(ctx, scene, camera, res_x, res_y, d_guides, stream);  // guides alone: yk_render_guides_device
-    return render_guides(ctx, scene, camera, res_x, res_y, d_guides, stream, d_ids);
+    return render_guides(ctx, scene, camera, res_x, res_y, d_guides, stream, d_ids);  // without ids: yk_render_guides_device
 }
 
 yk_status yk_render_guides_ids(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, uint16_t res_x, uint16_t res_y, yk_guide* out_guides, yk_surface_id* out_ids) {
@@ -845,120 +1010,37 @@ yk_status yk_render_guides_ids(yk_context* ctx, const yk_scene* scene, const yk_
     return sg.finish();
 }
 
-yk_status yk_render_tile(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler,
-                         const yk_integrator_desc* integrator, const yk_tile* tile, float* tile_pixels, uint64_t* out_rays) {
-    yk_render_stats stats;
-    yk_status st = yk_render_tiles(ctx, scene, camera, sampler, integrator, tile, 1, tile_pixels, &stats, nullptr, nullptr);
-    if (st == YK_OK && out_rays) *out_rays = stats.rays;
-    return st;
-}
-
-}  // extern "C"
-
-static yk_status film_tiles_device(yk_context* ctx, const yk_tile* tiles, size_t n_tiles, const void* d_tile_rgb, uint16_t res_x, uint16_t res_y,
-                                   void* d_film_rgb, void* stream, int accumulate);
-
-extern "C" {
-
-yk_status yk_film_update_tiles_device(yk_context* ctx, const yk_tile* tiles, size_t n_tiles, const void* d_tile_rgb, uint16_t res_x, uint16_t res_y,
-                                      void* d_film_rgb, void* stream) {
-    return film_tiles_device(ctx, tiles, n_tiles, d_tile_rgb, res_x, res_y, d_film_rgb, stream, 0);
-}
-
-yk_status yk_film_accumulate_tiles_device(yk_context* ctx, const yk_tile* tiles, size_t n_tiles, const void* d_tile_rgb, uint16_t res_x, uint16_t res_y,
-                                          void* d_film_rgb, void* stream) {
-    return film_tiles_device(ctx, tiles, n_tiles, d_tile_rgb, res_x, res_y, d_film_rgb, stream, 1);
-}
-
-}  // extern "C"
-
-static yk_status film_tiles_device(yk_context* ctx, const yk_tile* tiles, size_t n_tiles, const void* d_tile_rgb, uint16_t res_x, uint16_t res_y,
-                                   void* d_film_rgb, void* stream, int accumulate) try {
-    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
-    YK_LOCK(ctx);
-    if (!tiles || !d_tile_rgb || !d_film_rgb || n_tiles == 0) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null argument");
-    (void)hipSetDevice(ctx->device);
-    hipStream_t st = stream ? (hipStream_t)stream : ctx->stream;
-    std::vector<uint32_t> off(n_tiles + 1, 0);
-    uint64_t total = 0;
-    for (size_t t = 0; t < n_tiles; ++t) {
-        if (tiles[t].x1 > res_x || tiles[t].y1 > res_y || tiles[t].x0 >= tiles[t].x1 || tiles[t].y0 >= tiles[t].y1)
-            return fail(ctx, YK_ERR_INVALID_ARGUMENT, "update_tile: Tile doesn't fit film");
-        total += (uint64_t)(tiles[t].x1 - tiles[t].x0) * (uint64_t)(tiles[t].y1 - tiles[t].y0);
-        if (total > 0xFFFFFFFFull) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "too many pixels");
-        off[t + 1] = (uint32_t)total;
-    }
-    HIP_TRY(ctx, ctx->film_tiles.ensure(n_tiles * sizeof(yk_tile)));
-    HIP_TRY(ctx, ctx->film_tile_off.ensure((n_tiles + 1) * 4));
-    HIP_TRY(ctx, ctx->film_pixel_xy.ensure(total * 4));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->film_tiles.p, tiles, n_tiles * sizeof(yk_tile), hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->film_tile_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    launch_pixel_table(st, ctx->film_tiles.as<yk_tile>(), ctx->film_tile_off.as<uint32_t>(), (uint32_t)n_tiles, (uint32_t)total, ctx->film_pixel_xy.as<uint32_t>());
-    launch_film_scatter(st, ctx->film_pixel_xy.as<uint32_t>(), (uint32_t)total, reinterpret_cast<const float*>(d_tile_rgb), res_x,
-                        reinterpret_cast<float*>(d_film_rgb), accumulate);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    return YK_OK;
-} YK_CATCH(ctx)
-
-extern "C" {
-
 yk_status yk_li(yk_context* ctx, const yk_scene* scene, const yk_sampler_desc* sampler, const yk_integrator_desc* integrator, size_t n,
                 const float* ray_o, const float* ray_d, const uint16_t* pixel_xy, const uint32_t* sample_index, uint32_t dimension, float* out_li,
                 uint32_t* out_ray_counts) try {
     if (!ctx) return YK_ERR_INVALID_ARGUMENT;
     YK_LOCK(ctx);
-    if (!scene || !ray_o || !ray_d || !pixel_xy || !sample_index || !out_li || n == 0) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null argument");
-    if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "scene was not created on this context's device");
-    if (n > ((size_t)1 << 28)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "too many rays");
-    RenderParams prm;
-    yk_status ps = make_params(ctx, sampler, integrator, prm);
-    if (ps != YK_OK) return ps;
-    if (prm.integrator != YK_INTEGRATOR_PATH && prm.integrator != YK_INTEGRATOR_WHITTED)
-        return fail(ctx, YK_ERR_UNSUPPORTED, "yk_li implements the Path and Whitted integrators");
-    prm.spe = 1;  // one table entry (pixel, sample index) per ray
-    for (size_t i = 0; i < n; ++i)
-        if (sample_index[i] >= prm.sampler.spp) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "sample_index >= samples per pixel");
+    LiCall li{ctx, scene, n};
+    const bool accepted = integrator && (integrator->kind == YK_INTEGRATOR_PATH || integrator->kind == YK_INTEGRATOR_WHITTED);
+    yk_status rc = li.check(ray_o && ray_d && pixel_xy && sample_index && out_li, sampler, integrator, sample_index, nullptr,
+                            accepted ? nullptr : "yk_li implements the Path and Whitted integrators");
+    if (rc != YK_OK) return rc;
+    const RenderParams& prm = li.prm;  // no CancelRef in it and no clear_cancel before: yk_li neither honours nor reports an interruption
     if (prm.max_depth > YK_CTRL_MAX_DEPTH) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "max_depth too large");
     Staging sg(ctx);
     hipStream_t st = sg.stream;
-    yk_status wb = ensure_work_buffers(ctx, ctx->ws[0], n, scene->n_lights, scene->n_delta_lights);
-    if (wb != YK_OK) return wb;
-    if ((wb = ensure_spill(ctx, ctx->ws[0])) != YK_OK) return wb;
-    HIP_TRY(ctx, ctx->pixel_xy.ensure(n * 4));
-    HIP_TRY(ctx, ctx->sample_buf.ensure(n * 16));
-    const float* d_ray_o = sg.upload(ray_o, n * 3);
-    const float* d_ray_d = sg.upload(ray_d, n * 3);
-    const uint16_t* d_pixel_xy = sg.upload(pixel_xy, n * 2);
-    const uint32_t* d_sample_index = sg.upload(sample_index, n);
-    if (!sg.ok()) return sg.status();
-    unsigned* ctrl = ctx->ws[0].ctrl.as<unsigned>();
+    if ((rc = li.grow()) != YK_OK) return rc;
+    if ((rc = li.raygen(sg, ray_o, ray_d, pixel_xy, sample_index, dimension)) != YK_OK) return rc;
     unsigned long long* counters = ctx->counters.as<unsigned long long>();
-    HIP_TRY(ctx, hipMemsetAsync(counters, 0, YK_COUNTER_BYTES, st));
-    HIP_TRY(ctx, hipMemsetAsync(ctrl, 0, YK_CTRL_WORDS * 4, st));
-    launch_raygen_user(st, prm, d_ray_o, d_ray_d, d_pixel_xy, d_sample_index, dimension, (uint32_t)n, path_buffers(ctx->ws[0], 0), ctx->sample_buf.as<float4>(),
-                       ctx->pixel_xy.as<uint32_t>(), ctrl + YK_CTRL_BOUNCE(0));
     KernelTimer kt;
     kt.ctx = ctx;
     kt.on = false;
     if (prm.integrator == YK_INTEGRATOR_WHITTED)
-        launch_whitted(st, trace_grid(ctx), scene->dev, prm, ctx->pixel_xy.as<uint32_t>(), d_sample_index, path_buffers(ctx->ws[0], 0), (uint32_t)n,
+        launch_whitted(st, trace_grid(ctx), scene->dev, prm, ctx->pixel_xy.as<uint32_t>(), li.d_sample_index, path_buffers(ctx->ws[0], 0), (uint32_t)n,
                        ctx->sample_buf.as<float4>(), ctx->ws[0].spill.as<uint2>(), trace_grid(ctx) * trace_block_size(), error_block(ctx), counters);
     else
-        run_bounces(ctx, ctx->ws[0], st, scene, prm, ctx->pixel_xy.as<uint32_t>(), d_sample_index, ctx->sample_buf.as<float4>(), kt, counters, false, (uint32_t)n, 0u, false);
+        run_bounces(ctx, ctx->ws[0], st, scene, prm, ctx->pixel_xy.as<uint32_t>(), li.d_sample_index, ctx->sample_buf.as<float4>(), kt, counters, false, (uint32_t)n, 0u, false);
     HIP_TRY(ctx, hipGetLastError());
     std::vector<float> tmp(n * 4);
-    unsigned host_err[4];
     HIP_TRY(ctx, hipMemcpyAsync(tmp.data(), ctx->sample_buf.p, n * 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(host_err, error_block(ctx), sizeof(host_err), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(li.words, error_block(ctx), sizeof(li.words), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (host_err[YK_CTRL_ERR] & 1u) return fail(ctx, YK_ERR_STACK_OVERFLOW, "BVH traversal stack exceeded 64 entries (bvh.rs:174)");
-    for (size_t i = 0; i < n; ++i) {
-        out_li[3 * i] = tmp[4 * i];
-        out_li[3 * i + 1] = tmp[4 * i + 1];
-        out_li[3 * i + 2] = tmp[4 * i + 2];
-    }
+    if ((rc = li.verdict_and_rgb(tmp, out_li)) != YK_OK) return rc;
     if (out_ray_counts) std::memset(out_ray_counts, 0, n * 4);  // per-ray counts are not tracked by the wavefront
     return YK_OK;
 } YK_CATCH(ctx)
@@ -968,70 +1050,43 @@ yk_status yk_li_debug(yk_context* ctx, const yk_scene* scene, const yk_sampler_d
                       float* out_li, uint32_t* out_ray_counts, yk_integrator_ray* out_rays, uint32_t* out_n_rays) try {
     if (!ctx) return YK_ERR_INVALID_ARGUMENT;
     YK_LOCK(ctx);
-    if (!scene || !ray_o || !ray_d || !pixel_xy || !sample_index || !out_li || !out_n_rays || (ray_cap && !out_rays) || n == 0)
-        return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null argument");
-    if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "scene was not created on this context's device");
-    if (n > ((size_t)1 << 28)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "too many rays");
-    if ((uint64_t)n * ray_cap > YK_LI_DEBUG_MAX_RECORDS) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "n * ray_cap exceeds YK_LI_DEBUG_MAX_RECORDS");
-    RenderParams prm;
-    yk_status ps = make_params(ctx, sampler, integrator, prm);
-    if (ps != YK_OK) return ps;
-    if (prm.integrator != YK_INTEGRATOR_PATH) return fail(ctx, YK_ERR_UNSUPPORTED, "yk_li_debug implements the Path integrator (the others keep the trait's default)");
-    prm.spe = 1;  // one table entry (pixel, sample index) per ray
-    for (size_t i = 0; i < n; ++i)
-        if (sample_index[i] >= prm.sampler.spp) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "sample_index >= samples per pixel");
+    LiCall li{ctx, scene, n};
+    yk_status rc = li.check(ray_o && ray_d && pixel_xy && sample_index && out_li && out_n_rays && !(ray_cap && !out_rays), sampler, integrator, sample_index,
+                            (uint64_t)n * ray_cap > YK_LI_DEBUG_MAX_RECORDS ? "n * ray_cap exceeds YK_LI_DEBUG_MAX_RECORDS" : nullptr,
+                            integrator && integrator->kind == YK_INTEGRATOR_PATH ? nullptr : "yk_li_debug implements the Path integrator (the others keep the trait's default)");
+    if (rc != YK_OK) return rc;
     (void)hipSetDevice(ctx->device);
-    yk_status cs = clear_cancel(ctx);
-    if (cs != YK_OK) return cs;
+    if ((rc = clear_cancel(ctx)) != YK_OK) return rc;
     hipStream_t st = ctx->stream;
-    yk_status wb = ensure_work_buffers(ctx, ctx->ws[0], n, scene->n_lights, scene->n_delta_lights);
-    if (wb != YK_OK) return wb;
-    if ((wb = ensure_spill(ctx, ctx->ws[0])) != YK_OK) return wb;
+    if ((rc = li.grow()) != YK_OK) return rc;
+    li.prm.cancel = cancel_ref(ctx);  // an interruption stops the kernels and is reported below
     const size_t n_rec = (size_t)n * ray_cap, rec_bytes = n_rec * sizeof(yk_integrator_ray);
-    HIP_TRY(ctx, ctx->pixel_xy.ensure(n * 4));
-    HIP_TRY(ctx, ctx->sample_buf.ensure(n * 16));
     std::vector<float> tmp(n * 4);
     std::vector<uint32_t> counts(n), n_rays(n);
     Staging sg(ctx);
     yk_integrator_ray* d_rec = sg.temp<yk_integrator_ray>(std::max<size_t>(n_rec, 1));  // copied back only once the sample is known to be whole
     uint32_t* d_counts = sg.output(counts.data(), n);
     uint32_t* d_n_rays = sg.output(n_rays.data(), n);
-    const float* d_ray_o = sg.upload(ray_o, n * 3);
-    const float* d_ray_d = sg.upload(ray_d, n * 3);
-    const uint16_t* d_pixel_xy = sg.upload(pixel_xy, n * 2);
-    const uint32_t* d_sample_index = sg.upload(sample_index, n);
-    if (!sg.ok()) return sg.status();
-    unsigned* ctrl = ctx->ws[0].ctrl.as<unsigned>();
-    HIP_TRY(ctx, hipMemsetAsync(ctx->counters.p, 0, YK_COUNTER_BYTES, st));  // the error block with it: stack-overflow flag, interruption word
-    HIP_TRY(ctx, hipMemsetAsync(ctrl, 0, YK_CTRL_WORDS * 4, st));
+    if ((rc = li.raygen(sg, ray_o, ray_d, pixel_xy, sample_index, dimension)) != YK_OK) return rc;
     if (rec_bytes) HIP_TRY(ctx, hipMemsetAsync(d_rec, 0, rec_bytes, st));  // the slots a sample leaves unused read as zero
-    prm.cancel = cancel_ref(ctx);
-    launch_raygen_user(st, prm, d_ray_o, d_ray_d, d_pixel_xy, d_sample_index, dimension, (uint32_t)n, path_buffers(ctx->ws[0], 0), ctx->sample_buf.as<float4>(),
-                       ctx->pixel_xy.as<uint32_t>(), ctrl + YK_CTRL_BOUNCE(0));
     // path.rs:58-62: min_debug_ray_length, the root box's extent on Bounds3::maximum_extent (bounds.rs:147-156) / 10
     const float* lo = scene->dev.root_bmin;
     const float* hi = scene->dev.root_bmax;
     const float dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
     const int axis = (dx > dy && dx > dz) ? 0 : (dy > dz ? 1 : 2);
     const float min_len = (hi[axis] - lo[axis]) / 10.0f;
-    launch_path_debug(st, trace_grid(ctx), scene->dev, prm, ctx->pixel_xy.as<uint32_t>(), d_sample_index, path_buffers(ctx->ws[0], 0), (uint32_t)n,
+    launch_path_debug(st, trace_grid(ctx), scene->dev, li.prm, ctx->pixel_xy.as<uint32_t>(), li.d_sample_index, path_buffers(ctx->ws[0], 0), (uint32_t)n,
                       ctx->sample_buf.as<float4>(), d_counts, reinterpret_cast<float4*>(d_rec), ray_cap, d_n_rays, min_len,
                       ctx->ws[0].spill.as<uint2>(), trace_grid(ctx) * trace_block_size(), error_block(ctx));
     HIP_TRY(ctx, hipGetLastError());
-    unsigned host_err[4];
     HIP_TRY(ctx, hipMemcpyAsync(tmp.data(), ctx->sample_buf.p, n * 16, hipMemcpyDeviceToHost, st));
     sg.download();  // counts, n_rays
-    HIP_TRY(ctx, hipMemcpyAsync(host_err, error_block(ctx), sizeof(host_err), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(li.words, error_block(ctx), sizeof(li.words), hipMemcpyDeviceToHost, st));
     if (yk_status fs = sg.finish()) return fs;
-    if (ctx->cancel_raised.load(std::memory_order_acquire) || host_err[YK_CTRL_CANCELLED])
+    if (ctx->cancel_raised.load(std::memory_order_acquire) || li.words[YK_CTRL_CANCELLED])
         return fail(ctx, YK_ERR_CANCELLED, "interrupted (yk_context_interrupt)");
-    if (host_err[YK_CTRL_ERR] & 1u) return fail(ctx, YK_ERR_STACK_OVERFLOW, "BVH traversal stack exceeded 64 entries (bvh.rs:174)");
+    if ((rc = li.verdict_and_rgb(tmp, out_li)) != YK_OK) return rc;
     if (rec_bytes) HIP_TRY(ctx, hipMemcpy(out_rays, d_rec, rec_bytes, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < n; ++i) {
-        out_li[3 * i] = tmp[4 * i];
-        out_li[3 * i + 1] = tmp[4 * i + 1];
-        out_li[3 * i + 2] = tmp[4 * i + 2];
-    }
     if (out_ray_counts) std::memcpy(out_ray_counts, counts.data(), n * 4);
     std::memcpy(out_n_rays, n_rays.data(), n * 4);
     return YK_OK;
