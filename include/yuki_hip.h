@@ -560,7 +560,9 @@ yk_status yk_film_update_tiles_device(yk_context* ctx, const yk_tile* tiles, siz
                                       uint16_t res_x, uint16_t res_y, void* d_film_rgb, void* stream);
 /* Integrator::li (integrators/mod.rs:94-101) for n caller-supplied rays; the
  * sampler is started at (pixel, sample_index) and advanced by `dimension`
- * draws already consumed by the caller (2 for a camera ray). */
+ * draws already consumed by the caller (2 for a camera ray).  out_ray_counts (may be NULL): the closest-hit rays of every
+ * sample (RadianceResult::ray_scene_intersections) for Whitted; zeros for Path, whose wavefront keeps no per-sample
+ * count (yk_li_debug reports it). */
 yk_status yk_li(yk_context* ctx, const yk_scene* scene, const yk_sampler_desc* sampler, const yk_integrator_desc* integrator,
                 size_t n, const float* ray_o, const float* ray_d, const uint16_t* pixel_xy, const uint32_t* sample_index,
                 uint32_t dimension, float* out_li, uint32_t* out_ray_counts);
@@ -988,7 +990,9 @@ yk_status yk_trace_closest(yk_context* ctx, const yk_scene* scene, size_t n, con
 /* BoundingVolumeHierarchy::any_intersect (bvh.rs:235-302) */
 yk_status yk_trace_any(yk_context* ctx, const yk_scene* scene, size_t n, const float* ray_o, const float* ray_d,
                        const float* t_max, const int32_t* area_light /* NULL = none */, uint8_t* out_hit);
-/* Sampler start_pixel_sample + draws, evaluated on the device */
+/* Sampler start_pixel_sample + draws, evaluated on the device.  A sample_index at or past the samples per pixel is served as
+ * the reference computes it (accumulation runs past them), except for a stratified sampler whose samples per pixel are no
+ * power of two: there the reference's permutation walk need not end, and the call returns YK_ERR_INVALID_ARGUMENT. */
 yk_status yk_sampler_sequence(yk_context* ctx, const yk_sampler_desc* sampler, uint16_t px, uint16_t py, uint32_t sample_index,
                               const uint8_t* dims, size_t n_draws, float* out /* 2 per draw */);
 /* Camera::ray for every pixel of a tile at one sample index (camera.rs:105-114) */

@@ -1,5 +1,7 @@
 """Float64 physics for the shading path: BSDF lobes, Fresnel terms, microfacet distribution, light sampling, polygon
-irradiance and directional albedo, written from the published models in plain numpy.
+irradiance and directional albedo; the pinhole camera; the structure of the samplers; Whitted's recursion over a stack of
+panes; Russian roulette and what it does to path lengths and to per-sample radiance; a floor under a pane — written from the
+published models in plain numpy.
 
 Test infrastructure only.  Nothing here imports the oracle or the product, calls their arithmetic or follows their
 operation order: every function states the formula of its source (named in its docstring) in float64, so a term that
@@ -99,10 +101,43 @@ DEVIATIONS = [
         asserts="spot light has-visibility flag = (Li is not black)",
         live=("light/spot", "flag_mismatch"),
     ),
+    dict(
+        key="camera_window_named_axis", quirk=None, where="camera.rs:73-87",
+        sentence="The camera's screen window is +-1 along the axis the field of view names and +-1/aspect along the other; pbrt puts +-1 on the shorter axis.",
+        asserts="camera ray direction with the field of view measured along the named axis, whichever is longer",
+        live=("camera/x90", "d_angle_abs"),
+    ),
+    dict(
+        key="strata_row_divides_by_ny", quirk=None, where="sampling/stratified.rs:127-128",
+        sentence="A 2-D stratum s goes to cell (s % nx, s / ny), not (s % nx, s / nx): with nx != ny cells repeat and values leave [0,1).",
+        asserts="the cells floor(u * (nx, ny)) of the spp samples of a pixel are the multiset {(s % nx, s / ny)}",
+        live=("sampler/strata-2d-rect", "cells_mismatch"),
+    ),
+    dict(
+        key="uniform_streams_overlap", quirk=None, where="sampling/uniform.rs:81-83",
+        sentence="The uniform sampler seeks one per-pixel stream to sample_index * 65536 + dimension, so the draws of consecutive sample indices overlap after 65536 values.",
+        asserts="32768 two-dimensional draws into sample index i, the stream continues with the first draws of index i + 1",
+        live=("sampler/uniform", "seek_mismatch"),
+    ),
+    dict(
+        key="rr_green_channel", quirk=None, where="integrators/path.rs:163-169",
+        sentence="Russian roulette reads the green channel of beta, q = max(0.05, 1 - beta.g), where pbrt reads the largest component.",
+        asserts="path lengths in a closed Lambert sphere whose albedo's green is not its largest channel follow q from beta.g",
+        live=("rr-lengths/warm", "length_z"),
+    ),
+    dict(
+        key="sphere_wo_transformed_again", quirk=None, where="shapes/sphere.rs:115-116",
+        sentence="A sphere builds its SurfaceInteraction with the world-space -ray.d and then transforms it object-to-world, so on a rotated or mirrored sphere wo is transformed once too often.",
+        asserts="a rotated Lambert sphere under a point light is lit only where (M wo).n and l.n have the same sign",
+        live=("sphere-wo/rotated", "li_zero_mismatch"),
+    ),
 ]
 # Read in the reference and found to agree with pbrt-v3, hence no entries: the spot light's falloff (lights/spot_light.rs:38-50:
 # smooth (delta^2)^2 between cos_total_width and cos_falloff_start, 0 outside, 1 inside) and the rectangular light's emitting
-# side (lights/rectangular_light.rs:48-55: the side its normal (0,-1,0) faces, as DiffuseAreaLight's n.w > 0).
+# side (lights/rectangular_light.rs:48-55: the side its normal (0,-1,0) faces, as DiffuseAreaLight's n.w > 0); of the camera,
+# look_at (math/transforms.rs:138-153: right = up x dir, new_up = dir x right, pbrt-v3 §2.7.7 LookAt term for term, so the same
+# left-handed camera space) and the raster's y axis (camera.rs:88-93: 1 / (screen_min.y - screen_max.y), downwards as in
+# pbrt-v3 §6.2 ProjectiveCamera).  The mutation `camera_y_up` shows that the comparison would notice the second.
 
 DISTANT_WORLD_RADIUS = 10.0  # only what `textbook("distant_fixed_reach")` expects instead of the fixed reach
 
@@ -117,6 +152,16 @@ MUTATIONS = [
     "rect_pdf_without_cos",  # area-to-solid-angle pdf d^2 / A
     "snell_eta_inverted",  # refraction with eta_t / eta_i
     "sigma_to_degrees",  # Oren-Nayar's sigma converted as if it were wanted in degrees
+    "camera_tan_full_fov",  # screen scaled by tan(fov) for tan(fov / 2)
+    "camera_y_up",  # raster y counted upwards
+    "camera_window_on_shorter_axis",  # the +-1 of the screen window put on the shorter axis whatever the fov names
+    "strata_cell_transposed",  # a 2-D stratum's cell read as (row, column)
+    "whitted_child_over_pdf",  # a Whitted child weighted f |cos| / pdf with the path tracer's lobe pdf of 1/2
+    "whitted_eta2",  # a Whitted transmission child weighted by (eta_i / eta_t)^2
+    "rr_from_bounce_3",  # Russian roulette from bounces > 2
+    "rr_without_compensation",  # survivors not divided by 1 - q
+    "rr_floor_010",  # q = max(0.10, ...)
+    "clamp_after_beta",  # the indirect clamp applied to the fully weighted contribution
 ]
 _MUTATION = None
 _OFF = set()
@@ -601,3 +646,275 @@ def directional_albedo(m, cos_o, n_mu=1024, n_phi=512):
             w = w * wi[:, 2]
         total += (f * w[:, None]).sum(axis=0)
     return total
+
+
+# ----------------------------------------------------------------------------- camera
+FOV_X, FOV_Y = 0, 1
+
+
+def angle_between(a, b):
+    """Angle between vectors as atan2(|a x b|, a.b): accurate at angles near 0 and pi, where acos of the dot product is not."""
+    a, b = f64(a), f64(b)
+    return np.arctan2(np.linalg.norm(np.cross(a, b), axis=-1), dot(a, b))
+
+
+def camera_basis(cam):
+    """(right, up, forward) of a camera at `position` looking at `target` — pbrt-v3 §2.7.7 (LookAt): forward = normalize(target -
+    position), right = normalize(normalize(up) x forward), up' = forward x right; camera space is left-handed, +z forward."""
+    fwd = normalize(f64(cam["target"]) - f64(cam["position"]))
+    right = normalize(np.cross(normalize(cam["up"]), fwd))
+    return right, np.cross(fwd, right), fwd
+
+
+def camera_window(cam, res):
+    """Half extents (wx, wy) of the screen window — pbrt-v3 §6.2 (the window of a ProjectiveCamera) with the ledger's choice of
+    the axis that gets +-1; the other axis is scaled by the aspect ratio so that pixels are square."""
+    rx, ry = float(res[0]), float(res[1])
+    named_x = cam["fov_axis"] == FOV_X
+    if not _on("camera_window_named_axis") or _m("camera_window_on_shorter_axis"):
+        named_x = rx <= ry  # pbrt: the field of view spans the shorter axis
+    return (1.0, ry / rx) if named_x else (rx / ry, 1.0)
+
+
+def _camera_tan(cam):
+    fov = np.radians(float(np.float32(cam["fov_degrees"])))
+    return np.tan(fov if _m("camera_tan_full_fov") else 0.5 * fov)
+
+
+def camera_ray(cam, res, p_film):
+    """Pinhole camera — pbrt-v3 §6.2.2 (PerspectiveCamera::GenerateRay without a lens): the ray through raster point p starts
+    at the camera position and runs along normalize(forward + x_s t right + y_s t up'), t = tan(fov / 2), where (x_s, y_s) is p
+    mapped to the screen window with raster y pointing down.  -> (origin (n, 3), direction (n, 3))."""
+    p = f64(p_film)
+    right, upv, fwd = camera_basis(cam)
+    wx, wy = camera_window(cam, res)
+    t = _camera_tan(cam)
+    xs = (2.0 * p[:, 0] / float(res[0]) - 1.0) * wx
+    ys = (1.0 - 2.0 * p[:, 1] / float(res[1])) * wy
+    if _m("camera_y_up"):
+        ys = -ys
+    d = normalize(fwd[None, :] + (xs * t)[:, None] * right[None, :] + (ys * t)[:, None] * upv[None, :])
+    return np.broadcast_to(f64(cam["position"]), d.shape).copy(), d
+
+
+def camera_raster(cam, res, d):
+    """The inverse of camera_ray: the raster point a ray direction passes through."""
+    d = f64(d)
+    right, upv, fwd = camera_basis(cam)
+    wx, wy = camera_window(cam, res)
+    t = _camera_tan(cam)
+    z = d @ fwd
+    xs, ys = (d @ right) / z / t / wx, (d @ upv) / z / t / wy
+    if _m("camera_y_up"):
+        ys = -ys
+    return np.stack([(xs + 1.0) * 0.5 * float(res[0]), (1.0 - ys) * 0.5 * float(res[1])], axis=-1)
+
+
+def camera_fov_from_rays(cam, res, d_first, d_last):
+    """The full angle between the two film edges on the camera's fov axis, from the rays through the centres of the first and the
+    last pixel of that axis (any row / column): the screen coordinate (d.axis)/(d.forward) is linear in the raster coordinate and the
+    two pixel centres lie 1 - 1/res of the half width from the middle, so the edges' tangent follows by proportion."""
+    right, upv, fwd = camera_basis(cam)
+    axis, n = (right, res[0]) if cam["fov_axis"] == FOV_X else (upv, res[1])
+    s0, s1 = (f64(d_first) @ axis) / (f64(d_first) @ fwd), (f64(d_last) @ axis) / (f64(d_last) @ fwd)
+    return 2.0 * np.arctan(0.5 * abs(s1 - s0) / (1.0 - 1.0 / float(n)))
+
+
+# ----------------------------------------------------------------------------- samplers
+def strata_cell(stratum, nx, ny):
+    """Cell (x, y) of stratum s in an nx x ny grid — pbrt-v3 §7.3 (StratifiedSample2D numbers the cells row by row: s = y nx + x)."""
+    s = np.asarray(stratum, dtype=np.int64)
+    x, y = s % nx, s // (ny if _on("strata_row_divides_by_ny") else nx)
+    return (y, x) if _m("strata_cell_transposed") else (x, y)
+
+
+def uniform_moments_z(u):
+    """z values of the sample mean and the sample variance of n draws against U[0,1): mean 1/2 with variance 1/(12 n); the variance
+    estimate has mean 1/12 and variance (mu_4 - sigma^4)/n = (1/80 - 1/144)/n = 1/(180 n)."""
+    u = f64(u).ravel()
+    n = len(u)
+    return float((u.mean() - 0.5) / np.sqrt(1.0 / 12.0 / n)), float((((u - 0.5) ** 2).mean() - 1.0 / 12.0) / np.sqrt(1.0 / 180.0 / n))
+
+
+# ----------------------------------------------------------------------------- Whitted over a stack of panes
+SPAWN_OFFSET = 1e-3  # the ledger's `fixed_offset`
+
+
+def _interface(cos_in, inside, eta):
+    """(F seen by the arriving ray, F seen from the transmitted direction, cosine of the transmitted ray, total internal reflection)
+    at a smooth interface of a pane of index eta in air, for a ray arriving at |cos| = cos_in from inside or outside the glass —
+    pbrt-v3 §8.2.1-8.2.3."""
+    signed = -cos_in if inside else cos_in  # fresnel_dielectric: a negative cosine arrives from the eta side
+    f_in = float(fresnel_dielectric(signed, 1.0, eta))
+    sin_t = float(sin_theta_t(signed, 1.0, eta))
+    if sin_t >= 1.0:
+        return 1.0, 1.0, 0.0, True
+    cos_t = np.sqrt(1.0 - sin_t * sin_t)
+    return f_in, float(fresnel_dielectric(cos_t if inside else -cos_t, 1.0, eta)), cos_t, False
+
+
+def whitted_stack(panes, eta, R, T, cos_start, start_y, start_inside, max_depth):
+    """Whitted's recursion (Whitted 1980; pbrt-v3 §14.2 WhittedIntegrator::Li with SpecularReflect / SpecularTransmit) over
+    horizontal panes [(y_bottom, y_top), ...] of index eta above a matte floor at y = 0, for a ray that starts at height start_y
+    going DOWN at |cos| = cos_start to the vertical, in the glass or in air.  Every hit on glass spawns a reflection child of
+    weight R F and, unless totally reflected, a transmission child of weight T (1 - F): f |cos|, no pdf, no eta^2 (the ledger's
+    `no_eta2_transmission`), while depth + 1 < max_depth.  Children start SPAWN_OFFSET off the surface on their own side (the
+    ledger's `fixed_offset`).  The rays stay in their vertical plane of incidence, so a leaf is described by its weight and the
+    horizontal distance travelled along the ray's heading.
+    -> (RGB weight reaching the background, [(RGB weight, horizontal distance) of every floor hit], closest-hit rays, the
+    largest horizontal distance any ray reached)."""
+    R, T = f64(R), f64(T)
+    faces = sorted([y for pane in panes for y in pane] + [0.0])
+    off = SPAWN_OFFSET if _on("fixed_offset") else 0.0
+    cos_of, tan_of, iface = {}, {}, {}
+    f_in, f_out, cos_t, tir = _interface(cos_start, start_inside, eta)
+    cos_of[start_inside] = cos_start
+    if not tir:
+        cos_of[not start_inside] = cos_t
+    for inside, c in cos_of.items():
+        tan_of[inside] = np.sqrt(max(0.0, 1.0 - c * c)) / c
+        iface[inside] = _interface(c, inside, eta)
+    over_pdf = 2.0 if _m("whitted_child_over_pdf") else 1.0
+    background, floor, reach = np.zeros(3), [], [0.0]
+
+    def trace(y, up, inside, depth, weight, s):
+        ahead = [f for f in faces if (f > y if up else f < y)]
+        if not ahead:
+            background[:] += weight
+            return 1
+        hit = min(ahead) if up else max(ahead)
+        s = s + abs(hit - y) * tan_of[inside]
+        reach[0] = max(reach[0], s)
+        if hit == 0.0:
+            floor.append((weight, s))
+            return 1
+        rays = 1
+        if depth + 1 < max_depth:
+            f_here, f_there, _, total = iface[inside]
+            rays += trace(hit + (-off if up else off), not up, inside, depth + 1, weight * R * (f_here * over_pdf), s)
+            if not total:
+                w = T * ((1.0 - f_there) * over_pdf)
+                if not _on("no_eta2_transmission") or _m("whitted_eta2"):
+                    w = w * ((eta if inside else 1.0 / eta) ** 2)  # (eta_i / eta_t)^2 along the path
+                rays += trace(hit + (off if up else -off), up, not inside, depth + 1, weight * w, s)
+        return rays
+
+    n = trace(start_y, False, start_inside, 0, np.ones(3), 0.0)
+    return background, floor, n, reach[0]
+
+
+# ----------------------------------------------------------------------------- Russian roulette
+def rr_rule(beta, bounce):
+    """Termination probability after the vertex of `bounce` (0 = the camera ray's hit), None when the roulette is not played —
+    pbrt-v3 §14.5.4 (PathIntegrator::Li, "Possibly terminate the path with Russian roulette"): from bounces > 3,
+    q = max(0.05, 1 - the largest component of beta), survivors divided by 1 - q; the ledger reads green instead."""
+    if not bounce > (2 if _m("rr_from_bounce_3") else 3):
+        return None
+    b = float(beta[1]) if _on("rr_green_channel") else float(np.max(beta))
+    return max(0.10 if _m("rr_floor_010") else 0.05, 1.0 - b)
+
+
+def rr_survive(beta, q):
+    return f64(beta) if _m("rr_without_compensation") else f64(beta) / (1.0 - q)
+
+
+def rr_length_distribution(rho, max_depth):
+    """{rays traced: probability} of a path that hits a Lambert surface of albedo rho at every vertex and finds no light: cosine
+    sampling makes f cos / pdf = rho exactly, so beta is deterministic and only the roulette ends a path before max_depth."""
+    rho = f64(np.asarray(rho, dtype=np.float32))
+    beta, alive, out = np.ones(3), 1.0, {}
+    for bounce in range(max_depth):
+        beta = beta * rho
+        q = rr_rule(beta, bounce)
+        if q is not None and bounce + 1 < max_depth:
+            out[bounce + 1] = alive * q
+            alive *= 1.0 - q
+            beta = rr_survive(beta, q)
+    out[max_depth] = alive
+    return {k: v for k, v in out.items() if v > 0}
+
+
+def slab_path_classes(cos_in, eta, max_depth):
+    """[(li / B, probability)] of one path-traced sample through a clear pane (R = T = 1) of index eta in air under a uniform
+    background B, no lights: every sequence of the uniform lobe choice (probability 1/2 each, weight F / 0.5 or (1 - F) / 0.5 — the
+    ledger's `lobe_choice_uniform`) and every roulette outcome is followed; a path that leaves the pane collects beta B when its
+    next ray is traced, one that is ended by the roulette or by max_depth collects nothing.  Equal values are merged."""
+    f_in, f_out, cos_t, tir = _interface(cos_in, False, eta)
+    assert not tir
+    f_glass = _interface(cos_t, True, eta)
+    classes = {}
+
+    def add(value, p):
+        key = round(value, 12)
+        classes[key] = classes.get(key, 0.0) + p
+
+    def trace(bounce, beta, p, inside, escaped):
+        if bounce >= max_depth:
+            return add(0.0, p)
+        if escaped:
+            return add(beta, p)
+        f_here, f_there = (f_glass[0], f_glass[1]) if inside else (f_in, f_out)
+        for reflect in (True, False):
+            b = beta * ((f_here if reflect else 1.0 - f_there) / 0.5)
+            pr = 0.5 * p
+            q = rr_rule(np.full(3, b), bounce)
+            if q is not None:
+                add(0.0, pr * q)
+                pr *= 1.0 - q
+                b = float(rr_survive(np.full(3, b), q)[0])
+            if pr > 0.0:
+                trace(bounce + 1, b, pr, inside if reflect else not inside, escaped=(reflect != inside))
+
+    trace(0, 1.0, 1.0, False, False)
+    return sorted(classes.items())
+
+
+def clamped_emission(beta, le, clamp):
+    """Emission found after a specular bounce under the reference's `indirect_clamp` (integrators/path.rs:121-129, a parameter of
+    its own; pbrt has none): the radiance of the vertex, which already carries beta once (the ledger's `emission_beta_squared`), is
+    clamped per channel, then weighted by beta like every vertex."""
+    le = f64(le)
+    if _m("clamp_after_beta"):
+        return np.minimum(beta * beta * le, clamp)
+    inner = beta * le if _on("emission_beta_squared") else le
+    return beta * np.minimum(inner, clamp)
+
+
+# ----------------------------------------------------------------------------- a Lambert floor under a clear pane
+def pane_terms(eta, n_vertices, n_mu=4096):
+    """Cosine-weighted hemispherical means, by the midpoint rule over mu^2, of what a clear pane of index eta does to light that
+    arrives from one side: r[j] / t[j] = the part that returns / passes after exactly j specular vertices (Stokes' sum over the
+    inter-reflections, e.g. Born and Wolf §7.6.1 without interference): r[1] = F, r[j] = (1-F)^2 F^(j-2) for odd j >= 3,
+    t[j] = (1-F)^2 F^(j-2) for even j.  Their sums are R = 2F / (1+F) and T = 1 - R.  -> (r, t, R mean, T mean)."""
+    x = (np.arange(n_mu) + 0.5) / n_mu  # x = mu^2: the cosine-weighted measure 2 mu d mu is d x
+    f = fresnel_dielectric(np.sqrt(x), 1.0, eta)
+    r, t = np.zeros(n_vertices + 1), np.zeros(n_vertices + 1)
+    for j in range(1, n_vertices + 1):
+        if j == 1:
+            r[j] = f.mean()
+        elif j % 2:
+            r[j] = ((1.0 - f) ** 2 * f ** (j - 2)).mean()
+        else:
+            t[j] = ((1.0 - f) ** 2 * f ** (j - 2)).mean()
+    big_r = 2.0 * f / (1.0 + f)
+    return r, t, float(big_r.mean()), float(1.0 - big_r.mean())
+
+
+def floor_under_pane(rho, eta, max_depth=None):
+    """Radiance, in units of the background's, leaving a Lambert floor of albedo rho under an infinite clear pane: the floor sees
+    the background through the pane and itself in it, L = rho (T B + R L), so L = rho T B / (1 - rho R) with the means of pane_terms.
+    With `max_depth`: the expectation of a path tracer that traces at most that many rays and starts with the ray that hits the
+    floor; the floor's diffuse bounce makes every return to it a renewal, so the truncated value follows by recursion over the bounce
+    index of the floor vertex.  (The roulette changes no expectation.)"""
+    rho = f64(rho)
+    if max_depth is None:
+        _, _, rm, tm = pane_terms(eta, 1)
+        return rho * tm / (1.0 - rho * rm)
+    r, t, _, _ = pane_terms(eta, max_depth)
+    value = np.zeros((max_depth + 1, len(rho)))  # value[d]: radiance gathered from a floor vertex hit by the ray of bounce d
+    for d in range(max_depth - 1, -1, -1):
+        acc = np.zeros(len(rho))
+        for j in range(1, max_depth - d):  # the ray after j pane vertices is ray d + j and must still be traced
+            acc += t[j] + r[j] * value[d + j]
+        value[d] = rho * acc
+    return value[0]

@@ -81,20 +81,48 @@ def test_device_sqrt_div_are_correctly_rounded(ctx, yk):
         assert np.array_equal(_bits(yk.device_math(ctx, 7, a, b)), _bits(a / b))
 
 
-@pytest.mark.parametrize("kind", ["uniform", "stratified", "stratified_nojitter"])
+SAMPLER_EDGE_GRIDS = [(4, 2), (2, 4), (5, 3), (1, 7)]
+SAMPLER_KINDS = ["uniform", "stratified", "stratified_nojitter"] + [f"{k}-{nx}x{ny}" for nx, ny in SAMPLER_EDGE_GRIDS for k in ("stratified", "stratified_nojitter")]
+
+
+@pytest.mark.parametrize("kind", SAMPLER_KINDS)
 def test_sampler_sequence(ctx, yk, oracle, kind):
-    if kind == "uniform":
-        s = yk.SamplerType.Uniform(16, SEED)
-    else:
-        s = yk.SamplerType.Stratified((8, 8), kind == "stratified", SEED)
-    dims = np.array([2, 2, 2, 2, 1, 2, 2, 1, 1, 2] * 4, dtype=np.uint8)
+    """A 40-entry mix of 1-D and 2-D draws, bit for bit: the first, a middle and the last sample index at four pixels, then at
+    pixels (0,0), (17,1033) and (65535,65535) the sample indices spp-1, spp, 3 spp + 1 (accumulation runs past spp) and 2^20, the
+    last of which reaches the high word of the generator's 64-bit seek.  A stratified sampler whose spp is no power of two has no
+    answer past spp — the reference's permutation walk need not end there, and does not for (5,3) and (1,7) at index spp, as the
+    Python restatement of tests/test_oracle_sampler.py shows — so there the device must refuse the call, and nothing is run."""
     import ctypes as C
 
-    for px, py, idx in [(0, 0, 0), (17, 1033, 5), (1919, 1079, 15), (65535, 65535, 3)]:
+    from test_oracle_sampler import stratum_py
+
+    name, _, grid = kind.partition("-")
+    nx, ny = (int(v) for v in grid.split("x")) if grid else (8, 8)
+    if name == "uniform":
+        s = yk.SamplerType.Uniform(16, SEED)
+        spp = 16
+    else:
+        s = yk.SamplerType.Stratified((nx, ny), name == "stratified", SEED)
+        spp = nx * ny
+    dims = np.array([2, 2, 2, 2, 1, 2, 2, 1, 1, 2] * 4, dtype=np.uint8)
+    dimension_of = np.concatenate([[0], np.cumsum(dims)[:-1]])
+    cases = [(0, 0, 0), (17, 1033, 5 % spp), (1919, 1079, 15 % spp), (65535, 65535, 3 % spp)]
+    cases += [(px, py, idx) for px, py in [(0, 0), (17, 1033), (65535, 65535)] for idx in (spp - 1, spp, 3 * spp + 1, 1 << 20)]
+    refused = 0
+    for px, py, idx in cases:
+        if name != "uniform" and idx >= spp and spp & (spp - 1):
+            with pytest.raises(yk.YukiError) as e:
+                yk.sampler_sequence(ctx, s, px, py, idx, dims)
+            assert e.value.status == 1, e.value  # YK_ERR_INVALID_ARGUMENT
+            refused += 1
+            continue
+        if name != "uniform":  # the walk ends at every dimension used, by Python integers, before anything runs it
+            assert all(stratum_py(px, py, int(d), SEED, idx, spp, max_walk=64) is not None for d in dimension_of), (kind, px, py, idx)
         got = yk.sampler_sequence(ctx, s, px, py, idx, dims)
         want = np.zeros((len(dims), 2), dtype=np.float32)
         oracle.lib().orc_sampler_sequence(C.byref(s), px, py, idx, dims.ctypes.data_as(C.c_void_p), len(dims), want.ctypes.data_as(C.c_void_p))
         assert np.array_equal(_bits(got), _bits(want)), (kind, px, py, idx)
+    assert refused == (9 if name != "uniform" and spp & (spp - 1) else 0)
 
 
 def test_camera_rays(ctx, yk, oracle):

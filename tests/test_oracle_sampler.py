@@ -46,6 +46,67 @@ def siphash_py(key, msg, c_rounds, d_rounds):
     return v0 ^ v1 ^ v2 ^ v3
 
 
+def permutation_element_py(i, l, p, max_walk=None):
+    """Kensler's permutation of 0 .. l-1 keyed by p ("Correlated Multi-Jittered Sampling", Pixar technical memo 13-01,
+    listing `permute`), in Python integers: a bijection of the next power of two, walked until it lands below l.
+    `max_walk` bounds the walk (None = unbounded): for i >= l the walk starts outside the domain, may enter a cycle that
+    lies wholly in l .. w and then never ends; -> None when the bound is reached."""
+    m = 0xFFFFFFFF
+    w = l - 1
+    for s in (1, 2, 4, 8, 16):
+        w |= w >> s
+    walked = 0
+    while True:
+        i ^= p
+        i = (i * 0xE170893D) & m
+        i ^= p >> 16
+        i ^= (i & w) >> 4
+        i ^= p >> 8
+        i = (i * 0x0929EB3F) & m
+        i ^= p >> 23
+        i ^= (i & w) >> 1
+        i = (i * (1 | p >> 27)) & m
+        i = (i * 0x6935FA69) & m
+        i ^= (i & w) >> 11
+        i = (i * 0x74DCB303) & m
+        i ^= (i & w) >> 2
+        i = (i * 0x9E501CC3) & m
+        i ^= (i & w) >> 2
+        i = (i * 0xC860A3DF) & m
+        i &= w
+        i ^= i >> 5
+        if i < l:
+            return ((i + p) & m) % l
+        walked += 1
+        if max_walk is not None and walked >= max_walk:
+            return None
+
+
+def stratum_py(px, py, dimension, seed, sample_index, spp, max_walk=None):
+    """The stratum a stratified draw at `dimension` uses: permutation_element(sample_index, spp, low 32 bits of
+    SipHash-1-3(pixel u16 x 2, dimension u32, seed u64)) (stratified.rs:105-106, 122-123)."""
+    h = siphash_py(bytes(16), struct.pack("<HHIQ", px, py, dimension, seed), 1, 3)
+    return permutation_element_py(sample_index, spp, h & 0xFFFFFFFF, max_walk)
+
+
+def test_python_permutation_restatement_matches_the_oracle(oracle):
+    L = oracle.lib()
+    rng = np.random.default_rng(11)
+    for l in (1, 2, 3, 4, 7, 8, 9, 15, 25, 64, 100):
+        for p in [0, 1, 0xDEADBEEF, 0xFFFFFFFF] + [int(v) for v in rng.integers(0, 1 << 32, 8)]:
+            for i in range(l):
+                assert L.orc_permutation_element(i, l, p) == permutation_element_py(i, l, p), (i, l, p)
+
+
+def test_permutation_walk_past_spp_need_not_end():
+    """Why tests/test_gpu_stages.py::test_sampler_sequence expects a refusal: at sample index spp the walk of Kensler's
+    permutation is still going after 10,000 steps for some dimension of every pixel tried, for both grids whose spp is no
+    power of two."""
+    for nx, ny in ((5, 3), (1, 7)):
+        for px, py in [(0, 0), (17, 1033), (65535, 65535)]:
+            assert any(stratum_py(px, py, d, 0x73B9642E74AC471C, nx * ny, nx * ny, max_walk=10000) is None for d in range(70)), (nx, ny, px, py)
+
+
 def test_python_siphash_restatement_against_the_paper_vector():
     # SipHash-2-4 reference vector (Aumasson & Bernstein, Appendix A): key 00..0f, msg 00..0e
     assert siphash_py(bytes(range(16)), bytes(range(15)), 2, 4) == 0xA129CA6149BE45E5

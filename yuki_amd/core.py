@@ -1458,15 +1458,17 @@ class Integrator:
         )
         return stats if want_stats else None
 
-    def li(self, scene, sampler, ray_o, ray_d, pixel_xy, sample_index, dimension=2):
-        """Integrator::li for caller-supplied rays (integrators/mod.rs:94-101)."""
+    def li(self, scene, sampler, ray_o, ray_d, pixel_xy, sample_index, dimension=2, ray_counts=False):
+        """Integrator::li for caller-supplied rays (integrators/mod.rs:94-101).  With `ray_counts`: (li, the closest-hit rays
+        every sample traced (n,) uint32 — RadianceResult::ray_scene_intersections; Whitted only, zeros for Path, see yk_li)."""
         o = np.ascontiguousarray(ray_o, dtype=np.float32)
         d = np.ascontiguousarray(ray_d, dtype=np.float32)
         pix = np.ascontiguousarray(pixel_xy, dtype=np.uint16)
         si = np.ascontiguousarray(sample_index, dtype=np.uint32)
         out = np.zeros((o.shape[0], 3), dtype=np.float32)
-        check(lib().yk_li(self.ctx.h, scene.h, C.byref(sampler), C.byref(self.desc), o.shape[0], _p(o), _p(d), _p(pix), _p(si), dimension, _p(out), None), self.ctx.h)
-        return out
+        counts = np.zeros(o.shape[0], dtype=np.uint32) if ray_counts else None
+        check(lib().yk_li(self.ctx.h, scene.h, C.byref(sampler), C.byref(self.desc), o.shape[0], _p(o), _p(d), _p(pix), _p(si), dimension, _p(out), _p(counts)), self.ctx.h)
+        return (out, counts) if ray_counts else out
 
     def li_debug(self, scene, sampler, ray_o, ray_d, pixel_xy, sample_index, dimension=2):
         """Integrator::li_debug (integrators/mod.rs:103-115), Path only: returns (li (n,3), ray_counts (n,), rays), where

@@ -17,7 +17,8 @@
 //     vis[i*VS+l]                  0 none, 1 pending/visible, 2 occluded; VS = YK_VIS_STRIDE(n_lights): 4 bytes per path for up to 4 lights
 //     shq[k]                       compacted list of pending shadow slots
 //   per chunk:
-//     sample_buf[sample_id] = (L.r, L.g, L.b, -)    radiance of one camera sample (Path: first written by k_accumulate of the camera bounce)
+//     sample_buf[sample_id] = (L.r, L.g, L.b, w)   radiance of one camera sample (Path: first written by k_accumulate of the camera bounce;
+//                                                   w: unused, but for k_whitted's count of the sample's closest-hit rays, as bits, for yk_li)
 //     pixel_xy[pixel]       = x | y<<16             pixel of each chunk-local pixel index
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1041,7 +1041,11 @@ yk_status yk_li(yk_context* ctx, const yk_scene* scene, const yk_sampler_desc* s
     HIP_TRY(ctx, hipMemcpyAsync(li.words, error_block(ctx), sizeof(li.words), hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     if ((rc = li.verdict_and_rgb(tmp, out_li)) != YK_OK) return rc;
-    if (out_ray_counts) std::memset(out_ray_counts, 0, n * 4);  // per-ray counts are not tracked by the wavefront
+    // k_whitted leaves every sample's closest-hit ray count in the sample's fourth word; the wavefront tracks none per sample
+    for (size_t i = 0; out_ray_counts && i < n; ++i) {
+        out_ray_counts[i] = 0;
+        if (prm.integrator == YK_INTEGRATOR_WHITTED) std::memcpy(out_ray_counts + i, tmp.data() + 4 * i + 3, 4);
+    }
     return YK_OK;
 } YK_CATCH(ctx)
 

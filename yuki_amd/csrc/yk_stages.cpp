@@ -191,6 +191,12 @@ yk_status yk_sampler_sequence(yk_context* ctx, const yk_sampler_desc* sampler, u
     yk_integrator_desc dummy = {YK_INTEGRATOR_PATH, 1, 0, 0.0f};
     yk_status ps = make_params(ctx, sampler, &dummy, prm);
     if (ps != YK_OK) return ps;
+    // permutation_element (stratified.rs:147-178) walks a bijection of the next power of two until it lands below spp.  From an
+    // index below spp the walk returns to it at the latest; from one at or past spp it may enter a cycle that lies wholly in
+    // spp .. 2^k - 1 and never end, so those are refused here as the render entry points refuse them (a power of two has no such cycle).
+    const uint32_t spp = prm.sampler.spp;
+    if (sampler->kind == YK_SAMPLER_STRATIFIED && sample_index >= spp && (spp & (spp - 1)) != 0)
+        return fail(ctx, YK_ERR_INVALID_ARGUMENT, "stratified sample_index >= samples per pixel, and that is no power of two: the permutation walk need not end");
     Staging sg(ctx);
     const uint8_t* d_dims = sg.upload(dims, n_draws);
     float* d_out = sg.output(out, n_draws * 2);

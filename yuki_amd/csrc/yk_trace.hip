@@ -622,9 +622,11 @@ __global__ __launch_bounds__(BLOCK) void k_whitted(DevScene sc, RenderParams prm
         int sp = 0;  // frames on the stack = depth of the call being evaluated
         bool is_specular = false;
         RGB ret = RGB{0.0f, 0.0f, 0.0f};
+        unsigned sample_rays = 0;  // RadianceResult::ray_scene_intersections of this sample (whitted.rs:174-178)
         for (;;) {
             // ---- call: li_internal(ray (o, d), depth = sp, is_specular)
             n_rays += 1;
+            sample_rays += 1;
             int shape;
             TriHit th = TriHit{0.0f, 0.0f, 0.0f, 0.0f};
             traverse_closest<false>(sc, ray_setup(o, d, __builtin_inff()), stk, shape, th, nullptr, err);
@@ -711,7 +713,7 @@ __global__ __launch_bounds__(BLOCK) void k_whitted(DevScene sc, RenderParams prm
             }
             if (!again) break;
         }
-        sample_buf[sid] = make_float4(ret.r, ret.g, ret.b, 0.0f);
+        sample_buf[sid] = make_float4(ret.r, ret.g, ret.b, __uint_as_float(sample_rays));  // .w: read by yk_li alone, as bits
     }
     // ray counts: one atomic per wave
     for (int off = 32; off > 0; off >>= 1) {
