@@ -981,6 +981,106 @@ yk_status yk_denoise_variance_device(yk_context* ctx, const yk_variance_desc* de
                                      const void* d_variance, const void* d_albedo, uint16_t res_x, uint16_t res_y, uint16_t tile_dim,
                                      const uint32_t* samples, void* d_out_rgb, void* stream);
 
+/* ---- adaptive sampling: per-pixel statistics choose where the next samples go ----
+ * The accumulating entry points give every pixel of a tile the same number of samples.  Here a film carries, beside its
+ * RGB sums, one yk_pixel_stats record a pixel; a selection pass lists the pixels that are still noisy, a render takes that
+ * list as it is, and a fold adds the results to the film and the statistics.  The library's own rule (the reference has
+ * no adaptive sampler), stated next to each expression in yuki_amd/csrc/yk_adaptive.h; the host and the device instance
+ * agree bit for bit, the order of the list included (binary32, every operation separate, no FMA, divisions correctly
+ * rounded, a NaN an operation produces is 0x7fc00000).
+ * Luminance l(c) = (0.2126f*r + 0.7152f*g) + 0.0722f*b (yk_variance's).
+ * Fold of one sample c: drawn += 1 always; ll = l(c)*l(c) NaN or infinite: nothing else changes (a non-finite sample never
+ *   enters the film or the statistics); otherwise film_sum += c (three adds), n += 1, d = l - mean,
+ *   mean' = mean + d / (float)n, m2' = m2 + d * (l - mean')  (Welford, in sample order).
+ * Wants: n < min_samples, or m2 > (threshold^2 * ((nf - 1) * nf)) * ((mean + epsilon) * (mean + epsilon)), nf = (float)n,
+ *   threshold^2 computed once: (standard error of the mean) > threshold * (mean + epsilon), squared.  NaN compares false.
+ * Selected: eligible (drawn + round_passes <= max_samples) and (wants, or dilate and one of the 8 neighbours inside the
+ *   film wants — eligible itself or not).
+ * Order of the list: tiles of 16 x 16 (a constant of the rule, not a film's tile_dim) over the ceil grid in row-major
+ *   tile order, row-major inside a tile, clipped at the film's edges.  Entry = (x | y << 16, drawn).
+ * Resolve: rgb = film_sum / (float)n where n > 0, zeros otherwise; variance of the mean = m2 / ((nf - 1) * nf) where
+ *   n >= 2, +inf otherwise, NaN or negative written as 0: the image yk_denoise_variance takes as `variance`.
+ * All zeros is the cleared state of film_sum and of the statistics.
+ * Limits: luminance only; yk_multi scenes are not served; selecting on the samples' own variance biases the estimate
+ *   slightly (the dilation and the floor on min_samples bound that, they do not remove it). */
+typedef struct yk_pixel_stats {
+    float mean;     /* running mean of the luminance of the samples taken */
+    float m2;       /* sum of squared deviations from it */
+    uint32_t n;     /* samples taken */
+    uint32_t drawn; /* sample indices consumed: the pixel's next sample index */
+} yk_pixel_stats;   /* 16 bytes; 16-byte aligned on the device */
+typedef struct yk_adaptive_desc {
+    uint32_t min_samples;  /* >= 2 */
+    uint32_t max_samples;  /* min_samples .. 2^24 */
+    uint32_t round_passes; /* 1 .. 0xFFFF: samples a selected pixel takes per round */
+    uint32_t max_rounds;   /* yk_render_adaptive_device: 0 = until nothing is selected */
+    uint32_t dilate;       /* 0 | 1 */
+    float threshold;       /* > 0 */
+    float epsilon;         /* >= 0 */
+} yk_adaptive_desc;
+typedef struct yk_adaptive_info {
+    uint32_t rounds;       /* rounds rendered by this call */
+    uint32_t converged;    /* 1: the last selection was empty; 0: max_rounds stopped the call */
+    uint32_t first_pixels; /* entries of the first round's list */
+    uint32_t last_pixels;  /* entries of the last rendered round's list */
+    uint64_t samples, rays, shadow_rays;
+} yk_adaptive_info;
+/* A list of (pixel, first sample index) entries in device memory with room for res_x * res_y of them: filled by
+ * yk_adaptive_select_device or yk_pixel_list_set, rendered by yk_render_pixel_list_device.  It belongs to `ctx` and must be
+ * destroyed before it. */
+typedef struct yk_pixel_list yk_pixel_list;
+yk_status yk_pixel_list_create(yk_context* ctx, uint16_t res_x, uint16_t res_y, yk_pixel_list** out);
+void yk_pixel_list_destroy(yk_pixel_list* list);
+/* Host entries (xy = x | y << 16), checked on the host before the upload: every pixel inside the list's resolution, no pixel
+ * twice, passes 1 .. 0xFFFF, sample + passes <= 2^24 (else YK_ERR_INVALID_ARGUMENT and the list is left as it was).
+ * n may be 0.  Synchronous. */
+yk_status yk_pixel_list_set(yk_pixel_list* list, const uint32_t* xy, const uint32_t* sample, uint32_t n, uint32_t passes);
+/* The entries back on the host (either array may be NULL), at most `cap`; *out_n = the list's entry count. */
+yk_status yk_pixel_list_read(const yk_pixel_list* list, uint32_t* out_xy, uint32_t* out_sample, uint32_t cap, uint32_t* out_n);
+/* The selection.  out_xy / out_sample hold res_x * res_y words each (either may be NULL); *out_n = the number selected.
+ * ctx NULL = the host instance.  YK_ERR_INVALID_ARGUMENT: a NULL desc, stats or out_n, a zero resolution, min_samples < 2,
+ * max_samples < min_samples or > 2^24, round_passes 0 or > 0xFFFF, dilate > 1, threshold <= 0 or NaN, epsilon < 0 or NaN. */
+yk_status yk_adaptive_select(yk_context* ctx, const yk_adaptive_desc* desc, const yk_pixel_stats* stats, uint16_t res_x, uint16_t res_y,
+                             uint32_t* out_xy, uint32_t* out_sample, uint32_t* out_n);
+/* The same on device statistics (16-byte aligned) into a list of the same resolution (anything else:
+ * YK_ERR_INVALID_ARGUMENT, nothing is launched): three launches on `stream` (NULL = the context's), then the count is read
+ * back — 4 bytes, one stream synchronisation — into *out_n and the list, with passes = round_passes and
+ * sample_end = max_samples. */
+yk_status yk_adaptive_select_device(yk_context* ctx, const yk_adaptive_desc* desc, const void* d_stats, uint16_t res_x, uint16_t res_y,
+                                    yk_pixel_list* list, uint32_t* out_n, void* stream);
+/* The fold: passes_rgb holds n_passes x n x RGB, pass-major (yk_render_pixel_list_device's output); entry e's values are
+ * folded in pass order into film_sum and stats at its pixel.  The entries are checked on the host: every pixel inside the
+ * film, none twice.  ctx NULL = the host instance.  n may be 0. */
+yk_status yk_adaptive_accumulate(yk_context* ctx, const uint32_t* xy, uint32_t n, const float* passes_rgb, uint32_t n_passes, uint16_t res_x,
+                                 uint16_t res_y, float* film_sum, yk_pixel_stats* stats);
+/* The same for a list on device buffers, one launch on `stream` without waiting: passes and film 4-byte aligned, statistics
+ * 16-byte aligned, no two buffers overlapping, the list of the call's resolution, n_passes 1 .. the list's passes
+ * (anything else: YK_ERR_INVALID_ARGUMENT, nothing is launched). */
+yk_status yk_adaptive_accumulate_device(yk_context* ctx, const yk_pixel_list* list, const void* d_passes_rgb, uint32_t n_passes, uint16_t res_x,
+                                        uint16_t res_y, void* d_film_sum, void* d_stats, void* stream);
+/* out_rgb (res_x * res_y * 3) and out_variance (res_x * res_y) may each be NULL, not both.  ctx NULL = the host instance. */
+yk_status yk_adaptive_resolve(yk_context* ctx, const float* film_sum, const yk_pixel_stats* stats, uint16_t res_x, uint16_t res_y, float* out_rgb,
+                              float* out_variance);
+/* The same on device buffers, one launch on `stream`: alignment and overlap rules as yk_adaptive_accumulate_device. */
+yk_status yk_adaptive_resolve_device(yk_context* ctx, const void* d_film_sum, const void* d_stats, uint16_t res_x, uint16_t res_y,
+                                     void* d_out_rgb, void* d_out_variance, void* stream);
+/* Integrator::render(accumulating = true) for a pixel list: passes sample .. sample + n_passes - 1 of every entry, raw
+ * values, pass-major: d_out_rgb holds n_passes x n x RGB, each value bit for bit what the accumulating tile render writes
+ * for that pixel at that sample index.  n_passes 1 .. the list's passes; a list whose sample_end exceeds the sampler's
+ * samples per pixel is refused before anything is launched; an empty list returns YK_OK with nothing launched.  Chunks,
+ * batches, work sets, stats and cancel as yk_render_tile_list_passes_device. */
+yk_status yk_render_pixel_list_device(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler,
+                                      const yk_integrator_desc* integrator, const yk_pixel_list* list, uint32_t n_passes, void* d_out_rgb,
+                                      void* stream, yk_render_stats* stats, yk_cancel_fn cancel, void* user);
+/* The driver: select -> stop when nothing is selected or max_rounds is reached -> render the list with round_passes,
+ * folding every chunk's samples straight into d_film_sum and d_stats (no pass-major buffer exists) -> again.  It continues
+ * from whatever the statistics hold: cleared buffers select every pixel (n < min_samples); a later call with a larger
+ * max_samples refines.  max_samples may not exceed the sampler's samples per pixel.  Synchronous (one count read-back per
+ * round).  On YK_ERR_CANCELLED film and statistics are undefined.  `info` may be NULL. */
+yk_status yk_render_adaptive_device(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler,
+                                    const yk_integrator_desc* integrator, const yk_adaptive_desc* desc, uint16_t res_x, uint16_t res_y,
+                                    void* d_film_sum, void* d_stats, void* stream, yk_adaptive_info* info, yk_cancel_fn cancel, void* user);
+
 /* ---- per-stage entry points (parity tests, profiling) ------------------------- */
 /* BoundingVolumeHierarchy::intersect (bvh.rs:160-232) for n host rays.
  * out_shape: source shape index or -1; counters as IntersectionResult. */

@@ -335,10 +335,46 @@ inline void denoise_variance_device(Context& ctx, const yk_variance_desc& desc, 
     check(yk_denoise_variance_device(ctx.handle(), &desc, d_film, d_guides, d_variance, d_albedo, res_x, res_y, tile_dim, samples, d_out, stream), ctx.handle());
 }
 
+// Adaptive sampling (the library's own passes; the rule is stated in yuki_hip.h and csrc/yk_adaptive.h): a film of RGB sums
+// with one yk_pixel_stats a pixel, both zeros when cleared.  ctx == nullptr: the host instance.
+using PixelStats = yk_pixel_stats;
+// The selected pixels in the rule's order: (x | y << 16, the pixel's next sample index).
+inline std::pair<std::vector<uint32_t>, std::vector<uint32_t>> adaptive_select(Context* ctx, const yk_adaptive_desc& desc, const PixelStats* stats, uint16_t res_x, uint16_t res_y) {
+    std::vector<uint32_t> xy((size_t)res_x * res_y), sample((size_t)res_x * res_y);
+    uint32_t n = 0;
+    yk_context* c = ctx ? ctx->handle() : nullptr;
+    check(yk_adaptive_select(c, &desc, stats, res_x, res_y, xy.data(), sample.data(), &n), c);
+    xy.resize(n);
+    sample.resize(n);
+    return {std::move(xy), std::move(sample)};
+}
+// passes: n_passes x xy.size() x RGB, pass-major; folded into film_sum and stats in place.
+inline void adaptive_accumulate(Context* ctx, const std::vector<uint32_t>& xy, const float* passes, uint32_t n_passes, uint16_t res_x, uint16_t res_y, float* film_sum, PixelStats* stats) {
+    yk_context* c = ctx ? ctx->handle() : nullptr;
+    check(yk_adaptive_accumulate(c, xy.data(), (uint32_t)xy.size(), passes, n_passes, res_x, res_y, film_sum, stats), c);
+}
+// The mean film and the variance of that mean (what denoise_variance takes); either output may be nullptr.
+inline void adaptive_resolve(Context* ctx, const float* film_sum, const PixelStats* stats, uint16_t res_x, uint16_t res_y, float* out_rgb, float* out_variance) {
+    yk_context* c = ctx ? ctx->handle() : nullptr;
+    check(yk_adaptive_resolve(c, film_sum, stats, res_x, res_y, out_rgb, out_variance), c);
+}
+inline void adaptive_resolve_device(Context& ctx, const void* d_film_sum, const void* d_stats, uint16_t res_x, uint16_t res_y, void* d_out_rgb, void* d_out_variance, void* stream = nullptr) {
+    check(yk_adaptive_resolve_device(ctx.handle(), d_film_sum, d_stats, res_x, res_y, d_out_rgb, d_out_variance, stream), ctx.handle());
+}
+
 // trait Integrator, integrators/mod.rs:92-186
 class Integrator {
    public:
     Integrator(Context& ctx, yk_integrator_desc desc) : ctx_(ctx), desc_(desc) {}
+    // Rounds of select -> render the selected pixels -> fold into the device film sums and statistics, until nothing is
+    // selected (or desc.max_rounds); continues from what the buffers hold.  Synchronous.
+    yk_adaptive_info render_adaptive_device(const Scene& scene, const Camera& camera, const yk_sampler_desc& sampler, const yk_adaptive_desc& desc, uint16_t res_x, uint16_t res_y,
+                                            void* d_film_sum, void* d_stats, void* stream = nullptr, yk_cancel_fn cancel = nullptr, void* user = nullptr) const {
+        yk_adaptive_info info{};
+        check(yk_render_adaptive_device(ctx_.handle(), scene.handle(), &camera.matrices, &sampler, &desc_, &desc, res_x, res_y, d_film_sum, d_stats, stream, &info, cancel, user),
+              ctx_.handle());
+        return info;
+    }
     // render(): one tile; tile_pixels holds >= tile area RGB triples; returns the ray count
     size_t render(const Scene& scene, const Camera& camera, const yk_sampler_desc& sampler, const FilmTile& tile, float* tile_pixels) const {
         uint64_t rays = 0;

@@ -244,6 +244,44 @@ pub struct yk_moments {
     pub n: f32,
 }
 
+/// A pixel's adaptive-sampling statistics beside its film sum: running mean and sum of squared deviations of the
+/// luminance of the samples taken, their number, and the pixel's next sample index (yuki_amd/csrc/yk_adaptive.h)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct yk_pixel_stats {
+    pub mean: f32,
+    pub m2: f32,
+    pub n: u32,
+    pub drawn: u32,
+}
+
+/// The adaptive sampler's rule: min_samples >= 2, max_samples in min_samples..=2^24, round_passes 1..=0xFFFF,
+/// max_rounds 0 = until nothing is selected, dilate 0 | 1, threshold > 0, epsilon >= 0
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct yk_adaptive_desc {
+    pub min_samples: u32,
+    pub max_samples: u32,
+    pub round_passes: u32,
+    pub max_rounds: u32,
+    pub dilate: u32,
+    pub threshold: f32,
+    pub epsilon: f32,
+}
+
+/// What `yk_render_adaptive_device` did
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct yk_adaptive_info {
+    pub rounds: u32,
+    pub converged: u32,
+    pub first_pixels: u32,
+    pub last_pixels: u32,
+    pub samples: u64,
+    pub rays: u64,
+    pub shadow_rays: u64,
+}
+
 /// The variance-guided a-trous filter: iterations 0..=8, the variance-scaled colour stop, the normal and plane stops (each
 /// > 0, +inf = off), epsilon under the colour stop and the factor on the spatial variance estimate (both >= 0)
 #[repr(C)]
@@ -437,6 +475,7 @@ pub enum yk_context {}
 pub enum yk_scene {}
 pub enum yk_loaded_scene {}
 pub enum yk_tile_list {}
+pub enum yk_pixel_list {}
 pub const YK_MULTI_SHARED_DEVICES: u32 = 1;
 pub const YK_MULTI_PEER_COPY: u32 = 2;
 pub enum yk_multi {}
@@ -529,6 +568,18 @@ extern "C" {
     pub fn yk_variance_device(ctx: *mut yk_context, desc: *const yk_variance_desc, d_moments: *const c_void, d_film_rgb: *const c_void, d_guides: *const c_void, d_albedo: *const c_void, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, d_out_variance: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_denoise_variance(ctx: *mut yk_context, desc: *const yk_variance_desc, film_rgb: *const f32, guides: *const yk_guide, variance: *const f32, albedo: *const yk_albedo, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, out_rgb: *mut f32) -> yk_status;
     pub fn yk_denoise_variance_device(ctx: *mut yk_context, desc: *const yk_variance_desc, d_film_rgb: *const c_void, d_guides: *const c_void, d_variance: *const c_void, d_albedo: *const c_void, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, d_out_rgb: *mut c_void, stream: *mut c_void) -> yk_status;
+    pub fn yk_pixel_list_create(ctx: *mut yk_context, res_x: u16, res_y: u16, out: *mut *mut yk_pixel_list) -> yk_status;
+    pub fn yk_pixel_list_destroy(list: *mut yk_pixel_list);
+    pub fn yk_pixel_list_set(list: *mut yk_pixel_list, xy: *const u32, sample: *const u32, n: u32, passes: u32) -> yk_status;
+    pub fn yk_pixel_list_read(list: *const yk_pixel_list, out_xy: *mut u32, out_sample: *mut u32, cap: u32, out_n: *mut u32) -> yk_status;
+    pub fn yk_adaptive_select(ctx: *mut yk_context, desc: *const yk_adaptive_desc, stats: *const yk_pixel_stats, res_x: u16, res_y: u16, out_xy: *mut u32, out_sample: *mut u32, out_n: *mut u32) -> yk_status;
+    pub fn yk_adaptive_select_device(ctx: *mut yk_context, desc: *const yk_adaptive_desc, d_stats: *const c_void, res_x: u16, res_y: u16, list: *mut yk_pixel_list, out_n: *mut u32, stream: *mut c_void) -> yk_status;
+    pub fn yk_adaptive_accumulate(ctx: *mut yk_context, xy: *const u32, n: u32, passes_rgb: *const f32, n_passes: u32, res_x: u16, res_y: u16, film_sum: *mut f32, stats: *mut yk_pixel_stats) -> yk_status;
+    pub fn yk_adaptive_accumulate_device(ctx: *mut yk_context, list: *const yk_pixel_list, d_passes_rgb: *const c_void, n_passes: u32, res_x: u16, res_y: u16, d_film_sum: *mut c_void, d_stats: *mut c_void, stream: *mut c_void) -> yk_status;
+    pub fn yk_adaptive_resolve(ctx: *mut yk_context, film_sum: *const f32, stats: *const yk_pixel_stats, res_x: u16, res_y: u16, out_rgb: *mut f32, out_variance: *mut f32) -> yk_status;
+    pub fn yk_adaptive_resolve_device(ctx: *mut yk_context, d_film_sum: *const c_void, d_stats: *const c_void, res_x: u16, res_y: u16, d_out_rgb: *mut c_void, d_out_variance: *mut c_void, stream: *mut c_void) -> yk_status;
+    pub fn yk_render_pixel_list_device(ctx: *mut yk_context, scene: *const yk_scene, camera: *const yk_camera, sampler: *const yk_sampler_desc, integrator: *const yk_integrator_desc, list: *const yk_pixel_list, n_passes: u32, d_out_rgb: *mut c_void, stream: *mut c_void, stats: *mut yk_render_stats, cancel: yk_cancel_fn, user: *mut c_void) -> yk_status;
+    pub fn yk_render_adaptive_device(ctx: *mut yk_context, scene: *const yk_scene, camera: *const yk_camera, sampler: *const yk_sampler_desc, integrator: *const yk_integrator_desc, desc: *const yk_adaptive_desc, res_x: u16, res_y: u16, d_film_sum: *mut c_void, d_stats: *mut c_void, stream: *mut c_void, info: *mut yk_adaptive_info, cancel: yk_cancel_fn, user: *mut c_void) -> yk_status;
     pub fn yk_write_png(path: *const c_char, width: u32, height: u32, channels: u32, pixels: *const u8) -> yk_status;
     pub fn yk_render_tile(ctx: *mut yk_context, scene: *const yk_scene, camera: *const yk_camera, sampler: *const yk_sampler_desc, integrator: *const yk_integrator_desc, tile: *const yk_tile, tile_pixels: *mut f32, out_rays: *mut u64) -> yk_status;
     pub fn yk_film_update_tiles_device(ctx: *mut yk_context, tiles: *const yk_tile, n_tiles: usize, d_tile_rgb: *const c_void, res_x: u16, res_y: u16, d_film_rgb: *mut c_void, stream: *mut c_void) -> yk_status;

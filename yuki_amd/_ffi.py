@@ -194,6 +194,18 @@ SYMBOLS = {
     "yk_variance_device": (C.c_int, [vp, C.POINTER(abi.VarianceDesc), vp, vp, vp, vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp]),
     "yk_denoise_variance": (C.c_int, [vp, C.POINTER(abi.VarianceDesc), vp, vp, vp, vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp]),
     "yk_denoise_variance_device": (C.c_int, [vp, C.POINTER(abi.VarianceDesc), vp, vp, vp, vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp]),
+    "yk_pixel_list_create": (C.c_int, [vp, C.c_uint16, C.c_uint16, C.POINTER(vp)]),
+    "yk_pixel_list_destroy": (None, [vp]),
+    "yk_pixel_list_set": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32]),
+    "yk_pixel_list_read": (C.c_int, [vp, vp, vp, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "yk_adaptive_select": (C.c_int, [vp, C.POINTER(abi.AdaptiveDesc), vp, C.c_uint16, C.c_uint16, vp, vp, C.POINTER(C.c_uint32)]),
+    "yk_adaptive_select_device": (C.c_int, [vp, C.POINTER(abi.AdaptiveDesc), vp, C.c_uint16, C.c_uint16, vp, C.POINTER(C.c_uint32), vp]),
+    "yk_adaptive_accumulate": (C.c_int, [vp, vp, C.c_uint32, vp, C.c_uint32, C.c_uint16, C.c_uint16, vp, vp]),
+    "yk_adaptive_accumulate_device": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint16, C.c_uint16, vp, vp, vp]),
+    "yk_adaptive_resolve": (C.c_int, [vp, vp, vp, C.c_uint16, C.c_uint16, vp, vp]),
+    "yk_adaptive_resolve_device": (C.c_int, [vp, vp, vp, C.c_uint16, C.c_uint16, vp, vp, vp]),
+    "yk_render_pixel_list_device": (C.c_int, [vp, vp, C.POINTER(abi.CameraMatrices), C.POINTER(abi.SamplerDesc), C.POINTER(abi.IntegratorDesc), vp, C.c_uint32, vp, vp, C.POINTER(RenderStats), vp, vp]),
+    "yk_render_adaptive_device": (C.c_int, [vp, vp, C.POINTER(abi.CameraMatrices), C.POINTER(abi.SamplerDesc), C.POINTER(abi.IntegratorDesc), C.POINTER(abi.AdaptiveDesc), C.c_uint16, C.c_uint16, vp, vp, vp, C.POINTER(abi.AdaptiveInfo), vp, vp]),
     "yk_write_png": (C.c_int, [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint32, vp]),
     # several GPUs
     "yk_multi_create": (C.c_int, [C.POINTER(C.c_int), C.c_uint32, C.POINTER(vp)]),

@@ -145,6 +145,18 @@ class VarianceDesc(C.Structure):
     _fields_ = [("iterations", C.c_uint32), ("sigma_variance", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float), ("epsilon", C.c_float), ("spatial_scale", C.c_float)]
 
 
+class AdaptiveDesc(C.Structure):
+    """yk_adaptive_desc: the adaptive sampler's rule (csrc/yk_adaptive.h)."""
+
+    _fields_ = [("min_samples", C.c_uint32), ("max_samples", C.c_uint32), ("round_passes", C.c_uint32), ("max_rounds", C.c_uint32), ("dilate", C.c_uint32), ("threshold", C.c_float), ("epsilon", C.c_float)]
+
+
+class AdaptiveInfo(C.Structure):
+    """yk_adaptive_info: what yk_render_adaptive_device did."""
+
+    _fields_ = [("rounds", C.c_uint32), ("converged", C.c_uint32), ("first_pixels", C.c_uint32), ("last_pixels", C.c_uint32), ("samples", C.c_uint64), ("rays", C.c_uint64), ("shadow_rays", C.c_uint64)]
+
+
 class IntegratorRay(C.Structure):
     """yk_integrator_ray: IntegratorRay (integrators/mod.rs:76-80), the ray and its yk_ray_type."""
 
@@ -224,6 +236,7 @@ MOTION_DTYPE = np.dtype([("p_prev", "<f4", 3), ("known", "<f4")])  # yk_motion, 
 ALBEDO_DTYPE = np.dtype([("a", "<f4", 3), ("known", "<f4")])  # yk_albedo, 16 bytes
 ALBEDO_FLOOR = 0.015625  # YK_ALBEDO_FLOOR, 2^-6
 MOMENTS_DTYPE = np.dtype([("m1", "<f4"), ("m2", "<f4"), ("frames", "<f4"), ("n", "<f4")])  # yk_moments, 16 bytes: yk_history's layout
+PIXEL_STATS_DTYPE = np.dtype([("mean", "<f4"), ("m2", "<f4"), ("n", "<u4"), ("drawn", "<u4")])  # yk_pixel_stats, 16 bytes
 
 # enums (include/yuki_hip.h)
 SPLIT_SAH, SPLIT_MIDDLE, SPLIT_EQUAL_COUNTS = 0, 1, 2

@@ -517,6 +517,94 @@ def variance(moments, film, guides, params, tile_dim=16, samples=None, ctx=None,
     return out
 
 
+# --------------------------------------------------------------------------- adaptive sampling (csrc/yk_adaptive.h)
+# film_sum (h, w, 3) float32 sums and stats (h, w) abi.PIXEL_STATS_DTYPE, both zeros when cleared.  Per round:
+# xy, sample = adaptive_select(stats, params); passes = the render of those entries (Integrator.render_pixel_list_device);
+# adaptive_accumulate(xy, passes, film_sum, stats).  At the end rgb, var = adaptive_resolve(film_sum, stats) and
+# denoise(rgb, guides, VarianceParams, variance=var).  Integrator.render_adaptive is that loop on the device.
+@dataclass
+class AdaptiveParams:
+    """yk_adaptive_desc (csrc/yk_adaptive.h): a pixel wants samples while it has fewer than min_samples or the standard
+    error of its mean luminance exceeds threshold x (mean + epsilon); with dilate its 8 neighbours are taken along; a
+    selected pixel takes round_passes samples a round and never more than max_samples in all; max_rounds 0 = until nothing
+    is selected.  The defaults are the best row of profiles/adaptive_quality.json; max_samples None stands for "the
+    sampler's samples per pixel" (for_sampler)."""
+
+    min_samples: int = 16
+    max_samples: int = None
+    round_passes: int = 8
+    max_rounds: int = 0
+    dilate: bool = True
+    threshold: float = 0.2
+    epsilon: float = 0.05
+
+    @staticmethod
+    def for_sampler(sampler, **kw):
+        """max_samples = the sampler's samples per pixel: the most a pixel can take."""
+        return AdaptiveParams(max_samples=samples_per_pixel(sampler), **kw)
+
+    def as_struct(self):
+        if self.max_samples is None:
+            raise ValueError("AdaptiveParams.max_samples is not set: use AdaptiveParams.for_sampler")
+        return abi.AdaptiveDesc(int(self.min_samples), int(self.max_samples), int(self.round_passes), int(self.max_rounds), int(self.dilate), float(self.threshold), float(self.epsilon))
+
+
+def _adaptive_desc(params):
+    if not isinstance(params, AdaptiveParams):
+        raise TypeError("params is an AdaptiveParams")
+    return params.as_struct()
+
+
+def _film_sum(film_sum):
+    if film_sum.dtype != np.float32 or not film_sum.flags.c_contiguous or film_sum.ndim != 3 or film_sum.shape[2] != 3:
+        raise ValueError("film_sum is a contiguous (h, w, 3) float32 array")
+    return film_sum.shape[1], film_sum.shape[0]
+
+
+def adaptive_select(stats, params, ctx=None):
+    """yk_adaptive_select: the (h, w) abi.PIXEL_STATS_DTYPE statistics -> (xy, sample), two uint32 arrays with one entry per
+    selected pixel in the rule's order (xy = x | y << 16, sample = the pixel's next sample index).  ctx None = the host
+    instance."""
+    if stats.ndim != 2:
+        raise ValueError("stats is (h, w)")
+    h, w = stats.shape
+    stats = _records(stats, abi.PIXEL_STATS_DTYPE, (w, h), "pixel stats")
+    d = _adaptive_desc(params)
+    xy = np.zeros(w * h, dtype=np.uint32)
+    sample = np.zeros(w * h, dtype=np.uint32)
+    n = C.c_uint32(0)
+    c = ctx.h if ctx else None
+    check(lib().yk_adaptive_select(c, C.byref(d), _p(stats), w, h, _p(xy), _p(sample), C.byref(n)), c)
+    return xy[: n.value].copy(), sample[: n.value].copy()
+
+
+def adaptive_accumulate(xy, passes, film_sum, stats, ctx=None):
+    """yk_adaptive_accumulate: folds passes (n_passes, n, 3) — entry e's values in pass order — into film_sum and stats IN
+    PLACE at the pixels xy names.  ctx None = the host instance."""
+    w, h = _film_sum(film_sum)
+    if stats.dtype != abi.PIXEL_STATS_DTYPE or not stats.flags.c_contiguous or stats.shape != (h, w):
+        raise ValueError("stats is a contiguous (h, w) array of abi.PIXEL_STATS_DTYPE")
+    xy = np.ascontiguousarray(xy, dtype=np.uint32)
+    passes = np.ascontiguousarray(passes, dtype=np.float32)
+    if passes.ndim != 3 or passes.shape[1] != len(xy) or passes.shape[2] != 3:
+        raise ValueError("passes is (n_passes, n, 3)")
+    c = ctx.h if ctx else None
+    check(lib().yk_adaptive_accumulate(c, _p(xy), len(xy), _p(passes), passes.shape[0], w, h, _p(film_sum), _p(stats)), c)
+
+
+def adaptive_resolve(film_sum, stats, ctx=None):
+    """yk_adaptive_resolve: (rgb (h, w, 3), variance (h, w)) — the mean film and the variance of that mean, the image
+    denoise(..., variance=) takes.  ctx None = the host instance."""
+    film_sum = np.ascontiguousarray(film_sum, dtype=np.float32)
+    w, h = _film_sum(film_sum)
+    stats = _records(stats, abi.PIXEL_STATS_DTYPE, (w, h), "pixel stats")
+    rgb = np.zeros((h, w, 3), dtype=np.float32)
+    var = np.zeros((h, w), dtype=np.float32)
+    c = ctx.h if ctx else None
+    check(lib().yk_adaptive_resolve(c, _p(film_sum), _p(stats), w, h, _p(rgb), _p(var)), c)
+    return rgb, var
+
+
 def _denoise_for_output(film, denoise_params, guides, tile_dim, samples, ctx, albedo=None, variance=None):
     """The denoise step of write_output / write_preview: (film, samples) for the tone map that follows — the denoised film
     is normalised already, so it goes on without the sample table."""
@@ -691,6 +779,49 @@ class TileList:
     def close(self):
         if getattr(self, "h", None):
             lib().yk_tile_list_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class PixelList:
+    """(pixel, first sample index) entries on the device with room for every pixel of a film (yk_pixel_list): filled by
+    Context.adaptive_select_device or set(), rendered by Integrator.render_pixel_list_device."""
+
+    def __init__(self, ctx, res):
+        self.ctx = ctx
+        self.res = (int(res[0]), int(res[1]))
+        h = C.c_void_p()
+        check(lib().yk_pixel_list_create(ctx.h, self.res[0], self.res[1], C.byref(h)), ctx.h)
+        self.h = h
+        self.n = 0
+
+    def set(self, xy, sample, passes=1):
+        """Host entries (xy = x | y << 16), checked before the upload: inside the resolution, no pixel twice."""
+        xy = np.ascontiguousarray(xy, dtype=np.uint32)
+        sample = np.ascontiguousarray(sample, dtype=np.uint32)
+        if xy.shape != sample.shape or xy.ndim != 1:
+            raise ValueError("one sample index per entry")
+        check(lib().yk_pixel_list_set(self.h, _p(xy), _p(sample), len(xy), int(passes)), self.ctx.h)
+        self.n = len(xy)
+
+    def read(self):
+        """(xy, sample) as the device holds them."""
+        n = C.c_uint32(0)
+        check(lib().yk_pixel_list_read(self.h, None, None, 0, C.byref(n)), self.ctx.h)
+        xy = np.zeros(n.value, dtype=np.uint32)
+        sample = np.zeros(n.value, dtype=np.uint32)
+        check(lib().yk_pixel_list_read(self.h, _p(xy), _p(sample), n.value, C.byref(n)), self.ctx.h)
+        self.n = n.value
+        return xy, sample
+
+    def close(self):
+        if getattr(self, "h", None):
+            lib().yk_pixel_list_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -898,6 +1029,28 @@ class Context:
         samples = _blend_samples(res, tile_dim, samples)
         vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
         check(lib().yk_denoise_variance_device(self.h, C.byref(d), vp(d_film_ptr), vp(d_guides_ptr), vp(d_variance_ptr), vp(albedo), int(res[0]), int(res[1]), int(tile_dim), _p(samples), vp(d_out_ptr), vp(stream)), self.h)
+
+    def adaptive_select_device(self, d_stats_ptr, res, params, pixel_list, stream=None):
+        """yk_adaptive_select_device: device statistics -> `pixel_list` (a PixelList of the same resolution); returns the
+        number selected.  Three launches on `stream` (default: the context's), then the count is read back: it waits."""
+        d = _adaptive_desc(params)
+        n = C.c_uint32(0)
+        vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
+        check(lib().yk_adaptive_select_device(self.h, C.byref(d), vp(d_stats_ptr), int(res[0]), int(res[1]), pixel_list.h, C.byref(n), vp(stream)), self.h)
+        pixel_list.n = n.value
+        return n.value
+
+    def adaptive_accumulate_device(self, pixel_list, d_passes_ptr, n_passes, res, d_film_sum_ptr, d_stats_ptr, stream=None):
+        """yk_adaptive_accumulate_device: the (n_passes, n, 3) device passes of `pixel_list` folded into the device film sums
+        and statistics, one launch on `stream` (default: the context's) without waiting."""
+        vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
+        check(lib().yk_adaptive_accumulate_device(self.h, pixel_list.h, vp(d_passes_ptr), int(n_passes), int(res[0]), int(res[1]), vp(d_film_sum_ptr), vp(d_stats_ptr), vp(stream)), self.h)
+
+    def adaptive_resolve_device(self, d_film_sum_ptr, d_stats_ptr, res, d_out_rgb_ptr, d_out_variance_ptr, stream=None):
+        """yk_adaptive_resolve_device: device film sums and statistics -> the device mean film and / or the variance of the
+        mean (None = not wanted), one launch on `stream` (default: the context's) without waiting."""
+        vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
+        check(lib().yk_adaptive_resolve_device(self.h, vp(d_film_sum_ptr), vp(d_stats_ptr), int(res[0]), int(res[1]), vp(d_out_rgb_ptr), vp(d_out_variance_ptr), vp(stream)), self.h)
 
     @property
     def stream_handle(self):
@@ -1457,6 +1610,41 @@ class Integrator:
             self.ctx.h,
         )
         return stats if want_stats else None
+
+    def render_pixel_list_device(self, scene, camera, sampler, pixel_list, n_passes, d_out_ptr, stream=None, want_stats=False, cancel=None):
+        """yk_render_pixel_list_device: passes sample .. sample + n_passes - 1 of every entry of a PixelList, raw values,
+        (n_passes, n, 3) pass-major into HBM at `d_out_ptr`: what the accumulating render writes for that pixel at that
+        sample index."""
+        stats = RenderStats()
+        cb = _ffi.CANCEL_FN(lambda _u: 1 if cancel() else 0) if cancel else None
+        check(
+            lib().yk_render_pixel_list_device(self.ctx.h, scene.h, C.byref(camera.matrices), C.byref(sampler), C.byref(self.desc), pixel_list.h, int(n_passes), C.c_void_p(d_out_ptr) if d_out_ptr else None, C.c_void_p(stream) if stream else None, C.byref(stats) if want_stats else None, C.cast(cb, C.c_void_p) if cb else None, None),
+            self.ctx.h,
+        )
+        return stats if want_stats else None
+
+    def render_adaptive(self, scene, camera, sampler, film_settings, params, film_sum=None, stats=None, stream=None, cancel=None):
+        """yk_render_adaptive_device: rounds of select -> render -> fold on the device until nothing is selected (or
+        params.max_rounds).  film_sum ((h, w, 3) float32) and stats ((h, w, 4) int32: the yk_pixel_stats records) are torch
+        tensors on the context's device or device addresses; None makes cleared torch tensors.  It continues from what they
+        hold: call again with a larger max_samples to refine.  Returns (film_sum, stats, abi.AdaptiveInfo)."""
+        w, h = int(film_settings.res[0]), int(film_settings.res[1])
+        if film_sum is None or stats is None:
+            import torch
+
+            dev = torch.device("cuda", self.ctx.device)
+            film_sum = torch.zeros((h, w, 3), dtype=torch.float32, device=dev) if film_sum is None else film_sum
+            stats = torch.zeros((h, w, 4), dtype=torch.int32, device=dev) if stats is None else stats
+        address, stream = _device_addresses({"film_sum": film_sum, "stats": stats}, {"film_sum": (("float32",), w * h * 3), "stats": (("int32",), w * h * 4)}, self.ctx, stream)
+        d = _adaptive_desc(params)
+        info = abi.AdaptiveInfo()
+        cb = _ffi.CANCEL_FN(lambda _u: 1 if cancel() else 0) if cancel else None
+        vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
+        check(
+            lib().yk_render_adaptive_device(self.ctx.h, scene.h, C.byref(camera.matrices), C.byref(sampler), C.byref(self.desc), C.byref(d), w, h, vp(address["film_sum"]), vp(address["stats"]), vp(stream), C.byref(info), C.cast(cb, C.c_void_p) if cb else None, None),
+            self.ctx.h,
+        )
+        return film_sum, stats, info
 
     def li(self, scene, sampler, ray_o, ray_d, pixel_xy, sample_index, dimension=2, ray_counts=False):
         """Integrator::li for caller-supplied rays (integrators/mod.rs:94-101).  With `ray_counts`: (li, the closest-hit rays

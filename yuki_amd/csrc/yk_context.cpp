@@ -124,6 +124,8 @@ void yk_context_destroy(yk_context* ctx) {
     ctx->denoise.ping[1].release();
     ctx->denoise.samples.release();
     ctx->temporal.samples.release();
+    ctx->adaptive.rank.release();
+    ctx->adaptive.tile_count.release();
     if (ctx->tonemap.staging) (void)hipHostFree(ctx->tonemap.staging);
     if (ctx->tonemap.staged) (void)hipEventDestroy(ctx->tonemap.staged);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);

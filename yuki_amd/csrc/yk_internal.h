@@ -150,6 +150,12 @@ struct yk_context {
         DevBuf ids;        // one u32 a pixel: the winning ordinal + 1
         int64_t coop_min = 32;  // "overlay_coop_min": segments of at least this many pixels are drawn by a whole wave
     } overlay;
+    // the adaptive selection's scratch (yk_adaptive.hip), grown on first use: a selection ends with a synchronisation, so
+    // the next one finds it free whatever stream it runs on
+    struct AdaptiveState {
+        DevBuf rank;        // one u32 a pixel: the rank inside its 16 x 16 tile, or ~0 where the pixel is not selected
+        DevBuf tile_count;  // one u32 a tile: the tile's count, then its base; one more word: the total
+    } adaptive;
     // every entry point that touches the context's buffers or streams holds this: calls on one
     // context from several host threads (the reference's tile workers) are serialised
     std::recursive_mutex mu;
@@ -248,6 +254,18 @@ struct yk_tile_list {
     std::vector<yk_tile> tiles;
     std::vector<uint16_t> samples;  // empty: plain film
     std::vector<uint32_t> off;      // n_tiles + 1 pixel offsets
+    DevBuf pixel_xy, pixel_sample;
+};
+
+// (pixel, first sample index) entries in HBM with room for every pixel of a res_x x res_y film (yk_adaptive.h): filled by
+// the selection kernels or by yk_pixel_list_set, which checks what it uploads — no kernel indexes a film with a
+// coordinate that was not checked.
+struct yk_pixel_list {
+    yk_context* ctx = nullptr;
+    uint32_t res_x = 0, res_y = 0;
+    uint32_t n = 0;           // entries, known to the host
+    uint32_t passes = 0;      // the round size the entries were chosen for
+    uint32_t sample_end = 0;  // sample + passes <= sample_end for every entry
     DevBuf pixel_xy, pixel_sample;
 };
 
@@ -350,6 +368,11 @@ hipError_t enqueue_shape_bounds(hipStream_t st, const float* d_points, const uin
 // on `st`.  It goes through the context's pinned staging (tonemap.staging), so the upload is truly asynchronous; the staging
 // is rewritten only once the previous upload out of it has run.
 yk_status stage_sample_table(yk_context* ctx, hipStream_t st, const uint32_t* samples, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, DevBuf& dst);
+
+// ------------------------------------------------------------------ yk_adaptive.hip
+// The selection (yk_adaptive.h) of device statistics of the list's resolution into `list`, on `st`; synchronises once to read
+// the count, which it leaves in the list and in *out_n.  The caller holds the lock and has checked desc, pointer and list.
+yk_status adaptive_select_into(yk_context* ctx, hipStream_t st, const yk_adaptive_desc* desc, const void* d_stats, yk_pixel_list* list, uint32_t* out_n);
 
 // ------------------------------------------------------------------ yk_scene.cpp
 // The exact sizes of a scene's seven record buffers (s->record_bytes) and the head of s->layout from what was laid out,

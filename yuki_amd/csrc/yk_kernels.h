@@ -55,6 +55,10 @@ void launch_debug_shade(hipStream_t s, const DevScene& sc, uint32_t integrator, 
 void launch_guides(hipStream_t s, const DevScene& sc, PathBuffers cur, const int* hit_tri, uint32_t n, const uint32_t* pixel_xy, uint32_t res_x, float4* guides);
 // the same with one yk_surface_id record (a uint4) per pixel beside it (yk_render_guides_ids); either output may be null
 void launch_guides_ids(hipStream_t s, const DevScene& sc, PathBuffers cur, const int* hit_tri, uint32_t n, const uint32_t* pixel_xy, uint32_t res_x, float4* guides, uint4* ids);
+// the adaptive fold of a rendered chunk (yk_adaptive.hip, k_ad_fold): entry e's n_passes samples sample_buf[e * n_passes + k]
+// into film_sum and stats at its pixel; the entries are unique pixels inside the res_x-wide film
+void launch_ad_fold_samples(hipStream_t s, const uint32_t* pixel_xy, uint32_t n, const float4* sample_buf, uint32_t n_passes, uint32_t res_x, float* film_sum,
+                            void* stats);
 void launch_device_math(hipStream_t s, int fn, size_t n, const float* a, const float* b, float* out);
 void launch_sampler_sequence(hipStream_t s, const SamplerCfg& cfg, uint32_t px, uint32_t py, uint32_t sample_index, const uint8_t* dims, size_t n_draws,
                              float* out);

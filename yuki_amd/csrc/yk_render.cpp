@@ -21,11 +21,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 
+#include "yk_adaptive.h"
 #include "yk_film_call.h"
 #include "yk_render_plan.h"
 #include "yk_staging.h"
@@ -312,6 +314,12 @@ struct RenderRequest {
     // 146-161): passes FilmTile.sample .. + n_passes - 1 of every tile, raw values stored pass-major.
     const uint16_t* tile_samples = nullptr;
     const yk_tile_list* list = nullptr;  // instead of the three above: a prepared list, its pixel table on the device already
+    // instead of tiles altogether: a pixel list (yk_adaptive.h) — every entry its own first sample index, n_passes of them
+    // rendered, the accumulating film.  With d_film_sum and d_stats (a film_res_x-wide film of sums and its yk_pixel_stats)
+    // instead of d_out, every chunk's samples are folded straight into them (k_ad_fold) and no pass-major buffer exists.
+    const yk_pixel_list* pixels = nullptr;
+    void* d_film_sum = nullptr;
+    void* d_stats = nullptr;
     uint32_t n_passes = 1;
     int64_t uniform_first_sample = -1;  // >= 0: the accumulating film with this first sample index for every tile
     void* d_out = nullptr;
@@ -383,7 +391,11 @@ struct Submission {
             tile_samples = rq.list->samples.empty() ? nullptr : rq.list->samples.data();
             n_tiles = rq.list->tiles.size();
         }
-        if (!scene || !rq.camera || !tiles || n_tiles == 0 || (!rq.d_out && !(rq.guides_res_x && rq.d_ids))) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null argument");
+        if (rq.pixels) {
+            if (rq.pixels->ctx != ctx) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "pixel list was not created on this context");
+            if (!scene || !rq.camera || (!rq.d_out && !(rq.d_film_sum && rq.d_stats))) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null argument");
+        } else if (!scene || !rq.camera || !tiles || n_tiles == 0 || (!rq.d_out && !(rq.guides_res_x && rq.d_ids)))
+            return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null argument");
         if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "scene was not created on this context's device");
         yk_status rc = make_params(ctx, rq.sampler, rq.integrator, prm);
         if (rc != YK_OK) return rc;
@@ -391,10 +403,15 @@ struct Submission {
         if (is_path && prm.max_depth > YK_CTRL_MAX_DEPTH) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "max_depth too large");
         (void)hipSetDevice(ctx->device);
         if ((rc = clear_cancel(ctx)) != YK_OK) return rc;
-        if (!rq.list && (rc = tile_offsets(ctx, tiles, n_tiles, own_off, "too many pixels in one call")) != YK_OK) return rc;
-        off = rq.list ? rq.list->off.data() : own_off.data();  // a list's were validated when it was made
-        const char* refusal = plan.set_samples(tile_samples, n_tiles, rq.uniform_first_sample, rq.n_passes, prm.sampler.spp);
-        if (!refusal) refusal = plan.set_chunks(off, n_tiles, (uint64_t)ctx->sample_buf_cap);
+        const char* refusal = nullptr;
+        if (rq.pixels) {
+            refusal = plan.set_pixel_list(rq.pixels->n, rq.n_passes, rq.pixels->passes, rq.pixels->sample_end, prm.sampler.spp, (uint64_t)ctx->sample_buf_cap);
+        } else {
+            if (!rq.list && (rc = tile_offsets(ctx, tiles, n_tiles, own_off, "too many pixels in one call")) != YK_OK) return rc;
+            off = rq.list ? rq.list->off.data() : own_off.data();  // a list's were validated when it was made
+            refusal = plan.set_samples(tile_samples, n_tiles, rq.uniform_first_sample, rq.n_passes, prm.sampler.spp);
+            if (!refusal) refusal = plan.set_chunks(off, n_tiles, (uint64_t)ctx->sample_buf_cap);
+        }
         if (refusal) return fail(ctx, YK_ERR_INVALID_ARGUMENT, refusal);
         plan.set_batch((uint64_t)ctx->batch_paths, ctx->streams, is_path, rq.stream != nullptr);
         prm.spe = plan.spp;
@@ -442,6 +459,11 @@ struct Submission {
         const bool sample_table = plan.sample_table;
         const size_t nt = c.t_end - c.t_begin;
         pixel_sample = nullptr;
+        if (rq.pixels) {  // the list's two tables are the chunk's, as they are
+            pixel_xy = rq.pixels->pixel_xy.as<uint32_t>() + c.px0;
+            pixel_sample = rq.pixels->pixel_sample.as<uint32_t>() + c.px0;
+            return YK_OK;
+        }
         if (rq.list) {  // the pixel table of the whole list is already on the device
             pixel_xy = rq.list->pixel_xy.as<uint32_t>() + c.px0;
             if (sample_table) pixel_sample = rq.list->pixel_sample.as<uint32_t>() + c.px0;
@@ -571,6 +593,8 @@ struct Submission {
         float* out = reinterpret_cast<float*>(rq.d_out) + 3 * (size_t)c.px0;
         if (rq.guides_res_x)  // k_guides wrote every record at its pixel: nothing to resolve
             ;
+        else if (rq.pixels && rq.d_film_sum)  // the fused route: the chunk's samples into the film sums and the statistics
+            launch_ad_fold_samples(st, pixel_xy, c.npx, sample_buf, spp, rq.pixels->res_x, reinterpret_cast<float*>(rq.d_film_sum), rq.d_stats);
         else if (plan.accumulating)  // raw values, pass-major over the whole tile list
             launch_resolve_passes(st, sample_buf, c.npx, spp, out, 3 * (size_t)plan.total_px);
         else
@@ -933,6 +957,75 @@ yk_status yk_render_tile_list_samples_device(yk_context* ctx, const yk_scene* sc
     rq.n_passes = n_passes;
     rq.uniform_first_sample = (int64_t)first_sample;
     return render_tile_list(ctx, rq, list, list && !list->samples.empty() ? "the list carries per-tile sample indices: use yk_render_tile_list_passes_device" : nullptr);
+}
+
+// a pixel list into a pass-major buffer, or (d_film_sum, d_stats) fused into a film; an empty list launches nothing
+static yk_status render_pixel_list(yk_context* ctx, RenderRequest rq, const yk_pixel_list* list, const char* who) {
+    if (!list) return fail(ctx, YK_ERR_INVALID_ARGUMENT, std::string(who) + ": null pixel list");
+    rq.pixels = list;
+    if (list->n == 0) {  // the arguments are still checked; the plan has no chunk and nothing is enqueued
+        Submission s(ctx, rq);
+        yk_status rc = s.check_and_plan();
+        if (rc == YK_OK && rq.stats) std::memset(rq.stats, 0, sizeof(*rq.stats));
+        return rc;
+    }
+    return render_tiles_impl(ctx, rq);
+}
+
+yk_status yk_render_pixel_list_device(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler, const yk_integrator_desc* integrator,
+                                      const yk_pixel_list* list, uint32_t n_passes, void* d_out_rgb, void* stream, yk_render_stats* stats, yk_cancel_fn cancel, void* user) {
+    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
+    YK_LOCK(ctx);
+    if (!d_out_rgb || misaligned(4, d_out_rgb)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_pixel_list_device: the output must be given and 4-byte aligned");
+    RenderRequest rq = request_for(scene, camera, sampler, integrator, d_out_rgb, stream, stats, cancel, user);
+    rq.n_passes = n_passes;
+    return render_pixel_list(ctx, rq, list, "yk_render_pixel_list_device");
+}
+
+// select -> stop on an empty selection or at max_rounds -> the fused render of the list with round_passes -> again
+yk_status yk_render_adaptive_device(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler, const yk_integrator_desc* integrator,
+                                    const yk_adaptive_desc* desc, uint16_t res_x, uint16_t res_y, void* d_film_sum, void* d_stats, void* stream, yk_adaptive_info* info,
+                                    yk_cancel_fn cancel, void* user) {
+    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
+    YK_LOCK(ctx);
+    if (info) std::memset(info, 0, sizeof(*info));
+    if (!ad_desc_ok(desc) || !scene || !camera || !d_film_sum || !d_stats || res_x == 0 || res_y == 0) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_adaptive_device: bad argument");
+    const size_t n_px = (size_t)res_x * res_y;
+    if (misaligned(4, d_film_sum) || misaligned(16, d_stats)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_adaptive_device: film must be 4-byte aligned, statistics 16-byte aligned");
+    if (overlaps(d_film_sum, n_px * 12, d_stats, n_px * 16)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_adaptive_device: film and statistics overlap");
+    RenderParams prm;  // the sampler and the integrator are refused before the first selection, not after it
+    yk_status rc = make_params(ctx, sampler, integrator, prm);
+    if (rc != YK_OK) return rc;
+    if (desc->max_samples > prm.sampler.spp) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_adaptive_device: max_samples beyond the sampler's samples per pixel");
+    yk_pixel_list* made = nullptr;
+    if ((rc = yk_pixel_list_create(ctx, res_x, res_y, &made)) != YK_OK) return rc;
+    std::unique_ptr<yk_pixel_list, void (*)(yk_pixel_list*)> list(made, yk_pixel_list_destroy);
+    yk_adaptive_info got = {};
+    hipStream_t st = device_call_stream(ctx, stream);
+    for (;;) {
+        uint32_t n = 0;
+        if ((rc = adaptive_select_into(ctx, st, desc, d_stats, list.get(), &n)) != YK_OK) return rc;
+        if (n == 0) {
+            got.converged = 1;
+            break;
+        }
+        if (desc->max_rounds && got.rounds == desc->max_rounds) break;
+        yk_render_stats stats;
+        RenderRequest rq = request_for(scene, camera, sampler, integrator, nullptr, stream, &stats, cancel, user);
+        rq.n_passes = desc->round_passes;
+        rq.d_film_sum = d_film_sum;
+        rq.d_stats = d_stats;
+        if ((rc = render_pixel_list(ctx, rq, list.get(), "yk_render_adaptive_device")) != YK_OK) return rc;
+        if (got.rounds == 0) got.first_pixels = n;
+        got.last_pixels = n;
+        ++got.rounds;
+        got.samples += stats.samples;
+        got.rays += stats.rays;
+        got.shadow_rays += stats.shadow_rays;
+        if (info) *info = got;
+    }
+    if (info) *info = got;
+    return YK_OK;
 }
 
 // An interruption from any thread (the call that renders holds the context's lock for its whole duration, this one

@@ -75,6 +75,27 @@ struct RenderPlan {
         return nullptr;
     }
 
+    // A pixel list instead of tiles (set_samples and set_chunks in one): n_pixels entries, each with its own first sample
+    // index on the device, n_passes of them rendered; list_passes: the round size the list was made for; sample_end: the
+    // host-known bound, sample + list_passes <= sample_end for every entry.  The entries' indices live on the device, so this
+    // bound is what keeps a list from asking a sampler for an index outside its domain (the stratified permutation walk
+    // need not end there).  Chunks are cut by pixel count — a list has no tile boundaries; t_begin / t_end stay 0.
+    const char* set_pixel_list(uint64_t n_pixels, uint32_t n_passes, uint32_t list_passes, uint64_t sample_end, uint32_t sampler_spp, uint64_t sample_buf_cap) {
+        accumulating = sample_table = true;
+        if (n_passes == 0 || n_passes > 0xFFFFu || n_passes > list_passes) return "bad number of passes";
+        if (sample_end > sampler_spp) return "pixel list: sample (+ passes) beyond the sampler's samples per pixel";
+        if (n_pixels > 0xFFFFFFFFull) return "too many pixels in one call";
+        spp = n_passes;
+        sample_base = 0;
+        total_px = n_pixels;
+        total_work = total_px * spp;
+        max_px_chunk = std::min<uint64_t>(0xFFFFFFF0ull / spp, sample_buf_cap / (16ull * spp));
+        if (max_px_chunk == 0) return "sample_buf_cap too small for one pixel";
+        chunks.clear();
+        for (uint64_t px0 = 0; px0 < total_px; px0 += max_px_chunk) chunks.push_back(Chunk{0, 0, (uint32_t)px0, (uint32_t)std::min<uint64_t>(max_px_chunk, total_px - px0)});
+        return nullptr;
+    }
+
     // after set_chunks.  Work is cut into batches of <= batch_paths camera samples.  With streams >= 2 batches alternate
     // between two work sets / HIP streams, so the latency-bound tail launches of one batch (late bounces, few rays) run
     // beside the bulk launches of the other.  A job that fits one batch stays on one work set: splitting it gains nothing
