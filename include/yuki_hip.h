@@ -284,7 +284,9 @@ yk_status yk_context_interrupt(yk_context* ctx);
  * edges of at least this many pixels are drawn by a whole wave in yk_overlay_draw[_device], shorter ones by one lane);
  * "denoise_lds_max_step" (0 | 1 | 2, default 2: the a-trous iterations of yk_denoise[_device] with a step up to this
  * stage their taps in LDS, the others read global memory); "update_top_block" (0 | 1, default 1: the device route of
- * yk_scene_update finishes the tree's top levels of at most 256 nodes each with one block instead of a launch per level).  Test hook: "trace_stage_kernel" (0, default: yk_trace_closest /
+ * yk_scene_update finishes the tree's top levels of at most 256 nodes each with one block instead of a launch per level);
+ * "albedo_mean_band_rows" (0 .. 65535, default 0: the output rows yk_render_albedo_mean[_device] traces and reduces at a
+ * time; 0 = as many as fit its 64 MiB scratch).  Test hook: "trace_stage_kernel" (0, default: yk_trace_closest /
  * yk_trace_any run the generic kernels as documented | 1: the generic kernels in the render loop's
  * flavour | 2: the wave-packet kernels; modes 1 and 2 report shape ids and verdicts only, and
  * refuse out_t, out_bary, counters, a closest-hit t_max and, in mode 2, a tree deeper than 64
@@ -874,9 +876,21 @@ yk_status yk_history_reproject_moved_device(yk_context* ctx, const yk_temporal_d
  *     these colours, so sigma_color acts on demodulated radiance;
  *   out: the last iteration's sum(w * c_Q) / sum(w) is multiplied by the pixel's own d;
  *   iterations = 0: the normalised film, copied as bits: no division, no product.
- * Not handled: texels smaller than a pixel (the albedo is that of ONE ray through the pixel centre, not the mean over the
- *   pixel's samples: there the quotient is noisier than the film and plain yk_denoise is the better choice), glass, metal and
- *   glossy surfaces, textured spheres, yk_multi scenes. */
+ * Pixel mean (yk_albedo_mean, yk_render_albedo_mean): where texels or edges are smaller than a pixel, the record of one
+ *   ray through the pixel centre is not the albedo of what the film averaged; these entry points write the mean of the
+ *   first-hit albedo over an s x s grid of sub-pixel rays into the same yk_albedo record, which every consumer takes
+ *   unchanged.
+ *   Sub-samples: output pixel (x, y) of a res_x x res_y film covers the pixels (s*x + i, s*y + j), i, j = 0..s-1, of the
+ *     (s*res_x) x (s*res_y) film of the same view: yk_camera_init with res = (s*res_x, s*res_y) and otherwise the same
+ *     parameters.  The sub-rays are that camera's pixel-centre rays, exactly what yk_render_guides_ids traces.
+ *   Per sub-sample: the record of its id by the six cases above; an unknown one enters the sum as (1, 1, 1).
+ *   Mean, per channel: the first value (j = 0, i = 0), then every further one added in binary32 with j outer and i inner,
+ *     left to right, every addition separate; one correctly rounded division by (float)(s*s); a NaN this produces is
+ *     0x7fc00000.  known = 1 if any sub-sample is known, else 0; a block of unknown sub-samples is (1, 1, 1, 0) exactly.
+ *     s = 1 copies the one record: yk_surface_albedo's, bit for bit.
+ *   Range: 1 <= s <= YK_ALBEDO_MEAN_MAX_S; s*res_x and s*res_y <= 65535 (pixel coordinates travel in 16 bits each).
+ * Not handled: glass, metal and glossy surfaces, textured spheres, yk_multi scenes.  The mean is over a regular grid, not
+ *   over the film's own samples; an edge pixel between a matte and a non-matte surface mixes its albedo with ones. */
 #define YK_ALBEDO_FLOOR 0.015625f /* 2^-6, exact */
 typedef struct yk_albedo {
     float a[3];  /* the first hit's diffuse albedo; (1, 1, 1) where it is not known */
@@ -893,6 +907,29 @@ yk_status yk_surface_albedo(yk_context* ctx, const yk_scene* scene, const yk_sur
  * launched), enqueued on `stream` (NULL = the context's) without waiting for the device: one launch, no allocation. */
 yk_status yk_surface_albedo_device(yk_context* ctx, const yk_scene* scene, const void* d_ids, uint16_t res_x, uint16_t res_y,
                                    void* d_out, void* stream);
+/* The pixel-mean albedo from the ids of the large film: the reduction alone.  ids_ss holds (s*res_x) * (s*res_y) records,
+ * row-major; out res_x * res_y.  ctx NULL = the host instance (it reads the scene's tables as yk_surface_albedo does), else
+ * on ctx's device (synchronous).
+ * YK_ERR_INVALID_ARGUMENT: a NULL pointer, a zero resolution, s outside 1..YK_ALBEDO_MEAN_MAX_S, s*res_x or s*res_y over
+ * 65535, an output that overlaps the ids, with a context a scene of another device. */
+#define YK_ALBEDO_MEAN_MAX_S 8u
+yk_status yk_albedo_mean(yk_context* ctx, const yk_scene* scene, const yk_surface_id* ids_ss, uint16_t res_x, uint16_t res_y,
+                         uint32_t s, yk_albedo* out);
+/* The same on device buffers (both 16-byte aligned, not overlapping; anything else: YK_ERR_INVALID_ARGUMENT, nothing is
+ * launched), enqueued on `stream` (NULL = the context's) without waiting for the device: one launch, no allocation. */
+yk_status yk_albedo_mean_device(yk_context* ctx, const yk_scene* scene, const void* d_ids_ss, uint16_t res_x, uint16_t res_y,
+                                uint32_t s, void* d_out, void* stream);
+/* The fused route: traces the large film and reduces it, bit for bit yk_albedo_mean of yk_render_guides_ids at
+ * (s*res_x, s*res_y) under camera_ss — the yk_camera of THAT resolution.  The large film is never materialised: it is
+ * traced in bands of output rows whose ids go through a scratch the context owns (64 MiB, allocated by the first call; the
+ * context option "albedo_mean_band_rows" sets the output rows per band, 0 = as many as fit the scratch; only a band that
+ * needs more than the scratch holds allocates again).  Needs a context, as yk_render_guides does.  The _device form is
+ * ordered on `stream` (NULL = the context's) as yk_render_guides_device is; d_out is 16-byte aligned.
+ * YK_ERR_INVALID_ARGUMENT, nothing launched: as yk_albedo_mean, a NULL camera, a misaligned output. */
+yk_status yk_render_albedo_mean(yk_context* ctx, const yk_scene* scene, const yk_camera* camera_ss, uint16_t res_x, uint16_t res_y,
+                                uint32_t s, yk_albedo* out);
+yk_status yk_render_albedo_mean_device(yk_context* ctx, const yk_scene* scene, const yk_camera* camera_ss, uint16_t res_x,
+                                       uint16_t res_y, uint32_t s, void* d_out, void* stream);
 /* yk_denoise with the albedo records; arguments and errors as yk_denoise, plus: a NULL albedo, an albedo that overlaps the
  * output. */
 yk_status yk_denoise_albedo(yk_context* ctx, const yk_denoise_desc* desc, const float* film_rgb, const yk_guide* guides,

@@ -280,6 +280,23 @@ inline std::vector<Albedo> surface_albedo(Context* ctx, const Scene& scene, cons
 inline void surface_albedo_device(Context& ctx, const Scene& scene, const void* d_ids, uint16_t res_x, uint16_t res_y, void* d_out, void* stream = nullptr) {
     check(yk_surface_albedo_device(ctx.handle(), scene.handle(), d_ids, res_x, res_y, d_out, stream), ctx.handle());
 }
+// The pixel-mean albedo: the mean of the first-hit albedo over the s x s block of the (s*res_x) x (s*res_y) film's ids under
+// every output pixel (res_x * res_y records).  ctx == nullptr: the host instance.
+inline std::vector<Albedo> albedo_mean(Context* ctx, const Scene& scene, const yk_surface_id* ids_ss, uint16_t res_x, uint16_t res_y, uint32_t s) {
+    std::vector<Albedo> out((size_t)res_x * res_y);
+    yk_context* c = ctx ? ctx->handle() : nullptr;
+    check(yk_albedo_mean(c, scene.handle(), ids_ss, res_x, res_y, s, out.data()), c);
+    return out;
+}
+// The same on device buffers, enqueued on `stream` (nullptr: the context's): one kernel, no allocation, no synchronisation.
+inline void albedo_mean_device(Context& ctx, const Scene& scene, const void* d_ids_ss, uint16_t res_x, uint16_t res_y, uint32_t s, void* d_out, void* stream = nullptr) {
+    check(yk_albedo_mean_device(ctx.handle(), scene.handle(), d_ids_ss, res_x, res_y, s, d_out, stream), ctx.handle());
+}
+// The fused route: the large film traced in bands under `camera_ss` (the camera of (s*res_x, s*res_y)) and reduced, never whole.
+inline void render_albedo_mean_device(Context& ctx, const Scene& scene, const yk_camera& camera_ss, uint16_t res_x, uint16_t res_y, uint32_t s, void* d_out,
+                                      void* stream = nullptr) {
+    check(yk_render_albedo_mean_device(ctx.handle(), scene.handle(), &camera_ss, res_x, res_y, s, d_out, stream), ctx.handle());
+}
 // yk_denoise on radiance / albedo: the film (row-major RGB; `samples` = Film.samples or nullptr) -> the denoised film.
 inline std::vector<float> denoise_albedo(Context* ctx, const yk_denoise_desc& desc, const float* film, const yk_guide* guides, const Albedo* albedo, uint16_t res_x,
                                          uint16_t res_y, uint16_t tile_dim, const uint32_t* samples = nullptr) {

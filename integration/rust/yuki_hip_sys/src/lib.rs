@@ -317,6 +317,7 @@ pub struct yk_motion {
 
 /// The floor under the divisor of `yk_denoise_albedo`, 2^-6
 pub const YK_ALBEDO_FLOOR: f32 = 0.015625;
+pub const YK_ALBEDO_MEAN_MAX_S: u32 = 8;
 
 /// The diffuse albedo of a pixel's first hit; known = 0: nothing to demodulate by (then a is all ones); 16-byte aligned on
 /// the device (yuki_amd/csrc/yk_albedo.h)
@@ -560,6 +561,10 @@ extern "C" {
     pub fn yk_history_reproject_moved_device(ctx: *mut yk_context, desc: *const yk_temporal_desc, d_prev_history: *const c_void, d_prev_guides: *const c_void, prev_camera: *const yk_camera, d_guides: *const c_void, d_motion: *const c_void, res_x: u16, res_y: u16, d_out_history: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_surface_albedo(ctx: *mut yk_context, scene: *const yk_scene, ids: *const yk_surface_id, res_x: u16, res_y: u16, out: *mut yk_albedo) -> yk_status;
     pub fn yk_surface_albedo_device(ctx: *mut yk_context, scene: *const yk_scene, d_ids: *const c_void, res_x: u16, res_y: u16, d_out: *mut c_void, stream: *mut c_void) -> yk_status;
+    pub fn yk_albedo_mean(ctx: *mut yk_context, scene: *const yk_scene, ids_ss: *const yk_surface_id, res_x: u16, res_y: u16, s: u32, out: *mut yk_albedo) -> yk_status;
+    pub fn yk_albedo_mean_device(ctx: *mut yk_context, scene: *const yk_scene, d_ids_ss: *const c_void, res_x: u16, res_y: u16, s: u32, d_out: *mut c_void, stream: *mut c_void) -> yk_status;
+    pub fn yk_render_albedo_mean(ctx: *mut yk_context, scene: *const yk_scene, camera_ss: *const yk_camera, res_x: u16, res_y: u16, s: u32, out: *mut yk_albedo) -> yk_status;
+    pub fn yk_render_albedo_mean_device(ctx: *mut yk_context, scene: *const yk_scene, camera_ss: *const yk_camera, res_x: u16, res_y: u16, s: u32, d_out: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_denoise_albedo(ctx: *mut yk_context, desc: *const yk_denoise_desc, film_rgb: *const f32, guides: *const yk_guide, albedo: *const yk_albedo, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, out_rgb: *mut f32) -> yk_status;
     pub fn yk_denoise_albedo_device(ctx: *mut yk_context, desc: *const yk_denoise_desc, d_film_rgb: *const c_void, d_guides: *const c_void, d_albedo: *const c_void, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, d_out_rgb: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_moments_blend(ctx: *mut yk_context, desc: *const yk_temporal_desc, film_rgb: *const f32, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, moments: *const yk_moments, out_moments: *mut yk_moments) -> yk_status;

@@ -156,10 +156,40 @@ pub unsafe fn albedo_device(
     }
 }
 
+/// The pixel-mean albedo (yuki_amd/csrc/yk_albedo.h, `al_mean_pixel`): where texels or edges are smaller than a pixel,
+/// the worker fills `d_albedo` with this instead of `albedo_device` — the mean of the first-hit albedo over an `s x s`
+/// grid of sub-pixel rays, in the same 16-byte record, so `denoise_albedo_device` below takes it unchanged.  It needs no
+/// ids: the library traces the `s`-times larger film itself, in bands through a scratch the context owns.  `camera_ss` is
+/// the `yk_camera` of that larger film: `yk_camera_init` with `res = (s * res.x, s * res.y)` and otherwise the parameters
+/// of the film's own camera.  Like the guides it changes only with the camera or the scene; at 1080p `s = 2` costs about
+/// three guide passes and `s = 4` about ten, so the worker calls it once per view, not per displayed
+/// frame.
+///
+/// # Safety
+/// `d_albedo` is a device allocation of `res.x * res.y * 16` bytes on `ctx`'s device, 16-byte aligned; `scene` was created
+/// on it; `1 <= s <= YK_ALBEDO_MEAN_MAX_S` and `s * res` fits 16 bits.
+pub unsafe fn albedo_mean_device(
+    ctx: *mut sys::yk_context,
+    scene: *const sys::yk_scene,
+    camera_ss: &sys::yk_camera,
+    res: Vec2<u16>,
+    s: u32,
+    d_albedo: *mut c_void,
+    stream: *mut c_void,
+) -> Result<(), sys::yk_status> {
+    let status = sys::yk_render_albedo_mean_device(ctx, scene, camera_ss, res.x, res.y, s, d_albedo, stream);
+    if status == sys::YK_OK {
+        Ok(())
+    } else {
+        Err(status)
+    }
+}
+
 /// `denoise_device` on radiance / albedo: the filter no longer has to choose between blurring a texture and keeping the
 /// noise on it.  Glass, metal, glossy surfaces and textured spheres are filtered as before (their albedo record is all
-/// ones); texels smaller than a pixel are better left to `denoise_device`.  After a temporal blend the blended RGB goes
-/// in with `samples = None`, as it goes into `denoise_device`.
+/// ones).  `d_albedo` is `albedo_device`'s record of the centre ray or, where texels are smaller than a pixel,
+/// `albedo_mean_device`'s mean over the pixel.  After a temporal blend the blended RGB goes in with `samples = None`, as
+/// it goes into `denoise_device`.
 ///
 /// # Safety
 /// As `denoise_device`; `d_albedo` is `albedo_device`'s buffer and does not overlap the output.

@@ -184,6 +184,10 @@ SYMBOLS = {
     "yk_surface_motion_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint16, C.c_uint16, vp, vp]),
     "yk_surface_albedo": (C.c_int, [vp, vp, vp, C.c_uint16, C.c_uint16, vp]),
     "yk_surface_albedo_device": (C.c_int, [vp, vp, vp, C.c_uint16, C.c_uint16, vp, vp]),
+    "yk_albedo_mean": (C.c_int, [vp, vp, vp, C.c_uint16, C.c_uint16, C.c_uint32, vp]),
+    "yk_albedo_mean_device": (C.c_int, [vp, vp, vp, C.c_uint16, C.c_uint16, C.c_uint32, vp, vp]),
+    "yk_render_albedo_mean": (C.c_int, [vp, vp, C.POINTER(abi.CameraMatrices), C.c_uint16, C.c_uint16, C.c_uint32, vp]),
+    "yk_render_albedo_mean_device": (C.c_int, [vp, vp, C.POINTER(abi.CameraMatrices), C.c_uint16, C.c_uint16, C.c_uint32, vp, vp]),
     "yk_denoise_albedo": (C.c_int, [vp, C.POINTER(abi.DenoiseDesc), vp, vp, vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp]),
     "yk_denoise_albedo_device": (C.c_int, [vp, C.POINTER(abi.DenoiseDesc), vp, vp, vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp]),
     "yk_history_reproject_moved": (C.c_int, [vp, C.POINTER(abi.TemporalDesc), vp, vp, C.POINTER(abi.CameraMatrices), vp, vp, C.c_uint16, C.c_uint16, vp]),

@@ -235,6 +235,7 @@ SURFACE_ID_DTYPE = np.dtype([("shape", "<u4"), ("b", "<f4", 3)])  # yk_surface_i
 MOTION_DTYPE = np.dtype([("p_prev", "<f4", 3), ("known", "<f4")])  # yk_motion, 16 bytes
 ALBEDO_DTYPE = np.dtype([("a", "<f4", 3), ("known", "<f4")])  # yk_albedo, 16 bytes
 ALBEDO_FLOOR = 0.015625  # YK_ALBEDO_FLOOR, 2^-6
+ALBEDO_MEAN_MAX_S = 8  # YK_ALBEDO_MEAN_MAX_S: the largest sub-sample grid of yk_albedo_mean
 MOMENTS_DTYPE = np.dtype([("m1", "<f4"), ("m2", "<f4"), ("frames", "<f4"), ("n", "<f4")])  # yk_moments, 16 bytes: yk_history's layout
 PIXEL_STATS_DTYPE = np.dtype([("mean", "<f4"), ("m2", "<f4"), ("n", "<u4"), ("drawn", "<u4")])  # yk_pixel_stats, 16 bytes
 

@@ -397,6 +397,50 @@ def surface_albedo(scene, ids, ctx=None):
     return out
 
 
+def _mean_s(s):
+    s = int(s)
+    if not 1 <= s <= abi.ALBEDO_MEAN_MAX_S:
+        raise ValueError(f"s is 1 .. {abi.ALBEDO_MEAN_MAX_S}, not {s}")
+    return s
+
+
+def albedo_mean(scene, ids_ss, s, ctx=None):
+    """yk_albedo_mean: the pixel-mean albedo.  `ids_ss` is render_guides_ids' (s * h, s * w) ids of the s-times larger film
+    of the same view -> (h, w) abi.ALBEDO_DTYPE records: per channel the float32 mean of surface_albedo's records over every
+    pixel's s x s block, known = 1 where any of them is known (csrc/yk_albedo.h).  Every consumer of surface_albedo's
+    records takes them.  ctx None = the host instance."""
+    s = _mean_s(s)
+    ids_ss = np.ascontiguousarray(ids_ss, dtype=abi.SURFACE_ID_DTYPE)
+    if ids_ss.ndim != 2 or ids_ss.shape[0] % s or ids_ss.shape[1] % s or ids_ss.size == 0:
+        raise ValueError("ids_ss is (s * h, s * w)")
+    h, w = ids_ss.shape[0] // s, ids_ss.shape[1] // s
+    out = np.zeros((h, w), dtype=abi.ALBEDO_DTYPE)
+    c = ctx.h if ctx else None
+    check(lib().yk_albedo_mean(c, scene.h, _p(ids_ss), w, h, s, _p(out)), c)
+    return out
+
+
+def supersampled(film_settings, s):
+    """The FilmSettings of the s-times larger film of the same view: the film whose pixel centres are the sub-pixel rays of
+    albedo_mean."""
+    s = _mean_s(s)
+    w, h = film_settings.res
+    if s * w > 65535 or s * h > 65535:
+        raise ValueError(f"s * res = {(s * w, s * h)} exceeds 65535")
+    return FilmSettings(res=(s * w, s * h), tile_dim=film_settings.tile_dim)
+
+
+def render_albedo_mean(ctx, scene, camera_params, film_settings, s=2):
+    """yk_render_albedo_mean: albedo_mean of the s-times larger film's ids, traced and reduced on the device in bands of rows
+    (the large film never exists) -> (h, w) abi.ALBEDO_DTYPE records, bit for bit albedo_mean(render_guides_ids(...)[1]) at
+    the large resolution.  `camera_params` is the camera description Camera takes; the s-times larger camera is built here."""
+    w, h = film_settings.res
+    cam_ss = Camera(camera_params, supersampled(film_settings, s))
+    out = np.zeros((h, w), dtype=abi.ALBEDO_DTYPE)
+    check(lib().yk_render_albedo_mean(ctx.h, scene.h, C.byref(cam_ss.matrices), w, h, int(s), _p(out)), ctx.h)
+    return out
+
+
 def reproject_history_moved(history, prev_guides, prev_camera, guides, motion, params, ctx=None):
     """yk_history_reproject_moved: reproject_history after the geometry moved: every pixel is carried from where its
     surface point stood (`motion`, surface_motion's records) instead of from where it stands.  ctx None = the host
@@ -989,6 +1033,20 @@ class Context:
         on `stream` (default: the context's) without waiting."""
         vp = C.c_void_p
         check(lib().yk_surface_albedo_device(self.h, scene.h, vp(d_ids_ptr), int(res[0]), int(res[1]), vp(d_out_ptr), vp(stream)), self.h)
+
+    def albedo_mean_device(self, scene, d_ids_ss_ptr, res, s, d_out_ptr, stream=None):
+        """yk_albedo_mean_device: the device ids of the (s * res[0]) x (s * res[1]) film -> res[0] * res[1] device yk_albedo
+        records (both 16-byte aligned), enqueued on `stream` (default: the context's) without waiting; one launch, no
+        allocation."""
+        vp = C.c_void_p
+        check(lib().yk_albedo_mean_device(self.h, scene.h, vp(d_ids_ss_ptr), int(res[0]), int(res[1]), int(s), vp(d_out_ptr), vp(stream)), self.h)
+
+    def render_albedo_mean_device(self, scene, camera_ss, res, s, d_out_ptr, stream=None):
+        """yk_render_albedo_mean_device: the pixel-mean albedo of the film `res` into res[0] * res[1] device yk_albedo records
+        (16-byte aligned), ordered on `stream` (default: the context's) without waiting on the host.  `camera_ss` is the
+        Camera of the s-times larger film (Camera(params, supersampled(film_settings, s)))."""
+        vp = C.c_void_p
+        check(lib().yk_render_albedo_mean_device(self.h, scene.h, C.byref(camera_ss.matrices), int(res[0]), int(res[1]), int(s), vp(d_out_ptr), vp(stream)), self.h)
 
     def reproject_history_moved_device(self, d_prev_history_ptr, d_prev_guides_ptr, prev_camera, d_guides_ptr, d_motion_ptr, res, params, d_out_history_ptr, stream=None):
         """yk_history_reproject_moved_device: reproject_history_device through the device motion records of

@@ -7,12 +7,13 @@
 //   - IEEE-754 binary32, round to nearest, every operation separate (-ffp-contract=off), divisions correctly rounded;
 //   - a NaN that an operation PRODUCES is 0x7fc00000 (dn_canon); a value that is only copied keeps its bits.
 // One text, two instances: the host instance (no context) and the kernels of yk_albedo.hip / yk_denoise.hip call
-// al_pixel, al_divisor, al_demodulate and al_remodulate and agree bit for bit.
+// al_pixel, al_mean_pixel, al_divisor, al_demodulate and al_remodulate and agree bit for bit.
 //
-// Limits (DESIGN.md §7.7):
-//   - Sub-pixel texels.  The albedo is that of ONE ray through the pixel centre, not the mean albedo of the pixel's
-//     samples: where texels are smaller than a pixel the quotient is noisier than the film and demodulation does not pay
-//     (measured: 0.0807 against 0.0790 plain on a 64x64 texture at 64x36).
+// Limits (DESIGN.md §7.7, §7.11):
+//   - Sub-pixel texels and edges.  al_pixel's record is that of ONE ray through the pixel centre; where texels or edges
+//     are smaller than a pixel the film averaged something else and the quotient is noisier than it should be.
+//     al_mean_pixel (below) is the answer: the mean over an s x s grid of sub-pixel rays.  That grid is regular, not the
+//     film's own samples, and an edge pixel between a matte and a non-matte surface mixes its albedo with ones.
 //   - Glass, metal and glossy surfaces are not demodulated (their record is all ones), nor are textured spheres: a
 //     sphere's uv needs the hit point and libm.
 //   - yk_multi scenes are not served; the temporal history stays in radiance.
@@ -132,5 +133,57 @@ YK_HD void al_remodulate(const float* albedo, float* c) {
     c[2] = dn_canon(c[2] * al_divisor(albedo[2]));
 }
 // iterations == 0 returns the normalised film, copied as bits: no division and no product.
+
+// ---- the pixel-mean albedo (yk_albedo_mean): the mean of al_pixel over an s x s grid of sub-pixel rays
+//
+// Sub-samples.  Output pixel (x, y) of a res_x x res_y film covers the s x s block of pixels (s*x + i, s*y + j), i, j =
+// 0..s-1, of the (s*res_x) x (s*res_y) film of the same view: the film of yk_camera_init with res = (s*res_x, s*res_y) and
+// otherwise the same parameters, whose pixel-centre rays yk_render_guides_ids traces.  `ids_ss` holds that film's id
+// records, row-major, s*a.res_x to a row; a.res_x and a.res_y are the OUTPUT film's.  1 <= s <= 8.
+// Per sub-sample: al_pixel's record of its id, all six cases; an unknown one is (1, 1, 1, 0) and enters the sum as ones.
+// Mean, per channel: the first value (j = 0, i = 0) as it is, then every further one added to it in binary32, j outer and
+// i inner, left to right, every addition separate; then ONE correctly rounded division by (float)(s*s), and dn_canon of
+// the quotient (a NaN the sum or the division produces is 0x7fc00000).  s == 1: no addition and no division — the one
+// record is copied, bit for bit yk_surface_albedo's.
+// known = 1.0f if any sub-sample is known, else 0.0f; s*s ones sum to s*s exactly and (float)(s*s) / (float)(s*s) is 1, so a
+// block of unknown sub-samples comes out as (1, 1, 1, 0) exactly.
+// The loop bounds are the same for every lane, every id index lies inside the film and al_pixel clamps the rest: no load
+// stands under a per-lane branch.
+// An id record as four words: one 16-byte load of the device's records (16-byte aligned), four fields of a host array's.
+YK_HD uint4 al_id(const uint4* p) { return *p; }
+YK_HD uint4 al_id(const yk_surface_id* p) { return make_uint4(p->shape, __builtin_bit_cast(uint32_t, p->b[0]), __builtin_bit_cast(uint32_t, p->b[1]), __builtin_bit_cast(uint32_t, p->b[2])); }
+template <class Id> YK_HD void al_mean_pixel(const AlParams& a, const DevScene& sc, const Id* ids_ss, uint32_t x, uint32_t y, uint32_t s, float* out) {
+    const size_t row = (size_t)s * a.res_x;  // records to a row of the large film
+    float sum0 = 0.0f, sum1 = 0.0f, sum2 = 0.0f;
+    bool any = false;
+    for (uint32_t j = 0; j < s; ++j) {
+        const Id* line = ids_ss + ((size_t)s * y + j) * row + (size_t)s * x;
+        for (uint32_t i = 0; i < s; ++i) {
+            const uint4 id = al_id(line + i);
+            float rec[4];
+            al_pixel(a, sc, id.x, __builtin_bit_cast(float, id.y), __builtin_bit_cast(float, id.z), __builtin_bit_cast(float, id.w), rec);
+            const bool first = j == 0u && i == 0u;
+            sum0 = first ? rec[0] : sum0 + rec[0];
+            sum1 = first ? rec[1] : sum1 + rec[1];
+            sum2 = first ? rec[2] : sum2 + rec[2];
+            any = any || rec[3] != 0.0f;
+        }
+    }
+    if (s != 1u) {
+        const float n = (float)(s * s);
+        sum0 = dn_canon(sum0 / n);
+        sum1 = dn_canon(sum1 / n);
+        sum2 = dn_canon(sum2 / n);
+    }
+    out[0] = sum0;
+    out[1] = sum1;
+    out[2] = sum2;
+    out[3] = any ? 1.0f : 0.0f;
+}
+
+// The two device steps of the fused route (yk_render_albedo_mean), defined in yk_albedo.hip and driven band by band from
+// yk_render.cpp.  launch_ids_band: k_guides_ids' id record of every traced camera ray of the rows [row0, row0 + rows) of a
+// res_x-wide film, written at (y - row0) * res_x + x of a band buffer instead of at its place in the whole film.
+void launch_ids_band(hipStream_t s, const DevScene& sc, PathBuffers cur, const int* hit_tri, uint32_t n, const uint32_t* pixel_xy, uint32_t res_x, uint32_t row0, uint32_t rows, uint4* ids);
 
 }  // namespace yk

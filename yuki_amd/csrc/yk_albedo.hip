@@ -1,6 +1,7 @@
-// yk_albedo.hip — first-hit albedo on gfx950, behind yk_surface_albedo[_device]; the per-pixel rule is yk_albedo.h's, whose
-// host instance these entry points run without a context.  (The demodulated denoise that reads the records is in
-// yk_denoise.hip, next to the filter it wraps.)
+// yk_albedo.hip — first-hit albedo on gfx950, behind yk_surface_albedo[_device], and its mean over a pixel, behind
+// yk_albedo_mean[_device] and the bands of yk_render_albedo_mean (driven from yk_render.cpp); the per-pixel rules are
+// yk_albedo.h's, whose host instances these entry points run without a context.  (The demodulated denoise that reads the
+// records is in yk_denoise.hip, next to the filter it wraps.)
 //
 // k_albedo: one lane per pixel, a block is an AL_TX x AL_TY tile of the film (k_motion's launch shape: neighbouring lanes
 //   hit neighbouring triangles and, on a textured surface, neighbouring texels, so their requests share cache lines).  A
@@ -32,6 +33,41 @@ __global__ __launch_bounds__(AL_TX* AL_TY) void k_albedo(const uint4* __restrict
     out[i] = make_float4(rec[0], rec[1], rec[2], rec[3]);
 }
 
+// k_albedo_mean (yk_albedo_mean[_device], and every band of yk_render_albedo_mean): one lane per OUTPUT pixel, the same
+//   AL_TX x AL_TY tile.  A lane walks its s x s block of the large film's ids row by row (j outer, i inner: al_mean_pixel's
+//   summation order), each id a 16-byte load followed by al_pixel's clamped four-hop gather, and writes one 16-byte record.
+//   Lanes along x read ids 16*s bytes apart: a wave's 32 lanes of one row cover 512*s contiguous bytes per j, every byte
+//   of which some lane uses within the same inner loop, so each line is fetched from HBM once and served from L2 after.
+//   a.res_x x a.res_y is the output film (or one band of it); the ids have s*a.res_x records to a row.
+__global__ __launch_bounds__(AL_TX* AL_TY) void k_albedo_mean(const uint4* __restrict__ ids_ss, DevScene sc, AlParams a, uint32_t s, float4* __restrict__ out) {
+    const uint32_t x = blockIdx.x * AL_TX + threadIdx.x, y = blockIdx.y * AL_TY + threadIdx.y;
+    if (x >= a.res_x || y >= a.res_y) return;
+    float rec[4];
+    al_mean_pixel(a, sc, ids_ss, x, y, s, rec);
+    out[(size_t)y * a.res_x + x] = make_float4(rec[0], rec[1], rec[2], rec[3]);
+}
+
+// k_ids_band: k_guides_ids' id record alone (the same hit_surface_prim call, so the same bits), for the rays of a band of
+//   rows [row0, row0 + rows) of a res_x-wide film, written at (y - row0) * res_x + x of the band's buffer.  The band's tile
+//   holds these rows only; a pixel outside them or right of res_x writes nothing, so the index stays inside res_x * rows.
+__global__ void k_ids_band(DevScene sc, PathBuffers cur, const int* hit_tri, uint32_t n, const uint32_t* pixel_xy, uint32_t res_x, uint32_t row0, uint32_t rows, uint4* ids) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 rd = cur.rayD[i];
+    const uint32_t xy = pixel_xy[__float_as_uint(rd.w)];
+    const uint32_t yb = (xy >> 16) - row0, xb = xy & 0xffffu;
+    if (yb >= rows || xb >= res_x) return;  // also a row above row0: the difference wraps
+    const size_t px = (size_t)yb * res_x + xb;
+    const int tri = hit_tri[i];
+    uint4 id = make_uint4(YK_SURFACE_NONE, 0u, 0u, 0u);
+    if (tri >= 0) {
+        float t = 0.0f;
+        const float4 ro = cur.rayO[i];
+        (void)hit_surface_prim(sc, (uint32_t)tri & YK_HIT_PRIM_MASK, V3{ro.x, ro.y, ro.z}, V3{rd.x, rd.y, rd.z}, sc.texels != nullptr, &t, &id);
+    }
+    ids[px] = id;
+}
+
 yk_status check_call(const yk_scene* scene, const void* ids, uint16_t res_x, uint16_t res_y, const void* out) {
     if (!scene || !ids || !out || res_x == 0 || res_y == 0) return YK_ERR_INVALID_ARGUMENT;
     const size_t n_px = (size_t)res_x * res_y;
@@ -39,7 +75,7 @@ yk_status check_call(const yk_scene* scene, const void* ids, uint16_t res_x, uin
     return YK_OK;
 }
 
-AlParams make_params(const yk_scene* scene, uint16_t res_x, uint16_t res_y) {
+AlParams make_params(const yk_scene* scene, uint32_t res_x, uint32_t res_y) {
     AlParams a{};
     a.res_x = res_x;
     a.res_y = res_y;
@@ -114,7 +150,40 @@ void albedo_host(const yk_scene* scene, const DevScene& sc, const yk_surface_id*
     }
 }
 
+// yk_albedo_mean's arguments: the ids are those of the (s * res_x) x (s * res_y) film
+yk_status check_mean_call(const yk_scene* scene, const void* ids_ss, uint16_t res_x, uint16_t res_y, uint32_t s, const void* out) {
+    if (!scene || !ids_ss || !out || res_x == 0 || res_y == 0) return YK_ERR_INVALID_ARGUMENT;
+    if (s < 1u || s > YK_ALBEDO_MEAN_MAX_S || s * res_x > 65535u || s * res_y > 65535u) return YK_ERR_INVALID_ARGUMENT;
+    const size_t n_px = (size_t)res_x * res_y;
+    if (overlaps(out, n_px * sizeof(yk_albedo), ids_ss, n_px * s * s * sizeof(yk_surface_id))) return YK_ERR_INVALID_ARGUMENT;
+    return YK_OK;
+}
+
+void albedo_mean_host(const yk_scene* scene, const DevScene& sc, const yk_surface_id* ids_ss, uint16_t res_x, uint16_t res_y, uint32_t s, yk_albedo* out) {
+    const AlParams a = make_params(scene, res_x, res_y);
+    for (uint32_t y = 0; y < res_y; ++y)
+        for (uint32_t x = 0; x < res_x; ++x) {
+            float rec[4];
+            al_mean_pixel(a, sc, ids_ss, x, y, s, rec);
+            std::memcpy(&out[(size_t)y * res_x + x], rec, 16);
+        }
+}
+
 }  // namespace
+
+namespace yk {
+void launch_ids_band(hipStream_t s, const DevScene& sc, PathBuffers cur, const int* hit_tri, uint32_t n, const uint32_t* pixel_xy, uint32_t res_x, uint32_t row0, uint32_t rows, uint4* ids) {
+    hipLaunchKernelGGL(k_ids_band, dim3((n + 255u) / 256u), dim3(256), 0, s, sc, cur, hit_tri, n, pixel_xy, res_x, row0, rows, ids);
+}
+}  // namespace yk
+
+yk_status albedo_mean_enqueue(yk_context* ctx, hipStream_t st, const yk_scene* scene, const void* d_ids_ss, uint32_t res_x, uint32_t rows, uint32_t s, void* d_out) {
+    const AlParams a = make_params(scene, res_x, rows);
+    const dim3 grid((res_x + AL_TX - 1) / AL_TX, (rows + AL_TY - 1) / AL_TY), block(AL_TX, AL_TY);
+    hipLaunchKernelGGL(k_albedo_mean, grid, block, 0, st, reinterpret_cast<const uint4*>(d_ids_ss), scene->dev, a, s, reinterpret_cast<float4*>(d_out));
+    HIP_TRY(ctx, hipGetLastError());
+    return YK_OK;
+}
 
 extern "C" {
 
@@ -152,6 +221,41 @@ yk_status yk_surface_albedo_device(yk_context* ctx, const yk_scene* scene, const
     if (misaligned(16, d_ids, d_out))  // 16-byte loads and stores of the records
         return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_surface_albedo_device: ids and output must be 16-byte aligned");
     return enqueue(ctx, device_call_stream(ctx, stream), scene, d_ids, res_x, res_y, d_out);
+}
+
+yk_status yk_albedo_mean(yk_context* ctx, const yk_scene* scene, const yk_surface_id* ids_ss, uint16_t res_x, uint16_t res_y, uint32_t s, yk_albedo* out) try {
+    if (check_mean_call(scene, ids_ss, res_x, res_y, s, out) != YK_OK) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_albedo_mean: bad argument");
+    const size_t n_px = (size_t)res_x * res_y;
+    if (!ctx) {  // the host instance, its tables as yk_surface_albedo's
+        if (!scene->on_device) {
+            albedo_mean_host(scene, host_view(scene->host_shading, scene->upd.host_indices.data()), ids_ss, res_x, res_y, s, out);
+            return YK_OK;
+        }
+        yk_scene::ShadingTables fetched;
+        (void)hipSetDevice(scene->device);
+        HIP_TRY(ctx, fetch_tables(scene, fetched));
+        albedo_mean_host(scene, host_view(fetched, fetched.indices.data()), ids_ss, res_x, res_y, s, out);
+        return YK_OK;
+    }
+    YK_LOCK(ctx);
+    if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_albedo_mean: scene was not created on this context's device");
+    Staging sg(ctx);
+    const yk_surface_id* d_ids = sg.upload(ids_ss, n_px * s * s);
+    yk_albedo* d_out = sg.output(out, n_px);
+    if (!sg.ok()) return sg.status();
+    yk_status rc = albedo_mean_enqueue(ctx, sg.stream, scene, d_ids, res_x, res_y, s, d_out);
+    if (rc != YK_OK) return rc;
+    return sg.finish();
+}
+YK_CATCH(ctx)
+
+yk_status yk_albedo_mean_device(yk_context* ctx, const yk_scene* scene, const void* d_ids_ss, uint16_t res_x, uint16_t res_y, uint32_t s, void* d_out, void* stream) {
+    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
+    YK_LOCK(ctx);
+    if (check_mean_call(scene, d_ids_ss, res_x, res_y, s, d_out) != YK_OK) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_albedo_mean_device: bad argument");
+    if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_albedo_mean_device: scene was not created on this context's device");
+    if (misaligned(16, d_ids_ss, d_out)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_albedo_mean_device: ids and output must be 16-byte aligned");
+    return albedo_mean_enqueue(ctx, device_call_stream(ctx, stream), scene, d_ids_ss, res_x, res_y, s, d_out);
 }
 
 }  // extern "C"

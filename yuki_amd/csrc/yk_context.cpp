@@ -126,6 +126,7 @@ void yk_context_destroy(yk_context* ctx) {
     ctx->temporal.samples.release();
     ctx->adaptive.rank.release();
     ctx->adaptive.tile_count.release();
+    ctx->albedo_mean.ids_band.release();
     if (ctx->tonemap.staging) (void)hipHostFree(ctx->tonemap.staging);
     if (ctx->tonemap.staged) (void)hipEventDestroy(ctx->tonemap.staged);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
@@ -198,6 +199,9 @@ yk_status yk_context_set_option(yk_context* ctx, const char* key, int64_t value)
     } else if (k == "denoise_lds_max_step") {
         if (value < 0 || value > 2) return YK_ERR_INVALID_ARGUMENT;
         ctx->denoise.lds_max_step = value;
+    } else if (k == "albedo_mean_band_rows") {
+        if (value < 0 || value > 65535) return YK_ERR_INVALID_ARGUMENT;
+        ctx->albedo_mean.band_rows = value;
     } else if (k == "update_top_block") {
         ctx->update_top_block = value != 0;
     } else if (k == "time_kernels") {

@@ -80,6 +80,7 @@ struct DevScratch {
     }
 };
 
+#define YK_ALBEDO_MEAN_SCRATCH ((size_t)64 << 20)  // the band scratch budget of yk_render_albedo_mean (the measurement)
 #define YK_BVH_SMALL_RANGE 32  // default of "bvh_small_range" (profiles/bvh_build_device.json: the sweep that chose it)
 
 struct yk_context {
@@ -156,6 +157,11 @@ struct yk_context {
         DevBuf rank;        // one u32 a pixel: the rank inside its 16 x 16 tile, or ~0 where the pixel is not selected
         DevBuf tile_count;  // one u32 a tile: the tile's count, then its base; one more word: the total
     } adaptive;
+    // the fused pixel-mean albedo's scratch (yk_render_albedo_mean, yk_render.cpp): the ids of one band of the large film
+    struct AlbedoMeanState {
+        DevBuf ids_band;        // YK_ALBEDO_MEAN_SCRATCH bytes from the first call on; more only for a band that needs more
+        int64_t band_rows = 0;  // "albedo_mean_band_rows": output rows per band; 0 = as many as fit the scratch budget
+    } albedo_mean;
     // every entry point that touches the context's buffers or streams holds this: calls on one
     // context from several host threads (the reference's tile workers) are serialised
     std::recursive_mutex mu;

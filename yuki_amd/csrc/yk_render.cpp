@@ -28,6 +28,7 @@
 #include <vector>
 
 #include "yk_adaptive.h"
+#include "yk_albedo.h"
 #include "yk_film_call.h"
 #include "yk_render_plan.h"
 #include "yk_staging.h"
@@ -326,8 +327,11 @@ struct RenderRequest {
     // != 0: the guide pass (yk_render_guides) — a debug integrator's trace, one sample a pixel; d_out is then a row-major
     // film of yk_guide records, guides_res_x wide, written by k_guides instead of the shade and resolve kernels.  With
     // d_ids (yk_render_guides_ids) k_guides_ids writes the yk_surface_id records there too, and d_out may be NULL.
+    // With ids_band_rows != 0 (yk_render_albedo_mean) the tiles are rows [ids_row0, ids_row0 + ids_band_rows) of the film and
+    // d_ids is a buffer of that band alone: k_ids_band writes the ids at their place in the band, and no guides.
     uint32_t guides_res_x = 0;
     void* d_ids = nullptr;
+    uint32_t ids_row0 = 0, ids_band_rows = 0;
     void* stream = nullptr;
     yk_render_stats* stats = nullptr;
     yk_cancel_fn cancel = nullptr;
@@ -549,7 +553,9 @@ struct Submission {
         launch_trace_closest(bs, trace_grid(ctx), dev_scene_for(scene, n), pc.rayO, pc.rayD, nullptr, bc0, bc0 + YK_CTRL_HEAD, ws.hit.as<int>(), nullptr,
                              want_stats ? ctx->stats4.as<uint4>() : nullptr, ws.spill.as<uint2>(), spill_stride, errblk, counters());
         kt.end(e, 0, bs);
-        if (rq.guides_res_x && rq.d_ids)
+        if (rq.guides_res_x && rq.d_ids && rq.ids_band_rows)
+            launch_ids_band(bs, scene->dev, pc, ws.hit.as<int>(), n, pixel_xy, rq.guides_res_x, rq.ids_row0, rq.ids_band_rows, reinterpret_cast<uint4*>(rq.d_ids));
+        else if (rq.guides_res_x && rq.d_ids)
             launch_guides_ids(bs, scene->dev, pc, ws.hit.as<int>(), n, pixel_xy, rq.guides_res_x, reinterpret_cast<float4*>(rq.d_out), reinterpret_cast<uint4*>(rq.d_ids));
         else if (rq.guides_res_x)
             launch_guides(bs, scene->dev, pc, ws.hit.as<int>(), n, pixel_xy, rq.guides_res_x, reinterpret_cast<float4*>(rq.d_out));
@@ -1102,6 +1108,76 @@ yk_status yk_render_guides_ids(yk_context* ctx, const yk_scene* scene, const yk_
     if (st != YK_OK) return st;
     return sg.finish();
 }
+
+// The fused pixel-mean albedo (yk_albedo.h): the large film is traced in bands of output rows, so that it never exists as a
+// whole — at 1080p with s = 4 its ids alone are 530 MB.  A band is render_guides' request for the rows [s*y0, s*(y0 + r)) of
+// the large film as one tile, its ids written by k_ids_band into the context's band scratch, then k_albedo_mean over the
+// band into rows [y0, y0 + r) of the output.  Band after band in the caller's stream order: the trace hands over from and
+// back to `stream` (render_tiles_impl), the reduction runs on it, and the next band's trace waits for it before it writes
+// the scratch again.  The scratch is YK_ALBEDO_MEAN_SCRATCH bytes from the first call on; the default band fits it whatever
+// the film (a row of ids is at most 65535 * 8 * 16 bytes), so only a larger "albedo_mean_band_rows" ever grows it.
+static yk_status render_albedo_mean(yk_context* ctx, const yk_scene* scene, const yk_camera* camera_ss, uint16_t res_x, uint16_t res_y, uint32_t s, void* d_out, void* stream) {
+    const uint32_t wide = s * res_x;
+    const size_t row_bytes = (size_t)wide * s * sizeof(yk_surface_id);  // the ids under one output row
+    uint32_t rows = ctx->albedo_mean.band_rows ? (uint32_t)ctx->albedo_mean.band_rows : (uint32_t)std::max<size_t>(1, YK_ALBEDO_MEAN_SCRATCH / row_bytes);
+    rows = std::min<uint32_t>(rows, res_y);
+    (void)hipSetDevice(ctx->device);
+    HIP_TRY(ctx, ctx->albedo_mean.ids_band.ensure(std::max<size_t>(YK_ALBEDO_MEAN_SCRATCH, rows * row_bytes)));
+    const hipStream_t st = device_call_stream(ctx, stream);
+    yk_sampler_desc smp = {};
+    smp.kind = YK_SAMPLER_STRATIFIED;
+    smp.nx = smp.ny = 1;
+    yk_integrator_desc integ = {};
+    integ.kind = YK_INTEGRATOR_SHADING_NORMALS;
+    for (uint32_t y0 = 0; y0 < res_y; y0 += rows) {
+        const uint32_t r = std::min<uint32_t>(rows, res_y - y0);
+        const yk_tile band = {0, (uint16_t)(s * y0), (uint16_t)wide, (uint16_t)(s * (y0 + r))};
+        RenderRequest rq;
+        rq.scene = scene;
+        rq.camera = camera_ss;
+        rq.sampler = &smp;
+        rq.integrator = &integ;
+        rq.tiles = &band;
+        rq.n_tiles = 1;
+        rq.guides_res_x = wide;
+        rq.d_ids = ctx->albedo_mean.ids_band.p;
+        rq.ids_row0 = s * y0;
+        rq.ids_band_rows = s * r;
+        rq.stream = stream;
+        yk_status rc = render_tiles_impl(ctx, rq);
+        if (rc != YK_OK) return rc;
+        if ((rc = albedo_mean_enqueue(ctx, st, scene, ctx->albedo_mean.ids_band.p, res_x, r, s, reinterpret_cast<yk_albedo*>(d_out) + (size_t)y0 * res_x)) != YK_OK) return rc;
+    }
+    return YK_OK;
+}
+
+static bool albedo_mean_args_ok(const yk_scene* scene, const yk_camera* camera_ss, uint16_t res_x, uint16_t res_y, uint32_t s, const void* out) {
+    return scene && camera_ss && out && res_x != 0 && res_y != 0 && s >= 1u && s <= YK_ALBEDO_MEAN_MAX_S && s * res_x <= 65535u && s * res_y <= 65535u;
+}
+
+yk_status yk_render_albedo_mean_device(yk_context* ctx, const yk_scene* scene, const yk_camera* camera_ss, uint16_t res_x, uint16_t res_y, uint32_t s, void* d_out, void* stream) try {
+    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
+    YK_LOCK(ctx);
+    if (!albedo_mean_args_ok(scene, camera_ss, res_x, res_y, s, d_out)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_albedo_mean_device: bad argument");
+    if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_albedo_mean_device: scene was not created on this context's device");
+    if (misaligned(16, d_out)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_albedo_mean_device: the output must be 16-byte aligned");
+    return render_albedo_mean(ctx, scene, camera_ss, res_x, res_y, s, d_out, stream);
+}
+YK_CATCH(ctx)
+
+yk_status yk_render_albedo_mean(yk_context* ctx, const yk_scene* scene, const yk_camera* camera_ss, uint16_t res_x, uint16_t res_y, uint32_t s, yk_albedo* out) try {
+    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
+    YK_LOCK(ctx);
+    if (!albedo_mean_args_ok(scene, camera_ss, res_x, res_y, s, out)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_albedo_mean: bad argument");
+    if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_albedo_mean: scene was not created on this context's device");
+    Staging sg(ctx);
+    yk_albedo* d_out = sg.output(out, (size_t)res_x * res_y);
+    if (!sg.ok()) return sg.status();
+    yk_status st = render_albedo_mean(ctx, scene, camera_ss, res_x, res_y, s, d_out, nullptr);
+    if (st != YK_OK) return st;
+    return sg.finish();
+}
+YK_CATCH(ctx)
 
 yk_status yk_li(yk_context* ctx, const yk_scene* scene, const yk_sampler_desc* sampler, const yk_integrator_desc* integrator, size_t n,
                 const float* ray_o, const float* ray_d, const uint16_t* pixel_xy, const uint32_t* sample_index, uint32_t dimension, float* out_li,
