@@ -126,6 +126,32 @@ def test_device_pointers_offsets_guard_words_and_in_place(ctx, yk, host_results)
         same_bits(_payload(d_film, 1, 3 * n).view(np.float32), want.reshape(-1))
 
 
+@pytest.mark.parametrize("size", [(37, 23), (1, 1)], ids=["37x23", "1x1"])
+def test_every_moments_instance_writes_its_records_only(ctx, yk, host_results, size):
+    """The four instances of the shared record blend that carry the moments rule — {table, no table} x {moments, none} —
+    through blend_moments_device: the records equal the host instance's bit for bit, and neither the film nor an
+    RGB-sized buffer of guard words — the history blend's instances have an RGB output, these have none — is written."""
+    import torch
+
+    s = torch.cuda.Stream()
+    w, h = size
+    n = w * h
+    p = PIC[size]
+    d_film, d_m = _between_guards(torch, 3 * n, 1, p["film"]), _between_guards(torch, 4 * n, 4, p["moments"])
+    d_rgb = _between_guards(torch, 3 * n, 3)
+    for name, case_size, td, sk, hist in BLEND_CASES:
+        if case_size != size:
+            continue
+        d_om = _between_guards(torch, 4 * n, 8)
+        torch.cuda.synchronize()
+        ctx.blend_moments_device(d_film.data_ptr() + 4, size, tparams(yk), td, None if sk is None else p[sk], d_m.data_ptr() + 16 if hist else None, d_om.data_ptr() + 32, stream=s.cuda_stream)
+        s.synchronize()
+        same_bits(_payload(d_om, 8, 4 * n).view(np.float32), moments_words(host_results["blend", name]).reshape(-1))
+        assert np.array_equal(_payload(d_film, 1, 3 * n), p["film"].view(np.uint32).reshape(-1)), name  # only read
+        assert np.array_equal(_payload(d_m, 4, 4 * n), np.ascontiguousarray(p["moments"]).view(np.uint32).reshape(-1)), name
+        assert np.all(d_rgb.cpu().numpy() == GUARD), name
+
+
 def test_misaligned_or_overlapping_buffers_are_refused(ctx, yk):
     import torch
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Device time of the temporal passes (yk_history_reproject_device: k_reproject, yk_history_blend_device: k_blend) on a
+"""Device time of the temporal passes (yk_history_reproject_device: k_reproject, yk_history_blend_device: k_record_blend) on a
 1080p film, from device events.
 
 The scene is cfg3 at 1080p.  Camera A is the scene's own, camera B the same camera a small orbit step (`--orbit-degrees`

@@ -28,6 +28,26 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _vp(a):
+    """A device address or a stream handle as a c_void_p; None or 0 — an array the call leaves out, the context's own
+    stream — as None (NULL)."""
+    return C.c_void_p(a) if a else None
+
+
+def _film(film):
+    """An (h, w, 3) float32 film -> (film, w, h), the film C-contiguous."""
+    film = np.ascontiguousarray(film, dtype=np.float32)
+    if film.ndim != 3 or film.shape[2] != 3:
+        raise ValueError("film is (h, w, 3)")
+    return film, film.shape[1], film.shape[0]
+
+
+def _scene_diagonal(scene):
+    """The diagonal of the scene's bounds (Scene.info()): what the for_scene constructors scale their plane stops by."""
+    i = scene.info()
+    return float(np.linalg.norm(np.array(i.bounds_max[:], dtype=np.float64) - np.array(i.bounds_min[:], dtype=np.float64)))
+
+
 # --------------------------------------------------------------------------- film
 @dataclass
 class FilmSettings:
@@ -222,9 +242,7 @@ class DenoiseParams:
     @staticmethod
     def for_scene(scene, **kw):
         """sigma_plane = 0.01 x the diagonal of the scene's bounds (Scene.info())."""
-        i = scene.info()
-        diag = float(np.linalg.norm(np.array(i.bounds_max[:], dtype=np.float64) - np.array(i.bounds_min[:], dtype=np.float64)))
-        return DenoiseParams(sigma_plane=0.01 * diag, **kw)
+        return DenoiseParams(sigma_plane=0.01 * _scene_diagonal(scene), **kw)
 
     def as_struct(self):
         return abi.DenoiseDesc(int(self.iterations), float(self.sigma_color), float(self.sigma_normal), float("inf") if self.sigma_plane is None else float(self.sigma_plane))
@@ -233,10 +251,7 @@ class DenoiseParams:
 def _denoise_args(res, params, guides, tile_dim, samples):
     if not isinstance(params, DenoiseParams):
         raise TypeError("params is a DenoiseParams")
-    if samples is not None:
-        samples = np.ascontiguousarray(samples, dtype=np.uint32)
-        if int(tile_dim) > 0 and samples.size != _table_len(res, int(tile_dim)):
-            raise ValueError(f"samples has {samples.size} entries, the film's tile grid {_table_len(res, int(tile_dim))}")
+    samples = _blend_samples(res, tile_dim, samples)
     if guides is not None:
         guides = np.ascontiguousarray(guides, dtype=abi.GUIDE_DTYPE)
         if guides.size != int(res[0]) * int(res[1]):
@@ -259,10 +274,7 @@ def denoise(film, guides, params, tile_dim=16, samples=None, ctx=None, albedo=No
     new film; ctx None = the host instance.  albedo (surface_albedo's (h, w) records): yk_denoise_albedo, the same filter
     on radiance / albedo (csrc/yk_albedo.h).  variance (variance()'s (h, w) image) with a VarianceParams:
     yk_denoise_variance, whose colour stop follows the variance (csrc/yk_variance.h); albedo is honoured there too."""
-    film = np.ascontiguousarray(film, dtype=np.float32)
-    if film.ndim != 3 or film.shape[2] != 3:
-        raise ValueError("film is (h, w, 3)")
-    h, w = film.shape[0], film.shape[1]
+    film, w, h = _film(film)
     if variance is not None or isinstance(params, VarianceParams):
         if variance is None:
             raise ValueError("a VarianceParams needs variance (variance())")
@@ -303,9 +315,7 @@ class TemporalParams:
     @staticmethod
     def for_scene(scene, **kw):
         """plane_tolerance = 0.01 x the diagonal of the scene's bounds (Scene.info()), as DenoiseParams.for_scene."""
-        i = scene.info()
-        diag = float(np.linalg.norm(np.array(i.bounds_max[:], dtype=np.float64) - np.array(i.bounds_min[:], dtype=np.float64)))
-        return TemporalParams(plane_tolerance=0.01 * diag, **kw)
+        return TemporalParams(plane_tolerance=0.01 * _scene_diagonal(scene), **kw)
 
     def as_struct(self):
         return abi.TemporalDesc(float("inf") if self.plane_tolerance is None else float(self.plane_tolerance), float(self.normal_cos_min), float(self.max_history))
@@ -471,10 +481,7 @@ def blend_history(film, params, tile_dim=16, samples=None, history=None, ctx=Non
     """yk_history_blend: the current view's (h, w, 3) float32 film (with `samples` = Film.samples for an accumulating one)
     folded into a reprojected history (or None) -> (rgb, history): the film of the means, which downstream passes take with
     samples=None, and the new (h, w) abi.HISTORY_DTYPE history.  ctx None = the host instance."""
-    film = np.ascontiguousarray(film, dtype=np.float32)
-    if film.ndim != 3 or film.shape[2] != 3:
-        raise ValueError("film is (h, w, 3)")
-    h, w = film.shape[0], film.shape[1]
+    film, w, h = _film(film)
     d = _temporal_desc(params)
     samples = _blend_samples((w, h), tile_dim, samples)
     if history is not None:
@@ -508,9 +515,7 @@ class VarianceParams:
     @staticmethod
     def for_scene(scene, **kw):
         """sigma_plane = 0.01 x the diagonal of the scene's bounds (Scene.info()), as DenoiseParams.for_scene."""
-        i = scene.info()
-        diag = float(np.linalg.norm(np.array(i.bounds_max[:], dtype=np.float64) - np.array(i.bounds_min[:], dtype=np.float64)))
-        return VarianceParams(sigma_plane=0.01 * diag, **kw)
+        return VarianceParams(sigma_plane=0.01 * _scene_diagonal(scene), **kw)
 
     def as_struct(self):
         return abi.VarianceDesc(int(self.iterations), float(self.sigma_variance), float(self.sigma_normal), float("inf") if self.sigma_plane is None else float(self.sigma_plane), float(self.epsilon), float(self.spatial_scale))
@@ -526,10 +531,7 @@ def blend_moments(film, params, tile_dim=16, samples=None, moments=None, ctx=Non
     """yk_moments_blend: the luminance of the film blend_history folds into the history, folded into the (reprojected)
     (h, w) abi.MOMENTS_DTYPE moments (or None) -> the new moments.  `params` is blend_history's TemporalParams.  ctx None =
     the host instance."""
-    film = np.ascontiguousarray(film, dtype=np.float32)
-    if film.ndim != 3 or film.shape[2] != 3:
-        raise ValueError("film is (h, w, 3)")
-    h, w = film.shape[0], film.shape[1]
+    film, w, h = _film(film)
     d = _temporal_desc(params)
     samples = _blend_samples((w, h), tile_dim, samples)
     if moments is not None:
@@ -544,10 +546,7 @@ def variance(moments, film, guides, params, tile_dim=16, samples=None, ctx=None,
     """yk_variance: the (h, w) float32 variance of the luminance of `film` as denoise(..., variance=) will filter it: from
     the moments (or None) where they hold two frames or more, from the 7 x 7 neighbourhood everywhere else.  With albedo:
     the variance of the demodulated film.  ctx None = the host instance."""
-    film = np.ascontiguousarray(film, dtype=np.float32)
-    if film.ndim != 3 or film.shape[2] != 3:
-        raise ValueError("film is (h, w, 3)")
-    h, w = film.shape[0], film.shape[1]
+    film, w, h = _film(film)
     d = _variance_desc(params)
     samples = _blend_samples((w, h), tile_dim, samples)
     guides = _records(guides, abi.GUIDE_DTYPE, (w, h), "guide")
@@ -762,13 +761,11 @@ def present(film, window, encode=2, fmt="rgba8", ctx=None):
     tone-mapped film stretched into a window (W, H) with bilinear filtering inside a letterbox.  encode 0 none, 1 the
     shader's linearToSRGB, 2 an sRGB back buffer (the reference's default).  Returns (H, W, 4) uint8 for fmt "rgba8",
     (H, W, 3) float32 (the values before quantisation) for "rgb32f".  ctx None = the host instance."""
-    film = np.ascontiguousarray(film, dtype=np.float32)
-    if film.ndim != 3 or film.shape[2] != 3:
-        raise ValueError("film is (h, w, 3)")
+    film, w, h = _film(film)
     d = _present_desc(window, encode, fmt)
     out = np.empty((d.window_y, d.window_x, 4), dtype=np.uint8) if d.format == abi.PRESENT_RGBA8 else np.empty((d.window_y, d.window_x, 3), dtype=np.float32)
     c = ctx.h if ctx else None
-    check(lib().yk_present(c, C.byref(d), _p(film), film.shape[1], film.shape[0], _p(out)), c)
+    check(lib().yk_present(c, C.byref(d), _p(film), w, h, _p(out)), c)
     return out
 
 
@@ -816,9 +813,9 @@ class TileList:
         if n_passes != 1:
             if not accumulate:
                 raise ValueError("several passes only make sense for the accumulating film")
-            check(lib().yk_film_accumulate_tile_list_passes_device(c.h, self.h, C.c_void_p(d_tile_rgb_ptr), n_passes, res[0], res[1], C.c_void_p(d_film_ptr), C.c_void_p(stream) if stream else None), c.h)
+            check(lib().yk_film_accumulate_tile_list_passes_device(c.h, self.h, C.c_void_p(d_tile_rgb_ptr), n_passes, res[0], res[1], C.c_void_p(d_film_ptr), _vp(stream)), c.h)
             return
-        check(lib().yk_film_update_tile_list_device(c.h, self.h, C.c_void_p(d_tile_rgb_ptr), res[0], res[1], C.c_void_p(d_film_ptr), C.c_void_p(stream) if stream else None, 1 if accumulate else 0), c.h)
+        check(lib().yk_film_update_tile_list_device(c.h, self.h, C.c_void_p(d_tile_rgb_ptr), res[0], res[1], C.c_void_p(d_film_ptr), _vp(stream), 1 if accumulate else 0), c.h)
 
     def close(self):
         if getattr(self, "h", None):
@@ -975,14 +972,14 @@ class Context:
         """yk_tone_map_device: device film -> device out, enqueued on `stream` (default: the context's) without waiting;
         `samples` is a host table (or None), copied before the call returns."""
         samples = _tone_map_args(res, tone_map, tile_dim, samples)
-        check(lib().yk_tone_map_device(self.h, C.byref(tone_map), C.c_void_p(d_film_ptr), res[0], res[1], int(tile_dim), _p(samples), C.c_void_p(d_out_ptr), C.c_void_p(stream) if stream else None), self.h)
+        check(lib().yk_tone_map_device(self.h, C.byref(tone_map), _vp(d_film_ptr), res[0], res[1], int(tile_dim), _p(samples), _vp(d_out_ptr), _vp(stream)), self.h)
 
     def draw_overlay_device(self, d_film_ptr, res, world_to_clip, d_lines_ptr=None, n_lines=0, d_boxes_ptr=None, n_boxes=0, stream=None):
         """yk_overlay_draw_device: n_lines yk_overlay_line records and n_boxes boxes of six floats, both on the device,
         drawn in place into the device film; enqueued on `stream` (default: the context's) without waiting."""
         m = np.ascontiguousarray(world_to_clip, dtype=np.float32).reshape(16)
         check(
-            lib().yk_overlay_draw_device(self.h, _p(m), C.c_void_p(d_lines_ptr) if d_lines_ptr else None, int(n_lines), C.c_void_p(d_boxes_ptr) if d_boxes_ptr else None, int(n_boxes), C.c_void_p(d_film_ptr), res[0], res[1], C.c_void_p(stream) if stream else None),
+            lib().yk_overlay_draw_device(self.h, _p(m), _vp(d_lines_ptr), int(n_lines), _vp(d_boxes_ptr), int(n_boxes), _vp(d_film_ptr), res[0], res[1], _vp(stream)),
             self.h,
         )
 
@@ -991,69 +988,62 @@ class Context:
         a pixel, "rgb32f": three floats), enqueued on `stream` (default: the context's) without waiting; one kernel, no
         allocation.  Both pointers need 4-byte alignment."""
         d = _present_desc(window, encode, fmt)
-        check(lib().yk_present_device(self.h, C.byref(d), C.c_void_p(d_film_ptr), int(res[0]), int(res[1]), C.c_void_p(d_out_ptr), C.c_void_p(stream) if stream else None), self.h)
+        check(lib().yk_present_device(self.h, C.byref(d), _vp(d_film_ptr), int(res[0]), int(res[1]), _vp(d_out_ptr), _vp(stream)), self.h)
 
     def render_guides_device(self, scene, camera, res, d_guides_ptr, stream=None):
         """yk_render_guides_device: res[0] * res[1] yk_guide records (32 bytes each, 16-byte aligned) into device memory,
         ordered on `stream` (default: the context's) without waiting on the host."""
-        check(lib().yk_render_guides_device(self.h, scene.h, C.byref(camera.matrices), int(res[0]), int(res[1]), C.c_void_p(d_guides_ptr), C.c_void_p(stream) if stream else None), self.h)
+        check(lib().yk_render_guides_device(self.h, scene.h, C.byref(camera.matrices), int(res[0]), int(res[1]), _vp(d_guides_ptr), _vp(stream)), self.h)
 
     def denoise_device(self, d_film_ptr, d_guides_ptr, res, params, tile_dim, samples, d_out_ptr, stream=None, albedo=None):
         """yk_denoise_device: device film + device guides -> device out (may be the film), enqueued on `stream` (default:
         the context's) without waiting; `samples` is a host table (or None), copied before the call returns."""
         d, _, samples = _denoise_args(res, params, None, tile_dim, samples)
         if albedo is not None:  # the device pointer of surface_albedo_device's records: yk_denoise_albedo_device
-            check(lib().yk_denoise_albedo_device(self.h, C.byref(d), C.c_void_p(d_film_ptr), C.c_void_p(d_guides_ptr), C.c_void_p(albedo), int(res[0]), int(res[1]), int(tile_dim), _p(samples), C.c_void_p(d_out_ptr), C.c_void_p(stream) if stream else None), self.h)
+            check(lib().yk_denoise_albedo_device(self.h, C.byref(d), _vp(d_film_ptr), _vp(d_guides_ptr), _vp(albedo), int(res[0]), int(res[1]), int(tile_dim), _p(samples), _vp(d_out_ptr), _vp(stream)), self.h)
             return
-        check(lib().yk_denoise_device(self.h, C.byref(d), C.c_void_p(d_film_ptr), C.c_void_p(d_guides_ptr), int(res[0]), int(res[1]), int(tile_dim), _p(samples), C.c_void_p(d_out_ptr), C.c_void_p(stream) if stream else None), self.h)
+        check(lib().yk_denoise_device(self.h, C.byref(d), _vp(d_film_ptr), _vp(d_guides_ptr), int(res[0]), int(res[1]), int(tile_dim), _p(samples), _vp(d_out_ptr), _vp(stream)), self.h)
 
     def reproject_history_device(self, d_prev_history_ptr, d_prev_guides_ptr, prev_camera, d_guides_ptr, res, params, d_out_history_ptr, stream=None):
         """yk_history_reproject_device: the previous view's device history and guides, its Camera and the current view's
         device guides -> the device history of the current view (all 16-byte aligned), enqueued on `stream` (default: the
         context's) without waiting."""
         d = _temporal_desc(params)
-        vp = C.c_void_p
-        check(lib().yk_history_reproject_device(self.h, C.byref(d), vp(d_prev_history_ptr), vp(d_prev_guides_ptr), C.byref(prev_camera.matrices), vp(d_guides_ptr), int(res[0]), int(res[1]), vp(d_out_history_ptr), vp(stream) if stream else None), self.h)
+        check(lib().yk_history_reproject_device(self.h, C.byref(d), _vp(d_prev_history_ptr), _vp(d_prev_guides_ptr), C.byref(prev_camera.matrices), _vp(d_guides_ptr), int(res[0]), int(res[1]), _vp(d_out_history_ptr), _vp(stream)), self.h)
 
     def render_guides_ids_device(self, scene, camera, res, d_guides_ptr, d_ids_ptr, stream=None):
         """yk_render_guides_ids_device: render_guides_device with res[0] * res[1] yk_surface_id records (16 bytes each,
         16-byte aligned) beside the guides, from the same trace; either pointer may be None, not both."""
-        vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
-        check(lib().yk_render_guides_ids_device(self.h, scene.h, C.byref(camera.matrices), int(res[0]), int(res[1]), vp(d_guides_ptr), vp(d_ids_ptr), vp(stream)), self.h)
+        check(lib().yk_render_guides_ids_device(self.h, scene.h, C.byref(camera.matrices), int(res[0]), int(res[1]), _vp(d_guides_ptr), _vp(d_ids_ptr), _vp(stream)), self.h)
 
     def surface_motion_device(self, scene, d_ids_ptr, d_guides_ptr, d_prev_points_ptr, res, d_out_ptr, stream=None):
         """yk_surface_motion_device: device ids and guides of the current geometry and the PREVIOUS vertex array on the device
         (3 floats for each of the scene's vertices: the caller answers for its length) -> res[0] * res[1] device yk_motion
         records, enqueued on `stream` (default: the context's) without waiting; one launch, no allocation."""
-        vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
-        check(lib().yk_surface_motion_device(self.h, scene.h, vp(d_ids_ptr), vp(d_guides_ptr), vp(d_prev_points_ptr), int(res[0]), int(res[1]), vp(d_out_ptr), vp(stream)), self.h)
+        check(lib().yk_surface_motion_device(self.h, scene.h, _vp(d_ids_ptr), _vp(d_guides_ptr), _vp(d_prev_points_ptr), int(res[0]), int(res[1]), _vp(d_out_ptr), _vp(stream)), self.h)
 
     def surface_albedo_device(self, scene, d_ids_ptr, res, d_out_ptr, stream=None):
         """yk_surface_albedo_device: device ids -> res[0] * res[1] device yk_albedo records (both 16-byte aligned), enqueued
         on `stream` (default: the context's) without waiting."""
-        vp = C.c_void_p
-        check(lib().yk_surface_albedo_device(self.h, scene.h, vp(d_ids_ptr), int(res[0]), int(res[1]), vp(d_out_ptr), vp(stream)), self.h)
+        check(lib().yk_surface_albedo_device(self.h, scene.h, _vp(d_ids_ptr), int(res[0]), int(res[1]), _vp(d_out_ptr), _vp(stream)), self.h)
 
     def albedo_mean_device(self, scene, d_ids_ss_ptr, res, s, d_out_ptr, stream=None):
         """yk_albedo_mean_device: the device ids of the (s * res[0]) x (s * res[1]) film -> res[0] * res[1] device yk_albedo
         records (both 16-byte aligned), enqueued on `stream` (default: the context's) without waiting; one launch, no
         allocation."""
-        vp = C.c_void_p
-        check(lib().yk_albedo_mean_device(self.h, scene.h, vp(d_ids_ss_ptr), int(res[0]), int(res[1]), int(s), vp(d_out_ptr), vp(stream)), self.h)
+        check(lib().yk_albedo_mean_device(self.h, scene.h, _vp(d_ids_ss_ptr), int(res[0]), int(res[1]), int(s), _vp(d_out_ptr), _vp(stream)), self.h)
 
     def render_albedo_mean_device(self, scene, camera_ss, res, s, d_out_ptr, stream=None):
         """yk_render_albedo_mean_device: the pixel-mean albedo of the film `res` into res[0] * res[1] device yk_albedo records
         (16-byte aligned), ordered on `stream` (default: the context's) without waiting on the host.  `camera_ss` is the
         Camera of the s-times larger film (Camera(params, supersampled(film_settings, s)))."""
-        vp = C.c_void_p
-        check(lib().yk_render_albedo_mean_device(self.h, scene.h, C.byref(camera_ss.matrices), int(res[0]), int(res[1]), int(s), vp(d_out_ptr), vp(stream)), self.h)
+        check(lib().yk_render_albedo_mean_device(self.h, scene.h, C.byref(camera_ss.matrices), int(res[0]), int(res[1]), int(s), _vp(d_out_ptr), _vp(stream)), self.h)
 
     def reproject_history_moved_device(self, d_prev_history_ptr, d_prev_guides_ptr, prev_camera, d_guides_ptr, d_motion_ptr, res, params, d_out_history_ptr, stream=None):
         """yk_history_reproject_moved_device: reproject_history_device through the device motion records of
         surface_motion_device (all 16-byte aligned), enqueued on `stream` (default: the context's) without waiting."""
         d = _temporal_desc(params)
-        vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
-        check(lib().yk_history_reproject_moved_device(self.h, C.byref(d), vp(d_prev_history_ptr), vp(d_prev_guides_ptr), C.byref(prev_camera.matrices), vp(d_guides_ptr), vp(d_motion_ptr), int(res[0]), int(res[1]), vp(d_out_history_ptr), vp(stream)), self.h)
+        check(lib().yk_history_reproject_moved_device(self.h, C.byref(d), _vp(d_prev_history_ptr), _vp(d_prev_guides_ptr), C.byref(prev_camera.matrices), _vp(d_guides_ptr), _vp(d_motion_ptr), int(res[0]), int(res[1]), _vp(d_out_history_ptr), _vp(stream)), self.h)
 
     def blend_history_device(self, d_film_ptr, res, params, tile_dim, samples, d_history_ptr, d_out_history_ptr, d_out_rgb_ptr, stream=None):
         """yk_history_blend_device: device film + device history (or None) -> device history and / or device RGB (None = not
@@ -1061,54 +1051,47 @@ class Context:
         table (or None), copied before the call returns."""
         d = _temporal_desc(params)
         samples = _blend_samples(res, tile_dim, samples)
-        vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
-        check(lib().yk_history_blend_device(self.h, C.byref(d), vp(d_film_ptr), int(res[0]), int(res[1]), int(tile_dim), _p(samples), vp(d_history_ptr), vp(d_out_history_ptr), vp(d_out_rgb_ptr), vp(stream)), self.h)
+        check(lib().yk_history_blend_device(self.h, C.byref(d), _vp(d_film_ptr), int(res[0]), int(res[1]), int(tile_dim), _p(samples), _vp(d_history_ptr), _vp(d_out_history_ptr), _vp(d_out_rgb_ptr), _vp(stream)), self.h)
 
     def blend_moments_device(self, d_film_ptr, res, params, tile_dim, samples, d_moments_ptr, d_out_moments_ptr, stream=None):
         """yk_moments_blend_device: device film + device moments (or None) -> device moments (may be the input), enqueued on
         `stream` (default: the context's) without waiting; `params` is blend_history_device's TemporalParams."""
         d = _temporal_desc(params)
         samples = _blend_samples(res, tile_dim, samples)
-        vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
-        check(lib().yk_moments_blend_device(self.h, C.byref(d), vp(d_film_ptr), int(res[0]), int(res[1]), int(tile_dim), _p(samples), vp(d_moments_ptr), vp(d_out_moments_ptr), vp(stream)), self.h)
+        check(lib().yk_moments_blend_device(self.h, C.byref(d), _vp(d_film_ptr), int(res[0]), int(res[1]), int(tile_dim), _p(samples), _vp(d_moments_ptr), _vp(d_out_moments_ptr), _vp(stream)), self.h)
 
     def variance_device(self, d_moments_ptr, d_film_ptr, d_guides_ptr, res, params, tile_dim, samples, d_out_ptr, stream=None, albedo=None):
         """yk_variance_device: device moments (or None), film, guides and albedo (or None) -> res[0] * res[1] device floats,
         enqueued on `stream` (default: the context's) without waiting; one launch."""
         d = _variance_desc(params)
         samples = _blend_samples(res, tile_dim, samples)
-        vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
-        check(lib().yk_variance_device(self.h, C.byref(d), vp(d_moments_ptr), vp(d_film_ptr), vp(d_guides_ptr), vp(albedo), int(res[0]), int(res[1]), int(tile_dim), _p(samples), vp(d_out_ptr), vp(stream)), self.h)
+        check(lib().yk_variance_device(self.h, C.byref(d), _vp(d_moments_ptr), _vp(d_film_ptr), _vp(d_guides_ptr), _vp(albedo), int(res[0]), int(res[1]), int(tile_dim), _p(samples), _vp(d_out_ptr), _vp(stream)), self.h)
 
     def denoise_variance_device(self, d_film_ptr, d_guides_ptr, d_variance_ptr, res, params, tile_dim, samples, d_out_ptr, stream=None, albedo=None):
         """yk_denoise_variance_device: denoise_device with the device variance image of variance_device and a
         VarianceParams; d_out_ptr may be the film."""
         d = _variance_desc(params)
         samples = _blend_samples(res, tile_dim, samples)
-        vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
-        check(lib().yk_denoise_variance_device(self.h, C.byref(d), vp(d_film_ptr), vp(d_guides_ptr), vp(d_variance_ptr), vp(albedo), int(res[0]), int(res[1]), int(tile_dim), _p(samples), vp(d_out_ptr), vp(stream)), self.h)
+        check(lib().yk_denoise_variance_device(self.h, C.byref(d), _vp(d_film_ptr), _vp(d_guides_ptr), _vp(d_variance_ptr), _vp(albedo), int(res[0]), int(res[1]), int(tile_dim), _p(samples), _vp(d_out_ptr), _vp(stream)), self.h)
 
     def adaptive_select_device(self, d_stats_ptr, res, params, pixel_list, stream=None):
         """yk_adaptive_select_device: device statistics -> `pixel_list` (a PixelList of the same resolution); returns the
         number selected.  Three launches on `stream` (default: the context's), then the count is read back: it waits."""
         d = _adaptive_desc(params)
         n = C.c_uint32(0)
-        vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
-        check(lib().yk_adaptive_select_device(self.h, C.byref(d), vp(d_stats_ptr), int(res[0]), int(res[1]), pixel_list.h, C.byref(n), vp(stream)), self.h)
+        check(lib().yk_adaptive_select_device(self.h, C.byref(d), _vp(d_stats_ptr), int(res[0]), int(res[1]), pixel_list.h, C.byref(n), _vp(stream)), self.h)
         pixel_list.n = n.value
         return n.value
 
     def adaptive_accumulate_device(self, pixel_list, d_passes_ptr, n_passes, res, d_film_sum_ptr, d_stats_ptr, stream=None):
         """yk_adaptive_accumulate_device: the (n_passes, n, 3) device passes of `pixel_list` folded into the device film sums
         and statistics, one launch on `stream` (default: the context's) without waiting."""
-        vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
-        check(lib().yk_adaptive_accumulate_device(self.h, pixel_list.h, vp(d_passes_ptr), int(n_passes), int(res[0]), int(res[1]), vp(d_film_sum_ptr), vp(d_stats_ptr), vp(stream)), self.h)
+        check(lib().yk_adaptive_accumulate_device(self.h, pixel_list.h, _vp(d_passes_ptr), int(n_passes), int(res[0]), int(res[1]), _vp(d_film_sum_ptr), _vp(d_stats_ptr), _vp(stream)), self.h)
 
     def adaptive_resolve_device(self, d_film_sum_ptr, d_stats_ptr, res, d_out_rgb_ptr, d_out_variance_ptr, stream=None):
         """yk_adaptive_resolve_device: device film sums and statistics -> the device mean film and / or the variance of the
         mean (None = not wanted), one launch on `stream` (default: the context's) without waiting."""
-        vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
-        check(lib().yk_adaptive_resolve_device(self.h, vp(d_film_sum_ptr), vp(d_stats_ptr), int(res[0]), int(res[1]), vp(d_out_rgb_ptr), vp(d_out_variance_ptr), vp(stream)), self.h)
+        check(lib().yk_adaptive_resolve_device(self.h, _vp(d_film_sum_ptr), _vp(d_stats_ptr), int(res[0]), int(res[1]), _vp(d_out_rgb_ptr), _vp(d_out_variance_ptr), _vp(stream)), self.h)
 
     @property
     def stream_handle(self):
@@ -1212,7 +1195,7 @@ class Scene:
             setattr(d, name, C.cast(C.c_void_p(address[name]), ptype))
         self.n_lights = int(d.n_lights)
         h = C.c_void_p()
-        check(lib().yk_scene_create_device(ctx.h, C.byref(d), C.c_void_p(stream) if stream else None, C.byref(h)), ctx.h)
+        check(lib().yk_scene_create_device(ctx.h, C.byref(d), _vp(stream), C.byref(h)), ctx.h)
         self.h = h
         del keep
         return self
@@ -1281,8 +1264,7 @@ class Scene:
         if self.ctx is None:
             raise ValueError("a host-only scene is updated with numpy arrays")
         address, stream = _device_addresses(given, {name: (("float32",), 3 * nv) for name in given}, self.ctx, stream)
-        vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
-        check(lib().yk_scene_update_device(self.ctx.h, self.h, vp(address["points"]), vp(address["normals"]), vp(stream)), self.ctx.h)
+        check(lib().yk_scene_update_device(self.ctx.h, self.h, _vp(address["points"]), _vp(address["normals"]), _vp(stream)), self.ctx.h)
 
     def update_info(self):
         """yk_scene_get_update_info: how many updates ran, the last one's route (abi.UPDATE_ROUTE_*) and reason
@@ -1505,7 +1487,7 @@ class Dist:
         self.h, self.rank, self.world = h, rank, world
 
     def gather(self, d_send_ptr, d_recv_ptr, count_floats, stream=None):
-        check(lib().yk_dist_gather(self.h, C.c_void_p(d_send_ptr), C.c_void_p(d_recv_ptr) if d_recv_ptr else None, count_floats, C.c_void_p(stream) if stream else None), self.ctx.h)
+        check(lib().yk_dist_gather(self.h, C.c_void_p(d_send_ptr), _vp(d_recv_ptr), count_floats, _vp(stream)), self.ctx.h)
 
     def close(self):
         if getattr(self, "h", None):
@@ -1636,7 +1618,7 @@ class Integrator:
         tiles = np.ascontiguousarray(tiles, dtype=abi.TILE_DTYPE)
         stats = RenderStats()
         check(
-            lib().yk_render_tiles_device(self.ctx.h, scene.h, C.byref(camera.matrices), C.byref(sampler), C.byref(self.desc), _p(tiles), len(tiles), C.c_void_p(d_out_ptr), C.c_void_p(stream) if stream else None, C.byref(stats) if want_stats else None, None, None),
+            lib().yk_render_tiles_device(self.ctx.h, scene.h, C.byref(camera.matrices), C.byref(sampler), C.byref(self.desc), _p(tiles), len(tiles), C.c_void_p(d_out_ptr), _vp(stream), C.byref(stats) if want_stats else None, None, None),
             self.ctx.h,
         )
         return stats
@@ -1647,7 +1629,7 @@ class Integrator:
         stats = RenderStats()
         cb = _ffi.CANCEL_FN(lambda _u: 1 if cancel() else 0) if cancel else None
         check(
-            lib().yk_render_tile_list_samples_device(self.ctx.h, scene.h, C.byref(camera.matrices), C.byref(sampler), C.byref(self.desc), tile_list.h, int(first_sample), int(n_passes), C.c_void_p(d_out_ptr), C.c_void_p(stream) if stream else None, C.byref(stats) if want_stats else None, C.cast(cb, C.c_void_p) if cb else None, None),
+            lib().yk_render_tile_list_samples_device(self.ctx.h, scene.h, C.byref(camera.matrices), C.byref(sampler), C.byref(self.desc), tile_list.h, int(first_sample), int(n_passes), C.c_void_p(d_out_ptr), _vp(stream), C.byref(stats) if want_stats else None, C.cast(cb, C.c_void_p) if cb else None, None),
             self.ctx.h,
         )
         return stats if want_stats else None
@@ -1659,12 +1641,12 @@ class Integrator:
         stats = RenderStats()
         if n_passes != 1:
             check(
-                lib().yk_render_tile_list_passes_device(self.ctx.h, scene.h, C.byref(camera.matrices), C.byref(sampler), C.byref(self.desc), tile_list.h, n_passes, C.c_void_p(d_out_ptr), C.c_void_p(stream) if stream else None, C.byref(stats) if want_stats else None, None, None),
+                lib().yk_render_tile_list_passes_device(self.ctx.h, scene.h, C.byref(camera.matrices), C.byref(sampler), C.byref(self.desc), tile_list.h, n_passes, C.c_void_p(d_out_ptr), _vp(stream), C.byref(stats) if want_stats else None, None, None),
                 self.ctx.h,
             )
             return stats if want_stats else None
         check(
-            lib().yk_render_tile_list_device(self.ctx.h, scene.h, C.byref(camera.matrices), C.byref(sampler), C.byref(self.desc), tile_list.h, C.c_void_p(d_out_ptr), C.c_void_p(stream) if stream else None, C.byref(stats) if want_stats else None, None, None),
+            lib().yk_render_tile_list_device(self.ctx.h, scene.h, C.byref(camera.matrices), C.byref(sampler), C.byref(self.desc), tile_list.h, C.c_void_p(d_out_ptr), _vp(stream), C.byref(stats) if want_stats else None, None, None),
             self.ctx.h,
         )
         return stats if want_stats else None
@@ -1676,7 +1658,7 @@ class Integrator:
         stats = RenderStats()
         cb = _ffi.CANCEL_FN(lambda _u: 1 if cancel() else 0) if cancel else None
         check(
-            lib().yk_render_pixel_list_device(self.ctx.h, scene.h, C.byref(camera.matrices), C.byref(sampler), C.byref(self.desc), pixel_list.h, int(n_passes), C.c_void_p(d_out_ptr) if d_out_ptr else None, C.c_void_p(stream) if stream else None, C.byref(stats) if want_stats else None, C.cast(cb, C.c_void_p) if cb else None, None),
+            lib().yk_render_pixel_list_device(self.ctx.h, scene.h, C.byref(camera.matrices), C.byref(sampler), C.byref(self.desc), pixel_list.h, int(n_passes), _vp(d_out_ptr), _vp(stream), C.byref(stats) if want_stats else None, C.cast(cb, C.c_void_p) if cb else None, None),
             self.ctx.h,
         )
         return stats if want_stats else None
@@ -1697,9 +1679,8 @@ class Integrator:
         d = _adaptive_desc(params)
         info = abi.AdaptiveInfo()
         cb = _ffi.CANCEL_FN(lambda _u: 1 if cancel() else 0) if cancel else None
-        vp = lambda a: C.c_void_p(a) if a else None  # noqa: E731
         check(
-            lib().yk_render_adaptive_device(self.ctx.h, scene.h, C.byref(camera.matrices), C.byref(sampler), C.byref(self.desc), C.byref(d), w, h, vp(address["film_sum"]), vp(address["stats"]), vp(stream), C.byref(info), C.cast(cb, C.c_void_p) if cb else None, None),
+            lib().yk_render_adaptive_device(self.ctx.h, scene.h, C.byref(camera.matrices), C.byref(sampler), C.byref(self.desc), C.byref(d), w, h, _vp(address["film_sum"]), _vp(address["stats"]), _vp(stream), C.byref(info), C.cast(cb, C.c_void_p) if cb else None, None),
             self.ctx.h,
         )
         return film_sum, stats, info

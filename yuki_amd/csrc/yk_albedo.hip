@@ -3,7 +3,7 @@
 // yk_albedo.h's, whose host instances these entry points run without a context.  (The demodulated denoise that reads the
 // records is in yk_denoise.hip, next to the filter it wraps.)
 //
-// k_albedo: one lane per pixel, a block is an AL_TX x AL_TY tile of the film (k_motion's launch shape: neighbouring lanes
+// k_albedo: one lane per pixel, a block is a 32 x 8 tile of the film (yk_film_tile.h: neighbouring lanes
 //   hit neighbouring triangles and, on a textured surface, neighbouring texels, so their requests share cache lines).  A
 //   lane reads its id (one 16-byte load) and follows a four-hop gather: the shape's material index, mesh and three vertex
 //   indices; the material (five dwords of its 44-byte record), the mesh flags and six uv floats; the texture's info (one
@@ -17,14 +17,13 @@
 
 #include "yk_albedo.h"
 #include "yk_film_call.h"
+#include "yk_film_tile.h"
 #include "yk_staging.h"
 
 namespace {
 
-constexpr unsigned AL_TX = 32, AL_TY = 8;  // 256 lanes: 4 waves of 64
-
-__global__ __launch_bounds__(AL_TX* AL_TY) void k_albedo(const uint4* __restrict__ ids, DevScene sc, AlParams a, float4* __restrict__ out) {
-    const uint32_t x = blockIdx.x * AL_TX + threadIdx.x, y = blockIdx.y * AL_TY + threadIdx.y;
+__global__ __launch_bounds__(FT_TX* FT_TY) void k_albedo(const uint4* __restrict__ ids, DevScene sc, AlParams a, float4* __restrict__ out) {
+    const uint32_t x = blockIdx.x * FT_TX + threadIdx.x, y = blockIdx.y * FT_TY + threadIdx.y;
     if (x >= a.res_x || y >= a.res_y) return;
     const size_t i = (size_t)y * a.res_x + x;
     const uint4 id = ids[i];
@@ -34,13 +33,13 @@ __global__ __launch_bounds__(AL_TX* AL_TY) void k_albedo(const uint4* __restrict
 }
 
 // k_albedo_mean (yk_albedo_mean[_device], and every band of yk_render_albedo_mean): one lane per OUTPUT pixel, the same
-//   AL_TX x AL_TY tile.  A lane walks its s x s block of the large film's ids row by row (j outer, i inner: al_mean_pixel's
+//   32 x 8 tile.  A lane walks its s x s block of the large film's ids row by row (j outer, i inner: al_mean_pixel's
 //   summation order), each id a 16-byte load followed by al_pixel's clamped four-hop gather, and writes one 16-byte record.
 //   Lanes along x read ids 16*s bytes apart: a wave's 32 lanes of one row cover 512*s contiguous bytes per j, every byte
 //   of which some lane uses within the same inner loop, so each line is fetched from HBM once and served from L2 after.
 //   a.res_x x a.res_y is the output film (or one band of it); the ids have s*a.res_x records to a row.
-__global__ __launch_bounds__(AL_TX* AL_TY) void k_albedo_mean(const uint4* __restrict__ ids_ss, DevScene sc, AlParams a, uint32_t s, float4* __restrict__ out) {
-    const uint32_t x = blockIdx.x * AL_TX + threadIdx.x, y = blockIdx.y * AL_TY + threadIdx.y;
+__global__ __launch_bounds__(FT_TX* FT_TY) void k_albedo_mean(const uint4* __restrict__ ids_ss, DevScene sc, AlParams a, uint32_t s, float4* __restrict__ out) {
+    const uint32_t x = blockIdx.x * FT_TX + threadIdx.x, y = blockIdx.y * FT_TY + threadIdx.y;
     if (x >= a.res_x || y >= a.res_y) return;
     float rec[4];
     al_mean_pixel(a, sc, ids_ss, x, y, s, rec);
@@ -91,8 +90,7 @@ AlParams make_params(const yk_scene* scene, uint32_t res_x, uint32_t res_y) {
 
 yk_status enqueue(yk_context* ctx, hipStream_t st, const yk_scene* scene, const void* ids, uint16_t res_x, uint16_t res_y, void* out) {
     const AlParams a = make_params(scene, res_x, res_y);
-    const dim3 grid((res_x + AL_TX - 1) / AL_TX, (res_y + AL_TY - 1) / AL_TY), block(AL_TX, AL_TY);
-    hipLaunchKernelGGL(k_albedo, grid, block, 0, st, reinterpret_cast<const uint4*>(ids), scene->dev, a, reinterpret_cast<float4*>(out));
+    hipLaunchKernelGGL(k_albedo, ft_grid(res_x, res_y), ft_block(), 0, st, reinterpret_cast<const uint4*>(ids), scene->dev, a, reinterpret_cast<float4*>(out));
     HIP_TRY(ctx, hipGetLastError());
     return YK_OK;
 }
@@ -140,6 +138,21 @@ hipError_t fetch_tables(const yk_scene* s, yk_scene::ShadingTables& h) {
     return get(h.texels, s->texels);
 }
 
+// The host instances' view of a scene's shading tables, handed to use(const DevScene&): a host-only scene keeps its tables,
+// a scene in device memory has them fetched for the call.
+template <class Use>
+yk_status with_host_tables(yk_context* ctx, const yk_scene* scene, const Use& use) {
+    if (!scene->on_device) {
+        use(host_view(scene->host_shading, scene->upd.host_indices.data()));
+        return YK_OK;
+    }
+    yk_scene::ShadingTables fetched;
+    (void)hipSetDevice(scene->device);
+    HIP_TRY(ctx, fetch_tables(scene, fetched));
+    use(host_view(fetched, fetched.indices.data()));
+    return YK_OK;
+}
+
 void albedo_host(const yk_scene* scene, const DevScene& sc, const yk_surface_id* ids, uint16_t res_x, uint16_t res_y, yk_albedo* out) {
     const AlParams a = make_params(scene, res_x, res_y);
     const size_t n_px = (size_t)res_x * res_y;
@@ -179,8 +192,7 @@ void launch_ids_band(hipStream_t s, const DevScene& sc, PathBuffers cur, const i
 
 yk_status albedo_mean_enqueue(yk_context* ctx, hipStream_t st, const yk_scene* scene, const void* d_ids_ss, uint32_t res_x, uint32_t rows, uint32_t s, void* d_out) {
     const AlParams a = make_params(scene, res_x, rows);
-    const dim3 grid((res_x + AL_TX - 1) / AL_TX, (rows + AL_TY - 1) / AL_TY), block(AL_TX, AL_TY);
-    hipLaunchKernelGGL(k_albedo_mean, grid, block, 0, st, reinterpret_cast<const uint4*>(d_ids_ss), scene->dev, a, s, reinterpret_cast<float4*>(d_out));
+    hipLaunchKernelGGL(k_albedo_mean, ft_grid(res_x, rows), ft_block(), 0, st, reinterpret_cast<const uint4*>(d_ids_ss), scene->dev, a, s, reinterpret_cast<float4*>(d_out));
     HIP_TRY(ctx, hipGetLastError());
     return YK_OK;
 }
@@ -190,26 +202,13 @@ extern "C" {
 yk_status yk_surface_albedo(yk_context* ctx, const yk_scene* scene, const yk_surface_id* ids, uint16_t res_x, uint16_t res_y, yk_albedo* out) try {
     if (check_call(scene, ids, res_x, res_y, out) != YK_OK) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_surface_albedo: bad argument");
     const size_t n_px = (size_t)res_x * res_y;
-    if (!ctx) {  // the host instance
-        if (!scene->on_device) {  // a host-only scene keeps its tables
-            albedo_host(scene, host_view(scene->host_shading, scene->upd.host_indices.data()), ids, res_x, res_y, out);
-            return YK_OK;
-        }
-        yk_scene::ShadingTables fetched;  // a scene in device memory: its tables live there
-        (void)hipSetDevice(scene->device);
-        HIP_TRY(ctx, fetch_tables(scene, fetched));
-        albedo_host(scene, host_view(fetched, fetched.indices.data()), ids, res_x, res_y, out);
-        return YK_OK;
-    }
+    if (!ctx) return with_host_tables(ctx, scene, [&](const DevScene& sc) { albedo_host(scene, sc, ids, res_x, res_y, out); });  // the host instance
     YK_LOCK(ctx);
-    if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_surface_albedo: scene was not created on this context's device");
+    if (yk_status rs = scene_on_context(ctx, scene, "yk_surface_albedo")) return rs;
     Staging sg(ctx);
     const yk_surface_id* d_ids = sg.upload(ids, n_px);
     yk_albedo* d_out = sg.output(out, n_px);
-    if (!sg.ok()) return sg.status();
-    yk_status s = enqueue(ctx, sg.stream, scene, d_ids, res_x, res_y, d_out);
-    if (s != YK_OK) return s;
-    return sg.finish();
+    return sg.run([&] { return enqueue(ctx, sg.stream, scene, d_ids, res_x, res_y, d_out); });
 }
 YK_CATCH(ctx)
 
@@ -217,7 +216,7 @@ yk_status yk_surface_albedo_device(yk_context* ctx, const yk_scene* scene, const
     if (!ctx) return YK_ERR_INVALID_ARGUMENT;
     YK_LOCK(ctx);
     if (check_call(scene, d_ids, res_x, res_y, d_out) != YK_OK) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_surface_albedo_device: bad argument");
-    if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_surface_albedo_device: scene was not created on this context's device");
+    if (yk_status rs = scene_on_context(ctx, scene, "yk_surface_albedo_device")) return rs;
     if (misaligned(16, d_ids, d_out))  // 16-byte loads and stores of the records
         return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_surface_albedo_device: ids and output must be 16-byte aligned");
     return enqueue(ctx, device_call_stream(ctx, stream), scene, d_ids, res_x, res_y, d_out);
@@ -226,26 +225,13 @@ yk_status yk_surface_albedo_device(yk_context* ctx, const yk_scene* scene, const
 yk_status yk_albedo_mean(yk_context* ctx, const yk_scene* scene, const yk_surface_id* ids_ss, uint16_t res_x, uint16_t res_y, uint32_t s, yk_albedo* out) try {
     if (check_mean_call(scene, ids_ss, res_x, res_y, s, out) != YK_OK) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_albedo_mean: bad argument");
     const size_t n_px = (size_t)res_x * res_y;
-    if (!ctx) {  // the host instance, its tables as yk_surface_albedo's
-        if (!scene->on_device) {
-            albedo_mean_host(scene, host_view(scene->host_shading, scene->upd.host_indices.data()), ids_ss, res_x, res_y, s, out);
-            return YK_OK;
-        }
-        yk_scene::ShadingTables fetched;
-        (void)hipSetDevice(scene->device);
-        HIP_TRY(ctx, fetch_tables(scene, fetched));
-        albedo_mean_host(scene, host_view(fetched, fetched.indices.data()), ids_ss, res_x, res_y, s, out);
-        return YK_OK;
-    }
+    if (!ctx) return with_host_tables(ctx, scene, [&](const DevScene& sc) { albedo_mean_host(scene, sc, ids_ss, res_x, res_y, s, out); });  // the host instance
     YK_LOCK(ctx);
-    if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_albedo_mean: scene was not created on this context's device");
+    if (yk_status rs = scene_on_context(ctx, scene, "yk_albedo_mean")) return rs;
     Staging sg(ctx);
     const yk_surface_id* d_ids = sg.upload(ids_ss, n_px * s * s);
     yk_albedo* d_out = sg.output(out, n_px);
-    if (!sg.ok()) return sg.status();
-    yk_status rc = albedo_mean_enqueue(ctx, sg.stream, scene, d_ids, res_x, res_y, s, d_out);
-    if (rc != YK_OK) return rc;
-    return sg.finish();
+    return sg.run([&] { return albedo_mean_enqueue(ctx, sg.stream, scene, d_ids, res_x, res_y, s, d_out); });
 }
 YK_CATCH(ctx)
 
@@ -253,7 +239,7 @@ yk_status yk_albedo_mean_device(yk_context* ctx, const yk_scene* scene, const vo
     if (!ctx) return YK_ERR_INVALID_ARGUMENT;
     YK_LOCK(ctx);
     if (check_mean_call(scene, d_ids_ss, res_x, res_y, s, d_out) != YK_OK) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_albedo_mean_device: bad argument");
-    if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_albedo_mean_device: scene was not created on this context's device");
+    if (yk_status rs = scene_on_context(ctx, scene, "yk_albedo_mean_device")) return rs;
     if (misaligned(16, d_ids_ss, d_out)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_albedo_mean_device: ids and output must be 16-byte aligned");
     return albedo_mean_enqueue(ctx, device_call_stream(ctx, stream), scene, d_ids_ss, res_x, res_y, s, d_out);
 }

@@ -209,11 +209,7 @@ yk_status enqueue_atrous(yk_context* ctx, hipStream_t st, Rule r, uint32_t n_it,
     AtIo io{};
     io.film = film;
     io.guides = reinterpret_cast<const float4*>(guides);
-    if (samples) {
-        yk_status ss = stage_sample_table(ctx, st, samples, (uint16_t)a.res_x, (uint16_t)a.res_y, (uint16_t)a.tile_dim, dn.samples);
-        if (ss != YK_OK) return ss;
-        io.samples = dn.samples.as<const uint32_t>();
-    }
+    if (yk_status ss = stage_samples(ctx, st, samples, (uint16_t)a.res_x, (uint16_t)a.res_y, (uint16_t)a.tile_dim, dn.samples, &io.samples)) return ss;
     if (n_it == 0) {
         if (samples) {
             io.out_rgb = out;
@@ -351,10 +347,7 @@ static yk_status denoise_arrays(yk_context* ctx, const char* name, bool has_albe
     const yk_guide* d_guides = sg.upload(guides, n_px);
     const yk_albedo* d_albedo = albedo ? sg.upload(albedo, n_px) : nullptr;
     float* d_out = sg.output(out_rgb, n_px * 3);
-    if (!sg.ok()) return sg.status();
-    yk_status s = enqueue(ctx, sg.stream, desc, d_film, d_guides, d_albedo, res_x, res_y, tile_dim, samples, d_out);
-    if (s != YK_OK) return s;
-    return sg.finish();
+    return sg.run([&] { return enqueue(ctx, sg.stream, desc, d_film, d_guides, d_albedo, res_x, res_y, tile_dim, samples, d_out); });
 } YK_CATCH(ctx)
 
 static yk_status denoise_device(yk_context* ctx, const char* name, bool has_albedo, const yk_denoise_desc* desc, const void* d_film_rgb, const void* d_guides, const void* d_albedo,
@@ -408,10 +401,7 @@ yk_status yk_denoise_variance(yk_context* ctx, const yk_variance_desc* desc, con
     const float* d_variance = sg.upload(variance, n_px);
     const yk_albedo* d_albedo = albedo ? sg.upload(albedo, n_px) : nullptr;
     float* d_out = sg.output(out_rgb, n_px * 3);
-    if (!sg.ok()) return sg.status();
-    yk_status s = enqueue_variance_guided(ctx, sg.stream, desc, d_film, d_guides, d_variance, d_albedo, res_x, res_y, tile_dim, samples, d_out);
-    if (s != YK_OK) return s;
-    return sg.finish();
+    return sg.run([&] { return enqueue_variance_guided(ctx, sg.stream, desc, d_film, d_guides, d_variance, d_albedo, res_x, res_y, tile_dim, samples, d_out); });
 }
 YK_CATCH(ctx)
 

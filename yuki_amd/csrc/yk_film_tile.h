@@ -1,5 +1,7 @@
-// yk_film_tile.h — the block shape of the film filters (the à-trous kernel, k_variance) and the staging of a block's tile
-// plus a halo in LDS.  Device code, library-private.
+// yk_film_tile.h — the block shape of the film kernels that map a lane to a pixel of a 2-D tile, and the staging of a
+// block's tile plus a halo in LDS.  The shape: the à-trous kernel (yk_denoise.hip), k_variance (yk_variance.hip), k_reproject
+// (yk_temporal.hip), k_motion (yk_motion.hip), k_albedo and k_albedo_mean (yk_albedo.hip); the LDS tile: the first two.  Device
+// code, library-private.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -374,6 +374,14 @@ hipError_t enqueue_shape_bounds(hipStream_t st, const float* d_points, const uin
 // on `st`.  It goes through the context's pinned staging (tonemap.staging), so the upload is truly asynchronous; the staging
 // is rewritten only once the previous upload out of it has run.
 yk_status stage_sample_table(yk_context* ctx, hipStream_t st, const uint32_t* samples, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, DevBuf& dst);
+// The same for a table the call may leave out: *d_samples is the table in `dst`, or NULL when `samples` is.
+inline yk_status stage_samples(yk_context* ctx, hipStream_t st, const uint32_t* samples, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, DevBuf& dst, const uint32_t** d_samples) {
+    *d_samples = nullptr;
+    if (!samples) return YK_OK;
+    yk_status s = stage_sample_table(ctx, st, samples, res_x, res_y, tile_dim, dst);
+    if (s == YK_OK) *d_samples = dst.as<const uint32_t>();
+    return s;
+}
 
 // ------------------------------------------------------------------ yk_adaptive.hip
 // The selection (yk_adaptive.h) of device statistics of the list's resolution into `list`, on `st`; synchronises once to read

@@ -1,7 +1,7 @@
 // yk_motion.hip — previous positions on gfx950, behind yk_surface_motion[_device]; the per-pixel arithmetic is yk_motion.h's,
 // whose host instance these entry points run without a context.
 //
-// k_motion: one lane per pixel, a block is a MO_TX x MO_TY tile of the film (k_reproject's launch shape: neighbouring lanes
+// k_motion: one lane per pixel, a block is a 32 x 8 tile of the film (yk_film_tile.h: neighbouring lanes
 //   hit neighbouring triangles, so their index and vertex requests share cache lines).  A lane reads its id (one 16-byte
 //   load) and its guide (two 16-byte loads), then follows a two-hop gather: three dword index loads requested together,
 //   then nine dword vertex loads requested together (a vertex is 12 bytes at a 4-byte aligned address: no wider load is
@@ -13,12 +13,11 @@
 #include <vector>
 
 #include "yk_film_call.h"
+#include "yk_film_tile.h"
 #include "yk_motion.h"
 #include "yk_staging.h"
 
 namespace {
-
-constexpr unsigned MO_TX = 32, MO_TY = 8;  // 256 lanes: 4 waves of 64
 
 struct MoIo {
     const uint4* ids;         // one uint4 a pixel: (shape, bits of b0, b1, b2)
@@ -28,8 +27,8 @@ struct MoIo {
     float4* out;
 };
 
-__global__ __launch_bounds__(MO_TX* MO_TY) void k_motion(MoIo io, MoParams a) {
-    const uint32_t x = blockIdx.x * MO_TX + threadIdx.x, y = blockIdx.y * MO_TY + threadIdx.y;
+__global__ __launch_bounds__(FT_TX* FT_TY) void k_motion(MoIo io, MoParams a) {
+    const uint32_t x = blockIdx.x * FT_TX + threadIdx.x, y = blockIdx.y * FT_TY + threadIdx.y;
     if (x >= a.res_x || y >= a.res_y) return;
     const size_t i = (size_t)y * a.res_x + x;
     const uint4 id = io.ids[i];
@@ -63,8 +62,7 @@ MoParams make_params(const yk_scene* scene, uint16_t res_x, uint16_t res_y) {
 yk_status enqueue(yk_context* ctx, hipStream_t st, const yk_scene* scene, const void* ids, const void* guides, const float* prev_points, uint16_t res_x, uint16_t res_y, void* out) {
     const MoParams a = make_params(scene, res_x, res_y);
     MoIo io{reinterpret_cast<const uint4*>(ids), reinterpret_cast<const float4*>(guides), scene->dev.indices, prev_points, reinterpret_cast<float4*>(out)};
-    const dim3 grid((res_x + MO_TX - 1) / MO_TX, (res_y + MO_TY - 1) / MO_TY), block(MO_TX, MO_TY);
-    hipLaunchKernelGGL(k_motion, grid, block, 0, st, io, a);
+    hipLaunchKernelGGL(k_motion, ft_grid(res_x, res_y), ft_block(), 0, st, io, a);
     HIP_TRY(ctx, hipGetLastError());
     return YK_OK;
 }
@@ -104,16 +102,13 @@ yk_status yk_surface_motion(yk_context* ctx, const yk_scene* scene, const yk_sur
         return YK_OK;
     }
     YK_LOCK(ctx);
-    if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_surface_motion: scene was not created on this context's device");
+    if (yk_status rs = scene_on_context(ctx, scene, "yk_surface_motion")) return rs;
     Staging sg(ctx);
     const yk_surface_id* d_ids = sg.upload(ids, n_px);
     const yk_guide* d_guides = sg.upload(guides, n_px);
     const float* d_points = sg.upload(prev_points, (size_t)scene->upd.n_vertices * 3);
     yk_motion* d_out = sg.output(out, n_px);
-    if (!sg.ok()) return sg.status();
-    yk_status s = enqueue(ctx, sg.stream, scene, d_ids, d_guides, d_points, res_x, res_y, d_out);
-    if (s != YK_OK) return s;
-    return sg.finish();
+    return sg.run([&] { return enqueue(ctx, sg.stream, scene, d_ids, d_guides, d_points, res_x, res_y, d_out); });
 }
 YK_CATCH(ctx)
 
@@ -122,7 +117,7 @@ yk_status yk_surface_motion_device(yk_context* ctx, const yk_scene* scene, const
     if (!ctx) return YK_ERR_INVALID_ARGUMENT;
     YK_LOCK(ctx);
     if (check_call(scene, d_ids, d_guides, d_prev_points, res_x, res_y, d_out) != YK_OK) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_surface_motion_device: bad argument");
-    if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_surface_motion_device: scene was not created on this context's device");
+    if (yk_status rs = scene_on_context(ctx, scene, "yk_surface_motion_device")) return rs;
     // 16-byte loads and stores of the records and the guides, dword loads of the vertices
     if (misaligned(16, d_ids, d_guides, d_out) || misaligned(4, d_prev_points))
         return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_surface_motion_device: ids, guides and output must be 16-byte aligned, prev_points 4-byte aligned");

@@ -332,10 +332,7 @@ yk_status yk_overlay_draw(yk_context* ctx, const float world_to_clip[16], const 
     float* d_film = sg.inout(film_rgb, (size_t)res_x * res_y * 3);
     const yk_overlay_line* d_lines = sg.upload(lines, n_lines);
     const float* d_boxes = sg.upload(boxes, n_boxes * 6);
-    if (!sg.ok()) return sg.status();
-    yk_status s = enqueue(ctx, sg.stream, world_to_clip, reinterpret_cast<const float*>(d_lines), n_lines, d_boxes, n_boxes, d_film, res_x, res_y);
-    if (s != YK_OK) return s;
-    return sg.finish();
+    return sg.run([&] { return enqueue(ctx, sg.stream, world_to_clip, reinterpret_cast<const float*>(d_lines), n_lines, d_boxes, n_boxes, d_film, res_x, res_y); });
 } YK_CATCH(ctx)
 
 yk_status yk_overlay_draw_device(yk_context* ctx, const float world_to_clip[16], const void* d_lines, size_t n_lines, const void* d_boxes, size_t n_boxes,

@@ -117,10 +117,7 @@ yk_status yk_present(yk_context* ctx, const yk_present_desc* desc, const float* 
     Staging sg(ctx);
     const float* d_film = sg.upload(film_rgb, (size_t)res_x * res_y * 3);
     void* d_out = sg.output(reinterpret_cast<uint8_t*>(out), out_bytes(desc));
-    if (!sg.ok()) return sg.status();
-    yk_status s = enqueue(ctx, sg.stream, desc, d_film, res_x, res_y, d_out);
-    if (s != YK_OK) return s;
-    return sg.finish();
+    return sg.run([&] { return enqueue(ctx, sg.stream, desc, d_film, res_x, res_y, d_out); });
 } YK_CATCH(ctx)
 
 yk_status yk_present_device(yk_context* ctx, const yk_present_desc* desc, const void* d_film_rgb, uint16_t res_x, uint16_t res_y, void* d_out, void* stream) {

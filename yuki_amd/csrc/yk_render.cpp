@@ -400,7 +400,7 @@ struct Submission {
             if (!scene || !rq.camera || (!rq.d_out && !(rq.d_film_sum && rq.d_stats))) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null argument");
         } else if (!scene || !rq.camera || !tiles || n_tiles == 0 || (!rq.d_out && !(rq.guides_res_x && rq.d_ids)))
             return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null argument");
-        if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "scene was not created on this context's device");
+        if (yk_status rs = scene_on_context(ctx, scene, "")) return rs;
         yk_status rc = make_params(ctx, rq.sampler, rq.integrator, prm);
         if (rc != YK_OK) return rc;
         is_path = prm.integrator == YK_INTEGRATOR_PATH;
@@ -778,7 +778,7 @@ struct LiCall {
     yk_status check(bool arrays_given, const yk_sampler_desc* sampler, const yk_integrator_desc* integrator, const uint32_t* sample_index, const char* refuse_size,
                     const char* refuse_integrator) {
         if (!scene || !arrays_given || n == 0) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null argument");
-        if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "scene was not created on this context's device");
+        if (yk_status rs = scene_on_context(ctx, scene, "")) return rs;
         if (n > ((size_t)1 << 28)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "too many rays");
         if (refuse_size) return fail(ctx, YK_ERR_INVALID_ARGUMENT, refuse_size);
         yk_status ps = make_params(ctx, sampler, integrator, prm);
@@ -1077,10 +1077,7 @@ yk_status yk_render_guides(yk_context* ctx, const yk_scene* scene, const yk_came
     if (!scene || !camera || !out || res_x == 0 || res_y == 0) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_guides: bad argument");
     Staging sg(ctx);
     yk_guide* d_guides = sg.output(out, (size_t)res_x * res_y);
-    if (!sg.ok()) return sg.status();
-    yk_status st = render_guides(ctx, scene, camera, res_x, res_y, d_guides, nullptr);
-    if (st != YK_OK) return st;
-    return sg.finish();
+    return sg.run([&] { return render_guides(ctx, scene, camera, res_x, res_y, d_guides, nullptr); });
 }
 
 // The guides with the surface ids beside them (yk_motion.h): the same single trace, k_guides_ids instead of k_guides.
@@ -1103,10 +1100,7 @@ yk_status yk_render_guides_ids(yk_context* ctx, const yk_scene* scene, const yk_
     Staging sg(ctx);
     yk_guide* d_guides = sg.output(out_guides, n_px);  // either may be left out
     yk_surface_id* d_ids = sg.output(out_ids, n_px);
-    if (!sg.ok()) return sg.status();
-    yk_status st = render_guides(ctx, scene, camera, res_x, res_y, d_guides, nullptr, d_ids);
-    if (st != YK_OK) return st;
-    return sg.finish();
+    return sg.run([&] { return render_guides(ctx, scene, camera, res_x, res_y, d_guides, nullptr, d_ids); });
 }
 
 // The fused pixel-mean albedo (yk_albedo.h): the large film is traced in bands of output rows, so that it never exists as a
@@ -1159,7 +1153,7 @@ yk_status yk_render_albedo_mean_device(yk_context* ctx, const yk_scene* scene, c
     if (!ctx) return YK_ERR_INVALID_ARGUMENT;
     YK_LOCK(ctx);
     if (!albedo_mean_args_ok(scene, camera_ss, res_x, res_y, s, d_out)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_albedo_mean_device: bad argument");
-    if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_albedo_mean_device: scene was not created on this context's device");
+    if (yk_status rs = scene_on_context(ctx, scene, "yk_render_albedo_mean_device")) return rs;
     if (misaligned(16, d_out)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_albedo_mean_device: the output must be 16-byte aligned");
     return render_albedo_mean(ctx, scene, camera_ss, res_x, res_y, s, d_out, stream);
 }
@@ -1169,13 +1163,10 @@ yk_status yk_render_albedo_mean(yk_context* ctx, const yk_scene* scene, const yk
     if (!ctx) return YK_ERR_INVALID_ARGUMENT;
     YK_LOCK(ctx);
     if (!albedo_mean_args_ok(scene, camera_ss, res_x, res_y, s, out)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_albedo_mean: bad argument");
-    if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_albedo_mean: scene was not created on this context's device");
+    if (yk_status rs = scene_on_context(ctx, scene, "yk_render_albedo_mean")) return rs;
     Staging sg(ctx);
     yk_albedo* d_out = sg.output(out, (size_t)res_x * res_y);
-    if (!sg.ok()) return sg.status();
-    yk_status st = render_albedo_mean(ctx, scene, camera_ss, res_x, res_y, s, d_out, nullptr);
-    if (st != YK_OK) return st;
-    return sg.finish();
+    return sg.run([&] { return render_albedo_mean(ctx, scene, camera_ss, res_x, res_y, s, d_out, nullptr); });
 }
 YK_CATCH(ctx)
 

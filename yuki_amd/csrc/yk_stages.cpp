@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 
+#include "yk_film_call.h"
 #include "yk_internal.h"
 #include "yk_staging.h"
 
@@ -52,7 +53,7 @@ yk_status yk_trace_closest(yk_context* ctx, const yk_scene* scene, size_t n, con
     if (!ctx) return YK_ERR_INVALID_ARGUMENT;
     YK_LOCK(ctx);
     if (!scene || !ray_o || !ray_d || !out_shape || n == 0) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null argument");
-    if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "scene was not created on this context's device");
+    if (yk_status rs = scene_on_context(ctx, scene, "")) return rs;
     if (n > 0xFFFFFF00ull) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "too many rays");
     const bool want_stats = out_node_tests || out_node_hits || out_shape_tests;
     yk_status wb = check_stage_kernel(ctx, scene, true, t_max, out_t || out_bary || want_stats);
@@ -138,7 +139,7 @@ yk_status yk_trace_any(yk_context* ctx, const yk_scene* scene, size_t n, const f
     if (!ctx) return YK_ERR_INVALID_ARGUMENT;
     YK_LOCK(ctx);
     if (!scene || !ray_o || !ray_d || !t_max || !out_hit || n == 0) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null argument");
-    if (!scene->on_device || scene->device != ctx->device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "scene was not created on this context's device");
+    if (yk_status rs = scene_on_context(ctx, scene, "")) return rs;
     if (n > 0xFFFFFF00ull) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "too many rays");
     yk_status wb = check_stage_kernel(ctx, scene, false, t_max, false);
     if (wb != YK_OK) return wb;

@@ -16,6 +16,8 @@
 //     launch(sg.stream, d_in, d_out);
 //     sg.check(hipGetLastError());
 //     return sg.finish();                         // the downloads in registration order, one synchronisation
+// or, where the device work is one enqueue function, the last four lines as
+//     return sg.run([&] { return enqueue(ctx, sg.stream, d_in, d_out); });
 #pragma once
 #include "yk_internal.h"
 
@@ -68,6 +70,13 @@ struct Staging {
         download();
         if (ok()) check(hipStreamSynchronize(stream));
         return status();
+    }
+    // The tail of an entry point whose device work is one call: nothing runs when a slot failed; a failure of enqueue()
+    // (which returns a yk_status) is the call's, with no download and no synchronisation; otherwise finish().
+    template <class Enqueue> yk_status run(const Enqueue& enqueue) {
+        if (!ok()) return status();
+        if (yk_status s = enqueue()) return s;
+        return finish();
     }
 
 private:

@@ -26,6 +26,22 @@ struct TpParams {
     DnParams dn;
     float plane_tolerance, normal_cos_min, max_history;
 };
+// What yk_history_reproject, yk_history_blend and yk_moments_blend ask of their descriptor, and the parameters it makes.
+inline bool tp_desc_ok(const yk_temporal_desc* d) {
+    if (!d) return false;
+    if (!(d->plane_tolerance > 0.0f)) return false;                                   // <= 0 or NaN
+    if (!(d->normal_cos_min >= -1.0f) || !(d->normal_cos_min <= 1.0f)) return false;  // outside [-1, 1] or NaN
+    if (!(d->max_history >= 1.0f)) return false;                                      // < 1 or NaN
+    return true;
+}
+inline TpParams tp_make_params(const yk_temporal_desc* d, uint32_t res_x, uint32_t res_y, uint32_t tile_dim) {
+    TpParams a{};
+    dn_set_grid(a.dn, res_x, res_y, tile_dim);
+    a.plane_tolerance = d->plane_tolerance;
+    a.normal_cos_min = d->normal_cos_min;
+    a.max_history = d->max_history;
+    return a;
+}
 
 // What a reprojection tap reads of a pixel of the previous view: its history record and its guide record (t is not used).
 struct TpTap {

@@ -1,32 +1,34 @@
 // yk_temporal.hip — reproject and blend on gfx950, behind yk_history_reproject[_device] and yk_history_blend[_device]; the
 // per-pixel arithmetic is yk_temporal.h's, whose host instance these entry points run without a context.
 //
-// k_reproject: one lane per pixel, a block is a TP_TX x TP_TY tile of the film (the à-trous launch shape: a wave covers two
-//   rows of 32 pixels, so under small motion neighbouring lanes project to neighbouring taps).  A lane reads its guide (two
+// k_reproject: one lane per pixel, a block is a 32 x 8 tile of the film (yk_film_tile.h: a wave covers two rows of 32
+//   pixels, so under small motion neighbouring lanes project to neighbouring taps).  A lane reads its guide (two
 //   16-byte loads), up to four taps of the previous view (two 16-byte guide loads and one 16-byte history load each, all
 //   issued before the first is consumed; a tap outside the film is never read, its request goes to the nearest pixel inside) and writes one 16-byte record.  The previous
 //   camera's two inverse matrices travel as kernel arguments: scalar registers.  No LDS: the footprint of a tile is not
 //   known before the projection.
-// k_blend: streaming, one lane per pixel: three dword loads of the film (4-byte alignment), one 16-byte load and one 16-byte
-//   store of the records, three dword stores of the RGB output.  "No table", "no history", "no history output" and "no RGB
-//   output" are template variants: no lane tests a pointer.  A lane reads its own pixel only, and before it writes it, so
-//   out_history may be the history and out_rgb the film.
+// k_record_blend: streaming, one lane per pixel: three dword loads of the film (4-byte alignment), one 16-byte load and one
+//   16-byte store of the records, three dword stores of the RGB output.  The pixel rule is a template parameter:
+//   tp_blend_pixel for yk_history_blend, vr_moments_pixel (yk_variance.h) for yk_moments_blend, whose entry points in
+//   yk_variance.hip reach the kernel through record_blend_enqueue (yk_film_call.h).  "No table", "no records", "no record
+//   output" and "no RGB output" are template variants: no lane tests a pointer.  Twelve instances of the history rule can be
+//   launched (one output at least) and four of the moments rule (records out, never RGB).  A lane reads its own pixel only,
+//   and before it writes it, so out_rec may be the records and out_rgb the film.
 // k_reproject<true> (yk_history_reproject_moved): the same lane with the pixel's motion record (one 16-byte load, requested
 //   with the guide loads) in the place of the guide's (p, t) half, which this instance does not read.  The motion pointer
 //   is the kernel's last argument: k_reproject<false> is the kernel as it was.
-// The sample table is staged through the pinned copy the tone map and the denoiser share; the stream-ordered entry points
-// allocate nothing once the context has seen a table of that size.
+// The sample table of either blend is staged into ctx->temporal.samples through the pinned copy the tone map and the
+// denoiser share; the stream-ordered entry points allocate nothing once the context has seen a table of that size.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 
 #include "yk_film_call.h"
+#include "yk_film_tile.h"
 #include "yk_staging.h"
-#include "yk_temporal.h"
+#include "yk_variance.h"
 
 namespace {
-
-constexpr unsigned TP_TX = 32, TP_TY = 8;  // 256 lanes: 4 waves of 64
 
 struct TpIo {
     const float4* prev_history;  // one float4 a pixel: (rgb, n)
@@ -36,8 +38,8 @@ struct TpIo {
 };
 
 template <bool MOVED>
-__global__ __launch_bounds__(TP_TX* TP_TY) void k_reproject(TpIo io, TpParams a, M44 c2w_inv, M44 r2c_inv, const float4* motion) {
-    const uint32_t x = blockIdx.x * TP_TX + threadIdx.x, y = blockIdx.y * TP_TY + threadIdx.y;
+__global__ __launch_bounds__(FT_TX* FT_TY) void k_reproject(TpIo io, TpParams a, M44 c2w_inv, M44 r2c_inv, const float4* motion) {
+    const uint32_t x = blockIdx.x * FT_TX + threadIdx.x, y = blockIdx.y * FT_TY + threadIdx.y;
     if (x >= a.dn.res_x || y >= a.dn.res_y) return;
     const size_t i = (size_t)y * a.dn.res_x + x;
     const float4 ga = io.guides[2 * i], gb = MOVED ? motion[i] : io.guides[2 * i + 1];  // MOVED: (p_prev, known) for (p, t)
@@ -62,16 +64,26 @@ __global__ __launch_bounds__(TP_TX* TP_TY) void k_reproject(TpIo io, TpParams a,
     io.out[i] = make_float4(rec[0], rec[1], rec[2], rec[3]);
 }
 
-struct TpBlendIo {
+// The pixel rules of the record blend as stateless types: the kernel and the host loop are instantiated on one.
+struct HistoryRule {  // yk_history_blend: (rgb, n) records, shown as RGB
+    static constexpr bool RGB_OUTPUT = true;
+    YK_HD void operator()(const TpParams& a, bool has_table, float m, const float* c, const float* h, float* out) const { tp_blend_pixel(a, has_table, m, c, h, out); }
+};
+struct MomentsRule {  // yk_moments_blend: (m1, m2, frames, n) records, never shown
+    static constexpr bool RGB_OUTPUT = false;
+    YK_HD void operator()(const TpParams& a, bool has_table, float m, const float* c, const float* h, float* out) const { vr_moments_pixel(a, has_table, m, c, h, out); }
+};
+
+struct BlendIo {
     const float* film;
     const uint32_t* samples;
-    const float4* history;
-    float4* out_history;
+    const float4* rec;
+    float4* out_rec;
     float* out_rgb;
 };
 
-template <bool TABLE, bool HIST, bool OUT_HIST, bool OUT_RGB>
-__global__ __launch_bounds__(256) void k_blend(TpBlendIo io, TpParams a) {
+template <class Rule, bool TABLE, bool HIST, bool OUT_REC, bool OUT_RGB>
+__global__ __launch_bounds__(256) void k_record_blend(BlendIo io, TpParams a) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.dn.res_x * a.dn.res_y) return;
     const float c[3] = {io.film[3 * (size_t)i], io.film[3 * (size_t)i + 1], io.film[3 * (size_t)i + 2]};
@@ -82,15 +94,15 @@ __global__ __launch_bounds__(256) void k_blend(TpBlendIo io, TpParams a) {
     }
     float h[4] = {0.0f, 0.0f, 0.0f, 0.0f};
     if (HIST) {
-        const float4 v = io.history[i];
+        const float4 v = io.rec[i];
         h[0] = v.x;
         h[1] = v.y;
         h[2] = v.z;
         h[3] = v.w;
     }
     float rec[4];
-    tp_blend_pixel(a, TABLE, m, c, HIST ? h : nullptr, rec);
-    if (OUT_HIST) io.out_history[i] = make_float4(rec[0], rec[1], rec[2], rec[3]);
+    Rule()(a, TABLE, m, c, HIST ? h : nullptr, rec);
+    if (OUT_REC) io.out_rec[i] = make_float4(rec[0], rec[1], rec[2], rec[3]);
     if (OUT_RGB) {
         io.out_rgb[3 * (size_t)i] = rec[0];
         io.out_rgb[3 * (size_t)i + 1] = rec[1];
@@ -98,45 +110,45 @@ __global__ __launch_bounds__(256) void k_blend(TpBlendIo io, TpParams a) {
     }
 }
 
-template <bool TABLE, bool HIST, bool OUT_HIST>
-void launch_blend3(hipStream_t st, uint32_t n_px, const TpBlendIo& io, const TpParams& a) {
+// The outputs: one at least (record_blend_check).  A rule without an RGB output has the records-only instance alone.
+template <class Rule, bool TABLE, bool HIST>
+void launch_blend2(hipStream_t st, uint32_t n_px, const BlendIo& io, const TpParams& a) {
     const dim3 grid((n_px - 1) / 256 + 1), block(256);
-    if (!OUT_HIST || io.out_rgb) hipLaunchKernelGGL((k_blend<TABLE, HIST, OUT_HIST, true>), grid, block, 0, st, io, a);  // one output at least (check_blend)
-    else hipLaunchKernelGGL((k_blend<TABLE, HIST, true, false>), grid, block, 0, st, io, a);
+    if constexpr (Rule::RGB_OUTPUT) {
+        if (io.out_rgb) {
+            if (io.out_rec) hipLaunchKernelGGL((k_record_blend<Rule, TABLE, HIST, true, true>), grid, block, 0, st, io, a);
+            else hipLaunchKernelGGL((k_record_blend<Rule, TABLE, HIST, false, true>), grid, block, 0, st, io, a);
+            return;
+        }
+    }
+    hipLaunchKernelGGL((k_record_blend<Rule, TABLE, HIST, true, false>), grid, block, 0, st, io, a);
 }
-template <bool TABLE, bool HIST>
-void launch_blend2(hipStream_t st, uint32_t n_px, const TpBlendIo& io, const TpParams& a) {
-    if (io.out_history) launch_blend3<TABLE, HIST, true>(st, n_px, io, a);
-    else launch_blend3<TABLE, HIST, false>(st, n_px, io, a);
-}
-void launch_blend(hipStream_t st, uint32_t n_px, const TpBlendIo& io, const TpParams& a) {
-    if (io.samples && io.history) launch_blend2<true, true>(st, n_px, io, a);
-    else if (io.samples) launch_blend2<true, false>(st, n_px, io, a);
-    else if (io.history) launch_blend2<false, true>(st, n_px, io, a);
-    else launch_blend2<false, false>(st, n_px, io, a);
-}
-
-bool desc_ok(const yk_temporal_desc* d) {
-    if (!d) return false;
-    if (!(d->plane_tolerance > 0.0f)) return false;                               // <= 0 or NaN
-    if (!(d->normal_cos_min >= -1.0f) || !(d->normal_cos_min <= 1.0f)) return false;  // outside [-1, 1] or NaN
-    if (!(d->max_history >= 1.0f)) return false;                                  // < 1 or NaN
-    return true;
+template <class Rule>
+void launch_blend(hipStream_t st, uint32_t n_px, const BlendIo& io, const TpParams& a) {
+    if (io.samples && io.rec) launch_blend2<Rule, true, true>(st, n_px, io, a);
+    else if (io.samples) launch_blend2<Rule, true, false>(st, n_px, io, a);
+    else if (io.rec) launch_blend2<Rule, false, true>(st, n_px, io, a);
+    else launch_blend2<Rule, false, false>(st, n_px, io, a);
 }
 
-TpParams make_params(const yk_temporal_desc* d, uint16_t res_x, uint16_t res_y, uint16_t tile_dim) {
-    TpParams a{};
-    dn_set_grid(a.dn, res_x, res_y, tile_dim);
-    a.plane_tolerance = d->plane_tolerance;
-    a.normal_cos_min = d->normal_cos_min;
-    a.max_history = d->max_history;
-    return a;
+template <class Rule>
+void blend_host(const TpParams& a, const float* film, const uint32_t* samples, const float* rec, float* out_rec, float* out_rgb) {
+    for (uint32_t y = 0; y < a.dn.res_y; ++y)
+        for (uint32_t x = 0; x < a.dn.res_x; ++x) {
+            const size_t i = (size_t)y * a.dn.res_x + x;
+            float c[3], h[4], r[4];
+            std::memcpy(c, film + 3 * i, 12);
+            if (rec) std::memcpy(h, rec + 4 * i, 16);
+            Rule()(a, samples != nullptr, samples ? dn_count(a.dn, samples, x, y) : 1.0f, c, rec ? h : nullptr, r);
+            if (out_rec) std::memcpy(out_rec + 4 * i, r, 16);
+            if (out_rgb) std::memcpy(out_rgb + 3 * i, r, 12);
+        }
 }
 
 // has_motion: the call is yk_history_reproject_moved's and `motion` is one more input
 yk_status check_reproject(const yk_temporal_desc* d, const void* prev_history, const void* prev_guides, const yk_camera* prev_camera, const void* guides, uint16_t res_x, uint16_t res_y,
                           const void* out, bool has_motion = false, const void* motion = nullptr) {
-    if (!desc_ok(d) || !prev_history || !prev_guides || !prev_camera || !guides || !out || res_x == 0 || res_y == 0 || (has_motion && !motion)) return YK_ERR_INVALID_ARGUMENT;
+    if (!tp_desc_ok(d) || !prev_history || !prev_guides || !prev_camera || !guides || !out || res_x == 0 || res_y == 0 || (has_motion && !motion)) return YK_ERR_INVALID_ARGUMENT;
     const size_t n_px = (size_t)res_x * res_y;
     if (overlaps(out, n_px * 16, prev_history, n_px * 16) || overlaps(out, n_px * 16, prev_guides, n_px * sizeof(yk_guide)) || overlaps(out, n_px * 16, guides, n_px * sizeof(yk_guide)))
         return YK_ERR_INVALID_ARGUMENT;
@@ -144,50 +156,15 @@ yk_status check_reproject(const yk_temporal_desc* d, const void* prev_history, c
     return YK_OK;
 }
 
-yk_status check_blend(const yk_temporal_desc* d, const void* film, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const void* history, const void* out_history, const void* out_rgb) {
-    if (!desc_ok(d) || !film || res_x == 0 || res_y == 0 || tile_dim == 0) return YK_ERR_INVALID_ARGUMENT;
-    if (!out_history && !out_rgb) return YK_ERR_INVALID_ARGUMENT;
-    const size_t n_px = (size_t)res_x * res_y;
-    if (out_history) {
-        if (overlaps(out_history, n_px * 16, film, n_px * 12)) return YK_ERR_INVALID_ARGUMENT;
-        if (history && out_history != history && overlaps(out_history, n_px * 16, history, n_px * 16)) return YK_ERR_INVALID_ARGUMENT;
-        if (out_rgb && overlaps(out_history, n_px * 16, out_rgb, n_px * 12)) return YK_ERR_INVALID_ARGUMENT;
-    }
-    if (out_rgb) {
-        if (out_rgb != film && overlaps(out_rgb, n_px * 12, film, n_px * 12)) return YK_ERR_INVALID_ARGUMENT;
-        if (history && overlaps(out_rgb, n_px * 12, history, n_px * 16)) return YK_ERR_INVALID_ARGUMENT;
-    }
-    return YK_OK;
-}
-
 yk_status enqueue_reproject(yk_context* ctx, hipStream_t st, const yk_temporal_desc* d, const void* prev_history, const void* prev_guides, const yk_camera* cam, const void* guides,
                             uint16_t res_x, uint16_t res_y, void* out, const void* motion = nullptr) {
-    const TpParams a = make_params(d, res_x, res_y, 1);
+    const TpParams a = tp_make_params(d, res_x, res_y, 1);
     TpIo io{reinterpret_cast<const float4*>(prev_history), reinterpret_cast<const float4*>(prev_guides), reinterpret_cast<const float4*>(guides), reinterpret_cast<float4*>(out)};
     M44 c2w_inv, r2c_inv;
     std::memcpy(c2w_inv.m, cam->camera_to_world_inv, 64);
     std::memcpy(r2c_inv.m, cam->raster_to_camera_inv, 64);
-    const dim3 grid((res_x + TP_TX - 1) / TP_TX, (res_y + TP_TY - 1) / TP_TY), block(TP_TX, TP_TY);
-    if (motion) hipLaunchKernelGGL(k_reproject<true>, grid, block, 0, st, io, a, c2w_inv, r2c_inv, reinterpret_cast<const float4*>(motion));
-    else hipLaunchKernelGGL(k_reproject<false>, grid, block, 0, st, io, a, c2w_inv, r2c_inv, (const float4*)nullptr);
-    HIP_TRY(ctx, hipGetLastError());
-    return YK_OK;
-}
-
-yk_status enqueue_blend(yk_context* ctx, hipStream_t st, const yk_temporal_desc* d, const float* film, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const uint32_t* samples,
-                        const void* history, void* out_history, float* out_rgb) {
-    const TpParams a = make_params(d, res_x, res_y, tile_dim);
-    TpBlendIo io{};
-    io.film = film;
-    io.history = reinterpret_cast<const float4*>(history);
-    io.out_history = reinterpret_cast<float4*>(out_history);
-    io.out_rgb = out_rgb;
-    if (samples) {
-        yk_status ss = stage_sample_table(ctx, st, samples, res_x, res_y, tile_dim, ctx->temporal.samples);
-        if (ss != YK_OK) return ss;
-        io.samples = ctx->temporal.samples.as<const uint32_t>();
-    }
-    launch_blend(st, (uint32_t)res_x * res_y, io, a);
+    if (motion) hipLaunchKernelGGL(k_reproject<true>, ft_grid(res_x, res_y), ft_block(), 0, st, io, a, c2w_inv, r2c_inv, reinterpret_cast<const float4*>(motion));
+    else hipLaunchKernelGGL(k_reproject<false>, ft_grid(res_x, res_y), ft_block(), 0, st, io, a, c2w_inv, r2c_inv, (const float4*)nullptr);
     HIP_TRY(ctx, hipGetLastError());
     return YK_OK;
 }
@@ -202,7 +179,7 @@ void fetch_host(const float* hist, const yk_guide* g, size_t q, TpTap& t) {
 
 void reproject_host(const yk_temporal_desc* d, const yk_history* prev_history, const yk_guide* prev_guides, const yk_camera* cam, const yk_guide* guides, uint16_t res_x, uint16_t res_y,
                     yk_history* out, const yk_motion* motion = nullptr) {
-    const TpParams a = make_params(d, res_x, res_y, 1);
+    const TpParams a = tp_make_params(d, res_x, res_y, 1);
     const float* hist = reinterpret_cast<const float*>(prev_history);
     const auto fetch = [&](uint32_t qx, uint32_t qy, TpTap& t) { fetch_host(hist, prev_guides, (size_t)qy * res_x + qx, t); };
     for (uint32_t y = 0; y < res_y; ++y)
@@ -219,22 +196,42 @@ void reproject_host(const yk_temporal_desc* d, const yk_history* prev_history, c
         }
 }
 
-void blend_host(const yk_temporal_desc* d, const float* film, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const uint32_t* samples, const yk_history* history, yk_history* out_history,
-                float* out_rgb) {
-    const TpParams a = make_params(d, res_x, res_y, tile_dim);
-    for (uint32_t y = 0; y < res_y; ++y)
-        for (uint32_t x = 0; x < res_x; ++x) {
-            const size_t i = (size_t)y * res_x + x;
-            float c[3], h[4], rec[4];
-            std::memcpy(c, film + 3 * i, 12);
-            if (history) std::memcpy(h, &history[i], 16);
-            tp_blend_pixel(a, samples != nullptr, samples ? dn_count(a.dn, samples, x, y) : 1.0f, c, history ? h : nullptr, rec);
-            if (out_history) std::memcpy(&out_history[i], rec, 16);
-            if (out_rgb) std::memcpy(out_rgb + 3 * i, rec, 12);
-        }
+}  // namespace
+
+// ------------------------------------------------------------------ the record blend (yk_film_call.h)
+yk_status record_blend_check(const yk_temporal_desc* d, const void* film, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const void* rec, const void* out_rec, const void* out_rgb) {
+    if (!tp_desc_ok(d) || !film || res_x == 0 || res_y == 0 || tile_dim == 0) return YK_ERR_INVALID_ARGUMENT;
+    if (!out_rec && !out_rgb) return YK_ERR_INVALID_ARGUMENT;
+    const size_t n_px = (size_t)res_x * res_y;
+    if (out_rec) {
+        if (overlaps(out_rec, n_px * 16, film, n_px * 12)) return YK_ERR_INVALID_ARGUMENT;
+        if (rec && out_rec != rec && overlaps(out_rec, n_px * 16, rec, n_px * 16)) return YK_ERR_INVALID_ARGUMENT;
+        if (out_rgb && overlaps(out_rec, n_px * 16, out_rgb, n_px * 12)) return YK_ERR_INVALID_ARGUMENT;
+    }
+    if (out_rgb) {
+        if (out_rgb != film && overlaps(out_rgb, n_px * 12, film, n_px * 12)) return YK_ERR_INVALID_ARGUMENT;
+        if (rec && overlaps(out_rgb, n_px * 12, rec, n_px * 16)) return YK_ERR_INVALID_ARGUMENT;
+    }
+    return YK_OK;
 }
 
-}  // namespace
+yk_status record_blend_enqueue(yk_context* ctx, hipStream_t st, BlendRule rule, const yk_temporal_desc* d, const float* film, uint16_t res_x, uint16_t res_y, uint16_t tile_dim,
+                               const uint32_t* samples, const void* rec, void* out_rec, float* out_rgb) {
+    const TpParams a = tp_make_params(d, res_x, res_y, tile_dim);
+    BlendIo io{film, nullptr, reinterpret_cast<const float4*>(rec), reinterpret_cast<float4*>(out_rec), out_rgb};
+    if (yk_status ss = stage_samples(ctx, st, samples, res_x, res_y, tile_dim, ctx->temporal.samples, &io.samples)) return ss;
+    if (rule == BlendRule::MOMENTS) launch_blend<MomentsRule>(st, (uint32_t)res_x * res_y, io, a);
+    else launch_blend<HistoryRule>(st, (uint32_t)res_x * res_y, io, a);
+    HIP_TRY(ctx, hipGetLastError());
+    return YK_OK;
+}
+
+void record_blend_host(BlendRule rule, const yk_temporal_desc* d, const float* film, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const uint32_t* samples, const void* rec, void* out_rec,
+                       float* out_rgb) {
+    const TpParams a = tp_make_params(d, res_x, res_y, tile_dim);
+    if (rule == BlendRule::MOMENTS) blend_host<MomentsRule>(a, film, samples, static_cast<const float*>(rec), static_cast<float*>(out_rec), out_rgb);
+    else blend_host<HistoryRule>(a, film, samples, static_cast<const float*>(rec), static_cast<float*>(out_rec), out_rgb);
+}
 
 // yk_history_reproject (has_motion false, motion NULL) and yk_history_reproject_moved behind one body each; `name` is the
 // entry point's, for its messages.
@@ -254,10 +251,7 @@ static yk_status reproject_arrays(yk_context* ctx, const char* name, bool has_mo
     const yk_guide* d_prev_guides = sg.upload(prev_guides, n_px);
     const yk_guide* d_guides = sg.upload(guides, n_px);
     yk_history* d_out = sg.output(out_history, n_px);
-    if (!sg.ok()) return sg.status();
-    yk_status s = enqueue_reproject(ctx, sg.stream, desc, d_prev_history, d_prev_guides, prev_camera, d_guides, res_x, res_y, d_out, d_motion);
-    if (s != YK_OK) return s;
-    return sg.finish();
+    return sg.run([&] { return enqueue_reproject(ctx, sg.stream, desc, d_prev_history, d_prev_guides, prev_camera, d_guides, res_x, res_y, d_out, d_motion); });
 }
 
 static yk_status reproject_device(yk_context* ctx, const char* name, bool has_motion, const yk_temporal_desc* desc, const void* d_prev_history, const void* d_prev_guides,
@@ -296,9 +290,9 @@ yk_status yk_history_reproject_moved_device(yk_context* ctx, const yk_temporal_d
 
 yk_status yk_history_blend(yk_context* ctx, const yk_temporal_desc* desc, const float* film_rgb, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const uint32_t* samples,
                            const yk_history* history, yk_history* out_history, float* out_rgb) {
-    if (check_blend(desc, film_rgb, res_x, res_y, tile_dim, history, out_history, out_rgb) != YK_OK) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_history_blend: bad argument");
+    if (record_blend_check(desc, film_rgb, res_x, res_y, tile_dim, history, out_history, out_rgb) != YK_OK) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_history_blend: bad argument");
     if (!ctx) {  // the host instance
-        blend_host(desc, film_rgb, res_x, res_y, tile_dim, samples, history, out_history, out_rgb);
+        record_blend_host(BlendRule::HISTORY, desc, film_rgb, res_x, res_y, tile_dim, samples, history, out_history, out_rgb);
         return YK_OK;
     }
     YK_LOCK(ctx);
@@ -308,22 +302,20 @@ yk_status yk_history_blend(yk_context* ctx, const yk_temporal_desc* desc, const 
     const yk_history* d_history = history ? sg.upload(history, n_px) : nullptr;
     yk_history* d_out_history = sg.output(out_history, n_px);  // an output the caller left out takes no slot and stays NULL
     float* d_out_rgb = sg.output(out_rgb, n_px * 3);
-    if (!sg.ok()) return sg.status();
-    yk_status s = enqueue_blend(ctx, sg.stream, desc, d_film, res_x, res_y, tile_dim, samples, d_history, d_out_history, d_out_rgb);
-    if (s != YK_OK) return s;
-    return sg.finish();
+    return sg.run([&] { return record_blend_enqueue(ctx, sg.stream, BlendRule::HISTORY, desc, d_film, res_x, res_y, tile_dim, samples, d_history, d_out_history, d_out_rgb); });
 }
 
 yk_status yk_history_blend_device(yk_context* ctx, const yk_temporal_desc* desc, const void* d_film_rgb, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const uint32_t* samples,
                                   const void* d_history, void* d_out_history, void* d_out_rgb, void* stream) {
     if (!ctx) return YK_ERR_INVALID_ARGUMENT;
     YK_LOCK(ctx);
-    if (check_blend(desc, d_film_rgb, res_x, res_y, tile_dim, d_history, d_out_history, d_out_rgb) != YK_OK)
+    if (record_blend_check(desc, d_film_rgb, res_x, res_y, tile_dim, d_history, d_out_history, d_out_rgb) != YK_OK)
         return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_history_blend_device: bad argument");
     // dword loads and stores of the film and the RGB output, 16-byte loads and stores of the records
     if (misaligned(4, d_film_rgb, d_out_rgb) || misaligned(16, d_history, d_out_history))
         return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_history_blend_device: film and RGB output must be 4-byte aligned, histories 16-byte aligned");
-    return enqueue_blend(ctx, device_call_stream(ctx, stream), desc, reinterpret_cast<const float*>(d_film_rgb), res_x, res_y, tile_dim, samples, d_history, d_out_history, reinterpret_cast<float*>(d_out_rgb));
+    return record_blend_enqueue(ctx, device_call_stream(ctx, stream), BlendRule::HISTORY, desc, reinterpret_cast<const float*>(d_film_rgb), res_x, res_y, tile_dim, samples, d_history, d_out_history,
+                                reinterpret_cast<float*>(d_out_rgb));
 }
 
 }  // extern "C"

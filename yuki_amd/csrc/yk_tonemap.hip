@@ -189,11 +189,8 @@ yk_status enqueue(yk_context* ctx, hipStream_t st, const yk_tone_map_desc* d, co
         if (film != out) HIP_TRY(ctx, hipMemcpyAsync(out, film, (size_t)n_px * 12, hipMemcpyDeviceToDevice, st));
         return YK_OK;
     }
-    if (d->kind == YK_TONE_MAP_FILMIC && samples) {
-        yk_status ss = stage_sample_table(ctx, st, samples, res_x, res_y, tile_dim, tm.samples);
-        if (ss != YK_OK) return ss;
-        a.samples = tm.samples.as<uint32_t>();
-    }
+    if (d->kind == YK_TONE_MAP_FILMIC)
+        if (yk_status ss = stage_samples(ctx, st, samples, res_x, res_y, tile_dim, tm.samples, &a.samples)) return ss;
     if (d->kind == YK_TONE_MAP_HEATMAP && !d->has_bounds) {
         HIP_TRY(ctx, tm.partials.ensure(TM_MAX_BLOCKS * sizeof(float2)));
         HIP_TRY(ctx, tm.bounds.ensure(256));

@@ -3,9 +3,9 @@
 // whose host instance these entry points run without a context.  The filter itself, yk_denoise_variance, is one more
 // instance of the à-trous kernel and lives with it in yk_denoise.hip.
 //
-// k_moments_blend: streaming, one lane per pixel, k_blend's sibling: three dword loads of the film, one 16-byte load and one
-//   16-byte store of the records.  "No table" and "no history" are template variants.  A lane reads its own pixel only, and
-//   before it writes it, so the output may be the input moments.
+// yk_moments_blend has no kernel of its own: it is the record blend of yk_temporal.hip (k_record_blend, reached through
+//   yk_film_call.h) with vr_moments_pixel as its pixel rule, records out and no RGB output.  The output may be the input
+//   moments.
 // k_variance: one lane per pixel, a block is a 32 x 8 tile of the film (yk_film_tile.h).  The temporal estimate is one 16-byte load
 //   (two with an albedo) and a handful of VALU operations.  Whether the block evaluates the 7 x 7 window at all is decided
 //   once per block (__syncthreads_or over "this lane has no temporal estimate"): after the first frames nearly no block
@@ -25,97 +25,6 @@
 #include "yk_variance.h"
 
 namespace {
-
-// ------------------------------------------------------------------ moments blend
-struct VrBlendIo {
-    const float* film;
-    const uint32_t* samples;
-    const float4* moments;
-    float4* out;
-};
-
-template <bool TABLE, bool HIST>
-__global__ __launch_bounds__(256) void k_moments_blend(VrBlendIo io, TpParams a) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= a.dn.res_x * a.dn.res_y) return;
-    const float c[3] = {io.film[3 * (size_t)i], io.film[3 * (size_t)i + 1], io.film[3 * (size_t)i + 2]};
-    float m = 1.0f;
-    if (TABLE) {
-        const uint32_t y = i / a.dn.res_x, x = i - y * a.dn.res_x;
-        m = dn_count(a.dn, io.samples, x, y);
-    }
-    float h[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-    if (HIST) {
-        const float4 v = io.moments[i];
-        h[0] = v.x;
-        h[1] = v.y;
-        h[2] = v.z;
-        h[3] = v.w;
-    }
-    float rec[4];
-    vr_moments_pixel(a, TABLE, m, c, HIST ? h : nullptr, rec);
-    io.out[i] = make_float4(rec[0], rec[1], rec[2], rec[3]);
-}
-
-bool temporal_desc_ok(const yk_temporal_desc* d) {  // yk_history_blend's rule
-    if (!d) return false;
-    if (!(d->plane_tolerance > 0.0f)) return false;
-    if (!(d->normal_cos_min >= -1.0f) || !(d->normal_cos_min <= 1.0f)) return false;
-    if (!(d->max_history >= 1.0f)) return false;
-    return true;
-}
-
-TpParams make_blend_params(const yk_temporal_desc* d, uint16_t res_x, uint16_t res_y, uint16_t tile_dim) {
-    TpParams a{};
-    dn_set_grid(a.dn, res_x, res_y, tile_dim);
-    a.plane_tolerance = d->plane_tolerance;
-    a.normal_cos_min = d->normal_cos_min;
-    a.max_history = d->max_history;
-    return a;
-}
-
-yk_status check_blend(const yk_temporal_desc* d, const void* film, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const void* moments, const void* out) {
-    if (!temporal_desc_ok(d) || !film || !out || res_x == 0 || res_y == 0 || tile_dim == 0) return YK_ERR_INVALID_ARGUMENT;
-    const size_t n_px = (size_t)res_x * res_y;
-    if (overlaps(out, n_px * 16, film, n_px * 12)) return YK_ERR_INVALID_ARGUMENT;
-    if (moments && out != moments && overlaps(out, n_px * 16, moments, n_px * 16)) return YK_ERR_INVALID_ARGUMENT;
-    return YK_OK;
-}
-
-yk_status enqueue_blend(yk_context* ctx, hipStream_t st, const yk_temporal_desc* d, const float* film, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const uint32_t* samples,
-                        const void* moments, void* out) {
-    const TpParams a = make_blend_params(d, res_x, res_y, tile_dim);
-    VrBlendIo io{};
-    io.film = film;
-    io.moments = reinterpret_cast<const float4*>(moments);
-    io.out = reinterpret_cast<float4*>(out);
-    if (samples) {
-        yk_status ss = stage_sample_table(ctx, st, samples, res_x, res_y, tile_dim, ctx->temporal.samples);
-        if (ss != YK_OK) return ss;
-        io.samples = ctx->temporal.samples.as<const uint32_t>();
-    }
-    const uint32_t n_px = (uint32_t)res_x * res_y;
-    const dim3 grid((n_px - 1) / 256 + 1), block(256);
-    if (io.samples && io.moments) hipLaunchKernelGGL((k_moments_blend<true, true>), grid, block, 0, st, io, a);
-    else if (io.samples) hipLaunchKernelGGL((k_moments_blend<true, false>), grid, block, 0, st, io, a);
-    else if (io.moments) hipLaunchKernelGGL((k_moments_blend<false, true>), grid, block, 0, st, io, a);
-    else hipLaunchKernelGGL((k_moments_blend<false, false>), grid, block, 0, st, io, a);
-    HIP_TRY(ctx, hipGetLastError());
-    return YK_OK;
-}
-
-void blend_host(const yk_temporal_desc* d, const float* film, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const uint32_t* samples, const yk_moments* moments, yk_moments* out) {
-    const TpParams a = make_blend_params(d, res_x, res_y, tile_dim);
-    for (uint32_t y = 0; y < res_y; ++y)
-        for (uint32_t x = 0; x < res_x; ++x) {
-            const size_t i = (size_t)y * res_x + x;
-            float c[3], h[4], rec[4];
-            std::memcpy(c, film + 3 * i, 12);
-            if (moments) std::memcpy(h, &moments[i], 16);
-            vr_moments_pixel(a, samples != nullptr, samples ? dn_count(a.dn, samples, x, y) : 1.0f, c, moments ? h : nullptr, rec);
-            std::memcpy(&out[i], rec, 16);
-        }
-}
 
 // ------------------------------------------------------------------ yk_variance
 struct VrVarIo {
@@ -190,11 +99,7 @@ yk_status enqueue_variance(yk_context* ctx, hipStream_t st, const yk_variance_de
     io.guides = reinterpret_cast<const float4*>(guides);
     io.albedo = reinterpret_cast<const float4*>(albedo);
     io.out = out;
-    if (samples) {
-        yk_status ss = stage_sample_table(ctx, st, samples, res_x, res_y, tile_dim, ctx->denoise.samples);
-        if (ss != YK_OK) return ss;
-        io.samples = ctx->denoise.samples.as<const uint32_t>();
-    }
+    if (yk_status ss = stage_samples(ctx, st, samples, res_x, res_y, tile_dim, ctx->denoise.samples, &io.samples)) return ss;
     hipLaunchKernelGGL(k_variance, ft_grid(res_x, res_y), ft_block(), 0, st, io, a);
     HIP_TRY(ctx, hipGetLastError());
     return YK_OK;
@@ -229,9 +134,9 @@ extern "C" {
 
 yk_status yk_moments_blend(yk_context* ctx, const yk_temporal_desc* desc, const float* film_rgb, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const uint32_t* samples,
                            const yk_moments* moments, yk_moments* out_moments) try {
-    if (check_blend(desc, film_rgb, res_x, res_y, tile_dim, moments, out_moments) != YK_OK) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_moments_blend: bad argument");
+    if (record_blend_check(desc, film_rgb, res_x, res_y, tile_dim, moments, out_moments, nullptr) != YK_OK) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_moments_blend: bad argument");
     if (!ctx) {  // the host instance
-        blend_host(desc, film_rgb, res_x, res_y, tile_dim, samples, moments, out_moments);
+        record_blend_host(BlendRule::MOMENTS, desc, film_rgb, res_x, res_y, tile_dim, samples, moments, out_moments, nullptr);
         return YK_OK;
     }
     YK_LOCK(ctx);
@@ -240,10 +145,7 @@ yk_status yk_moments_blend(yk_context* ctx, const yk_temporal_desc* desc, const 
     const float* d_film = sg.upload(film_rgb, n_px * 3);
     const yk_moments* d_moments = moments ? sg.upload(moments, n_px) : nullptr;
     yk_moments* d_out = sg.output(out_moments, n_px);
-    if (!sg.ok()) return sg.status();
-    yk_status s = enqueue_blend(ctx, sg.stream, desc, d_film, res_x, res_y, tile_dim, samples, d_moments, d_out);
-    if (s != YK_OK) return s;
-    return sg.finish();
+    return sg.run([&] { return record_blend_enqueue(ctx, sg.stream, BlendRule::MOMENTS, desc, d_film, res_x, res_y, tile_dim, samples, d_moments, d_out, nullptr); });
 }
 YK_CATCH(ctx)
 
@@ -251,11 +153,12 @@ yk_status yk_moments_blend_device(yk_context* ctx, const yk_temporal_desc* desc,
                                   const void* d_moments, void* d_out_moments, void* stream) {
     if (!ctx) return YK_ERR_INVALID_ARGUMENT;
     YK_LOCK(ctx);
-    if (check_blend(desc, d_film_rgb, res_x, res_y, tile_dim, d_moments, d_out_moments) != YK_OK) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_moments_blend_device: bad argument");
+    if (record_blend_check(desc, d_film_rgb, res_x, res_y, tile_dim, d_moments, d_out_moments, nullptr) != YK_OK) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_moments_blend_device: bad argument");
     // dword loads of the film, 16-byte loads and stores of the records
     if (misaligned(4, d_film_rgb) || misaligned(16, d_moments, d_out_moments))
         return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_moments_blend_device: film must be 4-byte aligned, moments 16-byte aligned");
-    return enqueue_blend(ctx, device_call_stream(ctx, stream), desc, reinterpret_cast<const float*>(d_film_rgb), res_x, res_y, tile_dim, samples, d_moments, d_out_moments);
+    return record_blend_enqueue(ctx, device_call_stream(ctx, stream), BlendRule::MOMENTS, desc, reinterpret_cast<const float*>(d_film_rgb), res_x, res_y, tile_dim, samples, d_moments, d_out_moments,
+                                nullptr);
 }
 
 yk_status yk_variance(yk_context* ctx, const yk_variance_desc* desc, const yk_moments* moments, const float* film_rgb, const yk_guide* guides, const yk_albedo* albedo, uint16_t res_x,
@@ -273,10 +176,7 @@ yk_status yk_variance(yk_context* ctx, const yk_variance_desc* desc, const yk_mo
     const yk_guide* d_guides = sg.upload(guides, n_px);
     const yk_albedo* d_albedo = albedo ? sg.upload(albedo, n_px) : nullptr;
     float* d_out = sg.output(out_variance, n_px);
-    if (!sg.ok()) return sg.status();
-    yk_status s = enqueue_variance(ctx, sg.stream, desc, d_moments, d_film, d_guides, d_albedo, res_x, res_y, tile_dim, samples, d_out);
-    if (s != YK_OK) return s;
-    return sg.finish();
+    return sg.run([&] { return enqueue_variance(ctx, sg.stream, desc, d_moments, d_film, d_guides, d_albedo, res_x, res_y, tile_dim, samples, d_out); });
 }
 YK_CATCH(ctx)
 
