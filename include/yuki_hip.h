@@ -286,7 +286,8 @@ yk_status yk_context_interrupt(yk_context* ctx);
  * stage their taps in LDS, the others read global memory); "update_top_block" (0 | 1, default 1: the device route of
  * yk_scene_update finishes the tree's top levels of at most 256 nodes each with one block instead of a launch per level);
  * "albedo_mean_band_rows" (0 .. 65535, default 0: the output rows yk_render_albedo_mean[_device] traces and reduces at a
- * time; 0 = as many as fit its 64 MiB scratch).  Test hook: "trace_stage_kernel" (0, default: yk_trace_closest /
+ * time; 0 = as many as fit its 64 MiB scratch); "exposure_wave_combine" (0 | 1, default 1: in the exposure meter's
+ * histogram pass a wave whose lanes all hit one bin adds to it once instead of once a lane; the counts are the same).  Test hook: "trace_stage_kernel" (0, default: yk_trace_closest /
  * yk_trace_any run the generic kernels as documented | 1: the generic kernels in the render loop's
  * flavour | 2: the wave-packet kernels; modes 1 and 2 report shape ids and verdicts only, and
  * refuse out_t, out_bary, counters, a closest-hit t_max and, in mode 2, a tree deeper than 64
@@ -552,6 +553,52 @@ yk_status yk_tone_map_device(yk_context* ctx, const yk_tone_map_desc* desc, cons
  * green, blue or luminance ((0.2126*r + 0.7152*g) + 0.0722*b).  ctx NULL = CPU.  The sign of a zero bound is not
  * specified. */
 yk_status yk_film_min_max(yk_context* ctx, const float* film_rgb, uint16_t res_x, uint16_t res_y, uint32_t channel, float out_min_max[2]);
+
+/* ---- exposure meter (the project's own; the reference's exposure is a slider, tonemap.rs:12-22) ----------
+ * A 256-bin integer histogram of the film's luminances chooses the Filmic exposure; the rule is stated in full in
+ * yuki_amd/csrc/yk_exposure.h and is integer arithmetic up to one division, so the host and the device instance agree bit
+ * for bit whatever the order of the device's additions.  In short:
+ *   pixel: r, g, b divided by (float)samples[flat] when > 0 (the tone map's step 1, same lookup), Y = (0.2126*r +
+ *     0.7152*g) + 0.0722*b.  Y not finite or <= 0: counted in `skipped` only.
+ *   bin = clamp((bits(Y) >> 20) - 888, 0, 255): eight bins to a stop over 2^-16 <= Y < 2^16; values below go to bin 0 and
+ *     `below`, values above to bin 255 and `above`.  A bin's value in Q16 stops is ((bin >> 3) - 16) * 65536 + Q[bin & 7],
+ *     Q = {5732, 16248, 25711, 34312, 42196, 49472, 56229, 62534}: at most 0.0875 stop from any luminance in the bin.
+ *   window {x0, y0, x1, y1}, half open: pixels outside are neither counted nor skipped.
+ *   cut: of the N counted samples in bin order, the lowest (N * low_cut) >> 16 and the highest (N * high_cut) >> 16 are
+ *     dropped (cuts in units of 1/65536); log2_metered = (float)((double)S / ((double)K * 65536.0)) over the K kept ones.
+ *   adapt: log2_adapted = prev.log2_adapted + (log2_metered - prev.log2_adapted) * (adapt_up when the difference is > 0,
+ *     else adapt_down); without a previous state, or with prev.frames == 0, log2_adapted = log2_metered.  N == 0 carries
+ *     the previous state, or gives log2_adapted = ev_bias and frames = 0 without one.
+ *   exposure = 2^clamp(ev_bias - log2_adapted, min_ev, max_ev) by a fixed polynomial (relative error below 1e-5).
+ *     ev_bias is log2 of the key (0.18) plus any compensation. */
+typedef struct yk_exposure_desc {
+    uint32_t low_cut, high_cut; /* units of 1/65536; low_cut + high_cut < 65536 */
+    float ev_bias, min_ev, max_ev, adapt_up, adapt_down; /* -24 <= min_ev <= max_ev <= 24; rates in [0, 1] */
+    uint16_t window[4]; /* x0, y0, x1, y1: x0 < x1 <= res_x, y0 < y1 <= res_y */
+} yk_exposure_desc;
+typedef struct yk_exposure_state {
+    float exposure, log2_adapted, log2_metered;
+    uint32_t frames, counted, skipped, below, above;
+} yk_exposure_state;
+/* The histogram alone, host film (as yk_tone_map's: ctx NULL = the host instance, samples may be NULL).  window NULL =
+ * the whole film.  out_bins and out_skipped_below_above may each be NULL, not both.
+ * YK_ERR_INVALID_ARGUMENT: NULL film, a zero resolution, tile_dim 0, an empty window or one outside the film. */
+yk_status yk_film_histogram(yk_context* ctx, const float* film_rgb, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const uint32_t* samples,
+                            const uint16_t window[4], uint32_t out_bins[256], uint32_t out_skipped_below_above[3]);
+/* Meter a host film: *out from the film and *prev (NULL: no history; may equal out).  ctx NULL = the host instance.
+ * YK_ERR_INVALID_ARGUMENT also for a descriptor outside the ranges above. */
+yk_status yk_exposure_meter(yk_context* ctx, const yk_exposure_desc* desc, const float* film_rgb, uint16_t res_x, uint16_t res_y, uint16_t tile_dim,
+                            const uint32_t* samples, const yk_exposure_state* prev, yk_exposure_state* out);
+/* The same on a device film, enqueued on `stream` (NULL = the context's) without waiting: d_prev (NULL: no history) and
+ * d_out_state are yk_exposure_state records in device memory, 4-byte aligned, and may be the same record, so a chain of
+ * frames never touches the host.  `samples` is a HOST table as for yk_tone_map_device.  Allocates on first use only. */
+yk_status yk_exposure_meter_device(yk_context* ctx, const yk_exposure_desc* desc, const void* d_film_rgb, uint16_t res_x, uint16_t res_y,
+                                   uint16_t tile_dim, const uint32_t* samples, const void* d_prev, void* d_out_state, void* stream);
+/* yk_tone_map_device for Filmic with the exposure desc->exposure * d_state->exposure (one binary32 multiply), the
+ * record read on the device when the kernel runs.  YK_ERR_INVALID_ARGUMENT: any kind but Filmic, a NULL or misaligned
+ * d_state, and what yk_tone_map_device refuses. */
+yk_status yk_tone_map_metered_device(yk_context* ctx, const yk_tone_map_desc* desc, const void* d_state, const void* d_film_rgb, uint16_t res_x,
+                                     uint16_t res_y, uint16_t tile_dim, const uint32_t* samples, void* d_out_rgb, void* stream);
 
 /* Exactly the trait method: one tile, returns the ray count through *out_rays. */
 yk_status yk_render_tile(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, const yk_sampler_desc* sampler,

@@ -185,6 +185,34 @@ pub struct yk_tone_map_desc {
     pub bounds: [f32; 2],
 }
 
+/// The exposure meter's rule (yk_exposure.h): cuts in units of 1/65536, bias, clamp, rates and window
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct yk_exposure_desc {
+    pub low_cut: u32,
+    pub high_cut: u32,
+    pub ev_bias: f32,
+    pub min_ev: f32,
+    pub max_ev: f32,
+    pub adapt_up: f32,
+    pub adapt_down: f32,
+    pub window: [u16; 4],
+}
+
+/// The exposure meter's 32-byte record
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct yk_exposure_state {
+    pub exposure: f32,
+    pub log2_adapted: f32,
+    pub log2_metered: f32,
+    pub frames: u32,
+    pub counted: u32,
+    pub skipped: u32,
+    pub below: u32,
+    pub above: u32,
+}
+
 /// ScaleOutput::draw (app/renderpasses/scale_output.rs): the window, the encode and the frame format
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -537,6 +565,10 @@ extern "C" {
     pub fn yk_tone_map(ctx: *mut yk_context, desc: *const yk_tone_map_desc, film_rgb: *const f32, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, out_rgb: *mut f32, used_bounds: *mut f32) -> yk_status;
     pub fn yk_tone_map_device(ctx: *mut yk_context, desc: *const yk_tone_map_desc, d_film_rgb: *const c_void, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, d_out_rgb: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_film_min_max(ctx: *mut yk_context, film_rgb: *const f32, res_x: u16, res_y: u16, channel: u32, out_min_max: *mut f32) -> yk_status;
+    pub fn yk_film_histogram(ctx: *mut yk_context, film_rgb: *const f32, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, window: *const u16, out_bins: *mut u32, out_skipped_below_above: *mut u32) -> yk_status;
+    pub fn yk_exposure_meter(ctx: *mut yk_context, desc: *const yk_exposure_desc, film_rgb: *const f32, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, prev: *const yk_exposure_state, out: *mut yk_exposure_state) -> yk_status;
+    pub fn yk_exposure_meter_device(ctx: *mut yk_context, desc: *const yk_exposure_desc, d_film_rgb: *const c_void, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, d_prev: *const c_void, d_out_state: *mut c_void, stream: *mut c_void) -> yk_status;
+    pub fn yk_tone_map_metered_device(ctx: *mut yk_context, desc: *const yk_tone_map_desc, d_state: *const c_void, d_film_rgb: *const c_void, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, d_out_rgb: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_scene_node_bounds(scene: *const yk_scene, target_level: i32, out_bounds: *mut f32, cap: usize) -> usize;
     pub fn yk_overlay_world_to_clip(params: *const yk_camera_params, scene_bounds: *const f32, out: *mut f32) -> yk_status;
     pub fn yk_overlay_ray_lines(rays: *const yk_integrator_ray, n: usize, out: *mut yk_overlay_line) -> yk_status;

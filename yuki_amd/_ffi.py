@@ -162,6 +162,10 @@ SYMBOLS = {
     "yk_tone_map": (C.c_int, [vp, C.POINTER(abi.ToneMapDesc), vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp]),
     "yk_tone_map_device": (C.c_int, [vp, C.POINTER(abi.ToneMapDesc), vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp]),
     "yk_film_min_max": (C.c_int, [vp, vp, C.c_uint16, C.c_uint16, C.c_uint32, vp]),
+    "yk_film_histogram": (C.c_int, [vp, vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp, vp]),
+    "yk_exposure_meter": (C.c_int, [vp, C.POINTER(abi.ExposureDesc), vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, C.POINTER(abi.ExposureState), C.POINTER(abi.ExposureState)]),
+    "yk_exposure_meter_device": (C.c_int, [vp, C.POINTER(abi.ExposureDesc), vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp, vp]),
+    "yk_tone_map_metered_device": (C.c_int, [vp, C.POINTER(abi.ToneMapDesc), vp, vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp]),
     "yk_scene_node_bounds": (C.c_size_t, [vp, C.c_int32, vp, C.c_size_t]),
     "yk_overlay_world_to_clip": (C.c_int, [C.POINTER(abi.CameraParams), vp, vp]),
     "yk_overlay_ray_lines": (C.c_int, [vp, C.c_size_t, vp]),

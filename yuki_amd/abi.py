@@ -114,6 +114,36 @@ class ToneMapDesc(C.Structure):
     _fields_ = [("kind", C.c_uint32), ("exposure", C.c_float), ("channel", C.c_uint32), ("has_bounds", C.c_uint32), ("bounds", C.c_float * 2)]
 
 
+class ExposureDesc(C.Structure):
+    """yk_exposure_desc: the meter's cuts (units of 1/65536), bias, clamp, adaptation rates and window (csrc/yk_exposure.h)."""
+
+    _fields_ = [
+        ("low_cut", C.c_uint32),
+        ("high_cut", C.c_uint32),
+        ("ev_bias", C.c_float),
+        ("min_ev", C.c_float),
+        ("max_ev", C.c_float),
+        ("adapt_up", C.c_float),
+        ("adapt_down", C.c_float),
+        ("window", C.c_uint16 * 4),
+    ]
+
+
+class ExposureState(C.Structure):
+    """yk_exposure_state: the meter's 32-byte record."""
+
+    _fields_ = [
+        ("exposure", C.c_float),
+        ("log2_adapted", C.c_float),
+        ("log2_metered", C.c_float),
+        ("frames", C.c_uint32),
+        ("counted", C.c_uint32),
+        ("skipped", C.c_uint32),
+        ("below", C.c_uint32),
+        ("above", C.c_uint32),
+    ]
+
+
 class PresentDesc(C.Structure):
     """yk_present_desc: the window, the encode (yk_present_encode) and the frame format (yk_present_format)."""
 

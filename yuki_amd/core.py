@@ -202,9 +202,21 @@ def _tone_map_args(res, tone_map, tile_dim, samples):
     return samples
 
 
-def tone_map(film, tone_map, tile_dim, samples=None, ctx=None, used_bounds=None):
+def _metered(desc, exposure_state):
+    """The Filmic descriptor whose exposure is desc.exposure * exposure_state.exposure, the one binary32 multiply of
+    yk_tone_map_metered_device."""
+    if desc.kind != abi.TONE_MAP_FILMIC:
+        raise ValueError("exposure_state needs the Filmic tone map: the others have no exposure")
+    e = np.float32(desc.exposure) * np.float32(exposure_state.exposure)
+    return abi.ToneMapDesc(abi.TONE_MAP_FILMIC, float(e), 0, 0, (C.c_float * 2)(0.0, 0.0))
+
+
+def tone_map(film, tone_map, tile_dim, samples=None, ctx=None, used_bounds=None, exposure_state=None):
     """ToneMapFilm::draw (tonemap.rs:143-213) plus the bounds search of headless.rs:135-145: (h, w, 3) float32 in and out.
-    ctx None = the host instance; `used_bounds` (a float32[2] array) receives the Heatmap bounds applied."""
+    ctx None = the host instance; `used_bounds` (a float32[2] array) receives the Heatmap bounds applied.  exposure_state
+    (an ExposureState, Filmic only): the exposure is the descriptor's times the meter's."""
+    if exposure_state is not None:
+        tone_map = _metered(tone_map, exposure_state)
     return _apply_tone_map(film, tone_map, tile_dim, samples, ctx, used_bounds)
 
 
@@ -225,6 +237,76 @@ def find_min_max(film, channel, ctx=None):
     c = ctx.h if ctx else None
     check(lib().yk_film_min_max(c, _p(film), film.shape[1], film.shape[0], int(channel), _p(out)), c)
     return float(out[0]), float(out[1])
+
+
+# --------------------------------------------------------------------------- exposure meter
+@dataclass
+class ExposureParams:
+    """yk_exposure_desc (csrc/yk_exposure.h): low_cut / high_cut are the fractions of the counted pixels dropped at the
+    dark and the bright end (converted by round(x * 65536)); the metered luminance is brought to `key`, `compensation`
+    stops brighter; the stops applied stay in [min_ev, max_ev]; adapt_up / adapt_down are the per-frame rates (1 = at
+    once) towards a brighter / a darker film; window (x0, y0, x1, y1), half open, None = the whole film."""
+
+    low_cut: float = 0.05
+    high_cut: float = 0.02
+    key: float = 0.18
+    compensation: float = 0.0
+    min_ev: float = -8.0
+    max_ev: float = 8.0
+    adapt_up: float = 1.0
+    adapt_down: float = 1.0
+    window: tuple = None
+
+    def desc(self, res):
+        w = (0, 0, int(res[0]), int(res[1])) if self.window is None else tuple(int(v) for v in self.window)
+        if len(w) != 4 or min(w) < 0 or max(w) > 65535:
+            raise ValueError("window is (x0, y0, x1, y1) in pixels")
+        ev_bias = float(np.log2(self.key)) + float(self.compensation)
+        return abi.ExposureDesc(int(round(self.low_cut * 65536)), int(round(self.high_cut * 65536)), ev_bias, self.min_ev, self.max_ev, self.adapt_up, self.adapt_down, (C.c_uint16 * 4)(*w))
+
+
+ExposureState = abi.ExposureState
+
+
+def _window(window):
+    if window is None:
+        return None
+    w = tuple(int(v) for v in window)
+    if len(w) != 4 or min(w) < 0 or max(w) > 65535:
+        raise ValueError("window is (x0, y0, x1, y1) in pixels")
+    return (C.c_uint16 * 4)(*w)
+
+
+def film_histogram(film, tile_dim, samples=None, window=None, ctx=None):
+    """yk_film_histogram: the meter's 256 luminance bins of an (h, w, 3) float32 film (uint32) and the (skipped, below,
+    above) counts, by the rule of csrc/yk_exposure.h.  ctx None = the host instance."""
+    film, w, h = _film(film)
+    samples = _tone_map_args((w, h), ToneMapType.Raw, tile_dim, samples)
+    bins = np.zeros(256, dtype=np.uint32)
+    sba = np.zeros(3, dtype=np.uint32)
+    c = ctx.h if ctx else None
+    check(lib().yk_film_histogram(c, _p(film), w, h, int(tile_dim), _p(samples), _window(window), _p(bins), _p(sba)), c)
+    return bins, tuple(int(v) for v in sba)
+
+
+def meter_exposure(film, tile_dim, params=None, samples=None, prev=None, ctx=None):
+    """yk_exposure_meter: the ExposureState of an (h, w, 3) float32 film under `params` (None = ExposureParams()), after
+    `prev` (an ExposureState, None = no history).  ctx None = the host instance."""
+    film, w, h = _film(film)
+    samples = _tone_map_args((w, h), ToneMapType.Raw, tile_dim, samples)
+    d = (params or ExposureParams()).desc((w, h))
+    out = ExposureState()
+    c = ctx.h if ctx else None
+    check(lib().yk_exposure_meter(c, C.byref(d), _p(film), w, h, int(tile_dim), _p(samples), None if prev is None else C.byref(prev), C.byref(out)), c)
+    return out
+
+
+def _auto_exposure(film, tone_map, auto_exposure, tile_dim, samples, ctx):
+    """The metered descriptor of write_output / write_preview: auto_exposure is True or an ExposureParams."""
+    if not auto_exposure:
+        return tone_map
+    params = ExposureParams() if auto_exposure is True else auto_exposure
+    return _metered(tone_map, meter_exposure(film, tile_dim, params, samples, None, ctx))
 
 
 # --------------------------------------------------------------------------- denoise
@@ -660,19 +742,23 @@ def _denoise_for_output(film, denoise_params, guides, tile_dim, samples, ctx, al
     return denoise(film, guides, denoise_params, tile_dim, samples, ctx, albedo, variance), None
 
 
-def write_output(path, film, tone_map=None, settings=None, samples=None, ctx=None, denoise=None, guides=None, albedo=None, variance=None):
+def write_output(path, film, tone_map=None, settings=None, samples=None, ctx=None, denoise=None, guides=None, albedo=None, variance=None, auto_exposure=None):
     """The Finished branch of app/headless.rs:62-84: Raw writes the film as it is, anything else writes the tone-mapped
     film (a Heatmap without bounds finds them first).  tone_map None = ToneMapType.default(); settings None = a film of the
     array's size with the default tile_dim.  denoise (a DenoiseParams) with guides: the film is denoised first; with albedo
     (surface_albedo's records) too: by the demodulated filter; with a VarianceParams and variance (variance()'s image): by
-    the variance-guided filter."""
+    the variance-guided filter.  auto_exposure (True or an ExposureParams, Filmic only): the film about to be tone-mapped
+    — after the denoise — is metered (meter_exposure) and the exposure is the tone map's times the meter's."""
     film = np.ascontiguousarray(film, dtype=np.float32)
     tone_map = ToneMapType.default() if tone_map is None else tone_map
     settings = settings or FilmSettings(res=(film.shape[1], film.shape[0]))
     film, samples = _denoise_for_output(film, denoise, guides, film_tile_dim(settings), samples, ctx, albedo, variance)
     if tone_map.kind == abi.TONE_MAP_RAW:
+        if auto_exposure:
+            raise ValueError("auto_exposure needs the Filmic tone map: the others have no exposure")
         write_exr(path, film)
         return
+    tone_map = _auto_exposure(film, tone_map, auto_exposure, film_tile_dim(settings), samples, ctx)
     write_exr(path, _apply_tone_map(film, tone_map, film_tile_dim(settings), samples, ctx, None))
 
 
@@ -777,18 +863,21 @@ def write_png(path, pixels):
     check(lib().yk_write_png(str(path).encode(), pixels.shape[1], pixels.shape[0], pixels.shape[2], _p(pixels)))
 
 
-def write_preview(path, film, tone_map=None, settings=None, samples=None, window=None, ctx=None, denoise=None, guides=None, albedo=None, variance=None):
+def write_preview(path, film, tone_map=None, settings=None, samples=None, window=None, ctx=None, denoise=None, guides=None, albedo=None, variance=None, auto_exposure=None):
     """What the window shows, as a PNG: the denoiser when `denoise` (a DenoiseParams) and `guides` are given (demodulated
     by `albedo`, surface_albedo's records, when that is given too; variance-guided when `denoise` is a VarianceParams and
     `variance` its image), the tone map
     (as write_output: None = ToneMapType.default(), Raw = none), then present into `window` (default: the film's size) as
-    an sRGB back buffer stores it (encode 2), then write_png."""
+    an sRGB back buffer stores it (encode 2), then write_png.  auto_exposure: as write_output's."""
     film = np.ascontiguousarray(film, dtype=np.float32)
     tone_map = ToneMapType.default() if tone_map is None else tone_map
     settings = settings or FilmSettings(res=(film.shape[1], film.shape[0]))
     film, samples = _denoise_for_output(film, denoise, guides, film_tile_dim(settings), samples, ctx, albedo, variance)
     if tone_map.kind != abi.TONE_MAP_RAW:
+        tone_map = _auto_exposure(film, tone_map, auto_exposure, film_tile_dim(settings), samples, ctx)
         film = _apply_tone_map(film, tone_map, film_tile_dim(settings), samples, ctx, None)
+    elif auto_exposure:
+        raise ValueError("auto_exposure needs the Filmic tone map: the others have no exposure")
     window = (film.shape[1], film.shape[0]) if window is None else window
     write_png(path, present(film, window, abi.PRESENT_ENCODE_SRGB, "rgba8", ctx))
 
@@ -968,11 +1057,24 @@ class Context:
         """yk_context_interrupt: stop what the context has enqueued (any thread)."""
         check(lib().yk_context_interrupt(self.h))
 
-    def tone_map_device(self, d_film_ptr, res, tile_dim, tone_map, samples, d_out_ptr, stream=None):
+    def tone_map_device(self, d_film_ptr, res, tile_dim, tone_map, samples, d_out_ptr, stream=None, exposure_state=None):
         """yk_tone_map_device: device film -> device out, enqueued on `stream` (default: the context's) without waiting;
-        `samples` is a host table (or None), copied before the call returns."""
+        `samples` is a host table (or None), copied before the call returns.  exposure_state: the device pointer of a
+        yk_exposure_state (meter_exposure_device's output) — yk_tone_map_metered_device, Filmic only: the exposure is the
+        descriptor's times the record's, read on the device when the kernel runs."""
         samples = _tone_map_args(res, tone_map, tile_dim, samples)
+        if exposure_state is not None:
+            check(lib().yk_tone_map_metered_device(self.h, C.byref(tone_map), _vp(exposure_state), _vp(d_film_ptr), res[0], res[1], int(tile_dim), _p(samples), _vp(d_out_ptr), _vp(stream)), self.h)
+            return
         check(lib().yk_tone_map_device(self.h, C.byref(tone_map), _vp(d_film_ptr), res[0], res[1], int(tile_dim), _p(samples), _vp(d_out_ptr), _vp(stream)), self.h)
+
+    def meter_exposure_device(self, d_film_ptr, res, tile_dim, params, samples, d_prev_ptr, d_out_state_ptr, stream=None):
+        """yk_exposure_meter_device: the device film's yk_exposure_state (32 bytes, 4-byte aligned) into device memory,
+        after the record at d_prev_ptr (None = no history; may be d_out_state_ptr), enqueued on `stream` (default: the
+        context's) without waiting.  params None = ExposureParams(); `samples` is a host table (or None)."""
+        samples = _tone_map_args(res, ToneMapType.Raw, tile_dim, samples)
+        d = (params or ExposureParams()).desc(res)
+        check(lib().yk_exposure_meter_device(self.h, C.byref(d), _vp(d_film_ptr), res[0], res[1], int(tile_dim), _p(samples), _vp(d_prev_ptr), _vp(d_out_state_ptr), _vp(stream)), self.h)
 
     def draw_overlay_device(self, d_film_ptr, res, world_to_clip, d_lines_ptr=None, n_lines=0, d_boxes_ptr=None, n_boxes=0, stream=None):
         """yk_overlay_draw_device: n_lines yk_overlay_line records and n_boxes boxes of six floats, both on the device,

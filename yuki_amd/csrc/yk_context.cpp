@@ -127,6 +127,8 @@ void yk_context_destroy(yk_context* ctx) {
     ctx->adaptive.rank.release();
     ctx->adaptive.tile_count.release();
     ctx->albedo_mean.ids_band.release();
+    ctx->exposure.slot.release();
+    ctx->exposure.samples.release();
     if (ctx->tonemap.staging) (void)hipHostFree(ctx->tonemap.staging);
     if (ctx->tonemap.staged) (void)hipEventDestroy(ctx->tonemap.staged);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
@@ -202,6 +204,8 @@ yk_status yk_context_set_option(yk_context* ctx, const char* key, int64_t value)
     } else if (k == "albedo_mean_band_rows") {
         if (value < 0 || value > 65535) return YK_ERR_INVALID_ARGUMENT;
         ctx->albedo_mean.band_rows = value;
+    } else if (k == "exposure_wave_combine") {
+        ctx->exposure.wave_combine = value != 0;
     } else if (k == "update_top_block") {
         ctx->update_top_block = value != 0;
     } else if (k == "time_kernels") {

@@ -162,6 +162,12 @@ struct yk_context {
         DevBuf ids_band;        // YK_ALBEDO_MEAN_SCRATCH bytes from the first call on; more only for a band that needs more
         int64_t band_rows = 0;  // "albedo_mean_band_rows": output rows per band; 0 = as many as fit the scratch budget
     } albedo_mean;
+    // the exposure meter's buffers (yk_exposure.hip), grown on first use
+    struct ExposureState {
+        DevBuf slot;     // EX_SUB_SLOTS x EX_SLOT_WORDS u32: partial histograms and side counts, zeroed on the stream before every pass
+        DevBuf samples;  // the sample table on the device (staged through the tone map's pinned copy)
+        int64_t wave_combine = 1;  // "exposure_wave_combine": a wave whose lanes all hit one bin adds once
+    } exposure;
     // every entry point that touches the context's buffers or streams holds this: calls on one
     // context from several host threads (the reference's tile workers) are serialised
     std::recursive_mutex mu;

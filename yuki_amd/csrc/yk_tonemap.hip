@@ -1,5 +1,5 @@
 // yk_tonemap.hip — the tone map of the film (app/renderpasses/tonemap.rs) on gfx950, behind yk_tone_map, yk_tone_map_device and
-// yk_film_min_max; the per-pixel arithmetic is yk_tonemap.h's, whose host instance these entry points run without a context.
+// yk_tone_map_metered_device and yk_film_min_max; the per-pixel arithmetic is yk_tonemap.h's, whose host instance these entry points run without a context.
 //
 // Two memory-bound passes over a row-major RGB film (12 bytes a pixel):
 //   - k_tone_map: film -> out (out may be the film).  A lane maps 4 pixels through three 16-byte loads and three 16-byte
@@ -29,7 +29,10 @@ struct TmArgs {
     uint32_t kind, channel;
     float exposure;
     float lo, hi;              // Heatmap bounds given by the caller ...
-    const float* bounds;       // ... or found on the device (bounds[0], bounds[1]); nullptr = use lo / hi
+    union {
+        const float* bounds;              // ... or found on the device (bounds[0], bounds[1]); nullptr = use lo / hi
+        const yk_exposure_state* state;   // k_tone_map<true> (Filmic, which has no bounds): the meter's record
+    };
     const uint32_t* samples;   // Filmic: Film.samples in FilmTile.index order, or nullptr
     uint32_t res_x, tile_dim, x_tile_count;
 };
@@ -48,10 +51,13 @@ __device__ __forceinline__ void tm_pixel(const TmArgs& a, float lo, float hi, ui
 }
 
 // film and out are deliberately not __restrict__: out == film (in place) is allowed; each lane reads its pixels before it
-// writes them and touches no other lane's.
-__global__ __launch_bounds__(TM_BLOCK) void k_tone_map(const float* film, float* out, uint32_t n_px, int vec, TmArgs a) {
+// writes them and touches no other lane's.  METERED (Filmic only): the exposure is a.exposure times the exposure of the
+// meter's record (yk_exposure.h), read here once per lane as the Heatmap reads its bounds.  The record's pointer shares the
+// bounds' place in TmArgs, so the unmetered instance keeps the kernel arguments and the code it had before there was a meter.
+template <bool METERED> __global__ __launch_bounds__(TM_BLOCK) void k_tone_map(const float* film, float* out, uint32_t n_px, int vec, TmArgs a) {
+    if (METERED) a.exposure = a.exposure * a.state->exposure;
     float lo = a.lo, hi = a.hi;
-    if (a.bounds) {
+    if (!METERED && a.bounds) {
         lo = a.bounds[0];
         hi = a.bounds[1];
     }
@@ -172,7 +178,7 @@ namespace {
 
 // The device passes on `st`; a Heatmap without bounds leaves the bounds it found in the context's slot (tm.bounds).
 yk_status enqueue(yk_context* ctx, hipStream_t st, const yk_tone_map_desc* d, const float* film, uint16_t res_x, uint16_t res_y, uint16_t tile_dim,
-                  const uint32_t* samples, float* out) {
+                  const uint32_t* samples, float* out, const yk_exposure_state* d_state = nullptr) {
     const uint32_t n_px = (uint32_t)res_x * res_y;
     const bool vec = aligned16(film) && aligned16(out);
     auto& tm = ctx->tonemap;
@@ -199,7 +205,12 @@ yk_status enqueue(yk_context* ctx, hipStream_t st, const yk_tone_map_desc* d, co
         hipLaunchKernelGGL(k_min_max_final, dim3(1), dim3(TM_BLOCK), 0, st, tm.partials.as<const float2>(), g, tm.bounds.as<float>());
         a.bounds = tm.bounds.as<const float>();
     }
-    hipLaunchKernelGGL(k_tone_map, dim3(tm_grid(n_px, vec)), dim3(TM_BLOCK), 0, st, film, out, n_px, vec ? 1 : 0, a);
+    if (d_state) {
+        a.state = d_state;
+        hipLaunchKernelGGL(k_tone_map<true>, dim3(tm_grid(n_px, vec)), dim3(TM_BLOCK), 0, st, film, out, n_px, vec ? 1 : 0, a);
+    } else {
+        hipLaunchKernelGGL(k_tone_map<false>, dim3(tm_grid(n_px, vec)), dim3(TM_BLOCK), 0, st, film, out, n_px, vec ? 1 : 0, a);
+    }
     HIP_TRY(ctx, hipGetLastError());
     return YK_OK;
 }
@@ -267,6 +278,17 @@ yk_status yk_tone_map_device(yk_context* ctx, const yk_tone_map_desc* desc, cons
     YK_LOCK(ctx);
     if (check_call(desc, d_film_rgb, res_x, res_y, tile_dim, d_out_rgb) != YK_OK) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_tone_map_device: bad argument");
     return enqueue(ctx, device_call_stream(ctx, stream), desc, reinterpret_cast<const float*>(d_film_rgb), res_x, res_y, tile_dim, samples, reinterpret_cast<float*>(d_out_rgb));
+}
+
+yk_status yk_tone_map_metered_device(yk_context* ctx, const yk_tone_map_desc* desc, const void* d_state, const void* d_film_rgb, uint16_t res_x, uint16_t res_y, uint16_t tile_dim,
+                                     const uint32_t* samples, void* d_out_rgb, void* stream) {
+    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
+    YK_LOCK(ctx);
+    if (check_call(desc, d_film_rgb, res_x, res_y, tile_dim, d_out_rgb) != YK_OK || !d_state) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_tone_map_metered_device: bad argument");
+    if (desc->kind != YK_TONE_MAP_FILMIC) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_tone_map_metered_device: only the Filmic tone map has an exposure");
+    if (misaligned(4, d_state)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_tone_map_metered_device: d_state needs 4-byte alignment");
+    return enqueue(ctx, device_call_stream(ctx, stream), desc, reinterpret_cast<const float*>(d_film_rgb), res_x, res_y, tile_dim, samples, reinterpret_cast<float*>(d_out_rgb),
+                   reinterpret_cast<const yk_exposure_state*>(d_state));
 }
 
 yk_status yk_film_min_max(yk_context* ctx, const float* film_rgb, uint16_t res_x, uint16_t res_y, uint32_t channel, float out_min_max[2]) try {
