@@ -106,13 +106,13 @@ inline Sorter& sorter() {
 
 }  // namespace yk_exp
 
-// Expanded inside run_bounces (yk_render.cpp) after launch_shade of bounce b: uses its locals ctx, ws, st, bc, b, prm, pn, ds, cur.
+// Expanded inside run_bounces (yk_render.cpp) after launch_shade of bounce b: uses its locals ctx, ws, st, q, b, prm, pn, ds, cur.
 #define YK_SORT_AFTER_SHADE \
         if (yk_exp::sorter().bounces > 0) { /* order the queues k_shade just wrote (synchronises: timing experiment) */ \
             yk_exp::Sorter& S = yk_exp::sorter(); \
             unsigned h[YK_CTRL_STRIDE + 1]; \
             (void)hipStreamSynchronize(st); \
-            (void)hipMemcpy(h, bc, sizeof(h), hipMemcpyDeviceToHost); \
+            (void)hipMemcpy(h, q.count, sizeof(h), hipMemcpyDeviceToHost); /* the bounce's words of the control block */ \
             const unsigned n_next = h[YK_CTRL_STRIDE], n_sh = h[YK_CTRL_SHQ]; \
             float ms_paths = 0.0f, ms_sh = 0.0f; \
             if ((int)(b + 1) <= S.bounces && b + 1 < prm.max_depth && n_next > 1) { \
@@ -144,6 +144,7 @@ inline Sorter& sorter() {
                 std::swap(ws.shO, S.shO); \
                 std::swap(ws.shD, S.shD); \
                 std::swap(ws.shq, S.shq); \
+                q = bounce_queues(ws, b); /* the area queue's buffers changed */ \
             } \
             std::fprintf(stderr, "  sort after shade %u: next queue %u rays %.3f ms | area-light shadow queue %u rays %.3f ms\n", b, n_next, ms_paths, n_sh, ms_sh); \
         }

@@ -18,7 +18,9 @@
 #include "yk_albedo.h"
 #include "yk_film_call.h"
 #include "yk_film_tile.h"
+#include "yk_path_state.h"
 #include "yk_staging.h"
+#include "yk_wave.h"
 
 namespace {
 
@@ -53,7 +55,7 @@ __global__ void k_ids_band(DevScene sc, PathBuffers cur, const int* hit_tri, uin
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const float4 rd = cur.rayD[i];
-    const uint32_t xy = pixel_xy[__float_as_uint(rd.w)];
+    const uint32_t xy = pixel_xy[path_sample_id(rd)];
     const uint32_t yb = (xy >> 16) - row0, xb = xy & 0xffffu;
     if (yb >= rows || xb >= res_x) return;  // also a row above row0: the difference wraps
     const size_t px = (size_t)yb * res_x + xb;
@@ -62,7 +64,7 @@ __global__ void k_ids_band(DevScene sc, PathBuffers cur, const int* hit_tri, uin
     if (tri >= 0) {
         float t = 0.0f;
         const float4 ro = cur.rayO[i];
-        (void)hit_surface_prim(sc, (uint32_t)tri & YK_HIT_PRIM_MASK, V3{ro.x, ro.y, ro.z}, V3{rd.x, rd.y, rd.z}, sc.texels != nullptr, &t, &id);
+        (void)hit_surface_prim(sc, (uint32_t)tri & YK_HIT_PRIM_MASK, f4_xyz(ro), f4_xyz(rd), sc.texels != nullptr, &t, &id);
     }
     ids[px] = id;
 }

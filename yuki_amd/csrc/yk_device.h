@@ -3,14 +3,8 @@
 // HBM layout (all 16-byte records so every lane moves one dwordx4 and a wave one
 // contiguous KiB; "SoA of float4"):
 //
-//   path state, ping-pong (compacted every bounce by `shade`):
-//     rayO[i] = (o.x, o.y, o.z, bits(flags))        flags: bounces | specular<<8
-//     rayD[i] = (d.x, d.y, d.z, bits(sample_id))    sample_id = index into sample_buf
-//     thru[i] = (beta.r, beta.g, beta.b, bits(sampler dimension))
-//     rngs[i] = (state.lo, state.hi, inc.lo, inc.hi)          PCG32 stream of the pixel
-//     (camera bounce of a Path render traced by the packet kernel: rayO and thru are NOT stored — one origin for all,
-//      throughput one; see YK_CTRL_CAM_O)
-//   per bounce, not carried:
+//   path state, ping-pong (compacted every bounce by `shade`): rayO, rayD, thru, rngs — yk_path_state.h
+//   per bounce, not carried (BounceQueues below):
 //     hit[i]                       source triangle or -1             (trace -> shade)
 //     pend[i] = (rgb, kind << 29 | sample slot in the batch)  emission / background term   (shade -> accumulate)
 //     shO/shD/shC[i*n_lights+l]    NEE shadow ray + its contribution (shade -> shadow -> accumulate)
@@ -174,6 +168,30 @@ struct PathBuffers {
 #define YK_CTRL_SHQ2 2  // shadow rays towards point / spot / distant lights (one target: coherent)
 #define YK_CTRL_HEAD 3  // + {0: closest, 1: any, 2: any (delta queue)}
 #define YK_CTRL_MAX_DEPTH ((YK_CTRL_WORDS - 8) / YK_CTRL_STRIDE - 1)
+
+// One shadow-ray queue of a bounce: dense rays (O = (origin, t_max), D = (direction, bits(area light))), the verdict byte
+// each belongs to, the queue's length and the work-queue head of the any-hit launch that drains it.
+struct ShadowQueue {
+    float4* O;
+    float4* D;
+    unsigned* slot;
+    unsigned* count;
+    unsigned* head;
+};
+// Everything one bounce hands from kernel to kernel (built in one place: bounce_queues, yk_render.cpp).  Shadow rays go to
+// one of two queues: rays towards an area light leave a surface patch in scattered directions, rays towards a point /
+// spot / distant light converge on one target and suit the wave-packet any-hit kernel (`delta`, used when the bounce
+// splits them).
+struct BounceQueues {
+    int* hit;
+    float4* pend;
+    float4* shC;
+    unsigned char* vis;
+    ShadowQueue area, delta;
+    unsigned* count;         // paths entering the bounce
+    unsigned* next_count;    // ... and the next one: k_shade's survivors
+    unsigned* closest_head;  // work-queue head of the bounce's closest-hit launch
+};
 
 // Interruption (integrators/mod.rs:153: the reference polls its predicate once per pixel sample).  Two words: `host` lives in
 // pinned host memory and is written by the host thread that polls the predicate; `dev` is a word in device memory that EVERY

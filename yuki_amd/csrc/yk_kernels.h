@@ -1,4 +1,4 @@
-// yk_kernels.h — host-callable launchers of the gfx950 kernels (yk_kernels.hip)
+// yk_kernels.h — host-callable launchers of the gfx950 kernels (yk_kernels.hip, yk_trace.hip, yk_packet.hip, yk_stage_kernels.hip)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,8 +15,9 @@ unsigned packet_blocks_per_cu();
 // rayO == nullptr: every ray starts at *lean_origin (the lean camera bounce, yk_device.h)
 void launch_trace_closest_packet(hipStream_t s, unsigned grid, const DevScene& sc, const float4* rayO, const float4* rayD, const unsigned* count_ptr,
                                  unsigned* head, int* hit_tri, unsigned long long* ray_counter, const float4* lean_origin = nullptr, CancelRef cancel = CancelRef{nullptr, nullptr});
-void launch_trace_any_packet(hipStream_t s, unsigned grid, const DevScene& sc, const float4* shO, const float4* shD, const unsigned* slot_of,
-                             const unsigned* count_ptr, unsigned* head, unsigned char* vis, unsigned long long* shadow_counter, CancelRef cancel = CancelRef{nullptr, nullptr});
+// q.slot == nullptr (stage entry points): ray k's verdict goes to vis[k]
+void launch_trace_any_packet(hipStream_t s, unsigned grid, const DevScene& sc, const ShadowQueue& q, unsigned char* vis, unsigned long long* shadow_counter,
+                             CancelRef cancel = CancelRef{nullptr, nullptr});
 unsigned trace_blocks_per_cu();
 
 void launch_pixel_table(hipStream_t s, const yk_tile* tiles, const uint32_t* tile_offset, uint32_t n_tiles, uint32_t n_pixels, uint32_t* pixel_xy,
@@ -37,14 +38,15 @@ unsigned whitted_max_depth();
 void launch_path_debug(hipStream_t s, unsigned grid, const DevScene& sc, const RenderParams& prm, const uint32_t* pixel_xy, const uint32_t* sample_index_tab,
                        PathBuffers cur, uint32_t n, float4* sample_buf, uint32_t* out_counts, float4* out_rays, unsigned ray_cap, uint32_t* out_n_rays,
                        float min_len, uint2* spill, unsigned spill_stride, unsigned* ctrl);
-void launch_trace_any(hipStream_t s, unsigned grid, const DevScene& sc, const float4* shO, const float4* shD, const unsigned* slot_of,
-                      const unsigned* count_ptr, unsigned* head, unsigned char* vis, uint2* spill, unsigned spill_stride, unsigned* ctrl,
-                      unsigned long long* shadow_counter, const unsigned* cancel_host = nullptr);
+void launch_trace_any(hipStream_t s, unsigned grid, const DevScene& sc, const ShadowQueue& q, unsigned char* vis, uint2* spill, unsigned spill_stride,
+                      unsigned* ctrl, unsigned long long* shadow_counter, const unsigned* cancel_host = nullptr);
+// one bounce's shade and accumulate over its queues (yk_device.h, BounceQueues).  split_delta: shadow rays towards point /
+// spot / distant lights go to q.delta; reorder: windows sorted by material kind; block_slots: resident blocks on the device
 void launch_shade(hipStream_t s, unsigned grid, const DevScene& sc, const RenderParams& prm, const uint32_t* pixel_xy, const uint32_t* sample_index_tab,
-                  PathBuffers cur, PathBuffers nxt, const int* hit_tri, float4* pend, float4* shO, float4* shD, float4* shC, unsigned char* vis,
-                  unsigned* shq, float4* shO2, float4* shD2, unsigned* shq2, unsigned* bc, unsigned split_delta, unsigned reorder, unsigned block_slots, unsigned sid_base, const float4* lean_origin);
-void launch_accumulate(hipStream_t s, unsigned grid, const RenderParams& prm, PathBuffers cur, const float4* pend, const float4* shC,
-                       const unsigned char* vis, unsigned nl, float4* sample_buf, const unsigned* bc, unsigned first, unsigned sid_base);
+                  PathBuffers cur, PathBuffers nxt, const BounceQueues& q, unsigned split_delta, unsigned reorder, unsigned block_slots, unsigned sid_base,
+                  const float4* lean_origin);
+void launch_accumulate(hipStream_t s, unsigned grid, const RenderParams& prm, PathBuffers cur, const BounceQueues& q, unsigned nl, float4* sample_buf,
+                       unsigned first, unsigned sid_base);
 void launch_resolve(hipStream_t s, const float4* sample_buf, uint32_t n_pixels, uint32_t spp, float* out_rgb);
 void launch_resolve_passes(hipStream_t s, const float4* sample_buf, uint32_t n_pixels, uint32_t n_passes, float* out_rgb, size_t pass_stride);
 void launch_film_scatter(hipStream_t s, const uint32_t* pixel_xy, uint32_t n_pixels, const float* tile_rgb, uint32_t res_x, float* film_rgb, int accumulate,
@@ -59,6 +61,7 @@ void launch_guides_ids(hipStream_t s, const DevScene& sc, PathBuffers cur, const
 // into film_sum and stats at its pixel; the entries are unique pixels inside the res_x-wide film
 void launch_ad_fold_samples(hipStream_t s, const uint32_t* pixel_xy, uint32_t n, const float4* sample_buf, uint32_t n_passes, uint32_t res_x, float* film_sum,
                             void* stats);
+// kernels of the per-stage entry points (yk_stage_kernels.hip)
 void launch_device_math(hipStream_t s, int fn, size_t n, const float* a, const float* b, float* out);
 void launch_sampler_sequence(hipStream_t s, const SamplerCfg& cfg, uint32_t px, uint32_t py, uint32_t sample_index, const uint8_t* dims, size_t n_draws,
                              float* out);

@@ -26,6 +26,7 @@
 #include "yk_device.h"
 #include "yk_geom.h"
 #include "yk_kernels.h"
+#include "yk_path_state.h"
 #include "yk_traverse.h"
 #include "yk_wave.h"
 
@@ -158,7 +159,7 @@ __global__ __launch_bounds__(YK_PKT_BLOCK, 8) void k_trace_closest_packet(DevSce
         const unsigned idx = base + lane_id();
         const bool valid = idx < n;
         // rayO == null: the lean camera bounce, all rays start at the camera's origin (yk_device.h, YK_CTRL_CAM_O)
-        const float4 ro = !valid ? make_float4(0, 0, 0, 0) : (rayO ? rayO[idx] : *lean_origin), rd = valid ? rayD[idx] : make_float4(0, 0, 1, 0);
+        const float4 ro = !valid ? make_float4(0, 0, 0, 0) : path_origin_word(rayO, idx, lean_origin), rd = valid ? rayD[idx] : make_float4(0, 0, 1, 0);
         TraceRay r = ray_setup(f4_xyz(ro), f4_xyz(rd), __builtin_inff());
         const bool alive = valid && root_hit(sc, r);
         int best = -1;
@@ -276,8 +277,11 @@ void launch_trace_closest_packet(hipStream_t s, unsigned grid, const DevScene& s
     else
         hipLaunchKernelGGL((k_trace_closest_packet<false>), dim3(grid), dim3(YK_PKT_BLOCK), 0, s, sc, rayO, rayD, count_ptr, head, hit_tri, ray_counter, lean_origin, cancel);
 }
-void launch_trace_any_packet(hipStream_t s, unsigned grid, const DevScene& sc, const float4* shO, const float4* shD, const unsigned* slot_of,
-                             const unsigned* count_ptr, unsigned* head, unsigned char* vis, unsigned long long* shadow_counter, CancelRef cancel) {
+void launch_trace_any_packet(hipStream_t s, unsigned grid, const DevScene& sc, const ShadowQueue& q, unsigned char* vis, unsigned long long* shadow_counter,
+                             CancelRef cancel) {
+    const float4 *shO = q.O, *shD = q.D;
+    const unsigned *slot_of = q.slot, *count_ptr = q.count;
+    unsigned* head = q.head;
     if (sc.spheres)
         hipLaunchKernelGGL((k_trace_any_packet<true>), dim3(grid), dim3(YK_PKT_BLOCK), 0, s, sc, shO, shD, slot_of, count_ptr, head, vis, shadow_counter, cancel);
     else

@@ -94,6 +94,23 @@ PathBuffers path_buffers(WorkSet& ws, int which) {
     return p;
 }
 
+// The queues of bounce b of the batch in `ws` (yk_device.h: BounceQueues, and the control block's words: the only place
+// that knows which word belongs to which queue).
+static BounceQueues bounce_queues(WorkSet& ws, unsigned b) {
+    unsigned* bc = ws.ctrl.as<unsigned>() + YK_CTRL_BOUNCE(b);  // this bounce's counters and queue heads, zeroed with the batch
+    BounceQueues q;
+    q.hit = ws.hit.as<int>();
+    q.pend = ws.pend.as<float4>();
+    q.shC = ws.shC.as<float4>();
+    q.vis = ws.vis.as<unsigned char>();
+    q.area = ShadowQueue{ws.shO.as<float4>(), ws.shD.as<float4>(), ws.shq.as<unsigned>(), bc + YK_CTRL_SHQ, bc + YK_CTRL_HEAD + 1};
+    q.delta = ShadowQueue{ws.shO2.as<float4>(), ws.shD2.as<float4>(), ws.shq2.as<unsigned>(), bc + YK_CTRL_SHQ2, bc + YK_CTRL_HEAD + 2};
+    q.count = bc;
+    q.next_count = bc + YK_CTRL_STRIDE;
+    q.closest_head = bc + YK_CTRL_HEAD;
+    return q;
+}
+
 yk_status make_params(yk_context* ctx, const yk_sampler_desc* smp, const yk_integrator_desc* integ, RenderParams& prm) {
     if (!smp || !integ) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null sampler/integrator");
     std::memset(&prm, 0, sizeof(prm));
@@ -171,20 +188,19 @@ void run_bounces(yk_context* ctx, WorkSet& ws, hipStream_t st, const yk_scene* s
         // otherwise everything goes to the first queue and one launch traces it
         const bool split = packet_shadow && scene->n_lights > scene->n_delta_lights;
         const bool all_delta = packet_shadow && !split;  // no area lights: the single queue is all coherent
-        unsigned* bc = ctrl + YK_CTRL_BOUNCE(b);  // this bounce's counters and queue heads, zeroed with the batch
+        BounceQueues q = bounce_queues(ws, b);
         int e = kt.begin(st);
         if (packet)
-            launch_trace_closest_packet(st, pg, ds, lean_origin ? nullptr : pc.rayO, pc.rayD, bc, bc + YK_CTRL_HEAD, ws.hit.as<int>(), counters, lean_origin, prm.cancel);
+            launch_trace_closest_packet(st, pg, ds, lean_origin ? nullptr : pc.rayO, pc.rayD, q.count, q.closest_head, q.hit, counters, lean_origin, prm.cancel);
         else {
-            launch_trace_closest(st, tg, ds, pc.rayO, pc.rayD, nullptr, bc, bc + YK_CTRL_HEAD, ws.hit.as<int>(), nullptr, nullptr,
+            launch_trace_closest(st, tg, ds, pc.rayO, pc.rayD, nullptr, q.count, q.closest_head, q.hit, nullptr, nullptr,
                                  ws.spill.as<uint2>(), spill_stride, errblk, counters, prm.cancel.host);
         }
         kt.end(e, 0, st);
         if (overlap && b > 0) (void)hipStreamWaitEvent(st, ws.ev_acc, 0);
         e = kt.begin(st);
-        launch_shade(st, sg, ds, prm, pixel_xy, sample_index_tab, pc, pn, ws.hit.as<int>(), ws.pend.as<float4>(), ws.shO.as<float4>(),
-                     ws.shD.as<float4>(), ws.shC.as<float4>(), ws.vis.as<unsigned char>(), ws.shq.as<unsigned>(), ws.shO2.as<float4>(),
-                     ws.shD2.as<float4>(), ws.shq2.as<unsigned>(), bc, split ? 1u : 0u, (b > 0 && ctx->shade_reorder) ? 1u : 0u, 3u * (unsigned)ctx->n_cu, sid_base, lean_origin);
+        launch_shade(st, sg, ds, prm, pixel_xy, sample_index_tab, pc, pn, q, split ? 1u : 0u, (b > 0 && ctx->shade_reorder) ? 1u : 0u, 3u * (unsigned)ctx->n_cu,
+                     sid_base, lean_origin);
         kt.end(e, 2, st);
 #ifdef YK_EXPERIMENT_SORT  // order the queues k_shade just wrote (synchronises: timing experiment, tools/micro/ray_sort_experiment.h)
         YK_SORT_AFTER_SHADE
@@ -196,25 +212,22 @@ void run_bounces(yk_context* ctx, WorkSet& ws, hipStream_t st, const yk_scene* s
         e = kt.begin(sb);
         uint2* any_spill = (overlap ? ws.spill_side : ws.spill).as<uint2>();
         if (all_delta) {
-            launch_trace_any_packet(sb, pg_any, ds, ws.shO.as<float4>(), ws.shD.as<float4>(), ws.shq.as<unsigned>(), bc + YK_CTRL_SHQ,
-                                    bc + YK_CTRL_HEAD + 1, ws.vis.as<unsigned char>(), counters + 1, prm.cancel);
+            launch_trace_any_packet(sb, pg_any, ds, q.area, q.vis, counters + 1, prm.cancel);
         } else {
-            launch_trace_any(sb, tg_any, ds, ws.shO.as<float4>(), ws.shD.as<float4>(), ws.shq.as<unsigned>(), bc + YK_CTRL_SHQ,
-                             bc + YK_CTRL_HEAD + 1, ws.vis.as<unsigned char>(), any_spill, spill_stride, errblk, counters + 1, prm.cancel.host);
+            launch_trace_any(sb, tg_any, ds, q.area, q.vis, any_spill, spill_stride, errblk, counters + 1, prm.cancel.host);
             if (split && n_shadow_launches) ++*n_shadow_launches;
             if (split)  // rays converging on a point / spot / distant light: wave packets
-                launch_trace_any_packet(sb, pg_any, ds, ws.shO2.as<float4>(), ws.shD2.as<float4>(), ws.shq2.as<unsigned>(), bc + YK_CTRL_SHQ2,
-                                        bc + YK_CTRL_HEAD + 2, ws.vis.as<unsigned char>(), counters + 1, prm.cancel);
+                launch_trace_any_packet(sb, pg_any, ds, q.delta, q.vis, counters + 1, prm.cancel);
         }
         kt.end(e, 1, sb);
         if (n_shadow_launches) ++*n_shadow_launches;
-        launch_accumulate(sb, sg, prm, pc, ws.pend.as<float4>(), ws.shC.as<float4>(), ws.vis.as<unsigned char>(), ds.n_lights, sample_buf, bc, b == 0 ? 1u : 0u, sid_base);
+        launch_accumulate(sb, sg, prm, pc, q, ds.n_lights, sample_buf, b == 0 ? 1u : 0u, sid_base);
         if (overlap) (void)hipEventRecord(ws.ev_acc, sb);
         if (kt.on && std::getenv("YK_DEBUG_BOUNCES")) {  // per-bounce breakdown (synchronises; diagnostics only)
             unsigned h[YK_CTRL_STRIDE + 1];
             (void)hipStreamSynchronize(st);
             (void)hipStreamSynchronize(sb);
-            (void)hipMemcpy(h, bc, sizeof(h), hipMemcpyDeviceToHost);
+            (void)hipMemcpy(h, q.count, sizeof(h), hipMemcpyDeviceToHost);  // the bounce's words of the control block (yk_device.h)
             float tt = 0, ts = 0, th = 0;
             (void)hipEventElapsedTime(&tt, ctx->ev_pool[kt.spans[0].back().first], ctx->ev_pool[kt.spans[0].back().second]);
             (void)hipEventElapsedTime(&ts, ctx->ev_pool[kt.spans[1].back().first], ctx->ev_pool[kt.spans[1].back().second]);

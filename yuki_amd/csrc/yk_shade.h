@@ -9,6 +9,7 @@
 #pragma once
 #include "yk_device.h"
 #include "yk_geom.h"
+#include "yk_path_state.h"
 #include "yk_rng.h"
 
 namespace yk {
@@ -21,21 +22,17 @@ struct PathVertex {
     V3 wo;
 };
 
-// The sampler state a path carries in PathBuffers: the PCG32 stream (rngs[i]), the next dimension (bits of thru[i].w)
-// and the sample id (bits of rayD[i].w), whose pixel-table entry gives the pixel and the sample index.
-__device__ __forceinline__ SamplerState path_sampler(const RenderParams& prm, const uint32_t* pixel_xy, const uint32_t* sample_index_tab, uint4 rng,
-                                                     uint32_t dimension, uint32_t sid) {
-    SamplerState st;
-    st.rng.state = (u64)rng.x | ((u64)rng.y << 32);
-    st.rng.inc = (u64)rng.z | ((u64)rng.w << 32);
-    st.dimension = dimension;
-    uint32_t pix, ks;  // entry of the pixel table and sample within it (yk_device.h: RenderParams::spe)
-    split_sample_id(sid, prm.spe, pix, ks);
-    const uint32_t xy = pixel_xy[pix];
-    st.px = xy & 0xffffu;
-    st.py = xy >> 16;
-    st.sample_index = (sample_index_tab ? sample_index_tab[pix] : prm.sample_base) + ks;
-    return st;
+// what a lane without a hit carries through the steps: it never reads the vertex, the defaults keep its registers defined
+__device__ __forceinline__ PathVertex vertex_inert() {
+    PathVertex v;
+    v.sf.p = v.sf.n = v.sf.ns = v.sf.dpdus = v.sf.wo = V3{0, 0, 1};
+    v.sf.material = 0;
+    v.sf.area_light = -1;
+    v.sf.u = v.sf.v = 0.0f;
+    v.mat.kind = MK_BLACK;
+    v.fr.s = v.fr.t = v.fr.n = v.fr.ng = V3{0, 0, 1};
+    v.wo = V3{0, 0, 1};
+    return v;
 }
 
 // the rest of the vertex once v.sf holds the surface: material (with its texture), shading frame, wo
@@ -68,14 +65,15 @@ struct NeeSample {
     V3 so, sd;
     int al;  // the sampled area light (its own surface does not occlude, bvh.rs:269-280) or -1
 };
-// VisibilityTester::ray = p0.spawn_ray_to(p1), interaction.rs:44-59 (t_max 0.9999)
+// VisibilityTester::ray = p0.spawn_ray_to(p1), interaction.rs:44-59
+#define YK_SHADOW_T_MAX 0.9999f  // its t_max
 __device__ __forceinline__ void vertex_shadow_ray(const PathVertex& v, const LightSample& ls, V3& so, V3& sd) {
     V3 offset = v.sf.n * 0.001f;
     so = dot(ls.p1 - v.sf.p, v.sf.n) > 0.0f ? v.sf.p + offset : v.sf.p - offset;
     sd = ls.p1 - so;
 }
-template <bool RAY_ALWAYS = false>
-__device__ __forceinline__ NeeSample vertex_light(const DevScene& sc, const RenderParams& prm, SamplerState& st, unsigned l, const PathVertex& v) {
+// "no sample": the light does not contribute (also what a lane without a vertex stages: nothing)
+__device__ __forceinline__ NeeSample nee_none() {
     NeeSample r;
     r.want = false;
     r.has_ray = false;
@@ -83,6 +81,11 @@ __device__ __forceinline__ NeeSample vertex_light(const DevScene& sc, const Rend
     r.so = V3{0, 0, 0};
     r.sd = V3{0, 0, 1};
     r.al = -1;
+    return r;
+}
+template <bool RAY_ALWAYS = false>
+__device__ __forceinline__ NeeSample vertex_light(const DevScene& sc, const RenderParams& prm, SamplerState& st, unsigned l, const PathVertex& v) {
+    NeeSample r = nee_none();
     float ux, uy;
     sampler_get_2d(prm.sampler, st, ux, uy);
     LightSample ls = sample_light(sc.lights[l], (int)l, v.sf.p, ux, uy);
@@ -108,6 +111,12 @@ __device__ __forceinline__ NeeSample vertex_light(const DevScene& sc, const Rend
 // pend[i].w = kind << 29 | (sample slot - first slot of the batch); batches hold at most 2^29 paths (yk_context_set_option)
 #define YK_PEND_KIND_SHIFT 29
 #define YK_PEND_SID_MASK 0x1fffffffu
+// the sample's slot travels with the term (as its offset in the batch): k_accumulate reads no path state for it
+__device__ __forceinline__ float4 pend_pack(RGB term, unsigned kind, unsigned slot) {
+    return make_float4(term.r, term.g, term.b, __uint_as_float((kind << YK_PEND_KIND_SHIFT) | slot));
+}
+__device__ __forceinline__ unsigned pend_kind(float4 p) { return __float_as_uint(p.w) >> YK_PEND_KIND_SHIFT; }
+__device__ __forceinline__ unsigned pend_slot(float4 p) { return __float_as_uint(p.w) & YK_PEND_SID_MASK; }
 
 // path.rs:155-160: incoming_radiance += beta * scene.background; break
 __device__ __forceinline__ RGB vertex_miss_term(const DevScene& sc, RGB beta) { return beta * RGB{sc.background[0], sc.background[1], sc.background[2]}; }

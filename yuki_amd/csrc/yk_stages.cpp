@@ -161,12 +161,13 @@ yk_status yk_trace_any(yk_context* ctx, const yk_scene* scene, size_t n, const f
     HIP_TRY(ctx, hipMemcpyAsync(ctrl, &nn, 4, hipMemcpyHostToDevice, st));
     if (slot_of) HIP_TRY(ctx, hipMemsetAsync(ctx->ws[0].vis.p, 0, n, st));  // as k_shade leaves it: the kernels only mark occluded slots
     HIP_TRY(ctx, hipStreamSynchronize(st));
+    // the stage's queue: the packed rays, word 0 of the control block as their count (yk_device.h)
+    const ShadowQueue q{ctx->ws[0].shO.as<float4>(), ctx->ws[0].shD.as<float4>(), const_cast<unsigned*>(slot_of), ctrl, ctrl + YK_CTRL_HEADS};
     if (mode == 2)
-        launch_trace_any_packet(st, packet_grid(ctx), dev_scene_for(scene, n), ctx->ws[0].shO.as<float4>(), ctx->ws[0].shD.as<float4>(), slot_of, ctrl,
-                                ctrl + YK_CTRL_HEADS, ctx->ws[0].vis.as<unsigned char>(), nullptr);
+        launch_trace_any_packet(st, packet_grid(ctx), dev_scene_for(scene, n), q, ctx->ws[0].vis.as<unsigned char>(), nullptr);
     else
-        launch_trace_any(st, trace_grid(ctx), dev_scene_for(scene, n), ctx->ws[0].shO.as<float4>(), ctx->ws[0].shD.as<float4>(), slot_of, ctrl, ctrl + YK_CTRL_HEADS,
-                         ctx->ws[0].vis.as<unsigned char>(), ctx->ws[0].spill.as<uint2>(), trace_grid(ctx) * trace_block_size(), ctrl, nullptr);
+        launch_trace_any(st, trace_grid(ctx), dev_scene_for(scene, n), q, ctx->ws[0].vis.as<unsigned char>(), ctx->ws[0].spill.as<uint2>(),
+                         trace_grid(ctx) * trace_block_size(), ctrl, nullptr);
     HIP_TRY(ctx, hipGetLastError());
     std::vector<uint8_t> vis(slot_of ? n : 0);
     HIP_TRY(ctx, hipMemcpyAsync(slot_of ? vis.data() : out_hit, ctx->ws[0].vis.p, n, hipMemcpyDeviceToHost, st));

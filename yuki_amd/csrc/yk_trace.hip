@@ -614,10 +614,10 @@ __global__ __launch_bounds__(BLOCK) void k_whitted(DevScene sc, RenderParams prm
     unsigned long long n_rays = 0, n_shadow = 0;
     if (cancel_raised(prm.cancel)) n = 0;  // interrupted before this launch started (yk_device.h, CancelRef)
     for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
-        const float4 a = cur.rayO[i], b = cur.rayD[i], c = cur.thru[i];
-        V3 o = f4_xyz(a), d = f4_xyz(b);
-        const unsigned sid = __float_as_uint(b.w);
-        SamplerState st = path_sampler(prm, pixel_xy, sample_index_tab, cur.rngs[i], __float_as_uint(c.w), sid);
+        const PathState ps = path_load(cur, i);
+        V3 o = ps.o, d = ps.d;
+        const unsigned sid = ps.sid;
+        SamplerState st = path_sampler(prm, pixel_xy, sample_index_tab, ps);
         WhittedFrame frames[YK_WHITTED_MAX_DEPTH];
         int sp = 0;  // frames on the stack = depth of the call being evaluated
         bool is_specular = false;
@@ -758,11 +758,11 @@ __global__ __launch_bounds__(BLOCK) void k_path_debug(DevScene sc, RenderParams 
     unsigned* err = ctrl + YK_CTRL_ERR;
     if (cancel_raised(prm.cancel)) n = 0;  // interrupted before this launch started (yk_device.h, CancelRef)
     for (uint32_t i = blockIdx.x * BLOCK + threadIdx.x; i < n; i += gridDim.x * BLOCK) {
-        const float4 a = cur.rayO[i], b = cur.rayD[i], c = cur.thru[i];
-        V3 o = f4_xyz(a), d = f4_xyz(b);
-        const unsigned sid = __float_as_uint(b.w);
-        SamplerState st = path_sampler(prm, pixel_xy, sample_index_tab, cur.rngs[i], __float_as_uint(c.w), sid);
-        RGB L = RGB{0.0f, 0.0f, 0.0f}, beta = RGB{c.x, c.y, c.z};
+        const PathState ps = path_load(cur, i);
+        V3 o = ps.o, d = ps.d;
+        const unsigned sid = ps.sid;
+        SamplerState st = path_sampler(prm, pixel_xy, sample_index_tab, ps);
+        RGB L = RGB{0.0f, 0.0f, 0.0f}, beta = ps.beta;
         unsigned bounces = 0, n_closest = 0, k = 0, type = YK_RAY_DIRECT;
         bool specular_bounce = false, alive = prm.max_depth > 0;
         while (alive) {
@@ -784,8 +784,8 @@ __global__ __launch_bounds__(BLOCK) void k_path_debug(DevScene sc, RenderParams 
             RGB radiance = RGB{0.0f, 0.0f, 0.0f};
             for (unsigned l = 0; l < sc.n_lights; ++l) {
                 const NeeSample ne = vertex_light<true>(sc, prm, st, l, v);
-                if (ne.want || ne.has_ray) debug_ray_store(out_rays, i, ray_cap, k++, ne.so, ne.sd, 0.9999f, YK_RAY_SHADOW);
-                if (ne.want && !traverse_any(sc, ray_setup(ne.so, ne.sd, 0.9999f), ne.al, stk, err)) radiance = radiance + ne.contrib;
+                if (ne.want || ne.has_ray) debug_ray_store(out_rays, i, ray_cap, k++, ne.so, ne.sd, YK_SHADOW_T_MAX, YK_RAY_SHADOW);
+                if (ne.want && !traverse_any(sc, ray_setup(ne.so, ne.sd, YK_SHADOW_T_MAX), ne.al, stk, err)) radiance = radiance + ne.contrib;
             }
             const RGB beta_in = beta;  // vertex_accumulate takes the throughput the vertex was entered with
             const VertexEnd e = vertex_finish(sc, prm, st, v, beta, bounces, specular_bounce);
@@ -861,12 +861,11 @@ void launch_path_debug(hipStream_t s, unsigned grid, const DevScene& sc, const R
     hipLaunchKernelGGL((k_path_debug<TRACE_BLOCK, TRACE_LDS>), dim3(grid), dim3(TRACE_BLOCK), 0, s, sc, prm, pixel_xy, sample_index_tab, cur, n, sample_buf,
                        out_counts, out_rays, ray_cap, out_n_rays, min_len, spill, spill_stride, ctrl);
 }
-void launch_trace_any(hipStream_t s, unsigned grid, const DevScene& sc, const float4* shO, const float4* shD, const unsigned* slot_of,
-                      const unsigned* count_ptr, unsigned* head, unsigned char* vis, uint2* spill, unsigned spill_stride, unsigned* ctrl,
-                      unsigned long long* shadow_counter, const unsigned* cancel_host) {
+void launch_trace_any(hipStream_t s, unsigned grid, const DevScene& sc, const ShadowQueue& q, unsigned char* vis, uint2* spill, unsigned spill_stride,
+                      unsigned* ctrl, unsigned long long* shadow_counter, const unsigned* cancel_host) {
 #define YK_LAUNCH_ANY(SPH, WIDE)                                                                                                                       \
     hipLaunchKernelGGL((k_trace_any_pt<TRACE_BLOCK, TRACE_ANY_LDS, TRACE_PF_MIN, TRACE_START_MIN, TRACE_LEAF_MIN, TRACE_CHUNK, SPH, WIDE>), dim3(grid),     \
-                       dim3(TRACE_BLOCK), 0, s, sc, shO, shD, slot_of, count_ptr, head, vis, spill, spill_stride, ctrl, shadow_counter, cancel_host)
+                       dim3(TRACE_BLOCK), 0, s, sc, (const float4*)q.O, (const float4*)q.D, (const unsigned*)q.slot, (const unsigned*)q.count, q.head, vis, spill, spill_stride, ctrl, shadow_counter, cancel_host)
     if (sc.spheres) {
         if (sc.nodes4) YK_LAUNCH_ANY(true, true); else YK_LAUNCH_ANY(true, false);
     } else {
