@@ -356,6 +356,19 @@ pub struct yk_albedo {
     pub known: f32,
 }
 
+/// The largest factor of `yk_upsample` (= YK_ALBEDO_MEAN_MAX_S)
+pub const YK_UPSAMPLE_MAX_S: u32 = 8;
+
+/// The factor (1 ..= 8) and the normal and plane-distance stops of the guided upsample; +inf switches a stop off
+/// (yuki_amd/csrc/yk_upsample.h)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct yk_upsample_desc {
+    pub s: u32,
+    pub sigma_normal: f32,
+    pub sigma_plane: f32,
+}
+
 /// The target rectangle of ScaleOutput::draw in top-down window coordinates
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -599,6 +612,8 @@ extern "C" {
     pub fn yk_render_albedo_mean_device(ctx: *mut yk_context, scene: *const yk_scene, camera_ss: *const yk_camera, res_x: u16, res_y: u16, s: u32, d_out: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_denoise_albedo(ctx: *mut yk_context, desc: *const yk_denoise_desc, film_rgb: *const f32, guides: *const yk_guide, albedo: *const yk_albedo, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, out_rgb: *mut f32) -> yk_status;
     pub fn yk_denoise_albedo_device(ctx: *mut yk_context, desc: *const yk_denoise_desc, d_film_rgb: *const c_void, d_guides: *const c_void, d_albedo: *const c_void, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, d_out_rgb: *mut c_void, stream: *mut c_void) -> yk_status;
+    pub fn yk_upsample(ctx: *mut yk_context, desc: *const yk_upsample_desc, low_rgb: *const f32, low_guides: *const yk_guide, low_albedo: *const yk_albedo, low_res_x: u16, low_res_y: u16, tile_dim: u16, samples: *const u32, guides: *const yk_guide, albedo: *const yk_albedo, out_rgb: *mut f32, out_weight: *mut f32) -> yk_status;
+    pub fn yk_upsample_device(ctx: *mut yk_context, desc: *const yk_upsample_desc, d_low_rgb: *const c_void, d_low_guides: *const c_void, d_low_albedo: *const c_void, low_res_x: u16, low_res_y: u16, tile_dim: u16, samples: *const u32, d_guides: *const c_void, d_albedo: *const c_void, d_out_rgb: *mut c_void, d_out_weight: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_moments_blend(ctx: *mut yk_context, desc: *const yk_temporal_desc, film_rgb: *const f32, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, moments: *const yk_moments, out_moments: *mut yk_moments) -> yk_status;
     pub fn yk_moments_blend_device(ctx: *mut yk_context, desc: *const yk_temporal_desc, d_film_rgb: *const c_void, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, d_moments: *const c_void, d_out_moments: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_variance(ctx: *mut yk_context, desc: *const yk_variance_desc, moments: *const yk_moments, film_rgb: *const f32, guides: *const yk_guide, albedo: *const yk_albedo, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, out_variance: *mut f32) -> yk_status;

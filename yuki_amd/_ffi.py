@@ -194,6 +194,8 @@ SYMBOLS = {
     "yk_render_albedo_mean_device": (C.c_int, [vp, vp, C.POINTER(abi.CameraMatrices), C.c_uint16, C.c_uint16, C.c_uint32, vp, vp]),
     "yk_denoise_albedo": (C.c_int, [vp, C.POINTER(abi.DenoiseDesc), vp, vp, vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp]),
     "yk_denoise_albedo_device": (C.c_int, [vp, C.POINTER(abi.DenoiseDesc), vp, vp, vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp]),
+    "yk_upsample": (C.c_int, [vp, C.POINTER(abi.UpsampleDesc), vp, vp, vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp, vp, vp]),
+    "yk_upsample_device": (C.c_int, [vp, C.POINTER(abi.UpsampleDesc), vp, vp, vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp, vp, vp, vp]),
     "yk_history_reproject_moved": (C.c_int, [vp, C.POINTER(abi.TemporalDesc), vp, vp, C.POINTER(abi.CameraMatrices), vp, vp, C.c_uint16, C.c_uint16, vp]),
     "yk_history_reproject_moved_device": (C.c_int, [vp, C.POINTER(abi.TemporalDesc), vp, vp, C.POINTER(abi.CameraMatrices), vp, vp, C.c_uint16, C.c_uint16, vp, vp]),
     "yk_moments_blend": (C.c_int, [vp, C.POINTER(abi.TemporalDesc), vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp]),

@@ -162,6 +162,12 @@ class DenoiseDesc(C.Structure):
     _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float)]
 
 
+class UpsampleDesc(C.Structure):
+    """yk_upsample_desc: the factor and the normal and plane stops of the guided upsample (csrc/yk_upsample.h)."""
+
+    _fields_ = [("s", C.c_uint32), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float)]
+
+
 class TemporalDesc(C.Structure):
     """yk_temporal_desc: the plane and normal tests of reproject and blend's history clamp (csrc/yk_temporal.h)."""
 
@@ -266,6 +272,7 @@ MOTION_DTYPE = np.dtype([("p_prev", "<f4", 3), ("known", "<f4")])  # yk_motion, 
 ALBEDO_DTYPE = np.dtype([("a", "<f4", 3), ("known", "<f4")])  # yk_albedo, 16 bytes
 ALBEDO_FLOOR = 0.015625  # YK_ALBEDO_FLOOR, 2^-6
 ALBEDO_MEAN_MAX_S = 8  # YK_ALBEDO_MEAN_MAX_S: the largest sub-sample grid of yk_albedo_mean
+UPSAMPLE_MAX_S = 8  # YK_UPSAMPLE_MAX_S: the largest factor of yk_upsample
 MOMENTS_DTYPE = np.dtype([("m1", "<f4"), ("m2", "<f4"), ("frames", "<f4"), ("n", "<f4")])  # yk_moments, 16 bytes: yk_history's layout
 PIXEL_STATS_DTYPE = np.dtype([("mean", "<f4"), ("m2", "<f4"), ("n", "<u4"), ("drawn", "<u4")])  # yk_pixel_stats, 16 bytes
 

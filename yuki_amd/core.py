@@ -533,6 +533,76 @@ def render_albedo_mean(ctx, scene, camera_params, film_settings, s=2):
     return out
 
 
+# --------------------------------------------------------------------------- guided upsampling (csrc/yk_upsample.h)
+# A frame sooner: render the film of subsampled(settings, s), its guides, and at FULL resolution the guides and ids alone —
+#   low = the film of Camera(params, subsampled(fs, s)); low_guides = render_guides(...) of that camera;
+#   guides, ids = render_guides_ids(...) of the full camera; albedo = surface_albedo(scene, ids);
+#   low_albedo = albedo_mean(scene, ids, s); low = denoise(low, low_guides, ..., albedo=low_albedo);
+#   full = upsample(low, low_guides, guides, UpsampleParams.for_scene(scene, s), low_albedo=low_albedo, albedo=albedo);
+# then the tone map as after a full-resolution denoise.
+@dataclass
+class UpsampleParams:
+    """yk_upsample_desc: the factor s (1 .. 8) and the normal and plane-distance stops of csrc/yk_upsample.h, which are
+    yk_denoise's; float("inf") switches a stop off.  sigma_plane is in scene units: None stands for "no plane stop" (+inf);
+    UpsampleParams.for_scene scales it to the scene."""
+
+    s: int = 2
+    sigma_normal: float = 0.3
+    sigma_plane: float = None
+
+    @staticmethod
+    def for_scene(scene, s, **kw):
+        """DenoiseParams.for_scene's stops: sigma_plane = 0.01 x the diagonal of the scene's bounds, sigma_normal 0.3."""
+        d = DenoiseParams.for_scene(scene)
+        return UpsampleParams(**{**dict(s=s, sigma_normal=d.sigma_normal, sigma_plane=d.sigma_plane), **kw})
+
+    def as_struct(self):
+        return abi.UpsampleDesc(int(self.s), float(self.sigma_normal), float("inf") if self.sigma_plane is None else float(self.sigma_plane))
+
+
+def _upsample_desc(params):
+    if not isinstance(params, UpsampleParams):
+        raise TypeError("params is an UpsampleParams")
+    if not 1 <= int(params.s) <= abi.UPSAMPLE_MAX_S:
+        raise ValueError(f"s is 1 .. {abi.UPSAMPLE_MAX_S}, not {params.s}")
+    return params.as_struct()
+
+
+def subsampled(film_settings, s):
+    """The FilmSettings of the s-times smaller film of the same view, the inverse of supersampled: the film whose pixels
+    each cover an s x s block of this one's.  Raises unless s divides both sides."""
+    s = _mean_s(s)
+    w, h = film_settings.res
+    if w % s or h % s or w < s or h < s:
+        raise ValueError(f"s = {s} does not divide res = {(w, h)}")
+    return FilmSettings(res=(w // s, h // s), tile_dim=film_settings.tile_dim)
+
+
+def upsample(low_film, low_guides, guides, params, tile_dim=16, samples=None, low_albedo=None, albedo=None, ctx=None, return_weight=False):
+    """yk_upsample: an (lh, lw, 3) float32 film of subsampled(...) rebuilt at (s * lh, s * lw) through its own (lh, lw) guides
+    and the full film's (s * lh, s * lw) guides (csrc/yk_upsample.h).  `samples` / `tile_dim` = the LOW film's sample table
+    (film_samples), whose sums are normalised first.  low_albedo (albedo_mean(scene, ids, s) of the full ids) and albedo
+    (surface_albedo of the full ids) are given both — the upsample then runs on radiance / albedo and multiplies the full
+    albedo back — or neither.  Returns the full film; with return_weight also the (s * lh, s * lw) float32 weight sums, 0
+    exactly where no tap was taken and the containing low pixel was copied.  ctx None = the host instance."""
+    low_film, lw, lh = _film(low_film)
+    d = _upsample_desc(params)
+    s = int(d.s)
+    samples = _blend_samples((lw, lh), tile_dim, samples)
+    low_guides = _records(low_guides, abi.GUIDE_DTYPE, (lw, lh), "low guide")
+    guides = _records(guides, abi.GUIDE_DTYPE, (s * lw, s * lh), "guide")
+    if (low_albedo is None) != (albedo is None):
+        raise ValueError("low_albedo and albedo are given both or neither")
+    if albedo is not None:
+        low_albedo = _records(low_albedo, abi.ALBEDO_DTYPE, (lw, lh), "low albedo")
+        albedo = _records(albedo, abi.ALBEDO_DTYPE, (s * lw, s * lh), "albedo")
+    out = np.empty((s * lh, s * lw, 3), np.float32)
+    weight = np.empty((s * lh, s * lw), np.float32) if return_weight else None
+    c = ctx.h if ctx else None
+    check(lib().yk_upsample(c, C.byref(d), _p(low_film), _p(low_guides), _p(low_albedo), lw, lh, int(tile_dim), _p(samples), _p(guides), _p(albedo), _p(out), _p(weight)), c)
+    return (out, weight) if return_weight else out
+
+
 def reproject_history_moved(history, prev_guides, prev_camera, guides, motion, params, ctx=None):
     """yk_history_reproject_moved: reproject_history after the geometry moved: every pixel is carried from where its
     surface point stood (`motion`, surface_motion's records) instead of from where it stands.  ctx None = the host
@@ -1140,6 +1210,17 @@ class Context:
         (16-byte aligned), ordered on `stream` (default: the context's) without waiting on the host.  `camera_ss` is the
         Camera of the s-times larger film (Camera(params, supersampled(film_settings, s)))."""
         check(lib().yk_render_albedo_mean_device(self.h, scene.h, C.byref(camera_ss.matrices), int(res[0]), int(res[1]), int(s), _vp(d_out_ptr), _vp(stream)), self.h)
+
+    def upsample_device(self, d_low_film_ptr, d_low_guides_ptr, low_res, d_guides_ptr, params, tile_dim, samples, d_out_ptr, stream=None, low_albedo=None, albedo=None, d_out_weight_ptr=None):
+        """yk_upsample_device: the device film and guides of the low_res film and the device guides of the s-times larger one
+        -> s * s * low_res[0] * low_res[1] device RGB pixels (and float weights where d_out_weight_ptr is given), enqueued on
+        `stream` (default: the context's) without waiting; one launch.  low_albedo / albedo: the device pointers of
+        albedo_mean_device's and surface_albedo_device's records, both or neither.  `samples` is the LOW film's host table
+        (or None), copied before the call returns."""
+        d = _upsample_desc(params)
+        samples = _blend_samples(low_res, tile_dim, samples)
+        check(lib().yk_upsample_device(self.h, C.byref(d), _vp(d_low_film_ptr), _vp(d_low_guides_ptr), _vp(low_albedo), int(low_res[0]), int(low_res[1]), int(tile_dim), _p(samples), _vp(d_guides_ptr),
+                                       _vp(albedo), _vp(d_out_ptr), _vp(d_out_weight_ptr), _vp(stream)), self.h)
 
     def reproject_history_moved_device(self, d_prev_history_ptr, d_prev_guides_ptr, prev_camera, d_guides_ptr, d_motion_ptr, res, params, d_out_history_ptr, stream=None):
         """yk_history_reproject_moved_device: reproject_history_device through the device motion records of

@@ -129,6 +129,7 @@ void yk_context_destroy(yk_context* ctx) {
     ctx->albedo_mean.ids_band.release();
     ctx->exposure.slot.release();
     ctx->exposure.samples.release();
+    ctx->upsample.samples.release();
     if (ctx->tonemap.staging) (void)hipHostFree(ctx->tonemap.staging);
     if (ctx->tonemap.staged) (void)hipEventDestroy(ctx->tonemap.staged);
     for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);

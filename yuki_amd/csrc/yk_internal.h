@@ -171,6 +171,11 @@ struct yk_context {
     // every entry point that touches the context's buffers or streams holds this: calls on one
     // context from several host threads (the reference's tile workers) are serialised
     std::recursive_mutex mu;
+    // the guided upsample's buffer (yk_upsample.hip), grown on first use.  It stands after every older member: their
+    // offsets, and with them the objects of the files that do not know this pass, stay what they were.
+    struct UpsampleState {
+        DevBuf samples;  // the LOW film's sample table on the device (staged through the tone map's pinned copy)
+    } upsample;
 };
 
 typedef yk_context::WorkSet WorkSet;
