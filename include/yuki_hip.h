@@ -1262,6 +1262,18 @@ yk_status yk_bsdf_sample(yk_context* ctx, const yk_material_desc* material, size
 yk_status yk_light_sample(yk_context* ctx, const yk_light_desc* light, int32_t light_index, size_t n, const float* p,
                           const float* n_geom, const float* u, float* out18);
 
+/* The SurfaceInteraction the integrators read (triangle.rs:141-226, sphere.rs:79-116, interaction.rs:95-164) of the closest hit
+ * of n rays, traced by the closest-hit kernel as the render loop launches it.  route 0 builds it from the leaf-order slot that
+ * kernel reports, as the Path wavefront, the debug integrators and the guide pass do; route 1 from the source shape through the
+ * scene's index-addressed arrays, as Whitted and yk_li_debug do: the two must agree bit for bit.  out: YK_SURFACE_FLOATS floats
+ * per ray — hit (0/1), t, p[3], n[3], shading n[3], shading dpdu[3], wo[3], u, v, material, area_light (-1 = none), source shape
+ * (-1 on a miss; the three ids as floats, exact below 2^24), barycentrics b0 b1 b2 (0 for a sphere), and the origin[3] of
+ * Interaction::spawn_ray (interaction.rs:27-40) for a ray that leaves the hit along ray_d.  A sphere's uv is computed only in a
+ * scene with image textures, as in a render.  A miss is all zeros but for the shape.  (Stage tests.) */
+#define YK_SURFACE_FLOATS 28
+yk_status yk_surface(yk_context* ctx, const yk_scene* scene, size_t n, const float* ray_o, const float* ray_d, int32_t route,
+                     float* out);
+
 size_t yk_sizeof(int what);
 
 /* ---- several GPUs ------------------------------------------------------

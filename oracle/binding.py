@@ -76,6 +76,8 @@ def lib():
     L.orc_camera_rays.restype = None
     L.orc_intersect.argtypes = [vp, C.c_size_t] + [vp] * 11
     L.orc_intersect.restype = None
+    L.orc_surface.argtypes = [vp, C.c_size_t, vp, vp, vp]
+    L.orc_surface.restype = None
     L.orc_any_intersect.argtypes = [vp, C.c_size_t, vp, vp, vp, vp, vp]
     L.orc_any_intersect.restype = None
     L.orc_siphash13.argtypes = [vp, C.c_size_t]
@@ -249,6 +251,14 @@ class OracleScene:
         )
         lib().orc_intersect(self.h, n, _p(o), _p(d), _p(tm), _p(r["shape"]), _p(r["t"]), _p(r["n"]), _p(r["ns"]), _p(r["p"]), _p(r["node_tests"]), _p(r["node_hits"]), _p(r["shape_tests"]))
         return r
+
+    def surface(self, o, d):
+        """(n, abi.SURFACE_FLOATS): the SurfaceInteraction of every ray's closest hit, fields abi.SURFACE_FIELDS (orc_surface)."""
+        o = np.ascontiguousarray(o, dtype=np.float32)
+        d = np.ascontiguousarray(d, dtype=np.float32)
+        out = np.zeros((o.shape[0], abi.SURFACE_FLOATS), dtype=np.float32)
+        lib().orc_surface(self.h, o.shape[0], _p(o), _p(d), _p(out))
+        return out
 
     def any_intersect(self, o, d, t_max, area_light=None):
         o = np.ascontiguousarray(o, dtype=np.float32)

@@ -421,6 +421,32 @@ void orc_intersect(const orc_scene* s, size_t n, const float* o, const float* d,
     }
 }
 
+void orc_surface(const orc_scene* s, size_t n, const float* o, const float* d, float* out28) {
+    for (size_t i = 0; i < n; ++i) {
+        float* r = out28 + 28 * i;
+        for (int k = 0; k < 28; ++k) r[k] = 0.0f;
+        r[21] = -1.0f;
+        Rayf ray(Point3f(o[3 * i], o[3 * i + 1], o[3 * i + 2]), Vec3f(d[3 * i], d[3 * i + 1], d[3 * i + 2]), std::numeric_limits<float>::infinity());
+        IntersectionResult ir = s->scene.bvh.intersect(ray);
+        if (!ir.has_hit) continue;
+        const SurfaceInteraction& si = ir.hit.si;
+        r[0] = 1.0f;
+        r[1] = ir.hit.t;
+        r[2] = si.p.x; r[3] = si.p.y; r[4] = si.p.z;
+        r[5] = si.n.x; r[6] = si.n.y; r[7] = si.n.z;
+        r[8] = si.shading.n.x; r[9] = si.shading.n.y; r[10] = si.shading.n.z;
+        r[11] = si.shading.dpdu.x; r[12] = si.shading.dpdu.y; r[13] = si.shading.dpdu.z;
+        r[14] = si.wo.x; r[15] = si.wo.y; r[16] = si.wo.z;
+        r[17] = si.uv.x; r[18] = si.uv.y;
+        r[19] = (float)ir.hit.shape->material;
+        r[20] = (float)si.area_light;
+        r[21] = (float)ir.hit.shape->source_index;
+        r[22] = ir.hit.b[0]; r[23] = ir.hit.b[1]; r[24] = ir.hit.b[2];
+        Rayf next = Interaction(si.p, si.n).spawn_ray(ray.d);
+        r[25] = next.o.x; r[26] = next.o.y; r[27] = next.o.z;
+    }
+}
+
 void orc_any_intersect(const orc_scene* s, size_t n, const float* o, const float* d, const float* t_max,
                        const int32_t* area_light, uint8_t* out_hit) {
     for (size_t i = 0; i < n; ++i) {

@@ -219,6 +219,12 @@ void orc_bsdf_sample(const orc_material_desc* m, const float* n_geom, const floa
 void orc_light_sample(const orc_light_desc* light, int32_t light_index, size_t n, const float* p, const float* n_geom, const float* u,
                       float* out18);
 
+/* The SurfaceInteraction of the closest hit of n rays (BoundingVolumeHierarchy::intersect), 28 floats per ray:
+ * hit (0/1), t, p[3], n[3], shading.n[3], shading.dpdu[3], wo[3], uv[2], material, area_light (-1 = none), source shape (-1 on a
+ * miss), barycentrics b0 b1 b2 (0 for a sphere), origin[3] of Interaction::spawn_ray along the ray's own direction.  A miss is
+ * all zeros but for the shape. */
+void orc_surface(const orc_scene* s, size_t n, const float* o, const float* d, float* out28);
+
 /* ImageTexture::evaluate at n uv pairs (KAT hook) */
 void orc_texture_eval(const orc_texture_desc* tex, size_t n, const float* uv, float* out_rgb);
 

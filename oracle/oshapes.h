@@ -116,6 +116,7 @@ struct Hit {
     float t;
     SurfaceInteraction si;
     const Shape* shape;
+    float b[3];  // a triangle's barycentrics (triangle.rs:133-136), zeros for a sphere: reported by orc_surface only
 };
 
 struct Geometry {
@@ -248,6 +249,7 @@ inline bool triangle_intersect(const Geometry& g, const Shape& s, const Rayf& ra
     out.t = t;
     out.si = si;
     out.shape = &s;
+    out.b[0] = b0; out.b[1] = b1; out.b[2] = b2;
     return true;
 }
 
@@ -305,6 +307,7 @@ inline bool sphere_intersect(const Shape& s, const Rayf& ray, Hit& out) {
     out.si = transform_si(s.object_to_world, si_obj);
     out.t = t;
     out.shape = &s;
+    out.b[0] = out.b[1] = out.b[2] = 0.0f;
     return true;
 }
 

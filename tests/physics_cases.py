@@ -9,6 +9,7 @@ differ only in the back end and the seed set.  A score is a dict of named figure
   *_mismatch            rows whose zero / no-sample / flag / cell / ray-count pattern differs from the float64 prediction; must be 0
   *_z                   |z| of observed counts against their float64 probabilities; at most Z_MAX, like every statistical bound
   excluded, compared    shares of the batch left out by a predicate on the INPUTS, and compared with a non-zero value
+  *_rows                how many compared rows took one branch of the code under test; the case built for a branch asserts it has rows
 
 How errors are measured is fixed here, before anything is calibrated:
   relative figures are max_c |got - ref| / max_c |ref| per row (RGB) or |got - ref| / |ref| (scalars);
@@ -136,6 +137,14 @@ class OracleBackend:
         finally:
             sc.close()
 
+    def surface(self, sd, o, d, route=0):
+        """orc_surface: the oracle has one way to the surface, `route` is ignored."""
+        sc = self.o.OracleScene(sd)
+        try:
+            return sc.surface(o, d)
+        finally:
+            sc.close()
+
     def li_counts(self, sd, sampler, integ, o, d, pix, si, dimension=2):
         """(li, closest-hit rays per sample)"""
         sc = self.o.OracleScene(sd)
@@ -144,6 +153,18 @@ class OracleBackend:
             return li, rays.astype(np.int64)
         finally:
             sc.close()
+
+
+class NullBackend:
+    """Answers nothing but zeros: what is left of a score is what the float64 reference alone decides — the excluded share."""
+
+    name = "null"
+
+    def surface(self, sd, o, d, route=0):
+        return np.zeros((len(o), abi.SURFACE_FLOATS), dtype=np.float32)
+
+    def li(self, sd, sampler, integ, o, d, pix, si, dimension=2):
+        return np.zeros((len(o), 3), dtype=np.float32)
 
 
 class DeviceBackend:
@@ -172,6 +193,13 @@ class DeviceBackend:
         sc = self.yk.Scene(self.ctx, sd)
         try:
             return self.yk.IntegratorType.instantiate(self.ctx, integ).li(sc, sampler, o, d, pix, si, dimension)
+        finally:
+            sc.close()
+
+    def surface(self, sd, o, d, route=0):
+        sc = self.yk.Scene(self.ctx, sd)
+        try:
+            return self.yk.surface(self.ctx, sc, o, d, route)
         finally:
             sc.close()
 
@@ -1200,6 +1228,454 @@ def run_sphere_wo(be, seed):
                 dark_where_textbook_is_lit=float(((ln > 0) & ~lit & ~ex).mean()))
 
 
+# ----------------------------------------------------------------------------- the surface stage
+SURFACE_SEED, SURFACE_CALIBRATION = 7600, (9050, 9060, 9070)
+SURFACE_CASES = ("plain", "uvs", "normals", "mixed-meshes", "degenerate", "sphere-rigid", "sphere-scaled", "sphere-mirrored", "sphere-inside", "sphere-poles")
+EDGE_CUT, DISC_CUT, AXIS_SCALE = 1e-4, 1e-4, 0.05
+SF = abi.SURFACE_FIELDS
+ONE_TEXEL = np.full((1, 1, 3), 0.5, dtype=np.float32)  # any image texture makes both back ends compute a sphere's uv
+
+
+def _unit(rng, k):
+    v = rng.normal(size=(k, 3))
+    return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+
+def _random_triangles(rng, k, spread=3.0):
+    """k triangles with sides of about 1 to 3 and no angle below 20 degrees, anywhere within +-spread: (3k, 3) f32 points."""
+    out = []
+    while len(out) < k:
+        c = rng.uniform(-spread, spread, 3)
+        p = c + rng.normal(size=(3, 3)) * rng.uniform(0.6, 1.4)
+        e = [p[(i + 1) % 3] - p[i] for i in range(3)]
+        cos = [np.dot(-e[i - 1], e[i]) / (np.linalg.norm(e[i - 1]) * np.linalg.norm(e[i])) for i in range(3)]
+        if max(cos) <= np.cos(np.radians(20.0)):
+            out.append(p)
+    return np.concatenate(out).astype(np.float32)
+
+
+def _random_uvs(rng, pts, mirrored):
+    """Per-vertex uvs in [-2.3, 3.1] with |uv_det| >= 0.05 |duv02| |duv12|; triangle k's winding is mirrored (uv_det < 0) where mirrored[k]."""
+    k = len(pts) // 3
+    uv = np.zeros((3 * k, 2), dtype=np.float32)
+    for t in range(k):
+        while True:
+            q = rng.uniform(-2.3, 3.1, (3, 2)).astype(np.float32).astype(np.float64)
+            a, b = q[0] - q[2], q[1] - q[2]
+            det = a[0] * b[1] - a[1] * b[0]
+            if abs(det) >= 0.05 * np.linalg.norm(a) * np.linalg.norm(b) and (det < 0) == bool(mirrored[t]):
+                uv[3 * t : 3 * t + 3] = q
+                break
+    return uv
+
+
+def _tilted_normals(rng, pts, far_side):
+    """Per-vertex normals up to 40 degrees from the face normal normalize((p0 - p2) x (p1 - p2)), lengths 0.3 .. 3; on the far side
+    of it where far_side[k]."""
+    p = pts.astype(np.float64).reshape(-1, 3, 3)
+    face = np.cross(p[:, 0] - p[:, 2], p[:, 1] - p[:, 2])
+    face /= np.linalg.norm(face, axis=1, keepdims=True)
+    face = np.where(np.asarray(far_side, dtype=bool)[:, None], -face, face)
+    out = np.zeros((len(p), 3, 3))
+    for v in range(3):
+        side = np.cross(face, _unit(rng, len(p)))
+        side /= np.linalg.norm(side, axis=1, keepdims=True)
+        a = np.radians(rng.uniform(0.0, 40.0, (len(p), 1)))
+        out[:, v] = (np.cos(a) * face + np.sin(a) * side) * rng.uniform(0.3, 3.0, (len(p), 1))
+    return out.reshape(-1, 3).astype(np.float32)
+
+
+LAMBERT = dict(kind=abi.MAT_MATTE, a=(0.7, 0.5, 0.3), c=0.0)
+
+
+def _mesh_scene(pts, meshes, tri_mesh, normals=None, uvs=None, tri_material=None, tri_area_light=None, materials=None, lights=(), order=None, name="physics-surface"):
+    k = len(pts) // 3
+    return scenes.SceneData(
+        points=pts, indices=np.arange(3 * k, dtype=np.uint32).reshape(k, 3), tri_mesh=np.asarray(tri_mesh, dtype=np.uint32),
+        tri_material=np.zeros(k, dtype=np.int32) if tri_material is None else np.asarray(tri_material, dtype=np.int32),
+        tri_area_light=np.full(k, -1, dtype=np.int32) if tri_area_light is None else np.asarray(tri_area_light, dtype=np.int32), meshes=list(meshes),
+        materials=[LAMBERT] if materials is None else materials, lights=list(lights), normals=normals, uvs=uvs, max_shapes_in_node=2, shape_order=order, name=name,
+    )
+
+
+def _aimed_rays(rng, targets, n=N_STAGE, reach=(1.0, 6.0)):
+    """n rays towards random members of `targets` (points on the primitives) from random directions, i.e. from both sides, from
+    origins at most 10 from the world's origin."""
+    hit = targets[rng.integers(0, len(targets), n)]
+    o = hit + _unit(rng, n) * rng.uniform(reach[0], reach[1], (n, 1))
+    o *= np.minimum(1.0, 9.9 / np.linalg.norm(o, axis=1, keepdims=True))
+    o = o.astype(np.float32)
+    d = hit - o
+    return o, (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32)
+
+
+def _points_on(rng, pts, per=64):
+    p = pts.astype(np.float64).reshape(-1, 3, 3)
+    w = rng.dirichlet((1.0, 1.0, 1.0), (len(p), per))
+    return np.einsum("kjv,kvc->kjc", w, p).reshape(-1, 3)
+
+
+SPHERE_SCALE = (1.0, 0.5, 2.0)
+
+
+def _sphere_transform(rng, kind):
+    """object_to_world of the sphere cases: rotation and translation; then with scale (1, 0.5, 2); then with a reflection besides.
+    `poles`: a quarter turn, the same scale and a translation in eighths, so that the object z-axis is reached exactly in f32."""
+    if kind == "poles":
+        rot = np.array([[0.0, 0.0, 1.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0]])
+        lin, c = rot @ np.diag(SPHERE_SCALE), np.round(rng.uniform(-2, 2, 3) * 8) / 8
+    else:
+        rot = _rigid(rng)[0][:3, :3].astype(np.float64)
+        c = rng.uniform(-2, 2, 3)
+        lin = rot if kind == "rigid" else rot @ np.diag(SPHERE_SCALE)
+        if kind == "mirrored":
+            lin = lin @ np.diag([1.0, -1.0, 1.0])
+    return lin, c
+
+
+def surface_inputs(name, seed):
+    """(SceneData, ray origins, ray directions) of one surface case; everything follows from the seed."""
+    rng = np.random.default_rng([seed, SURFACE_CASES.index(name)])
+    if name.startswith("sphere-"):
+        kind = name.split("-")[1]
+        lin, c = _sphere_transform(rng, {"inside": "scaled"}.get(kind, kind))
+        radius = 1.5
+        sd = sphere_scene(dict(LAMBERT, tex=0), c, radius, lin)
+        sd.textures = [ONE_TEXEL]
+        n = N_STAGE
+        if kind == "poles":
+            sign = rng.choice([-1.0, 1.0], (n, 1))
+            tilt = np.radians(rng.uniform(0, 1e-3 * 180 / np.pi, (n, 1)))
+            tilt[:64] = 0.0
+            phi = rng.uniform(0, 2 * np.pi, (n, 1))
+            axis_dir = np.concatenate([np.sin(tilt) * np.cos(phi), np.sin(tilt) * np.sin(phi), np.cos(tilt)], axis=1) * sign
+            dist = np.where(np.arange(n)[:, None] < 64, 8.0 * rng.integers(1, 4, (n, 1)), rng.uniform(4.0, 8.0, (n, 1)))
+            o = (c + (axis_dir * dist) @ lin.T).astype(np.float32)  # object space: on the axis, scaled by dist
+            d = -(axis_dir @ lin.T)
+            d = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32)
+            return sd, o, d
+        target = c + (_unit(rng, n) * radius * rng.uniform(0, 1, (n, 1)) ** (1 / 3) * 0.98) @ lin.T
+        if kind == "inside":
+            o = (c + (_unit(rng, n) * radius * 0.9 * rng.uniform(0, 1, (n, 1)) ** (1 / 3)) @ lin.T).astype(np.float32)
+            d = _unit(rng, n).astype(np.float32)
+            return sd, o, d
+        o = target + _unit(rng, n) * rng.uniform(4.5, 7.5, (n, 1))
+        o = o.astype(np.float32)
+        d = target - o
+        return sd, o, (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32)
+    if name == "degenerate":
+        # eighths, so that every difference of coordinates is exact in f32.  Mesh 0: uvs whose three values are equal (and swaps_handedness
+        # without normals, the one place where a triangle's flag decides the side of n); mesh 1: flagged
+        # as having normals, all zero; mesh 2: a triangle in the xy-plane with p1 - p0 along x and no uvs, so dpdu = p1 - p0 = (2, 0, 0),
+        # whose vertex normals are that very vector
+        pts = (np.round(_random_triangles(rng, 16).astype(np.float64) * 8) / 8).astype(np.float32)
+        z = float(np.round(rng.uniform(-3, 3) * 8) / 8)
+        x, y = (float(v) for v in np.round(rng.uniform(-2, 2, 2) * 8) / 8)
+        pts = np.concatenate([pts, np.array([(x, y, z), (x + 2, y, z), (x + 0.5, y + 1.5, z)], dtype=np.float32)])
+        k = 17
+        tri_mesh = [0] * 8 + [1] * 8 + [2]
+        uvs = np.repeat(rng.uniform(-2.3, 3.1, (k, 2)), 3, axis=0).astype(np.float32)
+        normals = np.zeros((3 * k, 3), dtype=np.float32)
+        normals[48:51] = (2.0, 0.0, 0.0)
+        sd = _mesh_scene(pts, [(False, True, True), (True, False, False), (True, False, False)], tri_mesh, normals=normals, uvs=uvs, order=rng.permutation(k).astype(np.uint32))
+        targets = np.concatenate([_points_on(rng, pts[:48]), np.repeat(_points_on(rng, pts[48:]), 12, axis=0)])
+        o, d = _aimed_rays(rng, targets)
+        return sd, o, d
+    if name == "mixed-meshes":
+        k = 64
+        pts = _random_triangles(rng, k)
+        tri_mesh = np.repeat(np.arange(4), 16)
+        meshes = [(False, False, False), (False, True, False), (True, True, False), (True, True, True)]
+        uvs = _random_uvs(rng, pts, rng.integers(0, 2, k))
+        normals = _tilted_normals(rng, pts, rng.integers(0, 4, k) == 0)
+        materials = [dict(kind=abi.MAT_MATTE, a=(0.2 + 0.01 * m, 0.5, 0.3), c=0.0) for m in range(70)]
+        tri_material = rng.permutation(70)[:k]
+        tri_material[:3] = (69, 64, 63)
+        tri_al = np.full(k, -1)
+        lit = rng.choice(k, 2, replace=False)
+        tri_al[lit] = (0, 1)
+        lm, lmi = _translate((0.0, 6.0, 0.0))
+        lights = [dict(kind="rect", l2w=lm, l2w_inv=lmi, L=(1.0, 1.0, 1.0), size=(1.0, 1.0))] * 2
+        perm = rng.permutation(k)  # the meshes' triangles interleave in source order
+        idx = np.arange(3 * k).reshape(k, 3)[perm]
+        sd = _mesh_scene(pts, meshes, tri_mesh[perm], normals=normals, uvs=uvs, tri_material=tri_material[perm], tri_area_light=tri_al[perm], materials=materials,
+                         lights=lights, order=rng.permutation(k).astype(np.uint32))
+        sd.indices = idx.astype(np.uint32)
+        o, d = _aimed_rays(rng, _points_on(rng, pts))
+        return sd, o, d
+    k = 64
+    pts = _random_triangles(rng, k)
+    uvs = _random_uvs(rng, pts, np.arange(k) % 2) if name == "uvs" else None
+    normals = _tilted_normals(rng, pts, np.arange(k) % 4 == 0) if name == "normals" else None
+    sd = _mesh_scene(pts, [(name == "normals", name == "uvs", False)], np.zeros(k), normals=normals, uvs=uvs, order=rng.permutation(k).astype(np.uint32))
+    o, d = _aimed_rays(rng, _points_on(rng, pts))
+    return sd, o, d
+
+
+def scene_arrays(sd, points=None, normals=None):
+    """The f32 arrays of a SceneData as tests/physics_ref.py's surface functions take them."""
+    flags = np.asarray(sd.meshes, dtype=bool).reshape(-1, 3)[np.asarray(sd.tri_mesh, dtype=np.int64)] if len(sd.indices) else np.zeros((0, 3), dtype=bool)
+    return dict(points=sd.points if points is None else points, indices=sd.indices, tri_flags=flags, normals=sd.normals if normals is None else normals, uvs=sd.uvs,
+                spheres=[(s["o2w"], s["w2o"], s["radius"]) for s in sd.spheres])
+
+
+def surface_reference(sd, o, d, points=None, normals=None):
+    """P.surface plus what the scene description itself says of the hit shape: material and area light."""
+    r = P.surface(scene_arrays(sd, points, normals), o, d)
+    nt = sd.n_triangles
+    shape = r["shape"]
+    tri = np.clip(shape, 0, max(nt - 1, 0))
+    mat = np.asarray(sd.tri_material, dtype=np.int64)[tri] if nt else np.zeros(len(shape), dtype=np.int64)
+    al = np.asarray(sd.tri_area_light, dtype=np.int64)[tri] if nt else np.full(len(shape), -1)
+    for k, s in enumerate(sd.spheres):
+        mat = np.where(shape == nt + k, int(s["material"]), mat)
+        al = np.where(shape == nt + k, -1, al)
+    r["material"], r["area_light"] = np.where(r["hit"], mat, 0), np.where(r["hit"], al, 0)
+    return r
+
+
+def surface_excluded(r, d):
+    """Rows left out, by the float64 reference alone: grazing rays, hits at a triangle's edge, rays that graze a sphere, and shading
+    normals in the plane of their triangle (where f32 decides the side of n) unless the case is about that very branch."""
+    d = P.f64(d)
+    graze = np.abs(P.dot(d, r["face"])) < COS_CUT
+    edge = ~r["is_sphere"] & (r["edge"] < EDGE_CUT)
+    disc = r["is_sphere"] & (r["disc"] < DISC_CUT)
+    flat = ~r["tangent_along_ns"] & (np.abs(P.dot(r["ns"], r["face"])) < COS_CUT * np.linalg.norm(r["ns"], axis=1))
+    return r["hit"] & (graze | edge | disc | flat)
+
+
+def score_surface(sd, o, d, got, points=None, normals=None):
+    """One yk_surface / orc_surface answer against the float64 surface.
+
+    Conditioning factors (reference only), on sphere rows.  Pole: a sphere's u and tangent turn by 1 / sin theta per unit of
+    rounding in the object-space point, and v by the same through the arc cosine, so their errors are multiplied by
+    min(1, sin theta / 0.05), the factor tests/test_gpu_li_debug.py::test_shading_uvs_on_spheres divides its tolerance by; so are
+    those of n and ns, because Sphere::intersect forms the normal as dpdu x dpdv with dpdv.z = -r sin(acos(z / r)) (sphere.rs:88-104,
+    as pbrt-v3 §3.2.3 does), which carries the same arc cosine: unscaled, n is off by 1.4e-3 at 1e-3 rad from a pole.  Grazing: the
+    hit distance solves a quadratic whose root moves by 1 / sqrt(disc / b^2) per unit of rounding in the ray, and with it the point and
+    all that is read off it, so every position-dependent error of a sphere row is multiplied by sqrt(disc / b^2) (<= 1; rows below
+    1e-4 are excluded outright).  u is compared around the seam.
+    On every row t's relative error is multiplied by min(1, t / max(1, |p|, |o|)): a hit distance carries the rounding of the coordinates
+    it is a difference of, so a ray that starts next to a surface has an absolute error of that size in however short a t.
+    The tangent is compared as a unit vector: a mesh without normals and a sphere report dpdu itself, the BSDF frame normalises it.
+    Rows whose tangent the geometry leaves open (equal uvs; dpdu along ns) are held to what holds in any frame instead: s.ns = 0 and,
+    with vertex normals, |s| = 1 — for every triangle row; a vanished interpolated normal must give ns = n (`ns_n_abs`: the frame is
+    rebuilt from s x t, so to rounding)."""
+    r = surface_reference(sd, o, d, points, normals)
+    got = P.f64(got)
+    ex = surface_excluded(r, d)
+    keep = r["hit"] & ~ex
+    hit_got = got[:, SF["hit"]] != 0
+    both = keep & hit_got
+    out = dict(hit_mismatch=int(((hit_got != r["hit"]) & ~ex).sum()), shape_mismatch=int(((got[:, SF["shape"]] != r["shape"]) & ~ex).sum()))
+    both &= got[:, SF["shape"]] == r["shape"]
+    out["material_mismatch"] = int((got[both, SF["material"]] != r["material"][both]).sum())
+    out["light_mismatch"] = int((got[both, SF["area_light"]] != r["area_light"][both]).sum())
+    out["side_mismatch"] = int((P.dot(got[:, SF["n"]], r["n"]) <= 0)[both].sum())
+    out["nan_mismatch"] = int((~np.isfinite(got)).any(axis=1).sum())
+    scale = np.maximum(1.0, np.maximum(np.linalg.norm(r["p"], axis=1), np.linalg.norm(P.f64(o), axis=1)))
+    graze = np.where(r["is_sphere"], np.sqrt(np.clip(r["disc"], 0.0, 1.0)), 1.0)
+    cond = np.minimum(1.0, r["axis"] / AXIS_SCALE) * graze
+    out["t_rel"] = _worst(_rel(got[:, SF["t"]], r["t"]) * graze * np.minimum(1.0, r["t"] / scale), both)
+    out["p_pos"] = _worst(_vec_abs(got[:, SF["p"]], r["p"]) / scale * graze, both)
+    out["origin_pos"] = _worst(_vec_abs(got[:, SF["origin"]], r["origin"]) / scale * graze, both)
+    out["n_abs"] = _worst(_vec_abs(got[:, SF["n"]], r["n"]) * cond, both)
+    out["ns_abs"] = _worst(_vec_abs(got[:, SF["ns"]], r["ns"]) * cond, both)
+    out["ns_n_abs"] = _worst(_vec_abs(got[:, SF["ns"]], got[:, SF["n"]]), both & r["ns_zero"])
+    out["wo_abs"] = _worst(_vec_abs(got[:, SF["wo"]], r["wo"]), both)
+    s_got = got[:, SF["dpdus"]]
+    with np.errstate(all="ignore"):
+        s_unit = s_got / np.linalg.norm(s_got, axis=1, keepdims=True)
+    open_frame = r["uv_degenerate"] | r["tangent_along_ns"] | r["ns_zero"]
+    out["s_abs"] = _worst(_vec_abs(s_unit, r["s"]) * cond, both & ~open_frame)
+    tri = both & ~r["is_sphere"]
+    out["s_perp_abs"] = _worst(np.abs(P.dot(s_unit, got[:, SF["ns"]])), tri)
+    out["s_unit_abs"] = _worst(np.abs(np.linalg.norm(s_got, axis=1) - 1.0), tri & r["has_normals"])
+    uv_got = np.stack([got[:, SF["u"]], got[:, SF["v"]]], axis=-1)
+    duv = np.abs(uv_got - r["uv"])
+    duv[:, 0] = np.where(r["is_sphere"], np.minimum(duv[:, 0], 1.0 - duv[:, 0]), duv[:, 0])
+    out["uv_abs"] = _worst(np.linalg.norm(duv, axis=1) * cond / np.maximum(1.0, np.linalg.norm(r["uv"], axis=1)), both)
+    out["excluded"] = float(ex.mean())
+    out["compared"] = float(both.mean())
+    back = P.dot(P.f64(d), r["face"]) > 0
+    flags = np.asarray(scene_arrays(sd)["tri_flags"], dtype=bool)
+    tri_of = np.clip(r["shape"], 0, max(sd.n_triangles - 1, 0))
+    is_tri = both & ~r["is_sphere"]
+    uv3 = None if sd.uvs is None else P.f64(sd.uvs)[np.asarray(sd.indices, dtype=np.int64)[tri_of]] if sd.n_triangles else None
+    out.update(
+        back_rows=int((both & back).sum()), sphere_rows=int((both & r["is_sphere"]).sum()), inside_rows=int((both & r["inside"]).sum()),
+        nudge_rows=int((both & r["is_sphere"] & (r["axis"] == 0)).sum()), near_pole_rows=int((both & r["is_sphere"] & (r["axis"] < AXIS_SCALE)).sum()),
+        uv_degenerate_rows=int((both & r["uv_degenerate"]).sum()), ns_zero_rows=int((both & r["ns_zero"]).sum()), tangent_along_ns_rows=int((both & r["tangent_along_ns"]).sum()),
+        flipped_rows=int((is_tri & (P.dot(r["n"], r["face"]) < 0)).sum()), normals_rows=int((is_tri & r["has_normals"]).sum()),
+        light_rows=int((both & (r["area_light"] >= 0)).sum()), material_high_rows=int((both & (r["material"] >= 64)).sum()),
+        swaps_rows=int((is_tri & flags[tri_of, 2]).sum()) if sd.n_triangles else 0,
+        default_uv_rows=int((is_tri & ~flags[tri_of, 1]).sum()) if sd.n_triangles else 0,
+        uv_mirrored_rows=0 if uv3 is None else int((is_tri & flags[tri_of, 1] & (np.linalg.det(np.stack([uv3[:, 0] - uv3[:, 2], uv3[:, 1] - uv3[:, 2]], axis=1)) < 0)).sum()),
+    )
+    return out
+
+
+SURFACE_BRANCH = {  # the rows each case was built for: every named count must be > 0 (tests/test_physics.py)
+    "plain": ("back_rows", "default_uv_rows"), "uvs": ("uv_mirrored_rows", "back_rows"), "normals": ("flipped_rows", "normals_rows"),
+    "mixed-meshes": ("light_rows", "material_high_rows", "swaps_rows", "default_uv_rows", "normals_rows", "uv_mirrored_rows"),
+    "degenerate": ("uv_degenerate_rows", "ns_zero_rows", "tangent_along_ns_rows", "swaps_rows"), "sphere-rigid": ("sphere_rows",), "sphere-scaled": ("sphere_rows",),
+    "sphere-mirrored": ("sphere_rows",), "sphere-inside": ("inside_rows",), "sphere-poles": ("nudge_rows", "near_pole_rows"),
+}
+
+
+def surface_stage_cases():
+    """The cases that pin the surface stage and the estimator above it."""
+    return [c for c in deterministic_cases() if c.startswith(("surface/", "direct-smooth/", "direct-textured/"))]
+
+
+def excluded_share(case_id, seed):
+    """The share of a case's batch that the float64 predicates leave out, with no back end at all."""
+    return run_case(NullBackend(), case_id, seed, cache=False)["excluded"]
+
+
+def run_surface(be, name, seed, route=0, cache=True):
+    sd, o, d = surface_inputs(name, seed)
+    key = (be.name, "surface", name, seed, route)
+    if not cache or key not in _ANSWERS:
+        _ANSWERS[key] = be.surface(sd, o, d, route)
+    return score_surface(sd, o, d, _ANSWERS[key])
+
+
+# ----------------------------------------------------------------------------- the surface under the estimator
+TEXTURE_SIZES = ((7, 5), (1, 1), (16, 3))  # width x height
+TEXEL_CUT = 1e-4  # texels: far wider than the uv_abs tolerance times 16 texels
+POINT_LIGHT = dict(pos=(1.0, 3.0, -0.5), I=(20.0, 15.0, 10.0))
+
+
+@functools.lru_cache(maxsize=None)
+def texture_pattern(w, h):
+    """A w x h PNG, written by scene_files.write_png and read back by the product's ImageTexture::new: (h, w, 3) f32 texels, pixel / 255.
+    Horizontally and vertically adjacent texels differ by at least 26 / 255 > 0.1 in red."""
+    import tempfile
+
+    import scene_files
+    from yuki_amd import loaders
+
+    y, x = np.mgrid[0:h, 0:w]
+    img = np.stack([40 + 26 * ((x + 3 * y) % 7), 230 - 26 * ((2 * x + y) % 5), 70 + 13 * ((x + y) % 3)], axis=-1).astype(np.uint8)
+    with tempfile.TemporaryDirectory() as tmp:
+        path = os.path.join(tmp, f"pattern-{w}x{h}.png")
+        scene_files.write_png(path, img)
+        tex = loaders.load_image_texture(path)
+    assert tex.shape == (h, w, 3) and np.array_equal(tex, img.astype(np.float32) / np.float32(255))
+    return tex
+
+
+def _point_light():
+    pm, _ = _translate(POINT_LIGHT["pos"])
+    return dict(kind="point", l2w=pm, I=POINT_LIGHT["I"]), dict(kind=P.POINT, l2w=pm, I=POINT_LIGHT["I"])
+
+
+def _lambert_direct(be, sd, o, d, kd, lit_rule, ex):
+    """Path::li at depth 1 under the point light against kd / pi * I * clamp(ns.l) / d^2 where `lit_rule(r, light sample)` holds, 0
+    elsewhere; r is the float64 surface of the scene."""
+    n = len(o)
+    got = P.f64(be.li(sd, _sampler(1), _path(1), o, d, np.zeros((n, 2), np.uint16), np.zeros(n, np.uint32)))
+    r = surface_reference(sd, o, d)
+    ls = P.light_sample(_point_light()[1], 0, r["p"], r["n"], np.zeros((n, 2)))
+    lit = r["hit"] & lit_rule(r, ls)
+    ref = np.where(lit[:, None], kd(r) / np.pi * ls["li"] * np.clip(P.dot(r["ns"], ls["l"]), 0.0, 1.0)[:, None], 0.0)
+    ex = ex(r, ls) | surface_excluded(r, d)
+    nz_ref, nz_got = ref.max(axis=1) > 0, got.max(axis=1) > 0
+    cmp_ = ~ex & nz_ref & nz_got
+    # measured against the value without its cosine, whose relative error is unbounded at the terminator; a sphere row times its
+    # grazing factor (score_surface)
+    full = (kd(r) / np.pi * ls["li"]).max(axis=1)
+    graze = np.where(r["is_sphere"], np.sqrt(np.clip(r["disc"], 0.0, 1.0)), 1.0)
+    with np.errstate(all="ignore"):
+        err = np.abs(got - ref).max(axis=1) / full * graze
+    return dict(li_rel=_worst(err, cmp_), li_zero_mismatch=int(((nz_ref != nz_got) & ~ex).sum()), excluded=float(ex.mean()), compared=float(cmp_.mean()),
+                dark_rows=int((~nz_ref & ~ex).sum()))
+
+
+def _merge(scores):
+    out = {}
+    for sc in scores:
+        for k, v in sc.items():
+            out[k] = v + out.get(k, 0) if k.endswith(("_mismatch", "_rows")) else max(v, out.get(k, 0.0)) if k != "compared" else min(v, out.get(k, 1.0))
+    return out
+
+
+def _same_side(r, ls):
+    """BSDF::f's filter (pbrt-v3 §9.1): reflection counts where wo and wi lie on one side of the GEOMETRIC normal."""
+    return P.dot(r["wo"], r["n"]) * P.dot(ls["l"], r["n"]) > 0
+
+
+def _side_band(r, ls):
+    return (np.abs(P.dot(r["wo"], r["n"])) < 1e-3) | (np.abs(P.dot(ls["l"], r["n"])) < 1e-3) | (np.abs(P.dot(ls["l"], r["ns"])) < 1e-3)
+
+
+def run_direct_textured(be, which, seed):
+    """A matte surface whose kd is an image texture, at depth 1 under a point light: kd is the texel the float64 uv selects (repeat,
+    v flipped, point sampled, the ledger's index rule).  `quad`: the floor with vertex uvs in [-2.3, 3.1], once per texture of 7 x 5,
+    1 x 1 and 16 x 3 texels (PNG files, decoded by the product's loader).  `sphere`: the scaled sphere with the 7 x 5.
+    Excluded: a float64 uv within 1e-4 texel of a texel boundary; on the sphere also u within 1e-4 of the seam, sin theta < 0.05 and
+    the side bands of sphere-wo/rotated."""
+    rng = np.random.default_rng(seed)
+    sl, _ = _point_light()
+    scores = []
+    if which == "quad":
+        pts, idx = _quad(0.0, FLOOR_HALF, True)
+        uvs = np.array([(-2.3, -2.3), (3.1, -2.3), (3.1, 3.1), (-2.3, 3.1)], dtype=np.float32)
+        for w, h in TEXTURE_SIZES:
+            tex = texture_pattern(w, h)
+            sd = scenes.SceneData(points=pts, indices=idx, tri_mesh=np.zeros(2, np.uint32), tri_material=np.zeros(2, np.int32), tri_area_light=np.full(2, -1, np.int32),
+                                  meshes=[(False, True, False)], materials=[dict(LAMBERT, tex=0)], lights=[sl], uvs=uvs, textures=[tex], name="physics-textured-quad")
+            o, d = direct_rays(int(rng.integers(1 << 30)))
+            look = lambda r, tex=tex: P.texel_lookup(tex, r["uv"])
+            scores.append(_lambert_direct(be, sd, o, d, lambda r: look(r)[0], _same_side, lambda r, ls: look(r)[1] < TEXEL_CUT))
+        return _merge(scores)
+    tex = texture_pattern(7, 5)
+    lin, c = _sphere_transform(rng, "scaled")
+    c = c * 0.25 + np.array([0.0, -2.0, 0.0])  # some 5 from the light: nearly half of the sphere is lit
+    sd = sphere_scene(dict(LAMBERT, tex=0), c, 1.0, lin, [sl])
+    sd.textures = [tex]
+    n = 8 * 2000  # candidates; the ledger's sphere_wo_transformed_again leaves a fifth of the lit side visible to the lobe, so the
+    o = (c + 4.0 * _unit(rng, n)).astype(np.float32)  # batch is drawn from them by the float64 prediction alone: 1000 lit rows, 1000 dark
+    aim = c + (0.8 * rng.uniform(0, 1, (n, 1)) ** (1 / 3) * _unit(rng, n)) @ lin.T
+    d = aim - o
+    d = (d / np.linalg.norm(d, axis=1, keepdims=True)).astype(np.float32)
+    r = surface_reference(sd, o, d)
+    ls = P.light_sample(_point_light()[1], 0, r["p"], r["n"], np.zeros((n, 2)))
+    lit = r["hit"] & _same_side(r, ls) & (P.dot(r["ns"], ls["l"]) > 0)
+    rows = np.sort(np.concatenate([np.nonzero(lit)[0][:1000], np.nonzero(~lit)[0][:1000]]))
+    o, d = o[rows], d[rows]
+    look = lambda r: P.texel_lookup(tex, r["uv"])
+    ex = lambda r, ls: (look(r)[1] < TEXEL_CUT) | (np.minimum(r["uv"][:, 0], 1.0 - r["uv"][:, 0]) < 1e-4) | (r["axis"] < AXIS_SCALE) | _side_band(r, ls)
+    return _lambert_direct(be, sd, o, d, lambda r: look(r)[0], _same_side, ex)
+
+
+SMOOTH_TILT = 35.0
+
+
+def run_direct_smooth(be, which, seed):
+    """A Lambert quad pair with tilted vertex normals under the point light at depth 1: kd / pi * I * clamp(ns.l) / d^2 where wo and l
+    are on one side of the geometric normal, 0 elsewhere.  Half of the quad (one triangle) carries normals on the far side of its face
+    normal, so its n is flipped to them.  `up`: seen from above; `both`: rays from either side."""
+    rng = np.random.default_rng(seed)
+    sl, _ = _point_light()
+    pts, idx = _quad(0.0, FLOOR_HALF, True)
+    pts = np.concatenate([pts[idx[0]], pts[idx[1]]])  # two triangles with vertices of their own
+    a = np.radians(rng.uniform(5.0, SMOOTH_TILT, (6, 1)))
+    side = np.cross(UP, _unit(rng, 6))
+    side /= np.linalg.norm(side, axis=1, keepdims=True)
+    normals = (np.cos(a) * UP + np.sin(a) * side) * rng.uniform(0.3, 3.0, (6, 1))
+    normals[3:] *= -1.0
+    sd = _mesh_scene(pts.astype(np.float32), [(True, False, False)], [0, 0], normals=normals.astype(np.float32), lights=[sl], name="physics-smooth-quad")
+    o, d = direct_rays(int(rng.integers(1 << 30)))
+    if which == "both":
+        o[::2, 1] *= -1.0
+        d[::2, 1] *= -1.0
+    kd = P.f64(np.asarray(LAMBERT["a"], dtype=np.float32))
+    return _lambert_direct(be, sd, o, d, lambda r: kd[None, :], _same_side, _side_band)
+
+
 # ----------------------------------------------------------------------------- one entry point per deterministic case
 def deterministic_cases():
     """id -> (kind, arguments, test seed, calibration seeds) of every deterministic case the tests run."""
@@ -1233,6 +1709,12 @@ def deterministic_cases():
         out[f"slab-classes/{angle}"] = ("slab-classes", (angle,), MC_SEED, (MC_SEED + 1, MC_SEED + 2))
     out["clamp/emitter-through-pane"] = ("clamp", (), MC_SEED, (MC_SEED + 1, MC_SEED + 2))
     out["sphere-wo/rotated"] = ("sphere-wo", (), LI_SEED, LI_CALIBRATION)
+    for name in SURFACE_CASES:
+        out[f"surface/{name}"] = ("surface", (name,), SURFACE_SEED, SURFACE_CALIBRATION)
+    for which in ("up", "both"):
+        out[f"direct-smooth/{which}"] = ("direct-smooth", (which,), SURFACE_SEED, SURFACE_CALIBRATION)
+    for which in ("quad", "sphere"):
+        out[f"direct-textured/{which}"] = ("direct-textured", (which,), SURFACE_SEED, SURFACE_CALIBRATION)
     return out
 
 
@@ -1284,6 +1766,12 @@ def run_case(be, case_id, seed=None, cache=True):
         return run_clamp(be, seed)
     if kind == "sphere-wo":
         return run_sphere_wo(be, seed)
+    if kind == "surface":
+        return run_surface(be, args[0], seed, cache=cache)
+    if kind == "direct-smooth":
+        return run_direct_smooth(be, args[0], seed)
+    if kind == "direct-textured":
+        return run_direct_textured(be, args[0], seed)
     return run_furnace_exact(be, args[0], seed)
 
 

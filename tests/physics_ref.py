@@ -1,7 +1,8 @@
 """Float64 physics for the shading path: BSDF lobes, Fresnel terms, microfacet distribution, light sampling, polygon
 irradiance and directional albedo; the pinhole camera; the structure of the samplers; Whitted's recursion over a stack of
-panes; Russian roulette and what it does to path lengths and to per-sample radiance; a floor under a pane — written from the
-published models in plain numpy.
+panes; Russian roulette and what it does to path lengths and to per-sample radiance; a floor under a pane; the surface of a
+triangle or sphere hit (point, normals, tangent, uv, spawn origin) and the texel an image texture shows there — written from the
+published models and the geometry in plain numpy.
 
 Test infrastructure only.  Nothing here imports the oracle or the product, calls their arithmetic or follows their
 operation order: every function states the formula of its source (named in its docstring) in float64, so a term that
@@ -131,6 +132,18 @@ DEVIATIONS = [
         asserts="a rotated Lambert sphere under a point light is lit only where (M wo).n and l.n have the same sign",
         live=("sphere-wo/rotated", "li_zero_mismatch"),
     ),
+    dict(
+        key="tangent_half_turn", quirk=None, where="shapes/triangle.rs:211-219",
+        sentence="With vertex normals a triangle's shading tangent is (normalize(dpdu) x ns) x ns, which is minus dpdu's projection perpendicular to ns: the shading frame is turned half a turn about ns.",
+        asserts="the unit tangent of a triangle with vertex normals is -normalize(dpdu - ns (dpdu.ns))",
+        live=("surface/normals", "s_abs"),
+    ),
+    dict(
+        key="texel_index_half_texel", quirk=None, where="textures/image_texture.rs:102-108",
+        sentence="An image texture's texel index is trunc(max(s*w - 0.5, 0)), not floor(s*w): texel 0 is one and a half texels wide and the last texel half a texel.",
+        asserts="a textured matte quad under a point light shows the texel trunc(max(s w - 0.5, 0)) of the float64 uv",
+        live=("direct-textured/quad", "li_rel"),
+    ),
 ]
 # Read in the reference and found to agree with pbrt-v3, hence no entries: the spot light's falloff (lights/spot_light.rs:38-50:
 # smooth (delta^2)^2 between cos_total_width and cos_falloff_start, 0 outside, 1 inside) and the rectangular light's emitting
@@ -162,6 +175,14 @@ MUTATIONS = [
     "rr_without_compensation",  # survivors not divided by 1 - q
     "rr_floor_010",  # q = max(0.10, ...)
     "clamp_after_beta",  # the indirect clamp applied to the fully weighted contribution
+    "bary_rotated",  # a triangle's barycentric weights applied to (p1, p2, p0)
+    "ns_unnormalised",  # the interpolated vertex normal used as it comes
+    "swaps_ignored",  # swaps_handedness does not negate the normal
+    "n_not_faceforwarded",  # the geometric normal left on its own side of the shading normal
+    "tangent_from_dpdv",  # the tangent taken from dpdv
+    "sphere_normal_by_m",  # a sphere's normal transformed by M instead of its inverse transpose
+    "texel_v_not_flipped",  # image rows counted from the bottom
+    "spawn_along_ns",  # the spawn offset taken along the shading normal
 ]
 _MUTATION = None
 _OFF = set()
@@ -918,3 +939,215 @@ def floor_under_pane(rho, eta, max_depth=None):
             acc += t[j] + r[j] * value[d + j]
         value[d] = rho * acc
     return value[0]
+
+
+# ----------------------------------------------------------------------------- the surface of a hit
+# What the integrators read off a hit, from the geometry: the f32 ray and the f32 scene arrays promoted to float64, every hit
+# found by solving for it against every primitive.  The scene is a dict of plain arrays: points (nv, 3), indices (nt, 3),
+# tri_flags (nt, 3) booleans (has normals, has uvs, swaps handedness: its mesh's), normals (nv, 3) or None, uvs (nv, 2) or None,
+# spheres = [(object_to_world 4x4, world_to_object 4x4, radius)].  Source shapes are numbered triangles first, then spheres.
+DEFAULT_UVS = np.array([[0.0, 0.0], [1.0, 0.0], [1.0, 1.0]])  # a triangle of a mesh without uvs (pbrt-v3 §3.6.2 GetUVs)
+SPAWN_OFFSET = 1e-3
+
+
+def _bary(b):
+    """The weights of (p0, p1, p2)."""
+    return np.roll(b, 1, axis=-1) if _m("bary_rotated") else b
+
+
+def _unit_or_zero(v):
+    n = np.linalg.norm(v, axis=-1, keepdims=True)
+    with np.errstate(all="ignore"):
+        return np.where(n > 0, v / n, 0.0)
+
+
+def triangle_hits(scene, o, d):
+    """Closest triangle hit of every ray by Cramer's rule on o + t d = p2 + b0 (p0 - p2) + b1 (p1 - p2) (Moeller and Trumbore 1997):
+    (t, triangle, barycentrics (n, 3)); t = inf where no triangle is hit in front of the origin."""
+    o, d = f64(o), f64(d)
+    pts, idx = f64(scene["points"]), np.asarray(scene["indices"], dtype=np.int64)
+    n = len(o)
+    best_t, best_k, best_b = np.full(n, np.inf), np.full(n, -1), np.zeros((n, 3))
+    for k in range(len(idx)):
+        p0, p1, p2 = pts[idx[k, 0]], pts[idx[k, 1]], pts[idx[k, 2]]
+        e0, e1 = p0 - p2, p1 - p2
+        m = np.stack([np.broadcast_to(e0, (n, 3)), np.broadcast_to(e1, (n, 3)), -d], axis=-1)  # columns: e0, e1, -d
+        det = np.linalg.det(m)
+        with np.errstate(all="ignore"):
+            sol = np.linalg.solve(np.where((det != 0)[:, None, None], m, np.eye(3)), (o - p2)[:, :, None])[:, :, 0]
+        b0, b1, t = sol[:, 0], sol[:, 1], sol[:, 2]
+        b2 = 1.0 - b0 - b1
+        ok = (det != 0) & (b0 >= 0) & (b1 >= 0) & (b2 >= 0) & (t > 0) & (t < best_t)
+        best_t = np.where(ok, t, best_t)
+        best_k = np.where(ok, k, best_k)
+        best_b = np.where(ok[:, None], np.stack([b0, b1, b2], axis=-1), best_b)
+    return best_t, best_k, best_b
+
+
+def triangle_surface(scene, o, d, tri, b):
+    """p, uv, geometric and shading normal and the unit tangent of triangle hits with barycentrics b — pbrt-v3 §3.6.2-3.6.3:
+    p = sum b_i p_i and uv = sum b_i uv_i; the face normal is normalize((p0 - p2) x (p1 - p2)), negated under swaps_handedness;
+    with vertex normals ns = normalize(sum b_i n_i) and n is the face normal on ns's side; dpdu solves the 2 x 2 uv system and the
+    tangent is its normalised projection into the plane perpendicular to ns.  Also the branch each row takes: uv_degenerate (the
+    three uvs span no area: no dpdu, any tangent perpendicular to ns will do), ns_zero (the interpolated normal vanishes: ns = n),
+    tangent_along_ns (dpdu has no component perpendicular to ns)."""
+    d = f64(d)
+    pts, idx = f64(scene["points"]), np.asarray(scene["indices"], dtype=np.int64)[tri]
+    flags = np.asarray(scene["tri_flags"], dtype=bool)[tri]
+    has_n, has_uv, swaps = flags[:, 0], flags[:, 1], flags[:, 2]
+    w = _bary(f64(b))
+    p0, p1, p2 = pts[idx[:, 0]], pts[idx[:, 1]], pts[idx[:, 2]]
+    p = w[:, 0:1] * p0 + w[:, 1:2] * p1 + w[:, 2:3] * p2
+    uv3 = np.broadcast_to(DEFAULT_UVS, (len(tri), 3, 2)).copy()
+    if scene.get("uvs") is not None:
+        uv3 = np.where(has_uv[:, None, None], f64(scene["uvs"])[idx], uv3)
+    uv = (w[:, :, None] * uv3).sum(axis=1)
+    face = normalize(np.cross(p0 - p2, p1 - p2))
+    if not _m("swaps_ignored"):
+        face = np.where(swaps[:, None], -face, face)
+    # dpdu, dpdv from (p0 - p2, p1 - p2) = (duv02, duv12) (dpdu, dpdv)
+    duv02, duv12 = uv3[:, 0] - uv3[:, 2], uv3[:, 1] - uv3[:, 2]
+    det = duv02[:, 0] * duv12[:, 1] - duv02[:, 1] * duv12[:, 0]
+    uv_degenerate = det == 0
+    with np.errstate(all="ignore"):
+        dpdu = (duv12[:, 1:2] * (p0 - p2) - duv02[:, 1:2] * (p1 - p2)) / det[:, None]
+        dpdv = (-duv12[:, 0:1] * (p0 - p2) + duv02[:, 0:1] * (p1 - p2)) / det[:, None]
+    along = np.where(uv_degenerate[:, None], 0.0, dpdv if _m("tangent_from_dpdv") else dpdu)
+    ns, n = face.copy(), face.copy()
+    ns_zero = np.zeros(len(tri), dtype=bool)
+    if scene.get("normals") is not None:
+        nsum = (w[:, :, None] * f64(scene["normals"])[idx]).sum(axis=1)
+        ns_zero = has_n & (np.linalg.norm(nsum, axis=1) == 0)
+        interp = nsum if _m("ns_unnormalised") else _unit_or_zero(nsum)
+        ns = np.where((has_n & ~ns_zero)[:, None], interp, face)
+        if not _m("n_not_faceforwarded"):
+            n = np.where((dot(face, ns) < 0)[:, None], -face, face)
+    s = along - ns * (dot(along, ns) / dot(ns, ns))[:, None]
+    tangent_along_ns = ~uv_degenerate & (np.linalg.norm(s, axis=1) <= 1e-12 * np.linalg.norm(along, axis=1))
+    s = _unit_or_zero(np.where(tangent_along_ns[:, None], 0.0, s))
+    if _on("tangent_half_turn"):
+        s = np.where(has_n[:, None], -s, s)
+    return dict(p=p, uv=uv, n=n, ns=ns, s=s, face=face, wo=-d, has_normals=has_n, uv_degenerate=uv_degenerate, ns_zero=ns_zero, tangent_along_ns=tangent_along_ns,
+                edge=np.abs(f64(b)).min(axis=1))
+
+
+def _linear(m):
+    m = f64(m).reshape(4, 4)
+    return m[:3, :3], m[:3, 3]
+
+
+def sphere_hits(scene, o, d):
+    """Closest sphere hit: the world ray against the ellipsoid |W x + w| = r (W, w: world_to_object): the smallest positive root of
+    the quadratic in t, which is the far root when the origin is inside.  -> (t, sphere, discriminant / b^2, origin inside)."""
+    o, d = f64(o), f64(d)
+    n = len(o)
+    best_t, best_k, best_disc, best_in = np.full(n, np.inf), np.full(n, -1), np.full(n, np.inf), np.zeros(n, dtype=bool)
+    for k, (_, w2o, r) in enumerate(scene.get("spheres", ())):
+        lin, off = _linear(w2o)
+        oo, dd = o @ lin.T + off, d @ lin.T
+        a, b, c = dot(dd, dd), 2.0 * dot(oo, dd), dot(oo, oo) - float(r) ** 2
+        disc = b * b - 4.0 * a * c
+        with np.errstate(all="ignore"):
+            root = np.sqrt(disc)
+            t0, t1 = (-b - root) / (2.0 * a), (-b + root) / (2.0 * a)
+            t = np.where(t0 > 0, t0, t1)
+            ok = (disc >= 0) & (t > 0) & (t < best_t)
+            rel = disc / (b * b)
+        best_t, best_k = np.where(ok, t, best_t), np.where(ok, k, best_k)
+        best_disc, best_in = np.where(ok, rel, best_disc), np.where(ok, c < 0, best_in)
+    return best_t, best_k, best_disc, best_in
+
+
+def sphere_surface(scene, o, d, sph, t):
+    """p on the ellipsoid, its unit normal (the gradient of |W x + w|^2, W^T (W x + w): outward; inward when the transform swaps
+    handedness, pbrt-v3 §3.1.1 / §2.8.3), (u, v) = (phi / 2 pi, (theta - pi) / (0 - pi)) of the object-space point as pbrt-v3 §3.2.3
+    parametrises a full sphere (theta_min = pi at z = -r), and the unit tangent, the world image M (-y, x, 0) of the longitude
+    direction.  axis = sin theta of the point: the conditioning of u and the tangent near the poles."""
+    o, d = f64(o), f64(d)
+    n = len(o)
+    p = o + t[:, None] * d
+    nrm, uv, s, wo, axis = np.zeros((n, 3)), np.zeros((n, 2)), np.zeros((n, 3)), -d.copy(), np.ones(n)
+    for k, (o2w, w2o, r) in enumerate(scene.get("spheres", ())):
+        rows = sph == k
+        if not rows.any():
+            continue
+        m, _ = _linear(o2w)
+        lin, off = _linear(w2o)
+        x = p[rows] @ lin.T + off
+        grad = x @ m.T if _m("sphere_normal_by_m") else x @ lin
+        if np.linalg.det(m) < 0 and not _m("swaps_ignored"):
+            grad = -grad
+        nrm[rows] = normalize(grad)
+        phi = np.arctan2(x[:, 1], x[:, 0])
+        phi = np.where(phi < 0, phi + 2.0 * np.pi, phi)
+        z = np.clip(x[:, 2] / float(r), -1.0, 1.0)
+        uv[rows] = np.stack([phi / (2.0 * np.pi), (np.arccos(z) - np.pi) / (0.0 - np.pi)], axis=-1)
+        s[rows] = _unit_or_zero(np.stack([-x[:, 1], x[:, 0], np.zeros(len(x))], axis=-1) @ m.T)
+        axis[rows] = np.hypot(x[:, 0], x[:, 1]) / float(r)
+        if _on("sphere_wo_transformed_again"):
+            wo[rows] = normalize(-d[rows] @ m.T)
+    return dict(p=p, uv=uv, n=nrm, ns=nrm.copy(), s=s, wo=wo, axis=axis)
+
+
+def surface(scene, o, d):
+    """The record of every ray's closest hit: hit, t, shape (source order, -1 on a miss), p, n, ns, s (unit tangent), uv, wo, the
+    origin of a ray that leaves the hit along d (spawn_origin), and the per-row facts the exclusion predicates and branch counts
+    read: is_sphere, edge (smallest barycentric), disc (sphere discriminant / b^2), inside, axis, has_normals, uv_degenerate,
+    ns_zero, tangent_along_ns, face."""
+    o, d = f64(o), f64(d)
+    n = len(o)
+    nt = len(scene["indices"])
+    tt, tri, b = triangle_hits(scene, o, d) if nt else (np.full(n, np.inf), np.full(n, -1), np.zeros((n, 3)))
+    ts, sph, disc, inside = sphere_hits(scene, o, d)
+    is_sphere = ts < tt
+    t = np.minimum(tt, ts)
+    hit = np.isfinite(t)
+    out = dict(hit=hit, t=t, is_sphere=is_sphere & hit, shape=np.where(hit, np.where(is_sphere, nt + sph, tri), -1), b=b, disc=disc, inside=inside & is_sphere)
+    fields = dict(p=3, uv=2, n=3, ns=3, s=3, wo=3, face=3)
+    for k, width in fields.items():
+        out[k] = np.zeros((n, width))
+    for k in ("has_normals", "uv_degenerate", "ns_zero", "tangent_along_ns"):
+        out[k] = np.zeros(n, dtype=bool)
+    out["edge"], out["axis"] = np.ones(n), np.ones(n)
+    rows = hit & ~is_sphere
+    if rows.any():
+        r = triangle_surface(scene, o[rows], d[rows], tri[rows], b[rows])
+        for k, v in r.items():
+            out[k][rows] = v
+    rows = hit & is_sphere
+    if rows.any():
+        r = sphere_surface(scene, o[rows], d[rows], sph[rows], t[rows])
+        for k, v in r.items():
+            out[k][rows] = v
+        out["face"][rows] = r["n"]
+    out["origin"] = spawn_origin(out["p"], out["n"], out["ns"], d)
+    return out
+
+
+def spawn_origin(p, n, ns, d):
+    """Where a ray along d leaves the surface: the ledger's `fixed_offset`, p +- 1e-3 n with the geometric normal, on d's side."""
+    if not _on("fixed_offset"):
+        return f64(p)
+    along = f64(ns) if _m("spawn_along_ns") else f64(n)
+    return f64(p) + SPAWN_OFFSET * np.where(dot(d, along) > 0, 1.0, -1.0)[:, None] * along
+
+
+def texel_lookup(tex, uv):
+    """An image texture at uv — repeat, v flipped (images are stored top row first), point sampled: pbrt-v3 §10.4.1 (ImageTexture
+    with the UV mapping) and §10.4.3 with a one-texel box: texel floor(s w) of s in [0, 1).  The ledger's `texel_index_half_texel`
+    takes trunc(max(s w - 0.5, 0)) instead.  -> (rgb (n, 3), distance of every row to the nearest texel boundary, in texels)."""
+    tex, uv = f64(tex), f64(uv)
+    h, w = tex.shape[:2]
+    s = uv - np.floor(uv)
+    if not _m("texel_v_not_flipped"):
+        s = np.stack([s[:, 0], 1.0 - s[:, 1]], axis=-1)
+    x = s * np.array([w, h])
+    if _on("texel_index_half_texel"):
+        x = np.maximum(x - 0.5, 0.0)
+    i = np.minimum(np.floor(x).astype(np.int64), np.array([w - 1, h - 1]))
+    frac = x - np.floor(x)
+    wrap = np.minimum(s, 1.0 - s) * np.array([w, h])  # the repeat's own seam
+    boundary = np.minimum(np.minimum(frac, 1.0 - frac), wrap)
+    if _on("texel_index_half_texel"):  # texel 0 starts at the seam and runs to s w = 1.5: no boundary at x = 0
+        boundary = np.where(s * np.array([w, h]) < 1.0, wrap, boundary)
+    return tex[i[:, 1], i[:, 0]], boundary.min(axis=1)

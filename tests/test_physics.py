@@ -1,5 +1,5 @@
 """Shading against float64 physics, on the CPU oracle: BSDF lobes, lights, the camera, the samplers' structure, Whitted's
-recursion and the Path estimator with its roulette.
+recursion, the Path estimator with its roulette, and the surface a hit is turned into before any of them sees it.
 
 Every other shading test asks whether the device equals the oracle; these ask whether the oracle (and, in
 tests/test_gpu_physics.py, the device) equals the published models, restated in float64 by tests/physics_ref.py from the
@@ -31,7 +31,9 @@ def test_stage_or_estimator_matches_physics(be, case_id):
     point, spot and distant light and the exact furnaces; camera rays over five resolutions, three fields of view on either
     axis, a far and a downward camera, and their jittered link to the sampler; the samplers' strata, permutations and seek rule;
     Whitted over one and three panes to depth 16, with ray counts; path lengths under the roulette, per-sample radiance through a
-    pane, the indirect clamp and the sphere's wo: every figure within its measured tolerance (a |z| within 4), the zero /
+    pane, the indirect clamp and the sphere's wo; the SurfaceInteraction of triangle and sphere hits (ten scenes of
+    tests/physics_cases.py SURFACE_CASES) and, at depth 1 above it, Lambert quads with tilted vertex normals and image-textured
+    surfaces: every figure within its measured tolerance (a |z| within 4), the zero /
     no-sample / flag / count patterns exactly as float64 predicts, at most 5 % of a batch excluded."""
     K.check_deterministic(be, case_id)
 
@@ -103,6 +105,14 @@ MUTATION_CASES = {
     "rr_without_compensation": ("rr-lengths/green", "length_z"),
     "rr_floor_010": ("rr-lengths/green", "length_z"),
     "clamp_after_beta": ("clamp/emitter-through-pane", "emission_rel"),
+    "bary_rotated": ("surface/plain", "p_pos"),
+    "ns_unnormalised": ("surface/normals", "ns_abs"),
+    "swaps_ignored": ("surface/sphere-mirrored", "side_mismatch"),  # a mesh with normals turns n to ns whatever the flag says
+    "n_not_faceforwarded": ("surface/normals", "side_mismatch"),
+    "tangent_from_dpdv": ("surface/uvs", "s_abs"),
+    "sphere_normal_by_m": ("surface/sphere-scaled", "n_abs"),
+    "texel_v_not_flipped": ("direct-textured/quad", "li_rel"),
+    "spawn_along_ns": ("surface/normals", "origin_pos"),
 }
 
 
@@ -120,6 +130,36 @@ def test_mutation_is_caught(be, name):
             value, tol = K.run_case(be, case_id)[figure], _bound(case_id, figure)
     print(name, case_id, figure, value, tol)
     assert value >= 10 * tol and value > 0, (name, value, tol)  # a count of mismatches is held to 0: any will do
+
+
+@pytest.mark.parametrize("name", K.SURFACE_CASES)
+def test_surface_case_reaches_its_branch(be, name):
+    """Every surface case records how many compared rows took each branch of the surface code; the branches it was built for
+    (tests/physics_cases.py SURFACE_BRANCH) have rows, and no output is NaN."""
+    score = K.run_case(be, f"surface/{name}")
+    for rows in K.SURFACE_BRANCH[name]:
+        assert score[rows] > 0, (name, rows)
+    if name == "sphere-poles":
+        assert score["nudge_rows"] == 64
+    assert score["nan_mismatch"] == 0
+
+
+@pytest.mark.parametrize("case_id", K.surface_stage_cases())
+def test_surface_exclusions_stay_under_the_cap(case_id):
+    """What a surface case leaves out is decided by the float64 reference alone: evaluated with no back end, on the test seed and on
+    every calibration seed, the excluded share stays at or below MAX_EXCLUDED."""
+    _, _, seed, calibration = K.all_cases()[case_id]
+    for s in (seed,) + tuple(calibration):
+        assert K.excluded_share(case_id, s) <= K.MAX_EXCLUDED, (case_id, s)
+
+
+def test_surface_tolerances_stay_below_the_cap():
+    """No figure of the surface stage calibrates above 1e-4, an order below where a misread term shows: one that did would mean a
+    missing conditioning factor or a wrong oracle, not a reason for a wider bound."""
+    rows = {k: v for k, v in K.tolerances()["rows"].items() if k.split(":")[0] in K.surface_stage_cases()}
+    assert len(rows) >= 100
+    for key, row in rows.items():
+        assert row["tolerance"] <= 1e-4 and row["excluded"] <= K.MAX_EXCLUDED, (key, row)
 
 
 def test_every_mutation_has_a_case():

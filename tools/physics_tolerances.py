@@ -81,8 +81,8 @@ def measure(be, log=None):
         what="oracle-vs-float64 errors on calibration seeds; tolerance = margin x worst, at least floor (tools/physics_tolerances.py)",
         margin=K.MARGIN, floor=K.FLOOR, max_excluded=K.MAX_EXCLUDED,
         calibration_seeds=dict(bsdf=list(K.BSDF_CALIBRATION), light=list(K.LIGHT_CALIBRATION), li=list(K.LI_CALIBRATION), sampler=[K.MC_SEED + 1, K.MC_SEED + 2],
-                               camera=list(K.CAMERA_CALIBRATION), whitted=list(K.WHITTED_CALIBRATION)),
-        test_seeds=dict(bsdf=[K.BSDF_SEED, K.BSDF_SEED + 1], light=K.LIGHT_SEEDS, li=K.LI_SEED, sampler=K.MC_SEED, camera=K.CAMERA_SEED, whitted=K.WHITTED_SEED),
+                               camera=list(K.CAMERA_CALIBRATION), whitted=list(K.WHITTED_CALIBRATION), surface=list(K.SURFACE_CALIBRATION)),
+        test_seeds=dict(bsdf=[K.BSDF_SEED, K.BSDF_SEED + 1], light=K.LIGHT_SEEDS, li=K.LI_SEED, sampler=K.MC_SEED, camera=K.CAMERA_SEED, whitted=K.WHITTED_SEED, surface=K.SURFACE_SEED),
         rows=rows, monte_carlo=mc,
     )
 

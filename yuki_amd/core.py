@@ -1978,6 +1978,16 @@ def light_sample(ctx, light, light_index, p, n_geom, u):
     return out
 
 
+def surface(ctx, scene, ray_o, ray_d, route=0):
+    """The SurfaceInteraction of the closest hit of n rays: (n, abi.SURFACE_FLOATS) floats, fields abi.SURFACE_FIELDS, see yk_surface.
+    route 0: by leaf-order slot (the Path wavefront, debug integrators, guides); 1: by source shape (Whitted, li_debug)."""
+    o = np.ascontiguousarray(ray_o, dtype=np.float32)
+    d = np.ascontiguousarray(ray_d, dtype=np.float32)
+    out = np.zeros((o.shape[0], abi.SURFACE_FLOATS), dtype=np.float32)
+    check(lib().yk_surface(ctx.h, scene.h, o.shape[0], _p(o), _p(d), int(route), _p(out)), ctx.h)
+    return out
+
+
 def bsdf_sample(ctx, material, n_geom, n_shading, dpdu, wo, u):
     arrs = [np.ascontiguousarray(x, dtype=np.float32) for x in (n_geom, n_shading, dpdu, wo, u)]
     out = np.zeros((arrs[0].shape[0], 8), dtype=np.float32)

@@ -68,6 +68,7 @@ void launch_sampler_sequence(hipStream_t s, const SamplerCfg& cfg, uint32_t px, 
 void launch_light_test(hipStream_t s, const DevLight& L, int index, size_t n, const float* p, const float* ng, const float* u, float* out);
 void launch_bsdf_test(hipStream_t s, const Material& m, size_t n, const float* ng, const float* ns, const float* dpdu, const float* wo,
                       const float* wi_or_u, int sample, float* out);
+void launch_surface_test(hipStream_t s, const DevScene& sc, size_t n, const float4* rayO, const float4* rayD, const int* hit_word, int route, float* out);
 void launch_pack_rays(hipStream_t s, size_t n, const float* o, const float* d, float4* rayO, float4* rayD);
 void launch_pack_shadow_rays(hipStream_t s, size_t n, const float* o, const float* d, const float* t_max, const int* area_light, float4* shO,
                              float4* shD);

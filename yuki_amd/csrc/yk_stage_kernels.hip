@@ -1,5 +1,5 @@
-// yk_stage_kernels.hip — kernels of the per-stage entry points (yk_stages.cpp): the device math, sampler, BSDF and light
-// functions called on arrays for the unit tests, and the packing of caller-supplied rays.  None runs in the render loop.
+// yk_stage_kernels.hip — kernels of the per-stage entry points (yk_stages.cpp): the device math, sampler, BSDF, light and
+// surface functions called on arrays for the unit tests, and the packing of caller-supplied rays.  None runs in the render loop.
 #include <hip/hip_runtime.h>
 
 #include "yk_device.h"
@@ -132,6 +132,60 @@ __global__ void k_light_test(DevLight L, int index, size_t n, const float* p, co
     o[15] = sd.x; o[16] = sd.y; o[17] = sd.z;
 }
 
+// The SurfaceInteraction of n closest hits (stage entry yk_surface), YK_SURFACE_FLOATS floats per ray.  hit_word[i] is what
+// the render-loop closest-hit kernel reported: -1 or the leaf-order slot | kind bits.  route 0 builds the surface as k_shade,
+// the debug integrators and the guide pass do (hit_surface_prim, by slot); route 1 as k_whitted and k_path_debug do
+// (hit_surface, by the source shape the slot's record names); t and the barycentrics of route 1 come from the same intersection
+// functions hit_surface calls.  A miss is an all-zero record with shape -1.
+__global__ void k_surface_test(DevScene sc, size_t n, const float4* rayO, const float4* rayD, const int* hit_word, int route, float* out) {
+    size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float* r = out + YK_SURFACE_FLOATS * i;
+    for (int k = 0; k < YK_SURFACE_FLOATS; ++k) r[k] = 0.0f;
+    r[21] = -1.0f;
+    const int h = hit_word[i];
+    if (h < 0) return;
+    const uint32_t prim = (uint32_t)h & YK_HIT_PRIM_MASK;
+    const float4 fo = rayO[i], fd = rayD[i];
+    const V3 o = V3{fo.x, fo.y, fo.z}, d = V3{fd.x, fd.y, fd.z};
+    Surface sf;
+    float t = 0.0f;
+    uint4 id = make_uint4(0u, 0u, 0u, 0u);
+    if (route == 0) {
+        sf = hit_surface_prim(sc, prim, o, d, sc.texels != nullptr, &t, &id);
+    } else {
+        const uint32_t shape = __float_as_uint(sc.tris[3 * prim + 1].w);
+        sf = hit_surface(sc, shape, o, d);
+        id.x = shape;
+        if (shape >= sc.n_triangles) {
+            V3 ro, rd;
+            sphere_hit_t(sc.spheres[shape - sc.n_triangles], o, d, __builtin_inff(), t, ro, rd);
+        } else {
+            const uint32_t i0 = sc.indices[3 * shape], i1 = sc.indices[3 * shape + 1], i2 = sc.indices[3 * shape + 2];
+            TriHit th = TriHit{0.0f, 0.0f, 0.0f, 0.0f};
+            tri_intersect(o, ray_tri_setup(d), __builtin_inff(), ld3(sc.points, i0), ld3(sc.points, i1), ld3(sc.points, i2), th);
+            t = th.t;
+            id.y = __float_as_uint(th.b0);
+            id.z = __float_as_uint(th.b1);
+            id.w = __float_as_uint(th.b2);
+        }
+    }
+    r[0] = 1.0f;
+    r[1] = t;
+    r[2] = sf.p.x; r[3] = sf.p.y; r[4] = sf.p.z;
+    r[5] = sf.n.x; r[6] = sf.n.y; r[7] = sf.n.z;
+    r[8] = sf.ns.x; r[9] = sf.ns.y; r[10] = sf.ns.z;
+    r[11] = sf.dpdus.x; r[12] = sf.dpdus.y; r[13] = sf.dpdus.z;
+    r[14] = sf.wo.x; r[15] = sf.wo.y; r[16] = sf.wo.z;
+    r[17] = sf.u; r[18] = sf.v;
+    r[19] = (float)sf.material;
+    r[20] = (float)sf.area_light;
+    r[21] = (float)id.x;
+    r[22] = __uint_as_float(id.y); r[23] = __uint_as_float(id.z); r[24] = __uint_as_float(id.w);
+    const V3 so = spawn_origin(sf.p, sf.n, d);  // Interaction::spawn_ray for a ray that goes on along d
+    r[25] = so.x; r[26] = so.y; r[27] = so.z;
+}
+
 __global__ void k_pack_rays(size_t n, const float* o, const float* d, float4* rayO, float4* rayD) {
     size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -167,6 +221,9 @@ void launch_light_test(hipStream_t s, const DevLight& L, int index, size_t n, co
 void launch_bsdf_test(hipStream_t s, const Material& m, size_t n, const float* ng, const float* ns, const float* dpdu, const float* wo,
                       const float* wi_or_u, int sample, float* out) {
     hipLaunchKernelGGL(k_bsdf_test, dim3(blocks_for(n, 256)), dim3(256), 0, s, m, n, ng, ns, dpdu, wo, wi_or_u, sample, out);
+}
+void launch_surface_test(hipStream_t s, const DevScene& sc, size_t n, const float4* rayO, const float4* rayD, const int* hit_word, int route, float* out) {
+    hipLaunchKernelGGL(k_surface_test, dim3(blocks_for(n, 256)), dim3(256), 0, s, sc, n, rayO, rayD, hit_word, route, out);
 }
 void launch_pack_rays(hipStream_t s, size_t n, const float* o, const float* d, float4* rayO, float4* rayD) {
     hipLaunchKernelGGL(k_pack_rays, dim3(blocks_for(n, 256)), dim3(256), 0, s, n, o, d, rayO, rayD);

@@ -134,6 +134,49 @@ yk_status yk_trace_closest(yk_context* ctx, const yk_scene* scene, size_t n, con
     return YK_OK;
 } YK_CATCH(ctx)
 
+yk_status yk_surface(yk_context* ctx, const yk_scene* scene, size_t n, const float* ray_o, const float* ray_d, int32_t route, float* out) try {
+    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
+    YK_LOCK(ctx);
+    if (!scene || !ray_o || !ray_d || !out || n == 0) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null argument");
+    if (route != 0 && route != 1) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "route: 0 = by leaf-order slot (hit_surface_prim), 1 = by source shape (hit_surface)");
+    if (yk_status rs = scene_on_context(ctx, scene, "")) return rs;
+    if (n > 0xFFFFFF00ull / YK_SURFACE_FLOATS) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "too many rays");
+    Staging sg(ctx);
+    hipStream_t st = sg.stream;
+    yk_status wb;
+    if ((wb = ensure_work_buffers(ctx, ctx->ws[0], n, scene->n_lights, scene->n_delta_lights)) != YK_OK) return wb;
+    if ((wb = ensure_spill(ctx, ctx->ws[0])) != YK_OK) return wb;
+    const float* d_o = sg.upload(ray_o, n * 3);
+    const float* d_d = sg.upload(ray_d, n * 3);
+    float* d_out = sg.output(out, n * YK_SURFACE_FLOATS);
+    if (!sg.ok()) return sg.status();
+    PathBuffers pb = path_buffers(ctx->ws[0], 0);
+    launch_pack_rays(st, n, d_o, d_d, pb.rayO, pb.rayD);
+    unsigned* ctrl = ctx->ws[0].ctrl.as<unsigned>();
+    HIP_TRY(ctx, hipMemsetAsync(ctrl, 0, YK_CTRL_WORDS * 4, st));
+    unsigned nn = (unsigned)n;
+    HIP_TRY(ctx, hipMemcpyAsync(ctrl, &nn, 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    // the closest-hit kernel as the render loop launches it (no t_max, no hit_out): hit word = leaf-order slot | kind bits
+    launch_trace_closest(st, trace_grid(ctx), dev_scene_for(scene, n), pb.rayO, pb.rayD, nullptr, ctrl, ctrl + YK_CTRL_HEADS, ctx->ws[0].hit.as<int>(), nullptr,
+                         nullptr, ctx->ws[0].spill.as<uint2>(), trace_grid(ctx) * trace_block_size(), ctrl, nullptr);
+    HIP_TRY(ctx, hipGetLastError());
+    std::vector<int32_t> words(n);
+    unsigned host_ctrl[4];
+    HIP_TRY(ctx, hipMemcpyAsync(words.data(), ctx->ws[0].hit.p, n * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(host_ctrl, ctrl, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (host_ctrl[YK_CTRL_ERR] & 1u) return fail(ctx, YK_ERR_STACK_OVERFLOW, "BVH traversal stack exceeded 64 entries (bvh.rs:174)");
+    const HostBvh* tree = scene_host_tree(scene);  // the surface kernel indexes the leaf-order records by these words: none may lie outside them
+    if (!tree) return fail(ctx, YK_ERR_DEVICE, "the scene's shape order could not be copied back from the device");
+    for (size_t i = 0; i < n; ++i)
+        if (words[i] != -1 && (words[i] < 0 || ((uint32_t)words[i] & YK_HIT_PRIM_MASK) >= tree->shape_order.size()))
+            return fail(ctx, YK_ERR_DEVICE, "yk_surface: ray " + std::to_string(i) + " got hit word " + std::to_string(words[i]));
+    launch_surface_test(st, dev_scene_for(scene, n), n, pb.rayO, pb.rayD, ctx->ws[0].hit.as<int>(), route, d_out);
+    sg.check(hipGetLastError());
+    return sg.finish();
+} YK_CATCH(ctx)
+
 yk_status yk_trace_any(yk_context* ctx, const yk_scene* scene, size_t n, const float* ray_o, const float* ray_d, const float* t_max,
                        const int32_t* area_light, uint8_t* out_hit) try {
     if (!ctx) return YK_ERR_INVALID_ARGUMENT;
