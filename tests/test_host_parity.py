@@ -174,3 +174,19 @@ def test_parallel_bvh_build_is_the_sequential_one(yk, oracle, method, max_shapes
         assert n.tobytes() == n_ref.tobytes(), threads
         assert np.array_equal(o, o_ref), threads
         assert hs.info().n_nodes == len(n_ref)
+
+
+@pytest.mark.parametrize("method,max_shapes", [(abi.SPLIT_SAH, 1), (abi.SPLIT_MIDDLE, 4), (abi.SPLIT_EQUAL_COUNTS, 2)])
+def test_threaded_reductions_of_a_long_range_build_the_sequential_tree(yk, oracle, method, max_shapes, monkeypatch):
+    """A range of 2^18 shapes or more has its bounds, centroid bounds and SAH buckets reduced by several
+    threads: the root range of this scene is one, and the tree still equals the oracle's sequential
+    builder's, node for node, for every thread count."""
+    sd = scenes.city((16, 13), 3, 1, "mixed")  # 266,252 triangles
+    sd.split_method, sd.max_shapes_in_node = method, max_shapes
+    assert sd.n_triangles >= 1 << 18
+    n_ref, o_ref = oracle.OracleScene(sd).export_bvh()
+    for threads in ("1", "3", "16"):
+        monkeypatch.setenv("YK_BVH_THREADS", threads)
+        n, o = yk.Scene(None, sd).export_bvh()
+        assert n.tobytes() == n_ref.tobytes(), threads
+        assert np.array_equal(o, o_ref), threads

@@ -1,5 +1,5 @@
 #!/bin/bash
-# ThreadSanitizer run of the parallel host BVH builder (yk_host.cpp) on 200 k random boxes, every split method.
+# ThreadSanitizer run of the parallel host BVH builder (yk_host.cpp) on 300 k random boxes, every split method.
 set -e
 ROOT=$(cd "$(dirname "$0")/../.." && pwd)
 OUT=${TMPDIR:-/tmp}/yk_tsan

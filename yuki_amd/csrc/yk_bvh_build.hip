@@ -1,10 +1,9 @@
 // yk_bvh_build.hip — the level-synchronous BVH builder (yk_bvh_build.h): its gfx950 kernels and driver
 // (build_bvh_device) and the host instance of the same algorithm (build_bvh_levels).  Both return the
-// host recursion's tree (yk_host.cpp) or refuse with a reason; neither changes `out` when it refuses.
+// one tree that every builder builds (yk_bvh_build.h) or refuse with a reason; neither changes `out` when it refuses.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -22,7 +21,7 @@ const int kLevelThreads = 512;  // one block per open range
 // ------------------------------------------------------------------ the two executors of level_range
 struct HostExec {
     uint32_t tid = 0, nt = 1;
-    Shared* sh;
+    Shared* sh = nullptr;
     void sync() {}
     void sync_memory() {}
     template <int NB> void all_reduce(Box (&b)[NB], uint32_t (&cnt)[NB]) {
@@ -115,14 +114,14 @@ struct DevExec {
 __global__ void k_prepare(const float* __restrict__ sb, uint32_t n, Prims p, uint32_t* bad) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    bool ok = true;
+    const float* b = sb + 6 * (size_t)i;
+    const float lo[3] = {b[0], b[1], b[2]}, hi[3] = {b[3], b[4], b[5]};
+    float c[3];
+    const bool ok = prim_from_bound(lo, hi, c);
     for (int k = 0; k < 3; ++k) {
-        const float lo = sb[6 * (size_t)i + k], hi = sb[6 * (size_t)i + 3 + k];
-        const float c = lo + ((hi - lo) / 0.5f);
-        p.bmin[k][i] = lo;
-        p.bmax[k][i] = hi;
-        p.c[k][i] = c;
-        ok = ok && fabsf(lo) <= 3.40282347e+38f && fabsf(hi) <= 3.40282347e+38f && fabsf(c) <= 3.40282347e+38f;
+        p.bmin[k][i] = lo[k];
+        p.bmax[k][i] = hi[k];
+        p.c[k][i] = c[k];
     }
     p.shape[i] = i;
     if (!ok) *bad = 1u;
@@ -338,13 +337,12 @@ bool build_bvh_levels(const std::vector<ShapeBounds>& sb, uint32_t max_shapes, u
     }
     p.shape = shape.data();
     for (uint32_t i = 0; i < N; ++i) {
+        float c[3];
+        if (!prim_from_bound(sb[i].bmin, sb[i].bmax, c)) return refuse(bi, YK_BVH_REASON_NON_FINITE);
         for (int k = 0; k < 3; ++k) {
-            const float lo = sb[i].bmin[k], hi = sb[i].bmax[k];
-            const float c = lo + ((hi - lo) / 0.5f);
-            if (!std::isfinite(lo) || !std::isfinite(hi) || !std::isfinite(c)) return refuse(bi, YK_BVH_REASON_NON_FINITE);
-            p.bmin[k][i] = lo;
-            p.bmax[k][i] = hi;
-            p.c[k][i] = c;
+            p.bmin[k][i] = sb[i].bmin[k];
+            p.bmax[k][i] = sb[i].bmax[k];
+            p.c[k][i] = c[k];
         }
         shape[i] = i;
     }
@@ -413,24 +411,18 @@ bool build_bvh_levels(const std::vector<ShapeBounds>& sb, uint32_t max_shapes, u
     return true;
 }
 
+// The block partition on flags given one by one: `order` is the array, its key the flag of the position.
+namespace {
+struct PlanArray {
+    const uint8_t* pass;
+    uint32_t* order;
+    bool key(uint32_t i) const { return pass[i] != 0; }
+    void swap(uint32_t i, uint32_t j) const { std::swap(order[i], order[j]); }
+};
+}  // namespace
 extern "C" size_t yk_bvh_partition_plan(const uint8_t* pass, size_t n, uint32_t* order) {
     if (!pass || !order || n == 0 || n > 0x7fffffffu) return 0;
-    const uint32_t start = 0, end = (uint32_t)n;
     std::vector<uint32_t> list(n);
     HostExec ex;
-    uint32_t n_pass = 0;
-    for (uint32_t base = start; base < end; base += ex.nt) {  // the loop of level_range
-        const uint32_t i = base + ex.tid;
-        const bool flag = pass[i] != 0;
-        uint32_t total;
-        const uint32_t before = n_pass + ex.scan(flag, total);
-        list[part_list_slot(start, end, i, flag, before)] = i;
-        n_pass += total;
-    }
-    const uint32_t pairs = std::min(n_pass, end - n_pass);
-    for (uint32_t k = 0; k < pairs; ++k) {
-        uint32_t f, t;
-        if (part_swap_pair(list.data(), start, end, n_pass, k, f, t)) std::swap(order[f], order[t]);
-    }
-    return n_pass;
+    return block_partition(ex, PlanArray{pass, order}, list.data(), 0u, (uint32_t)n, [](bool passes) { return passes; });
 }

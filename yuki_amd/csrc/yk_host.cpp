@@ -23,6 +23,7 @@
 #include <utility>
 
 #include "yk_bsdf.h"
+#include "yk_bvh_build.h"
 #include "yk_libm.h"
 #include "yk_math.h"
 
@@ -238,101 +239,25 @@ struct Prim {
     float c[3];  // "centroid" = p_min + diagonal/0.5 (sic, bvh.rs:56)
 };
 
-struct Box {
-    float lo[3], hi[3];
+using lv::Box;
+using lv::box_add;
+using lv::box_empty;
+using lv::kBuckets;
+
+struct PrimKeys {  // the primitive array as select_nth and swap_partition take it (yk_bvh_build.h)
+    Prim* a;
+    int axis;
+    float key(size_t i) const { return a[i].c[axis]; }
+    void swap(size_t i, size_t j) const { std::swap(a[i], a[j]); }
 };
-inline Box box_empty() {
-    const float big = 3.40282347e+38f;
-    return Box{{big, big, big}, {-big, -big, -big}};
-}
-inline void box_add_box(Box& b, const float* lo, const float* hi) {
+
+void put_box(yk_bvh_node& n, const Box& b) {
     for (int k = 0; k < 3; ++k) {
-        b.lo[k] = rmin(b.lo[k], lo[k]);
-        b.hi[k] = rmax(b.hi[k], hi[k]);
+        n.bmin[k] = b.lo[k];
+        n.bmax[k] = b.hi[k];
     }
 }
-inline void box_add_point(Box& b, const float* p) {
-    for (int k = 0; k < 3; ++k) {
-        b.lo[k] = rmin(b.lo[k], p[k]);
-        b.hi[k] = rmax(b.hi[k], p[k]);
-    }
-}
-// bounds.rs:134-138
-inline float box_area(const Box& b) {
-    float dx = b.hi[0] - b.lo[0], dy = b.hi[1] - b.lo[1], dz = b.hi[2] - b.lo[2];
-    return 2.0f * (dx * dy + dz * dy + dx * dz);
-}
-// bounds.rs:147-156
-inline int box_max_extent(const Box& b) {
-    float dx = b.hi[0] - b.lo[0], dy = b.hi[1] - b.lo[1], dz = b.hi[2] - b.lo[2];
-    if (dx > dy && dx > dz) return 0;
-    if (dy > dz) return 1;
-    return 2;
-}
-
-const size_t kNoSplit = (size_t)-1;
-const int kBuckets = 12;
-
-// SAH bucket of a primitive: impl_bounds.rs offset() then `(12*o).max(0) as usize`
-inline int sah_bucket(const Box& cb, const Prim& p, int axis) {
-    float o = p.c[axis] - cb.lo[axis];
-    if (cb.hi[axis] != cb.lo[axis]) o /= cb.hi[axis] - cb.lo[axis];
-    float bf = (float)kBuckets * o;
-    float m = rmax(bf, 0.0f);
-    if (m != m) return 0;
-    if (m >= (float)kBuckets) return kBuckets - 1;
-    int b = (int)m;
-    return b < kBuckets - 1 ? b : kBuckets - 1;
-}
-
-// two-ended swap partition (the algorithm of itertools::partition)
-template <class Pred> size_t swap_partition(Prim* a, size_t lo, size_t hi, Pred pred) {
-    size_t count = 0, front = lo, back = hi;
-    while (front < back) {
-        size_t f = front++;
-        if (!pred(a[f])) {
-            bool swapped = false;
-            while (front < back) {
-                size_t b = --back;
-                if (pred(a[b])) {
-                    std::swap(a[f], a[b]);
-                    swapped = true;
-                    break;
-                }
-            }
-            if (!swapped) return count;
-        }
-        ++count;
-    }
-    return count;
-}
-
-// "select_nth spec" (DESIGN.md): 3-way quickselect, middle pivot, on c[axis]
-void select_nth(Prim* a, size_t lo, size_t hi, size_t k, int axis) {
-    while (hi - lo > 1) {
-        const float pivot = a[lo + (hi - lo) / 2].c[axis];
-        size_t i = lo, lt = lo, gt = hi;
-        while (i < gt) {
-            const float v = a[i].c[axis];
-            if (v < pivot) {
-                std::swap(a[lt], a[i]);
-                ++lt;
-                ++i;
-            } else if (v > pivot) {
-                --gt;
-                std::swap(a[i], a[gt]);
-            } else {
-                ++i;
-            }
-        }
-        if (k < lt)
-            hi = lt;
-        else if (k >= gt)
-            lo = gt;
-        else
-            return;
-    }
-}
+Box child_box(const yk_bvh_node& n0, const yk_bvh_node& n1) { return lv::child_union(n0.bmin, n0.bmax, n1.bmin, n1.bmax); }
 
 // fn(chunk_index, lo, hi) on `threads` contiguous chunks of [start, end), chunk 0 on the caller
 template <class Fn> void for_chunks(size_t start, size_t end, unsigned threads, Fn fn) {
@@ -371,87 +296,62 @@ struct Builder {
         auto one = [&](size_t lo, size_t hi) {
             Box b = box_empty();
             if (centroids)
-                for (size_t i = lo; i < hi; ++i) box_add_point(b, prims[i].c);
+                for (size_t i = lo; i < hi; ++i) box_add(b, prims[i].c, prims[i].c);
             else
-                for (size_t i = lo; i < hi; ++i) box_add_box(b, prims[i].bmin, prims[i].bmax);
+                for (size_t i = lo; i < hi; ++i) box_add(b, prims[i].bmin, prims[i].bmax);
             return b;
         };
         if (par_threads <= 1 || end - start < kParallelRange) return one(start, end);
         Box part[kMaxThreads];
         for_chunks(start, end, par_threads, [&](unsigned t, size_t lo, size_t hi) { part[t] = one(lo, hi); });
         Box b = part[0];
-        for (unsigned t = 1; t < par_threads; ++t) box_add_box(b, part[t].lo, part[t].hi);
+        for (unsigned t = 1; t < par_threads; ++t) box_add(b, part[t].lo, part[t].hi);
         return b;
     }
 
-    size_t split_equal_counts(size_t start, size_t end, int axis) {
-        size_t mid = (start + end) / 2;
-        select_nth(prims, start, end, mid, axis);
-        return mid;
+    // ---- the steps of lv::split_range
+    void reduce(size_t start, size_t end, Box& bounds, Box& cb) const {
+        bounds = range_bounds(start, end, false);
+        cb = range_bounds(start, end, true);
     }
-    size_t split_middle(const Box& cb, size_t start, size_t end, int axis) {
-        const float mid_value = (cb.lo[axis] + cb.hi[axis]) / 2.0f;
-        return swap_partition(prims, start, end, [&](const Prim& p) { return p.c[axis] < mid_value; }) + start;
-    }
-    size_t split_sah(const Box& bounds, const Box& cb, size_t start, size_t end, int axis) {
+    int sah_best(size_t start, size_t end, int axis, float cl, float ch, const Box& bounds) const {
         const size_t n = end - start;
-        if (n <= 2) return start;
-        size_t counts[kBuckets];
+        auto fill = [&](size_t lo, size_t hi, uint32_t* cnt, Box* bx) {
+            for (size_t i = lo; i < hi; ++i) {
+                int b = lv::sah_bucket(cl, ch, prims[i].c[axis]);
+                cnt[b] += 1;
+                box_add(bx[b], prims[i].bmin, prims[i].bmax);
+            }
+        };
+        uint32_t counts[kBuckets];
         Box boxes[kBuckets];
         for (int b = 0; b < kBuckets; ++b) {
             counts[b] = 0;
             boxes[b] = box_empty();
         }
-        auto fill = [&](size_t lo, size_t hi, size_t* cnt, Box* bx) {
-            for (size_t i = lo; i < hi; ++i) {
-                int b = sah_bucket(cb, prims[i], axis);
-                cnt[b] += 1;
-                box_add_box(bx[b], prims[i].bmin, prims[i].bmax);
-            }
-        };
         if (par_threads <= 1 || n < kParallelRange) {
             fill(start, end, counts, boxes);
         } else {
-            std::vector<size_t> pc((size_t)par_threads * kBuckets, 0);
+            std::vector<uint32_t> pc((size_t)par_threads * kBuckets, 0);
             std::vector<Box> pb((size_t)par_threads * kBuckets, box_empty());
             for_chunks(start, end, par_threads, [&](unsigned t, size_t lo, size_t hi) { fill(lo, hi, &pc[(size_t)t * kBuckets], &pb[(size_t)t * kBuckets]); });
             for (unsigned t = 0; t < par_threads; ++t)
                 for (int b = 0; b < kBuckets; ++b) {
                     counts[b] += pc[(size_t)t * kBuckets + b];
-                    box_add_box(boxes[b], pb[(size_t)t * kBuckets + b].lo, pb[(size_t)t * kBuckets + b].hi);
+                    box_add(boxes[b], pb[(size_t)t * kBuckets + b].lo, pb[(size_t)t * kBuckets + b].hi);
                 }
         }
-        float best_cost = 0.0f;
-        int best = 0;
-        const float denom = rmax(box_area(bounds), 1e-10f);
-        for (int i = 0; i < kBuckets - 1; ++i) {
-            Box b0 = box_empty(), b1 = box_empty();
-            size_t c0 = 0, c1 = 0;
-            for (int j = 0; j <= i; ++j) {
-                box_add_box(b0, boxes[j].lo, boxes[j].hi);
-                c0 += counts[j];
-            }
-            for (int j = i + 1; j < kBuckets; ++j) {
-                box_add_box(b1, boxes[j].lo, boxes[j].hi);
-                c1 += counts[j];
-            }
-            float cost = 1.0f + ((float)c0 * box_area(b0) + (float)c1 * box_area(b1)) / denom;
-            if (i == 0 || cost < best_cost) {  // min_by keeps the first minimum
-                best_cost = cost;
-                best = i;
-            }
-        }
-        if (best_cost < (float)n)
-            return swap_partition(prims, start, end, [&](const Prim& p) { return sah_bucket(cb, p, axis) <= best; }) + start;
-        return kNoSplit;
+        return lv::sah_choose(counts, boxes, bounds, (uint32_t)n);
+    }
+    size_t partition(size_t start, size_t end, int axis, const lv::Pass& pass) const { return lv::swap_partition(PrimKeys{prims, axis}, start, end, pass); }
+    bool select_nth(size_t start, size_t end, size_t mid, int axis) const {
+        lv::select_nth(PrimKeys{prims, axis}, start, end, mid);
+        return true;
     }
 
     uint32_t emit_leaf(const Box& b, size_t start, size_t end) {
         yk_bvh_node n;
-        for (int k = 0; k < 3; ++k) {
-            n.bmin[k] = b.lo[k];
-            n.bmax[k] = b.hi[k];
-        }
+        put_box(n, b);
         n.a = (uint32_t)out->shape_order.size();
         n.count = (uint16_t)(end - start);
         n.axis = 0;
@@ -478,40 +378,18 @@ struct Builder {
             return (uint32_t)out->nodes.size() - 1;
         }
         if (depth > out->depth) out->depth = depth;
-        const Box bounds = range_bounds(start, end, false);
-        const size_t n = end - start;
-        if (n <= max_shapes) return emit_leaf(bounds, start, end);
-        const Box cb = range_bounds(start, end, true);
-        const int axis = box_max_extent(cb);
-        if (cb.hi[axis] == cb.lo[axis]) return emit_leaf(bounds, start, end);
-        size_t mid;
-        if (method == YK_SPLIT_SAH) {
-            mid = split_sah(bounds, cb, start, end, axis);
-            if (!(mid != start && mid != end)) mid = split_equal_counts(start, end, axis);
-        } else if (method == YK_SPLIT_MIDDLE) {
-            mid = split_middle(cb, start, end, axis);
-            if (!(mid != start && mid != end)) mid = split_equal_counts(start, end, axis);
-        } else {
-            mid = split_equal_counts(start, end, axis);
-        }
-        if (mid == start) {
-            out->split_failed = true;
-            return emit_leaf(bounds, start, end);
-        }
-        if (mid == kNoSplit) return emit_leaf(bounds, start, end);
+        const lv::Split<size_t> s = lv::split_range(*this, max_shapes, method, start, end);
+        if (s.split_failed) out->split_failed = true;
+        if (s.leaf) return emit_leaf(end - start > max_shapes ? s.bounds : range_bounds(start, end, false), start, end);
         const uint32_t self = (uint32_t)out->nodes.size();
         out->nodes.push_back(yk_bvh_node());
-        const uint32_t c0 = build(start, mid, depth + 1);
-        const uint32_t c1 = build(mid, end, depth + 1);
-        yk_bvh_node n0 = out->nodes[c0], n1 = out->nodes[c1];
+        const uint32_t c0 = build(start, s.mid, depth + 1);
+        const uint32_t c1 = build(s.mid, end, depth + 1);
         yk_bvh_node me;
-        for (int k = 0; k < 3; ++k) {  // BVHBuildNode::interior: child0.bounds.union_b(child1.bounds)
-            me.bmin[k] = rmin(n0.bmin[k], n1.bmin[k]);
-            me.bmax[k] = rmax(n0.bmax[k], n1.bmax[k]);
-        }
+        put_box(me, child_box(out->nodes[c0], out->nodes[c1]));
         me.a = c1;
         me.count = 0;
-        me.axis = (uint8_t)axis;
+        me.axis = (uint8_t)s.axis;
         me.is_leaf = 0;
         out->nodes[self] = me;
         return self;
@@ -520,13 +398,14 @@ struct Builder {
 
 }  // namespace
 
-// The build is the reference's recursion (bvh.rs:305-420), node for node.  For large inputs the
+// The build is the reference's recursion (bvh.rs:305-420), node for node; how a range splits is
+// lv::split_range (yk_bvh_build.h), which every builder shares.  For large inputs the
 // recursion is cut where a range holds at most n / (8 * threads) shapes: the top of the tree is
 // built on the calling thread exactly as before (same partitions in the same order on the same
 // data), the cut-off ranges — disjoint slices of the primitive array, which nothing else touches
 // — are built by worker threads into arenas of their own, and the arenas are spliced back in
 // depth-first order with their node and shape indices rebased.  The result is the sequential
-// build's, bit for bit (tests/test_bvh.py compares it with the oracle's sequential builder).
+// build's, bit for bit (tests/test_host_parity.py compares it with the oracle's sequential builder).
 void build_bvh(const std::vector<ShapeBounds>& bounds, uint32_t max_shapes_in_node, uint32_t split_method, HostBvh& out) {
     out.nodes.clear();
     out.shape_order.clear();
@@ -541,8 +420,8 @@ void build_bvh(const std::vector<ShapeBounds>& bounds, uint32_t max_shapes_in_no
         for (int k = 0; k < 3; ++k) {
             p.bmin[k] = bounds[i].bmin[k];
             p.bmax[k] = bounds[i].bmax[k];
-            p.c[k] = p.bmin[k] + ((p.bmax[k] - p.bmin[k]) / 0.5f);
         }
+        lv::prim_from_bound(p.bmin, p.bmax, p.c);  // non-finite bounds are built like any other here
     }
     Builder b;
     b.prims = prims.data();
@@ -631,11 +510,7 @@ void build_bvh(const std::vector<ShapeBounds>& bounds, uint32_t max_shapes_in_no
         if (tn.is_leaf) continue;
         yk_bvh_node& me = out.nodes[final_index[i]];
         const uint32_t c0 = final_index[i + 1], c1 = final_index[tn.a];
-        const yk_bvh_node &n0 = out.nodes[c0], &n1 = out.nodes[c1];
-        for (int k = 0; k < 3; ++k) {  // BVHBuildNode::interior: child0.bounds.union_b(child1.bounds)
-            me.bmin[k] = rmin(n0.bmin[k], n1.bmin[k]);
-            me.bmax[k] = rmax(n0.bmax[k], n1.bmax[k]);
-        }
+        put_box(me, child_box(out.nodes[c0], out.nodes[c1]));
         me.a = c1;
     }
     if (tm) std::fprintf(stderr, "[bvh] top %.3f s (%zu tasks, grain %zu), subtrees %.3f s on %u threads, splice %.3f s\n", t1 - t0, tasks.size(), b.grain, t2 - t1, n_threads, now() - t2);
