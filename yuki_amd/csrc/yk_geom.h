@@ -385,9 +385,15 @@ struct LightSample {
     int area_light;  // identity of the sampled area light or -1
 };
 
+// Whether sample_light reads (ux, uy) for a light of this kind: the point, spot and distant lights have one position or
+// direction to offer.  sample_light lets the sample in through this predicate alone, so a caller that asks it and skips the
+// draw (sampler_skip_2d) sees what every caller sees.
+YK_HD bool light_reads_sample(uint32_t kind) { return kind == YK_LIGHT_RECT; }
+
 // Light::sample_li — point_light.rs:27-50, spot_light.rs:38-80,
 // distant_light.rs:24-43, rectangular_light.rs:46-71
 YK_HD LightSample sample_light(const DevLight& L, int index, V3 sp, float ux, float uy) {
+    if (!light_reads_sample(L.kind)) ux = uy = 0.0f;
     LightSample s;
     s.has_vis = true;
     s.area_light = -1;

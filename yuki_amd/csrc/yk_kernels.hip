@@ -233,11 +233,6 @@ __global__ void k_accumulate(RenderParams prm, PathBuffers cur, BounceQueues q, 
         const unsigned sid = sid_base + pend_slot(p);
         RGB beta = RGB{1.0f, 1.0f, 1.0f};  // the throughput the vertex was entered with (one at the camera's); a miss adds its term as it is
         if (!first && !(kind & YK_PEND_MISS)) beta = path_beta(cur.thru[i]);
-        RGB L = RGB{0.0f, 0.0f, 0.0f};
-        if (!first) {
-            const float4 acc = sample_buf[sid];
-            L = RGB{acc.x, acc.y, acc.z};
-        }
         RGB radiance = RGB{0.0f, 0.0f, 0.0f};
         if (!(kind & YK_PEND_MISS)) {
             const unsigned vs = YK_VIS_STRIDE(nl);
@@ -251,7 +246,18 @@ __global__ void k_accumulate(RenderParams prm, PathBuffers cur, BounceQueues q, 
                 }
             }
         }
-        L = vertex_accumulate(prm, L, beta, radiance, RGB{p.x, p.y, p.z}, kind);
+        const RGB add = vertex_addend(prm, beta, radiance, RGB{p.x, p.y, p.z}, kind);
+        // A vertex after the camera's that adds +-0 in every component leaves the slot as it is, bit for bit: the slot never
+        // holds -0 (the first pass writes +0 + x, and a sum is -0 only when both operands are), so it is neither read nor
+        // written.  Decided from the product itself: a NaN or an infinity in beta is no zero and goes through.  `L + add` is
+        // the former `L + beta * radiance` bit for bit because the library is built with -ffp-contract=off (no fused multiply-add).
+        if (!first && !(kind & YK_PEND_MISS) && is_black(add)) continue;
+        RGB L = RGB{0.0f, 0.0f, 0.0f};
+        if (!first) {
+            const float4 acc = sample_buf[sid];
+            L = RGB{acc.x, acc.y, acc.z};
+        }
+        L = L + add;
         sample_buf[sid] = make_float4(L.r, L.g, L.b, 0.0f);
     }
 }

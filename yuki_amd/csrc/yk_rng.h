@@ -263,5 +263,15 @@ YK_HD void sampler_get_2d(const SamplerCfg& c, SamplerState& s, float& ux, float
     ux = ((float)x + dx) / (float)c.nx;
     uy = ((float)y + dy) / (float)c.ny;
 }
+// sampler_get_2d for a caller that ignores the values: the same state afterwards (two dimensions consumed; the PCG stepped
+// twice where get_2d draws from it — always for Uniform, for the jitter of Stratified), without the hash, the permutation
+// and the divisions that only the values need
+YK_HD void sampler_skip_2d(const SamplerCfg& c, SamplerState& s) {
+    s.dimension += 2;
+    if (c.kind == 0 || c.jitter) {
+        (void)pcg_next(s.rng);
+        (void)pcg_next(s.rng);
+    }
+}
 
 }  // namespace yk

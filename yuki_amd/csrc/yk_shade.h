@@ -83,11 +83,21 @@ __device__ __forceinline__ NeeSample nee_none() {
     r.al = -1;
     return r;
 }
+// The two sampler dimensions of a light (path.rs:102, whitted.rs:113): consumed whether or not the light contributes, and
+// whether or not it reads them — only a light that does (light_reads_sample, yk_geom.h) has their values computed, the
+// others get zeros.  The light is the same for the whole wave: no lane disagrees about the branch.
+__device__ __forceinline__ void light_draw_2d(const SamplerCfg& c, SamplerState& st, const DevLight& L, float& ux, float& uy) {
+    ux = uy = 0.0f;  // only defines the outputs of a skipped draw; what keeps caller and callee together is sample_light's own gate
+    if (light_reads_sample(L.kind))
+        sampler_get_2d(c, st, ux, uy);
+    else
+        sampler_skip_2d(c, st);
+}
 template <bool RAY_ALWAYS = false>
 __device__ __forceinline__ NeeSample vertex_light(const DevScene& sc, const RenderParams& prm, SamplerState& st, unsigned l, const PathVertex& v) {
     NeeSample r = nee_none();
     float ux, uy;
-    sampler_get_2d(prm.sampler, st, ux, uy);
+    light_draw_2d(prm.sampler, st, sc.lights[l], ux, uy);
     LightSample ls = sample_light(sc.lights[l], (int)l, v.sf.p, ux, uy);
     if (!is_black(ls.li)) {
         RGB f = bsdf_f(v.mat, v.fr, v.sf.wo, ls.l);  // path.rs:105 uses si.wo
@@ -180,11 +190,15 @@ __device__ __forceinline__ VertexEnd vertex_finish(const DevScene& sc, const Ren
 
 // `incoming_radiance += beta * radiance` of one vertex (path.rs:102-129), the fold a vertex ends with: `radiance` holds
 // the unoccluded light contributions summed in light order; `beta` is the throughput the vertex was ENTERED with.
-__device__ __forceinline__ RGB vertex_accumulate(const RenderParams& prm, RGB L, RGB beta, RGB radiance, RGB term, unsigned kind) {
-    if (kind & YK_PEND_MISS) return L + term;
+// vertex_addend is what the vertex adds to the sample, vertex_accumulate the sum.
+__device__ __forceinline__ RGB vertex_addend(const RenderParams& prm, RGB beta, RGB radiance, RGB term, unsigned kind) {
+    if (kind & YK_PEND_MISS) return term;
     if (kind & YK_PEND_EMISSION) radiance = radiance + term;
     if (kind & YK_PEND_CLAMP) radiance = rgb_min(radiance, RGB{1.0f, 1.0f, 1.0f} * prm.clamp);
-    return L + beta * radiance;
+    return beta * radiance;
+}
+__device__ __forceinline__ RGB vertex_accumulate(const RenderParams& prm, RGB L, RGB beta, RGB radiance, RGB term, unsigned kind) {
+    return L + vertex_addend(prm, beta, radiance, term, kind);
 }
 
 }  // namespace yk

@@ -647,7 +647,7 @@ __global__ __launch_bounds__(BLOCK) void k_whitted(DevScene sc, RenderParams prm
                 RGB sum = RGB{0.0f, 0.0f, 0.0f};
                 for (unsigned l = 0; l < sc.n_lights; ++l) {  // whitted.rs:113-133, the fold of path.rs:102-119
                     float ux, uy;
-                    sampler_get_2d(prm.sampler, st, ux, uy);
+                    light_draw_2d(prm.sampler, st, sc.lights[l], ux, uy);
                     LightSample ls = sample_light(sc.lights[l], (int)l, sf.p, ux, uy);
                     if (is_black(ls.li)) continue;
                     RGB f = bsdf_f(mat, fr, sf.wo, ls.l);
