@@ -784,8 +784,9 @@ yk_status yk_denoise_device(yk_context* ctx, const yk_denoise_desc* desc, const 
  * Intended use: while a camera stands, every displayed frame is blend(R, film, samples) with R reprojected ONCE when the
  * camera moved (R NULL before the first move); the last blend's history output is the next move's previous history, and
  * the guides of that view are its previous guides.  Downstream passes take the blended RGB with samples = NULL.
- * Reprojected radiance is exact for diffuse surfaces only: on glass and metal it lags the view, for as long as
- * max_history lets it (a new sample always weighs at least m / (max_history + m)).
+ * Reprojected radiance is exact for diffuse surfaces only: on glass and metal it lags the view.  max_history is the
+ * loosest bound on that lag (a new sample always weighs at least m / (max_history + m)); yk_history_rectify, run before
+ * the blend, is the tight one: it clips a history the current frame contradicts and shrinks its count.
  * Reproject, current pixel P with guide G[P]:
  *   1. G[P] a miss: the all-zero record.
  *   2. p_cam = camera_to_world_inv' . p_P, r = raster_to_camera_inv' . p_cam (the point transform of Camera::ray; ' = the
@@ -856,8 +857,8 @@ yk_status yk_history_blend_device(yk_context* ctx, const yk_temporal_desc* desc,
  *   position, and the plane test d = dot(ns_P, p_Q - p'_P) runs in the previous frame's world, where the previous guides
  *   live — with the CURRENT normal: exact for a translation, approximate under a rotation (the error is the tap distance
  *   times the sine of the turn), and a surface that turns by more than acos(normal_cos_min) between two frames loses its
- *   history.  Carried radiance is the radiance the surface HAD: shadows and reflections of things that moved lag for as
- *   long as max_history lets them.
+ *   history.  Carried radiance is the radiance the surface HAD: shadows and reflections of things that moved lag until
+ *   yk_history_rectify (run after this pass, before the blend) clips them to the current frame, or max_history ends them.
  * Not handled: moving spheres or lights, yk_multi scenes. */
 #define YK_SURFACE_NONE 0xffffffffu
 typedef struct yk_surface_id {
@@ -1075,8 +1076,8 @@ yk_status yk_upsample_device(yk_context* ctx, const yk_upsample_desc* desc, cons
  *   the film whose variance is finite, renormalised (g = +inf where P's own variance is; sigma_variance = +inf: the stop is
  *   off); no / 2^i.  The variance travels with the colours: var' = sum(w*w * var_Q) / (sum w)^2 over the taken taps whose
  *   variance is finite; an infinite variance stays where it is and does not spread.
- * Limits: variance of luminance only; yk_multi scenes are not served; the temporal estimate inherits the history's lag on
- *   glass and metal. */
+ * Limits: variance of luminance only; yk_multi scenes are not served; the temporal estimate inherits what lag
+ *   yk_history_rectify leaves the history on glass and metal (it shrinks the moments' count with the history's). */
 typedef struct yk_moments {
     float m1;     /* the mean luminance */
     float m2;     /* the mean squared luminance of the frame means */
@@ -1121,6 +1122,50 @@ yk_status yk_denoise_variance(yk_context* ctx, const yk_variance_desc* desc, con
 yk_status yk_denoise_variance_device(yk_context* ctx, const yk_variance_desc* desc, const void* d_film_rgb, const void* d_guides,
                                      const void* d_variance, const void* d_albedo, uint16_t res_x, uint16_t res_y, uint16_t tile_dim,
                                      const uint32_t* samples, void* d_out_rgb, void* stream);
+
+/* ---- history rectification: carried radiance clipped to the current frame ----
+ * A carried history is right for the previous view, the previous lighting and the previous positions.  This pass compares
+ * it with the frame at hand, before yk_history_blend folds that frame in: after yk_history_reproject[_moved] when something
+ * moved, on the last blend's history while the view stands (lights and materials change under a still camera too).  The
+ * rule is stated next to each expression in yuki_amd/csrc/yk_rectify.h; the host and the device instance agree bit for bit
+ * (binary32, every operation separate, no FMA, division and sqrtf correctly rounded, a NaN an operation produces is
+ * 0x7fc00000, a value that is only copied keeps its bits).
+ * Per pixel P, with m_Q and c_Q the count and the colour of film pixel Q as yk_history_blend reads them (m = 1 and the
+ * film's bits without a table; with one, m = (float)samples[flat] and c divided by m where m > 0):
+ *   1. Taps: the (2 radius + 1)^2 pixels around P, row-major; taken when inside the film, m_Q != 0 and c_Q finite in all
+ *      three channels; k of them are.  A tap outside the film is never read.
+ *   2. The output is history[P]'s 16 bytes when the history is absent by the blend's test (n <= 0 or NaN, a channel not
+ *      finite), k < 2, a mu_c or e_c below is not finite, or no channel is clipped.
+ *   3. Per channel over the taken taps in tap order: mu = sum(c) / k; sigma = sqrtf(sum((c - mu)(c - mu)) / k);
+ *      e = gamma * sigma; lo = mu - e, hi = mu + e.
+ *   4. out_c = h_c < lo ? lo : (h_c > hi ? hi : h_c); f_c = e / |h_c - mu| for a clipped channel (in [0, 1]) and 1 for
+ *      any other; f = the least of the three.
+ *   5. n' = n * f: how much of the history the clip kept.  n' == 0 makes the history absent, and the blend starts over.
+ *   6. With moments: where the history was clipped and the moments record is present (n > 0, the other fields finite),
+ *      its n becomes n' (the history's bits) and its frames are multiplied by f; m1 and m2 keep their bits.  Every other
+ *      record is copied.
+ * Limits: a per-channel RGB box, no chroma space; m1 and m2 stay stale after a clip; a history that is wrong but lies inside
+ * the current frame's noise box stays; yk_multi scenes are not served. */
+typedef struct yk_rectify_desc {
+    uint32_t radius; /* 1 .. 3: the window is (2 radius + 1)^2 pixels */
+    float gamma;     /* >= 0: the half-width of the box in standard deviations; +inf: every pixel passes through */
+} yk_rectify_desc;
+/* film_rgb, `samples` and tile_dim as yk_history_blend takes them; moments may be NULL, and out_moments is NULL exactly
+ * then.  out_history may equal history and out_moments may equal moments: a pixel reads only its own records, the window
+ * reads the film.  ctx NULL = the host instance on the CPU, else on ctx's device (synchronous).
+ * YK_ERR_INVALID_ARGUMENT: a NULL desc, film, history or out_history, a zero resolution, tile_dim 0, a radius outside
+ * 1 .. 3, a gamma that is < 0 or NaN, out_moments without moments or moments without out_moments, an output that overlaps
+ * an input without being equal to its own counterpart, outputs that overlap each other. */
+yk_status yk_history_rectify(yk_context* ctx, const yk_rectify_desc* desc, const float* film_rgb, uint16_t res_x, uint16_t res_y,
+                             uint16_t tile_dim, const uint32_t* samples, const yk_history* history, const yk_moments* moments,
+                             yk_history* out_history, yk_moments* out_moments);
+/* The same on device buffers, enqueued on `stream` (NULL = the context's) without waiting for the device: one launch, and
+ * no allocation beyond the temporal pass's staged sample table (`samples` is a HOST table, copied before the call returns).
+ * d_film_rgb needs 4-byte alignment, the records 16-byte alignment (anything else: YK_ERR_INVALID_ARGUMENT, nothing is
+ * launched). */
+yk_status yk_history_rectify_device(yk_context* ctx, const yk_rectify_desc* desc, const void* d_film_rgb, uint16_t res_x, uint16_t res_y,
+                                    uint16_t tile_dim, const uint32_t* samples, const void* d_history, const void* d_moments,
+                                    void* d_out_history, void* d_out_moments, void* stream);
 
 /* ---- adaptive sampling: per-pixel statistics choose where the next samples go ----
  * The accumulating entry points give every pixel of a tile the same number of samples.  Here a film carries, beside its

@@ -326,6 +326,22 @@ inline void moments_blend_device(Context& ctx, const yk_temporal_desc& desc, con
                                  const void* d_moments, void* d_out_moments, void* stream = nullptr) {
     check(yk_moments_blend_device(ctx.handle(), &desc, d_film, res_x, res_y, tile_dim, samples, d_moments, d_out_moments, stream), ctx.handle());
 }
+// History rectification, before history_blend / moments_blend on every frame (the rule is stated in yuki_hip.h and
+// csrc/yk_rectify.h): the carried history clipped to the box of the current film around each pixel -> (history, moments);
+// moments may be nullptr, the second vector is then empty.  ctx == nullptr: the host instance.
+inline std::pair<std::vector<yk_history>, std::vector<Moments>> history_rectify(Context* ctx, const yk_rectify_desc& desc, const float* film, uint16_t res_x, uint16_t res_y, uint16_t tile_dim,
+                                                                                const uint32_t* samples, const yk_history* history, const Moments* moments = nullptr) {
+    std::vector<yk_history> out((size_t)res_x * res_y);
+    std::vector<Moments> out_m(moments ? (size_t)res_x * res_y : 0);
+    yk_context* c = ctx ? ctx->handle() : nullptr;
+    check(yk_history_rectify(c, &desc, film, res_x, res_y, tile_dim, samples, history, moments, out.data(), moments ? out_m.data() : nullptr), c);
+    return {std::move(out), std::move(out_m)};
+}
+// The same on device buffers (each output may be its own input; the moments both or neither), enqueued on `stream`: one launch.
+inline void history_rectify_device(Context& ctx, const yk_rectify_desc& desc, const void* d_film, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const uint32_t* samples,
+                                   const void* d_history, const void* d_moments, void* d_out_history, void* d_out_moments, void* stream = nullptr) {
+    check(yk_history_rectify_device(ctx.handle(), &desc, d_film, res_x, res_y, tile_dim, samples, d_history, d_moments, d_out_history, d_out_moments, stream), ctx.handle());
+}
 // The variance of the luminance of `film` as denoise_variance will filter it; moments and albedo may be nullptr.
 inline std::vector<float> variance(Context* ctx, const yk_variance_desc& desc, const Moments* moments, const float* film, const yk_guide* guides, const Albedo* albedo, uint16_t res_x,
                                    uint16_t res_y, uint16_t tile_dim, const uint32_t* samples = nullptr) {

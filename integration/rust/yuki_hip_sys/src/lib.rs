@@ -369,6 +369,16 @@ pub struct yk_upsample_desc {
     pub sigma_plane: f32,
 }
 
+/// The window and the box of the history rectification: the (2 radius + 1)^2 pixels of the current film around a pixel
+/// (radius 1 .. 3) and the half-width of the box in standard deviations (>= 0, +inf = every pixel passes through)
+/// (yuki_amd/csrc/yk_rectify.h)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct yk_rectify_desc {
+    pub radius: u32,
+    pub gamma: f32,
+}
+
 /// The target rectangle of ScaleOutput::draw in top-down window coordinates
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -620,6 +630,8 @@ extern "C" {
     pub fn yk_variance_device(ctx: *mut yk_context, desc: *const yk_variance_desc, d_moments: *const c_void, d_film_rgb: *const c_void, d_guides: *const c_void, d_albedo: *const c_void, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, d_out_variance: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_denoise_variance(ctx: *mut yk_context, desc: *const yk_variance_desc, film_rgb: *const f32, guides: *const yk_guide, variance: *const f32, albedo: *const yk_albedo, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, out_rgb: *mut f32) -> yk_status;
     pub fn yk_denoise_variance_device(ctx: *mut yk_context, desc: *const yk_variance_desc, d_film_rgb: *const c_void, d_guides: *const c_void, d_variance: *const c_void, d_albedo: *const c_void, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, d_out_rgb: *mut c_void, stream: *mut c_void) -> yk_status;
+    pub fn yk_history_rectify(ctx: *mut yk_context, desc: *const yk_rectify_desc, film_rgb: *const f32, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, history: *const yk_history, moments: *const yk_moments, out_history: *mut yk_history, out_moments: *mut yk_moments) -> yk_status;
+    pub fn yk_history_rectify_device(ctx: *mut yk_context, desc: *const yk_rectify_desc, d_film_rgb: *const c_void, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, d_history: *const c_void, d_moments: *const c_void, d_out_history: *mut c_void, d_out_moments: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_pixel_list_create(ctx: *mut yk_context, res_x: u16, res_y: u16, out: *mut *mut yk_pixel_list) -> yk_status;
     pub fn yk_pixel_list_destroy(list: *mut yk_pixel_list);
     pub fn yk_pixel_list_set(list: *mut yk_pixel_list, xy: *const u32, sample: *const u32, n: u32, passes: u32) -> yk_status;

@@ -181,6 +181,12 @@ class VarianceDesc(C.Structure):
     _fields_ = [("iterations", C.c_uint32), ("sigma_variance", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float), ("epsilon", C.c_float), ("spatial_scale", C.c_float)]
 
 
+class RectifyDesc(C.Structure):
+    """yk_rectify_desc: the window and the box of the history rectification (csrc/yk_rectify.h)."""
+
+    _fields_ = [("radius", C.c_uint32), ("gamma", C.c_float)]
+
+
 class AdaptiveDesc(C.Structure):
     """yk_adaptive_desc: the adaptive sampler's rule (csrc/yk_adaptive.h)."""
 

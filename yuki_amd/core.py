@@ -712,6 +712,49 @@ def variance(moments, film, guides, params, tile_dim=16, samples=None, ctx=None,
     return out
 
 
+# --------------------------------------------------------------------------- rectification (csrc/yk_rectify.h)
+# Per frame, before the blends: history = rectify_history(carried, film, rp, samples=...) — carried being the reprojected
+# history after a move and the last blend's history while the view stands — or, with moments,
+# history, moments = rectify_history(carried, film, rp, samples=..., moments=carried_moments); then blend_history and
+# blend_moments from the same film.
+@dataclass
+class RectifyParams:
+    """yk_rectify_desc: the window is (2 radius + 1)^2 pixels of the current film (radius 1 .. 3), the box mean +- gamma
+    standard deviations per channel (gamma >= 0; float("inf") lets every history through).  The defaults are the best row
+    of profiles/rectify_quality.json."""
+
+    radius: int = 2
+    gamma: float = 0.75
+
+    def as_struct(self):
+        return abi.RectifyDesc(int(self.radius), float(self.gamma))
+
+
+def _rectify_desc(params):
+    if not isinstance(params, RectifyParams):
+        raise TypeError("params is a RectifyParams")
+    return params.as_struct()
+
+
+def rectify_history(history, film, params, tile_dim=16, samples=None, moments=None, ctx=None):
+    """yk_history_rectify: the carried (h, w) abi.HISTORY_DTYPE history clipped to the box of the current view's (h, w, 3)
+    float32 film (with `samples` = Film.samples for an accumulating one, as blend_history takes it) -> the history for
+    blend_history; with the (h, w) abi.MOMENTS_DTYPE moments beside it -> (history, moments).  ctx None = the host
+    instance."""
+    film, w, h = _film(film)
+    d = _rectify_desc(params)
+    samples = _blend_samples((w, h), tile_dim, samples)
+    history = _records(history, abi.HISTORY_DTYPE, (w, h), "history")
+    out = np.zeros((h, w), dtype=abi.HISTORY_DTYPE)
+    out_m = None
+    if moments is not None:
+        moments = _records(moments, abi.MOMENTS_DTYPE, (w, h), "moments")
+        out_m = np.zeros((h, w), dtype=abi.MOMENTS_DTYPE)
+    c = ctx.h if ctx else None
+    check(lib().yk_history_rectify(c, C.byref(d), _p(film), w, h, int(tile_dim), _p(samples), _p(history), _p(moments), _p(out), _p(out_m)), c)
+    return out if moments is None else (out, out_m)
+
+
 # --------------------------------------------------------------------------- adaptive sampling (csrc/yk_adaptive.h)
 # film_sum (h, w, 3) float32 sums and stats (h, w) abi.PIXEL_STATS_DTYPE, both zeros when cleared.  Per round:
 # xy, sample = adaptive_select(stats, params); passes = the render of those entries (Integrator.render_pixel_list_device);
@@ -1242,6 +1285,15 @@ class Context:
         d = _temporal_desc(params)
         samples = _blend_samples(res, tile_dim, samples)
         check(lib().yk_moments_blend_device(self.h, C.byref(d), _vp(d_film_ptr), int(res[0]), int(res[1]), int(tile_dim), _p(samples), _vp(d_moments_ptr), _vp(d_out_moments_ptr), _vp(stream)), self.h)
+
+    def rectify_history_device(self, d_film_ptr, res, params, tile_dim, samples, d_history_ptr, d_out_history_ptr, stream=None, moments=None, out_moments=None):
+        """yk_history_rectify_device: device film + device history -> device history (may be the input), enqueued on
+        `stream` (default: the context's) without waiting; one launch.  moments / out_moments: the device pointers of the
+        moments beside the history and of their output (may be the same), both or neither.  `samples` is a host table (or
+        None), copied before the call returns."""
+        d = _rectify_desc(params)
+        samples = _blend_samples(res, tile_dim, samples)
+        check(lib().yk_history_rectify_device(self.h, C.byref(d), _vp(d_film_ptr), int(res[0]), int(res[1]), int(tile_dim), _p(samples), _vp(d_history_ptr), _vp(moments), _vp(d_out_history_ptr), _vp(out_moments), _vp(stream)), self.h)
 
     def variance_device(self, d_moments_ptr, d_film_ptr, d_guides_ptr, res, params, tile_dim, samples, d_out_ptr, stream=None, albedo=None):
         """yk_variance_device: device moments (or None), film, guides and albedo (or None) -> res[0] * res[1] device floats,

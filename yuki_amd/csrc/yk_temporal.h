@@ -11,9 +11,10 @@
 // below and agree bit for bit.
 //
 // Reprojected radiance is exact for view-independent (diffuse) surfaces only.  On glass and metal the carried mean is the
-// radiance towards the PREVIOUS eye: it lags the view, and max_history bounds how long — a new sample always weighs at
-// least m / (max_history + m).  Geometry that moves: tp_reproject_moved_pixel below, through the motion records of
-// yk_motion.h.
+// radiance towards the PREVIOUS eye: it lags the view.  max_history is the loosest bound on how long — a new sample always
+// weighs at least m / (max_history + m) — and yk_rectify.h, run before the blend, the tight one: it clips a history the
+// current frame contradicts and shrinks its count.  Geometry that moves: tp_reproject_moved_pixel below, through the motion
+// records of yk_motion.h.
 #pragma once
 #include "yk_denoise.h"
 #include "yk_math.h"
@@ -158,8 +159,8 @@ YK_HD void tp_reproject_pixel(const TpParams& a, const float* c2w_inv, const flo
 //   - nsP is the CURRENT shading normal, in the plane test and in the normal test.  The plane test is therefore exact for
 //     a translation and approximate under a rotation: the error is the tap distance times the sine of the turn.  A surface
 //     that turns by more than acos(normal_cos_min) between two frames loses its history.
-// Carried radiance is the radiance the surface HAD: shadows and reflections of things that moved lag, for as long as
-// max_history lets them.  A NaN in p_prev makes the projection's w a NaN (0 * NaN included): the zero record.
+// Carried radiance is the radiance the surface HAD: shadows and reflections of things that moved lag until yk_rectify.h
+// clips them to the current frame, or max_history ends them.  A NaN in p_prev makes the projection's w a NaN (0 * NaN included): the zero record.
 template <class Fetch>
 YK_HD void tp_reproject_moved_pixel(const TpParams& a, const float* c2w_inv, const float* r2c_inv, V3 nsP, float hitP, const float* mv, const Fetch& fetch, float* out) {
     tp_reproject_pixel(a, c2w_inv, r2c_inv, nsP, mv[3] == 0.0f ? 0.0f : hitP, V3{mv[0], mv[1], mv[2]}, fetch, out);

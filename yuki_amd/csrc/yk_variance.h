@@ -18,7 +18,8 @@
 // m1, m2 and frames are interpolated like colours — all three are linear in what they average.
 //
 // Limits: the variance is that of LUMINANCE only (a pixel noisy in chroma alone looks converged); yk_multi scenes are not
-// served; the temporal estimate inherits the lag of the history on glass and metal (yk_temporal.h).
+// served; the temporal estimate inherits what lag yk_rectify.h leaves the history on glass and metal (it shrinks the
+// moments' count with the history's; m1 and m2 it does not touch).
 #pragma once
 #include "yk_albedo.h"
 #include "yk_denoise.h"
