@@ -269,7 +269,8 @@ yk_status yk_context_interrupt(yk_context* ctx);
  * seconds in yk_render_stats for jobs of at least 2^20 samples | 2: always),
  * "packet_bounces" / "packet_shadow_bounces" (leading bounces traced by the wave-packet
  * kernels), "overlap_shadow" (0|1), "shade_reorder" (0|1: paths of a shade block dealt to
- * lanes by material kind), "top_nodes" (tree-top nodes the traversal kernels keep
+ * lanes by material kind), "nee_skip" (a bit mask, 0 | 2, default 2: bit 2 — a shadow ray whose contribution
+ * is +-0 in every component is counted in shadow_rays but not traced; 0 traces every ray), "top_nodes" (tree-top nodes the traversal kernels keep
  * in LDS, 0..1023; the kernels hold at most what they were built for), "wide_bvh" (0: binary nodes only | 1: traverse the 4-wide collapse of the
  * BVH | 2, default: keep both, jobs of up to 6 M paths use the 4-wide one), "bvh_builder" (0, default: the
  * tree is built by the host recursion | 1: by the level-synchronous builder on the device where the input

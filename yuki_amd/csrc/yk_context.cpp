@@ -85,6 +85,7 @@ yk_status yk_context_create(int device, yk_context** out) {
     if (const char* w = std::getenv("YK_WIDE_BVH")) ctx->wide_bvh = std::min(std::max(std::atoi(w), 0), 2);  // experiments; same as set_option("wide_bvh")
     if (const char* w = std::getenv("YK_PACKET_BOUNCES")) ctx->packet_bounces = std::max(std::atoi(w), 0);
     if (const char* w = std::getenv("YK_PACKET_SHADOW_BOUNCES")) ctx->packet_shadow_bounces = std::max(std::atoi(w), 0);
+    if (const char* w = std::getenv("YK_NEE_SKIP")) ctx->nee_skip = std::atoi(w) & (int)YK_NEE_SKIP_ZERO;
     if (const char* w = std::getenv("YK_TOP_NODES")) ctx->top_nodes = std::min(std::max(std::atoi(w), 0), YK_TOP_MAX);
     *out = ctx;
     return YK_OK;
@@ -174,6 +175,9 @@ yk_status yk_context_set_option(yk_context* ctx, const char* key, int64_t value)
     } else if (k == "packet_shadow_bounces") {
         if (value < 0) return YK_ERR_INVALID_ARGUMENT;
         ctx->packet_shadow_bounces = value;
+    } else if (k == "nee_skip") {
+        if (value != 0 && value != (int64_t)YK_NEE_SKIP_ZERO) return YK_ERR_INVALID_ARGUMENT;  // the only bit there is
+        ctx->nee_skip = value;
     } else if (k == "shade_reorder") {
         ctx->shade_reorder = value != 0;
     } else if (k == "overlap_shadow") {

@@ -232,8 +232,12 @@ struct RenderParams {
     // yk_li) the sample index is table[entry] + k; spe = the number of passes rendered at once.
     uint32_t spe;
     uint32_t sample_base;  // sample index of an entry when there is no table: 0 for the plain film, FilmTile.sample shared by all tiles otherwise
+    uint32_t nee_skip;     // the context's "nee_skip" (YK_NEE_SKIP_*): light work no result reads that the light loops leave out
     CancelRef cancel;
 };
+// "nee_skip" bits (vertex_light, yk_shade.h; k_whitted): the film, the rays and the reported shadow rays are the same under every mask.
+// (Bit 1, no light sampling at a vertex whose material takes no light, was measured and not kept: DESIGN.md §9.)
+#define YK_NEE_SKIP_ZERO 2u  // a shadow ray whose contribution is +-0 in every component is reported but not traced
 
 // sample id -> (entry of the pixel table, sample within the entry): id = entry * spe + k.  `spe` is uniform and nearly always a
 // power of two (8x8, 16x16 strata; 1 for yk_li): a shift and a mask then, the division otherwise.

@@ -92,6 +92,7 @@ struct yk_context {
     int64_t batch_paths = 128 << 20;
     int64_t packet_bounces = 1;         // leading bounces whose closest-hit rays use the wave-packet kernel (camera rays are coherent); 0 = never
     int64_t packet_shadow_bounces = 1;  // same for the shadow rays towards point / spot / distant lights (their own queue)
+    int64_t nee_skip = 2;        // light work no result reads that the light loops leave out, a bit mask (yk_device.h, YK_NEE_SKIP_*): 2 no trace of a shadow ray whose contribution is +-0; 0 = every ray
     int64_t shade_reorder = 1;   // deal the paths of a shade block to its lanes sorted by material kind (bounces > 0)
     int64_t overlap_shadow = 1;  // run {trace_any, accumulate}(b) on a side stream beside trace_closest(b+1)
     int64_t wide_bvh = 2;   // scenes created afterwards: 0 binary nodes only, 1 traverse the 4-wide collapse, 2 keep both and pick per job

@@ -44,7 +44,7 @@ void launch_trace_any(hipStream_t s, unsigned grid, const DevScene& sc, const Sh
 // spot / distant lights go to q.delta; reorder: windows sorted by material kind; block_slots: resident blocks on the device
 void launch_shade(hipStream_t s, unsigned grid, const DevScene& sc, const RenderParams& prm, const uint32_t* pixel_xy, const uint32_t* sample_index_tab,
                   PathBuffers cur, PathBuffers nxt, const BounceQueues& q, unsigned split_delta, unsigned reorder, unsigned block_slots, unsigned sid_base,
-                  const float4* lean_origin);
+                  const float4* lean_origin, unsigned long long* shadow_counter);
 void launch_accumulate(hipStream_t s, unsigned grid, const RenderParams& prm, PathBuffers cur, const BounceQueues& q, unsigned nl, float4* sample_buf,
                        unsigned first, unsigned sid_base);
 void launch_resolve(hipStream_t s, const float4* sample_buf, uint32_t n_pixels, uint32_t spp, float* out_rgb);

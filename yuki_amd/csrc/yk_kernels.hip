@@ -217,7 +217,7 @@ __global__ __launch_bounds__(BLOCK, SHADE_MIN_WAVES) void k_shade(DevScene sc, R
         if (a.reorder) __syncthreads();  // the next window's sort overwrites `order`
     }
     YK_PROF_FLUSH
-    sq.finish();
+    sq.finish(a.shadow_counter);
 }
 
 // ------------------------------------------------------------------ accumulate
@@ -422,8 +422,8 @@ void launch_raygen_user(hipStream_t s, const RenderParams& prm, const float* o, 
 }
 void launch_shade(hipStream_t s, unsigned grid, const DevScene& sc, const RenderParams& prm, const uint32_t* pixel_xy, const uint32_t* sample_index_tab,
                   PathBuffers cur, PathBuffers nxt, const BounceQueues& q, unsigned split_delta, unsigned reorder, unsigned block_slots, unsigned sid_base,
-                  const float4* lean_origin) {
-    const ShadeArgs a{split_delta, reorder, (unsigned)SHADE_WIN, block_slots, sid_base};
+                  const float4* lean_origin, unsigned long long* shadow_counter) {
+    const ShadeArgs a{split_delta, reorder, (unsigned)SHADE_WIN, block_slots, sid_base, shadow_counter};
     hipLaunchKernelGGL((k_shade<256, SHADE_CAP, SHADE_CAPQ>), dim3(grid), dim3(256), 0, s, sc, prm, pixel_xy, sample_index_tab, cur, nxt, q, a, lean_origin);
 }
 void launch_accumulate(hipStream_t s, unsigned grid, const RenderParams& prm, PathBuffers cur, const BounceQueues& q, unsigned nl, float4* sample_buf,

@@ -128,6 +128,7 @@ yk_status make_params(yk_context* ctx, const yk_sampler_desc* smp, const yk_inte
     prm.has_clamp = integ->has_clamp;
     prm.clamp = integ->indirect_clamp;
     prm.integrator = integ->kind;
+    prm.nee_skip = ctx ? (uint32_t)ctx->nee_skip : 0u;
     if (integ->kind == YK_INTEGRATOR_WHITTED && integ->max_depth > whitted_max_depth())
         return fail(ctx, YK_ERR_UNSUPPORTED, "Whitted: max_depth above 16 is not supported on the device");
     if (integ->kind > YK_INTEGRATOR_SHADING_UVS) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "bad integrator kind");
@@ -169,6 +170,11 @@ void run_bounces(yk_context* ctx, WorkSet& ws, hipStream_t st, const yk_scene* s
     const unsigned sg = fit((unsigned)ctx->n_cu * shade_bpc, n_paths);  // k_accumulate: 256 paths per block and step
     const unsigned spill_stride = trace_grid(ctx) * trace_block_size();
     unsigned cur = 0;
+    unsigned long long debug_reported = 0;  // YK_DEBUG_BOUNCES: the render's shadow-ray count when the bounce began
+    if (kt.on && std::getenv("YK_DEBUG_BOUNCES")) {
+        (void)hipDeviceSynchronize();
+        (void)hipMemcpy(&debug_reported, counters + 1, sizeof(debug_reported), hipMemcpyDeviceToHost);
+    }
     // Bounce b: trace_closest -> shade on `st`; then {trace_any, accumulate}(b) go to the side
     // stream while `st` already traces bounce b+1 — two persistent kernels whose drained
     // CUs are picked up by the other one (the tail of a small launch is one long ray).
@@ -200,7 +206,7 @@ void run_bounces(yk_context* ctx, WorkSet& ws, hipStream_t st, const yk_scene* s
         if (overlap && b > 0) (void)hipStreamWaitEvent(st, ws.ev_acc, 0);
         e = kt.begin(st);
         launch_shade(st, sg, ds, prm, pixel_xy, sample_index_tab, pc, pn, q, split ? 1u : 0u, (b > 0 && ctx->shade_reorder) ? 1u : 0u, 3u * (unsigned)ctx->n_cu,
-                     sid_base, lean_origin);
+                     sid_base, lean_origin, counters + 1);
         kt.end(e, 2, st);
 #ifdef YK_EXPERIMENT_SORT  // order the queues k_shade just wrote (synchronises: timing experiment, tools/micro/ray_sort_experiment.h)
         YK_SORT_AFTER_SHADE
@@ -225,9 +231,14 @@ void run_bounces(yk_context* ctx, WorkSet& ws, hipStream_t st, const yk_scene* s
         if (overlap) (void)hipEventRecord(ws.ev_acc, sb);
         if (kt.on && std::getenv("YK_DEBUG_BOUNCES")) {  // per-bounce breakdown (synchronises; diagnostics only)
             unsigned h[YK_CTRL_STRIDE + 1];
-            (void)hipStreamSynchronize(st);
-            (void)hipStreamSynchronize(sb);
+            (void)hipDeviceSynchronize();  // the other work set's batch as well: the shadow counter is the context's
             (void)hipMemcpy(h, q.count, sizeof(h), hipMemcpyDeviceToHost);  // the bounce's words of the control block (yk_device.h)
+            // traced: what the any-hit queues held; reported: what the bounce added to the render's shadow-ray count, the queues and
+            // the rays k_shade left out because they add +-0 ("nee_skip" bit 2)
+            unsigned long long reported_now = 0;
+            (void)hipMemcpy(&reported_now, counters + 1, sizeof(reported_now), hipMemcpyDeviceToHost);
+            std::fprintf(stderr, "bounce %u: shadow rays traced / reported %u / %llu\n", b, h[YK_CTRL_SHQ] + h[YK_CTRL_SHQ2], reported_now - debug_reported);
+            debug_reported = reported_now;
             float tt = 0, ts = 0, th = 0;
             (void)hipEventElapsedTime(&tt, ctx->ev_pool[kt.spans[0].back().first], ctx->ev_pool[kt.spans[0].back().second]);
             (void)hipEventElapsedTime(&ts, ctx->ev_pool[kt.spans[1].back().first], ctx->ev_pool[kt.spans[1].back().second]);

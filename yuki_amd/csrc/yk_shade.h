@@ -58,9 +58,15 @@ __device__ __forceinline__ void vertex_setup(const DevScene& sc, uint32_t prim, 
 // contributes returns the contribution f * li * clamp(ns . l) / pdf and the shadow ray of its VisibilityTester.
 // RAY_ALWAYS (k_path_debug): the shadow ray is also returned when the light has a visibility tester but f is black
 // (`has_ray`; path.rs:103-113 records that ray although it traces nothing).
+//
+// A contribution that is +-0 in every component (the light behind the shading normal, or the vertex seen and lit from the
+// back) is added by the reference after a trace, and c + (+-0) is c bit for bit (c starts at +0; a sum is -0 only when both
+// operands are): with prm.nee_skip & YK_NEE_SKIP_ZERO the ray is not wanted.  It still counts as a shadow ray of the render
+// (`zero`: the reference calls `unoccluded` for it), and RAY_ALWAYS still reports it.  A NaN or an infinity is no zero.
 struct NeeSample {
     bool want;
-    bool has_ray;  // RAY_ALWAYS only: f was black; so / sd hold the tester's ray, nothing is to be traced
+    bool has_ray;  // RAY_ALWAYS only: nothing is to be traced (f was black, or the contribution zero); so / sd hold the tester's ray
+    bool zero;     // the reference traces a ray here that adds +-0: not wanted, but reported
     RGB contrib;
     V3 so, sd;
     int al;  // the sampled area light (its own surface does not occlude, bvh.rs:269-280) or -1
@@ -77,6 +83,7 @@ __device__ __forceinline__ NeeSample nee_none() {
     NeeSample r;
     r.want = false;
     r.has_ray = false;
+    r.zero = false;
     r.contrib = RGB{0, 0, 0};
     r.so = V3{0, 0, 0};
     r.sd = V3{0, 0, 1};
@@ -105,7 +112,9 @@ __device__ __forceinline__ NeeSample vertex_light(const DevScene& sc, const Rend
             r.contrib = f * ls.li * rclamp(dot_nv(v.sf.ns, ls.l), 0.0f, 1.0f) / ls.pdf;
             vertex_shadow_ray(v, ls, r.so, r.sd);
             r.al = ls.area_light;
-            r.want = true;
+            r.zero = (prm.nee_skip & YK_NEE_SKIP_ZERO) && is_black(r.contrib);
+            r.want = !r.zero;
+            if (RAY_ALWAYS) r.has_ray = r.zero;
         } else if (RAY_ALWAYS && ls.has_vis) {
             vertex_shadow_ray(v, ls, r.so, r.sd);
             r.has_ray = true;

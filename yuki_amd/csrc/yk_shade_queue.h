@@ -43,7 +43,8 @@ template <int CAP, int CAPQ> struct ShadeStaging {
     unsigned fill_p, fill_q, gbase;
     unsigned q_delta;  // class of the staged shadow rays: 1 = towards a point/spot/distant light
     unsigned cancel;   // the render was interrupted (yk_device.h, CancelRef): block-uniform copy of what thread 0 read
-    unsigned bucket[8];                  // material-kind histogram of the window's paths
+    unsigned untraced;  // shadow rays the block reported without staging them (NeeSample::zero); sits in what was padding: the struct keeps its 53248 bytes
+    unsigned bucket[8];                 // material-kind histogram of the window's paths
     unsigned short order[SHADE_WIN * 256];  // sorted position -> offset of the path inside the window
 };
 
@@ -54,6 +55,7 @@ struct ShadeArgs {
     unsigned win_max;      // iterations per window at most (<= SHADE_WIN)
     unsigned block_slots;  // resident blocks on the device
     unsigned sid_base;     // first sample slot of the batch
+    unsigned long long* shadow_counter;  // the batch's count of reported shadow rays (the word queue_length adds the any-hit queues to)
 };
 
 // returns the staging position of the lanes that `want` one
@@ -155,6 +157,7 @@ template <int BLOCK, int CAP, int CAPQ> struct ShadeQueue {
             stg.fill_p = 0;
             stg.fill_q = 0;
             stg.q_delta = 0;
+            stg.untraced = 0;
             stg.cancel = cancel_raised(cancel) ? 1u : 0u;
         }
         __syncthreads();
@@ -232,6 +235,8 @@ template <int BLOCK, int CAP, int CAPQ> struct ShadeQueue {
             vword |= (want ? 1u : 0u) << (8u * l);
         else if (valid)
             q.vis[vslot] = want ? 1 : 0;
+        const unsigned long long zm = __ballot(ne.zero);  // not wanted, but shadow rays of the render: finish() reports the block's
+        if (zm != 0ull && lane_id() == 0) atomicAdd(&stg.untraced, (unsigned)__popcll(zm));
         room_for_light(l);
         const unsigned k = block_append(want, &stg.fill_q);
         if (want) {
@@ -257,11 +262,16 @@ template <int BLOCK, int CAP, int CAPQ> struct ShadeQueue {
         }
     }
 
-    __device__ __forceinline__ void finish() {
+    // Flushes what is staged and reports the block's untraced shadow rays: one atomic per block that has any, the last thing
+    // the block does (an agent-scope access at a block's start or in front of a barrier is waited for: yk_device.h, cancel_raised).
+    // The waves count into LDS as they go (stage_shadow): a count carried in a register through the loops cost k_shade two
+    // spilled VGPRs at its 168.
+    __device__ __forceinline__ void finish(unsigned long long* shadow_counter) {
         __syncthreads();
-        const unsigned fq = stg.fill_q, fp = stg.fill_p;
+        const unsigned fq = stg.fill_q, fp = stg.fill_p, nz = stg.untraced;
         if (fq) flush_q(fq, stg.q_delta);
         if (fp) flush_p(fp);
+        if (threadIdx.x == 0 && nz && shadow_counter) atomicAdd(shadow_counter, (unsigned long long)nz);
     }
 };
 

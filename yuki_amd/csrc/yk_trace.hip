@@ -655,8 +655,9 @@ __global__ __launch_bounds__(BLOCK) void k_whitted(DevScene sc, RenderParams prm
                     V3 offset = sf.n * 0.001f;  // VisibilityTester::ray = p0.spawn_ray_to(p1), interaction.rs:44-59
                     V3 so = dot(ls.p1 - sf.p, sf.n) > 0.0f ? sf.p + offset : sf.p - offset;
                     n_shadow += 1;
-                    if (!traverse_any(sc, ray_setup(so, ls.p1 - so, 0.9999f), ls.area_light, stk, err))
-                        sum = sum + f * ls.li * rclamp(dot_nv(sf.ns, ls.l), 0.0f, 1.0f) / ls.pdf;
+                    const RGB contrib = f * ls.li * rclamp(dot_nv(sf.ns, ls.l), 0.0f, 1.0f) / ls.pdf;
+                    if ((prm.nee_skip & YK_NEE_SKIP_ZERO) && is_black(contrib)) continue;  // vertex_light's rule (yk_shade.h): sum + (+-0) is sum, the ray is counted and not walked
+                    if (!traverse_any(sc, ray_setup(so, ls.p1 - so, 0.9999f), ls.area_light, stk, err)) sum = sum + contrib;
                 }
                 if (sp == 0 || is_specular) {  // whitted.rs:135-137, rectangular_light.rs:75-81
                     if (sf.area_light >= 0) {
