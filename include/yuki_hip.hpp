@@ -266,6 +266,28 @@ inline void write_png(const std::string& path, uint32_t width, uint32_t height, 
     check(yk_write_png(path.c_str(), width, height, channels, pixels));
 }
 
+// Guides through glass (the rule is stated in yuki_hip.h and csrc/yk_guides_through.h): the guide and the surface id of the
+// surface every pixel shows and the number of glass interfaces crossed on the way, res_x * res_y records each, row-major.
+struct GuidesThrough {
+    std::vector<yk_guide> guides;
+    std::vector<yk_surface_id> ids;
+    std::vector<uint32_t> through;
+};
+inline GuidesThrough render_guides_through(Context& ctx, const Scene& scene, const yk_camera& camera, uint16_t res_x, uint16_t res_y, uint32_t max_through = 4) {
+    GuidesThrough g;
+    const size_t n = (size_t)res_x * res_y;
+    g.guides.resize(n);
+    g.ids.resize(n);
+    g.through.resize(n);
+    check(yk_render_guides_through(ctx.handle(), scene.handle(), &camera, res_x, res_y, max_through, g.guides.data(), g.ids.data(), g.through.data()), ctx.handle());
+    return g;
+}
+// The same into device buffers (any of the three may be nullptr, not all), ordered on `stream`; no read-back, no allocation.
+inline void render_guides_through_device(Context& ctx, const Scene& scene, const yk_camera& camera, uint16_t res_x, uint16_t res_y, uint32_t max_through, void* d_guides,
+                                         void* d_ids, void* d_through, void* stream = nullptr) {
+    check(yk_render_guides_through_device(ctx.handle(), scene.handle(), &camera, res_x, res_y, max_through, d_guides, d_ids, d_through, stream), ctx.handle());
+}
+
 // Textures under the denoiser (the library's own passes; the rule is stated in yuki_hip.h and csrc/yk_albedo.h).
 using Albedo = yk_albedo;
 // The first-hit albedo of every pixel from yk_render_guides_ids' ids (res_x * res_y records, row-major).  ctx == nullptr: the

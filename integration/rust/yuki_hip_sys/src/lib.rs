@@ -325,6 +325,8 @@ pub struct yk_variance_desc {
 
 /// `yk_surface_id::shape` on a miss
 pub const YK_SURFACE_NONE: u32 = 0xffff_ffff;
+/// the most glass interfaces `yk_render_guides_through` follows
+pub const YK_GUIDES_THROUGH_MAX: u32 = 8;
 
 /// The identity of a pixel's first hit beside its guide: the source shape (a sphere is n_triangles + k) and the hit's
 /// barycentrics; 16-byte aligned on the device (yuki_amd/csrc/yk_motion.h)
@@ -610,6 +612,9 @@ extern "C" {
     pub fn yk_history_blend_device(ctx: *mut yk_context, desc: *const yk_temporal_desc, d_film_rgb: *const c_void, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, d_history: *const c_void, d_out_history: *mut c_void, d_out_rgb: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_render_guides_ids(ctx: *mut yk_context, scene: *const yk_scene, camera: *const yk_camera, res_x: u16, res_y: u16, out_guides: *mut yk_guide, out_ids: *mut yk_surface_id) -> yk_status;
     pub fn yk_render_guides_ids_device(ctx: *mut yk_context, scene: *const yk_scene, camera: *const yk_camera, res_x: u16, res_y: u16, d_guides: *mut c_void, d_ids: *mut c_void, stream: *mut c_void) -> yk_status;
+    /// guides through glass (yuki_amd/csrc/yk_guides_through.h): the same records at the first hit that is not glass
+    pub fn yk_render_guides_through(ctx: *mut yk_context, scene: *const yk_scene, camera: *const yk_camera, res_x: u16, res_y: u16, max_through: u32, out_guides: *mut yk_guide, out_ids: *mut yk_surface_id, out_through: *mut u32) -> yk_status;
+    pub fn yk_render_guides_through_device(ctx: *mut yk_context, scene: *const yk_scene, camera: *const yk_camera, res_x: u16, res_y: u16, max_through: u32, d_guides: *mut c_void, d_ids: *mut c_void, d_through: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_surface_motion(ctx: *mut yk_context, scene: *const yk_scene, ids: *const yk_surface_id, guides: *const yk_guide, prev_points: *const f32, res_x: u16, res_y: u16, out: *mut yk_motion) -> yk_status;
     pub fn yk_surface_motion_device(ctx: *mut yk_context, scene: *const yk_scene, d_ids: *const c_void, d_guides: *const c_void, d_prev_points: *const f32, res_x: u16, res_y: u16, d_out: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_history_reproject_moved(ctx: *mut yk_context, desc: *const yk_temporal_desc, prev_history: *const yk_history, prev_guides: *const yk_guide, prev_camera: *const yk_camera, guides: *const yk_guide, motion: *const yk_motion, res_x: u16, res_y: u16, out_history: *mut yk_history) -> yk_status;

@@ -185,6 +185,8 @@ SYMBOLS = {
     "yk_history_blend_device": (C.c_int, [vp, C.POINTER(abi.TemporalDesc), vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp, vp, vp]),
     "yk_render_guides_ids": (C.c_int, [vp, vp, C.POINTER(abi.CameraMatrices), C.c_uint16, C.c_uint16, vp, vp]),
     "yk_render_guides_ids_device": (C.c_int, [vp, vp, C.POINTER(abi.CameraMatrices), C.c_uint16, C.c_uint16, vp, vp, vp]),
+    "yk_render_guides_through": (C.c_int, [vp, vp, C.POINTER(abi.CameraMatrices), C.c_uint16, C.c_uint16, C.c_uint32, vp, vp, vp]),
+    "yk_render_guides_through_device": (C.c_int, [vp, vp, C.POINTER(abi.CameraMatrices), C.c_uint16, C.c_uint16, C.c_uint32, vp, vp, vp, vp]),
     "yk_surface_motion": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint16, C.c_uint16, vp]),
     "yk_surface_motion_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint16, C.c_uint16, vp, vp]),
     "yk_surface_albedo": (C.c_int, [vp, vp, vp, C.c_uint16, C.c_uint16, vp]),

@@ -273,6 +273,7 @@ OVERLAY_LINE_DTYPE = np.dtype([("p0", "<f4", 3), ("p1", "<f4", 3), ("rgb", "<f4"
 GUIDE_DTYPE = np.dtype([("ns", "<f4", 3), ("hit", "<f4"), ("p", "<f4", 3), ("t", "<f4")])  # yk_guide, 32 bytes
 HISTORY_DTYPE = np.dtype([("rgb", "<f4", 3), ("n", "<f4")])  # yk_history, 16 bytes
 SURFACE_NONE = 0xFFFFFFFF  # YK_SURFACE_NONE
+GUIDES_THROUGH_MAX = 8  # YK_GUIDES_THROUGH_MAX
 SURFACE_ID_DTYPE = np.dtype([("shape", "<u4"), ("b", "<f4", 3)])  # yk_surface_id, 16 bytes
 SURFACE_FLOATS = 28  # YK_SURFACE_FLOATS: one record of yk_surface
 SURFACE_FIELDS = dict(hit=0, t=1, p=slice(2, 5), n=slice(5, 8), ns=slice(8, 11), dpdus=slice(11, 14), wo=slice(14, 17), u=17, v=18, material=19, area_light=20, shape=21, b=slice(22, 25), origin=slice(25, 28))

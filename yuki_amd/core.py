@@ -449,6 +449,19 @@ def render_guides_ids(ctx, scene, camera, film_settings):
     return guides, ids
 
 
+def render_guides_through(ctx, scene, camera, film_settings, max_through=4):
+    """yk_render_guides_through (csrc/yk_guides_through.h): render_guides_ids' records of the surface every pixel SHOWS —
+    glass is followed (transmission; reflection on total internal reflection or a black Kt) for up to max_through
+    (0 .. abi.GUIDES_THROUGH_MAX) interfaces -> (guides, ids, through): the (h, w) records of render_guides_ids at the
+    first hit that is not glass, and (h, w) uint32, the interfaces crossed.  max_through = 0 is render_guides_ids."""
+    w, h = film_settings.res
+    guides = np.zeros((h, w), dtype=abi.GUIDE_DTYPE)
+    ids = np.zeros((h, w), dtype=abi.SURFACE_ID_DTYPE)
+    through = np.zeros((h, w), dtype=np.uint32)
+    check(lib().yk_render_guides_through(ctx.h, scene.h, C.byref(camera.matrices), w, h, int(max_through), _p(guides), _p(ids), _p(through)), ctx.h)
+    return guides, ids, through
+
+
 def _prev_points(scene, prev_points):
     nv = int(scene.data.points.shape[0])
     a = np.asarray(prev_points)
@@ -855,16 +868,39 @@ def _denoise_for_output(film, denoise_params, guides, tile_dim, samples, ctx, al
     return denoise(film, guides, denoise_params, tile_dim, samples, ctx, albedo, variance), None
 
 
-def write_output(path, film, tone_map=None, settings=None, samples=None, ctx=None, denoise=None, guides=None, albedo=None, variance=None, auto_exposure=None):
+def _guides_through_for_output(guides_through, settings, ctx, guides, albedo):
+    """The guides_through= keyword of write_output / write_preview: (scene, camera) or (scene, camera, max_through) — the
+    guides are rendered here by render_guides_through on `ctx` instead of being passed in, and albedo=True asks for
+    surface_albedo of the same call's ids.  -> (guides, albedo)."""
+    if guides_through is None:
+        if albedo is True:
+            raise ValueError("albedo=True needs guides_through: the ids come from its call")
+        return guides, albedo
+    if guides is not None:
+        raise ValueError("guides_through renders the guides: pass one of the two")
+    if ctx is None:
+        raise ValueError("guides_through renders on the device: it needs ctx")
+    scene, camera = guides_through[0], guides_through[1]
+    max_through = guides_through[2] if len(guides_through) > 2 else 4
+    guides, ids, _ = render_guides_through(ctx, scene, camera, settings, max_through)
+    if albedo is True:
+        albedo = surface_albedo(scene, ids, ctx)
+    return guides, albedo
+
+
+def write_output(path, film, tone_map=None, settings=None, samples=None, ctx=None, denoise=None, guides=None, albedo=None, variance=None, auto_exposure=None, guides_through=None):
     """The Finished branch of app/headless.rs:62-84: Raw writes the film as it is, anything else writes the tone-mapped
     film (a Heatmap without bounds finds them first).  tone_map None = ToneMapType.default(); settings None = a film of the
     array's size with the default tile_dim.  denoise (a DenoiseParams) with guides: the film is denoised first; with albedo
     (surface_albedo's records) too: by the demodulated filter; with a VarianceParams and variance (variance()'s image): by
     the variance-guided filter.  auto_exposure (True or an ExposureParams, Filmic only): the film about to be tone-mapped
-    — after the denoise — is metered (meter_exposure) and the exposure is the tone map's times the meter's."""
+    — after the denoise — is metered (meter_exposure) and the exposure is the tone map's times the meter's.
+    guides_through ((scene, camera[, max_through]), instead of guides, with ctx): the guides are render_guides_through's —
+    what the pixel shows behind glass — and albedo=True takes surface_albedo of that call's ids."""
     film = np.ascontiguousarray(film, dtype=np.float32)
     tone_map = ToneMapType.default() if tone_map is None else tone_map
     settings = settings or FilmSettings(res=(film.shape[1], film.shape[0]))
+    guides, albedo = _guides_through_for_output(guides_through, settings, ctx, guides, albedo)
     film, samples = _denoise_for_output(film, denoise, guides, film_tile_dim(settings), samples, ctx, albedo, variance)
     if tone_map.kind == abi.TONE_MAP_RAW:
         if auto_exposure:
@@ -976,15 +1012,16 @@ def write_png(path, pixels):
     check(lib().yk_write_png(str(path).encode(), pixels.shape[1], pixels.shape[0], pixels.shape[2], _p(pixels)))
 
 
-def write_preview(path, film, tone_map=None, settings=None, samples=None, window=None, ctx=None, denoise=None, guides=None, albedo=None, variance=None, auto_exposure=None):
+def write_preview(path, film, tone_map=None, settings=None, samples=None, window=None, ctx=None, denoise=None, guides=None, albedo=None, variance=None, auto_exposure=None, guides_through=None):
     """What the window shows, as a PNG: the denoiser when `denoise` (a DenoiseParams) and `guides` are given (demodulated
     by `albedo`, surface_albedo's records, when that is given too; variance-guided when `denoise` is a VarianceParams and
     `variance` its image), the tone map
     (as write_output: None = ToneMapType.default(), Raw = none), then present into `window` (default: the film's size) as
-    an sRGB back buffer stores it (encode 2), then write_png.  auto_exposure: as write_output's."""
+    an sRGB back buffer stores it (encode 2), then write_png.  auto_exposure and guides_through: as write_output's."""
     film = np.ascontiguousarray(film, dtype=np.float32)
     tone_map = ToneMapType.default() if tone_map is None else tone_map
     settings = settings or FilmSettings(res=(film.shape[1], film.shape[0]))
+    guides, albedo = _guides_through_for_output(guides_through, settings, ctx, guides, albedo)
     film, samples = _denoise_for_output(film, denoise, guides, film_tile_dim(settings), samples, ctx, albedo, variance)
     if tone_map.kind != abi.TONE_MAP_RAW:
         tone_map = _auto_exposure(film, tone_map, auto_exposure, film_tile_dim(settings), samples, ctx)
@@ -1230,6 +1267,12 @@ class Context:
         """yk_render_guides_ids_device: render_guides_device with res[0] * res[1] yk_surface_id records (16 bytes each,
         16-byte aligned) beside the guides, from the same trace; either pointer may be None, not both."""
         check(lib().yk_render_guides_ids_device(self.h, scene.h, C.byref(camera.matrices), int(res[0]), int(res[1]), _vp(d_guides_ptr), _vp(d_ids_ptr), _vp(stream)), self.h)
+
+    def render_guides_through_device(self, scene, camera, res, d_guides_ptr, d_ids_ptr, d_through_ptr, max_through=4, stream=None):
+        """yk_render_guides_through_device: render_guides_ids_device following glass for up to max_through interfaces, with
+        res[0] * res[1] uint32 (4-byte aligned) of interfaces crossed beside the records; any pointer may be None, not all
+        three, no two buffers may overlap.  No read-back: ordered on `stream` like the other guide calls."""
+        check(lib().yk_render_guides_through_device(self.h, scene.h, C.byref(camera.matrices), int(res[0]), int(res[1]), int(max_through), _vp(d_guides_ptr), _vp(d_ids_ptr), _vp(d_through_ptr), _vp(stream)), self.h)
 
     def surface_motion_device(self, scene, d_ids_ptr, d_guides_ptr, d_prev_points_ptr, res, d_out_ptr, stream=None):
         """yk_surface_motion_device: device ids and guides of the current geometry and the PREVIOUS vertex array on the device

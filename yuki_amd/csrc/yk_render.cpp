@@ -30,6 +30,7 @@
 #include "yk_adaptive.h"
 #include "yk_albedo.h"
 #include "yk_film_call.h"
+#include "yk_guides_through.h"
 #include "yk_render_plan.h"
 #include "yk_staging.h"
 #ifdef YK_EXPERIMENT_SORT  // timing builds only (tools/build_variant.sh sort -DYK_EXPERIMENT_SORT): DESIGN.md §9
@@ -356,6 +357,12 @@ struct RenderRequest {
     uint32_t guides_res_x = 0;
     void* d_ids = nullptr;
     uint32_t ids_row0 = 0, ids_band_rows = 0;
+    // through (yk_render_guides_through, yk_guides_through.h): the guide pass follows glass for up to max_through
+    // interfaces — k_guides_step instead of k_guides after every trace; d_out, d_ids and d_through (one uint32 a pixel: the
+    // interfaces crossed) may each be NULL, not all three.
+    bool through = false;
+    uint32_t max_through = 0;
+    void* d_through = nullptr;
     void* stream = nullptr;
     yk_render_stats* stats = nullptr;
     yk_cancel_fn cancel = nullptr;
@@ -422,7 +429,7 @@ struct Submission {
         if (rq.pixels) {
             if (rq.pixels->ctx != ctx) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "pixel list was not created on this context");
             if (!scene || !rq.camera || (!rq.d_out && !(rq.d_film_sum && rq.d_stats))) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null argument");
-        } else if (!scene || !rq.camera || !tiles || n_tiles == 0 || (!rq.d_out && !(rq.guides_res_x && rq.d_ids)))
+        } else if (!scene || !rq.camera || !tiles || n_tiles == 0 || (!rq.d_out && !(rq.guides_res_x && (rq.d_ids || rq.d_through))))
             return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null argument");
         if (yk_status rs = scene_on_context(ctx, scene, "")) return rs;
         yk_status rc = make_params(ctx, rq.sampler, rq.integrator, prm);
@@ -577,6 +584,7 @@ struct Submission {
         launch_trace_closest(bs, trace_grid(ctx), dev_scene_for(scene, n), pc.rayO, pc.rayD, nullptr, bc0, bc0 + YK_CTRL_HEAD, ws.hit.as<int>(), nullptr,
                              want_stats ? ctx->stats4.as<uint4>() : nullptr, ws.spill.as<uint2>(), spill_stride, errblk, counters());
         kt.end(e, 0, bs);
+        if (rq.guides_res_x && rq.through) return enqueue_guides_through(ws, bs, n);
         if (rq.guides_res_x && rq.d_ids && rq.ids_band_rows)
             launch_ids_band(bs, scene->dev, pc, ws.hit.as<int>(), n, pixel_xy, rq.guides_res_x, rq.ids_row0, rq.ids_band_rows, reinterpret_cast<uint4*>(rq.d_ids));
         else if (rq.guides_res_x && rq.d_ids)
@@ -585,6 +593,32 @@ struct Submission {
             launch_guides(bs, scene->dev, pc, ws.hit.as<int>(), n, pixel_xy, rq.guides_res_x, reinterpret_cast<float4*>(rq.d_out));
         else
             launch_debug_shade(bs, scene->dev, prm.integrator, pc, ws.hit.as<int>(), ctx->stats4.as<uint4>(), n, sample_buf);
+        return YK_OK;
+    }
+
+    // The guide pass through glass (yk_guides_through.h) after the batch's camera rays were traced: k_guides_step of pass 0,
+    // then per further pass the closest-hit trace of the continuation queue and its k_guides_step.  Pass k's rays live in
+    // path buffer k & 1, their count in word 0 of bounce k's control words (raygen wrote bounce 0's, the step before wrote
+    // the others into the batch's zeroed block) and the trace's work-queue head beside it; nothing is read back — the later
+    // launches are sized for the batch (`n`) and find their count on the device.
+    yk_status enqueue_guides_through(WorkSet& ws, hipStream_t bs, uint32_t n) {
+        unsigned* ctrl = ws.ctrl.as<unsigned>();
+        const DevScene ds = dev_scene_for(scene, n);
+        const unsigned tg = (unsigned)std::min<uint64_t>(trace_grid(ctx), std::max<uint64_t>(1, ((uint64_t)n + 255) / 256));
+        const unsigned spill_stride = trace_grid(ctx) * trace_block_size();
+        for (uint32_t k = 0; k <= rq.max_through; ++k) {
+            unsigned* bc = ctrl + YK_CTRL_BOUNCE(k);
+            const PathBuffers cur = path_buffers(ws, (int)(k & 1u)), nxt = path_buffers(ws, (int)((k & 1u) ^ 1u));
+            if (k > 0) {
+                ++n_trace;
+                int e = kt.begin(bs);
+                launch_trace_closest(bs, tg, ds, cur.rayO, cur.rayD, nullptr, bc, bc + YK_CTRL_HEAD, ws.hit.as<int>(), nullptr, nullptr, ws.spill.as<uint2>(), spill_stride,
+                                     error_block(ctx), counters());
+                kt.end(e, 0, bs);
+            }
+            launch_guides_step(bs, scene->dev, cur, nxt, ws.hit.as<int>(), bc, bc + YK_CTRL_STRIDE, n, k, k == rq.max_through, pixel_xy, rq.guides_res_x,
+                               reinterpret_cast<float4*>(rq.d_out), reinterpret_cast<uint4*>(rq.d_ids), reinterpret_cast<uint32_t*>(rq.d_through));
+        }
         return YK_OK;
     }
 
@@ -724,7 +758,13 @@ static yk_status render_tiles_host(yk_context* ctx, RenderRequest rq, float* out
 
 // The guides: the ShadingNormals integrator's trace of the whole film as one tile under a 1 x 1 Stratified sampler without
 // jitter, whose camera sample is the pixel centre whatever its seed, so the ray is Camera::ray((x + 0.5, y + 0.5)).
-static yk_status render_guides(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, uint16_t res_x, uint16_t res_y, void* d_guides, void* stream, void* d_ids = nullptr) {
+// through != NULL: the pass through glass (yk_guides_through.h) with its bound and its third output.
+struct GuidesThrough {
+    uint32_t max_through;
+    void* d_through;
+};
+static yk_status render_guides(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, uint16_t res_x, uint16_t res_y, void* d_guides, void* stream, void* d_ids = nullptr,
+                               const GuidesThrough* through = nullptr) {
     yk_sampler_desc smp = {};
     smp.kind = YK_SAMPLER_STRATIFIED;
     smp.nx = smp.ny = 1;
@@ -741,6 +781,11 @@ static yk_status render_guides(yk_context* ctx, const yk_scene* scene, const yk_
     rq.d_out = d_guides;
     rq.guides_res_x = res_x;
     rq.d_ids = d_ids;
+    if (through) {
+        rq.through = true;
+        rq.max_through = through->max_through;
+        rq.d_through = through->d_through;
+    }
     rq.stream = stream;
     return render_tiles_impl(ctx, rq);
 }
@@ -1125,6 +1170,42 @@ yk_status yk_render_guides_ids(yk_context* ctx, const yk_scene* scene, const yk_
     yk_guide* d_guides = sg.output(out_guides, n_px);  // either may be left out
     yk_surface_id* d_ids = sg.output(out_ids, n_px);
     return sg.run([&] { return render_guides(ctx, scene, camera, res_x, res_y, d_guides, nullptr, d_ids); });
+}
+
+// The guides through glass (yk_guides_through.h): the records of the surface a pixel shows.  The refusals are
+// yk_render_guides_ids_device's, plus the bound on max_through and outputs that overlap one another; nothing is launched
+// before the last of them.
+yk_status yk_render_guides_through_device(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, uint16_t res_x, uint16_t res_y, uint32_t max_through, void* d_guides,
+                                          void* d_ids, void* d_through, void* stream) {
+    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
+    YK_LOCK(ctx);
+    if (!scene || !camera || (!d_guides && !d_ids && !d_through) || res_x == 0 || res_y == 0)
+        return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_guides_through_device: bad argument");
+    if (max_through > YK_GUIDES_THROUGH_MAX) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_guides_through_device: max_through above YK_GUIDES_THROUGH_MAX");
+    if (misaligned(16, d_guides, d_ids)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_guides_through_device: guides and ids must be 16-byte aligned");
+    if (misaligned(4, d_through)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_guides_through_device: through must be 4-byte aligned");
+    const size_t n_px = (size_t)res_x * res_y;
+    const size_t bg = n_px * sizeof(yk_guide), bi = n_px * sizeof(yk_surface_id), bt = n_px * sizeof(uint32_t);
+    if ((d_guides && d_ids && overlaps(d_guides, bg, d_ids, bi)) || (d_guides && d_through && overlaps(d_guides, bg, d_through, bt)) ||
+        (d_ids && d_through && overlaps(d_ids, bi, d_through, bt)))
+        return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_guides_through_device: outputs overlap");
+    const GuidesThrough gt{max_through, d_through};
+    return render_guides(ctx, scene, camera, res_x, res_y, d_guides, stream, d_ids, &gt);
+}
+
+yk_status yk_render_guides_through(yk_context* ctx, const yk_scene* scene, const yk_camera* camera, uint16_t res_x, uint16_t res_y, uint32_t max_through, yk_guide* out_guides,
+                                   yk_surface_id* out_ids, uint32_t* out_through) {
+    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
+    YK_LOCK(ctx);
+    if (!scene || !camera || (!out_guides && !out_ids && !out_through) || res_x == 0 || res_y == 0) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_guides_through: bad argument");
+    if (max_through > YK_GUIDES_THROUGH_MAX) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "yk_render_guides_through: max_through above YK_GUIDES_THROUGH_MAX");
+    const size_t n_px = (size_t)res_x * res_y;
+    Staging sg(ctx);
+    yk_guide* d_guides = sg.output(out_guides, n_px);  // each may be left out
+    yk_surface_id* d_ids = sg.output(out_ids, n_px);
+    uint32_t* d_through = sg.output(out_through, n_px);
+    const GuidesThrough gt{max_through, d_through};
+    return sg.run([&] { return render_guides(ctx, scene, camera, res_x, res_y, d_guides, nullptr, d_ids, &gt); });
 }
 
 // The fused pixel-mean albedo (yk_albedo.h): the large film is traced in bands of output rows, so that it never exists as a
