@@ -342,9 +342,10 @@ yk_status yk_scene_create_device(yk_context* ctx, const yk_scene_desc* desc, voi
 /* Update in place: the scene's vertices move, its tree is refitted and its records are rewritten ("Update in
  * place").  `points` holds 3 floats for each of the scene's n_vertices (the count of its description); `normals` is the
  * same size, or NULL to keep the normals the scene has — non-NULL for a scene created without normals is
- * YK_ERR_INVALID_ARGUMENT.  Indices, uvs, materials, lights and spheres do not change, and neither does the tree's
+ * YK_ERR_INVALID_ARGUMENT.  Indices and uvs do not change (spheres, lights and materials change through
+ * yk_scene_apply_edit, below), and neither does the tree's
  * topology: every node keeps its children, split axis, leaf flag, first slot and count, and the leaf order stays.  A leaf's
- * box is folded from its shapes in leaf order (a triangle's bound from the new points, a sphere's as at creation), an
+ * box is folded from its shapes in leaf order (a triangle's bound from the new points, a sphere's as the scene has it), an
  * interior node's from its two children in child order, and all seven record buffers, yk_scene_info.bounds_min/max and the
  * layout info's scalars follow.  A scene updated with its own points is byte for byte what it was.  A rectangular light's
  * record is not moved: vertices of triangles that carry an area light are the caller's business.  The tree's depth stays
@@ -381,6 +382,57 @@ typedef struct yk_scene_update_info {
                             * the arrays into the scene), leaf and interior boxes, the seven record buffers, the whole call */
 } yk_scene_update_info;
 yk_status yk_scene_get_update_info(const yk_scene* scene, yk_scene_update_info* out);
+/* Edit in place: the scene's spheres, lights, materials and background change; its triangles stay ("Edit in
+ * place").  Every table of `edit` is either NULL (keep what the scene has) or holds as many records as the scene was
+ * created with: counts never change.  Neither does a light's kind (tri_area_light binds triangles to rectangular lights
+ * and the count of delta lights sizes the work buffers).  A material's kind may change and so may a sphere's material.
+ * What is rewritten follows from what changed:
+ *   lights, or materials whose device BSDF kinds all stay   that device table only: no refit, no record pass;
+ *   a material's device BSDF kind changed                   also the scene's kind tables and its record buffers, by the
+ *                                                            layout's own code (the tree stays);
+ *   spheres                                                 also the device sphere table, the spheres' world bounds
+ *                                                            (Sphere::world_bound), the refit of yk_scene_update with
+ *                                                            those bounds, and the records;
+ *   background                                              the scene's constant.
+ * After an edit of lights, materials or background the scene is byte for byte the scene yk_scene_create makes of the
+ * edited description with the same options; after a sphere edit it is the refitted one (the tree's topology stays, as
+ * after yk_scene_update).  An edit with the scene's own tables changes no byte of it.
+ * All or nothing, checked before anything of the scene is written, YK_ERR_INVALID_ARGUMENT each: "null edit"; "spheres
+ * given as a host table and as a device table"; "lights: a light's kind cannot change"; "sphere material out of range" and
+ * "material texture index out of range" (yk_scene_create's checks); "spheres: matrix entry or radius not finite".
+ * Triangles that carry a rectangular light are not moved by an edit of that light: to move one consistently, call
+ * yk_scene_update with the moved vertices of its two triangles and yk_scene_apply_edit with the moved light record (either
+ * order, nothing rendered in between).
+ *   yk_scene_apply_edit         host tables.  It follows the scene's layout as yk_scene_update does: a device-laid scene
+ *                               refits and lays out on the device, a host-laid one on the host.  ctx may be NULL for a
+ *                               host-only scene.
+ *   yk_scene_apply_edit_device  the same with the sphere table in DEVICE memory: n_spheres yk_sphere_desc records at a
+ *                               4-byte aligned address on ctx's device, produced on `stream`; edit->spheres must be NULL.
+ *                               One kernel checks the records (a flag word, read back before anything is written) and
+ *                               writes the device sphere table, the bounds and the material column.  It takes the device
+ *                               route and falls back to the host route with a recorded reason, as yk_scene_update_device.
+ * Ordering and staleness are yk_scene_update's: the call drains the context's streams first, so renders enqueued before it
+ * finish on the old scene; after a device-route sphere edit the host copy of the tree is stale until something reads it.
+ * Still out of reach of an edit: counts, light kinds, indices, the vertices of rectangular-light triangles, and scenes of a
+ * yk_multi (no entry point takes one). */
+typedef struct yk_scene_edit {
+    const yk_sphere_desc* spheres;      /* the scene's n_spheres records, or NULL: keep */
+    const yk_light_desc* lights;        /* the scene's n_lights records, or NULL: keep */
+    const yk_material_desc* materials;  /* the scene's n_materials records, or NULL: keep */
+    const float* background;            /* 3 floats, or NULL: keep */
+} yk_scene_edit;
+enum { YK_EDIT_LIGHTS = 1, YK_EDIT_MATERIALS = 2, YK_EDIT_SPHERES = 4, YK_EDIT_BOXES = 8, YK_EDIT_RECORDS = 16, YK_EDIT_BACKGROUND = 32 };
+typedef struct yk_scene_edit_info {
+    uint32_t n_edits;  /* edits that were carried out (refused ones do not count) */
+    uint32_t route;    /* YK_UPDATE_ROUTE_* of the last edit */
+    uint32_t reason;   /* YK_LAYOUT_REASON_* : non-zero when the last edit asked for the device route and ran on the host */
+    uint32_t rewrote;  /* YK_EDIT_* bits: what the last edit rewrote */
+    double seconds_check, seconds_tables, seconds_boxes, seconds_records, seconds_total; /* last edit: the checks, the small
+                        * tables, leaf and interior boxes, the seven record buffers, the whole call */
+} yk_scene_edit_info;
+yk_status yk_scene_apply_edit(yk_context* ctx, yk_scene* scene, const yk_scene_edit* edit);
+yk_status yk_scene_apply_edit_device(yk_context* ctx, yk_scene* scene, const yk_scene_edit* edit, const void* d_spheres, void* stream);
+yk_status yk_scene_get_edit_info(const yk_scene* scene, yk_scene_edit_info* out);
 /* The refit rule on the host, over an exported tree (yk_scene_export_bvh): the boxes of `nodes` are recomputed in place
  * from shape_bounds — six floats (min.xyz, max.xyz) per SOURCE shape, n_shapes of them — leaves folded from the default
  * bounds in leaf order through shape_order, interior nodes from their children in descending array index.  Nothing else
@@ -850,7 +902,11 @@ yk_status yk_history_blend_device(yk_context* ctx, const yk_temporal_desc* desc,
  * Motion, per pixel, the cases in this order:
  *   1. ids.shape == YK_SURFACE_NONE or guides.hit == 0: the all-zero record.
  *   2. shape >= n_triangles + n_spheres: the all-zero record; the index is never followed.
- *   3. shape >= n_triangles (a sphere; updates do not move spheres): (guides.p as bits, 1).
+ *   3. shape >= n_triangles (sphere k = shape - n_triangles): without a previous sphere table (yk_surface_motion)
+ *      (guides.p as bits, 1): the sphere did not move.  With one (yk_surface_motion_spheres, after yk_scene_apply_edit
+ *      moved spheres): q = xf_point(world_to_object of the scene's CURRENT record k, p), q = q * (radius_prev / radius)
+ *      unless the two radii have equal bits, p_prev = xf_point(object_to_world of the PREVIOUS record k, q), every
+ *      component canonical; known = 1.  The point keeps its place in the sphere's object space, scaled with the radius.
  *   4. A triangle with vertex indices i0, i1, i2: p_prev = P'[i0]*b0 + P'[i1]*b1 + P'[i2]*b2 per component, products first,
  *      summed left to right (the expression of si.p), P' = prev_points; known = 1.
  * Reproject-moved: yk_history_reproject's rule with p_P := motion.p_prev; known == 0 gives the zero record as a miss does;
@@ -860,7 +916,8 @@ yk_status yk_history_blend_device(yk_context* ctx, const yk_temporal_desc* desc,
  *   times the sine of the turn), and a surface that turns by more than acos(normal_cos_min) between two frames loses its
  *   history.  Carried radiance is the radiance the surface HAD: shadows and reflections of things that moved lag until
  *   yk_history_rectify (run after this pass, before the blend) clips them to the current frame, or max_history ends them.
- * Not handled: moving spheres or lights, yk_multi scenes. */
+ * Not handled: lights (a light carries no film; what its move changes in the picture is yk_history_rectify's business),
+ * shapes whose count or indices changed, yk_multi scenes. */
 #define YK_SURFACE_NONE 0xffffffffu
 typedef struct yk_surface_id {
     uint32_t shape; /* source shape index as yk_trace_closest reports it (a sphere is n_triangles + k); YK_SURFACE_NONE on a miss */
@@ -917,6 +974,15 @@ yk_status yk_surface_motion(yk_context* ctx, const yk_scene* scene, const yk_sur
  * waiting for the device: one launch, no allocation.  An id whose shape is out of range is answered as in the rule. */
 yk_status yk_surface_motion_device(yk_context* ctx, const yk_scene* scene, const void* d_ids, const void* d_guides,
                                    const float* d_prev_points, uint16_t res_x, uint16_t res_y, void* d_out, void* stream);
+/* Motion with the sphere case: prev_spheres holds the scene's n_spheres records as they were BEFORE the last
+ * yk_scene_apply_edit (the caller keeps the table it gave, as it keeps prev_points); the current records are the scene's
+ * own.  prev_spheres NULL is yk_surface_motion byte for byte; prev_points may be NULL for a scene without triangles.
+ * Everything else as yk_surface_motion / yk_surface_motion_device (d_prev_spheres 4-byte aligned); the records go to
+ * yk_history_reproject_moved unchanged. */
+yk_status yk_surface_motion_spheres(yk_context* ctx, const yk_scene* scene, const yk_surface_id* ids, const yk_guide* guides,
+                                    const float* prev_points, const yk_sphere_desc* prev_spheres, uint16_t res_x, uint16_t res_y, yk_motion* out);
+yk_status yk_surface_motion_spheres_device(yk_context* ctx, const yk_scene* scene, const void* d_ids, const void* d_guides,
+                                           const float* d_prev_points, const void* d_prev_spheres, uint16_t res_x, uint16_t res_y, void* d_out, void* stream);
 /* yk_history_reproject through the motion records; arguments and errors as yk_history_reproject, plus `motion`. */
 yk_status yk_history_reproject_moved(yk_context* ctx, const yk_temporal_desc* desc, const yk_history* prev_history,
                                      const yk_guide* prev_guides, const yk_camera* prev_camera, const yk_guide* guides,

@@ -485,6 +485,37 @@ pub struct yk_scene_layout_info {
 pub const YK_UPDATE_ROUTE_HOST: u32 = 0;
 pub const YK_UPDATE_ROUTE_DEVICE: u32 = 1;
 
+/// the tables of an edit in place (yk_scene_apply_edit); a null table keeps what the scene has
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct yk_scene_edit {
+    pub spheres: *const yk_sphere_desc,
+    pub lights: *const yk_light_desc,
+    pub materials: *const yk_material_desc,
+    pub background: *const f32,
+}
+
+pub const YK_EDIT_LIGHTS: u32 = 1;
+pub const YK_EDIT_MATERIALS: u32 = 2;
+pub const YK_EDIT_SPHERES: u32 = 4;
+pub const YK_EDIT_BOXES: u32 = 8;
+pub const YK_EDIT_RECORDS: u32 = 16;
+pub const YK_EDIT_BACKGROUND: u32 = 32;
+
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct yk_scene_edit_info {
+    pub n_edits: u32,
+    pub route: u32,
+    pub reason: u32,
+    pub rewrote: u32,
+    pub seconds_check: f64,
+    pub seconds_tables: f64,
+    pub seconds_boxes: f64,
+    pub seconds_records: f64,
+    pub seconds_total: f64,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct yk_scene_update_info {
@@ -561,6 +592,9 @@ extern "C" {
     pub fn yk_scene_update(ctx: *mut yk_context, scene: *mut yk_scene, points: *const f32, normals: *const f32) -> yk_status;
     pub fn yk_scene_update_device(ctx: *mut yk_context, scene: *mut yk_scene, d_points: *const f32, d_normals: *const f32, stream: *mut c_void) -> yk_status;
     pub fn yk_scene_get_update_info(scene: *const yk_scene, out: *mut yk_scene_update_info) -> yk_status;
+    pub fn yk_scene_apply_edit(ctx: *mut yk_context, scene: *mut yk_scene, edit: *const yk_scene_edit) -> yk_status;
+    pub fn yk_scene_apply_edit_device(ctx: *mut yk_context, scene: *mut yk_scene, edit: *const yk_scene_edit, d_spheres: *const c_void, stream: *mut c_void) -> yk_status;
+    pub fn yk_scene_get_edit_info(scene: *const yk_scene, out: *mut yk_scene_edit_info) -> yk_status;
     pub fn yk_bvh_refit(nodes: *mut yk_bvh_node, n_nodes: usize, shape_order: *const u32, n_shapes: usize, shape_bounds: *const f32) -> yk_status;
     pub fn yk_scene_export_bvh(scene: *const yk_scene, nodes: *mut yk_bvh_node, shape_order: *mut u32) -> yk_status;
     pub fn yk_scene_get_build_info(scene: *const yk_scene, out: *mut yk_bvh_build_info) -> yk_status;
@@ -617,6 +651,8 @@ extern "C" {
     pub fn yk_render_guides_through_device(ctx: *mut yk_context, scene: *const yk_scene, camera: *const yk_camera, res_x: u16, res_y: u16, max_through: u32, d_guides: *mut c_void, d_ids: *mut c_void, d_through: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_surface_motion(ctx: *mut yk_context, scene: *const yk_scene, ids: *const yk_surface_id, guides: *const yk_guide, prev_points: *const f32, res_x: u16, res_y: u16, out: *mut yk_motion) -> yk_status;
     pub fn yk_surface_motion_device(ctx: *mut yk_context, scene: *const yk_scene, d_ids: *const c_void, d_guides: *const c_void, d_prev_points: *const f32, res_x: u16, res_y: u16, d_out: *mut c_void, stream: *mut c_void) -> yk_status;
+    pub fn yk_surface_motion_spheres(ctx: *mut yk_context, scene: *const yk_scene, ids: *const yk_surface_id, guides: *const yk_guide, prev_points: *const f32, prev_spheres: *const yk_sphere_desc, res_x: u16, res_y: u16, out: *mut yk_motion) -> yk_status;
+    pub fn yk_surface_motion_spheres_device(ctx: *mut yk_context, scene: *const yk_scene, d_ids: *const c_void, d_guides: *const c_void, d_prev_points: *const f32, d_prev_spheres: *const c_void, res_x: u16, res_y: u16, d_out: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_history_reproject_moved(ctx: *mut yk_context, desc: *const yk_temporal_desc, prev_history: *const yk_history, prev_guides: *const yk_guide, prev_camera: *const yk_camera, guides: *const yk_guide, motion: *const yk_motion, res_x: u16, res_y: u16, out_history: *mut yk_history) -> yk_status;
     pub fn yk_history_reproject_moved_device(ctx: *mut yk_context, desc: *const yk_temporal_desc, d_prev_history: *const c_void, d_prev_guides: *const c_void, prev_camera: *const yk_camera, d_guides: *const c_void, d_motion: *const c_void, res_x: u16, res_y: u16, d_out_history: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_surface_albedo(ctx: *mut yk_context, scene: *const yk_scene, ids: *const yk_surface_id, res_x: u16, res_y: u16, out: *mut yk_albedo) -> yk_status;

@@ -10,7 +10,8 @@
 //! The normal in the plane and normal tests is the current one: exact for translations, approximate under rotations; a
 //! surface that turns by more than acos(normal_cos_min) between frames loses its history.  Carried radiance is the
 //! radiance the surface had: shadows and reflections of things that moved lag for as long as `max_history` lets them.
-//! Spheres and lights do not move under an update.  The rule: yuki_amd/csrc/yk_motion.h, yk_temporal.h.  SOURCE ONLY.
+//! Spheres move through `edit_scene` (update.rs): `motion_spheres_device` takes the sphere table from before the edit
+//! beside the previous vertex buffer and carries a moved sphere's pixels along.  Lights carry no film.  The rule: yuki_amd/csrc/yk_motion.h, yk_temporal.h.  SOURCE ONLY.
 #![cfg(feature = "hip")]
 
 use crate::math::Vec2;
@@ -55,6 +56,25 @@ pub unsafe fn motion_device(
     stream: *mut c_void,
 ) -> Result<(), sys::yk_status> {
     done(sys::yk_surface_motion_device(ctx, scene, d_ids, d_guides, d_prev_points, res.x, res.y, d_motion, stream))
+}
+
+/// `motion_device` with the sphere case: `d_prev_spheres` is the scene's count of `yk_sphere_desc` records as they were
+/// before the last edit (4-byte aligned); null is `motion_device`.
+///
+/// # Safety
+/// As `motion_device`; `d_prev_points` may be null for a scene without triangles.
+pub unsafe fn motion_spheres_device(
+    ctx: *mut sys::yk_context,
+    scene: *const sys::yk_scene,
+    d_ids: *const c_void,
+    d_guides: *const c_void,
+    d_prev_points: *const f32,
+    d_prev_spheres: *const c_void,
+    res: Vec2<u16>,
+    d_motion: *mut c_void,
+    stream: *mut c_void,
+) -> Result<(), sys::yk_status> {
+    done(sys::yk_surface_motion_spheres_device(ctx, scene, d_ids, d_guides, d_prev_points, d_prev_spheres, res.x, res.y, d_motion, stream))
 }
 
 /// # Safety

@@ -110,6 +110,9 @@ SYMBOLS = {
     "yk_scene_update": (C.c_int, [vp, vp, vp, vp]),
     "yk_scene_update_device": (C.c_int, [vp, vp, vp, vp, vp]),
     "yk_scene_get_update_info": (C.c_int, [vp, C.POINTER(abi.SceneUpdateInfo)]),
+    "yk_scene_apply_edit": (C.c_int, [vp, vp, C.POINTER(abi.SceneEdit)]),
+    "yk_scene_apply_edit_device": (C.c_int, [vp, vp, C.POINTER(abi.SceneEdit), vp, vp]),
+    "yk_scene_get_edit_info": (C.c_int, [vp, C.POINTER(abi.SceneEditInfo)]),
     "yk_bvh_refit": (C.c_int, [vp, C.c_size_t, vp, C.c_size_t, vp]),
     "yk_scene_destroy": (None, [vp]),
     "yk_scene_get_info": (C.c_int, [vp, C.POINTER(SceneInfo)]),
@@ -189,6 +192,8 @@ SYMBOLS = {
     "yk_render_guides_through_device": (C.c_int, [vp, vp, C.POINTER(abi.CameraMatrices), C.c_uint16, C.c_uint16, C.c_uint32, vp, vp, vp, vp]),
     "yk_surface_motion": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint16, C.c_uint16, vp]),
     "yk_surface_motion_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint16, C.c_uint16, vp, vp]),
+    "yk_surface_motion_spheres": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_uint16, C.c_uint16, vp]),
+    "yk_surface_motion_spheres_device": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_uint16, C.c_uint16, vp, vp]),
     "yk_surface_albedo": (C.c_int, [vp, vp, vp, C.c_uint16, C.c_uint16, vp]),
     "yk_surface_albedo_device": (C.c_int, [vp, vp, vp, C.c_uint16, C.c_uint16, vp, vp]),
     "yk_albedo_mean": (C.c_int, [vp, vp, vp, C.c_uint16, C.c_uint16, C.c_uint32, vp]),

@@ -270,6 +270,29 @@ BVH_NODE_DTYPE = np.dtype(
 TILE_DTYPE = np.dtype([("x0", "<u2"), ("y0", "<u2"), ("x1", "<u2"), ("y1", "<u2")])
 INTEGRATOR_RAY_DTYPE = np.dtype([("o", "<f4", 3), ("d", "<f4", 3), ("t_max", "<f4"), ("ray_type", "<u4")])
 OVERLAY_LINE_DTYPE = np.dtype([("p0", "<f4", 3), ("p1", "<f4", 3), ("rgb", "<f4", 3)])  # yk_overlay_line, 36 bytes
+class SceneEdit(C.Structure):
+    """yk_scene_edit: the tables of an edit in place (yk_scene_apply_edit); a NULL table keeps what the scene has."""
+
+    _fields_ = [("spheres", C.POINTER(SphereDesc)), ("lights", C.POINTER(LightDesc)), ("materials", C.POINTER(MaterialDesc)), ("background", f32p)]
+
+
+class SceneEditInfo(C.Structure):
+    """yk_scene_edit_info: how a scene's last edit in place ran and what it rewrote (EDIT_* bits)."""
+
+    _fields_ = [
+        ("n_edits", C.c_uint32),
+        ("route", C.c_uint32),
+        ("reason", C.c_uint32),
+        ("rewrote", C.c_uint32),
+        ("seconds_check", C.c_double),
+        ("seconds_tables", C.c_double),
+        ("seconds_boxes", C.c_double),
+        ("seconds_records", C.c_double),
+        ("seconds_total", C.c_double),
+    ]
+
+
+SPHERE_DTYPE = np.dtype([("object_to_world", "<f4", 16), ("world_to_object", "<f4", 16), ("radius", "<f4"), ("material", "<i4")])  # yk_sphere_desc, 136 bytes
 GUIDE_DTYPE = np.dtype([("ns", "<f4", 3), ("hit", "<f4"), ("p", "<f4", 3), ("t", "<f4")])  # yk_guide, 32 bytes
 HISTORY_DTYPE = np.dtype([("rgb", "<f4", 3), ("n", "<f4")])  # yk_history, 16 bytes
 SURFACE_NONE = 0xFFFFFFFF  # YK_SURFACE_NONE
@@ -299,9 +322,22 @@ PRESENT_ENCODE_NONE, PRESENT_ENCODE_SHADER, PRESENT_ENCODE_SRGB = 0, 1, 2
 PRESENT_RGBA8, PRESENT_RGB32F = 0, 1
 LAYOUT_HOST, LAYOUT_DEVICE = 0, 1
 UPDATE_ROUTE_HOST, UPDATE_ROUTE_DEVICE = 0, 1
+EDIT_LIGHTS, EDIT_MATERIALS, EDIT_SPHERES, EDIT_BOXES, EDIT_RECORDS, EDIT_BACKGROUND = 1, 2, 4, 8, 16, 32  # yk_scene_edit_info.rewrote
 LAYOUT_REASON_NONE, LAYOUT_REASON_OUT_OF_MEMORY, LAYOUT_REASON_DEVICE_ERROR, LAYOUT_REASON_MULTI = 0, 1, 2, 3
 RECORDS_NODES, RECORDS_NODES4, RECORDS_TOP, RECORDS_TOP_ANY, RECORDS_TRIS, RECORDS_PRIM_SHADE, RECORDS_PRIM_ATTR = range(7)
 RECORD_NAMES = ("nodes", "nodes4", "top", "top_any", "tris", "prim_shade", "prim_attr")
+
+
+def pack_spheres(spheres):
+    """A list of SceneData spheres (dicts of o2w, w2o, radius, material) -> (n,) SPHERE_DTYPE records, the array
+    yk_scene_desc.spheres and yk_scene_edit.spheres point at."""
+    out = np.zeros(len(spheres), dtype=SPHERE_DTYPE)
+    if len(spheres):
+        out["object_to_world"] = np.asarray([np.asarray(s["o2w"], dtype=np.float32).reshape(16) for s in spheres], dtype=np.float32)
+        out["world_to_object"] = np.asarray([np.asarray(s["w2o"], dtype=np.float32).reshape(16) for s in spheres], dtype=np.float32)
+        out["radius"] = np.asarray([s["radius"] for s in spheres], dtype=np.float64).astype(np.float32)
+        out["material"] = np.asarray([int(s["material"]) for s in spheres], dtype=np.int32)
+    return out
 
 
 def ptr(a, ty):

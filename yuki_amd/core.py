@@ -472,19 +472,31 @@ def _prev_points(scene, prev_points):
     return np.ascontiguousarray(a)
 
 
-def surface_motion(scene, ids, guides, prev_points, ctx=None):
+def surface_motion(scene, ids, guides, prev_points, ctx=None, prev_spheres=None):
     """yk_surface_motion: where every pixel's surface point stood when the scene's vertices were `prev_points`
     ((n_vertices, 3) float32, the array given to the previous update or to creation) -> (h, w) abi.MOTION_DTYPE records
-    (p_prev, known).  `ids` and `guides` are render_guides_ids' of the current geometry.  ctx None = the host instance."""
+    (p_prev, known).  `ids` and `guides` are render_guides_ids' of the current geometry.  ctx None = the host instance.
+    With `prev_spheres` — the scene's spheres as they were before the last Scene.edit: a list of SceneData spheres or
+    (n_spheres,) abi.SPHERE_DTYPE records — yk_surface_motion_spheres: a moved sphere carries its points along;
+    `prev_points` may then be None for a scene without triangles."""
     guides = np.ascontiguousarray(guides, dtype=abi.GUIDE_DTYPE)
     if guides.ndim != 2:
         raise ValueError("guides is (h, w)")
     h, w = guides.shape
     ids = _records(ids, abi.SURFACE_ID_DTYPE, (w, h), "surface id")
-    prev_points = _prev_points(scene, prev_points)
+    if prev_points is not None or prev_spheres is None:
+        prev_points = _prev_points(scene, prev_points)
     out = np.zeros((h, w), dtype=abi.MOTION_DTYPE)
     c = ctx.h if ctx else None
-    check(lib().yk_surface_motion(c, scene.h, _p(ids), _p(guides), _p(prev_points), w, h, _p(out)), c)
+    if prev_spheres is None:
+        check(lib().yk_surface_motion(c, scene.h, _p(ids), _p(guides), _p(prev_points), w, h, _p(out)), c)
+        return out
+    if not isinstance(prev_spheres, np.ndarray):
+        prev_spheres = abi.pack_spheres(prev_spheres)
+    if prev_spheres.dtype != abi.SPHERE_DTYPE or prev_spheres.shape != (len(scene.data.spheres),):
+        raise ValueError(f"prev_spheres is ({len(scene.data.spheres)},) abi.SPHERE_DTYPE records, not {prev_spheres.shape} {prev_spheres.dtype}")
+    prev_spheres = np.ascontiguousarray(prev_spheres)
+    check(lib().yk_surface_motion_spheres(c, scene.h, _p(ids), _p(guides), _p(prev_points), _p(prev_spheres), w, h, _p(out)), c)
     return out
 
 
@@ -1274,10 +1286,16 @@ class Context:
         three, no two buffers may overlap.  No read-back: ordered on `stream` like the other guide calls."""
         check(lib().yk_render_guides_through_device(self.h, scene.h, C.byref(camera.matrices), int(res[0]), int(res[1]), int(max_through), _vp(d_guides_ptr), _vp(d_ids_ptr), _vp(d_through_ptr), _vp(stream)), self.h)
 
-    def surface_motion_device(self, scene, d_ids_ptr, d_guides_ptr, d_prev_points_ptr, res, d_out_ptr, stream=None):
+    def surface_motion_device(self, scene, d_ids_ptr, d_guides_ptr, d_prev_points_ptr, res, d_out_ptr, stream=None, d_prev_spheres_ptr=None):
         """yk_surface_motion_device: device ids and guides of the current geometry and the PREVIOUS vertex array on the device
         (3 floats for each of the scene's vertices: the caller answers for its length) -> res[0] * res[1] device yk_motion
-        records, enqueued on `stream` (default: the context's) without waiting; one launch, no allocation."""
+        records, enqueued on `stream` (default: the context's) without waiting; one launch, no allocation.  With
+        d_prev_spheres_ptr (the scene's n_spheres yk_sphere_desc records from before the last edit, on the device)
+        yk_surface_motion_spheres_device: spheres that moved carry their points along."""
+        if d_prev_spheres_ptr:
+            check(lib().yk_surface_motion_spheres_device(self.h, scene.h, _vp(d_ids_ptr), _vp(d_guides_ptr), _vp(d_prev_points_ptr), _vp(d_prev_spheres_ptr), int(res[0]), int(res[1]), _vp(d_out_ptr),
+                                                         _vp(stream)), self.h)
+            return
         check(lib().yk_surface_motion_device(self.h, scene.h, _vp(d_ids_ptr), _vp(d_guides_ptr), _vp(d_prev_points_ptr), int(res[0]), int(res[1]), _vp(d_out_ptr), _vp(stream)), self.h)
 
     def surface_albedo_device(self, scene, d_ids_ptr, res, d_out_ptr, stream=None):
@@ -1549,6 +1567,72 @@ class Scene:
         (abi.LAYOUT_REASON_*), the level launches and device bytes of the plan, and the last update's phase seconds."""
         i = abi.SceneUpdateInfo()
         check(lib().yk_scene_get_update_info(self.h, C.byref(i)))
+        return i
+
+    def edit(self, spheres=None, lights=None, materials=None, background=None, stream=None):
+        """yk_scene_apply_edit / yk_scene_apply_edit_device: the scene's spheres, lights, materials and background change
+        in place; its triangles stay.  Every table is None (keep) or as long as the scene's own: `spheres`, `lights` and
+        `materials` are lists of what SceneData holds for them (lights may also be ready abi.LightDesc values), `background`
+        is three floats.  Counts and light kinds cannot change; a material's kind and a sphere's material can.  `spheres`
+        may also be a torch tensor on the context's device, or a raw device address (int), of n_spheres *
+        sizeof(yk_sphere_desc) bytes (abi.SPHERE_DTYPE records; a tensor is uint8 with that many elements, or int32 / float32
+        with a quarter of them): it goes to yk_scene_apply_edit_device, which takes the device route — `stream` as in
+        from_device.  A tensor's element type, contiguity, element count and device are checked here (ValueError) before the
+        library is reached.  With host input `self.data` becomes a copy that carries the new tables; a sphere table in
+        device memory leaves its spheres as they were."""
+        import copy
+
+        new = copy.copy(self.data)
+        e, keep = abi.SceneEdit(), []
+        d_spheres = None
+        n_spheres = len(self.data.spheres)
+        if spheres is not None and (hasattr(spheres, "data_ptr") or isinstance(spheres, (int, np.integer))):
+            if self.ctx is None:
+                raise ValueError("a host-only scene is edited with host tables")
+            n_bytes = n_spheres * abi.SPHERE_DTYPE.itemsize
+            per = spheres.element_size() if hasattr(spheres, "element_size") else 1
+            address, stream = _device_addresses({"spheres": spheres}, {"spheres": (("uint8",) if per == 1 else ("int32", "float32"), n_bytes // per)}, self.ctx, stream)
+            d_spheres = address["spheres"]
+        elif spheres is not None:
+            if len(spheres) != n_spheres:
+                raise ValueError(f"spheres: {len(spheres)} records, the scene has {n_spheres}")
+            new.spheres = list(spheres)
+            keep.append(new.sphere_descs())
+            e.spheres = C.cast(keep[-1], C.POINTER(abi.SphereDesc))
+        if lights is not None:
+            n_lights = len(self.data.lights) if self.data.light_structs is None else len(self.data.light_structs)
+            if len(lights) != n_lights:
+                raise ValueError(f"lights: {len(lights)} records, the scene has {n_lights}")
+            if lights and isinstance(lights[0], abi.LightDesc):
+                new.light_structs = list(lights)
+            else:
+                new.lights, new.light_structs = list(lights), None
+            keep.append(new.light_descs(LightFactory))
+            e.lights = C.cast(keep[-1], C.POINTER(abi.LightDesc))
+        if materials is not None:
+            if len(materials) != len(self.data.materials):
+                raise ValueError(f"materials: {len(materials)} records, the scene has {len(self.data.materials)}")
+            new.materials = list(materials)
+            keep.append(new.material_descs())
+            e.materials = C.cast(keep[-1], C.POINTER(abi.MaterialDesc))
+        if background is not None:
+            if len(background) != 3:
+                raise ValueError("background is three floats")
+            new.background = tuple(float(x) for x in background)
+            keep.append(abi.f3(new.background))
+            e.background = C.cast(keep[-1], abi.f32p)
+        ctx_h = self.ctx.h if self.ctx else None
+        if d_spheres is not None:
+            check(lib().yk_scene_apply_edit_device(ctx_h, self.h, C.byref(e), _vp(d_spheres), _vp(stream)), ctx_h)
+        else:
+            check(lib().yk_scene_apply_edit(ctx_h, self.h, C.byref(e)), ctx_h)
+        self.data = new
+
+    def edit_info(self):
+        """yk_scene_get_edit_info: how many edits ran, the last one's route (abi.UPDATE_ROUTE_*) and reason
+        (abi.LAYOUT_REASON_*), what it rewrote (abi.EDIT_* bits) and its phase seconds."""
+        i = abi.SceneEditInfo()
+        check(lib().yk_scene_get_edit_info(self.h, C.byref(i)))
         return i
 
     def device_records(self, which):

@@ -254,6 +254,12 @@ struct yk_scene {
         std::vector<float4> texels;
         std::vector<uint4> tex_info;
     } host_shading;
+    // What yk_scene_apply_edit needs after creation.  It stands after every older member: their offsets stay what they were.
+    struct EditState {
+        std::vector<uint8_t> light_kind;  // yk_light_kind per light: an edit keeps it
+        std::vector<float> host_points;   // host-only scenes: the vertices the tree was last fitted to (a sphere edit folds every leaf again)
+        yk_scene_edit_info info = {};
+    } edit;
 };
 
 // The device scene a job of `n` rays traverses: with both node layouts present the 4-wide one
@@ -368,6 +374,25 @@ uint32_t layout_scene_device(yk_context* ctx, yk_scene* s, const DeviceTree& tre
 // layout.  Returns YK_LAYOUT_REASON_NONE, or the reason with the scene to be rewritten by the host route; *not_finite: the
 // test refused the points and the scene is untouched.  The caller holds the context's lock and has drained its streams.
 uint32_t update_scene_device(yk_context* ctx, yk_scene* s, const float* d_points, const float* d_normals, bool* not_finite);
+// The two halves of that route that an edit in place (yk_scene_apply_edit) runs too: the plan, built once and kept, and —
+// from the scene's own arrays as they stand — the boxes (`boxes` false: the tree stays as it is) and the layout's records.
+// Both return YK_LAYOUT_REASON_*; seconds_boxes / seconds_records receive the two phases' times.
+uint32_t plan_scene_update(yk_context* ctx, yk_scene* s);
+uint32_t refit_scene_device(yk_context* ctx, yk_scene* s, bool boxes, double* seconds_boxes, double* seconds_records);
+
+// ------------------------------------------------------------------ yk_scene_edit.hip
+// The sphere table of an edit in place on the device.  d_in: n_spheres yk_sphere_desc records in HBM (4-byte aligned).
+// stage: one kernel writes the DevSphere table, the six-float bounds and the material column into `staged` (scratch of the
+// caller) and raises *flag (YK_SPHERES_*) — nothing of the scene is written.  commit: the staged tables into the scene's
+// sphere table and the plan's bounds, and back to the host copies (bounds, material column).  Both return YK_LAYOUT_REASON_*.
+enum { YK_SPHERES_NOT_FINITE = 1u, YK_SPHERES_MATERIAL = 2u };
+struct StagedSpheres {
+    DevSphere* table = nullptr;
+    float* bounds = nullptr;
+    int32_t* material = nullptr;
+};
+uint32_t stage_spheres_device(yk_context* ctx, yk_scene* s, const void* d_in, DevScratch& tmp, StagedSpheres* staged, uint32_t* flag);
+uint32_t commit_spheres_device(yk_context* ctx, yk_scene* s, const StagedSpheres& staged, std::vector<int32_t>* material);
 
 // ------------------------------------------------------------------ yk_scene_input.hip
 // The input stage of yk_scene_create_device (yk_scene_input.h); both enqueue on `st` and return the launch status.
@@ -412,6 +437,7 @@ hipError_t upload_host_tree(const HostBvh& bvh, DeviceTree& tree);
 void adopt_device_tree(yk_scene* s, DeviceTree& tree, const std::shared_ptr<HostBvh>& lazy);
 Material make_material(const yk_material_desc& m);  // per-hit constants folded (GGX alpha, Oren-Nayar A / B)
 DevLight make_light(const yk_light_desc& l);
+DevSphere make_sphere(const yk_sphere_desc& sp);  // with Transform::swaps_handedness of object_to_world
 
 // ------------------------------------------------------------------ yk_render.cpp (used by yk_stages.cpp too)
 // ctx->counters: 8 x u64 (closest-hit rays, shadow rays, ...) followed by a 4-word error block whose word

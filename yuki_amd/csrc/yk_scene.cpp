@@ -41,6 +41,8 @@ static void set_scene_counts(yk_scene* s, const yk_scene_desc* d) {
     s->n_meshes = d->n_meshes;
     s->n_textures = d->n_textures;
     for (uint32_t l = 0; l < d->n_lights; ++l) s->n_delta_lights += d->lights[l].kind != YK_LIGHT_RECT ? 1u : 0u;
+    s->edit.light_kind.resize(d->n_lights);  // an edit in place keeps every light's kind
+    for (uint32_t l = 0; l < d->n_lights; ++l) s->edit.light_kind[l] = (uint8_t)d->lights[l].kind;
 }
 
 Material make_material(const yk_material_desc& m) {
@@ -105,6 +107,17 @@ DevLight make_light(const yk_light_desc& l) {
     d.n[2] = n.z;
     d.area = l.area;
     return d;
+}
+
+DevSphere make_sphere(const yk_sphere_desc& sp) {
+    DevSphere o;
+    std::memcpy(o.o2w, sp.object_to_world, 64);
+    std::memcpy(o.w2o, sp.world_to_object, 64);
+    o.radius = sp.radius;
+    o.material = sp.material;
+    o.swaps_handedness = inp::swaps_handedness(o.o2w) ? 1u : 0u;
+    o.pad = 0;
+    return o;
 }
 
 // Every device buffer a scene owns.  The first seven are its record buffers, in the order of YK_RECORDS_*.
@@ -200,21 +213,12 @@ static yk_status check_description(yk_context* ctx, const yk_scene_desc* d, bool
     return YK_OK;
 }
 
-// Sphere::world_bound (sphere.rs:121-123)
+// Sphere::world_bound (sphere.rs:121-123): the rule is inp::sphere_bound's (yk_scene_input.h)
 static ShapeBounds sphere_bound(const yk_sphere_desc& sp) {
-    const float r = sp.radius;
-    const float lo[3] = {-r, -r, -r}, hi[3] = {r, r, r};
-    const float big = 3.40282347e+38f;
-    ShapeBounds b = {{big, big, big}, {-big, -big, -big}};
-    const int corner[8][3] = {{0, 0, 0}, {1, 0, 0}, {0, 1, 0}, {0, 0, 1}, {1, 1, 0}, {1, 0, 1}, {0, 1, 1}, {1, 1, 1}};  // transform.rs:194-206
-    for (int c = 0; c < 8; ++c) {
-        V3 q = xf_point(sp.object_to_world, V3{corner[c][0] ? hi[0] : lo[0], corner[c][1] ? hi[1] : lo[1], corner[c][2] ? hi[2] : lo[2]});
-        const float qq[3] = {q.x, q.y, q.z};
-        for (int k = 0; k < 3; ++k) {
-            b.bmin[k] = rmin(b.bmin[k], qq[k]);
-            b.bmax[k] = rmax(b.bmax[k], qq[k]);
-        }
-    }
+    float six[6];
+    inp::sphere_bound(sp.object_to_world, sp.radius, six);
+    ShapeBounds b;
+    std::memcpy(&b, six, sizeof(b));
     return b;
 }
 // world bounds of every shape — Triangle::world_bound (triangle.rs:229-235), Sphere::world_bound — in the caller's shape
@@ -300,17 +304,7 @@ static yk_status small_tables(yk_context* ctx, const yk_scene_desc* d, SceneImag
     for (uint32_t m = 0; m < d->n_meshes; ++m)
         s->mesh_flags[m] = (d->meshes[m].has_normals ? YK_MESH_NORMALS : 0u) | (d->meshes[m].has_uvs ? YK_MESH_UVS : 0u) | (d->meshes[m].swaps_handedness ? YK_MESH_SWAPS : 0u);
     s->spheres.resize(std::max<uint32_t>(d->n_spheres, 1));
-    for (uint32_t k = 0; k < d->n_spheres; ++k) {
-        DevSphere& o = s->spheres[k];
-        std::memcpy(o.o2w, d->spheres[k].object_to_world, 64);
-        std::memcpy(o.w2o, d->spheres[k].world_to_object, 64);
-        o.radius = d->spheres[k].radius;
-        o.material = d->spheres[k].material;
-        const float* m = o.o2w;  // Transform::swaps_handedness, transform.rs:85-91
-        float det = m[0] * (m[5] * m[10] - m[6] * m[9]) - m[1] * (m[4] * m[10] - m[6] * m[8]) + m[2] * (m[4] * m[9] - m[5] * m[8]);
-        o.swaps_handedness = det < 0.0f ? 1u : 0u;
-        o.pad = 0;
-    }
+    for (uint32_t k = 0; k < d->n_spheres; ++k) s->spheres[k] = make_sphere(d->spheres[k]);
     s->lights.resize(std::max<uint32_t>(d->n_lights, 1));
     for (uint32_t l = 0; l < d->n_lights; ++l) s->lights[l] = make_light(d->lights[l]);
     for (uint32_t t = 0; t < d->n_textures; ++t) {
@@ -533,6 +527,7 @@ static void init_update_state(yk_scene* s, const yk_scene_desc* d, const LayoutO
         std::memcpy(&u.sphere_bounds[6 * (size_t)k], &b, sizeof(b));
     }
     if (host_only && d->n_triangles) u.host_indices.assign(d->indices, d->indices + 3 * (size_t)d->n_triangles);
+    if (host_only && d->n_triangles) s->edit.host_points.assign(d->points, d->points + 3 * (size_t)d->n_vertices);
 }
 
 // Device half: one copy of the image in the HBM of ctx's device.
@@ -832,13 +827,12 @@ static bool all_finite(const float* p, size_t n) {
     return true;
 }
 
-// The host route: yk_bvh_refit on a copy of the host tree, layout_records_host, an upload of the arrays, upload_records.
-// `points` (and `normals`, may be NULL) are host arrays that have passed the finite test.  ctx NULL: a host-only scene.
-// `reason`: why the device route was not taken or did not finish (YK_LAYOUT_REASON_*), for the update info.
-static yk_status update_scene_host(yk_context* ctx, yk_scene* s, const float* points, const float* normals, uint32_t reason) {
+// The host route of an update and of an edit: yk_bvh_refit on a copy of the host tree (`refit` false: the tree stays),
+// layout_records_host, an upload of the arrays, upload_records.  `points` (and `normals`, may be NULL) are host arrays that
+// have passed the finite test; points NULL (an edit): the scene's own, which are fetched and not uploaded again.
+// ctx NULL: a host-only scene.  The two phases' times go to *seconds_boxes and *seconds_records.
+static yk_status rewrite_scene_host(yk_context* ctx, yk_scene* s, const float* points, const float* normals, bool refit, double* seconds_boxes, double* seconds_records) {
     yk_scene::UpdateState& u = s->upd;
-    u.info.route = YK_UPDATE_ROUTE_HOST;
-    u.info.reason = reason;
     const size_t nt = s->n_triangles, ns = s->n_spheres, nv = u.n_vertices;
     const HostBvh* old = scene_host_tree(s);
     if (!old) return fail(ctx, YK_ERR_DEVICE, "the scene's tree could not be copied back from the device");
@@ -848,6 +842,13 @@ static yk_status update_scene_host(yk_context* ctx, yk_scene* s, const float* po
     std::vector<uint32_t> fetched_indices(ctx ? 3 * nt : 0);
     if (ctx) HIP_TRY(ctx, fetch(fetched_indices, s->indices));
     const uint32_t* indices = ctx ? fetched_indices.data() : u.host_indices.data();
+    const bool own_points = points == nullptr;
+    std::vector<float> fetched_points(own_points && ctx ? 3 * nv : 0);
+    if (own_points) {
+        if (ctx) HIP_TRY(ctx, fetch(fetched_points, s->points));
+        points = ctx ? fetched_points.data() : s->edit.host_points.data();
+        if (!ctx && nt && s->edit.host_points.size() != 3 * nv) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "the scene has no vertices on the host");
+    }
     std::vector<float> sb(6 * (nt + ns));  // per source shape
     for (size_t i = 0; i < nt; ++i) {
         float b[6];
@@ -856,9 +857,9 @@ static yk_status update_scene_host(yk_context* ctx, yk_scene* s, const float* po
     }
     std::copy(u.sphere_bounds.begin(), u.sphere_bounds.end(), sb.begin() + 6 * nt);
     std::shared_ptr<HostBvh> tree = std::make_shared<HostBvh>(*old);  // never through a tree that may be shared
-    yk_status rc = yk_bvh_refit(tree->nodes.data(), tree->nodes.size(), tree->shape_order.data(), nt + ns, sb.data());
+    yk_status rc = refit ? yk_bvh_refit(tree->nodes.data(), tree->nodes.size(), tree->shape_order.data(), nt + ns, sb.data()) : YK_OK;
     if (rc != YK_OK) return fail(ctx, rc, "the scene's tree does not fit its shapes");
-    u.info.seconds_boxes = now_seconds() - t0;
+    *seconds_boxes = refit ? now_seconds() - t0 : 0.0;
     t0 = now_seconds();
     if (ctx) {
         // the host layout's input: the new points and normals, everything else fetched from the scene
@@ -889,10 +890,10 @@ static yk_status update_scene_host(yk_context* ctx, yk_scene* s, const float* po
         in.sphere_material = sphere_material.data();
         in.mat_kind = u.mat_kind.data();
         in.opt = u.opt;  // the records as creation laid them out, whatever the context's options say today
-        if ((rc = upload(ctx, s->points, points, 3 * nv)) != YK_OK || (normals && (rc = upload(ctx, s->normals, normals, 3 * nv)) != YK_OK) ||
+        if ((!own_points && (rc = upload(ctx, s->points, points, 3 * nv)) != YK_OK) || (normals && (rc = upload(ctx, s->normals, normals, 3 * nv)) != YK_OK) ||
             (rc = upload_records(ctx, s, layout_records_host(in))) != YK_OK)
             return rc;
-        if (s->tree_nodes.p)  // the tree a later device-route update starts from
+        if (s->tree_nodes.p && refit)  // the tree a later device-route update starts from
             HIP_TRY(ctx, hipMemcpy(s->tree_nodes.p, tree->nodes.data(), tree->nodes.size() * sizeof(yk_bvh_node), hipMemcpyHostToDevice));
     }
     for (int k = 0; k < 3; ++k) {
@@ -906,8 +907,17 @@ static yk_status update_scene_host(yk_context* ctx, yk_scene* s, const float* po
         s->tree_fetched.store(1u);
     }
     if (ctx) bind_records(s);
-    u.info.seconds_records = now_seconds() - t0;
+    if (!ctx && !own_points) s->edit.host_points.assign(points, points + 3 * nv);  // what a later sphere edit folds the leaves from
+    *seconds_records = now_seconds() - t0;
     return YK_OK;
+}
+
+// `reason`: why the device route was not taken or did not finish (YK_LAYOUT_REASON_*), for the update info.
+static yk_status update_scene_host(yk_context* ctx, yk_scene* s, const float* points, const float* normals, uint32_t reason) {
+    yk_scene::UpdateState& u = s->upd;
+    u.info.route = YK_UPDATE_ROUTE_HOST;
+    u.info.reason = reason;
+    return rewrite_scene_host(ctx, s, points, normals, true, &u.info.seconds_boxes, &u.info.seconds_records);
 }
 
 // everything the context has enqueued: renders of the scene that were enqueued before the update finish on the old geometry
@@ -920,6 +930,17 @@ static yk_status drain_context(yk_context* ctx) {
     return YK_OK;
 }
 
+// after a device-route refit the host copy of the tree is stale: the next reader fetches the refitted one
+static void forget_host_tree(yk_scene* s) {
+    std::lock_guard<std::mutex> lock(s->tree_mu);
+    std::shared_ptr<HostBvh> fresh = std::make_shared<HostBvh>();
+    fresh->max_leaf_shapes = s->bvh->max_leaf_shapes;
+    fresh->depth = s->bvh->depth;
+    fresh->split_failed = s->bvh->split_failed;
+    s->bvh = s->bvh_lazy = fresh;
+    s->tree_fetched.store(0u);
+}
+
 // The device route on device arrays; where it fails, the arrays go to the host once (h_points / h_normals when the caller
 // has them there already) and the host route rewrites the scene.
 static yk_status update_scene(yk_context* ctx, yk_scene* s, const float* d_points, const float* d_normals, const float* h_points, const float* h_normals) {
@@ -927,14 +948,8 @@ static yk_status update_scene(yk_context* ctx, yk_scene* s, const float* d_point
     bool not_finite = false;
     const uint32_t reason = update_scene_device(ctx, s, d_points, d_normals, &not_finite);
     if (not_finite) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "points: coordinate not finite");
-    if (reason == YK_LAYOUT_REASON_NONE) {  // the host copy of the tree is stale: the next reader fetches the refitted one
-        std::lock_guard<std::mutex> lock(s->tree_mu);
-        std::shared_ptr<HostBvh> fresh = std::make_shared<HostBvh>();
-        fresh->max_leaf_shapes = s->bvh->max_leaf_shapes;
-        fresh->depth = s->bvh->depth;
-        fresh->split_failed = s->bvh->split_failed;
-        s->bvh = s->bvh_lazy = fresh;
-        s->tree_fetched.store(0u);
+    if (reason == YK_LAYOUT_REASON_NONE) {
+        forget_host_tree(s);
         bind_records(s);
         u.info.route = YK_UPDATE_ROUTE_DEVICE;
         u.info.reason = YK_LAYOUT_REASON_NONE;
@@ -963,6 +978,182 @@ static yk_status check_update(yk_context* ctx, const yk_scene* s, const float* p
 static void finish_update(yk_scene* s, double t_begin) {
     s->upd.info.n_updates += 1;
     s->upd.info.seconds_total = now_seconds() - t_begin;
+}
+
+// ------------------------------------------------------------------ yk_scene_apply_edit
+// Edit in place: spheres, lights, materials and the background change, the triangles stay.  The checks run
+// before anything of the scene is written; what is rewritten follows from what changed (include/yuki_hip.h has the table).
+
+// the host tables of an edit, checked against the scene: yk_scene_create's checks with its messages, and the two of an edit
+static yk_status check_edit_tables(yk_context* ctx, const yk_scene* s, const yk_scene_edit* e) {
+    if (e->lights)
+        for (uint32_t l = 0; l < s->n_lights; ++l)
+            if ((uint8_t)e->lights[l].kind != s->edit.light_kind[l] || e->lights[l].kind > 255u) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "lights: a light's kind cannot change");
+    if (e->spheres) {
+        for (uint32_t k = 0; k < s->n_spheres; ++k)
+            if (e->spheres[k].material < 0 || (uint32_t)e->spheres[k].material >= s->n_materials) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "sphere material out of range");
+        for (uint32_t k = 0; k < s->n_spheres; ++k)
+            if (!all_finite(reinterpret_cast<const float*>(&e->spheres[k]), 33)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "spheres: matrix entry or radius not finite");  // two matrices and the radius
+    }
+    if (e->materials)
+        for (uint32_t m = 0; m < s->n_materials; ++m)
+            if ((e->materials[m].flags & YK_MAT_FLAG_TEXTURED_A) && e->materials[m].kind == YK_MAT_MATTE && e->materials[m].a_texture >= s->n_textures)
+                return fail(ctx, YK_ERR_INVALID_ARGUMENT, "material texture index out of range");
+    return YK_OK;
+}
+
+// Every table the scene keeps of its shapes' BSDF kinds, from u.mat_kind (just rewritten) and the spheres' materials: the
+// plan's device copy, the lazy pair of a scene made from device arrays, and the shape table where it exists already.
+static yk_status refresh_kind_tables(yk_context* ctx, yk_scene* s, const std::vector<int32_t>& sphere_material) {
+    yk_scene::UpdateState& u = s->upd;
+    if (ctx && u.mat_kind_d.p) HIP_TRY(ctx, put_host_array(u.mat_kind_d, u.mat_kind.data(), u.mat_kind.size()));
+    if (s->shape_kind_lazy) {
+        s->lazy_mat_kind = u.mat_kind;
+        for (uint32_t k = 0; k < s->n_spheres; ++k) s->lazy_sphere_kind[k] = u.mat_kind[(uint32_t)sphere_material[k]];
+    }
+    const bool filled = s->shape_kind_lazy ? s->kind_fetched.load() != 0u : !s->shape_kind.empty();
+    if (!filled) return YK_OK;  // a lazy table is filled from the pair above when something asks; a host-only scene has none
+    std::vector<int32_t> mat(s->n_triangles);
+    if (ctx && s->n_triangles) HIP_TRY(ctx, hipMemcpy(mat.data(), s->tri_material.p, mat.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (!ctx) mat = s->host_shading.tri_material;
+    if (mat.size() != s->n_triangles || s->shape_kind.size() != (size_t)s->n_triangles + s->n_spheres) return fail(ctx, YK_ERR_DEVICE, "the scene's shape kinds do not fit its shapes");
+    for (uint32_t i = 0; i < s->n_triangles; ++i) s->shape_kind[i] = u.mat_kind[(uint32_t)mat[i]];
+    for (uint32_t k = 0; k < s->n_spheres; ++k) s->shape_kind[(size_t)s->n_triangles + k] = u.mat_kind[(uint32_t)sphere_material[k]];
+    return YK_OK;
+}
+
+// The edit itself, after the arguments have passed.  d_spheres: the sphere table in HBM (the _device entry), or NULL.
+static yk_status apply_edit(yk_context* ctx, yk_scene* s, const yk_scene_edit* e, const void* d_spheres, double t_begin) {
+    yk_scene::UpdateState& u = s->upd;
+    yk_scene_edit_info info = s->edit.info;
+    info.reason = YK_LAYOUT_REASON_NONE;
+    info.rewrote = 0;
+    info.seconds_tables = info.seconds_boxes = info.seconds_records = 0.0;
+    const size_t ns = s->n_spheres;
+    const bool spheres = (e->spheres || d_spheres) && ns != 0;
+    const bool device_laid = ctx && s->layout.layout == YK_LAYOUT_DEVICE;
+    bool device_route = ctx && (device_laid || (d_spheres && spheres));
+    if (ctx) (void)hipSetDevice(ctx->device);
+
+    // ---- all or nothing: the host tables, then — device route — the sphere table's flag word
+    yk_status rc = check_edit_tables(ctx, s, e);
+    if (rc != YK_OK) return rc;
+    std::vector<Material> mats;
+    std::vector<uint8_t> mat_kind;
+    if (e->materials && s->n_materials) {
+        mats.resize(s->n_materials);
+        mat_kind.assign(s->n_materials, 0u);  // a host-only scene has kept none so far
+        for (uint32_t m = 0; m < s->n_materials; ++m) {
+            mats[m] = make_material(e->materials[m]);
+            mat_kind[m] = (uint8_t)(mats[m].kind & 7u);
+        }
+    }
+    const bool kinds_changed = !mats.empty() && mat_kind != u.mat_kind;
+    const bool records = ctx && (spheres || kinds_changed);
+    DevScratch tmp;
+    StagedSpheres staged;
+    std::vector<yk_sphere_desc> fetched_spheres;  // a device table that takes the host route after all
+    const yk_sphere_desc* h_spheres = e->spheres;
+    if (device_route && (records || spheres)) {  // the plan: the tree, its levels and the two small tables in HBM
+        info.reason = plan_scene_update(ctx, s);
+        device_route = info.reason == YK_LAYOUT_REASON_NONE;
+    }
+    if (device_route && spheres) {
+        const void* d_in = d_spheres;
+        yk_sphere_desc* d_up = nullptr;
+        uint32_t flag = 0;
+        if (!d_in) {  // a host table on a device-laid scene goes up, as the points of yk_scene_update do
+            if (tmp.get(d_up, ns) && hipMemcpy(d_up, e->spheres, ns * sizeof(yk_sphere_desc), hipMemcpyHostToDevice) == hipSuccess)
+                d_in = d_up;
+            else
+                info.reason = layout_reason_of(tmp.err != hipSuccess ? tmp.err : hipErrorUnknown);
+        }
+        if (d_in) info.reason = stage_spheres_device(ctx, s, d_in, tmp, &staged, &flag);
+        device_route = info.reason == YK_LAYOUT_REASON_NONE;
+        if (device_route && (flag & YK_SPHERES_MATERIAL)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "sphere material out of range");
+        if (device_route && (flag & YK_SPHERES_NOT_FINITE)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "spheres: matrix entry or radius not finite");
+    }
+    if (!device_route && spheres && !h_spheres) {  // the device table to the host once, and the host's checks
+        fetched_spheres.resize(ns);
+        HIP_TRY(ctx, hipMemcpy(fetched_spheres.data(), d_spheres, ns * sizeof(yk_sphere_desc), hipMemcpyDeviceToHost));
+        h_spheres = fetched_spheres.data();
+        yk_scene_edit only_spheres = {h_spheres, nullptr, nullptr, nullptr};
+        if ((rc = check_edit_tables(ctx, s, &only_spheres)) != YK_OK) return rc;
+    }
+    info.seconds_check = now_seconds() - t_begin;
+
+    // ---- the small tables
+    double t0 = now_seconds();
+    if (e->lights && s->n_lights) {
+        std::vector<DevLight> lights(s->n_lights);
+        for (uint32_t l = 0; l < s->n_lights; ++l) lights[l] = make_light(e->lights[l]);
+        if (ctx && (rc = upload(ctx, s->lights, lights.data(), lights.size())) != YK_OK) return rc;
+        info.rewrote |= YK_EDIT_LIGHTS;
+    }
+    if (!mats.empty()) {
+        if (ctx && (rc = upload(ctx, s->materials, mats.data(), mats.size())) != YK_OK) return rc;
+        if (!ctx) s->host_shading.materials = mats;
+        u.mat_kind = mat_kind;
+        info.rewrote |= YK_EDIT_MATERIALS;
+    }
+    std::vector<int32_t> sphere_material(ns);
+    if (spheres && device_route) {
+        info.reason = commit_spheres_device(ctx, s, staged, &sphere_material);
+        if (info.reason != YK_LAYOUT_REASON_NONE) return fail(ctx, YK_ERR_DEVICE, "the staged sphere table could not be copied into the scene");
+    } else if (spheres) {
+        std::vector<DevSphere> table(ns);
+        for (size_t k = 0; k < ns; ++k) {
+            table[k] = make_sphere(h_spheres[k]);
+            sphere_material[k] = h_spheres[k].material;
+            const ShapeBounds b = sphere_bound(h_spheres[k]);
+            std::memcpy(&u.sphere_bounds[6 * k], &b, sizeof(b));
+        }
+        if (ctx && (rc = upload(ctx, s->spheres, table.data(), table.size())) != YK_OK) return rc;
+        if (ctx && u.sphere_b.p) HIP_TRY(ctx, put_host_array(u.sphere_b, u.sphere_bounds.data(), u.sphere_bounds.size() * 4));
+        if (!ctx) s->host_shading.spheres = table;
+    } else if (kinds_changed && ns) {  // the spheres' materials as the scene has them
+        std::vector<DevSphere> table(ctx ? ns : 0);
+        if (ctx) HIP_TRY(ctx, hipMemcpy(table.data(), s->spheres.p, ns * sizeof(DevSphere), hipMemcpyDeviceToHost));
+        const std::vector<DevSphere>& have = ctx ? table : s->host_shading.spheres;
+        for (size_t k = 0; k < ns && k < have.size(); ++k) sphere_material[k] = have[k].material;
+    }
+    if (spheres) info.rewrote |= YK_EDIT_SPHERES;
+    if ((spheres || kinds_changed) && (rc = refresh_kind_tables(ctx, s, sphere_material)) != YK_OK) return rc;
+    if (e->background) {
+        for (int k = 0; k < 3; ++k) s->dev.background[k] = e->background[k];
+        info.rewrote |= YK_EDIT_BACKGROUND;
+    }
+    info.seconds_tables = now_seconds() - t0;
+
+    // ---- boxes and records
+    if (device_route && records) {
+        info.reason = refit_scene_device(ctx, s, spheres, &info.seconds_boxes, &info.seconds_records);
+        if (info.reason == YK_LAYOUT_REASON_NONE) {
+            if (spheres) forget_host_tree(s);
+            bind_records(s);
+        } else {
+            (void)hipGetLastError();
+            device_route = false;
+        }
+    }
+    if (!device_route && (records || (spheres && !ctx)) && (rc = rewrite_scene_host(ctx, s, nullptr, nullptr, spheres, &info.seconds_boxes, &info.seconds_records)) != YK_OK) return rc;
+    if (spheres) info.rewrote |= YK_EDIT_BOXES;
+    if (records) info.rewrote |= YK_EDIT_RECORDS;
+    info.route = device_route ? YK_UPDATE_ROUTE_DEVICE : YK_UPDATE_ROUTE_HOST;
+    if (!device_laid && !d_spheres) info.reason = YK_LAYOUT_REASON_NONE;  // the host route was the one asked for
+    info.n_edits += 1;
+    info.seconds_total = now_seconds() - t_begin;
+    s->edit.info = info;
+    return YK_OK;
+}
+
+// the arguments both entry points refuse alike
+static yk_status check_edit(yk_context* ctx, const yk_scene* s, const yk_scene_edit* e, const void* d_spheres) {
+    if (!s) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null scene");
+    if (!e) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null edit");
+    if (e->spheres && d_spheres) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "spheres given as a host table and as a device table");
+    if (ctx ? (!s->on_device || s->device != ctx->device) : s->on_device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "scene was not created on this context's device");
+    return YK_OK;
 }
 
 extern "C" {
@@ -1061,6 +1252,44 @@ yk_status yk_scene_update_device(yk_context* ctx, yk_scene* s, const float* d_po
 yk_status yk_scene_get_update_info(const yk_scene* s, yk_scene_update_info* out) {
     if (!s || !out) return YK_ERR_INVALID_ARGUMENT;
     *out = s->upd.info;
+    return YK_OK;
+}
+
+yk_status yk_scene_apply_edit(yk_context* ctx, yk_scene* s, const yk_scene_edit* edit) try {
+    std::unique_lock<std::recursive_mutex> yk_lock_;
+    if (ctx) yk_lock_ = std::unique_lock<std::recursive_mutex>(ctx->mu);
+    const double t_begin = now_seconds();
+    yk_status rc = check_edit(ctx, s, edit, nullptr);
+    if (rc != YK_OK) return rc;
+    if (ctx) {
+        (void)hipSetDevice(ctx->device);
+        if ((rc = drain_context(ctx)) != YK_OK) return rc;
+    }
+    return apply_edit(ctx, s, edit, nullptr, t_begin);
+} YK_CATCH(ctx)
+
+yk_status yk_scene_apply_edit_device(yk_context* ctx, yk_scene* s, const yk_scene_edit* edit, const void* d_spheres, void* stream) try {
+    if (!ctx) return fail(nullptr, YK_ERR_INVALID_ARGUMENT, edit && edit->spheres && d_spheres ? "spheres given as a host table and as a device table" : "a sphere table in device memory needs a context");
+    YK_LOCK(ctx);
+    const double t_begin = now_seconds();
+    yk_status rc = check_edit(ctx, s, edit, d_spheres);
+    if (rc != YK_OK) return rc;
+    (void)hipSetDevice(ctx->device);
+    if (d_spheres && s->n_spheres) {  // the pointer checks of yk_scene_create_device, with its messages
+        if ((rc = check_device_arrays(ctx, {{"spheres", d_spheres, sizeof(yk_sphere_desc) * (size_t)s->n_spheres}})) != YK_OK) return rc;
+        if (reinterpret_cast<uintptr_t>(d_spheres) & 3u) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "spheres must be 4-byte aligned");
+    }
+    if (stream) {  // the caller's table is complete where its stream stands now
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_in, (hipStream_t)stream));
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_in, 0));
+    }
+    if ((rc = drain_context(ctx)) != YK_OK) return rc;
+    return apply_edit(ctx, s, edit, d_spheres, t_begin);
+} YK_CATCH(ctx)
+
+yk_status yk_scene_get_edit_info(const yk_scene* s, yk_scene_edit_info* out) {
+    if (!s || !out) return YK_ERR_INVALID_ARGUMENT;
+    *out = s->edit.info;
     return YK_OK;
 }
 

@@ -82,5 +82,34 @@ YK_HD bool tri_bound(const float* points, const uint32_t* indices, uint32_t i, f
     return finite;
 }
 
+// Sphere::world_bound (sphere.rs:121-123): the object-space box [-r, r]^3 through object_to_world — its eight corners in
+// the order of transform.rs:194-206, each through xf_point, folded with rmin / rmax from -+FLT_MAX.  out = {min.xyz, max.xyz}.
+// One text for creation (yk_scene.cpp), the host route of an edit and k_spheres_in (yk_scene_edit.hip).
+YK_HD void sphere_bound(const float* object_to_world, float radius, float (&out)[6]) {
+    const float big = 3.40282347e+38f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        out[k] = big;
+        out[3 + k] = -big;
+    }
+    // corner c takes the box's maximum on an axis where its bit is set: (0,0,0) (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1)
+    const unsigned x_hi = 0xb2u, y_hi = 0xd4u, z_hi = 0xe8u;
+#pragma unroll
+    for (int c = 0; c < 8; ++c) {
+        const V3 q = xf_point(object_to_world, V3{(x_hi >> c) & 1u ? radius : -radius, (y_hi >> c) & 1u ? radius : -radius, (z_hi >> c) & 1u ? radius : -radius});
+        const float qq[3] = {q.x, q.y, q.z};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            out[k] = rmin(out[k], qq[k]);
+            out[3 + k] = rmax(out[3 + k], qq[k]);
+        }
+    }
+}
+// Transform::swaps_handedness (transform.rs:85-91) of a sphere's object_to_world: the sign of the upper 3 x 3 determinant
+YK_HD bool swaps_handedness(const float* m) {
+    const float det = m[0] * (m[5] * m[10] - m[6] * m[9]) - m[1] * (m[4] * m[10] - m[6] * m[8]) + m[2] * (m[4] * m[9] - m[5] * m[8]);
+    return det < 0.0f;
+}
+
 }  // namespace inp
 }  // namespace yk

@@ -4,7 +4,8 @@
 // The rule.  A refit keeps the tree's topology and the leaf order and recomputes what depends on coordinates:
 //   * a leaf's box is folded from the default bounds, left to right in leaf order, with rmin / rmax — exactly as the
 //     builder folds a leaf (yk_bvh_build.h: the fold's order decides the sign of a zero).  A triangle contributes
-//     Triangle::world_bound of the new points (inp::tri_bound), a sphere the bound it had at creation;
+//     Triangle::world_bound of the new points (inp::tri_bound), a sphere Sphere::world_bound of its record (inp::sphere_bound:
+//     as at creation, or as the last yk_scene_apply_edit left it);
 //   * an interior node's box is lv::interior_bounds, in child order, once both children are done;
 //   * the records follow from the refitted tree through the layout's own code (yk_scene_layout.h / layout_records_host).
 // Words 6 and 7 of a node (links, slot, count, axis, leaf flag) are never written.

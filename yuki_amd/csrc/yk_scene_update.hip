@@ -15,6 +15,8 @@
 // per level with integer atomics, a host scan over the few levels, a scatter; the order inside a level is free — with the
 // leaves as the last group, the spheres' bounds and the materials' kinds.  The interior index, the wide slots and the
 // last-in-leaf marks are recomputed by the layout on every update (DESIGN.md §3 has the measurement).
+// An edit in place (yk_scene_apply_edit, yk_scene.cpp) runs the same plan and the same boxes and records (plan_scene_update,
+// refit_scene_device) after it has rewritten the spheres' bounds or the materials' kinds.
 // Also here: yk_bvh_refit, the host instance of the rule.
 #include <hip/hip_runtime.h>
 
@@ -186,6 +188,11 @@ uint32_t build_plan(yk_context* ctx, yk_scene* s) {
 
 }  // namespace
 
+uint32_t plan_scene_update(yk_context* ctx, yk_scene* s) {
+    (void)hipSetDevice(ctx->device);
+    return s->upd.planned ? (uint32_t)YK_LAYOUT_REASON_NONE : build_plan(ctx, s);
+}
+
 uint32_t update_scene_device(yk_context* ctx, yk_scene* s, const float* d_points, const float* d_normals, bool* not_finite) {
     *not_finite = false;
     yk_scene::UpdateState& u = s->upd;
@@ -193,7 +200,7 @@ uint32_t update_scene_device(yk_context* ctx, yk_scene* s, const float* d_points
     hipStream_t st = ctx->stream;
     double t0 = now_seconds();
     if (!u.planned) {
-        const uint32_t r = build_plan(ctx, s);
+        const uint32_t r = plan_scene_update(ctx, s);
         if (r != YK_LAYOUT_REASON_NONE) return r;
         t0 = now_seconds();  // the plan counts in seconds_total only
     }
@@ -216,25 +223,35 @@ uint32_t update_scene_device(yk_context* ctx, yk_scene* s, const float* d_points
     UPD_TRY(hipMemcpyAsync(s->points.p, d_points, n_floats * 4, hipMemcpyDeviceToDevice, st));
     if (d_normals) UPD_TRY(hipMemcpyAsync(s->normals.p, d_normals, n_floats * 4, hipMemcpyDeviceToDevice, st));
     u.info.seconds_check = now_seconds() - t0;
+    return refit_scene_device(ctx, s, true, &u.info.seconds_boxes, &u.info.seconds_records);
+}
+
+uint32_t refit_scene_device(yk_context* ctx, yk_scene* s, bool boxes, double* seconds_boxes, double* seconds_records) {
+    yk_scene::UpdateState& u = s->upd;
+    (void)hipSetDevice(ctx->device);
+    hipStream_t st = ctx->stream;
+    if (!u.planned) return YK_LAYOUT_REASON_DEVICE_ERROR;
 
     // boxes: the leaves, then the levels bottom-up
-    t0 = now_seconds();
+    double t0 = now_seconds();
     const uint32_t n = (uint32_t)s->info.n_nodes, np = (uint32_t)s->info.n_shapes, n_levels = u.info.n_levels;
     uint32_t* nodes = s->tree_nodes.as<uint32_t>();
-    const uint32_t* list = u.list.as<uint32_t>();
-    const uint32_t n_leaves = u.level_off[n_levels + 2u] - u.level_off[n_levels + 1u];
-    k_leaves<<<blocks(n_leaves), kThreads, 0, st>>>(nodes, list + u.level_off[n_levels + 1u], n_leaves, n, s->tree_order.as<uint32_t>(),
-                                                    GeometryBound{s->points.as<float>(), s->indices.as<uint32_t>(), u.sphere_b.as<float>(), s->n_triangles, np});
-    UPD_TRY(hipGetLastError());
-    uint32_t n_top = 0;  // the levels at the top that one block finishes
-    while (ctx->update_top_block && n_top < n_levels && u.level_off[n_top + 1u] - u.level_off[n_top] <= (uint32_t)kThreads) ++n_top;
-    if (n_top < 2u) n_top = 0;  // one level is one launch either way
-    for (uint32_t d = n_levels; d-- > n_top;) {
-        const uint32_t count = u.level_off[d + 1u] - u.level_off[d];
-        k_level<<<blocks(count), kThreads, 0, st>>>(nodes, list + u.level_off[d], count, n);
+    if (boxes) {
+        const uint32_t* list = u.list.as<uint32_t>();
+        const uint32_t n_leaves = u.level_off[n_levels + 2u] - u.level_off[n_levels + 1u];
+        k_leaves<<<blocks(n_leaves), kThreads, 0, st>>>(nodes, list + u.level_off[n_levels + 1u], n_leaves, n, s->tree_order.as<uint32_t>(),
+                                                        GeometryBound{s->points.as<float>(), s->indices.as<uint32_t>(), u.sphere_b.as<float>(), s->n_triangles, np});
+        UPD_TRY(hipGetLastError());
+        uint32_t n_top = 0;  // the levels at the top that one block finishes
+        while (ctx->update_top_block && n_top < n_levels && u.level_off[n_top + 1u] - u.level_off[n_top] <= (uint32_t)kThreads) ++n_top;
+        if (n_top < 2u) n_top = 0;  // one level is one launch either way
+        for (uint32_t d = n_levels; d-- > n_top;) {
+            const uint32_t count = u.level_off[d + 1u] - u.level_off[d];
+            k_level<<<blocks(count), kThreads, 0, st>>>(nodes, list + u.level_off[d], count, n);
+        }
+        if (n_top) k_top_levels<<<1, kThreads, 0, st>>>(nodes, list, u.words.as<uint32_t>(), n_top, n);
+        UPD_TRY(hipGetLastError());
     }
-    if (n_top) k_top_levels<<<1, kThreads, 0, st>>>(nodes, list, u.words.as<uint32_t>(), n_top, n);
-    UPD_TRY(hipGetLastError());
     DeviceTree tree;  // borrowed: the buffers stay the scene's
     tree.nodes = s->tree_nodes;
     tree.depth = u.depth;
@@ -243,14 +260,14 @@ uint32_t update_scene_device(yk_context* ctx, yk_scene* s, const float* d_points
     tree.n_shapes = np;
     UPD_TRY(hipMemcpyAsync(tree.root_words, nodes, 32, hipMemcpyDeviceToHost, st));
     UPD_TRY(hipStreamSynchronize(st));
-    u.info.seconds_boxes = now_seconds() - t0;
+    *seconds_boxes = boxes ? now_seconds() - t0 : 0.0;
 
     // records, by the layout's own kernels
     t0 = now_seconds();
     bool order_applied = false;
     const uint32_t r = layout_scene_device(ctx, s, tree, nullptr, u.mat_kind_d.as<uint8_t>(), s->record_bytes[YK_RECORDS_PRIM_ATTR] != 0, s->bvh->depth, &order_applied);
     if (r != YK_LAYOUT_REASON_NONE) return r;
-    u.info.seconds_records = now_seconds() - t0;
+    *seconds_records = now_seconds() - t0;
     yk_bvh_node root;
     std::memcpy(&root, tree.root_words, sizeof(root));
     for (int k = 0; k < 3; ++k) {

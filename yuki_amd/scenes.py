@@ -122,6 +122,25 @@ class SceneData:
                 raise ValueError(l["kind"])
         return arr
 
+    def sphere_descs(self):
+        """The spheres as a ctypes array of SphereDesc (one element where there is none), for yk_scene_desc and yk_scene_edit."""
+        sph = (abi.SphereDesc * max(1, len(self.spheres)))()
+        packed = abi.pack_spheres(self.spheres)
+        C.memmove(sph, packed.ctypes.data, packed.nbytes)
+        return sph
+
+    def material_descs(self):
+        """The materials as a ctypes array of MaterialDesc (one element where there is none)."""
+        mats = (abi.MaterialDesc * max(1, len(self.materials)))()
+        for k, m in enumerate(self.materials):
+            mats[k].kind = m["kind"]
+            mats[k].a = abi.f3(m.get("a", (0, 0, 0)))
+            mats[k].b = abi.f3(m.get("b", (0, 0, 0)))
+            mats[k].c = float(m.get("c", 0.0))
+            mats[k].flags = (1 if m.get("remap", False) else 0) | (2 if m.get("tex") is not None else 0)
+            mats[k].a_texture = int(m["tex"]) if m.get("tex") is not None else 0
+        return mats
+
     def desc(self, factory):
         """(SceneDesc, keepalive) for yk_scene_create."""
         keep = {}
@@ -148,23 +167,11 @@ class SceneData:
         keep["meshes"] = meshes
         d.n_meshes = len(self.meshes)
         d.meshes = C.cast(meshes, C.POINTER(abi.MeshDesc))
-        sph = (abi.SphereDesc * max(1, len(self.spheres)))()
-        for k, s in enumerate(self.spheres):
-            sph[k].object_to_world = abi.f16(s["o2w"])
-            sph[k].world_to_object = abi.f16(s["w2o"])
-            sph[k].radius = float(s["radius"])
-            sph[k].material = int(s["material"])
+        sph = self.sphere_descs()
         keep["spheres"] = sph
         d.n_spheres = len(self.spheres)
         d.spheres = C.cast(sph, C.POINTER(abi.SphereDesc))
-        mats = (abi.MaterialDesc * max(1, len(self.materials)))()
-        for k, m in enumerate(self.materials):
-            mats[k].kind = m["kind"]
-            mats[k].a = abi.f3(m.get("a", (0, 0, 0)))
-            mats[k].b = abi.f3(m.get("b", (0, 0, 0)))
-            mats[k].c = float(m.get("c", 0.0))
-            mats[k].flags = (1 if m.get("remap", False) else 0) | (2 if m.get("tex") is not None else 0)
-            mats[k].a_texture = int(m["tex"]) if m.get("tex") is not None else 0
+        mats = self.material_descs()
         keep["materials"] = mats
         d.n_materials = len(self.materials)
         d.materials = C.cast(mats, C.POINTER(abi.MaterialDesc))
