@@ -1,9 +1,10 @@
 """Scene.edit / yk_scene_apply_edit[_device] and yk_surface_motion_spheres on the device (yuki_amd/csrc/yk_scene_edit.hip,
-yk_scene.cpp, yk_motion.hip): an edit with the scene's own tables changes no byte; an edit of lights, materials or the
+yk_scene_change.cpp, yk_motion.hip): an edit with the scene's own tables changes no byte; an edit of lights, materials or the
 background gives the scene creation makes of the edited description, records and rendered bits; the device route of a
 sphere edit writes what the host route writes; the edited scene answers rays as the moved geometry does; a render enqueued
 before an edit sees the old scene; bad tables are refused with nothing written; the motion pass with a previous sphere table
-equals its host instance; and the chain carries a moved sphere's history to where the float64 statement says."""
+equals its host instance; the chain carries a moved sphere's history to where the float64 statement says; and every edit and
+update of a host-laid and of a device-laid scene runs as the hand-written table of tests/cpp/scene_change_table.inc says."""
 import copy
 
 import numpy as np
@@ -18,7 +19,9 @@ from test_gpu_scene_from_device import _render_tile, _snapshot, _tensors
 from test_gpu_scene_layout import SEED as LAYOUT_SEED
 from test_gpu_scene_update import _same
 from test_gpu_trace_kernels import closest_ids
-from test_scene_edit import motion_tolerance, own_tables
+from test_scene_change_plan import row_of
+from test_scene_edit import follow_the_edit_rows, motion_tolerance, own_tables
+from test_scene_update import wobble
 from test_temporal import same_bits
 from yuki_amd import _ffi, abi, scenes
 
@@ -375,4 +378,25 @@ def test_the_history_of_a_moved_sphere_lands_where_float64_says(yk, contexts):
         print(f"carried positions {label} sphere motion: median {distance[label][0]:.3f} of the move over {distance[label][1]} pixels")
     assert distance["with"][1] >= 10 and distance["with"][0] < 0.25
     assert distance["without"][1] == 0 or distance["without"][0] > 0.75
+    s.close()
+
+
+# ---- 15. the library follows the plan
+@pytest.mark.parametrize("layout", list(LAYOUTS))
+@pytest.mark.parametrize("name", ["cornell", "glass_balls"])
+def test_a_scene_on_the_device_follows_the_plan(yk, contexts, name, layout):
+    sd = SCENES[name]()
+    kind = {"host-laid": "HOST_LAID", "device-laid": "DEVICE_LAID"}[layout]
+    s = yk.Scene(contexts(**LAYOUTS[layout]), sd)
+    assert s.layout_info().layout == (abi.LAYOUT_DEVICE if layout == "device-laid" else abi.LAYOUT_HOST)
+    moved = ref.moved_spheres(sd.spheres, "rotation")
+    seen = follow_the_edit_rows(s, sd, kind, {"NONE": None, "SPHERES_HOST": moved, "SPHERES_DEVICE": _dev_spheres(moved)})
+    assert {r[:4] for r in seen} == {(kind, b, 1, k) for b in ("NONE", "SPHERES_HOST", "SPHERES_DEVICE") for k in (0, 1)}
+    points = wobble(sd, 0.02)
+    for brings, given in (("POINTS_HOST", points), ("POINTS_DEVICE", torch.from_numpy(points).to("cuda:0")), ("POINTS_HOST", np.ascontiguousarray(sd.points, F))):
+        row = row_of(kind, brings, True, False)
+        before = s.update_info().n_updates
+        s.update(given)
+        i = s.update_info()
+        assert (i.n_updates, i.route, i.reason) == (before + 1, {"HOST": abi.UPDATE_ROUTE_HOST, "DEVICE": abi.UPDATE_ROUTE_DEVICE}[row.verdict], 0), (kind, brings, i.route, i.reason)
     s.close()

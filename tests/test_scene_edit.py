@@ -2,9 +2,11 @@
 with the scene's own tables leaves the tree as it is; the bound rule restated in numpy (tests/scene_edit_ref.py) is
 creation's, bit for bit; moved spheres give the tree of tests/refit_ref.py fed with the restated bounds; refused edits write
 nothing; the host instance of the motion pass with a previous sphere table equals its float32 restatement bit for bit and
-stays within a measured tolerance (profiles/scene_edit_tolerances.json) of the float64 statement."""
+stays within a measured tolerance (profiles/scene_edit_tolerances.json) of the float64 statement; and every edit a host-only
+scene can be given runs as the hand-written table of tests/cpp/scene_change_table.inc says."""
 import copy
 import ctypes as C
+import itertools
 import json
 import os
 
@@ -15,6 +17,7 @@ import motion_ref
 import refit_ref
 import scene_edit_ref as ref
 from test_motion import oracle_view
+from test_scene_change_plan import row_of
 from test_scene_update import SCENES as UPDATE_SCENES
 from test_scene_update import sphere_table, tree_state
 from test_temporal import camera, same_bits
@@ -169,6 +172,51 @@ def test_refused_edits_write_nothing(yk):
         with pytest.raises(ValueError):
             s.edit(**wrong)
     assert tree_state(s) == before and s.edit_info().n_edits == 0
+    s.close()
+
+
+# ---- 4b. the library follows the plan
+def glass_for_matte(materials):
+    """The table with material 2 (matte in cornell and in glass_balls) turned into glass, or back: its device BSDF kind changes."""
+    out = copy.deepcopy(materials)
+    out[2] = dict(kind=abi.MAT_GLASS, a=(1, 0.9, 0.9), b=(1, 1, 1), c=1.5) if out[2]["kind"] != abi.MAT_GLASS else dict(kind=abi.MAT_MATTE, a=(0.1, 0.2, 0.7), c=0.0)
+    return out
+
+
+def follow_the_edit_rows(s, sd, scene_kind, sphere_tables):
+    """Every combination of sphere table (`sphere_tables`: row name -> what Scene.edit takes), lights, materials (none, the
+    same kinds, changed kinds) and background, applied to `s` one after the other: route, reason and rewrote are the row's
+    of tests/cpp/scene_change_table.inc, and n_edits rises by one.  Returns the rows it went through."""
+    seen = set()
+    materials = sd.materials  # as the scene has them now
+    for brings, lights, mats, background in itertools.product(sphere_tables, (False, True), (None, "same", "changed"), (False, True)):
+        row = row_of(scene_kind, brings, len(sd.spheres), mats == "changed")
+        if mats == "changed":
+            materials = glass_for_matte(materials)
+        before = s.edit_info().n_edits
+        s.edit(spheres=sphere_tables[brings], lights=own_tables(sd)["lights"] if lights else None, materials=materials if mats else None, background=(0.25, 0.5, 0.125) if background else None)
+        i = s.edit_info()
+        want = (abi.EDIT_LIGHTS * (lights and bool(len(sd.lights))) | abi.EDIT_MATERIALS * bool(mats) | abi.EDIT_BACKGROUND * background | abi.EDIT_SPHERES * row.spheres | abi.EDIT_BOXES * row.boxes
+                | abi.EDIT_RECORDS * row.records)
+        case = (scene_kind, brings, lights, mats, background)
+        assert i.n_edits == before + 1, case
+        assert (i.route, i.reason) == ({"HOST": abi.UPDATE_ROUTE_HOST, "DEVICE": abi.UPDATE_ROUTE_DEVICE}[row.verdict], 0), (case, i.route, i.reason)
+        assert i.rewrote == want, (case, i.rewrote, want)
+        assert (row.boxes or i.seconds_boxes == 0.0) and (row.boxes or row.records or i.seconds_records == 0.0), case  # a phase that did not run took no time
+        seen.add(row)
+    return seen
+
+
+@pytest.mark.parametrize("name", ["cornell", "glass_balls"])
+def test_a_host_only_scene_follows_the_plan(yk, name):
+    sd = SCENES[name]()
+    s = yk.Scene(None, sd)
+    seen = follow_the_edit_rows(s, sd, "HOST_ONLY", {"NONE": None, "SPHERES_HOST": ref.moved_spheres(sd.spheres, "rotation")})
+    assert {r[:4] for r in seen} == {("HOST_ONLY", b, 1, k) for b in ("NONE", "SPHERES_HOST") for k in (0, 1)}  # every row such a scene can reach
+    with pytest.raises(ValueError):  # the REFUSED rows: Scene.edit sends no device table without a context ...
+        s.edit(spheres=0x1000)
+    e = abi.SceneEdit()  # ... and neither does the library
+    assert yk.lib().yk_scene_apply_edit_device(None, s.h, C.byref(e), C.c_void_p(0x1000), None) == 1
     s.close()
 
 

@@ -97,61 +97,24 @@ yk_status enqueue(yk_context* ctx, hipStream_t st, const yk_scene* scene, const 
     return YK_OK;
 }
 
-// The arrays al_pixel reads, as host arrays behind a DevScene.
-DevScene host_view(const yk_scene::ShadingTables& h, const uint32_t* indices) {
-    DevScene sc{};
-    sc.indices = indices;
-    sc.uvs = h.uvs.data();
-    sc.tri_mesh = h.tri_mesh.data();
-    sc.tri_material = h.tri_material.data();
-    sc.mesh_flags = h.mesh_flags.data();
-    sc.materials = h.materials.data();
-    sc.spheres = h.spheres.data();
-    sc.texels = h.texels.data();
-    sc.tex_info = h.tex_info.data();
-    return sc;
-}
-
-// A scene in device memory: the same arrays copied back from its device.
-hipError_t fetch_tables(const yk_scene* s, yk_scene::ShadingTables& h) {
-    const size_t nt = s->n_triangles;
-    h.indices.resize(3 * nt);
-    h.tri_mesh.resize(nt);
-    h.tri_material.resize(nt);
-    h.mesh_flags.resize(std::max<uint32_t>(s->n_meshes, 1));
-    h.materials.resize(std::max<uint32_t>(s->n_materials, 1));
-    h.spheres.resize(std::max<uint32_t>(s->n_spheres, 1));
-    h.uvs.resize(s->upd.has_uvs ? 2 * (size_t)s->upd.n_vertices : 0);
-    h.tex_info.resize(s->n_textures);
-    const auto get = [](auto& v, const DevBuf& b) -> hipError_t {
-        const size_t bytes = v.size() * sizeof(v[0]);
-        if (bytes == 0) return hipSuccess;
-        if (!b.p || b.bytes < bytes) return hipErrorInvalidValue;
-        return hipMemcpy(v.data(), b.p, bytes, hipMemcpyDeviceToHost);
-    };
-    hipError_t e;
-    if ((e = get(h.indices, s->indices)) != hipSuccess || (e = get(h.tri_mesh, s->tri_mesh)) != hipSuccess || (e = get(h.tri_material, s->tri_material)) != hipSuccess ||
-        (e = get(h.mesh_flags, s->mesh_flags)) != hipSuccess || (e = get(h.materials, s->materials)) != hipSuccess || (e = get(h.spheres, s->spheres)) != hipSuccess ||
-        (e = get(h.uvs, s->uvs)) != hipSuccess || (e = get(h.tex_info, s->tex_info)) != hipSuccess)
-        return e;
-    size_t n_texels = 0;
-    for (const uint4& t : h.tex_info) n_texels = std::max(n_texels, (size_t)t.x + (size_t)t.y * t.z);
-    h.texels.resize(n_texels);
-    return get(h.texels, s->texels);
-}
-
-// The host instances' view of a scene's shading tables, handed to use(const DevScene&): a host-only scene keeps its tables,
-// a scene in device memory has them fetched for the call.
+// The host instances' view of a scene's shading tables — the arrays al_pixel reads, as host arrays behind a DevScene —
+// handed to use(const DevScene&): a host-only scene keeps them, a scene in device memory has them fetched for the call.
 template <class Use>
 yk_status with_host_tables(yk_context* ctx, const yk_scene* scene, const Use& use) {
-    if (!scene->on_device) {
-        use(host_view(scene->host_shading, scene->upd.host_indices.data()));
-        return YK_OK;
-    }
-    yk_scene::ShadingTables fetched;
-    (void)hipSetDevice(scene->device);
-    HIP_TRY(ctx, fetch_tables(scene, fetched));
-    use(host_view(fetched, fetched.indices.data()));
+    HostArrays h;
+    const yk_status rc = scene_host_arrays(ctx, scene, HOST_INDICES | HOST_UVS | HOST_TRI_MESH | HOST_TRI_MATERIAL | HOST_MESH_FLAGS | HOST_MATERIALS | HOST_SPHERES | HOST_TEXTURES, "", h);
+    if (rc != YK_OK) return rc;
+    DevScene sc{};
+    sc.indices = h->indices.data();
+    sc.uvs = h->uvs.data();
+    sc.tri_mesh = h->tri_mesh.data();
+    sc.tri_material = h->tri_material.data();
+    sc.mesh_flags = h->mesh_flags.data();
+    sc.materials = h->materials.data();
+    sc.spheres = h->spheres.data();
+    sc.texels = h->texels.data();
+    sc.tex_info = h->tex_info.data();
+    use(sc);
     return YK_OK;
 }
 

@@ -1,5 +1,5 @@
 // yk_internal.h — library-private definitions shared by the host files of the library (yk_context.cpp,
-// yk_scene.cpp, yk_render.cpp, yk_stages.cpp: the single-device entry points; yk_multi.cpp: several devices of
+// yk_scene.cpp, yk_scene_change.cpp, yk_render.cpp, yk_stages.cpp: the single-device entry points; yk_multi.cpp: several devices of
 // one process, RCCL): the objects behind the opaque handles of include/yuki_hip.h.  Not installed.
 // Two private headers build on it: yk_staging.h (the staged arrays of a host-array entry point, the one user of
 // yk_context::scratch) and yk_film_call.h (what the film passes' argument checks share).
@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -226,15 +227,14 @@ struct yk_scene {
     DevBuf nodes, nodes4, top_nodes, top_nodes_any, tris, prim_shade, prim_attr, indices, points, normals, uvs, tri_mesh, tri_material, tri_area_light, mesh_flags, materials, lights, spheres, texels, tex_info;
     DevScene dev;
     bool on_device = false;
-    // What yk_scene_update needs after creation (yk_scene_update.h).  A host-only scene (no context) keeps its indices on the
-    // host; every other scene reads them from its device copy.
+    // What a change in place needs after creation (yk_scene_update.h, yk_scene_change.h).
     struct UpdateState {
         uint32_t n_vertices = 0;
         bool has_normals = false, has_uvs = false;
         LayoutOptions opt;  // the context's "top_nodes" / "wide_bvh" at creation: every layout of the scene, then and at an update, reads these
-        std::vector<float> sphere_bounds;     // six floats a sphere: Sphere::world_bound as at creation
+        std::vector<float> sphere_bounds;     // six floats a sphere: Sphere::world_bound as at creation or as the last edit left it
         std::vector<uint8_t> mat_kind;        // device BSDF kind (MK_*) per material
-        std::vector<uint32_t> host_indices;   // host-only scenes
+        std::vector<uint8_t> light_kind;      // yk_light_kind per light: an edit keeps it
         // the plan of the device route, built by the first update that takes it: the tree's nodes and order stay in
         // tree_nodes / tree_order; depth = every node's depth; list = the interior nodes grouped by depth (level_off[d] ..
         // level_off[d + 1] holds depth d + 1), then the leaves (from level_off[n_levels])
@@ -242,24 +242,19 @@ struct yk_scene {
         DevBuf depth, list, sphere_b, mat_kind_d, words;
         std::vector<uint32_t> level_off;
         yk_scene_update_info info = {};
+        yk_scene_edit_info edit_info = {};
     } upd;
-    // What the host instance of yk_surface_albedo reads (yk_albedo.h).  A host-only scene keeps these; for a scene in device
-    // memory they are copied back from its device with every call.
-    struct ShadingTables {
+    // A scene's arrays on the host: what a host-only scene keeps (`host`; points: the vertices the tree was last fitted to; materials
+    // and spheres follow an edit), and what scene_host_arrays() fills for a call on a scene in device memory.  Every reader goes there.
+    struct HostCopy {
         std::vector<uint32_t> indices, tri_mesh, mesh_flags;
-        std::vector<int32_t> tri_material;
-        std::vector<float> uvs;
+        std::vector<int32_t> tri_material, tri_area_light;  // (the last one and the normals: only ever fetched)
+        std::vector<float> points, normals, uvs;
         std::vector<Material> materials;
         std::vector<DevSphere> spheres;
         std::vector<float4> texels;
         std::vector<uint4> tex_info;
-    } host_shading;
-    // What yk_scene_apply_edit needs after creation.  It stands after every older member: their offsets stay what they were.
-    struct EditState {
-        std::vector<uint8_t> light_kind;  // yk_light_kind per light: an edit keeps it
-        std::vector<float> host_points;   // host-only scenes: the vertices the tree was last fitted to (a sphere edit folds every leaf again)
-        yk_scene_edit_info info = {};
-    } edit;
+    } host;
 };
 
 // The device scene a job of `n` rays traverses: with both node layouts present the 4-wide one
@@ -341,6 +336,17 @@ yk_status yk_upload_scene_image(yk_context* ctx, const std::shared_ptr<SceneImag
 // them there (thread-safe).  NULL when that copy fails.
 const HostBvh* scene_host_tree(const yk_scene* scene);
 
+// A scene's arrays on the host, as scene_host_tree() gives its tree: `mask` says which (HOST_*).  A host-only scene answers
+// with its kept copy (`who` prefixes its refusals), a scene in device memory with copies fetched and size-checked for the call.
+enum : uint32_t { HOST_INDICES = 1u, HOST_POINTS = 2u, HOST_NORMALS = 4u, HOST_UVS = 8u, HOST_TRI_MESH = 16u, HOST_TRI_MATERIAL = 32u, HOST_TRI_AREA_LIGHT = 64u,
+                  HOST_MESH_FLAGS = 128u, HOST_MATERIALS = 256u, HOST_SPHERES = 512u, HOST_TEXTURES = 1024u /* tex_info and texels */ };
+struct HostArrays {
+    const yk_scene::HostCopy* arrays = nullptr;  // the scene's, or `fetched`
+    yk_scene::HostCopy fetched;
+    const yk_scene::HostCopy* operator->() const { return arrays; }
+};
+yk_status scene_host_arrays(yk_context* ctx, const yk_scene* scene, uint32_t mask, const std::string& who, HostArrays& out);
+
 // The scene's shape -> BSDF kind table, filled from the device copy of tri_material on the first call when the scene was
 // made from device arrays (thread-safe).  NULL when that copy fails.
 const std::vector<uint8_t>* scene_shape_kind(const yk_scene* scene);
@@ -368,23 +374,19 @@ bool build_bvh_levels(const std::vector<ShapeBounds>& bounds, uint32_t max_shape
 // "top_nodes" and "wide_bvh" are s->upd.opt, the values captured at creation, as for the host layout.
 uint32_t layout_scene_device(yk_context* ctx, yk_scene* s, const DeviceTree& tree, const uint32_t* d_user_order, const uint8_t* d_mat_kind, bool has_attr, uint32_t tree_depth, bool* order_applied);
 
-// ------------------------------------------------------------------ yk_scene_update.hip
-// The device route of yk_scene_update[_device] (yk_scene_update.h): the finite test over d_points, then — nothing of the scene
-// is written before it has passed — the copies into the scene's arrays, leaf boxes, interior boxes level by level and the
-// layout.  Returns YK_LAYOUT_REASON_NONE, or the reason with the scene to be rewritten by the host route; *not_finite: the
-// test refused the points and the scene is untouched.  The caller holds the context's lock and has drained its streams.
-uint32_t update_scene_device(yk_context* ctx, yk_scene* s, const float* d_points, const float* d_normals, bool* not_finite);
-// The two halves of that route that an edit in place (yk_scene_apply_edit) runs too: the plan, built once and kept, and —
-// from the scene's own arrays as they stand — the boxes (`boxes` false: the tree stays as it is) and the layout's records.
-// Both return YK_LAYOUT_REASON_*; seconds_boxes / seconds_records receive the two phases' times.
+// ------------------------------------------------------------------ yk_scene_update.hip, yk_scene_edit.hip
+// The device route of a change in place, step by step (yk_scene_change.cpp runs them; the refit rule is yk_scene_update.h's): the
+// plan, built once and kept; stage, one kernel that tests the caller's array and raises *flag, nothing of the scene written; commit,
+// device-to-device copies into the scene's arrays; refit, from the scene's own arrays, the boxes (`boxes` false: the tree stays) and
+// the layout's records, with their times.  Every step returns YK_LAYOUT_REASON_*: NONE, or why the host route must rewrite the scene.
 uint32_t plan_scene_update(yk_context* ctx, yk_scene* s);
 uint32_t refit_scene_device(yk_context* ctx, yk_scene* s, bool boxes, double* seconds_boxes, double* seconds_records);
-
-// ------------------------------------------------------------------ yk_scene_edit.hip
-// The sphere table of an edit in place on the device.  d_in: n_spheres yk_sphere_desc records in HBM (4-byte aligned).
-// stage: one kernel writes the DevSphere table, the six-float bounds and the material column into `staged` (scratch of the
-// caller) and raises *flag (YK_SPHERES_*) — nothing of the scene is written.  commit: the staged tables into the scene's
-// sphere table and the plan's bounds, and back to the host copies (bounds, material column).  Both return YK_LAYOUT_REASON_*.
+// points (yk_scene_update), after the plan, the context's device current: *flag non-zero says a coordinate is not finite
+uint32_t stage_points_device(yk_context* ctx, yk_scene* s, const float* d_points, uint32_t* flag);
+uint32_t commit_points_device(yk_context* ctx, yk_scene* s, const float* d_points, const float* d_normals);
+// spheres (yk_scene_apply_edit).  d_in: n_spheres yk_sphere_desc records in HBM (4-byte aligned).  stage writes the DevSphere
+// table, the six-float bounds and the material column into `staged` (scratch of the caller) and raises *flag (YK_SPHERES_*);
+// commit copies them into the scene's sphere table and the plan's bounds, and back to the host (bounds, material column).
 enum { YK_SPHERES_NOT_FINITE = 1u, YK_SPHERES_MATERIAL = 2u };
 struct StagedSpheres {
     DevSphere* table = nullptr;
@@ -438,6 +440,23 @@ void adopt_device_tree(yk_scene* s, DeviceTree& tree, const std::shared_ptr<Host
 Material make_material(const yk_material_desc& m);  // per-hit constants folded (GGX alpha, Oren-Nayar A / B)
 DevLight make_light(const yk_light_desc& l);
 DevSphere make_sphere(const yk_sphere_desc& sp);  // with Transform::swaps_handedness of object_to_world
+// host array -> device buffer.  Not put_host_array inside HIP_TRY: the context's message names the call that failed
+// ("buf.ensure(bytes): ..." or "hipMemcpy(...): ..."), and those texts stay.
+template <class T> static yk_status upload(yk_context* ctx, DevBuf& buf, const T* src, size_t count) {
+    size_t bytes = std::max<size_t>(count * sizeof(T), 16);
+    HIP_TRY(ctx, buf.ensure(bytes));
+    if (count) HIP_TRY(ctx, hipMemcpy(buf.p, src, count * sizeof(T), hipMemcpyHostToDevice));
+    return YK_OK;
+}
+// The seven record vectors of a host layout into the scene's record buffers, and the sizes and layout head that go with them.
+yk_status upload_records(yk_context* ctx, yk_scene* s, const SceneRecords& r);
+// What the kernels are handed of the records and the root box (which reaches DevScene here only): at creation, and after a change.
+void bind_records(yk_scene* s);
+// every non-NULL array is device memory of ctx's device, and its allocation reaches as far as its count says
+struct DeviceArray { const char* name; const void* p; size_t bytes; };
+yk_status check_device_arrays(yk_context* ctx, std::initializer_list<DeviceArray> arrays);
+// The context's stream waits for what the caller's stream (a hipStream_t, may be NULL) holds now: its arrays are complete there.
+yk_status wait_for_caller_stream(yk_context* ctx, void* stream);
 
 // ------------------------------------------------------------------ yk_render.cpp (used by yk_stages.cpp too)
 // ctx->counters: 8 x u64 (closest-hit rays, shadow rays, ...) followed by a 4-word error block whose word

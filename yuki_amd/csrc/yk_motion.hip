@@ -122,27 +122,9 @@ yk_status surface_motion(yk_context* ctx, const yk_scene* scene, const yk_surfac
     if (scene->n_spheres == 0u) prev_spheres = nullptr;  // nothing to read of it
     const size_t n_px = (size_t)res_x * res_y;
     if (!ctx) {  // the host instance
-        const size_t n_idx = 3 * (size_t)scene->n_triangles;
-        std::vector<uint32_t> fetched;
-        const uint32_t* indices = scene->upd.host_indices.data();
-        if (n_idx && scene->upd.host_indices.size() != n_idx) {  // a scene in device memory: its indices live there
-            if (!scene->on_device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, std::string(name) + ": the scene has no vertex indices");
-            fetched.resize(n_idx);
-            (void)hipSetDevice(scene->device);
-            HIP_TRY(ctx, hipMemcpy(fetched.data(), scene->indices.p, n_idx * 4, hipMemcpyDeviceToHost));
-            indices = fetched.data();
-        }
-        std::vector<DevSphere> fetched_spheres;
-        const DevSphere* current = scene->host_shading.spheres.data();
-        if (prev_spheres && scene->on_device) {  // ... and so does its sphere table
-            fetched_spheres.resize(scene->n_spheres);
-            (void)hipSetDevice(scene->device);
-            HIP_TRY(ctx, hipMemcpy(fetched_spheres.data(), scene->spheres.p, fetched_spheres.size() * sizeof(DevSphere), hipMemcpyDeviceToHost));
-            current = fetched_spheres.data();
-        } else if (prev_spheres && scene->host_shading.spheres.size() < scene->n_spheres) {
-            return fail(ctx, YK_ERR_INVALID_ARGUMENT, std::string(name) + ": the scene has no sphere table");
-        }
-        motion_host(scene, indices, ids, guides, prev_points, current, prev_spheres, res_x, res_y, out);
+        HostArrays h;  // a scene in device memory: its indices and its sphere table live there
+        if (yk_status rs = scene_host_arrays(ctx, scene, HOST_INDICES | (prev_spheres ? HOST_SPHERES : 0u), std::string(name) + ": ", h)) return rs;
+        motion_host(scene, h->indices.data(), ids, guides, prev_points, h->spheres.data(), prev_spheres, res_x, res_y, out);
         return YK_OK;
     }
     YK_LOCK(ctx);

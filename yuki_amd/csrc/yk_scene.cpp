@@ -1,9 +1,10 @@
-// yk_scene.cpp — a scene's creation and update, one pipeline (the record layouts are in yk_device.h):
+// yk_scene.cpp — a scene's creation, one pipeline (the record layouts are in yk_device.h):
 //   inputs   a tree (the reference's BVH, bvh.rs:39-115 via yk_host.cpp, or the device builder's), the geometry, the small
 //            tables and the LayoutOptions captured at creation — from a description, from arrays in HBM, or from the scene
 //   layout   layout_records_host (yk_scene_records.cpp) + upload_records, or layout_scene_device (yk_scene_layout.hip)
-//   bind     bind_records, at creation (inside bind_device_scene) and after an update
+//   bind     bind_records, at creation (inside bind_device_scene) and after a change in place
 // Which builder and which layout is an argument (SceneBuild); nothing here writes a context option.
+// Also here: the getters, scene_host_tree and scene_host_arrays.  yk_scene_change.cpp changes a live scene through the same calls.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -18,16 +19,6 @@
 
 #include "yk_internal.h"
 #include "yk_scene_layout.h"
-#include "yk_scene_update.h"
-
-// host array -> device buffer.  Not put_host_array inside HIP_TRY: the context's message names the call that failed
-// ("buf.ensure(bytes): ..." or "hipMemcpy(...): ..."), and those texts stay.
-template <class T> static yk_status upload(yk_context* ctx, DevBuf& buf, const T* src, size_t count) {
-    size_t bytes = std::max<size_t>(count * sizeof(T), 16);
-    HIP_TRY(ctx, buf.ensure(bytes));
-    if (count) HIP_TRY(ctx, hipMemcpy(buf.p, src, count * sizeof(T), hipMemcpyHostToDevice));
-    return YK_OK;
-}
 
 // a scene under construction: destroyed (yk_scene_destroy) on every early return and on an exception, released into *out at the end
 typedef std::unique_ptr<yk_scene, void (*)(yk_scene*)> ScenePtr;
@@ -41,8 +32,8 @@ static void set_scene_counts(yk_scene* s, const yk_scene_desc* d) {
     s->n_meshes = d->n_meshes;
     s->n_textures = d->n_textures;
     for (uint32_t l = 0; l < d->n_lights; ++l) s->n_delta_lights += d->lights[l].kind != YK_LIGHT_RECT ? 1u : 0u;
-    s->edit.light_kind.resize(d->n_lights);  // an edit in place keeps every light's kind
-    for (uint32_t l = 0; l < d->n_lights; ++l) s->edit.light_kind[l] = (uint8_t)d->lights[l].kind;
+    s->upd.light_kind.resize(d->n_lights);  // an edit in place keeps every light's kind
+    for (uint32_t l = 0; l < d->n_lights; ++l) s->upd.light_kind[l] = (uint8_t)d->lights[l].kind;
 }
 
 Material make_material(const yk_material_desc& m) {
@@ -408,6 +399,43 @@ const HostBvh* scene_host_tree(const yk_scene* s) {
     return s->tree_fetched.load() ? s->bvh.get() : nullptr;
 }
 
+yk_status scene_host_arrays(yk_context* ctx, const yk_scene* s, uint32_t mask, const std::string& who, HostArrays& out) {
+    const size_t nt = s->n_triangles, nv = s->upd.n_vertices;
+    if (!s->on_device) {
+        const yk_scene::HostCopy& h = s->host;
+        if ((mask & HOST_INDICES) && h.indices.size() != 3 * nt) return fail(ctx, YK_ERR_INVALID_ARGUMENT, who + "the scene has no vertex indices");
+        if ((mask & HOST_POINTS) && nt && h.points.size() != 3 * nv) return fail(ctx, YK_ERR_INVALID_ARGUMENT, who + "the scene has no vertices on the host");
+        if ((mask & HOST_SPHERES) && h.spheres.size() < s->n_spheres) return fail(ctx, YK_ERR_INVALID_ARGUMENT, who + "the scene has no sphere table");
+        out.arrays = &h;
+        return YK_OK;
+    }
+    (void)hipSetDevice(s->device);
+    yk_scene::HostCopy& h = out.fetched;
+    out.arrays = &h;
+    const auto get = [mask](uint32_t bit, auto& v, size_t count, const DevBuf& b) -> hipError_t {
+        const size_t bytes = count * sizeof(v[0]);
+        if (!(mask & bit) || bytes == 0) return hipSuccess;
+        if (!b.p || b.bytes < bytes) return hipErrorInvalidValue;
+        v.resize(count);
+        return hipMemcpy(v.data(), b.p, bytes, hipMemcpyDeviceToHost);
+    };
+    HIP_TRY(ctx, get(HOST_INDICES, h.indices, 3 * nt, s->indices));
+    HIP_TRY(ctx, get(HOST_POINTS, h.points, 3 * nv, s->points));
+    HIP_TRY(ctx, get(HOST_NORMALS, h.normals, s->upd.has_normals ? 3 * nv : 0, s->normals));
+    HIP_TRY(ctx, get(HOST_UVS, h.uvs, s->upd.has_uvs ? 2 * nv : 0, s->uvs));
+    HIP_TRY(ctx, get(HOST_TRI_MESH, h.tri_mesh, nt, s->tri_mesh));
+    HIP_TRY(ctx, get(HOST_TRI_MATERIAL, h.tri_material, nt, s->tri_material));
+    HIP_TRY(ctx, get(HOST_TRI_AREA_LIGHT, h.tri_area_light, nt, s->tri_area_light));
+    HIP_TRY(ctx, get(HOST_MESH_FLAGS, h.mesh_flags, std::max<uint32_t>(s->n_meshes, 1), s->mesh_flags));
+    HIP_TRY(ctx, get(HOST_MATERIALS, h.materials, std::max<uint32_t>(s->n_materials, 1), s->materials));
+    HIP_TRY(ctx, get(HOST_SPHERES, h.spheres, std::max<uint32_t>(s->n_spheres, 1), s->spheres));
+    HIP_TRY(ctx, get(HOST_TEXTURES, h.tex_info, s->n_textures, s->tex_info));
+    size_t n_texels = 0;
+    for (const uint4& t : h.tex_info) n_texels = std::max(n_texels, (size_t)t.x + (size_t)t.y * t.z);
+    HIP_TRY(ctx, get(HOST_TEXTURES, h.texels, n_texels, s->texels));
+    return YK_OK;
+}
+
 hipError_t upload_host_tree(const HostBvh& bvh, DeviceTree& tree) {
     const std::vector<uint32_t> depth = lay::node_depths(reinterpret_cast<const uint32_t*>(bvh.nodes.data()), bvh.nodes.size());  // children follow their parent in the array
     tree.n_nodes = (uint32_t)bvh.nodes.size();
@@ -454,8 +482,7 @@ static uint32_t layout_on_device(yk_context* ctx, SceneImage* img, yk_scene* s) 
     return YK_LAYOUT_REASON_NONE;
 }
 
-// The seven record vectors of a host layout into the scene's record buffers, and the sizes and layout head that go with them.
-static yk_status upload_records(yk_context* ctx, yk_scene* s, const SceneRecords& r) {
+yk_status upload_records(yk_context* ctx, yk_scene* s, const SceneRecords& r) {
     yk_status st;
     if ((st = upload(ctx, s->nodes, r.nodes.data(), r.nodes.size())) != YK_OK || (st = upload(ctx, s->nodes4, r.nodes4.data(), r.nodes4.size())) != YK_OK ||
         (st = upload(ctx, s->top_nodes, r.top.data(), r.top.size())) != YK_OK || (st = upload(ctx, s->top_nodes_any, r.top_any.data(), r.top_any.size())) != YK_OK ||
@@ -467,9 +494,7 @@ static yk_status upload_records(yk_context* ctx, yk_scene* s, const SceneRecords
     return YK_OK;
 }
 
-// What the kernels are handed of the records and the root box, from the scene's record buffers, its layout info and its
-// bounds: at creation and again after either route of an update rewrote them.  The root box reaches DevScene here only.
-static void bind_records(yk_scene* s) {
+void bind_records(yk_scene* s) {
     const yk_scene_layout_info& li = s->layout;
     DevScene& ds = s->dev;
     ds.nodes = s->nodes.as<DevNode>();
@@ -513,8 +538,8 @@ static void bind_device_scene(yk_scene* s, const yk_scene_desc* d) {
     for (DevBuf* b : scene_buffers(s)) s->info.device_bytes += b->bytes;
 }
 
-// What an update needs of the description after creation (yk_scene::UpdateState).
-static void init_update_state(yk_scene* s, const yk_scene_desc* d, const LayoutOptions& opt, const std::vector<uint8_t>& mat_kind, bool host_only) {
+// What a change in place needs of the description after creation (yk_scene::UpdateState).
+static void init_update_state(yk_scene* s, const yk_scene_desc* d, const LayoutOptions& opt, const std::vector<uint8_t>& mat_kind) {
     yk_scene::UpdateState& u = s->upd;
     u.n_vertices = d->n_vertices;
     u.has_normals = d->normals != nullptr;
@@ -526,8 +551,6 @@ static void init_update_state(yk_scene* s, const yk_scene_desc* d, const LayoutO
         const ShapeBounds b = sphere_bound(d->spheres[k]);
         std::memcpy(&u.sphere_bounds[6 * (size_t)k], &b, sizeof(b));
     }
-    if (host_only && d->n_triangles) u.host_indices.assign(d->indices, d->indices + 3 * (size_t)d->n_triangles);
-    if (host_only && d->n_triangles) s->edit.host_points.assign(d->points, d->points + 3 * (size_t)d->n_vertices);
 }
 
 // Device half: one copy of the image in the HBM of ctx's device.
@@ -543,13 +566,13 @@ yk_status yk_upload_scene_image(yk_context* ctx, const std::shared_ptr<SceneImag
     s->info = img->info;
     s->build_info = img->build_info;
     s->shape_kind = img->shape_kind;
-    init_update_state(s, img->d, img->opt, img->mat_kind, ctx == nullptr);
-    if (!ctx) {  // a host-only scene keeps what the host instance of yk_surface_albedo reads (its indices: init_update_state)
+    init_update_state(s, img->d, img->opt, img->mat_kind);
+    if (!ctx) {  // a host-only scene keeps its arrays (yk_scene::HostCopy)
         const yk_scene_desc* d = img->d;
         SceneImage tables;
         yk_status st = small_tables(nullptr, d, &tables);
         if (st != YK_OK) return st;
-        yk_scene::ShadingTables& h = s->host_shading;
+        yk_scene::HostCopy& h = s->host;
         h.mesh_flags.swap(tables.mesh_flags);
         h.materials.swap(tables.mats);
         h.spheres.swap(tables.spheres);
@@ -559,6 +582,8 @@ yk_status yk_upload_scene_image(yk_context* ctx, const std::shared_ptr<SceneImag
         if (d->tri_mesh) std::memcpy(h.tri_mesh.data(), d->tri_mesh, sizeof(uint32_t) * d->n_triangles);
         if (d->n_triangles) h.tri_material.assign(d->tri_material, d->tri_material + d->n_triangles);
         if (d->uvs) h.uvs.assign(d->uvs, d->uvs + 2 * (size_t)d->n_vertices);
+        if (d->n_triangles) h.indices.assign(d->indices, d->indices + 3 * (size_t)d->n_triangles);
+        if (d->n_triangles) h.points.assign(d->points, d->points + 3 * (size_t)d->n_vertices);
     }
     if (ctx) {
         if (!img->has_device_records) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "scene image was built without device records");
@@ -630,13 +655,7 @@ const std::vector<uint8_t>* scene_shape_kind(const yk_scene* s) {
 // checks, the permutation test and the shape bounds run as kernels (yk_scene_input.hip), the builder starts from bounds
 // it finds in HBM and the layout reads the scene's own device-to-device copies.
 
-// every non-NULL large array is device memory of ctx's device, and its allocation reaches as far as its count says
-struct DeviceArray {
-    const char* name;
-    const void* p;
-    size_t bytes;
-};
-static yk_status check_device_arrays(yk_context* ctx, std::initializer_list<DeviceArray> arrays) {
+yk_status check_device_arrays(yk_context* ctx, std::initializer_list<DeviceArray> arrays) {
     for (const DeviceArray& a : arrays) {
         if (!a.p) continue;
         hipPointerAttribute_t at;
@@ -652,6 +671,13 @@ static yk_status check_device_arrays(yk_context* ctx, std::initializer_list<Devi
             return fail(ctx, YK_ERR_INVALID_ARGUMENT, std::string(a.name) + " is shorter than its count says");
         }
     }
+    return YK_OK;
+}
+
+yk_status wait_for_caller_stream(yk_context* ctx, void* stream) {
+    if (!stream) return YK_OK;
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_in, (hipStream_t)stream));
+    HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_in, 0));
     return YK_OK;
 }
 
@@ -689,7 +715,7 @@ static yk_status create_scene_on_device(yk_context* ctx, const yk_scene_desc* d,
     if (rc != YK_OK) return rc;
     std::vector<uint8_t> light_kind(std::max<uint32_t>(d->n_lights, 1), 0);
     std::vector<uint8_t>& mat_kind = img.mat_kind;
-    init_update_state(s, d, LayoutOptions{ctx->top_nodes, ctx->wide_bvh}, mat_kind, false);
+    init_update_state(s, d, LayoutOptions{ctx->top_nodes, ctx->wide_bvh}, mat_kind);
     for (uint32_t l = 0; l < d->n_lights; ++l) light_kind[l] = (uint8_t)d->lights[l].kind;
     std::vector<ShapeBounds> sphere_b(std::max<uint32_t>(d->n_spheres, 1));
     for (uint32_t k = 0; k < d->n_spheres; ++k) sphere_b[k] = sphere_bound(d->spheres[k]);
@@ -814,348 +840,6 @@ static yk_status create_scene_from_host_copy(yk_context* ctx, const yk_scene_des
     return YK_OK;
 }
 
-// ------------------------------------------------------------------ yk_scene_update
-// Update in place: the rule is yk_scene_update.h's, the device route yk_scene_update.hip's; here are the
-// host route and the entry points.
-
-static bool all_finite(const float* p, size_t n) {
-    for (size_t i = 0; i < n; ++i) {
-        uint32_t u;
-        std::memcpy(&u, p + i, 4);
-        if (upd::not_finite_bits(u)) return false;
-    }
-    return true;
-}
-
-// The host route of an update and of an edit: yk_bvh_refit on a copy of the host tree (`refit` false: the tree stays),
-// layout_records_host, an upload of the arrays, upload_records.  `points` (and `normals`, may be NULL) are host arrays that
-// have passed the finite test; points NULL (an edit): the scene's own, which are fetched and not uploaded again.
-// ctx NULL: a host-only scene.  The two phases' times go to *seconds_boxes and *seconds_records.
-static yk_status rewrite_scene_host(yk_context* ctx, yk_scene* s, const float* points, const float* normals, bool refit, double* seconds_boxes, double* seconds_records) {
-    yk_scene::UpdateState& u = s->upd;
-    const size_t nt = s->n_triangles, ns = s->n_spheres, nv = u.n_vertices;
-    const HostBvh* old = scene_host_tree(s);
-    if (!old) return fail(ctx, YK_ERR_DEVICE, "the scene's tree could not be copied back from the device");
-    double t0 = now_seconds();
-    if (ctx) (void)hipSetDevice(ctx->device);
-    auto fetch = [&](auto& v, const DevBuf& src) -> hipError_t { return v.empty() ? hipSuccess : hipMemcpy(v.data(), src.p, v.size() * sizeof(v[0]), hipMemcpyDeviceToHost); };
-    std::vector<uint32_t> fetched_indices(ctx ? 3 * nt : 0);
-    if (ctx) HIP_TRY(ctx, fetch(fetched_indices, s->indices));
-    const uint32_t* indices = ctx ? fetched_indices.data() : u.host_indices.data();
-    const bool own_points = points == nullptr;
-    std::vector<float> fetched_points(own_points && ctx ? 3 * nv : 0);
-    if (own_points) {
-        if (ctx) HIP_TRY(ctx, fetch(fetched_points, s->points));
-        points = ctx ? fetched_points.data() : s->edit.host_points.data();
-        if (!ctx && nt && s->edit.host_points.size() != 3 * nv) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "the scene has no vertices on the host");
-    }
-    std::vector<float> sb(6 * (nt + ns));  // per source shape
-    for (size_t i = 0; i < nt; ++i) {
-        float b[6];
-        (void)inp::tri_bound(points, indices, (uint32_t)i, b);
-        std::memcpy(&sb[6 * i], b, sizeof(b));
-    }
-    std::copy(u.sphere_bounds.begin(), u.sphere_bounds.end(), sb.begin() + 6 * nt);
-    std::shared_ptr<HostBvh> tree = std::make_shared<HostBvh>(*old);  // never through a tree that may be shared
-    yk_status rc = refit ? yk_bvh_refit(tree->nodes.data(), tree->nodes.size(), tree->shape_order.data(), nt + ns, sb.data()) : YK_OK;
-    if (rc != YK_OK) return fail(ctx, rc, "the scene's tree does not fit its shapes");
-    *seconds_boxes = refit ? now_seconds() - t0 : 0.0;
-    t0 = now_seconds();
-    if (ctx) {
-        // the host layout's input: the new points and normals, everything else fetched from the scene
-        std::vector<float> old_normals(u.has_normals && !normals ? 3 * nv : 0), uvs(u.has_uvs ? 2 * nv : 0);
-        std::vector<uint32_t> tri_mesh(nt), mesh_flags(s->mesh_flags.bytes / 4);
-        std::vector<int32_t> tri_material(nt), tri_al(nt), sphere_material(ns);
-        std::vector<DevSphere> dev_spheres(ns);
-        HIP_TRY(ctx, fetch(old_normals, s->normals));
-        HIP_TRY(ctx, fetch(uvs, s->uvs));
-        HIP_TRY(ctx, fetch(tri_mesh, s->tri_mesh));
-        HIP_TRY(ctx, fetch(mesh_flags, s->mesh_flags));
-        HIP_TRY(ctx, fetch(tri_material, s->tri_material));
-        HIP_TRY(ctx, fetch(tri_al, s->tri_area_light));
-        HIP_TRY(ctx, fetch(dev_spheres, s->spheres));
-        for (size_t k = 0; k < ns; ++k) sphere_material[k] = dev_spheres[k].material;
-        HostLayoutInput in;
-        in.bvh = tree.get();
-        in.n_interior = s->info.n_interior;
-        in.indices = indices;
-        in.points = points;
-        in.normals = normals ? normals : (u.has_normals ? old_normals.data() : nullptr);
-        in.uvs = u.has_uvs ? uvs.data() : nullptr;
-        in.tri_material = tri_material.data();
-        in.tri_area_light = tri_al.data();
-        in.tri_mesh = tri_mesh.data();
-        in.mesh_flags = mesh_flags.data();
-        in.n_triangles = (uint32_t)nt;
-        in.sphere_material = sphere_material.data();
-        in.mat_kind = u.mat_kind.data();
-        in.opt = u.opt;  // the records as creation laid them out, whatever the context's options say today
-        if ((!own_points && (rc = upload(ctx, s->points, points, 3 * nv)) != YK_OK) || (normals && (rc = upload(ctx, s->normals, normals, 3 * nv)) != YK_OK) ||
-            (rc = upload_records(ctx, s, layout_records_host(in))) != YK_OK)
-            return rc;
-        if (s->tree_nodes.p && refit)  // the tree a later device-route update starts from
-            HIP_TRY(ctx, hipMemcpy(s->tree_nodes.p, tree->nodes.data(), tree->nodes.size() * sizeof(yk_bvh_node), hipMemcpyHostToDevice));
-    }
-    for (int k = 0; k < 3; ++k) {
-        s->info.bounds_min[k] = tree->nodes[0].bmin[k];
-        s->info.bounds_max[k] = tree->nodes[0].bmax[k];
-    }
-    {
-        std::lock_guard<std::mutex> lock(s->tree_mu);
-        s->bvh = tree;
-        s->bvh_lazy.reset();
-        s->tree_fetched.store(1u);
-    }
-    if (ctx) bind_records(s);
-    if (!ctx && !own_points) s->edit.host_points.assign(points, points + 3 * nv);  // what a later sphere edit folds the leaves from
-    *seconds_records = now_seconds() - t0;
-    return YK_OK;
-}
-
-// `reason`: why the device route was not taken or did not finish (YK_LAYOUT_REASON_*), for the update info.
-static yk_status update_scene_host(yk_context* ctx, yk_scene* s, const float* points, const float* normals, uint32_t reason) {
-    yk_scene::UpdateState& u = s->upd;
-    u.info.route = YK_UPDATE_ROUTE_HOST;
-    u.info.reason = reason;
-    return rewrite_scene_host(ctx, s, points, normals, true, &u.info.seconds_boxes, &u.info.seconds_records);
-}
-
-// everything the context has enqueued: renders of the scene that were enqueued before the update finish on the old geometry
-static yk_status drain_context(yk_context* ctx) {
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    for (WorkSet& w : ctx->ws) {
-        if (w.stream && w.stream != ctx->stream) HIP_TRY(ctx, hipStreamSynchronize(w.stream));
-        if (w.side) HIP_TRY(ctx, hipStreamSynchronize(w.side));
-    }
-    return YK_OK;
-}
-
-// after a device-route refit the host copy of the tree is stale: the next reader fetches the refitted one
-static void forget_host_tree(yk_scene* s) {
-    std::lock_guard<std::mutex> lock(s->tree_mu);
-    std::shared_ptr<HostBvh> fresh = std::make_shared<HostBvh>();
-    fresh->max_leaf_shapes = s->bvh->max_leaf_shapes;
-    fresh->depth = s->bvh->depth;
-    fresh->split_failed = s->bvh->split_failed;
-    s->bvh = s->bvh_lazy = fresh;
-    s->tree_fetched.store(0u);
-}
-
-// The device route on device arrays; where it fails, the arrays go to the host once (h_points / h_normals when the caller
-// has them there already) and the host route rewrites the scene.
-static yk_status update_scene(yk_context* ctx, yk_scene* s, const float* d_points, const float* d_normals, const float* h_points, const float* h_normals) {
-    yk_scene::UpdateState& u = s->upd;
-    bool not_finite = false;
-    const uint32_t reason = update_scene_device(ctx, s, d_points, d_normals, &not_finite);
-    if (not_finite) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "points: coordinate not finite");
-    if (reason == YK_LAYOUT_REASON_NONE) {
-        forget_host_tree(s);
-        bind_records(s);
-        u.info.route = YK_UPDATE_ROUTE_DEVICE;
-        u.info.reason = YK_LAYOUT_REASON_NONE;
-        return YK_OK;
-    }
-    (void)hipGetLastError();
-    const size_t n = 3 * (size_t)u.n_vertices;
-    std::vector<float> points(h_points ? 0 : n), normals(d_normals && !h_normals ? n : 0);
-    if (!h_points) HIP_TRY(ctx, hipMemcpy(points.data(), d_points, n * 4, hipMemcpyDeviceToHost));
-    if (d_normals && !h_normals) HIP_TRY(ctx, hipMemcpy(normals.data(), d_normals, n * 4, hipMemcpyDeviceToHost));
-    if (!h_points) h_points = points.data();
-    if (d_normals && !h_normals) h_normals = normals.data();
-    if (!all_finite(h_points, n)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "points: coordinate not finite");
-    return update_scene_host(ctx, s, h_points, h_normals, reason);
-}
-
-// the arguments both entry points refuse alike
-static yk_status check_update(yk_context* ctx, const yk_scene* s, const float* points, const float* normals) {
-    if (!s) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null scene");
-    if (!points) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null points");
-    if (normals && !s->upd.has_normals) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "normals given for a scene created without normals");
-    if (ctx ? (!s->on_device || s->device != ctx->device) : s->on_device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "scene was not created on this context's device");
-    return YK_OK;
-}
-
-static void finish_update(yk_scene* s, double t_begin) {
-    s->upd.info.n_updates += 1;
-    s->upd.info.seconds_total = now_seconds() - t_begin;
-}
-
-// ------------------------------------------------------------------ yk_scene_apply_edit
-// Edit in place: spheres, lights, materials and the background change, the triangles stay.  The checks run
-// before anything of the scene is written; what is rewritten follows from what changed (include/yuki_hip.h has the table).
-
-// the host tables of an edit, checked against the scene: yk_scene_create's checks with its messages, and the two of an edit
-static yk_status check_edit_tables(yk_context* ctx, const yk_scene* s, const yk_scene_edit* e) {
-    if (e->lights)
-        for (uint32_t l = 0; l < s->n_lights; ++l)
-            if ((uint8_t)e->lights[l].kind != s->edit.light_kind[l] || e->lights[l].kind > 255u) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "lights: a light's kind cannot change");
-    if (e->spheres) {
-        for (uint32_t k = 0; k < s->n_spheres; ++k)
-            if (e->spheres[k].material < 0 || (uint32_t)e->spheres[k].material >= s->n_materials) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "sphere material out of range");
-        for (uint32_t k = 0; k < s->n_spheres; ++k)
-            if (!all_finite(reinterpret_cast<const float*>(&e->spheres[k]), 33)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "spheres: matrix entry or radius not finite");  // two matrices and the radius
-    }
-    if (e->materials)
-        for (uint32_t m = 0; m < s->n_materials; ++m)
-            if ((e->materials[m].flags & YK_MAT_FLAG_TEXTURED_A) && e->materials[m].kind == YK_MAT_MATTE && e->materials[m].a_texture >= s->n_textures)
-                return fail(ctx, YK_ERR_INVALID_ARGUMENT, "material texture index out of range");
-    return YK_OK;
-}
-
-// Every table the scene keeps of its shapes' BSDF kinds, from u.mat_kind (just rewritten) and the spheres' materials: the
-// plan's device copy, the lazy pair of a scene made from device arrays, and the shape table where it exists already.
-static yk_status refresh_kind_tables(yk_context* ctx, yk_scene* s, const std::vector<int32_t>& sphere_material) {
-    yk_scene::UpdateState& u = s->upd;
-    if (ctx && u.mat_kind_d.p) HIP_TRY(ctx, put_host_array(u.mat_kind_d, u.mat_kind.data(), u.mat_kind.size()));
-    if (s->shape_kind_lazy) {
-        s->lazy_mat_kind = u.mat_kind;
-        for (uint32_t k = 0; k < s->n_spheres; ++k) s->lazy_sphere_kind[k] = u.mat_kind[(uint32_t)sphere_material[k]];
-    }
-    const bool filled = s->shape_kind_lazy ? s->kind_fetched.load() != 0u : !s->shape_kind.empty();
-    if (!filled) return YK_OK;  // a lazy table is filled from the pair above when something asks; a host-only scene has none
-    std::vector<int32_t> mat(s->n_triangles);
-    if (ctx && s->n_triangles) HIP_TRY(ctx, hipMemcpy(mat.data(), s->tri_material.p, mat.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
-    if (!ctx) mat = s->host_shading.tri_material;
-    if (mat.size() != s->n_triangles || s->shape_kind.size() != (size_t)s->n_triangles + s->n_spheres) return fail(ctx, YK_ERR_DEVICE, "the scene's shape kinds do not fit its shapes");
-    for (uint32_t i = 0; i < s->n_triangles; ++i) s->shape_kind[i] = u.mat_kind[(uint32_t)mat[i]];
-    for (uint32_t k = 0; k < s->n_spheres; ++k) s->shape_kind[(size_t)s->n_triangles + k] = u.mat_kind[(uint32_t)sphere_material[k]];
-    return YK_OK;
-}
-
-// The edit itself, after the arguments have passed.  d_spheres: the sphere table in HBM (the _device entry), or NULL.
-static yk_status apply_edit(yk_context* ctx, yk_scene* s, const yk_scene_edit* e, const void* d_spheres, double t_begin) {
-    yk_scene::UpdateState& u = s->upd;
-    yk_scene_edit_info info = s->edit.info;
-    info.reason = YK_LAYOUT_REASON_NONE;
-    info.rewrote = 0;
-    info.seconds_tables = info.seconds_boxes = info.seconds_records = 0.0;
-    const size_t ns = s->n_spheres;
-    const bool spheres = (e->spheres || d_spheres) && ns != 0;
-    const bool device_laid = ctx && s->layout.layout == YK_LAYOUT_DEVICE;
-    bool device_route = ctx && (device_laid || (d_spheres && spheres));
-    if (ctx) (void)hipSetDevice(ctx->device);
-
-    // ---- all or nothing: the host tables, then — device route — the sphere table's flag word
-    yk_status rc = check_edit_tables(ctx, s, e);
-    if (rc != YK_OK) return rc;
-    std::vector<Material> mats;
-    std::vector<uint8_t> mat_kind;
-    if (e->materials && s->n_materials) {
-        mats.resize(s->n_materials);
-        mat_kind.assign(s->n_materials, 0u);  // a host-only scene has kept none so far
-        for (uint32_t m = 0; m < s->n_materials; ++m) {
-            mats[m] = make_material(e->materials[m]);
-            mat_kind[m] = (uint8_t)(mats[m].kind & 7u);
-        }
-    }
-    const bool kinds_changed = !mats.empty() && mat_kind != u.mat_kind;
-    const bool records = ctx && (spheres || kinds_changed);
-    DevScratch tmp;
-    StagedSpheres staged;
-    std::vector<yk_sphere_desc> fetched_spheres;  // a device table that takes the host route after all
-    const yk_sphere_desc* h_spheres = e->spheres;
-    if (device_route && (records || spheres)) {  // the plan: the tree, its levels and the two small tables in HBM
-        info.reason = plan_scene_update(ctx, s);
-        device_route = info.reason == YK_LAYOUT_REASON_NONE;
-    }
-    if (device_route && spheres) {
-        const void* d_in = d_spheres;
-        yk_sphere_desc* d_up = nullptr;
-        uint32_t flag = 0;
-        if (!d_in) {  // a host table on a device-laid scene goes up, as the points of yk_scene_update do
-            if (tmp.get(d_up, ns) && hipMemcpy(d_up, e->spheres, ns * sizeof(yk_sphere_desc), hipMemcpyHostToDevice) == hipSuccess)
-                d_in = d_up;
-            else
-                info.reason = layout_reason_of(tmp.err != hipSuccess ? tmp.err : hipErrorUnknown);
-        }
-        if (d_in) info.reason = stage_spheres_device(ctx, s, d_in, tmp, &staged, &flag);
-        device_route = info.reason == YK_LAYOUT_REASON_NONE;
-        if (device_route && (flag & YK_SPHERES_MATERIAL)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "sphere material out of range");
-        if (device_route && (flag & YK_SPHERES_NOT_FINITE)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "spheres: matrix entry or radius not finite");
-    }
-    if (!device_route && spheres && !h_spheres) {  // the device table to the host once, and the host's checks
-        fetched_spheres.resize(ns);
-        HIP_TRY(ctx, hipMemcpy(fetched_spheres.data(), d_spheres, ns * sizeof(yk_sphere_desc), hipMemcpyDeviceToHost));
-        h_spheres = fetched_spheres.data();
-        yk_scene_edit only_spheres = {h_spheres, nullptr, nullptr, nullptr};
-        if ((rc = check_edit_tables(ctx, s, &only_spheres)) != YK_OK) return rc;
-    }
-    info.seconds_check = now_seconds() - t_begin;
-
-    // ---- the small tables
-    double t0 = now_seconds();
-    if (e->lights && s->n_lights) {
-        std::vector<DevLight> lights(s->n_lights);
-        for (uint32_t l = 0; l < s->n_lights; ++l) lights[l] = make_light(e->lights[l]);
-        if (ctx && (rc = upload(ctx, s->lights, lights.data(), lights.size())) != YK_OK) return rc;
-        info.rewrote |= YK_EDIT_LIGHTS;
-    }
-    if (!mats.empty()) {
-        if (ctx && (rc = upload(ctx, s->materials, mats.data(), mats.size())) != YK_OK) return rc;
-        if (!ctx) s->host_shading.materials = mats;
-        u.mat_kind = mat_kind;
-        info.rewrote |= YK_EDIT_MATERIALS;
-    }
-    std::vector<int32_t> sphere_material(ns);
-    if (spheres && device_route) {
-        info.reason = commit_spheres_device(ctx, s, staged, &sphere_material);
-        if (info.reason != YK_LAYOUT_REASON_NONE) return fail(ctx, YK_ERR_DEVICE, "the staged sphere table could not be copied into the scene");
-    } else if (spheres) {
-        std::vector<DevSphere> table(ns);
-        for (size_t k = 0; k < ns; ++k) {
-            table[k] = make_sphere(h_spheres[k]);
-            sphere_material[k] = h_spheres[k].material;
-            const ShapeBounds b = sphere_bound(h_spheres[k]);
-            std::memcpy(&u.sphere_bounds[6 * k], &b, sizeof(b));
-        }
-        if (ctx && (rc = upload(ctx, s->spheres, table.data(), table.size())) != YK_OK) return rc;
-        if (ctx && u.sphere_b.p) HIP_TRY(ctx, put_host_array(u.sphere_b, u.sphere_bounds.data(), u.sphere_bounds.size() * 4));
-        if (!ctx) s->host_shading.spheres = table;
-    } else if (kinds_changed && ns) {  // the spheres' materials as the scene has them
-        std::vector<DevSphere> table(ctx ? ns : 0);
-        if (ctx) HIP_TRY(ctx, hipMemcpy(table.data(), s->spheres.p, ns * sizeof(DevSphere), hipMemcpyDeviceToHost));
-        const std::vector<DevSphere>& have = ctx ? table : s->host_shading.spheres;
-        for (size_t k = 0; k < ns && k < have.size(); ++k) sphere_material[k] = have[k].material;
-    }
-    if (spheres) info.rewrote |= YK_EDIT_SPHERES;
-    if ((spheres || kinds_changed) && (rc = refresh_kind_tables(ctx, s, sphere_material)) != YK_OK) return rc;
-    if (e->background) {
-        for (int k = 0; k < 3; ++k) s->dev.background[k] = e->background[k];
-        info.rewrote |= YK_EDIT_BACKGROUND;
-    }
-    info.seconds_tables = now_seconds() - t0;
-
-    // ---- boxes and records
-    if (device_route && records) {
-        info.reason = refit_scene_device(ctx, s, spheres, &info.seconds_boxes, &info.seconds_records);
-        if (info.reason == YK_LAYOUT_REASON_NONE) {
-            if (spheres) forget_host_tree(s);
-            bind_records(s);
-        } else {
-            (void)hipGetLastError();
-            device_route = false;
-        }
-    }
-    if (!device_route && (records || (spheres && !ctx)) && (rc = rewrite_scene_host(ctx, s, nullptr, nullptr, spheres, &info.seconds_boxes, &info.seconds_records)) != YK_OK) return rc;
-    if (spheres) info.rewrote |= YK_EDIT_BOXES;
-    if (records) info.rewrote |= YK_EDIT_RECORDS;
-    info.route = device_route ? YK_UPDATE_ROUTE_DEVICE : YK_UPDATE_ROUTE_HOST;
-    if (!device_laid && !d_spheres) info.reason = YK_LAYOUT_REASON_NONE;  // the host route was the one asked for
-    info.n_edits += 1;
-    info.seconds_total = now_seconds() - t_begin;
-    s->edit.info = info;
-    return YK_OK;
-}
-
-// the arguments both entry points refuse alike
-static yk_status check_edit(yk_context* ctx, const yk_scene* s, const yk_scene_edit* e, const void* d_spheres) {
-    if (!s) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null scene");
-    if (!e) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null edit");
-    if (e->spheres && d_spheres) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "spheres given as a host table and as a device table");
-    if (ctx ? (!s->on_device || s->device != ctx->device) : s->on_device) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "scene was not created on this context's device");
-    return YK_OK;
-}
-
 extern "C" {
 
 yk_status yk_scene_create(yk_context* ctx, const yk_scene_desc* d, yk_scene** out) {
@@ -1185,10 +869,7 @@ yk_status yk_scene_create_device(yk_context* ctx, const yk_scene_desc* d, void* 
                                    {"tri_area_light", d->tri_area_light, 4 * nt}, {"shape_order", d->shape_order, 4 * ns}});
     if (rc != YK_OK) return rc;
     hipStream_t st = ctx->stream;
-    if (stream) {  // the caller's arrays are complete where its stream stands now
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_in, (hipStream_t)stream));
-        HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_in, 0));
-    }
+    if ((rc = wait_for_caller_stream(ctx, stream)) != YK_OK) return rc;
     bool fall_back = false;
     yk_bvh_build_info refused;
     rc = create_scene_on_device(ctx, d, st, out, &fall_back, &refused);
@@ -1199,97 +880,15 @@ yk_status yk_scene_create_device(yk_context* ctx, const yk_scene_desc* d, void* 
     return create_scene_from_host_copy(ctx, d, st, refused, out);
 } YK_CATCH(ctx)
 
-yk_status yk_scene_update(yk_context* ctx, yk_scene* s, const float* points, const float* normals) try {
-    std::unique_lock<std::recursive_mutex> yk_lock_;
-    if (ctx) yk_lock_ = std::unique_lock<std::recursive_mutex>(ctx->mu);
-    const double t_begin = now_seconds();
-    yk_status rc = check_update(ctx, s, points, normals);
-    if (rc != YK_OK) return rc;
-    yk_scene::UpdateState& u = s->upd;
-    const size_t n = 3 * (size_t)u.n_vertices;
-    if (!all_finite(points, n)) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "points: coordinate not finite");
-    u.info.seconds_check = now_seconds() - t_begin;
-    if (ctx) {
-        (void)hipSetDevice(ctx->device);
-        if ((rc = drain_context(ctx)) != YK_OK) return rc;
-    }
-    if (ctx && s->layout.layout == YK_LAYOUT_DEVICE) {  // the arrays go up and the device route runs
-        DevScratch tmp;
-        float *d_points = nullptr, *d_normals = nullptr;
-        if (tmp.get(d_points, n) && (!normals || tmp.get(d_normals, n)) && hipMemcpy(d_points, points, n * 4, hipMemcpyHostToDevice) == hipSuccess &&
-            (!normals || hipMemcpy(d_normals, normals, n * 4, hipMemcpyHostToDevice) == hipSuccess)) {
-            rc = update_scene(ctx, s, d_points, d_normals, points, normals);
-        } else {
-            (void)hipGetLastError();
-            rc = update_scene_host(ctx, s, points, normals, YK_LAYOUT_REASON_OUT_OF_MEMORY);
-        }
-    } else {
-        rc = update_scene_host(ctx, s, points, normals, YK_LAYOUT_REASON_NONE);
-    }
-    if (rc == YK_OK) finish_update(s, t_begin);
-    return rc;
-} YK_CATCH(ctx)
-
-yk_status yk_scene_update_device(yk_context* ctx, yk_scene* s, const float* d_points, const float* d_normals, void* stream) try {
-    if (!ctx) return YK_ERR_INVALID_ARGUMENT;
-    YK_LOCK(ctx);
-    const double t_begin = now_seconds();
-    yk_status rc = check_update(ctx, s, d_points, d_normals);
-    if (rc != YK_OK) return rc;
-    (void)hipSetDevice(ctx->device);
-    const size_t bytes = 12 * (size_t)s->upd.n_vertices;  // the pointer checks of yk_scene_create_device, with its messages
-    if ((rc = check_device_arrays(ctx, {{"points", d_points, bytes}, {"normals", d_normals, bytes}})) != YK_OK) return rc;
-    if (stream) {  // the caller's arrays are complete where its stream stands now
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_in, (hipStream_t)stream));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_in, 0));
-    }
-    if ((rc = drain_context(ctx)) != YK_OK) return rc;
-    rc = update_scene(ctx, s, d_points, d_normals, nullptr, nullptr);
-    if (rc == YK_OK) finish_update(s, t_begin);
-    return rc;
-} YK_CATCH(ctx)
-
 yk_status yk_scene_get_update_info(const yk_scene* s, yk_scene_update_info* out) {
     if (!s || !out) return YK_ERR_INVALID_ARGUMENT;
     *out = s->upd.info;
     return YK_OK;
 }
 
-yk_status yk_scene_apply_edit(yk_context* ctx, yk_scene* s, const yk_scene_edit* edit) try {
-    std::unique_lock<std::recursive_mutex> yk_lock_;
-    if (ctx) yk_lock_ = std::unique_lock<std::recursive_mutex>(ctx->mu);
-    const double t_begin = now_seconds();
-    yk_status rc = check_edit(ctx, s, edit, nullptr);
-    if (rc != YK_OK) return rc;
-    if (ctx) {
-        (void)hipSetDevice(ctx->device);
-        if ((rc = drain_context(ctx)) != YK_OK) return rc;
-    }
-    return apply_edit(ctx, s, edit, nullptr, t_begin);
-} YK_CATCH(ctx)
-
-yk_status yk_scene_apply_edit_device(yk_context* ctx, yk_scene* s, const yk_scene_edit* edit, const void* d_spheres, void* stream) try {
-    if (!ctx) return fail(nullptr, YK_ERR_INVALID_ARGUMENT, edit && edit->spheres && d_spheres ? "spheres given as a host table and as a device table" : "a sphere table in device memory needs a context");
-    YK_LOCK(ctx);
-    const double t_begin = now_seconds();
-    yk_status rc = check_edit(ctx, s, edit, d_spheres);
-    if (rc != YK_OK) return rc;
-    (void)hipSetDevice(ctx->device);
-    if (d_spheres && s->n_spheres) {  // the pointer checks of yk_scene_create_device, with its messages
-        if ((rc = check_device_arrays(ctx, {{"spheres", d_spheres, sizeof(yk_sphere_desc) * (size_t)s->n_spheres}})) != YK_OK) return rc;
-        if (reinterpret_cast<uintptr_t>(d_spheres) & 3u) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "spheres must be 4-byte aligned");
-    }
-    if (stream) {  // the caller's table is complete where its stream stands now
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_in, (hipStream_t)stream));
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_in, 0));
-    }
-    if ((rc = drain_context(ctx)) != YK_OK) return rc;
-    return apply_edit(ctx, s, edit, d_spheres, t_begin);
-} YK_CATCH(ctx)
-
 yk_status yk_scene_get_edit_info(const yk_scene* s, yk_scene_edit_info* out) {
     if (!s || !out) return YK_ERR_INVALID_ARGUMENT;
-    *out = s->edit.info;
+    *out = s->upd.edit_info;
     return YK_OK;
 }
 

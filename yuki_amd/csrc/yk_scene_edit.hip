@@ -14,7 +14,7 @@
 #include <cstring>
 #include <vector>
 
-#include "yk_internal.h"
+#include "yk_scene_route.h"
 #include "yk_scene_update.h"
 
 using namespace yk;
@@ -57,17 +57,6 @@ __global__ void __launch_bounds__(kThreads) k_spheres_in(const uint32_t* __restr
     material[k] = m;
 }
 
-unsigned blocks(size_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
-
-#define EDIT_TRY(expr)                      \
-    do {                                    \
-        const hipError_t e_ = (expr);       \
-        if (e_ != hipSuccess) {             \
-            (void)hipStreamSynchronize(st); \
-            return layout_reason_of(e_);    \
-        }                                   \
-    } while (0)
-
 }  // namespace
 
 uint32_t stage_spheres_device(yk_context* ctx, yk_scene* s, const void* d_in, DevScratch& tmp, StagedSpheres* staged, uint32_t* flag) {
@@ -77,12 +66,12 @@ uint32_t stage_spheres_device(yk_context* ctx, yk_scene* s, const void* d_in, De
     const uint32_t n = s->n_spheres;
     uint32_t* d_flag = nullptr;
     if (!tmp.get(staged->table, n) || !tmp.get(staged->bounds, 6 * (size_t)n) || !tmp.get(staged->material, n) || !tmp.get(d_flag, 1)) return layout_reason_of(tmp.err);
-    EDIT_TRY(hipMemsetAsync(d_flag, 0, 4, st));
-    k_spheres_in<<<blocks(n), kThreads, 0, st>>>(reinterpret_cast<const uint32_t*>(d_in), n, s->n_materials, reinterpret_cast<uint4*>(staged->table), reinterpret_cast<float2*>(staged->bounds),
+    ROUTE_TRY(st, hipMemsetAsync(d_flag, 0, 4, st));
+    k_spheres_in<<<route_blocks(n, kThreads), kThreads, 0, st>>>(reinterpret_cast<const uint32_t*>(d_in), n, s->n_materials, reinterpret_cast<uint4*>(staged->table), reinterpret_cast<float2*>(staged->bounds),
                                                  staged->material, d_flag);
-    EDIT_TRY(hipGetLastError());
-    EDIT_TRY(hipMemcpyAsync(flag, d_flag, 4, hipMemcpyDeviceToHost, st));
-    EDIT_TRY(hipStreamSynchronize(st));
+    ROUTE_TRY(st, hipGetLastError());
+    ROUTE_TRY(st, hipMemcpyAsync(flag, d_flag, 4, hipMemcpyDeviceToHost, st));
+    ROUTE_TRY(st, hipStreamSynchronize(st));
     return YK_LAYOUT_REASON_NONE;
 }
 
@@ -93,10 +82,10 @@ uint32_t commit_spheres_device(yk_context* ctx, yk_scene* s, const StagedSpheres
     const size_t n = s->n_spheres;
     if (!u.planned || s->spheres.bytes < n * sizeof(DevSphere) || u.sphere_b.bytes < 24 * n || u.sphere_bounds.size() != 6 * n) return YK_LAYOUT_REASON_DEVICE_ERROR;
     material->resize(n);
-    EDIT_TRY(hipMemcpyAsync(s->spheres.p, staged.table, n * sizeof(DevSphere), hipMemcpyDeviceToDevice, st));
-    EDIT_TRY(hipMemcpyAsync(u.sphere_b.p, staged.bounds, 24 * n, hipMemcpyDeviceToDevice, st));
-    EDIT_TRY(hipMemcpyAsync(u.sphere_bounds.data(), staged.bounds, 24 * n, hipMemcpyDeviceToHost, st));
-    EDIT_TRY(hipMemcpyAsync(material->data(), staged.material, 4 * n, hipMemcpyDeviceToHost, st));
-    EDIT_TRY(hipStreamSynchronize(st));
+    ROUTE_TRY(st, hipMemcpyAsync(s->spheres.p, staged.table, n * sizeof(DevSphere), hipMemcpyDeviceToDevice, st));
+    ROUTE_TRY(st, hipMemcpyAsync(u.sphere_b.p, staged.bounds, 24 * n, hipMemcpyDeviceToDevice, st));
+    ROUTE_TRY(st, hipMemcpyAsync(u.sphere_bounds.data(), staged.bounds, 24 * n, hipMemcpyDeviceToHost, st));
+    ROUTE_TRY(st, hipMemcpyAsync(material->data(), staged.material, 4 * n, hipMemcpyDeviceToHost, st));
+    ROUTE_TRY(st, hipStreamSynchronize(st));
     return YK_LAYOUT_REASON_NONE;
 }

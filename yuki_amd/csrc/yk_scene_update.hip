@@ -15,8 +15,8 @@
 // per level with integer atomics, a host scan over the few levels, a scatter; the order inside a level is free — with the
 // leaves as the last group, the spheres' bounds and the materials' kinds.  The interior index, the wide slots and the
 // last-in-leaf marks are recomputed by the layout on every update (DESIGN.md §3 has the measurement).
-// An edit in place (yk_scene_apply_edit, yk_scene.cpp) runs the same plan and the same boxes and records (plan_scene_update,
-// refit_scene_device) after it has rewritten the spheres' bounds or the materials' kinds.
+// yk_scene_change.cpp calls the route's steps (plan_scene_update, stage_points_device, commit_points_device, refit_scene_device);
+// an edit in place runs the same plan, boxes and records after it has rewritten the spheres' bounds or the materials' kinds.
 // Also here: yk_bvh_refit, the host instance of the rule.
 #include <hip/hip_runtime.h>
 
@@ -24,7 +24,7 @@
 #include <cstring>
 #include <vector>
 
-#include "yk_internal.h"
+#include "yk_scene_route.h"
 #include "yk_scene_update.h"
 
 using namespace yk::upd;
@@ -105,17 +105,6 @@ __global__ void __launch_bounds__(kThreads) k_top_levels(uint32_t* nodes, const 
     }
 }
 
-unsigned blocks(size_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
-
-#define UPD_TRY(expr)                       \
-    do {                                    \
-        const hipError_t e_ = (expr);       \
-        if (e_ != hipSuccess) {             \
-            (void)hipStreamSynchronize(st); \
-            return layout_reason_of(e_);    \
-        }                                   \
-    } while (0)
-
 // The plan of the device route.  Returns YK_LAYOUT_REASON_*; a plan that fails is dropped and the next update tries again.
 uint32_t build_plan(yk_context* ctx, yk_scene* s) {
     yk_scene::UpdateState& u = s->upd;
@@ -131,15 +120,15 @@ uint32_t build_plan(yk_context* ctx, yk_scene* s) {
         const hipError_t e = upload_host_tree(*bvh, up);
         if (e == hipSuccess) adopt_device_tree(s, up, nullptr);  // the host copy stays current
         up.release();  // what the scene held before (resident beside the upload until here), or the failed upload
-        UPD_TRY(e);
+        ROUTE_TRY(st, e);
         added += s->tree_nodes.bytes + s->tree_order.bytes + u.depth.bytes - had;  // growth only: a tree's buffers have one size
     } else {
         added += u.depth.bytes;  // the builder's own, kept since creation
     }
     {
         const size_t had = u.sphere_b.bytes + u.mat_kind_d.bytes;
-        UPD_TRY(put_host_array(u.sphere_b, u.sphere_bounds.data(), u.sphere_bounds.size() * 4));
-        UPD_TRY(put_host_array(u.mat_kind_d, u.mat_kind.data(), u.mat_kind.size()));
+        ROUTE_TRY(st, put_host_array(u.sphere_b, u.sphere_bounds.data(), u.sphere_bounds.size() * 4));
+        ROUTE_TRY(st, put_host_array(u.mat_kind_d, u.mat_kind.data(), u.mat_kind.size()));
         added += u.sphere_b.bytes + u.mat_kind_d.bytes - had;
     }
     // groups: interior nodes by depth below the root (fewer than the tree's depth), then the leaves
@@ -147,16 +136,16 @@ uint32_t build_plan(yk_context* ctx, yk_scene* s) {
     std::vector<uint32_t> words(leaf_group + 2u, 0u);
     {
         const size_t had = u.words.bytes + u.list.bytes;
-        UPD_TRY(u.words.ensure((words.size() + 1) * 4));  // one more word: the flag of k_points_finite
-        UPD_TRY(u.list.ensure(std::max<size_t>((size_t)n * 4, 16)));
+        ROUTE_TRY(st, u.words.ensure((words.size() + 1) * 4));  // one more word: the flag of k_points_finite
+        ROUTE_TRY(st, u.list.ensure(std::max<size_t>((size_t)n * 4, 16)));
         added += u.words.bytes + u.list.bytes - had;
     }
     uint32_t* d_words = u.words.as<uint32_t>();
-    UPD_TRY(hipMemsetAsync(d_words, 0, (words.size() + 1) * 4, st));
-    k_group_count<<<blocks(n), kThreads, 0, st>>>(s->tree_nodes.as<uint32_t>(), u.depth.as<uint32_t>(), n, leaf_group, d_words);
-    UPD_TRY(hipGetLastError());
-    UPD_TRY(hipMemcpyAsync(words.data(), d_words, words.size() * 4, hipMemcpyDeviceToHost, st));
-    UPD_TRY(hipStreamSynchronize(st));
+    ROUTE_TRY(st, hipMemsetAsync(d_words, 0, (words.size() + 1) * 4, st));
+    k_group_count<<<route_blocks(n, kThreads), kThreads, 0, st>>>(s->tree_nodes.as<uint32_t>(), u.depth.as<uint32_t>(), n, leaf_group, d_words);
+    ROUTE_TRY(st, hipGetLastError());
+    ROUTE_TRY(st, hipMemcpyAsync(words.data(), d_words, words.size() * 4, hipMemcpyDeviceToHost, st));
+    ROUTE_TRY(st, hipStreamSynchronize(st));
     if (words[leaf_group + 1u]) return YK_LAYOUT_REASON_DEVICE_ERROR;
     uint32_t n_levels = 0;
     for (uint32_t g = 0; g < leaf_group; ++g)
@@ -171,11 +160,11 @@ uint32_t build_plan(yk_context* ctx, yk_scene* s) {
     }
     off[leaf_group + 1u] = run;
     if (run != n || words[leaf_group] != n - (n - 1u) / 2u) return YK_LAYOUT_REASON_DEVICE_ERROR;
-    UPD_TRY(hipMemcpyAsync(d_words, off.data(), off.size() * 4, hipMemcpyHostToDevice, st));
-    k_group_scatter<<<blocks(n), kThreads, 0, st>>>(s->tree_nodes.as<uint32_t>(), u.depth.as<uint32_t>(), n, leaf_group, d_words, u.list.as<uint32_t>());
-    UPD_TRY(hipGetLastError());
-    UPD_TRY(hipMemcpyAsync(d_words, off.data(), off.size() * 4, hipMemcpyHostToDevice, st));  // the cursors become the offsets again: k_top_levels reads them
-    UPD_TRY(hipStreamSynchronize(st));  // `off` is pageable
+    ROUTE_TRY(st, hipMemcpyAsync(d_words, off.data(), off.size() * 4, hipMemcpyHostToDevice, st));
+    k_group_scatter<<<route_blocks(n, kThreads), kThreads, 0, st>>>(s->tree_nodes.as<uint32_t>(), u.depth.as<uint32_t>(), n, leaf_group, d_words, u.list.as<uint32_t>());
+    ROUTE_TRY(st, hipGetLastError());
+    ROUTE_TRY(st, hipMemcpyAsync(d_words, off.data(), off.size() * 4, hipMemcpyHostToDevice, st));  // the cursors become the offsets again: k_top_levels reads them
+    ROUTE_TRY(st, hipStreamSynchronize(st));  // `off` is pageable
     u.level_off.assign(off.begin(), off.begin() + n_levels + 1u);
     u.level_off.push_back(off[leaf_group]);      // [n_levels + 1]: where the leaves begin ...
     u.level_off.push_back(off[leaf_group + 1]);  // [n_levels + 2]: ... and end
@@ -193,37 +182,32 @@ uint32_t plan_scene_update(yk_context* ctx, yk_scene* s) {
     return s->upd.planned ? (uint32_t)YK_LAYOUT_REASON_NONE : build_plan(ctx, s);
 }
 
-uint32_t update_scene_device(yk_context* ctx, yk_scene* s, const float* d_points, const float* d_normals, bool* not_finite) {
-    *not_finite = false;
+uint32_t stage_points_device(yk_context* ctx, yk_scene* s, const float* d_points, uint32_t* flag) {
+    *flag = 0;
     yk_scene::UpdateState& u = s->upd;
-    (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
-    double t0 = now_seconds();
-    if (!u.planned) {
-        const uint32_t r = plan_scene_update(ctx, s);
-        if (r != YK_LAYOUT_REASON_NONE) return r;
-        t0 = now_seconds();  // the plan counts in seconds_total only
-    }
-    // all or nothing: the test, read back before anything of the scene is written
+    if (!u.planned) return YK_LAYOUT_REASON_DEVICE_ERROR;
     const size_t n_floats = 3 * (size_t)u.n_vertices;
     uint32_t* d_flag = u.words.as<uint32_t>() + (s->bvh->depth + 3u);  // behind the plan's offsets; zero between updates
     const uint32_t head = (uint32_t)std::min<size_t>(n_floats, ((16u - (uint32_t)(reinterpret_cast<uintptr_t>(d_points) & 15u)) & 15u) / 4u);
     const size_t nvec = (n_floats - head) / 4;
-    uint32_t flag = 0;
-    k_points_finite<<<std::max(blocks(nvec), 1u), kThreads, 0, st>>>(reinterpret_cast<const uint32_t*>(d_points), n_floats, head, nvec, d_flag);
-    UPD_TRY(hipGetLastError());
-    UPD_TRY(hipMemcpyAsync(&flag, d_flag, 4, hipMemcpyDeviceToHost, st));
-    UPD_TRY(hipStreamSynchronize(st));
-    if (flag) {
-        UPD_TRY(hipMemsetAsync(d_flag, 0, 4, st));
-        UPD_TRY(hipStreamSynchronize(st));
-        *not_finite = true;
-        return YK_LAYOUT_REASON_NONE;
+    k_points_finite<<<std::max(route_blocks(nvec, kThreads), 1u), kThreads, 0, st>>>(reinterpret_cast<const uint32_t*>(d_points), n_floats, head, nvec, d_flag);
+    ROUTE_TRY(st, hipGetLastError());
+    ROUTE_TRY(st, hipMemcpyAsync(flag, d_flag, 4, hipMemcpyDeviceToHost, st));
+    ROUTE_TRY(st, hipStreamSynchronize(st));
+    if (*flag) {
+        ROUTE_TRY(st, hipMemsetAsync(d_flag, 0, 4, st));
+        ROUTE_TRY(st, hipStreamSynchronize(st));
     }
-    UPD_TRY(hipMemcpyAsync(s->points.p, d_points, n_floats * 4, hipMemcpyDeviceToDevice, st));
-    if (d_normals) UPD_TRY(hipMemcpyAsync(s->normals.p, d_normals, n_floats * 4, hipMemcpyDeviceToDevice, st));
-    u.info.seconds_check = now_seconds() - t0;
-    return refit_scene_device(ctx, s, true, &u.info.seconds_boxes, &u.info.seconds_records);
+    return YK_LAYOUT_REASON_NONE;
+}
+
+uint32_t commit_points_device(yk_context* ctx, yk_scene* s, const float* d_points, const float* d_normals) {
+    hipStream_t st = ctx->stream;
+    const size_t bytes = 12 * (size_t)s->upd.n_vertices;
+    ROUTE_TRY(st, hipMemcpyAsync(s->points.p, d_points, bytes, hipMemcpyDeviceToDevice, st));
+    if (d_normals) ROUTE_TRY(st, hipMemcpyAsync(s->normals.p, d_normals, bytes, hipMemcpyDeviceToDevice, st));
+    return YK_LAYOUT_REASON_NONE;
 }
 
 uint32_t refit_scene_device(yk_context* ctx, yk_scene* s, bool boxes, double* seconds_boxes, double* seconds_records) {
@@ -239,18 +223,18 @@ uint32_t refit_scene_device(yk_context* ctx, yk_scene* s, bool boxes, double* se
     if (boxes) {
         const uint32_t* list = u.list.as<uint32_t>();
         const uint32_t n_leaves = u.level_off[n_levels + 2u] - u.level_off[n_levels + 1u];
-        k_leaves<<<blocks(n_leaves), kThreads, 0, st>>>(nodes, list + u.level_off[n_levels + 1u], n_leaves, n, s->tree_order.as<uint32_t>(),
+        k_leaves<<<route_blocks(n_leaves, kThreads), kThreads, 0, st>>>(nodes, list + u.level_off[n_levels + 1u], n_leaves, n, s->tree_order.as<uint32_t>(),
                                                         GeometryBound{s->points.as<float>(), s->indices.as<uint32_t>(), u.sphere_b.as<float>(), s->n_triangles, np});
-        UPD_TRY(hipGetLastError());
+        ROUTE_TRY(st, hipGetLastError());
         uint32_t n_top = 0;  // the levels at the top that one block finishes
         while (ctx->update_top_block && n_top < n_levels && u.level_off[n_top + 1u] - u.level_off[n_top] <= (uint32_t)kThreads) ++n_top;
         if (n_top < 2u) n_top = 0;  // one level is one launch either way
         for (uint32_t d = n_levels; d-- > n_top;) {
             const uint32_t count = u.level_off[d + 1u] - u.level_off[d];
-            k_level<<<blocks(count), kThreads, 0, st>>>(nodes, list + u.level_off[d], count, n);
+            k_level<<<route_blocks(count, kThreads), kThreads, 0, st>>>(nodes, list + u.level_off[d], count, n);
         }
         if (n_top) k_top_levels<<<1, kThreads, 0, st>>>(nodes, list, u.words.as<uint32_t>(), n_top, n);
-        UPD_TRY(hipGetLastError());
+        ROUTE_TRY(st, hipGetLastError());
     }
     DeviceTree tree;  // borrowed: the buffers stay the scene's
     tree.nodes = s->tree_nodes;
@@ -258,8 +242,8 @@ uint32_t refit_scene_device(yk_context* ctx, yk_scene* s, bool boxes, double* se
     tree.order = s->tree_order;
     tree.n_nodes = n;
     tree.n_shapes = np;
-    UPD_TRY(hipMemcpyAsync(tree.root_words, nodes, 32, hipMemcpyDeviceToHost, st));
-    UPD_TRY(hipStreamSynchronize(st));
+    ROUTE_TRY(st, hipMemcpyAsync(tree.root_words, nodes, 32, hipMemcpyDeviceToHost, st));
+    ROUTE_TRY(st, hipStreamSynchronize(st));
     *seconds_boxes = boxes ? now_seconds() - t0 : 0.0;
 
     // records, by the layout's own kernels
