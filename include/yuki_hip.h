@@ -1260,6 +1260,61 @@ yk_status yk_history_rectify_device(yk_context* ctx, const yk_rectify_desc* desc
                                     uint16_t tile_dim, const uint32_t* samples, const void* d_history, const void* d_moments,
                                     void* d_out_history, void* d_out_moments, void* stream);
 
+/* ---- despeckle: film outliers clamped to their neighbourhood ----
+ * A pixel of the CURRENT frame's film that is far brighter than everything around it (a firefly) enters yk_history_blend at
+ * full weight, widens yk_history_rectify's box, inflates the luminance moments and survives the à-trous filter.  This pass
+ * runs first in a frame, on the film, before all of them: a pixel whose luminance exceeds `gain` times the rank-th largest
+ * luminance among the OTHER pixels of its (2 radius + 1)^2 window is scaled down to that bound, its chromaticity kept.  It
+ * reads the film and nothing else (no guides).  The rule is stated next to each expression in yuki_amd/csrc/yk_despeckle.h;
+ * the host and the device instance agree bit for bit (binary32, every operation separate, no FMA, division correctly
+ * rounded, a NaN an operation produces is 0x7fc00000, a value that is only copied keeps its bits).
+ * Luminance l(c) = (0.2126f*r + 0.7152f*g) + 0.0722f*b (yk_variance's).  Finite: neither NaN nor +-inf.
+ * Per pixel P, with m_Q and c_Q the count and the colour of film pixel Q as yk_history_blend reads them (m = 1 and the
+ * film's bits without a table; with one, m = (float)samples[flat] and c = film / m per channel where m > 0), and s_P the
+ * three floats the film STORES at P (s_P = c_P without a table):
+ *   1. m_P == 0: the output is s_P.
+ *   2. Taps: the (2 radius + 1)^2 - 1 pixels around P without P, row-major; taken when inside the film, m_Q != 0 and c_Q
+ *      finite in all three channels; k of them are, l_Q = l(c_Q).  A tap outside the film is never read.
+ *      k < max(min_taps, rank): the output is s_P.
+ *   3. v = the rank-th largest l_Q (as a multiset); a v that is not > 0 counts as +0.  bound = gain * v; where
+ *      bound < floor, bound = floor.  A NaN bound (+inf * 0) : the output is s_P.
+ *   4. c_P finite in all three channels: where l_P = l(c_P) > bound, the output is s_P * (bound / l_P) per channel — one
+ *      division, one multiplication a channel — and the mask is 1; the factor is in [0, 1).  Otherwise the output is s_P.
+ *   5. c_P not finite: with YK_DESPECKLE_REPAIR, per channel the sum of the taken taps' c_Q in tap order (sequential, from
+ *      0), divided by (float)k, and with a table multiplied by m_P; the mask is 2.  Without the flag the output is s_P.
+ * The output film uses the input's convention: a film of sums stays a film of sums, with the same sample table.
+ * A negative v counting as 0 changes no bound at a finite gain > 0 (gain * v < 0 <= floor either way); it makes
+ * gain = +inf, floor = 0 the identity on every film: +inf * v is +inf, which nothing exceeds, or the NaN of step 3.
+ * Limits: biased by design — it removes energy from heavy-tailed light transport (caustics, small bright emitters seen
+ * through glossy paths) and does not vanish as the film converges: it belongs in front of an accumulating or denoising
+ * chain, not on a film meant to converge.  Luminance only.  A real glint narrower than the window's rank is clamped like a
+ * firefly.  yk_multi scenes are not served. */
+#define YK_DESPECKLE_REPAIR 1u /* yk_despeckle_desc::flags: a pixel that is not finite becomes the mean of its taken taps */
+typedef struct yk_despeckle_desc {
+    uint32_t radius;   /* 1 .. 2: the (2 radius + 1)^2 - 1 pixels around P */
+    uint32_t rank;     /* 1 .. 4: the rank-th largest neighbour luminance bounds P (1 = the maximum) */
+    uint32_t min_taps; /* >= rank: fewer taken taps and P passes through */
+    uint32_t flags;    /* YK_DESPECKLE_REPAIR */
+    float gain;        /* >= 0, +inf allowed (nothing is clamped), NaN refused; -0 is taken as +0 */
+    float floor;       /* >= 0, finite: a luminance below which nothing is clamped; -0 is taken as +0 */
+} yk_despeckle_desc;
+/* film_rgb, `samples` and tile_dim as yk_history_blend takes them.  out_rgb: res_x * res_y * 3 floats.  out_mask (may be
+ * NULL): one byte a pixel, 0 untouched, 1 clamped, 2 repaired.  out_counts (may be NULL): two words, the pixels clamped and
+ * the pixels repaired.  ctx NULL = the host instance on the CPU, else on ctx's device (synchronous).
+ * YK_ERR_INVALID_ARGUMENT: a NULL desc, film or out_rgb, a zero resolution, tile_dim 0, a radius outside 1 .. 2, a rank
+ * outside 1 .. 4, min_taps < rank, an unknown flag, a gain that is < 0 or NaN, a floor that is < 0, NaN or infinite, an
+ * out_rgb that overlaps film_rgb (a pixel reads its neighbours' input: the pass does not run in place), a mask or counts
+ * that overlap a film or each other. */
+yk_status yk_despeckle(yk_context* ctx, const yk_despeckle_desc* desc, const float* film_rgb, uint16_t res_x, uint16_t res_y,
+                       uint16_t tile_dim, const uint32_t* samples, float* out_rgb, uint8_t* out_mask, uint32_t* out_counts);
+/* The same on device buffers, enqueued on `stream` (NULL = the context's) without waiting for the device: one launch (and
+ * a memset of the two count words), and no allocation beyond the temporal pass's staged sample table (`samples` is a HOST
+ * table, copied before the call returns).  The films and the counts need 4-byte alignment (anything else:
+ * YK_ERR_INVALID_ARGUMENT, nothing is launched). */
+yk_status yk_despeckle_device(yk_context* ctx, const yk_despeckle_desc* desc, const void* d_film_rgb, uint16_t res_x, uint16_t res_y,
+                              uint16_t tile_dim, const uint32_t* samples, void* d_out_rgb, void* d_out_mask, void* d_out_counts,
+                              void* stream);
+
 /* ---- adaptive sampling: per-pixel statistics choose where the next samples go ----
  * The accumulating entry points give every pixel of a tile the same number of samples.  Here a film carries, beside its
  * RGB sums, one yk_pixel_stats record a pixel; a selection pass lists the pixels that are still noisy, a render takes that

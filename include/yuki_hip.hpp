@@ -364,6 +364,22 @@ inline void history_rectify_device(Context& ctx, const yk_rectify_desc& desc, co
                                    const void* d_history, const void* d_moments, void* d_out_history, void* d_out_moments, void* stream = nullptr) {
     check(yk_history_rectify_device(ctx.handle(), &desc, d_film, res_x, res_y, tile_dim, samples, d_history, d_moments, d_out_history, d_out_moments, stream), ctx.handle());
 }
+// Despeckle, first in a frame on the current frame's film, before history_rectify (the rule is stated in yuki_hip.h and
+// csrc/yk_despeckle.h): a pixel far brighter than its neighbourhood is scaled down to gain x the rank-th largest luminance
+// around it -> the film, in the input's convention.  mask (res_x * res_y bytes: 0 untouched, 1 clamped, 2 repaired) and
+// counts (two words: clamped, repaired) may be nullptr.  ctx == nullptr: the host instance.
+inline std::vector<float> despeckle(Context* ctx, const yk_despeckle_desc& desc, const float* film, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const uint32_t* samples = nullptr,
+                                    uint8_t* mask = nullptr, uint32_t* counts = nullptr) {
+    std::vector<float> out((size_t)res_x * res_y * 3);
+    yk_context* c = ctx ? ctx->handle() : nullptr;
+    check(yk_despeckle(c, &desc, film, res_x, res_y, tile_dim, samples, out.data(), mask, counts), c);
+    return out;
+}
+// The same on device buffers (the output is another buffer: the pass does not run in place), enqueued on `stream`: one launch.
+inline void despeckle_device(Context& ctx, const yk_despeckle_desc& desc, const void* d_film, uint16_t res_x, uint16_t res_y, uint16_t tile_dim, const uint32_t* samples, void* d_out_rgb,
+                             void* d_out_mask = nullptr, void* d_out_counts = nullptr, void* stream = nullptr) {
+    check(yk_despeckle_device(ctx.handle(), &desc, d_film, res_x, res_y, tile_dim, samples, d_out_rgb, d_out_mask, d_out_counts, stream), ctx.handle());
+}
 // The variance of the luminance of `film` as denoise_variance will filter it; moments and albedo may be nullptr.
 inline std::vector<float> variance(Context* ctx, const yk_variance_desc& desc, const Moments* moments, const float* film, const yk_guide* guides, const Albedo* albedo, uint16_t res_x,
                                    uint16_t res_y, uint16_t tile_dim, const uint32_t* samples = nullptr) {

@@ -381,6 +381,24 @@ pub struct yk_rectify_desc {
     pub gamma: f32,
 }
 
+/// yk_despeckle_desc::flags: a pixel that is not finite becomes the mean of its taken taps
+pub const YK_DESPECKLE_REPAIR: u32 = 1;
+
+/// The window, the rank and the gain of the despeckle pass: a film pixel brighter than `gain` x the rank-th largest
+/// luminance among the other pixels of its (2 radius + 1)^2 window (radius 1 .. 2, rank 1 .. 4) is scaled down to that
+/// bound; fewer than max(min_taps, rank) usable taps, or a luminance below `floor`, and it passes through
+/// (yuki_amd/csrc/yk_despeckle.h)
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct yk_despeckle_desc {
+    pub radius: u32,
+    pub rank: u32,
+    pub min_taps: u32,
+    pub flags: u32,
+    pub gain: f32,
+    pub floor: f32,
+}
+
 /// The target rectangle of ScaleOutput::draw in top-down window coordinates
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
@@ -673,6 +691,8 @@ extern "C" {
     pub fn yk_denoise_variance_device(ctx: *mut yk_context, desc: *const yk_variance_desc, d_film_rgb: *const c_void, d_guides: *const c_void, d_variance: *const c_void, d_albedo: *const c_void, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, d_out_rgb: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_history_rectify(ctx: *mut yk_context, desc: *const yk_rectify_desc, film_rgb: *const f32, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, history: *const yk_history, moments: *const yk_moments, out_history: *mut yk_history, out_moments: *mut yk_moments) -> yk_status;
     pub fn yk_history_rectify_device(ctx: *mut yk_context, desc: *const yk_rectify_desc, d_film_rgb: *const c_void, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, d_history: *const c_void, d_moments: *const c_void, d_out_history: *mut c_void, d_out_moments: *mut c_void, stream: *mut c_void) -> yk_status;
+    pub fn yk_despeckle(ctx: *mut yk_context, desc: *const yk_despeckle_desc, film_rgb: *const f32, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, out_rgb: *mut f32, out_mask: *mut u8, out_counts: *mut u32) -> yk_status;
+    pub fn yk_despeckle_device(ctx: *mut yk_context, desc: *const yk_despeckle_desc, d_film_rgb: *const c_void, res_x: u16, res_y: u16, tile_dim: u16, samples: *const u32, d_out_rgb: *mut c_void, d_out_mask: *mut c_void, d_out_counts: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_pixel_list_create(ctx: *mut yk_context, res_x: u16, res_y: u16, out: *mut *mut yk_pixel_list) -> yk_status;
     pub fn yk_pixel_list_destroy(list: *mut yk_pixel_list);
     pub fn yk_pixel_list_set(list: *mut yk_pixel_list, xy: *const u32, sample: *const u32, n: u32, passes: u32) -> yk_status;

@@ -214,6 +214,8 @@ SYMBOLS = {
     "yk_denoise_variance_device": (C.c_int, [vp, C.POINTER(abi.VarianceDesc), vp, vp, vp, vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp]),
     "yk_history_rectify": (C.c_int, [vp, C.POINTER(abi.RectifyDesc), vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp, vp, vp]),
     "yk_history_rectify_device": (C.c_int, [vp, C.POINTER(abi.RectifyDesc), vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp, vp, vp, vp]),
+    "yk_despeckle": (C.c_int, [vp, C.POINTER(abi.DespeckleDesc), vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp, vp]),
+    "yk_despeckle_device": (C.c_int, [vp, C.POINTER(abi.DespeckleDesc), vp, C.c_uint16, C.c_uint16, C.c_uint16, vp, vp, vp, vp, vp]),
     "yk_pixel_list_create": (C.c_int, [vp, C.c_uint16, C.c_uint16, C.POINTER(vp)]),
     "yk_pixel_list_destroy": (None, [vp]),
     "yk_pixel_list_set": (C.c_int, [vp, vp, vp, C.c_uint32, C.c_uint32]),

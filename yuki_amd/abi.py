@@ -187,6 +187,16 @@ class RectifyDesc(C.Structure):
     _fields_ = [("radius", C.c_uint32), ("gamma", C.c_float)]
 
 
+DESPECKLE_REPAIR = 1  # yk_despeckle_desc::flags
+DESPECKLE_UNTOUCHED, DESPECKLE_CLAMPED, DESPECKLE_REPAIRED = 0, 1, 2  # the values of yk_despeckle's mask
+
+
+class DespeckleDesc(C.Structure):
+    """yk_despeckle_desc: the window, the rank and the gain of the despeckle pass (csrc/yk_despeckle.h)."""
+
+    _fields_ = [("radius", C.c_uint32), ("rank", C.c_uint32), ("min_taps", C.c_uint32), ("flags", C.c_uint32), ("gain", C.c_float), ("floor", C.c_float)]
+
+
 class AdaptiveDesc(C.Structure):
     """yk_adaptive_desc: the adaptive sampler's rule (csrc/yk_adaptive.h)."""
 

@@ -780,6 +780,57 @@ def rectify_history(history, film, params, tile_dim=16, samples=None, moments=No
     return out if moments is None else (out, out_m)
 
 
+# --------------------------------------------------------------------------- despeckle (csrc/yk_despeckle.h)
+# Per frame, first: film = despeckle(film, dp, samples=...) on the current frame's film — the output keeps the input's
+# convention, so the same sample table goes on with it — then rectify_history, blend_history, blend_moments as above.
+@dataclass
+class DespeckleParams:
+    """yk_despeckle_desc: a pixel brighter than gain x the rank-th largest luminance among the other pixels of its
+    (2 radius + 1)^2 window (radius 1 .. 2, rank 1 .. 4) is scaled down to that bound; with fewer than max(min_taps, rank)
+    usable neighbours, or below the luminance `floor`, it is left alone; repair replaces a pixel that is not finite by the
+    mean of its usable neighbours.  gain float("inf") clamps nothing.  The defaults of radius, rank and gain are the best
+    row of profiles/despeckle_quality.json.  Biased by design: not for a film meant to converge."""
+
+    radius: int = 2
+    rank: int = 3
+    gain: float = 1.5
+    min_taps: int = 3
+    floor: float = 0.0
+    repair: bool = False
+
+    def as_struct(self):
+        return abi.DespeckleDesc(int(self.radius), int(self.rank), int(self.min_taps), abi.DESPECKLE_REPAIR if self.repair else 0, float(self.gain), float(self.floor))
+
+
+def _despeckle_desc(params):
+    if not isinstance(params, DespeckleParams):
+        raise TypeError("params is a DespeckleParams")
+    return params.as_struct()
+
+
+def despeckle(film, params, tile_dim=16, samples=None, ctx=None, return_mask=False):
+    """yk_despeckle: the (h, w, 3) float32 film (with `samples` = Film.samples for an accumulating one, as blend_history
+    takes it) with its outliers clamped -> the film, in the input's convention (a film of sums stays one).  With
+    return_mask: (film, mask, counts) — the (h, w) uint8 mask (0 untouched, 1 clamped, 2 repaired) and the two counts
+    (clamped, repaired).  ctx None = the host instance."""
+    film, w, h = _film(film)
+    d = _despeckle_desc(params)
+    samples = _blend_samples((w, h), tile_dim, samples)
+    out = np.empty_like(film)
+    mask = np.zeros((h, w), dtype=np.uint8) if return_mask else None
+    counts = np.zeros(2, dtype=np.uint32) if return_mask else None
+    c = ctx.h if ctx else None
+    check(lib().yk_despeckle(c, C.byref(d), _p(film), w, h, int(tile_dim), _p(samples), _p(out), _p(mask), _p(counts)), c)
+    return (out, mask, (int(counts[0]), int(counts[1]))) if return_mask else out
+
+
+def _despeckle_for_output(film, despeckle_params, tile_dim, samples, ctx):
+    """The despeckle step of write_output / write_preview, before the denoise: None leaves the film as it is."""
+    if despeckle_params is None:
+        return film
+    return despeckle(film, despeckle_params, tile_dim, samples, ctx)
+
+
 # --------------------------------------------------------------------------- adaptive sampling (csrc/yk_adaptive.h)
 # film_sum (h, w, 3) float32 sums and stats (h, w) abi.PIXEL_STATS_DTYPE, both zeros when cleared.  Per round:
 # xy, sample = adaptive_select(stats, params); passes = the render of those entries (Integrator.render_pixel_list_device);
@@ -900,7 +951,7 @@ def _guides_through_for_output(guides_through, settings, ctx, guides, albedo):
     return guides, albedo
 
 
-def write_output(path, film, tone_map=None, settings=None, samples=None, ctx=None, denoise=None, guides=None, albedo=None, variance=None, auto_exposure=None, guides_through=None):
+def write_output(path, film, tone_map=None, settings=None, samples=None, ctx=None, denoise=None, guides=None, albedo=None, variance=None, auto_exposure=None, guides_through=None, despeckle=None):
     """The Finished branch of app/headless.rs:62-84: Raw writes the film as it is, anything else writes the tone-mapped
     film (a Heatmap without bounds finds them first).  tone_map None = ToneMapType.default(); settings None = a film of the
     array's size with the default tile_dim.  denoise (a DenoiseParams) with guides: the film is denoised first; with albedo
@@ -908,10 +959,12 @@ def write_output(path, film, tone_map=None, settings=None, samples=None, ctx=Non
     the variance-guided filter.  auto_exposure (True or an ExposureParams, Filmic only): the film about to be tone-mapped
     — after the denoise — is metered (meter_exposure) and the exposure is the tone map's times the meter's.
     guides_through ((scene, camera[, max_through]), instead of guides, with ctx): the guides are render_guides_through's —
-    what the pixel shows behind glass — and albedo=True takes surface_albedo of that call's ids."""
+    what the pixel shows behind glass — and albedo=True takes surface_albedo of that call's ids.  despeckle (a
+    DespeckleParams): the film's outliers are clamped first, before the denoise."""
     film = np.ascontiguousarray(film, dtype=np.float32)
     tone_map = ToneMapType.default() if tone_map is None else tone_map
     settings = settings or FilmSettings(res=(film.shape[1], film.shape[0]))
+    film = _despeckle_for_output(film, despeckle, film_tile_dim(settings), samples, ctx)
     guides, albedo = _guides_through_for_output(guides_through, settings, ctx, guides, albedo)
     film, samples = _denoise_for_output(film, denoise, guides, film_tile_dim(settings), samples, ctx, albedo, variance)
     if tone_map.kind == abi.TONE_MAP_RAW:
@@ -1024,15 +1077,17 @@ def write_png(path, pixels):
     check(lib().yk_write_png(str(path).encode(), pixels.shape[1], pixels.shape[0], pixels.shape[2], _p(pixels)))
 
 
-def write_preview(path, film, tone_map=None, settings=None, samples=None, window=None, ctx=None, denoise=None, guides=None, albedo=None, variance=None, auto_exposure=None, guides_through=None):
+def write_preview(path, film, tone_map=None, settings=None, samples=None, window=None, ctx=None, denoise=None, guides=None, albedo=None, variance=None, auto_exposure=None, guides_through=None, despeckle=None):
     """What the window shows, as a PNG: the denoiser when `denoise` (a DenoiseParams) and `guides` are given (demodulated
     by `albedo`, surface_albedo's records, when that is given too; variance-guided when `denoise` is a VarianceParams and
     `variance` its image), the tone map
     (as write_output: None = ToneMapType.default(), Raw = none), then present into `window` (default: the film's size) as
-    an sRGB back buffer stores it (encode 2), then write_png.  auto_exposure and guides_through: as write_output's."""
+    an sRGB back buffer stores it (encode 2), then write_png.  auto_exposure, guides_through and despeckle: as
+    write_output's."""
     film = np.ascontiguousarray(film, dtype=np.float32)
     tone_map = ToneMapType.default() if tone_map is None else tone_map
     settings = settings or FilmSettings(res=(film.shape[1], film.shape[0]))
+    film = _despeckle_for_output(film, despeckle, film_tile_dim(settings), samples, ctx)
     guides, albedo = _guides_through_for_output(guides_through, settings, ctx, guides, albedo)
     film, samples = _denoise_for_output(film, denoise, guides, film_tile_dim(settings), samples, ctx, albedo, variance)
     if tone_map.kind != abi.TONE_MAP_RAW:
@@ -1355,6 +1410,16 @@ class Context:
         d = _rectify_desc(params)
         samples = _blend_samples(res, tile_dim, samples)
         check(lib().yk_history_rectify_device(self.h, C.byref(d), _vp(d_film_ptr), int(res[0]), int(res[1]), int(tile_dim), _p(samples), _vp(d_history_ptr), _vp(moments), _vp(d_out_history_ptr), _vp(out_moments), _vp(stream)), self.h)
+
+    def despeckle_device(self, d_film_ptr, res, params, tile_dim, samples, d_out_ptr, stream=None, mask=None, counts=None):
+        """yk_despeckle_device: device film -> device film (another buffer: the pass does not run in place), enqueued on
+        `stream` (default: the context's) without waiting; one launch.  Each of the film, the output, mask (one byte a
+        pixel) and counts (two uint32 words) is a torch tensor or a device address; mask and counts may be None.
+        `samples` is a host table (or None), copied before the call returns."""
+        d = _despeckle_desc(params)
+        samples = _blend_samples(res, tile_dim, samples)
+        ptr = [a.data_ptr() if hasattr(a, "data_ptr") else a for a in (d_film_ptr, d_out_ptr, mask, counts)]
+        check(lib().yk_despeckle_device(self.h, C.byref(d), _vp(ptr[0]), int(res[0]), int(res[1]), int(tile_dim), _p(samples), _vp(ptr[1]), _vp(ptr[2]), _vp(ptr[3]), _vp(stream)), self.h)
 
     def variance_device(self, d_moments_ptr, d_film_ptr, d_guides_ptr, res, params, tile_dim, samples, d_out_ptr, stream=None, albedo=None):
         """yk_variance_device: device moments (or None), film, guides and albedo (or None) -> res[0] * res[1] device floats,
