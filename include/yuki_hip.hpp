@@ -157,6 +157,14 @@ class Scene {
         check(yk_scene_get_update_info(h_, &i));
         return i;
     }
+    // yk_scene_transform / yk_scene_transform_device: one matrix pair a mesh, absolute, relative to the rest pose the scene keeps
+    void transform(const yk_mesh_transform* transforms) { check(yk_scene_transform(ctx_ ? ctx_->handle() : nullptr, h_, transforms), ctx_ ? ctx_->handle() : nullptr); }
+    void transform_device(const void* d_transforms, void* stream = nullptr) { check(yk_scene_transform_device(ctx_->handle(), h_, d_transforms, stream), ctx_->handle()); }
+    yk_scene_transform_info transform_info() const {  // the last transform's route and reason, the rest copy's bytes, the tree's cost now and at rest
+        yk_scene_transform_info i;
+        check(yk_scene_get_transform_info(h_, &i));
+        return i;
+    }
     std::vector<uint8_t> device_records(uint32_t which) const {  // test hook: one record buffer (YK_RECORDS_*) copied back
         size_t n = 0;
         check(yk_scene_read_records(h_, which, nullptr, 0, &n));

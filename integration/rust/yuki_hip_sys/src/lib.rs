@@ -548,6 +548,33 @@ pub struct yk_scene_update_info {
     pub seconds_total: f64,
 }
 
+/// one record a mesh of yk_scene_transform: the mesh's place relative to its rest pose, row-major; the pair is the caller's
+#[repr(C)]
+#[derive(Clone, Copy)]
+pub struct yk_mesh_transform {
+    pub rest_to_world: [f32; 16],
+    pub world_to_rest: [f32; 16],
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Default)]
+pub struct yk_scene_transform_info {
+    pub n_transforms: u32,
+    pub route: u32,
+    pub reason: u32,
+    pub n_moved_meshes: u32,
+    pub n_flipped_meshes: u32,
+    pub reserved: u32,
+    pub rest_bytes: u64,
+    pub tree_cost: f64,
+    pub tree_cost_rest: f64,
+    pub seconds_check: f64,
+    pub seconds_points: f64,
+    pub seconds_boxes: f64,
+    pub seconds_records: f64,
+    pub seconds_total: f64,
+}
+
 #[repr(C)]
 #[derive(Clone, Copy, Default)]
 pub struct yk_combiner_info {
@@ -613,6 +640,9 @@ extern "C" {
     pub fn yk_scene_apply_edit(ctx: *mut yk_context, scene: *mut yk_scene, edit: *const yk_scene_edit) -> yk_status;
     pub fn yk_scene_apply_edit_device(ctx: *mut yk_context, scene: *mut yk_scene, edit: *const yk_scene_edit, d_spheres: *const c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_scene_get_edit_info(scene: *const yk_scene, out: *mut yk_scene_edit_info) -> yk_status;
+    pub fn yk_scene_transform(ctx: *mut yk_context, scene: *mut yk_scene, transforms: *const yk_mesh_transform) -> yk_status;
+    pub fn yk_scene_transform_device(ctx: *mut yk_context, scene: *mut yk_scene, d_transforms: *const c_void, stream: *mut c_void) -> yk_status;
+    pub fn yk_scene_get_transform_info(scene: *const yk_scene, out: *mut yk_scene_transform_info) -> yk_status;
     pub fn yk_bvh_refit(nodes: *mut yk_bvh_node, n_nodes: usize, shape_order: *const u32, n_shapes: usize, shape_bounds: *const f32) -> yk_status;
     pub fn yk_scene_export_bvh(scene: *const yk_scene, nodes: *mut yk_bvh_node, shape_order: *mut u32) -> yk_status;
     pub fn yk_scene_get_build_info(scene: *const yk_scene, out: *mut yk_bvh_build_info) -> yk_status;
@@ -671,6 +701,8 @@ extern "C" {
     pub fn yk_surface_motion_device(ctx: *mut yk_context, scene: *const yk_scene, d_ids: *const c_void, d_guides: *const c_void, d_prev_points: *const f32, res_x: u16, res_y: u16, d_out: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_surface_motion_spheres(ctx: *mut yk_context, scene: *const yk_scene, ids: *const yk_surface_id, guides: *const yk_guide, prev_points: *const f32, prev_spheres: *const yk_sphere_desc, res_x: u16, res_y: u16, out: *mut yk_motion) -> yk_status;
     pub fn yk_surface_motion_spheres_device(ctx: *mut yk_context, scene: *const yk_scene, d_ids: *const c_void, d_guides: *const c_void, d_prev_points: *const f32, d_prev_spheres: *const c_void, res_x: u16, res_y: u16, d_out: *mut c_void, stream: *mut c_void) -> yk_status;
+    pub fn yk_surface_motion_transforms(ctx: *mut yk_context, scene: *const yk_scene, ids: *const yk_surface_id, guides: *const yk_guide, prev_transforms: *const yk_mesh_transform, prev_spheres: *const yk_sphere_desc, res_x: u16, res_y: u16, out: *mut yk_motion) -> yk_status;
+    pub fn yk_surface_motion_transforms_device(ctx: *mut yk_context, scene: *const yk_scene, d_ids: *const c_void, d_guides: *const c_void, d_prev_transforms: *const c_void, d_prev_spheres: *const c_void, res_x: u16, res_y: u16, d_out: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_history_reproject_moved(ctx: *mut yk_context, desc: *const yk_temporal_desc, prev_history: *const yk_history, prev_guides: *const yk_guide, prev_camera: *const yk_camera, guides: *const yk_guide, motion: *const yk_motion, res_x: u16, res_y: u16, out_history: *mut yk_history) -> yk_status;
     pub fn yk_history_reproject_moved_device(ctx: *mut yk_context, desc: *const yk_temporal_desc, d_prev_history: *const c_void, d_prev_guides: *const c_void, prev_camera: *const yk_camera, d_guides: *const c_void, d_motion: *const c_void, res_x: u16, res_y: u16, d_out_history: *mut c_void, stream: *mut c_void) -> yk_status;
     pub fn yk_surface_albedo(ctx: *mut yk_context, scene: *const yk_scene, ids: *const yk_surface_id, res_x: u16, res_y: u16, out: *mut yk_albedo) -> yk_status;

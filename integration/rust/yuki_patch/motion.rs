@@ -11,7 +11,9 @@
 //! surface that turns by more than acos(normal_cos_min) between frames loses its history.  Carried radiance is the
 //! radiance the surface had: shadows and reflections of things that moved lag for as long as `max_history` lets them.
 //! Spheres move through `edit_scene` (update.rs): `motion_spheres_device` takes the sphere table from before the edit
-//! beside the previous vertex buffer and carries a moved sphere's pixels along.  Lights carry no film.  The rule: yuki_amd/csrc/yk_motion.h, yk_temporal.h.  SOURCE ONLY.
+//! beside the previous vertex buffer and carries a moved sphere's pixels along.  Lights carry no film.  After
+//! `transform_scene_device` (transform.rs) the previous frame's records, 128 bytes a mesh, stand in for the previous vertex
+//! buffer: `transform::motion_device`.  The rule: yuki_amd/csrc/yk_motion.h, yk_temporal.h.  SOURCE ONLY.
 #![cfg(feature = "hip")]
 
 use crate::math::Vec2;

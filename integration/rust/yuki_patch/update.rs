@@ -11,6 +11,7 @@
 //!   * the call waits for what this context has enqueued; renders from other contexts must not be in flight;
 //!   * a refit never improves the tree: after a large deformation traversal is slower than through a rebuilt tree
 //!     (profiles/scene_update_device.json has both), so a worker may rebuild every so often.
+//! A mesh that moves by a matrix needs none of this bookkeeping: `transform.rs` (yk_scene_transform) takes the matrix.
 //! The rule: yuki_amd/csrc/yk_scene_update.h.  SOURCE ONLY.
 #![cfg(feature = "hip")]
 

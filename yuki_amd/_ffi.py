@@ -113,6 +113,9 @@ SYMBOLS = {
     "yk_scene_apply_edit": (C.c_int, [vp, vp, C.POINTER(abi.SceneEdit)]),
     "yk_scene_apply_edit_device": (C.c_int, [vp, vp, C.POINTER(abi.SceneEdit), vp, vp]),
     "yk_scene_get_edit_info": (C.c_int, [vp, C.POINTER(abi.SceneEditInfo)]),
+    "yk_scene_transform": (C.c_int, [vp, vp, vp]),
+    "yk_scene_transform_device": (C.c_int, [vp, vp, vp, vp]),
+    "yk_scene_get_transform_info": (C.c_int, [vp, C.POINTER(abi.SceneTransformInfo)]),
     "yk_bvh_refit": (C.c_int, [vp, C.c_size_t, vp, C.c_size_t, vp]),
     "yk_scene_destroy": (None, [vp]),
     "yk_scene_get_info": (C.c_int, [vp, C.POINTER(SceneInfo)]),
@@ -194,6 +197,8 @@ SYMBOLS = {
     "yk_surface_motion_device": (C.c_int, [vp, vp, vp, vp, vp, C.c_uint16, C.c_uint16, vp, vp]),
     "yk_surface_motion_spheres": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_uint16, C.c_uint16, vp]),
     "yk_surface_motion_spheres_device": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_uint16, C.c_uint16, vp, vp]),
+    "yk_surface_motion_transforms": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_uint16, C.c_uint16, vp]),
+    "yk_surface_motion_transforms_device": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_uint16, C.c_uint16, vp, vp]),
     "yk_surface_albedo": (C.c_int, [vp, vp, vp, C.c_uint16, C.c_uint16, vp]),
     "yk_surface_albedo_device": (C.c_int, [vp, vp, vp, C.c_uint16, C.c_uint16, vp, vp]),
     "yk_albedo_mean": (C.c_int, [vp, vp, vp, C.c_uint16, C.c_uint16, C.c_uint32, vp]),

@@ -302,7 +302,29 @@ class SceneEditInfo(C.Structure):
     ]
 
 
+class SceneTransformInfo(C.Structure):
+    """yk_scene_transform_info: how a scene's last transform in place ran, what it keeps of the rest pose and the tree's cost."""
+
+    _fields_ = [
+        ("n_transforms", C.c_uint32),
+        ("route", C.c_uint32),
+        ("reason", C.c_uint32),
+        ("n_moved_meshes", C.c_uint32),
+        ("n_flipped_meshes", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("rest_bytes", C.c_uint64),
+        ("tree_cost", C.c_double),
+        ("tree_cost_rest", C.c_double),
+        ("seconds_check", C.c_double),
+        ("seconds_points", C.c_double),
+        ("seconds_boxes", C.c_double),
+        ("seconds_records", C.c_double),
+        ("seconds_total", C.c_double),
+    ]
+
+
 SPHERE_DTYPE = np.dtype([("object_to_world", "<f4", 16), ("world_to_object", "<f4", 16), ("radius", "<f4"), ("material", "<i4")])  # yk_sphere_desc, 136 bytes
+MESH_TRANSFORM_DTYPE = np.dtype([("rest_to_world", "<f4", 16), ("world_to_rest", "<f4", 16)])  # yk_mesh_transform, 128 bytes
 GUIDE_DTYPE = np.dtype([("ns", "<f4", 3), ("hit", "<f4"), ("p", "<f4", 3), ("t", "<f4")])  # yk_guide, 32 bytes
 HISTORY_DTYPE = np.dtype([("rgb", "<f4", 3), ("n", "<f4")])  # yk_history, 16 bytes
 SURFACE_NONE = 0xFFFFFFFF  # YK_SURFACE_NONE
@@ -347,6 +369,23 @@ def pack_spheres(spheres):
         out["world_to_object"] = np.asarray([np.asarray(s["w2o"], dtype=np.float32).reshape(16) for s in spheres], dtype=np.float32)
         out["radius"] = np.asarray([s["radius"] for s in spheres], dtype=np.float64).astype(np.float32)
         out["material"] = np.asarray([int(s["material"]) for s in spheres], dtype=np.int32)
+    return out
+
+
+def pack_mesh_transforms(matrices):
+    """One 4 x 4 matrix a mesh (row-major; an (n, 4, 4) array, or a list whose entries may be None for the identity) ->
+    (n,) MESH_TRANSFORM_DTYPE records for Scene.transform.  rest_to_world is the matrix rounded to float32; world_to_rest
+    is numpy.linalg.inv of the GIVEN matrix in float64, rounded once to float32 (the library does not invert: a caller
+    that has a better inverse fills the records itself).  An identity entry gets the identity pair."""
+    out = np.zeros(len(matrices), dtype=MESH_TRANSFORM_DTYPE)
+    eye = np.eye(4, dtype=np.float32).reshape(16)
+    for k, m in enumerate(matrices):
+        if m is None:
+            out["rest_to_world"][k] = out["world_to_rest"][k] = eye
+            continue
+        m = np.asarray(m, dtype=np.float64).reshape(4, 4)
+        out["rest_to_world"][k] = m.astype(np.float32).reshape(16)
+        out["world_to_rest"][k] = eye if np.array_equal(out["rest_to_world"][k], eye) else np.linalg.inv(m).astype(np.float32).reshape(16)
     return out
 
 

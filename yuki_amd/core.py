@@ -472,18 +472,51 @@ def _prev_points(scene, prev_points):
     return np.ascontiguousarray(a)
 
 
-def surface_motion(scene, ids, guides, prev_points, ctx=None, prev_spheres=None):
+_AT_REST = object()  # surface_motion(prev_transforms=): not given.  None is a value: the scene stood at rest
+
+
+def _prev_spheres(scene, prev_spheres):
+    if not isinstance(prev_spheres, np.ndarray):
+        prev_spheres = abi.pack_spheres(prev_spheres)
+    if prev_spheres.dtype != abi.SPHERE_DTYPE or prev_spheres.shape != (len(scene.data.spheres),):
+        raise ValueError(f"prev_spheres is ({len(scene.data.spheres)},) abi.SPHERE_DTYPE records, not {prev_spheres.shape} {prev_spheres.dtype}")
+    return np.ascontiguousarray(prev_spheres)
+
+
+def _motion_transforms(scene, ids, guides, prev_transforms, prev_spheres, w, h, c):
+    n_meshes = len(scene.data.meshes)
+    if prev_transforms is not None:
+        if not (isinstance(prev_transforms, np.ndarray) and prev_transforms.dtype == abi.MESH_TRANSFORM_DTYPE):
+            prev_transforms = abi.pack_mesh_transforms(prev_transforms)
+        if prev_transforms.shape != (n_meshes,):
+            raise ValueError(f"prev_transforms: {prev_transforms.shape} records, the scene has {n_meshes} meshes")
+        prev_transforms = np.ascontiguousarray(prev_transforms)
+    if prev_spheres is not None:
+        prev_spheres = _prev_spheres(scene, prev_spheres)
+    out = np.zeros((h, w), dtype=abi.MOTION_DTYPE)
+    check(lib().yk_surface_motion_transforms(c, scene.h, _p(ids), _p(guides), _p(prev_transforms), _p(prev_spheres), w, h, _p(out)), c)
+    return out
+
+
+def surface_motion(scene, ids, guides, prev_points=None, ctx=None, prev_spheres=None, prev_transforms=_AT_REST):
     """yk_surface_motion: where every pixel's surface point stood when the scene's vertices were `prev_points`
     ((n_vertices, 3) float32, the array given to the previous update or to creation) -> (h, w) abi.MOTION_DTYPE records
     (p_prev, known).  `ids` and `guides` are render_guides_ids' of the current geometry.  ctx None = the host instance.
     With `prev_spheres` — the scene's spheres as they were before the last Scene.edit: a list of SceneData spheres or
     (n_spheres,) abi.SPHERE_DTYPE records — yk_surface_motion_spheres: a moved sphere carries its points along;
-    `prev_points` may then be None for a scene without triangles."""
+    `prev_points` may then be None for a scene without triangles.
+    With `prev_transforms` instead of prev_points — what the previous Scene.transform got (the same forms), or None: the
+    scene stood at rest — yk_surface_motion_transforms: the previous vertices are made of the scene's rest pose and the
+    previous matrices, 128 bytes a mesh kept instead of 12 bytes a vertex."""
     guides = np.ascontiguousarray(guides, dtype=abi.GUIDE_DTYPE)
     if guides.ndim != 2:
         raise ValueError("guides is (h, w)")
     h, w = guides.shape
     ids = _records(ids, abi.SURFACE_ID_DTYPE, (w, h), "surface id")
+    if prev_transforms is not _AT_REST:
+        if prev_points is not None:
+            raise ValueError("prev_points and prev_transforms are two ways to say where the vertices stood: give one")
+        return _motion_transforms(scene, ids, guides, prev_transforms, prev_spheres, w, h, ctx.h if ctx else None)
     if prev_points is not None or prev_spheres is None:
         prev_points = _prev_points(scene, prev_points)
     out = np.zeros((h, w), dtype=abi.MOTION_DTYPE)
@@ -1341,12 +1374,21 @@ class Context:
         three, no two buffers may overlap.  No read-back: ordered on `stream` like the other guide calls."""
         check(lib().yk_render_guides_through_device(self.h, scene.h, C.byref(camera.matrices), int(res[0]), int(res[1]), int(max_through), _vp(d_guides_ptr), _vp(d_ids_ptr), _vp(d_through_ptr), _vp(stream)), self.h)
 
-    def surface_motion_device(self, scene, d_ids_ptr, d_guides_ptr, d_prev_points_ptr, res, d_out_ptr, stream=None, d_prev_spheres_ptr=None):
+    def surface_motion_device(self, scene, d_ids_ptr, d_guides_ptr, d_prev_points_ptr, res, d_out_ptr, stream=None, d_prev_spheres_ptr=None, d_prev_transforms_ptr=_AT_REST):
         """yk_surface_motion_device: device ids and guides of the current geometry and the PREVIOUS vertex array on the device
         (3 floats for each of the scene's vertices: the caller answers for its length) -> res[0] * res[1] device yk_motion
         records, enqueued on `stream` (default: the context's) without waiting; one launch, no allocation.  With
         d_prev_spheres_ptr (the scene's n_spheres yk_sphere_desc records from before the last edit, on the device)
-        yk_surface_motion_spheres_device: spheres that moved carry their points along."""
+        yk_surface_motion_spheres_device: spheres that moved carry their points along.  With d_prev_transforms_ptr (the
+        scene's n_meshes yk_mesh_transform records of the previous Scene.transform on the device, 4-byte aligned; None or 0:
+        the scene stood at rest) and d_prev_points_ptr None, yk_surface_motion_transforms_device: the previous vertices
+        are made of the scene's rest pose."""
+        if d_prev_transforms_ptr is not _AT_REST:
+            if d_prev_points_ptr:
+                raise ValueError("d_prev_points_ptr and d_prev_transforms_ptr are two ways to say where the vertices stood: give one")
+            check(lib().yk_surface_motion_transforms_device(self.h, scene.h, _vp(d_ids_ptr), _vp(d_guides_ptr), _vp(d_prev_transforms_ptr), _vp(d_prev_spheres_ptr), int(res[0]), int(res[1]),
+                                                            _vp(d_out_ptr), _vp(stream)), self.h)
+            return
         if d_prev_spheres_ptr:
             check(lib().yk_surface_motion_spheres_device(self.h, scene.h, _vp(d_ids_ptr), _vp(d_guides_ptr), _vp(d_prev_points_ptr), _vp(d_prev_spheres_ptr), int(res[0]), int(res[1]), _vp(d_out_ptr),
                                                          _vp(stream)), self.h)
@@ -1698,6 +1740,40 @@ class Scene:
         (abi.LAYOUT_REASON_*), what it rewrote (abi.EDIT_* bits) and its phase seconds."""
         i = abi.SceneEditInfo()
         check(lib().yk_scene_get_edit_info(self.h, C.byref(i)))
+        return i
+
+    def transform(self, transforms, stream=None):
+        """yk_scene_transform / yk_scene_transform_device: every mesh of the scene is placed by a matrix, relative to its
+        rest pose (the points and normals after creation or the last update); absolute, not cumulative.  Host input —
+        an (n_meshes, 4, 4) array, a list of n_meshes matrices with None for the identity (both through
+        abi.pack_mesh_transforms, which inverts in float64), or (n_meshes,) abi.MESH_TRANSFORM_DTYPE records whose pairs
+        are the caller's — goes to yk_scene_transform, which follows the scene's layout.  A torch tensor on the context's
+        device, or a raw device address (int), holding the packed records (uint8 with 128 * n_meshes elements, or int32 /
+        float32 with a quarter of them) goes to yk_scene_transform_device, which takes the device route — `stream` and
+        the argument checks (ValueError) as in Scene.update.  `self.data` keeps describing the rest pose."""
+        n_meshes = len(self.data.meshes)
+        if hasattr(transforms, "data_ptr") or isinstance(transforms, (int, np.integer)):
+            if self.ctx is None:
+                raise ValueError("a host-only scene is transformed with host records")
+            n_bytes = n_meshes * abi.MESH_TRANSFORM_DTYPE.itemsize
+            per = transforms.element_size() if hasattr(transforms, "element_size") else 1
+            address, stream = _device_addresses({"transforms": transforms}, {"transforms": (("uint8",) if per == 1 else ("int32", "float32"), n_bytes // per)}, self.ctx, stream)
+            check(lib().yk_scene_transform_device(self.ctx.h, self.h, _vp(address["transforms"]), _vp(stream)), self.ctx.h)
+            return
+        if transforms is not None:
+            if not (isinstance(transforms, np.ndarray) and transforms.dtype == abi.MESH_TRANSFORM_DTYPE):
+                transforms = abi.pack_mesh_transforms(transforms)
+            if transforms.shape != (n_meshes,):
+                raise ValueError(f"transforms: {transforms.shape} records, the scene has {n_meshes} meshes")
+            transforms = np.ascontiguousarray(transforms)
+        ctx_h = self.ctx.h if self.ctx else None
+        check(lib().yk_scene_transform(ctx_h, self.h, _p(transforms)), ctx_h)
+
+    def transform_info(self):
+        """yk_scene_get_transform_info: how many transforms ran, the last one's route and reason, its moved and flipped
+        meshes, the bytes kept of the rest pose, tree_cost and tree_cost_rest, and the phase seconds."""
+        i = abi.SceneTransformInfo()
+        check(lib().yk_scene_get_transform_info(self.h, C.byref(i)))
         return i
 
     def device_records(self, which):

@@ -255,6 +255,20 @@ struct yk_scene {
         std::vector<float4> texels;
         std::vector<uint4> tex_info;
     } host;
+    // What yk_scene_transform keeps between calls (yk_scene_transform.h): the rest pose, snapshotted by the first transform after
+    // creation or an update, and the table vertex -> mesh.  A scene in device memory keeps them there (rest_points, rest_normals,
+    // vertex_mesh: two words a vertex; mesh_words: per mesh its lit bit, then its kind of the call in progress), a host-only
+    // scene in the vectors.  It stands after every older member: their offsets, and with them the objects of the files that
+    // do not know this call, stay what they were.
+    struct TransformState {
+        bool active = false;   // the rest copy is valid
+        bool shared = false;   // a vertex is indexed by triangles of two meshes: every transform is refused
+        DevBuf rest_points, rest_normals, vertex_mesh, mesh_words, cost_words;
+        std::vector<float> h_rest_points;                  // a host-only scene (it keeps no normals)
+        std::vector<uint32_t> h_vertex_mesh, h_mesh_lit;
+        std::vector<uint32_t> flags_created;  // YK_MESH_* per mesh as creation made them (the rest pose on the host)
+        yk_scene_transform_info info = {};
+    } xf;
 };
 
 // The device scene a job of `n` rays traverses: with both node layouts present the 4-wide one
@@ -395,6 +409,21 @@ struct StagedSpheres {
 };
 uint32_t stage_spheres_device(yk_context* ctx, yk_scene* s, const void* d_in, DevScratch& tmp, StagedSpheres* staged, uint32_t* flag);
 uint32_t commit_spheres_device(yk_context* ctx, yk_scene* s, const StagedSpheres& staged, std::vector<int32_t>* material);
+
+// ------------------------------------------------------------------ yk_scene_transform.hip
+// The steps of yk_scene_transform on a scene in device memory (the rule: yk_scene_transform.h), each YK_LAYOUT_REASON_*:
+// snapshot: the rest copy and the table vertex -> mesh where the scene has none yet (s->xf; rest_bytes go into device_bytes),
+//   with tree_cost_rest from the tree in HBM (`tree_on_device`) or from the host tree;
+// stage: the per-mesh kinds and the check pass over d_transforms (n_meshes records in HBM): *flag gets the XF_BAD_* bits,
+//   counts[0 .. 1] the moved and flipped meshes; nothing of the scene is written;
+// commit: the write pass: points, normals, mesh flags;
+// tree_cost_device: the cost of the tree in s->tree_nodes.
+uint32_t snapshot_rest_device(yk_context* ctx, yk_scene* s, bool tree_on_device);
+uint32_t stage_transforms_device(yk_context* ctx, yk_scene* s, const void* d_transforms, uint32_t* flag, uint32_t* counts);
+uint32_t commit_transforms_device(yk_context* ctx, yk_scene* s, const void* d_transforms);
+uint32_t tree_cost_device(yk_context* ctx, yk_scene* s, double* cost);
+// the rest copy goes, the mesh flags are creation's again (yk_scene_update*); the scene's device is current
+yk_status drop_rest(yk_context* ctx, yk_scene* s);
 
 // ------------------------------------------------------------------ yk_scene_input.hip
 // The input stage of yk_scene_create_device (yk_scene_input.h); both enqueue on `st` and return the launch status.

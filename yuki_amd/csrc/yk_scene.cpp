@@ -581,6 +581,8 @@ yk_status yk_upload_scene_image(yk_context* ctx, const std::shared_ptr<SceneImag
         h.tri_mesh.assign(d->n_triangles, 0);
         if (d->tri_mesh) std::memcpy(h.tri_mesh.data(), d->tri_mesh, sizeof(uint32_t) * d->n_triangles);
         if (d->n_triangles) h.tri_material.assign(d->tri_material, d->tri_material + d->n_triangles);
+        h.tri_area_light.assign(d->n_triangles, -1);  // what yk_scene_transform tests: a mesh that carries an area light does not move
+        if (d->tri_area_light) std::memcpy(h.tri_area_light.data(), d->tri_area_light, sizeof(int32_t) * d->n_triangles);
         if (d->uvs) h.uvs.assign(d->uvs, d->uvs + 2 * (size_t)d->n_vertices);
         if (d->n_triangles) h.indices.assign(d->indices, d->indices + 3 * (size_t)d->n_triangles);
         if (d->n_triangles) h.points.assign(d->points, d->points + 3 * (size_t)d->n_vertices);
@@ -892,11 +894,18 @@ yk_status yk_scene_get_edit_info(const yk_scene* s, yk_scene_edit_info* out) {
     return YK_OK;
 }
 
+yk_status yk_scene_get_transform_info(const yk_scene* s, yk_scene_transform_info* out) {
+    if (!s || !out) return YK_ERR_INVALID_ARGUMENT;
+    *out = s->xf.info;
+    return YK_OK;
+}
+
 void yk_scene_destroy(yk_scene* s) {
     if (!s) return;
     if (s->device >= 0) (void)hipSetDevice(s->device);
     for (DevBuf* b : scene_buffers(s)) b->release();
     for (DevBuf* b : {&s->upd.depth, &s->upd.list, &s->upd.sphere_b, &s->upd.mat_kind_d, &s->upd.words}) b->release();
+    for (DevBuf* b : {&s->xf.rest_points, &s->xf.rest_normals, &s->xf.vertex_mesh, &s->xf.mesh_words, &s->xf.cost_words}) b->release();
     delete s;
 }
 

@@ -1,6 +1,7 @@
 // yk_scene_change.cpp — a live scene changed in place ("One plan, one prelude, named phases"): the entry points
-// yk_scene_update[_device] and yk_scene_apply_edit[_device], their prelude and the phases (Change) that run a ChangePlan
-// (yk_scene_change.h) and the host route.  The device route's steps are yk_scene_update.hip's and yk_scene_edit.hip's.
+// yk_scene_update[_device], yk_scene_apply_edit[_device] and yk_scene_transform[_device], their prelude and the phases (Change)
+// that run a ChangePlan (yk_scene_change.h) and the host route.  The device route's steps are yk_scene_update.hip's,
+// yk_scene_edit.hip's and yk_scene_transform.hip's.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -10,6 +11,7 @@
 
 #include "yk_internal.h"
 #include "yk_scene_change.h"
+#include "yk_scene_transform.h"
 #include "yk_scene_update.h"
 
 using namespace yk_change;
@@ -98,7 +100,12 @@ struct Change {
     std::vector<uint8_t> mat_kind;
     DevScratch tmp;  // uploads for staging, and what the stage wrote
     StagedSpheres staged;
-    double check = 0.0, tables = 0.0, boxes = 0.0, records = 0.0;  // the phases' seconds: both info structs are filled from these
+    Brought<yk_mesh_transform> xf;                    // ... or a transform's records
+    std::vector<float> xf_points, xf_normals;         // what the host route made of the rest pose (points.h, normals.h)
+    std::vector<uint32_t> xf_flags;                   // ... and the mesh flags that go with them
+    uint32_t n_moved = 0, n_flipped = 0;
+    double tree_cost = 0.0;
+    double check = 0.0, tables = 0.0, boxes = 0.0, records = 0.0;  // the phases' seconds: the info structs are filled from these
     explicit Change(yk_context* c) : ctx(c) {
         if (ctx) lock = std::unique_lock<std::recursive_mutex>(ctx->mu);
         t_begin = now_seconds();
@@ -130,15 +137,173 @@ struct Change {
 
     yk_status run() {
         plan = plan_change(facts);
-        yk_status rc = check_and_stage();
-        if (rc == YK_OK && (rc = write_tables()) == YK_OK && (rc = boxes_and_records()) == YK_OK) publish();
+        yk_status rc = plan.transform ? check_and_stage_transform() : check_and_stage();
+        if (rc == YK_OK && (rc = write_tables()) == YK_OK && (rc = boxes_and_records()) == YK_OK && (rc = cost_of_tree()) == YK_OK) publish();
         return rc;
+    }
+
+    // The rest pose on the host for the host route of a transform: snapshotted now where the scene has none (a host-only scene keeps
+    // no normals and has no records that read them), fetched where a device-route call left it in HBM.
+    struct RestOnHost {
+        const float *points = nullptr, *normals = nullptr;
+        const uint32_t *vertex_mesh = nullptr, *mesh_lit = nullptr, *flags_created = nullptr;
+        std::vector<float> f_points, f_normals;
+        std::vector<uint32_t> f_vertex_mesh, f_words;
+    };
+    yk_status rest_on_host(RestOnHost& r) {
+        yk_scene::TransformState& x = s->xf;
+        const size_t nv = s->upd.n_vertices, nt = s->n_triangles, run = std::max<uint32_t>(s->n_meshes, 1u);
+        const bool normals_kept = ctx && s->upd.has_normals;
+        if (ctx && !x.active) {  // a scene in device memory keeps its rest pose there whatever the route: the motion pass reads it
+            const uint32_t why = snapshot_rest_device(ctx, s, false);
+            if (why != YK_LAYOUT_REASON_NONE)
+                return fail(ctx, why == YK_LAYOUT_REASON_OUT_OF_MEMORY ? YK_ERR_OUT_OF_MEMORY : YK_ERR_DEVICE, "transforms: the rest pose could not be kept in device memory");
+        }
+        if (!x.active) {  // a host-only scene: in its own vectors
+            HostArrays have;
+            yk_status rc = scene_host_arrays(ctx, s, HOST_INDICES | HOST_POINTS | HOST_TRI_MESH | HOST_TRI_AREA_LIGHT | HOST_MESH_FLAGS, "", have);
+            if (rc != YK_OK) return rc;
+            const HostBvh* bvh = scene_host_tree(s);
+            if (!bvh) return fail(ctx, YK_ERR_DEVICE, "the scene's tree could not be copied back from the device");
+            if (have->tri_mesh.size() != nt || have->tri_area_light.size() != nt || have->mesh_flags.size() < run) return fail(ctx, YK_ERR_DEVICE, "the scene's mesh tables do not fit its triangles");
+            x.h_rest_points.assign(have->points.begin(), have->points.end());
+            x.h_rest_points.resize(3 * nv);
+            x.flags_created.assign(have->mesh_flags.begin(), have->mesh_flags.begin() + run);
+            x.h_vertex_mesh.assign(2 * nv, 0u);
+            for (size_t v = 0; v < nv; ++v) x.h_vertex_mesh[2 * v] = xfm::XF_NO_MESH;
+            x.h_mesh_lit.assign(run, 0u);
+            x.shared = false;
+            for (size_t t = 0; t < nt; ++t) {
+                const uint32_t mesh = have->tri_mesh[t];
+                for (int k = 0; k < 3; ++k)
+                    if (have->indices[3 * t + k] < nv) xfm::table_add(x.h_vertex_mesh.data(), have->indices[3 * t + k], mesh);
+                if (have->tri_area_light[t] >= 0 && mesh < s->n_meshes) x.h_mesh_lit[mesh] = 1u;
+            }
+            for (size_t v = 0; v < nv; ++v) x.shared = x.shared || xfm::vertex_shared(x.h_vertex_mesh[2 * v], x.h_vertex_mesh[2 * v + 1]);
+            x.info.tree_cost_rest = xfm::tree_cost(reinterpret_cast<const uint32_t*>(bvh->nodes.data()), bvh->nodes.size());
+            x.info.rest_bytes = 4 * (x.h_rest_points.size() + x.h_vertex_mesh.size() + x.h_mesh_lit.size() + x.flags_created.size());
+            x.active = true;
+        }
+        if (!x.rest_points.p) {
+            r.points = x.h_rest_points.data();
+            r.vertex_mesh = x.h_vertex_mesh.data();
+            r.mesh_lit = x.h_mesh_lit.data();
+            r.flags_created = x.flags_created.data();
+            return YK_OK;
+        }
+        r.f_points.resize(3 * nv);  // a scene in device memory: it comes down for the call (yk_scene_transform.hip: mesh_words holds lit, kinds, created)
+        r.f_vertex_mesh.resize(2 * nv);
+        r.f_words.resize(3 * run);
+        if (nv) HIP_TRY(ctx, hipMemcpy(r.f_points.data(), x.rest_points.p, 12 * nv, hipMemcpyDeviceToHost));
+        if (nv) HIP_TRY(ctx, hipMemcpy(r.f_vertex_mesh.data(), x.vertex_mesh.p, 8 * nv, hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(r.f_words.data(), x.mesh_words.p, 12 * run, hipMemcpyDeviceToHost));
+        if (normals_kept) {
+            r.f_normals.resize(3 * nv);
+            if (nv) HIP_TRY(ctx, hipMemcpy(r.f_normals.data(), x.rest_normals.p, 12 * nv, hipMemcpyDeviceToHost));
+            r.normals = r.f_normals.data();
+        }
+        r.points = r.f_points.data();
+        r.vertex_mesh = r.f_vertex_mesh.data();
+        r.mesh_lit = r.f_words.data();
+        r.flags_created = r.f_words.data() + 2 * run;
+        return YK_OK;
+    }
+
+    // The host instance of the rule (yk_scene_transform.h): the checks, then the points, normals and mesh flags rewrite_scene_host takes.
+    yk_status transform_on_host() {
+        RestOnHost r;
+        yk_status rc = rest_on_host(r);
+        if (rc != YK_OK) return rc;
+        const uint32_t nm = s->n_meshes, run = std::max<uint32_t>(nm, 1u);
+        const size_t nv = s->upd.n_vertices;
+        const float* records = reinterpret_cast<const float*>(xf.h);
+        std::vector<uint32_t> kinds(run, 0u);
+        uint32_t flag = s->xf.shared ? (uint32_t)xfm::XF_BAD_SHARED : 0u;
+        n_moved = n_flipped = 0;
+        for (uint32_t m = 0; m < nm; ++m) {
+            uint32_t bad;
+            kinds[m] = xfm::mesh_kind(records + xfm::XF_RECORD_FLOATS * (size_t)m, r.mesh_lit[m] != 0u, &bad);
+            flag |= bad;
+            n_moved += (kinds[m] & xfm::XF_MOVED) ? 1u : 0u;
+            n_flipped += (kinds[m] & xfm::XF_FLIPS) ? 1u : 0u;
+        }
+        xf_points.resize(3 * nv);
+        for (size_t v = 0; v < nv; ++v) {
+            const uint32_t mesh = r.vertex_mesh[2 * v];
+            const V3 p = xfm::vertex_point(records, kinds.data(), nm, mesh, V3{r.points[3 * v], r.points[3 * v + 1], r.points[3 * v + 2]});
+            if (xfm::vertex_moves(kinds.data(), nm, mesh) && xfm::point_not_finite(p)) flag |= xfm::XF_BAD_POINT;
+            std::memcpy(&xf_points[3 * v], &p, 12);
+        }
+        if (flag) return fail(ctx, YK_ERR_INVALID_ARGUMENT, xfm::refusal(flag));
+        if (r.normals) {
+            xf_normals.resize(3 * nv);
+            for (size_t v = 0; v < nv; ++v) {
+                const V3 n = xfm::vertex_normal(records, kinds.data(), nm, r.vertex_mesh[2 * v], V3{r.normals[3 * v], r.normals[3 * v + 1], r.normals[3 * v + 2]});
+                std::memcpy(&xf_normals[3 * v], &n, 12);
+            }
+        }
+        xf_flags.assign(r.flags_created, r.flags_created + run);
+        for (uint32_t m = 0; m < nm; ++m) xf_flags[m] = xfm::mesh_flags_of(xf_flags[m], kinds[m]);
+        points.h = xf_points.data();
+        normals.h = r.normals ? xf_normals.data() : nullptr;
+        return YK_OK;
+    }
+
+    // check_and_stage of a transform: the plan, the rest pose, the records in HBM, the per-mesh kinds and the check pass with their flag word.
+    yk_status check_and_stage_transform() {
+        if (plan.refused) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "scene change: arguments no entry point accepts");
+        const double t0 = now_seconds();
+        yk_status rc = YK_OK;
+        bool on_host = false;  // fall_back ran: the host instance has checked and computed
+        const auto device_step = [&](uint32_t r) {
+            if ((reason = r) == YK_LAYOUT_REASON_NONE) return true;
+            on_host = true;
+            rc = fall_back();
+            return false;
+        };
+        const auto records_up = [&] {  // a host table on a device-laid scene goes up
+            const hipError_t e = xf.to_device(tmp, s->n_meshes);
+            return e == hipSuccess ? (uint32_t)YK_LAYOUT_REASON_NONE : layout_reason_of(e);
+        };
+        if (plan.device_route && device_step(plan_scene_update(ctx, s)) && device_step(snapshot_rest_device(ctx, s, true)) && (!plan.upload || device_step(records_up()))) {
+            uint32_t flag = 0, counts[2] = {0u, 0u};
+            if (device_step(stage_transforms_device(ctx, s, xf.d, &flag, counts))) {
+                if (flag) return fail(ctx, YK_ERR_INVALID_ARGUMENT, xfm::refusal(flag));
+                n_moved = counts[0];
+                n_flipped = counts[1];
+            }
+        }
+        if (!plan.device_route && !on_host) rc = transform_on_host();
+        check = now_seconds() - t0;
+        return rc;
+    }
+
+    // The tree's cost after the refit of a transform (yk_scene_transform.h): where the tree was refitted.
+    yk_status cost_of_tree() {
+        if (!plan.transform) return YK_OK;
+        if (plan.device_route) {  // the refitted tree is in HBM and the host copy is stale until publish() says so: never read that one
+            if (tree_cost_device(ctx, s, &tree_cost) == YK_LAYOUT_REASON_NONE) return YK_OK;
+            (void)hipGetLastError();  // the reduction failed: the same nodes come down and the host sums them
+            std::vector<uint32_t> nodes(8 * (size_t)s->info.n_nodes);
+            if (!s->tree_nodes.p || s->tree_nodes.bytes < nodes.size() * 4) return fail(ctx, YK_ERR_DEVICE, "transforms: the refitted tree is not in device memory");
+            HIP_TRY(ctx, hipMemcpy(nodes.data(), s->tree_nodes.p, nodes.size() * 4, hipMemcpyDeviceToHost));
+            tree_cost = xfm::tree_cost(nodes.data(), (size_t)s->info.n_nodes);
+            return YK_OK;
+        }
+        const HostBvh* bvh = scene_host_tree(s);
+        if (!bvh) return fail(ctx, YK_ERR_DEVICE, "the scene's tree could not be copied back from the device");
+        tree_cost = xfm::tree_cost(reinterpret_cast<const uint32_t*>(bvh->nodes.data()), bvh->nodes.size());
+        return YK_OK;
     }
 
     // A device step failed with `reason`: the host route does the rest.  Arrays that were in device memory only come down, once, and get the host's checks.
     yk_status fall_back() {
         (void)hipGetLastError();
         plan = after_device_failure(plan);
+        if (plan.transform) {
+            HIP_TRY(ctx, xf.to_host(s->n_meshes));
+            return transform_on_host();
+        }
         const size_t n = 3 * (size_t)s->upd.n_vertices;
         const bool new_points = plan.points && !points.h, new_spheres = plan.spheres && !spheres.h;
         HIP_TRY(ctx, points.to_host(n));
@@ -206,7 +371,14 @@ struct Change {
             s->upd.mat_kind = mat_kind;
         }
         std::vector<int32_t> sphere_material(ns);
-        if (plan.points && plan.stage) {
+        if (plan.points && !plan.transform && (rc = drop_rest(ctx, s)) != YK_OK) return rc;  // an update makes a new rest pose: the flags are creation's again
+        if (plan.transform) {
+            if (plan.stage && (reason = commit_transforms_device(ctx, s, xf.d)) != YK_LAYOUT_REASON_NONE && (rc = fall_back()) != YK_OK) return rc;
+            if (!plan.stage) {  // the host route (also the one just fallen back to): the flags its records are laid out with
+                if (ctx && (rc = upload(ctx, s->mesh_flags, xf_flags.data(), xf_flags.size())) != YK_OK) return rc;
+                if (!ctx) s->host.mesh_flags = xf_flags;
+            }
+        } else if (plan.points && plan.stage) {
             if ((reason = commit_points_device(ctx, s, points.d, normals.d)) != YK_LAYOUT_REASON_NONE && (rc = fall_back()) != YK_OK) return rc;
         } else if (plan.spheres && plan.stage) {
             if ((reason = commit_spheres_device(ctx, s, staged, &sphere_material)) != YK_LAYOUT_REASON_NONE) return fail(ctx, YK_ERR_DEVICE, "the staged sphere table could not be copied into the scene");
@@ -313,7 +485,10 @@ struct Change {
         if (ctx && plan.records) bind_records(s);
         const uint32_t route = plan.device_route ? YK_UPDATE_ROUTE_DEVICE : YK_UPDATE_ROUTE_HOST, said = reported_reason(facts, reason);
         const double total = now_seconds() - t_begin;
-        if (plan.points)  // seconds_check: the finite test, with the copy of the arrays into the scene; n_levels and plan_bytes are the plan's
+        if (plan.transform) {
+            yk_scene_transform_info& i = s->xf.info;  // rest_bytes and tree_cost_rest are the snapshot's
+            i = yk_scene_transform_info{i.n_transforms + 1u, route, said, n_moved, n_flipped, 0u, i.rest_bytes, tree_cost, i.tree_cost_rest, check, tables, boxes, records, total};
+        } else if (plan.points)  // seconds_check: the finite test, with the copy of the arrays into the scene; n_levels and plan_bytes are the plan's
             u.info = yk_scene_update_info{u.info.n_updates + 1u, route, said, u.info.n_levels, u.info.plan_bytes, check + tables, boxes, records, total};
         else
             u.edit_info = yk_scene_edit_info{u.edit_info.n_edits + 1u, route, said, plan.rewrote, check, tables, boxes, records, total};
@@ -337,6 +512,22 @@ yk_status update_scene(yk_context* ctx, yk_scene* s, const float* points, const 
     (on_device ? c.normals.d : c.normals.h) = normals;
     (on_device ? c.facts.points_device : c.facts.points_host) = true;
     c.facts.normals = normals != nullptr;
+    return c.run();
+}
+
+yk_status transform_scene(yk_context* ctx, yk_scene* s, const void* transforms, bool on_device, void* stream) {
+    Change c(ctx);
+    if (!s) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null scene");
+    if (!transforms) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "null transforms");
+    yk_status rc = c.scene(s);
+    if (rc != YK_OK) return rc;
+    if (on_device && s->n_meshes) {  // the pointer checks of yk_scene_create_device, with its messages
+        if ((rc = check_device_arrays(ctx, {{"transforms", transforms, sizeof(yk_mesh_transform) * (size_t)s->n_meshes}})) != YK_OK) return rc;
+        if (reinterpret_cast<uintptr_t>(transforms) & 3u) return fail(ctx, YK_ERR_INVALID_ARGUMENT, "transforms must be 4-byte aligned");
+    }
+    if ((rc = c.wait(stream)) != YK_OK) return rc;
+    (on_device ? c.xf.d : c.xf.h) = static_cast<const yk_mesh_transform*>(transforms);
+    (on_device ? c.facts.transforms_device : c.facts.transforms_host) = true;
     return c.run();
 }
 
@@ -378,6 +569,14 @@ yk_status yk_scene_update(yk_context* ctx, yk_scene* s, const float* points, con
 
 yk_status yk_scene_update_device(yk_context* ctx, yk_scene* s, const float* d_points, const float* d_normals, void* stream) try {
     return ctx ? update_scene(ctx, s, d_points, d_normals, true, stream) : YK_ERR_INVALID_ARGUMENT;
+} YK_CATCH(ctx)
+
+yk_status yk_scene_transform(yk_context* ctx, yk_scene* s, const yk_mesh_transform* transforms) try {
+    return transform_scene(ctx, s, transforms, false, nullptr);
+} YK_CATCH(ctx)
+
+yk_status yk_scene_transform_device(yk_context* ctx, yk_scene* s, const void* d_transforms, void* stream) try {
+    return ctx ? transform_scene(ctx, s, d_transforms, true, stream) : YK_ERR_INVALID_ARGUMENT;
 } YK_CATCH(ctx)
 
 yk_status yk_scene_apply_edit(yk_context* ctx, yk_scene* s, const yk_scene_edit* edit) try {

@@ -1,7 +1,8 @@
-// yk_scene_change.h — what yk_scene_update[_device] and yk_scene_apply_edit[_device] decide before they write anything, as
-// pure functions over plain values.  The specification is the comment of yk_scene_apply_edit in include/yuki_hip.h ("What is
-// rewritten follows from what changed"); yk_scene_change.cpp runs the plan.  No HIP here: tests/cpp/scene_change_plan_test.cpp
-// compiles this header alone.  Library-private.
+// yk_scene_change.h — what yk_scene_update[_device], yk_scene_apply_edit[_device] and yk_scene_transform[_device] decide before
+// they write anything, as pure functions over plain values.  The specification is the comment of yk_scene_apply_edit in
+// include/yuki_hip.h ("What is rewritten follows from what changed"), and for a transform that of yk_scene_transform;
+// yk_scene_change.cpp runs the plan.  No HIP here: tests/cpp/scene_change_plan_test.cpp and scene_transform_plan_test.cpp
+// compile this header alone.  Library-private.
 #pragma once
 #include <cstdint>
 
@@ -16,6 +17,7 @@ struct ChangeFacts {
     bool points_host = false, points_device = false, normals = false;  // what the call brings: an update ...
     bool spheres_host = false, spheres_device = false, lights = false, materials = false, background = false;  // ... or an edit
     bool kinds_changed = false;  // the new material table's device BSDF kinds differ from the scene's
+    bool transforms_host = false, transforms_device = false;  // ... or a transform: one matrix pair a mesh (yk_scene_transform[_device])
 };
 
 struct ChangePlan {
@@ -27,19 +29,23 @@ struct ChangePlan {
     bool kind_tables = false;   // the scene's tables of its shapes' BSDF kinds are refreshed
     bool boxes = false, records = false;  // the tree is refitted; the seven record buffers are rewritten
     uint32_t rewrote = 0;       // YK_EDIT_* for the edit info
+    bool transform = false;     // the points (and normals) are made of the rest pose by the call's matrices: it plans like an update of points ...
+    bool mesh_flags = false;    // ... plus the table of mesh flags, which a mirroring matrix flips
 };
 
 // the scene's layout decides, and arrays that are in device memory already stay there
-inline bool asks_device_route(const ChangeFacts& f) { return f.has_context && (f.device_laid || f.points_device || (f.spheres_device && f.n_spheres != 0)); }
+inline bool asks_device_route(const ChangeFacts& f) { return f.has_context && (f.device_laid || f.points_device || f.transforms_device || (f.spheres_device && f.n_spheres != 0)); }
 
 inline ChangePlan plan_change(const ChangeFacts& f) {
     ChangePlan p;
     const bool update = f.points_host || f.points_device;
     const bool edit = f.spheres_host || f.spheres_device || f.lights || f.materials || f.background || f.kinds_changed;
-    p.refused = ((f.points_device || f.spheres_device || f.device_laid) && !f.has_context) || (f.points_host && f.points_device) || (f.spheres_host && f.spheres_device) || (update && edit) ||
-                (f.normals && !update) || (f.kinds_changed && !f.materials);
+    const bool transform = f.transforms_host || f.transforms_device;  // alone in its call: with an update or an edit it is refused
+    p.refused = ((f.points_device || f.spheres_device || f.transforms_device || f.device_laid) && !f.has_context) || (f.points_host && f.points_device) || (f.spheres_host && f.spheres_device) ||
+                (f.transforms_host && f.transforms_device) || (update && edit) || (transform && (update || edit)) || (f.normals && !update) || (f.kinds_changed && !f.materials);
     if (p.refused) return p;
-    p.points = update;
+    p.points = update || transform;
+    p.transform = p.mesh_flags = transform;
     p.spheres = (f.spheres_host || f.spheres_device) && f.n_spheres != 0;
     p.lights = f.lights && f.n_lights != 0;
     p.materials = f.materials && f.n_materials != 0;
@@ -51,7 +57,7 @@ inline ChangePlan plan_change(const ChangeFacts& f) {
     p.device_route = asks_device_route(f);
     p.device_plan = p.device_route && p.records;
     p.stage = p.device_route && p.boxes;
-    p.upload = p.stage && (f.points_host || f.spheres_host);
+    p.upload = p.stage && (f.points_host || f.spheres_host || f.transforms_host);
     p.rewrote = (p.lights ? YK_EDIT_LIGHTS : 0u) | (p.materials ? YK_EDIT_MATERIALS : 0u) | (p.spheres ? YK_EDIT_SPHERES : 0u) | (p.boxes ? YK_EDIT_BOXES : 0u) |
                 (p.records ? YK_EDIT_RECORDS : 0u) | (p.background ? YK_EDIT_BACKGROUND : 0u);
     return p;
